@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- face-ID rasterization throughput on BASELINE.json config 2 (1.2 M-face mesh, 4000x3000 views).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment makes this process a LAUNCHER: it starts N fresh ranks
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, one rank per GPU over
@@ -11,12 +11,15 @@ is a rank.  A line that claims N GPUs is only printed when N ranks answered (exi
 One "step" = one pass of the hot path (pix2face: cull -> set-up/bin -> tile raster) over this rank's batch of 50
 synthetic views, inputs (mesh, camera records) resident in HBM, ids written to HBM.  Weak scaling: every rank rasterizes
 its own 50 views of the same replicated mesh, no data-path collective (pix2face has no exchange step).  After W
-warm-up steps, windows of EXACTLY K steps each are timed -- at least --windows of them, and as many more as it takes to
-put --min-timed-s (1 s) of GPU time inside timed regions --, every window bracketed by barrier + synchronize on both
-sides and reduced with MAX over ranks; `value` / `ms_per_step` are the median window, the spread is reported beside it.
-The per-kernel HIP-event durations of the roofline objects are collected over the timed windows themselves.
+warm-up steps, EXACTLY K steps are timed in one window, bracketed by barrier + synchronize on both sides and reduced
+with MAX over ranks; `value` and `ms_per_step` come from that window.  `--dump-outputs DIR` then writes what the last
+timed step computed (a fixed, seeded sample of its face ids, see dump_outputs) as .npy files.  A plain run stops there
+and prints the headline line.
 
-Outside the headline region the same run times
+`--full` adds everything else, after the headline window and without changing it.  First, windows of K steps with the
+library's HIP events on -- at least --windows of them, and as many more as it takes to put --min-timed-s (1 s) of GPU
+time inside them --, reduced the same way and reported as `ms_per_step_windows`; the per-kernel HIP-event durations of
+the roofline objects are collected over those windows.  Then the same run times
   (a) "aggregate": BASELINE config 3 -- the 500-view grid with 4-class labels through the fused raster + last-writer-wins
       projection + per-face votes (one RCCL all-reduce of the votes at N > 1), checked against the CPU oracle on one view;
   (b) "c4": BASELINE config 4's per-GPU shard (250 views of the 2000-view set, view i -> GPU i mod N) with the single
@@ -26,7 +29,7 @@ Outside the headline region the same run times
   (d) at N == 1, "workload_2": a hostile scene (terrain + 20 000 trees, cameras tilted 30-45 degrees) at full and at quarter
       resolution, with sampled oracle parity, and "api": the PCIe-inclusive rates of the reference-shaped numpy API;
   (e) at N == 1, the CPU oracle on a bounded sample ("cpu_baseline", one thread and all cores).
-Rank 0 prints ONE JSON line.
+The --no-<leg> flags drop single legs of a --full run.  Rank 0 prints ONE JSON line.
 
 `run(args, rig)` takes the platform glue as an object: the default `GpuRig` is the MI355X box (RCCL, HipRaster, the
 BASELINE sizes); tests/test_bench_distributed.py drives the same control flow -- every collective, every MAX reduction,
@@ -51,6 +54,7 @@ HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 N_SIMD = 1024           # 256 CUs x 4 SIMDs
 SHADER_GHZ = 2.4        # nominal shader clock the VALU-issue fraction is priced at
 XGMI_LINK_GBS = 153.0   # one xGMI link, per direction; 7 links per GPU
+PRECONDITION_STEPS = 12  # untimed steps per pre-conditioning round, before the --warmup ones (see run)
 
 
 @dataclass
@@ -76,6 +80,7 @@ class Workload:
     c5_classes: int = 10
     c5_raster_views: int = 20    # ids-only sample of the shard (96 MB of ids per view)
     min_leg_s: float = 0.3       # every side leg is timed until this much GPU time lies inside its timed regions
+    precondition_s: float = 0.25  # untimed pre-conditioning before the warm-up steps
 
     def cam_kw(self):
         return dict(f=self.f, width=self.W, height=self.H)
@@ -142,9 +147,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=5, help="least number of timed windows of --steps steps each")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the profiled windows, the roofline objects, the side legs and the CPU baseline")
+    ap.add_argument("--windows", type=int, default=5, help="--full: least number of profiled windows of --steps steps each")
     ap.add_argument("--min-timed-s", type=float, default=1.0,
-                    help="keep adding timed windows until this much GPU time lies inside timed regions")
+                    help="--full: keep adding profiled windows until this much GPU time lies inside them")
     ap.add_argument("--views", type=int, default=0, help="views per rank per step (default: the workload's 50)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for the all-core CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -241,6 +250,34 @@ def device_labels(ids, view, n_classes=4, seed_face=4, seed_pix=5):
     cls = torch.where(u < 100, (r >> 10) % n_classes, cls)
     cls = torch.where(u >= 990, torch.full_like(cls, 255), cls)
     return cls.to(torch.uint8).reshape(ids.shape)
+
+
+DUMP_SAMPLES = 1 << 22   # id samples written by --dump-outputs: 16 MB of float32 ids + 32 MB of float64 indices
+DUMP_SEED = 20260101
+
+
+def dump_outputs(out_dir, ids, n_faces, rank, world):
+    """--dump-outputs: the (views, H, W) int32 face ids of the last timed step, as float32 (exact: every id is below 2^24).
+    Larger than DUMP_SAMPLES elements (2.4 GB at the default sizes), they are sampled at DUMP_SAMPLES distinct positions
+    drawn with a fixed seed, so that two runs with the same arguments sample the same pixels:
+      face_ids.npy        the sampled ids, in the order of
+      face_ids_index.npy  their flat indices into the (views, H, W) array (float64), ascending.
+    Below that size face_ids.npy is the whole array in its own shape and no index is written.  At N > 1 every rank writes
+    its own views, with the suffix _rank<r>."""
+    import torch
+
+    assert n_faces < 1 << 24, "face ids would not be exact in float32"
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    n = ids.numel()
+    if n <= DUMP_SAMPLES:
+        np.save(out / f"face_ids{tag}.npy", ids.cpu().numpy().astype(np.float32))
+        return
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_SAMPLES, replace=False))
+    got = ids.reshape(-1)[torch.from_numpy(idx).to(ids.device)].cpu().numpy()
+    np.save(out / f"face_ids{tag}.npy", got.astype(np.float32))
+    np.save(out / f"face_ids_index{tag}.npy", idx.astype(np.float64))
 
 
 def main(argv=None):
@@ -394,16 +431,71 @@ def run(args, rig=None) -> int:
 
     hip.raster_face_ids(recs, H, W, out=ids, check=True)  # sizes the bin lists once (any overflow is retried here)
     blocks_per_view = hip.last_stats.get("blocks", 0) / max(nv, 1)  # 64-face blocks that pass the per-view frustum cull
-    # untimed pre-conditioning (clocks, TLBs of the scratch): the device needs ~15 ms of this workload to reach its
-    # steady state after start-up; without it a short run (K <= 10) reads 5-8 % lower than a long one
-    for _ in range(12):
-        step()
+    # untimed pre-conditioning (clocks, TLBs of the scratch): without it a short run (K <= 10) reads 5-8 % lower than a long
+    # one, and after only 12 steps (~10 ms) a 40-step window still read 1-2 % below a 1000-step one.  Rounds of
+    # PRECONDITION_STEPS steps, each ended by a synchronize, until wl.precondition_s of wall time has passed.
+    t_pre = time.perf_counter()
+    while True:
+        for _ in range(PRECONDITION_STEPS):
+            step()
+        rig.synchronize(dev)
+        if time.perf_counter() - t_pre >= wl.precondition_s:
+            break
     for _ in range(args.warmup):
         step()
+    # the headline: ONE window of exactly --steps steps, library events off
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    barrier()
+    elapsed = max_over_ranks(time.perf_counter() - t0)
+    stats = hip.raster_status()
+    assert stats["overflow"] == 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ids, F, rank, world)
+    views_per_s = world * nv * args.steps / elapsed
+    mpix_per_s = views_per_s * P / 1e6
+    line = {
+        "metric": "Mpix/s rasterized (face-ID pix2face), 1.2M-face mesh @ 4000x3000",
+        "value": round(mpix_per_s, 1),
+        "unit": "Mpix/s",
+        "n_gpus": world,
+        "ranks_seen": ranks_seen,
+        "ranks": rank_map,
+        "collective_backend": rig.backend_version() if hasattr(rig, "backend_version") else rig.dist_backend,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int32 (fixed-point edge functions) / fp32 (vertex transform, depth)",
+        "data": "synthetic",
+        "config": {
+            "workload": f"BASELINE config 2: {F}-face heightfield (V={V}), {nv} pinhole views/GPU @ {W}x{H}, "
+                        f"f={wl.f:g} px, 120 m AGL lawn-mower grid, face-ID raster to int32 in HBM",
+            "views_per_gpu_per_step": nv,
+            "faces": F,
+            "vertices": V,
+            "parallelism": f"views sharded, mesh replicated, dp{world}",
+        },
+        "views_per_s": round(views_per_s, 2),
+        "records_per_view": round(stats["records"] / max(nv, 1), 1),
+        "bin_entries_per_view": round(stats["entries"] / max(nv, 1), 1),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if distributed:
+            dist.destroy_process_group()
+        return 0
+
+    # ---- --full from here on: nothing below changes `value` or `ms_per_step` ----------------------------------------------
     # the library's HIP events (on the stream the kernels run on; for the two stages of a raster call they ride on the kernel
     # launches themselves -- hipExtLaunchKernelGGL stop events, a stage = [end of the kernel before it, end of its last kernel]
     # -- so that timing the kernels does not slow them: recorded events cost the step 1.65 %) stay ON through the
-    # timed windows: the per-kernel durations of the roofline object are those of exactly the timed steps
+    # profiled windows: the per-kernel durations of the roofline object are those of exactly these steps
     hip.set_profiling(True)
     # windows of EXACTLY --steps steps; at least --windows of them, and as many more as it takes to put --min-timed-s of GPU
     # time inside timed regions (every rank takes the same decision: it is made on the MAX-reduced times)
@@ -417,15 +509,10 @@ def run(args, rig=None) -> int:
         window_s.append(max_over_ranks(time.perf_counter() - t0))
     st = hip.stage_times()
     hip.set_profiling(False)
-    stats = hip.raster_status()
-    assert stats["overflow"] == 0
-    elapsed = statistics.median(window_s)
-    views_per_window = world * nv * args.steps
-    views_per_s = views_per_window / elapsed
-    mpix_per_s = views_per_s * P / 1e6
+    assert hip.raster_status()["overflow"] == 0
     ms_windows = [round(s / args.steps * 1e3, 4) for s in window_s]
 
-    # ---- per-kernel HIP-event times: st, collected over the timed windows above -----------------------------------------
+    # ---- per-kernel HIP-event times: st, collected over the profiled windows above --------------------------------------
     launches = max(st["raster_launches"], 1)
     raster_ms_per_launch = st["raster_ms"] / launches
     setup_ms_per_launch = st["setup_ms"] / launches
@@ -738,38 +825,12 @@ def run(args, rig=None) -> int:
             if quarter.get("fused"):
                 roofline["c3_quarter_scale_fused_views_per_s"] = quarter["fused"]["views_per_s"]
                 roofline["c3_quarter_scale_fused_us_per_view"] = quarter["fused"]["us_per_view"]
-        line = {
-            "metric": "Mpix/s rasterized (face-ID pix2face), 1.2M-face mesh @ 4000x3000",
-            "value": round(mpix_per_s, 1),
-            "unit": "Mpix/s",
-            "n_gpus": world,
-            "ranks_seen": ranks_seen,
-            "ranks": rank_map,
-            "collective_backend": rig.backend_version() if hasattr(rig, "backend_version") else rig.dist_backend,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        line["config"]["workload_2"] = None if workload_2 is None else workload_2["workload"]
+        line["config"]["workload_3"] = None if workload_3 is None else workload_3["workload"]
+        line.update({
             "ms_per_step_windows": {"n": len(ms_windows), "median": statistics.median(ms_windows), "min": min(ms_windows),
                                     "max": max(ms_windows), "first": ms_windows[:5], "last": ms_windows[-5:]},
             "timed_gpu_s": round(sum(window_s), 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int32 (fixed-point edge functions) / fp32 (vertex transform, depth)",
-            "data": "synthetic",
-            "config": {
-                "workload": f"BASELINE config 2: {F}-face heightfield (V={V}), {nv} pinhole views/GPU @ {W}x{H}, "
-                            f"f={wl.f:g} px, 120 m AGL lawn-mower grid, face-ID raster to int32 in HBM",
-                "views_per_gpu_per_step": nv,
-                "faces": F,
-                "vertices": V,
-                "parallelism": f"views sharded, mesh replicated, dp{world}",
-                "workload_2": None if workload_2 is None else workload_2["workload"],
-                "workload_3": None if workload_3 is None else workload_3["workload"],
-            },
-            "views_per_s": round(views_per_s, 2),
-            "records_per_view": round(stats["records"] / max(nv, 1), 1),
-            "bin_entries_per_view": round(stats["entries"] / max(nv, 1), 1),
             "roofline": roofline,
             "rooflines": rooflines,
             "cpu_baseline": cpu_baseline,
@@ -781,7 +842,7 @@ def run(args, rig=None) -> int:
             "quarter_scale": quarter,
             "api": api,
             "io": io,
-        }
+        })
         print(json.dumps(line), flush=True)
     if distributed:
         dist.destroy_process_group()

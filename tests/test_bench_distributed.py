@@ -2,7 +2,8 @@
 the very function the driver launches -- every `all_reduce` call site (ranks_seen, the MAX-over-ranks reductions of the
 timed windows, the packed vote reduce of the aggregate / c4 / c5 legs), the barriers, the rank-0-only JSON line, the exit
 code of a line that would claim more GPUs than answered -- with a stand-in for the HIP backend (the CPU oracle dressed as
-`HipRaster`, tests/oracle_backend.py) and a toy workload.  What it cannot cover is RCCL itself."""
+`HipRaster`, tests/oracle_backend.py) and a toy workload.  What it cannot cover is RCCL itself.  The legs run with
+`--full`; the plain run (headline window only, `--dump-outputs`) is checked on its own."""
 import io
 import json
 import os
@@ -31,6 +32,7 @@ class _BenchStub(OracleBackend):
 
     def __init__(self):
         super().__init__()
+        self.unchecked_calls = 0   # steps: raster calls with check=False
         self.last_retries = 0
         self.last_stats = {}
         self._prof = None
@@ -61,6 +63,7 @@ class _BenchStub(OracleBackend):
             out.copy_(ids)
         self._note(ids.shape[0], time.perf_counter() - t0)
         if not check:
+            self.unchecked_calls += 1
             self.last_stats = {"unchecked": True}
         return out if out is not None else ids
 
@@ -76,13 +79,14 @@ class _BenchStub(OracleBackend):
 class _StubRig:
     dist_backend = "gloo"
     overrides = {}
+    backends = []
 
     def __init__(self):
         import bench
 
         kw = dict(n_side=24, extent=400.0, H=48, W=64, f=48.0, views_per_rank=3, c3_views=6, c4_views_per_rank=4, n_classes=4,
                   c5_n_side=30, c5_extent=800.0, c5_H=40, c5_W=60, c5_f=45.0, c5_views_total=8, c5_views_per_rank=4,
-                  c5_classes=10, c5_raster_views=2, min_leg_s=0.0)
+                  c5_classes=10, c5_raster_views=2, min_leg_s=0.0, precondition_s=0.0)
         kw.update(self.overrides)
         self.workload = bench.Workload(**kw)
 
@@ -96,7 +100,8 @@ class _StubRig:
         pass
 
     def make_raster(self, local_rank):
-        return _BenchStub()
+        self.backends.append(_BenchStub())
+        return self.backends[-1]
 
     def checker(self):
         from oracle import oracle_c
@@ -107,23 +112,26 @@ class _StubRig:
         return False
 
 
-def _rank(rank, world, port, out_dir, gpus_flag, overrides=None):
+FULL = ["--steps", "2", "--warmup", "1", "--windows", "2", "--min-timed-s", "0", "--full"]
+
+
+def _rank(rank, world, port, out_dir, gpus_flag, overrides=None, flags=FULL):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world), RANK=str(rank), LOCAL_RANK=str(rank))
     sys.modules.pop("bench", None)
     import bench
 
     _StubRig.overrides = dict(overrides or {})
 
-    args = bench.parse_args(["--gpus", str(gpus_flag), "--steps", "2", "--warmup", "1", "--windows", "2", "--min-timed-s", "0"])
+    args = bench.parse_args(["--gpus", str(gpus_flag), *flags])
     buf = io.StringIO()
     with redirect_stdout(buf):
         rc = bench.run(args, _StubRig())
     with open(os.path.join(out_dir, f"rank{rank}.json"), "w") as fh:
-        json.dump({"rc": rc, "stdout": buf.getvalue()}, fh)
+        json.dump({"rc": rc, "stdout": buf.getvalue(), "unchecked_calls": [b.unchecked_calls for b in _StubRig.backends]}, fh)
 
 
-def _run(tmp_path, world, gpus_flag, overrides=None):
-    mp.spawn(_rank, args=(world, _free_port(), str(tmp_path), gpus_flag, overrides), nprocs=world, join=True)
+def _run(tmp_path, world, gpus_flag, overrides=None, flags=FULL):
+    mp.spawn(_rank, args=(world, _free_port(), str(tmp_path), gpus_flag, overrides, flags), nprocs=world, join=True)
     return [json.load(open(tmp_path / f"rank{r}.json")) for r in range(world)]
 
 
@@ -186,3 +194,67 @@ def test_a_rank_without_views_still_joins_every_collective(tmp_path, world):
     assert line["c4"]["views_per_gpu"] == 1 and line["c5"]["views_per_gpu"] == 1      # rank 0 holds the one view
     assert line["c4"]["face_observations_after_reduce"] > 0 and line["c5"]["face_observations_after_reduce"] > 0
     assert line["c4"]["reps"] >= 3 and line["c5"]["aggregate_reps"] >= 2
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("world", [1, 2])
+def test_a_plain_run_times_exactly_its_steps_and_nothing_else(tmp_path, world):
+    """Without --full: set-up, warm-up, ONE window of exactly --steps steps and the headline line -- no profiled windows, no
+    roofline, no side leg, no CPU baseline."""
+    import bench
+
+    res = _run(tmp_path, world, world, flags=["--steps", "5", "--warmup", "2"])
+    assert [r["rc"] for r in res] == [0] * world
+    assert all(r["unchecked_calls"] == [bench.PRECONDITION_STEPS + 2 + 5] for r in res)
+    assert all(r["stdout"].strip() == "" for r in res[1:])
+    lines = [l for l in res[0]["stdout"].splitlines() if l.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["n_gpus"] == world and line["value"] > 0
+    assert line["unit"] == "Mpix/s" and line["higher_is_better"] is True
+    for key in ("ms_per_step_windows", "timed_gpu_s", "roofline", "rooflines", "cpu_baseline", "aggregate", "c4", "c5",
+                "workload_2", "workload_3", "quarter_scale", "api", "io"):
+        assert key not in line, key
+    assert abs(line["views_per_s"] - world * 3 * 5 / (line["ms_per_step"] * 5e-3)) / line["views_per_s"] < 1e-3
+
+
+@pytest.mark.timeout(600)
+def test_dump_outputs_holds_the_last_step_and_repeats_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the ids of the last timed step (small enough here to be written whole) as float32, the same in two
+    runs with the same arguments, and equal to the CPU oracle's ids of the same views."""
+    from geograypher_amd.utils import synthetic
+    from oracle import oracle_c
+
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"out{k}"
+        res = _run(tmp_path, 1, 1, flags=["--steps", "3", "--warmup", "0", "--dump-outputs", str(out)])
+        assert res[0]["rc"] == 0
+        assert sorted(p.name for p in out.iterdir()) == ["face_ids.npy"]
+        dumps.append(np.load(out / "face_ids.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (3, 48, 64)
+    assert np.array_equal(dumps[0], dumps[1])
+    points, faces = synthetic.terrain_mesh(24, 400.0)
+    recs = synthetic.survey_cameras(10, 5, 40.0, 60.0, seed=3, f=48.0, width=64, height=48).get_raster_records(1.0, near=1.0)[:3]
+    want, _ = oracle_c.raster_views(points, faces, recs, 48, 64, n_threads=1)
+    assert np.array_equal(dumps[0], want.astype(np.float32)) and (want >= 0).any()
+
+
+def test_dump_outputs_samples_a_large_output_at_fixed_positions(tmp_path, monkeypatch):
+    """Above DUMP_SAMPLES elements the ids are sampled at seeded, distinct, ascending positions whose flat indices are
+    written beside them; at the default sample size both files together stay within 64 MB."""
+    sys.modules.pop("bench", None)
+    import bench
+
+    assert bench.DUMP_SAMPLES * (4 + 8) <= 64 << 20
+    monkeypatch.setattr(bench, "DUMP_SAMPLES", 1000)
+    ids = torch.arange(-1, 5 * 40 * 30 - 1, dtype=torch.int32).reshape(5, 40, 30)
+    bench.dump_outputs(tmp_path / "a", ids, 6000, 0, 1)
+    bench.dump_outputs(tmp_path / "b", ids, 6000, 1, 2)
+    got, idx = np.load(tmp_path / "a" / "face_ids.npy"), np.load(tmp_path / "a" / "face_ids_index.npy")
+    assert got.dtype == np.float32 and idx.dtype == np.float64 and got.shape == idx.shape == (1000,)
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < ids.numel()
+    assert np.array_equal(got, ids.reshape(-1).numpy()[idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "b" / "face_ids_rank1.npy"), got)
+    assert np.array_equal(np.load(tmp_path / "b" / "face_ids_index_rank1.npy"), idx)

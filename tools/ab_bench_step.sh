@@ -8,7 +8,7 @@ for r in $(seq 1 $R); do
   for k in $(seq 0 $((N - 1))); do
     T=${L[$(((k + r - 1) % N))]}
     if [ $T = base ]; then unset GEOGRAYPHER_AMD_LIB; else export GEOGRAYPHER_AMD_LIB=$PWD/geograypher_amd/csrc/libgeograster_$T.so; fi
-    python bench.py --no-cpu-baseline --no-api --no-io --no-c4 --no-c5 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-api --no-io --no-c4 --no-c5 2>/dev/null | python -c "
 import sys, json
 j = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 r = j['roofline']

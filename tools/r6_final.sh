@@ -11,7 +11,7 @@ bash tools/profile.sh r06 > $OUT/profile.log 2>&1
 grep -E "k_raster_tile|k_setup_cull|k_vote|k_cull" gpurun_out/prof_r06/summary_r06.txt | cut -c1-170
 # the counter files of THIS tree in place before the bench line is taken, so that the line carries `traffic` / `valu`
 cp gpurun_out/prof_r06/traffic.json gpurun_out/prof_r06/valu.json profiles/
-( time timeout 900 python bench.py ) > $OUT/bench.json 2> $OUT/bench.err
+( time timeout 900 python bench.py --full ) > $OUT/bench.json 2> $OUT/bench.err
 tail -4 $OUT/bench.err
 python -c "
 import json
