@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "gr_mesh_upload",
     "gr_raster_face_ids",
     "gr_raster_status",
+    "gr_raster_overflow_causes",
     "gr_gather_texture_f64",
     "gr_project_labels_u8",
     "gr_project_values_f64",
@@ -133,6 +134,8 @@ def load_library() -> ctypes.CDLL:
     lib.gr_raster_face_ids.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.gr_raster_status.restype = i32
     lib.gr_raster_status.argtypes = [vp, ctypes.POINTER(RasterStats)]
+    lib.gr_raster_overflow_causes.restype = i32
+    lib.gr_raster_overflow_causes.argtypes = [vp]
     lib.gr_gather_texture_f64.restype = i32
     lib.gr_gather_texture_f64.argtypes = [vp, vp, i64, vp, i64, i32, vp, vp]
     lib.gr_project_labels_u8.restype = i32
@@ -200,7 +203,9 @@ def _torch():
 class _StatsAccumulator:
     """Statistics of a checked raster call over its attempts: an attempt that overflowed contributes the views it
     completed (records and entries are summed over the views a call processed, so they are scaled by the completed share);
-    `max_entries` is the largest per-tile (single-pass) or per-view (exact binning) count any attempt saw."""
+    `max_entries` is the largest per-tile (single-pass) or per-view (exact binning) count any attempt saw;
+    `overflow_causes` the OR of every attempt's causes (gr_raster_overflow_causes: 1 a list outgrew its slots, 2 a face missed
+    the 40-byte entry form, 4 a tile's entry and micro lists met)."""
 
     def __init__(self):
         self.records = 0.0
@@ -210,9 +215,10 @@ class _StatsAccumulator:
         self.max_entries = 0
         self.views = 0
         self.rebinned = 0
+        self.causes = 0
         self.last = None
 
-    def add(self, st: "RasterStats", n_views: int, partial: bool):
+    def add(self, st: "RasterStats", n_views: int, partial: bool, causes: int = 0):
         done = int(st.views_done) if partial else n_views
         share = done / max(n_views, 1)
         self.records += st.records * share
@@ -222,13 +228,14 @@ class _StatsAccumulator:
         self.max_entries = max(self.max_entries, int(st.max_entries))
         self.views += done
         self.rebinned += int(st.rebinned_groups)
+        self.causes |= int(causes)
         self.last = st
 
     def result(self) -> dict:
         d = self.last.as_dict()
         d.update(records=int(round(self.records)), entries=int(round(self.entries)), max_entries=self.max_entries,
                  views_done=self.views, blocks=int(round(self.blocks)), chunk_visits=int(round(self.chunk_visits)),
-                 rebinned_groups=self.rebinned)
+                 rebinned_groups=self.rebinned, overflow_causes=self.causes)
         return d
 
 
@@ -478,13 +485,14 @@ class HipRaster:
                 break
             st = RasterStats()
             rc = self.lib.gr_raster_status(self._ctx, ctypes.byref(st))
+            causes = self.lib.gr_raster_overflow_causes(self._ctx)
             if rc == GR_EOVERFLOW and attempt < 3:
-                acc.add(st, n - v0, partial=True)
+                acc.add(st, n - v0, partial=True, causes=causes)
                 v0 += int(st.views_done)  # the library has recorded the need; only the unfinished views are repeated
                 self.last_retries += 1
                 continue
             self._check(rc, "gr_raster_status")
-            acc.add(st, n - v0, partial=False)
+            acc.add(st, n - v0, partial=False, causes=causes)
             self.last_stats = acc.result()
             break
         return (out, depth) if want_depth else out
@@ -493,6 +501,12 @@ class HipRaster:
         st = RasterStats()
         self._check(self.lib.gr_raster_status(self._ctx, ctypes.byref(st)), "gr_raster_status")
         return st.as_dict()
+
+    def overflow_causes(self) -> int:
+        """Why the last raster call overflowed, as far as `raster_status()` (or the call's own check) has read it: the OR of
+        1 (a tile list outgrew its slots), 2 (a face missed the 40-byte entry form) and 4 (a tile's entry and micro lists
+        met); 0 for a call without overflow."""
+        return int(self.lib.gr_raster_overflow_causes(self._ctx))
 
     # -- render_flat gather --------------------------------------------------------------------------------------
     def gather_texture(self, ids, face_texture):
@@ -656,14 +670,15 @@ class HipRaster:
                 break
             st = RasterStats()
             rc = self.lib.gr_raster_status(self._ctx, ctypes.byref(st))
+            causes = self.lib.gr_raster_overflow_causes(self._ctx)
             if rc == GR_EOVERFLOW and attempt < 3:
                 # the votes of the first views_done views are in; the library skipped the rest on the device
-                acc.add(st, n - v0, partial=True)
+                acc.add(st, n - v0, partial=True, causes=causes)
                 v0 += int(st.views_done)
                 self.last_retries += 1
                 continue
             self._check(rc, "gr_raster_status")
-            acc.add(st, n - v0, partial=False)
+            acc.add(st, n - v0, partial=False, causes=causes)
             self.last_stats = acc.result()
             break
         return ids_out

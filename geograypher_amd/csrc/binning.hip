@@ -533,7 +533,9 @@ void k_setup_cull(const float *__restrict__ cams, BinArgs a) {
         const int Pxc = (px0 + TWh) * 256 + 128, Pyc = (py0 + THh) * 256 + 128;   // centre of the tile's centre pixel
         const uint32_t pos = (uint32_t)(k == 0 ? r3.x : k == 1 ? r3.y : k == 2 ? r3.z : r3.w);
         const int ncx = (jhi - jlo + 4) >> 2;   // 4-pixel columns of the part: 1 or 2
-        if ((pos + (uint32_t)nk) * 4u <= (uint32_t)a.cap_tile * 5u) {   // inside the segment (cap slots of 40 bytes; whether the two lists met: k_bin_stats)
+        // inside the segment (cap slots of 40 bytes).  This bounds the micro list alone: two lists that each fit here and in
+        // entry positions below cap can still meet -- k_bin_stats raises the view's overflow word for that (bit 4)
+        if ((pos + (uint32_t)nk) * 4u <= (uint32_t)a.cap_tile * 5u) {
           // record p of the tile's list: the 32 bytes that end 32 p bytes before the end of the tile's segment
           char *const rec_end = segs + ((int64_t)(ty * a.TX + tx) + 1) * a.cap_tile * 40 - (int64_t)pos * 32;
           const int4 va = make_int4(pack16(X0 - Pxc, Y0 - Pyc), pack16(X1 - Pxc, Y1 - Pyc), pack16(X2 - Pxc, Y2 - Pyc), r1.z);
@@ -652,34 +654,53 @@ void k_setup_cull(const float *__restrict__ cams, BinArgs a) {
 __global__ __launch_bounds__(1024) void k_bin_stats(BinArgs a) {
   __shared__ unsigned long long part[16];
   __shared__ uint32_t pmax[16];
+  __shared__ uint32_t pmet[16];
   const int slot = blockIdx.x;
   uint32_t *ctrl = a.ctrl + slot * a.ctrl_stride;
   const uint32_t *cnt = ctrl + GR_CTRL_HDR;
+  const uint32_t cap = (uint32_t)a.cap_tile;
   unsigned long long sum = 0;
-  uint32_t mx = 0;
+  uint32_t mx = 0, met = 0;
   // (with micro lists a tile's segment holds both lists, one from each end: compiled entries in whole chunks of 64 x 40 bytes
-  // from the front, 32-byte micro records from the back -- together, in 40-byte slots, they must fit)
+  // from the front, 32-byte micro records from the back -- together, in 40-byte slots, they must fit.  Each list is bounded
+  // only on its own where it is stored (k_setup_cull) and walked (raster_one_tile): a tile whose lists are each within their
+  // bounds but together outgrow the segment has lists that overwrote each other -- "the lists met", told here alone)
   for (int t = threadIdx.x; t < a.T; t += 1024) {
     const int64_t i = cidx(a, t);
     uint32_t c = cnt[i];
-    if (a.micro) { const uint32_t cm = cnt[a.Tcap + i]; if (cm) c = ((c + 63u) & ~63u) + (cm * 32u + 39u) / 40u; }
+    if (a.micro) {
+      const uint32_t cm = cnt[a.Tcap + i];
+      if (cm) {
+        const uint32_t both = ((c + 63u) & ~63u) + (cm * 32u + 39u) / 40u;
+        if (both > cap && c <= cap && cm * 4u <= cap * 5u) met = 1u;
+        c = both;
+      }
+    }
     sum += c; mx = max(mx, c);
   }
-  for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o); mx = max(mx, (uint32_t)__shfl_xor((int)mx, o)); }
-  if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6] = sum; pmax[threadIdx.x >> 6] = mx; }
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o); mx = max(mx, (uint32_t)__shfl_xor((int)mx, o)); met |= (uint32_t)__shfl_xor((int)met, o);
+  }
+  if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6] = sum; pmax[threadIdx.x >> 6] = mx; pmet[threadIdx.x >> 6] = met; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    unsigned long long total = 0; uint32_t m = 0;
-    for (int k = 0; k < 16; ++k) { total += part[k]; m = max(m, pmax[k]); }
+    unsigned long long total = 0; uint32_t m = 0, lists_met = 0;
+    for (int k = 0; k < 16; ++k) { total += part[k]; m = max(m, pmax[k]); lists_met |= pmet[k]; }
     ctrl[1] = (uint32_t)total;
+    // the view's overflow word: 1 a list outgrew its slots (k_setup_cull), 2 a face missed the 40-byte form (store_entry), 4 the
+    // lists met.  Any bit keeps the fused tile kernel off the view's lists -- it runs after this kernel on the same stream
+    // (fused calls never defer it) -- and the view is repeated like any overflow
+    uint32_t why = ctrl[2];
+    if (lists_met) { atomicOr(&ctrl[2], 4u); why |= 4u; }
     atomicAdd(&a.stats[6], (unsigned long long)ctrl[3]);   // 64-face blocks that passed the frustum cull
-    const bool ovf = m > (uint32_t)a.cap_tile || ctrl[2] != 0;
+    const bool ovf = m > cap || why != 0;
     atomicAdd(&a.stats[0], (unsigned long long)ctrl[0]);
     atomicAdd(&a.stats[1], total);
     atomicAdd(&a.stats[8], (unsigned long long)ctrl[6]);  // micro faces (pixel box at most 4 x 4)
     atomicMax(&a.stats[2], (unsigned long long)m);  // direct mode: the largest per-tile count
     if (ovf) { atomicMax(&a.stats[3], 1ull); atomicMin(&a.stats[4], (unsigned long long)a.group); }
-    if (ctrl[2] & 2u) atomicMax(&a.stats[5], 1ull);  // a face the 40-byte entry form cannot hold
+    if (why & 2u) atomicMax(&a.stats[5], 1ull);  // a face the 40-byte entry form cannot hold
+    if (why) atomicOr(&a.stats[10], (unsigned long long)why);   // the call's overflow causes (gr_raster_overflow_causes)
   }
 }
 
@@ -725,7 +746,7 @@ __global__ __launch_bounds__(1024) void k_scan_tiles(BinArgs a) {
     atomicAdd(&a.stats[1], (unsigned long long)total);
     atomicMax(&a.stats[2], (unsigned long long)total);
     atomicMax(&a.stats[9], (unsigned long long)ctrl[0]);   // records the view needs (clipped faces: several each)
-    if (ovf) { atomicMax(&a.stats[3], 1ull); atomicMin(&a.stats[4], (unsigned long long)a.group); }
+    if (ovf) { atomicMax(&a.stats[3], 1ull); atomicMin(&a.stats[4], (unsigned long long)a.group); atomicOr(&a.stats[10], 1ull); }
   }
 }
 
@@ -1034,7 +1055,10 @@ __device__ void emit_triangle(const BinArgs &a, int slot, uint32_t *ctrl, Vtx v0
     // (k_scan_tiles: stats[9]; found by tools/fuzz_parity.py seed 934669: 18 faces around the camera, exact binning)
     const uint32_t s = atomicAdd(&ctrl[0], 1u);
     const int64_t RP = a.rec_stride >> 2;
-    if ((int64_t)s >= RP) { atomicMax(&a.stats[3], 1ull); atomicMin(&a.stats[4], (unsigned long long)a.group); return; }
+    if ((int64_t)s >= RP) {
+      atomicMax(&a.stats[3], 1ull); atomicMin(&a.stats[4], (unsigned long long)a.group); atomicOr(&a.stats[10], 1ull);
+      return;
+    }
     const bool small_fp = (tx1 - tx0 <= 1) && (ty1 - ty0 <= 1);
     int4 r3 = {0, 0, 0, 0};
     if (small_fp) {
@@ -1143,8 +1167,8 @@ __global__ __launch_bounds__(256) void k_bin_init(uint4 *__restrict__ ctrl16, in
   for (int64_t i = i0; i < n16; i += step) ctrl16[i] = make_uint4(0u, 0u, 0u, 0u);
   for (int64_t i = i0; i < nt; i += step) touched[i] = 0u;
   // [0..3] records, entries, largest count, overflow; [4] first overflowed launch group: none; [5..9] short-form miss, blocks,
-  // chunk visits, micro faces, records of a view (gr_raster_status)
-  if (stats && i0 < 10) stats[i0] = i0 == 4 ? ~0ull : 0ull;
+  // chunk visits, micro faces, records of a view; [10] overflow causes (gr_raster_status, gr_raster_overflow_causes)
+  if (stats && i0 < 11) stats[i0] = i0 == 4 ? ~0ull : 0ull;
 }
 
 // (view, 64-face group) pairs the vote passes of the last fused call visited, added up for gr_raster_status (k_vote_labels keeps a

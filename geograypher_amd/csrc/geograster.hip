@@ -206,6 +206,7 @@ int raster_views(gr_ctx *c, const float *cams, int n_views, int h, int w, int32_
   int rc = check_common(c, n_views, h, w);
   if (rc) return rc;
   c->rebinned = again;
+  if (again == 0) c->causes = 0;
   if (!c->verts) return fail(c, GR_ENOMESH, "gr_mesh_upload has not been called");
   if (!cams) return fail(c, GR_EINVAL, "null cams");
   if (n_views == 0) return GR_OK;
@@ -278,9 +279,10 @@ int raster_views(gr_ctx *c, const float *cams, int n_views, int h, int w, int32_
       // costs, where rounds 1-4 paid the whole call once more after gr_raster_status).  Otherwise the slots in use are noted as
       // sufficient and no call looks again.  Later groups of the call, and later calls with more crowded views, keep the
       // GR_EOVERFLOW protocol.
-      unsigned long long st[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      unsigned long long st[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       GR_HIP(c, hipMemcpyAsync(st, c->stats, sizeof(st), hipMemcpyDeviceToHost, s));
       GR_HIP(c, hipStreamSynchronize(s));
+      c->causes |= (int)(st[10] & 7u);   // (the attempt that starts over zeroes the device's word: kept here for the caller)
       const bool grow = st[3] && (int64_t)st[2] > c->cur_cap, miss = st[3] && st[5] != 0;
       const bool micro = !c->cur_micro && !(c->opt_var & (128 | 4096)) && !miss && st[0] > 0 && 5 * st[8] > 2 * st[0];
       if (grow) learn_slots(c, T, (int64_t)st[2], miss, micro);
@@ -496,7 +498,7 @@ int gr_raster_face_ids(gr_ctx *c, const float *cams, int n_views, int h, int w, 
 
 int gr_raster_status(gr_ctx *c, gr_raster_stats *o) {
   if (!c || !o) return GR_EINVAL;
-  unsigned long long st[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long st[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   {
     int rc = bin_stats_deferred(c, c->last_stream);   // the view totals of a call that left them for now
     if (!rc) rc = sum_visits(c, c->last_stream);      // ... and the visit counters of a fused call's vote passes
@@ -508,6 +510,7 @@ int gr_raster_status(gr_ctx *c, gr_raster_stats *o) {
   o->entry_cap = c->ent_cap; o->overflow = (int32_t)st[3];
   o->blocks = (int64_t)st[6]; o->chunk_visits = (int64_t)st[7];
   o->rebinned_groups = c->rebinned;
+  c->causes |= (int)(st[10] & 7u);
   // views of the last call whose results are complete: every launch group in front of the first one that overflowed
   o->views_done = st[3] ? (int32_t)std::min<unsigned long long>(st[4] * (unsigned long long)std::max(c->last_B, 1),
                                                                 (unsigned long long)c->last_n_views)
@@ -547,6 +550,8 @@ int gr_raster_status(gr_ctx *c, gr_raster_stats *o) {
   }
   return GR_OK;
 }
+
+int gr_raster_overflow_causes(const gr_ctx *c) { return c ? c->causes : 0; }
 
 int gr_raster_project_labels_u8(gr_ctx *c, const float *cams, const uint8_t *labels, int n_views, int h, int w, int C,
                                 uint32_t *votes, uint32_t *counts, int32_t *ids_or_null, int flags, void *stream) {

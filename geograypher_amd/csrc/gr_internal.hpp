@@ -55,7 +55,8 @@ struct BinArgs {
                          //                            each at the front of the same slot memory)
   uint8_t *nrow8;        // [slot][ent_cap] rows of each entry inside its tile (the tile kernel's scan input: a compact stream)
   unsigned long long *stats;  // [6] records, entries, max_entries, overflow, first overflowed launch group (over the call),
-                              //     short-form miss (a face the 40-byte entry cannot hold: the caller repeats with 48 bytes)
+                              //     short-form miss (a face the 40-byte entry cannot hold: the caller repeats with 48 bytes);
+                              //     [10] the call's overflow causes, ORed (1 list outgrew its slots, 2 short-form miss, 4 lists met)
   int group;             // index of this launch group inside the call
   int64_t ctrl_stride;   // words per slot
   int64_t rec_stride;    // int4 per slot: four planes of rec_stride / 4 >= F records
@@ -157,6 +158,7 @@ struct gr_ctx {
   bool cur_look = false;               // nothing learned about this (mesh, image size): the first launch group's counts are read
                                        // before its tile kernel runs (raster_views)
   int rebinned = 0;                    // times the last raster call started over after that look
+  int causes = 0;                      // overflow causes the last raster call met, as read by that look and gr_raster_status
   bool stats_pending = false;          // the call's statistics have not been reset yet (the first launch group's init kernel does)
   bool defer_stats = false;            // this call's view totals (k_bin_stats) wait for gr_raster_status: one launch group, not fused, no look
   bool stats_deferred = false;         // ... and have not been added up yet

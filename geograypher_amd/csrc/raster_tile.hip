@@ -626,9 +626,11 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
   const uint8_t *nr8 = a.nrow8 + slot * a.ent_cap + beg;
 
   // the tile's MICRO list (single-pass binning with 40-byte entries): cntm entries from the back of the segment; the scanline
-  // list must not reach into it (the two can only collide in a pass whose tile outgrew its segment: the view is repeated)
+  // list must not reach into it.  The clamps below bound each list on its own; two lists that each fit but together outgrow the
+  // segment have overwritten each other -- k_bin_stats raises the view's overflow word for that (bit 4): the fused kernel does
+  // not walk such a view, and the ids of this pass are repeated after the status call
   if (!(SHORT && MICRO)) cntm = 0u;
-  if (SHORT && MICRO) {   // both lists inside the segment (a view whose lists met is repeated: k_bin_stats)
+  if (SHORT && MICRO) {   // both lists inside the segment
     cntm = min(cntm, (uint32_t)a.cap_tile * 5u / 4u);
     cnt = min(cnt, (uint32_t)a.cap_tile);
   }

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GR_VERSION 123 /* 0.2.3: the first launch group of an unknown (mesh, image size) is looked at before its tile kernel runs (gr_raster_stats.rebinned_groups); 0.2.2: micro lists (a fifth field in the learned-table file); 0.2.1: gr_learned_cache_clear; 0.2.0: gr_resize_image_f64, gr_learned_cache_file, mesh-signature keyed learned table */
+#define GR_VERSION 124 /* 0.2.4: gr_raster_overflow_causes; 0.2.3: the first launch group of an unknown (mesh, image size) is looked at before its tile kernel runs (gr_raster_stats.rebinned_groups); 0.2.2: micro lists (a fifth field in the learned-table file); 0.2.1: gr_learned_cache_clear; 0.2.0: gr_resize_image_f64, gr_learned_cache_file, mesh-signature keyed learned table */
 
 enum {
   GR_OK = 0,
@@ -193,6 +193,13 @@ int gr_raster_face_ids(gr_ctx *ctx, const float *cams, int n_views, int h, int w
  * GR_OPT_DIRECT_CAP) now knows the segment size / entry form this mesh and image size need: call again for the remaining
  * views.  At most one such retry per cause for a given (mesh, image size). */
 int gr_raster_status(gr_ctx *ctx, gr_raster_stats *out_h);
+/* Why the last raster call overflowed, as far as gr_raster_status (and the look at a first launch group) read it: the OR of
+ * 1 = a tile list outgrew its slots where it was stored (single-pass: compiled entries beyond the slots per tile, micro records
+ *     beyond 1.25 x the slots per tile; exact binning: a view's entry or record list),
+ * 2 = a face did not fit the 40-byte entry form,
+ * 4 = with micro lists: a tile's two lists, each within its own bound, together outgrew the tile's segment (they met).
+ * 0 after a call without overflow.  Host only: no device work, no synchronisation. */
+int gr_raster_overflow_causes(const gr_ctx *ctx);
 
 /* render_flat gather -- replaces meshes.py:1921-1937: out[p,:] = face_tex[ids[p],:] where ids[p] != -1 else NaN.
  * ids: n_pix int32; face_tex: F x C f64; out: n_pix x C f64. */

@@ -19,12 +19,15 @@ def test_header_and_binding_agree():
     assert _declared_symbols() == sorted(_hip.EXPORTED_SYMBOLS)
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_at_the_header_version():
+    """Every declared symbol is exported, and the library reports the version the header declares (124: the ABI that added
+    gr_raster_overflow_causes) -- a stale build or a header bumped without the library fails here."""
     lib = ctypes.CDLL(str(_hip.library_path()))
     for name in _declared_symbols():
         assert hasattr(lib, name), f"libgeograster.so does not export {name}"
+    header = int(re.search(r"#define GR_VERSION (\d+)", (ROOT / "include" / "geograster.h").read_text()).group(1))
     lib.gr_version.restype = ctypes.c_int
-    assert lib.gr_version() == 123
+    assert lib.gr_version() == header == 124
 
 
 def _header_struct(name):
@@ -74,3 +77,15 @@ def test_product_never_imports_the_oracle():
     for path in (ROOT / "geograypher_amd").rglob("*.py"):
         text = path.read_text()
         assert "import oracle" not in text and "from oracle" not in text, path
+
+
+def test_overflow_causes_is_bound_and_answers_without_a_device():
+    """gr_raster_overflow_causes (header <-> export <-> binding): bound with the declared signature; it only reads the context
+    on the host, so a null context answers 0 without a GPU."""
+    text = (ROOT / "include" / "geograster.h").read_text()
+    assert re.search(r"\bint gr_raster_overflow_causes\(const gr_ctx \*ctx\);", text)
+    assert "gr_raster_overflow_causes" in _hip.EXPORTED_SYMBOLS
+    lib = _hip.load_library()
+    assert lib.gr_raster_overflow_causes.restype is ctypes.c_int
+    assert lib.gr_raster_overflow_causes.argtypes == [ctypes.c_void_p]
+    assert lib.gr_raster_overflow_causes(None) == 0
