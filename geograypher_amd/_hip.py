@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "gr_raster_project_labels_u8",
     "gr_gather_texture_u8",
     "gr_project_index_pairs",
+    "gr_project_rect_pairs",
     "gr_count_pairs",
     "gr_warp_nearest_i32",
     "gr_warp_f64",
@@ -151,6 +152,8 @@ def load_library() -> ctypes.CDLL:
     lib.gr_gather_texture_u8.argtypes = [vp, vp, i64, vp, i64, i32, i32, vp, vp]
     lib.gr_project_index_pairs.restype = i32
     lib.gr_project_index_pairs.argtypes = [vp, vp, vp, i32, i32, i32, i64, vp, vp, i64, vp, i32, vp]
+    lib.gr_project_rect_pairs.restype = i32
+    lib.gr_project_rect_pairs.argtypes = [vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, i64, vp, i32, vp]
     lib.gr_count_pairs.restype = i32
     lib.gr_count_pairs.argtypes = [vp, vp, i64, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
     lib.gr_warp_nearest_i32.restype = i32
@@ -281,6 +284,7 @@ class PairAccumulator:
         if ids_t.shape != img_t.shape:
             raise ValueError(f"ids {tuple(ids_t.shape)} and index image {tuple(img_t.shape)} differ in shape")
         n, h, w = (int(x) for x in ids_t.shape)
+        self._fit_mesh()
         if n * b.n_faces > self.cap:
             for k in range(n):
                 self.add(ids_t[k], img_t[k])
@@ -295,12 +299,60 @@ class PairAccumulator:
         b._check(rc, "gr_project_index_pairs")
         self.bound += n * b.n_faces
 
+    def add_rects(self, ids, rects, offsets):
+        """`add` for views whose label image is a list of rectangles (`Segmentor.label_rectangles`): ids (n, h, w) or
+        (h, w); rects int (R, 5) rows {imin, jmin, imax, jmax, class}, half-open and in paint order; offsets (n + 1,), view
+        k's rows are rects[offsets[k]:offsets[k + 1]].  The tables go to the device as ONE small int32 upload; the label of a
+        face's winning pixel is the class of the last rectangle containing it (`gr_project_rect_pairs`)."""
+        torch = _torch()
+        b = self.b
+        ids_t = b._dev(ids, torch.int32)
+        if ids_t.ndim == 2:
+            ids_t = ids_t[None]
+        n, h, w = (int(x) for x in ids_t.shape)
+        self._fit_mesh()
+        rects = np.asarray(rects.cpu() if isinstance(rects, torch.Tensor) else rects).reshape(-1, 5)
+        offsets = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets).reshape(-1)
+        if offsets.shape[0] != n + 1:
+            raise ValueError(f"{n} views need {n + 1} rectangle offsets, got {offsets.shape[0]}")
+        if offsets[0] != 0 or offsets[-1] != rects.shape[0] or np.any(np.diff(offsets) < 0):
+            raise ValueError(f"rectangle offsets must rise from 0 to {rects.shape[0]} (the number of rectangles)")
+        if rects.size and (rects.min() < np.iinfo(np.int32).min or rects.max() > np.iinfo(np.int32).max):
+            raise ValueError("rectangle corners and classes must fit in int32")
+        if n * b.n_faces > self.cap:
+            for k in range(n):
+                lo, hi = int(offsets[k]), int(offsets[k + 1])
+                self.add_rects(ids_t[k], rects[lo:hi], np.array([0, hi - lo]))
+            return
+        if self.bound + n * b.n_faces > self.cap:
+            self._compact()
+        # one upload: offsets, then the rectangle rows
+        table = b._dev(np.concatenate([offsets.astype(np.int32), rects.astype(np.int32).reshape(-1)]), torch.int32)
+        offs_ptr = table.data_ptr()
+        rects_ptr = offs_ptr + 4 * (n + 1)
+        with torch.cuda.device(b.device):
+            rc = b.lib.gr_project_rect_pairs(
+                b._ctx, ids_t.data_ptr(), rects_ptr, offs_ptr, n, h, w, self.n_classes, self.counts.data_ptr(),
+                self.keys.data_ptr(), self.cap, self.key_count.data_ptr(), self.flags, b._stream(),
+            )
+        b._check(rc, "gr_project_rect_pairs")
+        self.bound += n * b.n_faces
+
+    def _fit_mesh(self):
+        """The mesh may be uploaded (or replaced by a larger one) after the accumulator was made: the buffer must hold at
+        least one view's pairs, or a single view could never be added."""
+        if self.b.n_faces > self.cap:
+            self._compact()
+            self.cap = max(8 * self.b.n_faces, 1 << 20)
+            self.keys = _torch().empty((self.cap,), dtype=_torch().int64, device=self.b.device)
+
     def _compact(self):
         torch = _torch()
         b = self.b
         raw, bad = (int(x) for x in self.key_count.cpu().tolist())
         if bad:
-            raise IndexError(f"gr_project_index_pairs: an image value is not a class index in [0, {self.n_classes})")
+            raise IndexError(f"gr_project_index_pairs / gr_project_rect_pairs: an image value is not a class index in "
+                             f"[0, {self.n_classes})")
         if raw > 0:
             uniq = torch.empty((raw,), dtype=torch.int64, device=b.device)
             mult = torch.empty((raw,), dtype=torch.int32, device=b.device)

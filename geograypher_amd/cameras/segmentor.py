@@ -51,6 +51,15 @@ class SegmentorPhotogrammetryCameraSet(PhotogrammetryCameraSet):
         image_filename = self.base_camera_set.get_image_filename(index, absolute=True)
         return fn(self._raw(index, image_scale), filename=image_filename, image_scale=image_scale)
 
+    def get_label_rectangles(self, index: int, image_scale: float = 1):
+        """(int32 (R, 5) rectangles {imin, jmin, imax, jmax, class} in paint order, (h, w)) that make up view `index`'s
+        label image, or None when the segmentor cannot describe it by rectangles exactly."""
+        fn = getattr(self.segmentor, "label_rectangles", None)
+        if fn is None:
+            return None
+        image_filename = self.base_camera_set.get_image_filename(index, absolute=True)
+        return fn(image_filename, image_scale=image_scale)
+
     def get_raw_image_by_index(self, index: int, image_scale: float = 1) -> np.ndarray:
         return self.base_camera_set.get_image_by_index(index=index, image_scale=image_scale)
 

@@ -274,6 +274,84 @@ __global__ __launch_bounds__(256) void k_emit_index_pairs(uint32_t *__restrict__
   if (f < F && c) counts[f] += c;
 }
 
+// K10r sparse index aggregation of rectangle labels (detections / image IDs): K10 with the label image replaced by a
+//     lookup.  The winner pixel p = (p / w, p % w) takes the class of the LAST rectangle of its view's list that contains it
+//     (the list is in paint order: a later rectangle overwrites an earlier one); no rectangle = no observation.  The view's
+//     rectangles are staged in LDS in chunks of RECT_CHUNK, walked from the end; a block stops at the first chunk in which
+//     none of its faces is still searching.  rects: int32 rows {imin, jmin, imax, jmax, class}, half-open, already clipped
+//     to the image; offs: per view [offs[v], offs[v + 1]) into rects.
+#define RECT_CHUNK 512
+__global__ __launch_bounds__(256) void k_emit_rect_pairs(uint32_t *__restrict__ winner, const int32_t *__restrict__ rects,
+                                                         const int32_t *__restrict__ offs, int n_views, int64_t F, int w,
+                                                         long long n_classes, uint32_t *__restrict__ counts,
+                                                         unsigned long long *__restrict__ keys, long long key_cap,
+                                                         unsigned long long *__restrict__ key_count,
+                                                         int *__restrict__ bad) {
+  __shared__ int4 box[RECT_CHUNK];
+  __shared__ int box_cls[RECT_CHUNK];
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  uint32_t c = 0;
+  for (int v = 0; v < n_views; ++v) {
+    int pi = 0, pj = 0;
+    bool searching = false;
+    if (f < F) {
+      const uint32_t wk = winner[v * F + f];
+      if (wk != 0) {
+        winner[v * F + f] = 0;
+        pi = (int)((wk - 1) / (uint32_t)w);
+        pj = (int)((wk - 1) % (uint32_t)w);
+        searching = true;
+      }
+    }
+    bool found = false;
+    int cls = 0;
+    const int r0 = offs[v], r1 = offs[v + 1];
+    for (int end = r1; end > r0; end -= RECT_CHUNK) {
+      // also the barrier that lets the chunk before this one (or the previous view's last one) be overwritten
+      if (!__syncthreads_or(searching)) break;
+      const int beg = end - RECT_CHUNK > r0 ? end - RECT_CHUNK : r0;
+      const int n = end - beg;
+      for (int k = threadIdx.x; k < n; k += 256) {
+        const int32_t *r = rects + (int64_t)(beg + k) * 5;
+        box[k] = make_int4(r[0], r[1], r[2], r[3]);
+        box_cls[k] = r[4];
+      }
+      __syncthreads();
+      if (searching) {
+        for (int k = n - 1; k >= 0; --k) {
+          const int4 b = box[k];
+          if (pi >= b.x && pj >= b.y && pi < b.z && pj < b.w) {
+            cls = box_cls[k];
+            found = true;
+            searching = false;
+            break;
+          }
+        }
+      }
+    }
+    bool emit = false;
+    unsigned long long key = 0;
+    if (found) {
+      ++c;
+      if (cls < 0 || (long long)cls >= n_classes) atomicOr(bad, 1);
+      else { emit = true; key = (unsigned long long)f * (unsigned long long)n_classes + (unsigned long long)cls; }
+    }
+    const unsigned long long m = __ballot(emit);
+    if (m) {
+      const int leader = __ffsll((long long)m) - 1;
+      unsigned long long base = 0;
+      if (lane == leader) base = atomicAdd(key_count, (unsigned long long)__popcll(m));
+      base = __shfl(base, leader);
+      if (emit) {
+        const unsigned long long idx = base + __popcll(m & ((1ull << lane) - 1ull));
+        if ((long long)idx < key_cap) keys[idx] = key;
+      }
+    }
+  }
+  if (f < F && c) counts[f] += c;
+}
+
 __global__ __launch_bounds__(256) void k_finalize_votes(const uint32_t *__restrict__ votes,
                                                         const uint32_t *__restrict__ counts, int64_t F, int C,
                                                         double *__restrict__ average, double *__restrict__ summed,
@@ -510,6 +588,49 @@ int gr_project_index_pairs(gr_ctx *c, const int32_t *ids, const double *img, int
   GR_HIP(c, hipMemcpyAsync(&bad, c->flag, sizeof(int), hipMemcpyDeviceToHost, s));
   GR_HIP(c, hipStreamSynchronize(s));
   if (bad) return fail(c, GR_EINDEX, "an image value is not a class index in [0, %lld)", (long long)n_classes);
+  return GR_OK;
+}
+
+int gr_project_rect_pairs(gr_ctx *c, const int32_t *ids, const int32_t *rects, const int32_t *rect_offsets, int n_views,
+                          int h, int w, int64_t n_classes, uint32_t *counts, uint64_t *keys, int64_t key_cap,
+                          uint64_t *key_count, int flags, void *stream) {
+  int rc = check_common(c, n_views, h, w);
+  if (rc) return rc;
+  if (c->F <= 0) return fail(c, GR_ENOMESH, "gr_mesh_upload has not been called");
+  if (!ids || !rect_offsets || !counts || !keys || !key_count || n_classes <= 0 || key_cap < 0)
+    return fail(c, GR_EINVAL, "bad sparse projection args");
+  if (n_views == 0) return GR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
+  const int64_t P = (int64_t)h * w, F = c->F;
+  const int B = n_views < GR_MAX_BATCH ? n_views : GR_MAX_BATCH;
+  rc = ensure_winner(c, sizeof(uint32_t) * (size_t)F * B, s);
+  if (rc) return rc;
+  note_stream(c, s);
+  uint32_t *win = (uint32_t *)c->winner;
+  const bool defer = (flags & GR_FLAG_DEFER_CHECK) != 0;
+  int *bad_flag = defer ? reinterpret_cast<int *>(key_count + 1) : c->flag;
+  if (!defer) GR_HIP(c, hipMemsetAsync(c->flag, 0, sizeof(int), s));
+  for (int v0 = 0; v0 < n_views; v0 += B) {
+    const int nb = (n_views - v0) < B ? (n_views - v0) : B;
+    {
+      Timed t(c, s, ST_PROJECT);
+      hipLaunchKernelGGL(k_winner, dim3((unsigned)ceil_div(ceil_div(w, 4), 256), (unsigned)ceil_div(h, WIN_ROWS), nb), dim3(256), 0, s, ids + v0 * P, win, F, h, w,
+                         (flags & GR_FLAG_NEG1_IS_LAST_FACE) ? 1 : 0);
+    }
+    {
+      Timed t(c, s, ST_VOTE);
+      hipLaunchKernelGGL(k_emit_rect_pairs, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, rects, rect_offsets + v0,
+                         nb, F, w, (long long)n_classes, counts, (unsigned long long *)keys, (long long)key_cap,
+                         (unsigned long long *)key_count, bad_flag);
+    }
+  }
+  GR_HIP(c, hipGetLastError());
+  if (defer) return GR_OK;
+  int bad = 0;
+  GR_HIP(c, hipMemcpyAsync(&bad, c->flag, sizeof(int), hipMemcpyDeviceToHost, s));
+  GR_HIP(c, hipStreamSynchronize(s));
+  if (bad) return fail(c, GR_EINDEX, "a rectangle's class is not a class index in [0, %lld)", (long long)n_classes);
   return GR_OK;
 }
 

@@ -9,7 +9,9 @@ Mirror of geograypher/meshes/derived_meshes.py for the two variants whose work i
   un-chunked class (a superset of what a 125 m-buffered chunk can see).
 * `TexturedPhotogrammetryMeshIndexPredictions` (derived_meshes.py:414-550): aggregation of single-channel class-index
   images with many classes into scipy CSR arrays; the per-view projection, pair emission, radix sort and
-  run-length count run on the device (`gr_project_index_pairs`, `gr_count_pairs`).
+  run-length count run on the device (`gr_project_index_pairs`, `gr_count_pairs`).  Where the camera set's segmentor
+  describes its label images as rectangles (detections, image IDs: `get_label_rectangles`), no label image is built at
+  all: the label of a face's winning pixel is looked up in the view's rectangle table (`gr_project_rect_pairs`).
 """
 import typing
 
@@ -78,7 +80,16 @@ class TexturedPhotogrammetryMeshIndexPredictions(TexturedPhotogrammetryMesh):
         counts = torch.zeros((n_faces,), dtype=torch.int32, device=self.backend.device)
         # the (face, class) pair keys of all views stay on the device; ONE sort + run-length count at the end
         acc = self.backend.new_pair_accumulator(n_classes, counts, neg1_is_last_face=self.neg1_is_last_face)
-        gen = self._iter_view_inputs(cameras, batch_size, aggregate_img_scale, True, kwargs)
+        batch_stop = max(len(cameras) - batch_size + 1, 1)  # trailing views that do not fill a batch are dropped
+        tables = None
+        if not return_all and hasattr(acc, "add_rects") and hasattr(cameras, "get_label_rectangles"):
+            n_used = len(range(0, batch_stop, batch_size)) * batch_size
+            tables = [cameras.get_label_rectangles(i, aggregate_img_scale) for i in range(n_used)]
+            if any(t is None for t in tables):
+                tables = None
+        gen = () if tables is not None else self._iter_view_inputs(cameras, batch_size, aggregate_img_scale, True, kwargs)
+        if tables is not None:
+            self._add_rectangle_pairs(acc, cameras, tables, batch_size, batch_stop, aggregate_img_scale, kwargs)
         for _, ids, img, n_channels in tqdm(gen, total=len(cameras), desc="Aggregating projected viewpoints"):
             if return_all:
                 if img is None:
@@ -108,3 +119,27 @@ class TexturedPhotogrammetryMeshIndexPredictions(TexturedPhotogrammetryMesh):
         )
         average_projections = summed_projections.multiply(reciprocal)
         return average_projections, info
+
+    def _add_rectangle_pairs(self, acc, cameras, tables, batch_size, batch_stop, aggregate_img_scale, pix2face_kwargs):
+        """The label-rectangle path of `aggregate_projected_images`: ids come from pix2face exactly as on the image path
+        (same batches, mesh, distortion and keywords); the rectangle tables of a batch go to the device as one small int32
+        upload and the label of each face's winning pixel is looked up there.  No label image is loaded or built."""
+        torch = _torch()
+        mesh = self.get_mesh_in_cameras_coords(cameras)
+        for batch_start in tqdm(range(0, batch_stop, batch_size), desc="Aggregating projected viewpoints"):
+            batch_cameras = cameras.get_subset_cameras(list(range(batch_start, batch_start + batch_size)))
+            ids = self.pix2face(
+                cameras=batch_cameras, mesh=mesh, render_img_scale=aggregate_img_scale, return_tensor=True,
+                **pix2face_kwargs,
+            )
+            if isinstance(ids, np.ndarray):  # distortion applied on the host
+                ids = self.backend._dev(ids.astype(np.int32), torch.int32)
+            batch = tables[batch_start:batch_start + batch_size]
+            for rects, hw in batch:
+                if tuple(hw) != tuple(ids.shape[1:]):
+                    raise ValueError(
+                        f"ids {tuple(ids.shape[1:])} and index image {tuple(hw)} differ in shape"
+                    )
+            offsets = np.zeros(len(batch) + 1, dtype=np.int64)
+            offsets[1:] = np.cumsum([rects.shape[0] for rects, _ in batch])
+            acc.add_rects(ids, np.concatenate([rects for rects, _ in batch]), offsets)

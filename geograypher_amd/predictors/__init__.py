@@ -1,4 +1,9 @@
 from geograypher_amd.predictors.segmentor import Segmentor
-from geograypher_amd.predictors.derived_segmentors import ArrayLabelSegmentor, LookUpSegmentor
+from geograypher_amd.predictors.derived_segmentors import (
+    ArrayLabelSegmentor,
+    ImageIDSegmentor,
+    LookUpSegmentor,
+    TabularRectangleSegmentor,
+)
 
-__all__ = ["Segmentor", "LookUpSegmentor", "ArrayLabelSegmentor"]
+__all__ = ["Segmentor", "LookUpSegmentor", "ArrayLabelSegmentor", "ImageIDSegmentor", "TabularRectangleSegmentor"]

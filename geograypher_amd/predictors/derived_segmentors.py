@@ -1,4 +1,7 @@
-"""Segmentors that feed the aggregation loop (reference: geograypher/predictors/derived_segmentors.py:32-51)."""
+"""Segmentors that feed the aggregation loop (reference: geograypher/predictors/derived_segmentors.py:32-306)."""
+import csv
+import re
+import typing
 from pathlib import Path
 
 import numpy as np
@@ -125,3 +128,258 @@ class ArrayLabelSegmentor(Segmentor):
         return self.inds_to_one_hot(
             self.segment_image_indices(image, filename=filename, image_scale=image_scale), self.num_classes
         )
+
+
+# -- detections and image IDs (reference: derived_segmentors.py:54-306) ------------------------------------------------
+# Both segmentors describe their label image as rectangles.  Besides the reference's per-pixel `segment_image`, each has
+# `label_rectangles(filename, image_scale)` -> (int32 (R, 5) rows {imin, jmin, imax, jmax, class} in paint order, (h, w)),
+# or None where rectangles cannot express the image exactly: the sparse aggregation then looks the label of a face's
+# winning pixel up on the device instead of building, uploading and reading a per-pixel float64 image.
+
+_INT_RE = re.compile(r"[+-]?\d+\Z")
+_FLOAT_RE = re.compile(r"[+-]?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?\Z|[+-]?(nan|inf|infinity)\Z", re.IGNORECASE)
+
+
+def _column_values(cells: typing.List[str]) -> list:
+    """pandas.read_csv's type inference for one column, restated for the cases a detection table holds: int64 when every
+    cell is an integer, float64 when every cell is a number (an empty cell is NaN), str otherwise (empty cells NaN)."""
+    if cells and all(_INT_RE.match(c) for c in cells):
+        return [int(c) for c in cells]
+    if all(c == "" or _FLOAT_RE.match(c) for c in cells):
+        return [float(c) if c != "" else float("nan") for c in cells]
+    return [c if c != "" else float("nan") for c in cells]
+
+
+def _csv_cell(value) -> str:
+    """One cell the way DataFrame.to_csv writes it (NaN as an empty cell, floats by repr)."""
+    if isinstance(value, float):
+        return "" if value != value else repr(value)
+    return str(value)
+
+
+def _normalised_rect(imin, jmin, imax, jmax, h, w):
+    """The (imin, jmin, imax, jmax) that `image[imin:imax, jmin:jmax]` of an (h, w) image covers (negative corners wrap,
+    corners beyond the image clamp), or None when it covers nothing."""
+    i0, i1, _ = slice(imin, imax).indices(h)
+    j0, j1, _ = slice(jmin, jmax).indices(w)
+    if i1 <= i0 or j1 <= j0:
+        return None
+    return i0, j0, i1, j1
+
+
+class _DetectionTable:
+    """The detections table: columns in file order, one list of values per column (what the reference keeps in a pandas
+    DataFrame, without pandas)."""
+
+    def __init__(self, columns: typing.List[str], data: typing.Dict[str, list]):
+        self.columns = columns
+        self.data = data
+
+    def __len__(self):
+        return len(self.data[self.columns[0]]) if self.columns else 0
+
+    def __getitem__(self, key):
+        return self.data[key]
+
+    def row(self, i: int) -> dict:
+        return {c: self.data[c][i] for c in self.columns}
+
+    def to_csv(self, path):
+        with open(path, "w", newline="") as f:
+            out = csv.writer(f, lineterminator="\n")
+            out.writerow([""] + self.columns)
+            for i in range(len(self)):
+                out.writerow([str(i)] + [_csv_cell(self.data[c][i]) for c in self.columns])
+
+
+class ImageIDSegmentor(Segmentor):
+    """Every pixel holds the index of the view's file in `image_filenames` (reference: derived_segmentors.py:54-82).
+    Feeds the face-visibility matrix of `TexturedPhotogrammetryMeshIndexPredictions` (n_classes = number of views)."""
+
+    thread_safe_lookup = True  # stateless: a header read and a list look-up
+
+    def __init__(self, image_filenames: typing.List[PATH_TYPE]):
+        self.image_filenames = image_filenames
+
+    def _shape_and_index(self, filename, image_scale):
+        from PIL import Image
+
+        with Image.open(filename) as img_handler:  # the header only, as the reference does
+            w, h = img_handler.size
+        image_index = self.image_filenames.index(filename)  # ValueError for a file not in the list
+        return (int(h * image_scale), int(w * image_scale)), image_index
+
+    def segment_image(self, image: np.ndarray, filename: PATH_TYPE, image_scale: float):
+        output_shape, image_index = self._shape_and_index(filename, image_scale)
+        return np.full(output_shape, fill_value=image_index, dtype=int)
+
+    def label_rectangles(self, filename: PATH_TYPE, image_scale: float = 1):
+        """One rectangle covering the image: exact at every scale."""
+        (h, w), image_index = self._shape_and_index(filename, image_scale)
+        rects = [(0, 0, h, w, image_index)] if h > 0 and w > 0 else []
+        return np.array(rects, dtype=np.int32).reshape(-1, 5), (h, w)
+
+
+class TabularRectangleSegmentor(Segmentor):
+    """Bounding boxes from a CSV file (or a folder of them) painted into an (h, w) float image, NaN where there is no box
+    (reference: derived_segmentors.py:85-306).  The class of a box is the index of its `label_key` value among the sorted
+    distinct values of that column; with the default `instance_ID` every detection is a class of its own."""
+
+    thread_safe_lookup = True  # the table is read once, look-ups only read it
+
+    def __init__(
+        self,
+        detection_file_or_folder: PATH_TYPE,
+        image_shape: tuple,
+        label_key: str = "instance_ID",
+        image_path_key: str = "image_path",
+        imin_key: str = "ymin",
+        imax_key: str = "ymax",
+        jmin_key: str = "xmin",
+        jmax_key: str = "xmax",
+        detection_file_extension: str = "csv",
+        strip_image_extension: bool = False,
+        use_absolute_filepaths: bool = False,
+        split_bbox: bool = True,
+        image_folder: typing.Union[PATH_TYPE, None] = None,
+    ):
+        self.image_shape = image_shape
+        self.label_key = label_key
+        self.image_path_key = image_path_key
+        self.imin_key = imin_key
+        self.imax_key = imax_key
+        self.jmin_key = jmin_key
+        self.jmax_key = jmax_key
+        self.split_bbox = split_bbox
+
+        self.labels_df = self.load_detection_files(
+            detection_file_or_folder=detection_file_or_folder,
+            detection_file_extension=detection_file_extension,
+            image_folder=image_folder,
+            use_absolute_filepaths=use_absolute_filepaths,
+            strip_image_extension=strip_image_extension,
+            image_path_key=image_path_key,
+        )
+        # groupby(image_path_key): sorted keys (NaN dropped), each group's rows in table order
+        groups: typing.Dict[typing.Any, typing.List[int]] = {}
+        for i, key in enumerate(self.labels_df[self.image_path_key]):
+            if not (isinstance(key, float) and key != key):
+                groups.setdefault(key, []).append(i)
+        self.image_names = sorted(groups)
+        self._groups = {k: groups[k] for k in self.image_names}
+        self.class_names = np.unique(np.array(self.labels_df[self.label_key])).tolist()
+        self.num_classes = len(self.class_names)
+        self._class_index = {name: i for i, name in enumerate(self.class_names)}
+
+    def load_detection_files(
+        self,
+        detection_file_or_folder: PATH_TYPE,
+        detection_file_extension: str,
+        image_folder: PATH_TYPE,
+        use_absolute_filepaths: bool,
+        strip_image_extension: bool,
+        image_path_key: str,
+    ) -> _DetectionTable:
+        if Path(detection_file_or_folder).is_file():
+            files = [detection_file_or_folder]
+        else:
+            files = sorted(Path(detection_file_or_folder).glob("*" + detection_file_extension))
+        if not files:
+            raise ValueError("No objects to concatenate")  # what pd.concat([]) raises
+
+        # read every file, then concatenate: columns in order of first appearance, missing cells empty
+        columns: typing.List[str] = []
+        rows: typing.List[dict] = []
+        for f in files:
+            with open(f, newline="") as fh:
+                reader = csv.reader(fh)
+                header = next(reader, None)
+                if header is None:
+                    raise ValueError(f"No columns to parse from file {f}")
+                for c in header:
+                    if c not in columns:
+                        columns.append(c)
+                for cells in reader:
+                    if cells:
+                        rows.append(dict(zip(header, cells)))
+        data = {c: _column_values([r.get(c, "") for r in rows]) for c in columns}
+        table = _DetectionTable(columns, data)
+
+        if "instance_ID" not in table.columns:
+            table.columns.append("instance_ID")
+            table.data["instance_ID"] = list(range(len(rows)))
+        if image_folder is not None and use_absolute_filepaths:
+            table.data[image_path_key] = [str(Path(image_folder, p)) for p in table[image_path_key]]
+        if strip_image_extension:
+            table.data[image_path_key] = [str(Path(p).with_suffix("")) for p in table[image_path_key]]
+        return table
+
+    def get_all_detections(self) -> _DetectionTable:
+        """The concatenated detections table (columns `.columns`, values `table[column]`)."""
+        return self.labels_df
+
+    def save_detection_data(self, output_csv_file: PATH_TYPE):
+        """Write the detections table in DataFrame.to_csv's layout (a leading unnamed index column); the containing
+        folder is created if needed."""
+        Path(output_csv_file).parent.mkdir(parents=True, exist_ok=True)
+        self.labels_df.to_csv(output_csv_file)
+
+    def get_corners(self, data, as_int=True):
+        if self.split_bbox:
+            bbox = data["bbox"][1:-1]  # "[x, y, w, h]"
+            jmin, imin, width, height = [float(s) for s in bbox.split(", ")]
+            imax = imin + height
+            jmax = jmin + width
+        else:
+            imin = data[self.imin_key]
+            imax = data[self.imax_key]
+            jmin = data[self.jmin_key]
+            jmax = data[self.jmax_key]
+        corners = imin, jmin, imax, jmax
+        if as_int:
+            corners = list(map(int, corners))  # truncation toward zero
+        return corners
+
+    def _image_rows(self, filename):
+        name = Path(filename).name
+        return self._groups.get(name, [])
+
+    def segment_image(self, image, filename, image_scale, vis=False):
+        if vis:
+            raise NotImplementedError("TabularRectangleSegmentor: vis=True (plotting) is not supported")
+        if image_scale != 1.0:
+            # the reference resizes the NaN-background float image with skimage's default anti-aliasing, which smears the
+            # NaN into the boxes; that is not reproduced here
+            raise NotImplementedError(
+                "TabularRectangleSegmentor: image_scale != 1 would anti-alias a float image that holds NaN (the reference's "
+                "skimage resize); only image_scale == 1 is supported"
+            )
+        label_image = np.full(self.image_shape, fill_value=np.nan, dtype=float)
+        for i in self._image_rows(filename):
+            row = self.labels_df.row(i)
+            label_ind = self._class_index[row[self.label_key]]
+            imin, jmin, imax, jmax = self.get_corners(row)
+            label_image[imin:imax, jmin:jmax] = label_ind
+        return label_image
+
+    def label_rectangles(self, filename, image_scale: float = 1):
+        """The boxes `segment_image` paints, in paint order, clipped like numpy slices; None at image_scale != 1 (see
+        `segment_image`) or for an image_shape that is not (h, w)."""
+        if image_scale != 1 or len(self.image_shape) != 2:
+            return None
+        h, w = (int(x) for x in self.image_shape)
+        rects = []
+        for i in self._image_rows(filename):
+            row = self.labels_df.row(i)
+            r = _normalised_rect(*self.get_corners(row), h, w)
+            if r is not None:
+                rects.append((*r, self._class_index[row[self.label_key]]))
+        return np.array(rects, dtype=np.int32).reshape(-1, 5), (h, w)
+
+    def get_detection_centers(self, filename):
+        """(n, 2) (i, j) centres of the detections of `filename` (matched on the whole string, as in the reference)."""
+        if filename not in self.image_names:
+            return np.zeros((0, 2))
+        all_corners = [self.get_corners(self.labels_df.row(i), as_int=False) for i in self._groups[filename]]
+        imin, jmin, imax, jmax = [np.array(x) for x in zip(*all_corners)]
+        return np.vstack([(imin + imax) / 2, (jmin + jmax) / 2]).T

@@ -259,6 +259,15 @@ int gr_gather_texture_u8(gr_ctx *ctx, const int32_t *ids, int64_t n_pix, const d
 int gr_project_index_pairs(gr_ctx *ctx, const int32_t *ids, const double *img, int n_views, int h, int w,
                            int64_t n_classes, uint32_t *counts, uint64_t *keys, int64_t key_cap, uint64_t *key_count,
                            int flags, void *stream);
+/* gr_project_index_pairs with the label image given as rectangles (detections, image IDs): same winners, flags, pair
+ * keys, counts and class check, but the winner pixel (p / w, p % w) of a face takes the class of the LAST rectangle of its
+ * view's list that contains it, and a pixel no rectangle contains is no observation.  No per-pixel label image exists.
+ * rects: int32 rows {imin, jmin, imax, jmax, class} (half-open, in paint order; device memory, may be NULL when no view
+ * has a rectangle); rect_offsets: n_views + 1 non-decreasing device int32, view v's rows are
+ * [rect_offsets[v], rect_offsets[v + 1]) -- the caller guarantees they index rects.  Added without a GR_VERSION bump. */
+int gr_project_rect_pairs(gr_ctx *ctx, const int32_t *ids, const int32_t *rects, const int32_t *rect_offsets,
+                          int n_views, int h, int w, int64_t n_classes, uint32_t *counts, uint64_t *keys,
+                          int64_t key_cap, uint64_t *key_count, int flags, void *stream);
 /* multiplicity of every distinct pair key: radix sort + run-length encode (rocPRIM via hipcub) in context scratch.
  * unique_keys / pair_counts: capacity n.  *n_unique_h (host) receives the number of distinct keys.  Synchronises. */
 int gr_count_pairs(gr_ctx *ctx, uint64_t *keys, int64_t n, uint64_t *unique_keys, uint32_t *pair_counts,
