@@ -25,6 +25,8 @@ GR_EOVERFLOW = -6
 GR_FLAG_NEG1_IS_LAST_FACE = 1
 GR_FLAG_DEFER_CHECK = 2
 GR_CAM_FLOATS = 16
+GR_DTYPE_F32 = 1
+GR_DTYPE_F64 = 2
 
 # every symbol include/geograster.h declares (tests check that the library exports each of them)
 EXPORTED_SYMBOLS = (
@@ -56,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "gr_resize_image_f64",
     "gr_finalize_votes",
     "gr_finalize_sums_f64",
+    "gr_argmax_nonzero",
     "gr_argmax_nonzero_f64",
 )
 
@@ -172,6 +175,8 @@ def load_library() -> ctypes.CDLL:
     lib.gr_finalize_votes.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp]
     lib.gr_finalize_sums_f64.restype = i32
     lib.gr_finalize_sums_f64.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp]
+    lib.gr_argmax_nonzero.restype = i32
+    lib.gr_argmax_nonzero.argtypes = [vp, vp, i32, i64, i32, vp, vp]
     lib.gr_argmax_nonzero_f64.restype = i32
     lib.gr_argmax_nonzero_f64.argtypes = [vp, vp, i64, i32, vp, vp]
     _lib = lib
@@ -890,12 +895,21 @@ class HipRaster:
         return avg, sums, cnt
 
     def argmax_nonzero(self, array):
-        """utils/indexing.py:9-32 on device: (F,C) float64 -> (F,) float64."""
+        """utils/indexing.py:9-32 on device: (F,C) -> (F,) float64.  float32 stays float32, as numpy sums it; every other
+        dtype is converted to float64 -- exact for the integer vote arrays this is given while their partial row sums stay
+        below 2^53.  The row sum follows numpy's pairwise order for a C-contiguous array; a Fortran-ordered array (which
+        numpy sums left to right) is made C-contiguous here and summed in that order."""
         torch = _torch()
-        arr = self._dev(array, torch.float64)
+        if isinstance(array, torch.Tensor):
+            is_f32 = array.dtype == torch.float32
+        else:
+            array = np.asarray(array)
+            is_f32 = array.dtype == np.float32
+        arr = self._dev(array, torch.float32 if is_f32 else torch.float64)
+        dtype = GR_DTYPE_F32 if is_f32 else GR_DTYPE_F64
         F, C = int(arr.shape[0]), int(arr.shape[1])
         out = torch.empty((F,), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            rc = self.lib.gr_argmax_nonzero_f64(self._ctx, arr.data_ptr(), F, C, out.data_ptr(), self._stream())
-        self._check(rc, "gr_argmax_nonzero_f64")
+            rc = self.lib.gr_argmax_nonzero(self._ctx, arr.data_ptr(), dtype, F, C, out.data_ptr(), self._stream())
+        self._check(rc, "gr_argmax_nonzero")
         return out

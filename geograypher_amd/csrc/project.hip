@@ -253,9 +253,13 @@ __global__ __launch_bounds__(256) void k_emit_index_pairs(uint32_t *__restrict__
         const double x = img[(int64_t)v * P + (w - 1)];
         if (isfinite(x)) {
           ++c;
-          const long long cls = (long long)x;  // astype(int): truncation
-          if (cls < 0 || cls >= n_classes) atomicOr(bad, 1);
-          else { emit = true; key = (unsigned long long)f * (unsigned long long)n_classes + (unsigned long long)cls; }
+          // astype(int) truncates toward zero: the class lies in [0, n_classes) exactly when -1 < x < n_classes (exact in
+          // double: n_classes <= 2^53).  Decided before the conversion, which is undefined for |x| >= 2^63.
+          if (!(x > -1.0 && x < (double)n_classes)) atomicOr(bad, 1);
+          else {
+            emit = true;
+            key = (unsigned long long)f * (unsigned long long)n_classes + (unsigned long long)(long long)x;
+          }
         }
       }
     }
@@ -381,27 +385,95 @@ __global__ __launch_bounds__(256) void k_finalize_sums(double *__restrict__ sums
   if (i == f * C) counts_f64[f] = (double)c;
 }
 
-// utils/indexing.py:9-32
-__global__ __launch_bounds__(256) void k_argmax_nonzero(const double *__restrict__ arr, int64_t F, int C,
+// numpy's pairwise sum of n contiguous values (the order np.sum(a, axis=1) takes on a C-contiguous row): fewer than 8 values
+// are added one by one from zero; up to 128 go to eight accumulators r[k] += a[8i + k], combined as
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), and the n % 8 tail is added one by one; more are split at
+// n2 = n / 2 - (n / 2) % 8 and both halves summed the same way.
+template <typename T>
+__device__ T leaf_sum(const T *a, int n) {
+  if (n < 8) {
+    T res = (T)0;
+    for (int i = 0; i < n; ++i) res += a[i];
+    return res;
+  }
+  T r[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) r[k] = a[k];
+  int i = 8;
+  for (; i <= n - 8; i += 8) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] += a[i + k];
+  }
+  T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) res += a[i];
+  return res;
+}
+
+// The recursion is walked leaf by leaf, left to right, without a call stack: `path` holds the turns from the root to the
+// current node (bit k set: the right half at depth k), a node's (offset, length) is found again by walking down from the
+// root, and the sums of left halves whose right half is still open wait in `left` -- a last-in first-out stack kept in
+// registers (shifted, never indexed by a run-time value: no scratch memory).  Any int n splits at most PW_DEPTH times.
+#define PW_DEPTH 25
+template <typename T>
+__device__ T numpy_pairwise_sum(const T *a, int n) {
+  T left[PW_DEPTH];
+  uint32_t path = 0;
+  int depth = 0, off = 0, len = n;
+  T v;
+  for (;;) {
+    while (len > 128) {  // down the left halves
+      int n2 = len / 2;
+      n2 -= n2 % 8;
+      len = n2;
+      ++depth;
+    }
+    v = leaf_sum(a + off, len);
+    while (depth > 0 && ((path >> (depth - 1)) & 1u)) {  // a right half done: add it to its left half, go up
+      v = left[0] + v;
+#pragma unroll
+      for (int k = 0; k < PW_DEPTH - 1; ++k) left[k] = left[k + 1];
+      path &= ~(1u << (depth - 1));
+      --depth;
+    }
+    if (depth == 0) break;
+#pragma unroll
+    for (int k = PW_DEPTH - 1; k > 0; --k) left[k] = left[k - 1];
+    left[0] = v;  // a left half done: keep its sum, go to its right half
+    path |= 1u << (depth - 1);
+    off = 0;
+    len = n;
+    for (int k = 0; k < depth; ++k) {
+      int n2 = len / 2;
+      n2 -= n2 % 8;
+      if ((path >> k) & 1u) { off += n2; len -= n2; }
+      else len = n2;
+    }
+  }
+  return v;
+}
+
+// utils/indexing.py:9-32 on float32 or float64 rows: the row sum in numpy's order and precision (a row whose sum is zero
+// in that order is NaN), np.argmax's first maximum with the first NaN winning.
+template <typename T>
+__global__ __launch_bounds__(256) void k_argmax_nonzero(const T *__restrict__ arr, int64_t F, int C,
                                                         double *__restrict__ out) {
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (f >= F) return;
-  const double *row = arr + f * C;
-  double best = row[0], sum = 0.0;
+  const T *row = arr + f * C;
+  T best = row[0];
   int arg = 0;
   bool bad = false;
   // np.argmax: first maximum; a NaN is "maximal" and the first NaN wins
   bool best_nan = isnan(best);
   for (int c = 0; c < C; ++c) {
-    const double x = row[c];
+    const T x = row[c];
     if (!isfinite(x)) bad = true;
-    sum += x;
     if (c > 0 && !best_nan) {
       if (isnan(x)) { best_nan = true; arg = c; }
       else if (x > best) { best = x; arg = c; }
     }
   }
-  out[f] = (bad || sum == 0.0) ? __longlong_as_double(0x7FF8000000000000ll) : (double)arg;
+  out[f] = (bad || numpy_pairwise_sum(row, C) == (T)0) ? __longlong_as_double(0x7FF8000000000000ll) : (double)arg;
 }
 
 }  // namespace
@@ -554,6 +626,7 @@ int gr_project_index_pairs(gr_ctx *c, const int32_t *ids, const double *img, int
   if (c->F <= 0) return fail(c, GR_ENOMESH, "gr_mesh_upload has not been called");
   if (!ids || !img || !counts || !keys || !key_count || n_classes <= 0 || key_cap < 0)
     return fail(c, GR_EINVAL, "bad sparse projection args");
+  if (n_classes > (1ll << 53)) return fail(c, GR_EINVAL, "n_classes %lld exceeds 2^53", (long long)n_classes);
   if (n_views == 0) return GR_OK;
   hipStream_t s = (hipStream_t)stream;
   GR_HIP(c, hipSetDevice(c->device));
@@ -698,13 +771,26 @@ int gr_finalize_sums_f64(gr_ctx *c, double *sums, const uint32_t *counts, int64_
   return GR_OK;
 }
 
-int gr_argmax_nonzero_f64(gr_ctx *c, const double *array, int64_t F, int C, double *out, void *stream) {
-  if (!c || !array || !out || F <= 0 || C <= 0) return fail(c, GR_EINVAL, "bad argmax args");
+int gr_argmax_nonzero(gr_ctx *c, const void *array, int dtype, int64_t F, int C, double *out, void *stream) {
+  if (!c) return GR_EINVAL;
+  if (F < 0 || C <= 0) return fail(c, GR_EINVAL, "bad argmax args");
+  if (dtype != GR_DTYPE_F32 && dtype != GR_DTYPE_F64) return fail(c, GR_EINVAL, "argmax dtype %d is not f32 / f64", dtype);
+  if (F == 0) return GR_OK;  // (an empty tensor's data pointer may be null)
+  if (!array || !out) return fail(c, GR_EINVAL, "bad argmax args");
   hipStream_t s = (hipStream_t)stream;
   GR_HIP(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(k_argmax_nonzero, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, array, F, C, out);
+  if (dtype == GR_DTYPE_F32)
+    hipLaunchKernelGGL(k_argmax_nonzero<float>, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, (const float *)array, F,
+                       C, out);
+  else
+    hipLaunchKernelGGL(k_argmax_nonzero<double>, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, (const double *)array,
+                       F, C, out);
   GR_HIP(c, hipGetLastError());
   return GR_OK;
+}
+
+int gr_argmax_nonzero_f64(gr_ctx *c, const double *array, int64_t F, int C, double *out, void *stream) {
+  return gr_argmax_nonzero(c, array, GR_DTYPE_F64, F, C, out, stream);
 }
 
 }  // extern "C"

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GR_VERSION 124 /* 0.2.4: gr_raster_overflow_causes; 0.2.3: the first launch group of an unknown (mesh, image size) is looked at before its tile kernel runs (gr_raster_stats.rebinned_groups); 0.2.2: micro lists (a fifth field in the learned-table file); 0.2.1: gr_learned_cache_clear; 0.2.0: gr_resize_image_f64, gr_learned_cache_file, mesh-signature keyed learned table */
+#define GR_VERSION 125 /* 0.2.5: gr_argmax_nonzero (float32 / float64 rows, numpy's pairwise row sum), F = 0 is an empty result; 0.2.4: gr_raster_overflow_causes; 0.2.3: the first launch group of an unknown (mesh, image size) is looked at before its tile kernel runs (gr_raster_stats.rebinned_groups); 0.2.2: micro lists (a fifth field in the learned-table file); 0.2.1: gr_learned_cache_clear; 0.2.0: gr_resize_image_f64, gr_learned_cache_file, mesh-signature keyed learned table */
 
 enum {
   GR_OK = 0,
@@ -255,7 +255,8 @@ int gr_gather_texture_u8(gr_ctx *ctx, const int32_t *ids, int64_t n_pix, const d
  * key_cap; pairs beyond it are dropped but still counted in *key_count).  Calls APPEND: the caller zeroes *key_count and may
  * collect the pairs of many calls in one buffer before counting them once (gr_count_pairs).  Synchronises `stream` and
  * returns GR_EINDEX when a value is outside [0, n_classes) -- unless GR_FLAG_DEFER_CHECK is set: then the call only enqueues
- * work, key_count must point to two 64-bit words (both zeroed by the caller) and such a value makes key_count[1] non-zero. */
+ * work, key_count must point to two 64-bit words (both zeroed by the caller) and such a value makes key_count[1] non-zero.
+ * A value v is a class index when -1 < v < n_classes (int(v) truncates); n_classes above 2^53 is GR_EINVAL. */
 int gr_project_index_pairs(gr_ctx *ctx, const int32_t *ids, const double *img, int n_views, int h, int w,
                            int64_t n_classes, uint32_t *counts, uint64_t *keys, int64_t key_cap, uint64_t *key_count,
                            int flags, void *stream);
@@ -316,8 +317,11 @@ int gr_finalize_votes(gr_ctx *ctx, const uint32_t *votes, const uint32_t *counts
 int gr_finalize_sums_f64(gr_ctx *ctx, double *sums_inout, const uint32_t *counts, int64_t F, int C, double *average,
                          double *counts_f64, void *stream);
 
-/* find_argmax_nonzero_value -- utils/indexing.py:9-32 on an F x C f64 array: argmax per row as f64, NaN when the
- * row sums to zero or holds a non-finite value. */
+/* find_argmax_nonzero_value -- utils/indexing.py:9-32 on an F x C C-contiguous array of dtype GR_DTYPE_F32 or
+ * GR_DTYPE_F64: argmax per row as f64 (the first maximum; the first NaN wins), NaN when the row holds a non-finite value
+ * or sums to zero -- summed in the array's own precision and in numpy's pairwise order (np.sum(array, axis=1)), so that
+ * the zero test agrees with numpy's bit for bit.  F = 0 is an empty result.  gr_argmax_nonzero_f64 is the f64 form. */
+int gr_argmax_nonzero(gr_ctx *ctx, const void *array, int dtype, int64_t F, int C, double *out, void *stream);
 int gr_argmax_nonzero_f64(gr_ctx *ctx, const double *array, int64_t F, int C, double *out, void *stream);
 
 #ifdef __cplusplus

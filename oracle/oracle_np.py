@@ -7,6 +7,7 @@ numpy restatement of the reference's numpy stages on the projection path, one fu
     aggregate                    geograypher/meshes/meshes.py:2044-2084
     inds_to_one_hot              geograypher/predictors/segmentor.py:37-69
     find_argmax_nonzero_value    geograypher/utils/indexing.py:9-32
+    numpy_row_sum                the order of the np.sum(array, axis=1) inside it
     get_image_size               geograypher/cameras/cameras.py:179-200
     view_parameters              geograypher/cameras/cameras.py:446-477
 
@@ -98,6 +99,41 @@ def find_argmax_nonzero_value(array, keepdims=False, axis=1):
     infinite_mask = np.any(~np.isfinite(array), axis=axis)
     argmax[np.logical_or(zero_sum_mask, infinite_mask)] = np.nan
     return argmax
+
+
+def _pairwise(row, t):
+    n = len(row)
+    if n < 8:
+        res = t(0.0)
+        for x in row:
+            res = t(res + x)
+        return res
+    if n <= 128:
+        r = [t(row[k]) for k in range(8)]
+        i = 8
+        while i + 8 <= n:
+            for k in range(8):
+                r[k] = t(r[k] + row[i + k])
+            i += 8
+        res = t(t(t(r[0] + r[1]) + t(r[2] + r[3])) + t(t(r[4] + r[5]) + t(r[6] + r[7])))
+        for x in row[i:]:
+            res = t(res + x)
+        return res
+    n2 = n // 2
+    n2 -= n2 % 8
+    return t(_pairwise(row[:n2], t) + _pairwise(row[n2:], t))
+
+
+def numpy_row_sum(row, dtype):
+    """np.sum(a, axis=1)[i] for one row of a C-contiguous (F, C) array of `dtype` (float32 / float64), restated in plain
+    Python: numpy's pairwise sum in the array's own precision -- fewer than 8 values are added one by one from zero; up to
+    128 go to eight accumulators r[k] += a[8i + k], combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the
+    n % 8 tail is added one by one; more are split at n2 = n / 2 - (n / 2) % 8 and both halves summed the same way.  The
+    reduction adds that to its initial zero (so an all -0.0 row sums to +0.0).  The order `find_argmax_nonzero_value`'s
+    zero test depends on and the device kernel reproduces."""
+    t = np.dtype(dtype).type
+    vals = [t(x) for x in row]
+    return t(t(0.0) + _pairwise(vals, t))
 
 
 def render_postprocess_uint8(rendered, null_value=0):

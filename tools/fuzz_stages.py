@@ -5,9 +5,9 @@ checker like the tests (the product never calls the oracle).
 
 Per seed: F faces, N views of h x w ids (piecewise-constant patches + noise, -1 background, faces missing), then
   project_view        (meshes.py:1987-2001: last pixel per face wins; -1 -> last face)            exact, NaN for NaN
-  project_values + finalize_sums (meshes.py:2057-2082: nansum, counts, average)                    rtol 1e-12 / exact counts
+  project_values + finalize_sums (meshes.py:2057-2082: nansum, counts, average)                    exact
   gather_texture, gather_texture_u8 (render_flat, save_renders epilogue)                             exact
-  argmax_nonzero      (utils/indexing.py:9-32)                                                       exact
+  argmax_nonzero      (utils/indexing.py:9-32; float64 / float32, C up to 300, sums that cancel)     exact
   project_index_pairs (derived_meshes.py:470-520: sparse (face, class) pairs)                       exact
   resize_image        (cameras.py:154-174: /255 + scikit-image resize; uint8 / float32 / float64)    1e-12 absolute
   warp_image          (utils/image.py:72-126: nearest / bilinear through a coordinate map)           exact / 1e-12
@@ -67,7 +67,7 @@ def one(hip, seed):
     rng = np.random.default_rng(seed)
     bad = []
     F = int(np.exp(rng.uniform(np.log(1), np.log(5000))))
-    n = int(rng.integers(1, 5))
+    n = int(rng.integers(1, 71)) if rng.random() < 0.1 else int(rng.integers(1, 5))  # sometimes past a 64-view launch group
     h, w = int(rng.integers(1, 120)), int(rng.integers(1, 160))
     C = int(rng.integers(1, 7))
     # the stage kernels take F from the context's mesh: a mesh of F degenerate faces stands in
@@ -98,10 +98,7 @@ def one(hip, seed):
         w_sum[w_cnt == 0] = np.nan
         with np.errstate(divide="ignore", invalid="ignore"):
             w_avg = w_sum / w_cnt[:, None]
-    with np.errstate(invalid="ignore"):
-        ok = (np.allclose(avg, w_avg, rtol=1e-12, atol=0, equal_nan=True) and
-              np.allclose(summed, w_sum, rtol=1e-12, atol=0, equal_nan=True) and same(counts, w_cnt))
-    if not ok:
+    if not (same(avg, w_avg) and same(summed, w_sum) and same(counts, w_cnt)):
         bad.append("project_values / finalize_sums")
     # gather
     tex = random_values(rng, (F, C)) * rng.choice([1.0, 100.0])
@@ -115,9 +112,15 @@ def one(hip, seed):
     if not np.array_equal(hip.gather_texture_u8(ids[0], tex, null_value=null).cpu().numpy(), f64.astype(np.uint8)):
         bad.append("gather_texture_u8")
     # argmax
-    arr = rng.integers(0, 4, (F, C)).astype(np.float64) * rng.choice([1.0, 0.5])
-    arr[rng.random((F, C)) < 0.05] = np.nan
+    Ca = int(rng.integers(1, 301)) if rng.random() < 0.5 else C
+    if rng.random() < 0.5:
+        arr = rng.integers(0, 4, (F, Ca)).astype(np.float64) * rng.choice([1.0, 0.5])
+    else:  # mixed signs that cancel: where the order of the row sum decides whether it is zero
+        arr = rng.integers(-3, 4, (F, Ca)) * rng.choice([0.1, 0.3, 1e-3])
+    arr[rng.random((F, Ca)) < 0.05] = np.nan
     arr[rng.random(F) < 0.2] = 0.0
+    if rng.random() < 0.3:
+        arr = arr.astype(np.float32)  # summed in float32, as numpy does
     if not same(hip.argmax_nonzero(arr).cpu().numpy(), np.asarray(oracle_np.find_argmax_nonzero_value(arr)).reshape(F)):
         bad.append("argmax_nonzero")
     # sparse index pairs
@@ -175,7 +178,7 @@ def one(hip, seed):
             bad.append(f"warp_image {wdt} {wshape} order {order} fill {fill}: {int(diff.sum())} values differ")
     elif not np.allclose(gotw, wantw, rtol=0, atol=1e-12 * max(1.0, float(np.abs(wantw).max())) if wdt == "float64" else 1e-5):
         bad.append(f"warp_image {wdt} {wshape} order 1: max |diff| {float(np.abs(gotw.astype(np.float64) - wantw).max()):.3e}")
-    return {"seed": seed, "F": F, "views": n, "image": f"{w}x{h}", "C": C, "resize": f"{dt} {wi}x{hi}->{wo}x{ho}"}, bad
+    return {"seed": seed, "F": F, "views": n, "image": f"{w}x{h}", "C": C, "argmax": f"{arr.dtype} C={Ca}", "resize": f"{dt} {wi}x{hi}->{wo}x{ho}"}, bad
 
 
 def main():
