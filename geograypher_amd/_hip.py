@@ -809,7 +809,12 @@ class HipRaster:
 
         Integer images with order 0 are gathered as integers (gr_warp_nearest_i32); everything else goes through the
         float64 kernel and is cast back to the input dtype by truncation like the reference's `.astype(initial_dtype)`.
-        numpy in -> numpy out, tensor in -> tensor out."""
+        A NaN or infinite sampling coordinate reads `fill_value`, in both orders.  numpy in -> numpy out, tensor in ->
+        tensor out.
+
+        reference_float_roundtrip=True (the reference's float rescale and truncation, bit for bit) exists in the int32
+        kernel only: order 0, an integer image within the int32 range, an integer fill value.  Every other combination
+        raises NotImplementedError instead of returning the exact gather under the flag's name."""
         torch = _torch()
         is_tensor = isinstance(input_image, torch.Tensor)
         img = input_image if is_tensor else np.asarray(input_image)
@@ -830,6 +835,9 @@ class HipRaster:
                 return torch.full_like(img.squeeze(), fill_value)
             return np.full_like(np.squeeze(img), fill_value=fill_value)
         small_int = is_int and -2**31 <= lo and hi < 2**31 and float(fill_value) == int(fill_value)
+        if reference_float_roundtrip and not (small_int and order == 0):
+            raise NotImplementedError("reference_float_roundtrip=True is reproduced only for order 0 on integer images "
+                                      "within the int32 range with an integer fill value")
         with torch.cuda.device(self.device) if self.device.type == "cuda" else _nullcontext():
             if small_int and order == 0:
                 src = self._dev(img, torch.int32)

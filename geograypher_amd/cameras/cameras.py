@@ -522,7 +522,8 @@ class PhotogrammetryCameraSet:
         reference_float_roundtrip: the reference pushes every image -- integer face-id images included -- through a
             float rescale to [0,1] and back before truncating to the input dtype (utils/image.py:102, 123), which
             returns ids that are off by one for a few percent of the pixels.  False (default) gathers integers exactly;
-            True reproduces the reference's arithmetic bit for bit (order 0).
+            True reproduces the reference's arithmetic bit for bit for `interpolation_order=0` on an integer image within
+            the int32 range with an integer `fill_value`, and raises NotImplementedError for every other combination.
         """
         dkey = self.distortion_key(camera.distortion_params, image_scale)
         if dkey not in self._maps_ideal_to_warped:  # a set without a lens model raises NotImplementedError here

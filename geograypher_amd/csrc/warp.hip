@@ -47,13 +47,14 @@ __global__ __launch_bounds__(256) void k_warp_f64(const double *__restrict__ in,
   double v;
   if (order == 0) {
     v = at(floor(mr + 0.5), floor(mc + 0.5));
+  } else if (!(isfinite(mr) && isfinite(mc))) {
+    v = fill;  // NaN and infinite coordinates (inf - floor(inf) is a NaN weight), as order 0 reads them
   } else {
     const double r0 = floor(mr), c0 = floor(mc);
     const double tr = mr - r0, tc = mc - c0;
     const double top = at(r0, c0) * (1.0 - tc) + at(r0, c0 + 1.0) * tc;
     const double bot = at(r0 + 1.0, c0) * (1.0 - tc) + at(r0 + 1.0, c0 + 1.0) * tc;
     v = top * (1.0 - tr) + bot * tr;
-    if (!(mr == mr) || !(mc == mc)) v = fill;  // NaN coordinates
   }
   out[i] = v;
 }

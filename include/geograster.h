@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GR_VERSION 125 /* 0.2.5: gr_argmax_nonzero (float32 / float64 rows, numpy's pairwise row sum), F = 0 is an empty result; 0.2.4: gr_raster_overflow_causes; 0.2.3: the first launch group of an unknown (mesh, image size) is looked at before its tile kernel runs (gr_raster_stats.rebinned_groups); 0.2.2: micro lists (a fifth field in the learned-table file); 0.2.1: gr_learned_cache_clear; 0.2.0: gr_resize_image_f64, gr_learned_cache_file, mesh-signature keyed learned table */
+#define GR_VERSION 126 /* 0.2.6: gr_warp_f64 order 1 reads `fill` at an infinite sampling coordinate (it wrote NaN); 0.2.5: gr_argmax_nonzero (float32 / float64 rows, numpy's pairwise row sum), F = 0 is an empty result; 0.2.4: gr_raster_overflow_causes; 0.2.3: the first launch group of an unknown (mesh, image size) is looked at before its tile kernel runs (gr_raster_stats.rebinned_groups); 0.2.2: micro lists (a fifth field in the learned-table file); 0.2.1: gr_learned_cache_clear; 0.2.0: gr_resize_image_f64, gr_learned_cache_file, mesh-signature keyed learned table */
 
 enum {
   GR_OK = 0,
@@ -283,7 +283,9 @@ int gr_count_pairs(gr_ctx *ctx, uint64_t *keys, int64_t n, uint64_t *unique_keys
 int gr_warp_nearest_i32(gr_ctx *ctx, const int32_t *in, int h_in, int w_in, const double *map_rows,
                         const double *map_cols, int h_out, int w_out, int32_t fill, int reference_float_roundtrip,
                         double value_min, double value_range, int32_t *out, void *stream);
-/* same for float64 images with C interleaved channels; order 0 (nearest) or 1 (bilinear). */
+/* same for float64 images with C interleaved channels; order 0 (nearest) or 1 (bilinear: the four taps at floor and
+ * floor + 1, each reading `fill` outside `in` -- scipy's "grid-constant").  In all three kernels a NaN or infinite
+ * coordinate reads `fill`. */
 int gr_warp_f64(gr_ctx *ctx, const double *in, int h_in, int w_in, int C, const double *map_rows, const double *map_cols,
                 int h_out, int w_out, int order, double fill, double *out, void *stream);
 

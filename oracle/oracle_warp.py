@@ -7,6 +7,9 @@ numpy/scipy restatement of the reference's distortion-warp stage (SURVEY.md sect
                                      mode "grid-constant"), clip, rescale back, truncate to the input dtype
     warp_exact                       the same resampling WITHOUT the float round trip (what the product returns by
                                      default: integers are gathered as integers)
+    sample_grid_constant, warp_total the "grid-constant" sampling of orders 0 / 1 in plain numpy, defined for every double
+                                     (NaN / infinite coordinates read the fill value); pinned to live scipy on finite
+                                     coordinates by tests/test_image_oracles.py
 
 PARITY STATUS: pinned.  tests/golden/reference_warp.npz holds outputs of the REAL flexible_inputs_warp (run with
 scikit-image 0.18.3 by tests/golden/make_golden_warp.py); tests/test_warp.py checks this restatement against them bit
@@ -54,6 +57,51 @@ def warp_exact(input_image, inverse_map, interpolation_order=0, fill_value=0.0):
     for ch in range(img3.shape[2]):
         out[:, :, ch] = _map_coordinates(img3[:, :, ch].astype(float), inverse_map, interpolation_order, float(fill_value))
     return np.squeeze(out.astype(img3.dtype))
+
+
+def sample_grid_constant(img2d, rows, cols, order, fill):
+    """scipy.ndimage.map_coordinates(mode="grid-constant", prefilter=False) for order 0 / 1 in plain numpy, defined for
+    EVERY double (scipy converts the coordinate to an integer, which is undefined for NaN, inf and beyond 2^63): nearest
+    is floor(x + 0.5); bilinear takes the four taps at floor and floor + 1 with weights 1 - t and t; every tap outside the
+    input reads `fill`; a non-finite coordinate reads `fill`.  float64 result of the coordinates' shape.  Pinned to live
+    scipy on finite coordinates by tests/test_image_oracles.py (order 0 bit for bit, order 1 to 1e-12)."""
+    img = np.asarray(img2d, dtype=np.float64)
+    assert img.ndim == 2 and order in (0, 1)
+    H, W = img.shape
+    rows, cols = np.broadcast_arrays(np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.float64))
+    fill = float(fill)
+    finite = np.isfinite(rows) & np.isfinite(cols)
+    r, c = np.where(finite, rows, 0.0), np.where(finite, cols, 0.0)
+
+    def tap(rr, cc):
+        ok = (rr >= 0) & (rr < H) & (cc >= 0) & (cc < W)
+        ri, ci = np.where(ok, rr, 0.0).astype(np.int64), np.where(ok, cc, 0.0).astype(np.int64)
+        return np.where(ok, img[ri, ci], fill)
+
+    with np.errstate(invalid="ignore", over="ignore"):  # inf * 0 of an infinite pixel is NaN, as in scipy
+        if order == 0:
+            out = tap(np.floor(r + 0.5), np.floor(c + 0.5))
+        else:
+            r0, c0 = np.floor(r), np.floor(c)
+            tr, tc = r - r0, c - c0
+            top = tap(r0, c0) * (1.0 - tc) + tap(r0, c0 + 1.0) * tc
+            bot = tap(r0 + 1.0, c0) * (1.0 - tc) + tap(r0 + 1.0, c0 + 1.0) * tc
+            out = top * (1.0 - tr) + bot * tr
+    return np.where(finite, out, fill)
+
+
+def warp_total(input_image, inverse_map, interpolation_order=0, fill_value=0.0):
+    """`warp_exact` through `sample_grid_constant`: the same result on finite coordinates (order 1: to rounding), and
+    `fill_value` where a coordinate is NaN or infinite."""
+    img3 = np.atleast_3d(input_image)
+    with np.errstate(invalid="ignore"):
+        if max(float(np.max(img3)), fill_value) - min(float(np.min(img3)), fill_value) == 0:
+            return np.full_like(np.squeeze(img3), fill_value=fill_value)
+    out = np.zeros(inverse_map.shape[1:] + (img3.shape[2],))
+    for ch in range(img3.shape[2]):
+        out[:, :, ch] = sample_grid_constant(img3[:, :, ch], inverse_map[0], inverse_map[1], interpolation_order, fill_value)
+    with np.errstate(invalid="ignore"):
+        return np.squeeze(out.astype(img3.dtype))
 
 
 def inside_mask(inverse_map, in_shape):
@@ -112,3 +160,16 @@ def newton_inverse_map(params, h, w, scale=1.0, iters=12, fill=-1.0, tol=1e-9):
     ok = (np.abs(fr - ti) < tol * max(h, w)) & (np.abs(fc - tj) < tol * max(h, w))
     ok &= (r >= 0) & (r <= h - 1) & (c >= 0) & (c <= w - 1)
     return np.stack([np.where(ok, r, fill), np.where(ok, c, fill)], axis=0)
+
+
+def forward_jacobian_det(params, h, w, scale=1.0):
+    """det d(forward_map_position) / d(row, col) on every pixel of the h x w ideal image, by central differences: positive
+    everywhere where the lens is one-to-one over the image (a fold-over has several inverses, and two Newton variants may
+    pick different ones)."""
+    r, c = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    e = 1e-3
+    ar, ac = forward_map_position(params, r + e, c, scale)
+    br, bc = forward_map_position(params, r - e, c, scale)
+    cr, cc = forward_map_position(params, r, c + e, scale)
+    dr, dc = forward_map_position(params, r, c - e, scale)
+    return ((ar - br) * (cc - dc) - (cr - dr) * (ac - bc)) / (4 * e * e)

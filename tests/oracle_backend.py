@@ -169,8 +169,18 @@ class OracleBackend:
         return torch.from_numpy(oracle_warp.newton_inverse_map(dict(params), h, w, image_scale, fill=fill))
 
     def warp_image(self, input_image, map_t, order=1, fill_value=0.0, reference_float_roundtrip=False):
-        fn = oracle_warp.flexible_inputs_warp_reference if reference_float_roundtrip else oracle_warp.warp_exact
-        return fn(np.asarray(input_image), map_t.numpy(), order, fill_value)
+        img = np.asarray(input_image)
+        if reference_float_roundtrip:
+            # the combinations HipRaster.warp_image reproduces, and its refusal of the others (the constant shortcut first)
+            lo, hi = min(float(np.min(img)), float(fill_value)), max(float(np.max(img)), float(fill_value))
+            small_int = (np.issubdtype(img.dtype, np.integer) or img.dtype == bool) and -2**31 <= lo and hi < 2**31 \
+                and float(fill_value) == int(fill_value)
+            if hi - lo != 0 and not (small_int and order == 0):
+                raise NotImplementedError("reference_float_roundtrip=True is reproduced only for order 0 on integer images "
+                                          "within the int32 range with an integer fill value")
+            return oracle_warp.flexible_inputs_warp_reference(img, map_t.numpy(), order, fill_value)
+        # warp_total: warp_exact (scipy) restated so that NaN / infinite coordinates read the fill value, as the kernels do
+        return oracle_warp.warp_total(img, map_t.numpy(), order, fill_value)
 
     def argmax_nonzero(self, array):
         return torch.from_numpy(oracle_np.find_argmax_nonzero_value(np.asarray(array)))

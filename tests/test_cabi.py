@@ -19,15 +19,15 @@ def test_header_and_binding_agree():
     assert _declared_symbols() == sorted(_hip.EXPORTED_SYMBOLS)
 
 
-def test_library_exports_every_declared_symbol_at_header_version_125():
-    """Every declared symbol is exported, and the library reports the version the header declares (125: the ABI that added
-    gr_argmax_nonzero) -- a stale build or a header bumped without the library fails here."""
+def test_library_exports_every_declared_symbol_at_header_version_126():
+    """Every declared symbol is exported, and the library reports the version the header declares (126: gr_warp_f64 reads
+    `fill` at infinite coordinates) -- a stale build or a header bumped without the library fails here."""
     lib = ctypes.CDLL(str(_hip.library_path()))
     for name in _declared_symbols():
         assert hasattr(lib, name), f"libgeograster.so does not export {name}"
     header = int(re.search(r"#define GR_VERSION (\d+)", (ROOT / "include" / "geograster.h").read_text()).group(1))
     lib.gr_version.restype = ctypes.c_int
-    assert lib.gr_version() == header == 125
+    assert lib.gr_version() == header == 126
 
 
 def _header_struct(name):

@@ -10,7 +10,10 @@ Per seed: F faces, N views of h x w ids (piecewise-constant patches + noise, -1 
   argmax_nonzero      (utils/indexing.py:9-32; float64 / float32, C up to 300, sums that cancel)     exact
   project_index_pairs (derived_meshes.py:470-520: sparse (face, class) pairs)                       exact
   resize_image        (cameras.py:154-174: /255 + scikit-image resize; uint8 / float32 / float64)    1e-12 absolute
-  warp_image          (utils/image.py:72-126: nearest / bilinear through a coordinate map)           exact / 1e-12
+  warp_image          (utils/image.py:72-126: nearest / bilinear through a coordinate map, NaN / inf coordinates included)
+                                                                                                     exact / 1e-12
+  invert_distortion   (cameras.py:1045-1062 as a dense Newton solve; random one-to-one lenses)       same mask, 1e-8 px,
+                                                                                                     round trip 1e-9 max(h, w)
 on images with NaN / inf / negative zeros / out-of-range values where the reference's code admits them."""
 import json
 import sys
@@ -138,8 +141,10 @@ def one(hip, seed):
             bad.append("project_index_pairs")
     # resize
     hi, wi = int(rng.integers(1, 200)), int(rng.integers(1, 260))
+    if rng.random() < 0.15:  # a single row or a single column
+        hi, wi = (1, wi) if rng.random() < 0.5 else (hi, 1)
     ho, wo = max(1, int(hi * np.exp(rng.uniform(np.log(0.05), np.log(2.0))))), max(1, int(wi * np.exp(rng.uniform(np.log(0.05), np.log(2.0)))))
-    Cr = int(rng.choice([0, 1, 3, 4]))
+    Cr = int(rng.choice([0, 1, 2, 3, 4, 5]))
     shape = (hi, wi) if Cr == 0 else (hi, wi, Cr)
     dt = rng.choice(["uint8", "float32", "float64"])
     raw = rng.integers(0, 256, shape).astype(np.uint8) if dt == "uint8" else (rng.normal(0, 1, shape) * 50).astype(dt)
@@ -158,6 +163,9 @@ def one(hip, seed):
     m = np.stack([rr + rng.normal(0, 1, rr.shape) * rng.choice([0.0, 0.3, 3.0]), cc + rng.normal(0, 1, cc.shape) * rng.choice([0.0, 0.3, 3.0])])
     snap = rng.random(m.shape) < 0.3
     m = np.where(snap, np.round(m * 2) / 2, m)  # integers and exact halves
+    if rng.random() < 0.5:  # coordinates no integer conversion survives: they read the fill value, in both orders
+        wild = np.array([np.nan, np.inf, -np.inf, 1e300, -1e300, 2.0**31, -(2.0**63)])
+        m = np.where(rng.random(m.shape) < 0.05, wild[rng.integers(0, wild.size, m.shape)], m)
     wdt = rng.choice(["int32", "int64", "uint8", "float64", "float32"])
     wshape = (hs, ws) if rng.random() < 0.6 else (hs, ws, int(rng.integers(1, 4)))
     wimg = rng.integers(-5 if "int" in wdt and wdt != "uint8" else 0, 200, wshape).astype(wdt) if "float" not in wdt else rng.normal(0, 10, wshape).astype(wdt)
@@ -165,7 +173,7 @@ def one(hip, seed):
     fill = float(rng.choice([0, -1, 7])) if wdt != "uint8" else float(rng.choice([0, 7]))
     mt = hip.upload_map(m)
     gotw = hip.warp_image(wimg, mt, order=order, fill_value=fill)
-    wantw = oracle_warp.warp_exact(wimg, m, order, fill)
+    wantw = oracle_warp.warp_total(wimg, m, order, fill)  # warp_exact (scipy), defined for every double
     gotw = np.asarray(gotw)
     if gotw.shape != wantw.shape or gotw.dtype != wantw.dtype:
         bad.append(f"warp_image {wdt} order {order}: shape/dtype {gotw.shape} {gotw.dtype} vs {wantw.shape} {wantw.dtype}")
@@ -178,7 +186,32 @@ def one(hip, seed):
             bad.append(f"warp_image {wdt} {wshape} order {order} fill {fill}: {int(diff.sum())} values differ")
     elif not np.allclose(gotw, wantw, rtol=0, atol=1e-12 * max(1.0, float(np.abs(wantw).max())) if wdt == "float64" else 1e-5):
         bad.append(f"warp_image {wdt} {wshape} order 1: max |diff| {float(np.abs(gotw.astype(np.float64) - wantw).max()):.3e}")
-    return {"seed": seed, "F": F, "views": n, "image": f"{w}x{h}", "C": C, "argmax": f"{arr.dtype} C={Ca}", "resize": f"{dt} {wi}x{hi}->{wo}x{ho}"}, bad
+    # lens inverse (cameras.py:1045-1062 replaced by a dense Newton solve): a random lens of photogrammetric magnitudes, made
+    # milder until it is one-to-one over the image (a fold-over has several inverses); same valid mask and 1e-8 px against the
+    # numpy solver, and forward(inverse(p)) = p within the kernel's acceptance bound
+    Hl, Wl = int(np.exp(rng.uniform(0, np.log(300)))), int(np.exp(rng.uniform(0, np.log(300))))
+    ls = float(rng.choice([1.0, 1.0 + 1e-6, 1.0 + 2e-5, 0.5, 0.37, 2.0]))
+    hl, wl = max(1, int(Hl * ls)), max(1, int(Wl * ls))
+    mags = {"k1": 0.09, "k2": 0.08, "k3": 0.12, "k4": 0.08, "p1": 3e-3, "p2": 2e-3, "b1": 0.5, "b2": 0.3}
+    coeffs = {k: float(v * rng.uniform(-1, 1)) for k, v in mags.items() if rng.random() < 0.7}
+    lens = {"f": float(max(Hl, Wl) * rng.uniform(0.7, 2.0)), "cx": float(rng.uniform(-3, 3)), "cy": float(rng.uniform(-3, 3)),
+            "image_width": Wl, "image_height": Hl, **coeffs}
+    while oracle_warp.forward_jacobian_det(lens, hl, wl, ls).min() <= 0.1:
+        lens.update({k: 0.5 * lens[k] for k in coeffs})
+    lfill = float(rng.choice([-1.0, 0.0, np.nan]))
+    goti = hip.invert_distortion(lens, hl, wl, ls, fill=lfill).cpu().numpy()
+    wanti = oracle_warp.newton_inverse_map(lens, hl, wl, ls, fill=-1.0)
+    okl = wanti[0] != -1.0
+    ti, tj = np.meshgrid(np.arange(hl), np.arange(wl), indexing="ij")
+    fr, fc = oracle_warp.forward_map_position(lens, goti[0], goti[1], ls)
+    if not np.array_equal(goti[:, ~okl], np.full((2, int((~okl).sum())), lfill), equal_nan=True):
+        bad.append(f"invert_distortion {lens} {hl}x{wl} scale {ls}: valid masks differ")
+    elif okl.any() and not (np.abs(goti - wanti)[:, okl].max() <= 1e-8 and
+                            max(np.abs(fr - ti)[okl].max(), np.abs(fc - tj)[okl].max()) < 1e-9 * max(hl, wl)):
+        bad.append(f"invert_distortion {lens} {hl}x{wl} scale {ls}: max |diff| {np.abs(goti - wanti)[:, okl].max():.3e}, "
+                   f"round trip {max(np.abs(fr - ti)[okl].max(), np.abs(fc - tj)[okl].max()):.3e}")
+    return {"seed": seed, "F": F, "views": n, "image": f"{w}x{h}", "C": C, "argmax": f"{arr.dtype} C={Ca}",
+            "resize": f"{dt} {wi}x{hi}->{wo}x{ho}", "lens": f"{wl}x{hl} scale {ls}"}, bad
 
 
 def main():
