@@ -52,6 +52,9 @@ EXPORTED_SYMBOLS = (
     "gr_project_index_pairs",
     "gr_project_rect_pairs",
     "gr_count_pairs",
+    "gr_ray_pairs",
+    "gr_ray_pairs_tile",
+    "gr_rays_clip",
     "gr_warp_nearest_i32",
     "gr_warp_f64",
     "gr_invert_distortion_f64",
@@ -159,6 +162,12 @@ def load_library() -> ctypes.CDLL:
     lib.gr_project_rect_pairs.argtypes = [vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, i64, vp, i32, vp]
     lib.gr_count_pairs.restype = i32
     lib.gr_count_pairs.argtypes = [vp, vp, i64, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
+    lib.gr_ray_pairs.restype = i32
+    lib.gr_ray_pairs.argtypes = [vp, vp, vp, vp, i64, f64, vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64), vp]
+    lib.gr_ray_pairs_tile.restype = i32
+    lib.gr_ray_pairs_tile.argtypes = [i64, i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    lib.gr_rays_clip.restype = i32
+    lib.gr_rays_clip.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.gr_warp_nearest_i32.restype = i32
     lib.gr_warp_nearest_i32.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, ctypes.c_int32, i32, f64, f64, vp, vp]
     lib.gr_warp_f64.restype = i32
@@ -636,6 +645,88 @@ class HipRaster:
         """Sparse index aggregation over MANY views with the (face, class) pair keys kept on the device: `add(ids, img)` per
         view (or group of views) only enqueues work, `finish()` sorts and counts the pairs ONCE -- see `PairAccumulator`."""
         return PairAccumulator(self, n_classes, counts, neg1_is_last_face)
+
+    # -- multiview detections: ray-pair graph, boundary clip -------------------------------------------------------
+    CLIP_TRIANGLE_LIMIT = 65536  # triangles per gr_rays_clip call
+
+    def ray_pair_count(self, starts, ends, ray_ids, threshold: float) -> int:
+        """Number of edges `ray_pair_edges` would return (gr_ray_pairs with no edge buffer: the count alone)."""
+        torch = _torch()
+        s_t, e_t, id_t = self._ray_inputs(starts, ends, ray_ids)
+        total = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gr_ray_pairs(self._ctx, s_t.data_ptr(), e_t.data_ptr(), id_t.data_ptr(), int(s_t.shape[0]),
+                                       float(threshold), None, None, None, 0, ctypes.byref(total), self._stream())
+        self._check(rc, "gr_ray_pairs")
+        return int(total.value)
+
+    def ray_pair_edges(self, starts, ends, ray_ids, threshold: float, capacity: Optional[int] = None):
+        """The ray-pair graph of calc_graph_weights (utils/numeric.py:428-498) before its host steps: starts, ends (N, 3)
+        float64, ray_ids (N,) int (the image of each ray) -> (i, j, dist): int32, int32, float64 tensors of every pair
+        i < j from different images whose clamped segment distance is <= threshold, sorted by (i, j).  Count-then-fill inside:
+        the first call offers `capacity` edge slots (default max(8 N, 65536)); when the library reports more
+        (`last_ray_pair_calls` == 2) the buffers are allocated at that total and the call repeated: the quadratic kernel then
+        runs twice, so pass `capacity` where the number of edges is roughly known.  The library synchronises the stream: the
+        result is complete on return."""
+        torch = _torch()
+        s_t, e_t, id_t = self._ray_inputs(starts, ends, ray_ids)
+        n = int(s_t.shape[0])
+        cap = max(8 * n, 1 << 16) if capacity is None else int(capacity)
+        total = ctypes.c_int64(0)
+        self.last_ray_pair_calls = 0
+        for _attempt in range(2):
+            ei = torch.empty((max(cap, 1),), dtype=torch.int32, device=self.device)
+            ej = torch.empty((max(cap, 1),), dtype=torch.int32, device=self.device)
+            ed = torch.empty((max(cap, 1),), dtype=torch.float64, device=self.device)
+            with torch.cuda.device(self.device):
+                rc = self.lib.gr_ray_pairs(self._ctx, s_t.data_ptr(), e_t.data_ptr(), id_t.data_ptr(), n, float(threshold),
+                                           ei.data_ptr() if cap else None, ej.data_ptr() if cap else None,
+                                           ed.data_ptr() if cap else None, cap, ctypes.byref(total), self._stream())
+            self.last_ray_pair_calls += 1
+            m = int(total.value)
+            if rc == GR_EOVERFLOW or (rc == GR_OK and cap == 0 and m > 0):
+                cap = m   # the library counted every edge: the repeat fits exactly
+                continue
+            self._check(rc, "gr_ray_pairs")
+            return ei[:m], ej[:m], ed[:m]
+        self._check(rc, "gr_ray_pairs")
+        raise RuntimeError("gr_ray_pairs reported two different edge totals for the same input")
+
+    def _ray_inputs(self, starts, ends, ray_ids):
+        torch = _torch()
+        s_t = self._dev(starts, torch.float64)
+        e_t = self._dev(ends, torch.float64)
+        id_t = self._dev(ray_ids, torch.int32)
+        if s_t.ndim != 2 or s_t.shape[1] != 3 or s_t.shape != e_t.shape:
+            raise ValueError(f"starts and ends must both be (N, 3), got {tuple(s_t.shape)} and {tuple(e_t.shape)}")
+        if id_t.ndim != 1 or id_t.shape[0] != s_t.shape[0]:
+            raise ValueError(f"{s_t.shape[0]} rays need {s_t.shape[0]} ray ids, got shape {tuple(id_t.shape)}")
+        return s_t, e_t, id_t
+
+    def clip_rays(self, origins, directions, points, faces):
+        """Nearest intersection (t >= 0) of every ray with a small triangle mesh (gr_rays_clip; a boundary surface of
+        clip_line_segments, utils/geometric.py:210-222): origins, directions (N, 3) float64, points (V, 3) float64, faces (F, 3)
+        int -> (hit bool (N,), t float64 (N,), hit points float64 (N, 3); NaN where nothing is hit).  More than
+        CLIP_TRIANGLE_LIMIT triangles is a ValueError."""
+        torch = _torch()
+        o_t = self._dev(origins, torch.float64)
+        d_t = self._dev(directions, torch.float64)
+        p_t = self._dev(points, torch.float64)
+        f_t = self._dev(faces, torch.int32)
+        if o_t.ndim != 2 or o_t.shape[1] != 3 or o_t.shape != d_t.shape:
+            raise ValueError(f"origins and directions must both be (N, 3), got {tuple(o_t.shape)} and {tuple(d_t.shape)}")
+        if p_t.ndim != 2 or p_t.shape[1] != 3 or f_t.ndim != 2 or f_t.shape[1] != 3:
+            raise ValueError(f"boundary must be (V, 3) points and (F, 3) faces, got {tuple(p_t.shape)} and {tuple(f_t.shape)}")
+        n = int(o_t.shape[0])
+        hit = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        t = torch.full((n,), float("nan"), dtype=torch.float64, device=self.device)
+        pts = torch.full((n, 3), float("nan"), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gr_rays_clip(self._ctx, o_t.data_ptr(), d_t.data_ptr(), n, p_t.data_ptr(), int(p_t.shape[0]),
+                                       f_t.data_ptr(), int(f_t.shape[0]), hit.data_ptr(), t.data_ptr(), pts.data_ptr(),
+                                       self._stream())
+        self._check(rc, "gr_rays_clip")
+        return hit.to(torch.bool), t, pts
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):

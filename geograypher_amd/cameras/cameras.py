@@ -206,6 +206,28 @@ class PhotogrammetryCamera:
         """reference: cameras.py:311-326"""
         return self._local_to_epsg_4978_transform
 
+    def cast_rays(self, pixel_coords_ij: np.ndarray, line_length: float = 10):
+        """Rays from the camera centre through pixels (reference: cameras.py:574-628): pixel_coords_ij (n, 2) (i, j) pixel
+        coordinates -> (2 n, 3) points in the local frame, alternating start (the camera centre) and end rows, every segment
+        `line_length` long in camera units; None when there are no pixels.  The principal point is
+        (image_width / 2 + cx, image_height / 2 + cy); a homogeneous scale in the transform's [3, 3] is divided out."""
+        pixel_coords_xy = np.flip(np.asarray(pixel_coords_ij), axis=1)
+        principal_point = np.array([[self.image_width / 2.0 + self.cx, self.image_height / 2.0 + self.cy]])
+        scaled = (pixel_coords_xy - principal_point) / self.f
+        n_points = len(scaled)
+        if n_points == 0:
+            return None
+        homogeneous = np.concatenate([scaled, np.ones((n_points, 1))], axis=1)
+        ends = homogeneous / np.linalg.norm(homogeneous, axis=1, keepdims=True) * line_length
+        line_verts = np.zeros((2 * n_points, 4))
+        line_verts[:, 3] = 1
+        line_verts[1::2, :3] = ends
+        transform = np.asarray(self.cam_to_world_transform, dtype=np.float64)
+        projected = transform @ line_verts.T
+        if transform[3, 3] != 1.0:
+            projected = projected / transform[3, 3]
+        return projected[:3, :].T
+
     # -- view ----------------------------------------------------------------------------------------------------
     def get_view_parameters(self, focal_dist: float = 10) -> dict:
         """The numbers the reference loads into a pyvista camera (cameras.py:446-477): position, focal point,
@@ -429,6 +451,110 @@ class PhotogrammetryCameraSet:
             [cam.get_raster_record(image_scale, nr, principal_point, origin, focal_scaling)
              for cam, nr in zip(self.cameras, nears)], axis=0
         )
+
+    # -- multiview detections (reference: cameras.py:1275-1398, 1483-1608) -------------------------------------------
+    def calc_line_segments(self, detector, boundaries=None, ray_length_local: float = 1e3, out_dir: Optional[PATH_TYPE] = None,
+                           limit_ray_length_local: Optional[float] = None, limit_angle_from_vert: Optional[float] = None,
+                           backend=None):
+        """One ray per detection centre of every image (cameras.py:1483-1608): `detector.get_detection_centers(filename)` ->
+        `cast_rays` -> optional filter by the angle from the vertical (radians) -> optional clip between two boundary surfaces
+        ((points, faces) pairs; `clip_line_segments`, on the device).  Returns {"ray_starts", "ray_ends", "ray_IDs"} or, with
+        `out_dir`, the path of the `line_segments.npz` saved there."""
+        from geograypher_amd.utils.geometric import clip_line_segments
+
+        all_line_segments, all_image_IDs = [], []
+        for camera_ind in range(len(self.cameras)):
+            centers = detector.get_detection_centers(str(self.get_image_filename(camera_ind)))
+            if len(centers) > 0:
+                line_segments = self.cameras[camera_ind].cast_rays(pixel_coords_ij=centers, line_length=ray_length_local)
+                all_line_segments.append(line_segments)
+                all_image_IDs.append(np.full(int(line_segments.shape[0] / 2), fill_value=camera_ind))
+        if len(all_line_segments) > 0:
+            all_line_segments = np.concatenate(all_line_segments, axis=0)
+            all_image_IDs = np.concatenate(all_image_IDs, axis=0)
+            ray_starts, ray_ends = all_line_segments[0::2], all_line_segments[1::2]
+            ray_directions = ray_ends - ray_starts
+            ray_directions = ray_directions / np.linalg.norm(ray_directions, axis=1, keepdims=True)
+            if limit_angle_from_vert is not None:
+                keep_mask = np.arccos(np.abs(ray_directions[:, 2])) <= limit_angle_from_vert
+                ray_starts, ray_ends = ray_starts[keep_mask], ray_ends[keep_mask]
+                ray_directions, all_image_IDs = ray_directions[keep_mask], all_image_IDs[keep_mask]
+            if boundaries is not None:
+                ray_starts, ray_ends, ray_directions, all_image_IDs = clip_line_segments(
+                    boundaries=boundaries, origins=ray_starts, directions=ray_directions, image_indices=all_image_IDs,
+                    ray_limit=limit_ray_length_local, backend=backend)
+        else:
+            ray_starts, ray_ends = np.empty((0, 3)), np.empty((0, 3))
+            all_image_IDs = np.empty((0,), dtype=int)
+        data = {"ray_starts": ray_starts, "ray_ends": ray_ends, "ray_IDs": all_image_IDs}
+        if out_dir is None:
+            return data
+        path = Path(out_dir) / "line_segments.npz"
+        np.savez(path, **data)
+        return path
+
+    def triangulate_detections(self, detector, ray_length_meters: float = 1e3, boundaries=None,
+                               limit_ray_length_meters: Optional[float] = None, limit_angle_from_vert: Optional[float] = None,
+                               similarity_threshold_meters: float = 0.1, transform=None, louvain_resolution: float = 1.0,
+                               out_dir: Optional[PATH_TYPE] = None, seed=None, backend=None) -> np.ndarray:
+        """Per-image detections -> 3D locations (cameras.py:1275-1398): rays through the detection centres
+        (`calc_line_segments`), the graph of rays from different images that pass within `similarity_threshold_meters` of each
+        other (`calc_graph_weights`: the ray-pair kernel on the device), Louvain communities and one point per community
+        (`calc_communities`).  Lengths in metres are scaled to local units by the local -> EPSG:4978 transform.  With `out_dir`
+        each stage saves its file there (`line_segments.npz`, `edge_weights.json`, `communities.npz`) and a stage whose file
+        exists is not computed again.  Returns (M, 3): lat / lon / alt when a transform and pyproj are at hand, local
+        coordinates otherwise.  Beyond the reference's keywords: `seed` (Louvain) and `backend` (the device backend)."""
+        from geograypher_amd.utils.geometric import get_scale_from_transform
+        from geograypher_amd.utils.numeric import calc_communities, calc_graph_weights
+
+        if out_dir is not None:
+            out_dir = Path(out_dir)
+
+        def check_exists(file):
+            if out_dir is None:
+                return False
+            if isinstance(file, str):
+                return (out_dir / file).is_file()
+            return isinstance(file, Path) and file.is_file()
+
+        transform_to_epsg_4978 = self.get_local_to_epsg_4978_transform()
+        meters_to_local_scale = 1 / get_scale_from_transform(transform_to_epsg_4978)
+        ray_length_local = ray_length_meters * meters_to_local_scale
+        similarity_threshold_local = similarity_threshold_meters * meters_to_local_scale
+        limit_ray_length_local = None if limit_ray_length_meters is None else limit_ray_length_meters * meters_to_local_scale
+
+        if check_exists("line_segments.npz"):
+            line_results = out_dir / "line_segments.npz"
+        else:
+            line_results = self.calc_line_segments(
+                detector=detector, boundaries=boundaries, ray_length_local=ray_length_local, out_dir=out_dir,
+                limit_ray_length_local=limit_ray_length_local, limit_angle_from_vert=limit_angle_from_vert, backend=backend)
+        if check_exists(line_results):
+            with np.load(line_results) as d:
+                line_results = {k: d[k] for k in d.files}
+
+        if check_exists("edge_weights.json"):
+            weight_results = out_dir / "edge_weights.json"
+        else:
+            weight_results = calc_graph_weights(
+                starts=line_results["ray_starts"], ends=line_results["ray_ends"], ray_IDs=line_results["ray_IDs"],
+                similarity_threshold=similarity_threshold_local, out_dir=out_dir, step=5000, transform=transform,
+                backend=backend)
+        if check_exists(weight_results):
+            with weight_results.open("r") as file:
+                weight_results = json.load(file)
+
+        if check_exists("communities.npz"):
+            community_results = out_dir / "communities.npz"
+        else:
+            community_results = calc_communities(
+                starts=line_results["ray_starts"], ends=line_results["ray_ends"], edge_weights=weight_results,
+                louvain_resolution=louvain_resolution, out_dir=out_dir, transform_to_epsg_4978=transform_to_epsg_4978,
+                seed=seed)
+        if check_exists(community_results):
+            with np.load(community_results) as d:
+                community_results = {k: d[k] for k in d.files}
+        return community_results.get("community_points_latlon", community_results["community_points"])
 
     # -- distortion (the warp stage itself is the "next" row f1 of SURVEY.md section 8) -------------------------------
     def distortion_key(self, parameters: Dict[str, float], image_scale: float = 1.0) -> str:

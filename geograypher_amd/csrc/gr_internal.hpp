@@ -8,6 +8,7 @@
 //   project.hip      winners, votes, gathers, sparse pairs, finalize, argmax + their entry points
 //   warp.hip         distortion warp, lens inversion (row f1)
 //   resize.hip       photo down-scale of get_image (anti-aliased resize)
+//   rays.hip         multiview detections: ray-pair graph (k_ray_prep, k_ray_pairs + radix sort), ray / boundary clip; no mesh needed
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 

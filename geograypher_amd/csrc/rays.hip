@@ -1,0 +1,351 @@
+// geograypher_amd/csrc/rays.hip -- the multiview-detection workflow's device side: the ray-pair graph (clamped segment-to-segment
+// distance of every pair of rays from different images, kept when within a threshold) and the clip of rays against a small
+// boundary mesh.  Needs no uploaded mesh.  Everything is float64 and, like the rest of the library, compiled without
+// contraction: the exact `denom == 0` test for parallel rays relies on a1 * b2 - a2 * b1 of two identical directions being
+// exactly zero, which a fused multiply-add would break.
+#include <hipcub/hipcub.hpp>
+
+#include "gr_internal.hpp"
+
+using namespace grimpl;
+
+#define GR_RAY_TILE 256            // rays per side of a tile = threads of a workgroup (4 waves)
+#define GR_RAY_MAX_N (1 << 23)     // rays per call: 32768 tiles a side, 536 887 296 tiles of the upper triangle
+#define GR_RAY_MAX_GRID (1 << 20)  // workgroups of k_ray_pairs: beyond that many tiles a workgroup strides over several (2^28 threads a launch)
+#define GR_CLIP_CHUNK 128          // triangles staged in LDS at a time by k_rays_clip
+#define GR_CLIP_MAX_TRIANGLES 65536
+
+namespace {
+
+// what k_ray_prep derives per ray, once: 64 bytes, the unit of the B tile in LDS
+struct RayRec {
+  double sx, sy, sz;   // start
+  double ux, uy, uz;   // (end - start) / mag: NaN for a zero-length segment (0 / 0), which therefore meets no threshold
+  double mag;          // |end - start|
+  int32_t id;          // image the ray came from
+  int32_t pad;
+};
+
+// Tile (row, col), row <= col, of linear index k in the row-major upper triangle of a T x T grid of tiles.  Row r starts at
+// off(r) = r T - r (r - 1) / 2.  The double-precision estimate is corrected with 64-bit integers, so the decode is exact for every T
+// the ray limit allows ((2 T + 1)^2 < 2^53, off < 2^63).
+__host__ __device__ inline int64_t tri_off(int64_t r, int64_t T) { return r * T - r * (r - 1) / 2; }
+__host__ __device__ inline void tri_decode(int64_t k, int64_t T, int64_t &row, int64_t &col) {
+  const double b = 2.0 * (double)T + 1.0;
+  int64_t r = (int64_t)((b - sqrt(b * b - 8.0 * (double)k)) * 0.5);
+  if (r < 0) r = 0;
+  if (r > T - 1) r = T - 1;
+  while (r + 1 < T && tri_off(r + 1, T) <= k) ++r;
+  while (r > 0 && tri_off(r, T) > k) --r;
+  row = r;
+  col = r + (k - tri_off(r, T));
+}
+
+// np.clip(x, 0, hi) as far as the result can matter: a NaN x stays NaN (a NaN `hi` comes with NaN directions, which make
+// every point NaN anyway)
+__device__ __forceinline__ double clip0(double x, double hi) {
+  x = x < 0.0 ? 0.0 : x;
+  return x > hi ? hi : x;
+}
+
+__device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
+  return (ax * bx + ay * by) + az * bz;
+}
+
+// Distance between the closest points of segment A (this lane's ray) and segment B, both clamped to their segments.
+// Non-parallel rays: the closest points of the two infinite lines are at parameters t0 = det(t, uB, n) / |n|^2 along A and
+// t1 = det(t, uA, n) / |n|^2 along B, n = uA x uB, t = b0 - a0; a parameter outside [0, mag] is clamped, and then the OTHER
+// point is the projection of the clamped one onto its segment: first B from the clamped A, then A from the updated B.
+// Parallel rays (|n|^2 exactly 0): B's end points are projected on A's axis (d0, d1, measured from a0); B wholly before a0 or
+// wholly behind a1 pairs that end of A with B's nearer end, otherwise A's point is d0 clamped and B's the foot of the
+// perpendicular.  `ends` is read in the parallel case only.
+__device__ __forceinline__ double segment_distance(const RayRec &a, const RayRec &b, const double *__restrict__ ends,
+                                                   int64_t i, int64_t j) {
+  const double cx = a.uy * b.uz - a.uz * b.uy, cy = a.uz * b.ux - a.ux * b.uz, cz = a.ux * b.uy - a.uy * b.ux;
+  const double cn = sqrt((cx * cx + cy * cy) + cz * cz);
+  double denom = cn * cn;
+  const bool parallel = denom == 0.0;
+  if (parallel) denom = 1.0;
+  const double tx = b.sx - a.sx, ty = b.sy - a.sy, tz = b.sz - a.sz;
+  const double detA = dot3(ty * b.uz - tz * b.uy, tz * b.ux - tx * b.uz, tx * b.uy - ty * b.ux, cx, cy, cz);
+  const double detB = dot3(ty * a.uz - tz * a.uy, tz * a.ux - tx * a.uz, tx * a.uy - ty * a.ux, cx, cy, cz);
+  const double t0 = detA / denom, t1 = detB / denom;
+  const double t0c = clip0(t0, a.mag), t1c = clip0(t1, b.mag);
+  double pax = a.sx + t0c * a.ux, pay = a.sy + t0c * a.uy, paz = a.sz + t0c * a.uz;
+  double pbx = b.sx + t1c * b.ux, pby = b.sy + t1c * b.uy, pbz = b.sz + t1c * b.uz;
+  const bool oob_a = (t0 < 0.0) | (t0 > a.mag), oob_b = (t1 < 0.0) | (t1 > b.mag);
+  {
+    const double d = clip0(dot3(pax - b.sx, pay - b.sy, paz - b.sz, b.ux, b.uy, b.uz), b.mag);
+    const double qx = b.sx + d * b.ux, qy = b.sy + d * b.uy, qz = b.sz + d * b.uz;
+    pbx = oob_a ? qx : pbx; pby = oob_a ? qy : pby; pbz = oob_a ? qz : pbz;
+  }
+  {
+    const double d = clip0(dot3(pbx - a.sx, pby - a.sy, pbz - a.sz, a.ux, a.uy, a.uz), a.mag);
+    const double qx = a.sx + d * a.ux, qy = a.sy + d * a.uy, qz = a.sz + d * a.uz;
+    pax = oob_b ? qx : pax; pay = oob_b ? qy : pay; paz = oob_b ? qz : paz;
+  }
+  if (parallel) {
+    const double b1x = ends[3 * j], b1y = ends[3 * j + 1], b1z = ends[3 * j + 2];
+    const double base = dot3(a.ux, a.uy, a.uz, a.sx, a.sy, a.sz);
+    const double d0 = dot3(a.ux, a.uy, a.uz, b.sx, b.sy, b.sz) - base;
+    const double d1 = dot3(a.ux, a.uy, a.uz, b1x, b1y, b1z) - base;
+    const bool before = (d0 <= 0.0) & (d1 <= 0.0);
+    const bool after = (d0 >= a.mag) & (d1 >= a.mag);
+    if (before | after) {
+      const bool near0 = fabs(d0) < fabs(d1);
+      pbx = near0 ? b.sx : b1x; pby = near0 ? b.sy : b1y; pbz = near0 ? b.sz : b1z;
+      if (after) { pax = ends[3 * i]; pay = ends[3 * i + 1]; paz = ends[3 * i + 2]; }
+      else { pax = a.sx; pay = a.sy; paz = a.sz; }
+    } else {
+      const double tm = clip0(d0, a.mag);
+      pax = a.sx + tm * a.ux; pay = a.sy + tm * a.uy; paz = a.sz + tm * a.uz;
+      const double gx = b.sx - pax, gy = b.sy - pay, gz = b.sz - paz;
+      const double al = dot3(gx, gy, gz, a.ux, a.uy, a.uz);
+      pbx = pax + (gx - al * a.ux); pby = pay + (gy - al * a.uy); pbz = paz + (gz - al * a.uz);
+    }
+  }
+  const double ex = pax - pbx, ey = pay - pby, ez = paz - pbz;
+  return sqrt((ex * ex + ey * ey) + ez * ez);
+}
+
+__global__ void __launch_bounds__(256) k_ray_prep(const double *__restrict__ starts, const double *__restrict__ ends,
+                                                  const int32_t *__restrict__ ids, int64_t n, RayRec *__restrict__ rec) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  RayRec r;
+  r.sx = starts[3 * i]; r.sy = starts[3 * i + 1]; r.sz = starts[3 * i + 2];
+  const double dx = ends[3 * i] - r.sx, dy = ends[3 * i + 1] - r.sy, dz = ends[3 * i + 2] - r.sz;
+  r.mag = sqrt((dx * dx + dy * dy) + dz * dz);
+  r.ux = dx / r.mag; r.uy = dy / r.mag; r.uz = dz / r.mag;
+  r.id = ids[i]; r.pad = 0;
+  rec[i] = r;
+}
+
+// One workgroup per tile of the upper triangle (1-D grid, tri_decode; a grid-stride loop over the tiles once there are more than
+// GR_RAY_MAX_GRID of them).  The B side of the tile is staged in LDS; every lane
+// keeps one A ray in registers and walks the B rays -- all lanes read the same LDS address, a broadcast.  Hits (i < j, different
+// image, d <= threshold; a NaN d never is) are compacted per wave: one ballot, one atomic of the wave's leader on the edge
+// counter, one 64-bit key (i << 32 | j) and one distance per hit lane.  FILL false: the count alone (one atomic per wave).
+template <bool FILL>
+__global__ void __launch_bounds__(GR_RAY_TILE) k_ray_pairs(const RayRec *__restrict__ rec, const double *__restrict__ ends,
+                                                           int64_t n, int64_t T, int64_t tiles, double threshold,
+                                                           unsigned long long *__restrict__ counter,
+                                                           unsigned long long *__restrict__ keys, double *__restrict__ dist,
+                                                           int64_t cap) {
+  __shared__ RayRec tile[GR_RAY_TILE];
+  const int tid = threadIdx.x, lane = tid & 63;
+  unsigned long long found = 0;
+  for (int64_t k = blockIdx.x; k < tiles; k += gridDim.x) {
+    int64_t row, col;
+    tri_decode(k, T, row, col);
+    const int64_t j0 = col * GR_RAY_TILE;
+    const int nb = (int)((n - j0) < GR_RAY_TILE ? (n - j0) : GR_RAY_TILE);
+    __syncthreads();   // the tile before this one has been walked by every wave
+    if (tid < nb) tile[tid] = rec[j0 + tid];
+    const int64_t i = row * GR_RAY_TILE + tid;
+    const bool have_a = i < n;
+    const RayRec a = rec[have_a ? i : n - 1];
+    __syncthreads();
+    // a tile on the diagonal: the wave's first ray is row * TILE + (tid - lane); nothing at or before it can be a j > i
+    const int jj0 = row == col ? (tid - lane) + 1 : 0;
+    for (int jj = jj0; jj < nb; ++jj) {
+      const RayRec b = tile[jj];
+      const int64_t j = j0 + jj;
+      const double d = segment_distance(a, b, ends, i, j);
+      const bool hit = have_a & (i < j) & (a.id != b.id) & (d <= threshold);
+      const unsigned long long mask = __ballot(hit);
+      if (mask == 0) continue;
+      if (FILL) {
+        const int first = __ffsll((long long)mask) - 1;
+        unsigned long long base = 0;
+        if (lane == first) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
+        base = __shfl(base, first);
+        if (hit) {
+          const unsigned long long pos = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
+          if (pos < (unsigned long long)cap) {
+            keys[pos] = ((unsigned long long)i << 32) | (unsigned long long)j;
+            dist[pos] = d;
+          }
+        }
+      } else {
+        found += (unsigned long long)__popcll(mask);
+      }
+    }
+  }
+  if (!FILL && lane == 0 && found) atomicAdd(counter, found);
+}
+
+__global__ void __launch_bounds__(256) k_ray_split_keys(const unsigned long long *__restrict__ keys, int64_t m,
+                                                        int32_t *__restrict__ ei, int32_t *__restrict__ ej) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= m) return;
+  const unsigned long long key = keys[k];
+  ei[k] = (int32_t)(key >> 32);
+  ej[k] = (int32_t)(key & 0xFFFFFFFFull);
+}
+
+// One lane per ray, the triangles staged through LDS GR_CLIP_CHUNK at a time (nine doubles each; a face with an index outside
+// [0, V) is staged as NaN and can never be hit).  Double-sided Moller-Trumbore: the nearest hit with t >= 0 along the
+// infinite ray; of two triangles hit at the same t the first in `faces` wins.
+__global__ void __launch_bounds__(256) k_rays_clip(const double *__restrict__ origins, const double *__restrict__ dirs, int64_t n,
+                                                   const double *__restrict__ points, int64_t V,
+                                                   const int32_t *__restrict__ faces, int F, int32_t *__restrict__ hit,
+                                                   double *__restrict__ t_out, double *__restrict__ p_out) {
+  __shared__ double tri[GR_CLIP_CHUNK][9];
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool have = r < n;
+  const int64_t rr = have ? r : 0;
+  double ox = 0, oy = 0, oz = 0, dx = 0, dy = 0, dz = 0;
+  if (n > 0) {
+    ox = origins[3 * rr]; oy = origins[3 * rr + 1]; oz = origins[3 * rr + 2];
+    dx = dirs[3 * rr]; dy = dirs[3 * rr + 1]; dz = dirs[3 * rr + 2];
+  }
+  double best = INFINITY;
+  bool any = false;
+  for (int f0 = 0; f0 < F; f0 += GR_CLIP_CHUNK) {
+    const int nf = (F - f0) < GR_CLIP_CHUNK ? (F - f0) : GR_CLIP_CHUNK;
+    __syncthreads();
+    for (int e = threadIdx.x; e < nf * 3; e += 256) {   // element e: vertex e % 3 of triangle e / 3
+      const int32_t v = faces[3 * (int64_t)f0 + e];
+      const bool ok = v >= 0 && v < V;
+      const int64_t vv = ok ? v : 0;
+      double *dst = &tri[e / 3][3 * (e % 3)];
+      dst[0] = ok ? points[3 * vv] : NAN;
+      dst[1] = ok ? points[3 * vv + 1] : NAN;
+      dst[2] = ok ? points[3 * vv + 2] : NAN;
+    }
+    __syncthreads();
+    for (int k = 0; k < nf; ++k) {
+      const double *q = tri[k];
+      const double e1x = q[3] - q[0], e1y = q[4] - q[1], e1z = q[5] - q[2];
+      const double e2x = q[6] - q[0], e2y = q[7] - q[1], e2z = q[8] - q[2];
+      const double px = dy * e2z - dz * e2y, py = dz * e2x - dx * e2z, pz = dx * e2y - dy * e2x;
+      const double det = dot3(e1x, e1y, e1z, px, py, pz);
+      const double inv = 1.0 / det;
+      const double sx = ox - q[0], sy = oy - q[1], sz = oz - q[2];
+      const double u = dot3(sx, sy, sz, px, py, pz) * inv;
+      const double qx = sy * e1z - sz * e1y, qy = sz * e1x - sx * e1z, qz = sx * e1y - sy * e1x;
+      const double v = dot3(dx, dy, dz, qx, qy, qz) * inv;
+      const double t = dot3(e2x, e2y, e2z, qx, qy, qz) * inv;
+      // every comparison is false for NaN: a degenerate triangle or a parallel ray (det == 0: inv infinite, u, v or t NaN or
+      // infinite) is never a hit
+      const bool ok = (det != 0.0) & (u >= 0.0) & (v >= 0.0) & (u + v <= 1.0) & (t >= 0.0) & (t < best);
+      best = ok ? t : best;
+      any |= ok;
+    }
+  }
+  if (!have) return;
+  hit[r] = any ? 1 : 0;
+  t_out[r] = any ? best : NAN;
+  p_out[3 * r] = any ? ox + best * dx : NAN;
+  p_out[3 * r + 1] = any ? oy + best * dy : NAN;
+  p_out[3 * r + 2] = any ? oz + best * dz : NAN;
+}
+
+inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+
+}  // namespace
+
+extern "C" {
+
+int gr_ray_pairs_tile(int64_t tile, int64_t tiles_per_side, int64_t *row_h, int64_t *col_h) {
+  if (!row_h || !col_h || tiles_per_side <= 0 || tiles_per_side > GR_RAY_MAX_N / GR_RAY_TILE || tile < 0 ||
+      tile >= tri_off(tiles_per_side, tiles_per_side))
+    return GR_EINVAL;
+  tri_decode(tile, tiles_per_side, *row_h, *col_h);
+  return GR_OK;
+}
+
+int gr_ray_pairs(gr_ctx *c, const double *starts, const double *ends, const int32_t *ray_ids, int64_t n, double threshold,
+                 int32_t *edge_i, int32_t *edge_j, double *edge_d, int64_t edge_cap, int64_t *total_h, void *stream) {
+  if (!c) return GR_EINVAL;
+  if (!total_h || n < 0 || edge_cap < 0 || edge_cap > 0x7FFFFFFFll)
+    return fail(c, GR_EINVAL, "bad ray-pair args (n=%lld, edge_cap=%lld)", (long long)n, (long long)edge_cap);
+  if (n > GR_RAY_MAX_N) return fail(c, GR_EINVAL, "%lld rays: gr_ray_pairs takes at most %d per call", (long long)n, GR_RAY_MAX_N);
+  const bool fill = edge_cap > 0 && edge_i && edge_j && edge_d;
+  if (edge_cap > 0 && !fill) return fail(c, GR_EINVAL, "edge_cap %lld without edge buffers", (long long)edge_cap);
+  *total_h = 0;
+  if (n > 0 && (!starts || !ends || !ray_ids)) return fail(c, GR_EINVAL, "null ray arrays");
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
+  const int64_t T = ceil_div(n, GR_RAY_TILE), tiles = tri_off(T, T);
+  const int64_t cap = fill ? edge_cap : 0;
+  // context scratch: edge counter | ray records | keys | distances | sorted keys | rocPRIM
+  size_t sort_bytes = 0;
+  int end_bit = 64;
+  if (fill) {
+    int nbits = 1;
+    while (((int64_t)1 << nbits) < n) ++nbits;
+    end_bit = 32 + nbits;   // i < n sits above bit 32
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                                 (double *)nullptr, (double *)nullptr, (int)cap, 0, end_bit, s));
+  }
+  const size_t o_rec = 256, o_keys = o_rec + up256(sizeof(RayRec) * (size_t)(n > 0 ? n : 1));
+  const size_t o_dist = o_keys + up256(8 * (size_t)cap), o_sorted = o_dist + up256(8 * (size_t)cap);
+  const size_t o_tmp = o_sorted + up256(8 * (size_t)cap), need = o_tmp + sort_bytes + 256;
+  if (c->sort_bytes < need) {
+    quiesce(c);
+    GR_HIP(c, hipStreamSynchronize(s));
+    if (c->sort_tmp) (void)hipFree(c->sort_tmp);
+    c->sort_tmp = nullptr; c->sort_bytes = 0;
+    if (hipMalloc(&c->sort_tmp, need) != hipSuccess) return fail(c, GR_ENOMEM, "ray-pair scratch allocation failed (%zu bytes)", need);
+    c->sort_bytes = need;
+  }
+  note_stream(c, s);
+  char *base = (char *)c->sort_tmp;
+  if (c->opt_dbg & 1024) GR_HIP(c, hipMemsetAsync(base, 0xFF, c->sort_bytes, s));   // test hook: nothing survives between calls
+  unsigned long long *counter = (unsigned long long *)base;
+  RayRec *rec = (RayRec *)(base + o_rec);
+  unsigned long long *keys = (unsigned long long *)(base + o_keys), *sorted = (unsigned long long *)(base + o_sorted);
+  double *dist = (double *)(base + o_dist);
+  GR_HIP(c, hipMemsetAsync(counter, 0, sizeof(unsigned long long), s));
+  if (tiles > 0) {
+    hipLaunchKernelGGL(k_ray_prep, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, starts, ends, ray_ids, n, rec);
+    const int64_t max_grid = (c->opt_dbg & 2048) ? 7 : GR_RAY_MAX_GRID;   // test hook: a few workgroups stride over all tiles
+    const unsigned grid = (unsigned)(tiles < max_grid ? tiles : max_grid);
+    if (fill)
+      hipLaunchKernelGGL(k_ray_pairs<true>, dim3(grid), dim3(GR_RAY_TILE), 0, s, rec, ends, n, T, tiles, threshold, counter,
+                         keys, dist, cap);
+    else
+      hipLaunchKernelGGL(k_ray_pairs<false>, dim3(grid), dim3(GR_RAY_TILE), 0, s, rec, ends, n, T, tiles, threshold, counter,
+                         (unsigned long long *)nullptr, (double *)nullptr, (int64_t)0);
+    GR_HIP(c, hipGetLastError());
+  }
+  unsigned long long total = 0;
+  GR_HIP(c, hipMemcpyAsync(&total, counter, sizeof(total), hipMemcpyDeviceToHost, s));
+  GR_HIP(c, hipStreamSynchronize(s));
+  *total_h = (int64_t)total;
+  if (!fill || total == 0) return GR_OK;
+  if ((int64_t)total > cap)
+    return fail(c, GR_EOVERFLOW, "%llu ray pairs within the threshold, the edge buffers hold %lld: call again with that capacity",
+                total, (long long)cap);
+  size_t tb = sort_bytes;
+  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, tb, keys, sorted, dist, edge_d, (int)total, 0, end_bit, s));
+  hipLaunchKernelGGL(k_ray_split_keys, dim3((unsigned)ceil_div((int64_t)total, 256)), dim3(256), 0, s, sorted, (int64_t)total,
+                     edge_i, edge_j);
+  GR_HIP(c, hipGetLastError());
+  // the sort and the split still read the context's scratch: the call ends only when they are through, so that the next call
+  // on ANY stream of this context (and every other user of the sort scratch) finds it free
+  GR_HIP(c, hipStreamSynchronize(s));
+  return GR_OK;
+}
+
+int gr_rays_clip(gr_ctx *c, const double *origins, const double *directions, int64_t n, const double *points, int64_t V,
+                 const int32_t *faces, int64_t F, int32_t *hit, double *t, double *hit_points, void *stream) {
+  if (!c) return GR_EINVAL;
+  if (n < 0 || V < 0 || F < 0 || n > 0x7FFFFFFFll * 256) return fail(c, GR_EINVAL, "bad ray-clip args");
+  if (F > GR_CLIP_MAX_TRIANGLES)
+    return fail(c, GR_EINVAL, "%lld triangles: gr_rays_clip tests every ray against every triangle and takes at most %d (a coarse "
+                "boundary surface, not the photogrammetry mesh)", (long long)F, GR_CLIP_MAX_TRIANGLES);
+  if (n == 0) return GR_OK;
+  if (!origins || !directions || !hit || !t || !hit_points || (F > 0 && (!points || !faces || V <= 0)))
+    return fail(c, GR_EINVAL, "null ray-clip arrays");
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(k_rays_clip, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, origins, directions, n, points, V, faces,
+                     (int)F, hit, t, hit_points);
+  GR_HIP(c, hipGetLastError());
+  return GR_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,195 @@
+"""Numeric stage of the multiview-detection workflow (reference: geograypher/utils/numeric.py:39-236, 330-619).
+
+The quadratic part -- the clamped segment-to-segment distance of every pair of rays -- runs on the device
+(`HipRaster.ray_pair_edges`, gr_ray_pairs); what is left on the host works on the kept edges only: the `min_dist` floor, the
+optional transform, the 1 / d weight, the reference's edge order, and the Louvain communities (networkx).  There is no CPU
+fallback for the distance stage: `backend` is a `HipRaster` (default: the shared one of the current device) or any object with
+the same `ray_pair_edges(starts, ends, ray_ids, threshold)` method.
+"""
+from __future__ import annotations
+
+import json
+import typing
+from pathlib import Path
+
+import numpy as np
+
+from geograypher_amd.constants import PATH_TYPE
+
+
+def _host(x) -> np.ndarray:
+    """device tensor or array -> numpy"""
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def _clip0(x, hi):
+    return np.minimum(np.maximum(x, 0.0), hi)
+
+
+def _dot(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1],
+                     a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def segment_closest_points(a0: np.ndarray, a1: np.ndarray, b0: np.ndarray, b1: np.ndarray):
+    """Closest points between every segment a0 -> a1 (N of them, axis 0) and every segment b0 -> b1 (M, axis 1), clamped to
+    the segments: (pA (N, M, 3), pB (N, M, 3), dist (N, M)).  The host form of what gr_ray_pairs evaluates per pair
+    (compute_approximate_ray_intersections(clamp=True), numeric.py:39-236); used on the few rays of one community.
+
+    Skew lines meet closest at t0 = det(t, uB, n) / |n|^2 along A and t1 = det(t, uA, n) / |n|^2 along B (n = uA x uB,
+    t = b0 - a0).  A parameter outside its segment is clamped and the other point re-projected: B from the clamped A first,
+    then A from the updated B.  Exactly parallel segments (|n|^2 == 0) are placed by the projections d0, d1 of B's ends on A's
+    axis: B wholly before a0 or behind a1 pairs that end of A with B's nearer end, otherwise A's point is d0 clamped and B's
+    point the foot of the perpendicular.  A zero-length segment has NaN directions and NaN results."""
+    a0, a1, b0, b1 = (np.asarray(x, dtype=np.float64) for x in (a0, a1, b0, b1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        A, B = a1 - a0, b1 - b0
+        magA = np.sqrt((A[:, 0] ** 2 + A[:, 1] ** 2) + A[:, 2] ** 2)[:, None]
+        magB = np.sqrt((B[:, 0] ** 2 + B[:, 1] ** 2) + B[:, 2] ** 2)[None, :]
+        uA = (A / magA)[:, None, :]
+        uB = (B / magB.T)[None, :, :]
+        sA, sB = a0[:, None, :], b0[None, :, :]
+        n = _cross(uA, uB)
+        denom = np.sqrt(_dot(n, n)) ** 2
+        parallel = denom == 0
+        denom = np.where(parallel, 1.0, denom)
+        t = sB - sA
+        t0 = _dot(_cross(t, uB), n) / denom
+        t1 = _dot(_cross(t, uA), n) / denom
+        pA = sA + _clip0(t0, magA)[..., None] * uA
+        pB = sB + _clip0(t1, magB)[..., None] * uB
+        oobA = (t0 < 0) | (t0 > magA)
+        oobB = (t1 < 0) | (t1 > magB)
+        pB = np.where(oobA[..., None], sB + _clip0(_dot(pA - sB, uB), magB)[..., None] * uB, pB)
+        pA = np.where(oobB[..., None], sA + _clip0(_dot(pB - sA, uA), magA)[..., None] * uA, pA)
+        if parallel.any():
+            base = _dot(uA, sA)
+            d0 = _dot(uA, sB) - base
+            d1 = _dot(uA, b1[None, :, :]) - base
+            before = (d0 <= 0) & (d1 <= 0)
+            after = (d0 >= magA) & (d1 >= magA)
+            nearer = np.where((np.abs(d0) < np.abs(d1))[..., None], sB, b1[None, :, :])
+            mA = sA + _clip0(d0, magA)[..., None] * uA
+            g = sB - mA
+            mB = mA + (g - _dot(g, uA)[..., None] * uA)
+            qA = np.where(after[..., None], a1[:, None, :], np.where(before[..., None], sA, mA))
+            qB = np.where((before | after)[..., None], nearer, mB)
+            pA = np.where(parallel[..., None], qA, pA)
+            pB = np.where(parallel[..., None], qB, pB)
+        e = pA - pB
+        dist = np.sqrt((e[..., 0] ** 2 + e[..., 1] ** 2) + e[..., 2] ** 2)
+    return pA, pB, dist
+
+
+def intersection_average(starts: np.ndarray, ends: np.ndarray) -> np.ndarray:
+    """Mean of the closest points between all pairs of distinct segments (numeric.py:330-347): (3,)."""
+    starts, ends = np.asarray(starts, dtype=np.float64), np.asarray(ends, dtype=np.float64)
+    pA, pB, _ = segment_closest_points(starts, ends, starts, ends)
+    mask = ~np.eye(starts.shape[0], dtype=bool)
+    return np.mean(np.vstack([pA[mask], pB[mask]]), axis=0)
+
+
+def ray_pair_edges(starts, ends, ray_IDs, similarity_threshold: float, min_dist: float = 1e-6, step: int = 5000,
+                   transform: typing.Optional[typing.Callable[[np.ndarray], np.ndarray]] = None, backend=None):
+    """`calc_graph_weights` as arrays: (i, j, weight) -- int64, int64, float64 -- of every graph edge, in the reference's order
+    for `step`.  A Python list of millions of tuples costs more than the kernel; use this form for large surveys.
+
+    After the device call, on the kept distances and in this order (numeric.py:488-498, 410-425): d < min_dist -> min_dist;
+    `transform` (it is given the 1-D array of kept distances where the reference hands it a whole block matrix: elementwise
+    callables only); non-finite values dropped; weight = 1 / d in float64.  Order: the reference visits the (step, step)
+    blocks of the upper triangle row by row (its `chunk_slices`) and each block row-major, and networkx takes its node order
+    from the edge list, so the order is part of the result."""
+    if step <= 0:
+        raise ValueError(f"step must be positive, got {step}")
+    if backend is None:
+        from geograypher_amd._hip import default_backend
+
+        backend = default_backend()
+    starts, ends = np.asarray(starts, dtype=np.float64).reshape(-1, 3), np.asarray(ends, dtype=np.float64).reshape(-1, 3)
+    ids = np.asarray(ray_IDs).reshape(-1)
+    if not np.array_equal(ids, ids.astype(np.int32)):
+        raise ValueError("ray_IDs must be integers within the int32 range")
+    i, j, d = (_host(x) for x in backend.ray_pair_edges(starts, ends, ids.astype(np.int32), float(similarity_threshold)))
+    i, j, d = i.astype(np.int64), j.astype(np.int64), d.astype(np.float64)
+    d = np.where(d < min_dist, min_dist, d)
+    if transform is not None:
+        d = np.asarray(transform(d), dtype=np.float64)
+        if d.shape != i.shape:
+            raise ValueError("transform must be elementwise: it changed the shape of the distances")
+    keep = np.isfinite(d)
+    i, j, d = i[keep], j[keep], d[keep]
+    with np.errstate(divide="ignore"):
+        w = 1 / d
+    order = np.lexsort((j, i, j // step, i // step))
+    return i[order], j[order], w[order]
+
+
+def calc_graph_weights(starts, ends, ray_IDs, similarity_threshold: float, out_dir: typing.Optional[PATH_TYPE] = None,
+                       min_dist: float = 1e-6, step: int = 5000,
+                       transform: typing.Optional[typing.Callable[[np.ndarray], np.ndarray]] = None, backend=None):
+    """Graph edges between rays of different images that pass within `similarity_threshold` of each other, weighted by the
+    inverse distance (numeric.py:428-506): a list of (i, j, {"weight": w}) or, with `out_dir`, the path of the
+    `edge_weights.json` written there.  `step` only decides the ORDER of the list (see `ray_pair_edges`); the device kernel has
+    its own tiling.  `transform`: elementwise callables only."""
+    i, j, w = ray_pair_edges(starts, ends, ray_IDs, similarity_threshold, min_dist=min_dist, step=step, transform=transform,
+                             backend=backend)
+    edge_weights = [(a, b, {"weight": c}) for a, b, c in zip(i.tolist(), j.tolist(), w.tolist())]
+    if out_dir is None:
+        return edge_weights
+    path = Path(out_dir) / "edge_weights.json"
+    with path.open("w") as file:
+        json.dump(edge_weights, file)
+    return path
+
+
+def calc_communities(starts, ends, edge_weights, louvain_resolution: float = 1.0, out_dir: typing.Optional[PATH_TYPE] = None,
+                     transform_to_epsg_4978: typing.Optional[np.ndarray] = None, seed=None):
+    """Louvain communities of the ray graph and one 3D point per community (numeric.py:509-619).  Returns, or with `out_dir`
+    saves as `communities.npz`, a dict with "ray_IDs" ((N,) float: community of every ray, NaN for a ray without an edge) and
+    "community_points" ((M, 3): `intersection_average` of the community's rays), communities ordered by falling size.
+
+    `seed` goes to networkx.community.louvain_communities (the reference is unseeded).  With `transform_to_epsg_4978` the
+    reference adds "community_points_latlon" through pyproj.  Where pyproj is missing the transformed points are returned as
+    "community_points_epsg_4978" instead and no lat/lon key is written: the conversion is not approximated."""
+    import networkx
+
+    starts, ends = np.asarray(starts, dtype=np.float64), np.asarray(ends, dtype=np.float64)
+    graph = networkx.Graph([(int(e[0]), int(e[1]), dict(e[2])) for e in edge_weights])
+    ecef = None
+    if len(graph) > 0:
+        communities = networkx.community.louvain_communities(graph, weight="weight", resolution=louvain_resolution, seed=seed)
+        communities = sorted(communities, key=len, reverse=True)
+        ray_IDs = np.full(starts.shape[0], fill_value=np.nan)
+        community_points = []
+        for community_ID, community in enumerate(communities):
+            inds = np.array(list(community))
+            ray_IDs[inds] = community_ID
+            community_points.append(intersection_average(starts[inds], ends[inds]))
+        community_points = np.vstack(community_points)
+        result = {"ray_IDs": ray_IDs, "community_points": community_points}
+        if transform_to_epsg_4978 is not None:
+            homogenous = np.concatenate([community_points, np.ones_like(community_points[:, 0:1])], axis=1)
+            ecef = (np.asarray(transform_to_epsg_4978) @ homogenous.T).T
+    else:
+        result = {"ray_IDs": np.zeros((0,), dtype=int), "community_points": np.zeros((0, 3))}
+        if transform_to_epsg_4978 is not None:
+            ecef = np.zeros((0, 4))
+    if ecef is not None:
+        try:
+            import pyproj
+        except ImportError:
+            result["community_points_epsg_4978"] = ecef[:, :3]
+        else:
+            tr = pyproj.Transformer.from_crs(pyproj.CRS.from_epsg(4978), pyproj.CRS.from_epsg(4326))
+            lat, lon, alt = tr.transform(ecef[:, 0], ecef[:, 1], ecef[:, 2])
+            result["community_points_latlon"] = np.vstack([lat, lon, alt]).T
+    if out_dir is not None:
+        path = Path(out_dir) / "communities.npz"
+        np.savez(path, **result)
+        return path
+    return result

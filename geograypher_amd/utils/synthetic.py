@@ -399,3 +399,68 @@ def config5_scene(n_views: int = 2000):
     points, faces = terrain_mesh(1582, 800.0)
     cams = survey_cameras(50, 40, 15.0, 18.0, agl=150.0, f=4500.0, width=6000, height=4000, seed=6)
     return (points, faces), (cams[:n_views] if n_views < len(cams) else cams)
+
+
+def detection_survey(n_objects: int = 60, n_cameras: int = 40, seed: int = 0, extent: float = 200.0, sigma: float = 0.15,
+                     z_range=(-2.0, 30.0), p_seen: float = 0.5):
+    """Synthetic input of the multiview-detection workflow (`triangulate_detections`): objects on an `extent` m square (heights
+    0-20 m), cameras 80-120 m above it; each camera sees each object with probability `p_seen` and casts one ray at it whose
+    aim is off by N(0, sigma) m per axis at the object; the rays are clipped to z in `z_range`.  Returns a dict: ray_starts,
+    ray_ends (R, 3), ray_IDs (R,) the camera of each ray, ray_objects (R,) the object it was aimed at, objects (n_objects, 3),
+    cameras (n_cameras, 3).  Rays come camera by camera, objects in ascending order."""
+    rng = np.random.default_rng(seed)
+    objects = np.column_stack([rng.uniform(0.0, extent, n_objects), rng.uniform(0.0, extent, n_objects),
+                               rng.uniform(0.0, 20.0, n_objects)])
+    cameras = np.column_stack([rng.uniform(0.0, extent, n_cameras), rng.uniform(0.0, extent, n_cameras),
+                               rng.uniform(80.0, 120.0, n_cameras)])
+    seen = rng.random((n_cameras, n_objects)) < p_seen
+    cam_idx, obj_idx = np.nonzero(seen)
+    aim = objects[obj_idx] + rng.normal(0.0, sigma, (cam_idx.size, 3))
+    origin = cameras[cam_idx]
+    direction = aim - origin
+    t_hi = (z_range[1] - origin[:, 2]) / direction[:, 2]
+    t_lo = (z_range[0] - origin[:, 2]) / direction[:, 2]
+    return {
+        "ray_starts": origin + t_hi[:, None] * direction, "ray_ends": origin + t_lo[:, None] * direction,
+        "ray_IDs": cam_idx.astype(np.int64), "ray_objects": obj_idx.astype(np.int64), "objects": objects, "cameras": cameras,
+    }
+
+
+def boundary_grid(n, height_fn, lo=-150.0, hi=350.0):
+    """A coarse boundary surface for `clip_line_segments`: (points, faces) of an n x n vertex grid over [lo, hi]^2 at
+    z = height_fn(x, y), two triangles per cell."""
+    xs = np.linspace(lo, hi, n)
+    x, y = np.meshgrid(xs, xs, indexing="ij")
+    pts = np.column_stack([x.ravel(), y.ravel(), height_fn(x, y).ravel()])
+    faces = []
+    for i in range(n - 1):
+        for j in range(n - 1):
+            a, b, c, d = i * n + j, i * n + j + 1, (i + 1) * n + j, (i + 1) * n + j + 1
+            faces += [(a, b, c), (b, d, c)]
+    return pts, np.array(faces, dtype=np.int32)
+
+
+class CenterDetector:
+    """A detector that knows its detections per image name: the `get_detection_centers(filename)` side of
+    TabularRectangleSegmentor, for synthetic surveys."""
+
+    def __init__(self, centers_by_filename):
+        self.centers = dict(centers_by_filename)
+
+    def get_detection_centers(self, filename):
+        return self.centers.get(str(filename), np.zeros((0, 2)))
+
+
+def detection_survey_cameras(survey, f: float = 3000.0, width: int = 4000, height: int = 3000):
+    """Nadir cameras at the survey's camera positions and a `CenterDetector` holding, per camera, the (i, j) pixel at which
+    each of its rays leaves it (pinhole, principal point at the image centre; detections may lie outside the sensor).
+    `cameras.triangulate_detections(detector, ...)` then sees the rays of `detection_survey` again."""
+    poses = [nadir_pose(x, y, z) for x, y, z in survey["cameras"]]
+    cams = camera_set_from_poses(poses, f, width, height, name_prefix="/synthetic/detections")
+    centers = {}
+    for k, T in enumerate(poses):
+        mine = survey["ray_IDs"] == k
+        d = (survey["ray_ends"][mine] - survey["ray_starts"][mine]) @ T[:3, :3]   # directions in the camera frame
+        centers[str(cams.get_image_filename(k))] = np.column_stack([f * d[:, 1] / d[:, 2] + height / 2.0,
+                                                                    f * d[:, 0] / d[:, 2] + width / 2.0])
+    return cams, CenterDetector(centers)

@@ -157,7 +157,9 @@ enum {
                                switch (oracle_raster.c R1-GL) and the parity tests run both                              */
   GR_OPT_DEBUG_LDS = 98,    /* extra dynamic LDS bytes per tile workgroup: lowers occupancy (timing experiments)     */
   GR_OPT_DEBUG = 99         /* test hook: 512 = entry slots and row counts are poisoned with 0xFF before every launch group is
-                               binned (results stay right: tests/test_overflow_protocol.py)                      */
+                               binned (results stay right: tests/test_overflow_protocol.py); 1024 = gr_ray_pairs poisons its
+                               scratch with 0xFF at the start of every call, 2048 = its grid is capped at 7 workgroups, which
+                               stride over all tiles as a launch beyond 2^20 tiles does (tests/test_ray_pairs.py)  */
 };
 int gr_set_option(gr_ctx *ctx, int key, int value);
 
@@ -273,6 +275,33 @@ int gr_project_rect_pairs(gr_ctx *ctx, const int32_t *ids, const int32_t *rects,
  * unique_keys / pair_counts: capacity n.  *n_unique_h (host) receives the number of distinct keys.  Synchronises. */
 int gr_count_pairs(gr_ctx *ctx, uint64_t *keys, int64_t n, uint64_t *unique_keys, uint32_t *pair_counts,
                    int64_t *n_unique_h, void *stream);
+
+/* ray-pair graph of the multiview-detection workflow -- replaces the distance stage of calc_graph_weights
+ * (utils/numeric.py:428-498: compute_approximate_ray_intersections(clamp=True), numeric.py:39-236, over 5000 x 5000 blocks, the
+ * threshold, and the i < j / different-image filter of format_graph_edges, numeric.py:379-425).  starts, ends: n x 3 f64 segment
+ * end points; ray_ids: n int32, the image each ray came from; n <= 8 388 608.  An EDGE is a pair i < j with
+ * ray_ids[i] != ray_ids[j] whose clamped segment-to-segment distance d satisfies d <= threshold (a NaN d -- a zero-length
+ * segment, NaN or infinite coordinates -- never does).  *total_h (HOST) receives the number of edges, whether or not they fit.
+ * edge_i, edge_j (int32) and edge_d (f64), capacity edge_cap <= 2^31 - 1 each, receive the edges SORTED by (i, j) (rocPRIM radix
+ * sort of the 64-bit key i << 32 | j), so the result does not depend on wave scheduling.  total > edge_cap: GR_EOVERFLOW and
+ * the edge buffers hold NOTHING (they are not written); call again with edge_cap >= *total_h.  edge_cap == 0 (the buffers may
+ * be NULL): the count alone.  The min_dist floor, the transform and the 1 / d weight of the reference stay on the host.
+ * Uses context scratch (64 B per ray, 24 B per edge slot + the sort's) and synchronises `stream` twice: to read the count, and
+ * again behind the sort, its last use of the scratch -- on return the edges are complete and the scratch is free, so calls on
+ * different streams of one context follow each other.  Added without a GR_VERSION bump. */
+int gr_ray_pairs(gr_ctx *ctx, const double *starts, const double *ends, const int32_t *ray_ids, int64_t n, double threshold,
+                 int32_t *edge_i, int32_t *edge_j, double *edge_d, int64_t edge_cap, int64_t *total_h, void *stream);
+/* The tile (row <= col) that has index `tile` in gr_ray_pairs' 1-D order of the upper triangle (one workgroup each, strided beyond
+ * 2^20 tiles), for tiles_per_side (<= 32768) tiles of 256 rays a
+ * side: the kernel's own decode of the row-major upper triangle, exposed so that it can be checked on the host.  No device work. */
+int gr_ray_pairs_tile(int64_t tile, int64_t tiles_per_side, int64_t *row_h, int64_t *col_h);
+/* ray / boundary-surface intersection of clip_line_segments (utils/geometric.py:210-222: pyvista's multi_ray_trace with
+ * first_point=True, an Embree BVH) for a SMALL mesh, by brute force: origins, directions n x 3 f64; points V x 3 f64; faces
+ * F x 3 int32 (a face with an index outside [0, V) is never hit), F <= 65536 -- more is GR_EINVAL: this is for a coarse covering
+ * surface, not the photogrammetry mesh.  Double-sided Moller-Trumbore in f64, the nearest hit with t >= 0 along the infinite
+ * ray.  hit: n int32 (1 / 0); t: n f64; hit_points: n x 3 f64 = origin + t direction (NaN where hit is 0).  Only enqueues work. */
+int gr_rays_clip(gr_ctx *ctx, const double *origins, const double *directions, int64_t n, const double *points, int64_t V,
+                 const int32_t *faces, int64_t F, int32_t *hit, double *t, double *hit_points, void *stream);
 
 /* distortion warp of an image through a cached sampling map (row f1) -- replaces utils/image.py:72-126
  * (flexible_inputs_warp -> skimage.transform.warp, mode "constant") as called by cameras.py:1092-1156 for the face-id
