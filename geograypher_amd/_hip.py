@@ -25,6 +25,7 @@ GR_EOVERFLOW = -6
 GR_FLAG_NEG1_IS_LAST_FACE = 1
 GR_FLAG_DEFER_CHECK = 2
 GR_CAM_FLOATS = 16
+GR_DTYPE_U8 = 0
 GR_DTYPE_F32 = 1
 GR_DTYPE_F64 = 2
 
@@ -59,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "gr_warp_f64",
     "gr_invert_distortion_f64",
     "gr_resize_image_f64",
+    "gr_equirect_view",
     "gr_finalize_votes",
     "gr_finalize_sums_f64",
     "gr_argmax_nonzero",
@@ -176,6 +178,9 @@ def load_library() -> ctypes.CDLL:
     lib.gr_invert_distortion_f64.argtypes = [vp, ctypes.POINTER(f64), i32, i32, f64, i32, f64, vp, vp, vp]
     lib.gr_resize_image_f64.restype = i32
     lib.gr_resize_image_f64.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
+    lib.gr_equirect_view.restype = i32
+    lib.gr_equirect_view.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, ctypes.POINTER(f64), i32, i32, i32, i32, f64, f64, vp,
+                                     vp, vp, vp, vp]
     lib.gr_learned_cache_file.restype = i32
     lib.gr_learned_cache_file.argtypes = [ctypes.c_char_p]
     lib.gr_learned_cache_clear.restype = i32
@@ -865,6 +870,99 @@ class HipRaster:
                                               1 if divide_by_255 else 0, h_out, w_out, out.data_ptr(), self._stream())
         self._check(rc, "gr_resize_image_f64")
         return out
+
+    # -- 360-degree photos: perspective views of an equirectangular image -------------------------------------------
+    equirect_uploads = 0   # photos this backend sent to the device (equirect_upload): one per photo, however many views
+
+    class EquirectSource:
+        """An equirectangular photo resident on the device, with what every view of it needs (utils/image.py:89-104 and
+        skimage's clip range): the file-dtype tensor, the value range and the per-channel normalised clip bounds."""
+
+        def __init__(self, tensor, np_dtype, squeeze, vmin, vrange, bounds):
+            self.tensor, self.np_dtype, self.squeeze = tensor, np_dtype, squeeze
+            self.vmin, self.vrange, self.bounds = vmin, vrange, bounds
+            self.shape = tuple(tensor.shape)
+
+    def equirect_upload(self, equi_img):
+        """(H, W) or (H, W, C) uint8 / float64 numpy image -> `EquirectSource`.  The photo crosses the link once, in its file
+        dtype; its range and channel bounds are reduced on the device."""
+        torch = _torch()
+        img = np.asarray(equi_img)
+        if img.dtype == bool:
+            img = img.astype(np.uint8)
+        if img.dtype not in (np.uint8, np.float64):
+            raise NotImplementedError(f"equirectangular source dtype {img.dtype} is not supported (uint8 or float64)")
+        if img.ndim not in (2, 3) or img.size == 0:
+            raise ValueError(f"equi_img must be a non-empty (H, W) or (H, W, C) image, got shape {img.shape}")
+        squeeze = img.ndim == 2
+        t = torch.as_tensor(np.ascontiguousarray(img)).to(self.device)
+        self.equirect_uploads += 1
+        if squeeze:
+            t = t[..., None]
+        t = t.contiguous()
+        C = int(t.shape[2])
+        flat = t.reshape(-1, C)
+        # exact in float64 for both dtypes: min / max select values, the normalisation below is image.py:102 on 2 C numbers
+        ch = torch.stack([flat.min(dim=0).values, flat.max(dim=0).values], dim=1).to(torch.float64).cpu().numpy()
+        vmin = min(float(ch[:, 0].min()), 0.0)
+        vmax = max(float(ch[:, 1].max()), 0.0)
+        vrange = vmax - vmin
+        bounds = None
+        if vrange > 0:
+            norm = (ch - vmin) / vrange
+            nfill = (0.0 - vmin) / vrange
+            norm[:, 0] = np.minimum(norm[:, 0], nfill)
+            norm[:, 1] = np.maximum(norm[:, 1], nfill)
+            bounds = torch.as_tensor(np.ascontiguousarray(norm)).to(self.device)
+        return self.EquirectSource(t, img.dtype, squeeze, vmin, vrange, bounds)
+
+    def equirect_view(self, source, x, y, rot, output_size, oversample_factor: int = 1, order: int = 1,
+                      return_mask: bool = False, return_debug: bool = False):
+        """One perspective view of a device-resident equirectangular photo (gr_equirect_view; utils/image.py:129-267): numpy
+        (out_h, out_w[, C]) -- float64, or the source dtype at oversample_factor 1 --, then the (H, W) bool sampling mask when
+        asked for, then {"ij": (2, ny, nx) float64} when `return_debug`.  x, y: the host-computed ray coordinates of the
+        oversampled view; rot: the 3 x 3 matrix of rotate_by_roll_pitch_yaw."""
+        torch = _torch()
+        if order not in (0, 1):
+            raise NotImplementedError(f"warp_order {order} is not implemented on the device (0 or 1)")
+        out_h, out_w = int(output_size[0]), int(output_size[1])
+        os_ = int(oversample_factor)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if len(x) != int(out_w * oversample_factor) or len(y) != int(out_h * oversample_factor) or os_ != oversample_factor:
+            raise ValueError(f"ray grid of {len(y)} x {len(x)} samples does not match an output of {out_h} x {out_w} at "
+                             f"oversampling {oversample_factor}")
+        H, W, C = source.shape
+        native = os_ == 1
+        res = []
+        with torch.cuda.device(self.device):
+            mask = torch.zeros((H, W + 1), dtype=torch.uint8, device=self.device) if return_mask else None
+            dbg = torch.empty((2, len(y), len(x)), dtype=torch.float64, device=self.device) if return_debug else None
+            vrange, bounds = source.vrange, source.bounds
+            if vrange == 0 and (return_mask or return_debug):   # the coordinates are still wanted: a unit range samples zeros
+                vrange, bounds = 1.0, torch.zeros((C, 2), dtype=torch.float64, device=self.device)
+            if vrange == 0:   # image.py:94-97: no variation, the fill everywhere; nothing to launch
+                out = torch.zeros((out_h, out_w, C), dtype=source.tensor.dtype if native else torch.float64, device=self.device)
+            else:
+                out = torch.empty((out_h, out_w, C), dtype=source.tensor.dtype if native else torch.float64, device=self.device)
+                xy = torch.as_tensor(np.concatenate([x, y])).to(self.device)
+                R = (ctypes.c_double * 9)(*[float(v) for v in np.asarray(rot, dtype=np.float64).reshape(9)])
+                dtype = GR_DTYPE_U8 if source.np_dtype == np.uint8 else GR_DTYPE_F64
+                rc = self.lib.gr_equirect_view(
+                    self._ctx, source.tensor.data_ptr(), dtype, H, W, C, xy.data_ptr(), xy.data_ptr() + 8 * len(x), R, out_h,
+                    out_w, os_, int(order), source.vmin, vrange, bounds.data_ptr(), out.data_ptr(),
+                    mask.data_ptr() if mask is not None else None, dbg.data_ptr() if dbg is not None else None, self._stream())
+                self._check(rc, "gr_equirect_view")
+            if mask is not None:   # image.py:261-265: the appended column belongs to column 0
+                mask[:, 0] |= mask[:, W]
+                mask = mask[:, :W]
+        arr = out.cpu().numpy()
+        res.append(arr[..., 0] if (source.squeeze or C == 1) else arr)
+        if return_mask:
+            res.append(mask.cpu().numpy().astype(bool))
+        if return_debug:
+            res.append({"ij": dbg.cpu().numpy()})
+        return res[0] if len(res) == 1 else tuple(res)
 
     # -- distortion warp (row f1) --------------------------------------------------------------------------------
     def upload_map(self, inverse_map):

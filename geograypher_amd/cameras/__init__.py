@@ -6,6 +6,7 @@ from geograypher_amd.cameras.cameras import (
 )
 from geograypher_amd.cameras.segmentor import SegmentorPhotogrammetryCameraSet
 from geograypher_amd.cameras.derived_cameras import MetashapeCameraSet
+from geograypher_amd.cameras.rig_cameras import create_rig_cameras_from_equirectangular
 
 __all__ = [
     "PhotogrammetryCamera",
@@ -13,4 +14,5 @@ __all__ = [
     "SegmentorPhotogrammetryCameraSet",
     "MetashapeCameraSet",
     "vtk_like_near_plane",
+    "create_rig_cameras_from_equirectangular",
 ]

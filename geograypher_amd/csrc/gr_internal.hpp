@@ -9,6 +9,7 @@
 //   warp.hip         distortion warp, lens inversion (row f1)
 //   resize.hip       photo down-scale of get_image (anti-aliased resize)
 //   rays.hip         multiview detections: ray-pair graph (k_ray_prep, k_ray_pairs + radix sort), ray / boundary clip; no mesh needed
+//   equirect.hip     360-degree photos: perspective views resampled from an equirectangular image (k_equirect_view)
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 

@@ -341,6 +341,27 @@ enum { GR_DTYPE_U8 = 0, GR_DTYPE_F32 = 1, GR_DTYPE_F64 = 2 };
 int gr_resize_image_f64(gr_ctx *ctx, const void *src, int dtype, int h_in, int w_in, int C, int divide_by_255, int h_out,
                         int w_out, double *out, void *stream);
 
+/* 360-degree photos -- replaces utils/image.py:129-267 (perspective_from_equirectangular: the ray grid, flexible_inputs_warp
+ * of image.py:72-126 = skimage.transform.warp over scipy.ndimage.map_coordinates one channel at a time, then
+ * downscale_local_mean) as driven per folder by entrypoints/equirectangular_to_cube_mapped.py:45-166.  Resamples ONE
+ * perspective view of out_h x out_w pixels from the equirectangular image src (h_in x w_in x C interleaved, in its FILE dtype:
+ * GR_DTYPE_U8 or GR_DTYPE_F64; GR_DTYPE_F32 is not built: GR_EINVAL), which stays on the device across the views of a photo.
+ * Fused: every output pixel forms its oversample x oversample samples itself -- ray (x[col], -y[row], 1) normalised, rotated
+ * by rotation_h (HOST pointer, 9 doubles, row-major: the matrix of rotate_by_roll_pitch_yaw), atan2 / asin to
+ * (i, j) = ((0.5 - alt / pi) h_in, (hor / 2 pi + 0.5) w_in) clipped to [0, h_in - 1] x [0, w_in], sampled with column w_in
+ * reading column 0 (order 1: bilinear, taps outside read the fill 0 as "grid-constant" does; order 0: floor(x + 0.5)), the
+ * reference's value round trip ((v - value_min) / value_range, clip to channel_bounds (device, C x {lo, hi}), back, truncated
+ * toward zero for uint8) -- and stores their mean as f64; oversample == 1 stores the sample in the source dtype.  x, y: DEVICE
+ * f64 vectors of out_w * oversample and out_h * oversample ray coordinates, computed on the host as image.py:181-196 does.
+ * value_range > 0 (an image without variation never reaches the device).  Optional: mask (h_in x (w_in + 1) bytes, zeroed by
+ * the caller; every sample stores 1 at (rint(i), rint(j)); image.py:255-265, the fold of column w_in into column 0 is the
+ * caller's) and debug_ij (2 x ny x nx f64: the (i, j) of every sample; for tests).  Only enqueues work.  Added without a
+ * GR_VERSION bump. */
+int gr_equirect_view(gr_ctx *ctx, const void *src, int dtype, int h_in, int w_in, int C, const double *x, const double *y,
+                     const double *rotation_h, int out_h, int out_w, int oversample, int order, double value_min,
+                     double value_range, const double *channel_bounds, void *out, uint8_t *mask, double *debug_ij,
+                     void *stream);
+
 /* finalise -- meshes.py:2069-2082: summed[counts==0] = NaN; average = summed / counts.
  * votes_u32 (F x C) is converted to f64 `summed`; average and summed are F x C f64, counts_f64 is F f64. */
 int gr_finalize_votes(gr_ctx *ctx, const uint32_t *votes, const uint32_t *counts, int64_t F, int C, double *average,
