@@ -12,60 +12,57 @@ import threading
 from pathlib import Path
 from typing import Optional
 
-import numpy as np
-
 import os as _os
+
+import numpy as np
 
 # GEOGRAYPHER_AMD_LIB: a diagnostic build of the same library (geograypher_amd.build.build_variant) instead of the product's
 _LIB_PATH = Path(_os.environ.get("GEOGRAYPHER_AMD_LIB") or Path(__file__).resolve().parent / "csrc" / "libgeograster.so")
 _lib = None
 
+# The enumerators of include/geograster.h, name for name (tests/test_cabi.py parses the header and compares).
 GR_OK = 0
+GR_EINVAL = -1
+GR_EHIP = -2
+GR_ENOMEM = -3
+GR_ENOMESH = -4
+GR_EINDEX = -5
 GR_EOVERFLOW = -6
+GR_ENODEVICE = -7
 GR_FLAG_NEG1_IS_LAST_FACE = 1
 GR_FLAG_DEFER_CHECK = 2
 GR_CAM_FLOATS = 16
 GR_DTYPE_U8 = 0
 GR_DTYPE_F32 = 1
 GR_DTYPE_F64 = 2
-
-# every symbol include/geograster.h declares (tests check that the library exports each of them)
-EXPORTED_SYMBOLS = (
-    "gr_version",
-    "gr_ctx_create",
-    "gr_ctx_destroy",
-    "gr_last_error",
-    "gr_set_profiling",
-    "gr_set_option",
-    "gr_learned_cache_file",
-    "gr_learned_cache_clear",
-    "gr_get_stage_times",
-    "gr_mesh_upload",
-    "gr_raster_face_ids",
-    "gr_raster_status",
-    "gr_raster_overflow_causes",
-    "gr_gather_texture_f64",
-    "gr_project_labels_u8",
-    "gr_project_values_f64",
-    "gr_project_view_f64",
-    "gr_raster_project_labels_u8",
-    "gr_gather_texture_u8",
-    "gr_project_index_pairs",
-    "gr_project_rect_pairs",
-    "gr_count_pairs",
-    "gr_ray_pairs",
-    "gr_ray_pairs_tile",
-    "gr_rays_clip",
-    "gr_warp_nearest_i32",
-    "gr_warp_f64",
-    "gr_invert_distortion_f64",
-    "gr_resize_image_f64",
-    "gr_equirect_view",
-    "gr_finalize_votes",
-    "gr_finalize_sums_f64",
-    "gr_argmax_nonzero",
-    "gr_argmax_nonzero_f64",
-)
+# keys of set_option
+GR_OPT_TILE_H_LOG2 = 2
+GR_OPT_BATCH = 3
+GR_OPT_DIRECT_CAP = 6
+GR_OPT_VARIANT = 7
+GR_OPT_SHARE_LEARNED = 8
+GR_OPT_DIRECT_BUDGET_MB = 9
+GR_OPT_VERTEX_ORDER = 10
+GR_OPT_DEBUG_LDS = 98
+GR_OPT_DEBUG = 99
+# bits of GR_OPT_VARIANT
+GR_VAR_ONE_TILE = 1
+GR_VAR_VOTES_INLINE = 4
+GR_VAR_CHAINS = 16
+GR_VAR_ENT48 = 128
+GR_VAR_GENERAL_IDS = 512
+GR_VAR_MICRO_NEVER = 4096
+GR_VAR_MICRO_ALWAYS = 8192
+GR_VAR_NO_LOOK = 16384
+GR_VAR_PACKED_COUNTERS = 131072
+# bits of GR_OPT_DEBUG
+GR_DBG_POISON_SLOTS = 512
+GR_DBG_POISON_RAYS = 1024
+GR_DBG_RAY_GRID_7 = 2048
+# bits of overflow_causes()
+GR_CAUSE_LIST_OUTGREW = 1
+GR_CAUSE_SHORT_MISS = 2
+GR_CAUSE_LISTS_MET = 4
 
 
 class StageTimes(ctypes.Structure):
@@ -102,6 +99,50 @@ class RasterStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+_vp, _i32, _i64, _f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
+_i64p, _f64p = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)
+# Every symbol include/geograster.h declares -> its argument types (tests check that the header declares and the library
+# exports exactly these).  All return int, gr_last_error excepted.
+_SIGNATURES = {
+    "gr_version": [],
+    "gr_ctx_create": [_i32, ctypes.POINTER(_vp)],
+    "gr_ctx_destroy": [_vp],
+    "gr_last_error": [_vp],
+    "gr_set_profiling": [_vp, _i32],
+    "gr_set_option": [_vp, _i32, _i32],
+    "gr_learned_cache_file": [ctypes.c_char_p],
+    "gr_learned_cache_clear": [],
+    "gr_get_stage_times": [_vp, ctypes.POINTER(StageTimes)],
+    "gr_mesh_upload": [_vp, _vp, _vp, _i64, _i64, _vp],
+    "gr_raster_face_ids": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "gr_raster_status": [_vp, ctypes.POINTER(RasterStats)],
+    "gr_raster_overflow_causes": [_vp],
+    "gr_gather_texture_f64": [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp],
+    "gr_project_labels_u8": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp],
+    "gr_project_values_f64": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp],
+    "gr_project_view_f64": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp],
+    "gr_raster_project_labels_u8": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp],
+    "gr_gather_texture_u8": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp],
+    "gr_project_index_pairs": [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp],
+    "gr_project_rect_pairs": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp],
+    "gr_count_pairs": [_vp, _vp, _i64, _vp, _vp, _i64p, _vp],
+    "gr_ray_pairs": [_vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _i64, _i64p, _vp],
+    "gr_ray_pairs_tile": [_i64, _i64, _i64p, _i64p],
+    "gr_rays_clip": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
+    "gr_warp_nearest_i32": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, ctypes.c_int32, _i32, _f64, _f64, _vp, _vp],
+    "gr_warp_f64": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _f64, _vp, _vp],
+    "gr_invert_distortion_f64": [_vp, _f64p, _i32, _i32, _f64, _i32, _f64, _vp, _vp, _vp],
+    "gr_resize_image_f64": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
+    "gr_equirect_view": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _f64p, _i32, _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp,
+                         _vp, _vp],
+    "gr_finalize_votes": [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
+    "gr_finalize_sums_f64": [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "gr_argmax_nonzero": [_vp, _vp, _i32, _i64, _i32, _vp, _vp],
+    "gr_argmax_nonzero_f64": [_vp, _vp, _i64, _i32, _vp, _vp],
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+
 def library_path() -> Path:
     return _LIB_PATH
 
@@ -122,77 +163,10 @@ def load_library() -> ctypes.CDLL:
     # library's runtime without devices and gr_ctx_create answers GR_ENODEVICE.
     _torch()
     lib = ctypes.CDLL(str(_LIB_PATH))
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    lib.gr_version.restype = i32
-    lib.gr_version.argtypes = []
-    lib.gr_ctx_create.restype = i32
-    lib.gr_ctx_create.argtypes = [i32, ctypes.POINTER(vp)]
-    lib.gr_ctx_destroy.restype = i32
-    lib.gr_ctx_destroy.argtypes = [vp]
-    lib.gr_last_error.restype = ctypes.c_char_p
-    lib.gr_last_error.argtypes = [vp]
-    lib.gr_set_profiling.restype = i32
-    lib.gr_set_profiling.argtypes = [vp, i32]
-    lib.gr_set_option.restype = i32
-    lib.gr_set_option.argtypes = [vp, i32, i32]
-    lib.gr_get_stage_times.restype = i32
-    lib.gr_get_stage_times.argtypes = [vp, ctypes.POINTER(StageTimes)]
-    lib.gr_mesh_upload.restype = i32
-    lib.gr_mesh_upload.argtypes = [vp, vp, vp, i64, i64, vp]
-    lib.gr_raster_face_ids.restype = i32
-    lib.gr_raster_face_ids.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
-    lib.gr_raster_status.restype = i32
-    lib.gr_raster_status.argtypes = [vp, ctypes.POINTER(RasterStats)]
-    lib.gr_raster_overflow_causes.restype = i32
-    lib.gr_raster_overflow_causes.argtypes = [vp]
-    lib.gr_gather_texture_f64.restype = i32
-    lib.gr_gather_texture_f64.argtypes = [vp, vp, i64, vp, i64, i32, vp, vp]
-    lib.gr_project_labels_u8.restype = i32
-    lib.gr_project_labels_u8.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
-    lib.gr_project_values_f64.restype = i32
-    lib.gr_project_values_f64.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
-    lib.gr_project_view_f64.restype = i32
-    lib.gr_project_view_f64.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp]
-    lib.gr_raster_project_labels_u8.restype = i32
-    lib.gr_raster_project_labels_u8.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]
-    f64 = ctypes.c_double
-    lib.gr_gather_texture_u8.restype = i32
-    lib.gr_gather_texture_u8.argtypes = [vp, vp, i64, vp, i64, i32, i32, vp, vp]
-    lib.gr_project_index_pairs.restype = i32
-    lib.gr_project_index_pairs.argtypes = [vp, vp, vp, i32, i32, i32, i64, vp, vp, i64, vp, i32, vp]
-    lib.gr_project_rect_pairs.restype = i32
-    lib.gr_project_rect_pairs.argtypes = [vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, i64, vp, i32, vp]
-    lib.gr_count_pairs.restype = i32
-    lib.gr_count_pairs.argtypes = [vp, vp, i64, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
-    lib.gr_ray_pairs.restype = i32
-    lib.gr_ray_pairs.argtypes = [vp, vp, vp, vp, i64, f64, vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64), vp]
-    lib.gr_ray_pairs_tile.restype = i32
-    lib.gr_ray_pairs_tile.argtypes = [i64, i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
-    lib.gr_rays_clip.restype = i32
-    lib.gr_rays_clip.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]
-    lib.gr_warp_nearest_i32.restype = i32
-    lib.gr_warp_nearest_i32.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, ctypes.c_int32, i32, f64, f64, vp, vp]
-    lib.gr_warp_f64.restype = i32
-    lib.gr_warp_f64.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, f64, vp, vp]
-    lib.gr_invert_distortion_f64.restype = i32
-    lib.gr_invert_distortion_f64.argtypes = [vp, ctypes.POINTER(f64), i32, i32, f64, i32, f64, vp, vp, vp]
-    lib.gr_resize_image_f64.restype = i32
-    lib.gr_resize_image_f64.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
-    lib.gr_equirect_view.restype = i32
-    lib.gr_equirect_view.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, ctypes.POINTER(f64), i32, i32, i32, i32, f64, f64, vp,
-                                     vp, vp, vp, vp]
-    lib.gr_learned_cache_file.restype = i32
-    lib.gr_learned_cache_file.argtypes = [ctypes.c_char_p]
-    lib.gr_learned_cache_clear.restype = i32
-    lib.gr_learned_cache_clear.argtypes = []
-    lib.gr_finalize_votes.restype = i32
-    lib.gr_finalize_votes.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp]
-    lib.gr_finalize_sums_f64.restype = i32
-    lib.gr_finalize_sums_f64.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp]
-    lib.gr_argmax_nonzero.restype = i32
-    lib.gr_argmax_nonzero.argtypes = [vp, vp, i32, i64, i32, vp, vp]
-    lib.gr_argmax_nonzero_f64.restype = i32
-    lib.gr_argmax_nonzero_f64.argtypes = [vp, vp, i64, i32, vp, vp]
+    for name, argtypes in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
+        fn.argtypes = argtypes
     _lib = lib
     _attach_learned_cache(lib)
     return lib
@@ -202,11 +176,9 @@ def _attach_learned_cache(lib):
     """What overflowed raster calls taught the library (slots per tile, entry form per mesh and image size) is kept under
     the reference's CACHE_FOLDER (constants.py:18, the default of pix2face's `cache_folder`), so that a new process starts
     with bins that fit.  GEOGRAYPHER_AMD_CACHE=<dir> moves the file, GEOGRAYPHER_AMD_CACHE=off switches persistence off."""
-    import os
-
     from geograypher_amd.constants import CACHE_FOLDER
 
-    where = os.environ.get("GEOGRAYPHER_AMD_CACHE", str(CACHE_FOLDER))
+    where = _os.environ.get("GEOGRAYPHER_AMD_CACHE", str(CACHE_FOLDER))
     if where.lower() in ("off", "0", ""):
         return
     try:
@@ -226,8 +198,7 @@ class _StatsAccumulator:
     """Statistics of a checked raster call over its attempts: an attempt that overflowed contributes the views it
     completed (records and entries are summed over the views a call processed, so they are scaled by the completed share);
     `max_entries` is the largest per-tile (single-pass) or per-view (exact binning) count any attempt saw;
-    `overflow_causes` the OR of every attempt's causes (gr_raster_overflow_causes: 1 a list outgrew its slots, 2 a face missed
-    the 40-byte entry form, 4 a tile's entry and micro lists met)."""
+    `overflow_causes` the OR of every attempt's causes (GR_CAUSE_*)."""
 
     def __init__(self):
         self.records = 0.0
@@ -310,12 +281,8 @@ class PairAccumulator:
             return
         if self.bound + n * b.n_faces > self.cap:
             self._compact()
-        with torch.cuda.device(b.device):
-            rc = b.lib.gr_project_index_pairs(
-                b._ctx, ids_t.data_ptr(), img_t.contiguous().data_ptr(), n, h, w, self.n_classes, self.counts.data_ptr(),
-                self.keys.data_ptr(), self.cap, self.key_count.data_ptr(), self.flags, b._stream(),
-            )
-        b._check(rc, "gr_project_index_pairs")
+        b._call("gr_project_index_pairs", ids_t.data_ptr(), img_t.contiguous().data_ptr(), n, h, w, self.n_classes,
+                self.counts.data_ptr(), self.keys.data_ptr(), self.cap, self.key_count.data_ptr(), self.flags, b._stream())
         self.bound += n * b.n_faces
 
     def add_rects(self, ids, rects, offsets):
@@ -349,12 +316,8 @@ class PairAccumulator:
         table = b._dev(np.concatenate([offsets.astype(np.int32), rects.astype(np.int32).reshape(-1)]), torch.int32)
         offs_ptr = table.data_ptr()
         rects_ptr = offs_ptr + 4 * (n + 1)
-        with torch.cuda.device(b.device):
-            rc = b.lib.gr_project_rect_pairs(
-                b._ctx, ids_t.data_ptr(), rects_ptr, offs_ptr, n, h, w, self.n_classes, self.counts.data_ptr(),
-                self.keys.data_ptr(), self.cap, self.key_count.data_ptr(), self.flags, b._stream(),
-            )
-        b._check(rc, "gr_project_rect_pairs")
+        b._call("gr_project_rect_pairs", ids_t.data_ptr(), rects_ptr, offs_ptr, n, h, w, self.n_classes,
+                self.counts.data_ptr(), self.keys.data_ptr(), self.cap, self.key_count.data_ptr(), self.flags, b._stream())
         self.bound += n * b.n_faces
 
     def _fit_mesh(self):
@@ -366,22 +329,12 @@ class PairAccumulator:
             self.keys = _torch().empty((self.cap,), dtype=_torch().int64, device=self.b.device)
 
     def _compact(self):
-        torch = _torch()
-        b = self.b
         raw, bad = (int(x) for x in self.key_count.cpu().tolist())
         if bad:
             raise IndexError(f"gr_project_index_pairs / gr_project_rect_pairs: an image value is not a class index in "
                              f"[0, {self.n_classes})")
         if raw > 0:
-            uniq = torch.empty((raw,), dtype=torch.int64, device=b.device)
-            mult = torch.empty((raw,), dtype=torch.int32, device=b.device)
-            n_unique = ctypes.c_int64(0)
-            with torch.cuda.device(b.device):
-                rc = b.lib.gr_count_pairs(b._ctx, self.keys.data_ptr(), raw, uniq.data_ptr(), mult.data_ptr(),
-                                          ctypes.byref(n_unique), b._stream())
-            b._check(rc, "gr_count_pairs")
-            k = int(n_unique.value)
-            self.parts.append((uniq[:k].cpu().numpy(), mult[:k].cpu().numpy().astype(np.int64)))
+            self.parts.append(self.b._count_pairs(self.keys, raw))
             self.compactions += 1
         self.key_count.zero_()
         self.bound = 0
@@ -473,11 +426,28 @@ class HipRaster:
             return
         msg = self.lib.gr_last_error(self._ctx)
         msg = msg.decode("utf-8", "replace") if msg else ""
-        if rc == -1:
+        if rc == GR_EINVAL:
             raise ValueError(f"{what}: {msg}")
-        if rc == -5:
+        if rc == GR_EINDEX:
             raise IndexError(f"{what}: {msg}")
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")
+
+    def _call(self, name: str, *args):
+        """lib.<name>(ctx, *args) with this backend's device current; a code other than GR_OK raises (`_check`)."""
+        with _torch().cuda.device(self.device):
+            rc = getattr(self.lib, name)(self._ctx, *args)
+        self._check(rc, name)
+
+    def _count_pairs(self, keys, n: int):
+        """gr_count_pairs over the first n > 0 pair keys of a device buffer: (distinct keys, multiplicities), int64 numpy."""
+        torch = _torch()
+        uniq = torch.empty((n,), dtype=torch.int64, device=self.device)
+        mult = torch.empty((n,), dtype=torch.int32, device=self.device)
+        n_unique = ctypes.c_int64(0)
+        self._call("gr_count_pairs", keys.data_ptr(), n, uniq.data_ptr(), mult.data_ptr(), ctypes.byref(n_unique),
+                   self._stream())
+        k = int(n_unique.value)
+        return uniq[:k].cpu().numpy(), mult[:k].cpu().numpy().astype(np.int64)
 
     def _dev(self, array, dtype):
         """numpy / tensor -> contiguous tensor of `dtype` on this device (no copy when already there)."""
@@ -490,8 +460,9 @@ class HipRaster:
         self._check(self.lib.gr_set_profiling(self._ctx, 1 if enabled else 0), "gr_set_profiling")
 
     def set_option(self, key: int, value: int):
-        """Tuning knobs of include/geograster.h (GR_OPT_*): 2 tile height log2, 3 views per launch group, 6 single-pass
-        slots per tile (0 = exact binning), 7 variant bits (see GR_OPT_VARIANT in the header)."""
+        """Tuning knobs of include/geograster.h, by name: key one of this module's GR_OPT_* (GR_OPT_TILE_H_LOG2,
+        GR_OPT_BATCH, GR_OPT_DIRECT_CAP: 0 = exact binning, ...); GR_OPT_VARIANT takes the OR of GR_VAR_*, GR_OPT_DEBUG that
+        of GR_DBG_*."""
         self._check(self.lib.gr_set_option(self._ctx, int(key), int(value)), "gr_set_option")
 
     def set_vertex_order(self, name: str):
@@ -500,7 +471,7 @@ class HipRaster:
         window centre).  The only option results depend on."""
         if name not in ("r1", "gl"):
             raise ValueError(f"vertex_order must be 'r1' or 'gl', got {name!r}")
-        self.set_option(10, 1 if name == "gl" else 0)
+        self.set_option(GR_OPT_VERTEX_ORDER, 1 if name == "gl" else 0)
         self.vertex_order = name
 
     def stage_times(self) -> dict:
@@ -516,9 +487,7 @@ class HipRaster:
         f = self._dev(faces, torch.int32)
         if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
             raise ValueError(f"mesh must be (V,3) vertices and (F,3) faces, got {tuple(v.shape)} and {tuple(f.shape)}")
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_mesh_upload(self._ctx, v.data_ptr(), f.data_ptr(), v.shape[0], f.shape[0], self._stream())
-        self._check(rc, "gr_mesh_upload")
+        self._call("gr_mesh_upload", v.data_ptr(), f.data_ptr(), v.shape[0], f.shape[0], self._stream())
         self._verts, self._faces = v, f  # borrowed by the library: keep alive
         self.n_verts, self.n_faces = int(v.shape[0]), int(f.shape[0])
 
@@ -541,32 +510,34 @@ class HipRaster:
         elif tuple(out.shape) != (n, h, w) or out.dtype != torch.int32 or not out.is_contiguous():
             raise ValueError("out must be a contiguous int32 tensor of shape (N,h,w)")
         depth = torch.empty((n, h, w), dtype=torch.float32, device=self.device) if want_depth else None
+        self._checked_raster(n, check, lambda v0: self._call(
+            "gr_raster_face_ids", cams_t[v0:].data_ptr(), n - v0, h, w, out[v0:].data_ptr(),
+            depth[v0:].data_ptr() if depth is not None else None, self._stream()))
+        return (out, depth) if want_depth else out
+
+    def _checked_raster(self, n: int, check: bool, launch):
+        """The attempts of a raster call over n views: `launch(v0)` enqueues views v0 .. n - 1.  With `check`, the status is
+        read back and, while it says GR_EOVERFLOW, the call is repeated from the first unfinished view -- the library has
+        recorded the need -- four attempts at most; `last_retries` and `last_stats` describe all of them."""
         v0 = 0
         self.last_retries = 0
         acc = _StatsAccumulator()
         for attempt in range(4):
-            with torch.cuda.device(self.device):
-                rc = self.lib.gr_raster_face_ids(
-                    self._ctx, cams_t[v0:].data_ptr(), n - v0, h, w, out[v0:].data_ptr(),
-                    depth[v0:].data_ptr() if depth is not None else None, self._stream(),
-                )
-            self._check(rc, "gr_raster_face_ids")
+            launch(v0)
             if not check:
                 self.last_stats = {"unchecked": True}
-                break
+                return
             st = RasterStats()
             rc = self.lib.gr_raster_status(self._ctx, ctypes.byref(st))
             causes = self.lib.gr_raster_overflow_causes(self._ctx)
-            if rc == GR_EOVERFLOW and attempt < 3:
-                acc.add(st, n - v0, partial=True, causes=causes)
-                v0 += int(st.views_done)  # the library has recorded the need; only the unfinished views are repeated
-                self.last_retries += 1
-                continue
-            self._check(rc, "gr_raster_status")
-            acc.add(st, n - v0, partial=False, causes=causes)
-            self.last_stats = acc.result()
-            break
-        return (out, depth) if want_depth else out
+            if rc != GR_EOVERFLOW or attempt == 3:
+                self._check(rc, "gr_raster_status")
+                acc.add(st, n - v0, partial=False, causes=causes)
+                self.last_stats = acc.result()
+                return
+            acc.add(st, n - v0, partial=True, causes=causes)
+            v0 += int(st.views_done)  # only the unfinished views are repeated
+            self.last_retries += 1
 
     def raster_status(self) -> dict:
         st = RasterStats()
@@ -575,8 +546,8 @@ class HipRaster:
 
     def overflow_causes(self) -> int:
         """Why the last raster call overflowed, as far as `raster_status()` (or the call's own check) has read it: the OR of
-        1 (a tile list outgrew its slots), 2 (a face missed the 40-byte entry form) and 4 (a tile's entry and micro lists
-        met); 0 for a call without overflow."""
+        GR_CAUSE_LIST_OUTGREW (a tile list outgrew its slots), GR_CAUSE_SHORT_MISS (a face missed the 40-byte entry form) and
+        GR_CAUSE_LISTS_MET (a tile's entry and micro lists met); 0 for a call without overflow."""
         return int(self.lib.gr_raster_overflow_causes(self._ctx))
 
     # -- render_flat gather --------------------------------------------------------------------------------------
@@ -587,11 +558,8 @@ class HipRaster:
         tex = self._dev(face_texture, torch.float64)
         F, C = int(tex.shape[0]), int(tex.shape[1])
         out = torch.empty(tuple(ids_t.shape) + (C,), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_gather_texture_f64(
-                self._ctx, ids_t.data_ptr(), ids_t.numel(), tex.data_ptr(), F, C, out.data_ptr(), self._stream()
-            )
-        self._check(rc, "gr_gather_texture_f64")
+        self._call("gr_gather_texture_f64", ids_t.data_ptr(), ids_t.numel(), tex.data_ptr(), F, C, out.data_ptr(),
+                   self._stream())
         return out
 
     def gather_texture_u8(self, ids, face_texture, null_value: int = 0):
@@ -601,12 +569,8 @@ class HipRaster:
         tex = self._dev(face_texture, torch.float64)
         F, C = int(tex.shape[0]), int(tex.shape[1])
         out = torch.empty(tuple(ids_t.shape) + (C,), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_gather_texture_u8(
-                self._ctx, ids_t.data_ptr(), ids_t.numel(), tex.data_ptr(), F, C, int(null_value), out.data_ptr(),
-                self._stream(),
-            )
-        self._check(rc, "gr_gather_texture_u8")
+        self._call("gr_gather_texture_u8", ids_t.data_ptr(), ids_t.numel(), tex.data_ptr(), F, C, int(null_value),
+                   out.data_ptr(), self._stream())
         return out
 
     def project_index_pairs(self, ids, img, n_classes: int, counts, neg1_is_last_face: bool = True):
@@ -627,24 +591,12 @@ class HipRaster:
         keys = torch.empty((max(cap, 1),), dtype=torch.int64, device=self.device)
         key_count = torch.zeros((1,), dtype=torch.int64, device=self.device)
         flags = GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_project_index_pairs(
-                self._ctx, ids_t.data_ptr(), img_t.contiguous().data_ptr(), n, h, w, int(n_classes), counts.data_ptr(),
-                keys.data_ptr(), cap, key_count.data_ptr(), flags, self._stream(),
-            )
-        self._check(rc, "gr_project_index_pairs")
+        self._call("gr_project_index_pairs", ids_t.data_ptr(), img_t.contiguous().data_ptr(), n, h, w, int(n_classes),
+                   counts.data_ptr(), keys.data_ptr(), cap, key_count.data_ptr(), flags, self._stream())
         m = int(key_count.item())
         if m == 0:
             return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
-        uniq = torch.empty((m,), dtype=torch.int64, device=self.device)
-        mult = torch.empty((m,), dtype=torch.int32, device=self.device)
-        n_unique = ctypes.c_int64(0)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_count_pairs(self._ctx, keys.data_ptr(), m, uniq.data_ptr(), mult.data_ptr(),
-                                         ctypes.byref(n_unique), self._stream())
-        self._check(rc, "gr_count_pairs")
-        k = int(n_unique.value)
-        return uniq[:k].cpu().numpy(), mult[:k].cpu().numpy().astype(np.int64)
+        return self._count_pairs(keys, m)
 
     def new_pair_accumulator(self, n_classes: int, counts, neg1_is_last_face: bool = True):
         """Sparse index aggregation over MANY views with the (face, class) pair keys kept on the device: `add(ids, img)` per
@@ -656,13 +608,10 @@ class HipRaster:
 
     def ray_pair_count(self, starts, ends, ray_ids, threshold: float) -> int:
         """Number of edges `ray_pair_edges` would return (gr_ray_pairs with no edge buffer: the count alone)."""
-        torch = _torch()
         s_t, e_t, id_t = self._ray_inputs(starts, ends, ray_ids)
         total = ctypes.c_int64(0)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_ray_pairs(self._ctx, s_t.data_ptr(), e_t.data_ptr(), id_t.data_ptr(), int(s_t.shape[0]),
-                                       float(threshold), None, None, None, 0, ctypes.byref(total), self._stream())
-        self._check(rc, "gr_ray_pairs")
+        self._call("gr_ray_pairs", s_t.data_ptr(), e_t.data_ptr(), id_t.data_ptr(), int(s_t.shape[0]), float(threshold),
+                   None, None, None, 0, ctypes.byref(total), self._stream())
         return int(total.value)
 
     def ray_pair_edges(self, starts, ends, ray_ids, threshold: float, capacity: Optional[int] = None):
@@ -726,11 +675,8 @@ class HipRaster:
         hit = torch.zeros((n,), dtype=torch.int32, device=self.device)
         t = torch.full((n,), float("nan"), dtype=torch.float64, device=self.device)
         pts = torch.full((n, 3), float("nan"), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_rays_clip(self._ctx, o_t.data_ptr(), d_t.data_ptr(), n, p_t.data_ptr(), int(p_t.shape[0]),
-                                       f_t.data_ptr(), int(f_t.shape[0]), hit.data_ptr(), t.data_ptr(), pts.data_ptr(),
-                                       self._stream())
-        self._check(rc, "gr_rays_clip")
+        self._call("gr_rays_clip", o_t.data_ptr(), d_t.data_ptr(), n, p_t.data_ptr(), int(p_t.shape[0]), f_t.data_ptr(),
+                   int(f_t.shape[0]), hit.data_ptr(), t.data_ptr(), pts.data_ptr(), self._stream())
         return hit.to(torch.bool), t, pts
 
     # -- projection / aggregation --------------------------------------------------------------------------------
@@ -751,12 +697,8 @@ class HipRaster:
             raise ValueError(f"ids {tuple(ids_t.shape)} and labels {tuple(lab_t.shape)} differ in shape")
         n, h, w = (int(x) for x in ids_t.shape)
         flags = GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_project_labels_u8(
-                self._ctx, ids_t.data_ptr(), lab_t.data_ptr(), n, h, w, C, votes.data_ptr(), counts.data_ptr(), flags,
-                self._stream(),
-            )
-        self._check(rc, "gr_project_labels_u8")
+        self._call("gr_project_labels_u8", ids_t.data_ptr(), lab_t.data_ptr(), n, h, w, C, votes.data_ptr(),
+                   counts.data_ptr(), flags, self._stream())
 
     def project_values(self, ids, img, sums, counts, neg1_is_last_face: bool = True):
         """ids (N,h,w) int32, img (N,h,w,C) float64; accumulates nansum into sums (F,C) and counts (F,)."""
@@ -770,12 +712,8 @@ class HipRaster:
         if tuple(img_t.shape) != (n, h, w, C):
             raise ValueError(f"img {tuple(img_t.shape)} does not match ids {tuple(ids_t.shape)}")
         flags = GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_project_values_f64(
-                self._ctx, ids_t.data_ptr(), img_t.data_ptr(), n, h, w, C, sums.data_ptr(), counts.data_ptr(), flags,
-                self._stream(),
-            )
-        self._check(rc, "gr_project_values_f64")
+        self._call("gr_project_values_f64", ids_t.data_ptr(), img_t.data_ptr(), n, h, w, C, sums.data_ptr(),
+                   counts.data_ptr(), flags, self._stream())
 
     def project_view(self, ids, img, neg1_is_last_face: bool = True):
         """One view of project_images: ids (h,w) int32, img (h,w,C) float64 -> (F,C) float64, NaN for unseen faces."""
@@ -788,11 +726,7 @@ class HipRaster:
             raise ValueError(f"img {tuple(img_t.shape)} does not match ids {tuple(ids_t.shape)}")
         tex = torch.empty((self.n_faces, C), dtype=torch.float64, device=self.device)
         flags = GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_project_view_f64(
-                self._ctx, ids_t.data_ptr(), img_t.data_ptr(), h, w, C, tex.data_ptr(), flags, self._stream()
-            )
-        self._check(rc, "gr_project_view_f64")
+        self._call("gr_project_view_f64", ids_t.data_ptr(), img_t.data_ptr(), h, w, C, tex.data_ptr(), flags, self._stream())
         return tex
 
     def raster_project_labels(self, cams, labels, C: int, votes, counts, ids_out=None, neg1_is_last_face: bool = True,
@@ -808,36 +742,14 @@ class HipRaster:
         if cams_t.shape[0] != n:
             raise ValueError(f"{cams_t.shape[0]} camera records for {n} label images")
         flags = GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
-        v0 = 0
-        self.last_retries = 0
-        acc = _StatsAccumulator()
-        for attempt in range(4):
-            with torch.cuda.device(self.device):
-                rc = self.lib.gr_raster_project_labels_u8(
-                    self._ctx, cams_t[v0:].data_ptr(), lab_t[v0:].data_ptr(), n - v0, h, w, C, votes.data_ptr(),
-                    counts.data_ptr(), ids_out[v0:].data_ptr() if ids_out is not None else None, flags, self._stream(),
-                )
-            self._check(rc, "gr_raster_project_labels_u8")
-            if not check:
-                self.last_stats = {"unchecked": True}
-                break
-            st = RasterStats()
-            rc = self.lib.gr_raster_status(self._ctx, ctypes.byref(st))
-            causes = self.lib.gr_raster_overflow_causes(self._ctx)
-            if rc == GR_EOVERFLOW and attempt < 3:
-                # the votes of the first views_done views are in; the library skipped the rest on the device
-                acc.add(st, n - v0, partial=True, causes=causes)
-                v0 += int(st.views_done)
-                self.last_retries += 1
-                continue
-            self._check(rc, "gr_raster_status")
-            acc.add(st, n - v0, partial=False, causes=causes)
-            self.last_stats = acc.result()
-            break
+        # (after an overflow the votes of the first views_done views are in; the library skipped the rest on the device)
+        self._checked_raster(n, check, lambda v0: self._call(
+            "gr_raster_project_labels_u8", cams_t[v0:].data_ptr(), lab_t[v0:].data_ptr(), n - v0, h, w, C, votes.data_ptr(),
+            counts.data_ptr(), ids_out[v0:].data_ptr() if ids_out is not None else None, flags, self._stream()))
         return ids_out
 
     # -- get_image(image_scale) behind the file read (row a5) -----------------------------------------------------
-    _RESIZE_DTYPES = {"uint8": 0, "float32": 1, "float64": 2}
+    _RESIZE_DTYPES = {"uint8": GR_DTYPE_U8, "float32": GR_DTYPE_F32, "float64": GR_DTYPE_F64}
 
     def resize_image(self, image, out_hw=None, divide_by_255: Optional[bool] = None):
         """cameras.py:154-174 on the device: `image` ((H,W) or (H,W,C); numpy or tensor, uint8 / float32 / float64, in the dtype
@@ -865,10 +777,8 @@ class HipRaster:
         if divide_by_255 is None:
             divide_by_255 = name == "uint8"
         out = torch.empty((h_out, w_out) + tuple(t.shape[2:]), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_resize_image_f64(self._ctx, t.data_ptr(), self._RESIZE_DTYPES[name], h_in, w_in, C,
-                                              1 if divide_by_255 else 0, h_out, w_out, out.data_ptr(), self._stream())
-        self._check(rc, "gr_resize_image_f64")
+        self._call("gr_resize_image_f64", t.data_ptr(), self._RESIZE_DTYPES[name], h_in, w_in, C, 1 if divide_by_255 else 0,
+                   h_out, w_out, out.data_ptr(), self._stream())
         return out
 
     # -- 360-degree photos: perspective views of an equirectangular image -------------------------------------------
@@ -948,11 +858,10 @@ class HipRaster:
                 xy = torch.as_tensor(np.concatenate([x, y])).to(self.device)
                 R = (ctypes.c_double * 9)(*[float(v) for v in np.asarray(rot, dtype=np.float64).reshape(9)])
                 dtype = GR_DTYPE_U8 if source.np_dtype == np.uint8 else GR_DTYPE_F64
-                rc = self.lib.gr_equirect_view(
-                    self._ctx, source.tensor.data_ptr(), dtype, H, W, C, xy.data_ptr(), xy.data_ptr() + 8 * len(x), R, out_h,
-                    out_w, os_, int(order), source.vmin, vrange, bounds.data_ptr(), out.data_ptr(),
-                    mask.data_ptr() if mask is not None else None, dbg.data_ptr() if dbg is not None else None, self._stream())
-                self._check(rc, "gr_equirect_view")
+                self._call("gr_equirect_view", source.tensor.data_ptr(), dtype, H, W, C, xy.data_ptr(),
+                           xy.data_ptr() + 8 * len(x), R, out_h, out_w, os_, int(order), source.vmin, vrange,
+                           bounds.data_ptr(), out.data_ptr(), mask.data_ptr() if mask is not None else None,
+                           dbg.data_ptr() if dbg is not None else None, self._stream())
             if mask is not None:   # image.py:261-265: the appended column belongs to column 0
                 mask[:, 0] |= mask[:, W]
                 mask = mask[:, :W]
@@ -986,10 +895,8 @@ class HipRaster:
             raise ValueError(f"Unexpected distortion params found: {sorted(unknown)}")
         par = (ctypes.c_double * 13)(*[float(params.get(k, 0.0)) for k in self.LENS_PARAMS])
         out = torch.empty((2, h, w), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_invert_distortion_f64(self._ctx, par, int(h), int(w), float(image_scale), int(max_iters),
-                                                   float(fill), out[0].data_ptr(), out[1].data_ptr(), self._stream())
-        self._check(rc, "gr_invert_distortion_f64")
+        self._call("gr_invert_distortion_f64", par, int(h), int(w), float(image_scale), int(max_iters), float(fill),
+                   out[0].data_ptr(), out[1].data_ptr(), self._stream())
         return out
 
     def warp_image(self, input_image, map_t, order: int = 1, fill_value: float = 0.0,
@@ -1037,12 +944,9 @@ class HipRaster:
                 for ch in range(src.shape[2]):
                     plane = src[..., ch].contiguous()
                     out = torch.empty((h_out, w_out), dtype=torch.int32, device=self.device)
-                    rc = self.lib.gr_warp_nearest_i32(
-                        self._ctx, plane.data_ptr(), h_in, w_in, map_t[0].data_ptr(), map_t[1].data_ptr(), h_out, w_out,
-                        int(fill_value), 1 if reference_float_roundtrip else 0, lo, hi - lo, out.data_ptr(),
-                        self._stream(),
-                    )
-                    self._check(rc, "gr_warp_nearest_i32")
+                    self._call("gr_warp_nearest_i32", plane.data_ptr(), h_in, w_in, map_t[0].data_ptr(), map_t[1].data_ptr(),
+                               h_out, w_out, int(fill_value), 1 if reference_float_roundtrip else 0, lo, hi - lo,
+                               out.data_ptr(), self._stream())
                     outs.append(out)
                 res = outs[0] if squeeze else torch.stack(outs, dim=-1)
             else:
@@ -1053,11 +957,8 @@ class HipRaster:
                 src = src.contiguous()
                 C = int(src.shape[2])
                 res = torch.empty((h_out, w_out, C), dtype=torch.float64, device=self.device)
-                rc = self.lib.gr_warp_f64(
-                    self._ctx, src.data_ptr(), h_in, w_in, C, map_t[0].data_ptr(), map_t[1].data_ptr(), h_out, w_out,
-                    int(order), float(fill_value), res.data_ptr(), self._stream(),
-                )
-                self._check(rc, "gr_warp_f64")
+                self._call("gr_warp_f64", src.data_ptr(), h_in, w_in, C, map_t[0].data_ptr(), map_t[1].data_ptr(), h_out,
+                           w_out, int(order), float(fill_value), res.data_ptr(), self._stream())
                 if squeeze:
                     res = res[..., 0]
         if is_tensor:
@@ -1071,12 +972,8 @@ class HipRaster:
         avg = torch.empty((F, C), dtype=torch.float64, device=self.device)
         summed = torch.empty((F, C), dtype=torch.float64, device=self.device)
         cnt = torch.empty((F,), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_finalize_votes(
-                self._ctx, votes.data_ptr(), counts.data_ptr(), F, C, avg.data_ptr(), summed.data_ptr(), cnt.data_ptr(),
-                self._stream(),
-            )
-        self._check(rc, "gr_finalize_votes")
+        self._call("gr_finalize_votes", votes.data_ptr(), counts.data_ptr(), F, C, avg.data_ptr(), summed.data_ptr(),
+                   cnt.data_ptr(), self._stream())
         return avg, summed, cnt
 
     def finalize_sums(self, sums, counts):
@@ -1084,11 +981,8 @@ class HipRaster:
         F, C = int(sums.shape[0]), int(sums.shape[1])
         avg = torch.empty((F, C), dtype=torch.float64, device=self.device)
         cnt = torch.empty((F,), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_finalize_sums_f64(
-                self._ctx, sums.data_ptr(), counts.data_ptr(), F, C, avg.data_ptr(), cnt.data_ptr(), self._stream()
-            )
-        self._check(rc, "gr_finalize_sums_f64")
+        self._call("gr_finalize_sums_f64", sums.data_ptr(), counts.data_ptr(), F, C, avg.data_ptr(), cnt.data_ptr(),
+                   self._stream())
         return avg, sums, cnt
 
     def argmax_nonzero(self, array):
@@ -1106,7 +1000,5 @@ class HipRaster:
         dtype = GR_DTYPE_F32 if is_f32 else GR_DTYPE_F64
         F, C = int(arr.shape[0]), int(arr.shape[1])
         out = torch.empty((F,), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gr_argmax_nonzero(self._ctx, arr.data_ptr(), dtype, F, C, out.data_ptr(), self._stream())
-        self._check(rc, "gr_argmax_nonzero")
+        self._call("gr_argmax_nonzero", arr.data_ptr(), dtype, F, C, out.data_ptr(), self._stream())
         return out

@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void k_cull_blocks(const float *__restrict__ c
     const int lane = threadIdx.x & 63;
     const int leader = __ffsll((long long)m) - 1;
     uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&ctrl[3], (uint32_t)__popcll(m));
+    if (lane == leader) base = atomicAdd(&ctrl[GR_CTRL_WORK], (uint32_t)__popcll(m));
     base = __shfl(base, leader);
     if (keep) a.work[(int64_t)slot * a.work_stride + base + __popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)b;
   }
@@ -297,7 +297,7 @@ __device__ __forceinline__ void bin_big_pairs(const BinArgs &a, uint32_t *__rest
     if (tile >= 0) {
       if (pos < (uint32_t)a.cap_tile) {
         store_entry(a, ctrl, comp, nr8, (int64_t)tile * a.cap_tile + pos, e0, e1, e2, rows);
-      } else atomicOr(&ctrl[2], 1u);
+      } else atomicOr(&ctrl[GR_CTRL_OVERFLOW], GR_WHY_OUTGREW);
     }
   }
 }
@@ -344,7 +344,7 @@ void k_setup_cull(const float *__restrict__ cams, BinArgs a) {
   const uint32_t *work = a.work + (int64_t)slot * a.work_stride;
   // every wave takes its own 64-face block from the view's work list (wave-uniform control flow, no workgroup barrier)
   const uint32_t wave0 = blockIdx.x * 4 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t n_work = ctrl[3];       // (a) blocks that passed k_cull_blocks for this view
+  const uint32_t n_work = ctrl[GR_CTRL_WORK];       // (a) blocks that passed k_cull_blocks for this view
   if (wave0 >= n_work) return;
   // The grid is sized by the MESH (bin_batch: a workgroup per 128 blocks before culling); how many blocks of the view survive
   // the cull is only known here.  The view's list goes to its first ceil(n_work / GR_SETUP_BPW) waves -- at least that many
@@ -417,7 +417,7 @@ void k_setup_cull(const float *__restrict__ cams, BinArgs a) {
   if (mc) {
     const int lead = __ffsll((long long)mc) - 1;
     uint32_t cb = 0;
-    if (lane == lead) cb = atomicAdd(&ctrl[4], (uint32_t)__popcll(mc));
+    if (lane == lead) cb = atomicAdd(&ctrl[GR_CTRL_CLIP], (uint32_t)__popcll(mc));
     cb = __shfl(cb, lead);
     if (clip_me) a.clip[(int64_t)slot * a.F + cb + __popcll(mc & ((1ull << lane) - 1ull))] = (uint32_t)f;
   }
@@ -500,7 +500,7 @@ void k_setup_cull(const float *__restrict__ cams, BinArgs a) {
   // atomic per block on the view's one address made every wave of the view queue there: same-address atomics are served
   // one after the other, tools/ubench/atomic_rate.hip)
   if (DIRECT) n_rec += (uint32_t)n;
-  else if (lane == leader) base = atomicAdd(&ctrl[0], (uint32_t)n);
+  else if (lane == leader) base = atomicAdd(&ctrl[GR_CTRL_RECORDS], (uint32_t)n);
   if (t00 >= 0 && lane == l0) b0 = atomicAdd(counter_of(t00), (uint32_t)n0);
   if (t01 >= 0 && lane == l1) b1 = atomicAdd(counter_of(t01), (uint32_t)n1);
   if (t10 >= 0 && lane == l2) b2 = atomicAdd(counter_of(t10), (uint32_t)n2);
@@ -534,7 +534,7 @@ void k_setup_cull(const float *__restrict__ cams, BinArgs a) {
         const uint32_t pos = (uint32_t)(k == 0 ? r3.x : k == 1 ? r3.y : k == 2 ? r3.z : r3.w);
         const int ncx = (jhi - jlo + 4) >> 2;   // 4-pixel columns of the part: 1 or 2
         // inside the segment (cap slots of 40 bytes).  This bounds the micro list alone: two lists that each fit here and in
-        // entry positions below cap can still meet -- k_bin_stats raises the view's overflow word for that (bit 4)
+        // entry positions below cap can still meet -- k_bin_stats raises the view's overflow word for that (GR_WHY_MET)
         if ((pos + (uint32_t)nk) * 4u <= (uint32_t)a.cap_tile * 5u) {
           // record p of the tile's list: the 32 bytes that end 32 p bytes before the end of the tile's segment
           char *const rec_end = segs + ((int64_t)(ty * a.TX + tx) + 1) * a.cap_tile * 40 - (int64_t)pos * 32;
@@ -546,7 +546,7 @@ void k_setup_cull(const float *__restrict__ cams, BinArgs a) {
             dst[0] = va;
             dst[1] = make_int4(r2.x, r2.y, (int)~(uint32_t)r1.w, c0 | ((c1 - c0) << 6) | (q0 << 8) | ((q1 - q0 + 1) << 14));
           }
-        } else atomicOr(&ctrl[2], 1u);
+        } else atomicOr(&ctrl[GR_CTRL_OVERFLOW], GR_WHY_OUTGREW);
       }
     }
   }
@@ -577,7 +577,7 @@ void k_setup_cull(const float *__restrict__ cams, BinArgs a) {
         build_entry(r0, r1, r2, tx0 << a.twl, ty0 << a.thl, TW, TH, e0, e1, e2, rows);
         if (first_general) {
           if ((uint32_t)r3.x < (uint32_t)a.cap_tile) store_entry(a, ctrl, comp, nr8, (int64_t)t00 * a.cap_tile + (uint32_t)r3.x, e0, e1, e2, rows);
-          else atomicOr(&ctrl[2], 1u);
+          else atomicOr(&ctrl[GR_CTRL_OVERFLOW], GR_WHY_OUTGREW);
         }
         vt[lane] = e0;                                          // c_first c_mid c_last | slopes a
         vt[64 + lane] = make_int4(e1.x, e1.z, e1.w, e2.x);      // slopes b | iz0 A B
@@ -611,7 +611,7 @@ void k_setup_cull(const float *__restrict__ cams, BinArgs a) {
           int rows;
           shifted_entry(b0, b1, b2, boxx, boxy, tx << a.twl, ty << a.thl, (k & 1) ? TW : 0, (k >> 1) ? TH : 0, TW, TH, e0, e1, e2, rows);
           store_entry(a, ctrl, comp, nr8, (int64_t)(ty * a.TX + tx) * a.cap_tile + pos, e0, e1, e2, rows);
-        } else atomicOr(&ctrl[2], 1u);
+        } else atomicOr(&ctrl[GR_CTRL_OVERFLOW], GR_WHY_OUTGREW);
       }
     }
   }
@@ -636,8 +636,8 @@ void k_setup_cull(const float *__restrict__ cams, BinArgs a) {
   }
   GR_SSTAMP(5);
   }  // work list loop
-  if (DIRECT && lane == 0 && n_rec) atomicAdd(&ctrl[0], n_rec);
-  if (DIRECT && lane == 0 && n_mic) atomicAdd(&ctrl[6], n_mic);
+  if (DIRECT && lane == 0 && n_rec) atomicAdd(&ctrl[GR_CTRL_RECORDS], n_rec);
+  if (DIRECT && lane == 0 && n_mic) atomicAdd(&ctrl[GR_CTRL_MICRO], n_mic);
 #ifdef GR_STAMPS
   if (lane == 0 && a.stamps) {  // the second half of the stamp buffer: 1024 slots of 16 words
     unsigned long long *sd = a.stamps + 16 * 1024 + 16 * ((blockIdx.x * 4 + (threadIdx.x >> 6) + blockIdx.y * 977) & 1023);
@@ -686,21 +686,21 @@ __global__ __launch_bounds__(1024) void k_bin_stats(BinArgs a) {
   if (threadIdx.x == 0) {
     unsigned long long total = 0; uint32_t m = 0, lists_met = 0;
     for (int k = 0; k < 16; ++k) { total += part[k]; m = max(m, pmax[k]); lists_met |= pmet[k]; }
-    ctrl[1] = (uint32_t)total;
+    ctrl[GR_CTRL_ENTRIES] = (uint32_t)total;
     // the view's overflow word: 1 a list outgrew its slots (k_setup_cull), 2 a face missed the 40-byte form (store_entry), 4 the
     // lists met.  Any bit keeps the fused tile kernel off the view's lists -- it runs after this kernel on the same stream
     // (fused calls never defer it) -- and the view is repeated like any overflow
-    uint32_t why = ctrl[2];
-    if (lists_met) { atomicOr(&ctrl[2], 4u); why |= 4u; }
-    atomicAdd(&a.stats[6], (unsigned long long)ctrl[3]);   // 64-face blocks that passed the frustum cull
+    uint32_t why = ctrl[GR_CTRL_OVERFLOW];
+    if (lists_met) { atomicOr(&ctrl[GR_CTRL_OVERFLOW], GR_WHY_MET); why |= GR_WHY_MET; }
+    atomicAdd(&a.stats[GR_ST_BLOCKS], (unsigned long long)ctrl[GR_CTRL_WORK]);   // 64-face blocks that passed the frustum cull
     const bool ovf = m > cap || why != 0;
-    atomicAdd(&a.stats[0], (unsigned long long)ctrl[0]);
-    atomicAdd(&a.stats[1], total);
-    atomicAdd(&a.stats[8], (unsigned long long)ctrl[6]);  // micro faces (pixel box at most 4 x 4)
-    atomicMax(&a.stats[2], (unsigned long long)m);  // direct mode: the largest per-tile count
-    if (ovf) { atomicMax(&a.stats[3], 1ull); atomicMin(&a.stats[4], (unsigned long long)a.group); }
-    if (why & 2u) atomicMax(&a.stats[5], 1ull);  // a face the 40-byte entry form cannot hold
-    if (why) atomicOr(&a.stats[10], (unsigned long long)why);   // the call's overflow causes (gr_raster_overflow_causes)
+    atomicAdd(&a.stats[GR_ST_RECORDS], (unsigned long long)ctrl[GR_CTRL_RECORDS]);
+    atomicAdd(&a.stats[GR_ST_ENTRIES], total);
+    atomicAdd(&a.stats[GR_ST_MICRO], (unsigned long long)ctrl[GR_CTRL_MICRO]);  // micro faces (pixel box at most 4 x 4)
+    atomicMax(&a.stats[GR_ST_MAX_ENTRIES], (unsigned long long)m);  // direct mode: the largest per-tile count
+    if (ovf) { atomicMax(&a.stats[GR_ST_OVERFLOW], 1ull); atomicMin(&a.stats[GR_ST_FIRST_GROUP], (unsigned long long)a.group); }
+    if (why & GR_WHY_SHORT_MISS) atomicMax(&a.stats[GR_ST_SHORT_MISS], 1ull);  // a face the 40-byte entry form cannot hold
+    if (why) atomicOr(&a.stats[GR_ST_CAUSES], (unsigned long long)why);   // the call's overflow causes (gr_raster_overflow_causes)
   }
 }
 
@@ -739,14 +739,14 @@ __global__ __launch_bounds__(1024) void k_scan_tiles(BinArgs a) {
   }
   if (tid == 0) {
     const uint32_t total = carry_s;
-    ctrl[1] = total;
+    ctrl[GR_CTRL_ENTRIES] = total;
     const bool ovf = (int64_t)total > a.ent_cap;
-    ctrl[2] = ovf ? 1u : 0u;
-    atomicAdd(&a.stats[0], (unsigned long long)ctrl[0]);
-    atomicAdd(&a.stats[1], (unsigned long long)total);
-    atomicMax(&a.stats[2], (unsigned long long)total);
-    atomicMax(&a.stats[9], (unsigned long long)ctrl[0]);   // records the view needs (clipped faces: several each)
-    if (ovf) { atomicMax(&a.stats[3], 1ull); atomicMin(&a.stats[4], (unsigned long long)a.group); atomicOr(&a.stats[10], 1ull); }
+    ctrl[GR_CTRL_OVERFLOW] = ovf ? GR_WHY_OUTGREW : 0u;
+    atomicAdd(&a.stats[GR_ST_RECORDS], (unsigned long long)ctrl[GR_CTRL_RECORDS]);
+    atomicAdd(&a.stats[GR_ST_ENTRIES], (unsigned long long)total);
+    atomicMax(&a.stats[GR_ST_MAX_ENTRIES], (unsigned long long)total);
+    atomicMax(&a.stats[GR_ST_REC_NEED], (unsigned long long)ctrl[GR_CTRL_RECORDS]);   // records the view needs (clipped faces: several each)
+    if (ovf) { atomicMax(&a.stats[GR_ST_OVERFLOW], 1ull); atomicMin(&a.stats[GR_ST_FIRST_GROUP], (unsigned long long)a.group); atomicOr(&a.stats[GR_ST_CAUSES], (unsigned long long)GR_WHY_OUTGREW); }
   }
 }
 
@@ -923,7 +923,7 @@ __device__ __forceinline__ void store_entry(const BinArgs &a, uint32_t *__restri
     // e1.y (the third slope word) is zero for 16-bit slopes; bit 0 of it is build_entry's "too large for the short form"
     // (the slot was handed out already: it must not keep stale bytes -- an older view's entry, or 48-byte data read as a
     // 40-byte entry.  Zero rows: no work item of the tile kernel ever looks at it; the view is repeated anyway)
-    if (e1.y != 0 || e2.w < 0) { atomicOr(&ctrl[2], 2u); nr8[idx] = 0; return; }
+    if (e1.y != 0 || e2.w < 0) { atomicOr(&ctrl[GR_CTRL_OVERFLOW], GR_WHY_SHORT_MISS); nr8[idx] = 0; return; }
     // a chunk of 64 entries (2560 bytes) holds the 64 x {s0 .. s7} first, then the 64 x {s8, s9}: the tile kernel copies the
     // chunk to LDS as it is and reads an entry with two 16-byte reads and one 8-byte read, all aligned.  (Three planes -- 64 x
     // {s0 .. s3}, 64 x {s4 .. s7}, 64 x {s8, s9}: a tile group's lanes write consecutive bytes with every store -- take 4.5 % off
@@ -957,7 +957,7 @@ __global__ __launch_bounds__(256) void k_fill_compile(BinArgs a) {
   const int slot = blockIdx.y;
   uint32_t *ctrl = a.ctrl + slot * a.ctrl_stride;
   const int64_t RP = a.rec_stride >> 2;                                  // records per plane
-  const uint32_t n_rec = (uint32_t)min((int64_t)ctrl[0], RP);            // (the counter keeps counting past the planes: the call is repeated)
+  const uint32_t n_rec = (uint32_t)min((int64_t)ctrl[GR_CTRL_RECORDS], RP);            // (the counter keeps counting past the planes: the call is repeated)
   const uint32_t *cntS = ctrl + GR_CTRL_HDR;
   const uint32_t *off = ctrl + GR_CTRL_HDR + 2 * a.Tcap;
   uint32_t *cur = ctrl + GR_CTRL_HDR + 3 * a.Tcap;
@@ -1047,16 +1047,16 @@ __device__ void emit_triangle(const BinArgs &a, int slot, uint32_t *ctrl, Vtx v0
         if (pos < (uint32_t)a.cap_tile) {
           const int64_t idx = (int64_t)t * a.cap_tile + pos;
           compile_entry(a, ctrl, comp, nr8, idx, r0, r1, r2, tx << a.twl, ty << a.thl, 1 << a.twl, 1 << a.thl);
-        } else atomicOr(&ctrl[2], 1u);
+        } else atomicOr(&ctrl[GR_CTRL_OVERFLOW], GR_WHY_OUTGREW);
       }
   } else {
     // a clipped face becomes up to six triangles, each a record: more records than the planes hold (F, unless an earlier call
     // asked for more) -> the view is reported like any overflow; the counter keeps counting, so the retry knows the need
-    // (k_scan_tiles: stats[9]; found by tools/fuzz_parity.py seed 934669: 18 faces around the camera, exact binning)
-    const uint32_t s = atomicAdd(&ctrl[0], 1u);
+    // (k_scan_tiles: stats[GR_ST_REC_NEED]; found by tools/fuzz_parity.py seed 934669: 18 faces around the camera, exact binning)
+    const uint32_t s = atomicAdd(&ctrl[GR_CTRL_RECORDS], 1u);
     const int64_t RP = a.rec_stride >> 2;
     if ((int64_t)s >= RP) {
-      atomicMax(&a.stats[3], 1ull); atomicMin(&a.stats[4], (unsigned long long)a.group); atomicOr(&a.stats[10], 1ull);
+      atomicMax(&a.stats[GR_ST_OVERFLOW], 1ull); atomicMin(&a.stats[GR_ST_FIRST_GROUP], (unsigned long long)a.group); atomicOr(&a.stats[GR_ST_CAUSES], (unsigned long long)GR_WHY_OUTGREW);
       return;
     }
     const bool small_fp = (tx1 - tx0 <= 1) && (ty1 - ty0 <= 1);
@@ -1085,7 +1085,7 @@ __global__ __launch_bounds__(64) void k_clip_faces(const float *__restrict__ cam
   const int slot = blockIdx.y, tid = threadIdx.x;
   const float *cam = cams + (int64_t)slot * GR_CAM_FLOATS;
   uint32_t *ctrl = a.ctrl + slot * a.ctrl_stride;
-  const int64_t n_clip = min((int64_t)ctrl[4], a.F);
+  const int64_t n_clip = min((int64_t)ctrl[GR_CTRL_CLIP], a.F);
   if ((int64_t)blockIdx.x * 64 >= n_clip) return;  // the usual case: nothing to clip in this view
   const float fe = cam[12], cxp = cam[13], cyp = cam[14], nearp = cam[15];
   if (!(nearp > 0.0f) || !(fe > 0.0f) || !isfinite(fe) || !isfinite(cxp) || !isfinite(cyp)) return;
@@ -1168,7 +1168,7 @@ __global__ __launch_bounds__(256) void k_bin_init(uint4 *__restrict__ ctrl16, in
   for (int64_t i = i0; i < nt; i += step) touched[i] = 0u;
   // [0..3] records, entries, largest count, overflow; [4] first overflowed launch group: none; [5..9] short-form miss, blocks,
   // chunk visits, micro faces, records of a view; [10] overflow causes (gr_raster_status, gr_raster_overflow_causes)
-  if (stats && i0 < 11) stats[i0] = i0 == 4 ? ~0ull : 0ull;
+  if (stats && i0 < GR_ST_WORDS) stats[i0] = i0 == GR_ST_FIRST_GROUP ? ~0ull : 0ull;
 }
 
 // (view, 64-face group) pairs the vote passes of the last fused call visited, added up for gr_raster_status (k_vote_labels keeps a
@@ -1202,7 +1202,7 @@ int bin_batch(gr_ctx *c, const float *cams, int nb, int h, int w, int slot0, int
     GR_LAUNCH_EV((hipEvent_t) nullptr, chain_begin(c), k_bin_init, dim3(blocks), dim3(256), 0, s, reinterpret_cast<uint4 *>(a.ctrl), n16, a.touched, nt, st);
     c->stats_pending = false;
   }
-  if (a.dbg & 512) {  // test hook: every entry slot and row count starts as garbage (0xFF), like scratch that an earlier call left behind
+  if (a.dbg & GR_DBG_POISON_SLOTS) {  // test hook: every entry slot and row count starts as garbage (0xFF), like scratch that an earlier call left behind
     GR_HIP(c, hipMemsetAsync(a.comp, 0xFF, sizeof(int4) * GR_ENT_Q * (size_t)c->ent_cap * nb, s));
     GR_HIP(c, hipMemsetAsync(a.nrow8, 0xFF, (size_t)c->ent_cap * nb, s));
   }
@@ -1251,7 +1251,7 @@ int bin_batch(gr_ctx *c, const float *cams, int nb, int h, int w, int slot0, int
 int sum_visits(gr_ctx *c, hipStream_t s) {
   if (!c->visits_pending) return GR_OK;
   c->visits_pending = false;
-  hipLaunchKernelGGL(k_sum_visits, dim3(64), dim3(256), 0, s, c->visits, ceil_div(c->F, 64), c->stats + 7);
+  hipLaunchKernelGGL(k_sum_visits, dim3(64), dim3(256), 0, s, c->visits, ceil_div(c->F, 64), c->stats + GR_ST_VISITS);
   GR_HIP(c, hipGetLastError());
   return GR_OK;
 }

@@ -47,7 +47,32 @@ char g_learned_path[1024] = {0};
 
 inline int merge_cap(int a, int b) { return (a == GR_LEARNED_EXACT || b == GR_LEARNED_EXACT) ? GR_LEARNED_EXACT : std::max(a, b); }
 
+// the entry of (mesh signature, T) among the n valid ones of a learned table (a ring: n = min(entries ever put, its size)), or null
+template <typename L>
+L *find_learned(L *tab, int n, uint64_t mesh, int T) {
+  for (int i = 0; i < n; ++i)
+    if (tab[i].mesh == mesh && tab[i].T == T) return tab + i;
+  return nullptr;
+}
+
+// a request for `need` elements of scratch: an eighth more, and a margin
+inline int64_t with_headroom(int64_t need, int64_t margin) { return need + need / 8 + margin; }
+
+// The statistics block of a raster call (GR_ST_*) as the host reads it: read_stats copies it behind the work on `s` (synchronises)
+struct CallStats {
+  unsigned long long w[GR_ST_WORDS] = {};
+  unsigned long long operator[](int i) const { return w[i]; }
+  int causes() const { return (int)(w[GR_ST_CAUSES] & GR_WHY_ALL); }
+  bool mostly_micro() const { return w[GR_ST_RECORDS] > 0 && 5 * w[GR_ST_MICRO] > 2 * w[GR_ST_RECORDS]; }   // micro lists pay
+};
+int read_stats(gr_ctx *c, hipStream_t s, CallStats &st) {
+  GR_HIP(c, hipMemcpyAsync(st.w, c->stats, sizeof(st.w), hipMemcpyDeviceToHost, s));
+  GR_HIP(c, hipStreamSynchronize(s));
+  return GR_OK;
+}
+
 void put_global_locked(const gr_ctx::Learned &v);
+void read_learned_file_locked(const char *path);
 
 bool parse_learned_line(const char *line, gr_ctx::Learned &v) {
   unsigned long long m; int T, cap, full, micro = 0;
@@ -61,13 +86,7 @@ void save_learned_locked() {
   if (!g_learned_path[0]) return;
   // several processes (the ranks of one job) share the file: what the others wrote since this process read it is merged
   // in before the rewrite (entry-wise maximum), so that no rank's lesson is lost to another's rename
-  if (FILE *f = fopen(g_learned_path, "r")) {
-    char line[256];
-    gr_ctx::Learned v;
-    while (fgets(line, sizeof(line), f))
-      if (parse_learned_line(line, v)) put_global_locked(v);
-    fclose(f);
-  }
+  read_learned_file_locked(g_learned_path);
   char tmp[1100];
   snprintf(tmp, sizeof(tmp), "%s.tmp.%d", g_learned_path, (int)getpid());
   FILE *f = fopen(tmp, "w");
@@ -80,44 +99,42 @@ void save_learned_locked() {
   if (rename(tmp, g_learned_path) != 0) (void)remove(tmp);
 }
 
+void read_learned_file_locked(const char *path) {   // a missing file is fine: it appears with the first overflow
+  FILE *f = fopen(path, "r");
+  if (!f) return;
+  char line[256];
+  gr_ctx::Learned v;
+  while (fgets(line, sizeof(line), f))
+    if (parse_learned_line(line, v)) put_global_locked(v);
+  fclose(f);
+}
+
 void put_global_locked(const gr_ctx::Learned &v) {
-  int j = 0;
-  for (; j < std::min(g_n_learned, 64); ++j)
-    if (g_learned[j].mesh == v.mesh && g_learned[j].T == v.T) break;
-  if (j == std::min(g_n_learned, 64)) {
-    j = g_n_learned % 64; g_n_learned += 1;
-    g_learned[j] = v;
-    return;
-  }
-  g_learned[j].cap = merge_cap(g_learned[j].cap, v.cap);
-  g_learned[j].full = g_learned[j].full || v.full;
-  g_learned[j].micro = g_learned[j].micro || v.micro;
+  gr_ctx::Learned *e = find_learned(g_learned, std::min(g_n_learned, 64), v.mesh, v.T);
+  if (!e) { g_learned[g_n_learned % 64] = v; g_n_learned += 1; return; }
+  e->cap = merge_cap(e->cap, v.cap);
+  e->full = e->full || v.full;
+  e->micro = e->micro || v.micro;
 }
 
 // what is known about images of T tiles of the current mesh: slots per tile (0: nothing learned) and the entry form
 void lookup_learned(const gr_ctx *c, int T, int &cap, bool &full, bool *micro = nullptr) {
   cap = 0; full = false;
   if (micro) *micro = false;
-  for (int i = 0; i < std::min(c->n_learned, 8); ++i)
-    if (c->learned[i].mesh == c->mesh_sig && c->learned[i].T == T) {
-      cap = c->learned[i].cap; full = c->learned[i].full;
-      if (micro) *micro = c->learned[i].micro;
-      return;
-    }
-  if (c->share_learned) {
-    std::lock_guard<std::mutex> lk(g_learned_mu);
-    for (int i = 0; i < std::min(g_n_learned, 64); ++i)
-      if (g_learned[i].mesh == c->mesh_sig && g_learned[i].T == T) {
-        cap = g_learned[i].cap; full = g_learned[i].full;
-        if (micro) *micro = g_learned[i].micro;
-        return;
-      }
+  const gr_ctx::Learned *e = find_learned(c->learned, std::min(c->n_learned, 8), c->mesh_sig, T);
+  std::unique_lock<std::mutex> lk(g_learned_mu, std::defer_lock);
+  if (!e && c->share_learned) {
+    lk.lock();
+    e = find_learned(g_learned, std::min(g_n_learned, 64), c->mesh_sig, T);
   }
+  if (!e) return;
+  cap = e->cap; full = e->full;
+  if (micro) *micro = e->micro;
 }
 
 // The binning configuration of one raster call, from ONE look at the tables: slots per tile (0 = exact two-pass binning)
 // and the entry form.  The 40-byte entry form (store_entry) is the default of the single-pass binning; images with faces it
-// cannot hold (93 px and more) are remembered like the slots per tile.  Variant bit 128: always 48 bytes.  The short form is
+// cannot hold (93 px and more) are remembered like the slots per tile.  GR_VAR_ENT48: always 48 bytes.  The short form is
 // laid out in chunks of 64 entries (store_entry): a tile's segment must be a whole number of chunks -- slots per tile set by
 // hand to anything else: 48 bytes.
 void resolve_binning(gr_ctx *c, int T) {
@@ -127,16 +144,16 @@ void resolve_binning(gr_ctx *c, int T) {
   lookup_learned(c, T, cap, full, &micro);
   if (cap == GR_LEARNED_EXACT) return;  // this (mesh, image size) bins exactly: one view's segments would not fit the budget
   // nothing is known about the slots this mesh and image size need: the call looks at the counts of its first launch group
-  // before that group's tile kernel runs (raster_views).  Variant bit 16384: never (rounds 1-4: gr_raster_status reports it)
-  c->cur_look = cap == 0 && !(c->opt_var & 16384);
+  // before that group's tile kernel runs (raster_views).  GR_VAR_NO_LOOK: never (rounds 1-4: gr_raster_status reports it)
+  c->cur_look = cap == 0 && !(c->opt_var & GR_VAR_NO_LOOK);
   c->cur_cap = std::max(cap, c->opt_direct_cap);
-  c->cur_ent40 = !(c->cur_cap & 63) && !(c->opt_var & 128) && !full;
+  c->cur_ent40 = !(c->cur_cap & 63) && !(c->opt_var & GR_VAR_ENT48) && !full;
   // micro lists: where an earlier call found most faces of the image at most 4 x 4 pixels (gr_raster_status; remembered like
-  // the slots per tile), with 40-byte entries.  Variant bits: 8192 = always, 4096 = never.
-  c->cur_micro = c->cur_ent40 && !(c->opt_var & 4096) && (micro || (c->opt_var & 8192));
+  // the slots per tile), with 40-byte entries.  GR_VAR_MICRO_ALWAYS / GR_VAR_MICRO_NEVER override.
+  c->cur_micro = c->cur_ent40 && !(c->opt_var & GR_VAR_MICRO_NEVER) && (micro || (c->opt_var & GR_VAR_MICRO_ALWAYS));
   // micro faces are counted where the count can still switch the lists on: by the call that looks at its first launch group, and
-  // by every call of the status-call protocol (variant bit 16384)
-  c->cur_count_micro = c->cur_ent40 && !c->cur_micro && !(c->opt_var & 4096) && (c->cur_look || (c->opt_var & 16384));
+  // by every call of the status-call protocol (GR_VAR_NO_LOOK)
+  c->cur_count_micro = c->cur_ent40 && !c->cur_micro && !(c->opt_var & GR_VAR_MICRO_NEVER) && (c->cur_look || (c->opt_var & GR_VAR_NO_LOOK));
 }
 
 // cap > 0: the slots per tile the image needs; full: it needs 48-byte entries (both are kept once learned)
@@ -144,11 +161,9 @@ void learn(gr_ctx *c, int T, int cap, bool full, bool micro = false) {
   int old_cap; bool old_full, old_micro;
   lookup_learned(c, T, old_cap, old_full, &old_micro);
   const gr_ctx::Learned v = {c->mesh_sig, T, merge_cap(cap, old_cap), full || old_full, micro || old_micro};
-  int i = 0;
-  for (; i < std::min(c->n_learned, 8); ++i)
-    if (c->learned[i].mesh == c->mesh_sig && c->learned[i].T == T) break;
-  if (i == std::min(c->n_learned, 8)) { i = c->n_learned % 8; c->n_learned += 1; }
-  c->learned[i] = v;
+  gr_ctx::Learned *e = find_learned(c->learned, std::min(c->n_learned, 8), c->mesh_sig, T);
+  if (!e) { e = &c->learned[c->n_learned % 8]; c->n_learned += 1; }
+  *e = v;
   if (!c->share_learned) return;
   std::lock_guard<std::mutex> lk(g_learned_mu);
   put_global_locked(v);
@@ -160,7 +175,7 @@ void learn(gr_ctx *c, int T, int cap, bool full, bool micro = false) {
 // priced the failed call's whole group and switched single-pass binning off for the CONTEXT, every image size, for good --,
 // exact binning (count, scan, fill) otherwise.  max_tile: the largest count a tile reached.
 void learn_slots(gr_ctx *c, int T, int64_t max_tile, bool full, bool micro) {
-  const int64_t need = (max_tile + max_tile / 8 + 16 + 63) / 64 * 64;
+  const int64_t need = (with_headroom(max_tile, 16) + 63) / 64 * 64;
   const int64_t bytes_one_view = need * (16 * GR_ENT_Q) * (int64_t)T;
   if (need <= GR_LEARNED_MAX_CAP && bytes_one_view <= (c->opt_budget_mb << 20)) learn(c, T, (int)need, full, micro);
   else learn(c, T, GR_LEARNED_EXACT, full, micro);   // this (mesh, image size) bins exactly from now on
@@ -178,9 +193,9 @@ int ensure_bins(gr_ctx *c, int n_slots, int T) {
   // addresses (32 counters in one line: 5.9 ns per atomic chip-wide, one per line: 0.37 -- profiles/r03_ubench_atomic_rate.txt),
   // and an image of 1000 x 750 has all its 384 counters in twelve lines, hit by every wave that bins the view.  (Images of
   // thousands of tiles spread their atomics over hundreds of lines anyway, and padding them would cost the init kernel 32 x the
-  // bytes.)  Single-pass binning only; variant bit 131072: packed counters everywhere.
+  // bytes.)  Single-pass binning only; GR_VAR_PACKED_COUNTERS: packed counters everywhere.
   int clg = -1;
-  if (direct && !(c->opt_var & 131072)) {
+  if (direct && !(c->opt_var & GR_VAR_PACKED_COUNTERS)) {
     if (T <= 1024) { clg = 0; while ((1 << clg) < T + 3) ++clg; }          // a line per tile
   }
   const int Tcap = clg < 0 ? ((T + 3) & ~3) : (32 << clg);  // words per counter array; the arrays start 16-byte aligned (a chain reads four counters at once)
@@ -226,7 +241,7 @@ int raster_views(gr_ctx *c, const float *cams, int n_views, int h, int w, int32_
   // Fused aggregation over several launch groups: the vote kernel of group g (a light, latency-bound pass over F winners)
   // runs on a side stream beside the binning of group g + 1 (also light); the tile kernels in between fill the machine on
   // their own.  Two winner buffers alternate; votes are still added group by group, in order (one side stream).
-  const bool overlap = labels && n_views > B && !(c->opt_var & 4);
+  const bool overlap = labels && n_views > B && !(c->opt_var & GR_VAR_VOTES_INLINE);
   // group maps for the vote kernel: a byte per 64 consecutive caller face ids, set by the tile kernel's epilogue where it
   // issues a winner (zeroed by the launch group's init kernel); in words; one map per view of the launch groups in flight
   const int tw = (int)ceil_div(ceil_div(F, 64), 4);
@@ -279,13 +294,13 @@ int raster_views(gr_ctx *c, const float *cams, int n_views, int h, int w, int32_
       // costs, where rounds 1-4 paid the whole call once more after gr_raster_status).  Otherwise the slots in use are noted as
       // sufficient and no call looks again.  Later groups of the call, and later calls with more crowded views, keep the
       // GR_EOVERFLOW protocol.
-      unsigned long long st[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      GR_HIP(c, hipMemcpyAsync(st, c->stats, sizeof(st), hipMemcpyDeviceToHost, s));
-      GR_HIP(c, hipStreamSynchronize(s));
-      c->causes |= (int)(st[10] & 7u);   // (the attempt that starts over zeroes the device's word: kept here for the caller)
-      const bool grow = st[3] && (int64_t)st[2] > c->cur_cap, miss = st[3] && st[5] != 0;
-      const bool micro = !c->cur_micro && !(c->opt_var & (128 | 4096)) && !miss && st[0] > 0 && 5 * st[8] > 2 * st[0];
-      if (grow) learn_slots(c, T, (int64_t)st[2], miss, micro);
+      CallStats st;
+      rc = read_stats(c, s, st);
+      if (rc) return rc;
+      c->causes |= st.causes();   // (the attempt that starts over zeroes the device's word: kept here for the caller)
+      const bool grow = st[GR_ST_OVERFLOW] && (int64_t)st[GR_ST_MAX_ENTRIES] > c->cur_cap, miss = st[GR_ST_OVERFLOW] && st[GR_ST_SHORT_MISS] != 0;
+      const bool micro = !c->cur_micro && !(c->opt_var & (GR_VAR_ENT48 | GR_VAR_MICRO_NEVER)) && !miss && st.mostly_micro();
+      if (grow) learn_slots(c, T, (int64_t)st[GR_ST_MAX_ENTRIES], miss, micro);
       else learn(c, T, c->cur_cap, miss, micro);
       if (grow || miss || micro) return raster_views(c, cams, n_views, h, w, ids, depth, labels, C, votes, counts, flags, s, again + 1);
     }
@@ -335,12 +350,12 @@ int gr_ctx_create(int device, gr_ctx **out) {
   gr_ctx *c = new (std::nothrow) gr_ctx();
   if (!c) return GR_ENOMEM;
   c->device = device;
-  if (hipMalloc(&c->stats, sizeof(unsigned long long) * 16) != hipSuccess ||
+  if (hipMalloc(&c->stats, sizeof(unsigned long long) * GR_ST_ALLOC) != hipSuccess ||
       hipMalloc(&c->flag, sizeof(int) * 8) != hipSuccess) {  // flag word + upload scratch (vertex bounds)
     delete c;
     return GR_ENOMEM;
   }
-  (void)hipMemset(c->stats, 0, sizeof(unsigned long long) * 16);
+  (void)hipMemset(c->stats, 0, sizeof(unsigned long long) * GR_ST_ALLOC);
   (void)hipDeviceSynchronize();   // (the null stream's memset: a non-blocking stream of the first call would not wait for it)
 #ifdef GR_STAMPS
   if (hipMalloc(&c->stamps, sizeof(unsigned long long) * 32 * 1024) == hipSuccess) (void)hipMemset(c->stamps, 0, sizeof(unsigned long long) * 32 * 1024);
@@ -355,29 +370,15 @@ int gr_ctx_destroy(gr_ctx *c) {
   (void)hipDeviceSynchronize();
   for (auto &sp : c->spans) { if (sp.own_a) (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
   for (auto e : c->pool) (void)hipEventDestroy(e);
-  if (c->ctrl) (void)hipFree(c->ctrl);
-  if (c->rec) (void)hipFree(c->rec);
-  if (c->comp) (void)hipFree(c->comp);
-  if (c->nrow8) (void)hipFree(c->nrow8);
-  if (c->work) (void)hipFree(c->work);
-  if (c->clip) (void)hipFree(c->clip);
-  if (c->winner) (void)hipFree(c->winner);
   for (int i = 0; i < 2; ++i) {
     if (c->ev_raster[i]) (void)hipEventDestroy(c->ev_raster[i]);
     if (c->ev_vote[i]) (void)hipEventDestroy(c->ev_vote[i]);
   }
   if (c->side) (void)hipStreamDestroy(c->side);
-  if (c->sort_tmp) (void)hipFree(c->sort_tmp);
-  if (c->resize_tmp) (void)hipFree(c->resize_tmp);
-  if (c->blk) (void)hipFree(c->blk);
-  if (c->visits) (void)hipFree(c->visits);
-  if (c->touched) (void)hipFree(c->touched);
-  if (c->soup) (void)hipFree(c->soup);
-  if (c->bvert) (void)hipFree(c->bvert);
-  if (c->bidx) (void)hipFree(c->bidx);
-  if (c->orig) (void)hipFree(c->orig);
-  if (c->stats) (void)hipFree(c->stats);
-  if (c->flag) (void)hipFree(c->flag);
+  for (void *p : {(void *)c->ctrl, (void *)c->rec, (void *)c->comp, (void *)c->nrow8, (void *)c->work, (void *)c->clip, c->winner,
+                  c->sort_tmp, (void *)c->resize_tmp, (void *)c->blk, (void *)c->visits, (void *)c->touched, (void *)c->soup,
+                  (void *)c->bvert, (void *)c->bidx, (void *)c->orig, (void *)c->stats, (void *)c->flag})
+    if (p) (void)hipFree(p);
   delete c;
   return GR_OK;
 }
@@ -428,13 +429,7 @@ int gr_learned_cache_file(const char *path_h) {
   if (!path_h || !path_h[0]) { g_learned_path[0] = 0; return GR_OK; }
   if (strlen(path_h) >= sizeof(g_learned_path)) return GR_EINVAL;
   snprintf(g_learned_path, sizeof(g_learned_path), "%s", path_h);
-  FILE *f = fopen(path_h, "r");
-  if (!f) return GR_OK;  // nothing learned yet: the file appears with the first overflow
-  char line[256];
-  gr_ctx::Learned v;
-  while (fgets(line, sizeof(line), f))
-    if (parse_learned_line(line, v)) put_global_locked(v);
-  fclose(f);
+  read_learned_file_locked(path_h);
   return GR_OK;
 }
 
@@ -446,31 +441,21 @@ int gr_learned_cache_clear(void) {
 }
 
 #ifdef GR_STAMPS
-// diagnostic build only (tools/tile_phases.py): read and clear the tile kernel's phase-cycle sums (synchronises the device)
-int gr_debug_read_stamps(gr_ctx *c, unsigned long long *out16_h) {
+// diagnostic build only: read and clear the phase-cycle sums of the tile kernel (tools/tile_phases.py; the first half of the
+// stamp buffer) or of the set-up kernel (tools/setup_phases.py; the second half); synchronises the device
+static int read_stamps(gr_ctx *c, unsigned long long *out16_h, int half) {
   if (!c || !out16_h || !c->stamps) return GR_EINVAL;
   GR_HIP(c, hipDeviceSynchronize());
   std::vector<unsigned long long> all(16 * 1024);
-  GR_HIP(c, hipMemcpy(all.data(), c->stamps, sizeof(unsigned long long) * all.size(), hipMemcpyDeviceToHost));
-  GR_HIP(c, hipMemset(c->stamps, 0, sizeof(unsigned long long) * all.size()));
+  unsigned long long *const src = c->stamps + half * 16 * 1024;
+  GR_HIP(c, hipMemcpy(all.data(), src, sizeof(unsigned long long) * all.size(), hipMemcpyDeviceToHost));
+  GR_HIP(c, hipMemset(src, 0, sizeof(unsigned long long) * all.size()));
   for (int k = 0; k < 16; ++k) out16_h[k] = 0;
   for (size_t i = 0; i < all.size(); ++i) out16_h[i & 15] += all[i];
   return GR_OK;
 }
-#endif
-
-#ifdef GR_STAMPS
-// diagnostic build only (tools/setup_phases.py): the set-up kernel's phase-cycle sums (the second half of the stamp buffer)
-int gr_debug_read_setup_stamps(gr_ctx *c, unsigned long long *out16_h) {
-  if (!c || !out16_h || !c->stamps) return GR_EINVAL;
-  GR_HIP(c, hipDeviceSynchronize());
-  std::vector<unsigned long long> all(16 * 1024);
-  GR_HIP(c, hipMemcpy(all.data(), c->stamps + 16 * 1024, sizeof(unsigned long long) * all.size(), hipMemcpyDeviceToHost));
-  GR_HIP(c, hipMemset(c->stamps + 16 * 1024, 0, sizeof(unsigned long long) * all.size()));
-  for (int k = 0; k < 16; ++k) out16_h[k] = 0;
-  for (size_t i = 0; i < all.size(); ++i) out16_h[i & 15] += all[i];
-  return GR_OK;
-}
+int gr_debug_read_stamps(gr_ctx *c, unsigned long long *out16_h) { return read_stamps(c, out16_h, 0); }
+int gr_debug_read_setup_stamps(gr_ctx *c, unsigned long long *out16_h) { return read_stamps(c, out16_h, 1); }
 #endif
 
 int gr_get_stage_times(gr_ctx *c, gr_stage_times *o) {
@@ -498,55 +483,54 @@ int gr_raster_face_ids(gr_ctx *c, const float *cams, int n_views, int h, int w, 
 
 int gr_raster_status(gr_ctx *c, gr_raster_stats *o) {
   if (!c || !o) return GR_EINVAL;
-  unsigned long long st[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  {
-    int rc = bin_stats_deferred(c, c->last_stream);   // the view totals of a call that left them for now
-    if (!rc) rc = sum_visits(c, c->last_stream);      // ... and the visit counters of a fused call's vote passes
-    if (rc) return rc;
-  }
-  GR_HIP(c, hipMemcpyAsync(st, c->stats, sizeof(st), hipMemcpyDeviceToHost, c->last_stream));
-  GR_HIP(c, hipStreamSynchronize(c->last_stream));
-  o->records = (int64_t)st[0]; o->entries = (int64_t)st[1]; o->max_entries = (int64_t)st[2];
-  o->entry_cap = c->ent_cap; o->overflow = (int32_t)st[3];
-  o->blocks = (int64_t)st[6]; o->chunk_visits = (int64_t)st[7];
+  CallStats st;
+  int rc = bin_stats_deferred(c, c->last_stream);   // the view totals of a call that left them for now
+  if (!rc) rc = sum_visits(c, c->last_stream);      // ... and the visit counters of a fused call's vote passes
+  if (!rc) rc = read_stats(c, c->last_stream, st);
+  if (rc) return rc;
+  const bool ovf = st[GR_ST_OVERFLOW] != 0;
+  const unsigned long long max_entries = st[GR_ST_MAX_ENTRIES], rec_need = st[GR_ST_REC_NEED];
+  o->records = (int64_t)st[GR_ST_RECORDS]; o->entries = (int64_t)st[GR_ST_ENTRIES]; o->max_entries = (int64_t)max_entries;
+  o->entry_cap = c->ent_cap; o->overflow = (int32_t)st[GR_ST_OVERFLOW];
+  o->blocks = (int64_t)st[GR_ST_BLOCKS]; o->chunk_visits = (int64_t)st[GR_ST_VISITS];
   o->rebinned_groups = c->rebinned;
-  c->causes |= (int)(st[10] & 7u);
+  c->causes |= st.causes();
   // views of the last call whose results are complete: every launch group in front of the first one that overflowed
-  o->views_done = st[3] ? (int32_t)std::min<unsigned long long>(st[4] * (unsigned long long)std::max(c->last_B, 1),
-                                                                (unsigned long long)c->last_n_views)
-                        : c->last_n_views;
-  if (st[3] && c->last_direct) {
-    // A tile outgrew its fixed segment, or a face did not fit the 40-byte entry form (st[5]).  The counters kept counting,
-    // so the need is known: the retry uses segments of that size if a launch group's entry memory stays within budget, and
-    // bins exactly (count, scan, fill) otherwise; it uses 48-byte entries if the short form was missed.
+  o->views_done = ovf ? (int32_t)std::min<unsigned long long>(st[GR_ST_FIRST_GROUP] * (unsigned long long)std::max(c->last_B, 1),
+                                                              (unsigned long long)c->last_n_views)
+                      : c->last_n_views;
+  if (ovf && c->last_direct) {
+    // A tile outgrew its fixed segment, or a face did not fit the 40-byte entry form (GR_ST_SHORT_MISS).  The counters kept
+    // counting, so the need is known: the retry uses segments of that size if a launch group's entry memory stays within
+    // budget, and bins exactly (count, scan, fill) otherwise; it uses 48-byte entries if the short form was missed.
     const int used = c->cur_cap;  // what the call ran with
-    const bool grow = (int64_t)st[2] > used;
-    if (st[5] != 0) learn(c, c->last_T, 0, true);
+    const bool grow = (int64_t)max_entries > used;
+    if (st[GR_ST_SHORT_MISS] != 0) learn(c, c->last_T, 0, true);
     if (grow) {
-      learn_slots(c, c->last_T, (int64_t)st[2], false, false);
+      learn_slots(c, c->last_T, (int64_t)max_entries, false, false);
       return fail(c, GR_EOVERFLOW, "single-pass binning overflow: a tile received %llu entries (slots per tile %d); "
-                  "retry the call", st[2], used);
+                  "retry the call", max_entries, used);
     }
     return fail(c, GR_EOVERFLOW, "single-pass binning: a face does not fit the 40-byte entry form; retry the call "
                 "(48-byte entries from now on)");
   }
   // Most of the image's faces are at most 4 x 4 pixels (K1 counts them; a survey mesh rendered at a quarter of its photos'
   // resolution: 85-95 %): the next call for this mesh and image size keeps micro lists (no retry: this call's result stands)
-  if (!st[3] && c->last_direct && c->cur_ent40 && !c->cur_micro && !(c->opt_var & 4096) && st[0] > 0 && 5 * st[8] > 2 * st[0])
+  if (!ovf && c->last_direct && c->cur_ent40 && !c->cur_micro && !(c->opt_var & GR_VAR_MICRO_NEVER) && st.mostly_micro())
     learn(c, c->last_T, 0, false, true);
-  if (st[3] && (int64_t)st[9] > c->rec_F) {
+  if (ovf && (int64_t)rec_need > c->rec_F) {
     // exact binning: the clipped faces of a view became more triangles than the record planes hold (one record per face
     // unless a call asked for more): the planes grow on the next call, the need is known
-    c->rec_cap_request = (int64_t)st[9] + (int64_t)st[9] / 8 + 64;
-    if ((int64_t)st[2] > c->ent_cap) c->ent_cap_request = (int64_t)st[2] + (int64_t)st[2] / 8 + 65536;
+    c->rec_cap_request = with_headroom((int64_t)rec_need, 64);
+    if ((int64_t)max_entries > c->ent_cap) c->ent_cap_request = with_headroom((int64_t)max_entries, 65536);
     return fail(c, GR_EOVERFLOW, "record list overflow: a view needs %llu records (a clipped face becomes several triangles), "
-                "capacity %lld; retry the call", st[9], (long long)c->rec_F);
+                "capacity %lld; retry the call", rec_need, (long long)c->rec_F);
   }
-  if (st[3]) {
+  if (ovf) {
     // grow on the next call: exact need is known
-    c->ent_cap_request = (int64_t)st[2] + (int64_t)st[2] / 8 + 65536;
+    c->ent_cap_request = with_headroom((int64_t)max_entries, 65536);
     return fail(c, GR_EOVERFLOW, "bin list overflow: a view needs %llu entries, capacity %lld; retry the call",
-                st[2], (long long)c->ent_cap);
+                max_entries, (long long)c->ent_cap);
   }
   return GR_OK;
 }

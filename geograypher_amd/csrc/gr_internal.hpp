@@ -30,14 +30,45 @@
 #define GR_TILE_LOG2 6
 #define GR_MAX_BATCH 64     // views per launch group (amortises kernel boundaries and per-launch tails)
 #define GR_ENT_Q 3          // int4 per compiled (face, tile) entry: 48 bytes, 12 words
-#define GR_CTRL_HDR 8       // ctrl words before the tile arrays: rec_count, total_entries, overflow, work_count, clip_count, -, micro_count
+#define GR_CTRL_HDR 8       // ctrl words before the tile arrays (GR_CTRL_* below)
 #define GR_MAX_DIM 16384    // h, w limit (guard band and 16-bit bbox packing)
 #define GR_BLOCK 64         // faces per block of the Morton-ordered soup: one wave, one bounding sphere
 #define GR_BLOCK_VERTS 192  // distinct vertices a block can have (3 per face); a patch of a manifold mesh has about 48
 namespace grimpl {
 
+// The words of the overflow protocol, named once: kernels, host decode and the vote pass all index through these.
+enum {  // header of a view's `ctrl` slot (BinArgs::ctrl); word 5 is unused
+  GR_CTRL_RECORDS = 0,   // records (faces that survived culling; a clipped face several)
+  GR_CTRL_ENTRIES = 1,   // (face, tile) entries of the view
+  GR_CTRL_OVERFLOW = 2,  // != 0: the view's lists are incomplete; single-pass binning: the OR of GR_WHY_*
+  GR_CTRL_WORK = 3,      // blocks that passed the frustum test (BinArgs::work)
+  GR_CTRL_CLIP = 4,      // faces on the clip list (BinArgs::clip)
+  GR_CTRL_MICRO = 6      // micro faces (pixel box at most 4 x 4)
+};
+enum {  // the call's statistics block (BinArgs::stats), summed / maximised over its views
+  GR_ST_RECORDS = 0,      // records
+  GR_ST_ENTRIES = 1,      // entries
+  GR_ST_MAX_ENTRIES = 2,  // largest entry count: of a tile (single-pass binning), of a view (exact binning)
+  GR_ST_OVERFLOW = 3,     // != 0: some view overflowed
+  GR_ST_FIRST_GROUP = 4,  // first launch group that overflowed (~0: none)
+  GR_ST_SHORT_MISS = 5,   // != 0: a face the 40-byte entry cannot hold (the caller repeats with 48 bytes)
+  GR_ST_BLOCKS = 6,       // 64-face blocks that passed the frustum cull
+  GR_ST_VISITS = 7,       // (view, 64-face group) pairs the vote passes visited
+  GR_ST_MICRO = 8,        // micro faces
+  GR_ST_REC_NEED = 9,     // records the most demanding view needs (exact binning)
+  GR_ST_CAUSES = 10,      // the call's overflow causes, ORed (GR_WHY_*)
+  GR_ST_WORDS = 11,       // words in use
+  GR_ST_ALLOC = 16        // words allocated
+};
+enum {  // overflow causes (GR_CTRL_OVERFLOW, GR_ST_CAUSES; what gr_raster_overflow_causes reports as GR_CAUSE_*)
+  GR_WHY_OUTGREW = GR_CAUSE_LIST_OUTGREW,    // a list outgrew its slots
+  GR_WHY_SHORT_MISS = GR_CAUSE_SHORT_MISS,  // a face did not fit the 40-byte entry form
+  GR_WHY_MET = GR_CAUSE_LISTS_MET,        // with micro lists: a tile's two lists met
+  GR_WHY_ALL = GR_WHY_OUTGREW | GR_WHY_SHORT_MISS | GR_WHY_MET
+};
+
 struct BinArgs {
-  uint32_t *ctrl;        // [slot][GR_CTRL_HDR + 4*Tcap]  rec_count,total,overflow,work_count,clip_count,- | cntS[T] | cntB[T] | offset[T] | curB[T]
+  uint32_t *ctrl;        // [slot][GR_CTRL_HDR + 4*Tcap]  header (GR_CTRL_*) | cntS[T] | cntB[T] | offset[T] | curB[T]
                          //   cntS: entries whose list position was handed out in k_setup_cull (faces touching <= 2x2 tiles)
                          //   cntB: entries of larger faces, placed by k_fill_compile behind the cntS block of their tile (exact path)
   int4 *rec;             // [slot][4][F]  plane0 {X0,Y0,X1,Y1} plane1 {X2,Y2,iz0,face} plane2 {A,B,jmin|jmax<<16,imin|imax<<16}
@@ -50,15 +81,13 @@ struct BinArgs {
   uint32_t *touched;     // fused aggregation: [slot][tw] a BYTE per group of 64 consecutive CALLER face ids that received a winner in the
                          // view (set by the tile kernel's epilogue beside its winner atomic; zeroed by the group's init kernel), or null
   int tw;                // words per slot of `touched`
-  uint32_t *work;        // [slot][work_stride] blocks of this view that passed the frustum test (ctrl[3] = count)
-  uint32_t *clip;        // [slot][F] soup faces that straddle the near plane / guard band (R7; ctrl[4] = count)
+  uint32_t *work;        // [slot][work_stride] blocks of this view that passed the frustum test (ctrl[GR_CTRL_WORK] = count)
+  uint32_t *clip;        // [slot][F] soup faces that straddle the near plane / guard band (R7; ctrl[GR_CTRL_CLIP] = count)
   int64_t work_stride;
   int4 *comp;            // [slot][ent_cap][GR_ENT_Q]  compiled (face, tile) entries grouped by tile, 48 bytes each (ent40: 40 bytes
                          //                            each at the front of the same slot memory)
   uint8_t *nrow8;        // [slot][ent_cap] rows of each entry inside its tile (the tile kernel's scan input: a compact stream)
-  unsigned long long *stats;  // [6] records, entries, max_entries, overflow, first overflowed launch group (over the call),
-                              //     short-form miss (a face the 40-byte entry cannot hold: the caller repeats with 48 bytes);
-                              //     [10] the call's overflow causes, ORed (1 list outgrew its slots, 2 short-form miss, 4 lists met)
+  unsigned long long *stats;  // [GR_ST_ALLOC] the call's statistics, GR_ST_WORDS in use (GR_ST_* above)
   int group;             // index of this launch group inside the call
   int64_t ctrl_stride;   // words per slot
   int64_t rec_stride;    // int4 per slot: four planes of rec_stride / 4 >= F records
@@ -78,7 +107,7 @@ struct BinArgs {
 #ifdef GR_STAMPS
   unsigned long long *stamps;  // diagnostic build: [16] cycles per tile-kernel phase, summed over waves (raster_tile.hip)
 #endif
-  int dbg;               // GR_OPT_DEBUG: 512 (a TEST hook, results stay right): entry slots and row counts are poisoned with 0xFF
+  int dbg;               // GR_OPT_DEBUG: GR_DBG_POISON_SLOTS (a TEST hook, results stay right): entry slots and row counts are poisoned with 0xFF
                          // before every launch group is binned
 };
 

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void k_vote_labels(uint32_t *__restrict__ winn
   if (f >= F) return;
   // a launch group whose binning overflowed (and every group after it) must not vote: its winners are incomplete.  The
   // caller learns how many views were folded in (gr_raster_status: views_done) and repeats the call for the rest.
-  const bool skip = stats != nullptr && stats[4] <= (unsigned long long)group;
+  const bool skip = stats != nullptr && stats[GR_ST_FIRST_GROUP] <= (unsigned long long)group;
   uint32_t c = 0;
   // up to sixteen classes: the face's votes of the whole launch group are collected in TWO registers, a byte per class (a group has
   // at most 64 views), and folded into votes[] once at the end -- loads first, then stores.  (`votes[f][label] += 1` view by view

@@ -627,7 +627,7 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
 
   // the tile's MICRO list (single-pass binning with 40-byte entries): cntm entries from the back of the segment; the scanline
   // list must not reach into it.  The clamps below bound each list on its own; two lists that each fit but together outgrow the
-  // segment have overwritten each other -- k_bin_stats raises the view's overflow word for that (bit 4): the fused kernel does
+  // segment have overwritten each other -- k_bin_stats raises the view's overflow word for that (GR_WHY_MET): the fused kernel does
   // not walk such a view, and the ids of this pass are repeated after the status call
   if (!(SHORT && MICRO)) cntm = 0u;
   if (SHORT && MICRO) {   // both lists inside the segment
@@ -832,7 +832,7 @@ __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile(BinArgs a, Rast
   // fused projection: a view whose binning did not finish (a tile outgrew its segment, a face missed the 40-byte form) is
   // repeated by the caller and its launch group does not vote -- its winners are not wanted, and a list with a hole in it is
   // not walked at all (one scalar load beside the counters')
-  if (FUSE && ctrl[2] != 0u) return;
+  if (FUSE && ctrl[GR_CTRL_OVERFLOW] != 0u) return;
   uint32_t cnt0, cnt1 = 0, cnt2 = 0, cnt3 = 0;
   uint32_t cm0 = 0, cm1 = 0, cm2 = 0, cm3 = 0;   // the tiles' micro lists (counted in the cntB array: binning.hip)
   int64_t beg0, beg1 = 0, beg2 = 0, beg3 = 0;
@@ -947,7 +947,7 @@ __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile_roll(BinArgs a,
   const v4i *base = reinterpret_cast<const v4i *>(a.comp + (int64_t)slot * a.ent_cap * GR_ENT_Q);
   auto needed = [](uint32_t qq, uint32_t n) { return SHORT ? short_piece_needed(qq, min(n, 64u)) : qq < n * GR_ENT_Q; };
   const uint32_t *ctrl = a.ctrl + slot * a.ctrl_stride;
-  if (FUSE && ctrl[2] != 0u) return;
+  if (FUSE && ctrl[GR_CTRL_OVERFLOW] != 0u) return;
   const uint32_t cap = (uint32_t)a.cap_tile;
   const int64_t sbase = slot * a.ent_cap;
   // the chain's counters: lane k holds tile k's (ONE vector register for the whole chain, read with v_readlane: no counter is
@@ -1036,7 +1036,7 @@ int tile_batch(gr_ctx *c, int nb, int h, int w, int slot0, RasterOut out, hipStr
     // takes chains as well, 2.52 -> 2.42 us per C2 view at 1000 x 750; its FUSED kernel does not: rolling chains of 16 leave a
     // 1000 x 750 launch with 24 workgroups per view, 3.56 -> 4.13 us -- profiles/r06_ab/micro_chains.log.)
     const bool light = a.cap_tile > 0 && (a.cap_tile <= 512 || (a.micro && out.winner == nullptr));
-    const bool chain = (a.var & 1) == 0 && ((a.var & 16) != 0 || (light && (int64_t)a.T * nb >= 16384));
+    const bool chain = (a.var & GR_VAR_ONE_TILE) == 0 && ((a.var & GR_VAR_CHAINS) != 0 || (light && (int64_t)a.T * nb >= 16384));
     // Rolling chains of GR_ROLL_KT tiles (k_raster_tile_roll) where a chain of four would run -- for the FUSED kernel, whose
     // epilogue stores nothing: C2 15.07 -> 14.22 us per view, C5 29.99 -> 28.67 (profiles/r05_ab/rolling_chains.log).  The ids
     // kernels lose with them (C2 13.21 -> 13.94, C5 28.5 -> 33.3): the wait for the next tile's request, placed before the
@@ -1061,7 +1061,7 @@ int tile_batch(gr_ctx *c, int nb, int h, int w, int slot0, RasterOut out, hipStr
     // the usual ids-only call: rows of whole 16-byte pieces, every view's plane 16-byte aligned, no depth image
     // (variant bit 512: the general ids kernel also where the plain one would run)
     const bool plain = !out.winner && out.ids && !out.depth && (w & 3) == 0 && (reinterpret_cast<uintptr_t>(out.ids) & 15) == 0 &&
-                       !(a.var & 512);
+                       !(a.var & GR_VAR_GENERAL_IDS);
     if (roll) {  // fused, 64 x 32 tiles, single-pass binning
       if (a.ent40 && a.micro) GR_LAUNCH_EV(ev_none, ev_stop, (k_raster_tile_roll<6, 5, 256, true, GR_LDS_PAD, true, false, GR_ROLL_KT, true>), grid, block, pad, s, a, out);
       else if (a.ent40) GR_LAUNCH_EV(ev_none, ev_stop, (k_raster_tile_roll<6, 5, 256, true, GR_LDS_PAD, true, false, GR_ROLL_KT, false>), grid, block, pad, s, a, out);

@@ -293,7 +293,7 @@ int gr_ray_pairs(gr_ctx *c, const double *starts, const double *ends, const int3
   }
   note_stream(c, s);
   char *base = (char *)c->sort_tmp;
-  if (c->opt_dbg & 1024) GR_HIP(c, hipMemsetAsync(base, 0xFF, c->sort_bytes, s));   // test hook: nothing survives between calls
+  if (c->opt_dbg & GR_DBG_POISON_RAYS) GR_HIP(c, hipMemsetAsync(base, 0xFF, c->sort_bytes, s));   // test hook: nothing survives between calls
   unsigned long long *counter = (unsigned long long *)base;
   RayRec *rec = (RayRec *)(base + o_rec);
   unsigned long long *keys = (unsigned long long *)(base + o_keys), *sorted = (unsigned long long *)(base + o_sorted);
@@ -301,7 +301,7 @@ int gr_ray_pairs(gr_ctx *c, const double *starts, const double *ends, const int3
   GR_HIP(c, hipMemsetAsync(counter, 0, sizeof(unsigned long long), s));
   if (tiles > 0) {
     hipLaunchKernelGGL(k_ray_prep, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, starts, ends, ray_ids, n, rec);
-    const int64_t max_grid = (c->opt_dbg & 2048) ? 7 : GR_RAY_MAX_GRID;   // test hook: a few workgroups stride over all tiles
+    const int64_t max_grid = (c->opt_dbg & GR_DBG_RAY_GRID_7) ? 7 : GR_RAY_MAX_GRID;   // test hook: a few workgroups stride over all tiles
     const unsigned grid = (unsigned)(tiles < max_grid ? tiles : max_grid);
     if (fill)
       hipLaunchKernelGGL(k_ray_pairs<true>, dim3(grid), dim3(GR_RAY_TILE), 0, s, rec, ends, n, T, tiles, threshold, counter,

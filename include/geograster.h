@@ -119,23 +119,8 @@ enum {
                                set by hand -- process-wide, so that another context for the same mesh and image size
                                starts with segments that fit) or, beyond 65536 slots, or 24 GB of entry memory for ONE
                                view, bins exactly.  Setting the option forgets what the context learned          */
-  GR_OPT_VARIANT = 7,       /* mode bits (results identical; the parity tests run every one against the oracle):
-                                    1 = one tile per workgroup of the tile kernel (default: chains of four consecutive tiles in
-                                        large launches of light tiles, rolling chains of 16 for the fused kernel);
-                                    4 = fused votes on the caller's stream (default: a side stream beside the next group's binning;
-                                        the profiling scripts use it: rocprofv3 counter passes do not survive the side stream);
-                                   16 = chains whatever the size of the launch (tests: small images through the chain kernels);
-                                  128 = 48-byte entries always (default: 40-byte entries; images with faces of 93 pixels and more
-                                        fall back to 48 bytes, remembered like the slots per tile);
-                                  512 = the general ids kernel (depth output, any width) also where the plain one would run;
-                                 4096 = micro lists never, 8192 = always (default: a call whose views show mostly faces of at most
-                                        4 x 4 pixels -- a mesh rendered at a fraction of its photos' resolution -- teaches the
-                                        library to keep, for that mesh and image size, a second list per tile for such faces,
-                                        which the tile kernel point-samples one face per lane);
-                                16384 = no look at the first launch group's counts (every overflow goes through gr_raster_status);
-                               131072 = tile counters packed side by side whatever the image size (default: images of at most
-                                        1024 tiles keep one counter per 128-byte line -- atomics on one line are served one after
-                                        the other) */
+  GR_OPT_VARIANT = 7,       /* mode bits, the OR of GR_VAR_* below (results identical; the parity tests run every one against the
+                               oracle) */
   GR_OPT_SHARE_LEARNED = 8, /* 1 (default): consult and feed the process-wide table of learned slots per tile / entry forms
                                (and its file, gr_learned_cache_file); 0: this context learns for itself only.  Setting
                                GR_OPT_DIRECT_CAP by hand switches it off; this option switches it back on            */
@@ -156,10 +141,35 @@ enum {
                                camera of cameras.py:446-477); results depend on this option by design -- the oracle has the same
                                switch (oracle_raster.c R1-GL) and the parity tests run both                              */
   GR_OPT_DEBUG_LDS = 98,    /* extra dynamic LDS bytes per tile workgroup: lowers occupancy (timing experiments)     */
-  GR_OPT_DEBUG = 99         /* test hook: 512 = entry slots and row counts are poisoned with 0xFF before every launch group is
-                               binned (results stay right: tests/test_overflow_protocol.py); 1024 = gr_ray_pairs poisons its
-                               scratch with 0xFF at the start of every call, 2048 = its grid is capped at 7 workgroups, which
-                               stride over all tiles as a launch beyond 2^20 tiles does (tests/test_ray_pairs.py)  */
+  GR_OPT_DEBUG = 99         /* test hooks, the OR of GR_DBG_* below (results stay right)                             */
+};
+/* bits of GR_OPT_VARIANT */
+enum {
+  GR_VAR_ONE_TILE = 1,        /* one tile per workgroup of the tile kernel (default: chains of four consecutive tiles in large
+                                 launches of light tiles, rolling chains of 16 for the fused kernel)                       */
+  GR_VAR_VOTES_INLINE = 4,    /* fused votes on the caller's stream (default: a side stream beside the next group's binning;
+                                 the profiling scripts use it: rocprofv3 counter passes do not survive the side stream)    */
+  GR_VAR_CHAINS = 16,         /* chains whatever the size of the launch (tests: small images through the chain kernels)    */
+  GR_VAR_ENT48 = 128,         /* 48-byte entries always (default: 40-byte entries; images with faces of 93 pixels and more
+                                 fall back to 48 bytes, remembered like the slots per tile)                                */
+  GR_VAR_GENERAL_IDS = 512,   /* the general ids kernel (depth output, any width) also where the plain one would run       */
+  GR_VAR_MICRO_NEVER = 4096,  /* micro lists never, ...                                                                    */
+  GR_VAR_MICRO_ALWAYS = 8192, /* ... always (default: a call whose views show mostly faces of at most 4 x 4 pixels -- a mesh
+                                 rendered at a fraction of its photos' resolution -- teaches the library to keep, for that
+                                 mesh and image size, a second list per tile for such faces, which the tile kernel
+                                 point-samples one face per lane)                                                          */
+  GR_VAR_NO_LOOK = 16384,     /* no look at the first launch group's counts (every overflow goes through gr_raster_status) */
+  GR_VAR_PACKED_COUNTERS = 131072 /* tile counters packed side by side whatever the image size (default: images of at most
+                                 1024 tiles keep one counter per 128-byte line -- atomics on one line are served one after
+                                 the other)                                                                                */
+};
+/* bits of GR_OPT_DEBUG */
+enum {
+  GR_DBG_POISON_SLOTS = 512,  /* entry slots and row counts are poisoned with 0xFF before every launch group is binned
+                                 (tests/test_overflow_protocol.py)                                                         */
+  GR_DBG_POISON_RAYS = 1024,  /* gr_ray_pairs poisons its scratch with 0xFF at the start of every call                      */
+  GR_DBG_RAY_GRID_7 = 2048    /* gr_ray_pairs' grid is capped at 7 workgroups, which stride over all tiles as a launch beyond
+                                 2^20 tiles does (tests/test_ray_pairs.py)                                                 */
 };
 int gr_set_option(gr_ctx *ctx, int key, int value);
 
@@ -196,11 +206,15 @@ int gr_raster_face_ids(gr_ctx *ctx, const float *cams, int n_views, int h, int w
  * views.  At most one such retry per cause for a given (mesh, image size). */
 int gr_raster_status(gr_ctx *ctx, gr_raster_stats *out_h);
 /* Why the last raster call overflowed, as far as gr_raster_status (and the look at a first launch group) read it: the OR of
- * 1 = a tile list outgrew its slots where it was stored (single-pass: compiled entries beyond the slots per tile, micro records
- *     beyond 1.25 x the slots per tile; exact binning: a view's entry or record list),
- * 2 = a face did not fit the 40-byte entry form,
- * 4 = with micro lists: a tile's two lists, each within its own bound, together outgrew the tile's segment (they met).
- * 0 after a call without overflow.  Host only: no device work, no synchronisation. */
+ * GR_CAUSE_*; 0 after a call without overflow.  Host only: no device work, no synchronisation. */
+enum {
+  GR_CAUSE_LIST_OUTGREW = 1, /* a tile list outgrew its slots where it was stored (single-pass: compiled entries beyond the slots
+                                per tile, micro records beyond 1.25 x the slots per tile; exact binning: a view's entry or record
+                                list)                                                                                       */
+  GR_CAUSE_SHORT_MISS = 2,   /* a face did not fit the 40-byte entry form                                                    */
+  GR_CAUSE_LISTS_MET = 4     /* with micro lists: a tile's two lists, each within its own bound, together outgrew the tile's
+                                segment (they met)                                                                          */
+};
 int gr_raster_overflow_causes(const gr_ctx *ctx);
 
 /* render_flat gather -- replaces meshes.py:1921-1937: out[p,:] = face_tex[ids[p],:] where ids[p] != -1 else NaN.

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from geograypher_amd import _hip
 from geograypher_amd.utils import synthetic
 from oracle import oracle_c
 
@@ -267,7 +268,7 @@ def test_irregular_tin_workload_full_size_and_quarter_scale(hip):
     """The bench's workload_3 (synthetic.tin_mesh: 1.2 M faces, log-normal triangle areas, Delaunay slivers, folded bumps; the
     caller's face order is spatially incoherent) under a C2 camera: ids at 4000 x 3000 and at the reference's aggregate scale
     0.25, and the fused votes of the view, bit for bit against the oracle."""
-    hip.set_option(2, 5); hip.set_option(6, 512); hip.set_option(7, 0); hip.set_option(3, 64)
+    hip.set_option(_hip.GR_OPT_TILE_H_LOG2, 5); hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512); hip.set_option(_hip.GR_OPT_VARIANT, 0); hip.set_option(_hip.GR_OPT_BATCH, 64)
     pts, faces = synthetic.tin_mesh()
     F, C = faces.shape[0], 4
     cams = synthetic.config2_cameras(50)

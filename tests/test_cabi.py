@@ -30,6 +30,31 @@ def test_library_exports_every_declared_symbol_at_header_version_126():
     assert lib.gr_version() == header == 126
 
 
+def _header_enumerators():
+    """{name: value} of every enumerator of every `enum { ... }` in include/geograster.h."""
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "geograster.h").read_text(), flags=re.S)
+    found = {}
+    for body in re.findall(r"\benum\s*\{(.*?)\}", text, re.S):
+        for item in filter(None, (x.strip() for x in body.split(","))):
+            name, value = re.fullmatch(r"(GR_\w+)\s*=\s*(-?\d+)", item).groups()
+            assert name not in found, name
+            found[name] = int(value)
+    return found
+
+
+def test_binding_constants_are_the_header_enumerators():
+    """Every enumerator of the header is a module constant of the binding with the same value, and the binding has no GR_*
+    integer the header does not define (GR_CAM_FLOATS is the header's one #define among them): a name missing on either side
+    fails, so does a value that moved on one side only."""
+    header = _header_enumerators()
+    assert len(header) >= 35 and header["GR_EOVERFLOW"] == -6 and header["GR_VAR_NO_LOOK"] == 16384
+    text = (ROOT / "include" / "geograster.h").read_text()
+    header["GR_CAM_FLOATS"] = int(re.search(r"#define GR_CAM_FLOATS (\d+)", text).group(1))
+    binding = {k: v for k, v in vars(_hip).items() if k.startswith("GR_") and isinstance(v, int)}
+    assert sorted(binding) == sorted(header)
+    assert binding == header
+
+
 def _header_struct(name):
     """[(field, C type)] of `typedef struct <name> { ... }` in include/geograster.h."""
     text = (ROOT / "include" / "geograster.h").read_text()

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from geograypher_amd import _hip
 from geograypher_amd.cameras import SegmentorPhotogrammetryCameraSet
 from geograypher_amd.meshes import TexturedPhotogrammetryMesh
 from geograypher_amd.predictors import ArrayLabelSegmentor
@@ -30,13 +31,13 @@ VARIANTS = {"default": (5, 512, 0), "tile32_chain": (5, 512, 16), "tile64_single
 @pytest.fixture(params=list(VARIANTS), autouse=True)
 def raster_variant(request, hip):
     thl, cap, var = VARIANTS[request.param]
-    hip.set_option(2, thl)
-    hip.set_option(6, cap)
-    hip.set_option(7, var)
+    hip.set_option(_hip.GR_OPT_TILE_H_LOG2, thl)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
+    hip.set_option(_hip.GR_OPT_VARIANT, var)
     yield request.param
-    hip.set_option(2, 5)
-    hip.set_option(6, 512)
-    hip.set_option(7, 0)
+    hip.set_option(_hip.GR_OPT_TILE_H_LOG2, 5)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)
+    hip.set_option(_hip.GR_OPT_VARIANT, 0)
 
 
 def _same(a, b):
@@ -97,12 +98,12 @@ def test_faces_centred_on_tile_corners_through_the_93_pixel_boundary(hip, varian
     rec = np.zeros((1, 16), dtype=np.float32)      # identity rotation, camera at the origin: q = p
     rec[0, [0, 4, 8]] = 1.0
     rec[0, 12], rec[0, 13], rec[0, 14], rec[0, 15] = f, 0.5 * w, 0.5 * h, 0.05
-    hip.set_option(7, variant)
+    hip.set_option(_hip.GR_OPT_VARIANT, variant)
     try:
         ids = _check_views(hip, points, faces, rec, h, w, depth=True)
     finally:
-        hip.set_option(7, 0)
-        hip.set_option(6, 512)
+        hip.set_option(_hip.GR_OPT_VARIANT, 0)
+        hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)
     assert (ids >= 0).mean() > 0.2 and len(np.unique(ids)) > 0.8 * faces.shape[0]
 
 
@@ -288,7 +289,7 @@ def test_empty_view_and_single_face(hip):
 @pytest.mark.parametrize("batch", [64, 32, 5, 1])
 def test_many_views_in_one_call_cross_batch_boundary(hip, batch):
     """More views than one launch group: results must not depend on the batching."""
-    hip.set_option(3, batch)
+    hip.set_option(_hip.GR_OPT_BATCH, batch)
     (points, faces), cams = synthetic.config1_scene()
     poses = [synthetic.nadir_pose(3.0 * k - 30, 2.0 * k - 20, 35.0 + k, yaw_deg=11.0 * k) for k in range(70)]
     cams = synthetic.camera_set_from_poses(poses, f=260.0, width=320, height=200)
@@ -304,7 +305,7 @@ def test_many_views_in_one_call_cross_batch_boundary(hip, batch):
         hip.raster_project_labels(recs, labels, 3, v2, c2)
         assert torch.equal(v1, v2) and torch.equal(c1, c2)
     finally:
-        hip.set_option(3, 64)
+        hip.set_option(_hip.GR_OPT_BATCH, 64)
 
 
 def test_single_pass_binning_overflow_learns_or_falls_back(hip):
@@ -312,10 +313,10 @@ def test_single_pass_binning_overflow_learns_or_falls_back(hip):
     needs and the retry (single-pass binning with segments of that size) must reproduce the oracle.  20 000 faces stacked
     in ONE tile need more slots than a segment may have: that retry bins exactly (two-pass), same results."""
     (points, faces), cams = synthetic.config1_scene()
-    hip.set_option(6, 8)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 8)
     ids = _check_views(hip, points, faces, _records(cams), 480, 640)
     assert hip.last_stats["overflow"] == 0 and (ids >= 0).mean() > 0.5
-    hip.set_option(6, 512)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)
     n = 20000
     rng = np.random.default_rng(5)
     centre = rng.uniform(-0.2, 0.2, size=(n, 1, 3)) * np.array([1.0, 1.0, 0.0]) + np.array([0.0, 0.0, 1.0]) * rng.uniform(-1, 0, size=(n, 1, 1))
@@ -325,7 +326,7 @@ def test_single_pass_binning_overflow_learns_or_falls_back(hip):
     cams2 = synthetic.camera_set_from_poses([synthetic.nadir_pose(0, 0, 5.0)], f=300.0, width=64, height=64)
     ids2 = _check_views(hip, points2, faces2, _records(cams2), 64, 64)
     assert hip.last_stats["overflow"] == 0 and hip.last_stats["entries"] > 16384 and (ids2 >= 0).mean() > 0.2
-    hip.set_option(6, 512)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)
 
 
 def test_bin_overflow_is_detected_and_retried(hip, raster_variant):
@@ -460,7 +461,7 @@ def test_fused_votes_with_partial_views_and_scattered_face_order(hip, compat, sh
     cams = synthetic.camera_set_from_poses(poses, f=300.0, width=320, height=200)
     recs = _records(cams)
     hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
-    hip.set_option(3, 4)  # three launch groups
+    hip.set_option(_hip.GR_OPT_BATCH, 4)  # three launch groups
     try:
         ids = hip.raster_face_ids(recs, 200, 320)
         ids_np = ids.cpu().numpy()
@@ -476,7 +477,7 @@ def test_fused_votes_with_partial_views_and_scattered_face_order(hip, compat, sh
             np.testing.assert_array_equal(v2.cpu().numpy().view(np.uint32), want_v)
             np.testing.assert_array_equal(c2.cpu().numpy().view(np.uint32), want_c)
     finally:
-        hip.set_option(3, 64)
+        hip.set_option(_hip.GR_OPT_BATCH, 64)
 
 
 def test_end_to_end_api_matches_oracle_pipeline(hip, oracle_backend_cls):

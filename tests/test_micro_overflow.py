@@ -8,14 +8,17 @@ import numpy as np
 import pytest
 import torch
 
+from geograypher_amd import _hip
 from geograypher_amd.utils import synthetic
 from oracle import oracle_c
 
 pytestmark = pytest.mark.gpu
 
-MICRO, NO_LOOK = 8192, 16384   # variant bits: micro lists always; no look at the first launch group (status-call protocol)
-SINGLE, CHAIN = 1, 16          # variant bits: one tile per workgroup; chains of tiles even in small launches
-LIST_OUTGREW, SHORT_MISS, LISTS_MET = 1, 2, 4   # gr_raster_overflow_causes
+# variant bits: micro lists always; no look at the first launch group (status-call protocol)
+MICRO, NO_LOOK = _hip.GR_VAR_MICRO_ALWAYS, _hip.GR_VAR_NO_LOOK
+# variant bits: one tile per workgroup; chains of tiles even in small launches
+SINGLE, CHAIN = _hip.GR_VAR_ONE_TILE, _hip.GR_VAR_CHAINS
+LIST_OUTGREW, LISTS_MET = _hip.GR_CAUSE_LIST_OUTGREW, _hip.GR_CAUSE_LISTS_MET   # gr_raster_overflow_causes
 H, W, C = 240, 320, 4
 
 
@@ -78,11 +81,11 @@ def both_lists():
 
 
 def _defaults(hip):
-    hip.set_option(99, 0)
-    hip.set_option(2, 5)
-    hip.set_option(3, 64)
-    hip.set_option(7, 0)
-    hip.set_option(6, 512)
+    hip.set_option(_hip.GR_OPT_DEBUG, 0)
+    hip.set_option(_hip.GR_OPT_TILE_H_LOG2, 5)
+    hip.set_option(_hip.GR_OPT_BATCH, 64)
+    hip.set_option(_hip.GR_OPT_VARIANT, 0)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)
 
 
 @pytest.fixture(autouse=True)
@@ -111,11 +114,11 @@ def _meeting_cap(hip, scene, thl):
     hip.upload_mesh(scene.points.astype(np.float32), scene.faces.astype(np.int32))
     if thl in _CAPS:
         return _CAPS[thl]
-    hip.set_option(2, thl)
-    hip.set_option(7, MICRO | NO_LOOK)
+    hip.set_option(_hip.GR_OPT_TILE_H_LOG2, thl)
+    hip.set_option(_hip.GR_OPT_VARIANT, MICRO | NO_LOOK)
     seen = {}
     for cap in range(64, 8193, 64):
-        hip.set_option(6, cap)
+        hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
         seen[cap] = _causes_of_unchecked_ids(hip, scene.recs[4:])
         if seen[cap] in (LISTS_MET, 0):
             break
@@ -146,9 +149,9 @@ def test_fused_first_call_whose_lists_meet(hip, both_lists, path):
     cap = _meeting_cap(hip, s, thl)
     views = slice(4, 8)
     want = s.votes(range(4, 8))
-    hip.set_option(2, thl)
-    hip.set_option(7, MICRO | NO_LOOK | extra)
-    hip.set_option(6, cap)
+    hip.set_option(_hip.GR_OPT_TILE_H_LOG2, thl)
+    hip.set_option(_hip.GR_OPT_VARIANT, MICRO | NO_LOOK | extra)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
     for attempt in range(2):
         votes, counts = hip.new_vote_buffers(C)
         ids_out = torch.full((4, H, W), -7, dtype=torch.int32, device=hip.device) if with_ids else None
@@ -172,15 +175,15 @@ def test_lists_meet_in_a_later_launch_group(hip, both_lists):
     s = both_lists
     cap = _meeting_cap(hip, s, 5)
     want = s.votes(range(8))
-    hip.set_option(3, 4)
-    hip.set_option(7, MICRO | NO_LOOK)
-    hip.set_option(6, cap)
+    hip.set_option(_hip.GR_OPT_BATCH, 4)
+    hip.set_option(_hip.GR_OPT_VARIANT, MICRO | NO_LOOK)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
     votes, counts = hip.new_vote_buffers(C)
     hip.raster_project_labels(s.recs, s.labels, C, votes, counts)
     st = hip.last_stats
     assert hip.last_retries == 1 and st["views_done"] == 8 and st["overflow"] == 0 and st["overflow_causes"] == LISTS_MET, st
     _assert_votes(votes, counts, want)
-    hip.set_option(6, cap)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
     votes, counts = hip.new_vote_buffers(C)
     hip.raster_project_labels(s.recs, s.labels, C, votes, counts, check=False)
     with pytest.raises(RuntimeError, match="overflow"):
@@ -195,8 +198,8 @@ def test_look_at_the_first_group_learns_a_segment_for_both_lists(hip, both_lists
     s = both_lists
     cap = _meeting_cap(hip, s, 5)
     want = s.votes(range(4, 8))
-    hip.set_option(7, MICRO)
-    hip.set_option(6, cap)
+    hip.set_option(_hip.GR_OPT_VARIANT, MICRO)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
     votes, counts = hip.new_vote_buffers(C)
     hip.raster_project_labels(s.recs[4:], s.labels[4:], C, votes, counts)
     st = hip.last_stats
@@ -213,14 +216,14 @@ def test_ids_only_call_whose_lists_meet(hip, both_lists):
     reports cause 4."""
     s = both_lists
     cap = _meeting_cap(hip, s, 5)
-    hip.set_option(7, MICRO | NO_LOOK)
-    hip.set_option(6, cap)
+    hip.set_option(_hip.GR_OPT_VARIANT, MICRO | NO_LOOK)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
     ids, depth = hip.raster_face_ids(s.recs[4:], H, W, want_depth=True)
     assert hip.last_retries == 1 and hip.last_stats["overflow_causes"] == LISTS_MET, hip.last_stats
     for v in range(4):
         np.testing.assert_array_equal(ids[v].cpu().numpy(), s.ids[4 + v])
         np.testing.assert_array_equal(depth[v].cpu().numpy().view(np.int32), s.depth[4 + v].view(np.int32))
-    hip.set_option(6, cap)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
     hip.raster_face_ids(s.recs[4:], H, W, check=False)
     with pytest.raises(RuntimeError, match="overflow"):
         hip.raster_status()
@@ -236,14 +239,14 @@ def test_single_list_overflow_with_micro_lists(hip, which):
     points, faces = _terrain() if which == "micro_records" else _merge(_layers())
     s = _Scene(points, faces, _recs(40.0, n=2))
     hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
-    hip.set_option(7, MICRO | NO_LOOK)
-    hip.set_option(6, 64)
+    hip.set_option(_hip.GR_OPT_VARIANT, MICRO | NO_LOOK)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 64)
     ids, depth = hip.raster_face_ids(s.recs, H, W, want_depth=True)
     assert hip.last_retries == 1 and hip.last_stats["overflow_causes"] & LIST_OUTGREW, hip.last_stats
     for v in range(2):
         np.testing.assert_array_equal(ids[v].cpu().numpy(), s.ids[v])
         np.testing.assert_array_equal(depth[v].cpu().numpy().view(np.int32), s.depth[v].view(np.int32))
-    hip.set_option(6, 64)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 64)
     votes, counts = hip.new_vote_buffers(C)
     hip.raster_project_labels(s.recs, s.labels, C, votes, counts)
     assert hip.last_retries == 1 and hip.last_stats["overflow_causes"] & LIST_OUTGREW, hip.last_stats
@@ -256,14 +259,14 @@ def test_poisoned_scratch_fused_call_whose_lists_meet(hip, both_lists):
     s = both_lists
     cap = _meeting_cap(hip, s, 5)
     want = s.votes(range(4, 8))
-    hip.set_option(7, MICRO | NO_LOOK)
-    hip.set_option(6, cap)
-    hip.set_option(99, 512)
+    hip.set_option(_hip.GR_OPT_VARIANT, MICRO | NO_LOOK)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
+    hip.set_option(_hip.GR_OPT_DEBUG, _hip.GR_DBG_POISON_SLOTS)
     votes, counts = hip.new_vote_buffers(C)
     hip.raster_project_labels(s.recs[4:], s.labels[4:], C, votes, counts)
     assert hip.last_retries == 1 and hip.last_stats["overflow_causes"] == LISTS_MET and hip.last_stats["views_done"] == 4
     _assert_votes(votes, counts, want)
-    hip.set_option(99, 0)
+    hip.set_option(_hip.GR_OPT_DEBUG, 0)
     votes, counts = hip.new_vote_buffers(C)
     hip.raster_project_labels(s.recs[4:], s.labels[4:], C, votes, counts)
     assert _lessons(hip) == 0 and hip.last_stats["overflow_causes"] == 0

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from geograypher_amd import _hip
 from geograypher_amd.utils import synthetic
 from oracle import oracle_c
 
@@ -15,7 +16,7 @@ def _records(cams, scale=1.0, near=0.05):
     return cams.get_raster_records(scale, near=near)
 
 
-NO_LOOK = 16384  # variant bit: no look at the first launch group's counts -- every overflow goes through gr_raster_status
+NO_LOOK = _hip.GR_VAR_NO_LOOK  # variant bit: no look at the first launch group's counts -- every overflow goes through gr_raster_status
 
 
 def _lessons(h):
@@ -26,13 +27,13 @@ def _lessons(h):
 
 @pytest.fixture(autouse=True)
 def _default_options(hip):
-    hip.set_option(2, 5)
-    hip.set_option(6, 512)
-    hip.set_option(7, 0)
-    hip.set_option(3, 64)
+    hip.set_option(_hip.GR_OPT_TILE_H_LOG2, 5)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)
+    hip.set_option(_hip.GR_OPT_VARIANT, 0)
+    hip.set_option(_hip.GR_OPT_BATCH, 64)
     yield
-    hip.set_option(3, 64)
-    hip.set_option(6, 512)
+    hip.set_option(_hip.GR_OPT_BATCH, 64)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)
 
 
 def test_maximum_image_size(hip):
@@ -67,7 +68,7 @@ def test_fused_call_resumes_after_a_later_launch_group_overflows(hip):
     recs = _records(cams)
     hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
     try:
-        hip.set_option(6, 4096)
+        hip.set_option(_hip.GR_OPT_DIRECT_CAP, 4096)
         need = []
         for v in range(len(cams)):
             hip.raster_face_ids(recs[v:v + 1], 480, 640)
@@ -79,14 +80,14 @@ def test_fused_call_resumes_after_a_later_launch_group_overflows(hip):
         labels = np.stack([synthetic.synthetic_labels(ids_np[v], v, C) for v in range(len(cams))])
         want_v, want_c = hip.new_vote_buffers(C)
         hip.project_labels(ids, labels, C, want_v, want_c)
-        hip.set_option(3, 4)      # groups: views 0-3 | 4-7 (overflows: views 6, 7) | 8-10
-        hip.set_option(6, cap)    # forgets what the context has learned
+        hip.set_option(_hip.GR_OPT_BATCH, 4)      # groups: views 0-3 | 4-7 (overflows: views 6, 7) | 8-10
+        hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)    # forgets what the context has learned
         v2, c2 = hip.new_vote_buffers(C)
         hip.raster_project_labels(recs, labels, C, v2, c2)
         assert hip.last_retries > 0 and hip.last_stats["overflow"] == 0 and hip.last_stats["views_done"] == len(cams)
         assert torch.equal(v2, want_v) and torch.equal(c2, want_c)
         # unchecked: the first group's votes only, and the status call is the one that tells
-        hip.set_option(6, cap)
+        hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
         v3, c3 = hip.new_vote_buffers(C)
         hip.raster_project_labels(recs, labels, C, v3, c3, check=False)
         assert hip.last_stats == {"unchecked": True}
@@ -96,8 +97,8 @@ def test_fused_call_resumes_after_a_later_launch_group_overflows(hip):
         hip.project_labels(ids[:4], labels[:4], C, part_v, part_c)
         assert torch.equal(v3, part_v) and torch.equal(c3, part_c)
     finally:
-        hip.set_option(3, 64)
-        hip.set_option(6, 512)
+        hip.set_option(_hip.GR_OPT_BATCH, 64)
+        hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)
 
 
 
@@ -114,7 +115,7 @@ def test_short_entries_fall_back_when_a_later_group_has_a_large_face(hip):
     cams = synthetic.camera_set_from_poses(poses, f=500.0, width=640, height=480)
     recs = _records(cams)
     hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
-    hip.set_option(7, 128)                     # 48-byte entries from the start
+    hip.set_option(_hip.GR_OPT_VARIANT, _hip.GR_VAR_ENT48)                     # 48-byte entries from the start
     want = hip.raster_face_ids(recs, 480, 640)
     assert hip.last_retries == 0
     for v in (0, 4):
@@ -122,9 +123,9 @@ def test_short_entries_fall_back_when_a_later_group_has_a_large_face(hip):
     labels = np.stack([synthetic.synthetic_labels(want[v].cpu().numpy(), v, C) for v in range(len(cams))])
     want_v, want_c = hip.new_vote_buffers(C)
     hip.project_labels(want, labels, C, want_v, want_c)
-    hip.set_option(7, 0)
-    hip.set_option(3, 4)                       # groups: views 0-3 (small faces) | 4-5 (view 4: large faces)
-    hip.set_option(6, 512)                     # forgets what the context has learned
+    hip.set_option(_hip.GR_OPT_VARIANT, 0)
+    hip.set_option(_hip.GR_OPT_BATCH, 4)                       # groups: views 0-3 (small faces) | 4-5 (view 4: large faces)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)                     # forgets what the context has learned
     got = hip.raster_face_ids(recs[:4], 480, 640)
     assert hip.last_retries == 0 and torch.equal(got, want[:4])          # small faces only: the short form holds them
     v2, c2 = hip.new_vote_buffers(C)
@@ -145,8 +146,8 @@ def test_slots_per_tile_set_by_hand_to_an_odd_size(hip, look):
     (points, faces), cams = synthetic.config1_scene()
     recs = _records(cams)
     hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
-    hip.set_option(7, 0 if look else NO_LOOK)
-    hip.set_option(6, 80)
+    hip.set_option(_hip.GR_OPT_VARIANT, 0 if look else NO_LOOK)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 80)
     ids = hip.raster_face_ids(recs, 480, 640)
     assert hip.last_stats["max_entries"] > 80
     assert (hip.last_retries, hip.last_stats["rebinned_groups"]) == ((0, 1) if look else (1, 0))
@@ -177,16 +178,16 @@ def test_short_form_miss_leaves_no_stale_entry(hip, look):
     points, faces, cams, recs = _big_face_scene()
     C = 3
     hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
-    hip.set_option(7, 128)
+    hip.set_option(_hip.GR_OPT_VARIANT, _hip.GR_VAR_ENT48)
     want = hip.raster_face_ids(recs, 480, 640)
     np.testing.assert_array_equal(want[0].cpu().numpy(), oracle_c.raster(points, faces, recs[0], 480, 640))
     labels = np.stack([synthetic.synthetic_labels(want[v].cpu().numpy(), v, C) for v in range(len(cams))])
     want_v, want_c = hip.new_vote_buffers(C)
     hip.project_labels(want, labels, C, want_v, want_c)
     try:
-        hip.set_option(7, 0 if look else NO_LOOK)
-        hip.set_option(6, 512)      # forgets the entry form: the call starts with 40-byte entries
-        hip.set_option(99, 512)     # poisoned scratch
+        hip.set_option(_hip.GR_OPT_VARIANT, 0 if look else NO_LOOK)
+        hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)      # forgets the entry form: the call starts with 40-byte entries
+        hip.set_option(_hip.GR_OPT_DEBUG, _hip.GR_DBG_POISON_SLOTS)     # poisoned scratch
         v2, c2 = hip.new_vote_buffers(C)
         hip.raster_project_labels(recs, labels, C, v2, c2)
         assert (hip.last_retries, hip.last_stats["rebinned_groups"]) == ((0, 1) if look else (1, 0))
@@ -200,7 +201,7 @@ def test_short_form_miss_leaves_no_stale_entry(hip, look):
         got = hip.raster_face_ids(recs, 480, 640)
         assert torch.equal(got, want)
     finally:
-        hip.set_option(99, 0)
+        hip.set_option(_hip.GR_OPT_DEBUG, 0)
 
 
 def test_second_context_and_new_process_start_sized(hip, tmp_path):
@@ -243,7 +244,7 @@ def test_second_context_and_new_process_start_sized(hip, tmp_path):
         assert _lessons(c) == 1
         # a context that opted out learns for itself only
         d = HipRaster(0)
-        d.set_option(8, 0)
+        d.set_option(_hip.GR_OPT_SHARE_LEARNED, 0)
         d.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
         d.raster_face_ids(recs, 480, 640)
         assert _lessons(d) == 1
@@ -280,7 +281,7 @@ def test_entry_memory_budget_option_shrinks_the_launch_group(hip):
     hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
     want = hip.raster_face_ids(recs, 480, 640)
     try:
-        hip.set_option(9, 4)     # 4 MiB: two views per launch group
+        hip.set_option(_hip.GR_OPT_DIRECT_BUDGET_MB, 4)     # 4 MiB: two views per launch group
         hip.set_profiling(True)
         got = hip.raster_face_ids(recs, 480, 640)
         st = hip.stage_times()
@@ -289,9 +290,9 @@ def test_entry_memory_budget_option_shrinks_the_launch_group(hip):
         assert st["raster_launches"] == -(-64 // ((4 << 20) // per_view)), st
         assert torch.equal(got, want)
         with pytest.raises(ValueError):
-            hip.set_option(9, 0)
+            hip.set_option(_hip.GR_OPT_DIRECT_BUDGET_MB, 0)
     finally:
-        hip.set_option(9, 24 << 10)
+        hip.set_option(_hip.GR_OPT_DIRECT_BUDGET_MB, 24 << 10)
 
 
 def test_argmax_uses_the_shared_context(hip):
@@ -336,7 +337,7 @@ def test_clipped_faces_outgrow_the_record_planes_of_exact_binning(hip):
     cams = synthetic.camera_set_from_poses(poses, f=150.0, width=320, height=240)
     recs = _records(cams, near=0.05)
     hip.upload_mesh(c.astype(np.float32), faces.astype(np.int32))
-    hip.set_option(6, 0)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 0)
     ids = hip.raster_face_ids(recs, 240, 320)
     assert hip.last_retries == 1, hip.last_stats
     for v in range(len(cams)):
@@ -356,13 +357,13 @@ def test_view_totals_left_to_the_status_call(hip):
     recs = _records(cams)
     hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
     keys = ("records", "entries", "max_entries", "overflow", "views_done", "blocks")
-    hip.set_option(7, 0)
-    hip.set_option(6, 512)
-    hip.set_option(3, 3)
+    hip.set_option(_hip.GR_OPT_VARIANT, 0)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)
+    hip.set_option(_hip.GR_OPT_BATCH, 3)
     want_ids = hip.raster_face_ids(recs, 480, 640)
     want = {k: hip.last_stats[k] for k in keys}
-    hip.set_option(3, 64)
-    hip.set_option(6, 512)
+    hip.set_option(_hip.GR_OPT_BATCH, 64)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512)
     hip.raster_face_ids(recs, 480, 640)                       # learns (the look): the next call is an ordinary one
     ids = hip.raster_face_ids(recs, 480, 640, check=False)
     assert hip.last_stats == {"unchecked": True}
@@ -371,8 +372,8 @@ def test_view_totals_left_to_the_status_call(hip):
     assert {k: got[k] for k in keys} == want and torch.equal(ids, want_ids)
     assert {k: hip.raster_status()[k] for k in keys} == want        # asking twice does not count twice
     # an overflow of an unchecked call (no look: the slots are known to be too few only to us)
-    hip.set_option(7, NO_LOOK)
-    hip.set_option(6, 64)
+    hip.set_option(_hip.GR_OPT_VARIANT, NO_LOOK)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 64)
     hip.raster_face_ids(recs, 480, 640, check=False)
     with pytest.raises(RuntimeError, match="overflow"):
         hip.raster_status()

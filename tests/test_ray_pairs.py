@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from geograypher_amd import _hip
 from geograypher_amd.utils import numeric, synthetic
 from tests.conftest import GOLDEN
 from tests.ray_standin import StandInBackend, clip_rays_np, ray_pair_edges_np, rows_distance
@@ -185,7 +186,7 @@ def test_two_streams_share_the_scratch_in_turn(hip, big):
     assert total > 1_000_000
     streams = [torch.cuda.Stream(device=hip.device) for _ in range(2)]
     outs = []
-    hip.set_option(99, 1024)
+    hip.set_option(_hip.GR_OPT_DEBUG, _hip.GR_DBG_POISON_RAYS)
     try:
         for k, st in enumerate(streams):
             with torch.cuda.stream(st):
@@ -193,11 +194,11 @@ def test_two_streams_share_the_scratch_in_turn(hip, big):
                 assert hip.last_ray_pair_calls == 1
         for st in streams:
             st.synchronize()
-        hip.set_option(99, 1024 | 2048)
+        hip.set_option(_hip.GR_OPT_DEBUG, _hip.GR_DBG_POISON_RAYS | _hip.GR_DBG_RAY_GRID_7)
         strided = [_np(x) for x in hip.ray_pair_edges(s_t, e_t, id_t, 0.5, capacity=total)]
         strided_count = hip.ray_pair_count(s_t, e_t, id_t, 0.5)
     finally:
-        hip.set_option(99, 0)
+        hip.set_option(_hip.GR_OPT_DEBUG, 0)
     got0 = [_np(x) for x in outs[0]]
     assert all(np.array_equal(a, b) for a, b in zip(got0, want))
     keep = want[0] >= 1   # the second call dropped ray 0: the same edges, indices one lower
@@ -210,13 +211,14 @@ def test_two_streams_share_the_scratch_in_turn(hip, big):
 def test_poisoned_scratch_strided_grid_and_permutation(hip, gold, survey):
     starts, ends, ids = survey["ray_starts"], survey["ray_ends"], survey["ray_IDs"]
     want = ray_pair_edges_np(starts, ends, ids, 0.5)
-    for dbg in (1024, 2048, 1024 | 2048):   # poisoned scratch; 7 workgroups striding over the 15 tiles; both
-        hip.set_option(99, dbg)
+    poison, grid7 = _hip.GR_DBG_POISON_RAYS, _hip.GR_DBG_RAY_GRID_7
+    for dbg in (poison, grid7, poison | grid7):   # poisoned scratch; 7 workgroups striding over the 15 tiles; both
+        hip.set_option(_hip.GR_OPT_DEBUG, dbg)
         try:
             got = [_np(x) for x in hip.ray_pair_edges(starts, ends, ids, 0.5)]
             count = hip.ray_pair_count(starts, ends, ids, 0.5)
         finally:
-            hip.set_option(99, 0)
+            hip.set_option(_hip.GR_OPT_DEBUG, 0)
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and count == len(want[0])
         assert np.abs(got[2] - want[2]).max() <= _standin_tol(gold)
     perm = np.random.default_rng(1).permutation(len(ids))

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from geograypher_amd import _hip
 from geograypher_amd.utils import synthetic
 from oracle import oracle_c
 
@@ -15,10 +16,10 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(autouse=True)
 def _defaults(hip):
-    hip.set_option(2, 5); hip.set_option(6, 512); hip.set_option(7, 0); hip.set_option(3, 64)
+    hip.set_option(_hip.GR_OPT_TILE_H_LOG2, 5); hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512); hip.set_option(_hip.GR_OPT_VARIANT, 0); hip.set_option(_hip.GR_OPT_BATCH, 64)
     yield
     hip.set_profiling(False)
-    hip.set_option(6, 512); hip.set_option(7, 0); hip.set_option(3, 64)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512); hip.set_option(_hip.GR_OPT_VARIANT, 0); hip.set_option(_hip.GR_OPT_BATCH, 64)
 
 
 @pytest.mark.parametrize("cap,var,batch", [(512, 0, 64), (0, 0, 64), (512, 0, 3), (512, 16384, 64)])
@@ -28,7 +29,7 @@ def test_results_do_not_depend_on_the_timing_events(hip, cap, var, batch):
     (points, faces), cams = synthetic.config1_scene()
     recs = cams.get_raster_records(1.0, near=0.05)
     hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
-    hip.set_option(6, cap); hip.set_option(7, var); hip.set_option(3, batch)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap); hip.set_option(_hip.GR_OPT_VARIANT, var); hip.set_option(_hip.GR_OPT_BATCH, batch)
     hip.set_profiling(True)
     ids, dep = hip.raster_face_ids(recs, 480, 640, want_depth=True)
     ids2 = hip.raster_face_ids(recs, 480, 640)

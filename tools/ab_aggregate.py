@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from geograypher_amd import _hip
 from geograypher_amd._hip import HipRaster
 from geograypher_amd.utils import synthetic
 
@@ -29,7 +30,7 @@ def main():
     labels = torch.randint(0, C, (64, H, W), dtype=torch.uint8, device="cuda").repeat((nv + 63) // 64, 1, 1)[:nv]
     ref = None
     for var in variants:
-        hip.set_option(7, var)
+        hip.set_option(_hip.GR_OPT_VARIANT, var)
         votes, counts = hip.new_vote_buffers(C)
         hip.raster_project_labels(recs, labels, C, votes, counts, ids_out=None, check=True)
         if ref is None:

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from geograypher_amd import _hip
 from geograypher_amd._hip import HipRaster
 from geograypher_amd.utils import synthetic
 
@@ -28,7 +29,7 @@ def main():
             parts = sp.split(":")
             nums = [int(x) for x in parts[1:]] + [None] * 5
             var, dbg, thl, cap, batch = nums[0] or 0, nums[1] or 0, nums[2] or 5, 512 if nums[3] is None else nums[3], nums[4] or 64
-            hip.set_option(2, thl); hip.set_option(6, cap); hip.set_option(7, var); hip.set_option(99, dbg); hip.set_option(3, batch)
+            hip.set_option(_hip.GR_OPT_TILE_H_LOG2, thl); hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap); hip.set_option(_hip.GR_OPT_VARIANT, var); hip.set_option(_hip.GR_OPT_DEBUG, dbg); hip.set_option(_hip.GR_OPT_BATCH, batch)
             hip.raster_face_ids(recs, h, w, out=ids, check=True)
             retries, st0 = hip.last_retries, dict(hip.last_stats)
             if dbg == 0:
@@ -47,7 +48,7 @@ def main():
             print(json.dumps({"variant": parts[0], "image": f"{w}x{h}", **per, "us_per_view": round(sum(per.values()), 1),
                               "entries_per_view": round(st0["entries"] / len(cams)), "max_entries_per_tile": st0["max_entries"],
                               "records_per_view": round(st0["records"] / len(cams)), "retries": retries}))
-    hip.set_option(2, 5); hip.set_option(6, 512); hip.set_option(7, 0); hip.set_option(99, 0); hip.set_option(3, 64)
+    hip.set_option(_hip.GR_OPT_TILE_H_LOG2, 5); hip.set_option(_hip.GR_OPT_DIRECT_CAP, 512); hip.set_option(_hip.GR_OPT_VARIANT, 0); hip.set_option(_hip.GR_OPT_DEBUG, 0); hip.set_option(_hip.GR_OPT_BATCH, 64)
 
 
 if __name__ == "__main__":

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from geograypher_amd import _hip
 from geograypher_amd._hip import HipRaster
 from geograypher_amd.utils import synthetic
 
@@ -61,12 +62,12 @@ def main():
     acc = {v[0]: {"plain": [], "fused": []} for v in variants}
 
     def setopt(var, dbg, thl, cap, ldspad=0, kt=4, batch=64, pfd=2048):
-        hip.set_option(3, batch)
-        hip.set_option(98, ldspad)
-        hip.set_option(2, thl)
-        hip.set_option(6, cap)
-        hip.set_option(7, var)
-        hip.set_option(99, dbg)
+        hip.set_option(_hip.GR_OPT_BATCH, batch)
+        hip.set_option(_hip.GR_OPT_DEBUG_LDS, ldspad)
+        hip.set_option(_hip.GR_OPT_TILE_H_LOG2, thl)
+        hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
+        hip.set_option(_hip.GR_OPT_VARIANT, var)
+        hip.set_option(_hip.GR_OPT_DEBUG, dbg)
 
     for rep in range(reps + 1):
         for name, var, dbg, thl, cap, ldspad, kt, batch, pfd in variants:

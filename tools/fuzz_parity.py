@@ -21,6 +21,7 @@ import torch
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+from geograypher_amd import _hip
 from geograypher_amd._hip import HipRaster
 from geograypher_amd.utils import synthetic
 from oracle import oracle_c
@@ -122,7 +123,7 @@ def one(hip, seed):
         if rng.random() < 0.2:
             var |= b
     batch = int(rng.choice([64, 64, 5, 2, 1]))
-    hip.set_option(2, thl); hip.set_option(6, cap); hip.set_option(7, var); hip.set_option(3, batch)
+    hip.set_option(_hip.GR_OPT_TILE_H_LOG2, thl); hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap); hip.set_option(_hip.GR_OPT_VARIANT, var); hip.set_option(_hip.GR_OPT_BATCH, batch)
     hip.set_vertex_order(order)
     info = {"seed": seed, "vertex_order": order, "faces": int(faces.shape[0]), "views": int(recs.shape[0]), "image": f"{w}x{h}", "thl": thl, "cap": cap,
             "var": var, "batch": batch}

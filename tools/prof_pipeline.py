@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from geograypher_amd import _hip
 from geograypher_amd._hip import HipRaster
 from geograypher_amd.utils import synthetic
 
@@ -20,7 +21,7 @@ H, W, C = 3000, 4000, 4
 points, faces = synthetic.terrain_mesh()
 hip = HipRaster(0)
 xvar = int(sys.argv[4]) if len(sys.argv) > 4 else 0
-hip.set_option(7, 4 | xvar)  # GR_OPT_VARIANT: fused votes on the caller's stream (+ the variant under study)
+hip.set_option(_hip.GR_OPT_VARIANT, _hip.GR_VAR_VOTES_INLINE | xvar)  # GR_OPT_VARIANT: fused votes on the caller's stream (+ the variant under study)
 hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
 recs = torch.from_numpy(synthetic.config2_cameras(50).get_raster_records(1.0, near=1.0)[:nv]).cuda()
 ids = torch.empty((nv, H, W), dtype=torch.int32, device="cuda")

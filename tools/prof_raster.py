@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from geograypher_amd import _hip
 from geograypher_amd._hip import HipRaster
 from geograypher_amd.utils import synthetic
 
@@ -19,8 +20,8 @@ points, faces = synthetic.terrain_mesh()
 cams = synthetic.config2_cameras(50)
 recs = torch.from_numpy(cams.get_raster_records(1.0, near=1.0)[:nv]).cuda()
 hip = HipRaster(0)
-hip.set_option(2, thl)
-hip.set_option(7, kernel)  # GR_OPT_VARIANT
+hip.set_option(_hip.GR_OPT_TILE_H_LOG2, thl)
+hip.set_option(_hip.GR_OPT_VARIANT, kernel)  # GR_OPT_VARIANT
 hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
 ids = torch.empty((nv, 3000, 4000), dtype=torch.int32, device="cuda")
 for _ in range(reps):

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from geograypher_amd import _hip
 from geograypher_amd._hip import HipRaster
 from geograypher_amd.utils import synthetic
 from oracle import oracle_c
@@ -24,7 +25,7 @@ hip.upload_mesh(points.astype(np.float32), faces.astype(np.int32))
 recs = torch.from_numpy(recs_np).cuda()
 out = {}
 for name, cap in (("single_pass_learned", 512), ("exact_two_pass", 0)):
-    hip.set_option(6, cap)
+    hip.set_option(_hip.GR_OPT_DIRECT_CAP, cap)
     ids = hip.raster_face_ids(recs, H, W)  # learns / sizes
     torch.cuda.synchronize()
     t0 = time.perf_counter()
