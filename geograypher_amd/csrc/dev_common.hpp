@@ -9,6 +9,23 @@ namespace {
 __device__ __forceinline__ int imin3(int a, int b, int c) { return min(a, min(b, c)); }
 __device__ __forceinline__ int imax3(int a, int b, int c) { return max(a, max(b, c)); }
 
+// R3 tie rule as a bias on an edge function: left and bottom edges own their pixels
+__device__ __forceinline__ int tie_bias(int dx, int dy) { return ((dy < 0) || (dy == 0 && dx < 0)) ? 0 : -1; }
+
+// Wave-aggregated append to a list whose length is `*counter` (32 or 64 bits).  takers = __ballot(this lane appends), not
+// empty: ONE atomicAdd of the takers' count by the first of them, the returned base shuffled to all.  A taker's place is
+// wave_append(...) + wave_rank(takers, lane), its rank being the takers below it (two values: a caller may add them to a wider
+// index one after the other).  (The ballot is the caller's: every caller skips a wave without takers, and the compiler drops
+// the empty-mask case of the first-lane search only when it sees that test on the same value.)
+__device__ __forceinline__ int wave_rank(unsigned long long takers, int lane) { return __popcll(takers & ((1ull << lane) - 1ull)); }
+template <typename C>
+__device__ __forceinline__ C wave_append(unsigned long long takers, C *counter, int lane) {
+  const int leader = __ffsll((long long)takers) - 1;
+  C base = 0;
+  if (lane == leader) base = atomicAdd(counter, (C)__popcll(takers));
+  return __shfl(base, leader);
+}
+
 // Inclusive prefix sum over the 64 lanes with DPP moves only: the LDS pipe (ds_bpermute shuffles included) is the tile
 // kernel's scarcest resource, VALU issue is not (one extra ds_bpermute per 64-item batch costs 0.34 us per C2 view, 48
 // extra VALU instructions 0.9).  Sources outside a row / masked rows contribute the `old` operand, 0.

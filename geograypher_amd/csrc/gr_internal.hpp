@@ -116,6 +116,34 @@ __device__ __forceinline__ int64_t cidx(const BinArgs &a, int t) {
   return a.clg < 0 ? (int64_t)t : (int64_t)((((uint32_t)t & ((1u << a.clg) - 1u)) << 5) | ((uint32_t)t >> a.clg));
 }
 
+// The SEGMENT of a tile under single-pass binning: cap_tile slots of entry memory (BinArgs::comp), written by k_setup_cull and
+// k_clip_faces (binning.hip: store_entry, the record writer of k_setup_cull), read by the tile kernel (raster_tile.hip).  The slot memory is sized
+// for full entries; short entries pack chunks of 64 at the front of the segment -- the 64 32-byte parts {s0 .. s7} first, then
+// the 64 8-byte parts {s8, s9} --, and with micro lists the tile's second list grows from the segment's END, record p being
+// the GR_MICRO_BYTES that end p records before it.
+enum {
+  GR_ENT_BYTES = GR_ENT_Q * 16,             // a full entry
+  GR_ENT40_BYTES = 40,                      // a short entry (BinArgs::ent40)
+  GR_CHUNK40_BYTES = 64 * GR_ENT40_BYTES,   // a chunk of 64 short entries: 2560
+  GR_CHUNK40_TAIL = 64 * 32,                // ... where its 8-byte parts start: 2048
+  GR_MICRO_BYTES = 32,                      // a micro record
+  // the micro list's own bound: records that fill the whole segment, cap_tile * GR_ENT40_BYTES / GR_MICRO_BYTES = 5/4 cap_tile
+  GR_MICRO_CAP_NUM = GR_ENT40_BYTES / 8,
+  GR_MICRO_CAP_DEN = GR_MICRO_BYTES / 8
+};
+__device__ __forceinline__ uint32_t micro_cap(uint32_t cap_tile) { return cap_tile * GR_MICRO_CAP_NUM / GR_MICRO_CAP_DEN; }
+__device__ __forceinline__ bool micro_fits(uint32_t n_rec, uint32_t cap_tile) {   // n_rec <= micro_cap(cap_tile), for a count that may be torn
+  return n_rec * GR_MICRO_CAP_DEN <= cap_tile * GR_MICRO_CAP_NUM;
+}
+// slots of a segment that n_ent short entries (whole chunks from the front) and n_mic micro records (from the back) take together
+__device__ __forceinline__ uint32_t seg_slots_used(uint32_t n_ent, uint32_t n_mic) {
+  return ((n_ent + 63u) & ~63u) + (n_mic * GR_MICRO_BYTES + (GR_ENT40_BYTES - 1)) / GR_ENT40_BYTES;
+}
+// the box word of a micro record: first column (6 bits) | columns - 1 (2) | first row (6) | rows (3), inside the tile
+struct MicroBox { int col0, dcol, row0, rows; };
+__device__ __forceinline__ int pack_micro_box(int c0, int c1, int q0, int q1) { return c0 | ((c1 - c0) << 6) | (q0 << 8) | ((q1 - q0 + 1) << 14); }
+__device__ __forceinline__ MicroBox unpack_micro_box(int box) { return {box & 63, (box >> 6) & 3, (box >> 8) & 63, (box >> 14) & 7}; }
+
 struct RasterOut {
   int32_t *ids;      // [slot][h][w] or null
   float *depth;      // [slot][h][w] or null

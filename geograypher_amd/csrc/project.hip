@@ -3,6 +3,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "gr_internal.hpp"
+#include "dev_common.hpp"
 
 using namespace grimpl;
 
@@ -265,12 +266,9 @@ __global__ __launch_bounds__(256) void k_emit_index_pairs(uint32_t *__restrict__
     }
     const unsigned long long m = __ballot(emit);
     if (m) {
-      const int leader = __ffsll((long long)m) - 1;
-      unsigned long long base = 0;
-      if (lane == leader) base = atomicAdd(key_count, (unsigned long long)__popcll(m));
-      base = __shfl(base, leader);
+      const unsigned long long base = wave_append(m, key_count, lane);
       if (emit) {
-        const unsigned long long idx = base + __popcll(m & ((1ull << lane) - 1ull));
+        const unsigned long long idx = base + wave_rank(m, lane);
         if ((long long)idx < key_cap) keys[idx] = key;
       }
     }
@@ -343,12 +341,9 @@ __global__ __launch_bounds__(256) void k_emit_rect_pairs(uint32_t *__restrict__ 
     }
     const unsigned long long m = __ballot(emit);
     if (m) {
-      const int leader = __ffsll((long long)m) - 1;
-      unsigned long long base = 0;
-      if (lane == leader) base = atomicAdd(key_count, (unsigned long long)__popcll(m));
-      base = __shfl(base, leader);
+      const unsigned long long base = wave_append(m, key_count, lane);
       if (emit) {
-        const unsigned long long idx = base + __popcll(m & ((1ull << lane) - 1ull));
+        const unsigned long long idx = base + wave_rank(m, lane);
         if ((long long)idx < key_cap) keys[idx] = key;
       }
     }

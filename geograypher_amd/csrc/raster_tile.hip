@@ -252,14 +252,12 @@ __device__ __forceinline__ void micro_item(unsigned long long *keys, const int4 
   const int X2 = __builtin_amdgcn_sbfe(ea.z, 0, 16), Y2 = ea.z >> 16;
   const float iz0 = __int_as_float(ea.w), A = __int_as_float(eb.x), B = __int_as_float(eb.y);
   const uint32_t key = (uint32_t)eb.z;
-  const int box = eb.w;
-  const int xc0 = (box & 63) - TW / 2, last_col = (box >> 6) & 3;          // centred first column; columns - 1
-  const int yc0 = ((box >> 8) & 63) - TH / 2;                              // centred first row
-  const int nrows = valid ? min((box >> 14) & 7, 4) : 0;
+  const MicroBox box = unpack_micro_box(eb.w);
+  const int xc0 = box.col0 - TW / 2, last_col = box.dcol;                  // centred first column; columns - 1
+  const int yc0 = box.row0 - TH / 2;                                       // centred first row
+  const int nrows = valid ? min(box.rows, 4) : 0;
   const int dx0 = X1 - X0, dy0 = Y1 - Y0, dx1 = X2 - X1, dy1 = Y2 - Y1, dx2 = X0 - X2, dy2 = Y0 - Y2;
-  const int t0 = ((dy0 < 0) || (dy0 == 0 && dx0 < 0)) ? 0 : -1;           // R3 tie rule as a bias (left and bottom edges own)
-  const int t1 = ((dy1 < 0) || (dy1 == 0 && dx1 < 0)) ? 0 : -1;
-  const int t2 = ((dy2 < 0) || (dy2 == 0 && dx2 < 0)) ? 0 : -1;
+  const int t0 = tie_bias(dx0, dy0), t1 = tie_bias(dx1, dy1), t2 = tie_bias(dx2, dy2);
   const int Px = xc0 * 256, Py = yc0 * 256;                                // the box's first pixel centre, same frame as the vertices
   int r0 = __mul24(dx0, Py - Y0) - __mul24(dy0, Px - X0) + t0;             // edge values at that pixel
   int r1 = __mul24(dx1, Py - Y1) - __mul24(dy1, Px - X1) + t1;
@@ -618,10 +616,10 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
   const int64_t plane = (int64_t)slot * P;
   const int tx = tile % a.TX, ty = tile / a.TX;
   const int px0 = tx << TWL, py0 = ty << THL;
-  constexpr int EL = SHORT ? 40 : 48;  // 16-byte pieces of a 64-entry chunk per wave (4 waves): 40 or 48 bytes per entry
+  constexpr int EL = SHORT ? GR_ENT40_BYTES : GR_ENT_BYTES;  // 16-byte pieces of a 64-entry chunk per wave (4 waves): the bytes of an entry
   // the tile's list: the slot's entry memory is laid out for 48-byte entries; the short form packs chunks of 64 40-byte
   // entries at the front of the tile's segment (tile * cap_tile is a multiple of 64 whenever the short form is chosen)
-  const int4 *comp = SHORT ? reinterpret_cast<const int4 *>(reinterpret_cast<const char *>(a.comp + slot * a.ent_cap * GR_ENT_Q) + beg * 40)
+  const int4 *comp = SHORT ? reinterpret_cast<const int4 *>(reinterpret_cast<const char *>(a.comp + slot * a.ent_cap * GR_ENT_Q) + beg * GR_ENT40_BYTES)
                            : a.comp + (slot * a.ent_cap + beg) * GR_ENT_Q;
   const uint8_t *nr8 = a.nrow8 + slot * a.ent_cap + beg;
 
@@ -631,7 +629,7 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
   // not walk such a view, and the ids of this pass are repeated after the status call
   if (!(SHORT && MICRO)) cntm = 0u;
   if (SHORT && MICRO) {   // both lists inside the segment
-    cntm = min(cntm, (uint32_t)a.cap_tile * 5u / 4u);
+    cntm = min(cntm, micro_cap((uint32_t)a.cap_tile));
     cnt = min(cnt, (uint32_t)a.cap_tile);
   }
   if (!FUSE && cnt == 0 && cntm == 0) {  // empty tile (a view that overhangs the mesh): background, without the LDS round trip
@@ -716,13 +714,13 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
   }
   if (SHORT && MICRO && cntm > 0) {
     // micro records: every wave reads ITS chunks of 64 straight from the segment (no staging, no barrier), one record per lane.
-    // Record k of the list: the 32 bytes that end 32 k bytes before the end of the tile's segment -- a wave's chunk is 2 KiB of
-    // consecutive memory.
-    const char *seg_end = reinterpret_cast<const char *>(comp) + (size_t)a.cap_tile * 40;
+    // Record k of the list: the GR_MICRO_BYTES that end k records before the end of the tile's segment -- a wave's chunk is 2 KiB
+    // of consecutive memory.
+    const char *seg_end = reinterpret_cast<const char *>(comp) + (size_t)a.cap_tile * GR_ENT40_BYTES;
 #pragma unroll 1
     for (uint32_t c = (uint32_t)wv; c * 64u < cntm; c += NW) {
       const uint32_t k = c * 64u + (uint32_t)lane;
-      const int4 *rec = reinterpret_cast<const int4 *>(seg_end - 32u * (min(k, cntm - 1u) + 1u));
+      const int4 *rec = reinterpret_cast<const int4 *>(seg_end - (uint32_t)GR_MICRO_BYTES * (min(k, cntm - 1u) + 1u));
       const int4 ea = rec[0], eb = rec[1];
       micro_item<TWL, TH, PAD>(keys, ea, eb, k < cntm);
     }
@@ -811,12 +809,12 @@ __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile(BinArgs a, Rast
   const bool spec = KT == 1 && a.cap_tile >= 64;
   const int tile0 = KT * (int)blockIdx.x;
   const int n_tiles = min(KT, a.T - tile0);
-  constexpr int EL = SHORT ? 40 : 48;
+  constexpr int EL = SHORT ? GR_ENT40_BYTES : GR_ENT_BYTES;
   const uint32_t q = wv * EL + lane;  // this thread's 16-byte piece of a 3 KiB (2.5 KiB) chunk (lanes 0 .. 47 (39) of every wave)
   // 16-byte pieces of the view's entry memory from entry `first` on, and the number of pieces `n` entries take
   auto pieces = [&](int64_t first) {
     const v4i *base = reinterpret_cast<const v4i *>(a.comp + (int64_t)slot * a.ent_cap * GR_ENT_Q);
-    return SHORT ? reinterpret_cast<const v4i *>(reinterpret_cast<const char *>(base) + first * 40) : base + first * GR_ENT_Q;
+    return SHORT ? reinterpret_cast<const v4i *>(reinterpret_cast<const char *>(base) + first * GR_ENT40_BYTES) : base + first * GR_ENT_Q;
   };
   auto needed = [](uint32_t q, uint32_t n) { return SHORT ? short_piece_needed(q, min(n, 64u)) : q < n * GR_ENT_Q; };
   uint32_t nr0 = 0, nr1 = 0, nr2 = 0, nr3 = 0;
@@ -942,7 +940,7 @@ __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile_roll(BinArgs a,
 #endif
   const int tile0 = KTL * (int)blockIdx.x;
   const int n_tiles = min(KTL, a.T - tile0);
-  constexpr int EL = SHORT ? 40 : 48;
+  constexpr int EL = SHORT ? GR_ENT40_BYTES : GR_ENT_BYTES;
   const uint32_t q = wv * EL + lane;
   const v4i *base = reinterpret_cast<const v4i *>(a.comp + (int64_t)slot * a.ent_cap * GR_ENT_Q);
   auto needed = [](uint32_t qq, uint32_t n) { return SHORT ? short_piece_needed(qq, min(n, 64u)) : qq < n * GR_ENT_Q; };
@@ -966,7 +964,7 @@ __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile_roll(BinArgs a,
     // the loaded register before the request is waited for: a byte load is followed by its zero extension at once, a register
     // that is zeroed and then loaded under a mask by a wait for every store in flight -- each a full wait at the tile's start.
     n = *reinterpret_cast<const u32_unaligned *>(a.nrow8 + sbase + beg + lane);
-    const char *seg = reinterpret_cast<const char *>(base) + beg * (SHORT ? 40 : 48);
+    const char *seg = reinterpret_cast<const char *>(base) + beg * (SHORT ? GR_ENT40_BYTES : GR_ENT_BYTES);
     if ((lane < EL) & needed(q, cnt)) e = *reinterpret_cast<const v4i *>(seg + (q << 4));
   };
   const int64_t beg0 = (int64_t)tile0 * a.cap_tile;

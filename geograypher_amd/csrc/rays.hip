@@ -6,6 +6,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "gr_internal.hpp"
+#include "dev_common.hpp"
 
 using namespace grimpl;
 
@@ -156,12 +157,9 @@ __global__ void __launch_bounds__(GR_RAY_TILE) k_ray_pairs(const RayRec *__restr
       const unsigned long long mask = __ballot(hit);
       if (mask == 0) continue;
       if (FILL) {
-        const int first = __ffsll((long long)mask) - 1;
-        unsigned long long base = 0;
-        if (lane == first) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
-        base = __shfl(base, first);
+        const unsigned long long base = wave_append(mask, counter, lane);
         if (hit) {
-          const unsigned long long pos = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
+          const unsigned long long pos = base + (unsigned long long)wave_rank(mask, lane);
           if (pos < (unsigned long long)cap) {
             keys[pos] = ((unsigned long long)i << 32) | (unsigned long long)j;
             dist[pos] = d;
