@@ -63,6 +63,13 @@ GR_DBG_RAY_GRID_7 = 2048
 GR_CAUSE_LIST_OUTGREW = 1
 GR_CAUSE_SHORT_MISS = 2
 GR_CAUSE_LISTS_MET = 4
+# mode of polygon_class_weights, words of its statistics block
+GR_POLY_OVERLAY = 0
+GR_POLY_WITHIN = 1
+GR_POLY_STAT_TESTED = 0
+GR_POLY_STAT_CONTRIBUTING = 1
+GR_POLY_STAT_LARGEST_RING = 2
+GR_POLY_STAT_WORDS = 4
 
 
 class StageTimes(ctypes.Structure):
@@ -139,6 +146,7 @@ _SIGNATURES = {
     "gr_finalize_sums_f64": [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
     "gr_argmax_nonzero": [_vp, _vp, _i32, _i64, _i32, _vp, _vp],
     "gr_argmax_nonzero_f64": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "gr_polygon_class_weights": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -678,6 +686,38 @@ class HipRaster:
         self._call("gr_rays_clip", o_t.data_ptr(), d_t.data_ptr(), n, p_t.data_ptr(), int(p_t.shape[0]), f_t.data_ptr(),
                    int(f_t.shape[0]), hit.data_ptr(), t.data_ptr(), pts.data_ptr(), self._stream())
         return hit.to(torch.bool), t, pts
+
+    # -- label_polygons: weighted face area per (polygon, class) ---------------------------------------------------
+    def polygon_class_weights(self, tri, face_class, face_weight, ring_vertices, ring_offsets, ring_polygon, ring_is_hole,
+                              polygon_boxes, n_classes: int, within: bool = True):
+        """gr_polygon_class_weights (DESIGN.md "Polygon labels"): tri (F, 6) int64 snapped face corners, face_class (F,) int
+        (< 0: skip), face_weight (F,) float64 -- numpy or device tensors --, and the snapped ring table of
+        `PlanarPolygons.snapped` -> (weights (P, n_classes) float64 tensor, stats (GR_POLY_STAT_WORDS,) int64 tensor: pairs
+        tested, pairs contributing, largest ring).  `within`: exact containment (sjoin), else clipped overlay.  Only enqueues."""
+        torch = _torch()
+        tri_t = self._dev(tri, torch.int64)
+        cls_t = self._dev(face_class, torch.int32)
+        w_t = self._dev(face_weight, torch.float64)
+        rv_t = self._dev(ring_vertices, torch.int64)
+        off_t = self._dev(ring_offsets, torch.int64)
+        rp_t = self._dev(ring_polygon, torch.int32)
+        rh_t = self._dev(ring_is_hole, torch.int32)
+        box_t = self._dev(polygon_boxes, torch.int64)
+        F, R, P, C = int(cls_t.shape[0]), int(rp_t.shape[0]), int(box_t.shape[0]), int(n_classes)
+        if tri_t.ndim != 2 or tuple(tri_t.shape) != (F, 6) or tuple(w_t.shape) != (F,):
+            raise ValueError(f"faces must be (F, 6) corners, (F,) classes and (F,) weights, got {tuple(tri_t.shape)}, "
+                             f"{tuple(cls_t.shape)} and {tuple(w_t.shape)}")
+        if rv_t.ndim != 2 or rv_t.shape[1] != 2 or tuple(off_t.shape) != (R + 1,) or tuple(rh_t.shape) != (R,) or \
+                box_t.ndim != 2 or box_t.shape[1] != 4:
+            raise ValueError(f"ring table must be (N, 2) vertices, (R + 1,) offsets, (R,) polygons, (R,) hole flags and (P, 4) "
+                             f"boxes, got {tuple(rv_t.shape)}, {tuple(off_t.shape)}, {tuple(rp_t.shape)}, {tuple(rh_t.shape)} and "
+                             f"{tuple(box_t.shape)}")
+        weights = torch.empty((P, C), dtype=torch.float64, device=self.device)
+        stats = torch.empty((GR_POLY_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        self._call("gr_polygon_class_weights", tri_t.data_ptr(), cls_t.data_ptr(), w_t.data_ptr(), F, rv_t.data_ptr(),
+                   int(rv_t.shape[0]), off_t.data_ptr(), rp_t.data_ptr(), rh_t.data_ptr(), R, box_t.data_ptr(), P,
+                   GR_POLY_WITHIN if within else GR_POLY_OVERLAY, C, weights.data_ptr(), stats.data_ptr(), self._stream())
+        return weights, stats
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):

@@ -10,6 +10,7 @@
 //   resize.hip       photo down-scale of get_image (anti-aliased resize)
 //   rays.hip         multiview detections: ray-pair graph (k_ray_prep, k_ray_pairs + radix sort), ray / boundary clip; no mesh needed
 //   equirect.hip     360-degree photos: perspective views resampled from an equirectangular image (k_equirect_view)
+//   polygons.hip     label_polygons: weighted face area per (polygon, class), exact containment or clipped overlay (k_polygon_weights); no mesh needed
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 

@@ -1,0 +1,269 @@
+// geograypher_amd/csrc/polygons.hip -- label_polygons on the device: the weighted area every mesh face contributes to every
+// polygon, summed per (polygon, class) (gr_polygon_class_weights; the rule-set is DESIGN.md "Polygon labels").  Needs no
+// uploaded mesh: the caller hands over the faces as snapped integer triangles.
+//
+// Shape: face-major, one face per lane.  The ring table is walked WAVE-UNIFORMLY: ring r, its polygon, the polygon's box and
+// every ring vertex have the same address in all lanes (scalar loads), so the only divergence is the execution mask of the lanes
+// whose box misses the polygon's -- and a wave none of whose faces meets the box skips the ring after one ballot.  A face's
+// state across the rings of one polygon lives in registers; when the polygon changes the wave sums its lanes per class
+// (butterfly, fixed order) and issues ONE f64 atomic per class present: a wave's faces share the polygon, so per-lane
+// atomics would all land in one row of `weights`.
+//   GR_POLY_WITHIN   exact: 128-bit integer orientation signs on the snapped coordinates decide "closed triangle inside the closed
+//                    polygon region" as  no ring edge meets the triangle's open interior  AND  3 x centroid is inside (even-odd)
+//   GR_POLY_OVERLAY  f64: the ring streamed vertex by vertex through the triangle's three half-planes (Sutherland-Hodgman with
+//                    O(1) state per stage, no per-lane vertex arrays) into a shoelace sum, in coordinates relative to the
+//                    triangle's first vertex
+#include "gr_internal.hpp"
+
+using namespace grimpl;
+
+namespace {
+
+typedef __int128 i128;
+
+struct PolyArgs {   // the scalars of a call; the arrays are kernel parameters of their own, so that they can be __restrict__
+  int64_t F;
+  int64_t n_rv;
+  int R, P, C, mode;
+};
+
+__device__ __forceinline__ i128 orient(int64_t ax, int64_t ay, int64_t bx, int64_t by, int64_t cx, int64_t cy) {
+  return (i128)(bx - ax) * (i128)(cy - ay) - (i128)(by - ay) * (i128)(cx - ax);   // |coordinates| <= 3 * 2^40: |products| < 2^87
+}
+__device__ __forceinline__ int sgn(i128 v) { return v > 0 ? 1 : (v < 0 ? -1 : 0); }
+
+// v >= 0 as a double: exact below 2^64 when v has at most 53 significant bits, within an ulp above
+__device__ __forceinline__ double to_double(i128 v) {
+  const uint64_t hi = (uint64_t)(v >> 64), lo = (uint64_t)v;
+  return hi == 0 ? (double)lo : (double)hi * 18446744073709551616.0 + (double)lo;
+}
+
+struct Tri {   // counter-clockwise
+  int64_t x[3], y[3];
+};
+
+// Does the closed segment a b meet the OPEN interior of t?  Signs only.  The line through a, b passes through the interior iff
+// it has vertices strictly on both sides; then one vertex p0 is alone on its side (the others weakly opposite), the line's
+// chord of the triangle ends on p0's two edges, and a point of the line is inside the open chord iff it is strictly inside both
+// of those edges' half-planes (f1, f2 > 0).  A point outside the open chord is behind one end (f1 <= 0) or the other (f2 <= 0):
+// the segment meets the chord iff an end point is inside it or the two end points are behind different ends.
+__device__ __forceinline__ bool edge_meets_interior(const Tri &t, int64_t ax, int64_t ay, int64_t bx, int64_t by) {
+  const int s0 = sgn(orient(ax, ay, bx, by, t.x[0], t.y[0]));
+  const int s1 = sgn(orient(ax, ay, bx, by, t.x[1], t.y[1]));
+  const int s2 = sgn(orient(ax, ay, bx, by, t.x[2], t.y[2]));
+  const int npos = (s0 > 0) + (s1 > 0) + (s2 > 0), nneg = (s0 < 0) + (s1 < 0) + (s2 < 0);
+  if (npos == 0 || nneg == 0) return false;
+  const int want = npos == 1 ? 1 : -1;
+  const int k = s0 == want ? 0 : (s1 == want ? 1 : 2);
+  int64_t p0x = t.x[0], p0y = t.y[0], p1x = t.x[1], p1y = t.y[1], p2x = t.x[2], p2y = t.y[2];   // selects, not indexed registers
+  if (k == 1) { p0x = t.x[1]; p0y = t.y[1]; p1x = t.x[2]; p1y = t.y[2]; p2x = t.x[0]; p2y = t.y[0]; }
+  if (k == 2) { p0x = t.x[2]; p0y = t.y[2]; p1x = t.x[0]; p1y = t.y[0]; p2x = t.x[1]; p2y = t.y[1]; }
+  const int f1a = sgn(orient(p0x, p0y, p1x, p1y, ax, ay)), f2a = sgn(orient(p2x, p2y, p0x, p0y, ax, ay));
+  const int f1b = sgn(orient(p0x, p0y, p1x, p1y, bx, by)), f2b = sgn(orient(p2x, p2y, p0x, p0y, bx, by));
+  return (f1a > 0 && f2a > 0) || (f1b > 0 && f2b > 0) || (f1a <= 0 && f2b <= 0) || (f1b <= 0 && f2a <= 0);
+}
+
+// ---- overlay: streamed Sutherland-Hodgman.  Stage K clips against the half-plane left of the triangle's edge K; what it emits
+// is put into stage K + 1, stage 3 is the shoelace sum.  Every stage keeps its first and its previous point with their side
+// values, nothing else.  Operation order: side d = ex * (y - ay) - ey * (x - ax), inside iff d >= 0; crossing point
+// of s -> p: t = ds / (ds - dp), s + t * (p - s); shoelace term of u -> v: ux * vy - vx * uy.
+struct Clip {
+  double ax, ay, ex, ey;
+  double fx, fy, fd, px, py, pd;
+  bool has;
+};
+struct ClipState {
+  Clip k[3];
+  double ofx, ofy, opx, opy, sum;   // the output ring's first and previous point, the running shoelace sum
+  bool ohas;
+};
+
+template <int K> __device__ __forceinline__ void clip_put(ClipState &S, double x, double y);
+
+template <int K> __device__ __forceinline__ void clip_edge(ClipState &S, double sx, double sy, double sd, double x, double y, double d) {
+  const bool in = d >= 0.0, s_in = sd >= 0.0;
+  if (in != s_in) {
+    const double t = sd / (sd - d);
+    clip_put<K + 1>(S, sx + t * (x - sx), sy + t * (y - sy));
+  }
+  if (in) clip_put<K + 1>(S, x, y);
+}
+
+template <int K> __device__ __forceinline__ void clip_put(ClipState &S, double x, double y) {
+  if constexpr (K == 3) {
+    if (!S.ohas) { S.ofx = x; S.ofy = y; S.ohas = true; }
+    else S.sum += S.opx * y - x * S.opy;
+    S.opx = x; S.opy = y;
+  } else {
+    Clip &k = S.k[K];
+    const double d = k.ex * (y - k.ay) - k.ey * (x - k.ax);
+    if (!k.has) { k.fx = x; k.fy = y; k.fd = d; k.has = true; }
+    else clip_edge<K>(S, k.px, k.py, k.pd, x, y, d);
+    k.px = x; k.py = y; k.pd = d;
+  }
+}
+
+template <int K> __device__ __forceinline__ void clip_close(ClipState &S) {   // the closing edge previous -> first of every stage, in order
+  if constexpr (K == 3) {
+    if (S.ohas) S.sum += S.opx * S.ofy - S.ofx * S.opy;
+  } else {
+    Clip &k = S.k[K];
+    if (k.has) clip_edge<K>(S, k.px, k.py, k.pd, k.fx, k.fy, k.fd);
+    clip_close<K + 1>(S);
+  }
+}
+
+__device__ __forceinline__ double wave_sum(double v) {   // butterfly: every lane ends with the same sum, in a fixed order
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// Add `val` of the lanes with `has` into row[class], one atomic per class present in the wave.  Called by all 64 lanes.
+__device__ __forceinline__ void flush_wave(double val, bool has, int cls, double *row, int lane) {
+  unsigned long long m = __ballot(has);
+  while (m) {
+    const int leader = __ffsll((long long)m) - 1;
+    const int cc = __shfl(cls, leader);
+    const bool mine = has && cls == cc;
+    const double v = wave_sum(mine ? val : 0.0);
+    if (lane == leader) atomicAdd(row + cc, v);
+    m &= ~__ballot(mine);
+  }
+}
+
+// tri [F][6] snapped x0 y0 x1 y1 x2 y2; cls [F] (< 0: skip); wgt [F]; rv [n_rv][2] ring vertices; roff [R + 1]; rpoly [R]
+// non-decreasing; rhole [R]; pbox [P][4] xmin ymin xmax ymax; weights [P][C]; stats [GR_POLY_STAT_WORDS]
+__global__ __launch_bounds__(256) void k_polygon_weights(const int64_t *__restrict__ tri, const int32_t *__restrict__ cls_in,
+                                                         const double *__restrict__ wgt, const int64_t *__restrict__ rv,
+                                                         const int64_t *__restrict__ roff, const int32_t *__restrict__ rpoly,
+                                                         const int32_t *__restrict__ rhole, const int64_t *__restrict__ pbox,
+                                                         double *__restrict__ weights, unsigned long long *__restrict__ stats,
+                                                         PolyArgs a) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  Tri t = {{0, 0, 0}, {0, 0, 0}};
+  int cls = -1;
+  double w = 0.0, area_t = 0.0;
+  bool live = f < a.F;
+  if (live) { cls = cls_in[f]; live = cls >= 0 && cls < a.C; }
+  if (live) {
+    const int64_t *p = tri + f * 6;
+    t.x[0] = p[0]; t.y[0] = p[1]; t.x[1] = p[2]; t.y[1] = p[3]; t.x[2] = p[4]; t.y[2] = p[5];
+    i128 o = orient(t.x[0], t.y[0], t.x[1], t.y[1], t.x[2], t.y[2]);
+    if (o < 0) { o = -o; const int64_t sx = t.x[1], sy = t.y[1]; t.x[1] = t.x[2]; t.y[1] = t.y[2]; t.x[2] = sx; t.y[2] = sy; }
+    live = o != 0;                       // a face the snap collapsed contributes nothing
+    area_t = to_double(o) / 2e12;        // square metres: twice the area in 1e-12 m^2, one conversion, one division
+    w = wgt[f];
+  }
+  // a face that takes no part pairs with no polygon (`live` gates in_poly below); its box is a placeholder
+  const int64_t xlo = live ? min(t.x[0], min(t.x[1], t.x[2])) : 1, xhi = live ? max(t.x[0], max(t.x[1], t.x[2])) : 0;
+  const int64_t ylo = live ? min(t.y[0], min(t.y[1], t.y[2])) : 1, yhi = live ? max(t.y[0], max(t.y[1], t.y[2])) : 0;
+  const int64_t c3x = t.x[0] + t.x[1] + t.x[2], c3y = t.y[0] + t.y[1] + t.y[2];
+  // overlay frame: metres relative to vertex 0 (the integer differences are exact)
+  const double e1x = (double)(t.x[1] - t.x[0]) * 1e-6, e1y = (double)(t.y[1] - t.y[0]) * 1e-6;
+  const double e2x = (double)(t.x[2] - t.x[0]) * 1e-6, e2y = (double)(t.y[2] - t.y[0]) * 1e-6;
+
+  int cur = -1;              // polygon of the rings being walked (wave-uniform)
+  bool in_poly = false;      // this lane's box overlaps its box
+  bool meets = false;        // within: a ring edge met the open interior
+  int parity = 0;            // within: crossings right of the centroid
+  double acc = 0.0;          // overlay: shoelace sums of the polygon's rings, holes negative
+  unsigned long long tested = 0, contributing = 0, largest = 0;
+
+  auto flush = [&]() {
+    if (cur < 0 || !__ballot(in_poly)) return;
+    double val;
+    bool has;
+    if (a.mode == GR_POLY_WITHIN) { has = in_poly && !meets && (parity & 1); val = area_t * w; }
+    else { const double area = 0.5 * acc; has = in_poly && area > 0.0; val = area * w; }
+    contributing += has ? 1 : 0;
+    flush_wave(val, has, cls, weights + (int64_t)cur * a.C, lane);
+  };
+
+  for (int r = 0; r < a.R; ++r) {
+    const int p = rpoly[r];
+    if (p != cur) {
+      flush();
+      cur = (p >= 0 && p < a.P) ? p : -1;
+      meets = false; parity = 0; acc = 0.0; in_poly = false;
+      if (cur >= 0) {
+        const int64_t *b = pbox + (int64_t)cur * 4;
+        in_poly = live && xlo <= b[2] && xhi >= b[0] && ylo <= b[3] && yhi >= b[1];
+        tested += in_poly ? 1 : 0;
+      }
+    }
+    int64_t i0 = roff[r], i1 = roff[r + 1];
+    i0 = min(max(i0, (int64_t)0), a.n_rv); i1 = min(max(i1, i0), a.n_rv);   // a bad offset table reads nothing outside the vertices
+    const int64_t n = i1 - i0;
+    largest = max(largest, (unsigned long long)n);
+    if (cur < 0 || n < 3 || !__ballot(in_poly)) continue;
+    const int64_t *v = rv + i0 * 2;
+    if (!in_poly) continue;
+    if (a.mode == GR_POLY_WITHIN) {
+      int64_t ax = v[2 * (n - 1)], ay = v[2 * (n - 1) + 1];
+      for (int64_t i = 0; i < n; ++i) {
+        const int64_t bx = v[2 * i], by = v[2 * i + 1];
+        const int64_t a3y = 3 * ay, b3y = 3 * by;
+        if ((a3y > c3y) != (b3y > c3y)) {   // even-odd, half-open in y; the centroid is on no edge unless `meets`
+          const i128 o = orient(3 * ax, a3y, 3 * bx, b3y, c3x, c3y);
+          parity ^= ((o > 0) == (b3y > a3y)) ? 1 : 0;
+        }
+        // the edge's box against the face's: an edge that stays at or beyond a side of the box cannot reach the open interior
+        if (!meets && max(ax, bx) > xlo && min(ax, bx) < xhi && max(ay, by) > ylo && min(ay, by) < yhi)
+          meets = edge_meets_interior(t, ax, ay, bx, by);
+        ax = bx; ay = by;
+      }
+    } else {
+      ClipState S;
+      S.k[0] = {0.0, 0.0, e1x, e1y, 0, 0, 0, 0, 0, 0, false};
+      S.k[1] = {e1x, e1y, e2x - e1x, e2y - e1y, 0, 0, 0, 0, 0, 0, false};
+      S.k[2] = {e2x, e2y, 0.0 - e2x, 0.0 - e2y, 0, 0, 0, 0, 0, 0, false};
+      S.ofx = S.ofy = S.opx = S.opy = 0.0; S.sum = 0.0; S.ohas = false;
+      for (int64_t i = 0; i < n; ++i)
+        clip_put<0>(S, (double)(v[2 * i] - t.x[0]) * 1e-6, (double)(v[2 * i + 1] - t.y[0]) * 1e-6);
+      clip_close<0>(S);
+      acc = rhole[r] ? acc - S.sum : acc + S.sum;
+    }
+  }
+  flush();
+
+  // statistics: one atomic per wave and word
+  const double ts = wave_sum((double)tested), cs = wave_sum((double)contributing);   // < 2^53: exact
+  if (lane == 0) {
+    if (ts > 0.0) atomicAdd(&stats[GR_POLY_STAT_TESTED], (unsigned long long)ts);
+    if (cs > 0.0) atomicAdd(&stats[GR_POLY_STAT_CONTRIBUTING], (unsigned long long)cs);
+    if (f == 0) atomicMax(&stats[GR_POLY_STAT_LARGEST_RING], largest);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int gr_polygon_class_weights(gr_ctx *c, const int64_t *tri, const int32_t *face_class, const double *face_weight, int64_t F,
+                             const int64_t *ring_vertices, int64_t n_ring_vertices, const int64_t *ring_offsets,
+                             const int32_t *ring_polygon, const int32_t *ring_is_hole, int64_t R, const int64_t *polygon_boxes,
+                             int64_t P, int mode, int C, double *weights, uint64_t *stats, void *stream) {
+  if (!c) return GR_EINVAL;
+  if (F < 0 || R < 0 || P < 0 || C < 0 || n_ring_vertices < 0 || F > 0x7FFFFFFFll * 256 || R > 0x7FFFFFFF || P > 0x7FFFFFFF)
+    return fail(c, GR_EINVAL, "bad polygon-weights shape F=%lld R=%lld P=%lld C=%d", (long long)F, (long long)R, (long long)P, C);
+  if (mode != GR_POLY_WITHIN && mode != GR_POLY_OVERLAY)
+    return fail(c, GR_EINVAL, "polygon-weights mode %d is neither GR_POLY_WITHIN nor GR_POLY_OVERLAY", mode);
+  if (!stats || (P > 0 && C > 0 && !weights)) return fail(c, GR_EINVAL, "null polygon-weights outputs");
+  if ((F > 0 && (!tri || !face_class || !face_weight)) ||
+      (R > 0 && (!ring_offsets || !ring_polygon || !ring_is_hole || !polygon_boxes || (n_ring_vertices > 0 && !ring_vertices))))
+    return fail(c, GR_EINVAL, "null polygon-weights arrays");
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
+  if (P > 0 && C > 0) GR_HIP(c, hipMemsetAsync(weights, 0, sizeof(double) * (size_t)P * (size_t)C, s));
+  GR_HIP(c, hipMemsetAsync(stats, 0, sizeof(uint64_t) * GR_POLY_STAT_WORDS, s));
+  if (F == 0 || R == 0 || P == 0 || C == 0) return GR_OK;
+  PolyArgs a;
+  a.F = F; a.n_rv = n_ring_vertices; a.R = (int)R; a.P = (int)P; a.C = C; a.mode = mode;
+  hipLaunchKernelGGL(k_polygon_weights, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, tri, face_class, face_weight, ring_vertices,
+                     ring_offsets, ring_polygon, ring_is_hole, polygon_boxes, weights, (unsigned long long *)stats, a);
+  GR_HIP(c, hipGetLastError());
+  return GR_OK;
+}
+
+}  // extern "C"

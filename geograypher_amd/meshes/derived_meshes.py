@@ -53,6 +53,17 @@ class TexturedPhotogrammetryMeshChunked(TexturedPhotogrammetryMesh):
                                                   aggregate_img_scale=aggregate_img_scale, **kwargs)
 
 
+    def label_polygons(self, face_labels, polygons, face_weighting=None, sjoin_overlay: bool = True,
+                       return_class_labels: bool = True, unknown_class_label: str = "unknown",
+                       buffer_dist_meters: float = 2.0, n_polygons_per_cluster: int = 1000, *, points_in_polygon_CRS=None):
+        """reference: derived_meshes.py:319-411, which clusters the polygons (KMeans) to keep gpd.overlay tractable; here every
+        face meets every polygon's box in one kernel, so `n_polygons_per_cluster` is accepted and ignored."""
+        self.logger.info(f"label_polygons: n_polygons_per_cluster={n_polygons_per_cluster} is ignored -- one kernel meets every "
+                         "face with every polygon's box, no polygon clustering")
+        return super().label_polygons(face_labels, polygons, face_weighting=face_weighting, sjoin_overlay=sjoin_overlay,
+                                      return_class_labels=return_class_labels, unknown_class_label=unknown_class_label,
+                                      buffer_dist_meters=buffer_dist_meters, points_in_polygon_CRS=points_in_polygon_CRS)
+
 class TexturedPhotogrammetryMeshIndexPredictions(TexturedPhotogrammetryMesh):
     def aggregate_projected_images(
         self,

@@ -995,6 +995,144 @@ class TexturedPhotogrammetryMesh:
     # the north star's name for the same method
     aggregate_viewpoints = aggregate_projected_images
 
+    # -- label_polygons (DESIGN.md "Polygon labels"; reference: meshes.py:1141-1306) ----------------------------------------
+    @staticmethod
+    def _squeezed_1d(values):
+        """np.squeeze + the reference's one-dimensional check (meshes.py:1181-1191), for arrays and device tensors."""
+        values = values.squeeze() if hasattr(values, "detach") else np.squeeze(np.asarray(values))
+        if values.ndim != 1:
+            raise ValueError(f"Faces labels must be one-dimensional, but is {values.ndim}")
+        return values
+
+    def _face_classes(self, face_labels):
+        """(class per face: int32 array or tensor, -1 = skip; n_classes).  Non-finite labels are skipped; a finite label must
+        be a whole number >= 0."""
+        n_faces = self.faces.shape[0]
+        if face_labels.shape[0] != n_faces:
+            raise ValueError(f"{face_labels.shape[0]} face labels for a mesh of {n_faces} faces")
+        if hasattr(face_labels, "detach"):
+            torch = _torch()
+            labels = face_labels.to(torch.float64)
+            finite = torch.isfinite(labels)
+            kept = labels[finite]
+            bad = bool(((kept != torch.floor(kept)) | (kept < 0)).any()) if kept.numel() else False
+            top = float(kept.max()) if kept.numel() else -1.0
+            classes = torch.where(finite, labels, torch.full_like(labels, -1.0))
+            to_int = lambda c: c.to(torch.int32)
+        else:
+            labels = np.asarray(face_labels, dtype=np.float64)
+            finite = np.isfinite(labels)
+            kept = labels[finite]
+            bad = bool(np.any((kept != np.floor(kept)) | (kept < 0)))
+            top = float(kept.max()) if kept.size else -1.0
+            classes = np.where(finite, labels, -1.0)
+            to_int = lambda c: c.astype(np.int32)
+        if bad:
+            raise ValueError("finite face labels must be whole numbers >= 0 (class ids)")
+        if top >= 2 ** 31 - 1:
+            raise ValueError(f"class id {top:.0f} does not fit the int32 class table")
+        return to_int(classes), int(top) + 1
+
+    def label_polygon_weights(self, face_labels, polygons, face_weighting=None, sjoin_overlay: bool = True,
+                              return_class_labels: bool = True, unknown_class_label: str = "unknown",
+                              buffer_dist_meters: float = 2.0, *, points_in_polygon_CRS=None) -> np.ndarray:
+        """The (n_polygons, n_classes) float64 matrix behind `label_polygons`: entry (p, c) is the weighted area the faces of
+        class c contribute to polygon p (same arguments; `return_class_labels`, `unknown_class_label` and `buffer_dist_meters`
+        play no part).  n_classes is the largest finite label + 1.  The pair statistics of the call are left in
+        `self.last_polygon_stats` (pairs_tested, pairs_contributing, largest_ring)."""
+        from geograypher_amd.utils.geometric import SNAP_LIMIT, PlanarPolygons, snap_to_grid
+
+        face_labels = self._squeezed_1d(face_labels)
+        if face_weighting is not None:
+            face_weighting = self._squeezed_1d(face_weighting)
+        if points_in_polygon_CRS is None:
+            raise NotImplementedError(
+                "label_polygons needs points_in_polygon_CRS: the mesh vertices (V, 3) in the polygons' planar CRS (CRS "
+                "reprojection needs pyproj and is outside the projection path)")
+        if isinstance(polygons, (str, Path)) or hasattr(polygons, "geometry"):
+            raise NotImplementedError(
+                "polygon files and GeoDataFrames need geopandas, which is outside the projection path: pass a PlanarPolygons "
+                "(geograypher_amd.utils.geometric)")
+        if not isinstance(polygons, PlanarPolygons):
+            polygons = PlanarPolygons.from_sequence(polygons)
+        verts = np.asarray(points_in_polygon_CRS, dtype=np.float64)
+        if verts.shape != (self.points.shape[0], 3):
+            raise ValueError(f"points_in_polygon_CRS must be ({self.points.shape[0]}, 3), got {verts.shape}")
+        if face_weighting is not None and face_weighting.shape[0] != self.faces.shape[0]:
+            raise ValueError(f"{face_weighting.shape[0]} face weights for a mesh of {self.faces.shape[0]} faces")
+        classes, n_classes = self._face_classes(face_labels)
+
+        # rule 4: area3D / area2D of the unsnapped corners, in the operation order of utils/numeric.py:305-327
+        A, B, C = (verts[self.faces[:, k]] for k in range(3))
+        u, v = B - A, C - A
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            u0v1_min_u1v0 = u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]
+            c0 = u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1]
+            c1 = u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2]
+            area = 1 / 2 * np.sqrt(c0 * c0 + c1 * c1 + u0v1_min_u1v0 * u0v1_min_u1v0)
+            ratio = area / (np.abs(u0v1_min_u1v0) / 2)
+        if face_weighting is None:
+            weight = ratio
+        elif hasattr(face_weighting, "detach"):
+            torch = _torch()
+            fw = face_weighting.to(torch.float64)
+            weight = torch.as_tensor(ratio).to(fw.device) * fw
+        else:
+            weight = ratio * np.asarray(face_weighting, dtype=np.float64)
+
+        # rule 3: the 1e-6 m grid behind a common integer origin
+        vq = snap_to_grid(verts[:, :2])
+        lo, hi = (vq.min(axis=0), vq.max(axis=0)) if len(vq) else (np.zeros(2, np.int64), np.zeros(2, np.int64))
+        ring_bounds = polygons.bounds_snapped()
+        if ring_bounds is not None:
+            lo, hi = np.minimum(lo, ring_bounds[0]), np.maximum(hi, ring_bounds[1])
+        origin = lo + (hi - lo) // 2
+        vq = vq - origin
+        if len(vq) and np.abs(vq).max() > SNAP_LIMIT:
+            raise ValueError("a mesh vertex lies more than 2^40 grid steps (1 099 512 m) from the common origin of mesh and "
+                             "polygons")
+        table = polygons.snapped(origin)
+        tri = vq[self.faces].reshape(-1, 6)
+
+        weights, stats = self.backend.polygon_class_weights(tri, classes, weight, *table, n_classes, within=bool(sjoin_overlay))
+        weights = _to_host(weights) if hasattr(weights, "detach") else np.asarray(weights)
+        stats = _to_host(stats) if hasattr(stats, "detach") else np.asarray(stats)
+        self.last_polygon_stats = {"pairs_tested": int(stats[0]), "pairs_contributing": int(stats[1]),
+                                   "largest_ring": int(stats[2])}
+        return np.array(weights, dtype=np.float64).reshape(len(polygons), n_classes)
+
+    def label_polygons(self, face_labels, polygons, face_weighting=None, sjoin_overlay: bool = True,
+                       return_class_labels: bool = True, unknown_class_label: str = "unknown",
+                       buffer_dist_meters: float = 2.0, *, points_in_polygon_CRS=None):
+        """Assign a class to polygons from labels per face (reference: meshes.py:1141-1306; rule-set: DESIGN.md "Polygon
+        labels").
+
+        face_labels: (n_faces,) class ids, NaN = no label; numpy or a device tensor (e.g. `backend.argmax_nonzero` of the
+        aggregated votes).  polygons: a `geograypher_amd.utils.geometric.PlanarPolygons`, or a sequence its `from_sequence`
+        takes; a file path or GeoDataFrame raises NotImplementedError (no geopandas here).  face_weighting: (n_faces,) factors
+        multiplied with each face's 3D / 2D area ratio.  sjoin_overlay: True counts the faces that lie entirely within a polygon
+        (decided exactly on the 1e-6 m grid), False the area of every face's intersection with it.  buffer_dist_meters: accepted
+        and unused (the reference's buffered ROI pre-filter is not reproduced).  points_in_polygon_CRS (required, keyword): the
+        mesh vertices (V, 3) in the polygons' planar CRS, x, y in metres, z up -- what the reference gets from
+        get_vertices_in_CRS.
+
+        Returns the (n_polygons,) list of the reference: the class with the largest weighted area as a float (the lowest class on
+        equality), NaN where nothing contributes; with `return_class_labels` and IDs_to_labels, the label strings, and
+        `unknown_class_label` for NaN."""
+        weights = self.label_polygon_weights(face_labels, polygons, face_weighting=face_weighting, sjoin_overlay=sjoin_overlay,
+                                             buffer_dist_meters=buffer_dist_meters, points_in_polygon_CRS=points_in_polygon_CRS)
+        predicted_class_IDs = np.full(weights.shape[0], np.nan)
+        if weights.shape[1] > 0:
+            best = np.argmax(weights, axis=1)   # the first maximum: groupby + idxmax over ascending class ids
+            top = weights[np.arange(weights.shape[0]), best]
+            has = top != 0
+            predicted_class_IDs[has] = best[has].astype(float)
+        predicted_class_IDs = predicted_class_IDs.tolist()
+        if return_class_labels and ((IDs_to_labels := self.get_IDs_to_labels()) is not None):
+            predicted_class_IDs = [(IDs_to_labels[int(pi)] if np.isfinite(pi) else unknown_class_label)
+                                   for pi in predicted_class_IDs]
+        return predicted_class_IDs
+
     # -- save_renders (SURVEY.md section 8, row f2) ----------------------------------------------------------------
     def save_IDs_to_labels(self, savepath: PATH_TYPE):
         """reference: meshes.py:1081-1108"""

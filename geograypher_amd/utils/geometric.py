@@ -1,4 +1,5 @@
-"""Geometric helpers of the multiview-detection workflow (reference: geograypher/utils/geometric.py:97-106, 144-254).
+"""Geometric helpers: the multiview-detection workflow (reference: geograypher/utils/geometric.py:97-106, 144-254) and the planar
+polygons of `label_polygons` (`PlanarPolygons`, the 1e-6 m grid).
 
 This package has no pyvista: a boundary surface is a `(points (V, 3) float, faces (F, 3) int)` pair, and the ray / surface
 intersection runs on the device (`HipRaster.clip_rays`, gr_rays_clip: brute force over a coarse covering mesh).
@@ -66,3 +67,130 @@ def clip_line_segments(boundaries, origins: np.ndarray, directions: np.ndarray,
     with np.errstate(invalid="ignore", divide="ignore"):
         new_directions = (pt1 - pt0) / np.linalg.norm(pt1 - pt0, axis=1, keepdims=True)
     return pt0, pt1, new_directions, np.asarray(image_indices)[keep]
+
+
+# -- label_polygons: planar polygons and the 1e-6 m grid (DESIGN.md "Polygon labels") ---------------------------------------------
+SNAP_GRID_METERS = 1e-6       # shapely.set_precision(..., 1e-6) of meshes.py:1222-1227
+SNAP_LIMIT = 1 << 40          # largest |snapped coordinate| behind the common origin: the device's 128-bit products stay exact
+
+
+def snap_to_grid(xy: np.ndarray) -> np.ndarray:
+    """Coordinates in metres -> int64 units of SNAP_GRID_METERS: np.rint(x / 1e-6)."""
+    q = np.rint(np.asarray(xy, dtype=np.float64) / SNAP_GRID_METERS)
+    if q.size and not np.all(np.abs(q) < 2.0 ** 62):
+        raise ValueError("coordinates are non-finite or too large to snap to the 1e-6 m grid")
+    return q.astype(np.int64)
+
+
+def _signed_area2_exact(q: np.ndarray) -> int:
+    """Twice the signed area of an integer ring, in Python integers (no overflow)."""
+    xs, ys = [int(v) for v in q[:, 0]], [int(v) for v in q[:, 1]]
+    return sum(xs[i - 1] * ys[i] - xs[i] * ys[i - 1] for i in range(len(xs)))
+
+
+class PlanarPolygons:
+    """Polygons in a planar CRS (x, y in metres), the `polygons` of `TexturedPhotogrammetryMesh.label_polygons` in place of the
+    reference's GeoDataFrame.
+
+    rings: list of (n, 2) float arrays, one closed ring each (a repeated closing vertex is dropped); ring_polygon[r]: the output
+    row ring r belongs to; ring_is_hole[r]: whether it is cut out of that row.  Several exterior rings on one row make a
+    multi-part polygon.  n_polygons: the number of rows (default: the largest row + 1); a row without rings is a polygon no
+    face can touch.  A ring with fewer than 3 distinct vertices or a non-finite coordinate is a ValueError.  Orientation does
+    not matter: every ring is stored counter-clockwise by its signed area.  A polygon's region is its exterior rings minus its
+    holes; rings of one polygon must not cross or overlap (a valid OGC polygon), and a SELF-INTERSECTING ring is undefined
+    behaviour: nothing checks for it, the containment test and the clipped area then mean nothing in particular."""
+
+    def __init__(self, rings, ring_polygon, ring_is_hole, n_polygons: typing.Optional[int] = None):
+        if isinstance(rings, (str, bytes)) or hasattr(rings, "geometry"):
+            raise NotImplementedError("polygon files and GeoDataFrames need geopandas, which is outside the projection path: "
+                                      "pass the rings as arrays")
+        ring_polygon = np.asarray(ring_polygon, dtype=np.int64).reshape(-1)
+        ring_is_hole = np.asarray(ring_is_hole, dtype=bool).reshape(-1)
+        if not (len(rings) == ring_polygon.shape[0] == ring_is_hole.shape[0]):
+            raise ValueError(f"{len(rings)} rings need as many polygon rows and hole flags, got {ring_polygon.shape[0]} and "
+                             f"{ring_is_hole.shape[0]}")
+        if ring_polygon.size and ring_polygon.min() < 0:
+            raise ValueError("ring_polygon holds a negative row")
+        rows = int(ring_polygon.max()) + 1 if ring_polygon.size else 0
+        self.n_polygons = rows if n_polygons is None else int(n_polygons)
+        if self.n_polygons < rows:
+            raise ValueError(f"ring_polygon names row {rows - 1} but n_polygons is {self.n_polygons}")
+        clean = []
+        for r, ring in enumerate(rings):
+            ring = np.asarray(ring, dtype=np.float64)
+            if ring.ndim != 2 or ring.shape[1] != 2:
+                raise ValueError(f"ring {r} must be an (n, 2) array, got shape {ring.shape}")
+            if not np.all(np.isfinite(ring)):
+                raise ValueError(f"ring {r} has a non-finite coordinate")
+            if len(ring) > 1 and np.array_equal(ring[0], ring[-1]):
+                ring = ring[:-1]
+            if len(np.unique(ring, axis=0)) < 3:
+                raise ValueError(f"ring {r} has fewer than 3 distinct vertices")
+            x, y = ring[:, 0] - ring[0, 0], ring[:, 1] - ring[0, 1]
+            if np.sum(x * np.roll(y, -1) - np.roll(x, -1) * y) < 0:
+                ring = ring[::-1]
+            clean.append(np.ascontiguousarray(ring))
+        order = np.argsort(ring_polygon, kind="stable")   # the device walks a polygon's rings consecutively
+        self.rings = [clean[i] for i in order]
+        self.ring_polygon = ring_polygon[order]
+        self.ring_is_hole = ring_is_hole[order]
+
+    def __len__(self):
+        return self.n_polygons
+
+    @classmethod
+    def from_sequence(cls, seq):
+        """One row per item: an (n, 2) array (a polygon without holes) or a list [exterior, hole, ...]."""
+        if isinstance(seq, (str, bytes)) or hasattr(seq, "geometry") or hasattr(seq, "__fspath__"):
+            raise NotImplementedError("polygon files and GeoDataFrames need geopandas, which is outside the projection path: "
+                                      "pass a sequence of ring arrays or a PlanarPolygons")
+        rings, rows, holes = [], [], []
+        for p, item in enumerate(seq):
+            parts = [item] if (isinstance(item, np.ndarray) and item.ndim == 2) else list(item)
+            if parts and np.ndim(parts[0]) == 1:   # a plain list of (x, y) pairs
+                parts = [np.asarray(item)]
+            for k, ring in enumerate(parts):
+                rings.append(ring)
+                rows.append(p)
+                holes.append(k > 0)
+        return cls(rings, rows, holes, n_polygons=len(seq))
+
+    def snapped(self, origin=(0, 0)):
+        """The ring table the device takes, on the 1e-6 m grid behind the integer `origin`: (ring_vertices (N, 2) int64,
+        ring_offsets (R + 1,) int64, ring_polygon (R,) int32, ring_is_hole (R,) int32, polygon_boxes (P, 4) int64 xmin ymin
+        xmax ymax).  Rings the snap collapses to zero area are dropped (GEOS makes them empty); one it turns over is turned back.
+        A row without rings has the empty box (1, 1, 0, 0)."""
+        origin = np.asarray(origin, dtype=np.int64).reshape(2)
+        verts, offsets, rows, holes = [], [0], [], []
+        boxes = np.tile(np.array([1, 1, 0, 0], dtype=np.int64), (self.n_polygons, 1))
+        seen = np.zeros(self.n_polygons, dtype=bool)
+        for ring, row, hole in zip(self.rings, self.ring_polygon, self.ring_is_hole):
+            q = snap_to_grid(ring) - origin
+            if np.abs(q).max() > SNAP_LIMIT:
+                raise ValueError(f"a polygon vertex lies more than 2^40 grid steps ({SNAP_LIMIT * SNAP_GRID_METERS:.0f} m) from "
+                                 "the common origin")
+            a2 = _signed_area2_exact(q)
+            if a2 == 0:
+                continue
+            if a2 < 0:
+                q = q[::-1]
+            lo, hi = q.min(axis=0), q.max(axis=0)
+            if seen[row]:
+                boxes[row, :2] = np.minimum(boxes[row, :2], lo)
+                boxes[row, 2:] = np.maximum(boxes[row, 2:], hi)
+            else:
+                boxes[row, :2], boxes[row, 2:], seen[row] = lo, hi, True
+            verts.append(q)
+            offsets.append(offsets[-1] + len(q))
+            rows.append(row)
+            holes.append(hole)
+        ring_vertices = np.concatenate(verts) if verts else np.zeros((0, 2), dtype=np.int64)
+        return (np.ascontiguousarray(ring_vertices, dtype=np.int64), np.asarray(offsets, dtype=np.int64),
+                np.asarray(rows, dtype=np.int32), np.asarray(holes, dtype=np.int32), boxes)
+
+    def bounds_snapped(self):
+        """(lo (2,), hi (2,)) int64 of all rings on the grid, before any origin; None without rings."""
+        if not self.rings:
+            return None
+        q = [snap_to_grid(r) for r in self.rings]
+        return np.min([v.min(axis=0) for v in q], axis=0), np.max([v.max(axis=0) for v in q], axis=0)

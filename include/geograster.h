@@ -390,6 +390,38 @@ int gr_finalize_sums_f64(gr_ctx *ctx, double *sums_inout, const uint32_t *counts
 int gr_argmax_nonzero(gr_ctx *ctx, const void *array, int dtype, int64_t F, int C, double *out, void *stream);
 int gr_argmax_nonzero_f64(gr_ctx *ctx, const double *array, int64_t F, int C, double *out, void *stream);
 
+/* label_polygons -- replaces the geopandas stage of meshes.py:1141-1306 (one shapely Polygon per face, gpd.sjoin / gpd.overlay,
+ * weighted area, groupby) up to the per-(polygon, class) sums; the rule-set is DESIGN.md "Polygon labels".
+ * Faces: tri F x 6 int64, the corners x0 y0 x1 y1 x2 y2 SNAPPED to integers (units of 1e-6 m, a common origin subtracted,
+ * |value| <= 2^40; either winding; zero area: the face contributes nothing); face_class F int32, a value outside [0, C) skips
+ * the face; face_weight F f64.  Rings: ring_vertices n_ring_vertices x 2 int64 in the same units and origin, no repeated closing
+ * vertex; ring r is vertices ring_offsets[r] .. ring_offsets[r + 1] (R + 1 int64; fewer than 3 vertices: ignored), belongs to
+ * row ring_polygon[r] (int32, NON-DECREASING in r: the rings of a polygon are consecutive; outside [0, P): ignored) and is a hole
+ * where ring_is_hole[r] != 0 (int32).  For GR_POLY_OVERLAY every ring must be counter-clockwise.  polygon_boxes: P x 4 int64
+ * xmin ymin xmax ymax over the polygon's rings.
+ *   GR_POLY_WITHIN   a face adds area(snapped triangle) * weight to weights[p][class] iff the closed triangle lies in the closed
+ *                    region of polygon p (exteriors minus holes, even-odd over its rings), decided exactly with integer signs
+ *   GR_POLY_OVERLAY  every face adds area(triangle n polygon) * weight, the area clipped in f64 (Sutherland-Hodgman, the ring
+ *                    against the triangle's three half-planes), exterior rings minus holes
+ * weights: P x C f64, zeroed and written by the call; faces of one wave are summed in a fixed order, waves meet in f64 atomics,
+ * so sums can differ in their last bits from run to run (the decisions cannot).  stats: GR_POLY_STAT_WORDS uint64 on the device.
+ * Only enqueues work on `stream`; needs no uploaded mesh and no context scratch.  Added without a GR_VERSION bump. */
+enum {
+  GR_POLY_OVERLAY = 0,
+  GR_POLY_WITHIN = 1
+};
+enum {
+  GR_POLY_STAT_TESTED = 0,        /* (face, polygon) pairs whose boxes overlap                                       */
+  GR_POLY_STAT_CONTRIBUTING = 1,  /* ... that added to `weights`                                                      */
+  GR_POLY_STAT_LARGEST_RING = 2,  /* vertices of the largest ring                                                     */
+  GR_POLY_STAT_WORDS = 4
+};
+int gr_polygon_class_weights(gr_ctx *ctx, const int64_t *tri, const int32_t *face_class, const double *face_weight, int64_t F,
+                             const int64_t *ring_vertices, int64_t n_ring_vertices, const int64_t *ring_offsets,
+                             const int32_t *ring_polygon, const int32_t *ring_is_hole, int64_t R,
+                             const int64_t *polygon_boxes, int64_t P, int mode, int C, double *weights, uint64_t *stats,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif
