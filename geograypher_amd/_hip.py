@@ -271,27 +271,13 @@ class PairAccumulator:
         self.compactions = 0
 
     def add(self, ids, img):
-        torch = _torch()
         b = self.b
-        ids_t = b._dev(ids, torch.int32)
-        img_t = b._dev(img, torch.float64)
-        if ids_t.ndim == 2:
-            ids_t, img_t = ids_t[None], img_t[None]
-        if img_t.ndim == 4 and img_t.shape[-1] == 1:
-            img_t = img_t[..., 0]
-        if ids_t.shape != img_t.shape:
-            raise ValueError(f"ids {tuple(ids_t.shape)} and index image {tuple(img_t.shape)} differ in shape")
+        ids_t, img_t = b._index_views(ids, img)
         n, h, w = (int(x) for x in ids_t.shape)
-        self._fit_mesh()
-        if n * b.n_faces > self.cap:
-            for k in range(n):
-                self.add(ids_t[k], img_t[k])
+        if not self._make_room(n, lambda k: self.add(ids_t[k], img_t[k])):
             return
-        if self.bound + n * b.n_faces > self.cap:
-            self._compact()
-        b._call("gr_project_index_pairs", ids_t.data_ptr(), img_t.contiguous().data_ptr(), n, h, w, self.n_classes,
+        b._call("gr_project_index_pairs", ids_t.data_ptr(), img_t.data_ptr(), n, h, w, self.n_classes,
                 self.counts.data_ptr(), self.keys.data_ptr(), self.cap, self.key_count.data_ptr(), self.flags, b._stream())
-        self.bound += n * b.n_faces
 
     def add_rects(self, ids, rects, offsets):
         """`add` for views whose label image is a list of rectangles (`Segmentor.label_rectangles`): ids (n, h, w) or
@@ -304,7 +290,6 @@ class PairAccumulator:
         if ids_t.ndim == 2:
             ids_t = ids_t[None]
         n, h, w = (int(x) for x in ids_t.shape)
-        self._fit_mesh()
         rects = np.asarray(rects.cpu() if isinstance(rects, torch.Tensor) else rects).reshape(-1, 5)
         offsets = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets).reshape(-1)
         if offsets.shape[0] != n + 1:
@@ -313,28 +298,35 @@ class PairAccumulator:
             raise ValueError(f"rectangle offsets must rise from 0 to {rects.shape[0]} (the number of rectangles)")
         if rects.size and (rects.min() < np.iinfo(np.int32).min or rects.max() > np.iinfo(np.int32).max):
             raise ValueError("rectangle corners and classes must fit in int32")
-        if n * b.n_faces > self.cap:
-            for k in range(n):
-                lo, hi = int(offsets[k]), int(offsets[k + 1])
-                self.add_rects(ids_t[k], rects[lo:hi], np.array([0, hi - lo]))
+        if not self._make_room(n, lambda k: self.add_rects(ids_t[k], rects[offsets[k]:offsets[k + 1]],
+                                                           np.array([0, offsets[k + 1] - offsets[k]]))):
             return
-        if self.bound + n * b.n_faces > self.cap:
-            self._compact()
         # one upload: offsets, then the rectangle rows
         table = b._dev(np.concatenate([offsets.astype(np.int32), rects.astype(np.int32).reshape(-1)]), torch.int32)
         offs_ptr = table.data_ptr()
         rects_ptr = offs_ptr + 4 * (n + 1)
         b._call("gr_project_rect_pairs", ids_t.data_ptr(), rects_ptr, offs_ptr, n, h, w, self.n_classes,
                 self.counts.data_ptr(), self.keys.data_ptr(), self.cap, self.key_count.data_ptr(), self.flags, b._stream())
-        self.bound += n * b.n_faces
 
-    def _fit_mesh(self):
-        """The mesh may be uploaded (or replaced by a larger one) after the accumulator was made: the buffer must hold at
-        least one view's pairs, or a single view could never be added."""
-        if self.b.n_faces > self.cap:
+    def _make_room(self, n: int, add_view) -> bool:
+        """Room for the pairs of a call over n views, at most one per face and view.  A call that exceeds the buffer on its own
+        is added view by view instead (`add_view(k)`) and False returned; otherwise the buffer is compacted first if the call
+        could overflow it, `bound` counts the call in, and the caller makes it."""
+        F = self.b.n_faces
+        if F > self.cap:
+            # the mesh may be uploaded (or replaced by a larger one) after the accumulator was made: the buffer must hold at
+            # least one view's pairs, or a single view could never be added
             self._compact()
-            self.cap = max(8 * self.b.n_faces, 1 << 20)
+            self.cap = max(8 * F, 1 << 20)
             self.keys = _torch().empty((self.cap,), dtype=_torch().int64, device=self.b.device)
+        if n * F > self.cap:
+            for k in range(n):
+                add_view(k)
+            return False
+        if self.bound + n * F > self.cap:
+            self._compact()
+        self.bound += n * F
+        return True
 
     def _compact(self):
         raw, bad = (int(x) for x in self.key_count.cpu().tolist())
@@ -581,10 +573,9 @@ class HipRaster:
                    out.data_ptr(), self._stream())
         return out
 
-    def project_index_pairs(self, ids, img, n_classes: int, counts, neg1_is_last_face: bool = True):
-        """Sparse index aggregation step (derived_meshes.py:470-520) for N views: ids (N,h,w) int32, img (N,h,w) float64
-        with NaN = no prediction.  Accumulates counts (F,) and returns (pair_keys, multiplicities) int64 numpy arrays
-        with pair key = face * n_classes + class."""
+    def _index_views(self, ids, img):
+        """The inputs of the index-pair path: ids (N,h,w) or (h,w), the class-index image of the same shape (a channel axis of
+        one is dropped) -> contiguous (N,h,w) int32 and float64 tensors on this device."""
         torch = _torch()
         ids_t = self._dev(ids, torch.int32)
         img_t = self._dev(img, torch.float64)
@@ -594,12 +585,20 @@ class HipRaster:
             img_t = img_t[..., 0]
         if ids_t.shape != img_t.shape:
             raise ValueError(f"ids {tuple(ids_t.shape)} and index image {tuple(img_t.shape)} differ in shape")
+        return ids_t, img_t.contiguous()
+
+    def project_index_pairs(self, ids, img, n_classes: int, counts, neg1_is_last_face: bool = True):
+        """Sparse index aggregation step (derived_meshes.py:470-520) for N views: ids (N,h,w) int32, img (N,h,w) float64
+        with NaN = no prediction.  Accumulates counts (F,) and returns (pair_keys, multiplicities) int64 numpy arrays
+        with pair key = face * n_classes + class."""
+        torch = _torch()
+        ids_t, img_t = self._index_views(ids, img)
         n, h, w = (int(x) for x in ids_t.shape)
         cap = n * self.n_faces
         keys = torch.empty((max(cap, 1),), dtype=torch.int64, device=self.device)
         key_count = torch.zeros((1,), dtype=torch.int64, device=self.device)
         flags = GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
-        self._call("gr_project_index_pairs", ids_t.data_ptr(), img_t.contiguous().data_ptr(), n, h, w, int(n_classes),
+        self._call("gr_project_index_pairs", ids_t.data_ptr(), img_t.data_ptr(), n, h, w, int(n_classes),
                    counts.data_ptr(), keys.data_ptr(), cap, key_count.data_ptr(), flags, self._stream())
         m = int(key_count.item())
         if m == 0:

@@ -323,7 +323,7 @@ int raster_views(gr_ctx *c, const float *cams, int n_views, int h, int w, int32_
         GR_HIP(c, hipStreamWaitEvent(c->side, c->ev_raster[buf], 0));
         vs = c->side;
       }
-      launch_vote_labels(c, vs, win, labels + v0 * P, nb, F, P, C, votes, counts, v0 / B, (const uint32_t *)tch, tw, flags);
+      launch_vote_labels(c, vs, win, labels + v0 * P, nb, F, P, C, votes, counts, v0 / B, (const uint32_t *)tch, tw);
       GR_HIP(c, hipGetLastError());
       if (overlap) GR_HIP(c, hipEventRecord(c->ev_vote[buf], c->side));
     }

@@ -408,9 +408,7 @@ int bin_batch(gr_ctx *c, const float *cams, int nb, int h, int w, int slot0, int
 int tile_batch(gr_ctx *c, int nb, int h, int w, int slot0, RasterOut out, hipStream_t s);                 // raster_tile.hip
 int bin_stats_deferred(gr_ctx *c, hipStream_t s);                                                         // binning.hip
 int sum_visits(gr_ctx *c, hipStream_t s);                                                                 // binning.hip
-int project_labels(gr_ctx *c, const int32_t *ids, const uint8_t *labels, int n_views, int h, int w, int C, uint32_t *votes,
-                   uint32_t *counts, int flags, hipStream_t s);                                           // project.hip
 void launch_vote_labels(gr_ctx *c, hipStream_t vs, uint32_t *win, const uint8_t *labels, int nb, int64_t F, int64_t P, int C,
-                        uint32_t *votes, uint32_t *counts, int group, const uint32_t *touched, int tw, int flags);  // project.hip
+                        uint32_t *votes, uint32_t *counts, int group, const uint32_t *touched, int tw);  // project.hip
 
 }  // namespace grimpl

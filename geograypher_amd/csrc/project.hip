@@ -232,6 +232,19 @@ __global__ __launch_bounds__(256) void k_gather_texture_u8(const int32_t *__rest
   out[i] = v;
 }
 
+// The tail of both emit kernels (K10, K10r): the lanes of a wave that hold a pair (takers = __ballot(emit), not empty: the
+// caller keeps the ballot and its test, dev_common.hpp says why) append their keys behind *key_count with one atomic; a key
+// beyond key_cap is counted and dropped.
+__device__ __forceinline__ void append_pair_keys(bool emit, unsigned long long key, unsigned long long takers, int lane,
+                                                 unsigned long long *__restrict__ keys, long long key_cap,
+                                                 unsigned long long *__restrict__ key_count) {
+  const unsigned long long base = wave_append(takers, key_count, lane);
+  if (emit) {
+    const unsigned long long idx = base + wave_rank(takers, lane);
+    if ((long long)idx < key_cap) keys[idx] = key;
+  }
+}
+
 // K10 sparse index aggregation (row f3, derived_meshes.py:470-520): one thread per face walks the views of the batch;
 //     a finite winner value v is one observation of class int(v): counts[f] += 1 and the pair key f * n_classes + class
 //     is appended to `keys` (wave ballot + one atomic per wave).  The pairs are counted later by sort + run-length.
@@ -265,13 +278,7 @@ __global__ __launch_bounds__(256) void k_emit_index_pairs(uint32_t *__restrict__
       }
     }
     const unsigned long long m = __ballot(emit);
-    if (m) {
-      const unsigned long long base = wave_append(m, key_count, lane);
-      if (emit) {
-        const unsigned long long idx = base + wave_rank(m, lane);
-        if ((long long)idx < key_cap) keys[idx] = key;
-      }
-    }
+    if (m) append_pair_keys(emit, key, m, lane, keys, key_cap, key_count);
   }
   if (f < F && c) counts[f] += c;
 }
@@ -340,13 +347,7 @@ __global__ __launch_bounds__(256) void k_emit_rect_pairs(uint32_t *__restrict__ 
       else { emit = true; key = (unsigned long long)f * (unsigned long long)n_classes + (unsigned long long)cls; }
     }
     const unsigned long long m = __ballot(emit);
-    if (m) {
-      const unsigned long long base = wave_append(m, key_count, lane);
-      if (emit) {
-        const unsigned long long idx = base + wave_rank(m, lane);
-        if ((long long)idx < key_cap) keys[idx] = key;
-      }
-    }
+    if (m) append_pair_keys(emit, key, m, lane, keys, key_cap, key_count);
   }
   if (f < F && c) counts[f] += c;
 }
@@ -475,42 +476,79 @@ __global__ __launch_bounds__(256) void k_argmax_nonzero(const T *__restrict__ ar
 
 namespace grimpl {
 
-// unfused label projection for id images already in memory: winner pass + vote pass per launch group
-int project_labels(gr_ctx *c, const int32_t *ids, const uint8_t *labels, int n_views, int h, int w, int C, uint32_t *votes,
-                   uint32_t *counts, int flags, hipStream_t s) {
+// the fused aggregation's vote pass of one launch group (raster_views, geograster.hip)
+void launch_vote_labels(gr_ctx *c, hipStream_t vs, uint32_t *win, const uint8_t *labels, int nb, int64_t F, int64_t P, int C,
+                        uint32_t *votes, uint32_t *counts, int group, const uint32_t *touched, int tw) {
+  Timed t(c, vs, ST_VOTE);
+  hipLaunchKernelGGL(k_vote_labels, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, vs, win, labels, nb, F, P, C, votes, counts,
+                     (const unsigned long long *)c->stats, group, touched, tw, touched ? c->visits : (uint32_t *)nullptr);
+}
+
+}  // namespace grimpl
+
+namespace {
+
+// What every projection entry point checks before its own arguments: the shape, then the mesh.
+int check_projection(gr_ctx *c, int n_views, int h, int w) {
+  int rc = check_common(c, n_views, h, w);
+  if (rc) return rc;
+  if (c->F <= 0) return fail(c, GR_ENOMESH, "gr_mesh_upload has not been called");
+  return GR_OK;
+}
+
+// The "a value is no class index" check of the two pair entry points.  The consumer kernel ORs into `flag`: the context's flag
+// word, zeroed ahead of the first launch group and read back behind the last (project_groups) -- or, with GR_FLAG_DEFER_CHECK,
+// the caller's SECOND 64-bit word behind the pair counter (a word of its own: the counter takes 64-bit atomics, the flag a
+// 32-bit one), which nobody reads here.
+struct ClassCheck {
+  bool defer;
+  int *flag;
+  const char *message;  // of GR_EINDEX; takes n_classes
+  long long n_classes;
+  ClassCheck(gr_ctx *c, uint64_t *key_count, int flags, const char *msg, int64_t nc)
+      : defer((flags & GR_FLAG_DEFER_CHECK) != 0), flag(defer ? reinterpret_cast<int *>(key_count + 1) : c->flag), message(msg),
+        n_classes((long long)nc) {}
+};
+
+// The launch-group protocol behind every projection entry point, once the arguments are checked: winner scratch for
+// min(n_views, GR_MAX_BATCH) views, then per group of that many views the winners of its id images (ST_PROJECT) and the caller's
+// consumer launch(es) `consume(win, v0, nb)` over views [v0, v0 + nb) (ST_VOTE), which leave the winners cleared.
+template <typename Consumer>
+int project_groups(gr_ctx *c, const int32_t *ids, int n_views, int h, int w, int flags, void *stream, Consumer consume,
+                   const ClassCheck *check = nullptr) {
+  if (n_views == 0) return GR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
   const int64_t P = (int64_t)h * w, F = c->F;
   const int B = n_views < GR_MAX_BATCH ? n_views : GR_MAX_BATCH;
   int rc = ensure_winner(c, sizeof(uint32_t) * (size_t)F * B, s);
   if (rc) return rc;
   note_stream(c, s);
   uint32_t *win = (uint32_t *)c->winner;
+  const int compat = (flags & GR_FLAG_NEG1_IS_LAST_FACE) ? 1 : 0;
+  if (check && !check->defer) GR_HIP(c, hipMemsetAsync(c->flag, 0, sizeof(int), s));
   for (int v0 = 0; v0 < n_views; v0 += B) {
     const int nb = (n_views - v0) < B ? (n_views - v0) : B;
     {
       Timed t(c, s, ST_PROJECT);
       hipLaunchKernelGGL(k_winner, dim3((unsigned)ceil_div(ceil_div(w, 4), 256), (unsigned)ceil_div(h, WIN_ROWS), nb), dim3(256), 0,
-                         s, ids + v0 * P, win, F, h, w, (flags & GR_FLAG_NEG1_IS_LAST_FACE) ? 1 : 0);
+                         s, ids + v0 * P, win, F, h, w, compat);
     }
     {
       Timed t(c, s, ST_VOTE);
-      hipLaunchKernelGGL(k_vote_labels, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, labels + v0 * P, nb, F, P, C,
-                         votes, counts, (const unsigned long long *)nullptr, 0, (const uint32_t *)nullptr, 0, (uint32_t *)nullptr);
+      consume(win, v0, nb);
     }
   }
   GR_HIP(c, hipGetLastError());
+  if (!check || check->defer) return GR_OK;
+  int bad = 0;
+  GR_HIP(c, hipMemcpyAsync(&bad, c->flag, sizeof(int), hipMemcpyDeviceToHost, s));
+  GR_HIP(c, hipStreamSynchronize(s));
+  if (bad) return fail(c, GR_EINDEX, check->message, check->n_classes);
   return GR_OK;
 }
 
-// the fused aggregation's vote pass of one launch group (raster_views, geograster.hip)
-void launch_vote_labels(gr_ctx *c, hipStream_t vs, uint32_t *win, const uint8_t *labels, int nb, int64_t F, int64_t P, int C,
-                        uint32_t *votes, uint32_t *counts, int group, const uint32_t *touched, int tw, int flags) {
-  Timed t(c, vs, ST_VOTE);
-  hipLaunchKernelGGL(k_vote_labels, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, vs, win, labels, nb, F, P, C, votes, counts,
-                     (const unsigned long long *)c->stats, group, touched, tw, touched ? c->visits : (uint32_t *)nullptr);
-  (void)flags;
-}
-
-}  // namespace grimpl
+}  // namespace
 
 extern "C" {
 
@@ -529,73 +567,41 @@ int gr_gather_texture_f64(gr_ctx *c, const int32_t *ids, int64_t n_pix, const do
 
 int gr_project_labels_u8(gr_ctx *c, const int32_t *ids, const uint8_t *labels, int n_views, int h, int w, int C,
                          uint32_t *votes, uint32_t *counts, int flags, void *stream) {
-  int rc = check_common(c, n_views, h, w);
+  int rc = check_projection(c, n_views, h, w);
   if (rc) return rc;
-  if (c->F <= 0) return fail(c, GR_ENOMESH, "gr_mesh_upload has not been called");
   if (!ids || !labels || !votes || !counts || C <= 0 || C > 255) return fail(c, GR_EINVAL, "bad project args C=%d", C);
-  if (n_views == 0) return GR_OK;
+  const int64_t P = (int64_t)h * w, F = c->F;
   hipStream_t s = (hipStream_t)stream;
-  GR_HIP(c, hipSetDevice(c->device));
-  return project_labels(c, ids, labels, n_views, h, w, C, votes, counts, flags, s);
+  return project_groups(c, ids, n_views, h, w, flags, stream, [&](uint32_t *win, int v0, int nb) {
+    hipLaunchKernelGGL(k_vote_labels, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, labels + v0 * P, nb, F, P, C,
+                       votes, counts, (const unsigned long long *)nullptr, 0, (const uint32_t *)nullptr, 0, (uint32_t *)nullptr);
+  });
 }
 
 int gr_project_values_f64(gr_ctx *c, const int32_t *ids, const double *img, int n_views, int h, int w, int C,
                           double *sums, uint32_t *counts, int flags, void *stream) {
-  int rc = check_common(c, n_views, h, w);
+  int rc = check_projection(c, n_views, h, w);
   if (rc) return rc;
-  if (c->F <= 0) return fail(c, GR_ENOMESH, "gr_mesh_upload has not been called");
   if (!ids || !img || !sums || !counts || C <= 0) return fail(c, GR_EINVAL, "bad project args");
-  if (n_views == 0) return GR_OK;
-  hipStream_t s = (hipStream_t)stream;
-  GR_HIP(c, hipSetDevice(c->device));
   const int64_t P = (int64_t)h * w, F = c->F;
-  const int B = n_views < GR_MAX_BATCH ? n_views : GR_MAX_BATCH;
-  rc = ensure_winner(c, sizeof(uint32_t) * (size_t)F * B, s);
-  if (rc) return rc;
-  note_stream(c, s);
-  uint32_t *win = (uint32_t *)c->winner;
-  for (int v0 = 0; v0 < n_views; v0 += B) {
-    const int nb = (n_views - v0) < B ? (n_views - v0) : B;
-    {
-      Timed t(c, s, ST_PROJECT);
-      hipLaunchKernelGGL(k_winner, dim3((unsigned)ceil_div(ceil_div(w, 4), 256), (unsigned)ceil_div(h, WIN_ROWS), nb), dim3(256), 0, s, ids + v0 * P, win, F, h, w,
-                         (flags & GR_FLAG_NEG1_IS_LAST_FACE) ? 1 : 0);
-    }
-    {
-      Timed t(c, s, ST_VOTE);
-      hipLaunchKernelGGL(k_vote_values, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, img + v0 * P * C, nb, F,
-                         P, C, sums, counts);
-    }
-  }
-  GR_HIP(c, hipGetLastError());
-  return GR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  return project_groups(c, ids, n_views, h, w, flags, stream, [&](uint32_t *win, int v0, int nb) {
+    hipLaunchKernelGGL(k_vote_values, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, img + v0 * P * C, nb, F, P, C,
+                       sums, counts);
+  });
 }
 
 int gr_project_view_f64(gr_ctx *c, const int32_t *ids, const double *img, int h, int w, int C, double *tex, int flags,
                         void *stream) {
-  int rc = check_common(c, 1, h, w);
+  int rc = check_projection(c, 1, h, w);
   if (rc) return rc;
-  if (c->F <= 0) return fail(c, GR_ENOMESH, "gr_mesh_upload has not been called");
   if (!ids || !img || !tex || C <= 0) return fail(c, GR_EINVAL, "bad project args");
-  hipStream_t s = (hipStream_t)stream;
-  GR_HIP(c, hipSetDevice(c->device));
   const int64_t F = c->F;
-  rc = ensure_winner(c, sizeof(uint32_t) * (size_t)F, s);
-  if (rc) return rc;
-  note_stream(c, s);
-  uint32_t *win = (uint32_t *)c->winner;
-  {
-    Timed t(c, s, ST_PROJECT);
-    hipLaunchKernelGGL(k_winner, dim3((unsigned)ceil_div(ceil_div(w, 4), 256), (unsigned)ceil_div(h, WIN_ROWS), 1), dim3(256), 0, s, ids, win, F, h, w,
-                         (flags & GR_FLAG_NEG1_IS_LAST_FACE) ? 1 : 0);
-  }
-  {
-    Timed t(c, s, ST_VOTE);
+  hipStream_t s = (hipStream_t)stream;
+  return project_groups(c, ids, 1, h, w, flags, stream, [&](uint32_t *win, int, int) {  // one view: one group
     hipLaunchKernelGGL(k_project_view, dim3((unsigned)ceil_div(F * C, 256)), dim3(256), 0, s, win, img, F, C, tex);
     hipLaunchKernelGGL(k_clear_u32, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, F);
-  }
-  GR_HIP(c, hipGetLastError());
-  return GR_OK;
+  });
 }
 
 int gr_gather_texture_u8(gr_ctx *c, const int32_t *ids, int64_t n_pix, const double *face_tex, int64_t F, int C,
@@ -616,90 +622,36 @@ int gr_gather_texture_u8(gr_ctx *c, const int32_t *ids, int64_t n_pix, const dou
 int gr_project_index_pairs(gr_ctx *c, const int32_t *ids, const double *img, int n_views, int h, int w, int64_t n_classes,
                            uint32_t *counts, uint64_t *keys, int64_t key_cap, uint64_t *key_count, int flags,
                            void *stream) {
-  int rc = check_common(c, n_views, h, w);
+  int rc = check_projection(c, n_views, h, w);
   if (rc) return rc;
-  if (c->F <= 0) return fail(c, GR_ENOMESH, "gr_mesh_upload has not been called");
   if (!ids || !img || !counts || !keys || !key_count || n_classes <= 0 || key_cap < 0)
     return fail(c, GR_EINVAL, "bad sparse projection args");
   if (n_classes > (1ll << 53)) return fail(c, GR_EINVAL, "n_classes %lld exceeds 2^53", (long long)n_classes);
-  if (n_views == 0) return GR_OK;
-  hipStream_t s = (hipStream_t)stream;
-  GR_HIP(c, hipSetDevice(c->device));
   const int64_t P = (int64_t)h * w, F = c->F;
-  const int B = n_views < GR_MAX_BATCH ? n_views : GR_MAX_BATCH;
-  rc = ensure_winner(c, sizeof(uint32_t) * (size_t)F * B, s);
-  if (rc) return rc;
-  note_stream(c, s);
-  uint32_t *win = (uint32_t *)c->winner;
-  // the "a value is no class index" flag: the context's flag word, read back below -- or, deferred, the caller's SECOND
-  // 64-bit word behind the pair counter (a word of its own: the counter takes 64-bit atomics, the flag a 32-bit one)
-  const bool defer = (flags & GR_FLAG_DEFER_CHECK) != 0;
-  int *bad_flag = defer ? reinterpret_cast<int *>(key_count + 1) : c->flag;
-  if (!defer) GR_HIP(c, hipMemsetAsync(c->flag, 0, sizeof(int), s));
-  for (int v0 = 0; v0 < n_views; v0 += B) {
-    const int nb = (n_views - v0) < B ? (n_views - v0) : B;
-    {
-      Timed t(c, s, ST_PROJECT);
-      hipLaunchKernelGGL(k_winner, dim3((unsigned)ceil_div(ceil_div(w, 4), 256), (unsigned)ceil_div(h, WIN_ROWS), nb), dim3(256), 0, s, ids + v0 * P, win, F, h, w,
-                         (flags & GR_FLAG_NEG1_IS_LAST_FACE) ? 1 : 0);
-    }
-    {
-      Timed t(c, s, ST_VOTE);
-      hipLaunchKernelGGL(k_emit_index_pairs, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, img + v0 * P, nb, F, P,
-                         (long long)n_classes, counts, (unsigned long long *)keys, (long long)key_cap,
-                         (unsigned long long *)key_count, bad_flag);
-    }
-  }
-  GR_HIP(c, hipGetLastError());
-  if (defer) return GR_OK;
-  int bad = 0;
-  GR_HIP(c, hipMemcpyAsync(&bad, c->flag, sizeof(int), hipMemcpyDeviceToHost, s));
-  GR_HIP(c, hipStreamSynchronize(s));
-  if (bad) return fail(c, GR_EINDEX, "an image value is not a class index in [0, %lld)", (long long)n_classes);
-  return GR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const ClassCheck check(c, key_count, flags, "an image value is not a class index in [0, %lld)", n_classes);
+  return project_groups(c, ids, n_views, h, w, flags, stream, [&](uint32_t *win, int v0, int nb) {
+    hipLaunchKernelGGL(k_emit_index_pairs, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, img + v0 * P, nb, F, P,
+                       (long long)n_classes, counts, (unsigned long long *)keys, (long long)key_cap,
+                       (unsigned long long *)key_count, check.flag);
+  }, &check);
 }
 
 int gr_project_rect_pairs(gr_ctx *c, const int32_t *ids, const int32_t *rects, const int32_t *rect_offsets, int n_views,
                           int h, int w, int64_t n_classes, uint32_t *counts, uint64_t *keys, int64_t key_cap,
                           uint64_t *key_count, int flags, void *stream) {
-  int rc = check_common(c, n_views, h, w);
+  int rc = check_projection(c, n_views, h, w);
   if (rc) return rc;
-  if (c->F <= 0) return fail(c, GR_ENOMESH, "gr_mesh_upload has not been called");
   if (!ids || !rect_offsets || !counts || !keys || !key_count || n_classes <= 0 || key_cap < 0)
     return fail(c, GR_EINVAL, "bad sparse projection args");
-  if (n_views == 0) return GR_OK;
+  const int64_t F = c->F;
   hipStream_t s = (hipStream_t)stream;
-  GR_HIP(c, hipSetDevice(c->device));
-  const int64_t P = (int64_t)h * w, F = c->F;
-  const int B = n_views < GR_MAX_BATCH ? n_views : GR_MAX_BATCH;
-  rc = ensure_winner(c, sizeof(uint32_t) * (size_t)F * B, s);
-  if (rc) return rc;
-  note_stream(c, s);
-  uint32_t *win = (uint32_t *)c->winner;
-  const bool defer = (flags & GR_FLAG_DEFER_CHECK) != 0;
-  int *bad_flag = defer ? reinterpret_cast<int *>(key_count + 1) : c->flag;
-  if (!defer) GR_HIP(c, hipMemsetAsync(c->flag, 0, sizeof(int), s));
-  for (int v0 = 0; v0 < n_views; v0 += B) {
-    const int nb = (n_views - v0) < B ? (n_views - v0) : B;
-    {
-      Timed t(c, s, ST_PROJECT);
-      hipLaunchKernelGGL(k_winner, dim3((unsigned)ceil_div(ceil_div(w, 4), 256), (unsigned)ceil_div(h, WIN_ROWS), nb), dim3(256), 0, s, ids + v0 * P, win, F, h, w,
-                         (flags & GR_FLAG_NEG1_IS_LAST_FACE) ? 1 : 0);
-    }
-    {
-      Timed t(c, s, ST_VOTE);
-      hipLaunchKernelGGL(k_emit_rect_pairs, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, rects, rect_offsets + v0,
-                         nb, F, w, (long long)n_classes, counts, (unsigned long long *)keys, (long long)key_cap,
-                         (unsigned long long *)key_count, bad_flag);
-    }
-  }
-  GR_HIP(c, hipGetLastError());
-  if (defer) return GR_OK;
-  int bad = 0;
-  GR_HIP(c, hipMemcpyAsync(&bad, c->flag, sizeof(int), hipMemcpyDeviceToHost, s));
-  GR_HIP(c, hipStreamSynchronize(s));
-  if (bad) return fail(c, GR_EINDEX, "a rectangle's class is not a class index in [0, %lld)", (long long)n_classes);
-  return GR_OK;
+  const ClassCheck check(c, key_count, flags, "a rectangle's class is not a class index in [0, %lld)", n_classes);
+  return project_groups(c, ids, n_views, h, w, flags, stream, [&](uint32_t *win, int v0, int nb) {
+    hipLaunchKernelGGL(k_emit_rect_pairs, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, rects, rect_offsets + v0,
+                       nb, F, w, (long long)n_classes, counts, (unsigned long long *)keys, (long long)key_cap,
+                       (unsigned long long *)key_count, check.flag);
+  }, &check);
 }
 
 int gr_count_pairs(gr_ctx *c, uint64_t *keys, int64_t n, uint64_t *unique_keys, uint32_t *pair_counts, int64_t *n_unique_h,

@@ -734,7 +734,6 @@ class TexturedPhotogrammetryMesh:
         if len(cameras) == 0 or batch_size > len(cameras):
             raise IndexError("list index out of range")  # what the reference's get_subset_cameras raises here
         rank, world = dist_utils.rank_world() if distributed else (0, 1)
-        torch = _torch()
         n_faces = self.faces.shape[0]
         check_null_image = bool(kwargs.pop("check_null_image", False))
 
@@ -778,10 +777,7 @@ class TexturedPhotogrammetryMesh:
 
                 with ThreadPoolExecutor(max_workers=len(backends)) as dev_pool:
                     parts = list(dev_pool.map(run, range(len(backends))))
-                votes, counts = parts[0]
-                for v_k, c_k in parts[1:]:
-                    votes += v_k.to(votes.device)
-                    counts += c_k.to(counts.device)
+                votes, counts = _add_on_first(parts)
             if distributed and world > 1:
                 dist_utils.all_reduce_votes(votes, counts)
             avg, summed, cnt = self.backend.finalize_votes(votes, counts)
@@ -795,11 +791,9 @@ class TexturedPhotogrammetryMesh:
         shard = distributed and world > 1 and not single_view
         if shard and return_all:
             raise NotImplementedError("return_all keeps every view's projection: not available with distributed=True")
-        all_projections = [] if return_all else None
-        sums = counts = first = None
-        n_channels = None
-        multi = len(self.backends) > 1 and not return_all and not single_view
-        if multi:
+        projections = []   # every view's own projection, for return_all and for the single view
+        mine = view_inds[rank::world] if shard else view_inds   # the per-view arithmetic does not depend on the other views
+        if len(self.backends) > 1 and not return_all and not single_view:
             # devices=[...]: this rank's views dealt round-robin to the devices, each running the per-view recurrence over its own
             # views on a host thread of its own; the partial sums and counts are added on the first device.  The float contract
             # is that of views sharded over processes (include/geograster.h, gr_project_values_f64): counts exact, sums of finite
@@ -807,7 +801,6 @@ class TexturedPhotogrammetryMesh:
             import copy
             from concurrent.futures import ThreadPoolExecutor
 
-            mine = view_inds[rank::world] if shard else view_inds
             self.get_mesh_in_cameras_coords(cameras)   # the local mesh, cached before the workers ask for it
 
             def run(k):
@@ -816,81 +809,66 @@ class TexturedPhotogrammetryMesh:
                     return None
                 worker = copy.copy(self)   # same arrays, caches and upload table; its own backend
                 worker._backend, worker._backends = self.backends[k], [self.backends[k]]
-                bk = self.backends[k]
-                ctx = contextlib.nullcontext()
-                if bk.device.type == "cuda":
-                    torch.cuda.set_device(bk.device)
-                    ctx = torch.cuda.stream(torch.cuda.Stream(bk.device))
-                with ctx:
-                    s_k = c_k = None
-                    nch = None
-                    for _, ids, img, nch in worker._iter_view_inputs(cameras.get_subset_cameras(inds_k), 1, aggregate_img_scale,
-                                                                     check_null_image, dict(kwargs), loader_threads):
-                        if s_k is None:
-                            s_k = torch.zeros((n_faces, nch), dtype=torch.float64, device=bk.device)
-                            c_k = torch.zeros((n_faces,), dtype=torch.int32, device=bk.device)
-                        if img is not None:
-                            bk.project_values(ids, img, s_k, c_k, neg1_is_last_face=self.neg1_is_last_face)
-                        else:
-                            torch.nan_to_num_(s_k, nan=0.0, posinf=float("inf"), neginf=float("-inf"))
-                    if bk.device.type == "cuda":
-                        torch.cuda.current_stream(bk.device).synchronize()
-                return s_k, c_k, nch
+                with _driving(self.backends[k], own_stream=True):
+                    return self._nansum_views(self.backends[k], (view[1:] for view in worker._iter_view_inputs(
+                        cameras.get_subset_cameras(inds_k), 1, aggregate_img_scale, check_null_image, dict(kwargs), loader_threads)))
 
             with ThreadPoolExecutor(max_workers=len(self.backends)) as dev_pool:
                 parts = [p for p in dev_pool.map(run, range(len(self.backends))) if p is not None and p[0] is not None]
-            for s_k, c_k, nch in parts:
-                n_channels = nch
-                if sums is None:
-                    sums, counts = s_k.to(self.backend.device), c_k.to(self.backend.device)
-                else:
-                    sums += s_k.to(sums.device)
-                    counts += c_k.to(counts.device)
-            gen, total = iter(()), 0
-        elif shard:  # this rank's views; the per-view arithmetic does not depend on the other views
-            my_cams = cameras.get_subset_cameras(view_inds[rank::world])
-            gen = self._iter_view_inputs(my_cams, 1, aggregate_img_scale, check_null_image, kwargs, loader_threads) if len(my_cams) else iter(())
-            total = len(my_cams)
+            sums, counts, n_channels = (*_add_on_first([p[:2] for p in parts]), parts[0][2]) if parts else (None, None, None)
         else:
-            gen = self._iter_view_inputs(cameras, batch_size, aggregate_img_scale, check_null_image, kwargs, loader_threads)
-            total = len(cameras)
-        for _, ids, img, n_channels in (gen if multi else tqdm(gen, total=total, desc="Aggregating projected viewpoints")):
-            if sums is None:
-                sums = torch.zeros((n_faces, n_channels), dtype=torch.float64, device=self.backend.device)
-                counts = torch.zeros((n_faces,), dtype=torch.int32, device=self.backend.device)
-            if return_all or single_view:
-                if img is None:
-                    proj = np.full((n_faces, n_channels), fill_value=np.nan)
-                else:
-                    proj = _to_host(self.backend.project_view(ids, img, neg1_is_last_face=self.neg1_is_last_face))
-                if return_all:
-                    all_projections.append(proj)
-                first = proj if first is None else first
-            if img is not None:
-                self.backend.project_values(ids, img, sums, counts, neg1_is_last_face=self.neg1_is_last_face)
-            else:
-                # a skipped (null) image still passes through np.nansum([summed, all-NaN projection]) in the reference
-                # (meshes.py:2060-2062), which drops a NaN of the running sum (+inf met -inf) like every other view does
-                torch.nan_to_num_(sums, nan=0.0, posinf=float("inf"), neginf=float("-inf"))
+            my_cams, per_batch = (cameras.get_subset_cameras(mine), 1) if shard else (cameras, batch_size)
+            gen = self._iter_view_inputs(my_cams, per_batch, aggregate_img_scale, check_null_image, kwargs, loader_threads) if len(my_cams) else iter(())
+
+            def views():
+                for _, ids, img, nch in tqdm(gen, total=len(my_cams), desc="Aggregating projected viewpoints"):
+                    if return_all or single_view:
+                        if img is None:
+                            projections.append(np.full((n_faces, nch), fill_value=np.nan))
+                        else:
+                            projections.append(_to_host(self.backend.project_view(ids, img, neg1_is_last_face=self.neg1_is_last_face)))
+                    yield ids, img, nch
+
+            sums, counts, n_channels = self._nansum_views(self.backend, views())
         if shard:
             if sums is None:  # a rank without views still takes part in the collective
                 n_channels = int(np.asarray(cameras.get_image_by_index(view_inds[0], aggregate_img_scale)).reshape(
                     cameras.cameras[view_inds[0]].get_image_size(aggregate_img_scale) + (-1,)).shape[-1])
-                sums = torch.zeros((n_faces, n_channels), dtype=torch.float64, device=self.backend.device)
-                counts = torch.zeros((n_faces,), dtype=torch.int32, device=self.backend.device)
+                sums, counts = self._zero_sums(self.backend, n_channels)
             dist_utils.all_reduce_sums(sums, counts)
         avg, summed, cnt = self.backend.finalize_sums(sums, counts)
         avg, summed, cnt = _to_host(avg), _to_host(summed), _to_host(cnt)
         if single_view:
             # the reference keeps the first projection as is (meshes.py:2057-2058): a NaN channel of a seen face survives
-            summed = first.astype(float)
+            summed = projections[0].astype(float)
             summed[cnt == 0] = np.nan
             with np.errstate(divide="ignore", invalid="ignore"):
                 avg = np.divide(summed, np.expand_dims(cnt, 1))
         info = {"projection_counts": cnt, "summed_projections": summed}
         if return_all:
-            info["all_projections"] = all_projections
+            info["all_projections"] = projections
         return avg, info
+
+    def _zero_sums(self, backend, n_channels):
+        torch, n_faces = _torch(), self.faces.shape[0]
+        return (torch.zeros((n_faces, n_channels), dtype=torch.float64, device=backend.device),
+                torch.zeros((n_faces,), dtype=torch.int32, device=backend.device))
+
+    def _nansum_views(self, backend, views):
+        """The per-view recurrence of the float path (meshes.py:2057-2067) on ONE backend: `views` yields (ids, image or None
+        for a null image, n_channels); returns that device's (sums (F,C) float64, counts (F,) int32, n_channels), all None
+        without a view."""
+        sums = counts = n_channels = None
+        for ids, img, n_channels in views:
+            if sums is None:
+                sums, counts = self._zero_sums(backend, n_channels)
+            if img is not None:
+                backend.project_values(ids, img, sums, counts, neg1_is_last_face=self.neg1_is_last_face)
+            else:
+                # a skipped (null) image still passes through np.nansum([summed, all-NaN projection]) in the reference
+                # (meshes.py:2060-2062), which drops a NaN of the running sum (+inf met -inf) like every other view does
+                _torch().nan_to_num_(sums, nan=0.0, posinf=float("inf"), neginf=float("-inf"))
+        return sums, counts, n_channels
 
     def _aggregate_label_views(self, backend, cameras, inds, mesh, C, label_fn, labels_known, batch_size, aggregate_img_scale,
                                loader_threads, fused_ok, kwargs, progress=True, own_stream=False):
@@ -902,12 +880,7 @@ class TexturedPhotogrammetryMesh:
         from concurrent.futures import ThreadPoolExecutor
 
         on_gpu = backend.device.type == "cuda"
-        stream_ctx = contextlib.nullcontext()
-        if on_gpu:
-            torch.cuda.set_device(backend.device)   # the current device is a property of the host thread
-            if own_stream:   # contexts that share a device would otherwise queue on its one default stream
-                stream_ctx = torch.cuda.stream(torch.cuda.Stream(backend.device))
-        with stream_ctx:
+        with _driving(backend, own_stream):
             self._ensure_uploaded(mesh, backend)
             votes, counts = backend.new_vote_buffers(C)
             if len(inds) == 0:
@@ -988,9 +961,7 @@ class TexturedPhotogrammetryMesh:
                         if tuple(ids.shape[-2:]) != (h0, w0):
                             raise ValueError(f"pix2face returned {tuple(ids.shape[-2:])} ids for {(h0, w0)} label images")
                         backend.project_labels(ids, lab, C, votes, counts, neg1_is_last_face=self.neg1_is_last_face)
-            if on_gpu and own_stream:
-                torch.cuda.current_stream(backend.device).synchronize()   # the partial is complete when the thread hands it back
-        return votes, counts
+            return votes, counts
 
     # the north star's name for the same method
     aggregate_viewpoints = aggregate_projected_images
@@ -1328,6 +1299,30 @@ class TexturedPhotogrammetryMesh:
 
 _FUSED_KWARGS = ("near", "principal_point", "focal_scaling")
 _PIX2FACE_KWARGS = _FUSED_KWARGS + ("mesh", "save_to_cache", "cache_folder", "distortion_set", "apply_distortion")
+
+
+@contextlib.contextmanager
+def _driving(backend, own_stream=False):
+    """This host thread drives `backend` inside the block: the backend's device is the thread's current one (a property of the
+    host thread) and, with `own_stream`, the work goes to a stream of its own -- contexts that share a device would otherwise
+    queue on its one default stream --, which is complete when the block ends: the thread hands a finished partial back."""
+    torch = _torch()
+    on_gpu = backend.device.type == "cuda"
+    if on_gpu:
+        torch.cuda.set_device(backend.device)
+    with torch.cuda.stream(torch.cuda.Stream(backend.device)) if on_gpu and own_stream else contextlib.nullcontext():
+        yield
+        if on_gpu and own_stream:
+            torch.cuda.current_stream(backend.device).synchronize()
+
+
+def _add_on_first(parts):
+    """Per-device partials (tuples of tensors, in device order) added onto the first one, on its device (peer copies)."""
+    total = parts[0]
+    for part in parts[1:]:
+        for t, p in zip(total, part):
+            t += p.to(t.device)
+    return total
 
 
 def _raster_kwargs(kwargs: dict) -> dict:

@@ -222,6 +222,11 @@ int gr_raster_overflow_causes(const gr_ctx *ctx);
 int gr_gather_texture_f64(gr_ctx *ctx, const int32_t *ids, int64_t n_pix, const double *face_tex, int64_t F, int C,
                           double *out, void *stream);
 
+/* The five gr_project_* calls below share their order of checks -- context and shape (GR_EINVAL), an uploaded mesh
+ * (GR_ENOMESH), then the call's own arguments (GR_EINVAL); n_views == 0 is GR_OK behind all of them -- and their protocol:
+ * the views are taken in launch groups of up to 64, per group one winner pass over the id images (per view the LAST pixel,
+ * row-major, of each face wins), then the call's own pass over the winners. */
+
 /* project_images + aggregate step for index labels -- replaces meshes.py:1987-2002 and 2057-2067 for the
  * one-hot label images of cameras/segmentor.py:33-42 + predictors/segmentor.py:37-69.
  * ids: n_views x h x w int32; labels: n_views x h x w uint8 class indices (>= C: all-zero one-hot row, still an

@@ -4,6 +4,7 @@ materialised path (the same segmentor's per-pixel image through `gr_project_inde
 derived_meshes.py:470-550 on oracle ids."""
 import numpy as np
 import pytest
+import torch
 
 from geograypher_amd.cameras import SegmentorPhotogrammetryCameraSet
 from geograypher_amd.cameras.cameras import vtk_like_near_planes
@@ -226,3 +227,38 @@ def test_tin_detections(hip, tmp_path):
     slow = _aggregate(mesh, cams, _PerPixel(seg), nc, 0.25)
     _assert_same(fast, slow)
     _check_oracle(fast[1], _oracle(points, faces, cams, seg, nc, 0.25, True), nc)
+
+
+@pytest.mark.parametrize("n", [65, 130])
+def test_views_beyond_one_launch_group(hip, n):
+    """More views than a launch group holds (64): from the second group on the kernel reads its views' rectangles at
+    rect_offsets + 64 k.  Drawn ids over 300 degenerate faces, 0-3 small rectangles per view; keys, multiplicities and counts
+    must equal `project_index_pairs` on the painted label images."""
+    rng = np.random.default_rng(7000 + n)
+    F, h, w, nc = 300, 9, 13, 6
+    hip.upload_mesh(np.zeros((3, 3), dtype=np.float32), np.zeros((F, 3), dtype=np.int32))
+    ids = rng.integers(-1, F, (n, h, w)).astype(np.int32)
+    rects, offsets, area = [], [0], 0
+    painted = np.full((n, h, w), np.nan)
+    for v in range(n):
+        for _ in range(int(rng.integers(0, 4))):
+            i0, j0 = int(rng.integers(0, h)), int(rng.integers(0, w))
+            i1, j1 = min(h, i0 + int(rng.integers(1, 6))), min(w, j0 + int(rng.integers(1, 6)))
+            cls = int(rng.integers(0, nc))
+            rects.append((i0, j0, i1, j1, cls))
+            painted[v, i0:i1, j0:j1] = cls  # in paint order: a later rectangle overwrites an earlier one
+            area += (i1 - i0) * (j1 - j0)
+        offsets.append(len(rects))
+    per_view = np.diff(offsets)
+    assert per_view.min() == 0 and per_view.max() == 3 and per_view[64:].sum() > 0
+    assert np.isfinite(painted).sum() < area  # some rectangles overlap
+    rects = np.array(rects, dtype=np.int32).reshape(-1, 5)
+    got_counts = torch.zeros((F,), dtype=torch.int32, device=hip.device)
+    acc = hip.new_pair_accumulator(nc, got_counts)
+    acc.add_rects(ids, rects, np.array(offsets))
+    got_keys, got_mult = acc.finish()
+    want_counts = torch.zeros((F,), dtype=torch.int32, device=hip.device)
+    want_keys, want_mult = hip.project_index_pairs(ids, painted, nc, want_counts)
+    assert want_keys.size > 0 and want_mult.max() > 1
+    assert np.array_equal(got_keys, want_keys) and np.array_equal(got_mult, want_mult)
+    assert np.array_equal(got_counts.cpu().numpy(), want_counts.cpu().numpy())
