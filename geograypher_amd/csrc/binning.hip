@@ -1048,6 +1048,11 @@ __global__ __launch_bounds__(64) void k_clip_faces(const float *__restrict__ cam
   const float fe = cam[12], cxp = cam[13], cyp = cam[14], nearp = cam[15];
   if (!(nearp > 0.0f) || !(fe > 0.0f) || !isfinite(fe) || !isfinite(cxp) || !isfinite(cyp)) return;
   constexpr double G = 16383.0;
+  // the guard planes bound the coordinate whose guard snap_vertex tests: s = c + f q / q_z under R1; in the GL order the window
+  // coordinate, win_x = w / 2 + f q_x / q_z and -- rows bottom-up -- win_y = h / 2 - f q_y / q_z: the y planes trade their offsets
+  // (with R1's planes a vertex with -16383 <= s_y <= h - 16384 passed every plane, failed the snap, and its face was dropped)
+  const double ccx = a.gl_order ? 0.5 * (double)a.w : (double)cxp;
+  const double ccy = a.gl_order ? -0.5 * (double)a.h : (double)cyp;
   for (int64_t i = (int64_t)blockIdx.x * 64 + tid; i < n_clip; i += (int64_t)gridDim.x * 64) {
     const int64_t f = a.clip[(int64_t)slot * a.F + i];
     const float *sp = a.soup + 9 * f;
@@ -1070,8 +1075,7 @@ __global__ __launch_bounds__(64) void k_clip_faces(const float *__restrict__ cam
       // plane pl:  a x + b y + c z + d >= 0   (near plane, then sx <= G, sx >= -G, sy <= G, sy >= -G)
       const double pa = pl == 1 ? -(double)fe : pl == 2 ? (double)fe : 0.0;
       const double pb = pl == 3 ? -(double)fe : pl == 4 ? (double)fe : 0.0;
-      const double pc = pl == 0 ? 1.0 : pl == 1 ? G - (double)cxp : pl == 2 ? G + (double)cxp : pl == 3 ? G - (double)cyp
-                                                                                                        : G + (double)cyp;
+      const double pc = pl == 0 ? 1.0 : pl == 1 ? G - ccx : pl == 2 ? G + ccx : pl == 3 ? G - ccy : G + ccy;
       const double pd = pl == 0 ? -(double)nearp : 0.0;
       const double plane[4] = {pa, pb, pc, pd};
       if (n == 0 || bad) break;

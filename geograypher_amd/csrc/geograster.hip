@@ -411,7 +411,10 @@ int gr_set_option(gr_ctx *c, int key, int value) {
       c->opt_lds_pad = value; return GR_OK;
     case GR_OPT_DIRECT_CAP:
       if (value < 0 || value > 65536) return fail(c, GR_EINVAL, "slots per tile must be in [0, 65536]");
-      c->opt_direct_cap = value; c->direct_ok = true; c->n_learned = 0; c->share_learned = false; return GR_OK;
+      // forgets what the context learned -- the record planes a call with many clipped faces asked for included: that need
+      // belonged to one mesh and its views, and left standing it decides whether a later, smaller mesh sees its own retry
+      c->opt_direct_cap = value; c->direct_ok = true; c->n_learned = 0; c->share_learned = false; c->rec_cap_request = 0;
+      return GR_OK;
     case GR_OPT_SHARE_LEARNED:
       c->share_learned = value != 0; return GR_OK;
     case GR_OPT_VERTEX_ORDER:

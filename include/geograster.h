@@ -138,7 +138,8 @@ enum {
                                which R1 and llvmpipe differ; the rest are faces llvmpipe clips at the image border:
                                profiles/r06_gl_residue.txt).  With 1 the library differs from llvmpipe on 14 of the 12 000 000 pixels
                                of a C2 view.  The principal point must be the window centre (cxp = w / 2, cyp = h / 2: the pyvista
-                               camera of cameras.py:446-477); results depend on this option by design -- the oracle has the same
+                               camera of cameras.py:446-477), and the guard planes of the clipping (R7) bound the window coordinate,
+                               |window| <= 16383, rows bottom-up, instead of R1's s; results depend on this option by design -- the oracle has the same
                                switch (oracle_raster.c R1-GL) and the parity tests run both                              */
   GR_OPT_DEBUG_LDS = 98,    /* extra dynamic LDS bytes per tile workgroup: lowers occupancy (timing experiments)     */
   GR_OPT_DEBUG = 99         /* test hooks, the OR of GR_DBG_* below (results stay right)                             */

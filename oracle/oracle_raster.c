@@ -202,12 +202,18 @@ static int orc_clip_face(const float *verts, const int32_t *face, const float *c
     if (q[k][2] > nearp) ++front;
   }
   if (front == 0) return 0;
+  /* the guard planes bound the coordinate whose guard the snap tests: s = c + f q / q_z under R1; under R1-GL the window
+   * coordinate, win_x = w / 2 + f q_x / q_z and -- rows bottom-up -- win_y = h / 2 - f q_y / q_z, so the two y planes trade
+   * their offsets.  (Until they did, a vertex with -16383 <= s_y <= h - 16384 was inside every plane and invalid for the
+   * snap, and its face was dropped instead of clipped: found by tests/test_oracle_raster.py's guard scene.) */
+  const double ccx = orc_vertex_order ? 0.5 * (double)orc_w : (double)cxp;
+  const double ccy = orc_vertex_order ? -0.5 * (double)orc_h : (double)cyp;
   const double planes[5][4] = {
       {0.0, 0.0, 1.0, -(double)nearp},
-      {-(double)fe, 0.0, ORC_CLIP_G - (double)cxp, 0.0},
-      {(double)fe, 0.0, ORC_CLIP_G + (double)cxp, 0.0},
-      {0.0, -(double)fe, ORC_CLIP_G - (double)cyp, 0.0},
-      {0.0, (double)fe, ORC_CLIP_G + (double)cyp, 0.0},
+      {-(double)fe, 0.0, ORC_CLIP_G - ccx, 0.0},
+      {(double)fe, 0.0, ORC_CLIP_G + ccx, 0.0},
+      {0.0, -(double)fe, ORC_CLIP_G - ccy, 0.0},
+      {0.0, (double)fe, ORC_CLIP_G + ccy, 0.0},
   };
   orc_p3 a[8], b[8];
   int n = 3;

@@ -188,3 +188,108 @@ def test_float_path_drops_a_running_nan_like_the_reference(kind, request, null_l
     np.testing.assert_array_equal(info["projection_counts"], want["projection_counts"])
     np.testing.assert_allclose(info["summed_projections"], want["summed_projections"], rtol=1e-12, equal_nan=True)
     np.testing.assert_allclose(avg, want_avg, rtol=1e-12, equal_nan=True)
+
+
+# ---- vertex_order="gl" through the mesh class -------------------------------------------------------------------------------------
+def _gl_label_views(points, faces, cams, C):
+    from geograypher_amd.cameras import SegmentorPhotogrammetryCameraSet
+    from geograypher_amd.predictors import ArrayLabelSegmentor
+
+    h, w = cams[0].get_image_size(1.0)
+    recs = cams.get_raster_records(1.0, near=0.05)
+    labels = [synthetic.synthetic_labels(oracle_c.raster(points, faces, recs[v], h, w), v, C) for v in range(len(cams))]
+    seg = ArrayLabelSegmentor(labels, C, filenames=[c.image_filename for c in cams.cameras])
+    return SegmentorPhotogrammetryCameraSet(cams, seg), labels
+
+
+def _same_aggregate(got, want):
+    np.testing.assert_array_equal(np.nan_to_num(got[0], nan=-7.0), np.nan_to_num(want[0], nan=-7.0))
+    np.testing.assert_array_equal(got[1]["projection_counts"], want[1]["projection_counts"])
+    np.testing.assert_array_equal(np.nan_to_num(got[1]["summed_projections"], nan=-7.0),
+                                  np.nan_to_num(want[1]["summed_projections"], nan=-7.0))
+
+
+def test_mesh_in_gl_vertex_order_equals_the_oracle_pipeline_in_gl_order(oracle_backend_cls):
+    """TexturedPhotogrammetryMesh(vertex_order="gl"): pix2face is the oracle's picture in GL order under the mesh's own near
+    planes, the label aggregation is oracle_np's of those pictures; both differ from what an "r1" mesh gives."""
+    from geograypher_amd.cameras.cameras import vtk_like_near_planes
+
+    points, faces, cams, _, _ = _scene(3)
+    scale, C, F = 1.0, 4, faces.shape[0]      # at full size the two orders differ on C1 (at a quarter they do not)
+    h, w = cams[0].get_image_size(scale)
+    mesh = TexturedPhotogrammetryMesh((points, faces), backend=oracle_backend_cls(), log_level="ERROR", vertex_order="gl")
+    r1 = TexturedPhotogrammetryMesh((points, faces), backend=oracle_backend_cls(), log_level="ERROR")
+    lo, hi = points.min(axis=0), points.max(axis=0)
+    nears = vtk_like_near_planes(np.stack([np.asarray(c.cam_to_world_transform, dtype=np.float64) for c in cams.cameras]),
+                                 np.array([lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]]))
+    recs = cams.get_raster_records(scale, near=list(nears))
+    want = np.stack([oracle_c.raster(points, faces, recs[v], h, w, vertex_order="gl") for v in range(3)])
+    got = mesh.pix2face(cams, render_img_scale=scale, apply_distortion=False)
+    np.testing.assert_array_equal(got, want)
+    assert (got != r1.pix2face(cams, render_img_scale=scale, apply_distortion=False)).sum() > 0
+    views, labels = _gl_label_views(points, faces, cams, C)
+    avg, info = mesh.aggregate_projected_images(views, aggregate_img_scale=scale)
+    projs = [oracle_np.project_image(want[v].astype(np.int64), oracle_np.inds_to_one_hot(labels[v], C).astype(float), F)
+             for v in range(3)]
+    want_avg, want_info = oracle_np.aggregate(projs, F)
+    _same_aggregate((avg, info), (want_avg, want_info))
+    assert want_info["projection_counts"].max() > 1
+
+
+def test_two_meshes_of_different_vertex_order_share_one_backend(oracle_backend_cls):
+    """_apply_vertex_order: a "gl" mesh and an "r1" mesh on ONE backend, used alternately -- each call runs in its mesh's order."""
+    points, faces, cams, h, w = _scene(2)
+    shared = oracle_backend_cls()
+    gl = TexturedPhotogrammetryMesh((points, faces), backend=shared, log_level="ERROR", vertex_order="gl")
+    r1 = TexturedPhotogrammetryMesh((points, faces), backend=shared, log_level="ERROR", vertex_order="r1")
+    want_gl = TexturedPhotogrammetryMesh((points, faces), backend=oracle_backend_cls(), log_level="ERROR",
+                                         vertex_order="gl").pix2face(cams, render_img_scale=1.0, apply_distortion=False)
+    want_r1 = TexturedPhotogrammetryMesh((points, faces), backend=oracle_backend_cls(),
+                                         log_level="ERROR").pix2face(cams, render_img_scale=1.0, apply_distortion=False)
+    assert (want_gl != want_r1).sum() > 0
+    for _ in range(2):
+        np.testing.assert_array_equal(gl.pix2face(cams, render_img_scale=1.0, apply_distortion=False), want_gl)
+        assert shared.vertex_order == "gl"
+        np.testing.assert_array_equal(r1.pix2face(cams, render_img_scale=1.0, apply_distortion=False), want_r1)
+        assert shared.vertex_order == "r1"
+
+
+def test_vertex_order_arguments_are_validated(oracle_backend_cls):
+    points, faces, cams, h, w = _scene(1)
+    gl = TexturedPhotogrammetryMesh((points, faces), backend=oracle_backend_cls(), log_level="ERROR", vertex_order="gl")
+    with pytest.raises(ValueError, match="principal_point"):
+        gl.pix2face(cams, render_img_scale=0.25, apply_distortion=False, principal_point="intrinsics")
+    with pytest.raises(ValueError, match="vertex_order"):
+        TexturedPhotogrammetryMesh((points, faces), backend=oracle_backend_cls(), log_level="ERROR", vertex_order="opengl")
+
+    class NoSwitch:
+        """a backend from before the switch: no vertex_order, no set_vertex_order"""
+
+    with pytest.raises(NotImplementedError, match="vertex_order"):
+        TexturedPhotogrammetryMesh((points, faces), backend=NoSwitch(), log_level="ERROR", vertex_order="gl").backend
+    assert isinstance(TexturedPhotogrammetryMesh((points, faces), backend=NoSwitch(), log_level="ERROR").backend, NoSwitch)
+
+
+@pytest.mark.gpu
+def test_mesh_in_gl_vertex_order_on_two_contexts_equals_one(hip, oracle_backend_cls):
+    """devices=[0, 0] with vertex_order="gl": the order is applied to every device's context -- pix2face and the label
+    aggregation equal the single-device mesh's and the oracle pipeline's in GL order."""
+    (points, faces), cams = synthetic.config1_scene()
+    sub = cams[0:4]
+    views, _ = _gl_label_views(points, faces, sub, 4)
+    kw = dict(log_level="ERROR", vertex_order="gl")
+    want = TexturedPhotogrammetryMesh((points, faces), backend=oracle_backend_cls(), **kw)
+    one = TexturedPhotogrammetryMesh((points, faces), backend=hip, **kw)
+    two = TexturedPhotogrammetryMesh((points, faces), devices=[0, 0], **kw)
+    r1 = TexturedPhotogrammetryMesh((points, faces), backend=oracle_backend_cls(), log_level="ERROR")
+    try:
+        want_ids = want.pix2face(sub, render_img_scale=0.5, apply_distortion=False)
+        np.testing.assert_array_equal(one.pix2face(sub, render_img_scale=0.5, apply_distortion=False), want_ids)
+        np.testing.assert_array_equal(two.pix2face(sub, render_img_scale=0.5, apply_distortion=False), want_ids)
+        assert (want_ids != r1.pix2face(sub, render_img_scale=0.5, apply_distortion=False)).sum() > 0
+        want_agg = want.aggregate_projected_images(views, aggregate_img_scale=0.5)
+        for mesh in (one, two):
+            _same_aggregate(mesh.aggregate_projected_images(views, aggregate_img_scale=0.5), want_agg)
+        assert len(two.backends) == 2 and all(b.vertex_order == "gl" for b in two.backends)
+    finally:
+        hip.set_vertex_order("r1")

@@ -11,6 +11,7 @@ from geograypher_amd.meshes import TexturedPhotogrammetryMesh
 from geograypher_amd.predictors import ArrayLabelSegmentor
 from geograypher_amd.utils import synthetic
 from oracle import oracle_c, oracle_np
+from tests import raster_scenes
 
 pytestmark = pytest.mark.gpu
 
@@ -76,28 +77,7 @@ def test_faces_centred_on_tile_corners_through_the_93_pixel_boundary(hip, varian
     slots), on vertical and on horizontal tile borders, at many orientations and depths, overlapping: ids and depth bits equal
     the oracle's with 40-byte entries (a face of 93 px and more makes the call fall back by itself), 48-byte entries and micro
     lists."""
-    rng = np.random.default_rng(93)
-    h, w, f = 448, 640, 500.0
-    pts, fcs = [], []
-    k = 0
-    for size in list(range(1, 20)) + list(range(20, 131, 3)) + [91, 92, 93, 94, 95]:
-        for rep in range(3):
-            cx = 64.0 * rng.integers(1, 9) + (rng.random() - 0.5) * (0.0 if rep == 0 else 0.4 * size)
-            cy = 32.0 * rng.integers(1, 13) + (rng.random() - 0.5) * (0.0 if rep == 1 else 0.4 * size)
-            ang = rng.random(3) * 0.6 + np.array([0.0, 2.1, 4.2]) + rng.random() * 6.28
-            r = 0.5 * size * (0.6 + 0.4 * rng.random(3))
-            z = 8.0 + 4.0 * rng.random(3)      # camera-space depth of each corner: tilted faces, overlapping in depth
-            px = cx + r * np.cos(ang) * (1.6 if rep == 2 else 1.0)
-            py = cy + r * np.sin(ang) * (0.4 if rep == 2 else 1.0)
-            for i in range(3):     # pinhole at the origin looking down -z ... the record maps (x, y, z) -> (f x / z + cx0, f y / z + cy0)
-                pts.append([(px[i] - 0.5 * w) * z[i] / f, (py[i] - 0.5 * h) * z[i] / f, z[i]])
-            fcs.append([k, k + 1, k + 2])
-            k += 3
-    points = np.asarray(pts, dtype=np.float64)
-    faces = np.asarray(fcs, dtype=np.int64)
-    rec = np.zeros((1, 16), dtype=np.float32)      # identity rotation, camera at the origin: q = p
-    rec[0, [0, 4, 8]] = 1.0
-    rec[0, 12], rec[0, 13], rec[0, 14], rec[0, 15] = f, 0.5 * w, 0.5 * h, 0.05
+    points, faces, rec, h, w = raster_scenes.boundary_93_scene()
     hip.set_option(_hip.GR_OPT_VARIANT, variant)
     try:
         ids = _check_views(hip, points, faces, rec, h, w, depth=True)
@@ -159,17 +139,14 @@ def test_face_order_does_not_matter(hip):
     flat = points.copy()
     flat[:, 2] = 0.0
     _check_views(hip, flat, shuffled, recs, 480, 640)
-    broken = np.vstack([points, [[np.nan, 0.0, 0.0], [np.inf, 1.0, 2.0], [0.0, -np.inf, 0.0]]])
-    extra = np.array([[0, 1, len(points)], [2, len(points) + 1, 3], [len(points) + 2, 4, 5]], dtype=faces.dtype)
-    _check_views(hip, broken, np.vstack([shuffled, extra]), recs, 480, 640)
+    broken, with_extra = raster_scenes.broken_vertices_scene(points, shuffled)
+    _check_views(hip, broken, with_extra, recs, 480, 640)
 
 
 @pytest.mark.parametrize("scale", [0.25, 0.37, 1.0])
 def test_ragged_sizes_and_scales(hip, scale):
     """h, w not multiples of the 64-pixel tile, and the int(H*s) truncation of cameras.py:179-200."""
-    (points, faces), cams = synthetic.config1_scene()
-    for c in cams.cameras:
-        c.image_width, c.image_height, c.image_size = 613, 457, (457, 613)
+    (points, faces), cams = raster_scenes.ragged_cameras()
     h, w = cams[0].get_image_size(scale)
     _check_views(hip, points, faces, _records(cams, scale), h, w)
 
@@ -179,19 +156,7 @@ def test_tile_sized_faces_many_tiles_per_wave(hip, pitch):
     """Faces about as large as a tile: the 64 faces of one wave of the set-up kernel touch more distinct tiles than the wave
     has lanes (the joint tile grouping hands one tile to each lane and takes the rest one by one), and small faces (at
     most 2x2 tiles, binned by k_setup_cull) mix with big ones (k_bin_big) in the same blocks."""
-    nx, ny = 24, 24
-    xs, ys = np.meshgrid(np.arange(nx + 1), np.arange(ny + 1))
-    rng = np.random.default_rng(int(pitch * 10))
-    z = rng.uniform(0.0, 0.4, xs.shape)
-    f = 300.0
-    height = 30.0
-    step = pitch * 64.0 * height / f  # world size of a cell that projects to `pitch` tile widths
-    points = np.stack([(xs - nx / 2) * step + 0.013, (ys - ny / 2) * step * 0.5 + 0.007, z], axis=-1).reshape(-1, 3)
-    idx = lambda i, j: j * (nx + 1) + i
-    faces = np.array([[idx(i, j), idx(i + 1, j), idx(i + 1, j + 1)] for j in range(ny) for i in range(nx)] +
-                     [[idx(i, j), idx(i + 1, j + 1), idx(i, j + 1)] for j in range(ny) for i in range(nx)])
-    poses = [synthetic.nadir_pose(0.0, 0.0, height), synthetic.nadir_pose(3.0, -2.0, height, yaw_deg=23.0)]
-    cams = synthetic.camera_set_from_poses(poses, f=f, width=1600, height=900)
+    points, faces, cams = raster_scenes.tile_sized_faces_scene(pitch)
     _check_views(hip, points, faces, _records(cams), 900, 1600)
 
 
@@ -200,20 +165,7 @@ def test_triangle_soup_occlusion_degenerates_behind_camera(hip, seed):
     """Random overlapping triangles of every size: sub-pixel slivers, triangles larger than a tile (64-bit edge path),
     coincident depths, zero-area faces, faces behind / straddling the camera plane (the large ones among the latter pass
     right in front of the lens and cover most of the picture once they are clipped instead of dropped)."""
-    rng = np.random.default_rng(seed)
-    n = 3000
-    centers = rng.uniform(-30, 30, (n, 1, 3)) * np.array([1, 1, 0.3])
-    size = np.exp(rng.uniform(np.log(0.02), np.log(40.0), (n, 1, 1)))
-    tri = centers + rng.normal(0, 1, (n, 3, 3)) * size
-    tri[:50, :, 2] = 45.0                       # behind the camera (camera at z = 40 looking down)
-    tri[50:100, 0, 2] = 45.0                    # straddling the camera plane -> clipped at the near plane (R7)
-    tri[100:120, 2] = tri[100:120, 1]           # zero area
-    tri[120:140] = tri[140:160]                 # coincident faces: lower id wins
-    points = tri.reshape(-1, 3)
-    faces = np.arange(3 * n).reshape(n, 3)
-    poses = [synthetic.nadir_pose(0, 0, 40.0, yaw_deg=17.0 * seed, tilt_x_deg=3.0 * seed),
-             synthetic.look_at((60, 10, 25), (0, 0, 0), up_hint=(0, 0, 1))]
-    cams = synthetic.camera_set_from_poses(poses, f=300.0, width=333, height=251)
+    points, faces, cams = raster_scenes.degenerate_soup_scene(seed)
     ids = _check_views(hip, points, faces, _records(cams, near=0.5), 251, 333, depth=True)
     assert len(np.unique(ids)) >= 3
 
@@ -223,10 +175,7 @@ def test_clipping_near_plane_and_guard_band(hip):
     behind the camera or far outside the guard band, the clipped faces fill the picture below the horizon, and the
     depth of the bottom-centre pixel is the analytic one.  Then a camera in the middle of a dense terrain (faces pass
     behind and beside the lens at every distance), and a camera whose near plane cuts the C1 plane obliquely."""
-    pts = np.array([[-500, -500, 0], [500, -500, 0], [500, 500, 0], [-500, 500, 0]], dtype=np.float64)
-    quad = np.array([[0, 1, 2], [0, 2, 3]])
-    pose = synthetic.look_at((0.0, 0.0, 2.0), (0.0, 100.0, 2.0), up_hint=(0, 0, 1))
-    cams = synthetic.camera_set_from_poses([pose], f=300.0, width=320, height=240)
+    pts, quad, cams = raster_scenes.ground_plane_scene()
     recs = _records(cams, near=0.1)
     hip.upload_mesh(pts.astype(np.float32), quad.astype(np.int32))
     ids, dep = hip.raster_face_ids(recs, 240, 320, want_depth=True)
@@ -237,11 +186,7 @@ def test_clipping_near_plane_and_guard_band(hip):
     assert rows[0] == 121 and rows[-1] == 239 and (want[121:] >= 0).all() and (want[:120] == -1).all()
     assert abs(wdep[239, 160] - 2.0 * 300.0 / 119.5) < 1e-3
 
-    (points, faces), _ = synthetic.config1_scene()
-    poses = [synthetic.look_at((1.0, 2.0, 0.9), (30.0, 20.0, 0.0), up_hint=(0, 0, 1)),
-             synthetic.look_at((-3.0, 0.5, 0.7), (0.0, 40.0, 5.0), up_hint=(0, 0, 1)),
-             synthetic.nadir_pose(0.0, 0.0, 0.8, tilt_x_deg=70.0)]
-    cams = synthetic.camera_set_from_poses(poses, f=250.0, width=333, height=251)
+    points, faces, cams = raster_scenes.cameras_inside_terrain()
     for near in (0.05, 0.7):
         ids = _check_views(hip, points, faces, _records(cams, near=near), 251, 333, depth=True)
         assert (ids >= 0).mean() > 0.3
@@ -253,26 +198,7 @@ def test_random_stress(hip, seed):
     hundreds to thousands of entries per tile (entry chunks beyond one per thread, single-pass segments overflowing into
     the exact path), edges parallel to the axes (A == 0 / B == 0), faces far larger than the image, cameras inside
     the scene's bounding box, principal points off-centre."""
-    rng = np.random.default_rng(1000 + seed)
-    h, w = [(1, 1), (3, 70), (65, 33), (64, 64), (97, 131), (200, 257)][seed % 6]
-    n = [50, 400, 3000, 9000][seed % 4]
-    if seed % 3 == 0:  # axis-aligned lattice of small quads plus noise-free coordinates -> exact ties and A/B == 0
-        g = int(np.sqrt(n / 2)) + 1
-        xs, ys = np.meshgrid(np.linspace(-3, 3, g + 1), np.linspace(-3, 3, g + 1))
-        points = np.stack([xs.ravel(), ys.ravel(), np.zeros(xs.size)], axis=1)
-        faces = synthetic.grid_faces(g + 1, g + 1)
-    else:
-        centers = rng.uniform(-4, 4, (n, 1, 3)) * np.array([1, 1, 0.2])
-        size = np.exp(rng.uniform(np.log(0.01), np.log(30.0 if seed % 2 else 0.3), (n, 1, 1)))
-        points = (centers + rng.normal(0, 1, (n, 3, 3)) * size).reshape(-1, 3)
-        faces = np.arange(3 * n).reshape(n, 3)
-    z_cam = [6.0, 1.0, 0.05][seed % 3]  # the last one sits inside the scene's bounding box
-    poses = [synthetic.nadir_pose(rng.uniform(-1, 1), rng.uniform(-1, 1), z_cam, yaw_deg=rng.uniform(0, 360),
-                                  tilt_x_deg=rng.uniform(-20, 20), tilt_y_deg=rng.uniform(-20, 20)) for _ in range(3)]
-    cams = synthetic.camera_set_from_poses(poses, f=float(max(h, w)) * rng.uniform(0.3, 2.0), width=w, height=h)
-    for c in cams.cameras:
-        c.cx, c.cy = rng.uniform(-5, 5), rng.uniform(-5, 5)
-    recs = cams.get_raster_records(1.0, near=0.02, principal_point="intrinsics" if seed % 2 else "center")
+    points, faces, recs, h, w = raster_scenes.random_stress_scene(seed)
     _check_views(hip, points, faces, recs, h, w, depth=True)
 
 
@@ -290,9 +216,7 @@ def test_empty_view_and_single_face(hip):
 def test_many_views_in_one_call_cross_batch_boundary(hip, batch):
     """More views than one launch group: results must not depend on the batching."""
     hip.set_option(_hip.GR_OPT_BATCH, batch)
-    (points, faces), cams = synthetic.config1_scene()
-    poses = [synthetic.nadir_pose(3.0 * k - 30, 2.0 * k - 20, 35.0 + k, yaw_deg=11.0 * k) for k in range(70)]
-    cams = synthetic.camera_set_from_poses(poses, f=260.0, width=320, height=200)
+    points, faces, cams = raster_scenes.many_views_scene()
     try:
         _check_views(hip, points, faces, _records(cams), 200, 320)
         # the fused aggregation path runs through the same pipelining
