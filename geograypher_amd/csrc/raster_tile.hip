@@ -73,6 +73,31 @@ __device__ __forceinline__ int lds_idx(int row, int col) {
   return __mul24(row, (1 << TWL) + PAD) + col;
 }
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+// The tile workgroup's only LDS, in 8-byte words: the keys, then 64 16-bit mailbox words per wave (raster_chunk_gather), then
+// one chunk of 64 entries (2.5 KiB of 40-byte ones, 3 KiB of 48-byte ones).  The budget at the top of the file is checked here.
+template <int TWL_, int THL_, int NT_, int PAD_, bool SHORT_>
+struct TileLds {
+  static constexpr int TWL = TWL_, THL = THL_, NT = NT_, PAD = PAD_;
+  static constexpr bool SHORT = SHORT_;
+  static constexpr int TW = 1 << TWL, TH = 1 << THL;
+  static constexpr int NKEYS = (TW + PAD) * TH;
+  static constexpr int NW = NT / 64;
+  static constexpr int NMAIL = NW * 16;  // u64 units: 64 16-bit mailbox words per wave
+  static constexpr int EL = SHORT ? GR_ENT40_BYTES : GR_ENT_BYTES;  // 16-byte pieces of a 64-entry chunk per wave (4 waves): the bytes of an entry
+  static constexpr int WORDS = NKEYS + NMAIL + 64 * EL / 8;
+  static_assert(NT == 256, "the entry copy deals EL 16-byte pieces to each of 4 waves");
+  static_assert(NKEYS % 2 == 0, "the fill stores key pairs");
+  static_assert((NKEYS + NMAIL) % 2 == 0, "the chunk buffer takes 16-byte stores");
+  static_assert(THL != 5 || WORDS * 8 <= 20480, "eight 64 x 32 workgroups per CU: an eighth of its LDS each");
+  // byte offset of wave wv's 64 mailbox words, behind the keys
+  static __device__ __forceinline__ int mailbox(int wv) { return NKEYS * 8 + wv * 128; }
+  // the chunk buffer, behind the mailboxes
+  static __device__ __forceinline__ v4i *chunk(unsigned long long *keys) { return reinterpret_cast<v4i *>(keys + NKEYS + NMAIL); }
+};
+
 // floor(E / m) for an integer edge value E (|E| < 2^23 wherever the result matters) and an edge slope magnitude
 // 0 <= m < 2^15, clamped to [-66, 65] (-67 / 66 with the correction): the scanline solver of the tile kernel.
 //   g = (E + 0.5) * rcp(m) in fp32.  (E + 0.5) / m is never an integer and at least 0.5 / m away from one; the fp32 error
@@ -118,14 +143,6 @@ __device__ __forceinline__ void span_solve(int C0, int C1, int C2, int w3, int w
   xe = a1 > 0 ? xe : hi;
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-// Phase 3 for ONE work item: scanline `q - et` of the entry whose 12 words (e0, e1, e2) the lane holds.
-// The tile kernel is VALU-issue bound (SQ_ACTIVE_INST_VALU: 85 % of the SIMD cycles), so this function is written for
-// instruction count: packed fp32 operands are broadcast by op_sel instead of being copied into register pairs, the
-// 64-bit key is formed in the pair the entry word ~face was read into, an odd span is extended to the LEFT (only the
-// first step has a spare slot, steered to the row's padding key), and the row addresses come from one multiply-add.
 // The fields of an entry the scanline code works with, from either form (store_entry).
 struct EntryView {
   int c0, c1, c2, w3, w4, w5;   // edge constants, slope words
@@ -168,6 +185,11 @@ __device__ __forceinline__ EntryView entry_view(const uint2 s01, const uint2 s23
   return v;
 }
 
+// Phase 3 for ONE work item: scanline `r` of the entry whose fields (`e`: the entry's 12 or 10 words) the lane holds.
+// The tile kernel is VALU-issue bound (SQ_ACTIVE_INST_VALU: 85 % of the SIMD cycles), so this function is written for
+// instruction count: packed fp32 operands are broadcast by op_sel instead of being copied into register pairs, the
+// 64-bit key is formed in the pair the entry word ~face was read into, an odd span is extended to the LEFT (only the
+// first step has a spare slot, steered to the row's padding key), and the row addresses come from one multiply-add.
 template <int TWL, int TH, int PAD>
 __device__ __forceinline__ void raster_item(unsigned long long *keys, const EntryView &e, const int r, const bool live) {
   constexpr int TW = 1 << TWL;
@@ -297,10 +319,12 @@ __device__ __forceinline__ void micro_item(unsigned long long *keys, const int4 
 // item -> entry: an entry that starts inside the batch posts gen | lane | slot into the mailbox of its start slot; the
 // words of the current batch are larger than any stale one (gen grows), and among them the latest start is the largest,
 // so an unsigned prefix maximum over the RAW words carries the right entry to every item lane.
-template <int TWL, int TH, int NW, int PAD, bool SHORT>
+template <typename L>
 __device__ __forceinline__ int raster_chunk_gather(unsigned long long *keys, const int tab_base, const int tab_self, uint32_t &gen,
                                                    const int4 *ent, const int nrows, const int lane,
                                                    const int first_b) {
+  constexpr int TWL = L::TWL, TH = L::TH, NW = L::NW, PAD = L::PAD;
+  constexpr bool SHORT = L::SHORT;
   char *const lds = reinterpret_cast<char *>(keys);
   const int incl = wave_incl_scan(nrows);
   int total = __builtin_amdgcn_readlane(incl, 63);
@@ -338,23 +362,22 @@ __device__ __forceinline__ int raster_chunk_gather(unsigned long long *keys, con
   return (total + 63) >> 6;
 }
 
-// ids-only epilogue.  16-byte stores where the rows allow it: a lane owns 4 consecutive pixels of a row (16 lanes per
-// 64-pixel row, 16 rows per pass); the four low dwords sit 8 bytes apart in LDS (two ds_read2_b32), id = ~low (0 for an
-// empty pixel -> -1).  Images whose width is not a multiple of 4 take one pixel per lane.
 // Stores to the output images are NON-TEMPORAL (global_store ... nt): an image is written once and never read by this kernel, and
 // as ordinary stores its dirty lines sat in L2 and the 256 MB Infinity Cache until the NEXT kernel's traffic pushed them out -- the
 // set-up kernel of the following launch group found the mesh evicted and paid for the write-back (a build of the tile kernel that
 // stores nothing made the SET-UP 15 % faster: profiles/r06_ab/tile_removal_probes.log).  Round 6, builds alternated on one box: C2
 // set-up 4.74 -> 4.23 us per view, ids kernel unchanged; config 5 set-up -6 %, ids kernel -7 %; C2 at 1000 x 750 ids kernel -13 %
 // (profiles/r06_ab/nontemporal_image_stores.log).
-typedef int gr_v4i __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store_ids16(int32_t *dst, const int4 v) {
-  gr_v4i x = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(x, reinterpret_cast<gr_v4i *>(dst));
+  v4i x = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(x, reinterpret_cast<v4i *>(dst));
 }
 template <typename T>
 __device__ __forceinline__ void store_px(T *dst, const T v) { __builtin_nontemporal_store(v, dst); }
 
+// ids-only epilogue.  16-byte stores where the rows allow it: a lane owns 4 consecutive pixels of a row (16 lanes per
+// 64-pixel row, 16 rows per pass); the four low dwords sit 8 bytes apart in LDS (two ds_read2_b32), id = ~low (0 for an
+// empty pixel -> -1).  Images whose width is not a multiple of 4 take one pixel per lane.
 template <int TWL, int TH, int NT, int PAD, bool PLAIN>
 __device__ __forceinline__ void store_ids(const unsigned long long *keys, const BinArgs &a, int32_t *ids_plane, int te,
                                           int px0, int py0) {
@@ -487,19 +510,19 @@ __device__ __forceinline__ void fused_winners(const unsigned long long *keys, co
   }
 }
 
+// The same candidates with a LANE PER COLUMN (round 6; the kernels with micro lists use it): a wave owns TH / 4 consecutive rows of
+// the tile and reads them one row per instruction -- 64 consecutive keys, every key of the tile once (+ one row of the wave below)
+// --; the neighbours to the right and below-left / below-right come from DPP wave shifts (wave_shl:1 / wave_shr:1: GFX9 has them;
+// the lane at the end keeps `old` = 1, "unknown across the tile edge").  What it buys is the ATOMICS: the 64 lanes of one
+// instruction are 64 neighbouring pixels of a row -- in a view of 3-pixel faces some twenty faces next to each other, whose
+// winner words share a few cache lines -- where the form above spreads an instruction over four row pairs and every fourth pixel.
+// A view of micro faces has a candidate every 4.7 pixels and its fused kernel was winner traffic (probes: 3.55 us per C2 view at
+// 1000 x 750, 1.77 with the candidates computed and nothing written, 1.56 without the epilogue): 3.54 -> 2.23 us.  Full-size views
+// (a candidate every 57 pixels) are 2.5 % slower this way and keep the form above.  profiles/r06_ab/fused_epilogue.log
 template <int TWL, int TH, int NT, int PAD, bool EDGE>
 __device__ __forceinline__ void fused_winners_rows(const unsigned long long *keys, const BinArgs &a, uint32_t *__restrict__ win,
                                               uint8_t *__restrict__ mark, int te, int px0, int py0) {
   static_assert(TWL == 6 && NT == 256 && TH % 32 == 0, "a wave per 64-pixel tile row, TH / 4 consecutive rows per wave");
-  // The same candidates with a LANE PER COLUMN (round 6; the kernels with micro lists use it): a wave owns TH / 4 consecutive rows of
-  // the tile and reads them one row per instruction -- 64 consecutive keys, every key of the tile once (+ one row of the wave below)
-  // --; the neighbours to the right and below-left / below-right come from DPP wave shifts (wave_shl:1 / wave_shr:1: GFX9 has them;
-  // the lane at the end keeps `old` = 1, "unknown across the tile edge").  What it buys is the ATOMICS: the 64 lanes of one
-  // instruction are 64 neighbouring pixels of a row -- in a view of 3-pixel faces some twenty faces next to each other, whose
-  // winner words share a few cache lines -- where the form above spreads an instruction over four row pairs and every fourth pixel.
-  // A view of micro faces has a candidate every 4.7 pixels and its fused kernel was winner traffic (probes: 3.55 us per C2 view at
-  // 1000 x 750, 1.77 with the candidates computed and nothing written, 1.56 without the epilogue): 3.54 -> 2.23 us.  Full-size views
-  // (a candidate every 57 pixels) are 2.5 % slower this way and keep the form above.  profiles/r06_ab/fused_epilogue.log
   constexpr int RW = TH / 4;
   const int lane = te & 63;
   const int wv = __builtin_amdgcn_readfirstlane(te >> 6);
@@ -575,14 +598,35 @@ __device__ __forceinline__ void tile_list(const BinArgs &a, const uint32_t *__re
 //   3 scanline items, first chunk   4 later chunks (barriers, loads, staging, items)   5 barrier behind the items
 //   6 epilogue (key reads, id stores / winner atomics)   7 barrier between the tiles of a chain   8 empty-tile path
 #ifdef GR_STAMPS
-struct StampAcc { unsigned long long t, acc[9], t0, r0; };  // t0 / r0: shader clock and 100 MHz real-time clock at the wave's start
-#define GR_STAMP_ARG , StampAcc &sa
-#define GR_STAMP_PASS , sa
-#define GR_STAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); sa.acc[k] += t_ - sa.t; sa.t = t_; } while (0)
+struct StampAcc {
+  unsigned long long t, acc[9], t0, r0;  // t0 / r0: shader clock and 100 MHz real-time clock at the wave's start
+  __device__ __forceinline__ void start() {
+    for (int k = 0; k < 9; ++k) acc[k] = 0;
+    t = t0 = __builtin_amdgcn_s_memtime();
+    r0 = __builtin_amdgcn_s_memrealtime();
+  }
+  __device__ __forceinline__ void stamp(int k) {  // the cycles since the last stamp belong to phase k
+    const unsigned long long t_ = __builtin_amdgcn_s_memtime();
+    acc[k] += t_ - t;
+    t = t_;
+  }
+  __device__ __forceinline__ void flush(const BinArgs &a, int n_tiles, int wv, int lane) const {
+    if (lane == 0 && a.stamps) {  // 1024 slots of 16 words: same-address atomics are served one per 11 ns
+      unsigned long long *st = a.stamps + 16 * ((blockIdx.x * 4 + wv + blockIdx.y * 977) & 1023);
+      for (int k = 0; k < 9; ++k) atomicAdd(&st[k], acc[k]);
+      atomicAdd(&st[12], __builtin_amdgcn_s_memtime() - t0);      // wave lifetime in shader cycles ...
+      atomicAdd(&st[13], __builtin_amdgcn_s_memrealtime() - r0);  // ... and in 10 ns ticks: their ratio x 100 MHz is the clock under load
+      atomicAdd(&st[15], 1ull);                 // waves
+      atomicAdd(&st[14], (unsigned long long)n_tiles);  // tile visits x waves
+    }
+  }
+};
 #else
-#define GR_STAMP_ARG
-#define GR_STAMP_PASS
-#define GR_STAMP(k) do { } while (0)
+struct StampAcc {  // the production build: nothing to keep, nothing to do
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ void stamp(int) {}
+  __device__ __forceinline__ void flush(const BinArgs &, int, int, int) const {}
+};
 #endif
 
 // 16-byte piece q (0 .. 159) of a chunk that holds n (1 .. 64) entries in the short form: the front of the 32-byte parts or the
@@ -591,24 +635,51 @@ __device__ __forceinline__ bool short_piece_needed(uint32_t q, uint32_t n) {
   return (q < 2 * n) | ((q >= 128) & (q < 128 + ((n + 1) >> 1)));  // no short-circuit: one predicate, one branch around the load
 }
 
+// A chunk request, in either entry form.  chunk_pieces: the 16-byte pieces of a view's entry memory from entry `first` on (the
+// memory is laid out for 48-byte entries; the short form packs chunks of 64 40-byte entries at the front of a tile's segment:
+// `first` is then a multiple of 64); chunk_piece_needed: does the chunk of the first min(n, 64) entries hold piece q;
+// row_count_dword: an entry's row count as the low byte of an unaligned dword load (a byte load is zero-extended at once, i.e.
+// waited for at once; the bytes read lie in the tile's segment or the 64 bytes of padding behind the array).
+template <bool SHORT>
+__device__ __forceinline__ const v4i *chunk_pieces(const BinArgs &a, int slot, int64_t first) {
+  const v4i *base = reinterpret_cast<const v4i *>(a.comp + (int64_t)slot * a.ent_cap * GR_ENT_Q);
+  return SHORT ? reinterpret_cast<const v4i *>(reinterpret_cast<const char *>(base) + first * GR_ENT40_BYTES) : base + first * GR_ENT_Q;
+}
+template <bool SHORT>
+__device__ __forceinline__ bool chunk_piece_needed(uint32_t q, uint32_t n) {
+  return SHORT ? short_piece_needed(q, min(n, 64u)) : q < n * GR_ENT_Q;
+}
+typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
+__device__ __forceinline__ uint32_t row_count_dword(const uint8_t *nr8) { return *reinterpret_cast<const u32_unaligned *>(nr8); }
+
+// What a tile kernel is built for, from the kernel's own template parameters: the LDS layout, the epilogue (FUSE: per-face
+// winners; PLAIN: ids in 16-byte stores only; neither: ids and / or depth, any width) and whether tiles have micro lists.
+template <int TWL, int THL, int NT, bool FUSE_, int PAD, bool SHORT, bool PLAIN_, bool MICRO_>
+struct TileForm {
+  using Lds = TileLds<TWL, THL, NT, PAD, SHORT>;
+  static constexpr bool FUSE = FUSE_, PLAIN = PLAIN_, MICRO = MICRO_;
+  static_assert(!(FUSE && PLAIN), "the plain kernel writes ids only");
+  static_assert(SHORT || !MICRO, "micro lists need 40-byte entries");
+};
+
+// The first-chunk request a rolling chain keeps in flight (k_raster_tile_roll): a whole 16-byte tuple + the row count.
+struct ChunkRing { v4i e0; uint32_t n0; };
+
 // One tile: keys in LDS -> chunks of entries -> scanline items -> epilogue.  nr_first / ex: the tile's first chunk (row
 // counts and this lane's 16 bytes of the 3 KiB (2.5 KiB) of entries), requested by the caller -- and waited for by the caller
 // (a chain), or here behind the fill of the key tile (WAIT: one tile per workgroup -- the request's latency overlaps the fill).
 // PLAIN: the ids-only kernel of the usual call -- ids to an image whose rows take 16-byte stores, no depth image: the epilogue's
 // other forms (depth, one pixel per lane) are not in the kernel at all (the cold paths cost the hot one registers and schedule)
-// The four first-chunk requests a rolling chain keeps in flight (k_raster_tile_roll): whole 16-byte tuples + the row counts.
-struct ChunkRing { v4i e0; uint32_t n0; };
-
-template <int TWL, int THL, int NT, bool FUSE, int PAD, bool SHORT, bool WAIT, bool PLAIN, bool ROLL = false, bool MICRO = false>
+// ring: the request a rolling chain (ROLL) has in flight for the next tile, else null; cntm: the tile's micro list (MICRO kernels).
+template <typename K, bool WAIT, bool ROLL>
 __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOut &out, unsigned long long *keys, const int slot,
-                                                const int tile, uint32_t cnt, const int64_t beg, uint32_t nr_first, v4i ex GR_STAMP_ARG,
-                                                ChunkRing *ring = nullptr, uint32_t cntm = 0u) {
-  constexpr int TW = 1 << TWL, TH = 1 << THL;
-  constexpr int NKEYS = (TW + PAD) * TH;
-  constexpr int NW = NT / 64;
-  constexpr int NMAIL = NW * 16;  // u64 units: 64 16-bit mailbox words per wave
-  int4 *ent_lds = reinterpret_cast<int4 *>(keys + NKEYS + NMAIL);
-  v4i *ent_st = reinterpret_cast<v4i *>(ent_lds);
+                                                const int tile, uint32_t cnt, const int64_t beg, uint32_t nr_first, v4i ex, StampAcc &sa,
+                                                ChunkRing *ring, uint32_t cntm) {
+  using L = typename K::Lds;
+  constexpr int TWL = L::TWL, THL = L::THL, NT = L::NT, PAD = L::PAD, TW = L::TW, TH = L::TH, NKEYS = L::NKEYS, NW = L::NW, EL = L::EL;
+  constexpr bool SHORT = L::SHORT, FUSE = K::FUSE, PLAIN = K::PLAIN, MICRO = K::MICRO;
+  v4i *ent_st = L::chunk(keys);
+  int4 *ent_lds = reinterpret_cast<int4 *>(ent_st);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int ROWS_PER_PASS = NT / TW;
@@ -616,7 +687,6 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
   const int64_t plane = (int64_t)slot * P;
   const int tx = tile % a.TX, ty = tile / a.TX;
   const int px0 = tx << TWL, py0 = ty << THL;
-  constexpr int EL = SHORT ? GR_ENT40_BYTES : GR_ENT_BYTES;  // 16-byte pieces of a 64-entry chunk per wave (4 waves): the bytes of an entry
   // the tile's list: the slot's entry memory is laid out for 48-byte entries; the short form packs chunks of 64 40-byte
   // entries at the front of the tile's segment (tile * cap_tile is a multiple of 64 whenever the short form is chosen)
   const int4 *comp = SHORT ? reinterpret_cast<const int4 *>(reinterpret_cast<const char *>(a.comp + slot * a.ent_cap * GR_ENT_Q) + beg * GR_ENT40_BYTES)
@@ -641,7 +711,7 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
       if (gx4 < a.w)
         for (int row = tid >> 4; row < TH && py0 + row < a.h; row += NT / 16)
           store_ids16(out.ids + plane + (int64_t)(py0 + row) * a.w + gx4, make_int4(-1, -1, -1, -1));
-      GR_STAMP(8);
+      sa.stamp(8);
       return;
     }
     const int col = tid & (TW - 1), gx = px0 + col;
@@ -652,10 +722,10 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
         if (out.depth) store_px(out.depth + p, INFINITY);
       }
     }
-    GR_STAMP(8);
+    sa.stamp(8);
     return;
   }
-  const int tab_base = NKEYS * 8 + wv * 128;  // byte offset of the wave's 64 mailbox words, behind the keys
+  const int tab_base = L::mailbox(wv);
   const int tab_self = tab_base + lane * 2;
   {  // fill the tile (16-byte LDS stores): depth 0 | the id background stands for (the waves wipe their mailboxes themselves)
     const int bg = (FUSE && out.compat) ? (int)out.F - 1 : -1;
@@ -671,9 +741,9 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
      // tile: a wait on the memory counter here would wait for the previous tile's stores)
     if (WAIT) asm volatile("" : "+v"(ex), "+v"(nr_first));
     if (!ROLL && lane < EL) ent_st[wv * EL + lane] = ex;   // a rolling chain staged it before it re-used the registers
-    GR_STAMP(1);
+    sa.stamp(1);
     __syncthreads();  // keys filled, chunk visible
-    GR_STAMP(2);
+    sa.stamp(2);
     GR_PRIO_ITEMS();
     // LATER CHUNKS ARE REQUESTED ONE CHUNK AHEAD (round 5).  A tile with more than 64 entries -- every tile of a down-scaled
     // or a hostile view: 3-6 chunks at 1000 x 750 on the terrain, dozens under the forest -- used to load each later chunk and
@@ -681,10 +751,9 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
     // per chunk, 80 % (terrain at quarter scale) to 94 % (forest) of a wave's life (tools/tile_phases.py).  Now the request
     // for chunk c + 1 goes out before chunk c's items are walked and has that whole phase to arrive.  The row counts come as
     // the low byte of an unaligned dword load: a byte load is zero-extended at once, i.e. waited for at once.
-    typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
     auto request_chunk = [&](uint32_t c0, v4i &exn, uint32_t &nrn) {
       if (c0 >= cnt) return;
-      nrn = *reinterpret_cast<const u32_unaligned *>(nr8 + c0 + lane);   // bytes behind the tile's entries: its segment / padding
+      nrn = row_count_dword(nr8 + c0 + lane);   // bytes behind the tile's entries: its segment / padding
       if (lane < EL) {
         const uint32_t qc = wv * EL + lane;  // piece of the chunk
         const uint32_t q = (SHORT ? (c0 >> 1) * 5 : c0 * GR_ENT_Q) + qc;
@@ -694,9 +763,9 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
     uint32_t nrn = 0u;
     request_chunk(64u, ex, nrn);
     const int nrows = (uint32_t)lane < cnt ? (int)nr_first : 0;
-    const int nb = raster_chunk_gather<TWL, TH, NW, PAD, SHORT>(keys, tab_base, tab_self, gen, ent_lds, nrows, lane, rot);
+    const int nb = raster_chunk_gather<L>(keys, tab_base, tab_self, gen, ent_lds, nrows, lane, rot);
     rot = (rot - nb) & (NW - 1);
-    GR_STAMP(3);
+    sa.stamp(3);
 #pragma unroll 1
     for (uint32_t c0 = 64; c0 < cnt; c0 += 64) {
       GR_PRIO_MEM();
@@ -707,9 +776,9 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
       request_chunk(c0 + 64u, ex, nrn);   // into the registers just staged: in flight through this chunk's items
       __syncthreads();
       GR_PRIO_ITEMS();
-      const int nbc = raster_chunk_gather<TWL, TH, NW, PAD, SHORT>(keys, tab_base, tab_self, gen, ent_lds, nrows_c, lane, rot);
+      const int nbc = raster_chunk_gather<L>(keys, tab_base, tab_self, gen, ent_lds, nrows_c, lane, rot);
       rot = (rot - nbc) & (NW - 1);
-      GR_STAMP(4);
+      sa.stamp(4);
     }
   }
   if (SHORT && MICRO && cntm > 0) {
@@ -734,7 +803,7 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
   if (ROLL) asm volatile("" : "+v"(ring->e0), "+v"(ring->n0));
   __syncthreads();              // keys complete
   if (GR_PRIO_E != GR_PRIO_M) __builtin_amdgcn_s_setprio(GR_PRIO_E);
-  GR_STAMP(5);
+  sa.stamp(5);
   if (FUSE) {
     uint32_t *win = out.winner + slot * out.F;
     uint8_t *mark = out.touched ? out.touched + slot * out.tb : nullptr;
@@ -765,7 +834,7 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
       }
   }
   if (GR_PRIO_E != GR_PRIO_M) __builtin_amdgcn_s_setprio(GR_PRIO_M);
-  GR_STAMP(6);
+  sa.stamp(6);
 }
 
 // K3  the tile kernel.  KT = 4: a workgroup takes four consecutive tiles one after the other.  The four counts are read
@@ -785,38 +854,25 @@ __device__ __forceinline__ void raster_one_tile(const BinArgs &a, const RasterOu
 template <int TWL, int THL, int NT, bool FUSE, int KT, int PAD, bool SHORT, bool PLAIN = false, bool MICRO = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(THL == 5 ? GR_WPE : (FUSE ? 1 : 4), 8)))
 __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile(BinArgs a, RasterOut out) {
-  constexpr int TW = 1 << TWL, TH = 1 << THL;
-  constexpr int NKEYS = (TW + PAD) * TH;
-  constexpr int NW = NT / 64;
-  constexpr int NMAIL = NW * 16;
+  using K = TileForm<TWL, THL, NT, FUSE, PAD, SHORT, PLAIN, MICRO>;
+  using L = typename K::Lds;
   // the kernel's only LDS: keys + 0.5 KiB of mailboxes + one chunk of entries (2.5 or 3 KiB): 8 workgroups/CU for 64 x 32 (top)
-  __shared__ __attribute__((aligned(16))) unsigned long long keys[NKEYS + NMAIL + 64 * (SHORT ? 5 : 6)];
-  static_assert(NT == 256, "the entry copy deals 48 int4 to each of 4 waves");
-  static_assert(NKEYS % 2 == 0 && TH % 32 == 0, "key pairs; two 16-row passes per fused group");
+  __shared__ __attribute__((aligned(16))) unsigned long long keys[L::WORDS];
+  static_assert(L::TH % 32 == 0, "two 16-row passes per fused group");
   static_assert(KT == 1 || KT == 4, "one tile per workgroup, or a chain of four");
   const int slot = blockIdx.y;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-#ifdef GR_STAMPS
   StampAcc sa;
-  for (int k = 0; k < 9; ++k) sa.acc[k] = 0;
-  sa.t = sa.t0 = __builtin_amdgcn_s_memtime();
-  sa.r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  sa.start();
   // one tile per workgroup: the first chunk is requested before the count is known (one round trip less).  A chain waits
   // for the exact requests of its tiles 1 - 3 anyway before it starts: requesting its first tile's chunk early saves
   // nothing there (14.9 us per C2 view either way) and fetches 1.6 MB of stale slots per view -- not done
   const bool spec = KT == 1 && a.cap_tile >= 64;
   const int tile0 = KT * (int)blockIdx.x;
   const int n_tiles = min(KT, a.T - tile0);
-  constexpr int EL = SHORT ? GR_ENT40_BYTES : GR_ENT_BYTES;
+  constexpr int EL = L::EL;
   const uint32_t q = wv * EL + lane;  // this thread's 16-byte piece of a 3 KiB (2.5 KiB) chunk (lanes 0 .. 47 (39) of every wave)
-  // 16-byte pieces of the view's entry memory from entry `first` on, and the number of pieces `n` entries take
-  auto pieces = [&](int64_t first) {
-    const v4i *base = reinterpret_cast<const v4i *>(a.comp + (int64_t)slot * a.ent_cap * GR_ENT_Q);
-    return SHORT ? reinterpret_cast<const v4i *>(reinterpret_cast<const char *>(base) + first * GR_ENT40_BYTES) : base + first * GR_ENT_Q;
-  };
-  auto needed = [](uint32_t q, uint32_t n) { return SHORT ? short_piece_needed(q, min(n, 64u)) : q < n * GR_ENT_Q; };
   uint32_t nr0 = 0, nr1 = 0, nr2 = 0, nr3 = 0;
   v4i ex0, ex1, ex2, ex3;  // whole 16-byte register tuples (the wait macro of raster_one_tile names them as such: with the
                            // components of an int4 struct named one by one the compiler split the tuples after the load -- and
@@ -824,7 +880,7 @@ __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile(BinArgs a, Rast
   if (spec) {
     const int64_t seg = (int64_t)tile0 * a.cap_tile;
     nr0 = a.nrow8[slot * a.ent_cap + seg + lane];
-    if (lane < EL) ex0 = pieces(seg)[q];
+    if (lane < EL) ex0 = chunk_pieces<SHORT>(a, slot, seg)[q];
   }
   const uint32_t *ctrl = a.ctrl + slot * a.ctrl_stride;
   // fused projection: a view whose binning did not finish (a tile outgrew its segment, a face missed the 40-byte form) is
@@ -871,44 +927,34 @@ __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile(BinArgs a, Rast
   const int64_t sbase = slot * a.ent_cap;
   if (!spec) {  // exact binning (or segments under 64 slots): the first chunk can only be requested now
     if ((uint32_t)lane < cnt0) nr0 = a.nrow8[sbase + beg0 + lane];
-    if ((lane < EL) & needed(q, cnt0)) ex0 = pieces(beg0)[q];
+    if ((lane < EL) & chunk_piece_needed<SHORT>(q, cnt0)) ex0 = chunk_pieces<SHORT>(a, slot, beg0)[q];
   }
   if (KT > 1) {
     if ((uint32_t)lane < cnt1) nr1 = a.nrow8[sbase + beg1 + lane];
-    if ((lane < EL) & needed(q, cnt1)) ex1 = pieces(beg1)[q];
+    if ((lane < EL) & chunk_piece_needed<SHORT>(q, cnt1)) ex1 = chunk_pieces<SHORT>(a, slot, beg1)[q];
     if ((uint32_t)lane < cnt2) nr2 = a.nrow8[sbase + beg2 + lane];
-    if ((lane < EL) & needed(q, cnt2)) ex2 = pieces(beg2)[q];
+    if ((lane < EL) & chunk_piece_needed<SHORT>(q, cnt2)) ex2 = chunk_pieces<SHORT>(a, slot, beg2)[q];
     if ((uint32_t)lane < cnt3) nr3 = a.nrow8[sbase + beg3 + lane];
-    if ((lane < EL) & needed(q, cnt3)) ex3 = pieces(beg3)[q];
+    if ((lane < EL) & chunk_piece_needed<SHORT>(q, cnt3)) ex3 = chunk_pieces<SHORT>(a, slot, beg3)[q];
   }
   // ONE wait for everything requested above, named as whole register tuples and BEFORE the first tile: behind this statement
   // the values are the statement's outputs, not loads in flight, so the compiler's bookkeeping of the (single, in-order)
   // memory counter has nothing left to wait for in the loop over tiles 1 .. 3 -- where a wait means waiting for the
   // previous tile's id stores (tests/test_isa_waits.py)
   if (KT > 1) asm volatile("" : "+v"(ex0), "+v"(ex1), "+v"(ex2), "+v"(ex3), "+v"(nr0), "+v"(nr1), "+v"(nr2), "+v"(nr3));
-  GR_STAMP(0);
-  static_assert(!(FUSE && PLAIN), "the plain kernel writes ids only");
-  raster_one_tile<TWL, THL, NT, FUSE, PAD, SHORT, KT == 1, PLAIN, false, MICRO>(a, out, keys, slot, tile0, cnt0, beg0, nr0, ex0 GR_STAMP_PASS, nullptr, cm0);
+  sa.stamp(0);
+  raster_one_tile<K, KT == 1, false>(a, out, keys, slot, tile0, cnt0, beg0, nr0, ex0, sa, nullptr, cm0);
   if (KT > 1) {
 #pragma unroll 1
     for (int k = 1; k < n_tiles; ++k) {  // ONE copy of the tile code for tiles 1 .. 3: the chunks rotate through ex1
       __syncthreads();                   // every wave has read the previous tile's keys
-      GR_STAMP(7);
-      raster_one_tile<TWL, THL, NT, FUSE, PAD, SHORT, false, PLAIN, false, MICRO>(a, out, keys, slot, tile0 + k, cnt1, beg1, nr1, ex1 GR_STAMP_PASS, nullptr, cm1);
+      sa.stamp(7);
+      raster_one_tile<K, false, false>(a, out, keys, slot, tile0 + k, cnt1, beg1, nr1, ex1, sa, nullptr, cm1);
       cnt1 = cnt2; cnt2 = cnt3; beg1 = beg2; beg2 = beg3; cm1 = cm2; cm2 = cm3;
       nr1 = nr2; nr2 = nr3; ex1 = ex2; ex2 = ex3;
     }
   }
-#ifdef GR_STAMPS
-  if (lane == 0 && a.stamps) {  // 1024 slots of 16 words: same-address atomics are served one per 11 ns
-    unsigned long long *st = a.stamps + 16 * ((blockIdx.x * 4 + wv + blockIdx.y * 977) & 1023);
-    for (int k = 0; k < 9; ++k) atomicAdd(&st[k], sa.acc[k]);
-    atomicAdd(&st[12], __builtin_amdgcn_s_memtime() - sa.t0);      // wave lifetime in shader cycles ...
-    atomicAdd(&st[13], __builtin_amdgcn_s_memrealtime() - sa.r0);  // ... and in 10 ns ticks: their ratio x 100 MHz is the clock under load
-    atomicAdd(&st[15], 1ull);                 // waves
-    atomicAdd(&st[14], (unsigned long long)n_tiles);  // tile visits x waves
-  }
-#endif
+  sa.flush(a, n_tiles, wv, lane);
 }
 
 // K3r  ROLLING chains (round 5).  A chain of four pays its prologue -- two dependent round trips: the tiles' counters, then
@@ -923,27 +969,21 @@ __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile(BinArgs a, Rast
 template <int TWL, int THL, int NT, bool FUSE, int PAD, bool SHORT, bool PLAIN, int KTL, bool MICRO = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(THL == 5 ? GR_WPE : (FUSE ? 1 : 4), 8)))
 __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile_roll(BinArgs a, RasterOut out) {
-  constexpr int TW = 1 << TWL, TH = 1 << THL;
-  constexpr int NKEYS = (TW + PAD) * TH;
-  constexpr int NW = NT / 64;
-  constexpr int NMAIL = NW * 16;
-  __shared__ __attribute__((aligned(16))) unsigned long long keys[NKEYS + NMAIL + 64 * (SHORT ? 5 : 6)];
-  static_assert(NT == 256 && KTL >= 2 && KTL <= 63, "one lane per counter, one more reads as zero");
+  using K = TileForm<TWL, THL, NT, FUSE, PAD, SHORT, PLAIN, MICRO>;
+  using L = typename K::Lds;
+  __shared__ __attribute__((aligned(16))) unsigned long long keys[L::WORDS];
+  static_assert(KTL >= 2 && KTL <= 63, "one lane per counter, one more reads as zero");
   const int slot = blockIdx.y;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-#ifdef GR_STAMPS
   StampAcc sa;
-  for (int k = 0; k < 9; ++k) sa.acc[k] = 0;
-  sa.t = sa.t0 = __builtin_amdgcn_s_memtime();
-  sa.r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  sa.start();
   const int tile0 = KTL * (int)blockIdx.x;
   const int n_tiles = min(KTL, a.T - tile0);
-  constexpr int EL = SHORT ? GR_ENT40_BYTES : GR_ENT_BYTES;
+  constexpr int EL = L::EL;
   const uint32_t q = wv * EL + lane;
-  const v4i *base = reinterpret_cast<const v4i *>(a.comp + (int64_t)slot * a.ent_cap * GR_ENT_Q);
-  auto needed = [](uint32_t qq, uint32_t n) { return SHORT ? short_piece_needed(qq, min(n, 64u)) : qq < n * GR_ENT_Q; };
+  const v4i *base = chunk_pieces<SHORT>(a, slot, 0);   // (kept outside the request: with the slot's base formed per request the
+                                                        // compiler scheduled the three rolling kernels differently)
   const uint32_t *ctrl = a.ctrl + slot * a.ctrl_stride;
   if (FUSE && ctrl[GR_CTRL_OVERFLOW] != 0u) return;
   const uint32_t cap = (uint32_t)a.cap_tile;
@@ -957,26 +997,25 @@ __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile_roll(BinArgs a,
   auto count_at = [&](int tt) { return (uint32_t)__builtin_amdgcn_readlane((int)cvec, tt); };   // tt < 64; lanes >= n_tiles hold 0
   ChunkRing r;
   r.n0 = 0u;
-  typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
   auto request = [&](uint32_t cnt, int64_t beg, v4i &e, uint32_t &n) {
     // The lane's row count as the low byte of an (unaligned) DWORD load, unconditionally (the bytes read lie in the tile's
     // segment or the 64 bytes of padding behind the array; entries beyond the count are never looked at).  Nothing may touch
     // the loaded register before the request is waited for: a byte load is followed by its zero extension at once, a register
     // that is zeroed and then loaded under a mask by a wait for every store in flight -- each a full wait at the tile's start.
-    n = *reinterpret_cast<const u32_unaligned *>(a.nrow8 + sbase + beg + lane);
-    const char *seg = reinterpret_cast<const char *>(base) + beg * (SHORT ? GR_ENT40_BYTES : GR_ENT_BYTES);
-    if ((lane < EL) & needed(q, cnt)) e = *reinterpret_cast<const v4i *>(seg + (q << 4));
+    n = row_count_dword(a.nrow8 + sbase + beg + lane);
+    const char *seg = reinterpret_cast<const char *>(base) + beg * EL;
+    if ((lane < EL) & chunk_piece_needed<SHORT>(q, cnt)) e = *reinterpret_cast<const v4i *>(seg + (q << 4));
   };
   const int64_t beg0 = (int64_t)tile0 * a.cap_tile;
   request(count_at(0), beg0, r.e0, r.n0);
   asm volatile("" : "+v"(r.e0), "+v"(r.n0));
-  GR_STAMP(0);
-  v4i *ent_st = reinterpret_cast<v4i *>(keys + NKEYS + NMAIL);
+  sa.stamp(0);
+  v4i *ent_st = L::chunk(keys);
 #pragma unroll 1
   for (int t = 0; t < n_tiles; ++t) {
     if (t > 0) {
       __syncthreads();                   // every wave has read the previous tile's keys (and is done with its last chunk)
-      GR_STAMP(7);
+      sa.stamp(7);
     }
     // stage the tile's first chunk from the request registers and re-use them at once for the NEXT tile's request
     const uint32_t cnt = count_at(t), cnt1 = count_at(t + 1);
@@ -985,19 +1024,45 @@ __attribute__((amdgpu_num_sgpr(GR_NUM_SGPR))) void k_raster_tile_roll(BinArgs a,
     const uint32_t nr_first = r.n0 & 0xFFu;
     request(cnt1, beg + a.cap_tile, r.e0, r.n0);
     // (the by-value chunk argument is the later chunks' temporary: NOT the request register, which is in flight again)
-    raster_one_tile<TWL, THL, NT, FUSE, PAD, SHORT, false, PLAIN, true, MICRO>(a, out, keys, slot, tile0 + t, cnt, beg, nr_first, v4i{0, 0, 0, 0} GR_STAMP_PASS, &r,
-                                                                                 (uint32_t)__builtin_amdgcn_readlane((int)mvec, t));
+    raster_one_tile<K, false, true>(a, out, keys, slot, tile0 + t, cnt, beg, nr_first, v4i{0, 0, 0, 0}, sa, &r,
+                                    (uint32_t)__builtin_amdgcn_readlane((int)mvec, t));
   }
-#ifdef GR_STAMPS
-  if (lane == 0 && a.stamps) {
-    unsigned long long *st = a.stamps + 16 * ((blockIdx.x * 4 + wv + blockIdx.y * 977) & 1023);
-    for (int kk = 0; kk < 9; ++kk) atomicAdd(&st[kk], sa.acc[kk]);
-    atomicAdd(&st[12], __builtin_amdgcn_s_memtime() - sa.t0);
-    atomicAdd(&st[13], __builtin_amdgcn_s_memrealtime() - sa.r0);
-    atomicAdd(&st[15], 1ull);
-    atomicAdd(&st[14], (unsigned long long)n_tiles);
+  sa.flush(a, n_tiles, wv, lane);
+}
+
+// The tile kernel of a launch, from what tile_batch decided.  The rules:
+//   - the output picks the epilogue: fused winners, PLAIN ids (16-byte stores only), or the general ids / depth form;
+//   - the entry form picks the LDS row padding; micro lists need 40-byte entries (resolve_binning grants them nothing else);
+//   - the schedule is one tile per workgroup, a chain of four, or -- fused, 64 x 32 tiles, single-pass binning (cap_tile > 0:
+//     tile_batch's condition) only -- a rolling chain of GR_ROLL_KT.
+using TileKernel = void (*)(BinArgs, RasterOut);
+
+template <int THL, bool FUSE, bool PLAIN, bool SHORT, bool MICRO>
+TileKernel tile_kernel_scheduled(bool chain, bool roll) {
+  constexpr int PAD = SHORT ? GR_LDS_PAD : GR_LDS_PAD48;
+  if constexpr (FUSE && THL == 5) {
+    if (roll) return k_raster_tile_roll<6, 5, 256, true, PAD, SHORT, false, GR_ROLL_KT, MICRO>;
   }
-#endif
+  if (chain) return k_raster_tile<6, THL, 256, FUSE, 4, PAD, SHORT, PLAIN, MICRO>;
+  return k_raster_tile<6, THL, 256, FUSE, 1, PAD, SHORT, PLAIN, MICRO>;
+}
+
+template <int THL, bool FUSE, bool PLAIN>
+TileKernel tile_kernel_of_entries(bool ent40, bool micro, bool chain, bool roll) {
+  if (!ent40) return tile_kernel_scheduled<THL, FUSE, PLAIN, false, false>(chain, roll);
+  if (micro) return tile_kernel_scheduled<THL, FUSE, PLAIN, true, true>(chain, roll);
+  return tile_kernel_scheduled<THL, FUSE, PLAIN, true, false>(chain, roll);
+}
+
+TileKernel tile_kernel(int thl, bool fused, bool plain, bool ent40, bool micro, bool chain, bool roll) {
+  if (thl == 6) {
+    if (fused) return tile_kernel_of_entries<6, true, false>(ent40, micro, chain, roll);
+    if (plain) return tile_kernel_of_entries<6, false, true>(ent40, micro, chain, roll);
+    return tile_kernel_of_entries<6, false, false>(ent40, micro, chain, roll);
+  }
+  if (fused) return tile_kernel_of_entries<5, true, false>(ent40, micro, chain, roll);
+  if (plain) return tile_kernel_of_entries<5, false, true>(ent40, micro, chain, roll);
+  return tile_kernel_of_entries<5, false, false>(ent40, micro, chain, roll);
 }
 
 }  // namespace
@@ -1042,38 +1107,12 @@ int tile_batch(gr_ctx *c, int nb, int h, int w, int slot0, RasterOut out, hipStr
     // one tile's stores in flight -- a chain of four has up to four.  They keep chains of four.
     const bool roll = chain && a.cap_tile > 0 && a.thl == 5 && out.winner != nullptr;
     const dim3 grid(roll ? (unsigned)((a.T + GR_ROLL_KT - 1) / GR_ROLL_KT) : chain ? (unsigned)((a.T + 3) >> 2) : (unsigned)a.T, nb), block(256);
-    const size_t pad = (size_t)c->opt_lds_pad;
-#define GR_LAUNCH_TILE_M(THL_, FUSE_, PLAIN_, MICRO_)                                                                 \
-  do {                                                                                                                \
-    if (a.ent40) {                                                                                                    \
-      if (chain) GR_LAUNCH_EV(ev_none, ev_stop, (k_raster_tile<6, THL_, 256, FUSE_, 4, GR_LDS_PAD, true, PLAIN_, MICRO_>), grid, block, pad, s, a, out);  \
-      else GR_LAUNCH_EV(ev_none, ev_stop, (k_raster_tile<6, THL_, 256, FUSE_, 1, GR_LDS_PAD, true, PLAIN_, MICRO_>), grid, block, pad, s, a, out);        \
-    } else if (chain) GR_LAUNCH_EV(ev_none, ev_stop, (k_raster_tile<6, THL_, 256, FUSE_, 4, GR_LDS_PAD48, false, PLAIN_, false>), grid, block, pad, s, a, out);  \
-    else GR_LAUNCH_EV(ev_none, ev_stop, (k_raster_tile<6, THL_, 256, FUSE_, 1, GR_LDS_PAD48, false, PLAIN_, false>), grid, block, pad, s, a, out);        \
-  } while (0)
-#define GR_LAUNCH_TILE(THL_, FUSE_, PLAIN_)                                                                           \
-  do {                                                                                                                \
-    if (a.micro) GR_LAUNCH_TILE_M(THL_, FUSE_, PLAIN_, true);                                                         \
-    else GR_LAUNCH_TILE_M(THL_, FUSE_, PLAIN_, false);                                                                \
-  } while (0)
     // the usual ids-only call: rows of whole 16-byte pieces, every view's plane 16-byte aligned, no depth image
     // (variant bit 512: the general ids kernel also where the plain one would run)
     const bool plain = !out.winner && out.ids && !out.depth && (w & 3) == 0 && (reinterpret_cast<uintptr_t>(out.ids) & 15) == 0 &&
                        !(a.var & GR_VAR_GENERAL_IDS);
-    if (roll) {  // fused, 64 x 32 tiles, single-pass binning
-      if (a.ent40 && a.micro) GR_LAUNCH_EV(ev_none, ev_stop, (k_raster_tile_roll<6, 5, 256, true, GR_LDS_PAD, true, false, GR_ROLL_KT, true>), grid, block, pad, s, a, out);
-      else if (a.ent40) GR_LAUNCH_EV(ev_none, ev_stop, (k_raster_tile_roll<6, 5, 256, true, GR_LDS_PAD, true, false, GR_ROLL_KT, false>), grid, block, pad, s, a, out);
-      else GR_LAUNCH_EV(ev_none, ev_stop, (k_raster_tile_roll<6, 5, 256, true, GR_LDS_PAD48, false, false, GR_ROLL_KT, false>), grid, block, pad, s, a, out);
-    } else if (out.winner) {
-      if (a.thl == 6) GR_LAUNCH_TILE(6, true, false);
-      else GR_LAUNCH_TILE(5, true, false);
-    } else if (plain) {
-      if (a.thl == 6) GR_LAUNCH_TILE(6, false, true);
-      else GR_LAUNCH_TILE(5, false, true);
-    } else if (a.thl == 6) GR_LAUNCH_TILE(6, false, false);
-    else GR_LAUNCH_TILE(5, false, false);
-#undef GR_LAUNCH_TILE
-#undef GR_LAUNCH_TILE_M
+    const TileKernel kernel = tile_kernel(a.thl, out.winner != nullptr, plain, a.ent40 != 0, a.micro != 0, chain, roll);
+    GR_LAUNCH_EV(ev_none, ev_stop, kernel, grid, block, (size_t)c->opt_lds_pad, s, a, out);
     c->chain_ev = nullptr;
     c->prof_raster_launches += 1;
   }

@@ -3,7 +3,8 @@
 Loads and stores of a wave share ONE in-order memory counter on gfx950, and the compiler's bookkeeping of it across the loop
 over the tiles of a chain is conservative: with a small change of the source (the form of the chunk requests, a register more
 or less) it puts a wait for an already finished chunk load into the tile loop, where it waits for the previous tile's id
-STORES instead -- 5 % of the kernel, invisible in any functional test (measured in round 3, geograster.hip k_raster_tile).
+STORES instead -- 5 % of the kernel, invisible in any functional test (measured in round 3 on k_raster_tile, which now lives in
+csrc/raster_tile.hip).
 This test compiles the device code to assembly (no GPU needed) and holds the default kernels to the known-good numbers."""
 import re
 import subprocess
