@@ -132,6 +132,7 @@ _SIGNATURES = {
     "gr_gather_texture_u8": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp],
     "gr_project_index_pairs": [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp],
     "gr_project_rect_pairs": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp],
+    "gr_project_polygon_pairs": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp],
     "gr_count_pairs": [_vp, _vp, _i64, _vp, _vp, _i64p, _vp],
     "gr_ray_pairs": [_vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _i64, _i64p, _vp],
     "gr_ray_pairs_tile": [_i64, _i64, _i64p, _i64p],
@@ -248,27 +249,53 @@ class _nullcontext:
         return False
 
 
+POLYGON_RING_CHUNK = 512  # ring records per LDS chunk of gr_project_polygon_pairs (RING_CHUNK, csrc/project.hip)
+
+
+def polygon_pair_bounds(boxes, poly_offsets, n_faces: int) -> np.ndarray:
+    """Upper bound of the pairs each view of a `gr_project_polygon_pairs` call can emit, from the ring table alone (int64,
+    one per view): a face has one winning pixel per view and emits at most one pair per class, so a view with K distinct
+    classes emits at most F * K; a ring can only be hit by a face whose pixel lies in its box, at most min(F, box area)
+    faces, so the view emits at most the sum of that over its rings.  The bound is the smaller of the two."""
+    boxes = np.asarray(boxes, dtype=np.int64).reshape(-1, 5)
+    poly_offsets = np.asarray(poly_offsets, dtype=np.int64).reshape(-1)
+    F = int(n_faces)
+    area = np.clip(boxes[:, 2] - boxes[:, 0], 0, None) * np.clip(boxes[:, 3] - boxes[:, 1], 0, None)
+    per_ring = np.minimum(area, F)
+    out = np.zeros(poly_offsets.shape[0] - 1, dtype=np.int64)
+    for v in range(out.shape[0]):
+        a, b = int(poly_offsets[v]), int(poly_offsets[v + 1])
+        out[v] = min(F * np.unique(boxes[a:b, 4]).size, int(per_ring[a:b].sum()))
+    return out
+
+
 class PairAccumulator:
     """Device-resident pair keys of the sparse index aggregation (derived_meshes.py:470-520).  Every `add` appends the
     keys `face * n_classes + class` of its views to one device buffer through `gr_project_index_pairs` with
     GR_FLAG_DEFER_CHECK (no synchronisation, no per-view sort, no host round trip); `finish` runs ONE radix sort +
     run-length encode over everything (`gr_count_pairs`) and returns (pair_keys, multiplicities) as int64 numpy arrays.
-    A view emits at most one pair per face, so the host knows an upper bound of the fill level without asking the
-    device; when the buffer could overflow it is counted down to its distinct pairs (with their multiplicities, kept on
-    the host) and reused."""
+    A view of `add` / `add_rects` emits at most one pair per face, one of `add_polygons` at most `polygon_pair_bounds`, so
+    the host knows an upper bound of the fill level without asking the device and nothing is ever dropped; when the buffer
+    could overflow it is counted down to its distinct pairs (with their multiplicities, kept on the host) and reused.  A call
+    over the buffer is split by views; a single view over it makes the buffer grow to that view's bound, up to MAX_KEYS
+    (MemoryError beyond).  `cap` (keyword only) sets the buffer's size in keys instead of max(8 F, 2^20)."""
 
-    def __init__(self, backend: "HipRaster", n_classes: int, counts, neg1_is_last_face: bool = True):
+    MAX_KEYS = 1 << 28  # 2 GiB of keys: the most the buffer grows to for a single view
+
+    def __init__(self, backend: "HipRaster", n_classes: int, counts, neg1_is_last_face: bool = True, *, cap=None):
         torch = _torch()
         self.b = backend
         self.n_classes = int(n_classes)
         self.counts = counts
         self.flags = (GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0) | GR_FLAG_DEFER_CHECK
-        self.cap = max(8 * backend.n_faces, 1 << 20)
+        self._fixed_cap = cap is not None
+        self.cap = max(int(cap), 1) if self._fixed_cap else max(8 * backend.n_faces, 1 << 20)
         self.keys = torch.empty((self.cap,), dtype=torch.int64, device=backend.device)
         self.key_count = torch.zeros((2,), dtype=torch.int64, device=backend.device)  # {pair count, error flag} (GR_FLAG_DEFER_CHECK)
         self.bound = 0          # upper bound of the pairs in the buffer
         self.parts = []         # (keys, multiplicities) of earlier compactions, host
         self.compactions = 0
+        self.grown = 0          # times the buffer grew to hold one view
 
     def add(self, ids, img):
         b = self.b
@@ -308,30 +335,94 @@ class PairAccumulator:
         b._call("gr_project_rect_pairs", ids_t.data_ptr(), rects_ptr, offs_ptr, n, h, w, self.n_classes,
                 self.counts.data_ptr(), self.keys.data_ptr(), self.cap, self.key_count.data_ptr(), self.flags, b._stream())
 
-    def _make_room(self, n: int, add_view) -> bool:
-        """Room for the pairs of a call over n views, at most one per face and view.  A call that exceeds the buffer on its own
-        is added view by view instead (`add_view(k)`) and False returned; otherwise the buffer is compacted first if the call
-        could overflow it, `bound` counts the call in, and the caller makes it."""
+    def add_polygons(self, ids, boxes, vert_offsets, verts, poly_offsets):
+        """`add` for views whose label image is the multi-hot mask of polygon rings (`Segmentor.label_regions`): ids (n, h, w)
+        or (h, w); boxes int (R, 5) rows {imin, jmin, imax, jmax, class}, each ring's clipped candidate box, half-open, sorted
+        by class within a view; vert_offsets (R + 1,), ring r's vertices are verts[vert_offsets[r]:vert_offsets[r + 1]];
+        verts float64 (N, 2) (row, col); poly_offsets (n + 1,), view k's rings are boxes[poly_offsets[k]:poly_offsets[k + 1]].
+        The tables go to the device as one int32 and one float64 upload; a face's winning pixel is one observation of every
+        class with a ring that contains it (`gr_project_polygon_pairs`)."""
+        torch = _torch()
+        b = self.b
+        ids_t = b._dev(ids, torch.int32)
+        if ids_t.ndim == 2:
+            ids_t = ids_t[None]
+        n, h, w = (int(x) for x in ids_t.shape)
+        host = lambda a: np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a)
+        boxes = host(boxes).reshape(-1, 5)
+        vert_offsets = host(vert_offsets).reshape(-1)
+        poly_offsets = host(poly_offsets).reshape(-1)
+        verts = np.ascontiguousarray(host(verts), dtype=np.float64).reshape(-1, 2)
+        R = boxes.shape[0]
+        if poly_offsets.shape[0] != n + 1:
+            raise ValueError(f"{n} views need {n + 1} polygon offsets, got {poly_offsets.shape[0]}")
+        if poly_offsets[0] != 0 or poly_offsets[-1] != R or np.any(np.diff(poly_offsets) < 0):
+            raise ValueError(f"polygon offsets must rise from 0 to {R} (the number of rings)")
+        if vert_offsets.shape[0] != R + 1:
+            raise ValueError(f"{R} rings need {R + 1} vertex offsets, got {vert_offsets.shape[0]}")
+        if vert_offsets[0] != 0 or vert_offsets[-1] != verts.shape[0] or np.any(np.diff(vert_offsets) < 1):
+            raise ValueError(f"vertex offsets must rise from 0 to {verts.shape[0]} (the number of vertices), at least one "
+                             "vertex per ring")
+        if boxes.size and (boxes.min() < np.iinfo(np.int32).min or boxes.max() > np.iinfo(np.int32).max):
+            raise ValueError("box corners and classes must fit in int32")
+        if verts.shape[0] > np.iinfo(np.int32).max:
+            raise ValueError("vertex offsets must fit in int32")
+        if boxes.size and (boxes[:, :2].min() < 0 or boxes[:, 2].max() > h or boxes[:, 3].max() > w):
+            raise ValueError(f"boxes must be clipped to the ({h}, {w}) image")
+        if R > 1:
+            falls = np.nonzero(np.diff(boxes[:, 4]) < 0)[0] + 1   # a class may only fall where a new view starts
+            if not np.isin(falls, poly_offsets).all():
+                raise ValueError("the rings of a view must be sorted by class")
+
+        def one_view(k):
+            a, e = int(poly_offsets[k]), int(poly_offsets[k + 1])
+            va, ve = int(vert_offsets[a]), int(vert_offsets[e])
+            self.add_polygons(ids_t[k], boxes[a:e], vert_offsets[a:e + 1] - va, verts[va:ve], np.array([0, e - a]))
+
+        if not self._make_room(n, one_view, polygon_pair_bounds(boxes, poly_offsets, b.n_faces)):
+            return
+        # two uploads: view offsets, vertex offsets and box rows as int32; the vertices as float64
+        table = b._dev(np.concatenate([poly_offsets.astype(np.int32), vert_offsets.astype(np.int32),
+                                       boxes.astype(np.int32).reshape(-1)]), torch.int32)
+        offs_ptr = table.data_ptr()
+        voffs_ptr = offs_ptr + 4 * (n + 1)
+        boxes_ptr = voffs_ptr + 4 * (R + 1)
+        verts_t = b._dev(verts, torch.float64)
+        b._call("gr_project_polygon_pairs", ids_t.data_ptr(), boxes_ptr, voffs_ptr, verts_t.data_ptr() if R else None, offs_ptr,
+                n, h, w, self.n_classes, self.counts.data_ptr(), self.keys.data_ptr(), self.cap, self.key_count.data_ptr(),
+                self.flags, b._stream())
+
+    def _make_room(self, n: int, add_view, bounds=None) -> bool:
+        """Room for the pairs of a call over n views: at most `bounds[k]` of view k, one per face where no bounds are given.
+        A call that exceeds the buffer on its own is added view by view instead (`add_view(k)`) and False returned; otherwise
+        the buffer is compacted first if the call could overflow it, `bound` counts the call in, and the caller makes it."""
         F = self.b.n_faces
-        if F > self.cap:
-            # the mesh may be uploaded (or replaced by a larger one) after the accumulator was made: the buffer must hold at
-            # least one view's pairs, or a single view could never be added
+        bounds = [F] * n if bounds is None else [int(x) for x in bounds]
+        largest = max(bounds, default=0)
+        if largest > self.cap:
+            # a single view must fit: the mesh may be uploaded (or replaced by a larger one) after the accumulator was made,
+            # a view of polygon rings may emit several pairs per face, or the caller chose a small buffer
+            if largest > self.MAX_KEYS:
+                raise MemoryError(f"one view may emit {largest} (face, class) pairs, more than the {self.MAX_KEYS} keys "
+                                  "(2 GiB) the pair buffer grows to")
             self._compact()
-            self.cap = max(8 * F, 1 << 20)
+            self.cap = largest if self._fixed_cap else max(largest, 8 * F, 1 << 20)
             self.keys = _torch().empty((self.cap,), dtype=_torch().int64, device=self.b.device)
-        if n * F > self.cap:
+            self.grown += 1
+        total = sum(bounds)
+        if total > self.cap:
             for k in range(n):
                 add_view(k)
             return False
-        if self.bound + n * F > self.cap:
+        if self.bound + total > self.cap:
             self._compact()
-        self.bound += n * F
+        self.bound += total
         return True
 
     def _compact(self):
         raw, bad = (int(x) for x in self.key_count.cpu().tolist())
         if bad:
-            raise IndexError(f"gr_project_index_pairs / gr_project_rect_pairs: an image value is not a class index in "
+            raise IndexError(f"gr_project_index_pairs / _rect_pairs / _polygon_pairs: an image value is not a class index in "
                              f"[0, {self.n_classes})")
         if raw > 0:
             self.parts.append(self.b._count_pairs(self.keys, raw))
@@ -605,10 +696,10 @@ class HipRaster:
             return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
         return self._count_pairs(keys, m)
 
-    def new_pair_accumulator(self, n_classes: int, counts, neg1_is_last_face: bool = True):
+    def new_pair_accumulator(self, n_classes: int, counts, neg1_is_last_face: bool = True, *, cap=None):
         """Sparse index aggregation over MANY views with the (face, class) pair keys kept on the device: `add(ids, img)` per
         view (or group of views) only enqueues work, `finish()` sorts and counts the pairs ONCE -- see `PairAccumulator`."""
-        return PairAccumulator(self, n_classes, counts, neg1_is_last_face)
+        return PairAccumulator(self, n_classes, counts, neg1_is_last_face, cap=cap)
 
     # -- multiview detections: ray-pair graph, boundary clip -------------------------------------------------------
     CLIP_TRIANGLE_LIMIT = 65536  # triangles per gr_rays_clip call

@@ -60,6 +60,16 @@ class SegmentorPhotogrammetryCameraSet(PhotogrammetryCameraSet):
         image_filename = self.base_camera_set.get_image_filename(index, absolute=True)
         return fn(image_filename, image_scale=image_scale)
 
+    def get_label_regions(self, index: int, image_scale: float = 1):
+        """((boxes int32 (R, 5) {imin, jmin, imax, jmax, class}, vert_offsets int32 (R + 1,), verts float64 (N, 2) (row, col)),
+        (h, w)): the class-sorted polygon rings that make up view `index`'s (h, w, C) mask (`label_regions` of the segmentor),
+        or None when the segmentor cannot describe it by rings exactly."""
+        fn = getattr(self.segmentor, "label_regions", None)
+        if fn is None:
+            return None
+        image_filename = self.base_camera_set.get_image_filename(index, absolute=True)
+        return fn(image_filename, image_scale=image_scale)
+
     def get_raw_image_by_index(self, index: int, image_scale: float = 1) -> np.ndarray:
         return self.base_camera_set.get_image_by_index(index=index, image_scale=image_scale)
 

@@ -5,7 +5,7 @@
 //   mesh_upload.hip  gr_mesh_upload: Morton order, de-indexed soup, block bounds            (per upload)
 //   binning.hip      k_cull_blocks, k_setup_cull, k_clip_faces, entry compilation, exact-path scan / fill  (per view)
 //   raster_tile.hip  k_raster_tile: the dominant kernel
-//   project.hip      winners, votes, gathers, sparse pairs, finalize, argmax + their entry points
+//   project.hip      winners, votes, gathers, sparse pairs (label images, rectangle tables, polygon rings), finalize, argmax + their entry points
 //   warp.hip         distortion warp, lens inversion (row f1)
 //   resize.hip       photo down-scale of get_image (anti-aliased resize)
 //   rays.hip         multiview detections: ray-pair graph (k_ray_prep, k_ray_pairs + radix sort), ray / boundary clip; no mesh needed

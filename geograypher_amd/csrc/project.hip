@@ -1,5 +1,5 @@
 // geograypher_amd/csrc/project.hip -- everything behind the rasterizer: last-writer-wins winners from id images, per-face
-// votes / nansums, per-view textures, texture gathers, sparse (face, class) pairs, finalize, argmax -- kernels and entry points.
+// votes / nansums, per-view textures, texture gathers, sparse (face, class) pairs (from label images, rectangles, polygon rings), finalize, argmax -- kernels and entry points.
 #include <hipcub/hipcub.hpp>
 
 #include "gr_internal.hpp"
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void k_gather_texture_u8(const int32_t *__rest
   out[i] = v;
 }
 
-// The tail of both emit kernels (K10, K10r): the lanes of a wave that hold a pair (takers = __ballot(emit), not empty: the
+// The tail of the emit kernels (K10, K10r, K10p): the lanes of a wave that hold a pair (takers = __ballot(emit), not empty: the
 // caller keeps the ballot and its test, dev_common.hpp says why) append their keys behind *key_count with one atomic; a key
 // beyond key_cap is counted and dropped.
 __device__ __forceinline__ void append_pair_keys(bool emit, unsigned long long key, unsigned long long takers, int lane,
@@ -348,6 +348,114 @@ __global__ __launch_bounds__(256) void k_emit_rect_pairs(uint32_t *__restrict__ 
     }
     const unsigned long long m = __ballot(emit);
     if (m) append_pair_keys(emit, key, m, lane, keys, key_cap, key_count);
+  }
+  if (f < F && c) counts[f] += c;
+}
+
+// The fill rule of skimage.draw.polygon for one pixel (x = column, y = row) and one ring of nv >= 1 vertices (row, col), in
+// double and in the host restatement's operation order (predictors/derived_segmentors.py, _ring_contains; every operation is
+// rounded on its own: -ffp-contract=off): edges in vertex order starting from the last vertex; a pixel within 1e-12 of a
+// vertex, or with differing parities of its right and left crossings (on an edge), is inside; otherwise inside iff the right
+// crossings are odd.  The quotient -- the only fp64 division -- is formed for the edges that straddle the pixel's row alone.
+__device__ __forceinline__ bool ring_contains(const double *__restrict__ vp, int nv, double x, double y) {
+  const double eps = 1e-12;
+  uint32_t right = 0, left = 0;
+  double y0 = vp[2 * (int64_t)(nv - 1)] - y, x0 = vp[2 * (int64_t)(nv - 1) + 1] - x;
+  for (int i = 0; i < nv; ++i) {
+    const double y1 = vp[2 * (int64_t)i] - y, x1 = vp[2 * (int64_t)i + 1] - x;
+    if (-eps < x0 && x0 < eps && -eps < y0 && y0 < eps) return true;
+    const bool up = (y0 > 0.0) != (y1 > 0.0), down = (y0 < 0.0) != (y1 < 0.0);
+    if (up || down) {
+      const double q = (x0 * y1 - x1 * y0) / (y1 - y0);
+      if (up && q > 0.0) ++right;
+      if (down && q < 0.0) ++left;
+    }
+    x0 = x1;
+    y0 = y1;
+  }
+  return ((right ^ left) & 1u) != 0u || (right & 1u) != 0u;
+}
+
+// K10p sparse index aggregation of polygon labels (region detections): K10r with rings in place of rectangles and a multi-hot
+//     answer.  The winner pixel of a face belongs to every class that has at least one ring of the view containing it: ONE
+//     pair (face, class) per class and view, however many rings of the class contain the pixel, and counts[f] += 1 when any
+//     ring does.  boxes: int32 rows {imin, jmin, imax, jmax, class}, a ring's clipped candidate box, half-open, SORTED BY CLASS
+//     within a view; voffs: ring r's vertices are verts[voffs[r] .. voffs[r + 1]) (double (row, col) pairs); offs: view v's
+//     rings are [offs[v], offs[v + 1]).  The ring records are staged in LDS in chunks of RING_CHUNK and walked in order;
+//     the vertices of a ring are read from global memory on a box hit only, and not at all once the face's pixel has been
+//     found in the ring's class.  Because the table is class-sorted, the end of a class run is a point the whole block
+//     reaches together (the records are the same LDS words for every lane): one ballot there, one append if a lane hit.
+#define RING_CHUNK 512
+__global__ __launch_bounds__(256) void k_emit_polygon_pairs(uint32_t *__restrict__ winner, const int32_t *__restrict__ boxes,
+                                                            const int32_t *__restrict__ voffs, const double *__restrict__ verts,
+                                                            const int32_t *__restrict__ offs, int n_views, int64_t F, int w,
+                                                            long long n_classes, uint32_t *__restrict__ counts,
+                                                            unsigned long long *__restrict__ keys, long long key_cap,
+                                                            unsigned long long *__restrict__ key_count,
+                                                            int *__restrict__ bad) {
+  __shared__ int4 box[RING_CHUNK];
+  __shared__ int box_cls[RING_CHUNK];
+  __shared__ int vert_beg[RING_CHUNK + 1];
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  uint32_t c = 0;
+  // the end of a class run: the lanes whose pixel lies in a ring of class `cls` emit their pair
+  auto close_run = [&](bool hit, int cls) {
+    bool emit = false;
+    unsigned long long key = 0;
+    if (hit) {
+      if (cls < 0 || (long long)cls >= n_classes) atomicOr(bad, 1);
+      else { emit = true; key = (unsigned long long)f * (unsigned long long)n_classes + (unsigned long long)cls; }
+    }
+    const unsigned long long m = __ballot(emit);
+    if (m) append_pair_keys(emit, key, m, lane, keys, key_cap, key_count);
+  };
+  for (int v = 0; v < n_views; ++v) {
+    int pi = 0, pj = 0;
+    bool live = false;
+    if (f < F) {
+      const uint32_t wk = winner[v * F + f];
+      if (wk != 0) {
+        winner[v * F + f] = 0;
+        pi = (int)((wk - 1) / (uint32_t)w);
+        pj = (int)((wk - 1) % (uint32_t)w);
+        live = true;
+      }
+    }
+    const double px = (double)pj, py = (double)pi;
+    bool hit = false, any = false;  // in a ring of the run's class; in any ring of the view
+    int run_cls = 0;
+    const int r0 = offs[v], r1 = offs[v + 1];
+    for (int beg = r0; beg < r1; beg += RING_CHUNK) {
+      // also the barrier that lets the chunk before this one (or the previous view's last one) be overwritten; a block that
+      // shows no face of the view has nothing to look up
+      if (!__syncthreads_or(live)) break;
+      const int n = r1 - beg < RING_CHUNK ? r1 - beg : RING_CHUNK;
+      for (int k = threadIdx.x; k < n; k += 256) {
+        const int32_t *r = boxes + (int64_t)(beg + k) * 5;
+        box[k] = make_int4(r[0], r[1], r[2], r[3]);
+        box_cls[k] = r[4];
+      }
+      for (int k = threadIdx.x; k <= n; k += 256) vert_beg[k] = voffs[beg + k];
+      __syncthreads();
+      for (int k = 0; k < n; ++k) {
+        const int cls = box_cls[k];
+        if (cls != run_cls) {  // the same LDS word in every lane: the block takes this branch together
+          close_run(hit, run_cls);
+          hit = false;
+          run_cls = cls;
+        }
+        if (live && !hit) {
+          const int4 b = box[k];
+          if (pi >= b.x && pj >= b.y && pi < b.z && pj < b.w) {
+            const int vb = vert_beg[k], nv = vert_beg[k + 1] - vb;
+            if (nv > 0 && ring_contains(verts + 2 * (int64_t)vb, nv, px, py)) hit = any = true;
+          }
+        }
+      }
+    }
+    close_run(hit, run_cls);
+    if (any) ++c;
   }
   if (f < F && c) counts[f] += c;
 }
@@ -650,6 +758,23 @@ int gr_project_rect_pairs(gr_ctx *c, const int32_t *ids, const int32_t *rects, c
   return project_groups(c, ids, n_views, h, w, flags, stream, [&](uint32_t *win, int v0, int nb) {
     hipLaunchKernelGGL(k_emit_rect_pairs, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, rects, rect_offsets + v0,
                        nb, F, w, (long long)n_classes, counts, (unsigned long long *)keys, (long long)key_cap,
+                       (unsigned long long *)key_count, check.flag);
+  }, &check);
+}
+
+int gr_project_polygon_pairs(gr_ctx *c, const int32_t *ids, const int32_t *boxes, const int32_t *vert_offsets,
+                             const double *verts, const int32_t *poly_offsets, int n_views, int h, int w, int64_t n_classes,
+                             uint32_t *counts, uint64_t *keys, int64_t key_cap, uint64_t *key_count, int flags, void *stream) {
+  int rc = check_projection(c, n_views, h, w);
+  if (rc) return rc;
+  if (!ids || !vert_offsets || !poly_offsets || !counts || !keys || !key_count || n_classes <= 0 || key_cap < 0)
+    return fail(c, GR_EINVAL, "bad sparse projection args");
+  const int64_t F = c->F;
+  hipStream_t s = (hipStream_t)stream;
+  const ClassCheck check(c, key_count, flags, "a polygon's class is not a class index in [0, %lld)", n_classes);
+  return project_groups(c, ids, n_views, h, w, flags, stream, [&](uint32_t *win, int v0, int nb) {
+    hipLaunchKernelGGL(k_emit_polygon_pairs, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, boxes, vert_offsets, verts,
+                       poly_offsets + v0, nb, F, w, (long long)n_classes, counts, (unsigned long long *)keys, (long long)key_cap,
                        (unsigned long long *)key_count, check.flag);
   }, &check);
 }

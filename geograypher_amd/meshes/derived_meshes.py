@@ -11,7 +11,10 @@ Mirror of geograypher/meshes/derived_meshes.py for the two variants whose work i
   images with many classes into scipy CSR arrays; the per-view projection, pair emission, radix sort and
   run-length count run on the device (`gr_project_index_pairs`, `gr_count_pairs`).  Where the camera set's segmentor
   describes its label images as rectangles (detections, image IDs: `get_label_rectangles`), no label image is built at
-  all: the label of a face's winning pixel is looked up in the view's rectangle table (`gr_project_rect_pairs`).
+  all: the label of a face's winning pixel is looked up in the view's rectangle table (`gr_project_rect_pairs`).  Where it
+  describes them as polygon rings (region detections: `get_label_regions`), the (h, w, C) multi-hot mask is never built
+  either: the winning pixel is tested against the view's rings and is one observation of every class that contains it
+  (`gr_project_polygon_pairs`).
 """
 import typing
 
@@ -92,15 +95,19 @@ class TexturedPhotogrammetryMeshIndexPredictions(TexturedPhotogrammetryMesh):
         # the (face, class) pair keys of all views stay on the device; ONE sort + run-length count at the end
         acc = self.backend.new_pair_accumulator(n_classes, counts, neg1_is_last_face=self.neg1_is_last_face)
         batch_stop = max(len(cameras) - batch_size + 1, 1)  # trailing views that do not fill a batch are dropped
+        # a camera set whose segmentor describes every used view as rectangles, or as polygon rings, is aggregated from those
+        # tables: no label image is loaded or built
         tables = None
-        if not return_all and hasattr(acc, "add_rects") and hasattr(cameras, "get_label_rectangles"):
-            n_used = len(range(0, batch_stop, batch_size)) * batch_size
-            tables = [cameras.get_label_rectangles(i, aggregate_img_scale) for i in range(n_used)]
-            if any(t is None for t in tables):
-                tables = None
+        n_used = len(range(0, batch_stop, batch_size)) * batch_size
+        for supplier, consumer, add_tables in (("get_label_rectangles", "add_rects", self._add_rectangle_tables),
+                                               ("get_label_regions", "add_polygons", self._add_region_tables)):
+            if tables is None and not return_all and hasattr(acc, consumer) and hasattr(cameras, supplier):
+                tables = [getattr(cameras, supplier)(i, aggregate_img_scale) for i in range(n_used)]
+                if any(t is None for t in tables):
+                    tables = None
+                else:
+                    self._add_table_pairs(acc, add_tables, cameras, tables, batch_size, batch_stop, aggregate_img_scale, kwargs)
         gen = () if tables is not None else self._iter_view_inputs(cameras, batch_size, aggregate_img_scale, True, kwargs)
-        if tables is not None:
-            self._add_rectangle_pairs(acc, cameras, tables, batch_size, batch_stop, aggregate_img_scale, kwargs)
         for _, ids, img, n_channels in tqdm(gen, total=len(cameras), desc="Aggregating projected viewpoints"):
             if return_all:
                 if img is None:
@@ -131,10 +138,10 @@ class TexturedPhotogrammetryMeshIndexPredictions(TexturedPhotogrammetryMesh):
         average_projections = summed_projections.multiply(reciprocal)
         return average_projections, info
 
-    def _add_rectangle_pairs(self, acc, cameras, tables, batch_size, batch_stop, aggregate_img_scale, pix2face_kwargs):
-        """The label-rectangle path of `aggregate_projected_images`: ids come from pix2face exactly as on the image path
-        (same batches, mesh, distortion and keywords); the rectangle tables of a batch go to the device as one small int32
-        upload and the label of each face's winning pixel is looked up there.  No label image is loaded or built."""
+    def _add_table_pairs(self, acc, add_tables, cameras, tables, batch_size, batch_stop, aggregate_img_scale, pix2face_kwargs):
+        """The table paths of `aggregate_projected_images` (label rectangles, polygon rings): ids come from pix2face exactly as
+        on the image path (same batches, mesh, distortion and keywords); `add_tables(acc, ids, [table of each view])` sends the
+        batch's tables to the device, where the label(s) of each face's winning pixel are looked up."""
         torch = _torch()
         mesh = self.get_mesh_in_cameras_coords(cameras)
         for batch_start in tqdm(range(0, batch_stop, batch_size), desc="Aggregating projected viewpoints"):
@@ -146,11 +153,28 @@ class TexturedPhotogrammetryMeshIndexPredictions(TexturedPhotogrammetryMesh):
             if isinstance(ids, np.ndarray):  # distortion applied on the host
                 ids = self.backend._dev(ids.astype(np.int32), torch.int32)
             batch = tables[batch_start:batch_start + batch_size]
-            for rects, hw in batch:
+            for _, hw in batch:
                 if tuple(hw) != tuple(ids.shape[1:]):
                     raise ValueError(
                         f"ids {tuple(ids.shape[1:])} and index image {tuple(hw)} differ in shape"
                     )
-            offsets = np.zeros(len(batch) + 1, dtype=np.int64)
-            offsets[1:] = np.cumsum([rects.shape[0] for rects, _ in batch])
-            acc.add_rects(ids, np.concatenate([rects for rects, _ in batch]), offsets)
+            add_tables(acc, ids, [table for table, _ in batch])
+
+    @staticmethod
+    def _add_rectangle_tables(acc, ids, batch):
+        """One (R, 5) rectangle table per view -> one `add_rects`."""
+        offsets = np.zeros(len(batch) + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([rects.shape[0] for rects in batch])
+        acc.add_rects(ids, np.concatenate(batch), offsets)
+
+    @staticmethod
+    def _add_region_tables(acc, ids, batch):
+        """One (boxes, vert_offsets, verts) ring table per view -> one `add_polygons`."""
+        poly_offsets = np.zeros(len(batch) + 1, dtype=np.int64)
+        poly_offsets[1:] = np.cumsum([boxes.shape[0] for boxes, _, _ in batch])
+        vert_base = np.concatenate([[0], np.cumsum([verts.shape[0] for _, _, verts in batch])]).astype(np.int64)
+        vert_offsets = np.concatenate([[0]] + [np.asarray(vo, dtype=np.int64)[1:] + vert_base[k]
+                                               for k, (_, vo, _) in enumerate(batch)])
+        acc.add_polygons(ids, np.concatenate([np.asarray(boxes).reshape(-1, 5) for boxes, _, _ in batch]), vert_offsets,
+                         np.concatenate([np.asarray(verts, dtype=np.float64).reshape(-1, 2) for _, _, verts in batch]),
+                         poly_offsets)

@@ -1,5 +1,7 @@
-"""Segmentors that feed the aggregation loop (reference: geograypher/predictors/derived_segmentors.py:32-306)."""
+"""Segmentors that feed the aggregation loop (reference: geograypher/predictors/derived_segmentors.py:32-462)."""
 import csv
+import json
+import math
 import re
 import typing
 from pathlib import Path
@@ -383,3 +385,247 @@ class TabularRectangleSegmentor(Segmentor):
         all_corners = [self.get_corners(self.labels_df.row(i), as_int=False) for i in self._groups[filename]]
         imin, jmin, imax, jmax = [np.array(x) for x in zip(*all_corners)]
         return np.vstack([(imin + imax) / 2, (jmin + jmax) / 2]).T
+
+
+# -- polygon detections (reference: derived_segmentors.py:309-462) ------------------------------------------------------
+# The fill rule is scikit-image's `draw.polygon(rows, cols, shape=...)`, restated in float64 numpy (no skimage here; pinned by
+# tests/golden/reference_draw_polygon.npz, made with the real one).  Candidate box per axis: int(max(0, min)) ...
+# min(size - 1, int(ceil(max))), both ends included; every integer pixel (r, c) of it is tested as the point (x = c, y = r) with
+# the crossing rule of `_ring_contains`, which counts pixels ON the boundary as inside.
+
+_VERTEX_EPS = 1e-12
+
+
+def _ring_box(rows: np.ndarray, cols: np.ndarray, h: int, w: int):
+    """The half-open candidate box (imin, jmin, imax, jmax) of a ring on an (h, w) image, or None when it holds no pixel."""
+    i0, i1 = int(max(0, rows.min())), min(h - 1, int(math.ceil(rows.max()))) + 1
+    j0, j1 = int(max(0, cols.min())), min(w - 1, int(math.ceil(cols.max()))) + 1
+    if i1 <= i0 or j1 <= j0:
+        return None
+    return i0, j0, i1, j1
+
+
+def _ring_contains(rows: np.ndarray, cols: np.ndarray, box) -> np.ndarray:
+    """(imax - imin, jmax - jmin) bool: which pixels of the half-open `box` the ring (rows, cols) covers.  Per pixel, the edges
+    are walked in vertex order starting from the last vertex, (x0, y0) and (x1, y1) being an edge's ends minus the pixel:
+    a pixel within 1e-12 of a vertex is inside; an edge with (y0 > 0) != (y1 > 0) is a right crossing when
+    (x0 * y1 - x1 * y0) / (y1 - y0) > 0, one with (y0 < 0) != (y1 < 0) a left crossing when that quotient is < 0; differing
+    parities of the two counts mean the pixel lies on an edge (inside), otherwise it is inside iff the right count is odd.
+    `gr_project_polygon_pairs` evaluates the same expressions in the same order in double."""
+    i0, j0, i1, j1 = box
+    yp, xp = np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.float64)
+    y = np.arange(i0, i1, dtype=np.float64)[:, None]
+    x = np.arange(j0, j1, dtype=np.float64)[None, :]
+    right = np.zeros((i1 - i0, j1 - j0), dtype=bool)   # parities of the crossing counts
+    left = np.zeros_like(right)
+    vertex = np.zeros_like(right)
+    x0, y0 = xp[-1] - x, yp[-1] - y
+    for i in range(xp.shape[0]):
+        x1, y1 = xp[i] - x, yp[i] - y
+        vertex |= ((-_VERTEX_EPS < x0) & (x0 < _VERTEX_EPS)) & ((-_VERTEX_EPS < y0) & (y0 < _VERTEX_EPS))
+        up = ((y0 > 0) != (y1 > 0))[:, 0]
+        down = ((y0 < 0) != (y1 < 0))[:, 0]
+        sel = np.nonzero(up | down)[0]   # the pixel rows this edge can cross: the quotient is only formed there (y1 != y0)
+        if sel.size:
+            ya, yb = y0[sel], y1[sel]
+            q = (x0 * yb - x1 * ya) / (yb - ya)
+            right[sel] ^= up[sel, None] & (q > 0)
+            left[sel] ^= down[sel, None] & (q < 0)
+        x0, y0 = x1, y1
+    return vertex | (right != left) | right
+
+
+def _ring_area_centroid(ring):
+    """Shoelace (|area|, cx, cy) of one ring of (x, y) points; a ring without area has its vertex mean as centre."""
+    pts = np.asarray(ring, dtype=np.float64)[:, :2]
+    if pts.shape[0] > 1 and np.array_equal(pts[0], pts[-1]):
+        pts = pts[:-1]
+    x, y = pts[:, 0], pts[:, 1]
+    xn, yn = np.roll(x, -1), np.roll(y, -1)
+    cross = x * yn - xn * y
+    a = cross.sum() / 2.0
+    if a == 0:
+        return 0.0, x.mean(), y.mean()
+    return abs(a), ((x + xn) * cross).sum() / (6.0 * a), ((y + yn) * cross).sum() / (6.0 * a)
+
+
+def _polygon_area_centroid(rings):
+    """(area, cx, cy) of a GeoJSON polygon: the exterior ring minus its holes, area-weighted."""
+    area, cx, cy = _ring_area_centroid(rings[0])
+    if area == 0:
+        return area, cx, cy
+    mx, my = area * cx, area * cy
+    for hole in rings[1:]:
+        ha, hx, hy = _ring_area_centroid(hole)
+        area, mx, my = area - ha, mx - ha * hx, my - ha * hy
+    return area, mx / area, my / area
+
+
+class RegionDetectionSegmentor(Segmentor):
+    """Polygon detections (tree crowns, instance masks) looked up per image in a geospatial vector file (reference:
+    derived_segmentors.py:309-462).  The file of an image is its path relative to `base_folder`, under `lookup_folder`, with
+    the suffix `geo_file_extension`.  There is no geopandas here: `.geojson` FeatureCollections are read with `json`, any
+    other extension raises NotImplementedError.
+
+    `segment_image` paints the exterior ring of every Polygon / part of a MultiPolygon (holes are filled) into the plane
+    `class_map[properties[label_key]]` of an (H, W, C) bool mask, C = max(class_map.values()) + 1, by scikit-image's
+    `draw.polygon` rule.
+
+    AXIS QUIRK: the reference writes `y, x = poly.exterior.xy` where shapely returns (x, y), so the mask ROW is the geometry's
+    x and the column its y -- while `get_detection_centers` returns (centroid.y, centroid.x), i.e. row = y.  The reference's own
+    test pins the former.  `xy_order="reference"` (default) reproduces it; `xy_order="image"` paints row = y, column = x,
+    consistent with the centres.
+
+    Beyond the reference: `num_classes`, the camera-set calling convention `segment_image(image, filename=, image_scale=)`
+    (the image shape then comes from `image_shape=` given to the constructor, else from the image file's header; a missing
+    detection file is an all-False (H, W, C) mask there, since a camera set needs one channel count for all views), and
+    `label_regions`, which hands the sparse aggregation the rings themselves so that no mask is ever built."""
+
+    thread_safe_lookup = True  # stateless file look-ups
+
+    def __init__(self, base_folder: PATH_TYPE, lookup_folder: PATH_TYPE, label_key: str, class_map: dict,
+                 geo_file_extension: str = ".gpkg", *, image_shape=None, xy_order: str = "reference"):
+        self.base_folder = Path(base_folder)
+        self.lookup_folder = Path(lookup_folder)
+        self.geo_file_extension = geo_file_extension
+        self.label_key = label_key
+        self.class_map = class_map
+        if xy_order not in ("reference", "image"):
+            raise ValueError(f"xy_order must be 'reference' or 'image', got {xy_order!r}")
+        self.xy_order = xy_order
+        self.image_shape = None if image_shape is None else tuple(int(x) for x in image_shape)
+        if not self.lookup_folder.is_dir():
+            raise ValueError(f"Folder {self.lookup_folder} not found")
+
+    @property
+    def num_classes(self) -> int:
+        return max(self.class_map.values()) + 1
+
+    def geomatch(self, impath):
+        """The geospatial file that belongs to an image."""
+        subpath = Path(impath).relative_to(self.base_folder)
+        return self.lookup_folder / subpath.with_suffix(self.geo_file_extension)
+
+    def _read_features(self, geo_path: Path):
+        """[(geometry type, coordinates, properties)] of a FeatureCollection, in file order."""
+        if geo_path.suffix.lower() != ".geojson":
+            raise NotImplementedError(
+                f"RegionDetectionSegmentor reads .geojson files only; {geo_path.suffix or geo_path.name!r} files need "
+                "geopandas, which this package does not use"
+            )
+        with open(geo_path) as fh:
+            doc = json.load(fh)
+        out = []
+        for feat in doc.get("features", []):
+            geom = feat.get("geometry") or {}
+            out.append((geom.get("type"), geom.get("coordinates"), feat.get("properties") or {}))
+        return out
+
+    def get_detection_centers(self, im_path: PATH_TYPE) -> np.ndarray:
+        """(n, 2) float64 (centroid.y, centroid.x) of every feature of the image's file, (0, 2) without a file: the
+        area-weighted shoelace centroid, holes subtracted, a MultiPolygon weighted over its parts."""
+        geo_path = self.geomatch(im_path)
+        if not geo_path.is_file():
+            return np.zeros((0, 2))
+        centers = []
+        for gtype, coords, _ in self._read_features(geo_path):
+            if gtype == "Polygon":
+                parts = [coords]
+            elif gtype == "MultiPolygon":
+                parts = list(coords)
+            else:
+                raise NotImplementedError(f"get_detection_centers: centroid of a {gtype} feature is not implemented")
+            acs = [_polygon_area_centroid(rings) for rings in parts]
+            total = sum(a for a, _, _ in acs)
+            if total > 0:
+                cx, cy = sum(a * x for a, x, _ in acs) / total, sum(a * y for a, _, y in acs) / total
+            else:
+                cx, cy = float(np.mean([x for _, x, _ in acs])), float(np.mean([y for _, _, y in acs]))
+            centers.append((cy, cx))
+        return np.array(centers, dtype=np.float64).reshape(-1, 2)
+
+    def _checked_rings(self, geo_path: Path):
+        """[(class index, rows, cols)] of every ring `segment_image` paints, in paint order, after the reference's checks."""
+        feats = self._read_features(geo_path)
+        columns = []
+        for _, _, props in feats:
+            columns.extend(k for k in props if k not in columns)
+        columns.append("geometry")
+        if self.label_key not in columns:
+            raise ValueError(f"label key ({self.label_key}) not found in GDF columns:\n{columns}")
+        labels = {props.get(self.label_key) for _, _, props in feats}
+        if len(difference := labels - set(self.class_map.keys())) > 0:
+            raise ValueError(f"Found the following label keys in a GDF which were not in the class map: {difference}")
+        if any([not isinstance(value, int) for value in self.class_map.values()]):
+            raise ValueError(f"Found class map values which were not integer indices:\n{self.class_map.values()}")
+        rings = []
+        for gtype, coords, props in feats:
+            if gtype == "Polygon":
+                parts = [coords]
+            elif gtype == "MultiPolygon":
+                parts = list(coords)
+            else:
+                continue
+            index = self.class_map[props.get(self.label_key)]
+            for poly in parts:
+                ext = np.asarray(poly[0], dtype=np.float64)[:, :2]  # the exterior ring: holes are filled
+                gx, gy = ext[:, 0], ext[:, 1]
+                rows, cols = (gx, gy) if self.xy_order == "reference" else (gy, gx)
+                rings.append((index, rows, cols))
+        return rings
+
+    def _shape_for(self, filename, image_scale):
+        if image_scale != 1:
+            raise NotImplementedError(
+                "RegionDetectionSegmentor: the reference defines no scaling of the polygons; only image_scale == 1 is supported"
+            )
+        if self.image_shape is not None:
+            return self.image_shape
+        from PIL import Image
+
+        with Image.open(filename) as img_handler:  # the header only
+            w, h = img_handler.size
+        return int(h), int(w)
+
+    def segment_image(self, image, im_path: PATH_TYPE = None, image_shape: tuple = None, *, filename: PATH_TYPE = None,
+                      image_scale: float = 1) -> np.ndarray:
+        """(H, W, C) bool mask of the image's polygons.  Reference call: `segment_image(image, im_path, image_shape)` (a
+        missing file gives (H, W, 0), as there).  Camera-set call: `segment_image(image, filename=..., image_scale=1)`."""
+        from_camera_set = filename is not None
+        if from_camera_set:
+            im_path, image_shape = filename, self._shape_for(filename, image_scale)
+        image_shape = tuple(image_shape)
+        geo_path = self.geomatch(im_path)
+        if not geo_path.is_file():
+            n_planes = self.num_classes if from_camera_set else 0
+            return np.full(image_shape + (n_planes,), fill_value=False, dtype=bool)
+        rings = self._checked_rings(geo_path)
+        label_image = np.full(image_shape + (self.num_classes,), fill_value=False, dtype=bool)
+        h, w = image_shape
+        for index, rows, cols in rings:
+            box = _ring_box(rows, cols, h, w)
+            if box is not None:
+                label_image[box[0]:box[2], box[1]:box[3], index] |= _ring_contains(rows, cols, box)
+        return label_image
+
+    def label_regions(self, filename: PATH_TYPE, image_scale: float = 1):
+        """((boxes, vert_offsets, verts), (h, w)) of what `segment_image(filename=)` paints, or None at image_scale != 1:
+        boxes int32 (R, 5) rows {imin, jmin, imax, jmax, class}, each ring's clipped candidate box, half-open (a ring whose
+        box is empty is dropped); vert_offsets int32 (R + 1,); verts float64 (N, 2) (row, col), the rings exactly as painted,
+        closing vertex included.  Rings are ordered by class (stable), so every class is one contiguous run."""
+        if image_scale != 1:
+            return None
+        h, w = self._shape_for(filename, image_scale)
+        geo_path = self.geomatch(filename)
+        kept = []
+        if geo_path.is_file():
+            for index, rows, cols in self._checked_rings(geo_path):
+                box = _ring_box(rows, cols, h, w)
+                if box is not None:
+                    kept.append((index, box, np.stack([rows, cols], axis=1)))
+            kept.sort(key=lambda t: t[0])
+        boxes = np.array([(*box, index) for index, box, _ in kept], dtype=np.int32).reshape(-1, 5)
+        vert_offsets = np.zeros(len(kept) + 1, dtype=np.int32)
+        vert_offsets[1:] = np.cumsum([v.shape[0] for _, _, v in kept])
+        verts = np.concatenate([v for _, _, v in kept]) if kept else np.zeros((0, 2))
+        return (boxes, vert_offsets, np.ascontiguousarray(verts, dtype=np.float64)), (h, w)

@@ -291,6 +291,21 @@ int gr_project_index_pairs(gr_ctx *ctx, const int32_t *ids, const double *img, i
 int gr_project_rect_pairs(gr_ctx *ctx, const int32_t *ids, const int32_t *rects, const int32_t *rect_offsets,
                           int n_views, int h, int w, int64_t n_classes, uint32_t *counts, uint64_t *keys,
                           int64_t key_cap, uint64_t *key_count, int flags, void *stream);
+/* gr_project_index_pairs for views whose label image is the MULTI-HOT mask of polygon rings (region detections): same
+ * winners, flags, counts protocol and class check, but the winner pixel (p / w, p % w) of a face is one observation of EVERY
+ * class that has at least one ring of the view containing it: one pair key f * n_classes + class per (face, class, view),
+ * however many rings of the class contain the pixel, and counts[f] += 1 when any ring does.  Containment is
+ * skimage.draw.polygon's rule in double (boundary pixels inside; DESIGN.md "Polygon detections").  No mask image exists.
+ * boxes: int32 rows {imin, jmin, imax, jmax, class}, ring r's clipped candidate box, half-open, SORTED BY CLASS within each
+ * view (an unsorted table emits a pair once per class run); vert_offsets: rings + 1 non-decreasing int32, ring r's vertices
+ * are verts[vert_offsets[r] .. vert_offsets[r + 1]), double (row, col) pairs (a ring without vertices contains nothing);
+ * poly_offsets: n_views + 1 non-decreasing int32, view v's rings are [poly_offsets[v], poly_offsets[v + 1]).  All device
+ * memory; boxes and verts may be NULL when no view has a ring; the caller guarantees that the offsets index their tables.
+ * A view may emit several pairs per face: the caller sizes key_cap (or reads *key_count, which counts dropped pairs too).
+ * Added without a GR_VERSION bump. */
+int gr_project_polygon_pairs(gr_ctx *ctx, const int32_t *ids, const int32_t *boxes, const int32_t *vert_offsets,
+                             const double *verts, const int32_t *poly_offsets, int n_views, int h, int w, int64_t n_classes,
+                             uint32_t *counts, uint64_t *keys, int64_t key_cap, uint64_t *key_count, int flags, void *stream);
 /* multiplicity of every distinct pair key: radix sort + run-length encode (rocPRIM via hipcub) in context scratch.
  * unique_keys / pair_counts: capacity n.  *n_unique_h (host) receives the number of distinct keys.  Synchronises. */
 int gr_count_pairs(gr_ctx *ctx, uint64_t *keys, int64_t n, uint64_t *unique_keys, uint32_t *pair_counts,
