@@ -137,6 +137,8 @@ _SIGNATURES = {
     "gr_ray_pairs": [_vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _i64, _i64p, _vp],
     "gr_ray_pairs_tile": [_i64, _i64, _i64p, _i64p],
     "gr_rays_clip": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
+    "gr_points_bounds": [_vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "gr_cover_grid": [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gr_warp_nearest_i32": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, ctypes.c_int32, _i32, _f64, _f64, _vp, _vp],
     "gr_warp_f64": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _f64, _vp, _vp],
     "gr_invert_distortion_f64": [_vp, _f64p, _i32, _i32, _f64, _i32, _f64, _vp, _vp, _vp],
@@ -776,6 +778,46 @@ class HipRaster:
         self._call("gr_rays_clip", o_t.data_ptr(), d_t.data_ptr(), n, p_t.data_ptr(), int(p_t.shape[0]), f_t.data_ptr(),
                    int(f_t.shape[0]), hit.data_ptr(), t.data_ptr(), pts.data_ptr(), self._stream())
         return hit.to(torch.bool), t, pts
+
+    # -- covering meshes: bounds of the points, extremes per grid cell ---------------------------------------------
+    COVER_MAX_N = 1024   # grid points a side of gr_cover_grid
+    COVER_LDS_N = 56     # ... up to which a workgroup keeps its accumulators in LDS (csrc/cover.hip)
+
+    def _cover_points(self, points):
+        p_t = self._dev(points, _torch().float64)
+        if p_t.ndim != 2 or p_t.shape[1] != 3:
+            raise ValueError(f"points must be (V, 3), got {tuple(p_t.shape)}")
+        return p_t
+
+    def points_bounds(self, points, stride: int = 1):
+        """gr_points_bounds: points (V, 3) float64, numpy or device tensor (a non-contiguous view is made contiguous), of which
+        rows 0, stride, 2 stride, ... are visited -> (bounds (6,) float64 tensor xmin xmax ymin ymax zmin zmax over the
+        visited finite rows, nonfinite (1,) int64 tensor: the visited rows with a NaN or infinite coordinate).  Only enqueues."""
+        torch = _torch()
+        p_t = self._cover_points(points)
+        bounds = torch.empty((6,), dtype=torch.float64, device=self.device)
+        nonfinite = torch.empty((1,), dtype=torch.int64, device=self.device)
+        self._call("gr_points_bounds", p_t.data_ptr(), int(p_t.shape[0]), int(stride), bounds.data_ptr(), nonfinite.data_ptr(),
+                   self._stream())
+        return bounds, nonfinite
+
+    def cover_grid(self, points, x_lo, x_hi, y_lo, y_hi, stride: int = 1):
+        """gr_cover_grid (DESIGN.md "Covering meshes"): points as for `points_bounds`; x_lo, x_hi, y_lo, y_hi (N,) float64, the
+        bounds of the grid cells per axis -> (z_max (N, N) float64, z_min (N, N) float64, count (N, N) int32 tensors), indexed
+        [xi, yi]: the extremes of z over the visited rows with x_lo[xi] <= x <= x_hi[xi] and y_lo[yi] <= y <= y_hi[yi], NaN
+        where count is 0.  Only enqueues."""
+        torch = _torch()
+        p_t = self._cover_points(points)
+        tabs = [self._dev(t, torch.float64).reshape(-1) for t in (x_lo, x_hi, y_lo, y_hi)]
+        N = int(tabs[0].shape[0])
+        if any(int(t.shape[0]) != N for t in tabs):
+            raise ValueError(f"the four bound tables must have one length, got {[int(t.shape[0]) for t in tabs]}")
+        z_max = torch.empty((N, N), dtype=torch.float64, device=self.device)
+        z_min = torch.empty((N, N), dtype=torch.float64, device=self.device)
+        count = torch.empty((N, N), dtype=torch.int32, device=self.device)   # uint32 payload
+        self._call("gr_cover_grid", p_t.data_ptr(), int(p_t.shape[0]), int(stride), N, *(t.data_ptr() for t in tabs),
+                   z_max.data_ptr(), z_min.data_ptr(), count.data_ptr(), self._stream())
+        return z_max, z_min, count
 
     # -- label_polygons: weighted face area per (polygon, class) ---------------------------------------------------
     def polygon_class_weights(self, tri, face_class, face_weight, ring_vertices, ring_offsets, ring_polygon, ring_is_hole,

@@ -10,6 +10,7 @@
 //   resize.hip       photo down-scale of get_image (anti-aliased resize)
 //   rays.hip         multiview detections: ray-pair graph (k_ray_prep, k_ray_pairs + radix sort), ray / boundary clip; no mesh needed
 //   equirect.hip     360-degree photos: perspective views resampled from an equirectangular image (k_equirect_view)
+//   cover.hip        covering meshes: bounds of a point set (k_points_bounds), highest / lowest member per grid cell (k_cover_grid); no mesh needed
 //   polygons.hip     label_polygons: weighted face area per (polygon, class), exact containment or clipped overlay (k_polygon_weights); no mesh needed
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -242,6 +243,8 @@ struct gr_ctx {
 #endif
   double *resize_tmp = nullptr;        // rows pass of gr_resize_image_f64: [2 h_out][w_in * C]
   int64_t resize_have = 0;
+  double *bounds_part = nullptr;       // per-workgroup partial records of gr_points_bounds (cover.hip): 1024 x 64 bytes
+  int64_t bounds_part_have = 0;
   hipStream_t last_stream = nullptr;   // of the last raster call (gr_raster_status reads its outcome there)
   std::vector<hipStream_t> used_streams;  // streams that work touching context scratch was enqueued on since the last quiesce
   // profiling

@@ -1,0 +1,126 @@
+"""Multiview detection and triangulation: per-image detections -> 3D locations.
+
+Mirror of geograypher/entrypoints/multiview_detections.py:183-303 in the formats this package reads: the mesh as `.npz`
+(points, faces; EPSG:4978), the cameras as a Metashape XML, the detections as one `.geojson` per image.  The mesh is brought into
+the cameras' frame, its covering meshes (`export_covering_meshes(N=50, z_buffer=(0, 1 * local_scale), subsample=2)`) bound the
+rays, and `triangulate_detections` does the rest.  Written under `output_dir`: `boundary_ceiling.npz` and `boundary_floor.npz`
+(points, faces), `tree_locations.npy` ((M, 3): lat / lon / alt with pyproj, else local coordinates) and the stage files of
+`triangulate_detections`.  Not carried over: `.ply` and `.gpkg` output and the `--vis` cylinders (pyvista, geopandas)."""
+import argparse
+import logging
+import typing
+from pathlib import Path
+
+import numpy as np
+
+from geograypher_amd.utils.geometric import get_scale_from_transform
+
+TRANSFORMS = {
+    None: None,
+    "square": lambda x: x**2,
+    "cube": lambda x: x**3,
+}
+COVERING_N = 50          # grid points a side of the two boundary surfaces
+COVERING_SUBSAMPLE = 2   # every second mesh vertex
+FLOOR_BUFFER_METERS = 1.0
+LIMIT_RAY_LENGTH_METERS = 160
+LIMIT_ANGLE_FROM_VERT = np.deg2rad(50)
+
+
+def multiview_detections(
+    images_dir: typing.Optional[Path],
+    detections_dir: typing.Optional[Path],
+    camera_file: typing.Optional[Path],
+    mesh_file,
+    output_dir: Path,
+    original_image_folder: typing.Optional[Path] = None,
+    similarity_threshold_meters: float = 0.1,
+    louvain_resolution: float = 2.0,
+    transform=None,
+    geo_file_extension: str = ".geojson",
+    seed=None,
+    camera_set=None,
+    detector=None,
+    backend=None,
+) -> np.ndarray:
+    """Triangulate object locations from detections in many images (see the module docstring for inputs and files).
+    `mesh_file`: a `.npz` path or a (points, faces) pair.  Beyond the reference's arguments: `seed` (Louvain), and `camera_set`,
+    `detector` and `backend`, which replace the objects built from `camera_file`, `detections_dir` and the device.  Returns the
+    (M, 3) points that `tree_locations.npy` holds."""
+    from geograypher_amd.meshes.meshes import TexturedPhotogrammetryMesh
+
+    logger = logging.getLogger(__name__)
+    output_dir = Path(output_dir)
+    output_dir.mkdir(parents=True, exist_ok=True)
+    if camera_set is None:
+        from geograypher_amd.cameras.derived_cameras import MetashapeCameraSet
+
+        camera_set = MetashapeCameraSet(camera_file=camera_file, image_folder=images_dir,
+                                        original_image_folder=original_image_folder, validate_images=True)
+    local_to_epsg_4978 = camera_set.get_local_to_epsg_4978_transform()
+
+    # the cameras live in the photogrammetry frame: bring the mesh there
+    mesh = TexturedPhotogrammetryMesh(mesh_file, backend=backend, log_level="ERROR")
+    mesh.get_mesh_in_cameras_coords(camera_set, inplace=True)
+    backend = mesh.backend   # one device context for the covering meshes, the ray clip and the ray-pair graph
+
+    # the ceiling follows the mesh's highest points, the floor lies FLOOR_BUFFER_METERS above its lowest (in local units)
+    local_scale = 1 / get_scale_from_transform(local_to_epsg_4978)
+    ceiling, floor = mesh.export_covering_meshes(N=COVERING_N, z_buffer=(0, FLOOR_BUFFER_METERS * local_scale),
+                                                 subsample=COVERING_SUBSAMPLE)
+    np.savez(output_dir / "boundary_ceiling.npz", points=ceiling[0], faces=ceiling[1])
+    np.savez(output_dir / "boundary_floor.npz", points=floor[0], faces=floor[1])
+    logger.info("Boundary meshes saved")
+
+    if detector is None:
+        from geograypher_amd.predictors.derived_segmentors import RegionDetectionSegmentor
+
+        detector = RegionDetectionSegmentor(base_folder=images_dir, lookup_folder=detections_dir, label_key=None, class_map=None,
+                                            geo_file_extension=geo_file_extension)
+    points = camera_set.triangulate_detections(
+        detector=detector, boundaries=(ceiling, floor), limit_ray_length_meters=LIMIT_RAY_LENGTH_METERS,
+        limit_angle_from_vert=LIMIT_ANGLE_FROM_VERT, similarity_threshold_meters=similarity_threshold_meters,
+        transform=transform, louvain_resolution=louvain_resolution, out_dir=output_dir, seed=seed, backend=backend)
+    np.save(output_dir / "tree_locations.npy", points)
+    logger.info("Saved %d triangulated locations to %s", len(points), output_dir / "tree_locations.npy")
+    return points
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description="Triangulate object locations from per-image detections.",
+                                     formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("--images-dir", type=Path, required=True, help="Directory containing the raw (possibly nested) images")
+    parser.add_argument("--detections-dir", type=Path, required=True,
+                        help="Directory of detection files, one per image, nested as --images-dir is")
+    parser.add_argument("--camera-file", type=Path, required=True, help="Metashape XML with camera calibrations and positions")
+    parser.add_argument("--mesh-file", type=Path, required=True, help="Mesh as .npz (points, faces) in EPSG:4978")
+    parser.add_argument("--output-dir", type=Path, required=True, help="Output directory")
+    parser.add_argument("--original-image-folder", type=Path,
+                        help="Removed from the beginning of the absolute image paths stored in --camera-file")
+    parser.add_argument("--geo-file-extension", default=".geojson", help="Suffix of the detection files")
+    parser.add_argument("--similarity-threshold-meters", type=float, default=4.0, help="Ray intersection threshold in meters")
+    parser.add_argument("--louvain-resolution", type=float, default=2.0,
+                        help="Louvain resolution parameter, larger value = smaller communities")
+    parser.add_argument("--nonlinearity", choices=[k for k in TRANSFORMS if k], default=None,
+                        help="Transform of the intersection distance x before the graph weight 1 / x is formed")
+    parser.add_argument("--seed", type=int, help="Seed of the Louvain communities")
+    args = parser.parse_args(argv)
+    for path, kind in ((args.images_dir, "is_dir"), (args.detections_dir, "is_dir"), (args.camera_file, "is_file"),
+                       (args.mesh_file, "is_file")):
+        if not getattr(path, kind)():
+            parser.error(f"{path} doesn't exist")
+    return args
+
+
+def main(argv=None):
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)s] %(message)s", datefmt="%Y-%m-%d %H:%M:%S")
+    args = parse_args(argv)
+    multiview_detections(
+        images_dir=args.images_dir, detections_dir=args.detections_dir, camera_file=args.camera_file, mesh_file=args.mesh_file,
+        output_dir=args.output_dir, original_image_folder=args.original_image_folder,
+        similarity_threshold_meters=args.similarity_threshold_meters, louvain_resolution=args.louvain_resolution,
+        transform=TRANSFORMS[args.nonlinearity], geo_file_extension=args.geo_file_extension, seed=args.seed)
+
+
+if __name__ == "__main__":
+    main()

@@ -359,6 +359,19 @@ class TexturedPhotogrammetryMesh:
             return None
         return mesh
 
+    def export_covering_meshes(self, N: int, z_buffer: tuple = (0, 0), subsample: typing.Union[int, None] = None):
+        """Upper and lower covering surface of `self.points` (reference: meshes.py:2399-2482): an (N, N) grid over the mesh's
+        (x, y) extent, every grid point at the highest (+ z_buffer[0]) and the lowest (+ z_buffer[1]) vertex of its cell,
+        `subsample` visiting points[::subsample].  Returns ((upper_points, upper_faces), (lower_points, lower_faces)) in
+        place of the reference's two pv.PolyData: the pairs `triangulate_detections(boundaries=...)` takes.  The device does
+        the work; rule, errors and the one divergence (Delaunay diagonals) are those of
+        `geograypher_amd.utils.geometric.covering_meshes`."""
+        from geograypher_amd.utils.geometric import covering_meshes
+
+        # (an empty mesh and arguments that raise need no device: the backend is not created for them)
+        backend = self.backend if len(self.points) and len(z_buffer) == 2 and int(N) >= 2 else None
+        return covering_meshes(self.points, N, z_buffer, subsample, backend=backend)
+
     def _ensure_uploaded(self, mesh: LocalMesh, backend=None):
         """Upload `mesh` to `backend` (default: the first) unless that device already holds exactly these arrays.  The cache
         holds strong references and compares identity (`is`) of the point and face arrays: a different array -- also one

@@ -2,7 +2,8 @@
 polygons of `label_polygons` (`PlanarPolygons`, the 1e-6 m grid).
 
 This package has no pyvista: a boundary surface is a `(points (V, 3) float, faces (F, 3) int)` pair, and the ray / surface
-intersection runs on the device (`HipRaster.clip_rays`, gr_rays_clip: brute force over a coarse covering mesh).
+intersection runs on the device (`HipRaster.clip_rays`, gr_rays_clip: brute force over a coarse covering mesh).  The covering
+meshes themselves come from `covering_meshes` (`HipRaster.points_bounds`, `HipRaster.cover_grid`).
 """
 from __future__ import annotations
 
@@ -67,6 +68,91 @@ def clip_line_segments(boundaries, origins: np.ndarray, directions: np.ndarray,
     with np.errstate(invalid="ignore", divide="ignore"):
         new_directions = (pt1 - pt0) / np.linalg.norm(pt1 - pt0, axis=1, keepdims=True)
     return pt0, pt1, new_directions, np.asarray(image_indices)[keep]
+
+
+COVER_FACE_WARN_N = 181   # 2 (N - 1)^2 triangles of a full N x N surface stay within gr_rays_clip's 65 536 up to here
+
+
+def _delaunay_faces(xy: np.ndarray) -> np.ndarray:
+    """(F, 3) int32 Delaunay triangles of planar points; (0, 3) for fewer than three points or points on one line."""
+    empty = np.zeros((0, 3), dtype=np.int32)
+    if len(xy) < 3:
+        return empty
+    d = xy - xy[0]
+    if np.linalg.matrix_rank(d) < 2:   # all on one line (or one point): Qhull would refuse
+        return empty
+    from scipy.spatial import Delaunay, QhullError
+
+    try:
+        return np.ascontiguousarray(Delaunay(xy).simplices, dtype=np.int32)
+    except QhullError:   # numerically flat input the rank test let through
+        return empty
+
+
+def covering_meshes(points, N: int, z_buffer=(0, 0), subsample: typing.Optional[int] = None, backend=None):
+    """Two coarse surfaces that enclose a point set from above and below: the boundaries `clip_line_segments` and
+    `triangulate_detections(boundaries=...)` take (reference: TexturedPhotogrammetryMesh.export_covering_meshes,
+    meshes/meshes.py:2399-2482).
+
+    With P = points[::subsample] (all points for None): an N x N grid of (x, y) points, np.linspace over P's x and y extent;
+    grid point (xi, yi) owns the points within half a grid step of it on both axes, bounds included (a point on a shared
+    bound belongs to both neighbours; an axis of zero extent puts every point in all its columns); the upper surface has the
+    grid point at max(z of its points) + z_buffer[0], the lower one at min(z) + z_buffer[1]; grid points without points are
+    dropped.  The extent (`gr_points_bounds`) and the per-cell extremes (`gr_cover_grid`) are computed on the device, in
+    float64 and exactly: the vertices equal the reference's bit for bit.
+
+    Returns ((upper_points (M, 3) float64, upper_faces (F, 3) int32), (lower_points, lower_faces)), vertices in the order
+    xi * N + yi.  The faces are the Delaunay triangulation of the surviving (x, y) (scipy / Qhull); fewer than three
+    survivors, or survivors on one line, give faces of shape (0, 3).  One divergence from the reference: the four corners of
+    a grid square lie on a circle, where VTK's delaunay_2d and Qhull may choose different diagonals -- the vertices are the
+    same, and the two surfaces differ only inside such a square.
+
+    ValueError: len(z_buffer) != 2; N < 2 (the reference divides by zero); a NaN or infinite coordinate among the visited
+    points (in the reference it poisons the extent).  N > 181 logs a warning: a full surface then has more than the 65 536
+    triangles `gr_rays_clip` takes.  Empty `points` returns two empty pairs without touching the device.  `backend`: a
+    `HipRaster` (default: the shared one) or an object with its `points_bounds` and `cover_grid` methods."""
+    if len(z_buffer) != 2:
+        raise ValueError(f"2 buffers (top, bottom) are required, not {len(z_buffer)}")
+    N = int(N)
+    if N < 2:
+        raise ValueError(f"N must be at least 2, got {N}")
+    if subsample is not None and int(subsample) < 1:
+        raise ValueError(f"subsample must be a positive step, got {subsample}")
+    stride = 1 if subsample is None else int(subsample)
+    n_points = int(points.shape[0]) if hasattr(points, "shape") else len(points)
+    if n_points == 0:
+        empty = (np.zeros((0, 3)), np.zeros((0, 3), dtype=np.int32))
+        return empty, (empty[0].copy(), empty[1].copy())
+    if N > COVER_FACE_WARN_N:
+        import logging
+
+        logging.getLogger(__name__).warning(
+            "covering_meshes: N=%d can give a surface of %d triangles, more than the 65536 gr_rays_clip takes", N,
+            2 * (N - 1) ** 2)
+    if backend is None:
+        from geograypher_amd._hip import default_backend
+
+        backend = default_backend()
+    if not hasattr(points, "detach"):
+        points = np.asarray(points, dtype=np.float64)
+    bounds, nonfinite = (_host(x) for x in backend.points_bounds(points, stride))
+    if int(np.asarray(nonfinite).reshape(-1)[0]) != 0:
+        raise ValueError(f"{int(np.asarray(nonfinite).reshape(-1)[0])} of the visited points have a NaN or infinite coordinate")
+    x_min, x_max, y_min, y_max = (np.float64(v) for v in bounds[:4])
+    # the reference's operands, formed as it forms them (meshes.py:2440-2446, 2453-2462)
+    x_grid = np.linspace(x_min, x_max, N)
+    y_grid = np.linspace(y_min, y_max, N)
+    cell_w_half = (x_max - x_min) / (N - 1) / 2
+    cell_h_half = (y_max - y_min) / (N - 1) / 2
+    z_max, z_min, count = (_host(x) for x in backend.cover_grid(points, x_grid - cell_w_half, x_grid + cell_w_half,
+                                                                y_grid - cell_h_half, y_grid + cell_h_half, stride))
+    keep = np.asarray(count).reshape(-1) != 0
+    xi, yi = np.divmod(np.arange(N * N), N)
+    xy = np.column_stack([x_grid[xi], y_grid[yi]])[keep]
+    upper = np.column_stack([xy, np.asarray(z_max, dtype=np.float64).reshape(-1)[keep] + z_buffer[0]])
+    lower = np.column_stack([xy, np.asarray(z_min, dtype=np.float64).reshape(-1)[keep] + z_buffer[1]])
+    faces = _delaunay_faces(xy)
+    return (upper, faces), (lower, faces.copy())
 
 
 # -- label_polygons: planar polygons and the 1e-6 m grid (DESIGN.md "Polygon labels") ---------------------------------------------

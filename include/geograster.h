@@ -337,6 +337,27 @@ int gr_ray_pairs_tile(int64_t tile, int64_t tiles_per_side, int64_t *row_h, int6
  * ray.  hit: n int32 (1 / 0); t: n f64; hit_points: n x 3 f64 = origin + t direction (NaN where hit is 0).  Only enqueues work. */
 int gr_rays_clip(gr_ctx *ctx, const double *origins, const double *directions, int64_t n, const double *points, int64_t V,
                  const int32_t *faces, int64_t F, int32_t *hit, double *t, double *hit_points, void *stream);
+/* covering meshes -- the two calls behind export_covering_meshes (meshes/meshes.py:2399-2482), whose boundary surfaces
+ * gr_rays_clip takes.  Neither needs an uploaded mesh; both only enqueue work.  Both visit rows 0, stride, 2 stride, ... of
+ * points (V x 3 f64; stride >= 1: the reference's points[::subsample]); V <= 0 or stride < 1 is GR_EINVAL.  A visited row
+ * with a NaN or infinite coordinate takes part in neither call's result.
+ * gr_points_bounds replaces the four full-array min / max of meshes.py:2435-2436: bounds6 (6 f64) receives xmin xmax ymin ymax
+ * zmin zmax over the visited finite rows (+inf / -inf when there is none), nonfinite (one uint64) the number of visited rows
+ * that are not finite.  A reduction per workgroup into context scratch (64 KiB, allocated by the first call), then one
+ * combine.  Added without a GR_VERSION bump. */
+int gr_points_bounds(gr_ctx *ctx, const double *points, int64_t V, int64_t stride, double *bounds6, uint64_t *nonfinite,
+                     void *stream);
+/* gr_cover_grid replaces the N^2 masked passes over all points of meshes.py:2453-2469.  x_lo, x_hi, y_lo, y_hi: N f64 each,
+ * the cells' bounds as the CALLER computed them (the reference's x_grid -+ cell_w_half, y_grid -+ cell_h_half, so that they are
+ * its operands bit for bit); a row belongs to cell (xi, yi), flat index xi * N + yi, iff x_lo[xi] <= x <= x_hi[xi] and
+ * y_lo[yi] <= y <= y_hi[yi] -- to one, two or four cells of a regular table, to every column of an axis of zero extent.
+ * z_max, z_min (N x N f64): the largest / smallest z among the cell's members, NaN for a cell without any; count (N x N
+ * uint32): its members.  All three are written by the call (in between z_max and z_min hold integer keys of the doubles,
+ * which unsigned max / min atomics order); the results are exact and do not depend on scheduling, except that a cell whose
+ * extreme is a zero may report either sign when both occur.  2 <= N <= 1024, else GR_EINVAL; accumulators in LDS for N <= 56,
+ * global atomics above.  No context scratch.  Added without a GR_VERSION bump. */
+int gr_cover_grid(gr_ctx *ctx, const double *points, int64_t V, int64_t stride, int N, const double *x_lo, const double *x_hi,
+                  const double *y_lo, const double *y_hi, double *z_max, double *z_min, uint32_t *count, void *stream);
 
 /* distortion warp of an image through a cached sampling map (row f1) -- replaces utils/image.py:72-126
  * (flexible_inputs_warp -> skimage.transform.warp, mode "constant") as called by cameras.py:1092-1156 for the face-id
