@@ -70,6 +70,13 @@ GR_POLY_STAT_TESTED = 0
 GR_POLY_STAT_CONTRIBUTING = 1
 GR_POLY_STAT_LARGEST_RING = 2
 GR_POLY_STAT_WORDS = 4
+# words of face_polygon_index's statistics block, the largest cell grid it takes
+GR_FPI_STAT_TESTED = 0
+GR_FPI_STAT_LABELLED = 1
+GR_FPI_STAT_LONGEST_LIST = 2
+GR_FPI_STAT_BAD_FACES = 3
+GR_FPI_STAT_WORDS = 4
+GR_FPI_MAX_CELLS = 16777216
 
 
 class StageTimes(ctypes.Structure):
@@ -150,6 +157,8 @@ _SIGNATURES = {
     "gr_argmax_nonzero": [_vp, _vp, _i32, _i64, _i32, _vp, _vp],
     "gr_argmax_nonzero_f64": [_vp, _vp, _i64, _i32, _vp, _vp],
     "gr_polygon_class_weights": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
+    "gr_face_polygon_index": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32,
+                              _vp, _vp, _i64, _vp, _vp, _vp],
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -850,6 +859,53 @@ class HipRaster:
                    int(rv_t.shape[0]), off_t.data_ptr(), rp_t.data_ptr(), rh_t.data_ptr(), R, box_t.data_ptr(), P,
                    GR_POLY_WITHIN if within else GR_POLY_OVERLAY, C, weights.data_ptr(), stats.data_ptr(), self._stream())
         return weights, stats
+
+    # -- vector textures: the polygon row of every face centre -----------------------------------------------------
+    def face_polygon_index(self, verts_q, faces, ring_vertices, ring_offsets, ring_polygon, ring_is_hole, polygon_boxes,
+                           cell_table, check: bool = True):
+        """gr_face_polygon_index (DESIGN.md "Vector textures"): verts_q (V, 2) int64 snapped vertices, faces (F, 3) int, the
+        snapped ring table of `PlanarPolygons.snapped` (the hole flags play no part: even-odd over all rings of a row) and
+        cell_table = (grid (6,) int: x0 y0 cell_w cell_h nx ny, cell_offsets (nx ny + 1,) int64, cell_polygons int32) of
+        `utils.geometric.polygon_cell_table` -- numpy or device tensors -> (face_polygon (F,) int32 tensor: the highest row whose
+        closed region holds the face centre, -1 for none; stats (GR_FPI_STAT_WORDS,) int64 tensor: ring walks started, faces
+        labelled, longest cell list met, faces with a vertex index outside [0, V)).  `check` (default) reads the statistics
+        back and raises ValueError when a face names a vertex that does not exist; check=False only enqueues."""
+        torch = _torch()
+        vq_t = self._dev(verts_q, torch.int64)
+        f_t = self._dev(faces, torch.int32)
+        rv_t = self._dev(ring_vertices, torch.int64)
+        off_t = self._dev(ring_offsets, torch.int64)
+        rp_t = self._dev(ring_polygon, torch.int32)
+        box_t = self._dev(polygon_boxes, torch.int64)
+        grid, cell_offsets, cell_polygons = cell_table
+        grid = [int(v) for v in np.asarray(grid.cpu() if hasattr(grid, "detach") else grid).reshape(-1)]
+        co_t = self._dev(cell_offsets, torch.int64)
+        cp_t = self._dev(cell_polygons, torch.int32)
+        if vq_t.ndim != 2 or vq_t.shape[1] != 2 or f_t.ndim != 2 or f_t.shape[1] != 3:
+            raise ValueError(f"vertices must be (V, 2) and faces (F, 3), got {tuple(vq_t.shape)} and {tuple(f_t.shape)}")
+        R, P = int(rp_t.shape[0]), int(box_t.shape[0])
+        if rv_t.ndim != 2 or rv_t.shape[1] != 2 or tuple(off_t.shape) != (R + 1,) or box_t.ndim != 2 or box_t.shape[1] != 4:
+            raise ValueError(f"ring table must be (N, 2) vertices, (R + 1,) offsets, (R,) polygons and (P, 4) boxes, got "
+                             f"{tuple(rv_t.shape)}, {tuple(off_t.shape)}, {tuple(rp_t.shape)} and {tuple(box_t.shape)}")
+        if len(grid) != 6:
+            raise ValueError(f"the cell grid is (x0, y0, cell_w, cell_h, nx, ny), got {len(grid)} values")
+        x0, y0, cw, ch, nx, ny = grid
+        # (the library checks the grid's ranges; the table's length has to fit the grid before its pointer is handed over)
+        if 1 <= nx and 1 <= ny and nx * ny <= GR_FPI_MAX_CELLS and tuple(co_t.shape) != (nx * ny + 1,):
+            raise ValueError(f"gr_face_polygon_index: a {nx} x {ny} cell grid needs {nx * ny + 1} cell offsets, got {tuple(co_t.shape)}")
+        if abs(nx) >= 2 ** 31 or abs(ny) >= 2 ** 31:
+            raise ValueError(f"gr_face_polygon_index: bad cell grid nx={nx} ny={ny}")
+        F = int(f_t.shape[0])
+        out = torch.empty((F,), dtype=torch.int32, device=self.device)
+        stats = torch.empty((GR_FPI_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        self._call("gr_face_polygon_index", vq_t.data_ptr(), int(vq_t.shape[0]), f_t.data_ptr(), F, rv_t.data_ptr(),
+                   int(rv_t.shape[0]), off_t.data_ptr(), rp_t.data_ptr(), R, box_t.data_ptr(), P, x0, y0, cw, ch, nx, ny,
+                   co_t.data_ptr(), cp_t.data_ptr(), int(cp_t.shape[0]), out.data_ptr(), stats.data_ptr(), self._stream())
+        if check:
+            n_bad = int(stats[GR_FPI_STAT_BAD_FACES].item())
+            if n_bad:
+                raise ValueError(f"gr_face_polygon_index: {n_bad} faces name a vertex outside [0, {int(vq_t.shape[0])})")
+        return out, stats
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):

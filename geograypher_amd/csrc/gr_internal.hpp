@@ -12,6 +12,7 @@
 //   equirect.hip     360-degree photos: perspective views resampled from an equirectangular image (k_equirect_view)
 //   cover.hip        covering meshes: bounds of a point set (k_points_bounds), highest / lowest member per grid cell (k_cover_grid); no mesh needed
 //   polygons.hip     label_polygons: weighted face area per (polygon, class), exact containment or clipped overlay (k_polygon_weights); no mesh needed
+//                    vector textures: the polygon row of every face centre through a cell index (k_face_polygon_index)
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 

@@ -1,7 +1,9 @@
 // geograypher_amd/csrc/polygons.hip -- label_polygons on the device: the weighted area every mesh face contributes to every
-// polygon, summed per (polygon, class) (gr_polygon_class_weights; the rule-set is DESIGN.md "Polygon labels").  Needs no
-// uploaded mesh: the caller hands over the faces as snapped integer triangles.
+// polygon, summed per (polygon, class) (gr_polygon_class_weights; the rule-set is DESIGN.md "Polygon labels"), and the polygon row
+// every face CENTRE lies in (gr_face_polygon_index, at the end of the file; DESIGN.md "Vector textures").  Neither needs an
+// uploaded mesh: the caller hands over snapped integer coordinates.
 //
+// gr_polygon_class_weights:
 // Shape: face-major, one face per lane.  The ring table is walked WAVE-UNIFORMLY: ring r, its polygon, the polygon's box and
 // every ring vertex have the same address in all lanes (scalar loads), so the only divergence is the execution mask of the lanes
 // whose box misses the polygon's -- and a wave none of whose faces meets the box skips the ring after one ballot.  A face's
@@ -236,6 +238,100 @@ __global__ __launch_bounds__(256) void k_polygon_weights(const int64_t *__restri
   }
 }
 
+// ---- gr_face_polygon_index: the polygon row each face CENTRE lies in (DESIGN.md "Vector textures", V3-V5) -------------------------
+struct FaceIndexArgs {
+  int64_t F, V, n_rv, n_cp;
+  int64_t gx0, gy0, cw, ch;   // the cell grid, in the 3 q units of the query point
+  int R, P, nx, ny;
+};
+
+__device__ __forceinline__ double wave_max(double v) {
+  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  return v;
+}
+
+// V4: is (px, py) = 3 x centre in the closed region of row p?  On an edge or vertex of any ring, or an odd count of crossings right
+// of the point over all rings.  The rings of a row are consecutive in rpoly (non-decreasing): the first one by binary search.
+__device__ __forceinline__ bool row_contains(const int64_t *__restrict__ rv, const int64_t *__restrict__ roff,
+                                             const int32_t *__restrict__ rpoly, const FaceIndexArgs &a, int p, int64_t px, int64_t py) {
+  int lo = 0, hi = a.R;
+  while (lo < hi) {
+    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+    if (rpoly[mid] < p) lo = mid + 1; else hi = mid;
+  }
+  int parity = 0;
+  for (int r = lo; r < a.R && rpoly[r] == p; ++r) {
+    int64_t i0 = roff[r], i1 = roff[r + 1];
+    i0 = min(max(i0, (int64_t)0), a.n_rv); i1 = min(max(i1, i0), a.n_rv);   // a bad offset table reads nothing outside the vertices
+    const int64_t n = i1 - i0;
+    if (n < 3) continue;
+    const int64_t *v = rv + i0 * 2;
+    int64_t ax = 3 * v[2 * (n - 1)], ay = 3 * v[2 * (n - 1) + 1];
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t bx = 3 * v[2 * i], by = 3 * v[2 * i + 1];
+      const bool cross = (ay <= py) != (by <= py);   // half-open in y: a horizontal edge never counts
+      const bool in_box = min(ax, bx) <= px && px <= max(ax, bx) && min(ay, by) <= py && py <= max(ay, by);
+      if (cross || in_box) {
+        const i128 o = orient(ax, ay, bx, by, px, py);
+        if (o == 0 && in_box) return true;             // on the boundary (a crossing edge with o == 0 holds the point in its box)
+        if (cross && (o > 0) == (by > ay)) parity ^= 1;   // strictly left of the edge taken upwards
+      }
+      ax = bx; ay = by;
+    }
+  }
+  return parity != 0;
+}
+
+// vq [V][2] snapped vertices; faces [F][3]; rv, roff, rpoly, pbox: the ring table; coff [nx ny + 1], cpoly [n_cp]: per cell the rows
+// whose box meets it, DESCENDING; out [F]; stats [GR_FPI_STAT_WORDS].  One face per lane; the lane walks the list of ITS cell and
+// stops at the first row that contains the centre (V5: the highest row wins).
+__global__ __launch_bounds__(256) void k_face_polygon_index(const int64_t *__restrict__ vq, const int32_t *__restrict__ faces,
+                                                            const int64_t *__restrict__ rv, const int64_t *__restrict__ roff,
+                                                            const int32_t *__restrict__ rpoly, const int64_t *__restrict__ pbox,
+                                                            const int64_t *__restrict__ coff, const int32_t *__restrict__ cpoly,
+                                                            int32_t *__restrict__ out, unsigned long long *__restrict__ stats,
+                                                            FaceIndexArgs a) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  unsigned long long tested = 0, labelled = 0, longest = 0, bad = 0;
+  if (f < a.F) {
+    const int64_t v0 = faces[f * 3], v1 = faces[f * 3 + 1], v2 = faces[f * 3 + 2];
+    int found = -1;
+    if (v0 < 0 || v0 >= a.V || v1 < 0 || v1 >= a.V || v2 < 0 || v2 >= a.V) {
+      bad = 1;   // reported, never dereferenced
+    } else {
+      const int64_t px = vq[v0 * 2] + vq[v1 * 2] + vq[v2 * 2], py = vq[v0 * 2 + 1] + vq[v1 * 2 + 1] + vq[v2 * 2 + 1];
+      const int64_t dx = px - a.gx0, dy = py - a.gy0;
+      const int64_t ix = dx >= 0 ? dx / a.cw : -1, iy = dy >= 0 ? dy / a.ch : -1;
+      if (ix >= 0 && ix < a.nx && iy >= 0 && iy < a.ny) {   // a centre outside the grid is in no box
+        const int64_t cell = iy * a.nx + ix;
+        int64_t j0 = coff[cell], j1 = coff[cell + 1];
+        j0 = min(max(j0, (int64_t)0), a.n_cp); j1 = min(max(j1, j0), a.n_cp);
+        longest = (unsigned long long)(j1 - j0);
+        for (int64_t j = j0; j < j1; ++j) {
+          const int p = cpoly[j];
+          if (p < 0 || p >= a.P) continue;
+          const int64_t *b = pbox + (int64_t)p * 4;
+          if (px < 3 * b[0] || px > 3 * b[2] || py < 3 * b[1] || py > 3 * b[3]) continue;
+          ++tested;
+          if (row_contains(rv, roff, rpoly, a, p, px, py)) { found = p; break; }
+        }
+      }
+    }
+    out[f] = found;
+    labelled = found >= 0 ? 1 : 0;
+  }
+  // statistics: one atomic per wave and word
+  const double ts = wave_sum((double)tested), ls = wave_sum((double)labelled), bs = wave_sum((double)bad);   // < 2^53: exact
+  const double lm = wave_max((double)longest);
+  if (lane == 0) {
+    if (ts > 0.0) atomicAdd(&stats[GR_FPI_STAT_TESTED], (unsigned long long)ts);
+    if (ls > 0.0) atomicAdd(&stats[GR_FPI_STAT_LABELLED], (unsigned long long)ls);
+    if (lm > 0.0) atomicMax(&stats[GR_FPI_STAT_LONGEST_LIST], (unsigned long long)lm);
+    if (bs > 0.0) atomicAdd(&stats[GR_FPI_STAT_BAD_FACES], (unsigned long long)bs);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -262,6 +358,39 @@ int gr_polygon_class_weights(gr_ctx *c, const int64_t *tri, const int32_t *face_
   a.F = F; a.n_rv = n_ring_vertices; a.R = (int)R; a.P = (int)P; a.C = C; a.mode = mode;
   hipLaunchKernelGGL(k_polygon_weights, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, tri, face_class, face_weight, ring_vertices,
                      ring_offsets, ring_polygon, ring_is_hole, polygon_boxes, weights, (unsigned long long *)stats, a);
+  GR_HIP(c, hipGetLastError());
+  return GR_OK;
+}
+
+int gr_face_polygon_index(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_t *faces, int64_t F,
+                          const int64_t *ring_vertices, int64_t n_ring_vertices, const int64_t *ring_offsets,
+                          const int32_t *ring_polygon, int64_t R, const int64_t *polygon_boxes, int64_t P, int64_t grid_x0,
+                          int64_t grid_y0, int64_t cell_w, int64_t cell_h, int nx, int ny, const int64_t *cell_offsets,
+                          const int32_t *cell_polygons, int64_t n_cell_polygons, int32_t *face_polygon, uint64_t *stats,
+                          void *stream) {
+  if (!c) return GR_EINVAL;
+  if (F < 0 || V < 0 || R < 0 || P < 0 || n_ring_vertices < 0 || n_cell_polygons < 0 || F > 0x7FFFFFFFll * 256 ||
+      V > 0x7FFFFFFFll || R > 0x7FFFFFFF || P > 0x7FFFFFFF)
+    return fail(c, GR_EINVAL, "gr_face_polygon_index: bad shape F=%lld V=%lld R=%lld P=%lld", (long long)F, (long long)V,
+                (long long)R, (long long)P);
+  if (nx < 1 || ny < 1 || (int64_t)nx * ny > GR_FPI_MAX_CELLS || cell_w < 1 || cell_h < 1)
+    return fail(c, GR_EINVAL, "gr_face_polygon_index: bad cell grid nx=%d ny=%d (1 <= nx ny <= %d) cell=%lld x %lld (>= 1)", nx, ny,
+                (int)GR_FPI_MAX_CELLS, (long long)cell_w, (long long)cell_h);
+  if (!stats || !cell_offsets || (F > 0 && (!faces || !face_polygon)) || (V > 0 && !verts_q) ||
+      (n_cell_polygons > 0 && !cell_polygons) || (P > 0 && !polygon_boxes) ||
+      (R > 0 && (!ring_offsets || !ring_polygon || (n_ring_vertices > 0 && !ring_vertices))))
+    return fail(c, GR_EINVAL, "gr_face_polygon_index: null arrays");
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
+  GR_HIP(c, hipMemsetAsync(stats, 0, sizeof(uint64_t) * GR_FPI_STAT_WORDS, s));
+  if (F == 0) return GR_OK;
+  FaceIndexArgs a;
+  a.F = F; a.V = V; a.n_rv = n_ring_vertices; a.n_cp = n_cell_polygons;
+  a.gx0 = grid_x0; a.gy0 = grid_y0; a.cw = cell_w; a.ch = cell_h;
+  a.R = (int)R; a.P = (int)P; a.nx = nx; a.ny = ny;
+  hipLaunchKernelGGL(k_face_polygon_index, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, verts_q, faces, ring_vertices,
+                     ring_offsets, ring_polygon, polygon_boxes, cell_offsets, cell_polygons, face_polygon,
+                     (unsigned long long *)stats, a);
   GR_HIP(c, hipGetLastError());
   return GR_OK;
 }

@@ -1,0 +1,146 @@
+"""Render image-based labels from geospatial ground truth: polygons (species, crown ids) -> a label per mesh face -> a label image
+per camera.
+
+Mirror of geograypher/entrypoints/render_labels.py:21-204 in the formats this package reads: the mesh as `.npz` (points, faces;
+EPSG:4978), the cameras as a Metashape XML, the texture as an array, a `.npy` file or a `.geojson` of Polygon / MultiPolygon
+features in a planar CRS.  A vector texture also needs `texture_points_file`: a `.npy` with the mesh vertices (V, 3) in the
+polygons' CRS (the reference reprojects them with pyproj).  Every face takes the value of the highest feature that holds its centre
+(`TexturedPhotogrammetryMesh.get_values_for_faces_from_vector`, on the device); `save_renders` writes one label image per camera under
+`render_savefolder`, at the cameras' paths relative to `image_folder`, and `IDs_to_labels.json` beside them.  Not carried over: the DTM
+ground class, ROI cropping of mesh and cameras, mesh decimation, saving the image subset or the textured mesh, and the
+visualisations (rasterio, geopandas, pyvista, matplotlib)."""
+import argparse
+import json
+import typing
+from math import ceil
+from pathlib import Path
+
+import numpy as np
+
+from geograypher_amd.constants import PATH_TYPE
+
+
+def render_labels(
+    mesh_file,
+    cameras_file: PATH_TYPE,
+    image_folder: PATH_TYPE,
+    texture: typing.Union[PATH_TYPE, np.ndarray, None],
+    render_savefolder: PATH_TYPE,
+    mesh_CRS,
+    original_image_folder: typing.Union[PATH_TYPE, None] = None,
+    subset_images_savefolder: typing.Union[PATH_TYPE, None] = None,
+    texture_column_name: typing.Union[str, None] = None,
+    DTM_file: typing.Union[PATH_TYPE, None] = None,
+    ground_height_threshold: typing.Union[float, None] = None,
+    render_ground_class: bool = False,
+    textured_mesh_savefile: typing.Union[PATH_TYPE, None] = None,
+    ROI=None,
+    mesh_ROI_buffer_radius_meters: float = 50,
+    cameras_ROI_buffer_radius_meters: float = 150,
+    IDs_to_labels: typing.Union[dict, None] = None,
+    render_image_scale: float = 1,
+    mesh_downsample: float = 1,
+    n_cameras_per_chunk: typing.Union[int, None] = None,
+    cast_to_uint8: bool = True,
+    save_as_npy: bool = False,
+    vis: bool = False,
+    mesh_vis_file: typing.Union[PATH_TYPE, None] = None,
+    labels_vis_folder: typing.Union[PATH_TYPE, None] = None,
+    texture_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
+    apply_distortion: bool = True,
+    camera_set=None,
+    backend=None,
+):
+    """Render the labels of `texture` into every camera's view (see the module docstring for inputs and files).  The reference's
+    arguments and defaults; `DTM_file`, `ROI`, `mesh_downsample != 1`, `subset_images_savefolder`, `textured_mesh_savefile`, `vis`,
+    `mesh_vis_file` and `labels_vis_folder` raise NotImplementedError.  `n_cameras_per_chunk` selects
+    `TexturedPhotogrammetryMeshChunked` with ceil(cameras / n_cameras_per_chunk) clusters, as in the reference (the GPU path
+    renders the whole mesh either way).  Beyond the reference: `texture_points_file` (a `.npy` path or the array itself, required
+    for a vector texture), `apply_distortion` (False for a camera set without a lens model), and `camera_set` and `backend`,
+    which replace the objects built from `cameras_file` and the device.  Returns the textured mesh."""
+    from geograypher_amd.meshes import TexturedPhotogrammetryMesh, TexturedPhotogrammetryMeshChunked
+
+    for name, value, why in (
+        ("DTM_file", DTM_file, "DTM rasters need rasterio"),
+        ("ROI", ROI, "ROI cropping needs geopandas"),
+        ("subset_images_savefolder", subset_images_savefolder, "copying the image subset is not part of this package"),
+        ("textured_mesh_savefile", textured_mesh_savefile, "mesh writers (pyvista) are not part of this package"),
+        ("mesh_vis_file", mesh_vis_file, "visualisations need pyvista"),
+        ("labels_vis_folder", labels_vis_folder, "visualisations need matplotlib"),
+    ):
+        if value is not None:
+            raise NotImplementedError(f"{name}: {why}, which is outside the projection path")
+    if vis:
+        raise NotImplementedError("vis: visualisations need pyvista, which is outside the projection path")
+    if mesh_downsample != 1:
+        raise NotImplementedError("mesh_downsample: mesh decimation is outside the projection path (meshes.py:215-226)")
+
+    if camera_set is None:
+        from geograypher_amd.cameras.derived_cameras import MetashapeCameraSet
+
+        camera_set = MetashapeCameraSet(cameras_file, image_folder, original_image_folder=original_image_folder)
+
+    n_render_chunks = None if n_cameras_per_chunk is None else int(ceil(len(camera_set) / n_cameras_per_chunk))
+    MeshClass = TexturedPhotogrammetryMesh if n_render_chunks is None else TexturedPhotogrammetryMeshChunked
+    mesh = MeshClass(mesh_file, input_CRS=mesh_CRS, IDs_to_labels=IDs_to_labels, backend=backend)
+
+    points_in_polygon_CRS = texture_points_file
+    if isinstance(points_in_polygon_CRS, (str, Path)):
+        points_in_polygon_CRS = np.load(points_in_polygon_CRS)
+    mesh.load_texture(texture, texture_column_name=texture_column_name, IDs_to_labels=mesh.IDs_to_labels,
+                      points_in_polygon_CRS=points_in_polygon_CRS)
+
+    render_kwargs = {} if n_render_chunks is None else {"n_clusters": n_render_chunks}
+    if not apply_distortion:
+        render_kwargs["apply_distortion"] = False
+    mesh.save_renders(camera_set=camera_set, render_image_scale=render_image_scale, save_native_resolution=True,
+                      output_folder=render_savefolder, make_composites=False, cast_to_uint8=cast_to_uint8,
+                      save_as_npy=save_as_npy, **render_kwargs)
+    return mesh
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description="Render labels onto individual images using geospatial textures.",
+                                     formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("--mesh-file", type=Path, required=True, help="Mesh as .npz (points, faces)")
+    parser.add_argument("--mesh-CRS", required=True, help="CRS of the mesh vertices (EPSG:4978)")
+    parser.add_argument("--cameras-file", type=Path, required=True, help="Metashape XML with camera calibrations and positions")
+    parser.add_argument("--image-folder", type=Path, required=True, help="Folder of the images the mesh was made from")
+    parser.add_argument("--texture", type=Path, required=True, help="Texture: a .npy array or a .geojson of polygons")
+    parser.add_argument("--render-savefolder", type=Path, required=True, help="Where the rendered labels are written")
+    parser.add_argument("--texture-points-file", type=Path,
+                        help=".npy with the mesh vertices (V, 3) in the CRS of a .geojson --texture (required for one)")
+    parser.add_argument("--original-image-folder", type=Path,
+                        help="Removed from the beginning of the absolute image paths stored in --cameras-file")
+    parser.add_argument("--subset-images-savefolder", type=Path, help="Not available here")
+    parser.add_argument("--texture-column-name", help="Property of the .geojson features to use as the label")
+    parser.add_argument("--DTM-file", help="Not available here")
+    parser.add_argument("--ground-height-threshold", type=float, default=2.0, help="Only applies with --DTM-file")
+    parser.add_argument("--render-ground-class", action="store_true", help="Only applies with --DTM-file")
+    parser.add_argument("--textured-mesh-savefile", help="Not available here")
+    parser.add_argument("--ROI", help="Not available here")
+    parser.add_argument("--mesh-ROI-buffer-radius-meters", default=50, type=float, help="Only applies with --ROI")
+    parser.add_argument("--cameras-ROI-buffer-radius-meters", default=100, type=float, help="Only applies with --ROI")
+    parser.add_argument("--render-image-scale", type=float, default=1, help="Render at this fraction of the image size")
+    parser.add_argument("--mesh-downsample", type=float, default=1, help="Only 1 is available here")
+    parser.add_argument("--IDs-to-labels", type=Path, help="JSON file {ID: label}")
+    parser.add_argument("--n-cameras-per-chunk", type=int, help="Selects the chunked mesh class, as in the reference")
+    parser.add_argument("--cast-to-uint8", action="store_true", help="Write uint8 labels (else uint16 / uint32)")
+    parser.add_argument("--save-as-npy", action="store_true", help="Write float64 .npy files instead of .tif")
+    parser.add_argument("--vis", action="store_true", help="Not available here")
+    parser.add_argument("--mesh-vis-file", type=Path, help="Not available here")
+    parser.add_argument("--labels-vis-folder", type=Path, help="Not available here")
+    args = parser.parse_args(argv)
+    if args.IDs_to_labels is not None:
+        with open(args.IDs_to_labels, "r") as file:
+            args.IDs_to_labels = {int(k): v for k, v in json.load(file).items()}
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    render_labels(**vars(args))
+
+
+if __name__ == "__main__":
+    main()

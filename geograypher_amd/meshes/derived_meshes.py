@@ -55,6 +55,12 @@ class TexturedPhotogrammetryMeshChunked(TexturedPhotogrammetryMesh):
         return super().aggregate_projected_images(cameras, batch_size=batch_size,
                                                   aggregate_img_scale=aggregate_img_scale, **kwargs)
 
+    def save_renders(self, camera_set, *args, n_clusters: int = 8,
+                     buffer_dist_meters: float = CHUNKED_MESH_BUFFER_DIST_METERS, vis_clusters: bool = False, **kwargs):
+        """The base class's `save_renders`; the chunking arguments the reference's forwards to its chunked `render_flat`
+        (meshes.py:2300-2305 -> derived_meshes.py:153-220) are accepted and ignored."""
+        self._say_unchunked("save_renders", n_clusters, buffer_dist_meters, vis_clusters)
+        return super().save_renders(camera_set, *args, **kwargs)
 
     def label_polygons(self, face_labels, polygons, face_weighting=None, sjoin_overlay: bool = True,
                        return_class_labels: bool = True, unknown_class_label: str = "unknown",

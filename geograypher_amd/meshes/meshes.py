@@ -132,7 +132,8 @@ class TexturedPhotogrammetryMesh:
         (F,3))`, any object with `.points`/`.faces` (pyvista layout accepted) or a `.npz` path.  The coordinates are
         interpreted in `input_CRS`; only EPSG:4978 (the frame the reference reprojects every mesh into,
         meshes.py:1659) is accepted because CRS reprojection is outside the projection path.  Decimation, ROI
-        cropping and vector/raster texture files are likewise outside it and raise NotImplementedError.
+        cropping and vector/raster texture files are likewise outside it and raise NotImplementedError (a `.geojson`
+        texture is loaded afterwards, by `load_texture(..., points_in_polygon_CRS=...)`).
 
         Extra keyword arguments (defaults keep reference behaviour):
             device: GPU index for the HIP backend (default: current torch device).
@@ -211,7 +212,8 @@ class TexturedPhotogrammetryMesh:
         self.IDs_to_labels = IDs_to_labels
         if isinstance(texture, (str, Path)):
             if Path(texture).suffix != ".npy":
-                raise NotImplementedError("only .npy texture files are read here (meshes.py:533-644 is out of scope)")
+                raise NotImplementedError("only .npy texture files are read here; a .geojson texture needs the vertices in "
+                                          "its CRS: load_texture(..., points_in_polygon_CRS=...)")
             texture = np.load(texture)
         if texture is not None:
             self.set_texture(np.asarray(texture))
@@ -327,6 +329,61 @@ class TexturedPhotogrammetryMesh:
             self.set_texture(face_texture, is_vertex_texture=False)
             return self.face_texture
         raise ValueError("Face texture not present and conversion was not requested")
+
+    def remap_texture(self, texture_array: np.ndarray, IDs_to_labels: typing.Union[None, dict] = None,
+                      all_discrete_texture_values=None, update_IDs_to_labels: bool = True, background_ID: int = None):
+        """Texture values -> floats, or IDs of a discrete texture (reference: meshes.py:383-474).  Several columns: cast to
+        float, `self.IDs_to_labels` cleared.  One column: `IDs_to_labels` (default: `determine_IDs_to_labels` of the values,
+        or of `all_discrete_texture_values`) maps labels back to IDs unless its keys equal its values; a value without an ID
+        becomes NaN.  ValueError for a table that is not one-to-one or whose IDs are not ints.  A continuous float column has no
+        table: the reference fails on it with AttributeError (`None.keys()`), and so does this."""
+        from geograypher_amd.utils.indexing import determine_IDs_to_labels
+
+        texture_array = self.standardize_texture(np.asarray(texture_array))
+        if texture_array.shape[1] != 1:
+            self.IDs_to_labels = None
+            return texture_array.astype(float)
+        if IDs_to_labels is None:
+            IDs_to_labels = determine_IDs_to_labels(texture_array, all_discrete_texture_values, background_ID)
+        if list(IDs_to_labels.keys()) != list(IDs_to_labels.values()):
+            labels_to_IDs = {label: ID for ID, label in IDs_to_labels.items()}
+            if len(labels_to_IDs) != len(IDs_to_labels):
+                raise ValueError("IDs_to_labels is not a one-to-one mapping")
+            if not all(isinstance(ID, int) for ID in labels_to_IDs.values()):
+                raise ValueError("The labels to IDs mapping does not produce only ints")
+            texture_array = np.expand_dims(np.array([labels_to_IDs.get(label, np.nan) for label in texture_array.squeeze(axis=1)]),
+                                           axis=1)
+        if update_IDs_to_labels:
+            self.IDs_to_labels = IDs_to_labels
+        return texture_array
+
+    def load_texture(self, texture, texture_column_name=None, IDs_to_labels=None, background_ID=None, *,
+                     points_in_polygon_CRS=None):
+        """Set the face or vertex texture from an array, a `.npy` file or a `.geojson` of polygons (reference: meshes.py:533-644;
+        tried in that order).  texture=None only sets `IDs_to_labels` (there is no texture in the mesh file here).  A vector
+        file goes through `get_values_for_faces_from_vector(texture, texture_column_name, points_in_polygon_CRS=...)`; any
+        other file is taken for a raster, which needs rasterio: NotImplementedError.  The values then pass `remap_texture` (which
+        sets `IDs_to_labels`) and `set_texture`."""
+        if texture is None:
+            self.logger.warning("No texture provided")
+            if IDs_to_labels is not None:
+                self.IDs_to_labels = IDs_to_labels
+            return
+        all_values = None
+        if isinstance(texture, np.ndarray):
+            texture_array = texture
+        elif not isinstance(texture, (str, Path)):
+            raise ValueError(f"Could not load texture for {texture}")
+        elif Path(texture).suffix == ".npy":
+            texture_array = np.load(texture, allow_pickle=True)
+        elif Path(texture).suffix == ".geojson":
+            texture_array, all_values = self.get_values_for_faces_from_vector(texture, texture_column_name,
+                                                                              points_in_polygon_CRS=points_in_polygon_CRS)
+        else:
+            raise NotImplementedError(f"texture file {texture}: raster textures need rasterio, which is outside the projection "
+                                      "path: pass an array, a .npy or a .geojson")
+        self.set_texture(self.remap_texture(texture_array, IDs_to_labels=IDs_to_labels, all_discrete_texture_values=all_values,
+                                            update_IDs_to_labels=True, background_ID=background_ID))
 
     # -- geometry ------------------------------------------------------------------------------------------------
     def get_mesh_hash(self):
@@ -1017,6 +1074,24 @@ class TexturedPhotogrammetryMesh:
             raise ValueError(f"class id {top:.0f} does not fit the int32 class table")
         return to_int(classes), int(top) + 1
 
+    @staticmethod
+    def _snap_with_polygons(verts, polygons):
+        """Rule P3 / V2: (snapped vertices (V, 2) int64, the polygons' snapped ring table), both on the 1e-6 m grid behind ONE
+        integer origin, the middle of their joint bounds."""
+        from geograypher_amd.utils.geometric import SNAP_LIMIT, snap_to_grid
+
+        vq = snap_to_grid(verts[:, :2])
+        lo, hi = (vq.min(axis=0), vq.max(axis=0)) if len(vq) else (np.zeros(2, np.int64), np.zeros(2, np.int64))
+        ring_bounds = polygons.bounds_snapped()
+        if ring_bounds is not None:
+            lo, hi = np.minimum(lo, ring_bounds[0]), np.maximum(hi, ring_bounds[1])
+        origin = lo + (hi - lo) // 2
+        vq = vq - origin
+        if len(vq) and np.abs(vq).max() > SNAP_LIMIT:
+            raise ValueError("a mesh vertex lies more than 2^40 grid steps (1 099 512 m) from the common origin of mesh and "
+                             "polygons")
+        return vq, polygons.snapped(origin)
+
     def label_polygon_weights(self, face_labels, polygons, face_weighting=None, sjoin_overlay: bool = True,
                               return_class_labels: bool = True, unknown_class_label: str = "unknown",
                               buffer_dist_meters: float = 2.0, *, points_in_polygon_CRS=None) -> np.ndarray:
@@ -1024,7 +1099,7 @@ class TexturedPhotogrammetryMesh:
         class c contribute to polygon p (same arguments; `return_class_labels`, `unknown_class_label` and `buffer_dist_meters`
         play no part).  n_classes is the largest finite label + 1.  The pair statistics of the call are left in
         `self.last_polygon_stats` (pairs_tested, pairs_contributing, largest_ring)."""
-        from geograypher_amd.utils.geometric import SNAP_LIMIT, PlanarPolygons, snap_to_grid
+        from geograypher_amd.utils.geometric import PlanarPolygons
 
         face_labels = self._squeezed_1d(face_labels)
         if face_weighting is not None:
@@ -1064,18 +1139,7 @@ class TexturedPhotogrammetryMesh:
         else:
             weight = ratio * np.asarray(face_weighting, dtype=np.float64)
 
-        # rule 3: the 1e-6 m grid behind a common integer origin
-        vq = snap_to_grid(verts[:, :2])
-        lo, hi = (vq.min(axis=0), vq.max(axis=0)) if len(vq) else (np.zeros(2, np.int64), np.zeros(2, np.int64))
-        ring_bounds = polygons.bounds_snapped()
-        if ring_bounds is not None:
-            lo, hi = np.minimum(lo, ring_bounds[0]), np.maximum(hi, ring_bounds[1])
-        origin = lo + (hi - lo) // 2
-        vq = vq - origin
-        if len(vq) and np.abs(vq).max() > SNAP_LIMIT:
-            raise ValueError("a mesh vertex lies more than 2^40 grid steps (1 099 512 m) from the common origin of mesh and "
-                             "polygons")
-        table = polygons.snapped(origin)
+        vq, table = self._snap_with_polygons(verts, polygons)   # rule 3
         tri = vq[self.faces].reshape(-1, 6)
 
         weights, stats = self.backend.polygon_class_weights(tri, classes, weight, *table, n_classes, within=bool(sjoin_overlay))
@@ -1116,6 +1180,84 @@ class TexturedPhotogrammetryMesh:
             predicted_class_IDs = [(IDs_to_labels[int(pi)] if np.isfinite(pi) else unknown_class_label)
                                    for pi in predicted_class_IDs]
         return predicted_class_IDs
+
+    # -- vector textures (DESIGN.md "Vector textures"; reference: meshes.py:990-1079) -----------------------------------------
+    def face_polygon_index(self, polygons, *, points_in_polygon_CRS=None, return_tensor: bool = False):
+        """The polygon row every face CENTRE lies in: (n_faces,) int32, -1 for none; the HIGHEST row where rows overlap, a centre
+        on a polygon's boundary (its holes' included) is inside.  polygons: a `PlanarPolygons` or a sequence its `from_sequence`
+        takes; points_in_polygon_CRS (required, keyword): the mesh vertices (V, 3) in the polygons' planar CRS.  Decided exactly on
+        the 1e-6 m grid (rules V1-V5).  `return_tensor=True` leaves the result on the device.  The statistics of the call are left
+        in `self.last_vector_stats` (pairs_tested, faces_labelled, longest_cell_list, cells)."""
+        from geograypher_amd.utils.geometric import PlanarPolygons, polygon_cell_table
+
+        if points_in_polygon_CRS is None:
+            raise NotImplementedError(
+                "face_polygon_index needs points_in_polygon_CRS: the mesh vertices (V, 3) in the polygons' planar CRS (CRS "
+                "reprojection needs pyproj and is outside the projection path)")
+        if isinstance(polygons, (str, Path)) or hasattr(polygons, "geometry"):
+            raise NotImplementedError(
+                "polygon files and GeoDataFrames need geopandas, which is outside the projection path: pass a PlanarPolygons "
+                "(geograypher_amd.utils.geometric)")
+        if not isinstance(polygons, PlanarPolygons):
+            polygons = PlanarPolygons.from_sequence(polygons)
+        verts = np.asarray(points_in_polygon_CRS, dtype=np.float64)
+        if verts.shape != (self.points.shape[0], 3):
+            raise ValueError(f"points_in_polygon_CRS must be ({self.points.shape[0]}, 3), got {verts.shape}")
+        vq, table = self._snap_with_polygons(verts, polygons)
+        cell_table = polygon_cell_table(table[4])
+        index, stats = self.backend.face_polygon_index(vq, self.faces.astype(np.int32), *table, cell_table)
+        stats = _to_host(stats) if hasattr(stats, "detach") else np.asarray(stats)
+        self.last_vector_stats = {"pairs_tested": int(stats[0]), "faces_labelled": int(stats[1]),
+                                  "longest_cell_list": int(stats[2]), "cells": (int(cell_table[0][4]), int(cell_table[0][5]))}
+        if return_tensor:
+            return index
+        index = _to_host(index) if hasattr(index, "detach") else np.asarray(index)
+        return np.array(index, dtype=np.int32)
+
+    def get_values_for_faces_from_vector(self, vector_source, column_names, *, points_in_polygon_CRS=None):
+        """The value of a polygon column at every face centre (reference: meshes.py:990-1079; rule V6).  vector_source: a
+        `.geojson` path (`PlanarPolygons.from_geojson`) or a `(PlanarPolygons, {column: array})` pair; other files and
+        GeoDataFrames raise NotImplementedError.  column_names: a name, a list of names, or None when there is exactly one
+        column.  A face in no polygon gets "null" (str / object columns), NULL_TEXTURE_INT_VALUE (integer columns) or NaN; the
+        result has the column's dtype (object for strings).  One column returns (labeled_faces, all_values), several return two dicts."""
+        from geograypher_amd.utils.geometric import PlanarPolygons
+
+        if isinstance(vector_source, (tuple, list)) and len(vector_source) == 2 and isinstance(vector_source[1], dict):
+            polygons, properties = vector_source
+        elif isinstance(vector_source, (str, Path)) and Path(vector_source).suffix == ".geojson":
+            polygons, properties = PlanarPolygons.from_geojson(vector_source)
+        else:
+            raise NotImplementedError(
+                "vector files other than .geojson and GeoDataFrames need geopandas, which is outside the projection path: pass "
+                "a .geojson path or a (PlanarPolygons, {column: values}) pair")
+        if column_names is None:
+            if len(properties) != 1:
+                self.logger.error("No column name provided and ambigious which column to use")
+                raise ValueError("No column name provided and ambigious which column to use")
+            column_names = list(properties)
+        elif isinstance(column_names, str):
+            column_names = [column_names]
+        index = self.face_polygon_index(polygons, points_in_polygon_CRS=points_in_polygon_CRS)
+        inside = index >= 0
+        labeled_faces, all_values = {}, {}
+        for name in column_names:
+            column = np.asarray(properties[name])
+            if len(column) != len(polygons):
+                raise ValueError(f"column {name!r} has {len(column)} values for {len(polygons)} polygons")
+            if column.dtype.kind in "US":   # a fixed-width string column would cut "null" short
+                column = column.astype(object)
+            if column.dtype.kind == "O":
+                null_value = "null"
+            elif column.dtype.kind in "iu":
+                null_value = NULL_TEXTURE_INT_VALUE
+            else:
+                null_value = np.nan
+            values = np.full(shape=index.shape[0], dtype=column.dtype, fill_value=null_value)
+            values[inside] = column[index[inside]]
+            labeled_faces[name], all_values[name] = values, column
+        if len(column_names) == 1:
+            return labeled_faces[column_names[0]], all_values[column_names[0]]
+        return labeled_faces, all_values
 
     # -- save_renders (SURVEY.md section 8, row f2) ----------------------------------------------------------------
     def save_IDs_to_labels(self, savepath: PATH_TYPE):

@@ -1,5 +1,5 @@
 """Geometric helpers: the multiview-detection workflow (reference: geograypher/utils/geometric.py:97-106, 144-254) and the planar
-polygons of `label_polygons` (`PlanarPolygons`, the 1e-6 m grid).
+polygons of `label_polygons` and of vector textures (`PlanarPolygons`, the 1e-6 m grid, `polygon_cell_table`).
 
 This package has no pyvista: a boundary surface is a `(points (V, 3) float, faces (F, 3) int)` pair, and the ray / surface
 intersection runs on the device (`HipRaster.clip_rays`, gr_rays_clip: brute force over a coarse covering mesh).  The covering
@@ -274,9 +274,112 @@ class PlanarPolygons:
         return (np.ascontiguousarray(ring_vertices, dtype=np.int64), np.asarray(offsets, dtype=np.int64),
                 np.asarray(rows, dtype=np.int32), np.asarray(holes, dtype=np.int32), boxes)
 
+    @classmethod
+    def from_geojson(cls, path):
+        """(polygons, properties) of a GeoJSON FeatureCollection, parsed with `json`: one row per feature in file order, so row
+        numbers equal feature numbers.  A Polygon feature is [exterior, hole, ...]; a MultiPolygon is a multi-part row (the
+        first ring of every part an exterior); a feature of any other geometry type, or without geometry, keeps its row and
+        has no rings.  A third coordinate is dropped.  properties: {name: (n_features,) array} over the union of the features'
+        property names, None where a feature lacks one: int64 when every value is an int, float64 when every value is a
+        number (bool is neither), otherwise object.  The coordinates are taken as they stand: planar metres, no CRS handling."""
+        import json
+
+        with open(path, "r") as file:
+            data = json.load(file)
+        features = data.get("features") if isinstance(data, dict) else None
+        if not isinstance(features, list):
+            raise ValueError(f"{path} is not a GeoJSON FeatureCollection")
+        rings, rows, holes = [], [], []
+        for row, feature in enumerate(features):
+            geometry = feature.get("geometry") or {}
+            kind = geometry.get("type")
+            parts = {"Polygon": [geometry.get("coordinates")], "MultiPolygon": geometry.get("coordinates")}.get(kind) or []
+            for part in parts:
+                for k, ring in enumerate(part or []):
+                    rings.append(np.asarray(ring, dtype=np.float64)[:, :2])
+                    rows.append(row)
+                    holes.append(k > 0)
+        names = []
+        for feature in features:
+            names += [k for k in (feature.get("properties") or {}) if k not in names]
+        properties = {}
+        for name in names:
+            values = [(feature.get("properties") or {}).get(name) for feature in features]
+            is_int = [isinstance(v, int) and not isinstance(v, bool) for v in values]
+            is_num = [i or isinstance(v, float) for i, v in zip(is_int, values)]
+            dtype = np.int64 if all(is_int) else (np.float64 if all(is_num) else object)
+            column = np.empty(len(values), dtype=dtype)
+            column[:] = values
+            properties[name] = column
+        return cls(rings, rows, holes, n_polygons=len(features)), properties
+
     def bounds_snapped(self):
         """(lo (2,), hi (2,)) int64 of all rings on the grid, before any origin; None without rings."""
         if not self.rings:
             return None
         q = [snap_to_grid(r) for r in self.rings]
         return np.min([v.min(axis=0) for v in q], axis=0), np.max([v.max(axis=0) for v in q], axis=0)
+
+
+# -- vector textures: a uniform cell index over the polygon boxes (DESIGN.md "Vector textures") ------------------------------------
+CELL_GRID_MAX_SIDE = 1024      # cells a side of the chosen grid
+CELL_LIST_BUDGET = 8           # list entries per polygon the chosen grid may spend (a floor of 4096 entries)
+
+
+def _cell_ranges(boxes3, grid):
+    """Per non-empty box the closed range of cells it meets on each axis: (rows, ix0, ix1, iy0, iy1)."""
+    x0, y0, cw, ch, nx, ny = (int(v) for v in grid)
+    rows = np.nonzero((boxes3[:, 0] <= boxes3[:, 2]) & (boxes3[:, 1] <= boxes3[:, 3]))[0]
+    b = boxes3[rows]
+    ix0, ix1 = np.floor_divide(b[:, 0] - x0, cw), np.floor_divide(b[:, 2] - x0, cw)
+    iy0, iy1 = np.floor_divide(b[:, 1] - y0, ch), np.floor_divide(b[:, 3] - y0, ch)
+    keep = (ix1 >= 0) & (ix0 < nx) & (iy1 >= 0) & (iy0 < ny)   # a box beside a grid the caller chose
+    return (rows[keep], np.clip(ix0[keep], 0, nx - 1), np.clip(ix1[keep], 0, nx - 1), np.clip(iy0[keep], 0, ny - 1),
+            np.clip(iy1[keep], 0, ny - 1))
+
+
+def choose_cell_grid(polygon_boxes) -> np.ndarray:
+    """The grid `polygon_cell_table` uses unless told otherwise, (x0, y0, cell_w, cell_h, nx, ny) int64 in units of a THIRD of a
+    grid step (the units of 3 x centre): over the joint bounds of the non-empty boxes, square cells whose side is the median of
+    the boxes' longer sides -- a typical polygon then meets about four cells and a cell about four polygons' boxes --, at most
+    CELL_GRID_MAX_SIDE cells a side; the side is doubled while the lists would hold more than
+    max(CELL_LIST_BUDGET x polygons, 4096) entries (a few polygons that span everything would otherwise be listed in every
+    cell).  A cell is one unit wider than extent / n needs: n cells cover the closed bounds.  No box: one cell."""
+    boxes3 = 3 * np.asarray(polygon_boxes, dtype=np.int64).reshape(-1, 4)
+    live = boxes3[(boxes3[:, 0] <= boxes3[:, 2]) & (boxes3[:, 1] <= boxes3[:, 3])]
+    if len(live) == 0:
+        return np.array([0, 0, 1, 1, 1, 1], dtype=np.int64)
+    x0, y0, x1, y1 = int(live[:, 0].min()), int(live[:, 1].min()), int(live[:, 2].max()), int(live[:, 3].max())
+    side = max(int(np.median(np.maximum(live[:, 2] - live[:, 0], live[:, 3] - live[:, 1]))), 1)
+    while True:
+        nx = int(min(max(-(-(x1 - x0 + 1) // side), 1), CELL_GRID_MAX_SIDE))
+        ny = int(min(max(-(-(y1 - y0 + 1) // side), 1), CELL_GRID_MAX_SIDE))
+        grid = np.array([x0, y0, (x1 - x0) // nx + 1, (y1 - y0) // ny + 1, nx, ny], dtype=np.int64)
+        _, ix0, ix1, iy0, iy1 = _cell_ranges(boxes3, grid)
+        if int(np.sum((ix1 - ix0 + 1) * (iy1 - iy0 + 1))) <= max(CELL_LIST_BUDGET * len(live), 4096) or nx * ny == 1:
+            return grid
+        side *= 2
+
+
+def polygon_cell_table(polygon_boxes, grid=None):
+    """The cell index `HipRaster.face_polygon_index` takes, from the (P, 4) int64 boxes of `PlanarPolygons.snapped`:
+    (grid (6,) int64 x0 y0 cell_w cell_h nx ny -- `choose_cell_grid` unless given --, cell_offsets (nx ny + 1,) int64,
+    cell_polygons int32).  Cell (ix, iy) has index iy nx + ix and lists, in DESCENDING order, every row whose box meets it, the
+    box closed on both sides; rows with the empty box are listed nowhere.  Work and memory are O(sum over polygons of the cells
+    their box meets)."""
+    boxes3 = 3 * np.asarray(polygon_boxes, dtype=np.int64).reshape(-1, 4)
+    grid = choose_cell_grid(polygon_boxes) if grid is None else np.asarray(grid, dtype=np.int64).reshape(6)
+    nx, ny = int(grid[4]), int(grid[5])
+    if nx < 1 or ny < 1 or grid[2] < 1 or grid[3] < 1:
+        raise ValueError(f"bad cell grid {grid.tolist()}: nx, ny and the cell size must be at least 1")
+    rows, ix0, ix1, iy0, iy1 = _cell_ranges(boxes3, grid)
+    w, h = ix1 - ix0 + 1, iy1 - iy0 + 1
+    n = w * h
+    owner = np.repeat(np.arange(len(rows)), n)
+    k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)      # position inside the polygon's block of cells
+    cell = (iy0[owner] + k // w[owner]) * nx + ix0[owner] + k % w[owner]
+    row = rows[owner]
+    order = np.lexsort((-row, cell))                                    # by cell, the highest row first
+    offsets = np.zeros(nx * ny + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cell, minlength=nx * ny), out=offsets[1:])
+    return grid, offsets, np.ascontiguousarray(row[order], dtype=np.int32)

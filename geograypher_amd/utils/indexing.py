@@ -1,5 +1,5 @@
-"""Post-aggregation helpers (reference: geograypher/utils/indexing.py:9-32) and the host-side inversion of a sampling
-map (reference: geograypher/utils/indexing.py:87-150)."""
+"""Post-aggregation helpers (reference: geograypher/utils/indexing.py:9-32), the ID <-> label table of a discrete texture
+(35-84) and the host-side inversion of a sampling map (87-150)."""
 import numpy as np
 
 
@@ -23,6 +23,26 @@ def find_argmax_nonzero_value(array, keepdims: bool = False, axis: int = 1, back
     if keepdims:
         out = out[:, None]
     return out if is_tensor else out.cpu().numpy()
+
+
+def determine_IDs_to_labels(texture_array: np.ndarray, all_discrete_texture_values=None, background_ID=None):
+    """{ID: label} of a discrete texture, or None for a float texture whose finite values are not whole numbers (reference:
+    utils/indexing.py:35-84).  The labels are the sorted unique values of `all_discrete_texture_values` (of the texture itself
+    when None); the IDs count up from 0 and step over `background_ID`."""
+    texture_array = np.asarray(texture_array)
+    if texture_array.dtype == float:
+        finite = texture_array[np.isfinite(texture_array)]
+        if not np.allclose(finite, finite.astype(int)):
+            return None
+    source = texture_array if all_discrete_texture_values is None else all_discrete_texture_values
+    IDs_to_labels = {}
+    next_ID = 0
+    for value in np.unique(source):
+        if next_ID == background_ID:
+            next_ID += 1
+        IDs_to_labels[next_ID] = value
+        next_ID += 1
+    return IDs_to_labels
 
 
 def inverse_map_interpolation(ijmap: np.ndarray, downsample: int = 1, fill: int = -1) -> np.ndarray:

@@ -464,6 +464,39 @@ int gr_polygon_class_weights(gr_ctx *ctx, const int64_t *tri, const int32_t *fac
                              const int64_t *polygon_boxes, int64_t P, int mode, int C, double *weights, uint64_t *stats,
                              void *stream);
 
+/* Vector textures -- replaces the gpd.overlay of face centres against polygons in get_values_for_faces_from_vector
+ * (meshes/meshes.py:990-1079): the polygon row each face centre lies in; the rule-set is DESIGN.md "Vector textures" (V1-V6).
+ * verts_q: V x 2 int64 snapped vertices (units of 1e-6 m behind a common origin, |value| <= 2^40); faces: F x 3 int32.  The query
+ * point of a face is the exact integer 3 x centre, the sum of its three vertices, formed on the device; ring vertices enter every
+ * comparison times 3.  Ring table as for gr_polygon_class_weights (ring_polygon non-decreasing; hole flags are not needed: a row's
+ * closed region is "on an edge or vertex of any of its rings, or an odd number of crossings over all of them").
+ * Cell index over the polygon boxes, in the units of the query point: cell (ix, iy) covers grid_x0 + ix cell_w <= x < grid_x0 +
+ * (ix + 1) cell_w, likewise in y, 0 <= ix < nx, 0 <= iy < ny; cell_offsets: nx ny + 1 int64, rising; cell_polygons
+ * [cell_offsets[iy nx + ix] .. cell_offsets[iy nx + ix + 1]): the rows whose box meets the cell, in DESCENDING order.  A centre
+ * outside the grid is in no row.  The lane of a face walks the list of the centre's cell -- box test, then the rings -- and stops at
+ * the first row that contains the centre: face_polygon[f] (F int32, written by the call) is the HIGHEST such row, -1 for none.  The
+ * result does not depend on the grid as long as every row is listed in every cell its box meets.
+ * stats: GR_FPI_STAT_WORDS uint64 on the device.  A face with a vertex index outside [0, V) reads nothing, gets -1 and is counted
+ * in GR_FPI_STAT_BAD_FACES; offsets and rows outside their tables are clamped or skipped.  GR_EINVAL (the message names
+ * gr_face_polygon_index): null arrays, negative sizes, nx or ny < 1, nx ny > GR_FPI_MAX_CELLS, a cell size < 1.  Only enqueues work
+ * on `stream`; needs no uploaded mesh and no context scratch.  Added without a GR_VERSION bump. */
+enum {
+  GR_FPI_STAT_TESTED = 0,        /* (face, row) pairs whose box holds the centre: ring walks started                  */
+  GR_FPI_STAT_LABELLED = 1,      /* faces with a row                                                                  */
+  GR_FPI_STAT_LONGEST_LIST = 2,  /* entries of the longest cell list a centre fell into                               */
+  GR_FPI_STAT_BAD_FACES = 3,     /* faces with a vertex index outside [0, V)                                          */
+  GR_FPI_STAT_WORDS = 4
+};
+enum {
+  GR_FPI_MAX_CELLS = 16777216
+};
+int gr_face_polygon_index(gr_ctx *ctx, const int64_t *verts_q, int64_t V, const int32_t *faces, int64_t F,
+                          const int64_t *ring_vertices, int64_t n_ring_vertices, const int64_t *ring_offsets,
+                          const int32_t *ring_polygon, int64_t R, const int64_t *polygon_boxes, int64_t P, int64_t grid_x0,
+                          int64_t grid_y0, int64_t cell_w, int64_t cell_h, int nx, int ny, const int64_t *cell_offsets,
+                          const int32_t *cell_polygons, int64_t n_cell_polygons, int32_t *face_polygon, uint64_t *stats,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif
