@@ -252,15 +252,40 @@ class _StatsAccumulator:
         return d
 
 
-class _nullcontext:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
+def _flags(neg1_is_last_face: bool) -> int:
+    return GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
 
 
-POLYGON_RING_CHUNK = 512  # ring records per LDS chunk of gr_project_polygon_pairs (RING_CHUNK, csrc/project.hip)
+def _require_gpu():
+    if not _torch().cuda.is_available():
+        raise RuntimeError(
+            "geograypher_amd: no ROCm GPU visible (torch.cuda.is_available() is False). "
+            "The projection path runs on MI355X only; there is no CPU fallback."
+        )
+
+
+POLYGON_RING_CHUNK = 512  # ring records per LDS chunk of gr_project_polygon_pairs (PAIR_CHUNK, csrc/project.hip)
+
+
+# The checks of the tables `PairAccumulator` takes: plain functions of host arrays (no device, no library).
+def _host_array(a) -> np.ndarray:
+    """tensor or array -> host array"""
+    return np.asarray(a.cpu() if isinstance(a, _torch().Tensor) else a)
+
+
+def _check_offsets(offsets, n: int, total: int, owners: str, kind: str, rows: str, at_least_one: Optional[str] = None):
+    """An offsets table over `n` owners (views, rings) of `total` rows (rectangles, rings, vertices): n + 1 entries that
+    rise from 0 to total; with `at_least_one`, every owner has a row."""
+    if offsets.shape[0] != n + 1:
+        raise ValueError(f"{n} {owners} need {n + 1} {kind} offsets, got {offsets.shape[0]}")
+    if offsets[0] != 0 or offsets[-1] != total or np.any(np.diff(offsets) < (1 if at_least_one else 0)):
+        raise ValueError(f"{kind} offsets must rise from 0 to {total} (the number of {rows})"
+                         + (f", at least one {at_least_one}" if at_least_one else ""))
+
+
+def _check_int32(table, what: str):
+    if table.size and (table.min() < np.iinfo(np.int32).min or table.max() > np.iinfo(np.int32).max):
+        raise ValueError(f"{what} must fit in int32")
 
 
 def polygon_pair_bounds(boxes, poly_offsets, n_faces: int) -> np.ndarray:
@@ -298,7 +323,7 @@ class PairAccumulator:
         self.b = backend
         self.n_classes = int(n_classes)
         self.counts = counts
-        self.flags = (GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0) | GR_FLAG_DEFER_CHECK
+        self.flags = _flags(neg1_is_last_face) | GR_FLAG_DEFER_CHECK
         self._fixed_cap = cap is not None
         self.cap = max(int(cap), 1) if self._fixed_cap else max(8 * backend.n_faces, 1 << 20)
         self.keys = torch.empty((self.cap,), dtype=torch.int64, device=backend.device)
@@ -308,43 +333,48 @@ class PairAccumulator:
         self.compactions = 0
         self.grown = 0          # times the buffer grew to hold one view
 
-    def add(self, ids, img):
+    def _views(self, ids):
+        """ids (n, h, w) or (h, w) -> (contiguous int32 (n, h, w) tensor on the device, n, h, w)"""
+        ids_t = self.b._dev(ids, _torch().int32)
+        if ids_t.ndim == 2:
+            ids_t = ids_t[None]
+        return (ids_t, *(int(x) for x in ids_t.shape))
+
+    def _upload(self, *tables):
+        """Several int tables as ONE int32 upload: (the tensor, which must outlive the call's enqueue; a pointer per table)."""
+        parts = [np.asarray(t).astype(np.int32).reshape(-1) for t in tables]
+        table = self.b._dev(np.concatenate(parts), _torch().int32)
+        starts = np.cumsum([0] + [p.size for p in parts[:-1]])
+        return table, [table.data_ptr() + 4 * int(k) for k in starts]
+
+    def _emit(self, name: str, *head):
+        """lib.<name>(ctx, *head, <what every pair entry point takes behind its own arguments>)"""
         b = self.b
-        ids_t, img_t = b._index_views(ids, img)
-        n, h, w = (int(x) for x in ids_t.shape)
+        b._call(name, *head, self.n_classes, self.counts.data_ptr(), self.keys.data_ptr(), self.cap, self.key_count.data_ptr(),
+                self.flags, b._stream())
+
+    def add(self, ids, img):
+        ids_t, img_t = self.b._index_views(ids, img)
+        ids_t, n, h, w = self._views(ids_t)
         if not self._make_room(n, lambda k: self.add(ids_t[k], img_t[k])):
             return
-        b._call("gr_project_index_pairs", ids_t.data_ptr(), img_t.data_ptr(), n, h, w, self.n_classes,
-                self.counts.data_ptr(), self.keys.data_ptr(), self.cap, self.key_count.data_ptr(), self.flags, b._stream())
+        self._emit("gr_project_index_pairs", ids_t.data_ptr(), img_t.data_ptr(), n, h, w)
 
     def add_rects(self, ids, rects, offsets):
         """`add` for views whose label image is a list of rectangles (`Segmentor.label_rectangles`): ids (n, h, w) or
         (h, w); rects int (R, 5) rows {imin, jmin, imax, jmax, class}, half-open and in paint order; offsets (n + 1,), view
         k's rows are rects[offsets[k]:offsets[k + 1]].  The tables go to the device as ONE small int32 upload; the label of a
         face's winning pixel is the class of the last rectangle containing it (`gr_project_rect_pairs`)."""
-        torch = _torch()
-        b = self.b
-        ids_t = b._dev(ids, torch.int32)
-        if ids_t.ndim == 2:
-            ids_t = ids_t[None]
-        n, h, w = (int(x) for x in ids_t.shape)
-        rects = np.asarray(rects.cpu() if isinstance(rects, torch.Tensor) else rects).reshape(-1, 5)
-        offsets = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets).reshape(-1)
-        if offsets.shape[0] != n + 1:
-            raise ValueError(f"{n} views need {n + 1} rectangle offsets, got {offsets.shape[0]}")
-        if offsets[0] != 0 or offsets[-1] != rects.shape[0] or np.any(np.diff(offsets) < 0):
-            raise ValueError(f"rectangle offsets must rise from 0 to {rects.shape[0]} (the number of rectangles)")
-        if rects.size and (rects.min() < np.iinfo(np.int32).min or rects.max() > np.iinfo(np.int32).max):
-            raise ValueError("rectangle corners and classes must fit in int32")
+        ids_t, n, h, w = self._views(ids)
+        rects = _host_array(rects).reshape(-1, 5)
+        offsets = _host_array(offsets).reshape(-1)
+        _check_offsets(offsets, n, rects.shape[0], "views", "rectangle", "rectangles")
+        _check_int32(rects, "rectangle corners and classes")
         if not self._make_room(n, lambda k: self.add_rects(ids_t[k], rects[offsets[k]:offsets[k + 1]],
                                                            np.array([0, offsets[k + 1] - offsets[k]]))):
             return
-        # one upload: offsets, then the rectangle rows
-        table = b._dev(np.concatenate([offsets.astype(np.int32), rects.astype(np.int32).reshape(-1)]), torch.int32)
-        offs_ptr = table.data_ptr()
-        rects_ptr = offs_ptr + 4 * (n + 1)
-        b._call("gr_project_rect_pairs", ids_t.data_ptr(), rects_ptr, offs_ptr, n, h, w, self.n_classes,
-                self.counts.data_ptr(), self.keys.data_ptr(), self.cap, self.key_count.data_ptr(), self.flags, b._stream())
+        table, (offs_ptr, rects_ptr) = self._upload(offsets, rects)
+        self._emit("gr_project_rect_pairs", ids_t.data_ptr(), rects_ptr, offs_ptr, n, h, w)
 
     def add_polygons(self, ids, boxes, vert_offsets, verts, poly_offsets):
         """`add` for views whose label image is the multi-hot mask of polygon rings (`Segmentor.label_regions`): ids (n, h, w)
@@ -353,31 +383,16 @@ class PairAccumulator:
         verts float64 (N, 2) (row, col); poly_offsets (n + 1,), view k's rings are boxes[poly_offsets[k]:poly_offsets[k + 1]].
         The tables go to the device as one int32 and one float64 upload; a face's winning pixel is one observation of every
         class with a ring that contains it (`gr_project_polygon_pairs`)."""
-        torch = _torch()
-        b = self.b
-        ids_t = b._dev(ids, torch.int32)
-        if ids_t.ndim == 2:
-            ids_t = ids_t[None]
-        n, h, w = (int(x) for x in ids_t.shape)
-        host = lambda a: np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a)
-        boxes = host(boxes).reshape(-1, 5)
-        vert_offsets = host(vert_offsets).reshape(-1)
-        poly_offsets = host(poly_offsets).reshape(-1)
-        verts = np.ascontiguousarray(host(verts), dtype=np.float64).reshape(-1, 2)
+        ids_t, n, h, w = self._views(ids)
+        boxes = _host_array(boxes).reshape(-1, 5)
+        vert_offsets = _host_array(vert_offsets).reshape(-1)
+        poly_offsets = _host_array(poly_offsets).reshape(-1)
+        verts = np.ascontiguousarray(_host_array(verts), dtype=np.float64).reshape(-1, 2)
         R = boxes.shape[0]
-        if poly_offsets.shape[0] != n + 1:
-            raise ValueError(f"{n} views need {n + 1} polygon offsets, got {poly_offsets.shape[0]}")
-        if poly_offsets[0] != 0 or poly_offsets[-1] != R or np.any(np.diff(poly_offsets) < 0):
-            raise ValueError(f"polygon offsets must rise from 0 to {R} (the number of rings)")
-        if vert_offsets.shape[0] != R + 1:
-            raise ValueError(f"{R} rings need {R + 1} vertex offsets, got {vert_offsets.shape[0]}")
-        if vert_offsets[0] != 0 or vert_offsets[-1] != verts.shape[0] or np.any(np.diff(vert_offsets) < 1):
-            raise ValueError(f"vertex offsets must rise from 0 to {verts.shape[0]} (the number of vertices), at least one "
-                             "vertex per ring")
-        if boxes.size and (boxes.min() < np.iinfo(np.int32).min or boxes.max() > np.iinfo(np.int32).max):
-            raise ValueError("box corners and classes must fit in int32")
-        if verts.shape[0] > np.iinfo(np.int32).max:
-            raise ValueError("vertex offsets must fit in int32")
+        _check_offsets(poly_offsets, n, R, "views", "polygon", "rings")
+        _check_offsets(vert_offsets, R, verts.shape[0], "rings", "vertex", "vertices", at_least_one="vertex per ring")
+        _check_int32(boxes, "box corners and classes")
+        _check_int32(vert_offsets, "vertex offsets")
         if boxes.size and (boxes[:, :2].min() < 0 or boxes[:, 2].max() > h or boxes[:, 3].max() > w):
             raise ValueError(f"boxes must be clipped to the ({h}, {w}) image")
         if R > 1:
@@ -390,18 +405,12 @@ class PairAccumulator:
             va, ve = int(vert_offsets[a]), int(vert_offsets[e])
             self.add_polygons(ids_t[k], boxes[a:e], vert_offsets[a:e + 1] - va, verts[va:ve], np.array([0, e - a]))
 
-        if not self._make_room(n, one_view, polygon_pair_bounds(boxes, poly_offsets, b.n_faces)):
+        if not self._make_room(n, one_view, polygon_pair_bounds(boxes, poly_offsets, self.b.n_faces)):
             return
-        # two uploads: view offsets, vertex offsets and box rows as int32; the vertices as float64
-        table = b._dev(np.concatenate([poly_offsets.astype(np.int32), vert_offsets.astype(np.int32),
-                                       boxes.astype(np.int32).reshape(-1)]), torch.int32)
-        offs_ptr = table.data_ptr()
-        voffs_ptr = offs_ptr + 4 * (n + 1)
-        boxes_ptr = voffs_ptr + 4 * (R + 1)
-        verts_t = b._dev(verts, torch.float64)
-        b._call("gr_project_polygon_pairs", ids_t.data_ptr(), boxes_ptr, voffs_ptr, verts_t.data_ptr() if R else None, offs_ptr,
-                n, h, w, self.n_classes, self.counts.data_ptr(), self.keys.data_ptr(), self.cap, self.key_count.data_ptr(),
-                self.flags, b._stream())
+        table, (offs_ptr, voffs_ptr, boxes_ptr) = self._upload(poly_offsets, vert_offsets, boxes)
+        verts_t = self.b._dev(verts, _torch().float64)
+        self._emit("gr_project_polygon_pairs", ids_t.data_ptr(), boxes_ptr, voffs_ptr, verts_t.data_ptr() if R else None,
+                   offs_ptr, n, h, w)
 
     def _make_room(self, n: int, add_view, bounds=None) -> bool:
         """Room for the pairs of a call over n views: at most `bounds[k]` of view k, one per face where no bounds are given.
@@ -461,13 +470,8 @@ def default_backend(device: Optional[int] = None):
     """One shared `HipRaster` per (device, host thread) for callers that are not handed a backend (camera-set warps, the
     down-scale of `get_image`).  A libgeograster context is not thread safe (include/geograster.h: one context per device and
     host thread): a loader thread that resizes photos while the caller's thread rasterizes gets a context of its own."""
-    torch = _torch()
-    if not torch.cuda.is_available():
-        raise RuntimeError(
-            "geograypher_amd: no ROCm GPU visible (torch.cuda.is_available() is False). "
-            "The projection path runs on MI355X only; there is no CPU fallback."
-        )
-    dev = torch.cuda.current_device() if device is None else int(device)
+    _require_gpu()
+    dev = _torch().cuda.current_device() if device is None else int(device)
     key = (dev, threading.get_ident())
     with _default_backends_lock:
         if key not in _default_backends:
@@ -485,11 +489,7 @@ class HipRaster:
     def __init__(self, device: Optional[int] = None):
         torch = _torch()
         self.lib = load_library()
-        if not torch.cuda.is_available():
-            raise RuntimeError(
-                "geograypher_amd: no ROCm GPU visible (torch.cuda.is_available() is False). "
-                "The projection path runs on MI355X only; there is no CPU fallback."
-            )
+        _require_gpu()
         if device is None:
             device = torch.cuda.current_device()
         self.device_index = int(device)
@@ -699,9 +699,8 @@ class HipRaster:
         cap = n * self.n_faces
         keys = torch.empty((max(cap, 1),), dtype=torch.int64, device=self.device)
         key_count = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        flags = GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
         self._call("gr_project_index_pairs", ids_t.data_ptr(), img_t.data_ptr(), n, h, w, int(n_classes),
-                   counts.data_ptr(), keys.data_ptr(), cap, key_count.data_ptr(), flags, self._stream())
+                   counts.data_ptr(), keys.data_ptr(), cap, key_count.data_ptr(), _flags(neg1_is_last_face), self._stream())
         m = int(key_count.item())
         if m == 0:
             return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
@@ -924,9 +923,8 @@ class HipRaster:
         if ids_t.shape != lab_t.shape:
             raise ValueError(f"ids {tuple(ids_t.shape)} and labels {tuple(lab_t.shape)} differ in shape")
         n, h, w = (int(x) for x in ids_t.shape)
-        flags = GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
         self._call("gr_project_labels_u8", ids_t.data_ptr(), lab_t.data_ptr(), n, h, w, C, votes.data_ptr(),
-                   counts.data_ptr(), flags, self._stream())
+                   counts.data_ptr(), _flags(neg1_is_last_face), self._stream())
 
     def project_values(self, ids, img, sums, counts, neg1_is_last_face: bool = True):
         """ids (N,h,w) int32, img (N,h,w,C) float64; accumulates nansum into sums (F,C) and counts (F,)."""
@@ -939,9 +937,8 @@ class HipRaster:
         C = int(img_t.shape[-1])
         if tuple(img_t.shape) != (n, h, w, C):
             raise ValueError(f"img {tuple(img_t.shape)} does not match ids {tuple(ids_t.shape)}")
-        flags = GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
         self._call("gr_project_values_f64", ids_t.data_ptr(), img_t.data_ptr(), n, h, w, C, sums.data_ptr(),
-                   counts.data_ptr(), flags, self._stream())
+                   counts.data_ptr(), _flags(neg1_is_last_face), self._stream())
 
     def project_view(self, ids, img, neg1_is_last_face: bool = True):
         """One view of project_images: ids (h,w) int32, img (h,w,C) float64 -> (F,C) float64, NaN for unseen faces."""
@@ -953,8 +950,8 @@ class HipRaster:
         if tuple(img_t.shape) != (h, w, C):
             raise ValueError(f"img {tuple(img_t.shape)} does not match ids {tuple(ids_t.shape)}")
         tex = torch.empty((self.n_faces, C), dtype=torch.float64, device=self.device)
-        flags = GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
-        self._call("gr_project_view_f64", ids_t.data_ptr(), img_t.data_ptr(), h, w, C, tex.data_ptr(), flags, self._stream())
+        self._call("gr_project_view_f64", ids_t.data_ptr(), img_t.data_ptr(), h, w, C, tex.data_ptr(), _flags(neg1_is_last_face),
+                   self._stream())
         return tex
 
     def raster_project_labels(self, cams, labels, C: int, votes, counts, ids_out=None, neg1_is_last_face: bool = True,
@@ -969,7 +966,7 @@ class HipRaster:
         n, h, w = (int(x) for x in lab_t.shape)
         if cams_t.shape[0] != n:
             raise ValueError(f"{cams_t.shape[0]} camera records for {n} label images")
-        flags = GR_FLAG_NEG1_IS_LAST_FACE if neg1_is_last_face else 0
+        flags = _flags(neg1_is_last_face)
         # (after an overflow the votes of the first views_done views are in; the library skipped the rest on the device)
         self._checked_raster(n, check, lambda v0: self._call(
             "gr_raster_project_labels_u8", cams_t[v0:].data_ptr(), lab_t[v0:].data_ptr(), n - v0, h, w, C, votes.data_ptr(),
@@ -1162,7 +1159,7 @@ class HipRaster:
         if reference_float_roundtrip and not (small_int and order == 0):
             raise NotImplementedError("reference_float_roundtrip=True is reproduced only for order 0 on integer images "
                                       "within the int32 range with an integer fill value")
-        with torch.cuda.device(self.device) if self.device.type == "cuda" else _nullcontext():
+        with torch.cuda.device(self.device):
             if small_int and order == 0:
                 src = self._dev(img, torch.int32)
                 squeeze = src.ndim == 2

@@ -232,16 +232,49 @@ __global__ __launch_bounds__(256) void k_gather_texture_u8(const int32_t *__rest
   out[i] = v;
 }
 
-// The tail of the emit kernels (K10, K10r, K10p): the lanes of a wave that hold a pair (takers = __ballot(emit), not empty: the
-// caller keeps the ballot and its test, dev_common.hpp says why) append their keys behind *key_count with one atomic; a key
-// beyond key_cap is counted and dropped.
-__device__ __forceinline__ void append_pair_keys(bool emit, unsigned long long key, unsigned long long takers, int lane,
-                                                 unsigned long long *__restrict__ keys, long long key_cap,
-                                                 unsigned long long *__restrict__ key_count) {
-  const unsigned long long base = wave_append(takers, key_count, lane);
-  if (emit) {
-    const unsigned long long idx = base + wave_rank(takers, lane);
-    if ((long long)idx < key_cap) keys[idx] = key;
+// A face's winner of view v, taken: the key (pixel + 1; 0 = the view does not show the face) with its slot cleared for reuse
+// (only the faces a view shows were written).  (The vote kernels load eight views' winners at once instead: measured.)
+__device__ __forceinline__ uint32_t take_winner(uint32_t *__restrict__ winner, int v, int64_t F, int64_t f) {
+  const uint32_t key = winner[v * F + f];
+  if (key != 0) winner[v * F + f] = 0;
+  return key;
+}
+
+// ... and the pixel (row pi, column pj) a non-zero key stands for in an image of width w
+__device__ __forceinline__ void winner_row_col(uint32_t key, int w, int &pi, int &pj) {
+  pi = (int)((key - 1) / (uint32_t)w);
+  pj = (int)((key - 1) % (uint32_t)w);
+}
+
+// The tail of the emit kernels (K10, K10r, K10p).  EVERY lane of the wave must reach it (it ballots), with or without a pair.
+// A lane that `has` an observation of class `cls` flags a class outside [0, n_classes) in `bad`; the others' pair keys
+// f * n_classes + cls are appended behind *key_count with one atomic per wave; a key beyond key_cap is counted and dropped.
+// (The ballot and the test of the same value stay together here, and this stays inlined: dev_common.hpp says why.)
+__device__ __forceinline__ void emit_class(bool has, long long cls, int64_t f, long long n_classes,
+                                           unsigned long long *__restrict__ keys, long long key_cap,
+                                           unsigned long long *__restrict__ key_count, int *__restrict__ bad) {
+  const bool emit = has && cls >= 0 && cls < n_classes;
+  if (has && !emit) atomicOr(bad, 1);
+  const unsigned long long key = (unsigned long long)f * (unsigned long long)n_classes + (unsigned long long)cls;
+  const unsigned long long takers = __ballot(emit);
+  if (takers) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long base = wave_append(takers, key_count, lane);
+    if (emit) {
+      const unsigned long long idx = base + wave_rank(takers, lane);
+      if ((long long)idx < key_cap) keys[idx] = key;
+    }
+  }
+}
+
+// K10r and K10p keep a view's table rows {imin, jmin, imax, jmax, class} in LDS, PAIR_CHUNK rows at a time: rows
+// [beg, beg + n) of `rows` go to box[0 .. n) / box_cls[0 .. n), a row per thread and step (the caller's barriers around it).
+#define PAIR_CHUNK 512
+__device__ __forceinline__ void stage_boxes(const int32_t *__restrict__ rows, int beg, int n, int4 *box, int *box_cls) {
+  for (int k = threadIdx.x; k < n; k += 256) {
+    const int32_t *r = rows + (int64_t)(beg + k) * 5;
+    box[k] = make_int4(r[0], r[1], r[2], r[3]);
+    box_cls[k] = r[4];
   }
 }
 
@@ -255,30 +288,21 @@ __global__ __launch_bounds__(256) void k_emit_index_pairs(uint32_t *__restrict__
                                                           unsigned long long *__restrict__ key_count,
                                                           int *__restrict__ bad) {
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   uint32_t c = 0;
   for (int v = 0; v < n_views; ++v) {
-    bool emit = false;
-    unsigned long long key = 0;
-    if (f < F) {
-      const uint32_t w = winner[v * F + f];
-      if (w != 0) {
-        winner[v * F + f] = 0;
-        const double x = img[(int64_t)v * P + (w - 1)];
-        if (isfinite(x)) {
-          ++c;
-          // astype(int) truncates toward zero: the class lies in [0, n_classes) exactly when -1 < x < n_classes (exact in
-          // double: n_classes <= 2^53).  Decided before the conversion, which is undefined for |x| >= 2^63.
-          if (!(x > -1.0 && x < (double)n_classes)) atomicOr(bad, 1);
-          else {
-            emit = true;
-            key = (unsigned long long)f * (unsigned long long)n_classes + (unsigned long long)(long long)x;
-          }
-        }
-      }
+    bool has = false;
+    long long cls = -1;
+    const uint32_t key = f < F ? take_winner(winner, v, F, f) : 0u;
+    if (key != 0) {
+      const double x = img[(int64_t)v * P + (key - 1)];
+      has = isfinite(x);
+      // astype(int) truncates toward zero: the class lies in [0, n_classes) exactly when -1 < x < n_classes (exact in
+      // double: n_classes <= 2^53).  Decided before the conversion, which is undefined for |x| >= 2^63: a value that
+      // fails is never converted and goes on as class -1.
+      if (x > -1.0 && x < (double)n_classes) cls = (long long)x;
     }
-    const unsigned long long m = __ballot(emit);
-    if (m) append_pair_keys(emit, key, m, lane, keys, key_cap, key_count);
+    if (has) ++c;
+    emit_class(has, cls, f, n_classes, keys, key_cap, key_count, bad);
   }
   if (f < F && c) counts[f] += c;
 }
@@ -286,46 +310,33 @@ __global__ __launch_bounds__(256) void k_emit_index_pairs(uint32_t *__restrict__
 // K10r sparse index aggregation of rectangle labels (detections / image IDs): K10 with the label image replaced by a
 //     lookup.  The winner pixel p = (p / w, p % w) takes the class of the LAST rectangle of its view's list that contains it
 //     (the list is in paint order: a later rectangle overwrites an earlier one); no rectangle = no observation.  The view's
-//     rectangles are staged in LDS in chunks of RECT_CHUNK, walked from the end; a block stops at the first chunk in which
+//     rectangles are staged in LDS in chunks of PAIR_CHUNK, walked from the end; a block stops at the first chunk in which
 //     none of its faces is still searching.  rects: int32 rows {imin, jmin, imax, jmax, class}, half-open, already clipped
 //     to the image; offs: per view [offs[v], offs[v + 1]) into rects.
-#define RECT_CHUNK 512
 __global__ __launch_bounds__(256) void k_emit_rect_pairs(uint32_t *__restrict__ winner, const int32_t *__restrict__ rects,
                                                          const int32_t *__restrict__ offs, int n_views, int64_t F, int w,
                                                          long long n_classes, uint32_t *__restrict__ counts,
                                                          unsigned long long *__restrict__ keys, long long key_cap,
                                                          unsigned long long *__restrict__ key_count,
                                                          int *__restrict__ bad) {
-  __shared__ int4 box[RECT_CHUNK];
-  __shared__ int box_cls[RECT_CHUNK];
+  __shared__ int4 box[PAIR_CHUNK];
+  __shared__ int box_cls[PAIR_CHUNK];
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   uint32_t c = 0;
   for (int v = 0; v < n_views; ++v) {
     int pi = 0, pj = 0;
-    bool searching = false;
-    if (f < F) {
-      const uint32_t wk = winner[v * F + f];
-      if (wk != 0) {
-        winner[v * F + f] = 0;
-        pi = (int)((wk - 1) / (uint32_t)w);
-        pj = (int)((wk - 1) % (uint32_t)w);
-        searching = true;
-      }
-    }
+    const uint32_t key = f < F ? take_winner(winner, v, F, f) : 0u;
+    bool searching = key != 0;
+    if (searching) winner_row_col(key, w, pi, pj);
     bool found = false;
     int cls = 0;
     const int r0 = offs[v], r1 = offs[v + 1];
-    for (int end = r1; end > r0; end -= RECT_CHUNK) {
+    for (int end = r1; end > r0; end -= PAIR_CHUNK) {
       // also the barrier that lets the chunk before this one (or the previous view's last one) be overwritten
       if (!__syncthreads_or(searching)) break;
-      const int beg = end - RECT_CHUNK > r0 ? end - RECT_CHUNK : r0;
+      const int beg = end - PAIR_CHUNK > r0 ? end - PAIR_CHUNK : r0;
       const int n = end - beg;
-      for (int k = threadIdx.x; k < n; k += 256) {
-        const int32_t *r = rects + (int64_t)(beg + k) * 5;
-        box[k] = make_int4(r[0], r[1], r[2], r[3]);
-        box_cls[k] = r[4];
-      }
+      stage_boxes(rects, beg, n, box, box_cls);
       __syncthreads();
       if (searching) {
         for (int k = n - 1; k >= 0; --k) {
@@ -339,15 +350,8 @@ __global__ __launch_bounds__(256) void k_emit_rect_pairs(uint32_t *__restrict__ 
         }
       }
     }
-    bool emit = false;
-    unsigned long long key = 0;
-    if (found) {
-      ++c;
-      if (cls < 0 || (long long)cls >= n_classes) atomicOr(bad, 1);
-      else { emit = true; key = (unsigned long long)f * (unsigned long long)n_classes + (unsigned long long)cls; }
-    }
-    const unsigned long long m = __ballot(emit);
-    if (m) append_pair_keys(emit, key, m, lane, keys, key_cap, key_count);
+    if (found) ++c;
+    emit_class(found, cls, f, n_classes, keys, key_cap, key_count, bad);
   }
   if (f < F && c) counts[f] += c;
 }
@@ -381,11 +385,10 @@ __device__ __forceinline__ bool ring_contains(const double *__restrict__ vp, int
 //     pair (face, class) per class and view, however many rings of the class contain the pixel, and counts[f] += 1 when any
 //     ring does.  boxes: int32 rows {imin, jmin, imax, jmax, class}, a ring's clipped candidate box, half-open, SORTED BY CLASS
 //     within a view; voffs: ring r's vertices are verts[voffs[r] .. voffs[r + 1]) (double (row, col) pairs); offs: view v's
-//     rings are [offs[v], offs[v + 1]).  The ring records are staged in LDS in chunks of RING_CHUNK and walked in order;
+//     rings are [offs[v], offs[v + 1]).  The ring records are staged in LDS in chunks of PAIR_CHUNK and walked in order;
 //     the vertices of a ring are read from global memory on a box hit only, and not at all once the face's pixel has been
 //     found in the ring's class.  Because the table is class-sorted, the end of a class run is a point the whole block
 //     reaches together (the records are the same LDS words for every lane): one ballot there, one append if a lane hit.
-#define RING_CHUNK 512
 __global__ __launch_bounds__(256) void k_emit_polygon_pairs(uint32_t *__restrict__ winner, const int32_t *__restrict__ boxes,
                                                             const int32_t *__restrict__ voffs, const double *__restrict__ verts,
                                                             const int32_t *__restrict__ offs, int n_views, int64_t F, int w,
@@ -393,55 +396,32 @@ __global__ __launch_bounds__(256) void k_emit_polygon_pairs(uint32_t *__restrict
                                                             unsigned long long *__restrict__ keys, long long key_cap,
                                                             unsigned long long *__restrict__ key_count,
                                                             int *__restrict__ bad) {
-  __shared__ int4 box[RING_CHUNK];
-  __shared__ int box_cls[RING_CHUNK];
-  __shared__ int vert_beg[RING_CHUNK + 1];
+  __shared__ int4 box[PAIR_CHUNK];
+  __shared__ int box_cls[PAIR_CHUNK];
+  __shared__ int vert_beg[PAIR_CHUNK + 1];
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   uint32_t c = 0;
-  // the end of a class run: the lanes whose pixel lies in a ring of class `cls` emit their pair
-  auto close_run = [&](bool hit, int cls) {
-    bool emit = false;
-    unsigned long long key = 0;
-    if (hit) {
-      if (cls < 0 || (long long)cls >= n_classes) atomicOr(bad, 1);
-      else { emit = true; key = (unsigned long long)f * (unsigned long long)n_classes + (unsigned long long)cls; }
-    }
-    const unsigned long long m = __ballot(emit);
-    if (m) append_pair_keys(emit, key, m, lane, keys, key_cap, key_count);
-  };
   for (int v = 0; v < n_views; ++v) {
     int pi = 0, pj = 0;
-    bool live = false;
-    if (f < F) {
-      const uint32_t wk = winner[v * F + f];
-      if (wk != 0) {
-        winner[v * F + f] = 0;
-        pi = (int)((wk - 1) / (uint32_t)w);
-        pj = (int)((wk - 1) % (uint32_t)w);
-        live = true;
-      }
-    }
+    const uint32_t key = f < F ? take_winner(winner, v, F, f) : 0u;
+    const bool live = key != 0;
+    if (live) winner_row_col(key, w, pi, pj);
     const double px = (double)pj, py = (double)pi;
     bool hit = false, any = false;  // in a ring of the run's class; in any ring of the view
     int run_cls = 0;
     const int r0 = offs[v], r1 = offs[v + 1];
-    for (int beg = r0; beg < r1; beg += RING_CHUNK) {
+    for (int beg = r0; beg < r1; beg += PAIR_CHUNK) {
       // also the barrier that lets the chunk before this one (or the previous view's last one) be overwritten; a block that
       // shows no face of the view has nothing to look up
       if (!__syncthreads_or(live)) break;
-      const int n = r1 - beg < RING_CHUNK ? r1 - beg : RING_CHUNK;
-      for (int k = threadIdx.x; k < n; k += 256) {
-        const int32_t *r = boxes + (int64_t)(beg + k) * 5;
-        box[k] = make_int4(r[0], r[1], r[2], r[3]);
-        box_cls[k] = r[4];
-      }
+      const int n = r1 - beg < PAIR_CHUNK ? r1 - beg : PAIR_CHUNK;
+      stage_boxes(boxes, beg, n, box, box_cls);
       for (int k = threadIdx.x; k <= n; k += 256) vert_beg[k] = voffs[beg + k];
       __syncthreads();
       for (int k = 0; k < n; ++k) {
         const int cls = box_cls[k];
         if (cls != run_cls) {  // the same LDS word in every lane: the block takes this branch together
-          close_run(hit, run_cls);
+          emit_class(hit, run_cls, f, n_classes, keys, key_cap, key_count, bad);  // the end of a class run
           hit = false;
           run_cls = cls;
         }
@@ -454,7 +434,7 @@ __global__ __launch_bounds__(256) void k_emit_polygon_pairs(uint32_t *__restrict
         }
       }
     }
-    close_run(hit, run_cls);
+    emit_class(hit, run_cls, f, n_classes, keys, key_cap, key_count, bad);
     if (any) ++c;
   }
   if (f < F && c) counts[f] += c;
@@ -604,7 +584,7 @@ int check_projection(gr_ctx *c, int n_views, int h, int w) {
   return GR_OK;
 }
 
-// The "a value is no class index" check of the two pair entry points.  The consumer kernel ORs into `flag`: the context's flag
+// The "a value is no class index" check of the three pair entry points.  The consumer kernel ORs into `flag`: the context's flag
 // word, zeroed ahead of the first launch group and read back behind the last (project_groups) -- or, with GR_FLAG_DEFER_CHECK,
 // the caller's SECOND 64-bit word behind the pair counter (a word of its own: the counter takes 64-bit atomics, the flag a
 // 32-bit one), which nobody reads here.
@@ -655,6 +635,40 @@ int project_groups(gr_ctx *c, const int32_t *ids, int n_views, int h, int w, int
   if (bad) return fail(c, GR_EINDEX, check->message, check->n_classes);
   return GR_OK;
 }
+
+// What the three pair entry points share.  The constructor checks the shape, the mesh and the arguments all three take
+// (`own_ptrs`: the entry point's own pointers are there) and leaves the code in `rc`; run() then makes the ClassCheck with the
+// entry point's GR_EINDEX text and drives `launch(win, v0, nb, bad)` through the launch groups.  The members are the arguments
+// every emit kernel takes, in the kernels' types (the pointers stay separate kernel parameters: polygons.hip).
+struct PairCall {
+  gr_ctx *c;
+  const int32_t *ids;
+  int n_views, h, w, flags;
+  void *stream;
+  hipStream_t s;
+  long long n_classes, key_cap;
+  unsigned long long *keys, *key_count;
+  int rc;
+  int64_t F = 0;
+  dim3 grid;  // a thread per face
+  PairCall(gr_ctx *c, const int32_t *ids, bool own_ptrs, int n_views, int h, int w, int64_t n_classes, const uint32_t *counts,
+           uint64_t *keys, int64_t key_cap, uint64_t *key_count, int flags, void *stream)
+      : c(c), ids(ids), n_views(n_views), h(h), w(w), flags(flags), stream(stream), s((hipStream_t)stream),
+        n_classes((long long)n_classes), key_cap((long long)key_cap), keys((unsigned long long *)keys),
+        key_count((unsigned long long *)key_count), rc(check_projection(c, n_views, h, w)) {
+    if (rc) return;
+    if (!ids || !own_ptrs || !counts || !keys || !key_count || n_classes <= 0 || key_cap < 0)
+      rc = fail(c, GR_EINVAL, "bad sparse projection args");
+    F = c->F;
+    grid = dim3((unsigned)ceil_div(F, 256));
+  }
+  template <typename Launch>
+  int run(const char *message, Launch launch) {
+    const ClassCheck check(c, (uint64_t *)key_count, flags, message, n_classes);
+    return project_groups(c, ids, n_views, h, w, flags, stream,
+                          [&](uint32_t *win, int v0, int nb) { launch(win, v0, nb, check.flag); }, &check);
+  }
+};
 
 }  // namespace
 
@@ -730,53 +744,36 @@ int gr_gather_texture_u8(gr_ctx *c, const int32_t *ids, int64_t n_pix, const dou
 int gr_project_index_pairs(gr_ctx *c, const int32_t *ids, const double *img, int n_views, int h, int w, int64_t n_classes,
                            uint32_t *counts, uint64_t *keys, int64_t key_cap, uint64_t *key_count, int flags,
                            void *stream) {
-  int rc = check_projection(c, n_views, h, w);
-  if (rc) return rc;
-  if (!ids || !img || !counts || !keys || !key_count || n_classes <= 0 || key_cap < 0)
-    return fail(c, GR_EINVAL, "bad sparse projection args");
+  PairCall p(c, ids, img != nullptr, n_views, h, w, n_classes, counts, keys, key_cap, key_count, flags, stream);
+  if (p.rc) return p.rc;
   if (n_classes > (1ll << 53)) return fail(c, GR_EINVAL, "n_classes %lld exceeds 2^53", (long long)n_classes);
-  const int64_t P = (int64_t)h * w, F = c->F;
-  hipStream_t s = (hipStream_t)stream;
-  const ClassCheck check(c, key_count, flags, "an image value is not a class index in [0, %lld)", n_classes);
-  return project_groups(c, ids, n_views, h, w, flags, stream, [&](uint32_t *win, int v0, int nb) {
-    hipLaunchKernelGGL(k_emit_index_pairs, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, img + v0 * P, nb, F, P,
-                       (long long)n_classes, counts, (unsigned long long *)keys, (long long)key_cap,
-                       (unsigned long long *)key_count, check.flag);
-  }, &check);
+  const int64_t P = (int64_t)h * w;
+  return p.run("an image value is not a class index in [0, %lld)", [&](uint32_t *win, int v0, int nb, int *bad) {
+    hipLaunchKernelGGL(k_emit_index_pairs, p.grid, dim3(256), 0, p.s, win, img + v0 * P, nb, p.F, P, p.n_classes, counts, p.keys,
+                       p.key_cap, p.key_count, bad);
+  });
 }
 
 int gr_project_rect_pairs(gr_ctx *c, const int32_t *ids, const int32_t *rects, const int32_t *rect_offsets, int n_views,
                           int h, int w, int64_t n_classes, uint32_t *counts, uint64_t *keys, int64_t key_cap,
                           uint64_t *key_count, int flags, void *stream) {
-  int rc = check_projection(c, n_views, h, w);
-  if (rc) return rc;
-  if (!ids || !rect_offsets || !counts || !keys || !key_count || n_classes <= 0 || key_cap < 0)
-    return fail(c, GR_EINVAL, "bad sparse projection args");
-  const int64_t F = c->F;
-  hipStream_t s = (hipStream_t)stream;
-  const ClassCheck check(c, key_count, flags, "a rectangle's class is not a class index in [0, %lld)", n_classes);
-  return project_groups(c, ids, n_views, h, w, flags, stream, [&](uint32_t *win, int v0, int nb) {
-    hipLaunchKernelGGL(k_emit_rect_pairs, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, rects, rect_offsets + v0,
-                       nb, F, w, (long long)n_classes, counts, (unsigned long long *)keys, (long long)key_cap,
-                       (unsigned long long *)key_count, check.flag);
-  }, &check);
+  PairCall p(c, ids, rect_offsets != nullptr, n_views, h, w, n_classes, counts, keys, key_cap, key_count, flags, stream);
+  if (p.rc) return p.rc;
+  return p.run("a rectangle's class is not a class index in [0, %lld)", [&](uint32_t *win, int v0, int nb, int *bad) {
+    hipLaunchKernelGGL(k_emit_rect_pairs, p.grid, dim3(256), 0, p.s, win, rects, rect_offsets + v0, nb, p.F, w, p.n_classes,
+                       counts, p.keys, p.key_cap, p.key_count, bad);
+  });
 }
 
 int gr_project_polygon_pairs(gr_ctx *c, const int32_t *ids, const int32_t *boxes, const int32_t *vert_offsets,
                              const double *verts, const int32_t *poly_offsets, int n_views, int h, int w, int64_t n_classes,
                              uint32_t *counts, uint64_t *keys, int64_t key_cap, uint64_t *key_count, int flags, void *stream) {
-  int rc = check_projection(c, n_views, h, w);
-  if (rc) return rc;
-  if (!ids || !vert_offsets || !poly_offsets || !counts || !keys || !key_count || n_classes <= 0 || key_cap < 0)
-    return fail(c, GR_EINVAL, "bad sparse projection args");
-  const int64_t F = c->F;
-  hipStream_t s = (hipStream_t)stream;
-  const ClassCheck check(c, key_count, flags, "a polygon's class is not a class index in [0, %lld)", n_classes);
-  return project_groups(c, ids, n_views, h, w, flags, stream, [&](uint32_t *win, int v0, int nb) {
-    hipLaunchKernelGGL(k_emit_polygon_pairs, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, win, boxes, vert_offsets, verts,
-                       poly_offsets + v0, nb, F, w, (long long)n_classes, counts, (unsigned long long *)keys, (long long)key_cap,
-                       (unsigned long long *)key_count, check.flag);
-  }, &check);
+  PairCall p(c, ids, vert_offsets && poly_offsets, n_views, h, w, n_classes, counts, keys, key_cap, key_count, flags, stream);
+  if (p.rc) return p.rc;
+  return p.run("a polygon's class is not a class index in [0, %lld)", [&](uint32_t *win, int v0, int nb, int *bad) {
+    hipLaunchKernelGGL(k_emit_polygon_pairs, p.grid, dim3(256), 0, p.s, win, boxes, vert_offsets, verts, poly_offsets + v0, nb,
+                       p.F, w, p.n_classes, counts, p.keys, p.key_cap, p.key_count, bad);
+  });
 }
 
 int gr_count_pairs(gr_ctx *c, uint64_t *keys, int64_t n, uint64_t *unique_keys, uint32_t *pair_counts, int64_t *n_unique_h,

@@ -262,3 +262,79 @@ def test_views_beyond_one_launch_group(hip, n):
     assert want_keys.size > 0 and want_mult.max() > 1
     assert np.array_equal(got_keys, want_keys) and np.array_equal(got_mult, want_mult)
     assert np.array_equal(got_counts.cpu().numpy(), want_counts.cpu().numpy())
+
+
+@pytest.mark.parametrize("neg1", [True, False])
+@pytest.mark.parametrize("F", [1, 255, 256, 257, 513])
+def test_rects_per_view_around_the_chunk(hip, F, neg1):
+    """K10r at the edges of its 512-row LDS chunk and of its 256-face block: drawn ids on a 17 x 33 image (ids[p] = p % F, three
+    background pixels per view), six views with 0, 1, 511, 512, 513 and 1025 rectangles.  The 1025 of the last view are
+    walked from the end in chunks of 512, 512 and 1: its last row covers the left half (those faces stop in the first chunk
+    visited), its first row the whole image (a face no later row covers must reach the third chunk), the rows between are
+    boxes of 1-2 pixels a side left of column 29.  Pairs and counts must equal numpy (rectangles painted in order,
+    `oracle_np.project_image`, `aggregate_index_sparse`) on every face, and `project_index_pairs` on the painted images."""
+    rng = np.random.default_rng(8000 + F)
+    h, w, nc = 17, 33, 9
+    sizes = [0, 1, 511, 512, 513, 1025]
+    n = len(sizes)
+    ids = np.tile((np.arange(h * w) % F).astype(np.int32), (n, 1))
+    for v in range(n):
+        ids[v, [7 * v + 3, 280 + v, h * w - 1 - v]] = -1   # view 0: the last pixel, which the last face wins with neg1
+    ids = ids.reshape(n, h, w)
+    rects = []
+    for v, size in enumerate(sizes):
+        for k in range(size):
+            if size == 1025 and k == 0:
+                rects.append((0, 0, h, w, 0))
+            elif size == 1025 and k == size - 1:
+                rects.append((0, 0, h, w // 2, 1))
+            else:
+                side = 2 if size == 1025 else 6
+                i0, j0 = int(rng.integers(0, h)), int(rng.integers(0, w - 5 if size == 1025 else w))
+                rects.append((i0, j0, min(h, i0 + int(rng.integers(1, side + 1))), min(w, j0 + int(rng.integers(1, side + 1))),
+                              int(rng.integers(2, nc))))
+    rects = np.array(rects, dtype=np.int32).reshape(-1, 5)
+    offsets = np.concatenate([[0], np.cumsum(sizes)])
+    painted = np.full((n, h, w), np.nan)
+    last_row = np.full((h, w), -1)   # of the 1025-rectangle view: the row that painted each pixel last
+    for v in range(n):
+        for k in range(offsets[v], offsets[v + 1]):
+            i0, j0, i1, j1, cls = rects[k].tolist()
+            painted[v, i0:i1, j0:j1] = cls
+            if v == n - 1:
+                last_row[i0:i1, j0:j1] = k - offsets[v]
+    # the pixels of that view end their walk in each of its three chunks, the single-row one included
+    assert (last_row == 1024).any() and ((last_row >= 513) & (last_row < 1024)).any()
+    assert ((last_row >= 1) & (last_row < 513)).any() and (last_row == 0).any()
+    projs = [oracle_np.project_image(ids[v].astype(np.int64), painted[v].reshape(h, w, 1), F, check_null_image=True,
+                                     neg1_is_last_face=neg1) for v in range(n)]
+    want_counts = np.zeros(F, dtype=np.int64)
+    want_summed = np.zeros((F, nc), dtype=np.int64)
+    if F > 1:
+        _, counts, want_summed = oracle_np.aggregate_index_sparse(projs, F, nc)
+        want_counts = np.asarray(counts).reshape(-1)
+    else:   # (aggregate_index_sparse squeezes a (1, 1) projection to a scalar: the same sums by hand)
+        for p in projs:
+            if np.isfinite(p[0, 0]):
+                want_counts[0] += 1
+                want_summed[0, int(p[0, 0])] += 1
+    assert want_counts.sum() > 0
+
+    hip.upload_mesh(np.zeros((3, 3), dtype=np.float32), np.zeros((F, 3), dtype=np.int32))
+
+    def dense(keys, mult):
+        out = np.zeros(F * nc, dtype=np.int64)
+        out[keys] = mult
+        return out.reshape(F, nc)
+
+    got_counts = torch.zeros((F,), dtype=torch.int32, device=hip.device)
+    acc = hip.new_pair_accumulator(nc, got_counts, neg1_is_last_face=neg1)
+    acc.add_rects(ids, rects, offsets)
+    got_keys, got_mult = acc.finish()
+    np.testing.assert_array_equal(dense(got_keys, got_mult), want_summed)
+    np.testing.assert_array_equal(got_counts.cpu().numpy(), want_counts)
+    img_counts = torch.zeros((F,), dtype=torch.int32, device=hip.device)
+    img_keys, img_mult = hip.project_index_pairs(ids, painted, nc, img_counts, neg1_is_last_face=neg1)
+    np.testing.assert_array_equal(dense(img_keys, img_mult), want_summed)
+    np.testing.assert_array_equal(img_counts.cpu().numpy(), want_counts)
+    assert np.array_equal(got_keys, img_keys) and np.array_equal(got_mult, img_mult)
