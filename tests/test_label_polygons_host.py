@@ -1,6 +1,7 @@
 """label_polygons on the host (no GPU): argument errors, label masking, weighting, ties, empty polygons, label strings, the
 chunked class, `PlanarPolygons`, the C ABI tables -- driven through `polygon_standin.StandInBackend` -- and the stand-in itself
-against the exact oracle on the committed scenes (tests/golden/label_polygons.npz)."""
+against the exact oracle on the committed scenes (tests/golden/label_polygons.npz) and on the generated lattice and wave scenes
+that tests/test_polygon_weights_edges.py runs on the device."""
 import re
 import sys
 from fractions import Fraction
@@ -261,3 +262,120 @@ def test_contact_cases_of_the_integer_scene():
     assert inside[2] == [cell(4, 4) + 1, cell(5, 4), cell(5, 4) + 1, cell(5, 5), cell(5, 5) + 1]   # cut faces are out
     assert cell(3, 0) not in inside[3] and len(inside[3]) == 7                                      # the face around the hole is out
     assert inside[4] == []                                                                          # ring vertices on its edges
+
+
+# -- the generated scenes: the rule's fuzz, and what the device tests rely on ----------------------------------------------------
+WAVE_FACES = (1, 63, 64, 65, 255, 256, 257, 513)
+
+
+def _rings(case):
+    return {p: ps.polygon_rings(case["table"], p) for p in range(len(case["table"][4]))}
+
+
+@pytest.mark.parametrize("name", ["small", "large"])
+def test_lattice_scene_standin_equals_oracle_and_has_every_category(name):
+    case = ps.lattice_case(name)
+    tri, table, info, exact = case["tri"], case["table"], case["info"], case["exact"]
+    assert len(tri) == 257 and np.abs(tri).max() < 2 ** 40 and np.abs(table[0]).max() < 2 ** 40
+    assert exact.keys() == case["within"].keys() == case["overlay"].keys()
+    assert [k for k in exact if exact[k][0] != case["within"][k]] == []          # containment: equal on every pair
+    worst = max(abs(Fraction(case["overlay"][k]) - exact[k][1] / (2 * ps.GRID2_PER_M2)) for k in exact)
+    assert case["e_scene"] == float(worst) > 0.0
+    print(f"[label_polygons] lattice {name}: {len(exact)} pairs, e_scene {case['e_scene']:.3e} m^2")
+    # valid input, checked again on the scaled table: simple counter-clockwise rings of 3 to 8 vertices, holes inside, parts apart
+    rings = _rings(case)
+    for p, rs in rings.items():
+        assert all(ps.ring_is_simple(r) and ps._area2_exact(r) > 0 and 3 <= len(r) <= 8 for r, _ in rs)
+        assert [h for _, h in rs] == ([False, True] if p in info["holed"] else [False] * len(rs))
+        if p in info["holed"]:
+            assert ps.ring_strictly_inside(rs[1][0], rs[0][0])
+        if p in info["two_part"]:
+            assert len(rs) == 2 and ps.rings_apart(rs[0][0], rs[1][0])
+    assert len(info["holed"]) >= 2 and len(info["two_part"]) >= 2
+    # the categories
+    contained = [k for k in exact if exact[k][0]]
+    partial = [k for k in exact if not exact[k][0] and exact[k][1] > 0]
+    contact = [k for k in exact if ps.has_contact(ps.ccw_triangle(tri[k[0]])[0], rings[k[1]])]
+    contact_in = sum(exact[k][0] for k in contact)
+    assert len(contained) >= 100 and len(partial) >= 100
+    assert len(contact) >= 100 and contact_in >= 30 and len(contact) - contact_in >= 30
+    for kind in ("holed", "two_part"):
+        assert any(k[1] in info[kind] for k in contained) and any(k[1] in info[kind] for k in partial)
+    short = sum(max(abs(t[0] - t[2]), abs(t[1] - t[3]), abs(t[0] - t[4]), abs(t[1] - t[5])) <= 2 * (ps.SMALL if name == "small"
+                else ps.LARGE)["scale"] for t in tri.tolist())
+    assert short >= 100                                                           # legs of 1-2 lattice steps
+
+
+def test_large_lattice_scene_needs_128_bits():
+    """Every triangle's twice-area is at least 2^64, and a `within` whose determinants wrap to 64 bits decides differently from
+    the exact oracle on at least 20 pairs: the scene tells a kernel without the 128-bit type from a right one.  The small scene
+    cannot (its determinants stay below 2^53)."""
+    case = ps.lattice_case("large")
+    assert all(ps.ccw_triangle(t)[1] >= 2 ** 64 for t in case["tri"])
+    rings = _rings(case)
+    wrong = [k for k, v in case["exact"].items() if ps.within_wrapped64(ps.ccw_triangle(case["tri"][k[0]])[0], rings[k[1]]) != v[0]]
+    print(f"[label_polygons] lattice large: 64-bit determinants decide {len(wrong)} of {len(case['exact'])} pairs wrongly")
+    assert len(wrong) >= 20
+    small = ps.lattice_case("small")
+    rings = _rings(small)
+    assert all(ps.ccw_triangle(t)[1] < 2 ** 53 for t in small["tri"])
+    assert all(ps.within_wrapped64(ps.ccw_triangle(small["tri"][k[0]])[0], rings[k[1]]) == v[0] for k, v in small["exact"].items())
+
+
+@pytest.mark.parametrize("n_faces", WAVE_FACES)
+def test_wave_scene_is_what_its_docstring_says(n_faces):
+    case = ps.wave_case(n_faces)
+    table, info, exact = case["table"], case["info"], case["exact"]
+    P = ps.WAVE_POLYGONS
+    assert exact.keys() == case["within"].keys() and [k for k in exact if exact[k][0] != case["within"][k]] == []
+    assert table[2].tolist() == [0, 0, -1, 2, 3, 3, 3, P, 4, 4, 5] and np.diff(table[1]).tolist()[4:7] == [0, 1, 2]
+    assert table[4][1].tolist() == list(ps.EMPTY_BOX) and table[4][3].tolist() != list(ps.EMPTY_BOX)
+    for p in (0, 2, 4, 5):
+        rs = ps.polygon_rings(table, p)
+        assert rs and all(ps.ring_is_simple(r) and ps._area2_exact(r) > 0 for r, _ in rs)
+    assert ps.polygon_rings(table, 1) == [] == ps.polygon_rings(table, 3)
+    far = {k[0] // 64 for k in exact if k[1] == info["far_polygon"]}
+    assert far == ({info["far_run"]} if n_faces > 1 else set())                   # the other waves skip it on the ballot
+    assert not any(k[1] == 1 for k in exact)
+    for n_classes in (1, 3, 70):
+        tri, cls, weight, table2, info2 = ps.wave_scene(n_faces, n_classes)
+        assert np.array_equal(tri, case["tri"]) and all(np.array_equal(a, b) for a, b in zip(table, table2))
+        assert cls.min() >= -1 and cls.max() <= n_classes and weight.min() >= 0.0
+        flat = np.array([ps.ccw_triangle(t)[1] == 0 for t in tri])
+        assert np.array_equal(flat, info2["collapsed"])
+        if n_classes > 1:
+            assert not np.any(cls[~flat] == info2["idle_class"])
+    if n_faces >= 63:
+        tri, cls, weight, _, info2 = ps.wave_scene(n_faces, 70)
+        o = [ps._orient(*t) for t in tri.tolist()]
+        assert min(o) < 0 < max(o) and info2["collapsed"].any() and (cls == -1).any() and (cls == 70).any() and (weight == 0).any()
+        assert len(set(cls[:64].tolist())) > 30 and any(exact[k][0] for k in exact)
+        assert any(k[1] == 3 for k in exact)                                      # faces meet the box of the row of short rings
+
+
+def test_pairs_tested_counts_box_overlap_whether_or_not_a_ring_is_usable():
+    """GR_POLY_STAT_TESTED is "(face, polygon) pairs whose boxes overlap": a polygon all of whose rings are shorter than 3 vertices
+    is tested against every face that meets its box and adds nothing; a polygon without any ring row has no box."""
+    unit = 10 ** 6
+    tri = np.array([[0, 0, 4, 0, 0, 4], [1, 1, 2, 1, 1, 2], [10, 10, 12, 10, 10, 12], [-1, -1, 3, -1, -1, 3]], dtype=np.int64) * unit
+    rows = [(0, [(0, 0), (6, 0), (6, 6), (0, 6)], False), (1, [(1, 1), (2, 2)], False), (1, [(1, 2)], False), (1, [], False)]
+    table = ps.make_table(rows, 3, unit)
+    assert table[4].tolist() == [[0, 0, 6 * unit, 6 * unit], [unit, unit, 2 * unit, 2 * unit], list(ps.EMPTY_BOX)]
+    cls, w = np.zeros(4, dtype=np.int32), np.ones(4)
+    for within in (True, False):
+        weights, stats = ps.polygon_class_weights_np(tri, cls, w, table, 1, within)
+        pairs = ps.standin_pairs(tri, cls, table, within)
+        # polygon 0 meets faces 0, 1, 3; polygon 1 (no usable ring) meets 0, 1, 3 as well; polygon 2 (no rows) none, though face 3's
+        # box holds the placeholder box
+        assert sorted(pairs) == [(0, 0), (0, 1), (1, 0), (1, 1), (3, 0), (3, 1)] == sorted(ps.exact_pairs(tri, cls, table))
+        assert stats.tolist() == [6, 2 if within else 3, 4, 0]
+        assert weights[1:].tolist() == [[0.0], [0.0]] and weights[0, 0] == (8.5 if within else 8.5 + 2.0)   # face 3 keeps x, y >= 0, x + y <= 2
+
+
+def test_committed_scenes_have_no_polygon_without_a_usable_ring():
+    """... so the change above leaves their `pairs_per_polygon` as committed."""
+    for name in SCENES:
+        d = load_scene(name)
+        table = d["polygons"].snapped()
+        for p in range(len(table[4])):
+            assert ps.polygon_has_rows(table, p) == bool(ps.polygon_rings(table, p))
