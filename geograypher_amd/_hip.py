@@ -77,6 +77,13 @@ GR_FPI_STAT_LONGEST_LIST = 2
 GR_FPI_STAT_BAD_FACES = 3
 GR_FPI_STAT_WORDS = 4
 GR_FPI_MAX_CELLS = 16777216
+# words of sample_raster's statistics block, its relabel flag
+GR_RS_STAT_INSIDE = 0
+GR_RS_STAT_NODATA = 1
+GR_RS_STAT_GROUND = 2
+GR_RS_STAT_BAD_FACES = 3
+GR_RS_STAT_WORDS = 4
+GR_RS_FLAG_ONLY_EXISTING = 1
 
 
 class StageTimes(ctypes.Structure):
@@ -159,6 +166,8 @@ _SIGNATURES = {
     "gr_polygon_class_weights": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
     "gr_face_polygon_index": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32,
                               _vp, _vp, _i64, _vp, _vp, _vp],
+    "gr_sample_raster": [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _f64, _f64,
+                         _i32, _vp, _vp],
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -905,6 +914,70 @@ class HipRaster:
             if n_bad:
                 raise ValueError(f"gr_face_polygon_index: {n_bad} faces name a vertex outside [0, {int(vq_t.shape[0])})")
         return out, stats
+
+    # -- raster samples: the value of a raster under every face centre or vertex -----------------------------------
+    def sample_raster(self, points, faces, raster_data, inverse6, nodata, fill, *, want_values: bool = True,
+                      want_height: bool = False, labels=None, threshold=None, ground_id=None, only_existing: bool = False,
+                      check: bool = True):
+        """gr_sample_raster (DESIGN.md "Raster samples"): points (V, 3) float64 in the raster's CRS; faces (F, 3) int for a query
+        per face centre, None for a query per vertex; raster_data (B, H, W) or (H, W), float32 or float64 (anything else is
+        converted to float64); inverse6: the six coefficients of the INVERSE transform (`PlanarRaster.inverse`); nodata a float or
+        None; fill what a sample equal to nodata becomes -- numpy or device tensors -> (values (N, B) float64 tensor or None,
+        height (N,) float64 tensor or None, labels or None, stats (GR_RS_STAT_WORDS,) int64 tensor).  `labels` ((N,) or (N, 1)
+        float64) with `threshold` and `ground_id` are relabelled: a DEVICE float64 contiguous tensor is rewritten in place and
+        returned, anything else is copied to the device first.  `check` (default) reads the statistics back and raises ValueError
+        when a face names a vertex that does not exist; check=False only enqueues."""
+        torch = _torch()
+        p_t = self._dev(points, torch.float64)
+        if p_t.ndim != 2 or p_t.shape[1] != 3:
+            raise ValueError(f"points must be (V, 3), got {tuple(p_t.shape)}")
+        V = int(p_t.shape[0])
+        f_t = None
+        if faces is not None:
+            f_t = self._dev(faces, torch.int32)
+            if f_t.ndim != 2 or f_t.shape[1] != 3:
+                raise ValueError(f"faces must be (F, 3), got {tuple(f_t.shape)}")
+        N = V if f_t is None else int(f_t.shape[0])
+        if isinstance(raster_data, torch.Tensor):
+            is_f32 = raster_data.dtype == torch.float32
+        else:
+            raster_data = np.asarray(raster_data)
+            is_f32 = raster_data.dtype == np.float32
+            if not is_f32:
+                raster_data = raster_data.astype(np.float64)   # on the host: exact for the integer dtypes of a DTM
+        r_t = self._dev(raster_data, torch.float32 if is_f32 else torch.float64)
+        if r_t.ndim == 2:
+            r_t = r_t[None]
+        if r_t.ndim != 3 or min(r_t.shape) < 1:
+            raise ValueError(f"raster data must be (B, H, W) or (H, W) with no empty axis, got {tuple(r_t.shape)}")
+        B, H, W = (int(v) for v in r_t.shape)
+        inv = [float(v) for v in np.asarray(inverse6, dtype=np.float64).reshape(-1)]
+        if len(inv) != 6:
+            raise ValueError(f"the inverse transform has six coefficients, got {len(inv)}")
+        inv_h = (ctypes.c_double * 6)(*inv)
+        lab_t = None
+        if labels is not None:
+            if threshold is None or ground_id is None:
+                raise ValueError("labels need threshold and ground_id")
+            lab_t = self._dev(labels, torch.float64)
+            if lab_t.numel() != N or lab_t.ndim > 2:
+                raise ValueError(f"labels must be ({N},) or ({N}, 1), got {tuple(lab_t.shape)}")
+        values = torch.empty((N, B), dtype=torch.float64, device=self.device) if want_values else None
+        height = torch.empty((N,), dtype=torch.float64, device=self.device) if want_height else None
+        stats = torch.zeros((GR_RS_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        if N > 0:   # (an empty tensor has no address: null faces would mean vertex mode)
+            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            self._call("gr_sample_raster", p_t.data_ptr(), V, ptr(f_t), 0 if f_t is None else N, r_t.data_ptr(),
+                       GR_DTYPE_F32 if is_f32 else GR_DTYPE_F64, B, H, W, ctypes.addressof(inv_h), 0 if nodata is None else 1,
+                       0.0 if nodata is None else float(nodata), float(fill), ptr(values), ptr(height), ptr(lab_t),
+                       float("nan") if threshold is None else float(threshold),
+                       float("nan") if ground_id is None else float(ground_id),
+                       GR_RS_FLAG_ONLY_EXISTING if only_existing else 0, stats.data_ptr(), self._stream())
+            if check:
+                n_bad = int(stats[GR_RS_STAT_BAD_FACES].item())
+                if n_bad:
+                    raise ValueError(f"gr_sample_raster: {n_bad} faces name a vertex outside [0, {V})")
+        return values, height, lab_t, stats
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):

@@ -13,6 +13,7 @@
 //   cover.hip        covering meshes: bounds of a point set (k_points_bounds), highest / lowest member per grid cell (k_cover_grid); no mesh needed
 //   polygons.hip     label_polygons: weighted face area per (polygon, class), exact containment or clipped overlay (k_polygon_weights); no mesh needed
 //                    vector textures: the polygon row of every face centre through a cell index (k_face_polygon_index)
+//   terrain.hip      raster samples: the value of a raster under every face centre or vertex, height above it, ground relabel (k_sample_raster); no mesh needed
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 

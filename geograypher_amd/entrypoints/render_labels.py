@@ -6,9 +6,11 @@ EPSG:4978), the cameras as a Metashape XML, the texture as an array, a `.npy` fi
 features in a planar CRS.  A vector texture also needs `texture_points_file`: a `.npy` with the mesh vertices (V, 3) in the
 polygons' CRS (the reference reprojects them with pyproj).  Every face takes the value of the highest feature that holds its centre
 (`TexturedPhotogrammetryMesh.get_values_for_faces_from_vector`, on the device); `save_renders` writes one label image per camera under
-`render_savefolder`, at the cameras' paths relative to `image_folder`, and `IDs_to_labels.json` beside them.  Not carried over: the DTM
-ground class, ROI cropping of mesh and cameras, mesh decimation, saving the image subset or the textured mesh, and the
-visualisations (rasterio, geopandas, pyvista, matplotlib)."""
+`render_savefolder`, at the cameras' paths relative to `image_folder`, and `IDs_to_labels.json` beside them.  With `DTM_file` (a
+single-band GeoTIFF or a `PlanarRaster`) and `ground_height_threshold`, labelled faces lower than the threshold above the DTM are
+relabelled before rendering (`label_ground_class`, on the device): to a new class "GROUND" with `render_ground_class`, else to NaN;
+this needs `DTM_points_file`, the vertices in the DTM's CRS.  Not carried over: ROI cropping of mesh and cameras, mesh decimation,
+saving the image subset or the textured mesh, and the visualisations (geopandas, pyvista, matplotlib)."""
 import argparse
 import json
 import typing
@@ -50,18 +52,20 @@ def render_labels(
     apply_distortion: bool = True,
     camera_set=None,
     backend=None,
+    DTM_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
 ):
     """Render the labels of `texture` into every camera's view (see the module docstring for inputs and files).  The reference's
-    arguments and defaults; `DTM_file`, `ROI`, `mesh_downsample != 1`, `subset_images_savefolder`, `textured_mesh_savefile`, `vis`,
+    arguments and defaults; `DTM_file` without `DTM_points_file`, `ROI`, `mesh_downsample != 1`, `subset_images_savefolder`, `textured_mesh_savefile`, `vis`,
     `mesh_vis_file` and `labels_vis_folder` raise NotImplementedError.  `n_cameras_per_chunk` selects
     `TexturedPhotogrammetryMeshChunked` with ceil(cameras / n_cameras_per_chunk) clusters, as in the reference (the GPU path
     renders the whole mesh either way).  Beyond the reference: `texture_points_file` (a `.npy` path or the array itself, required
-    for a vector texture), `apply_distortion` (False for a camera set without a lens model), and `camera_set` and `backend`,
+    for a vector texture), `DTM_points_file` (likewise, the vertices in the DTM's CRS, required with `DTM_file`), `apply_distortion` (False for a camera set without a lens model), and `camera_set` and `backend`,
     which replace the objects built from `cameras_file` and the device.  Returns the textured mesh."""
     from geograypher_amd.meshes import TexturedPhotogrammetryMesh, TexturedPhotogrammetryMeshChunked
 
     for name, value, why in (
-        ("DTM_file", DTM_file, "DTM rasters need rasterio"),
+        ("DTM_file", DTM_file if DTM_points_file is None else None,
+         "the vertices in the DTM's CRS are needed (DTM_points_file); reprojecting them needs pyproj"),
         ("ROI", ROI, "ROI cropping needs geopandas"),
         ("subset_images_savefolder", subset_images_savefolder, "copying the image subset is not part of this package"),
         ("textured_mesh_savefile", textured_mesh_savefile, "mesh writers (pyvista) are not part of this package"),
@@ -90,6 +94,13 @@ def render_labels(
     mesh.load_texture(texture, texture_column_name=texture_column_name, IDs_to_labels=mesh.IDs_to_labels,
                       points_in_polygon_CRS=points_in_polygon_CRS)
 
+    if DTM_file is not None and ground_height_threshold is not None:   # reference: render_labels.py:161-171
+        points_in_raster_CRS = np.load(DTM_points_file) if isinstance(DTM_points_file, (str, Path)) else DTM_points_file
+        mesh.label_ground_class(DTM_file=DTM_file, height_above_ground_threshold=ground_height_threshold,
+                                only_label_existing_labels=True, ground_class_name="GROUND",
+                                ground_ID=None if render_ground_class else np.nan, set_mesh_texture=True,
+                                points_in_raster_CRS=points_in_raster_CRS)
+
     render_kwargs = {} if n_render_chunks is None else {"n_clusters": n_render_chunks}
     if not apply_distortion:
         render_kwargs["apply_distortion"] = False
@@ -114,9 +125,13 @@ def parse_args(argv=None):
                         help="Removed from the beginning of the absolute image paths stored in --cameras-file")
     parser.add_argument("--subset-images-savefolder", type=Path, help="Not available here")
     parser.add_argument("--texture-column-name", help="Property of the .geojson features to use as the label")
-    parser.add_argument("--DTM-file", help="Not available here")
-    parser.add_argument("--ground-height-threshold", type=float, default=2.0, help="Only applies with --DTM-file")
-    parser.add_argument("--render-ground-class", action="store_true", help="Only applies with --DTM-file")
+    parser.add_argument("--DTM-file", type=Path, help="Single-band GeoTIFF of the terrain: labelled faces near it are relabelled")
+    parser.add_argument("--DTM-points-file", type=Path,
+                        help=".npy with the mesh vertices (V, 3) in the CRS of --DTM-file (required with it)")
+    parser.add_argument("--ground-height-threshold", type=float, default=2.0,
+                        help="Faces lower than this above the DTM are ground; only applies with --DTM-file")
+    parser.add_argument("--render-ground-class", action="store_true",
+                        help="Render ground as a class GROUND of its own instead of unlabelled; only applies with --DTM-file")
     parser.add_argument("--textured-mesh-savefile", help="Not available here")
     parser.add_argument("--ROI", help="Not available here")
     parser.add_argument("--mesh-ROI-buffer-radius-meters", default=50, type=float, help="Only applies with --ROI")

@@ -1259,6 +1259,126 @@ class TexturedPhotogrammetryMesh:
             return labeled_faces[column_names[0]], all_values[column_names[0]]
         return labeled_faces, all_values
 
+    # -- raster samples (DESIGN.md "Raster samples"; reference: meshes.py:1449-1629) ---------------------------------------------
+    def add_label(self, label_name, label_ID):
+        """reference: meshes.py:733-735 -- nothing for a NaN ID; beyond it, a numeric ID on a mesh without a table starts one
+        (the reference fails there: None has no items)."""
+        if isinstance(label_ID, float) and np.isnan(label_ID):
+            return
+        if self.IDs_to_labels is None:
+            self.IDs_to_labels = {}
+        self.IDs_to_labels[label_ID] = label_name
+
+    def _sample_raster(self, raster_file, use_vertex_locations, points_in_raster_CRS, what, nodata_fill_value=np.nan, **kwargs):
+        """The backend's sample_raster for this mesh: (values, height, labels, stats as the backend returns them, points (V, 3))."""
+        from geograypher_amd.utils.raster import PlanarRaster
+
+        if points_in_raster_CRS is None:
+            raise NotImplementedError(
+                f"{what} needs points_in_raster_CRS: the mesh vertices (V, 3) in the raster's CRS (CRS reprojection needs pyproj "
+                "and is outside the projection path)")
+        raster = raster_file if isinstance(raster_file, PlanarRaster) else PlanarRaster.from_geotiff(raster_file)
+        points = np.ascontiguousarray(points_in_raster_CRS, dtype=np.float64)
+        if points.shape != (self.points.shape[0], 3):
+            raise ValueError(f"points_in_raster_CRS must be ({self.points.shape[0]}, 3), got {points.shape}")
+        faces = None if use_vertex_locations else np.ascontiguousarray(self.faces, dtype=np.int32)
+        values, height, labels, stats = self.backend.sample_raster(points, faces, raster.data, raster.inverse, raster.nodata,
+                                                                   float(nodata_fill_value), **kwargs)
+        stats_h = _host_array(stats)
+        self.last_raster_stats = {"queries": int(points.shape[0] if faces is None else faces.shape[0]), "inside": int(stats_h[0]),
+                                  "nodata": int(stats_h[1]), "ground": int(stats_h[2]), "bad_faces": int(stats_h[3])}
+        return values, height, labels, points
+
+    def get_values_from_raster_file(self, raster_file, use_vertex_locations: bool = False, return_mesh_points: bool = False,
+                                    nodata_fill_value: float = np.nan, *, points_in_raster_CRS=None):
+        """The value of a raster under every face centre, or vertex (reference: meshes.py:1449-1499; rules T1-T5): (N,) float64
+        for one band, (N, B) for several.  raster_file: a single-band GeoTIFF path or a `PlanarRaster`
+        (geograypher_amd.utils.raster); points_in_raster_CRS (required, keyword): the mesh vertices (V, 3) in the raster's CRS.
+        The sample is that of the cell the point falls into; outside the raster it is nodata (0.0 without one); a sample equal
+        to nodata becomes `nodata_fill_value`.  `return_mesh_points` also returns the (N, 3) query points: the vertices, or the
+        face centres ((p0 + p1) + p2) / 3.0, the very operations the device forms them with.  The statistics of the call are left
+        in `self.last_raster_stats` (queries, inside, nodata, ground, bad_faces)."""
+        values, _, _, points = self._sample_raster(raster_file, use_vertex_locations, points_in_raster_CRS,
+                                                   "get_values_from_raster_file", nodata_fill_value, want_values=True,
+                                                   want_height=False)
+        values = np.array(_host_array(values), dtype=np.float64)
+        if values.shape[1] == 1:
+            values = values[:, 0]
+        if not return_mesh_points:
+            return values
+        if not use_vertex_locations:
+            corners = points[self.faces]
+            points = ((corners[:, 0] + corners[:, 1]) + corners[:, 2]) / 3.0   # rule T3
+        return values, points
+
+    def get_height_above_ground(self, DTM_file, use_vertex_locations: bool = False, threshold: float = None, *,
+                                points_in_raster_CRS=None, return_tensor: bool = False):
+        """Height of every face centre (or vertex) above the first band of a DTM (reference: meshes.py:1501-1538; rule T6): (N,)
+        float64, NaN where the DTM has no data or does not reach; with `threshold`, the bool array `height < threshold` (NaN:
+        False).  Arguments as for `get_values_from_raster_file`.  `return_tensor=True` leaves the result on the device."""
+        _, height, _, _ = self._sample_raster(DTM_file, use_vertex_locations, points_in_raster_CRS, "get_height_above_ground",
+                                              want_values=False, want_height=True)
+        if threshold is not None:
+            height = height < threshold
+        if return_tensor:
+            return height
+        return np.array(_host_array(height))
+
+    def label_ground_class(self, DTM_file, height_above_ground_threshold: float, labels=None,
+                           only_label_existing_labels: bool = True, ground_class_name: str = "ground", ground_ID=None,
+                           set_mesh_texture: bool = False, *, points_in_raster_CRS=None):
+        """Give the faces (or vertices) lower than `height_above_ground_threshold` above the DTM the ground class (reference:
+        meshes.py:1540-1629; rule T7).  labels: None (the face texture), or V vertex labels, or F face labels -- V is tried
+        first --, (N,) or (N, 1), numpy or a float64 device tensor; they are rewritten IN PLACE and returned, a device tensor on
+        the device.  The ground ID: NaN when the mesh has no IDs_to_labels and no ground_ID was passed; the existing ID when
+        `ground_class_name` is a label already; else `ground_ID`; else the largest ID + 1 (the reference's
+        `np.max(dict.keys()) + 1` raises TypeError there).  `add_label` records the name unless the ID is NaN."""
+        if labels is None:
+            use_vertex_locations = False
+            labels = self.get_texture(request_vertex_texture=False)
+            if labels is None:
+                raise ValueError("label_ground_class: no labels given and the mesh has no texture")
+        elif labels.shape[0] == self.points.shape[0]:
+            use_vertex_locations = True
+        elif labels.shape[0] == self.faces.shape[0]:
+            use_vertex_locations = False
+        else:
+            raise ValueError("Labels were provided but didn't match the shape of vertices or faces")
+        if labels.ndim > 2 or (labels.ndim == 2 and labels.shape[1] != 1):
+            raise ValueError(f"labels must be (N,) or (N, 1), got {tuple(labels.shape)}")
+
+        IDs_to_labels = self.get_IDs_to_labels()
+        if IDs_to_labels is None and ground_ID is None:
+            ground_ID = np.nan
+        elif IDs_to_labels is not None and ground_class_name in IDs_to_labels.values():
+            ground_ID = {v: k for k, v in IDs_to_labels.items()}.get(ground_class_name)
+        elif IDs_to_labels is not None and ground_ID is None:
+            ground_ID = max(IDs_to_labels.keys()) + 1
+
+        on_device = hasattr(labels, "detach")
+        in_place = on_device or labels.dtype == np.float64
+        _, height, relabelled, _ = self._sample_raster(
+            DTM_file, use_vertex_locations, points_in_raster_CRS, "label_ground_class", want_values=False,
+            want_height=not in_place, labels=labels if in_place else None,
+            threshold=height_above_ground_threshold if in_place else None, ground_id=ground_ID if in_place else None,
+            only_existing=bool(only_label_existing_labels))
+        self.add_label(label_name=ground_class_name, label_ID=ground_ID)
+        if on_device:
+            if relabelled.data_ptr() != labels.data_ptr():   # another device, dtype or layout: the backend worked on a copy
+                labels.copy_(relabelled.reshape(labels.shape))
+        elif in_place:
+            np.copyto(labels, _host_array(relabelled).reshape(labels.shape))
+        else:   # labels of another dtype: the assignment converts the ID as numpy does
+            ground_mask = _host_array(height) < height_above_ground_threshold
+            column = labels if labels.ndim == 1 else labels[:, 0]
+            if only_label_existing_labels:
+                ground_mask = np.logical_and(np.isfinite(column), ground_mask)
+            column[ground_mask] = ground_ID
+            self.last_raster_stats["ground"] = int(ground_mask.sum())
+        if set_mesh_texture:
+            self.set_texture(_host_array(labels) if on_device else labels)
+        return labels
+
     # -- save_renders (SURVEY.md section 8, row f2) ----------------------------------------------------------------
     def save_IDs_to_labels(self, savepath: PATH_TYPE):
         """reference: meshes.py:1081-1108"""
@@ -1563,6 +1683,11 @@ def _to_host(t) -> np.ndarray:
     host.copy_(t, non_blocking=True)
     torch.cuda.current_stream(t.device).synchronize()
     return host.numpy()
+
+
+def _host_array(x) -> np.ndarray:
+    """What a backend returned, on the host: a tensor through `_to_host`, anything else as a numpy array."""
+    return _to_host(x) if hasattr(x, "detach") else np.asarray(x)
 
 
 def _torch():

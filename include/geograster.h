@@ -497,6 +497,40 @@ int gr_face_polygon_index(gr_ctx *ctx, const int64_t *verts_q, int64_t V, const 
                           const int32_t *cell_polygons, int64_t n_cell_polygons, int32_t *face_polygon, uint64_t *stats,
                           void *stream);
 
+/* Raster samples -- replaces the per-point rasterio.sample of get_values_from_raster_file, the subtraction of
+ * get_height_above_ground and the masked write of label_ground_class (meshes/meshes.py:1449-1629): the value of a raster under
+ * every face centre or vertex; the rule-set is DESIGN.md "Raster samples" (T1-T7).  Every operation is a float64 operation
+ * rounded on its own, in the order written here.
+ * points: V x 3 float64, in the raster's CRS.  faces: F x 3 int32 -- a query per face, the centre ((p0 + p1) + p2) / 3.0 per
+ * component, formed on the device -- or NULL with F = 0: a query per vertex.  N is F or V accordingly.
+ * raster: B x H x W of raster_dtype GR_DTYPE_F32 or GR_DTYPE_F64, C-contiguous.  inverse6_h (a HOST pointer): the inverse affine
+ * transform (ia, ib, ic, id, ie, if): col = floor((x ia + y ib) + ic), row = floor((x id + y ie) + if); the query is inside iff
+ * 0 <= col < W and 0 <= row < H, compared as doubles (NaN, infinities and huge coordinates are outside).  Sample of band b:
+ * raster[b][row][col] widened to float64 inside, else nodata if has_nodata != 0, else 0.0; then a sample == nodata (has_nodata
+ * only; a NaN nodata matches nothing) becomes `fill`.
+ * Outputs, each may be NULL: values N x B float64; height N float64 = z of the query - the sample of band 0; labels_inout N
+ * float64, rewritten in place: labels[i] = ground_id where height < threshold (NaN: never) and, with GR_RS_FLAG_ONLY_EXISTING in
+ * `flags`, labels[i] is finite.  threshold, ground_id and flags are read only with labels_inout.
+ * stats: GR_RS_STAT_WORDS uint64 on the device, written by the call.  A face with a vertex index outside [0, V) reads nothing:
+ * its samples are those of a query outside the raster, its height is NaN, its label is kept, and it is counted in
+ * GR_RS_STAT_BAD_FACES only.  GR_EINVAL (the message names gr_sample_raster): null points / raster / inverse6_h / stats, null faces
+ * with F > 0, negative sizes, B, H or W < 1, another raster_dtype.  N = 0 is GR_OK.  Only enqueues work on `stream`; needs no
+ * uploaded mesh and no context scratch.  Added without a GR_VERSION bump. */
+enum {
+  GR_RS_STAT_INSIDE = 0,     /* queries whose cell lies in the raster                                              */
+  GR_RS_STAT_NODATA = 1,     /* queries with a sample that equalled nodata (those outside a raster with a nodata too) */
+  GR_RS_STAT_GROUND = 2,     /* labels rewritten to ground_id                                                      */
+  GR_RS_STAT_BAD_FACES = 3,  /* faces with a vertex index outside [0, V)                                           */
+  GR_RS_STAT_WORDS = 4
+};
+enum {
+  GR_RS_FLAG_ONLY_EXISTING = 1  /* relabel only labels that are finite (only_label_existing_labels) */
+};
+int gr_sample_raster(gr_ctx *ctx, const double *points, int64_t V, const int32_t *faces, int64_t F, const void *raster,
+                     int raster_dtype, int B, int H, int W, const double *inverse6_h, int has_nodata, double nodata, double fill,
+                     double *values, double *height, double *labels_inout, double threshold, double ground_id, int flags,
+                     uint64_t *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
