@@ -77,6 +77,11 @@ GR_FPI_STAT_LONGEST_LIST = 2
 GR_FPI_STAT_BAD_FACES = 3
 GR_FPI_STAT_WORDS = 4
 GR_FPI_MAX_CELLS = 16777216
+# words of points_in_region's statistics block
+GR_PIR_STAT_INSIDE = 0
+GR_PIR_STAT_BUFFER_ONLY = 1
+GR_PIR_STAT_WIDE = 2
+GR_PIR_STAT_WORDS = 4
 # words of sample_raster's statistics block, its relabel flag
 GR_RS_STAT_INSIDE = 0
 GR_RS_STAT_NODATA = 1
@@ -166,6 +171,8 @@ _SIGNATURES = {
     "gr_polygon_class_weights": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
     "gr_face_polygon_index": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32,
                               _vp, _vp, _i64, _vp, _vp, _vp],
+    "gr_points_in_region": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp],
+    "gr_submesh_extract": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
     "gr_sample_raster": [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _f64, _f64,
                          _i32, _vp, _vp],
 }
@@ -914,6 +921,59 @@ class HipRaster:
             if n_bad:
                 raise ValueError(f"gr_face_polygon_index: {n_bad} faces name a vertex outside [0, {int(vq_t.shape[0])})")
         return out, stats
+
+    # -- region of interest: points in a buffered union of polygon rows, the sub-mesh they select ----------------------
+    def points_in_region(self, points_q, ring_vertices, ring_offsets, ring_polygon, ring_is_hole, polygon_boxes, buffer_steps: int = 0):
+        """gr_points_in_region (DESIGN.md "Region of interest"): points_q (N, 2) int64 snapped points and the snapped ring table of
+        `PlanarPolygons.snapped` (the hole flags play no part) -- numpy or device tensors --, buffer_steps the buffer D in grid
+        steps, 0 <= D < 2^40 -> (mask (N,) bool tensor: the point lies in the closed region of some row or within D of an edge of
+        some ring; stats (GR_PIR_STAT_WORDS,) int64 tensor: points inside, inside by the buffer only, 256-bit comparisons
+        formed).  Only enqueues."""
+        torch = _torch()
+        pq_t = self._dev(points_q, torch.int64)
+        rv_t = self._dev(ring_vertices, torch.int64)
+        off_t = self._dev(ring_offsets, torch.int64)
+        rp_t = self._dev(ring_polygon, torch.int32)
+        box_t = self._dev(polygon_boxes, torch.int64)
+        if pq_t.ndim != 2 or pq_t.shape[1] != 2:
+            raise ValueError(f"points must be (N, 2), got {tuple(pq_t.shape)}")
+        R, P = int(rp_t.shape[0]), int(box_t.shape[0])
+        if rv_t.ndim != 2 or rv_t.shape[1] != 2 or tuple(off_t.shape) != (R + 1,) or box_t.ndim != 2 or box_t.shape[1] != 4:
+            raise ValueError(f"ring table must be (N, 2) vertices, (R + 1,) offsets, (R,) polygons and (P, 4) boxes, got "
+                             f"{tuple(rv_t.shape)}, {tuple(off_t.shape)}, {tuple(rp_t.shape)} and {tuple(box_t.shape)}")
+        D = int(buffer_steps)
+        if not 0 <= D < 2 ** 40:
+            raise ValueError(f"gr_points_in_region: buffer D={D} outside [0, 2^40) grid steps")
+        N = int(pq_t.shape[0])
+        mask = torch.empty((N,), dtype=torch.uint8, device=self.device)
+        stats = torch.empty((GR_PIR_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        self._call("gr_points_in_region", pq_t.data_ptr(), N, rv_t.data_ptr(), int(rv_t.shape[0]), off_t.data_ptr(),
+                   rp_t.data_ptr(), R, box_t.data_ptr(), P, D, mask.data_ptr(), stats.data_ptr(), self._stream())
+        return mask.to(torch.bool), stats
+
+    def submesh_extract(self, mask, faces, check: bool = True):
+        """gr_submesh_extract (DESIGN.md "Region of interest", Q5-Q6): mask (V,) bool or uint8 (the selected vertices), faces
+        (F, 3) int -- numpy or device tensors -> (face_ids (n_faces,) int64, point_ids (n_points,) int64, new_faces (n_faces, 3)
+        int32 tensors, counts (3,) int64 tensor: kept faces, kept vertices, faces with a vertex index outside [0, V)).  A face is
+        kept iff one of its vertices is selected, a vertex iff a kept face uses it; the ids are the ascending original indices
+        and new_faces indexes the kept vertices.  Reads the counts back (the results are cut to them); `check` (default) raises
+        ValueError when a face names a vertex that does not exist."""
+        torch = _torch()
+        m_t = self._dev(mask, torch.bool).to(torch.uint8).reshape(-1)
+        f_t = self._dev(faces, torch.int32)
+        if f_t.ndim != 2 or f_t.shape[1] != 3:
+            raise ValueError(f"faces must be (F, 3), got {tuple(f_t.shape)}")
+        V, F = int(m_t.shape[0]), int(f_t.shape[0])
+        face_ids = torch.empty((F,), dtype=torch.int64, device=self.device)
+        point_ids = torch.empty((V,), dtype=torch.int64, device=self.device)
+        new_faces = torch.empty((F, 3), dtype=torch.int32, device=self.device)
+        counts = torch.empty((3,), dtype=torch.int64, device=self.device)
+        self._call("gr_submesh_extract", m_t.data_ptr(), V, f_t.data_ptr(), F, face_ids.data_ptr(), point_ids.data_ptr(),
+                   new_faces.data_ptr(), counts.data_ptr(), self._stream())
+        n_faces, n_points, n_bad = (int(v) for v in counts.cpu())
+        if check and n_bad:
+            raise ValueError(f"gr_submesh_extract: {n_bad} faces name a vertex outside [0, {V})")
+        return face_ids[:n_faces], point_ids[:n_points], new_faces[:n_faces], counts
 
     # -- raster samples: the value of a raster under every face centre or vertex -----------------------------------
     def sample_raster(self, points, faces, raster_data, inverse6, nodata, fill, *, want_values: bool = True,

@@ -404,6 +404,65 @@ class PhotogrammetryCameraSet:
         subset_camera_set.cameras = [subset_camera_set[i] for i in inds]
         return subset_camera_set
 
+    def inds_in_folder(self, folder: PATH_TYPE) -> List[int]:
+        """The cameras whose image lies under `folder`."""
+        folder = Path(folder)
+        return [i for i, cam in enumerate(self.cameras)
+                if cam.image_filename is not None and Path(cam.image_filename).is_relative_to(folder)]
+
+    def inds_matching_filename_regex(self, filename_regex: str) -> List[int]:
+        """The cameras whose image path `re.search` finds the expression in."""
+        import re
+
+        return [i for i, cam in enumerate(self.cameras) if re.search(filename_regex, str(cam.image_filename))]
+
+    def get_cameras_in_folder(self, folder: PATH_TYPE):
+        """reference: cameras.py:819-836"""
+        return self.get_subset_cameras(self.inds_in_folder(folder))
+
+    def get_cameras_matching_filename_regex(self, filename_regex: str):
+        """reference: cameras.py:838-859"""
+        return self.get_subset_cameras(self.inds_matching_filename_regex(filename_regex))
+
+    def get_camera_locations(self) -> np.ndarray:
+        """(n, 3) float64: the translation of every camera's cam_to_world_transform, in the chunk-local frame (reference:
+        cameras.py:955-966)."""
+        return np.array([np.asarray(cam.cam_to_world_transform, dtype=np.float64)[:3, 3] for cam in self.cameras],
+                        dtype=np.float64).reshape(-1, 3)
+
+    def get_subset_ROI(self, ROI, buffer_radius: float = 0, is_geospatial: Optional[bool] = None, *, points_in_ROI_CRS=None,
+                       backend=None):
+        """The cameras within `buffer_radius` of a region (reference: cameras.py:1207-1273; DESIGN.md "Region of interest").
+
+        ROI: a `PlanarPolygons`, a sequence its `from_sequence` takes, or a `.geojson` path.  is_geospatial: None takes a
+        `.geojson` for geospatial and ring arrays for local.  A local ROI is compared with `get_camera_locations()` (x, y of the
+        chunk-local frame); a geospatial one needs the camera positions in ITS planar CRS as points_in_ROI_CRS (n, 2) or (n, 3)
+        -- the reference reprojects lon / lat with pyproj -- else NotImplementedError.  A camera ON the buffered region's
+        boundary is kept (`within` drops it).  backend: an object with `HipRaster.points_in_region` (default: a `HipRaster` on
+        the current device)."""
+        from geograypher_amd.utils.geometric import points_in_region
+
+        if is_geospatial is None:
+            is_geospatial = isinstance(ROI, (str, os.PathLike))
+        if points_in_ROI_CRS is not None:
+            locations = np.asarray(points_in_ROI_CRS, dtype=np.float64)
+            if locations.ndim != 2 or locations.shape[0] != len(self.cameras) or locations.shape[1] not in (2, 3):
+                raise ValueError(f"points_in_ROI_CRS must be ({len(self.cameras)}, 2) or ({len(self.cameras)}, 3), got "
+                                 f"{locations.shape}")
+        elif is_geospatial:
+            raise NotImplementedError(
+                "a geospatial ROI needs points_in_ROI_CRS: the camera positions in the ROI's planar CRS (CRS reprojection needs "
+                "pyproj and is outside the projection path)")
+        else:
+            locations = self.get_camera_locations()
+        if backend is None:
+            from geograypher_amd._hip import HipRaster
+
+            backend = HipRaster(None)
+        mask, _ = points_in_region(backend, ROI, locations, buffer_radius)
+        mask = np.asarray(mask.cpu() if hasattr(mask, "detach") else mask, dtype=bool)
+        return self.get_subset_cameras(np.nonzero(mask)[0].tolist())
+
     def get_image_by_index(self, index: int, image_scale: float = 1.0) -> np.ndarray:
         return self[index].get_image(image_scale=image_scale)
 

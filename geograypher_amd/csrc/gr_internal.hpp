@@ -13,6 +13,7 @@
 //   cover.hip        covering meshes: bounds of a point set (k_points_bounds), highest / lowest member per grid cell (k_cover_grid); no mesh needed
 //   polygons.hip     label_polygons: weighted face area per (polygon, class), exact containment or clipped overlay (k_polygon_weights); no mesh needed
 //                    vector textures: the polygon row of every face centre through a cell index (k_face_polygon_index)
+//                    region of interest: points in a buffered union of rows (k_points_in_region), the sub-mesh they select (k_submesh_flags, k_submesh_write + two scans)
 //   terrain.hip      raster samples: the value of a raster under every face centre or vertex, height above it, ground relabel (k_sample_raster); no mesh needed
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -38,6 +39,7 @@
 #define GR_MAX_DIM 16384    // h, w limit (guard band and 16-bit bbox packing)
 #define GR_BLOCK 64         // faces per block of the Morton-ordered soup: one wave, one bounding sphere
 #define GR_BLOCK_VERTS 192  // distinct vertices a block can have (3 per face); a patch of a manifold mesh has about 48
+#define GR_REGION_HEAD_WORDS 16  // 32-bit words at the front of gr_ctx::region_tmp: the joint box of gr_points_in_region (4 x int64), padded to 64 bytes
 namespace grimpl {
 
 // The words of the overflow protocol, named once: kernels, host decode and the vote pass all index through these.
@@ -247,6 +249,8 @@ struct gr_ctx {
   int64_t resize_have = 0;
   double *bounds_part = nullptr;       // per-workgroup partial records of gr_points_bounds (cover.hip): 1024 x 64 bytes
   int64_t bounds_part_have = 0;
+  uint32_t *region_tmp = nullptr;      // polygons.hip: the joint box of gr_points_in_region | flags, scans and hipcub's temporaries of gr_submesh_extract
+  int64_t region_have = 0;             // ... in 32-bit words
   hipStream_t last_stream = nullptr;   // of the last raster call (gr_raster_status reads its outcome there)
   std::vector<hipStream_t> used_streams;  // streams that work touching context scratch was enqueued on since the last quiesce
   // profiling

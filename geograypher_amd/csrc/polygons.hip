@@ -1,7 +1,9 @@
 // geograypher_amd/csrc/polygons.hip -- label_polygons on the device: the weighted area every mesh face contributes to every
 // polygon, summed per (polygon, class) (gr_polygon_class_weights; the rule-set is DESIGN.md "Polygon labels"), and the polygon row
-// every face CENTRE lies in (gr_face_polygon_index, at the end of the file; DESIGN.md "Vector textures").  Neither needs an
-// uploaded mesh: the caller hands over snapped integer coordinates.
+// every face CENTRE lies in (gr_face_polygon_index; DESIGN.md "Vector textures"), and the region of interest: which points lie in
+// a buffered union of polygon rows (gr_points_in_region) and the sub-mesh of the faces that touch them (gr_submesh_extract), at
+// the end of the file; DESIGN.md "Region of interest".  None needs an uploaded mesh: the caller hands over snapped integer
+// coordinates.
 //
 // gr_polygon_class_weights:
 // Shape: face-major, one face per lane.  The ring table is walked WAVE-UNIFORMLY: ring r, its polygon, the polygon's box and
@@ -15,6 +17,8 @@
 //   GR_POLY_OVERLAY  f64: the ring streamed vertex by vertex through the triangle's three half-planes (Sutherland-Hodgman with
 //                    O(1) state per stage, no per-lane vertex arrays) into a shoelace sum, in coordinates relative to the
 //                    triangle's first vertex
+#include <hipcub/hipcub.hpp>
+
 #include "gr_internal.hpp"
 
 using namespace grimpl;
@@ -332,6 +336,187 @@ __global__ __launch_bounds__(256) void k_face_polygon_index(const int64_t *__res
   }
 }
 
+// ---- gr_points_in_region: is a point in the union of the rows' closed regions, grown by D?  (DESIGN.md "Region of interest", Q3-Q4) ----
+typedef unsigned __int128 u128;
+
+struct RegionArgs {
+  int64_t N, n_rv, D;
+  int R, P;
+};
+
+struct U256 { uint64_t w[4]; };   // little-endian limbs
+
+// the full product of two unsigned 128-bit numbers, from 64-bit limbs
+__device__ __forceinline__ U256 mul_128x128(u128 a, u128 b) {
+  const uint64_t a0 = (uint64_t)a, a1 = (uint64_t)(a >> 64), b0 = (uint64_t)b, b1 = (uint64_t)(b >> 64);
+  U256 r;
+  r.w[0] = a0 * b0;
+  u128 acc = (u128)__umul64hi(a0, b0) + (u128)(a0 * b1) + (u128)(a1 * b0);
+  r.w[1] = (uint64_t)acc;
+  acc = (acc >> 64) + (u128)__umul64hi(a0, b1) + (u128)__umul64hi(a1, b0) + (u128)(a1 * b1);
+  r.w[2] = (uint64_t)acc;
+  r.w[3] = (uint64_t)(acc >> 64) + __umul64hi(a1, b1);
+  return r;
+}
+__device__ __forceinline__ bool le_256(const U256 &a, const U256 &b) {
+  if (a.w[3] != b.w[3]) return a.w[3] < b.w[3];
+  if (a.w[2] != b.w[2]) return a.w[2] < b.w[2];
+  if (a.w[1] != b.w[1]) return a.w[1] < b.w[1];
+  return a.w[0] <= b.w[0];
+}
+
+#define GR_REGION_FAR ((int64_t)1 << 62)   // bound of the joint box of nothing: stays empty when grown by D < 2^40
+
+// joint [4]: xmin ymin xmax ymax over the rows with a box (xmin <= xmax and ymin <= ymax).  One workgroup.
+__global__ __launch_bounds__(256) void k_region_joint_box(const int64_t *__restrict__ pbox, int P, int64_t *__restrict__ joint) {
+  __shared__ int64_t part[4][256];
+  int64_t x0 = GR_REGION_FAR, y0 = GR_REGION_FAR, x1 = -GR_REGION_FAR, y1 = -GR_REGION_FAR;
+  for (int p = (int)threadIdx.x; p < P; p += 256) {
+    const int64_t *b = pbox + (int64_t)p * 4;
+    if (b[0] <= b[2] && b[1] <= b[3]) { x0 = min(x0, b[0]); y0 = min(y0, b[1]); x1 = max(x1, b[2]); y1 = max(y1, b[3]); }
+  }
+  part[0][threadIdx.x] = x0; part[1][threadIdx.x] = y0; part[2][threadIdx.x] = x1; part[3][threadIdx.x] = y1;
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const bool lo = threadIdx.x < 2;
+    int64_t v = part[threadIdx.x][0];
+    for (int i = 1; i < 256; ++i) v = lo ? min(v, part[threadIdx.x][i]) : max(v, part[threadIdx.x][i]);
+    joint[threadIdx.x] = v;
+  }
+}
+
+// pq [N][2] snapped points; rv, roff, rpoly, pbox: the ring table; joint [4] of k_region_joint_box; mask [N]; stats
+// [GR_PIR_STAT_WORDS].  One point per lane; rows, rings and edges are walked WAVE-UNIFORMLY (every address of the table is the same
+// in all lanes: scalar loads), the lanes differ only in their execution mask.  A lane is `contained` once it is on a ring or a row's
+// crossings came out odd (Q3) and then takes no further part; `near` once an edge is within D (Q4), after which it only goes on
+// counting crossings (the statistics tell the two apart).  The wave leaves the table when every lane is contained.
+__global__ __launch_bounds__(256) void k_points_in_region(const int64_t *__restrict__ pq, const int64_t *__restrict__ rv,
+                                                          const int64_t *__restrict__ roff, const int32_t *__restrict__ rpoly,
+                                                          const int64_t *__restrict__ pbox, const int64_t *__restrict__ joint,
+                                                          uint8_t *__restrict__ mask, unsigned long long *__restrict__ stats,
+                                                          RegionArgs a) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t D = a.D;
+  const u128 D2 = (u128)(uint64_t)D * (u128)(uint64_t)D;
+  int64_t px = 0, py = 0;
+  bool live = idx < a.N;
+  if (live) {
+    px = pq[idx * 2]; py = pq[idx * 2 + 1];
+    live = px >= joint[0] - D && px <= joint[2] + D && py >= joint[1] - D && py <= joint[3] + D;   // most points of a mesh leave here
+  }
+  bool contained = false, near = false;
+  unsigned long long wide = 0;
+  int cur = -1;          // row of the rings being walked (wave-uniform)
+  bool in_row = false;   // this lane's point is in the row's box grown by D, and was not contained when the row began
+  int parity = 0;
+
+  for (int r = 0; r < a.R; ++r) {
+    const int p = rpoly[r];
+    if (p != cur) {
+      if (in_row && (parity & 1)) contained = true;
+      in_row = false; parity = 0;
+      if (!__ballot(live && !contained)) break;
+      cur = (p >= 0 && p < a.P) ? p : -1;
+      if (cur >= 0) {
+        const int64_t *b = pbox + (int64_t)cur * 4;
+        in_row = live && !contained && b[0] <= b[2] && b[1] <= b[3] && px >= b[0] - D && px <= b[2] + D && py >= b[1] - D &&
+                 py <= b[3] + D;
+      }
+    }
+    int64_t i0 = roff[r], i1 = roff[r + 1];
+    i0 = min(max(i0, (int64_t)0), a.n_rv); i1 = min(max(i1, i0), a.n_rv);   // a bad offset table reads nothing outside the vertices
+    const int64_t n = i1 - i0;
+    if (cur < 0 || n < 3 || !__ballot(in_row && !contained)) continue;
+    const int64_t *v = rv + i0 * 2;
+    int64_t ax = v[2 * (n - 1)], ay = v[2 * (n - 1) + 1];
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t bx = v[2 * i], by = v[2 * i + 1];
+      if (in_row && !contained) {
+        const int64_t exlo = min(ax, bx), exhi = max(ax, bx), eylo = min(ay, by), eyhi = max(ay, by);
+        // Q3: crossings right of the point, half-open in y; a point on the edge is contained at once
+        const bool cross = (ay <= py) != (by <= py);
+        const bool in_box = exlo <= px && px <= exhi && eylo <= py && py <= eyhi;
+        if (cross || in_box) {
+          const i128 o = orient(ax, ay, bx, by, px, py);
+          if (o == 0 && in_box) contained = true;
+          if (cross && (o > 0) == (by > ay)) parity ^= 1;
+        }
+        // Q4: the distance to the closed edge against D, for an edge whose box grown by D holds the point
+        if (D > 0 && !near && !contained && px >= exlo - D && px <= exhi + D && py >= eylo - D && py <= eyhi + D) {
+          const int64_t ux = px - ax, uy = py - ay, ex = bx - ax, ey = by - ay;   // |.| < 2^42: products below 2^84
+          const i128 t = (i128)ux * ex + (i128)uy * ey, L2 = (i128)ex * ex + (i128)ey * ey;
+          if (t <= 0) {
+            near = (u128)((i128)ux * ux + (i128)uy * uy) <= D2;
+          } else if (t >= L2) {
+            const int64_t wx = px - bx, wy = py - by;
+            near = (u128)((i128)wx * wx + (i128)wy * wy) <= D2;
+          } else {
+            const i128 c = (i128)ex * uy - (i128)ey * ux;
+            const u128 m = (u128)(c < 0 ? -c : c);
+            ++wide;
+            near = le_256(mul_128x128(m, m), mul_128x128(D2, (u128)L2));   // cross^2 <= D^2 L2: about 166 bits
+          }
+        }
+      }
+      ax = bx; ay = by;
+    }
+  }
+  if (in_row && (parity & 1)) contained = true;
+  if (idx < a.N) mask[idx] = (contained || near) ? 1 : 0;
+
+  // statistics: one atomic per wave and word
+  const double is = wave_sum((contained || near) ? 1.0 : 0.0), bs = wave_sum((near && !contained) ? 1.0 : 0.0);
+  const double ws = wave_sum((double)wide);   // < 2^53: exact
+  if (lane == 0) {
+    if (is > 0.0) atomicAdd(&stats[GR_PIR_STAT_INSIDE], (unsigned long long)is);
+    if (bs > 0.0) atomicAdd(&stats[GR_PIR_STAT_BUFFER_ONLY], (unsigned long long)bs);
+    if (ws > 0.0) atomicAdd(&stats[GR_PIR_STAT_WIDE], (unsigned long long)ws);
+  }
+}
+
+// ---- gr_submesh_extract: the faces with a vertex in the mask, the vertices they use, renumbered in order (Q5, Q6) ------------------
+// fflag [F], vused [V] (zeroed by the caller): 1 where kept.  A face that names a vertex outside [0, V) reads nothing and is counted.
+__global__ __launch_bounds__(256) void k_submesh_flags(const uint8_t *__restrict__ mask, int64_t V, const int32_t *__restrict__ faces,
+                                                       int64_t F, int32_t *__restrict__ fflag, int32_t *__restrict__ vused,
+                                                       unsigned long long *__restrict__ counts) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  double bad = 0.0;
+  if (f < F) {
+    const int64_t v0 = faces[f * 3], v1 = faces[f * 3 + 1], v2 = faces[f * 3 + 2];
+    int keep = 0;
+    if (v0 < 0 || v0 >= V || v1 < 0 || v1 >= V || v2 < 0 || v2 >= V) {
+      bad = 1.0;
+    } else {
+      keep = (mask[v0] | mask[v1] | mask[v2]) ? 1 : 0;
+      if (keep) { vused[v0] = 1; vused[v1] = 1; vused[v2] = 1; }   // every writer stores the same value
+    }
+    fflag[f] = keep;
+  }
+  const double bs = wave_sum(bad);
+  if (lane == 0 && bs > 0.0) atomicAdd(&counts[2], (unsigned long long)bs);
+}
+
+// fpos, vpos: the exclusive sums of fflag, vused.  One thread per face and per vertex.
+__global__ __launch_bounds__(256) void k_submesh_write(const int32_t *__restrict__ faces, int64_t F, int64_t V,
+                                                       const int32_t *__restrict__ fflag, const int32_t *__restrict__ fpos,
+                                                       const int32_t *__restrict__ vused, const int32_t *__restrict__ vpos,
+                                                       int64_t *__restrict__ face_ids, int64_t *__restrict__ point_ids,
+                                                       int32_t *__restrict__ new_faces, unsigned long long *__restrict__ counts) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < F && fflag[i]) {   // a kept face's vertices are in range and used
+    const int64_t j = fpos[i];
+    face_ids[j] = i;
+    for (int k = 0; k < 3; ++k) new_faces[j * 3 + k] = vpos[faces[i * 3 + k]];
+  }
+  if (i < V && vused[i]) point_ids[vpos[i]] = i;
+  if (i == 0) {
+    counts[0] = F > 0 ? (unsigned long long)(fpos[F - 1] + fflag[F - 1]) : 0ull;
+    counts[1] = V > 0 ? (unsigned long long)(vpos[V - 1] + vused[V - 1]) : 0ull;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -391,6 +576,76 @@ int gr_face_polygon_index(gr_ctx *c, const int64_t *verts_q, int64_t V, const in
   hipLaunchKernelGGL(k_face_polygon_index, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, verts_q, faces, ring_vertices,
                      ring_offsets, ring_polygon, polygon_boxes, cell_offsets, cell_polygons, face_polygon,
                      (unsigned long long *)stats, a);
+  GR_HIP(c, hipGetLastError());
+  return GR_OK;
+}
+
+int gr_points_in_region(gr_ctx *c, const int64_t *points_q, int64_t N, const int64_t *ring_vertices, int64_t n_ring_vertices,
+                        const int64_t *ring_offsets, const int32_t *ring_polygon, int64_t R, const int64_t *polygon_boxes,
+                        int64_t P, int64_t D, uint8_t *mask, uint64_t *stats, void *stream) {
+  if (!c) return GR_EINVAL;
+  if (N < 0 || R < 0 || P < 0 || n_ring_vertices < 0 || N > 0x7FFFFFFFll * 256 || R > 0x7FFFFFFF || P > 0x7FFFFFFF)
+    return fail(c, GR_EINVAL, "gr_points_in_region: bad shape N=%lld R=%lld P=%lld", (long long)N, (long long)R, (long long)P);
+  if (D < 0 || D >= ((int64_t)1 << 40))
+    return fail(c, GR_EINVAL, "gr_points_in_region: buffer D=%lld outside [0, 2^40) grid steps", (long long)D);
+  if (!stats || (N > 0 && (!points_q || !mask)) || (P > 0 && !polygon_boxes) ||
+      (R > 0 && (!ring_offsets || !ring_polygon || (n_ring_vertices > 0 && !ring_vertices))))
+    return fail(c, GR_EINVAL, "gr_points_in_region: null arrays");
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
+  GR_HIP(c, hipMemsetAsync(stats, 0, sizeof(uint64_t) * GR_PIR_STAT_WORDS, s));
+  if (N == 0) return GR_OK;
+  if (R == 0 || P == 0) {   // a region without rings holds nothing
+    GR_HIP(c, hipMemsetAsync(mask, 0, (size_t)N, s));
+    return GR_OK;
+  }
+  int rc = grow(c, c->region_tmp, c->region_have, (int64_t)GR_REGION_HEAD_WORDS, "region");
+  if (rc != GR_OK) return rc;
+  note_stream(c, s);
+  int64_t *joint = (int64_t *)c->region_tmp;
+  hipLaunchKernelGGL(k_region_joint_box, dim3(1), dim3(256), 0, s, polygon_boxes, (int)P, joint);
+  RegionArgs a;
+  a.N = N; a.n_rv = n_ring_vertices; a.D = D; a.R = (int)R; a.P = (int)P;
+  hipLaunchKernelGGL(k_points_in_region, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, points_q, ring_vertices, ring_offsets,
+                     ring_polygon, polygon_boxes, (const int64_t *)joint, mask, (unsigned long long *)stats, a);
+  GR_HIP(c, hipGetLastError());
+  return GR_OK;
+}
+
+int gr_submesh_extract(gr_ctx *c, const uint8_t *mask, int64_t V, const int32_t *faces, int64_t F, int64_t *face_ids,
+                       int64_t *point_ids, int32_t *new_faces, uint64_t *counts, void *stream) {
+  if (!c) return GR_EINVAL;
+  if (V < 0 || F < 0 || V > 0x7FFFFFFFll || F > 0x7FFFFFFFll)
+    return fail(c, GR_EINVAL, "gr_submesh_extract: bad shape V=%lld F=%lld", (long long)V, (long long)F);
+  if (!counts || (V > 0 && (!mask || !point_ids)) || (F > 0 && (!faces || !face_ids || !new_faces)))
+    return fail(c, GR_EINVAL, "gr_submesh_extract: null arrays");
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
+  GR_HIP(c, hipMemsetAsync(counts, 0, sizeof(uint64_t) * 3, s));
+  if (F == 0) return GR_OK;   // no face: nothing is kept (a vertex no face uses is dropped)
+  size_t fb = 0, vb = 0;
+  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, fb, (int32_t *)nullptr, (int32_t *)nullptr, (int)F, s));
+  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, vb, (int32_t *)nullptr, (int32_t *)nullptr, (int)V, s));
+  // scratch, in 32-bit words: head | fflag [F] | fpos [F] | vused [V] | vpos [V] | the scans' temporaries (16-byte aligned)
+  const int64_t o_ff = GR_REGION_HEAD_WORDS, o_fp = o_ff + F, o_vu = o_fp + F, o_vp = o_vu + V;
+  const int64_t o_tmp = (o_vp + V + 3) & ~(int64_t)3;
+  const int64_t tmp_words = (int64_t)((std::max(fb, vb) + 3) / 4) + 4;
+  int rc = grow(c, c->region_tmp, c->region_have, o_tmp + tmp_words, "sub-mesh");
+  if (rc != GR_OK) return rc;
+  note_stream(c, s);
+  int32_t *base = (int32_t *)c->region_tmp;
+  int32_t *fflag = base + o_ff, *fpos = base + o_fp, *vused = base + o_vu, *vpos = base + o_vp;
+  void *tmp = (void *)(base + o_tmp);
+  GR_HIP(c, hipMemsetAsync(vused, 0, sizeof(int32_t) * (size_t)V, s));
+  hipLaunchKernelGGL(k_submesh_flags, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, mask, V, faces, F, fflag, vused,
+                     (unsigned long long *)counts);
+  size_t tb = fb;
+  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, tb, fflag, fpos, (int)F, s));
+  tb = vb;
+  if (V > 0) GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, tb, vused, vpos, (int)V, s));
+  hipLaunchKernelGGL(k_submesh_write, dim3((unsigned)ceil_div(std::max(F, V), 256)), dim3(256), 0, s, faces, F, V,
+                     (const int32_t *)fflag, (const int32_t *)fpos, (const int32_t *)vused, (const int32_t *)vpos, face_ids, point_ids,
+                     new_faces, (unsigned long long *)counts);
   GR_HIP(c, hipGetLastError());
   return GR_OK;
 }

@@ -1,0 +1,199 @@
+"""Aggregate per-image predictions onto the mesh: label images from many viewpoints -> votes per face -> a class per face.
+
+Mirror of geograypher/entrypoints/aggregate_images.py:19-233 in the formats this package reads: the mesh as `.npz` (points, faces;
+EPSG:4978), the cameras as a Metashape XML, the predictions as index images under `label_folder` in the layout of `image_folder`
+(`LookUpSegmentor`).  The camera set is cut by `subset_images_folder`, `filename_regex`, `take_every_nth_camera` and -- with `ROI`
+and `ROI_camera_points_file` -- to the cameras within `ROI_buffer_radius_meters` of the ROI; the mesh is cropped to the ROI grown by
+the same distance (`select_mesh_ROI`, on the device), which needs `ROI_points_file`, the vertices in the ROI's CRS.  The aggregated
+face values (`aggregate_projected_images`) and the class per face (`argmax_nonzero`, NaN where nothing was seen) are written as
+`.npy`; with `DTM_file`, `DTM_points_file` and `height_above_ground_threshold` the faces near the terrain lose their class first
+(`label_ground_class`).  Not carried over: mesh decimation, the top-down vector export and the visualisations."""
+import argparse
+import json
+import math
+import typing
+from pathlib import Path
+
+import numpy as np
+
+from geograypher_amd.constants import PATH_TYPE
+
+
+def aggregate_images(
+    mesh_file,
+    cameras_file: PATH_TYPE,
+    image_folder: PATH_TYPE,
+    label_folder: PATH_TYPE,
+    mesh_CRS,
+    original_image_folder: typing.Union[PATH_TYPE, None] = None,
+    subset_images_folder: typing.Union[PATH_TYPE, None] = None,
+    filename_regex: typing.Optional[str] = None,
+    take_every_nth_camera: typing.Union[int, None] = 100,
+    DTM_file: typing.Union[PATH_TYPE, None] = None,
+    height_above_ground_threshold: float = 2.0,
+    ROI=None,
+    ROI_buffer_radius_meters: float = 50,
+    IDs_to_labels: typing.Union[dict, str, None] = None,
+    mesh_downsample: float = 1.0,
+    n_aggregation_clusters: typing.Union[int, None] = None,
+    n_cameras_per_aggregation_cluster: typing.Union[int, None] = None,
+    aggregate_image_scale: float = 1.0,
+    aggregated_face_values_savefile: typing.Union[PATH_TYPE, None] = None,
+    predicted_face_classes_savefile: typing.Union[PATH_TYPE, None] = None,
+    top_down_vector_projection_savefile: typing.Union[PATH_TYPE, None] = None,
+    vis: bool = False,
+    ROI_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
+    ROI_camera_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
+    DTM_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
+    camera_set=None,
+    backend=None,
+):
+    """Aggregate the labels under `label_folder` onto the mesh (see the module docstring).  The reference's arguments and defaults;
+    `mesh_downsample != 1`, `top_down_vector_projection_savefile`, `vis`, `ROI` without `ROI_points_file` and `DTM_file` without
+    `DTM_points_file` raise NotImplementedError.  Beyond the reference: `ROI_points_file` and `DTM_points_file` (`.npy` paths or
+    arrays: the V ORIGINAL vertices in the ROI's / the DTM's CRS), `ROI_camera_points_file` (the positions of the cameras of the full
+    set in the ROI's CRS; without it the camera set is not cut to the ROI, with a log line), and `camera_set` and `backend`, which
+    replace the objects built from `cameras_file` and the device.  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
+    from geograypher_amd.cameras.segmentor import SegmentorPhotogrammetryCameraSet
+    from geograypher_amd.meshes import TexturedPhotogrammetryMesh, TexturedPhotogrammetryMeshChunked
+    from geograypher_amd.predictors.derived_segmentors import LookUpSegmentor
+
+    for name, value, why in (
+        ("DTM_file", DTM_file if DTM_points_file is None else None,
+         "the vertices in the DTM's CRS are needed (DTM_points_file); reprojecting them needs pyproj"),
+        ("ROI", ROI if ROI_points_file is None else None,
+         "the vertices in the ROI's CRS are needed (ROI_points_file); reprojecting them needs pyproj"),
+        ("top_down_vector_projection_savefile", top_down_vector_projection_savefile, "the vector export needs geopandas"),
+    ):
+        if value is not None:
+            raise NotImplementedError(f"{name}: {why}, which is outside the projection path")
+    if vis:
+        raise NotImplementedError("vis: visualisations need pyvista, which is outside the projection path")
+    if mesh_downsample != 1:
+        raise NotImplementedError("mesh_downsample: mesh decimation is outside the projection path (meshes.py:215-226)")
+
+    def points_array(source):   # a .npy path or the array itself
+        return np.load(source) if isinstance(source, (str, Path)) else source
+
+    if isinstance(IDs_to_labels, (str, Path)):
+        with open(IDs_to_labels, "r") as file:
+            IDs_to_labels = {int(k): v for k, v in json.load(file).items()}
+
+    # the cameras first: they are cheap and catch bad inputs early (aggregate_images.py:106-136)
+    if camera_set is None:
+        from geograypher_amd.cameras.derived_cameras import MetashapeCameraSet
+
+        camera_set = MetashapeCameraSet(cameras_file, image_folder, original_image_folder=original_image_folder,
+                                        validate_images=True)
+    camera_points = points_array(ROI_camera_points_file)
+    if camera_points is not None:   # follows the cameras through the filters below
+        camera_points = np.asarray(camera_points, dtype=np.float64)
+        if camera_points.shape[0] != len(camera_set):
+            raise ValueError(f"ROI_camera_points_file has {camera_points.shape[0]} rows for {len(camera_set)} cameras")
+
+    def subset(inds):
+        nonlocal camera_set, camera_points
+        inds = [int(i) for i in inds]
+        camera_set = camera_set.get_subset_cameras(inds)
+        camera_points = None if camera_points is None else camera_points[inds]
+
+    if subset_images_folder is not None:
+        subset(camera_set.inds_in_folder(subset_images_folder))
+    if filename_regex is not None:
+        subset(camera_set.inds_matching_filename_regex(filename_regex))
+    if take_every_nth_camera is not None:
+        subset(range(0, len(camera_set), take_every_nth_camera))
+
+    MeshClass = (TexturedPhotogrammetryMesh if n_aggregation_clusters is None and n_cameras_per_aggregation_cluster is None
+                 else TexturedPhotogrammetryMeshChunked)
+    roi_kwargs = {}
+    if ROI is not None:
+        roi_kwargs = {"ROI": ROI, "ROI_buffer_meters": 0 if ROI_buffer_radius_meters is None else ROI_buffer_radius_meters,
+                      "points_in_ROI_CRS": points_array(ROI_points_file)}
+    mesh = MeshClass(mesh_file, input_CRS=mesh_CRS, IDs_to_labels=IDs_to_labels, backend=backend, **roi_kwargs)
+
+    if ROI is not None and ROI_buffer_radius_meters is not None:
+        if camera_points is not None:
+            camera_set = camera_set.get_subset_ROI(ROI=ROI, buffer_radius=ROI_buffer_radius_meters, is_geospatial=True,
+                                                   points_in_ROI_CRS=camera_points, backend=mesh.backend)
+        else:
+            mesh.logger.info("ROI without ROI_camera_points_file: the camera set is not cut to the ROI")
+    if n_aggregation_clusters is None and n_cameras_per_aggregation_cluster is not None:
+        n_aggregation_clusters = int(math.ceil(len(camera_set) / n_cameras_per_aggregation_cluster))
+
+    if mesh.get_IDs_to_labels() is None:
+        raise ValueError("aggregate_images needs IDs_to_labels: the number of classes is its largest ID + 1")
+    segmentor = LookUpSegmentor(base_folder=image_folder, lookup_folder=label_folder,
+                                num_classes=int(np.max(list(mesh.get_IDs_to_labels().keys()))) + 1)
+    segmentor_camera_set = SegmentorPhotogrammetryCameraSet(camera_set, segmentor=segmentor)
+
+    n_clusters_kwargs = {} if n_aggregation_clusters is None else {"n_clusters": n_aggregation_clusters}
+    aggregated_face_labels, _ = mesh.aggregate_projected_images(segmentor_camera_set, aggregate_img_scale=aggregate_image_scale,
+                                                                **n_clusters_kwargs)
+    if aggregated_face_values_savefile is not None:
+        Path(aggregated_face_values_savefile).parent.mkdir(parents=True, exist_ok=True)
+        np.save(aggregated_face_values_savefile, aggregated_face_labels)
+
+    predicted_face_classes = mesh.backend.argmax_nonzero(aggregated_face_labels)
+    if hasattr(predicted_face_classes, "detach"):
+        predicted_face_classes = predicted_face_classes.cpu().numpy()
+    predicted_face_classes = np.array(predicted_face_classes, dtype=np.float64).reshape(-1, 1)
+
+    if DTM_file is not None and height_above_ground_threshold is not None:   # reference: aggregate_images.py:198-206
+        points_in_raster_CRS = points_array(DTM_points_file)
+        if mesh.ROI_point_IDs is not None:
+            points_in_raster_CRS = np.asarray(points_in_raster_CRS)[mesh.ROI_point_IDs]
+        predicted_face_classes = mesh.label_ground_class(labels=predicted_face_classes,
+                                                         height_above_ground_threshold=height_above_ground_threshold,
+                                                         DTM_file=DTM_file, ground_ID=np.nan, set_mesh_texture=False,
+                                                         points_in_raster_CRS=points_in_raster_CRS)
+
+    if predicted_face_classes_savefile is not None:
+        Path(predicted_face_classes_savefile).parent.mkdir(parents=True, exist_ok=True)
+        np.save(predicted_face_classes_savefile, predicted_face_classes)
+    return mesh, aggregated_face_labels, predicted_face_classes
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description="Aggregate predictions from individual images onto the mesh.",
+                                     formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("--mesh-file", type=Path, required=True, help="Mesh as .npz (points, faces)")
+    parser.add_argument("--cameras-file", type=Path, required=True, help="Metashape XML with camera calibrations and positions")
+    parser.add_argument("--image-folder", type=Path, required=True, help="Folder of the images the mesh was made from")
+    parser.add_argument("--label-folder", type=Path, required=True, help="Folder of index images, laid out like --image-folder")
+    parser.add_argument("--mesh-CRS", required=True, help="CRS of the mesh vertices (EPSG:4978)")
+    parser.add_argument("--original-image-folder", type=Path,
+                        help="Removed from the beginning of the absolute image paths stored in --cameras-file")
+    parser.add_argument("--subset-images-folder", type=Path, help="Use only the images under this folder")
+    parser.add_argument("--filename-regex", help="Use only the images whose path matches this expression")
+    parser.add_argument("--take-every-nth-camera", type=int, help="Use only every nth camera")
+    parser.add_argument("--DTM-file", type=Path, help="Single-band GeoTIFF of the terrain: faces near it lose their class")
+    parser.add_argument("--DTM-points-file", type=Path,
+                        help=".npy with the mesh vertices (V, 3) in the CRS of --DTM-file (required with it)")
+    parser.add_argument("--height-above-ground-threshold", type=float, default=2.0, help="Only applies with --DTM-file")
+    parser.add_argument("--ROI", help=".geojson of the region of interest; needs --ROI-points-file")
+    parser.add_argument("--ROI-points-file", type=Path,
+                        help=".npy with the mesh vertices (V, 2) or (V, 3) in the CRS of --ROI (required with it)")
+    parser.add_argument("--ROI-camera-points-file", type=Path,
+                        help=".npy with the camera positions in the CRS of --ROI; without it the camera set is not cut")
+    parser.add_argument("--ROI-buffer-radius-meters", default=50, type=float, help="Only applies with --ROI")
+    parser.add_argument("--IDs-to-labels", type=Path, required=True, help="JSON file {ID: label}")
+    parser.add_argument("--mesh-downsample", type=float, default=1.0, help="Only 1 is available here")
+    parser.add_argument("--aggregate-image-scale", type=float, default=0.25, help="Aggregate at this fraction of the image size")
+    parser.add_argument("--n-aggregation-clusters", type=int, help="Selects the chunked mesh class, as in the reference")
+    parser.add_argument("--aggregated-face-values-savefile", type=Path, help="Where the (F, classes) values are saved (.npy)")
+    parser.add_argument("--predicted-face-classes-savefile", type=Path, help="Where the (F, 1) classes are saved (.npy)")
+    parser.add_argument("--top-down-vector-projection-savefile", help="Not available here")
+    parser.add_argument("--vis", action="store_true", help="Not available here")
+    args = parser.parse_args(argv)
+    args.IDs_to_labels = str(args.IDs_to_labels)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    aggregate_images(**vars(args))
+
+
+if __name__ == "__main__":
+    main()

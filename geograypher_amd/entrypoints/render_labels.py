@@ -9,8 +9,11 @@ polygons' CRS (the reference reprojects them with pyproj).  Every face takes the
 `render_savefolder`, at the cameras' paths relative to `image_folder`, and `IDs_to_labels.json` beside them.  With `DTM_file` (a
 single-band GeoTIFF or a `PlanarRaster`) and `ground_height_threshold`, labelled faces lower than the threshold above the DTM are
 relabelled before rendering (`label_ground_class`, on the device): to a new class "GROUND" with `render_ground_class`, else to NaN;
-this needs `DTM_points_file`, the vertices in the DTM's CRS.  Not carried over: ROI cropping of mesh and cameras, mesh decimation,
-saving the image subset or the textured mesh, and the visualisations (geopandas, pyvista, matplotlib)."""
+this needs `DTM_points_file`, the vertices in the DTM's CRS.  With `ROI` (a `.geojson`, a `PlanarPolygons` or ring arrays) and
+`ROI_points_file`, the vertices in the ROI's CRS, the mesh is cropped to the ROI grown by `mesh_ROI_buffer_radius_meters` before
+anything else (`select_mesh_ROI`, on the device); the camera set is cut to `cameras_ROI_buffer_radius_meters` when
+`ROI_camera_points_file` gives the camera positions in the same CRS.  Not carried over: mesh decimation, saving the image subset or
+the textured mesh, and the visualisations (geopandas, pyvista, matplotlib)."""
 import argparse
 import json
 import typing
@@ -53,20 +56,26 @@ def render_labels(
     camera_set=None,
     backend=None,
     DTM_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
+    ROI_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
+    ROI_camera_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
 ):
     """Render the labels of `texture` into every camera's view (see the module docstring for inputs and files).  The reference's
-    arguments and defaults; `DTM_file` without `DTM_points_file`, `ROI`, `mesh_downsample != 1`, `subset_images_savefolder`, `textured_mesh_savefile`, `vis`,
+    arguments and defaults; `DTM_file` without `DTM_points_file`, `ROI` without `ROI_points_file`, `mesh_downsample != 1`, `subset_images_savefolder`, `textured_mesh_savefile`, `vis`,
     `mesh_vis_file` and `labels_vis_folder` raise NotImplementedError.  `n_cameras_per_chunk` selects
     `TexturedPhotogrammetryMeshChunked` with ceil(cameras / n_cameras_per_chunk) clusters, as in the reference (the GPU path
     renders the whole mesh either way).  Beyond the reference: `texture_points_file` (a `.npy` path or the array itself, required
     for a vector texture), `DTM_points_file` (likewise, the vertices in the DTM's CRS, required with `DTM_file`), `apply_distortion` (False for a camera set without a lens model), and `camera_set` and `backend`,
-    which replace the objects built from `cameras_file` and the device.  Returns the textured mesh."""
+    which replace the objects built from `cameras_file` and the device; `ROI_points_file` (the V original vertices in the ROI's CRS,
+    required with `ROI`) and `ROI_camera_points_file` (the camera positions in that CRS; without it the camera set is not cut, with a
+    log line).  `texture_points_file` and `DTM_points_file` are given for the ORIGINAL mesh and indexed by the kept vertices.  Returns
+    the textured mesh."""
     from geograypher_amd.meshes import TexturedPhotogrammetryMesh, TexturedPhotogrammetryMeshChunked
 
     for name, value, why in (
         ("DTM_file", DTM_file if DTM_points_file is None else None,
          "the vertices in the DTM's CRS are needed (DTM_points_file); reprojecting them needs pyproj"),
-        ("ROI", ROI, "ROI cropping needs geopandas"),
+        ("ROI", ROI if ROI_points_file is None else None,
+         "the vertices in the ROI's CRS are needed (ROI_points_file); reprojecting them needs pyproj"),
         ("subset_images_savefolder", subset_images_savefolder, "copying the image subset is not part of this package"),
         ("textured_mesh_savefile", textured_mesh_savefile, "mesh writers (pyvista) are not part of this package"),
         ("mesh_vis_file", mesh_vis_file, "visualisations need pyvista"),
@@ -84,18 +93,34 @@ def render_labels(
 
         camera_set = MetashapeCameraSet(cameras_file, image_folder, original_image_folder=original_image_folder)
 
-    n_render_chunks = None if n_cameras_per_chunk is None else int(ceil(len(camera_set) / n_cameras_per_chunk))
-    MeshClass = TexturedPhotogrammetryMesh if n_render_chunks is None else TexturedPhotogrammetryMeshChunked
-    mesh = MeshClass(mesh_file, input_CRS=mesh_CRS, IDs_to_labels=IDs_to_labels, backend=backend)
+    MeshClass = TexturedPhotogrammetryMesh if n_cameras_per_chunk is None else TexturedPhotogrammetryMeshChunked
 
-    points_in_polygon_CRS = texture_points_file
-    if isinstance(points_in_polygon_CRS, (str, Path)):
-        points_in_polygon_CRS = np.load(points_in_polygon_CRS)
+    def points_array(source):   # a .npy path or the array itself
+        return np.load(source) if isinstance(source, (str, Path)) else source
+
+    roi_kwargs = {}
+    if ROI is not None:   # reference: render_labels.py:120-131 (cameras), 141-149 (mesh)
+        roi_kwargs = {"ROI": ROI, "ROI_buffer_meters": mesh_ROI_buffer_radius_meters, "points_in_ROI_CRS": points_array(ROI_points_file)}
+    mesh = MeshClass(mesh_file, input_CRS=mesh_CRS, IDs_to_labels=IDs_to_labels, backend=backend, **roi_kwargs)
+    if ROI is not None:
+        if ROI_camera_points_file is not None:
+            camera_set = camera_set.get_subset_ROI(ROI=ROI, buffer_radius=cameras_ROI_buffer_radius_meters, is_geospatial=True,
+                                                   points_in_ROI_CRS=points_array(ROI_camera_points_file), backend=mesh.backend)
+        else:
+            mesh.logger.info("ROI without ROI_camera_points_file: the camera set is not cut to the ROI")
+    n_render_chunks = None if n_cameras_per_chunk is None else int(ceil(len(camera_set) / n_cameras_per_chunk))
+
+    def kept(points):   # the rows of the vertices the ROI kept
+        return points if points is None or mesh.ROI_point_IDs is None else np.asarray(points)[mesh.ROI_point_IDs]
+
+    points_in_polygon_CRS = kept(points_array(texture_points_file))
+    if isinstance(texture, np.ndarray):   # an array for the original mesh is cut like the mesh
+        texture = mesh.crop_to_ROI(texture)
     mesh.load_texture(texture, texture_column_name=texture_column_name, IDs_to_labels=mesh.IDs_to_labels,
                       points_in_polygon_CRS=points_in_polygon_CRS)
 
     if DTM_file is not None and ground_height_threshold is not None:   # reference: render_labels.py:161-171
-        points_in_raster_CRS = np.load(DTM_points_file) if isinstance(DTM_points_file, (str, Path)) else DTM_points_file
+        points_in_raster_CRS = kept(points_array(DTM_points_file))
         mesh.label_ground_class(DTM_file=DTM_file, height_above_ground_threshold=ground_height_threshold,
                                 only_label_existing_labels=True, ground_class_name="GROUND",
                                 ground_ID=None if render_ground_class else np.nan, set_mesh_texture=True,
@@ -133,7 +158,11 @@ def parse_args(argv=None):
     parser.add_argument("--render-ground-class", action="store_true",
                         help="Render ground as a class GROUND of its own instead of unlabelled; only applies with --DTM-file")
     parser.add_argument("--textured-mesh-savefile", help="Not available here")
-    parser.add_argument("--ROI", help="Not available here")
+    parser.add_argument("--ROI", help=".geojson of the region of interest; needs --ROI-points-file")
+    parser.add_argument("--ROI-points-file", type=Path,
+                        help=".npy with the mesh vertices (V, 2) or (V, 3) in the CRS of --ROI (required with it)")
+    parser.add_argument("--ROI-camera-points-file", type=Path,
+                        help=".npy with the camera positions in the CRS of --ROI; without it the camera set is not cut")
     parser.add_argument("--mesh-ROI-buffer-radius-meters", default=50, type=float, help="Only applies with --ROI")
     parser.add_argument("--cameras-ROI-buffer-radius-meters", default=100, type=float, help="Only applies with --ROI")
     parser.add_argument("--render-image-scale", type=float, default=1, help="Render at this fraction of the image size")

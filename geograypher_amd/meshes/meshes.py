@@ -125,15 +125,19 @@ class TexturedPhotogrammetryMesh:
         neg1_is_last_face: bool = True,
         devices: typing.Optional[typing.Sequence[int]] = None,
         vertex_order: str = "r1",
+        points_in_ROI_CRS: typing.Optional[np.ndarray] = None,
     ):
         """A textured mesh that renders to / aggregates from camera views on an MI355X.
 
         Same leading arguments as the reference constructor (meshes.py:55-156).  `mesh` is `(points (V,3), faces
         (F,3))`, any object with `.points`/`.faces` (pyvista layout accepted) or a `.npz` path.  The coordinates are
         interpreted in `input_CRS`; only EPSG:4978 (the frame the reference reprojects every mesh into,
-        meshes.py:1659) is accepted because CRS reprojection is outside the projection path.  Decimation, ROI
-        cropping and vector/raster texture files are likewise outside it and raise NotImplementedError (a `.geojson`
-        texture is loaded afterwards, by `load_texture(..., points_in_polygon_CRS=...)`).
+        meshes.py:1659) is accepted because CRS reprojection is outside the projection path.  Decimation and
+        vector/raster texture files are likewise outside it and raise NotImplementedError (a `.geojson` texture is
+        loaded afterwards, by `load_texture(..., points_in_polygon_CRS=...)`).  `ROI` with `ROI_buffer_meters` crops
+        the mesh before the texture is loaded (`select_mesh_ROI`; needs `points_in_ROI_CRS`) and leaves the kept
+        original indices in `self.ROI_point_IDs` and `self.ROI_face_IDs`; a texture array of the ORIGINAL face or vertex
+        count is indexed by them, one of the cropped count is taken as it is.
 
         Extra keyword arguments (defaults keep reference behaviour):
             device: GPU index for the HIP backend (default: current torch device).
@@ -151,11 +155,14 @@ class TexturedPhotogrammetryMesh:
                 (`profiles/r06_gl_residue.txt`).  Needs the pyvista camera's principal point (`principal_point="center"`).
             neg1_is_last_face: reproduce meshes.py:1998-2001, where background pixels (-1) index the LAST face
                 during projection.  True matches the reference's aggregated textures on every face.
+            points_in_ROI_CRS: the mesh vertices (V, 2) or (V, 3) in the ROI's planar CRS, required with `ROI` (the
+                reference reprojects them with pyproj); without it `ROI` raises NotImplementedError.
         """
         if downsample_target != 1.0:
             raise NotImplementedError("mesh decimation is outside the projection path (meshes.py:215-226)")
-        if ROI is not None:
-            raise NotImplementedError("ROI cropping is outside the projection path (meshes.py:646-731)")
+        if ROI is not None and points_in_ROI_CRS is None:
+            raise NotImplementedError("ROI cropping is outside the projection path (meshes.py:646-731) unless the vertices "
+                                      "in the ROI's CRS are given: points_in_ROI_CRS")
         if input_CRS is not None and str(input_CRS).upper().replace(" ", "") not in ("EPSG:4978",):
             raise NotImplementedError(
                 f"input_CRS={input_CRS!r}: only EPSG:4978 meshes are accepted (CRS reprojection needs pyproj and is "
@@ -203,6 +210,13 @@ class TexturedPhotogrammetryMesh:
             raise ValueError(f"vertex_order must be 'r1' or 'gl', got {vertex_order!r}")
         self.vertex_order = vertex_order
 
+        self.ROI_point_IDs = None
+        self.ROI_face_IDs = None
+        self._n_original = (self.points.shape[0], self.faces.shape[0])   # vertices, faces before the crop
+        if ROI is not None:   # before the texture, as the reference does (meshes.py:200-213)
+            (self.points, self.faces), self.ROI_point_IDs, self.ROI_face_IDs = self.select_mesh_ROI(
+                ROI, buffer_meters=ROI_buffer_meters, return_original_IDs=True, points_in_ROI_CRS=points_in_ROI_CRS)
+
         self.logger.info("Loading texture")
         if isinstance(IDs_to_labels, (str, Path)):
             import json
@@ -216,7 +230,67 @@ class TexturedPhotogrammetryMesh:
                                           "its CRS: load_texture(..., points_in_polygon_CRS=...)")
             texture = np.load(texture)
         if texture is not None:
-            self.set_texture(np.asarray(texture))
+            self.set_texture(self.crop_to_ROI(np.asarray(texture)))
+
+    # -- region of interest (DESIGN.md "Region of interest"; reference: meshes.py:646-731) -------------------------
+    def crop_to_ROI(self, values: np.ndarray):
+        """A per-vertex or per-face array of the ORIGINAL mesh -> the rows of the vertices or faces the constructor's `ROI`
+        kept.  An array with a cropped count (or any other) is returned as it is, and so is everything on a mesh without ROI."""
+        if self.ROI_point_IDs is None or values.ndim == 0:
+            return values
+        n_points, n_faces = self._n_original
+        n = values.shape[0]
+        if n in (self.points.shape[0], self.faces.shape[0]):
+            return values
+        if n == n_points == n_faces:
+            raise ValueError("Cannot infer whether the array belongs to vertices or faces because the number is the same")
+        if n == n_points:
+            return values[self.ROI_point_IDs]
+        if n == n_faces:
+            return values[self.ROI_face_IDs]
+        return values
+
+    def select_mesh_ROI(self, region_of_interest, buffer_meters: float = 0, simplify_tol_meters: float = 0, default_CRS=None,
+                        return_original_IDs: bool = False, *, points_in_ROI_CRS=None):
+        """The part of the mesh in a region of interest (reference: meshes.py:646-731; rules Q1-Q6).
+
+        region_of_interest: a `PlanarPolygons`, a sequence its `from_sequence` takes or a `.geojson` path; all rows together
+        are the region.  None returns the mesh unchanged.  buffer_meters: a vertex within this distance of the region is in
+        it too.  simplify_tol_meters: only 0 (polygon simplification is not built: NotImplementedError).  default_CRS:
+        accepted and unused (coordinates are taken as they stand).  points_in_ROI_CRS (required, keyword): the mesh vertices
+        (V, 2) or (V, 3) in the ROI's planar CRS.
+
+        A face is kept iff one of its vertices is in the region (`extract_points(adjacent_cells=True)`), a vertex iff a kept
+        face uses it; both keep their order.  Returns (points, faces) -- faces index the kept points --, or with
+        `return_original_IDs` ((points, faces), point_IDs, face_IDs): the ascending int64 indices into the original mesh.
+        The point query and the compaction run on the device; the call's figures are left in `self.last_ROI_stats`."""
+        from geograypher_amd.utils.geometric import points_in_region
+
+        if region_of_interest is None:
+            return self.points, self.faces
+        if simplify_tol_meters != 0:
+            raise NotImplementedError("simplify_tol_meters: polygon simplification (Douglas-Peucker) is not built")
+        if points_in_ROI_CRS is None:
+            raise NotImplementedError(
+                "select_mesh_ROI needs points_in_ROI_CRS: the mesh vertices in the ROI's planar CRS (CRS reprojection needs "
+                "pyproj and is outside the projection path)")
+        verts = np.asarray(points_in_ROI_CRS, dtype=np.float64)
+        if verts.ndim != 2 or verts.shape[0] != self.points.shape[0] or verts.shape[1] not in (2, 3):
+            raise ValueError(f"points_in_ROI_CRS must be ({self.points.shape[0]}, 2) or ({self.points.shape[0]}, 3), got "
+                             f"{verts.shape}")
+        backend = self.backend
+        mask, stats = points_in_region(backend, region_of_interest, verts, buffer_meters)
+        face_IDs, point_IDs, new_faces, counts = backend.submesh_extract(mask, self.faces.astype(np.int32))
+        face_IDs, point_IDs, new_faces, stats = (np.asarray(_to_host(a) if hasattr(a, "detach") else a)
+                                                 for a in (face_IDs, point_IDs, new_faces, stats))
+        face_IDs = np.array(face_IDs, dtype=np.int64).reshape(-1)
+        point_IDs = np.array(point_IDs, dtype=np.int64).reshape(-1)
+        self.last_ROI_stats = {"points_inside": int(stats[0]), "points_inside_by_buffer_only": int(stats[1]),
+                               "wide_comparisons": int(stats[2]), "faces_kept": len(face_IDs), "points_kept": len(point_IDs)}
+        subset = (self.points[point_IDs], np.array(new_faces, dtype=np.int64).reshape(-1, 3))
+        if return_original_IDs:
+            return subset, point_IDs, face_IDs
+        return subset
 
     # -- backend -------------------------------------------------------------------------------------------------
     @property
@@ -1078,19 +1152,9 @@ class TexturedPhotogrammetryMesh:
     def _snap_with_polygons(verts, polygons):
         """Rule P3 / V2: (snapped vertices (V, 2) int64, the polygons' snapped ring table), both on the 1e-6 m grid behind ONE
         integer origin, the middle of their joint bounds."""
-        from geograypher_amd.utils.geometric import SNAP_LIMIT, snap_to_grid
+        from geograypher_amd.utils.geometric import snap_with_polygons
 
-        vq = snap_to_grid(verts[:, :2])
-        lo, hi = (vq.min(axis=0), vq.max(axis=0)) if len(vq) else (np.zeros(2, np.int64), np.zeros(2, np.int64))
-        ring_bounds = polygons.bounds_snapped()
-        if ring_bounds is not None:
-            lo, hi = np.minimum(lo, ring_bounds[0]), np.maximum(hi, ring_bounds[1])
-        origin = lo + (hi - lo) // 2
-        vq = vq - origin
-        if len(vq) and np.abs(vq).max() > SNAP_LIMIT:
-            raise ValueError("a mesh vertex lies more than 2^40 grid steps (1 099 512 m) from the common origin of mesh and "
-                             "polygons")
-        return vq, polygons.snapped(origin)
+        return snap_with_polygons(verts, polygons)
 
     def label_polygon_weights(self, face_labels, polygons, face_weighting=None, sjoin_overlay: bool = True,
                               return_class_labels: bool = True, unknown_class_label: str = "unknown",

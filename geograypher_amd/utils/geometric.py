@@ -321,6 +321,59 @@ class PlanarPolygons:
         return np.min([v.min(axis=0) for v in q], axis=0), np.max([v.max(axis=0) for v in q], axis=0)
 
 
+# -- region of interest (DESIGN.md "Region of interest") ----------------------------------------------------------------------------
+def snap_with_polygons(verts, polygons):
+    """Rule P3 / V2: (snapped points (N, 2) int64, the polygons' snapped ring table), both on the 1e-6 m grid behind ONE integer
+    origin, the middle of their joint bounds."""
+    vq = snap_to_grid(verts[:, :2])
+    lo, hi = (vq.min(axis=0), vq.max(axis=0)) if len(vq) else (np.zeros(2, np.int64), np.zeros(2, np.int64))
+    ring_bounds = polygons.bounds_snapped()
+    if ring_bounds is not None:
+        lo, hi = np.minimum(lo, ring_bounds[0]), np.maximum(hi, ring_bounds[1])
+    origin = lo + (hi - lo) // 2
+    vq = vq - origin
+    if len(vq) and np.abs(vq).max() > SNAP_LIMIT:
+        raise ValueError("a mesh vertex lies more than 2^40 grid steps (1 099 512 m) from the common origin of mesh and "
+                         "polygons")
+    return vq, polygons.snapped(origin)
+
+
+def region_polygons(ROI) -> "PlanarPolygons":
+    """Rule Q1: a `PlanarPolygons`, a `.geojson` path (`PlanarPolygons.from_geojson`) or anything `PlanarPolygons.from_sequence`
+    takes.  All rows together are the region."""
+    import os
+
+    if isinstance(ROI, PlanarPolygons):
+        return ROI
+    if isinstance(ROI, (str, os.PathLike)):
+        if os.path.splitext(os.fspath(ROI))[1] != ".geojson":
+            raise NotImplementedError(f"ROI file {ROI}: files other than .geojson need geopandas, which is outside the projection "
+                                      "path")
+        return PlanarPolygons.from_geojson(ROI)[0]
+    return PlanarPolygons.from_sequence(ROI)
+
+
+def region_buffer_steps(buffer_meters) -> int:
+    """Rule Q2: the buffer in grid steps, D = rint(buffer_meters / 1e-6), 0 <= D < 2^40 or ValueError."""
+    steps = np.rint(float(buffer_meters) / SNAP_GRID_METERS)
+    if not (0 <= steps < SNAP_LIMIT):
+        raise ValueError(f"buffer of {buffer_meters} m is outside [0, {SNAP_LIMIT * SNAP_GRID_METERS:.0f}) m")
+    return int(steps)
+
+
+def points_in_region(backend, ROI, points, buffer_meters=0):
+    """Rules Q1-Q4 through `backend.points_in_region`: (mask (N,) bool -- a device tensor from a device backend --, stats).  points:
+    (N, 2) or (N, 3) float64 in the ROI's planar CRS; a point is in the region iff it lies in the closed region of some row of the
+    ROI or within `buffer_meters` of one of its rings, decided exactly on the 1e-6 m grid."""
+    polygons = region_polygons(ROI)
+    points = np.asarray(points, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] not in (2, 3):
+        raise ValueError(f"points must be (N, 2) or (N, 3), got {points.shape}")
+    steps = region_buffer_steps(buffer_meters)
+    vq, table = snap_with_polygons(points, polygons)
+    return backend.points_in_region(vq, *table, steps)
+
+
 # -- vector textures: a uniform cell index over the polygon boxes (DESIGN.md "Vector textures") ------------------------------------
 CELL_GRID_MAX_SIDE = 1024      # cells a side of the chosen grid
 CELL_LIST_BUDGET = 8           # list entries per polygon the chosen grid may spend (a floor of 4096 entries)

@@ -497,6 +497,40 @@ int gr_face_polygon_index(gr_ctx *ctx, const int64_t *verts_q, int64_t V, const 
                           const int32_t *cell_polygons, int64_t n_cell_polygons, int32_t *face_polygon, uint64_t *stats,
                           void *stream);
 
+/* Region of interest -- replaces the gpd.overlay of every mesh vertex against the buffered ROI and VTK's extract_points in
+ * select_mesh_ROI (meshes/meshes.py:646-731) and the buffered `within` of get_subset_ROI (cameras/cameras.py:1207-1273); the
+ * rule-set is DESIGN.md "Region of interest" (Q1-Q6).
+ * gr_points_in_region: points_q N x 2 int64 snapped points (units of 1e-6 m behind a common origin, |value| <= 2^40); ring table as
+ * for gr_face_polygon_index (ring_polygon non-decreasing, a ring of fewer than 3 vertices is ignored, a row whose box is empty --
+ * xmin > xmax -- holds nothing); D: the buffer in grid steps, 0 <= D < 2^40.  mask[i] (N uint8, written by the call) is 1 iff point
+ * i lies in the closed region of ANY row (on an edge or vertex of one of its rings, or an odd number of crossings over the row's
+ * rings: overlapping rows unite) or, with D > 0, within D of an edge of any ring, holes included -- decided exactly in integers,
+ * the perpendicular case cross^2 <= D^2 |e|^2 through a 256-bit product.  Edges are visited in table order; a point stops being
+ * tested against the buffer once an edge is within D and against everything once it is contained.
+ * stats: GR_PIR_STAT_WORDS uint64 on the device.  GR_EINVAL (the message names gr_points_in_region): null arrays, negative sizes, D
+ * outside [0, 2^40).  R = 0 or P = 0: an all-zero mask.  Only enqueues work on `stream`; needs no uploaded mesh; 64 bytes of
+ * context scratch.  Added without a GR_VERSION bump. */
+enum {
+  GR_PIR_STAT_INSIDE = 0,       /* points in the region                                                              */
+  GR_PIR_STAT_BUFFER_ONLY = 1,  /* ... that no row contains: within D of an edge only                                */
+  GR_PIR_STAT_WIDE = 2,         /* 256-bit comparisons formed (the point's foot lies strictly inside the edge)       */
+  GR_PIR_STAT_WORDS = 4
+};
+int gr_points_in_region(gr_ctx *ctx, const int64_t *points_q, int64_t N, const int64_t *ring_vertices, int64_t n_ring_vertices,
+                        const int64_t *ring_offsets, const int32_t *ring_polygon, int64_t R, const int64_t *polygon_boxes,
+                        int64_t P, int64_t D, uint8_t *mask, uint64_t *stats, void *stream);
+
+/* gr_submesh_extract: mask V uint8 (non-zero: the vertex is selected); faces F x 3 int32.  A face is kept iff one of its vertices
+ * is selected, a vertex iff a kept face uses it; both keep their order.  face_ids (capacity F int64) and point_ids (capacity V
+ * int64): the ascending original indices of what is kept; new_faces (capacity F x 3 int32): the kept faces, indexing the kept
+ * vertices.  counts: 3 uint64 on the device, written by the call: kept faces, kept vertices, faces with a vertex index outside
+ * [0, V) -- such a face reads nothing and is not kept.  Entries behind the counts are not written.  Two exclusive scans
+ * (hipcub::DeviceScan) between a flag kernel and a write kernel; flags, scans and temporaries live in context scratch.  GR_EINVAL
+ * (the message names gr_submesh_extract): null arrays, negative sizes, V or F >= 2^31.  Only enqueues work on `stream`; needs no
+ * uploaded mesh.  Added without a GR_VERSION bump. */
+int gr_submesh_extract(gr_ctx *ctx, const uint8_t *mask, int64_t V, const int32_t *faces, int64_t F, int64_t *face_ids,
+                       int64_t *point_ids, int32_t *new_faces, uint64_t *counts, void *stream);
+
 /* Raster samples -- replaces the per-point rasterio.sample of get_values_from_raster_file, the subtraction of
  * get_height_above_ground and the masked write of label_ground_class (meshes/meshes.py:1449-1629): the value of a raster under
  * every face centre or vertex; the rule-set is DESIGN.md "Raster samples" (T1-T7).  Every operation is a float64 operation
