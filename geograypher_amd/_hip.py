@@ -82,6 +82,15 @@ GR_PIR_STAT_INSIDE = 0
 GR_PIR_STAT_BUFFER_ONLY = 1
 GR_PIR_STAT_WIDE = 2
 GR_PIR_STAT_WORDS = 4
+# words of class_outlines' statistics block, the most classes it takes
+GR_OUTL_STAT_NO_CLASS = 0
+GR_OUTL_STAT_ZERO_AREA = 1
+GR_OUTL_STAT_TURNED = 2
+GR_OUTL_STAT_CANCELLED = 3
+GR_OUTL_STAT_MULTI = 4
+GR_OUTL_STAT_BAD_FACES = 5
+GR_OUTL_STAT_WORDS = 8
+GR_OUTL_MAX_CLASSES = 65535
 # words of sample_raster's statistics block, its relabel flag
 GR_RS_STAT_INSIDE = 0
 GR_RS_STAT_NODATA = 1
@@ -173,6 +182,7 @@ _SIGNATURES = {
                               _vp, _vp, _i64, _vp, _vp, _vp],
     "gr_points_in_region": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp],
     "gr_submesh_extract": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "gr_class_outlines": [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i64p, _i64p, _vp, _vp],
     "gr_sample_raster": [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _f64, _f64,
                          _i32, _vp, _vp],
 }
@@ -974,6 +984,57 @@ class HipRaster:
         if check and n_bad:
             raise ValueError(f"gr_submesh_extract: {n_bad} faces name a vertex outside [0, {V})")
         return face_ids[:n_faces], point_ids[:n_points], new_faces[:n_faces], counts
+
+    # -- class outlines: the rings around the faces of every class -------------------------------------------------
+    def class_outlines(self, verts_q, faces, face_class, n_classes: int, capacity: Optional[int] = None, check: bool = True):
+        """gr_class_outlines: verts_q (V, 2) int64 snapped vertices, faces (F, 3) int, face_class (F,)
+        int (outside [0, n_classes): the face takes no part) -- numpy or device tensors -> (canon (V,) int32, ring_vertices (E,)
+        int32 canonical vertex ids ring after ring, ring_offsets (R + 1,) int64, ring_class (R,) int32 tensors, stats
+        (GR_OUTL_STAT_WORDS,) int64 tensor).  Count-then-fill as `ray_pair_edges`: the first call offers `capacity` ring vertices
+        (default: F + 64); when the library reports more (`last_outline_calls` == 2) the buffers are allocated at that total and the
+        call repeated.  The library synchronises: the result is complete on return.  `check` (default) raises ValueError when a
+        face names a vertex that does not exist."""
+        torch = _torch()
+        vq_t = self._dev(verts_q, torch.int64)
+        f_t = self._dev(faces, torch.int32)
+        c_t = self._dev(face_class, torch.int32).reshape(-1)
+        if vq_t.ndim != 2 or vq_t.shape[1] != 2 or f_t.ndim != 2 or f_t.shape[1] != 3:
+            raise ValueError(f"vertices must be (V, 2) and faces (F, 3), got {tuple(vq_t.shape)} and {tuple(f_t.shape)}")
+        V, F = int(vq_t.shape[0]), int(f_t.shape[0])
+        if int(c_t.shape[0]) != F:
+            raise ValueError(f"{F} faces need {F} classes, got {int(c_t.shape[0])}")
+        if not 0 <= int(n_classes) <= GR_OUTL_MAX_CLASSES:
+            raise ValueError(f"gr_class_outlines: n_classes={int(n_classes)} outside [0, {GR_OUTL_MAX_CLASSES}]")
+        cap = F + 64 if capacity is None else int(capacity)
+        stats = torch.empty((GR_OUTL_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        n_edges, n_rings = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.last_outline_calls = 0
+        for _attempt in range(2):
+            canon = torch.empty((V,), dtype=torch.int32, device=self.device)
+            ring_vertices = torch.empty((max(cap, 1),), dtype=torch.int32, device=self.device)
+            ring_offsets = torch.empty((cap // 3 + 1,), dtype=torch.int64, device=self.device)
+            ring_class = torch.empty((max(cap // 3, 1),), dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                rc = self.lib.gr_class_outlines(
+                    self._ctx, vq_t.data_ptr(), V, f_t.data_ptr(), F, c_t.data_ptr(), int(n_classes),
+                    canon.data_ptr() if cap else None, ring_vertices.data_ptr() if cap else None,
+                    ring_offsets.data_ptr() if cap else None, ring_class.data_ptr() if cap else None, cap,
+                    ctypes.byref(n_edges), ctypes.byref(n_rings), stats.data_ptr(), self._stream())
+            self.last_outline_calls += 1
+            E, R = int(n_edges.value), int(n_rings.value)
+            if rc == GR_EOVERFLOW or (rc == GR_OK and cap == 0 and (E > 0 or V > 0)):
+                cap = max(E, 1)   # the library counted every ring vertex: the repeat fits exactly
+                continue
+            self._check(rc, "gr_class_outlines")
+            if check:
+                n_bad = int(stats[GR_OUTL_STAT_BAD_FACES].item())
+                if n_bad:
+                    raise ValueError(f"gr_class_outlines: {n_bad} faces name a vertex outside [0, {V})")
+            if cap == 0:
+                ring_offsets.zero_()
+            return canon, ring_vertices[:E], ring_offsets[:R + 1], ring_class[:R], stats
+        self._check(rc, "gr_class_outlines")
+        raise RuntimeError("gr_class_outlines reported two different totals for the same input")
 
     # -- raster samples: the value of a raster under every face centre or vertex -----------------------------------
     def sample_raster(self, points, faces, raster_data, inverse6, nodata, fill, *, want_values: bool = True,

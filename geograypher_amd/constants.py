@@ -1,6 +1,6 @@
 """Defaults that appear in the reference's signatures on the hot path.
 
-Mirrors geograypher/constants.py:18 (CACHE_FOLDER), :27 (NULL_TEXTURE_INT_VALUE), :106-113 (EXAMPLE_INTRINSICS).
+Mirrors geograypher/constants.py:18 (CACHE_FOLDER), :22 / :25 (CLASS_ID_KEY, CLASS_NAMES_KEY), :27 (NULL_TEXTURE_INT_VALUE), :106-113 (EXAMPLE_INTRINSICS).
 Only the constants the image<->mesh projection path touches are restated.
 """
 from pathlib import Path
@@ -13,6 +13,10 @@ CACHE_FOLDER = Path(Path.home(), ".cache", "geograypher")
 
 # geograypher/constants.py:27
 NULL_TEXTURE_INT_VALUE = 0
+
+# geograypher/constants.py:22, :25 -- the columns of export_face_labels_vector
+CLASS_ID_KEY = "class_ID"
+CLASS_NAMES_KEY = "class_names"
 
 # geograypher/constants.py:106-113
 EXAMPLE_INTRINSICS = {

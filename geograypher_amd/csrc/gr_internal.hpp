@@ -14,6 +14,8 @@
 //   polygons.hip     label_polygons: weighted face area per (polygon, class), exact containment or clipped overlay (k_polygon_weights); no mesh needed
 //                    vector textures: the polygon row of every face centre through a cell index (k_face_polygon_index)
 //                    region of interest: points in a buffered union of rows (k_points_in_region), the sub-mesh they select (k_submesh_flags, k_submesh_write + two scans)
+//                    class outlines: canonical vertices (k_outline_canon), face edges (k_outline_face_edges), cancellation (k_outline_cancel), successors
+//                    (k_outline_successor), leader and rank rounds (k_outline_round), ring emit (k_outline_emit_rings) + radix sorts and scans
 //   terrain.hip      raster samples: the value of a raster under every face centre or vertex, height above it, ground relabel (k_sample_raster); no mesh needed
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -251,6 +253,10 @@ struct gr_ctx {
   int64_t bounds_part_have = 0;
   uint32_t *region_tmp = nullptr;      // polygons.hip: the joint box of gr_points_in_region | flags, scans and hipcub's temporaries of gr_submesh_extract
   int64_t region_have = 0;             // ... in 32-bit words
+  uint8_t *outline_a = nullptr;        // polygons.hip, gr_class_outlines: canon ids | the vertex sort, then the edge sort and its runs | hipcub's temporaries
+  int64_t outline_a_have = 0;          // ... in bytes
+  uint8_t *outline_b = nullptr;        // ... the slots, their successors, the two pointer-doubling sets, the ring scan (sized by the surviving edges)
+  int64_t outline_b_have = 0;
   hipStream_t last_stream = nullptr;   // of the last raster call (gr_raster_status reads its outcome there)
   std::vector<hipStream_t> used_streams;  // streams that work touching context scratch was enqueued on since the last quiesce
   // profiling

@@ -2,7 +2,8 @@
 // polygon, summed per (polygon, class) (gr_polygon_class_weights; the rule-set is DESIGN.md "Polygon labels"), and the polygon row
 // every face CENTRE lies in (gr_face_polygon_index; DESIGN.md "Vector textures"), and the region of interest: which points lie in
 // a buffered union of polygon rows (gr_points_in_region) and the sub-mesh of the faces that touch them (gr_submesh_extract), at
-// the end of the file; DESIGN.md "Region of interest".  None needs an uploaded mesh: the caller hands over snapped integer
+// the end of the file; DESIGN.md "Region of interest"; and the outline rings of every class of a per-face labelling
+// (gr_class_outlines; DESIGN.md "Class outlines"), behind them.  None needs an uploaded mesh: the caller hands over snapped integer
 // coordinates.
 //
 // gr_polygon_class_weights:
@@ -517,6 +518,219 @@ __global__ __launch_bounds__(256) void k_submesh_write(const int32_t *__restrict
   }
 }
 
+
+// ---- gr_class_outlines: the outline rings of every class of a per-face labelling ---------------------
+// Integers only.  Vertices are sorted by (x, y, index) (two stable radix passes) and every group of equal (x, y) takes its
+// smallest index (X2); every taking-part face emits three directed edges over those ids, counter-clockwise by the exact sign of its
+// doubled area (X3); the edges are sorted by (class, from, to), a run of equal edges looks its reverse up by binary search and keeps
+// the surplus (X4); the surviving copies, still sorted, are the slots.  Sorting the slots by (class, to) lines the incoming copies of
+// every (class, vertex) up with its outgoing ones, which are consecutive slots: position p of that order is followed by slot p
+// (X5).  Pointer doubling over that permutation finds the smallest slot of every ring and every slot's distance to it (X6).
+enum {   // 64-bit words at the front of the scratch: counts the host reads back
+  GR_OUTL_HEAD_RUNS = 0,    // distinct (class, from, to) among the directed edges
+  GR_OUTL_HEAD_EDGES = 1,   // surviving copies: slots
+  GR_OUTL_HEAD_WORDS = 32   // 256 bytes
+};
+
+__device__ __forceinline__ void outline_count(unsigned long long *stats, int word, bool one, int lane) {   // one atomic per wave
+  const unsigned long long m = __ballot(one);
+  if (lane == 0 && m) atomicAdd(&stats[word], (unsigned long long)__popcll(m));
+}
+
+// key [V] = y of vertex i; idx [V] = i
+__global__ __launch_bounds__(256) void k_outline_vertex_keys(const int64_t *__restrict__ vq, int64_t V, int64_t *__restrict__ key,
+                                                             int32_t *__restrict__ idx) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < V) { key[i] = vq[i * 2 + 1]; idx[i] = (int32_t)i; }
+}
+// key [V] = x of vertex idx[i]: the key of the second pass
+__global__ __launch_bounds__(256) void k_outline_vertex_gather(const int64_t *__restrict__ vq, int64_t V, const int32_t *__restrict__ idx,
+                                                               int64_t *__restrict__ key) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < V) key[i] = vq[(int64_t)idx[i] * 2];
+}
+// idx [V]: the vertices sorted by (x, y, index).  hp [V] = i where a group of equal (x, y) starts, else 0: its running maximum is
+// the position of the group's first member.
+__global__ __launch_bounds__(256) void k_outline_vertex_heads(const int64_t *__restrict__ vq, int64_t V, const int32_t *__restrict__ idx,
+                                                              int32_t *__restrict__ hp) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= V) return;
+  bool head = i == 0;
+  if (!head) {
+    const int64_t a = idx[i - 1], b = idx[i];
+    head = vq[a * 2] != vq[b * 2] || vq[a * 2 + 1] != vq[b * 2 + 1];
+  }
+  hp[i] = head ? (int32_t)i : 0;
+}
+__global__ __launch_bounds__(256) void k_outline_canon(int64_t V, const int32_t *__restrict__ idx, const int32_t *__restrict__ hp_max,
+                                                       int32_t *__restrict__ canon) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < V) canon[idx[i]] = idx[hp_max[i]];   // the group's smallest index: the sort is stable
+}
+
+// X3.  pair [3 F], cl [3 F]: the directed edges of face f at 3 f .. 3 f + 2, from << 31 | to and the class; a face that takes no part
+// writes three edges of the class n_classes, which sort behind every real one.  A face that names a vertex outside [0, V) reads nothing.
+__global__ __launch_bounds__(256) void k_outline_face_edges(const int64_t *__restrict__ vq, int64_t V, const int32_t *__restrict__ faces,
+                                                            int64_t F, const int32_t *__restrict__ face_class, int C,
+                                                            const int32_t *__restrict__ canon, unsigned long long *__restrict__ pair,
+                                                            uint32_t *__restrict__ cl, unsigned long long *__restrict__ stats) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool bad = false, no_class = false, flat = false, turned = false;
+  if (f < F) {
+    const int64_t v0 = faces[f * 3], v1 = faces[f * 3 + 1], v2 = faces[f * 3 + 2];
+    const int cls = face_class[f];
+    int64_t a = 0, b = 0, c = 0;
+    bool live = false;
+    if (v0 < 0 || v0 >= V || v1 < 0 || v1 >= V || v2 < 0 || v2 >= V) {
+      bad = true;   // reported, never dereferenced
+    } else if (cls < 0 || cls >= C) {
+      no_class = true;
+    } else {
+      a = canon[v0]; b = canon[v1]; c = canon[v2];
+      const i128 o = orient(vq[a * 2], vq[a * 2 + 1], vq[b * 2], vq[b * 2 + 1], vq[c * 2], vq[c * 2 + 1]);
+      flat = o == 0;
+      turned = o < 0;
+      if (turned) { const int64_t t = b; b = c; c = t; }
+      live = !flat;
+    }
+    const uint32_t k = live ? (uint32_t)cls : (uint32_t)C;
+    pair[f * 3] = live ? ((unsigned long long)a << 31 | (unsigned long long)b) : 0ull;
+    pair[f * 3 + 1] = live ? ((unsigned long long)b << 31 | (unsigned long long)c) : 0ull;
+    pair[f * 3 + 2] = live ? ((unsigned long long)c << 31 | (unsigned long long)a) : 0ull;
+    cl[f * 3] = k; cl[f * 3 + 1] = k; cl[f * 3 + 2] = k;
+  }
+  outline_count(stats, GR_OUTL_STAT_NO_CLASS, no_class, lane);
+  outline_count(stats, GR_OUTL_STAT_ZERO_AREA, flat, lane);
+  outline_count(stats, GR_OUTL_STAT_TURNED, turned, lane);
+  outline_count(stats, GR_OUTL_STAT_BAD_FACES, bad, lane);
+}
+
+// pair, cl [n] sorted by (class, from, to).  flag [n] = 1 where a run of equal real edges starts.
+__global__ __launch_bounds__(256) void k_outline_run_heads(const unsigned long long *__restrict__ pair, const uint32_t *__restrict__ cl,
+                                                           int64_t n, int C, int32_t *__restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t c = cl[i];
+  flag[i] = (c < (uint32_t)C && (i == 0 || cl[i - 1] != c || pair[i - 1] != pair[i])) ? 1 : 0;
+}
+// ex [n]: the exclusive sum of flag, the run of a head.  ustart [runs + 1]: where each run starts, and the end of the real edges.
+__global__ __launch_bounds__(256) void k_outline_run_starts(const uint32_t *__restrict__ cl, int64_t n, int C,
+                                                            const int32_t *__restrict__ flag, const int32_t *__restrict__ ex,
+                                                            int32_t *__restrict__ ustart, unsigned long long *__restrict__ head) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || cl[i] >= (uint32_t)C) return;
+  if (flag[i]) ustart[ex[i]] = (int32_t)i;
+  if (i == n - 1 || cl[i + 1] >= (uint32_t)C) {   // the last real edge
+    const int32_t runs = ex[i] + flag[i];
+    ustart[runs] = (int32_t)(i + 1);
+    head[GR_OUTL_HEAD_RUNS] = (unsigned long long)runs;
+  }
+}
+// X4.  One run per lane: its n1 copies of (c, a -> b) against the n2 copies of (c, b -> a), found by binary search over the sorted
+// edges; surv [run] = max(n1 - n2, 0) (zeroed by the caller behind the runs).
+__global__ __launch_bounds__(256) void k_outline_cancel(const unsigned long long *__restrict__ pair, const uint32_t *__restrict__ cl,
+                                                        const int32_t *__restrict__ ex, const int32_t *__restrict__ ustart,
+                                                        const unsigned long long *__restrict__ head, int32_t *__restrict__ surv,
+                                                        unsigned long long *__restrict__ stats) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t runs = (int64_t)head[GR_OUTL_HEAD_RUNS];
+  int32_t n_cancel = 0;
+  bool multi = false;
+  if (u < runs) {
+    const int32_t i0 = ustart[u], n1 = ustart[u + 1] - i0, n_real = ustart[runs];
+    const uint32_t c = cl[i0];
+    const unsigned long long p = pair[i0], a = p >> 31, b = p & 0x7FFFFFFFull, rp = b << 31 | a;
+    int32_t lo = 0, hi = n_real;
+    while (lo < hi) {
+      const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
+      const uint32_t cm = cl[mid];
+      if (cm < c || (cm == c && pair[mid] < rp)) lo = mid + 1; else hi = mid;
+    }
+    int32_t n2 = 0;
+    if (lo < n_real && cl[lo] == c && pair[lo] == rp) { const int32_t r = ex[lo]; n2 = ustart[r + 1] - ustart[r]; }   // lo is a head
+    const int32_t n = n1 > n2 ? n1 - n2 : 0;
+    surv[u] = n;
+    if (a < b) n_cancel = n1 < n2 ? n1 : n2;   // once per unordered pair
+    multi = n > 1;
+  }
+  for (int o = 32; o >= 1; o >>= 1) n_cancel += __shfl_xor(n_cancel, o);   // all cancelled pairs together are fewer than 2^31
+  if (lane == 0 && n_cancel > 0) atomicAdd(&stats[GR_OUTL_STAT_CANCELLED], (unsigned long long)n_cancel);
+  outline_count(stats, GR_OUTL_STAT_MULTI, multi, lane);
+}
+// soff [run]: the exclusive sum of surv, the first slot of the run.  Writes the slots: efrom, ecls, and the key (class, to) with the
+// slot as its value for the sort of X5.
+__global__ __launch_bounds__(256) void k_outline_emit_edges(const unsigned long long *__restrict__ pair, const uint32_t *__restrict__ cl,
+                                                            const int32_t *__restrict__ ustart, const int32_t *__restrict__ surv,
+                                                            const int32_t *__restrict__ soff, int64_t runs, int32_t *__restrict__ efrom,
+                                                            int32_t *__restrict__ ecls, unsigned long long *__restrict__ kin,
+                                                            int32_t *__restrict__ vin) {
+  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (u >= runs) return;
+  const int32_t n = surv[u];
+  if (n <= 0) return;
+  const int32_t i0 = ustart[u], base = soff[u];
+  const uint32_t c = cl[i0];
+  const unsigned long long p = pair[i0];
+  for (int32_t k = 0; k < n; ++k) {
+    efrom[base + k] = (int32_t)(p >> 31);
+    ecls[base + k] = (int32_t)c;
+    kin[base + k] = (unsigned long long)c << 31 | (p & 0x7FFFFFFFull);
+    vin[base + k] = base + k;
+  }
+}
+// X5.  vin_s [E]: the slots sorted by (class, to), stably.  Every (class, vertex) has as many incoming as outgoing copies, and the
+// outgoing ones are consecutive slots in the same order of (class, vertex): the slot at position p is followed by slot p.
+__global__ __launch_bounds__(256) void k_outline_successor(const int32_t *__restrict__ vin_s, int64_t E, int32_t *__restrict__ succ,
+                                                           int32_t *__restrict__ mn, int32_t *__restrict__ off) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= E) return;
+  succ[vin_s[p]] = (int32_t)p;
+  mn[p] = (int32_t)p; off[p] = 0;
+}
+// X6, one round of pointer doubling.  Before: nxt [s] is the slot `step` edges ahead of s, mn [s] the smallest slot among those `step`
+// edges from s on, off [s] how far ahead it first occurs.  After (the other buffer): the same for 2 step.
+__global__ __launch_bounds__(256) void k_outline_round(const int32_t *__restrict__ nxt, const int32_t *__restrict__ mn,
+                                                       const int32_t *__restrict__ off, int32_t *__restrict__ nxt2,
+                                                       int32_t *__restrict__ mn2, int32_t *__restrict__ off2, uint32_t step, int64_t E) {
+  const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= E) return;
+  const int32_t n = nxt[s], m1 = mn[s], m2 = mn[n];
+  const bool far = m2 < m1;   // equal: the ring has been walked round, the first occurrence stays
+  mn2[s] = far ? m2 : m1;
+  off2[s] = far ? (int32_t)(step + (uint32_t)off[n]) : off[s];
+  nxt2[s] = nxt[n];
+}
+// w [E + 1]: length << 32 | 1 at the leader of a ring (the slot that is its own minimum), else 0; the length is one more than the
+// distance of the leader's successor to it.
+__global__ __launch_bounds__(256) void k_outline_ring_words(const int32_t *__restrict__ succ, const int32_t *__restrict__ mn,
+                                                            const int32_t *__restrict__ off, int64_t E, unsigned long long *__restrict__ w) {
+  const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s > E) return;
+  w[s] = (s < E && mn[s] == (int32_t)s) ? ((unsigned long long)((uint32_t)off[succ[s]] + 1u) << 32 | 1ull) : 0ull;
+}
+// ws [E + 1]: the exclusive sum of w: at a leader, first ring vertex << 32 | ring.  Writes the caller's buffers.
+__global__ __launch_bounds__(256) void k_outline_emit_rings(const int32_t *__restrict__ mn, const int32_t *__restrict__ off,
+                                                            const int32_t *__restrict__ efrom, const int32_t *__restrict__ ecls,
+                                                            const unsigned long long *__restrict__ w,
+                                                            const unsigned long long *__restrict__ ws, int64_t E,
+                                                            int32_t *__restrict__ ring_vertices, int64_t *__restrict__ ring_offsets,
+                                                            int32_t *__restrict__ ring_class) {
+  const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= E) return;
+  const int32_t l = mn[s];
+  const unsigned long long wl = ws[l];
+  const int64_t start = (int64_t)(wl >> 32), ring = (int64_t)(wl & 0xFFFFFFFFull), len = (int64_t)(w[l] >> 32);
+  const int64_t rank = s == l ? 0 : len - (int64_t)off[s];
+  if (rank >= 0 && rank < len && start + rank < E) ring_vertices[start + rank] = efrom[s];   // (always: a guard against a torn table)
+  if (s == l) { ring_offsets[ring] = start; ring_class[ring] = ecls[s]; }
+  if (s == 0) ring_offsets[(int64_t)(ws[E] & 0xFFFFFFFFull)] = E;
+}
+
+inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+inline int bit_length(int64_t v) { int n = 0; while (v > 0) { ++n; v >>= 1; } return n; }
+
 }  // namespace
 
 extern "C" {
@@ -647,6 +861,183 @@ int gr_submesh_extract(gr_ctx *c, const uint8_t *mask, int64_t V, const int32_t 
                      (const int32_t *)fflag, (const int32_t *)fpos, (const int32_t *)vused, (const int32_t *)vpos, face_ids, point_ids,
                      new_faces, (unsigned long long *)counts);
   GR_HIP(c, hipGetLastError());
+  return GR_OK;
+}
+
+int gr_class_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_t *faces, int64_t F, const int32_t *face_class,
+                      int n_classes, int32_t *canon, int32_t *ring_vertices, int64_t *ring_offsets, int32_t *ring_class,
+                      int64_t ring_vertex_cap, int64_t *n_edges_h, int64_t *n_rings_h, uint64_t *stats, void *stream) {
+  if (!c) return GR_EINVAL;
+  if (V < 0 || F < 0 || ring_vertex_cap < 0 || V > 0x7FFFFFFFll || F > 0x7FFFFFFFll / 3 || ring_vertex_cap > 0x7FFFFFFFll)
+    return fail(c, GR_EINVAL, "gr_class_outlines: bad shape V=%lld F=%lld capacity=%lld (V < 2^31, 3 F < 2^31)", (long long)V,
+                (long long)F, (long long)ring_vertex_cap);
+  if (n_classes < 0 || n_classes > GR_OUTL_MAX_CLASSES)
+    return fail(c, GR_EINVAL, "gr_class_outlines: n_classes=%d outside [0, %d]", n_classes, (int)GR_OUTL_MAX_CLASSES);
+  if (!stats || !n_edges_h || !n_rings_h || (V > 0 && !verts_q) || (F > 0 && (!faces || !face_class)) ||
+      (ring_vertex_cap > 0 && (!ring_vertices || !ring_offsets || !ring_class || (V > 0 && !canon))))
+    return fail(c, GR_EINVAL, "gr_class_outlines: null arrays");
+  *n_edges_h = 0; *n_rings_h = 0;
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
+  GR_HIP(c, hipMemsetAsync(stats, 0, sizeof(uint64_t) * GR_OUTL_STAT_WORDS, s));
+  unsigned long long *st = (unsigned long long *)stats;
+  const int64_t N3 = 3 * F;
+  const int vbits = std::max(bit_length(V - 1), 1), cbits = std::max(bit_length(n_classes), 1);
+
+  // scratch A, sized by V and F: head | canon [V] | the vertex sort or the edge sort and its runs | hipcub's temporaries
+  size_t t_vs = 0, t_vm = 0, t_e1 = 0, t_e2 = 0, t_f = 0, t_s = 0;
+  if (V > 0) {
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, t_vs, (int64_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr,
+                                                 (int32_t *)nullptr, (int)V, 0, 64, s));
+    GR_HIP(c, hipcub::DeviceScan::InclusiveScan(nullptr, t_vm, (int32_t *)nullptr, (int32_t *)nullptr, hipcub::Max(), (int)V, s));
+  }
+  if (F > 0) {
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, t_e1, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                                 (uint32_t *)nullptr, (uint32_t *)nullptr, (int)N3, 0, 31 + vbits, s));
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, t_e2, (uint32_t *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr,
+                                                 (unsigned long long *)nullptr, (int)N3, 0, cbits, s));
+    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, t_f, (int32_t *)nullptr, (int32_t *)nullptr, (int)N3, s));
+    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, t_s, (int32_t *)nullptr, (int32_t *)nullptr, (int)(N3 + 1), s));
+  }
+  const size_t tmp_a = up256(std::max({t_vs, t_vm, t_e1, t_e2, t_f, t_s})) + 256;
+  const size_t o_canon = sizeof(unsigned long long) * GR_OUTL_HEAD_WORDS, o_x = o_canon + up256(4 * (size_t)V);
+  // vertex phase: key [V] i64 | key_s [V] i64 | idx [V] | idx_s [V] | hp [V] | hp_max [V]
+  const size_t v_key = o_x, v_key_s = v_key + up256(8 * (size_t)V), v_idx = v_key_s + up256(8 * (size_t)V);
+  const size_t v_idx_s = v_idx + up256(4 * (size_t)V), v_hp = v_idx_s + up256(4 * (size_t)V), v_hpm = v_hp + up256(4 * (size_t)V);
+  const size_t v_end = v_hpm + up256(4 * (size_t)V);
+  // edge phase: pair [N3] u64 | pair_s [N3] u64 | cl [N3] | cl_s [N3] | flag [N3] | ex [N3] | ustart, surv, soff [N3 + 1]
+  const size_t e_pair = o_x, e_pair_s = e_pair + up256(8 * (size_t)N3), e_cl = e_pair_s + up256(8 * (size_t)N3);
+  const size_t e_cl_s = e_cl + up256(4 * (size_t)N3), e_flag = e_cl_s + up256(4 * (size_t)N3), e_ex = e_flag + up256(4 * (size_t)N3);
+  const size_t e_ustart = e_ex + up256(4 * (size_t)N3), e_surv = e_ustart + up256(4 * (size_t)(N3 + 1));
+  const size_t e_soff = e_surv + up256(4 * (size_t)(N3 + 1)), e_end = e_soff + up256(4 * (size_t)(N3 + 1));
+  const size_t o_tmp_a = std::max(v_end, e_end);
+  int rc = grow(c, c->outline_a, c->outline_a_have, (int64_t)(o_tmp_a + tmp_a), "class-outline");
+  if (rc != GR_OK) return rc;
+  note_stream(c, s);
+  char *A = (char *)c->outline_a;
+  unsigned long long *head = (unsigned long long *)A;
+  int32_t *canon_d = (int32_t *)(A + o_canon);
+  void *tmp = A + o_tmp_a;
+  GR_HIP(c, hipMemsetAsync(head, 0, sizeof(unsigned long long) * GR_OUTL_HEAD_WORDS, s));
+
+  if (V > 0) {   // X2
+    int64_t *key = (int64_t *)(A + v_key), *key_s = (int64_t *)(A + v_key_s);
+    int32_t *idx = (int32_t *)(A + v_idx), *idx_s = (int32_t *)(A + v_idx_s), *hp = (int32_t *)(A + v_hp), *hpm = (int32_t *)(A + v_hpm);
+    const dim3 grid((unsigned)ceil_div(V, 256));
+    hipLaunchKernelGGL(k_outline_vertex_keys, grid, dim3(256), 0, s, verts_q, V, key, idx);
+    size_t tb = t_vs;
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key_s, idx, idx_s, (int)V, 0, 64, s));           // by y
+    hipLaunchKernelGGL(k_outline_vertex_gather, grid, dim3(256), 0, s, verts_q, V, (const int32_t *)idx_s, key);
+    tb = t_vs;
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key_s, idx_s, idx, (int)V, 0, 64, s));           // then by x, stably
+    hipLaunchKernelGGL(k_outline_vertex_heads, grid, dim3(256), 0, s, verts_q, V, (const int32_t *)idx, hp);
+    tb = t_vm;
+    GR_HIP(c, hipcub::DeviceScan::InclusiveScan(tmp, tb, hp, hpm, hipcub::Max(), (int)V, s));
+    hipLaunchKernelGGL(k_outline_canon, grid, dim3(256), 0, s, V, (const int32_t *)idx, (const int32_t *)hpm, canon_d);
+    GR_HIP(c, hipGetLastError());
+  }
+
+  int64_t E = 0, R = 0, runs = 0;
+  unsigned long long *pair = (unsigned long long *)(A + e_pair), *pair_s = (unsigned long long *)(A + e_pair_s);
+  uint32_t *cl = (uint32_t *)(A + e_cl), *cl_s = (uint32_t *)(A + e_cl_s);
+  int32_t *flag = (int32_t *)(A + e_flag), *ex = (int32_t *)(A + e_ex), *ustart = (int32_t *)(A + e_ustart);
+  int32_t *surv = (int32_t *)(A + e_surv), *soff = (int32_t *)(A + e_soff);
+  if (F > 0) {   // X3, X4
+    const dim3 gf((unsigned)ceil_div(F, 256)), ge((unsigned)ceil_div(N3, 256));
+    hipLaunchKernelGGL(k_outline_face_edges, gf, dim3(256), 0, s, verts_q, V, faces, F, face_class, n_classes,
+                       (const int32_t *)canon_d, pair, cl, st);
+    size_t tb = t_e1;
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, tb, pair, pair_s, cl, cl_s, (int)N3, 0, 31 + vbits, s));   // by (from, to)
+    tb = t_e2;
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, tb, cl_s, cl, pair_s, pair, (int)N3, 0, cbits, s));        // then by class, stably
+    hipLaunchKernelGGL(k_outline_run_heads, ge, dim3(256), 0, s, (const unsigned long long *)pair, (const uint32_t *)cl, N3,
+                       n_classes, flag);
+    tb = t_f;
+    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, tb, flag, ex, (int)N3, s));
+    GR_HIP(c, hipMemsetAsync(ustart, 0, sizeof(int32_t) * (size_t)(N3 + 1), s));
+    GR_HIP(c, hipMemsetAsync(surv, 0, sizeof(int32_t) * (size_t)(N3 + 1), s));
+    hipLaunchKernelGGL(k_outline_run_starts, ge, dim3(256), 0, s, (const uint32_t *)cl, N3, n_classes, (const int32_t *)flag,
+                       (const int32_t *)ex, ustart, head);
+    hipLaunchKernelGGL(k_outline_cancel, ge, dim3(256), 0, s, (const unsigned long long *)pair, (const uint32_t *)cl,
+                       (const int32_t *)ex, (const int32_t *)ustart, (const unsigned long long *)head, surv, st);
+    tb = t_s;
+    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, tb, surv, soff, (int)(N3 + 1), s));
+    GR_HIP(c, hipGetLastError());
+    unsigned long long runs_h = 0;
+    int32_t edges_h = 0;
+    GR_HIP(c, hipMemcpyAsync(&runs_h, head + GR_OUTL_HEAD_RUNS, sizeof(runs_h), hipMemcpyDeviceToHost, s));
+    GR_HIP(c, hipMemcpyAsync(&edges_h, soff + N3, sizeof(edges_h), hipMemcpyDeviceToHost, s));   // surv is 0 behind the runs: the total
+    GR_HIP(c, hipStreamSynchronize(s));
+    runs = (int64_t)runs_h; E = (int64_t)edges_h;
+    if (runs < 0 || runs > N3 || E < 0 || E > N3) return fail(c, GR_EHIP, "gr_class_outlines: inconsistent edge counts");
+  }
+  *n_edges_h = E;
+
+  const bool fill = ring_vertex_cap > 0;
+  if (E == 0) {   // no outline: an empty table
+    if (fill) {
+      GR_HIP(c, hipMemsetAsync(ring_offsets, 0, sizeof(int64_t), s));
+      if (V > 0) GR_HIP(c, hipMemcpyAsync(canon, canon_d, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, s));
+    }
+    GR_HIP(c, hipStreamSynchronize(s));   // the scratch is free on return
+    return GR_OK;
+  }
+
+  // scratch B, sized by E: efrom | ecls | succ | two sets of (nxt, mn, off) | kin, kin_s [E + 1] u64 | hipcub's temporaries
+  size_t t_in = 0, t_w = 0;
+  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, t_in, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                               (int32_t *)nullptr, (int32_t *)nullptr, (int)E, 0, 31 + cbits, s));
+  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, t_w, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)(E + 1), s));
+  const size_t tmp_b = up256(std::max(t_in, t_w)) + 256;
+  const size_t e4 = up256(4 * (size_t)E), e8 = up256(8 * (size_t)(E + 1));
+  const size_t b_from = 0, b_cls = b_from + e4, b_succ = b_cls + e4, b_set0 = b_succ + e4, b_set1 = b_set0 + 3 * e4;
+  const size_t b_kin = b_set1 + 3 * e4, b_kin_s = b_kin + e8, b_tmp = b_kin_s + e8;
+  rc = grow(c, c->outline_b, c->outline_b_have, (int64_t)(b_tmp + tmp_b), "class-outline ring");
+  if (rc != GR_OK) return rc;
+  char *B = (char *)c->outline_b;
+  int32_t *efrom = (int32_t *)(B + b_from), *ecls = (int32_t *)(B + b_cls), *succ = (int32_t *)(B + b_succ);
+  int32_t *set[2][3];
+  for (int k = 0; k < 3; ++k) { set[0][k] = (int32_t *)(B + b_set0 + k * e4); set[1][k] = (int32_t *)(B + b_set1 + k * e4); }
+  unsigned long long *kin = (unsigned long long *)(B + b_kin), *kin_s = (unsigned long long *)(B + b_kin_s);
+  int32_t *vin = set[1][0], *vin_s = set[1][1];   // free until the first round writes the second set
+  void *tmp2 = B + b_tmp;
+  const dim3 gE((unsigned)ceil_div(E, 256)), gE1((unsigned)ceil_div(E + 1, 256));
+  hipLaunchKernelGGL(k_outline_emit_edges, dim3((unsigned)ceil_div(runs, 256)), dim3(256), 0, s, (const unsigned long long *)pair,
+                     (const uint32_t *)cl, (const int32_t *)ustart, (const int32_t *)surv, (const int32_t *)soff, runs, efrom, ecls,
+                     kin, vin);
+  size_t tb = t_in;
+  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp2, tb, kin, kin_s, vin, vin_s, (int)E, 0, 31 + cbits, s));   // X5
+  hipLaunchKernelGGL(k_outline_successor, gE, dim3(256), 0, s, (const int32_t *)vin_s, E, succ, set[0][1], set[0][2]);
+  // X6: round r reads the successor table first, then its own doubled pointers
+  int cur = 0;
+  for (int r = 0; ((int64_t)1 << r) < E; ++r) {
+    const int32_t *nxt = r == 0 ? succ : set[cur][0];
+    hipLaunchKernelGGL(k_outline_round, gE, dim3(256), 0, s, nxt, (const int32_t *)set[cur][1], (const int32_t *)set[cur][2],
+                       set[cur ^ 1][0], set[cur ^ 1][1], set[cur ^ 1][2], (uint32_t)1 << r, E);
+    cur ^= 1;
+  }
+  const int32_t *mn = set[cur][1], *off = set[cur][2];
+  unsigned long long *w = kin, *ws = kin_s;
+  hipLaunchKernelGGL(k_outline_ring_words, gE1, dim3(256), 0, s, (const int32_t *)succ, mn, off, E, w);
+  tb = t_w;
+  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp2, tb, w, ws, (int)(E + 1), s));
+  GR_HIP(c, hipGetLastError());
+  unsigned long long total = 0;
+  GR_HIP(c, hipMemcpyAsync(&total, ws + E, sizeof(total), hipMemcpyDeviceToHost, s));
+  GR_HIP(c, hipStreamSynchronize(s));
+  R = (int64_t)(total & 0xFFFFFFFFull);
+  *n_rings_h = R;
+  if ((int64_t)(total >> 32) != E || R < 1 || 3 * R > E)
+    return fail(c, GR_EHIP, "gr_class_outlines: the rings hold %llu of %lld edges in %lld rings", total >> 32, (long long)E, (long long)R);
+  if (!fill) return GR_OK;
+  if (E > ring_vertex_cap)
+    return fail(c, GR_EOVERFLOW, "gr_class_outlines: %lld ring vertices in %lld rings, the buffers hold %lld: call again with that capacity",
+                (long long)E, (long long)R, (long long)ring_vertex_cap);
+  hipLaunchKernelGGL(k_outline_emit_rings, gE, dim3(256), 0, s, mn, off, (const int32_t *)efrom, (const int32_t *)ecls,
+                     (const unsigned long long *)w, (const unsigned long long *)ws, E, ring_vertices, ring_offsets, ring_class);
+  GR_HIP(c, hipGetLastError());
+  if (V > 0) GR_HIP(c, hipMemcpyAsync(canon, canon_d, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, s));
+  GR_HIP(c, hipStreamSynchronize(s));   // the last use of the scratch: free on return, as for gr_ray_pairs
   return GR_OK;
 }
 

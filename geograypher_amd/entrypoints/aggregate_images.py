@@ -7,7 +7,9 @@ and `ROI_camera_points_file` -- to the cameras within `ROI_buffer_radius_meters`
 the same distance (`select_mesh_ROI`, on the device), which needs `ROI_points_file`, the vertices in the ROI's CRS.  The aggregated
 face values (`aggregate_projected_images`) and the class per face (`argmax_nonzero`, NaN where nothing was seen) are written as
 `.npy`; with `DTM_file`, `DTM_points_file` and `height_above_ground_threshold` the faces near the terrain lose their class first
-(`label_ground_class`).  Not carried over: mesh decimation, the top-down vector export and the visualisations."""
+(`label_ground_class`); with `top_down_vector_projection_savefile` and `top_down_points_file` the classes are then written as a
+top-down vector map, one multipolygon per class (`export_face_labels_vector`, traced on the device).  Not carried over: mesh
+decimation and the visualisations."""
 import argparse
 import json
 import math
@@ -45,13 +47,15 @@ def aggregate_images(
     ROI_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
     ROI_camera_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
     DTM_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
+    top_down_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
     camera_set=None,
     backend=None,
 ):
     """Aggregate the labels under `label_folder` onto the mesh (see the module docstring).  The reference's arguments and defaults;
-    `mesh_downsample != 1`, `top_down_vector_projection_savefile`, `vis`, `ROI` without `ROI_points_file` and `DTM_file` without
-    `DTM_points_file` raise NotImplementedError.  Beyond the reference: `ROI_points_file` and `DTM_points_file` (`.npy` paths or
-    arrays: the V ORIGINAL vertices in the ROI's / the DTM's CRS), `ROI_camera_points_file` (the positions of the cameras of the full
+    `mesh_downsample != 1`, `vis`, `ROI` without `ROI_points_file`, `DTM_file` without `DTM_points_file` and
+    `top_down_vector_projection_savefile` without `top_down_points_file` raise NotImplementedError.  Beyond the reference:
+    `ROI_points_file`, `DTM_points_file` and `top_down_points_file` (`.npy` paths or arrays: the V ORIGINAL vertices in the ROI's / the
+    DTM's / the export's planar CRS; with the last, the class per face is written as a `.geojson` map, `export_face_labels_vector`), `ROI_camera_points_file` (the positions of the cameras of the full
     set in the ROI's CRS; without it the camera set is not cut to the ROI, with a log line), and `camera_set` and `backend`, which
     replace the objects built from `cameras_file` and the device.  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
     from geograypher_amd.cameras.segmentor import SegmentorPhotogrammetryCameraSet
@@ -63,7 +67,8 @@ def aggregate_images(
          "the vertices in the DTM's CRS are needed (DTM_points_file); reprojecting them needs pyproj"),
         ("ROI", ROI if ROI_points_file is None else None,
          "the vertices in the ROI's CRS are needed (ROI_points_file); reprojecting them needs pyproj"),
-        ("top_down_vector_projection_savefile", top_down_vector_projection_savefile, "the vector export needs geopandas"),
+        ("top_down_vector_projection_savefile", top_down_vector_projection_savefile if top_down_points_file is None else None,
+         "the vector export needs geopandas"),
     ):
         if value is not None:
             raise NotImplementedError(f"{name}: {why}, which is outside the projection path")
@@ -104,6 +109,9 @@ def aggregate_images(
     if take_every_nth_camera is not None:
         subset(range(0, len(camera_set), take_every_nth_camera))
 
+    if top_down_points_file is not None and top_down_vector_projection_savefile is None:
+        raise ValueError("top_down_points_file is given but top_down_vector_projection_savefile is not: there is no map to write")
+
     MeshClass = (TexturedPhotogrammetryMesh if n_aggregation_clusters is None and n_cameras_per_aggregation_cluster is None
                  else TexturedPhotogrammetryMeshChunked)
     roi_kwargs = {}
@@ -111,6 +119,17 @@ def aggregate_images(
         roi_kwargs = {"ROI": ROI, "ROI_buffer_meters": 0 if ROI_buffer_radius_meters is None else ROI_buffer_radius_meters,
                       "points_in_ROI_CRS": points_array(ROI_points_file)}
     mesh = MeshClass(mesh_file, input_CRS=mesh_CRS, IDs_to_labels=IDs_to_labels, backend=backend, **roi_kwargs)
+
+    if top_down_vector_projection_savefile is not None:   # fail before the aggregation, not behind it
+        if Path(top_down_vector_projection_savefile).suffix != ".geojson":
+            raise NotImplementedError(f"top_down_vector_projection_savefile {top_down_vector_projection_savefile}: files other than "
+                                      ".geojson need geopandas, which is outside the projection path")
+        top_down_points = np.asarray(points_array(top_down_points_file), dtype=np.float64)
+        n_original = top_down_points.shape[0] if mesh.ROI_point_IDs is None else None
+        if top_down_points.ndim != 2 or top_down_points.shape[1] not in (2, 3) or \
+                (n_original is not None and n_original != mesh.points.shape[0]) or \
+                (mesh.ROI_point_IDs is not None and len(mesh.ROI_point_IDs) and top_down_points.shape[0] <= int(np.max(mesh.ROI_point_IDs))):
+            raise ValueError(f"top_down_points_file must hold the (V, 2) or (V, 3) ORIGINAL vertices, got {top_down_points.shape}")
 
     if ROI is not None and ROI_buffer_radius_meters is not None:
         if camera_points is not None:
@@ -151,6 +170,16 @@ def aggregate_images(
     if predicted_face_classes_savefile is not None:
         Path(predicted_face_classes_savefile).parent.mkdir(parents=True, exist_ok=True)
         np.save(predicted_face_classes_savefile, predicted_face_classes)
+
+    if top_down_vector_projection_savefile is not None:   # reference: aggregate_images.py:216-231, behind the ground step
+        points_in_export_CRS = top_down_points
+        if mesh.ROI_point_IDs is not None:
+            points_in_export_CRS = points_in_export_CRS[mesh.ROI_point_IDs]
+        IDs = mesh.get_IDs_to_labels()
+        label_names = None if IDs is None else [IDs.get(i, None) for i in range(max(list(IDs.keys())) + 1)]
+        mesh.export_face_labels_vector(face_labels=np.squeeze(predicted_face_classes, axis=1),
+                                       export_file=top_down_vector_projection_savefile, label_names=label_names,
+                                       points_in_export_CRS=points_in_export_CRS)
     return mesh, aggregated_face_labels, predicted_face_classes
 
 
@@ -183,7 +212,10 @@ def parse_args(argv=None):
     parser.add_argument("--n-aggregation-clusters", type=int, help="Selects the chunked mesh class, as in the reference")
     parser.add_argument("--aggregated-face-values-savefile", type=Path, help="Where the (F, classes) values are saved (.npy)")
     parser.add_argument("--predicted-face-classes-savefile", type=Path, help="Where the (F, 1) classes are saved (.npy)")
-    parser.add_argument("--top-down-vector-projection-savefile", help="Not available here")
+    parser.add_argument("--top-down-vector-projection-savefile",
+                        help="Where the top-down map of the classes is saved (.geojson); needs --top-down-points-file")
+    parser.add_argument("--top-down-points-file", type=Path,
+                        help=".npy with the mesh vertices (V, 2) or (V, 3) in the planar CRS of the map (required with it)")
     parser.add_argument("--vis", action="store_true", help="Not available here")
     args = parser.parse_args(argv)
     args.IDs_to_labels = str(args.IDs_to_labels)

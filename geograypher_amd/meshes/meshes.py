@@ -30,6 +30,8 @@ from geograypher_amd.cameras.cameras import (
 )
 from geograypher_amd.constants import (
     CACHE_FOLDER,
+    CLASS_ID_KEY,
+    CLASS_NAMES_KEY,
     EARTH_CENTERED_EARTH_FIXED_CRS,
     NULL_TEXTURE_INT_VALUE,
     PATH_TYPE,
@@ -1322,6 +1324,174 @@ class TexturedPhotogrammetryMesh:
         if len(column_names) == 1:
             return labeled_faces[column_names[0]], all_values[column_names[0]]
         return labeled_faces, all_values
+
+    # -- class outlines (reference: meshes.py:1308-1445) -------------------------------------------------
+    def _outline_call(self, vq, faces, classes, n_classes, points):
+        """One backend call and what the host adds to it: (ring_offsets, class index per ring, ring_vertex_ids, ring_xy,
+        ring_is_hole, stats words, twice the exact area per ring as Python integers) as host arrays."""
+        from geograypher_amd.utils.geometric import ring_areas2_exact
+
+        _, ring_vertices, ring_offsets, ring_class, stats = self.backend.class_outlines(vq, faces, classes, n_classes)
+        ring_vertices = np.array(_host_array(ring_vertices), dtype=np.int32)
+        ring_offsets = np.array(_host_array(ring_offsets), dtype=np.int64)
+        ring_class = np.array(_host_array(ring_class), dtype=np.int64)
+        areas2 = ring_areas2_exact(vq[ring_vertices], ring_offsets)
+        is_hole = np.array([a < 0 for a in areas2], dtype=bool)
+        return (ring_offsets, ring_class, ring_vertices, points[ring_vertices, :2], is_hole, np.array(_host_array(stats), dtype=np.int64),
+                areas2)
+
+    def face_label_outlines(self, face_labels=None, *, points_in_export_CRS, drop_nan: bool = True, return_tensor: bool = False):
+        """The outline rings of every class of a per-face labelling, traced on the device (rules X1-X7 of DESIGN.md section 8i): a
+        `geograypher_amd.utils.geometric.FaceLabelOutlines`.
+
+        face_labels: (F,) or (F, 1) class ids, float or int, NaN = no label, numpy or a device tensor; None: the mesh's face
+        texture; (F, C) with C > 1: many-hot, one call per column with a value > 0, a face takes part where its value is > 0 and
+        `ring_class` is the column.  points_in_export_CRS (required, keyword): the V vertices (V, 2 | 3) in the planar CRS of the
+        export, metres; z is not used.  drop_nan=False: the faces without a label form one more class, reported with id NaN.
+        A wrong number of labels is a ValueError.  Filled with the non-zero rule, the rings of a class are the union of its faces
+        in plan view on the 1e-6 m grid; where a class overlaps itself in plan view its rings overlap too.  `return_tensor=True`
+        returns the arrays as tensors on the backend's device.  The counters are also left in `self.last_outline_stats`."""
+        from geograypher_amd.utils.geometric import OUTLINE_MAX_CLASSES, FaceLabelOutlines, snap_points
+
+        if face_labels is None:
+            face_labels = self.get_texture(request_vertex_texture=False)
+            if face_labels is None:
+                raise ValueError("face_label_outlines: no face labels given and the mesh has no face texture")
+        n_faces = self.faces.shape[0]
+        if face_labels.shape[0] != n_faces:
+            raise ValueError(f"{face_labels.shape[0]} face labels for a mesh of {n_faces} faces")
+        if points_in_export_CRS is None:
+            raise NotImplementedError(
+                "face_label_outlines needs points_in_export_CRS: the mesh vertices (V, 2 | 3) in the planar CRS of the export (CRS "
+                "reprojection needs pyproj and is outside the projection path)")
+        points = np.asarray(points_in_export_CRS, dtype=np.float64)
+        if points.ndim != 2 or points.shape[0] != self.points.shape[0] or points.shape[1] not in (2, 3):
+            raise ValueError(f"points_in_export_CRS must be ({self.points.shape[0]}, 2) or ({self.points.shape[0]}, 3), got {points.shape}")
+        vq = snap_points(points)   # X1
+        faces = np.ascontiguousarray(self.faces, dtype=np.int32)
+        on_device = hasattr(face_labels, "detach")
+        if face_labels.ndim > 2:
+            raise ValueError(f"face labels must be (F,), (F, 1) or (F, C), got {tuple(face_labels.shape)}")
+        parts = []
+        if face_labels.ndim == 2 and face_labels.shape[1] != 1:   # many-hot
+            for column in range(face_labels.shape[1]):
+                member = face_labels[:, column] > 0
+                if not bool(member.any()):
+                    continue
+                classes = member.to(_torch().int32) - 1 if on_device else member.astype(np.int32) - 1
+                out = self._outline_call(vq, faces, classes, 1, points)
+                parts.append((out, np.full(len(out[1]), float(column))))
+        else:
+            labels = face_labels.reshape(-1)
+            if on_device:
+                torch = _torch()
+                labels = labels.to(torch.float64)
+                nan = torch.isnan(labels)
+                ids = torch.unique(labels[~nan])
+                classes = torch.searchsorted(ids, torch.where(nan, torch.zeros_like(labels), labels)).to(torch.int32)
+                classes = torch.where(nan, torch.full_like(classes, -1 if drop_nan else int(ids.numel())), classes)
+                ids = ids.cpu().numpy()
+                any_nan = bool(nan.any())
+            else:
+                labels = np.asarray(labels, dtype=np.float64)
+                nan = np.isnan(labels)
+                ids = np.unique(labels[~nan])
+                classes = np.searchsorted(ids, np.where(nan, 0.0, labels)).astype(np.int32)
+                classes = np.where(nan, np.int32(-1 if drop_nan else len(ids)), classes).astype(np.int32)
+                any_nan = bool(nan.any())
+            if ids.size and (not np.all(np.isfinite(ids)) or np.any(ids != np.floor(ids)) or ids.min() < 0):
+                raise ValueError("face labels must be whole numbers >= 0 (class ids) or NaN")
+            ids = np.concatenate([ids, [np.nan]]) if (any_nan and not drop_nan) else ids
+            if len(ids) > OUTLINE_MAX_CLASSES:
+                raise ValueError(f"{len(ids)} distinct classes: one call takes at most {OUTLINE_MAX_CLASSES}")
+            out = self._outline_call(vq, faces, classes, len(ids), points)
+            parts.append((out, ids[out[1]] if len(out[1]) else np.zeros(0)))
+        shift, offsets, stats = 0, [np.zeros(1, dtype=np.int64)], np.zeros(8, dtype=np.int64)
+        for out, _ in parts:
+            offsets.append(out[0][1:] + shift)
+            shift += int(out[0][-1])
+            stats = stats + out[5]
+
+        def joined(k, dtype, tail=()):
+            chosen = [out[k] for out, _ in parts]
+            return np.concatenate(chosen).astype(dtype) if chosen else np.zeros((0, *tail), dtype=dtype)
+
+        ring_offsets = np.concatenate(offsets)
+        ring_class = np.concatenate([ids_ for _, ids_ in parts]).astype(np.float64) if parts else np.zeros(0)
+        stats = {"faces_without_class": int(stats[0]), "zero_area_faces": int(stats[1]), "turned_faces": int(stats[2]),
+                 "cancelled_edge_pairs": int(stats[3]), "multi_edges": int(stats[4]), "edges": int(ring_offsets[-1]),
+                 "rings": len(ring_offsets) - 1, "calls": len(parts)}
+        self.last_outline_stats = stats
+        fields = [ring_offsets, ring_class, joined(2, np.int32), joined(3, np.float64, (2,)), joined(4, bool)]
+        snapped = (vq[fields[2]], [a for out, _ in parts for a in out[6]])   # what the nesting of X8 works on
+        if return_tensor:
+            torch = _torch()
+            device = getattr(self.backend, "device", None)
+            fields = [torch.as_tensor(a).to(device) if device is not None else torch.as_tensor(a) for a in fields]
+        return FaceLabelOutlines(*fields, stats, snapped)
+
+    def export_face_labels_vector(self, face_labels=None, export_file: PATH_TYPE = None, export_crs=None, label_names=None,
+                                  ensure_non_overlapping: bool = False, simplify_tol: float = 0.0, drop_nan: bool = True,
+                                  vis: bool = False, *, points_in_export_CRS):
+        """Export the labels per face as one multipolygon per class (reference: meshes.py:1308-1445; rules X1-X8 of DESIGN.md
+        section 8i): `(PlanarPolygons, columns)` in the shape `PlanarPolygons.from_geojson` returns -- one row per present class in
+        ascending order (the NaN class last), every hole behind the exterior it lies in; a hole no exterior of its class holds
+        is a row of its own behind them (`self.last_outline_stats["orphan_holes"]`).  columns: CLASS_ID_KEY (float64, NaN for the
+        NaN class) and, with `label_names`, CLASS_NAMES_KEY (`label_names[int(id)]`, "nan" for NaN).  The coordinates are those
+        of `points_in_export_CRS`, which also names the CRS: `export_crs` must be None or equal what the caller passes the points
+        in.  `export_file` ending in `.geojson` is written as a FeatureCollection of MultiPolygon features (`json`).  Other
+        extensions, ensure_non_overlapping, simplify_tol > 0, vis and a reprojection raise NotImplementedError.  Where a class
+        overlaps itself in plan view (a crown above ground of the same class) its rings overlap: the output is then right under
+        the non-zero fill rule only and is not an OGC-valid polygon."""
+        from geograypher_amd.utils.geometric import PlanarPolygons, nest_outline_rings, write_geojson_multipolygons
+
+        if ensure_non_overlapping:
+            raise NotImplementedError("ensure_non_overlapping: resolving classes that overlap in plan view needs a polygon overlay "
+                                      "(geopandas), which is outside the projection path")
+        if simplify_tol > 0:
+            raise NotImplementedError("simplify_tol: simplification needs shapely, which is outside the projection path")
+        if vis:
+            raise NotImplementedError("vis: plotting needs geopandas and matplotlib, which are outside the projection path")
+        if export_crs is not None:
+            raise NotImplementedError(f"export_crs={export_crs!r}: reprojection needs pyproj, which is outside the projection path; "
+                                      "pass points_in_export_CRS in the CRS of the export and leave export_crs as None")
+        if export_file is not None and Path(export_file).suffix != ".geojson":
+            raise NotImplementedError(f"export_file {export_file}: files other than .geojson need geopandas, which is outside the "
+                                      "projection path")
+        outlines = self.face_label_outlines(face_labels, points_in_export_CRS=points_in_export_CRS, drop_nan=drop_nan)
+        ids = outlines.ring_class
+        order = sorted(set(ids[np.isfinite(ids)].tolist())) + ([np.nan] if np.isnan(ids).any() else [])
+        row_of = {(-1.0 if np.isnan(v) else v): k for k, v in enumerate(order)}
+        class_row = np.array([row_of[-1.0 if np.isnan(v) else v] for v in ids.tolist()], dtype=np.int64)
+        off = outlines.ring_offsets
+        areas2, home = nest_outline_rings(outlines.snapped[0], off, class_row, areas2=outlines.snapped[1])   # X8
+        holes_of = {}
+        for r in np.nonzero(home >= 0)[0]:
+            holes_of.setdefault(int(home[r]), []).append(int(r))
+        rings, rows, holes, row_class = [], [], [], list(order)
+        for r in range(len(ids)):   # every exterior, followed by its holes; an orphan hole: a row of its own behind the class rows
+            is_orphan = areas2[r] < 0 and home[r] < 0
+            if areas2[r] > 0 or is_orphan:
+                row = int(class_row[r])
+                if is_orphan:
+                    row = len(row_class)
+                    row_class.append(order[int(class_row[r])])
+                for k, ring in enumerate([r] + holes_of.get(r, [])):
+                    rings.append(outlines.ring_xy[off[ring]:off[ring + 1]])
+                    rows.append(row)
+                    holes.append(k > 0)
+        n_orphans = len(row_class) - len(order)
+        polygons = PlanarPolygons(rings, rows, holes, n_polygons=len(row_class))
+        class_ids = np.array(row_class, dtype=np.float64)
+        columns = {CLASS_ID_KEY: class_ids}
+        if label_names is not None:
+            names = np.empty(len(row_class), dtype=object)
+            names[:] = [(label_names[int(v)] if np.isfinite(v) else "nan") for v in class_ids.tolist()]
+            columns[CLASS_NAMES_KEY] = names
+        self.last_outline_stats = dict(outlines.stats, orphan_holes=n_orphans, rows=len(row_class))
+        if export_file is not None:
+            write_geojson_multipolygons(export_file, polygons, columns)
+        return polygons, columns
 
     # -- raster samples (DESIGN.md "Raster samples"; reference: meshes.py:1449-1629) ---------------------------------------------
     def add_label(self, label_name, label_ID):

@@ -8,6 +8,7 @@ meshes themselves come from `covering_meshes` (`HipRaster.points_bounds`, `HipRa
 from __future__ import annotations
 
 import typing
+from pathlib import Path
 
 import numpy as np
 
@@ -372,6 +373,199 @@ def points_in_region(backend, ROI, points, buffer_meters=0):
     steps = region_buffer_steps(buffer_meters)
     vq, table = snap_with_polygons(points, polygons)
     return backend.points_in_region(vq, *table, steps)
+
+
+# -- class outlines ---------------------------------------------------------------------------------------------
+OUTLINE_MAX_CLASSES = 65535    # GR_OUTL_MAX_CLASSES: classes of one gr_class_outlines call
+
+
+def snap_points(points):
+    """Rule X1: (V, 2 | 3) float64 metres -> (V, 2) int64 on the 1e-6 m grid behind the integer middle of their bounds; z is not
+    used.  A vertex more than 2^40 steps from that origin is a ValueError."""
+    points = np.asarray(points, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] not in (2, 3):
+        raise ValueError(f"points must be (V, 2) or (V, 3), got {points.shape}")
+    vq = snap_to_grid(points[:, :2])
+    if len(vq):
+        lo, hi = vq.min(axis=0), vq.max(axis=0)
+        vq = vq - (lo + (hi - lo) // 2)
+        if np.abs(vq).max() > SNAP_LIMIT:
+            raise ValueError("a mesh vertex lies more than 2^40 grid steps (1 099 512 m) from the middle of the mesh")
+    return np.ascontiguousarray(vq)
+
+
+class FaceLabelOutlines:
+    """What `TexturedPhotogrammetryMesh.face_label_outlines` returns: R rings over E ring vertices, in the order of rule X6.
+    ring_offsets (R + 1,) int64; ring_class (R,) float64, the label of the ring's faces (NaN: the class of the unlabelled faces, with
+    drop_nan=False; the column for many-hot labels); ring_vertex_ids (E,) int32 ORIGINAL vertex indices, the smallest of every group
+    of vertices that share a snapped (x, y); ring_xy (E, 2) float64, the coordinates of those vertices as they were passed in;
+    ring_is_hole (R,) bool, the exact signed area of the snapped ring is negative; stats: a dict of counters."""
+
+    def __init__(self, ring_offsets, ring_class, ring_vertex_ids, ring_xy, ring_is_hole, stats, snapped=None):
+        self.ring_offsets, self.ring_class, self.ring_vertex_ids = ring_offsets, ring_class, ring_vertex_ids
+        self.ring_xy, self.ring_is_hole, self.stats = ring_xy, ring_is_hole, stats
+        self.snapped = snapped   # (snapped ring vertices (E, 2) int64, twice the exact signed area per ring: Python integers), or None
+
+    def __len__(self):
+        return int(self.ring_offsets.shape[0]) - 1
+
+
+def ring_areas2_exact(ring_q, ring_offsets):
+    """Twice the exact signed area of every ring of an integer ring table: a list of Python integers.  Rings whose shoelace sum
+    fits int64 (relative to their first vertex) are summed by numpy, the others in Python integers."""
+    ring_q = np.asarray(ring_q, dtype=np.int64).reshape(-1, 2)
+    off = np.asarray(ring_offsets, dtype=np.int64)
+    R = len(off) - 1
+    if R <= 0:
+        return []
+    n = np.diff(off)
+    first = np.repeat(ring_q[off[:-1]], n, axis=0)
+    d = ring_q - first                                  # |d| <= 2^41
+    nxt = np.arange(len(ring_q)) + 1
+    nxt[off[1:] - 1] = off[:-1]                         # the closing edge
+    reach = np.maximum.reduceat(np.abs(d).max(axis=1), off[:-1]).astype(np.float64)
+    small = reach * reach * 2.0 * n < 2.0 ** 62
+    with np.errstate(over="ignore"):
+        terms = d[:, 0] * d[nxt, 1] - d[nxt, 0] * d[:, 1]
+    sums = np.add.reduceat(terms, off[:-1])
+    out = [int(v) for v in sums]
+    for r in np.nonzero(~small)[0]:
+        out[r] = _signed_area2_exact(d[off[r]:off[r + 1]])
+    return out
+
+
+class _RingLocator:
+    """The closed region of one integer ring -- on the ring, or a non-zero winding number -- asked point by point.  The edges are
+    bucketed into horizontal slabs (about sqrt(n) of them), so a query reads the edges of one slab only; the arithmetic is int64 numpy
+    where every product fits (|coordinate| < 2^30) and Python integers otherwise."""
+
+    def __init__(self, ring):
+        ring = np.asarray(ring, dtype=np.int64).reshape(-1, 2)
+        a, b = np.roll(ring, 1, axis=0), ring
+        self.ax, self.ay, self.bx, self.by = a[:, 0], a[:, 1], b[:, 0], b[:, 1]
+        self.fits = int(np.abs(ring).max()) < 2 ** 30
+        n = len(ring)
+        self.y0, self.y1 = int(ring[:, 1].min()), int(ring[:, 1].max())
+        n_slabs = min(4096, max(1, int(np.sqrt(n))))
+        self.h = (self.y1 - self.y0) // n_slabs + 1
+        lo = (np.minimum(self.ay, self.by) - self.y0) // self.h
+        hi = (np.maximum(self.ay, self.by) - self.y0) // self.h
+        count = hi - lo + 1
+        edge = np.repeat(np.arange(n), count)
+        slab = np.repeat(lo, count) + (np.arange(int(count.sum())) - np.repeat(np.cumsum(count) - count, count))
+        order = np.argsort(slab, kind="stable")
+        self.edges = edge[order]
+        self.start = np.searchsorted(slab[order], np.arange((self.y1 - self.y0) // self.h + 2))
+
+    def contains(self, px, py):
+        if py < self.y0 or py > self.y1:
+            return False
+        k = (py - self.y0) // self.h
+        e = self.edges[self.start[k]:self.start[k + 1]]
+        ax, ay, bx, by = self.ax[e], self.ay[e], self.bx[e], self.by[e]
+        if not self.fits:
+            ax, ay, bx, by = (v.astype(object) for v in (ax, ay, bx, by))
+            px, py = int(px), int(py)
+        o = (bx - ax) * (py - ay) - (by - ay) * (px - ax)
+        zero, up, down = (o == 0).astype(bool), (o > 0).astype(bool), (o < 0).astype(bool)
+        ax, ay, bx, by = self.ax[e], self.ay[e], self.bx[e], self.by[e]
+        if np.any(zero & (np.minimum(ax, bx) <= px) & (px <= np.maximum(ax, bx)) & (np.minimum(ay, by) <= py) & (py <= np.maximum(ay, by))):
+            return True
+        cross = (ay <= py) != (by <= py)
+        return int(np.sum(cross & (by > ay) & up)) - int(np.sum(cross & (by < ay) & down)) != 0
+
+
+NEST_CELL_SPREAD = 64   # an exterior whose box meets more cells of the candidate grid than this is kept on one list for every hole
+
+
+def nest_outline_rings(ring_q, ring_offsets, ring_class_index, areas2=None):
+    """Rule X8 on the snapped rings: (areas2: twice the exact signed area of every ring, a list of Python integers -- `areas2` when
+    the caller has them already; home (R,) int64).  A ring of positive area is an exterior, one of negative area a hole.  home[r] of
+    a hole is the exterior of its class with the smallest area (equal areas: the earlier ring) whose closed region -- non-zero
+    winding, or on the ring -- holds ALL of the hole's vertices; -1 for a hole without one (an orphan) and for every exterior.
+    The search is not quadratic: per class the exteriors' boxes go into a uniform grid of about as many cells as there are
+    exteriors (those that spread over more than NEST_CELL_SPREAD cells onto one common list), a hole looks up the cell of its first
+    vertex, one vectorised comparison keeps the candidates whose box holds the hole's box, and only those reach the exact test, in
+    order of area, through a `_RingLocator` per exterior (built when first asked)."""
+    ring_q = np.asarray(ring_q, dtype=np.int64).reshape(-1, 2)
+    off = np.asarray(ring_offsets, dtype=np.int64)
+    cls = np.asarray(ring_class_index, dtype=np.int64).reshape(-1)
+    R = len(cls)
+    if areas2 is None:
+        areas2 = ring_areas2_exact(ring_q, off)
+    home = np.full(R, -1, dtype=np.int64)
+    if R == 0:
+        return areas2, home
+    lo = np.minimum.reduceat(ring_q, off[:-1], axis=0)
+    hi = np.maximum.reduceat(ring_q, off[:-1], axis=0)
+    sign = np.array([(a > 0) - (a < 0) for a in areas2], dtype=np.int64)
+    locators = {}
+    for c in np.unique(cls[sign < 0]):
+        ext = np.nonzero((cls == c) & (sign > 0))[0]
+        holes = np.nonzero((cls == c) & (sign < 0))[0]
+        if not len(ext):
+            continue
+        ext = np.array(sorted(ext.tolist(), key=lambda r: (areas2[r], r)), dtype=np.int64)   # rank = position: area, then ring
+        e_lo, e_hi = lo[ext], hi[ext]
+        g_lo, g_hi = e_lo.min(axis=0), e_hi.max(axis=0)
+        side = min(1024, max(1, int(np.sqrt(len(ext)))))
+        cell = (g_hi - g_lo) // side + 1
+        c_lo, c_hi = (e_lo - g_lo) // cell, (e_hi - g_lo) // cell
+        spread = (c_hi - c_lo + 1).prod(axis=1)
+        wide = np.nonzero(spread > NEST_CELL_SPREAD)[0]                                      # ranks, ascending
+        small = np.nonzero(spread <= NEST_CELL_SPREAD)[0]
+        nx = (c_hi[small, 0] - c_lo[small, 0] + 1)
+        n = spread[small]
+        k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+        cx = np.repeat(c_lo[small, 0], n) + k % np.repeat(nx, n)
+        cy = np.repeat(c_lo[small, 1], n) + k // np.repeat(nx, n)
+        flat = cy * side + cx
+        order = np.argsort(flat, kind="stable")                                              # ranks stay ascending within a cell
+        listed = np.repeat(small, n)[order]
+        start = np.searchsorted(flat[order], np.arange(side * side + 1))
+        for r in holes.tolist():
+            first = ring_q[off[r]]
+            if np.any(first < g_lo) or np.any(first > g_hi):
+                continue
+            at = (first - g_lo) // cell
+            f = int(at[1] * side + at[0])
+            cand = np.concatenate([listed[start[f]:start[f + 1]], wide])
+            cand = cand[np.all(e_lo[cand] <= lo[r], axis=1) & np.all(e_hi[cand] >= hi[r], axis=1)]
+            points = ring_q[off[r]:off[r + 1]].tolist()
+            for rank in np.sort(cand).tolist():
+                e = int(ext[rank])
+                if e not in locators:
+                    locators[e] = _RingLocator(ring_q[off[e]:off[e + 1]])
+                if all(locators[e].contains(px, py) for px, py in points):
+                    home[r] = e
+                    break
+    return areas2, home
+
+
+def write_geojson_multipolygons(path, polygons: "PlanarPolygons", properties: dict):
+    """A FeatureCollection with one MultiPolygon feature per row of `polygons`, written with `json`: every exterior ring of the row
+    starts a part, the holes follow the exterior they were stored behind; rings are closed; the coordinates are those stored.  A
+    row without rings has a MultiPolygon without parts.  `PlanarPolygons.from_geojson` reads the file back."""
+    import json
+
+    rows = [[] for _ in range(polygons.n_polygons)]
+    for ring, row, hole in zip(polygons.rings, polygons.ring_polygon, polygons.ring_is_hole):
+        closed = [[float(x), float(y)] for x, y in ring] + [[float(ring[0][0]), float(ring[0][1])]]
+        if hole and rows[row]:
+            rows[row][-1].append(closed)
+        else:
+            rows[row].append([closed])
+
+    def plain(v):
+        if isinstance(v, (np.floating, float)):
+            return None if np.isnan(v) else float(v)
+        return int(v) if isinstance(v, np.integer) else v
+
+    features = [{"type": "Feature", "properties": {k: plain(v[row]) for k, v in properties.items()},
+                 "geometry": {"type": "MultiPolygon", "coordinates": parts}} for row, parts in enumerate(rows)]
+    Path(path).parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w") as file:
+        json.dump({"type": "FeatureCollection", "features": features}, file)
 
 
 # -- vector textures: a uniform cell index over the polygon boxes (DESIGN.md "Vector textures") ------------------------------------

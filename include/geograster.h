@@ -531,6 +531,41 @@ int gr_points_in_region(gr_ctx *ctx, const int64_t *points_q, int64_t N, const i
 int gr_submesh_extract(gr_ctx *ctx, const uint8_t *mask, int64_t V, const int32_t *faces, int64_t F, int64_t *face_ids,
                        int64_t *point_ids, int32_t *new_faces, uint64_t *counts, void *stream);
 
+/* Class outlines -- replaces the per-class unary_union of one shapely triangle per face in export_face_labels_vector
+ * (meshes/meshes.py:1308-1445): the outline rings of every class of a per-face labelling, traced on the device; the rule-set is
+ * DESIGN.md section 8i (X1-X8).  Integers only: the result is exact and does not depend on scheduling.
+ * verts_q: V x 2 int64 snapped vertices (units of 1e-6 m behind a common origin, |value| <= 2^40); faces: F x 3 int32; face_class: F
+ * int32; 0 <= n_classes <= GR_OUTL_MAX_CLASSES; V < 2^31 and 3 F < 2^31.  Vertices with equal (x, y) are one vertex, named by the
+ * smallest of their indices (canon: V int32).  A face takes part iff 0 <= class < n_classes and its snapped triangle (over the canon
+ * ids) has a non-zero area; a clockwise one is turned over.  Per class the directed edges a -> b and b -> a cancel in pairs; what is
+ * left, sorted by (class, from, to), are the SLOTS; at every (class, vertex) the k-th incoming slot (by from) is followed by the
+ * k-th outgoing one (by to), which closes the slots into rings.  A ring starts at its smallest slot, rings are ordered by that slot.
+ * Outputs on the device: ring_vertices (capacity ring_vertex_cap int32: the `from` ids of the slots, ring after ring), ring_offsets
+ * (capacity ring_vertex_cap / 3 + 1 int64; rings + 1 are written, the last is the number of ring vertices), ring_class (capacity
+ * max(ring_vertex_cap / 3, 1) int32) -- a ring has at least 3 vertices.  *n_edges_h, *n_rings_h (HOST): the number of slots (= ring
+ * vertices) and of rings, whether or not they fit.  More slots than ring_vertex_cap: GR_EOVERFLOW and NOTHING is written to the
+ * four output arrays; call again with ring_vertex_cap >= *n_edges_h.  ring_vertex_cap == 0 (the four may be NULL): the counts
+ * alone.  stats: GR_OUTL_STAT_WORDS uint64 on the device, always written.  A face with a vertex index outside [0, V) reads
+ * nothing, takes no part and is counted in GR_OUTL_STAT_BAD_FACES only.  GR_EINVAL (the message names the call): null arrays,
+ * negative sizes, V >= 2^31, 3 F >= 2^31, n_classes out of range.  Radix sorts and scans (hipcub) in context scratch (about 40 bytes
+ * per vertex or 48 per face corner, 60 per slot); synchronises `stream` to read the counts and behind its last kernel, so the scratch
+ * is free on return.  Added without a GR_VERSION bump. */
+enum {
+  GR_OUTL_STAT_NO_CLASS = 0,    /* faces whose class lies outside [0, n_classes)                                      */
+  GR_OUTL_STAT_ZERO_AREA = 1,   /* faces with a class whose snapped triangle has no area                              */
+  GR_OUTL_STAT_TURNED = 2,      /* clockwise faces that were turned over                                              */
+  GR_OUTL_STAT_CANCELLED = 3,   /* pairs of opposite directed edges of one class that cancelled                       */
+  GR_OUTL_STAT_MULTI = 4,       /* distinct (class, from, to) that survive in more than one copy                      */
+  GR_OUTL_STAT_BAD_FACES = 5,   /* faces with a vertex index outside [0, V)                                           */
+  GR_OUTL_STAT_WORDS = 8
+};
+enum {
+  GR_OUTL_MAX_CLASSES = 65535
+};
+int gr_class_outlines(gr_ctx *ctx, const int64_t *verts_q, int64_t V, const int32_t *faces, int64_t F, const int32_t *face_class,
+                      int n_classes, int32_t *canon, int32_t *ring_vertices, int64_t *ring_offsets, int32_t *ring_class,
+                      int64_t ring_vertex_cap, int64_t *n_edges_h, int64_t *n_rings_h, uint64_t *stats, void *stream);
+
 /* Raster samples -- replaces the per-point rasterio.sample of get_values_from_raster_file, the subtraction of
  * get_height_above_ground and the masked write of label_ground_class (meshes/meshes.py:1449-1629): the value of a raster under
  * every face centre or vertex; the rule-set is DESIGN.md "Raster samples" (T1-T7).  Every operation is a float64 operation
