@@ -98,6 +98,19 @@ GR_RS_STAT_GROUND = 2
 GR_RS_STAT_BAD_FACES = 3
 GR_RS_STAT_WORDS = 4
 GR_RS_FLAG_ONLY_EXISTING = 1
+# gr_set_cover: flags, limits, stats words
+GR_SETCOVER_PRUNE = 1
+GR_SETCOVER_GLOBAL_ATOMICS = 2
+GR_SETCOVER_MAX_VIEWS = 65536
+GR_SETCOVER_LDS_VIEWS = 4096
+GR_SETCOVER_BATCH = 64
+GR_SETCOVER_STAT_REQUIRED = 0
+GR_SETCOVER_STAT_COVERED = 1
+GR_SETCOVER_STAT_SELECTED = 2
+GR_SETCOVER_STAT_PRUNED = 3
+GR_SETCOVER_STAT_BATCHES = 4
+GR_SETCOVER_STAT_LDS_HISTOGRAM = 5
+GR_SETCOVER_STAT_WORDS = 8
 
 
 class StageTimes(ctypes.Structure):
@@ -185,6 +198,7 @@ _SIGNATURES = {
     "gr_class_outlines": [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i64p, _i64p, _vp, _vp],
     "gr_sample_raster": [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _f64, _f64,
                          _i32, _vp, _vp],
+    "gr_set_cover": [_vp, _vp, _vp, _i64, _i64, ctypes.c_int32, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -852,6 +866,49 @@ class HipRaster:
         self._call("gr_cover_grid", p_t.data_ptr(), int(p_t.shape[0]), int(stride), N, *(t.data_ptr() for t in tabs),
                    z_max.data_ptr(), z_min.data_ptr(), count.data_ptr(), self._stream())
         return z_max, z_min, count
+
+    # -- image selection: greedy set cover over a face x view incidence --------------------------------------------
+    SET_COVER_MAX_VIEWS = GR_SETCOVER_MAX_VIEWS   # n_views limit of gr_set_cover
+    SET_COVER_LDS_VIEWS = GR_SETCOVER_LDS_VIEWS   # ... up to which the gain updates go through LDS histograms (csrc/select.hip)
+    SET_COVER_BATCH = GR_SETCOVER_BATCH           # pick / apply pairs between two reads of the control words
+
+    def set_cover(self, face_ptr, face_views, n_faces: int, n_views: int, min_observations=1, prune: bool = True, *,
+                  return_tensor: bool = False, global_atomics: bool = False):
+        """gr_set_cover: the face-major CSR of a face x view incidence -- face_ptr (n_faces + 1,)
+        int64, face_views (nnz,) int32, unique within a row; numpy or device tensors -- -> the record {"selected" (n_views,)
+        bool, "order" (k,) int32, "gains" (k,) int64, "pruned" (p,) int32, "n_required", "n_covered", "batches",
+        "lds_histogram"} as numpy arrays and ints, or with `return_tensor` the arrays as device tensors.  A face is required iff
+        at least max(min_observations, 1) views see it; the greedy choice takes the view that sees most uncovered required faces,
+        ties to the lowest index; `prune` then drops selected views that later picks made redundant, last selected first.
+        `global_atomics` switches the LDS histograms off (same results).  A view index outside [0, n_views) is a ValueError.
+        The call waits for the device: the result is complete on return."""
+        torch = _torch()
+        n_faces, n_views = int(n_faces), int(n_views)
+        ptr_t = self._dev(face_ptr, torch.int64).reshape(-1)
+        views_t = self._dev(face_views, torch.int32).reshape(-1)
+        if n_faces < 0 or n_views < 0 or int(ptr_t.shape[0]) != n_faces + 1:
+            raise ValueError(f"face_ptr must hold n_faces + 1 = {n_faces + 1} offsets, got {int(ptr_t.shape[0])}")
+        nnz = int(views_t.shape[0])
+        selected = torch.empty((max(n_views, 1),), dtype=torch.uint8, device=self.device)
+        order = torch.empty((max(n_views, 1),), dtype=torch.int32, device=self.device)
+        gains = torch.empty((max(n_views, 1),), dtype=torch.int64, device=self.device)
+        pruned = torch.empty((max(n_views, 1),), dtype=torch.int32, device=self.device)
+        stats = torch.empty((GR_SETCOVER_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        flags = (GR_SETCOVER_PRUNE if prune else 0) | (GR_SETCOVER_GLOBAL_ATOMICS if global_atomics else 0)
+        try:
+            self._call("gr_set_cover", ptr_t.data_ptr(), views_t.data_ptr() if nnz else None, nnz, n_faces, n_views,
+                       float(min_observations), flags, selected.data_ptr(), order.data_ptr(), gains.data_ptr(), pruned.data_ptr(),
+                       stats.data_ptr(), self._stream())
+        except IndexError as err:   # GR_EINDEX: the input is wrong, not a position the caller asked for
+            raise ValueError(str(err)) from None
+        st = [int(x) for x in stats.cpu().tolist()]
+        k, p = st[GR_SETCOVER_STAT_SELECTED], st[GR_SETCOVER_STAT_PRUNED]
+        record = {"selected": selected[:n_views].to(torch.bool), "order": order[:k], "gains": gains[:k], "pruned": pruned[:p]}
+        if not return_tensor:
+            record = {name: t.cpu().numpy() for name, t in record.items()}
+        record.update(n_required=st[GR_SETCOVER_STAT_REQUIRED], n_covered=st[GR_SETCOVER_STAT_COVERED],
+                      batches=st[GR_SETCOVER_STAT_BATCHES], lds_histogram=bool(st[GR_SETCOVER_STAT_LDS_HISTOGRAM]))
+        return record
 
     # -- label_polygons: weighted face area per (polygon, class) ---------------------------------------------------
     def polygon_class_weights(self, tri, face_class, face_weight, ring_vertices, ring_offsets, ring_polygon, ring_is_hole,

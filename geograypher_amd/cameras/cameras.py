@@ -497,6 +497,28 @@ class PhotogrammetryCameraSet:
         """reference: cameras.py:911-926"""
         return self._local_to_epsg_4978_transform
 
+    def save_images(self, output_folder: PATH_TYPE, copy: bool = False, remove_folder: bool = True):
+        """Link (default) or copy the set's images into `output_folder`, keeping their paths relative to the image folder
+        (reference: cameras.py:928-949).  An existing `output_folder` is removed first when `remove_folder`; with `copy` a source
+        that does not exist is logged and skipped."""
+        import logging
+        import shutil
+
+        if remove_folder and os.path.isdir(output_folder):
+            logging.info(f"about to remove {output_folder}")
+            shutil.rmtree(output_folder)
+        for i in range(len(self.cameras)):
+            output_file = Path(output_folder, self.get_image_filename(i, absolute=False))
+            output_file.parent.mkdir(parents=True, exist_ok=True)
+            src_file = self.get_image_filename(i, absolute=True)
+            if copy:
+                try:
+                    shutil.copy(src_file, output_file)
+                except FileNotFoundError:
+                    logging.warning(f"Could not find {src_file}")
+            else:
+                os.symlink(src_file, output_file)
+
     def get_raster_records(
         self, image_scale: float = 1.0, near: Union[float, List[float]] = 1e-3, principal_point: str = "center",
         origin=None, focal_scaling: str = "scaled",

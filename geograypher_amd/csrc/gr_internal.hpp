@@ -17,6 +17,8 @@
 //                    class outlines: canonical vertices (k_outline_canon), face edges (k_outline_face_edges), cancellation (k_outline_cancel), successors
 //                    (k_outline_successor), leader and rank rounds (k_outline_round), ring emit (k_outline_emit_rings) + radix sorts and scans
 //   terrain.hip      raster samples: the value of a raster under every face centre or vertex, height above it, ground relabel (k_sample_raster); no mesh needed
+//   select.hip       image selection: greedy set cover over a face x view incidence (k_sc_rows, k_sc_scan, k_sc_scatter, k_sc_pick, k_sc_apply,
+//                    k_sc_prune_test, k_sc_prune_apply); no mesh needed
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -257,6 +259,8 @@ struct gr_ctx {
   int64_t outline_a_have = 0;          // ... in bytes
   uint8_t *outline_b = nullptr;        // ... the slots, their successors, the two pointer-doubling sets, the ring scan (sized by the surviving edges)
   int64_t outline_b_have = 0;
+  uint8_t *select_tmp = nullptr;       // select.hip, gr_set_cover: control words | gains, counts, pointers per view | m, flags per face | the view-major lists
+  int64_t select_have = 0;             // ... in bytes
   hipStream_t last_stream = nullptr;   // of the last raster call (gr_raster_status reads its outcome there)
   std::vector<hipStream_t> used_streams;  // streams that work touching context scratch was enqueued on since the last quiesce
   // profiling

@@ -5,6 +5,9 @@ The quadratic part -- the clamped segment-to-segment distance of every pair of r
 optional transform, the 1 / d weight, the reference's edge order, and the Louvain communities (networkx).  There is no CPU
 fallback for the distance stage: `backend` is a `HipRaster` (default: the shared one of the current device) or any object with
 the same `ray_pair_edges(starts, ends, ray_ids, threshold)` method.
+
+`select_covering_views` is the set-cover stage of the annotation_image_selection workflow: a face x view visibility matrix ->
+a small set of views that together see every required face, chosen on the device (`HipRaster.set_cover`, gr_set_cover).
 """
 from __future__ import annotations
 
@@ -193,3 +196,43 @@ def calc_communities(starts, ends, edge_weights, louvain_resolution: float = 1.0
         np.savez(path, **result)
         return path
     return result
+
+
+SET_COVER_MAX_VIEWS = 65536      # GR_SETCOVER_MAX_VIEWS of include/geograster.h
+SET_COVER_MAX_FACES = 2**31 - 1  # F < 2^31
+
+
+def select_covering_views(visibility, min_observations_to_be_included=1, prune: bool = True, backend=None) -> dict:
+    """A small set of views that together see every required face -- the set-cover stage of annotation_image_selection
+    (reference: entrypoints/annotation_image_selection.py:142-174, there SetCoverPy on a dense matrix; the rule-set here is
+    DESIGN.md section 8j, M1-M8, solved on the device by gr_set_cover).
+
+    `visibility`: (F, N) scipy sparse matrix or array of any format, or a dense 2-D array; a non-zero entry means "view v sees
+    face f".  It is brought to canonical CSR (duplicates summed, explicit zeros dropped, sorted indices, int64 pointers, int32
+    indices), uploaded and handed to `backend.set_cover` (default: the shared `HipRaster` of the current device).  A face is
+    required iff at least max(min_observations_to_be_included, 1) views see it -- a face that no view sees is never required,
+    where the reference's solver would be infeasible.  Returns the record of `HipRaster.set_cover`: "selected" (N,) bool is the
+    mask the workflow saves.  ValueError: `visibility` is not 2-D, or F or N exceed SET_COVER_MAX_FACES / SET_COVER_MAX_VIEWS."""
+    from scipy import sparse
+
+    is_sparse = sparse.issparse(visibility)
+    if not is_sparse:
+        visibility = np.asarray(visibility)
+    if visibility.ndim != 2:
+        raise ValueError(f"visibility must be (faces, views), got shape {tuple(visibility.shape)}")
+    n_faces, n_views = (int(x) for x in visibility.shape)
+    if n_faces > SET_COVER_MAX_FACES or n_views > SET_COVER_MAX_VIEWS:   # before a CSR of that many rows is built
+        raise ValueError(f"visibility of shape {(n_faces, n_views)} exceeds the limits of the selection: {SET_COVER_MAX_FACES} "
+                         f"faces, {SET_COVER_MAX_VIEWS} views")
+    csr = sparse.csr_matrix(visibility, copy=True) if is_sparse else sparse.csr_matrix(visibility != 0)   # (a CSR input shares its arrays otherwise)
+    if np.isnan(float(min_observations_to_be_included)):
+        raise ValueError("min_observations_to_be_included is not a number")
+    csr.sum_duplicates()
+    csr.eliminate_zeros()
+    csr.sort_indices()
+    if backend is None:
+        from geograypher_amd._hip import default_backend
+
+        backend = default_backend()
+    return backend.set_cover(csr.indptr.astype(np.int64), csr.indices.astype(np.int32), n_faces, n_views,
+                             min_observations=float(min_observations_to_be_included), prune=prune)

@@ -600,6 +600,45 @@ int gr_sample_raster(gr_ctx *ctx, const double *points, int64_t V, const int32_t
                      double *values, double *height, double *labels_inout, double threshold, double ground_id, int flags,
                      uint64_t *stats, void *stream);
 
+/* Image selection -- replaces the SetCoverPy stage of entrypoints/annotation_image_selection.py:142-174: a small set of views that
+ * together see every required face of a face x view incidence; the rule-set is DESIGN.md section 8j (M1-M8).  Integers only: the
+ * result is exact and does not depend on scheduling.
+ * The incidence is face-major CSR, all on the device: face_ptr F + 1 int64 (rising, face_ptr[0] = 0, face_ptr[F] = nnz), face_views
+ * nnz int32, unique within a row; an entry means "the view sees the face", values play no part.  A face is required iff its row has
+ * at least max(min_observations, 1) entries.  Greedy: while a view sees a required face that no selected view sees, the view that
+ * sees most of them is selected, ties to the LOWEST view index.  With GR_SETCOVER_PRUNE in `flags` the selected views are then
+ * examined last selected first, and one whose required faces are all seen by another selected view is deselected at once.
+ * Outputs on the device, written by the call: selected n_views uint8 (the mask); order n_views int32 (the views in the order
+ * selected, -1 behind them); gains n_views int64 (the faces each added, 0 behind them); pruned n_views int32 (the deselected views
+ * in the order examined, -1 behind them); stats GR_SETCOVER_STAT_WORDS int64.  GR_SETCOVER_GLOBAL_ATOMICS in `flags` makes the
+ * gain updates plain global atomics at every n_views (above GR_SETCOVER_LDS_VIEWS they always are; for measurements and tests: the
+ * results are the same).  GR_EINDEX: a view index outside [0, n_views) or a row pointer outside [0, nnz], found on the device; the
+ * outputs are then undefined.  GR_EINVAL (the message names gr_set_cover): null arrays, negative sizes, F >= 2^31, n_views >
+ * GR_SETCOVER_MAX_VIEWS, a NaN threshold.  F = 0 or n_views = 0: an empty selection.  Pick / apply launches are enqueued
+ * GR_SETCOVER_BATCH pairs at a time and `stream` is synchronised once per batch and behind the last kernel, so the context scratch
+ * (about 9 bytes per face, 4 per entry, 28 per view) is free on return.  Needs no uploaded mesh.  Added without a GR_VERSION bump. */
+enum {
+  GR_SETCOVER_PRUNE = 1,           /* M6: drop selected views that the later picks made redundant                         */
+  GR_SETCOVER_GLOBAL_ATOMICS = 2   /* no LDS histograms                                                                  */
+};
+enum {
+  GR_SETCOVER_MAX_VIEWS = 65536,   /* n_views limit                                                                      */
+  GR_SETCOVER_LDS_VIEWS = 4096,    /* n_views up to which a workgroup collects gain updates in an LDS histogram          */
+  GR_SETCOVER_BATCH = 64           /* pick / apply pairs enqueued between two reads of the control words                 */
+};
+enum {
+  GR_SETCOVER_STAT_REQUIRED = 0,       /* required faces                                                                 */
+  GR_SETCOVER_STAT_COVERED = 1,        /* ... that a selected view sees: counted from the flags, equal to the above      */
+  GR_SETCOVER_STAT_SELECTED = 2,       /* k: views the greedy stage selected                                             */
+  GR_SETCOVER_STAT_PRUNED = 3,         /* p: views the prune stage deselected                                            */
+  GR_SETCOVER_STAT_BATCHES = 4,        /* batches the greedy stage took                                                  */
+  GR_SETCOVER_STAT_LDS_HISTOGRAM = 5,  /* 1: gain updates went through LDS histograms                                    */
+  GR_SETCOVER_STAT_WORDS = 8
+};
+int gr_set_cover(gr_ctx *ctx, const int64_t *face_ptr, const int32_t *face_views, int64_t nnz, int64_t F, int32_t n_views,
+                 double min_observations, int flags, uint8_t *selected, int32_t *order, int64_t *gains, int32_t *pruned,
+                 int64_t *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
