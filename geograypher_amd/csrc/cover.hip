@@ -233,10 +233,12 @@ int gr_points_bounds(gr_ctx *c, const double *points, int64_t V, int64_t stride,
   GR_HIP(c, hipSetDevice(c->device));
   const int64_t n = ceil_div(V, stride);
   const int grid = (int)std::min<int64_t>(ceil_div(n, GR_BOUNDS_BLOCK * GR_BOUNDS_ROWS_PER_LANE), GR_BOUNDS_MAX_GRID);
-  int rc = grow(c, c->bounds_part, c->bounds_part_have, (int64_t)GR_BOUNDS_MAX_GRID * 8, "point-bounds");
+  // scratch: part [GR_BOUNDS_MAX_GRID]
+  Carve cv;
+  const size_t o_part = cv.array<BoundsPart>(GR_BOUNDS_MAX_GRID);
+  int rc = stage_acquire(c, c->stage, cv.total(), s, "point-bounds");
   if (rc != GR_OK) return rc;
-  note_stream(c, s);
-  BoundsPart *part = (BoundsPart *)c->bounds_part;
+  BoundsPart *part = Carve::at<BoundsPart>(c->stage.ptr, o_part);
   hipLaunchKernelGGL(k_points_bounds, dim3((unsigned)grid), dim3(GR_BOUNDS_BLOCK), 0, s, points, n, stride, part);
   hipLaunchKernelGGL(k_points_bounds_combine, dim3(1), dim3(64), 0, s, (const BoundsPart *)part, grid, bounds6,
                      (u64 *)nonfinite);

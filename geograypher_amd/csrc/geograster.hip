@@ -376,7 +376,7 @@ int gr_ctx_destroy(gr_ctx *c) {
   }
   if (c->side) (void)hipStreamDestroy(c->side);
   for (void *p : {(void *)c->ctrl, (void *)c->rec, (void *)c->comp, (void *)c->nrow8, (void *)c->work, (void *)c->clip, c->winner,
-                  c->sort_tmp, (void *)c->resize_tmp, (void *)c->bounds_part, (void *)c->region_tmp, (void *)c->outline_a, (void *)c->outline_b, (void *)c->select_tmp, (void *)c->blk, (void *)c->visits, (void *)c->touched, (void *)c->soup,
+                  (void *)c->stage.ptr, (void *)c->stage_b.ptr, (void *)c->blk, (void *)c->visits, (void *)c->touched, (void *)c->soup,
                   (void *)c->bvert, (void *)c->bidx, (void *)c->orig, (void *)c->stats, (void *)c->flag})
     if (p) (void)hipFree(p);
   delete c;

@@ -1,6 +1,7 @@
 #pragma once
 // geograypher_amd/csrc/gr_internal.hpp -- what the translation units of libgeograster share: constants, the kernel
-// argument blocks, the context, and the host-side helpers (error text, HIP-event spans, grow-only scratch).
+// argument blocks, the context, and the host-side helpers (error text, HIP-event spans, grow-only scratch, the stage arena:
+// Scratch, stage_acquire, GR_CUB_MAX; its layouts come from scratch_layout.hpp).
 //   geograster.hip   context, options, learned binning table, the raster call (launch groups, side stream), status
 //   mesh_upload.hip  gr_mesh_upload: Morton order, de-indexed soup, block bounds            (per upload)
 //   binning.hip      k_cull_blocks, k_setup_cull, k_clip_faces, entry compilation, exact-path scan / fill  (per view)
@@ -31,6 +32,7 @@
 #include <vector>
 
 #include "geograster.h"
+#include "scratch_layout.hpp"
 
 // ------------------------------------------------------------------------------------------------------------------
 // constants
@@ -43,7 +45,6 @@
 #define GR_MAX_DIM 16384    // h, w limit (guard band and 16-bit bbox packing)
 #define GR_BLOCK 64         // faces per block of the Morton-ordered soup: one wave, one bounding sphere
 #define GR_BLOCK_VERTS 192  // distinct vertices a block can have (3 per face); a patch of a manifold mesh has about 48
-#define GR_REGION_HEAD_WORDS 16  // 32-bit words at the front of gr_ctx::region_tmp: the joint box of gr_points_in_region (4 x int64), padded to 64 bytes
 namespace grimpl {
 
 // The words of the overflow protocol, named once: kernels, host decode and the vote pass all index through these.
@@ -164,6 +165,9 @@ struct RasterOut {
   int compat;        // GR_FLAG_NEG1_IS_LAST_FACE
 };
 
+// A block of per-call device scratch and the stream of its last user (stage_acquire below).
+struct Scratch { uint8_t *ptr = nullptr; int64_t have = 0; hipStream_t last = nullptr; };
+
 }  // namespace grimpl
 
 struct gr_ctx {
@@ -244,23 +248,13 @@ struct gr_ctx {
   // fused aggregation: the vote kernel of launch group g runs on a side stream beside the binning of group g + 1
   hipStream_t side = nullptr;
   hipEvent_t ev_raster[2] = {nullptr, nullptr}, ev_vote[2] = {nullptr, nullptr};
-  void *sort_tmp = nullptr;
-  size_t sort_bytes = 0;
 #ifdef GR_STAMPS
   unsigned long long *stamps = nullptr;  // diagnostic build: phase cycles of the tile kernel, summed since the last read
 #endif
-  double *resize_tmp = nullptr;        // rows pass of gr_resize_image_f64: [2 h_out][w_in * C]
-  int64_t resize_have = 0;
-  double *bounds_part = nullptr;       // per-workgroup partial records of gr_points_bounds (cover.hip): 1024 x 64 bytes
-  int64_t bounds_part_have = 0;
-  uint32_t *region_tmp = nullptr;      // polygons.hip: the joint box of gr_points_in_region | flags, scans and hipcub's temporaries of gr_submesh_extract
-  int64_t region_have = 0;             // ... in 32-bit words
-  uint8_t *outline_a = nullptr;        // polygons.hip, gr_class_outlines: canon ids | the vertex sort, then the edge sort and its runs | hipcub's temporaries
-  int64_t outline_a_have = 0;          // ... in bytes
-  uint8_t *outline_b = nullptr;        // ... the slots, their successors, the two pointer-doubling sets, the ring scan (sized by the surviving edges)
-  int64_t outline_b_have = 0;
-  uint8_t *select_tmp = nullptr;       // select.hip, gr_set_cover: control words | gains, counts, pointers per view | m, flags per face | the view-major lists
-  int64_t select_have = 0;             // ... in bytes
+  // The stage arena: the per-call scratch of every stage call (the mesh upload's sort, pair counts, ray pairs, resize, point
+  // bounds, region, sub-mesh, class outlines, set cover), one call at a time, each carving what it needs from offset 0.
+  grimpl::Scratch stage;
+  grimpl::Scratch stage_b;             // gr_class_outlines alone: its second block is sized after a read-back, while the first is live
   hipStream_t last_stream = nullptr;   // of the last raster call (gr_raster_status reads its outcome there)
   std::vector<hipStream_t> used_streams;  // streams that work touching context scratch was enqueued on since the last quiesce
   // profiling
@@ -376,6 +370,22 @@ int grow(gr_ctx *c, T *&ptr, int64_t &have, int64_t want, const char *what) {
   have = want;
   return GR_OK;
 }
+
+// The only way to stage scratch: `bytes` of `sc` for work that the caller enqueues on `s`.  The block's last user may have been
+// another stream of the context and may have returned without waiting (gr_resize_image_f64, gr_mesh_upload, ...): it is waited
+// for here, so calls of one context on different streams use the block in turn.  On one stream this adds nothing.
+inline int stage_acquire(gr_ctx *c, Scratch &sc, size_t bytes, hipStream_t s, const char *what) {
+  if (sc.ptr && sc.last != s) (void)hipStreamSynchronize(sc.last);   // (a block that was used: the null stream is a stream too)
+  const int rc = grow(c, sc.ptr, sc.have, (int64_t)bytes, what);
+  if (rc != GR_OK) return rc;
+  note_stream(c, s);
+  sc.last = s;
+  return GR_OK;
+}
+
+// A hipcub size query (null temporary storage, its size argument named cub_q): MAXB keeps the largest answer of a scratch block.
+// The real calls pass MAXB: hipcub takes more than it asked for.
+#define GR_CUB_MAX(ctx, MAXB, QUERY) do { size_t cub_q = 0; GR_HIP(ctx, QUERY); if (cub_q > (MAXB)) (MAXB) = cub_q; } while (0)
 
 // (the zeroes go out on the CALL's stream: a plain hipMemset runs on the null stream, which a non-blocking stream -- torch's
 // side streams, one per device thread of a devices=[...] mesh -- does not wait for: the first view's winners could be wiped

@@ -239,26 +239,20 @@ int gr_mesh_upload(gr_ctx *c, const float *verts, const int32_t *faces, int64_t 
     c->soup_cap = F;
   }
   // Morton codes -> stable radix sort of (code, face) pairs (rocPRIM through hipcub) -> orig[]
-  size_t sort_bytes = 0;
-  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                               (int32_t *)nullptr, (int32_t *)nullptr, (int)F, 0, 32, s));
-  const size_t arr = ((size_t)F * 4 + 255) / 256 * 256;
-  const size_t need = 3 * arr + sort_bytes + 256;
-  if (c->sort_bytes < need) {
-    GR_HIP(c, hipStreamSynchronize(s));
-    if (c->sort_tmp) (void)hipFree(c->sort_tmp);
-    c->sort_tmp = nullptr; c->sort_bytes = 0;
-    if (hipMalloc(&c->sort_tmp, need) != hipSuccess) return fail(c, GR_ENOMEM, "sort scratch allocation failed");
-    c->sort_bytes = need;
-  }
-  char *base = static_cast<char *>(c->sort_tmp);
-  uint32_t *code_in = reinterpret_cast<uint32_t *>(base), *code_out = reinterpret_cast<uint32_t *>(base + arr);
-  int32_t *idx_in = reinterpret_cast<int32_t *>(base + 2 * arr);
-  void *tmp = base + 3 * arr;
+  size_t cub = 0;
+  GR_CUB_MAX(c, cub, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr,
+                                                        (int32_t *)nullptr, (int)F, 0, 32, s));
+  // scratch: code_in [F] | code_out [F] | idx_in [F] | rocPRIM
+  Carve cv;
+  const size_t o_code_in = cv.array<uint32_t>(F), o_code_out = cv.array<uint32_t>(F), o_idx_in = cv.array<int32_t>(F), o_tmp = cv.bytes(cub);
+  int rc = stage_acquire(c, c->stage, cv.total(), s, "sort");
+  if (rc != GR_OK) return rc;
+  uint8_t *base = c->stage.ptr;
+  uint32_t *code_in = Carve::at<uint32_t>(base, o_code_in), *code_out = Carve::at<uint32_t>(base, o_code_out);
+  int32_t *idx_in = Carve::at<int32_t>(base, o_idx_in);
   hipLaunchKernelGGL(k_face_codes, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, verts, faces, F, ax0, ax1, lo[ax0], inv0,
                      lo[ax1], inv1, code_in, idx_in);
-  size_t tb = sort_bytes;
-  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, tb, code_in, code_out, idx_in, c->orig, (int)F, 0, 32, s));
+  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, cub, code_in, code_out, idx_in, c->orig, (int)F, 0, 32, s));
   hipLaunchKernelGGL(k_build_soup, dim3((unsigned)ceil_div(3 * F, 256)), dim3(256), 0, s, verts, faces, c->orig, F, c->soup);
   hipLaunchKernelGGL(k_block_bounds, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, c->soup, F, c->blk);
   hipLaunchKernelGGL(k_block_vertices, dim3((unsigned)ceil_div(nblk, 4)), dim3(256), 0, s, verts, faces, c->orig, F, c->bvert, c->bidx);

@@ -728,9 +728,6 @@ __global__ __launch_bounds__(256) void k_outline_emit_rings(const int32_t *__res
   if (s == 0) ring_offsets[(int64_t)(ws[E] & 0xFFFFFFFFull)] = E;
 }
 
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-inline int bit_length(int64_t v) { int n = 0; while (v > 0) { ++n; v >>= 1; } return n; }
-
 }  // namespace
 
 extern "C" {
@@ -813,10 +810,12 @@ int gr_points_in_region(gr_ctx *c, const int64_t *points_q, int64_t N, const int
     GR_HIP(c, hipMemsetAsync(mask, 0, (size_t)N, s));
     return GR_OK;
   }
-  int rc = grow(c, c->region_tmp, c->region_have, (int64_t)GR_REGION_HEAD_WORDS, "region");
+  // scratch: joint box [4] i64
+  Carve cv;
+  const size_t o_joint = cv.array<int64_t>(4);
+  int rc = stage_acquire(c, c->stage, cv.total(), s, "region");
   if (rc != GR_OK) return rc;
-  note_stream(c, s);
-  int64_t *joint = (int64_t *)c->region_tmp;
+  int64_t *joint = Carve::at<int64_t>(c->stage.ptr, o_joint);
   hipLaunchKernelGGL(k_region_joint_box, dim3(1), dim3(256), 0, s, polygon_boxes, (int)P, joint);
   RegionArgs a;
   a.N = N; a.n_rv = n_ring_vertices; a.D = D; a.R = (int)R; a.P = (int)P;
@@ -837,26 +836,23 @@ int gr_submesh_extract(gr_ctx *c, const uint8_t *mask, int64_t V, const int32_t 
   GR_HIP(c, hipSetDevice(c->device));
   GR_HIP(c, hipMemsetAsync(counts, 0, sizeof(uint64_t) * 3, s));
   if (F == 0) return GR_OK;   // no face: nothing is kept (a vertex no face uses is dropped)
-  size_t fb = 0, vb = 0;
-  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, fb, (int32_t *)nullptr, (int32_t *)nullptr, (int)F, s));
-  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, vb, (int32_t *)nullptr, (int32_t *)nullptr, (int)V, s));
-  // scratch, in 32-bit words: head | fflag [F] | fpos [F] | vused [V] | vpos [V] | the scans' temporaries (16-byte aligned)
-  const int64_t o_ff = GR_REGION_HEAD_WORDS, o_fp = o_ff + F, o_vu = o_fp + F, o_vp = o_vu + V;
-  const int64_t o_tmp = (o_vp + V + 3) & ~(int64_t)3;
-  const int64_t tmp_words = (int64_t)((std::max(fb, vb) + 3) / 4) + 4;
-  int rc = grow(c, c->region_tmp, c->region_have, o_tmp + tmp_words, "sub-mesh");
+  size_t cub = 0;
+  GR_CUB_MAX(c, cub, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)F, s));
+  GR_CUB_MAX(c, cub, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)V, s));
+  // scratch: fflag [F] | fpos [F] | vused [V] | vpos [V] | the scans' temporaries
+  Carve cv;
+  const size_t o_ff = cv.array<int32_t>(F), o_fp = cv.array<int32_t>(F), o_vu = cv.array<int32_t>(V), o_vp = cv.array<int32_t>(V), o_tmp = cv.bytes(cub);
+  int rc = stage_acquire(c, c->stage, cv.total(), s, "sub-mesh");
   if (rc != GR_OK) return rc;
-  note_stream(c, s);
-  int32_t *base = (int32_t *)c->region_tmp;
-  int32_t *fflag = base + o_ff, *fpos = base + o_fp, *vused = base + o_vu, *vpos = base + o_vp;
-  void *tmp = (void *)(base + o_tmp);
+  uint8_t *base = c->stage.ptr;
+  int32_t *fflag = Carve::at<int32_t>(base, o_ff), *fpos = Carve::at<int32_t>(base, o_fp);
+  int32_t *vused = Carve::at<int32_t>(base, o_vu), *vpos = Carve::at<int32_t>(base, o_vp);
+  void *tmp = base + o_tmp;
   GR_HIP(c, hipMemsetAsync(vused, 0, sizeof(int32_t) * (size_t)V, s));
   hipLaunchKernelGGL(k_submesh_flags, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, mask, V, faces, F, fflag, vused,
                      (unsigned long long *)counts);
-  size_t tb = fb;
-  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, tb, fflag, fpos, (int)F, s));
-  tb = vb;
-  if (V > 0) GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, tb, vused, vpos, (int)V, s));
+  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, cub, fflag, fpos, (int)F, s));
+  if (V > 0) GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, cub, vused, vpos, (int)V, s));
   hipLaunchKernelGGL(k_submesh_write, dim3((unsigned)ceil_div(std::max(F, V), 256)), dim3(256), 0, s, faces, F, V,
                      (const int32_t *)fflag, (const int32_t *)fpos, (const int32_t *)vused, (const int32_t *)vpos, face_ids, point_ids,
                      new_faces, (unsigned long long *)counts);
@@ -884,84 +880,76 @@ int gr_class_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_
   const int64_t N3 = 3 * F;
   const int vbits = std::max(bit_length(V - 1), 1), cbits = std::max(bit_length(n_classes), 1);
 
-  // scratch A, sized by V and F: head | canon [V] | the vertex sort or the edge sort and its runs | hipcub's temporaries
-  size_t t_vs = 0, t_vm = 0, t_e1 = 0, t_e2 = 0, t_f = 0, t_s = 0;
+  size_t cub_a = 0;
   if (V > 0) {
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, t_vs, (int64_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr,
-                                                 (int32_t *)nullptr, (int)V, 0, 64, s));
-    GR_HIP(c, hipcub::DeviceScan::InclusiveScan(nullptr, t_vm, (int32_t *)nullptr, (int32_t *)nullptr, hipcub::Max(), (int)V, s));
+    GR_CUB_MAX(c, cub_a, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (int64_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr,
+                                                            (int32_t *)nullptr, (int)V, 0, 64, s));
+    GR_CUB_MAX(c, cub_a, hipcub::DeviceScan::InclusiveScan(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, hipcub::Max(), (int)V, s));
   }
   if (F > 0) {
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, t_e1, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                                 (uint32_t *)nullptr, (uint32_t *)nullptr, (int)N3, 0, 31 + vbits, s));
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, t_e2, (uint32_t *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr,
-                                                 (unsigned long long *)nullptr, (int)N3, 0, cbits, s));
-    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, t_f, (int32_t *)nullptr, (int32_t *)nullptr, (int)N3, s));
-    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, t_s, (int32_t *)nullptr, (int32_t *)nullptr, (int)(N3 + 1), s));
+    GR_CUB_MAX(c, cub_a, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                                            (uint32_t *)nullptr, (uint32_t *)nullptr, (int)N3, 0, 31 + vbits, s));
+    GR_CUB_MAX(c, cub_a, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                            (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)N3, 0, cbits, s));
+    GR_CUB_MAX(c, cub_a, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)N3, s));
+    GR_CUB_MAX(c, cub_a, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)(N3 + 1), s));
   }
-  const size_t tmp_a = up256(std::max({t_vs, t_vm, t_e1, t_e2, t_f, t_s})) + 256;
-  const size_t o_canon = sizeof(unsigned long long) * GR_OUTL_HEAD_WORDS, o_x = o_canon + up256(4 * (size_t)V);
+  // scratch A, sized by V and F: head | canon [V] | the vertex sort or the edge sort and its runs | hipcub's temporaries
+  Carve ca;
+  const size_t o_head = ca.array<unsigned long long>(GR_OUTL_HEAD_WORDS), o_canon = ca.array<int32_t>(V), phase = ca.mark();
   // vertex phase: key [V] i64 | key_s [V] i64 | idx [V] | idx_s [V] | hp [V] | hp_max [V]
-  const size_t v_key = o_x, v_key_s = v_key + up256(8 * (size_t)V), v_idx = v_key_s + up256(8 * (size_t)V);
-  const size_t v_idx_s = v_idx + up256(4 * (size_t)V), v_hp = v_idx_s + up256(4 * (size_t)V), v_hpm = v_hp + up256(4 * (size_t)V);
-  const size_t v_end = v_hpm + up256(4 * (size_t)V);
+  const size_t v_key = ca.array<int64_t>(V), v_key_s = ca.array<int64_t>(V), v_idx = ca.array<int32_t>(V), v_idx_s = ca.array<int32_t>(V);
+  const size_t v_hp = ca.array<int32_t>(V), v_hpm = ca.array<int32_t>(V);
+  ca.rewind(phase);
   // edge phase: pair [N3] u64 | pair_s [N3] u64 | cl [N3] | cl_s [N3] | flag [N3] | ex [N3] | ustart, surv, soff [N3 + 1]
-  const size_t e_pair = o_x, e_pair_s = e_pair + up256(8 * (size_t)N3), e_cl = e_pair_s + up256(8 * (size_t)N3);
-  const size_t e_cl_s = e_cl + up256(4 * (size_t)N3), e_flag = e_cl_s + up256(4 * (size_t)N3), e_ex = e_flag + up256(4 * (size_t)N3);
-  const size_t e_ustart = e_ex + up256(4 * (size_t)N3), e_surv = e_ustart + up256(4 * (size_t)(N3 + 1));
-  const size_t e_soff = e_surv + up256(4 * (size_t)(N3 + 1)), e_end = e_soff + up256(4 * (size_t)(N3 + 1));
-  const size_t o_tmp_a = std::max(v_end, e_end);
-  int rc = grow(c, c->outline_a, c->outline_a_have, (int64_t)(o_tmp_a + tmp_a), "class-outline");
+  const size_t e_pair = ca.array<unsigned long long>(N3), e_pair_s = ca.array<unsigned long long>(N3);
+  const size_t e_cl = ca.array<uint32_t>(N3), e_cl_s = ca.array<uint32_t>(N3), e_flag = ca.array<int32_t>(N3), e_ex = ca.array<int32_t>(N3);
+  const size_t e_ustart = ca.array<int32_t>(N3 + 1), e_surv = ca.array<int32_t>(N3 + 1), e_soff = ca.array<int32_t>(N3 + 1);
+  ca.rewind(ca.total());   // behind both phases
+  const size_t o_tmp_a = ca.bytes(cub_a);
+  int rc = stage_acquire(c, c->stage, ca.total(), s, "class-outline");
   if (rc != GR_OK) return rc;
-  note_stream(c, s);
-  char *A = (char *)c->outline_a;
-  unsigned long long *head = (unsigned long long *)A;
-  int32_t *canon_d = (int32_t *)(A + o_canon);
+  uint8_t *A = c->stage.ptr;
+  unsigned long long *head = Carve::at<unsigned long long>(A, o_head);
+  int32_t *canon_d = Carve::at<int32_t>(A, o_canon);
   void *tmp = A + o_tmp_a;
   GR_HIP(c, hipMemsetAsync(head, 0, sizeof(unsigned long long) * GR_OUTL_HEAD_WORDS, s));
 
   if (V > 0) {   // X2
-    int64_t *key = (int64_t *)(A + v_key), *key_s = (int64_t *)(A + v_key_s);
-    int32_t *idx = (int32_t *)(A + v_idx), *idx_s = (int32_t *)(A + v_idx_s), *hp = (int32_t *)(A + v_hp), *hpm = (int32_t *)(A + v_hpm);
+    int64_t *key = Carve::at<int64_t>(A, v_key), *key_s = Carve::at<int64_t>(A, v_key_s);
+    int32_t *idx = Carve::at<int32_t>(A, v_idx), *idx_s = Carve::at<int32_t>(A, v_idx_s), *hp = Carve::at<int32_t>(A, v_hp), *hpm = Carve::at<int32_t>(A, v_hpm);
     const dim3 grid((unsigned)ceil_div(V, 256));
     hipLaunchKernelGGL(k_outline_vertex_keys, grid, dim3(256), 0, s, verts_q, V, key, idx);
-    size_t tb = t_vs;
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key_s, idx, idx_s, (int)V, 0, 64, s));           // by y
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub_a, key, key_s, idx, idx_s, (int)V, 0, 64, s));           // by y
     hipLaunchKernelGGL(k_outline_vertex_gather, grid, dim3(256), 0, s, verts_q, V, (const int32_t *)idx_s, key);
-    tb = t_vs;
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key_s, idx_s, idx, (int)V, 0, 64, s));           // then by x, stably
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub_a, key, key_s, idx_s, idx, (int)V, 0, 64, s));           // then by x, stably
     hipLaunchKernelGGL(k_outline_vertex_heads, grid, dim3(256), 0, s, verts_q, V, (const int32_t *)idx, hp);
-    tb = t_vm;
-    GR_HIP(c, hipcub::DeviceScan::InclusiveScan(tmp, tb, hp, hpm, hipcub::Max(), (int)V, s));
+    GR_HIP(c, hipcub::DeviceScan::InclusiveScan(tmp, cub_a, hp, hpm, hipcub::Max(), (int)V, s));
     hipLaunchKernelGGL(k_outline_canon, grid, dim3(256), 0, s, V, (const int32_t *)idx, (const int32_t *)hpm, canon_d);
     GR_HIP(c, hipGetLastError());
   }
 
   int64_t E = 0, R = 0, runs = 0;
-  unsigned long long *pair = (unsigned long long *)(A + e_pair), *pair_s = (unsigned long long *)(A + e_pair_s);
-  uint32_t *cl = (uint32_t *)(A + e_cl), *cl_s = (uint32_t *)(A + e_cl_s);
-  int32_t *flag = (int32_t *)(A + e_flag), *ex = (int32_t *)(A + e_ex), *ustart = (int32_t *)(A + e_ustart);
-  int32_t *surv = (int32_t *)(A + e_surv), *soff = (int32_t *)(A + e_soff);
+  unsigned long long *pair = Carve::at<unsigned long long>(A, e_pair), *pair_s = Carve::at<unsigned long long>(A, e_pair_s);
+  uint32_t *cl = Carve::at<uint32_t>(A, e_cl), *cl_s = Carve::at<uint32_t>(A, e_cl_s);
+  int32_t *flag = Carve::at<int32_t>(A, e_flag), *ex = Carve::at<int32_t>(A, e_ex), *ustart = Carve::at<int32_t>(A, e_ustart);
+  int32_t *surv = Carve::at<int32_t>(A, e_surv), *soff = Carve::at<int32_t>(A, e_soff);
   if (F > 0) {   // X3, X4
     const dim3 gf((unsigned)ceil_div(F, 256)), ge((unsigned)ceil_div(N3, 256));
     hipLaunchKernelGGL(k_outline_face_edges, gf, dim3(256), 0, s, verts_q, V, faces, F, face_class, n_classes,
                        (const int32_t *)canon_d, pair, cl, st);
-    size_t tb = t_e1;
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, tb, pair, pair_s, cl, cl_s, (int)N3, 0, 31 + vbits, s));   // by (from, to)
-    tb = t_e2;
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, tb, cl_s, cl, pair_s, pair, (int)N3, 0, cbits, s));        // then by class, stably
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub_a, pair, pair_s, cl, cl_s, (int)N3, 0, 31 + vbits, s));   // by (from, to)
+    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub_a, cl_s, cl, pair_s, pair, (int)N3, 0, cbits, s));        // then by class, stably
     hipLaunchKernelGGL(k_outline_run_heads, ge, dim3(256), 0, s, (const unsigned long long *)pair, (const uint32_t *)cl, N3,
                        n_classes, flag);
-    tb = t_f;
-    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, tb, flag, ex, (int)N3, s));
+    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, cub_a, flag, ex, (int)N3, s));
     GR_HIP(c, hipMemsetAsync(ustart, 0, sizeof(int32_t) * (size_t)(N3 + 1), s));
     GR_HIP(c, hipMemsetAsync(surv, 0, sizeof(int32_t) * (size_t)(N3 + 1), s));
     hipLaunchKernelGGL(k_outline_run_starts, ge, dim3(256), 0, s, (const uint32_t *)cl, N3, n_classes, (const int32_t *)flag,
                        (const int32_t *)ex, ustart, head);
     hipLaunchKernelGGL(k_outline_cancel, ge, dim3(256), 0, s, (const unsigned long long *)pair, (const uint32_t *)cl,
                        (const int32_t *)ex, (const int32_t *)ustart, (const unsigned long long *)head, surv, st);
-    tb = t_s;
-    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, tb, surv, soff, (int)(N3 + 1), s));
+    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, cub_a, surv, soff, (int)(N3 + 1), s));
     GR_HIP(c, hipGetLastError());
     unsigned long long runs_h = 0;
     int32_t edges_h = 0;
@@ -983,30 +971,30 @@ int gr_class_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_
     return GR_OK;
   }
 
+  size_t cub_b = 0;
+  GR_CUB_MAX(c, cub_b, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                                          (int32_t *)nullptr, (int32_t *)nullptr, (int)E, 0, 31 + cbits, s));
+  GR_CUB_MAX(c, cub_b, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)(E + 1), s));
   // scratch B, sized by E: efrom | ecls | succ | two sets of (nxt, mn, off) | kin, kin_s [E + 1] u64 | hipcub's temporaries
-  size_t t_in = 0, t_w = 0;
-  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, t_in, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                               (int32_t *)nullptr, (int32_t *)nullptr, (int)E, 0, 31 + cbits, s));
-  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, t_w, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)(E + 1), s));
-  const size_t tmp_b = up256(std::max(t_in, t_w)) + 256;
-  const size_t e4 = up256(4 * (size_t)E), e8 = up256(8 * (size_t)(E + 1));
-  const size_t b_from = 0, b_cls = b_from + e4, b_succ = b_cls + e4, b_set0 = b_succ + e4, b_set1 = b_set0 + 3 * e4;
-  const size_t b_kin = b_set1 + 3 * e4, b_kin_s = b_kin + e8, b_tmp = b_kin_s + e8;
-  rc = grow(c, c->outline_b, c->outline_b_have, (int64_t)(b_tmp + tmp_b), "class-outline ring");
+  Carve cb;
+  const size_t b_from = cb.array<int32_t>(E), b_cls = cb.array<int32_t>(E), b_succ = cb.array<int32_t>(E);
+  size_t b_set[2][3];
+  for (int k = 0; k < 6; ++k) b_set[k / 3][k % 3] = cb.array<int32_t>(E);
+  const size_t b_kin = cb.array<unsigned long long>(E + 1), b_kin_s = cb.array<unsigned long long>(E + 1), b_tmp = cb.bytes(cub_b);
+  rc = stage_acquire(c, c->stage_b, cb.total(), s, "class-outline ring");
   if (rc != GR_OK) return rc;
-  char *B = (char *)c->outline_b;
-  int32_t *efrom = (int32_t *)(B + b_from), *ecls = (int32_t *)(B + b_cls), *succ = (int32_t *)(B + b_succ);
+  uint8_t *B = c->stage_b.ptr;
+  int32_t *efrom = Carve::at<int32_t>(B, b_from), *ecls = Carve::at<int32_t>(B, b_cls), *succ = Carve::at<int32_t>(B, b_succ);
   int32_t *set[2][3];
-  for (int k = 0; k < 3; ++k) { set[0][k] = (int32_t *)(B + b_set0 + k * e4); set[1][k] = (int32_t *)(B + b_set1 + k * e4); }
-  unsigned long long *kin = (unsigned long long *)(B + b_kin), *kin_s = (unsigned long long *)(B + b_kin_s);
+  for (int k = 0; k < 6; ++k) set[k / 3][k % 3] = Carve::at<int32_t>(B, b_set[k / 3][k % 3]);
+  unsigned long long *kin = Carve::at<unsigned long long>(B, b_kin), *kin_s = Carve::at<unsigned long long>(B, b_kin_s);
   int32_t *vin = set[1][0], *vin_s = set[1][1];   // free until the first round writes the second set
   void *tmp2 = B + b_tmp;
   const dim3 gE((unsigned)ceil_div(E, 256)), gE1((unsigned)ceil_div(E + 1, 256));
   hipLaunchKernelGGL(k_outline_emit_edges, dim3((unsigned)ceil_div(runs, 256)), dim3(256), 0, s, (const unsigned long long *)pair,
                      (const uint32_t *)cl, (const int32_t *)ustart, (const int32_t *)surv, (const int32_t *)soff, runs, efrom, ecls,
                      kin, vin);
-  size_t tb = t_in;
-  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp2, tb, kin, kin_s, vin, vin_s, (int)E, 0, 31 + cbits, s));   // X5
+  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp2, cub_b, kin, kin_s, vin, vin_s, (int)E, 0, 31 + cbits, s));   // X5
   hipLaunchKernelGGL(k_outline_successor, gE, dim3(256), 0, s, (const int32_t *)vin_s, E, succ, set[0][1], set[0][2]);
   // X6: round r reads the successor table first, then its own doubled pointers
   int cur = 0;
@@ -1019,8 +1007,7 @@ int gr_class_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_
   const int32_t *mn = set[cur][1], *off = set[cur][2];
   unsigned long long *w = kin, *ws = kin_s;
   hipLaunchKernelGGL(k_outline_ring_words, gE1, dim3(256), 0, s, (const int32_t *)succ, mn, off, E, w);
-  tb = t_w;
-  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp2, tb, w, ws, (int)(E + 1), s));
+  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp2, cub_b, w, ws, (int)(E + 1), s));
   GR_HIP(c, hipGetLastError());
   unsigned long long total = 0;
   GR_HIP(c, hipMemcpyAsync(&total, ws + E, sizeof(total), hipMemcpyDeviceToHost, s));

@@ -786,29 +786,19 @@ int gr_count_pairs(gr_ctx *c, uint64_t *keys, int64_t n, uint64_t *unique_keys, 
   hipStream_t s = (hipStream_t)stream;
   GR_HIP(c, hipSetDevice(c->device));
   // radix sort (keys -> sorted copy in context scratch) + run-length encode, both rocPRIM through hipcub
-  size_t sort_bytes = 0, rle_bytes = 0;
+  size_t cub = 0;
   unsigned long long *kin = (unsigned long long *)keys, *uo = (unsigned long long *)unique_keys;
-  GR_HIP(c, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, kin, kin, (int)n, 0, 64, s));
-  int *d_runs = nullptr;
-  GR_HIP(c, hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, kin, uo, pair_counts, d_runs, (int)n, s));
-  const size_t tmp_bytes = (sort_bytes > rle_bytes ? sort_bytes : rle_bytes) + 256;
-  const size_t need = tmp_bytes + sizeof(unsigned long long) * (size_t)n + 256;
-  if (c->sort_bytes < need) {
-    quiesce(c);
-    GR_HIP(c, hipStreamSynchronize(s));
-    if (c->sort_tmp) (void)hipFree(c->sort_tmp);
-    c->sort_tmp = nullptr; c->sort_bytes = 0;
-    if (hipMalloc(&c->sort_tmp, need) != hipSuccess) return fail(c, GR_ENOMEM, "sort scratch allocation failed");
-    c->sort_bytes = need;
-  }
-  note_stream(c, s);
-  char *base = (char *)c->sort_tmp;
-  unsigned long long *sorted = (unsigned long long *)base;
-  void *tmp = base + ((sizeof(unsigned long long) * (size_t)n + 255) / 256) * 256;
-  size_t tb = sort_bytes;
-  GR_HIP(c, hipcub::DeviceRadixSort::SortKeys(tmp, tb, kin, sorted, (int)n, 0, 64, s));
-  tb = rle_bytes;
-  GR_HIP(c, hipcub::DeviceRunLengthEncode::Encode(tmp, tb, sorted, uo, pair_counts, (int *)c->flag, (int)n, s));
+  GR_CUB_MAX(c, cub, hipcub::DeviceRadixSort::SortKeys(nullptr, cub_q, kin, kin, (int)n, 0, 64, s));
+  GR_CUB_MAX(c, cub, hipcub::DeviceRunLengthEncode::Encode(nullptr, cub_q, kin, uo, pair_counts, (int *)nullptr, (int)n, s));
+  // scratch: sorted [n] | rocPRIM
+  Carve cv;
+  const size_t o_sorted = cv.array<unsigned long long>(n), o_tmp = cv.bytes(cub);
+  int rc = stage_acquire(c, c->stage, cv.total(), s, "sort");
+  if (rc != GR_OK) return rc;
+  unsigned long long *sorted = Carve::at<unsigned long long>(c->stage.ptr, o_sorted);
+  void *tmp = c->stage.ptr + o_tmp;
+  GR_HIP(c, hipcub::DeviceRadixSort::SortKeys(tmp, cub, kin, sorted, (int)n, 0, 64, s));
+  GR_HIP(c, hipcub::DeviceRunLengthEncode::Encode(tmp, cub, sorted, uo, pair_counts, (int *)c->flag, (int)n, s));
   int runs = 0;
   GR_HIP(c, hipMemcpyAsync(&runs, c->flag, sizeof(int), hipMemcpyDeviceToHost, s));
   GR_HIP(c, hipStreamSynchronize(s));

@@ -240,8 +240,6 @@ __global__ void __launch_bounds__(256) k_rays_clip(const double *__restrict__ or
   p_out[3 * r + 2] = any ? oz + best * dz : NAN;
 }
 
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 extern "C" {
@@ -268,34 +266,27 @@ int gr_ray_pairs(gr_ctx *c, const double *starts, const double *ends, const int3
   GR_HIP(c, hipSetDevice(c->device));
   const int64_t T = ceil_div(n, GR_RAY_TILE), tiles = tri_off(T, T);
   const int64_t cap = fill ? edge_cap : 0;
-  // context scratch: edge counter | ray records | keys | distances | sorted keys | rocPRIM
-  size_t sort_bytes = 0;
+  size_t cub = 0;
   int end_bit = 64;
   if (fill) {
     int nbits = 1;
     while (((int64_t)1 << nbits) < n) ++nbits;
     end_bit = 32 + nbits;   // i < n sits above bit 32
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                                 (double *)nullptr, (double *)nullptr, (int)cap, 0, end_bit, s));
+    GR_CUB_MAX(c, cub, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                                          (double *)nullptr, (double *)nullptr, (int)cap, 0, end_bit, s));
   }
-  const size_t o_rec = 256, o_keys = o_rec + up256(sizeof(RayRec) * (size_t)(n > 0 ? n : 1));
-  const size_t o_dist = o_keys + up256(8 * (size_t)cap), o_sorted = o_dist + up256(8 * (size_t)cap);
-  const size_t o_tmp = o_sorted + up256(8 * (size_t)cap), need = o_tmp + sort_bytes + 256;
-  if (c->sort_bytes < need) {
-    quiesce(c);
-    GR_HIP(c, hipStreamSynchronize(s));
-    if (c->sort_tmp) (void)hipFree(c->sort_tmp);
-    c->sort_tmp = nullptr; c->sort_bytes = 0;
-    if (hipMalloc(&c->sort_tmp, need) != hipSuccess) return fail(c, GR_ENOMEM, "ray-pair scratch allocation failed (%zu bytes)", need);
-    c->sort_bytes = need;
-  }
-  note_stream(c, s);
-  char *base = (char *)c->sort_tmp;
-  if (c->opt_dbg & GR_DBG_POISON_RAYS) GR_HIP(c, hipMemsetAsync(base, 0xFF, c->sort_bytes, s));   // test hook: nothing survives between calls
-  unsigned long long *counter = (unsigned long long *)base;
-  RayRec *rec = (RayRec *)(base + o_rec);
-  unsigned long long *keys = (unsigned long long *)(base + o_keys), *sorted = (unsigned long long *)(base + o_sorted);
-  double *dist = (double *)(base + o_dist);
+  // scratch: edge counter | rec [n] | keys [cap] | dist [cap] | sorted [cap] | rocPRIM
+  Carve cv;
+  const size_t o_counter = cv.array<unsigned long long>(1), o_rec = cv.array<RayRec>(n);
+  const size_t o_keys = cv.array<unsigned long long>(cap), o_dist = cv.array<double>(cap), o_sorted = cv.array<unsigned long long>(cap), o_tmp = cv.bytes(cub);
+  int rc = stage_acquire(c, c->stage, cv.total(), s, "ray-pair");
+  if (rc != GR_OK) return rc;
+  uint8_t *base = c->stage.ptr;
+  if (c->opt_dbg & GR_DBG_POISON_RAYS) GR_HIP(c, hipMemsetAsync(base, 0xFF, (size_t)c->stage.have, s));   // test hook: nothing survives between calls
+  unsigned long long *counter = Carve::at<unsigned long long>(base, o_counter);
+  RayRec *rec = Carve::at<RayRec>(base, o_rec);
+  unsigned long long *keys = Carve::at<unsigned long long>(base, o_keys), *sorted = Carve::at<unsigned long long>(base, o_sorted);
+  double *dist = Carve::at<double>(base, o_dist);
   GR_HIP(c, hipMemsetAsync(counter, 0, sizeof(unsigned long long), s));
   if (tiles > 0) {
     hipLaunchKernelGGL(k_ray_prep, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, starts, ends, ray_ids, n, rec);
@@ -317,8 +308,7 @@ int gr_ray_pairs(gr_ctx *c, const double *starts, const double *ends, const int3
   if ((int64_t)total > cap)
     return fail(c, GR_EOVERFLOW, "%llu ray pairs within the threshold, the edge buffers hold %lld: call again with that capacity",
                 total, (long long)cap);
-  size_t tb = sort_bytes;
-  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, tb, keys, sorted, dist, edge_d, (int)total, 0, end_bit, s));
+  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, cub, keys, sorted, dist, edge_d, (int)total, 0, end_bit, s));
   hipLaunchKernelGGL(k_ray_split_keys, dim3((unsigned)ceil_div((int64_t)total, 256)), dim3(256), 0, s, sorted, (int64_t)total,
                      edge_i, edge_j);
   GR_HIP(c, hipGetLastError());

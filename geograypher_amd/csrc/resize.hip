@@ -155,22 +155,25 @@ int gr_resize_image_f64(gr_ctx *c, const void *src, int dtype, int h_in, int w_i
   if (rr > GR_RESIZE_MAX_RADIUS || rc > GR_RESIZE_MAX_RADIUS)
     return fail(c, GR_EINVAL, "resize %dx%d -> %dx%d: anti-aliasing kernel radius %d exceeds %d", h_in, w_in, h_out, w_out,
                 std::max(rr, rc), GR_RESIZE_MAX_RADIUS);
-  int rc_ = grow(c, c->resize_tmp, c->resize_have, (int64_t)2 * h_out * E, "resize rows");
+  // scratch: rows [2 h_out][w_in * C] f64
+  Carve cv;
+  const size_t o_rows = cv.array<double>((int64_t)2 * h_out * E);
+  int rc_ = stage_acquire(c, c->stage, cv.total(), s, "resize rows");
   if (rc_) return rc_;
-  note_stream(c, s);
+  double *rows = Carve::at<double>(c->stage.ptr, o_rows);
   {
     const dim3 g((unsigned)ceil_div(E, 256), (unsigned)(2 * h_out)), b(256);
     const size_t lds = sizeof(double) * (size_t)(rr + 1 + 256);
     if (dtype == GR_DTYPE_U8)
-      hipLaunchKernelGGL(k_resize_rows<uint8_t>, g, b, lds, s, (const uint8_t *)src, h_in, E, divide_by_255, fr, sr, rr, c->resize_tmp);
+      hipLaunchKernelGGL(k_resize_rows<uint8_t>, g, b, lds, s, (const uint8_t *)src, h_in, E, divide_by_255, fr, sr, rr, rows);
     else if (dtype == GR_DTYPE_F32)
-      hipLaunchKernelGGL(k_resize_rows<float>, g, b, lds, s, (const float *)src, h_in, E, 0, fr, sr, rr, c->resize_tmp);
+      hipLaunchKernelGGL(k_resize_rows<float>, g, b, lds, s, (const float *)src, h_in, E, 0, fr, sr, rr, rows);
     else
-      hipLaunchKernelGGL(k_resize_rows<double>, g, b, lds, s, (const double *)src, h_in, E, 0, fr, sr, rr, c->resize_tmp);
+      hipLaunchKernelGGL(k_resize_rows<double>, g, b, lds, s, (const double *)src, h_in, E, 0, fr, sr, rr, rows);
   }
   {
     const dim3 g((unsigned)ceil_div((int64_t)w_out * C, 256), (unsigned)h_out), b(256);
-    hipLaunchKernelGGL(k_resize_cols, g, b, sizeof(double) * (size_t)(rc + 1), s, c->resize_tmp, w_in, C, w_out, fr, fc, sc, rc, out);
+    hipLaunchKernelGGL(k_resize_cols, g, b, sizeof(double) * (size_t)(rc + 1), s, rows, w_in, C, w_out, fr, fc, sc, rc, out);
   }
   GR_HIP(c, hipGetLastError());
   return GR_OK;

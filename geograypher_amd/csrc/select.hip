@@ -310,8 +310,6 @@ __global__ void k_sc_finish(const uint32_t *__restrict__ ctl, int64_t batches, i
   for (int i = GR_SETCOVER_STAT_LDS_HISTOGRAM + 1; i < GR_SETCOVER_STAT_WORDS; ++i) stats[i] = 0;
 }
 
-inline int64_t align16(int64_t bytes) { return (bytes + 15) & ~(int64_t)15; }
-
 }  // namespace
 
 extern "C" {
@@ -340,19 +338,18 @@ int gr_set_cover(gr_ctx *c, const int64_t *face_ptr, const int32_t *face_views, 
     return GR_OK;
   }
   // scratch: ctl | gain [N] | vcount [N] | red [N] | vptr [N + 1] | cursor [N] | m [F] | vfaces [nnz] | req [F]
-  const int64_t o_gain = align16(GR_SC_CTL_WORDS * 4), o_vcount = o_gain + align16(4 * (int64_t)N), o_red = o_vcount + align16(4 * (int64_t)N);
-  const int64_t o_vptr = o_red + align16(4 * (int64_t)N), o_cursor = o_vptr + align16(8 * ((int64_t)N + 1));
-  const int64_t o_m = o_cursor + align16(8 * (int64_t)N), o_vfaces = o_m + align16(4 * F), o_req = o_vfaces + align16(4 * nnz);
-  int rc = grow(c, c->select_tmp, c->select_have, o_req + align16(F), "set-cover");
+  Carve cv;
+  const size_t o_ctl = cv.array<uint32_t>(GR_SC_CTL_WORDS), o_gain = cv.array<int32_t>(N), o_vcount = cv.array<uint32_t>(N);
+  const size_t o_red = cv.array<int32_t>(N), o_vptr = cv.array<int64_t>((int64_t)N + 1), o_cursor = cv.array<u64>(N);
+  const size_t o_m = cv.array<int32_t>(F), o_vfaces = cv.array<int32_t>(nnz), o_req = cv.array<uint8_t>(F);
+  int rc = stage_acquire(c, c->stage, cv.total(), s, "set-cover");
   if (rc != GR_OK) return rc;
-  note_stream(c, s);
-  uint8_t *base = c->select_tmp;
-  uint32_t *ctl = (uint32_t *)base;
-  int32_t *gain = (int32_t *)(base + o_gain), *red = (int32_t *)(base + o_red), *m = (int32_t *)(base + o_m);
-  uint32_t *vcount = (uint32_t *)(base + o_vcount);
-  int64_t *vptr = (int64_t *)(base + o_vptr);
-  u64 *cursor = (u64 *)(base + o_cursor);
-  int32_t *vfaces = (int32_t *)(base + o_vfaces);
+  uint8_t *base = c->stage.ptr;
+  uint32_t *ctl = Carve::at<uint32_t>(base, o_ctl), *vcount = Carve::at<uint32_t>(base, o_vcount);
+  int32_t *gain = Carve::at<int32_t>(base, o_gain), *red = Carve::at<int32_t>(base, o_red), *m = Carve::at<int32_t>(base, o_m);
+  int64_t *vptr = Carve::at<int64_t>(base, o_vptr);
+  u64 *cursor = Carve::at<u64>(base, o_cursor);
+  int32_t *vfaces = Carve::at<int32_t>(base, o_vfaces);
   uint8_t *req = base + o_req;
 
   const double threshold = min_observations > 1.0 ? min_observations : 1.0;   // M2

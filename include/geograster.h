@@ -10,12 +10,15 @@
  * Conventions
  *  - Every pointer is a DEVICE pointer (hipMalloc / torch tensor .data_ptr()) unless its name ends in _h.
  *  - The caller allocates and owns all inputs and outputs.  The library allocates only per-context scratch
- *    (bin lists, per-face winners), grown lazily, freed by gr_ctx_destroy.
+ *    (bin lists, per-face winners, one arena for the stage calls), grown lazily, freed by gr_ctx_destroy.
  *  - All work is enqueued on `stream` (a hipStream_t passed as void*; NULL = the default stream) and is
  *    asynchronous.  No hidden synchronisation except: gr_ctx_destroy, gr_mesh_upload (index validation) and
  *    scratch growth (hipMalloc/hipFree when a larger batch, image or mesh is first seen).
  *  - Return value: 0 (GR_OK) or a negative GR_E* code; text via gr_last_error().  No C++ exception crosses the ABI.
  *  - A context belongs to one (device, host thread); distinct contexts are independent.
+ *  - Calls of one context on different streams may be issued back to back: the stage calls share one scratch arena per
+ *    context ("context scratch" below), and the library orders their use of it -- a call that finds the arena's last user
+ *    on another stream waits for that stream first.  On one stream nothing is added.
  */
 #ifndef GEOGRASTER_H
 #define GEOGRASTER_H
@@ -508,7 +511,7 @@ int gr_face_polygon_index(gr_ctx *ctx, const int64_t *verts_q, int64_t V, const 
  * the perpendicular case cross^2 <= D^2 |e|^2 through a 256-bit product.  Edges are visited in table order; a point stops being
  * tested against the buffer once an edge is within D and against everything once it is contained.
  * stats: GR_PIR_STAT_WORDS uint64 on the device.  GR_EINVAL (the message names gr_points_in_region): null arrays, negative sizes, D
- * outside [0, 2^40).  R = 0 or P = 0: an all-zero mask.  Only enqueues work on `stream`; needs no uploaded mesh; 64 bytes of
+ * outside [0, 2^40).  R = 0 or P = 0: an all-zero mask.  Only enqueues work on `stream`; needs no uploaded mesh; 32 bytes of
  * context scratch.  Added without a GR_VERSION bump. */
 enum {
   GR_PIR_STAT_INSIDE = 0,       /* points in the region                                                              */

@@ -315,11 +315,15 @@ def test_header_binding_and_source_name_the_new_call():
     assert len(definition.split(",")) == n_args
     kernels = ("k_outline_canon", "k_outline_face_edges", "k_outline_cancel", "k_outline_successor", "k_outline_round", "k_outline_emit_rings")
     assert all(k in source and k in internal for k in kernels)
-    assert "outline_a" in internal and "outline_b" in internal and "meshes/meshes.py:1308-1445" in header
+    assert "Scratch stage;" in internal and "Scratch stage_b;" in internal and "meshes/meshes.py:1308-1445" in header
+    call = source[source.index(f"int {name}(gr_ctx *c,"):]       # the call has two blocks: one in each arena member
+    assert "stage_acquire(c, c->stage, " in call and "stage_acquire(c, c->stage_b, " in call
     assert (_hip.GR_OUTL_STAT_NO_CLASS, _hip.GR_OUTL_STAT_ZERO_AREA, _hip.GR_OUTL_STAT_TURNED, _hip.GR_OUTL_STAT_CANCELLED,
             _hip.GR_OUTL_STAT_MULTI, _hip.GR_OUTL_STAT_BAD_FACES, _hip.GR_OUTL_STAT_WORDS, _hip.GR_OUTL_MAX_CLASSES) == (0, 1, 2, 3, 4, 5, 8, 65535)
     assert "hipcub::DeviceRadixSort::SortPairs" in source and "hipcub::DeviceScan::ExclusiveSum" in source
-    outline_part = source[source.index("gr_class_outlines: the outline rings"):source.index("inline size_t up256")]
+    outline_start = source.index("gr_class_outlines: the outline rings")
+    outline_part = source[outline_start:source.index('extern "C" {', outline_start)]       # every outline kernel and device helper
+    assert all(outline_part.count(k + "(") >= 1 for k in kernels) and "k_outline_ring_words(" in outline_part
     assert not re.search(r"\b(double|float)\b", outline_part)      # no floating point anywhere in the call
     assert any(p.name == "polygons.hip" for p in build.SOURCES) and callable(_hip.HipRaster.class_outlines)
     assert callable(TexturedPhotogrammetryMesh.face_label_outlines) and callable(TexturedPhotogrammetryMesh.export_face_labels_vector)
