@@ -598,6 +598,37 @@ class HipRaster:
             return array.to(device=self.device, dtype=dtype).contiguous()
         return torch.as_tensor(np.ascontiguousarray(array)).to(device=self.device, dtype=dtype).contiguous()
 
+    def _ring_table(self, ring_vertices, ring_offsets, ring_polygon, polygon_boxes, ring_is_hole=None):
+        """The snapped ring table of `PlanarPolygons.snapped` on this device, checked: (ring vertices (N, 2) int64, offsets
+        (R + 1,) int64, polygons (R,) int32, boxes (P, 4) int64, hole flags (R,) int32 or None, N, R, P)."""
+        torch = _torch()
+        rv_t = self._dev(ring_vertices, torch.int64)
+        off_t = self._dev(ring_offsets, torch.int64)
+        rp_t = self._dev(ring_polygon, torch.int32)
+        rh_t = None if ring_is_hole is None else self._dev(ring_is_hole, torch.int32)
+        box_t = self._dev(polygon_boxes, torch.int64)
+        R, P = int(rp_t.shape[0]), int(box_t.shape[0])
+        if rv_t.ndim != 2 or rv_t.shape[1] != 2 or tuple(off_t.shape) != (R + 1,) or box_t.ndim != 2 or box_t.shape[1] != 4 or \
+                (rh_t is not None and tuple(rh_t.shape) != (R,)):
+            holes = () if rh_t is None else (rh_t,)
+            got = ", ".join(str(tuple(t.shape)) for t in (rv_t, off_t, rp_t) + holes)
+            raise ValueError(f"ring table must be (N, 2) vertices, (R + 1,) offsets, (R,) polygons{', (R,) hole flags' if holes else ''} "
+                             f"and (P, 4) boxes, got {got} and {tuple(box_t.shape)}")
+        return rv_t, off_t, rp_t, box_t, rh_t, int(rv_t.shape[0]), R, P
+
+    def _mesh_2d(self, verts_q, faces):
+        """(verts_q (V, 2) int64, faces (F, 3) int32) on this device, checked."""
+        torch = _torch()
+        vq_t, f_t = self._dev(verts_q, torch.int64), self._dev(faces, torch.int32)
+        if vq_t.ndim != 2 or vq_t.shape[1] != 2 or f_t.ndim != 2 or f_t.shape[1] != 3:
+            raise ValueError(f"vertices must be (V, 2) and faces (F, 3), got {tuple(vq_t.shape)} and {tuple(f_t.shape)}")
+        return vq_t, f_t
+
+    @staticmethod
+    def _raise_bad_faces(name, n_bad, V):
+        if n_bad:
+            raise ValueError(f"{name}: {n_bad} faces name a vertex outside [0, {V})")
+
     def set_profiling(self, enabled: bool):
         self._check(self.lib.gr_set_profiling(self._ctx, 1 if enabled else 0), "gr_set_profiling")
 
@@ -921,24 +952,16 @@ class HipRaster:
         tri_t = self._dev(tri, torch.int64)
         cls_t = self._dev(face_class, torch.int32)
         w_t = self._dev(face_weight, torch.float64)
-        rv_t = self._dev(ring_vertices, torch.int64)
-        off_t = self._dev(ring_offsets, torch.int64)
-        rp_t = self._dev(ring_polygon, torch.int32)
-        rh_t = self._dev(ring_is_hole, torch.int32)
-        box_t = self._dev(polygon_boxes, torch.int64)
-        F, R, P, C = int(cls_t.shape[0]), int(rp_t.shape[0]), int(box_t.shape[0]), int(n_classes)
+        F, C = int(cls_t.shape[0]), int(n_classes)
         if tri_t.ndim != 2 or tuple(tri_t.shape) != (F, 6) or tuple(w_t.shape) != (F,):
             raise ValueError(f"faces must be (F, 6) corners, (F,) classes and (F,) weights, got {tuple(tri_t.shape)}, "
                              f"{tuple(cls_t.shape)} and {tuple(w_t.shape)}")
-        if rv_t.ndim != 2 or rv_t.shape[1] != 2 or tuple(off_t.shape) != (R + 1,) or tuple(rh_t.shape) != (R,) or \
-                box_t.ndim != 2 or box_t.shape[1] != 4:
-            raise ValueError(f"ring table must be (N, 2) vertices, (R + 1,) offsets, (R,) polygons, (R,) hole flags and (P, 4) "
-                             f"boxes, got {tuple(rv_t.shape)}, {tuple(off_t.shape)}, {tuple(rp_t.shape)}, {tuple(rh_t.shape)} and "
-                             f"{tuple(box_t.shape)}")
+        rv_t, off_t, rp_t, box_t, rh_t, n_rv, R, P = self._ring_table(ring_vertices, ring_offsets, ring_polygon, polygon_boxes,
+                                                                      ring_is_hole)
         weights = torch.empty((P, C), dtype=torch.float64, device=self.device)
         stats = torch.empty((GR_POLY_STAT_WORDS,), dtype=torch.int64, device=self.device)
         self._call("gr_polygon_class_weights", tri_t.data_ptr(), cls_t.data_ptr(), w_t.data_ptr(), F, rv_t.data_ptr(),
-                   int(rv_t.shape[0]), off_t.data_ptr(), rp_t.data_ptr(), rh_t.data_ptr(), R, box_t.data_ptr(), P,
+                   n_rv, off_t.data_ptr(), rp_t.data_ptr(), rh_t.data_ptr(), R, box_t.data_ptr(), P,
                    GR_POLY_WITHIN if within else GR_POLY_OVERLAY, C, weights.data_ptr(), stats.data_ptr(), self._stream())
         return weights, stats
 
@@ -953,22 +976,12 @@ class HipRaster:
         labelled, longest cell list met, faces with a vertex index outside [0, V)).  `check` (default) reads the statistics
         back and raises ValueError when a face names a vertex that does not exist; check=False only enqueues."""
         torch = _torch()
-        vq_t = self._dev(verts_q, torch.int64)
-        f_t = self._dev(faces, torch.int32)
-        rv_t = self._dev(ring_vertices, torch.int64)
-        off_t = self._dev(ring_offsets, torch.int64)
-        rp_t = self._dev(ring_polygon, torch.int32)
-        box_t = self._dev(polygon_boxes, torch.int64)
+        vq_t, f_t = self._mesh_2d(verts_q, faces)
+        rv_t, off_t, rp_t, box_t, _, n_rv, R, P = self._ring_table(ring_vertices, ring_offsets, ring_polygon, polygon_boxes)
         grid, cell_offsets, cell_polygons = cell_table
         grid = [int(v) for v in np.asarray(grid.cpu() if hasattr(grid, "detach") else grid).reshape(-1)]
         co_t = self._dev(cell_offsets, torch.int64)
         cp_t = self._dev(cell_polygons, torch.int32)
-        if vq_t.ndim != 2 or vq_t.shape[1] != 2 or f_t.ndim != 2 or f_t.shape[1] != 3:
-            raise ValueError(f"vertices must be (V, 2) and faces (F, 3), got {tuple(vq_t.shape)} and {tuple(f_t.shape)}")
-        R, P = int(rp_t.shape[0]), int(box_t.shape[0])
-        if rv_t.ndim != 2 or rv_t.shape[1] != 2 or tuple(off_t.shape) != (R + 1,) or box_t.ndim != 2 or box_t.shape[1] != 4:
-            raise ValueError(f"ring table must be (N, 2) vertices, (R + 1,) offsets, (R,) polygons and (P, 4) boxes, got "
-                             f"{tuple(rv_t.shape)}, {tuple(off_t.shape)}, {tuple(rp_t.shape)} and {tuple(box_t.shape)}")
         if len(grid) != 6:
             raise ValueError(f"the cell grid is (x0, y0, cell_w, cell_h, nx, ny), got {len(grid)} values")
         x0, y0, cw, ch, nx, ny = grid
@@ -981,12 +994,10 @@ class HipRaster:
         out = torch.empty((F,), dtype=torch.int32, device=self.device)
         stats = torch.empty((GR_FPI_STAT_WORDS,), dtype=torch.int64, device=self.device)
         self._call("gr_face_polygon_index", vq_t.data_ptr(), int(vq_t.shape[0]), f_t.data_ptr(), F, rv_t.data_ptr(),
-                   int(rv_t.shape[0]), off_t.data_ptr(), rp_t.data_ptr(), R, box_t.data_ptr(), P, x0, y0, cw, ch, nx, ny,
+                   n_rv, off_t.data_ptr(), rp_t.data_ptr(), R, box_t.data_ptr(), P, x0, y0, cw, ch, nx, ny,
                    co_t.data_ptr(), cp_t.data_ptr(), int(cp_t.shape[0]), out.data_ptr(), stats.data_ptr(), self._stream())
         if check:
-            n_bad = int(stats[GR_FPI_STAT_BAD_FACES].item())
-            if n_bad:
-                raise ValueError(f"gr_face_polygon_index: {n_bad} faces name a vertex outside [0, {int(vq_t.shape[0])})")
+            self._raise_bad_faces("gr_face_polygon_index", int(stats[GR_FPI_STAT_BAD_FACES].item()), int(vq_t.shape[0]))
         return out, stats
 
     # -- region of interest: points in a buffered union of polygon rows, the sub-mesh they select ----------------------
@@ -998,23 +1009,16 @@ class HipRaster:
         formed).  Only enqueues."""
         torch = _torch()
         pq_t = self._dev(points_q, torch.int64)
-        rv_t = self._dev(ring_vertices, torch.int64)
-        off_t = self._dev(ring_offsets, torch.int64)
-        rp_t = self._dev(ring_polygon, torch.int32)
-        box_t = self._dev(polygon_boxes, torch.int64)
         if pq_t.ndim != 2 or pq_t.shape[1] != 2:
             raise ValueError(f"points must be (N, 2), got {tuple(pq_t.shape)}")
-        R, P = int(rp_t.shape[0]), int(box_t.shape[0])
-        if rv_t.ndim != 2 or rv_t.shape[1] != 2 or tuple(off_t.shape) != (R + 1,) or box_t.ndim != 2 or box_t.shape[1] != 4:
-            raise ValueError(f"ring table must be (N, 2) vertices, (R + 1,) offsets, (R,) polygons and (P, 4) boxes, got "
-                             f"{tuple(rv_t.shape)}, {tuple(off_t.shape)}, {tuple(rp_t.shape)} and {tuple(box_t.shape)}")
+        rv_t, off_t, rp_t, box_t, _, n_rv, R, P = self._ring_table(ring_vertices, ring_offsets, ring_polygon, polygon_boxes)
         D = int(buffer_steps)
         if not 0 <= D < 2 ** 40:
             raise ValueError(f"gr_points_in_region: buffer D={D} outside [0, 2^40) grid steps")
         N = int(pq_t.shape[0])
         mask = torch.empty((N,), dtype=torch.uint8, device=self.device)
         stats = torch.empty((GR_PIR_STAT_WORDS,), dtype=torch.int64, device=self.device)
-        self._call("gr_points_in_region", pq_t.data_ptr(), N, rv_t.data_ptr(), int(rv_t.shape[0]), off_t.data_ptr(),
+        self._call("gr_points_in_region", pq_t.data_ptr(), N, rv_t.data_ptr(), n_rv, off_t.data_ptr(),
                    rp_t.data_ptr(), R, box_t.data_ptr(), P, D, mask.data_ptr(), stats.data_ptr(), self._stream())
         return mask.to(torch.bool), stats
 
@@ -1038,8 +1042,8 @@ class HipRaster:
         self._call("gr_submesh_extract", m_t.data_ptr(), V, f_t.data_ptr(), F, face_ids.data_ptr(), point_ids.data_ptr(),
                    new_faces.data_ptr(), counts.data_ptr(), self._stream())
         n_faces, n_points, n_bad = (int(v) for v in counts.cpu())
-        if check and n_bad:
-            raise ValueError(f"gr_submesh_extract: {n_bad} faces name a vertex outside [0, {V})")
+        if check:
+            self._raise_bad_faces("gr_submesh_extract", n_bad, V)
         return face_ids[:n_faces], point_ids[:n_points], new_faces[:n_faces], counts
 
     # -- class outlines: the rings around the faces of every class -------------------------------------------------
@@ -1052,11 +1056,8 @@ class HipRaster:
         call repeated.  The library synchronises: the result is complete on return.  `check` (default) raises ValueError when a
         face names a vertex that does not exist."""
         torch = _torch()
-        vq_t = self._dev(verts_q, torch.int64)
-        f_t = self._dev(faces, torch.int32)
+        vq_t, f_t = self._mesh_2d(verts_q, faces)
         c_t = self._dev(face_class, torch.int32).reshape(-1)
-        if vq_t.ndim != 2 or vq_t.shape[1] != 2 or f_t.ndim != 2 or f_t.shape[1] != 3:
-            raise ValueError(f"vertices must be (V, 2) and faces (F, 3), got {tuple(vq_t.shape)} and {tuple(f_t.shape)}")
         V, F = int(vq_t.shape[0]), int(f_t.shape[0])
         if int(c_t.shape[0]) != F:
             raise ValueError(f"{F} faces need {F} classes, got {int(c_t.shape[0])}")
@@ -1084,9 +1085,7 @@ class HipRaster:
                 continue
             self._check(rc, "gr_class_outlines")
             if check:
-                n_bad = int(stats[GR_OUTL_STAT_BAD_FACES].item())
-                if n_bad:
-                    raise ValueError(f"gr_class_outlines: {n_bad} faces name a vertex outside [0, {V})")
+                self._raise_bad_faces("gr_class_outlines", int(stats[GR_OUTL_STAT_BAD_FACES].item()), V)
             if cap == 0:
                 ring_offsets.zero_()
             return canon, ring_vertices[:E], ring_offsets[:R + 1], ring_class[:R], stats
@@ -1152,9 +1151,7 @@ class HipRaster:
                        float("nan") if ground_id is None else float(ground_id),
                        GR_RS_FLAG_ONLY_EXISTING if only_existing else 0, stats.data_ptr(), self._stream())
             if check:
-                n_bad = int(stats[GR_RS_STAT_BAD_FACES].item())
-                if n_bad:
-                    raise ValueError(f"gr_sample_raster: {n_bad} faces name a vertex outside [0, {V})")
+                self._raise_bad_faces("gr_sample_raster", int(stats[GR_RS_STAT_BAD_FACES].item()), V)
         return values, height, lab_t, stats
 
     # -- projection / aggregation --------------------------------------------------------------------------------

@@ -4,7 +4,9 @@
 // a buffered union of polygon rows (gr_points_in_region) and the sub-mesh of the faces that touch them (gr_submesh_extract), at
 // the end of the file; DESIGN.md "Region of interest"; and the outline rings of every class of a per-face labelling
 // (gr_class_outlines; DESIGN.md "Class outlines"), behind them.  None needs an uploaded mesh: the caller hands over snapped integer
-// coordinates.
+// coordinates.  The pieces the calls share are defined once: the ring span, the even-odd crossing rule, the checked face load and
+// the statistics reductions (one integer atomic per wave and word) in geom_dev.hpp, the host's check of a ring table
+// (check_ring_table) in front of the entry points.
 //
 // gr_polygon_class_weights:
 // Shape: face-major, one face per lane.  The ring table is walked WAVE-UNIFORMLY: ring r, its polygon, the polygon's box and
@@ -20,24 +22,18 @@
 //                    triangle's first vertex
 #include <hipcub/hipcub.hpp>
 
+#include "geom_dev.hpp"
 #include "gr_internal.hpp"
 
 using namespace grimpl;
 
 namespace {
 
-typedef __int128 i128;
-
 struct PolyArgs {   // the scalars of a call; the arrays are kernel parameters of their own, so that they can be __restrict__
   int64_t F;
   int64_t n_rv;
   int R, P, C, mode;
 };
-
-__device__ __forceinline__ i128 orient(int64_t ax, int64_t ay, int64_t bx, int64_t by, int64_t cx, int64_t cy) {
-  return (i128)(bx - ax) * (i128)(cy - ay) - (i128)(by - ay) * (i128)(cx - ax);   // |coordinates| <= 3 * 2^40: |products| < 2^87
-}
-__device__ __forceinline__ int sgn(i128 v) { return v > 0 ? 1 : (v < 0 ? -1 : 0); }
 
 // v >= 0 as a double: exact below 2^64 when v has at most 53 significant bits, within an ulp above
 __device__ __forceinline__ double to_double(i128 v) {
@@ -120,7 +116,8 @@ template <int K> __device__ __forceinline__ void clip_close(ClipState &S) {   //
   }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {   // butterfly: every lane ends with the same sum, in a fixed order
+// butterfly: every lane ends with the same sum, in a fixed order.  For the weights alone (flush_wave); counts are integers (stat_add)
+__device__ __forceinline__ double wave_sum(double v) {
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
   return v;
 }
@@ -199,9 +196,8 @@ __global__ __launch_bounds__(256) void k_polygon_weights(const int64_t *__restri
         tested += in_poly ? 1 : 0;
       }
     }
-    int64_t i0 = roff[r], i1 = roff[r + 1];
-    i0 = min(max(i0, (int64_t)0), a.n_rv); i1 = min(max(i1, i0), a.n_rv);   // a bad offset table reads nothing outside the vertices
-    const int64_t n = i1 - i0;
+    int64_t i0;
+    const int64_t n = ring_span(roff, r, a.n_rv, i0);
     largest = max(largest, (unsigned long long)n);
     if (cur < 0 || n < 3 || !__ballot(in_poly)) continue;
     const int64_t *v = rv + i0 * 2;
@@ -210,11 +206,7 @@ __global__ __launch_bounds__(256) void k_polygon_weights(const int64_t *__restri
       int64_t ax = v[2 * (n - 1)], ay = v[2 * (n - 1) + 1];
       for (int64_t i = 0; i < n; ++i) {
         const int64_t bx = v[2 * i], by = v[2 * i + 1];
-        const int64_t a3y = 3 * ay, b3y = 3 * by;
-        if ((a3y > c3y) != (b3y > c3y)) {   // even-odd, half-open in y; the centroid is on no edge unless `meets`
-          const i128 o = orient(3 * ax, a3y, 3 * bx, b3y, c3x, c3y);
-          parity ^= ((o > 0) == (b3y > a3y)) ? 1 : 0;
-        }
+        edge_crossing<false>(3 * ax, 3 * ay, 3 * bx, 3 * by, c3x, c3y, parity);   // the centroid is on no edge unless `meets`
         // the edge's box against the face's: an edge that stays at or beyond a side of the box cannot reach the open interior
         if (!meets && max(ax, bx) > xlo && min(ax, bx) < xhi && max(ay, by) > ylo && min(ay, by) < yhi)
           meets = edge_meets_interior(t, ax, ay, bx, by);
@@ -234,13 +226,9 @@ __global__ __launch_bounds__(256) void k_polygon_weights(const int64_t *__restri
   }
   flush();
 
-  // statistics: one atomic per wave and word
-  const double ts = wave_sum((double)tested), cs = wave_sum((double)contributing);   // < 2^53: exact
-  if (lane == 0) {
-    if (ts > 0.0) atomicAdd(&stats[GR_POLY_STAT_TESTED], (unsigned long long)ts);
-    if (cs > 0.0) atomicAdd(&stats[GR_POLY_STAT_CONTRIBUTING], (unsigned long long)cs);
-    if (f == 0) atomicMax(&stats[GR_POLY_STAT_LARGEST_RING], largest);
-  }
+  stat_add(stats, GR_POLY_STAT_TESTED, tested, lane);
+  stat_add(stats, GR_POLY_STAT_CONTRIBUTING, contributing, lane);
+  if (f == 0) atomicMax(&stats[GR_POLY_STAT_LARGEST_RING], largest);   // the same in every lane of every wave: one writer
 }
 
 // ---- gr_face_polygon_index: the polygon row each face CENTRE lies in (DESIGN.md "Vector textures", V3-V5) -------------------------
@@ -250,13 +238,8 @@ struct FaceIndexArgs {
   int R, P, nx, ny;
 };
 
-__device__ __forceinline__ double wave_max(double v) {
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  return v;
-}
-
-// V4: is (px, py) = 3 x centre in the closed region of row p?  On an edge or vertex of any ring, or an odd count of crossings right
-// of the point over all rings.  The rings of a row are consecutive in rpoly (non-decreasing): the first one by binary search.
+// V4: is (px, py) = 3 x centre in the closed region of row p?  On the boundary of any ring, or an odd parity over all rings
+// (edge_crossing).  The rings of a row are consecutive in rpoly (non-decreasing): the first one by binary search.
 __device__ __forceinline__ bool row_contains(const int64_t *__restrict__ rv, const int64_t *__restrict__ roff,
                                              const int32_t *__restrict__ rpoly, const FaceIndexArgs &a, int p, int64_t px, int64_t py) {
   int lo = 0, hi = a.R;
@@ -266,21 +249,14 @@ __device__ __forceinline__ bool row_contains(const int64_t *__restrict__ rv, con
   }
   int parity = 0;
   for (int r = lo; r < a.R && rpoly[r] == p; ++r) {
-    int64_t i0 = roff[r], i1 = roff[r + 1];
-    i0 = min(max(i0, (int64_t)0), a.n_rv); i1 = min(max(i1, i0), a.n_rv);   // a bad offset table reads nothing outside the vertices
-    const int64_t n = i1 - i0;
+    int64_t i0;
+    const int64_t n = ring_span(roff, r, a.n_rv, i0);
     if (n < 3) continue;
     const int64_t *v = rv + i0 * 2;
     int64_t ax = 3 * v[2 * (n - 1)], ay = 3 * v[2 * (n - 1) + 1];
     for (int64_t i = 0; i < n; ++i) {
       const int64_t bx = 3 * v[2 * i], by = 3 * v[2 * i + 1];
-      const bool cross = (ay <= py) != (by <= py);   // half-open in y: a horizontal edge never counts
-      const bool in_box = min(ax, bx) <= px && px <= max(ax, bx) && min(ay, by) <= py && py <= max(ay, by);
-      if (cross || in_box) {
-        const i128 o = orient(ax, ay, bx, by, px, py);
-        if (o == 0 && in_box) return true;             // on the boundary (a crossing edge with o == 0 holds the point in its box)
-        if (cross && (o > 0) == (by > ay)) parity ^= 1;   // strictly left of the edge taken upwards
-      }
+      if (edge_crossing<true>(ax, ay, bx, by, px, py, parity)) return true;
       ax = bx; ay = by;
     }
   }
@@ -298,13 +274,13 @@ __global__ __launch_bounds__(256) void k_face_polygon_index(const int64_t *__res
                                                             FaceIndexArgs a) {
   const int lane = (int)(threadIdx.x & 63);
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  unsigned long long tested = 0, labelled = 0, longest = 0, bad = 0;
+  unsigned long long tested = 0, longest = 0;
+  bool labelled = false, bad = false;
   if (f < a.F) {
-    const int64_t v0 = faces[f * 3], v1 = faces[f * 3 + 1], v2 = faces[f * 3 + 2];
+    int64_t v0, v1, v2;
     int found = -1;
-    if (v0 < 0 || v0 >= a.V || v1 < 0 || v1 >= a.V || v2 < 0 || v2 >= a.V) {
-      bad = 1;   // reported, never dereferenced
-    } else {
+    bad = !load_face(faces, f, a.V, v0, v1, v2);
+    if (!bad) {
       const int64_t px = vq[v0 * 2] + vq[v1 * 2] + vq[v2 * 2], py = vq[v0 * 2 + 1] + vq[v1 * 2 + 1] + vq[v2 * 2 + 1];
       const int64_t dx = px - a.gx0, dy = py - a.gy0;
       const int64_t ix = dx >= 0 ? dx / a.cw : -1, iy = dy >= 0 ? dy / a.ch : -1;
@@ -324,17 +300,12 @@ __global__ __launch_bounds__(256) void k_face_polygon_index(const int64_t *__res
       }
     }
     out[f] = found;
-    labelled = found >= 0 ? 1 : 0;
+    labelled = found >= 0;
   }
-  // statistics: one atomic per wave and word
-  const double ts = wave_sum((double)tested), ls = wave_sum((double)labelled), bs = wave_sum((double)bad);   // < 2^53: exact
-  const double lm = wave_max((double)longest);
-  if (lane == 0) {
-    if (ts > 0.0) atomicAdd(&stats[GR_FPI_STAT_TESTED], (unsigned long long)ts);
-    if (ls > 0.0) atomicAdd(&stats[GR_FPI_STAT_LABELLED], (unsigned long long)ls);
-    if (lm > 0.0) atomicMax(&stats[GR_FPI_STAT_LONGEST_LIST], (unsigned long long)lm);
-    if (bs > 0.0) atomicAdd(&stats[GR_FPI_STAT_BAD_FACES], (unsigned long long)bs);
-  }
+  stat_add(stats, GR_FPI_STAT_TESTED, tested, lane);
+  stat_count(stats, GR_FPI_STAT_LABELLED, labelled, lane);
+  stat_max(stats, GR_FPI_STAT_LONGEST_LIST, longest, lane);
+  stat_count(stats, GR_FPI_STAT_BAD_FACES, bad, lane);
 }
 
 // ---- gr_points_in_region: is a point in the union of the rows' closed regions, grown by D?  (DESIGN.md "Region of interest", Q3-Q4) ----
@@ -425,9 +396,8 @@ __global__ __launch_bounds__(256) void k_points_in_region(const int64_t *__restr
                  py <= b[3] + D;
       }
     }
-    int64_t i0 = roff[r], i1 = roff[r + 1];
-    i0 = min(max(i0, (int64_t)0), a.n_rv); i1 = min(max(i1, i0), a.n_rv);   // a bad offset table reads nothing outside the vertices
-    const int64_t n = i1 - i0;
+    int64_t i0;
+    const int64_t n = ring_span(roff, r, a.n_rv, i0);
     if (cur < 0 || n < 3 || !__ballot(in_row && !contained)) continue;
     const int64_t *v = rv + i0 * 2;
     int64_t ax = v[2 * (n - 1)], ay = v[2 * (n - 1) + 1];
@@ -435,14 +405,7 @@ __global__ __launch_bounds__(256) void k_points_in_region(const int64_t *__restr
       const int64_t bx = v[2 * i], by = v[2 * i + 1];
       if (in_row && !contained) {
         const int64_t exlo = min(ax, bx), exhi = max(ax, bx), eylo = min(ay, by), eyhi = max(ay, by);
-        // Q3: crossings right of the point, half-open in y; a point on the edge is contained at once
-        const bool cross = (ay <= py) != (by <= py);
-        const bool in_box = exlo <= px && px <= exhi && eylo <= py && py <= eyhi;
-        if (cross || in_box) {
-          const i128 o = orient(ax, ay, bx, by, px, py);
-          if (o == 0 && in_box) contained = true;
-          if (cross && (o > 0) == (by > ay)) parity ^= 1;
-        }
+        if (edge_crossing<true>(ax, ay, bx, by, px, py, parity)) contained = true;   // Q3; a point on the edge is contained at once
         // Q4: the distance to the closed edge against D, for an edge whose box grown by D holds the point
         if (D > 0 && !near && !contained && px >= exlo - D && px <= exhi + D && py >= eylo - D && py <= eyhi + D) {
           const int64_t ux = px - ax, uy = py - ay, ex = bx - ax, ey = by - ay;   // |.| < 2^42: products below 2^84
@@ -466,14 +429,9 @@ __global__ __launch_bounds__(256) void k_points_in_region(const int64_t *__restr
   if (in_row && (parity & 1)) contained = true;
   if (idx < a.N) mask[idx] = (contained || near) ? 1 : 0;
 
-  // statistics: one atomic per wave and word
-  const double is = wave_sum((contained || near) ? 1.0 : 0.0), bs = wave_sum((near && !contained) ? 1.0 : 0.0);
-  const double ws = wave_sum((double)wide);   // < 2^53: exact
-  if (lane == 0) {
-    if (is > 0.0) atomicAdd(&stats[GR_PIR_STAT_INSIDE], (unsigned long long)is);
-    if (bs > 0.0) atomicAdd(&stats[GR_PIR_STAT_BUFFER_ONLY], (unsigned long long)bs);
-    if (ws > 0.0) atomicAdd(&stats[GR_PIR_STAT_WIDE], (unsigned long long)ws);
-  }
+  stat_count(stats, GR_PIR_STAT_INSIDE, contained || near, lane);
+  stat_count(stats, GR_PIR_STAT_BUFFER_ONLY, near && !contained, lane);
+  stat_add(stats, GR_PIR_STAT_WIDE, wide, lane);
 }
 
 // ---- gr_submesh_extract: the faces with a vertex in the mask, the vertices they use, renumbered in order (Q5, Q6) ------------------
@@ -483,20 +441,18 @@ __global__ __launch_bounds__(256) void k_submesh_flags(const uint8_t *__restrict
                                                        unsigned long long *__restrict__ counts) {
   const int lane = (int)(threadIdx.x & 63);
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  double bad = 0.0;
+  bool bad = false;
   if (f < F) {
-    const int64_t v0 = faces[f * 3], v1 = faces[f * 3 + 1], v2 = faces[f * 3 + 2];
+    int64_t v0, v1, v2;
     int keep = 0;
-    if (v0 < 0 || v0 >= V || v1 < 0 || v1 >= V || v2 < 0 || v2 >= V) {
-      bad = 1.0;
-    } else {
+    bad = !load_face(faces, f, V, v0, v1, v2);
+    if (!bad) {
       keep = (mask[v0] | mask[v1] | mask[v2]) ? 1 : 0;
       if (keep) { vused[v0] = 1; vused[v1] = 1; vused[v2] = 1; }   // every writer stores the same value
     }
     fflag[f] = keep;
   }
-  const double bs = wave_sum(bad);
-  if (lane == 0 && bs > 0.0) atomicAdd(&counts[2], (unsigned long long)bs);
+  stat_count(counts, 2, bad, lane);
 }
 
 // fpos, vpos: the exclusive sums of fflag, vused.  One thread per face and per vertex.
@@ -531,11 +487,6 @@ enum {   // 64-bit words at the front of the scratch: counts the host reads back
   GR_OUTL_HEAD_EDGES = 1,   // surviving copies: slots
   GR_OUTL_HEAD_WORDS = 32   // 256 bytes
 };
-
-__device__ __forceinline__ void outline_count(unsigned long long *stats, int word, bool one, int lane) {   // one atomic per wave
-  const unsigned long long m = __ballot(one);
-  if (lane == 0 && m) atomicAdd(&stats[word], (unsigned long long)__popcll(m));
-}
 
 // key [V] = y of vertex i; idx [V] = i
 __global__ __launch_bounds__(256) void k_outline_vertex_keys(const int64_t *__restrict__ vq, int64_t V, int64_t *__restrict__ key,
@@ -578,15 +529,13 @@ __global__ __launch_bounds__(256) void k_outline_face_edges(const int64_t *__res
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
   bool bad = false, no_class = false, flat = false, turned = false;
   if (f < F) {
-    const int64_t v0 = faces[f * 3], v1 = faces[f * 3 + 1], v2 = faces[f * 3 + 2];
+    int64_t v0, v1, v2;
+    bad = !load_face(faces, f, V, v0, v1, v2);
     const int cls = face_class[f];
     int64_t a = 0, b = 0, c = 0;
     bool live = false;
-    if (v0 < 0 || v0 >= V || v1 < 0 || v1 >= V || v2 < 0 || v2 >= V) {
-      bad = true;   // reported, never dereferenced
-    } else if (cls < 0 || cls >= C) {
-      no_class = true;
-    } else {
+    no_class = !bad && (cls < 0 || cls >= C);
+    if (!bad && !no_class) {
       a = canon[v0]; b = canon[v1]; c = canon[v2];
       const i128 o = orient(vq[a * 2], vq[a * 2 + 1], vq[b * 2], vq[b * 2 + 1], vq[c * 2], vq[c * 2 + 1]);
       flat = o == 0;
@@ -600,10 +549,10 @@ __global__ __launch_bounds__(256) void k_outline_face_edges(const int64_t *__res
     pair[f * 3 + 2] = live ? ((unsigned long long)c << 31 | (unsigned long long)a) : 0ull;
     cl[f * 3] = k; cl[f * 3 + 1] = k; cl[f * 3 + 2] = k;
   }
-  outline_count(stats, GR_OUTL_STAT_NO_CLASS, no_class, lane);
-  outline_count(stats, GR_OUTL_STAT_ZERO_AREA, flat, lane);
-  outline_count(stats, GR_OUTL_STAT_TURNED, turned, lane);
-  outline_count(stats, GR_OUTL_STAT_BAD_FACES, bad, lane);
+  stat_count(stats, GR_OUTL_STAT_NO_CLASS, no_class, lane);
+  stat_count(stats, GR_OUTL_STAT_ZERO_AREA, flat, lane);
+  stat_count(stats, GR_OUTL_STAT_TURNED, turned, lane);
+  stat_count(stats, GR_OUTL_STAT_BAD_FACES, bad, lane);
 }
 
 // pair, cl [n] sorted by (class, from, to).  flag [n] = 1 where a run of equal real edges starts.
@@ -655,9 +604,8 @@ __global__ __launch_bounds__(256) void k_outline_cancel(const unsigned long long
     if (a < b) n_cancel = n1 < n2 ? n1 : n2;   // once per unordered pair
     multi = n > 1;
   }
-  for (int o = 32; o >= 1; o >>= 1) n_cancel += __shfl_xor(n_cancel, o);   // all cancelled pairs together are fewer than 2^31
-  if (lane == 0 && n_cancel > 0) atomicAdd(&stats[GR_OUTL_STAT_CANCELLED], (unsigned long long)n_cancel);
-  outline_count(stats, GR_OUTL_STAT_MULTI, multi, lane);
+  stat_add_u32(stats, GR_OUTL_STAT_CANCELLED, (uint32_t)n_cancel, lane);   // all cancelled pairs together are fewer than 2^31
+  stat_count(stats, GR_OUTL_STAT_MULTI, multi, lane);
 }
 // soff [run]: the exclusive sum of surv, the first slot of the run.  Writes the slots: efrom, ecls, and the key (class, to) with the
 // slot as its value for the sort of X5.
@@ -730,6 +678,17 @@ __global__ __launch_bounds__(256) void k_outline_emit_rings(const int32_t *__res
 
 }  // namespace
 
+// The ring table as every call here takes it: rv [n_rv][2], roff [R + 1], rpoly [R], pbox [P][4].  Its ranges and its pointers; the
+// hole flags are the weights call's own.  The boxes are needed with a row; boxes_with_rings: with a ring (the weights call, which
+// launches nothing without rings and has always taken the boxes so).
+static int check_ring_table(gr_ctx *c, const char *name, int64_t n_rv, int64_t R, int64_t P, const int64_t *rv, const int64_t *roff,
+                            const int32_t *rpoly, const int64_t *pbox, bool boxes_with_rings = false) {
+  if (R < 0 || P < 0 || n_rv < 0 || R > 0x7FFFFFFF || P > 0x7FFFFFFF)
+    return fail(c, GR_EINVAL, "%s: bad ring table R=%lld P=%lld ring vertices=%lld", name, (long long)R, (long long)P, (long long)n_rv);
+  if (((boxes_with_rings ? R : P) > 0 && !pbox) || (R > 0 && (!roff || !rpoly || (n_rv > 0 && !rv)))) return fail(c, GR_EINVAL, "%s: null ring table", name);
+  return GR_OK;
+}
+
 extern "C" {
 
 int gr_polygon_class_weights(gr_ctx *c, const int64_t *tri, const int32_t *face_class, const double *face_weight, int64_t F,
@@ -737,13 +696,14 @@ int gr_polygon_class_weights(gr_ctx *c, const int64_t *tri, const int32_t *face_
                              const int32_t *ring_polygon, const int32_t *ring_is_hole, int64_t R, const int64_t *polygon_boxes,
                              int64_t P, int mode, int C, double *weights, uint64_t *stats, void *stream) {
   if (!c) return GR_EINVAL;
-  if (F < 0 || R < 0 || P < 0 || C < 0 || n_ring_vertices < 0 || F > 0x7FFFFFFFll * 256 || R > 0x7FFFFFFF || P > 0x7FFFFFFF)
-    return fail(c, GR_EINVAL, "bad polygon-weights shape F=%lld R=%lld P=%lld C=%d", (long long)F, (long long)R, (long long)P, C);
+  if (F < 0 || C < 0 || F > 0x7FFFFFFFll * 256) return fail(c, GR_EINVAL, "gr_polygon_class_weights: bad shape F=%lld C=%d", (long long)F, C);
+  int rc = check_ring_table(c, "gr_polygon_class_weights", n_ring_vertices, R, P, ring_vertices, ring_offsets, ring_polygon, polygon_boxes,
+                            true);
+  if (rc != GR_OK) return rc;
   if (mode != GR_POLY_WITHIN && mode != GR_POLY_OVERLAY)
     return fail(c, GR_EINVAL, "polygon-weights mode %d is neither GR_POLY_WITHIN nor GR_POLY_OVERLAY", mode);
   if (!stats || (P > 0 && C > 0 && !weights)) return fail(c, GR_EINVAL, "null polygon-weights outputs");
-  if ((F > 0 && (!tri || !face_class || !face_weight)) ||
-      (R > 0 && (!ring_offsets || !ring_polygon || !ring_is_hole || !polygon_boxes || (n_ring_vertices > 0 && !ring_vertices))))
+  if ((F > 0 && (!tri || !face_class || !face_weight)) || (R > 0 && !ring_is_hole))
     return fail(c, GR_EINVAL, "null polygon-weights arrays");
   hipStream_t s = (hipStream_t)stream;
   GR_HIP(c, hipSetDevice(c->device));
@@ -765,16 +725,15 @@ int gr_face_polygon_index(gr_ctx *c, const int64_t *verts_q, int64_t V, const in
                           const int32_t *cell_polygons, int64_t n_cell_polygons, int32_t *face_polygon, uint64_t *stats,
                           void *stream) {
   if (!c) return GR_EINVAL;
-  if (F < 0 || V < 0 || R < 0 || P < 0 || n_ring_vertices < 0 || n_cell_polygons < 0 || F > 0x7FFFFFFFll * 256 ||
-      V > 0x7FFFFFFFll || R > 0x7FFFFFFF || P > 0x7FFFFFFF)
-    return fail(c, GR_EINVAL, "gr_face_polygon_index: bad shape F=%lld V=%lld R=%lld P=%lld", (long long)F, (long long)V,
-                (long long)R, (long long)P);
+  if (F < 0 || V < 0 || n_cell_polygons < 0 || F > 0x7FFFFFFFll * 256 || V > 0x7FFFFFFFll)
+    return fail(c, GR_EINVAL, "gr_face_polygon_index: bad shape F=%lld V=%lld", (long long)F, (long long)V);
+  int rc = check_ring_table(c, "gr_face_polygon_index", n_ring_vertices, R, P, ring_vertices, ring_offsets, ring_polygon, polygon_boxes);
+  if (rc != GR_OK) return rc;
   if (nx < 1 || ny < 1 || (int64_t)nx * ny > GR_FPI_MAX_CELLS || cell_w < 1 || cell_h < 1)
     return fail(c, GR_EINVAL, "gr_face_polygon_index: bad cell grid nx=%d ny=%d (1 <= nx ny <= %d) cell=%lld x %lld (>= 1)", nx, ny,
                 (int)GR_FPI_MAX_CELLS, (long long)cell_w, (long long)cell_h);
   if (!stats || !cell_offsets || (F > 0 && (!faces || !face_polygon)) || (V > 0 && !verts_q) ||
-      (n_cell_polygons > 0 && !cell_polygons) || (P > 0 && !polygon_boxes) ||
-      (R > 0 && (!ring_offsets || !ring_polygon || (n_ring_vertices > 0 && !ring_vertices))))
+      (n_cell_polygons > 0 && !cell_polygons))
     return fail(c, GR_EINVAL, "gr_face_polygon_index: null arrays");
   hipStream_t s = (hipStream_t)stream;
   GR_HIP(c, hipSetDevice(c->device));
@@ -795,13 +754,12 @@ int gr_points_in_region(gr_ctx *c, const int64_t *points_q, int64_t N, const int
                         const int64_t *ring_offsets, const int32_t *ring_polygon, int64_t R, const int64_t *polygon_boxes,
                         int64_t P, int64_t D, uint8_t *mask, uint64_t *stats, void *stream) {
   if (!c) return GR_EINVAL;
-  if (N < 0 || R < 0 || P < 0 || n_ring_vertices < 0 || N > 0x7FFFFFFFll * 256 || R > 0x7FFFFFFF || P > 0x7FFFFFFF)
-    return fail(c, GR_EINVAL, "gr_points_in_region: bad shape N=%lld R=%lld P=%lld", (long long)N, (long long)R, (long long)P);
+  if (N < 0 || N > 0x7FFFFFFFll * 256) return fail(c, GR_EINVAL, "gr_points_in_region: bad shape N=%lld", (long long)N);
+  int rc = check_ring_table(c, "gr_points_in_region", n_ring_vertices, R, P, ring_vertices, ring_offsets, ring_polygon, polygon_boxes);
+  if (rc != GR_OK) return rc;
   if (D < 0 || D >= ((int64_t)1 << 40))
     return fail(c, GR_EINVAL, "gr_points_in_region: buffer D=%lld outside [0, 2^40) grid steps", (long long)D);
-  if (!stats || (N > 0 && (!points_q || !mask)) || (P > 0 && !polygon_boxes) ||
-      (R > 0 && (!ring_offsets || !ring_polygon || (n_ring_vertices > 0 && !ring_vertices))))
-    return fail(c, GR_EINVAL, "gr_points_in_region: null arrays");
+  if (!stats || (N > 0 && (!points_q || !mask))) return fail(c, GR_EINVAL, "gr_points_in_region: null arrays");
   hipStream_t s = (hipStream_t)stream;
   GR_HIP(c, hipSetDevice(c->device));
   GR_HIP(c, hipMemsetAsync(stats, 0, sizeof(uint64_t) * GR_PIR_STAT_WORDS, s));
@@ -813,7 +771,7 @@ int gr_points_in_region(gr_ctx *c, const int64_t *points_q, int64_t N, const int
   // scratch: joint box [4] i64
   Carve cv;
   const size_t o_joint = cv.array<int64_t>(4);
-  int rc = stage_acquire(c, c->stage, cv.total(), s, "region");
+  rc = stage_acquire(c, c->stage, cv.total(), s, "region");
   if (rc != GR_OK) return rc;
   int64_t *joint = Carve::at<int64_t>(c->stage.ptr, o_joint);
   hipLaunchKernelGGL(k_region_joint_box, dim3(1), dim3(256), 0, s, polygon_boxes, (int)P, joint);

@@ -18,6 +18,7 @@
 // Prune: k_sc_fill_m, then per examined view k_sc_prune_test (clears red[i] when a required face of the view has m < 2) and
 // k_sc_prune_apply (conditional on red[i]), one word per examined view so that no launch resets what another reads.
 // No cooperative launch, no waiting between workgroups; every loop is bounded by F, n_views, nnz or a clamped row.
+#include "geom_dev.hpp"
 #include "gr_internal.hpp"
 
 using namespace grimpl;
@@ -48,18 +49,6 @@ __device__ __forceinline__ bool row_range(const int64_t *__restrict__ face_ptr, 
   b = b0 < 0 ? 0 : (b0 > nnz ? nnz : b0);
   e = e0 < b ? b : (e0 > nnz ? nnz : e0);
   return b == b0 && e == e0;
-}
-
-__device__ __forceinline__ u64 wave_max_u64(u64 v) {
-  for (int off = 32; off > 0; off >>= 1) {
-    const u64 o = (u64)__shfl_xor((long long)v, off);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-  for (int off = 32; off > 0; off >>= 1) v += (u64)__shfl_xor((long long)v, off);
-  return v;
 }
 
 __global__ void __launch_bounds__(GR_SC_BLOCK) k_sc_init(int n_views, uint32_t *__restrict__ ctl, int32_t *__restrict__ gain,

@@ -7,7 +7,9 @@
 // floating-point operation is a float64 operation rounded on its own (the unit is compiled with -ffp-contract=off like the rest
 // of the library), in the order T3-T6 write down, so that the results are bit-equal to numpy applying the same operations.
 // The inside test is made on the DOUBLES, before anything is converted to an integer: NaN, infinities and 1e300 are outside.
-// Nothing is read through an index that was not checked: a face with a vertex outside [0, V) reads no vertex and no sample.
+// Nothing is read through an index that was not checked: a face with a vertex outside [0, V) reads no vertex and no sample
+// (load_face).  The face load and the statistics reductions (integers, one atomic per wave and word) are geom_dev.hpp's.
+#include "geom_dev.hpp"
 #include "gr_internal.hpp"
 
 namespace {
@@ -24,11 +26,6 @@ struct SampleArgs {
   double nodata, fill, threshold, ground_id;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {   // butterfly: every lane ends with the same sum, in a fixed order
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // pts [V][3]; faces [N][3] or null; data [B][H][W]; values [N][B], height [N], labels [N]: each may be null;
 // stats [GR_RS_STAT_WORDS].
 template <typename T>
@@ -38,17 +35,16 @@ __global__ __launch_bounds__(256) void k_sample_raster(const double *__restrict_
                                                        unsigned long long *__restrict__ stats, SampleArgs a) {
   const int lane = (int)(threadIdx.x & 63);
   const int64_t stride = (int64_t)gridDim.x * 256;
-  unsigned int n_inside = 0, n_nodata = 0, n_ground = 0, n_bad = 0;   // per lane: at most N / stride + 1 < 2^32 (the launcher's grid)
+  unsigned int n_inside = 0, n_nodata = 0, n_ground = 0, n_bad = 0;   // per lane at most N / stride + 1 <= 2^18 + 1 (the launcher's grid): a wave's sum fits 32 bits
   const double outside = a.has_nodata ? a.nodata : 0.0;   // T5: what a boundless read fills with
   const int64_t plane = (int64_t)a.H * a.W;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.N; i += stride) {
     double x = 0.0, y = 0.0, z = 0.0;
     bool bad = false;
     if (a.face_mode) {
-      const int64_t v0 = faces[i * 3], v1 = faces[i * 3 + 1], v2 = faces[i * 3 + 2];
-      if (v0 < 0 || v0 >= a.V || v1 < 0 || v1 >= a.V || v2 < 0 || v2 >= a.V) {
-        bad = true;   // reported, never dereferenced
-      } else {
+      int64_t v0, v1, v2;
+      bad = !load_face(faces, i, a.V, v0, v1, v2);
+      if (!bad) {
         const double *p0 = pts + v0 * 3, *p1 = pts + v1 * 3, *p2 = pts + v2 * 3;
         x = ((p0[0] + p1[0]) + p2[0]) / 3.0;   // T3
         y = ((p0[1] + p1[1]) + p2[1]) / 3.0;
@@ -79,15 +75,10 @@ __global__ __launch_bounds__(256) void k_sample_raster(const double *__restrict_
     n_nodata += (hit && !bad) ? 1u : 0u;
     n_bad += bad ? 1u : 0u;
   }
-  // statistics: one atomic per wave and word (sums of 64 counts below 2^32: exact in a double)
-  const double is = wave_sum((double)n_inside), ns = wave_sum((double)n_nodata), gs = wave_sum((double)n_ground),
-               bs = wave_sum((double)n_bad);
-  if (lane == 0) {
-    if (is > 0.0) atomicAdd(&stats[GR_RS_STAT_INSIDE], (unsigned long long)is);
-    if (ns > 0.0) atomicAdd(&stats[GR_RS_STAT_NODATA], (unsigned long long)ns);
-    if (gs > 0.0) atomicAdd(&stats[GR_RS_STAT_GROUND], (unsigned long long)gs);
-    if (bs > 0.0) atomicAdd(&stats[GR_RS_STAT_BAD_FACES], (unsigned long long)bs);
-  }
+  stat_add_u32(stats, GR_RS_STAT_INSIDE, n_inside, lane);
+  stat_add_u32(stats, GR_RS_STAT_NODATA, n_nodata, lane);
+  stat_add_u32(stats, GR_RS_STAT_GROUND, n_ground, lane);
+  stat_add_u32(stats, GR_RS_STAT_BAD_FACES, n_bad, lane);
 }
 
 }  // namespace

@@ -325,6 +325,9 @@ def test_header_binding_and_source_name_the_new_call():
     outline_part = source[outline_start:source.index('extern "C" {', outline_start)]       # every outline kernel and device helper
     assert all(outline_part.count(k + "(") >= 1 for k in kernels) and "k_outline_ring_words(" in outline_part
     assert not re.search(r"\b(double|float)\b", outline_part)      # no floating point anywhere in the call
+    shared = (ROOT / "geograypher_amd" / "csrc" / "geom_dev.hpp").read_text()      # ... nor in the helpers it counts and loads faces with
+    assert "stat_count(" in outline_part and "load_face(" in outline_part and '#include "geom_dev.hpp"' in source
+    assert "stat_count(" in shared and not re.search(r"\b(double|float)\b", shared)
     assert any(p.name == "polygons.hip" for p in build.SOURCES) and callable(_hip.HipRaster.class_outlines)
     assert callable(TexturedPhotogrammetryMesh.face_label_outlines) and callable(TexturedPhotogrammetryMesh.export_face_labels_vector)
 

@@ -206,6 +206,15 @@ def hand_scene():
     return polygons, cases
 
 
+def lattice_scene():
+    """The hand scene's polygons under the 0.5 m lattice over x in [-1, 46), y in [-1, 15.5): (points_q (3102, 2) int64, faces
+    (3102, 3) int32, ring table).  Face i is [i, i, i], so 3 x its centre is 3 x point i: `face_polygon_index` and `points_in_region`
+    are asked about the same points -- on vertices, on horizontal and slanted edges, on the hole's boundary, in overlapping rows."""
+    x, y = np.meshgrid(np.arange(-1.0, 46.0, 0.5), np.arange(-1.0, 15.5, 0.5))
+    points_q, table = snapped_scene(np.stack([x.ravel(), y.ravel()], axis=1), hand_scene()[0])
+    return points_q, np.repeat(np.arange(len(points_q), dtype=np.int32)[:, None], 3, axis=1), table
+
+
 RANDOM_SEED = 3   # chosen on the CPU: the stand-in counts at least 50 boundary, 50 multi-row and 50 in-hole centres (asserted)
 
 
