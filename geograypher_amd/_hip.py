@@ -111,6 +111,15 @@ GR_SETCOVER_STAT_PRUNED = 3
 GR_SETCOVER_STAT_BATCHES = 4
 GR_SETCOVER_STAT_LDS_HISTOGRAM = 5
 GR_SETCOVER_STAT_WORDS = 8
+# gr_reproject_points: coordinate kinds, stats words, the launch's workgroup cap
+GR_CRS_ECEF = 0
+GR_CRS_GEOGRAPHIC = 1
+GR_CRS_TM = 2
+GR_CRS_STAT_NONFINITE = 0
+GR_CRS_STAT_BEYOND = 1
+GR_CRS_STAT_BAD_FACES = 2
+GR_CRS_STAT_WORDS = 4
+GR_CRS_MAX_GROUPS = 8192
 
 
 class StageTimes(ctypes.Structure):
@@ -145,6 +154,17 @@ class RasterStats(ctypes.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class Crs(ctypes.Structure):
+    """gr_crs: kind (GR_CRS_*), and the four parameters of a transverse Mercator."""
+    _fields_ = [
+        ("kind", ctypes.c_int32),
+        ("lon0", ctypes.c_double),
+        ("k0", ctypes.c_double),
+        ("false_easting", ctypes.c_double),
+        ("false_northing", ctypes.c_double),
+    ]
 
 
 _vp, _i32, _i64, _f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
@@ -199,6 +219,7 @@ _SIGNATURES = {
     "gr_sample_raster": [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _f64, _f64,
                          _i32, _vp, _vp],
     "gr_set_cover": [_vp, _vp, _vp, _i64, _i64, ctypes.c_int32, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gr_reproject_points": [_vp, _vp, _i64, _vp, _i64, _vp, ctypes.POINTER(Crs), ctypes.POINTER(Crs), _vp, _vp, _vp],
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1153,6 +1174,52 @@ class HipRaster:
             if check:
                 self._raise_bad_faces("gr_sample_raster", int(stats[GR_RS_STAT_BAD_FACES].item()), V)
         return values, height, lab_t, stats
+
+    # -- CRS reprojection: points between the WGS84 systems ------------------------------------------------------------
+    def reproject_points(self, points, from_crs, to_crs, faces=None, pre_transform=None, out=None, check: bool = True):
+        """gr_reproject_points (DESIGN.md "CRS reprojection"): points (V, 3) float64 in `from_crs` -> ((N, 3) float64 device tensor
+        in `to_crs`, stats (GR_CRS_STAT_WORDS,) int64 tensor).  from_crs / to_crs: what `geograypher_amd.utils.geospatial.WGS84CRS.parse`
+        takes; geographic rows are (lon, lat, h) here whatever the authority's axis order.  faces (F, 3) int: a row per face, the
+        mean of its reprojected vertices; None: a row per vertex.  pre_transform: a 4 x 4 applied to the input first (ECEF source
+        only).  out: a device float64 (N, 3) contiguous tensor to write -- `points` itself (a device tensor, without faces)
+        converts in place.  `check` (default) reads the statistics back and raises ValueError when a face names a vertex that does
+        not exist; check=False only enqueues.  Rows that cannot be converted are NaN and counted in the statistics."""
+        from geograypher_amd.utils.geospatial import crs_tuple
+
+        torch = _torch()
+        p_t = self._dev(points, torch.float64)
+        if p_t.ndim != 2 or p_t.shape[1] != 3:
+            raise ValueError(f"points must be (V, 3), got {tuple(p_t.shape)}")
+        p_t = p_t.contiguous()
+        V = int(p_t.shape[0])
+        f_t = None
+        if faces is not None:
+            f_t = self._dev(faces, torch.int32)
+            if f_t.ndim != 2 or f_t.shape[1] != 3:
+                raise ValueError(f"faces must be (F, 3), got {tuple(f_t.shape)}")
+            f_t = f_t.contiguous()
+        N = V if f_t is None else int(f_t.shape[0])
+        sides = [Crs(int(k), float(lon0), float(k0), float(fe), float(fn)) for k, lon0, k0, fe, fn in
+                 (crs_tuple(from_crs), crs_tuple(to_crs))]
+        pre_h = None
+        if pre_transform is not None:
+            pre = np.asarray(_host_array(pre_transform), dtype=np.float64)
+            if pre.shape != (4, 4):
+                raise ValueError(f"pre_transform must be (4, 4), got {pre.shape}")
+            pre_h = (ctypes.c_double * 16)(*pre.reshape(-1).tolist())
+        if out is None:
+            out = torch.empty((N, 3), dtype=torch.float64, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (N, 3)
+              or not out.is_contiguous() or out.device != p_t.device):
+            raise ValueError(f"out must be a contiguous float64 ({N}, 3) tensor on {p_t.device}")
+        stats = torch.zeros((GR_CRS_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        if N > 0:   # (an empty tensor has no address: null faces would mean vertex mode)
+            self._call("gr_reproject_points", p_t.data_ptr() if V else None, V, None if f_t is None else f_t.data_ptr(),
+                       0 if f_t is None else N, None if pre_h is None else ctypes.addressof(pre_h), ctypes.byref(sides[0]),
+                       ctypes.byref(sides[1]), out.data_ptr(), stats.data_ptr(), self._stream())
+            if check and f_t is not None:
+                self._raise_bad_faces("gr_reproject_points", int(stats[GR_CRS_STAT_BAD_FACES].item()), V)
+        return out, stats
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):

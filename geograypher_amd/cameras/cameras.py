@@ -71,6 +71,25 @@ def vtk_like_near_planes(cam_to_worlds: np.ndarray, bounds: np.ndarray, toleranc
     return np.where(near < tolerance * far, tolerance * far, near)
 
 
+def _locations_in_CRS(local_points: np.ndarray, local_to_epsg_4978_transform, as_CRS, backend=None,
+                      force_easting_northing: bool = False) -> np.ndarray:
+    """(n, 3) points of the chunk-local frame in `as_CRS`: local_to_epsg_4978 as the pre-transform of the device's reprojection
+    from EPSG:4978 (DESIGN.md "CRS reprojection", G1)."""
+    from geograypher_amd.constants import EARTH_CENTERED_EARTH_FIXED_CRS
+    from geograypher_amd.utils.geospatial import reproject_points
+
+    if local_to_epsg_4978_transform is None:
+        raise ValueError("camera positions in a CRS need the local_to_epsg_4978_transform")
+    if backend is None:
+        from geograypher_amd._hip import HipRaster
+
+        backend = HipRaster(None)
+    out, _ = reproject_points(backend, np.ascontiguousarray(local_points, dtype=np.float64), EARTH_CENTERED_EARTH_FIXED_CRS, as_CRS,
+                              pre_transform=np.asarray(local_to_epsg_4978_transform, dtype=np.float64),
+                              force_easting_northing=force_easting_northing)
+    return np.array(out, dtype=np.float64)
+
+
 class PhotogrammetryCamera:
     def __init__(
         self,
@@ -205,6 +224,16 @@ class PhotogrammetryCamera:
     def get_local_to_epsg_4978_transform(self) -> np.ndarray:
         """reference: cameras.py:311-326"""
         return self._local_to_epsg_4978_transform
+
+    def get_camera_location(self, get_z_coordinate: bool = False, as_CRS=None, backend=None):
+        """The camera centre (reference: cameras.py:212-242): the translation of cam_to_world_transform in the chunk-local frame,
+        or with `as_CRS` (what `geograypher_amd.utils.geospatial.WGS84CRS.parse` takes) in that CRS and its axis order, through
+        local_to_epsg_4978 and the device's reprojection.  (x, y) or with `get_z_coordinate` (x, y, z).  backend: an object with
+        `HipRaster.reproject_points` (default: a `HipRaster` on the current device)."""
+        point = np.asarray(self.cam_to_world_transform, dtype=np.float64)[0:3, 3]
+        if as_CRS is not None:
+            point = _locations_in_CRS(point.reshape(1, 3), self._local_to_epsg_4978_transform, as_CRS, backend)[0]
+        return tuple(float(v) for v in (point if get_z_coordinate else point[:2]))
 
     def cast_rays(self, pixel_coords_ij: np.ndarray, line_length: float = 10):
         """Rays from the camera centre through pixels (reference: cameras.py:574-628): pixel_coords_ij (n, 2) (i, j) pixel
@@ -424,11 +453,23 @@ class PhotogrammetryCameraSet:
         """reference: cameras.py:838-859"""
         return self.get_subset_cameras(self.inds_matching_filename_regex(filename_regex))
 
-    def get_camera_locations(self) -> np.ndarray:
+    def get_camera_locations(self, as_CRS=None, backend=None, force_easting_northing: bool = False) -> np.ndarray:
         """(n, 3) float64: the translation of every camera's cam_to_world_transform, in the chunk-local frame (reference:
-        cameras.py:955-966)."""
-        return np.array([np.asarray(cam.cam_to_world_transform, dtype=np.float64)[:3, 3] for cam in self.cameras],
-                        dtype=np.float64).reshape(-1, 3)
+        cameras.py:955-966); with `as_CRS` (what `geograypher_amd.utils.geospatial.WGS84CRS.parse` takes) in that CRS, in its
+        axis order unless `force_easting_northing`, one device call for the set."""
+        local = np.array([np.asarray(cam.cam_to_world_transform, dtype=np.float64)[:3, 3] for cam in self.cameras],
+                         dtype=np.float64).reshape(-1, 3)
+        if as_CRS is None:
+            return local
+        return _locations_in_CRS(local, self._local_to_epsg_4978_transform, as_CRS, backend, force_easting_northing)
+
+    def get_lon_lat_coords(self, backend=None):
+        """[(lon, lat)] of every camera, computed from its position on every call (the reference reads the cameras' stored
+        `lon_lat`, cameras.py:951-953): `lon_lats` is not filled, it enters `get_camera_hash`."""
+        from geograypher_amd.constants import LAT_LON_CRS
+
+        lon_lat = self.get_camera_locations(as_CRS=LAT_LON_CRS, backend=backend, force_easting_northing=True)
+        return [(float(lon), float(lat)) for lon, lat, _ in lon_lat]
 
     def get_subset_ROI(self, ROI, buffer_radius: float = 0, is_geospatial: Optional[bool] = None, *, points_in_ROI_CRS=None,
                        backend=None):
@@ -436,7 +477,8 @@ class PhotogrammetryCameraSet:
 
         ROI: a `PlanarPolygons`, a sequence its `from_sequence` takes, or a `.geojson` path.  is_geospatial: None takes a
         `.geojson` for geospatial and ring arrays for local.  A local ROI is compared with `get_camera_locations()` (x, y of the
-        chunk-local frame); a geospatial one needs the camera positions in ITS planar CRS as points_in_ROI_CRS (n, 2) or (n, 3)
+        chunk-local frame); a geospatial one needs the camera positions in ITS planar CRS as points_in_ROI_CRS (n, 2) or (n, 3),
+        or the name of that CRS (`WGS84CRS.parse`: the positions are then computed on the device, `get_camera_locations(as_CRS=)`)
         -- the reference reprojects lon / lat with pyproj -- else NotImplementedError.  A camera ON the buffered region's
         boundary is kept (`within` drops it).  backend: an object with `HipRaster.points_in_region` (default: a `HipRaster` on
         the current device)."""
@@ -445,6 +487,11 @@ class PhotogrammetryCameraSet:
         if is_geospatial is None:
             is_geospatial = isinstance(ROI, (str, os.PathLike))
         if points_in_ROI_CRS is not None:
+            from geograypher_amd.utils.geospatial import is_CRS_designator
+
+            if is_CRS_designator(points_in_ROI_CRS):   # the positions in that CRS, easting first, computed on the device
+                points_in_ROI_CRS = self.get_camera_locations(as_CRS=points_in_ROI_CRS, backend=backend,
+                                                              force_easting_northing=True)
             locations = np.asarray(points_in_ROI_CRS, dtype=np.float64)
             if locations.ndim != 2 or locations.shape[0] != len(self.cameras) or locations.shape[1] not in (2, 3):
                 raise ValueError(f"points_in_ROI_CRS must be ({len(self.cameras)}, 2) or ({len(self.cameras)}, 3), got "

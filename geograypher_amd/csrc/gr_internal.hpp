@@ -20,7 +20,9 @@
 //   terrain.hip      raster samples: the value of a raster under every face centre or vertex, height above it, ground relabel (k_sample_raster); no mesh needed
 //   select.hip       image selection: greedy set cover over a face x view incidence (k_sc_rows, k_sc_scan, k_sc_scatter, k_sc_pick, k_sc_apply,
 //                    k_sc_prune_test, k_sc_prune_apply); no mesh needed
-//   geom_dev.hpp     device helpers of polygons.hip, terrain.hip and select.hip: orient, ring_span, edge_crossing (THE even-odd rule of
+//   crs.hip          CRS reprojection: points between WGS84 ECEF, geographic and transverse Mercator coordinates (k_reproject_points; constants:
+//                    crs_constants.hpp, written by tools/make_crs_constants.py); no mesh needed
+//   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip and crs.hip: orient, ring_span, edge_crossing (THE even-odd rule of
 //                    k_polygon_weights, k_face_polygon_index and k_points_in_region), load_face, stat_add / stat_add_u32 / stat_max / stat_count
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

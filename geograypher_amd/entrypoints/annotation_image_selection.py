@@ -44,16 +44,24 @@ def determine_minimum_overlapping_images(
     ROI_camera_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
     camera_set=None,
     backend=None,
+    ROI_CRS=None,
+    ROI_camera_CRS=None,
 ):
     """Determine a subset of images that together observe the entire scene (see the module docstring).  The reference's arguments
     and defaults; `downsample_target != 1`, `vis` and `ROI` without `ROI_points_file` raise NotImplementedError.  Beyond the
     reference: `ROI_points_file` (a `.npy` path or array: the V ORIGINAL vertices in the ROI's CRS), `ROI_camera_points_file` (the
     positions of the cameras in that CRS; without it the camera set is not cut to the ROI, with a log line), and `camera_set`
-    and `backend`, which replace the objects built from `cameras_file` and the device.  `min_observations_to_be_included`: a
+    and `backend`, which replace the objects built from `cameras_file` and the device; `ROI_CRS` and `ROI_camera_CRS`: the CRS of
+    the ROI (e.g. "EPSG:32610") in place of the two points files -- the vertices and camera positions are then reprojected on the
+    device --, giving a file and its CRS sibling is a ValueError.  `min_observations_to_be_included`: a
     selected set need only see the faces that at least this many cameras see.  Returns a dict with what the stages that ran
     produced: "summed_projections", "selected_images" (the mask), "selection" (the record of `select_covering_views`),
     "subset_camera_set"."""
-    if ROI is not None and ROI_points_file is None:
+    from geograypher_amd.utils.geospatial import points_or_CRS
+
+    ROI_points = points_or_CRS("ROI_points_file", ROI_points_file, "ROI_CRS", ROI_CRS)
+    ROI_camera_points = points_or_CRS("ROI_camera_points_file", ROI_camera_points_file, "ROI_camera_CRS", ROI_camera_CRS)
+    if ROI is not None and ROI_points is None:
         raise NotImplementedError("ROI: the vertices in the ROI's CRS are needed (ROI_points_file); reprojecting them needs pyproj, "
                                   "which is outside the projection path")
     if vis:
@@ -63,9 +71,6 @@ def determine_minimum_overlapping_images(
     if isinstance(mesh_CRS, int) or (isinstance(mesh_CRS, str) and mesh_CRS.isdigit()):
         mesh_CRS = f"EPSG:{int(mesh_CRS)}"   # the reference's --mesh-CRS is an EPSG code
 
-    def points_array(source):   # a .npy path or the array itself
-        return np.load(source) if isinstance(source, (str, Path)) else source
-
     def load_cameras(roi_backend):
         """The camera set, cut to the ROI (annotation_image_selection.py:89-94, 178-183)."""
         cameras = camera_set
@@ -74,11 +79,9 @@ def determine_minimum_overlapping_images(
 
             cameras = MetashapeCameraSet(cameras_file, image_folder)
         if ROI is not None:
-            camera_points = points_array(ROI_camera_points_file)
-            if camera_points is not None:
+            if ROI_camera_points is not None:
                 cameras = cameras.get_subset_ROI(ROI=ROI, buffer_radius=ROI_buffer_meters, is_geospatial=True,
-                                                 points_in_ROI_CRS=np.asarray(camera_points, dtype=np.float64),
-                                                 backend=roi_backend)
+                                                 points_in_ROI_CRS=ROI_camera_points, backend=roi_backend)
             else:
                 import logging
 
@@ -95,7 +98,7 @@ def determine_minimum_overlapping_images(
 
         roi_kwargs = {}
         if ROI is not None:
-            roi_kwargs = {"ROI": ROI, "ROI_buffer_meters": ROI_buffer_meters, "points_in_ROI_CRS": points_array(ROI_points_file)}
+            roi_kwargs = {"ROI": ROI, "ROI_buffer_meters": ROI_buffer_meters, "points_in_ROI_CRS": ROI_points}
         mesh = TexturedPhotogrammetryMeshIndexPredictions(mesh_file, input_CRS=mesh_CRS, backend=backend, **roi_kwargs)
         cameras = load_cameras(mesh.backend)
         segmentor = ImageIDSegmentor(image_filenames=cameras.get_image_filename(index=None, absolute=True))
@@ -143,6 +146,9 @@ def parse_args(argv=None):
                         help=".npy with the mesh vertices (V, 2) or (V, 3) in the CRS of --ROI (required with it)")
     parser.add_argument("--ROI-camera-points-file", type=Path,
                         help=".npy with the camera positions in the CRS of --ROI; without it the camera set is not cut")
+    parser.add_argument("--ROI-CRS", help="CRS of --ROI (e.g. EPSG:32610) instead of --ROI-points-file: the vertices are reprojected "
+                        "on the device")
+    parser.add_argument("--ROI-camera-CRS", help="CRS of --ROI instead of --ROI-camera-points-file: the camera set is cut to the ROI")
     parser.add_argument("--ROI-buffer-meters", type=float, default=0.0, help="Only applies with --ROI")
     parser.add_argument("--compute-projection", action="store_true", help="Compute which images see which faces")
     parser.add_argument("--compute-minimal-set", action="store_true", help="Choose the images from --projections-filename")

@@ -34,21 +34,24 @@ def render_height_masks(
     apply_distortion: bool = True,
     camera_set=None,
     backend=None,
+    points_CRS=None,
 ):
     """Render the height of the mesh above `dtm_file` into every camera's view (see the module docstring).  The reference's
     arguments; `vis_folder` raises NotImplementedError, an unknown `output_mode` ValueError.  Beyond the reference: `points_file`
-    (a `.npy` path or the array itself, required), `apply_distortion` (False for a camera set without a lens model), and
+    (a `.npy` path or the array itself) or `points_CRS` (the CRS of `dtm_file`, e.g. "EPSG:32610": the vertices are reprojected on
+    the device), one of them required and both a ValueError, `apply_distortion` (False for a camera set without a lens model), and
     `camera_set` and `backend`, which replace the objects built from `camera_file` and the device.  Returns the mesh textured with
     what was rendered."""
     from geograypher_amd.meshes import TexturedPhotogrammetryMesh
+    from geograypher_amd.utils.geospatial import points_or_CRS
 
     if vis_folder is not None:
         raise NotImplementedError("vis_folder: visualisations need pyvista and matplotlib, which are outside the projection path")
     if output_mode not in ("threshold", "raw"):
         raise ValueError(f"Unknown mode: {output_mode}")
 
+    points_in_raster_CRS = points_or_CRS("points_file", points_file, "points_CRS", points_CRS)
     mesh = TexturedPhotogrammetryMesh(mesh_file, input_CRS=mesh_CRS, backend=backend)
-    points_in_raster_CRS = np.load(points_file) if isinstance(points_file, (str, Path)) else points_file
     # faces outside the DTM, or over its nodata cells, have a height of NaN
     height = mesh.get_height_above_ground(DTM_file=dtm_file, points_in_raster_CRS=points_in_raster_CRS)
 
@@ -79,7 +82,9 @@ def parse_args(argv=None):
     parser.add_argument("--camera-file", type=Path, required=True, help="Metashape XML with camera calibrations and positions")
     parser.add_argument("--mesh-file", type=Path, required=True, help="Mesh as .npz (points, faces)")
     parser.add_argument("--dtm-file", type=Path, required=True, help="Digital terrain model: a single-band GeoTIFF")
-    parser.add_argument("--points-file", type=Path, required=True, help=".npy with the mesh vertices (V, 3) in the CRS of --dtm-file")
+    parser.add_argument("--points-file", type=Path, help=".npy with the mesh vertices (V, 3) in the CRS of --dtm-file")
+    parser.add_argument("--points-CRS", help="CRS of --dtm-file (e.g. EPSG:32610) instead of --points-file: the vertices are "
+                        "reprojected on the device")
     parser.add_argument("--mesh-crs", required=True, help="CRS of the mesh vertices (EPSG:4978)")
     parser.add_argument("--original-image-folder", type=Path,
                         help="Removed from the beginning of the absolute image paths stored in --camera-file")
@@ -97,7 +102,7 @@ def main(argv=None):
     render_height_masks(image_folder=args.image_folder, camera_file=args.camera_file, mesh_file=args.mesh_file,
                         dtm_file=args.dtm_file, mesh_CRS=args.mesh_crs, original_image_folder=args.original_image_folder,
                         output_folder=args.output_folder, output_mode=args.output_mode, threshold_cutoff=args.threshold_cutoff,
-                        vis_folder=args.vis_folder, vis_n_images=args.vis_n_images, points_file=args.points_file)
+                        vis_folder=args.vis_folder, vis_n_images=args.vis_n_images, points_file=args.points_file, points_CRS=args.points_CRS)
 
 
 if __name__ == "__main__":

@@ -58,6 +58,10 @@ def render_labels(
     DTM_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
     ROI_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
     ROI_camera_points_file: typing.Union[PATH_TYPE, np.ndarray, None] = None,
+    texture_CRS=None,
+    DTM_CRS=None,
+    ROI_CRS=None,
+    ROI_camera_CRS=None,
 ):
     """Render the labels of `texture` into every camera's view (see the module docstring for inputs and files).  The reference's
     arguments and defaults; `DTM_file` without `DTM_points_file`, `ROI` without `ROI_points_file`, `mesh_downsample != 1`, `subset_images_savefolder`, `textured_mesh_savefile`, `vis`,
@@ -67,14 +71,22 @@ def render_labels(
     for a vector texture), `DTM_points_file` (likewise, the vertices in the DTM's CRS, required with `DTM_file`), `apply_distortion` (False for a camera set without a lens model), and `camera_set` and `backend`,
     which replace the objects built from `cameras_file` and the device; `ROI_points_file` (the V original vertices in the ROI's CRS,
     required with `ROI`) and `ROI_camera_points_file` (the camera positions in that CRS; without it the camera set is not cut, with a
-    log line).  `texture_points_file` and `DTM_points_file` are given for the ORIGINAL mesh and indexed by the kept vertices.  Returns
+    log line).  `texture_points_file` and `DTM_points_file` are given for the ORIGINAL mesh and indexed by the kept vertices.  Each
+    `*_points_file` has a sibling `texture_CRS`, `DTM_CRS`, `ROI_CRS`, `ROI_camera_CRS`: the CRS of the texture / DTM / ROI (e.g.
+    "EPSG:32610") in place of the points, which are then reprojected on the device; giving both is a ValueError.  Returns
     the textured mesh."""
     from geograypher_amd.meshes import TexturedPhotogrammetryMesh, TexturedPhotogrammetryMeshChunked
+    from geograypher_amd.utils.geospatial import is_CRS_designator, points_or_CRS
+
+    texture_points = points_or_CRS("texture_points_file", texture_points_file, "texture_CRS", texture_CRS)
+    DTM_points = points_or_CRS("DTM_points_file", DTM_points_file, "DTM_CRS", DTM_CRS)
+    ROI_points = points_or_CRS("ROI_points_file", ROI_points_file, "ROI_CRS", ROI_CRS)
+    ROI_camera_points = points_or_CRS("ROI_camera_points_file", ROI_camera_points_file, "ROI_camera_CRS", ROI_camera_CRS)
 
     for name, value, why in (
-        ("DTM_file", DTM_file if DTM_points_file is None else None,
+        ("DTM_file", DTM_file if DTM_points is None else None,
          "the vertices in the DTM's CRS are needed (DTM_points_file); reprojecting them needs pyproj"),
-        ("ROI", ROI if ROI_points_file is None else None,
+        ("ROI", ROI if ROI_points is None else None,
          "the vertices in the ROI's CRS are needed (ROI_points_file); reprojecting them needs pyproj"),
         ("subset_images_savefolder", subset_images_savefolder, "copying the image subset is not part of this package"),
         ("textured_mesh_savefile", textured_mesh_savefile, "mesh writers (pyvista) are not part of this package"),
@@ -95,32 +107,31 @@ def render_labels(
 
     MeshClass = TexturedPhotogrammetryMesh if n_cameras_per_chunk is None else TexturedPhotogrammetryMeshChunked
 
-    def points_array(source):   # a .npy path or the array itself
-        return np.load(source) if isinstance(source, (str, Path)) else source
-
     roi_kwargs = {}
     if ROI is not None:   # reference: render_labels.py:120-131 (cameras), 141-149 (mesh)
-        roi_kwargs = {"ROI": ROI, "ROI_buffer_meters": mesh_ROI_buffer_radius_meters, "points_in_ROI_CRS": points_array(ROI_points_file)}
+        roi_kwargs = {"ROI": ROI, "ROI_buffer_meters": mesh_ROI_buffer_radius_meters, "points_in_ROI_CRS": ROI_points}
     mesh = MeshClass(mesh_file, input_CRS=mesh_CRS, IDs_to_labels=IDs_to_labels, backend=backend, **roi_kwargs)
     if ROI is not None:
-        if ROI_camera_points_file is not None:
+        if ROI_camera_points is not None:
             camera_set = camera_set.get_subset_ROI(ROI=ROI, buffer_radius=cameras_ROI_buffer_radius_meters, is_geospatial=True,
-                                                   points_in_ROI_CRS=points_array(ROI_camera_points_file), backend=mesh.backend)
+                                                   points_in_ROI_CRS=ROI_camera_points, backend=mesh.backend)
         else:
             mesh.logger.info("ROI without ROI_camera_points_file: the camera set is not cut to the ROI")
     n_render_chunks = None if n_cameras_per_chunk is None else int(ceil(len(camera_set) / n_cameras_per_chunk))
 
-    def kept(points):   # the rows of the vertices the ROI kept
-        return points if points is None or mesh.ROI_point_IDs is None else np.asarray(points)[mesh.ROI_point_IDs]
+    def kept(points):   # the rows of the vertices the ROI kept (a CRS names the points of the cropped mesh already)
+        if points is None or mesh.ROI_point_IDs is None or is_CRS_designator(points):
+            return points
+        return np.asarray(points)[mesh.ROI_point_IDs]
 
-    points_in_polygon_CRS = kept(points_array(texture_points_file))
+    points_in_polygon_CRS = kept(texture_points)
     if isinstance(texture, np.ndarray):   # an array for the original mesh is cut like the mesh
         texture = mesh.crop_to_ROI(texture)
     mesh.load_texture(texture, texture_column_name=texture_column_name, IDs_to_labels=mesh.IDs_to_labels,
                       points_in_polygon_CRS=points_in_polygon_CRS)
 
     if DTM_file is not None and ground_height_threshold is not None:   # reference: render_labels.py:161-171
-        points_in_raster_CRS = kept(points_array(DTM_points_file))
+        points_in_raster_CRS = kept(DTM_points)
         mesh.label_ground_class(DTM_file=DTM_file, height_above_ground_threshold=ground_height_threshold,
                                 only_label_existing_labels=True, ground_class_name="GROUND",
                                 ground_ID=None if render_ground_class else np.nan, set_mesh_texture=True,
@@ -146,6 +157,8 @@ def parse_args(argv=None):
     parser.add_argument("--render-savefolder", type=Path, required=True, help="Where the rendered labels are written")
     parser.add_argument("--texture-points-file", type=Path,
                         help=".npy with the mesh vertices (V, 3) in the CRS of a .geojson --texture (required for one)")
+    parser.add_argument("--texture-CRS", help="CRS of a .geojson --texture (e.g. EPSG:32610) instead of --texture-points-file: the "
+                        "vertices are reprojected on the device")
     parser.add_argument("--original-image-folder", type=Path,
                         help="Removed from the beginning of the absolute image paths stored in --cameras-file")
     parser.add_argument("--subset-images-savefolder", type=Path, help="Not available here")
@@ -153,6 +166,7 @@ def parse_args(argv=None):
     parser.add_argument("--DTM-file", type=Path, help="Single-band GeoTIFF of the terrain: labelled faces near it are relabelled")
     parser.add_argument("--DTM-points-file", type=Path,
                         help=".npy with the mesh vertices (V, 3) in the CRS of --DTM-file (required with it)")
+    parser.add_argument("--DTM-CRS", help="CRS of --DTM-file instead of --DTM-points-file")
     parser.add_argument("--ground-height-threshold", type=float, default=2.0,
                         help="Faces lower than this above the DTM are ground; only applies with --DTM-file")
     parser.add_argument("--render-ground-class", action="store_true",
@@ -163,6 +177,8 @@ def parse_args(argv=None):
                         help=".npy with the mesh vertices (V, 2) or (V, 3) in the CRS of --ROI (required with it)")
     parser.add_argument("--ROI-camera-points-file", type=Path,
                         help=".npy with the camera positions in the CRS of --ROI; without it the camera set is not cut")
+    parser.add_argument("--ROI-CRS", help="CRS of --ROI instead of --ROI-points-file")
+    parser.add_argument("--ROI-camera-CRS", help="CRS of --ROI instead of --ROI-camera-points-file: the camera set is cut to the ROI")
     parser.add_argument("--mesh-ROI-buffer-radius-meters", default=50, type=float, help="Only applies with --ROI")
     parser.add_argument("--cameras-ROI-buffer-radius-meters", default=100, type=float, help="Only applies with --ROI")
     parser.add_argument("--render-image-scale", type=float, default=1, help="Render at this fraction of the image size")

@@ -109,6 +109,12 @@ def _parse_mesh(mesh) -> typing.Tuple[np.ndarray, np.ndarray]:
     return points, faces.astype(np.int64, copy=True)
 
 
+def _reproject_stats(stats) -> dict:
+    """The statistics words of `reproject_points` as a dict."""
+    stats = np.asarray(stats.cpu() if hasattr(stats, "detach") else stats)
+    return {"nonfinite": int(stats[0]), "beyond_central_meridian": int(stats[1]), "bad_faces": int(stats[2])}
+
+
 class TexturedPhotogrammetryMesh:
     def __init__(
         self,
@@ -133,8 +139,10 @@ class TexturedPhotogrammetryMesh:
 
         Same leading arguments as the reference constructor (meshes.py:55-156).  `mesh` is `(points (V,3), faces
         (F,3))`, any object with `.points`/`.faces` (pyvista layout accepted) or a `.npz` path.  The coordinates are
-        interpreted in `input_CRS`; only EPSG:4978 (the frame the reference reprojects every mesh into,
-        meshes.py:1659) is accepted because CRS reprojection is outside the projection path.  Decimation and
+        interpreted in `input_CRS`: EPSG:4978 (the frame the reference reprojects every mesh into, meshes.py:1659) or
+        another WGS84 system `geograypher_amd.utils.geospatial.WGS84CRS.parse` takes (EPSG:4326 / 4979 in the authority's
+        axis order lat, lon, h; the UTM zones), whose vertices are brought to EPSG:4978 on the device here; any other CRS
+        needs pyproj and raises NotImplementedError.  Decimation and
         vector/raster texture files are likewise outside it and raise NotImplementedError (a `.geojson` texture is
         loaded afterwards, by `load_texture(..., points_in_polygon_CRS=...)`).  `ROI` with `ROI_buffer_meters` crops
         the mesh before the texture is loaded (`select_mesh_ROI`; needs `points_in_ROI_CRS`) and leaves the kept
@@ -157,21 +165,30 @@ class TexturedPhotogrammetryMesh:
                 (`profiles/r06_gl_residue.txt`).  Needs the pyvista camera's principal point (`principal_point="center"`).
             neg1_is_last_face: reproduce meshes.py:1998-2001, where background pixels (-1) index the LAST face
                 during projection.  True matches the reference's aggregated textures on every face.
-            points_in_ROI_CRS: the mesh vertices (V, 2) or (V, 3) in the ROI's planar CRS, required with `ROI` (the
-                reference reprojects them with pyproj); without it `ROI` raises NotImplementedError.
+            points_in_ROI_CRS: the mesh vertices (V, 2) or (V, 3) in the ROI's planar CRS, or the name of that CRS ("EPSG:32610",
+                32610, a `WGS84CRS`: the vertices are then reprojected on the device), required with `ROI` (the reference
+                reprojects them with pyproj); without it `ROI` raises NotImplementedError.
         """
         if downsample_target != 1.0:
             raise NotImplementedError("mesh decimation is outside the projection path (meshes.py:215-226)")
         if ROI is not None and points_in_ROI_CRS is None:
             raise NotImplementedError("ROI cropping is outside the projection path (meshes.py:646-731) unless the vertices "
                                       "in the ROI's CRS are given: points_in_ROI_CRS")
+        source_CRS = None   # a WGS84 system other than EPSG:4978: the vertices are brought there on the device below
         if input_CRS is not None and str(input_CRS).upper().replace(" ", "") not in ("EPSG:4978",):
-            raise NotImplementedError(
-                f"input_CRS={input_CRS!r}: only EPSG:4978 meshes are accepted (CRS reprojection needs pyproj and is "
-                "outside the projection path)"
-            )
+            from geograypher_amd.utils.geospatial import KIND_ECEF, WGS84CRS
+
+            try:
+                source_CRS = WGS84CRS.parse(input_CRS)
+            except NotImplementedError:
+                raise NotImplementedError(
+                    f"input_CRS={input_CRS!r}: only meshes in EPSG:4978 or another WGS84 system (EPSG:4326, EPSG:4979, the UTM "
+                    "zones EPSG:326xx / 327xx) are accepted (any other CRS needs pyproj and is outside the projection path)"
+                ) from None
+            if source_CRS.kind == KIND_ECEF:
+                source_CRS = None
         self.downsample_target = downsample_target
-        self.CRS = input_CRS
+        self.CRS = input_CRS if source_CRS is None else EARTH_CENTERED_EARTH_FIXED_CRS
         self.texture = None
         self.vertex_texture = None
         self.face_texture = None
@@ -211,6 +228,14 @@ class TexturedPhotogrammetryMesh:
         if vertex_order not in ("r1", "gl"):
             raise ValueError(f"vertex_order must be 'r1' or 'gl', got {vertex_order!r}")
         self.vertex_order = vertex_order
+
+        if source_CRS is not None:   # the projection path needs EPSG:4978 (reference: meshes.py:1659)
+            from geograypher_amd.utils.geospatial import reproject_points
+
+            self.points, stats = reproject_points(self.backend, np.ascontiguousarray(self.points, dtype=np.float64), source_CRS,
+                                                  EARTH_CENTERED_EARTH_FIXED_CRS)
+            self.points = np.array(self.points, dtype=np.float64)
+            self.last_reproject_stats = _reproject_stats(stats)
 
         self.ROI_point_IDs = None
         self.ROI_face_IDs = None
@@ -260,7 +285,7 @@ class TexturedPhotogrammetryMesh:
         are the region.  None returns the mesh unchanged.  buffer_meters: a vertex within this distance of the region is in
         it too.  simplify_tol_meters: only 0 (polygon simplification is not built: NotImplementedError).  default_CRS:
         accepted and unused (coordinates are taken as they stand).  points_in_ROI_CRS (required, keyword): the mesh vertices
-        (V, 2) or (V, 3) in the ROI's planar CRS.
+        (V, 2) or (V, 3) in the ROI's planar CRS, or a CRS designator (`WGS84CRS.parse`: the vertices are then reprojected on the device).
 
         A face is kept iff one of its vertices is in the region (`extract_points(adjacent_cells=True)`), a vertex iff a kept
         face uses it; both keep their order.  Returns (points, faces) -- faces index the kept points --, or with
@@ -276,7 +301,7 @@ class TexturedPhotogrammetryMesh:
             raise NotImplementedError(
                 "select_mesh_ROI needs points_in_ROI_CRS: the mesh vertices in the ROI's planar CRS (CRS reprojection needs "
                 "pyproj and is outside the projection path)")
-        verts = np.asarray(points_in_ROI_CRS, dtype=np.float64)
+        verts = np.asarray(self._points_in_CRS(points_in_ROI_CRS), dtype=np.float64)
         if verts.ndim != 2 or verts.shape[0] != self.points.shape[0] or verts.shape[1] not in (2, 3):
             raise ValueError(f"points_in_ROI_CRS must be ({self.points.shape[0]}, 2) or ({self.points.shape[0]}, 3), got "
                              f"{verts.shape}")
@@ -293,6 +318,47 @@ class TexturedPhotogrammetryMesh:
         if return_original_IDs:
             return subset, point_IDs, face_IDs
         return subset
+
+    # -- CRS reprojection (DESIGN.md "CRS reprojection"; reference: meshes.py:231-286, 752-783) ----------------------
+    def get_mesh_points_in_CRS(self, output_CRS, use_vertices: bool = False, force_easting_northing: bool = True,
+                               return_tensor: bool = False):
+        """The face centres, or with `use_vertices` the vertices, in `output_CRS`: (n_faces | n_points, 3) float64, computed
+        on the device.  output_CRS: what `geograypher_amd.utils.geospatial.WGS84CRS.parse` takes.  A face centre is the mean
+        of the face's REPROJECTED vertices (`cell_centers()` of the reprojected mesh).  force_easting_northing: EPSG:4326 /
+        4979 come out as (lon, lat, h) instead of the authority's (lat, lon, h).  A mesh whose CRS is None is returned
+        untransformed, as the reference does.  `return_tensor=True` leaves the result on the device.  The counters of the call
+        are left in `self.last_reproject_stats` (nonfinite, beyond_central_meridian, bad_faces)."""
+        from geograypher_amd.utils.geospatial import reproject_points
+
+        if self.CRS is None:
+            self.logger.warning("mesh CRS is None, get_mesh_points_in_CRS is doing nothing")
+            if use_vertices:
+                return np.array(self.points, dtype=np.float64)
+            corners = np.asarray(self.points, dtype=np.float64)[self.faces]
+            return ((corners[:, 0] + corners[:, 1]) + corners[:, 2]) / 3.0
+        faces = None if use_vertices else np.ascontiguousarray(self.faces, dtype=np.int32)
+        out, stats = reproject_points(self.backend, np.ascontiguousarray(self.points, dtype=np.float64), self.CRS, output_CRS,
+                                      faces=faces, force_easting_northing=force_easting_northing, return_tensor=return_tensor)
+        self.last_reproject_stats = _reproject_stats(stats)
+        return out
+
+    def reproject_CRS(self, target_CRS, inplace: bool = False):
+        """The mesh vertices (n_points, 3) in `target_CRS`, in the CRS's own axis order.  The reference updates the mesh with
+        `inplace=True` (its default); here the projection path needs the mesh in EPSG:4978, so that raises NotImplementedError
+        and the default is False."""
+        if inplace:
+            raise NotImplementedError("reproject_CRS(inplace=True): the projection path needs the mesh in EPSG:4978; use the "
+                                      "returned points")
+        return self.get_mesh_points_in_CRS(target_CRS, use_vertices=True, force_easting_northing=False)
+
+    def _points_in_CRS(self, points_or_CRS):
+        """What every `points_in_*_CRS` keyword takes: an array is returned as it is; a CRS designator (a string, an EPSG
+        integer, a WGS84CRS) becomes the (V, 3) vertices in that CRS, easting first, computed on the device."""
+        from geograypher_amd.utils.geospatial import is_CRS_designator
+
+        if is_CRS_designator(points_or_CRS):
+            return self.get_mesh_points_in_CRS(points_or_CRS, use_vertices=True, force_easting_northing=True)
+        return points_or_CRS
 
     # -- backend -------------------------------------------------------------------------------------------------
     @property
@@ -1180,7 +1246,7 @@ class TexturedPhotogrammetryMesh:
                 "(geograypher_amd.utils.geometric)")
         if not isinstance(polygons, PlanarPolygons):
             polygons = PlanarPolygons.from_sequence(polygons)
-        verts = np.asarray(points_in_polygon_CRS, dtype=np.float64)
+        verts = np.asarray(self._points_in_CRS(points_in_polygon_CRS), dtype=np.float64)
         if verts.shape != (self.points.shape[0], 3):
             raise ValueError(f"points_in_polygon_CRS must be ({self.points.shape[0]}, 3), got {verts.shape}")
         if face_weighting is not None and face_weighting.shape[0] != self.faces.shape[0]:
@@ -1228,7 +1294,7 @@ class TexturedPhotogrammetryMesh:
         (decided exactly on the 1e-6 m grid), False the area of every face's intersection with it.  buffer_dist_meters: accepted
         and unused (the reference's buffered ROI pre-filter is not reproduced).  points_in_polygon_CRS (required, keyword): the
         mesh vertices (V, 3) in the polygons' planar CRS, x, y in metres, z up -- what the reference gets from
-        get_vertices_in_CRS.
+        get_vertices_in_CRS --, or a CRS designator (`WGS84CRS.parse`: the vertices are then reprojected on the device).
 
         Returns the (n_polygons,) list of the reference: the class with the largest weighted area as a float (the lowest class on
         equality), NaN where nothing contributes; with `return_class_labels` and IDs_to_labels, the label strings, and
@@ -1251,7 +1317,7 @@ class TexturedPhotogrammetryMesh:
     def face_polygon_index(self, polygons, *, points_in_polygon_CRS=None, return_tensor: bool = False):
         """The polygon row every face CENTRE lies in: (n_faces,) int32, -1 for none; the HIGHEST row where rows overlap, a centre
         on a polygon's boundary (its holes' included) is inside.  polygons: a `PlanarPolygons` or a sequence its `from_sequence`
-        takes; points_in_polygon_CRS (required, keyword): the mesh vertices (V, 3) in the polygons' planar CRS.  Decided exactly on
+        takes; points_in_polygon_CRS (required, keyword): the mesh vertices (V, 3) in the polygons' planar CRS, or a CRS designator (`WGS84CRS.parse`: the vertices are then reprojected on the device).  Decided exactly on
         the 1e-6 m grid (rules V1-V5).  `return_tensor=True` leaves the result on the device.  The statistics of the call are left
         in `self.last_vector_stats` (pairs_tested, faces_labelled, longest_cell_list, cells)."""
         from geograypher_amd.utils.geometric import PlanarPolygons, polygon_cell_table
@@ -1266,7 +1332,7 @@ class TexturedPhotogrammetryMesh:
                 "(geograypher_amd.utils.geometric)")
         if not isinstance(polygons, PlanarPolygons):
             polygons = PlanarPolygons.from_sequence(polygons)
-        verts = np.asarray(points_in_polygon_CRS, dtype=np.float64)
+        verts = np.asarray(self._points_in_CRS(points_in_polygon_CRS), dtype=np.float64)
         if verts.shape != (self.points.shape[0], 3):
             raise ValueError(f"points_in_polygon_CRS must be ({self.points.shape[0]}, 3), got {verts.shape}")
         vq, table = self._snap_with_polygons(verts, polygons)
@@ -1347,7 +1413,7 @@ class TexturedPhotogrammetryMesh:
         face_labels: (F,) or (F, 1) class ids, float or int, NaN = no label, numpy or a device tensor; None: the mesh's face
         texture; (F, C) with C > 1: many-hot, one call per column with a value > 0, a face takes part where its value is > 0 and
         `ring_class` is the column.  points_in_export_CRS (required, keyword): the V vertices (V, 2 | 3) in the planar CRS of the
-        export, metres; z is not used.  drop_nan=False: the faces without a label form one more class, reported with id NaN.
+        export, metres, or a CRS designator (`WGS84CRS.parse`: the vertices are then reprojected on the device); z is not used.  drop_nan=False: the faces without a label form one more class, reported with id NaN.
         A wrong number of labels is a ValueError.  Filled with the non-zero rule, the rings of a class are the union of its faces
         in plan view on the 1e-6 m grid; where a class overlaps itself in plan view its rings overlap too.  `return_tensor=True`
         returns the arrays as tensors on the backend's device.  The counters are also left in `self.last_outline_stats`."""
@@ -1364,7 +1430,7 @@ class TexturedPhotogrammetryMesh:
             raise NotImplementedError(
                 "face_label_outlines needs points_in_export_CRS: the mesh vertices (V, 2 | 3) in the planar CRS of the export (CRS "
                 "reprojection needs pyproj and is outside the projection path)")
-        points = np.asarray(points_in_export_CRS, dtype=np.float64)
+        points = np.asarray(self._points_in_CRS(points_in_export_CRS), dtype=np.float64)
         if points.ndim != 2 or points.shape[0] != self.points.shape[0] or points.shape[1] not in (2, 3):
             raise ValueError(f"points_in_export_CRS must be ({self.points.shape[0]}, 2) or ({self.points.shape[0]}, 3), got {points.shape}")
         vq = snap_points(points)   # X1
@@ -1512,7 +1578,7 @@ class TexturedPhotogrammetryMesh:
                 f"{what} needs points_in_raster_CRS: the mesh vertices (V, 3) in the raster's CRS (CRS reprojection needs pyproj "
                 "and is outside the projection path)")
         raster = raster_file if isinstance(raster_file, PlanarRaster) else PlanarRaster.from_geotiff(raster_file)
-        points = np.ascontiguousarray(points_in_raster_CRS, dtype=np.float64)
+        points = np.ascontiguousarray(self._points_in_CRS(points_in_raster_CRS), dtype=np.float64)
         if points.shape != (self.points.shape[0], 3):
             raise ValueError(f"points_in_raster_CRS must be ({self.points.shape[0]}, 3), got {points.shape}")
         faces = None if use_vertex_locations else np.ascontiguousarray(self.faces, dtype=np.int32)
@@ -1527,7 +1593,7 @@ class TexturedPhotogrammetryMesh:
                                     nodata_fill_value: float = np.nan, *, points_in_raster_CRS=None):
         """The value of a raster under every face centre, or vertex (reference: meshes.py:1449-1499; rules T1-T5): (N,) float64
         for one band, (N, B) for several.  raster_file: a single-band GeoTIFF path or a `PlanarRaster`
-        (geograypher_amd.utils.raster); points_in_raster_CRS (required, keyword): the mesh vertices (V, 3) in the raster's CRS.
+        (geograypher_amd.utils.raster); points_in_raster_CRS (required, keyword): the mesh vertices (V, 3) in the raster's CRS, or a CRS designator (`WGS84CRS.parse`: the vertices are then reprojected on the device) -- e.g. `raster.epsg`.
         The sample is that of the cell the point falls into; outside the raster it is nodata (0.0 without one); a sample equal
         to nodata becomes `nodata_fill_value`.  `return_mesh_points` also returns the (N, 3) query points: the vertices, or the
         face centres ((p0 + p1) + p2) / 3.0, the very operations the device forms them with.  The statistics of the call are left

@@ -200,6 +200,7 @@ class PlanarPolygons:
             raise ValueError("ring_polygon holds a negative row")
         rows = int(ring_polygon.max()) + 1 if ring_polygon.size else 0
         self.n_polygons = rows if n_polygons is None else int(n_polygons)
+        self.epsg = None   # read only: the EPSG code `from_geojson` found in the file's `crs` member
         if self.n_polygons < rows:
             raise ValueError(f"ring_polygon names row {rows - 1} but n_polygons is {self.n_polygons}")
         clean = []
@@ -282,7 +283,8 @@ class PlanarPolygons:
         first ring of every part an exterior); a feature of any other geometry type, or without geometry, keeps its row and
         has no rings.  A third coordinate is dropped.  properties: {name: (n_features,) array} over the union of the features'
         property names, None where a feature lacks one: int64 when every value is an int, float64 when every value is a
-        number (bool is neither), otherwise object.  The coordinates are taken as they stand: planar metres, no CRS handling."""
+        number (bool is neither), otherwise object.  The coordinates are taken as they stand: planar metres, no CRS handling; the
+        EPSG code of a `crs` member is recorded as `.epsg` of the polygons (None without one) and nothing consults it."""
         import json
 
         with open(path, "r") as file:
@@ -312,7 +314,9 @@ class PlanarPolygons:
             column = np.empty(len(values), dtype=dtype)
             column[:] = values
             properties[name] = column
-        return cls(rings, rows, holes, n_polygons=len(features)), properties
+        polygons = cls(rings, rows, holes, n_polygons=len(features))
+        polygons.epsg = _geojson_epsg(data.get("crs"))
+        return polygons, properties
 
     def bounds_snapped(self):
         """(lo (2,), hi (2,)) int64 of all rings on the grid, before any origin; None without rings."""
@@ -320,6 +324,16 @@ class PlanarPolygons:
             return None
         q = [snap_to_grid(r) for r in self.rings]
         return np.min([v.min(axis=0) for v in q], axis=0), np.max([v.max(axis=0) for v in q], axis=0)
+
+
+def _geojson_epsg(crs):
+    """The EPSG code of a GeoJSON `crs` member ({"type": "name", "properties": {"name": "urn:ogc:def:crs:EPSG::32610"}} or
+    "EPSG:32610"); None for anything else."""
+    import re
+
+    name = ((crs.get("properties") or {}).get("name") if isinstance(crs, dict) else None)
+    match = re.fullmatch(r"(?:urn:ogc:def:crs:)?EPSG:(?:[\d.]*:)?(\d+)", name.strip(), re.I) if isinstance(name, str) else None
+    return int(match.group(1)) if match else None
 
 
 # -- region of interest (DESIGN.md "Region of interest") ----------------------------------------------------------------------------

@@ -3,8 +3,9 @@
 `PlanarRaster` holds the bands, the affine transform in the order of rasterio's `Affine` and the nodata value; `inverse` is the
 inverse transform in Python floats, in the order of operations of the `affine` package.  `from_geotiff` reads single-band GeoTIFFs
 with PIL (there is no rasterio / GDAL here): the transform from the ModelPixelScale + ModelTiepoint or ModelTransformation tags,
-the PixelIsPoint half-pixel shift from the GeoKeyDirectory, the nodata value from GDAL_NODATA.  The CRS of the file is NOT read:
-the caller supplies the query points in it."""
+the PixelIsPoint half-pixel shift from the GeoKeyDirectory, the nodata value from GDAL_NODATA.  The EPSG code of the file's CRS
+is recorded as `.epsg` (ProjectedCSTypeGeoKey, else GeographicTypeGeoKey, else None) and nothing consults it: the caller supplies
+the query points in the raster's CRS, or names that CRS (`points_in_raster_CRS=dtm.epsg`)."""
 import math
 from pathlib import Path
 
@@ -16,6 +17,9 @@ TAG_MODEL_TRANSFORMATION = 34264
 TAG_GEO_KEY_DIRECTORY = 34735
 TAG_GDAL_NODATA = 42113
 GEO_KEY_RASTER_TYPE = 1025
+GEO_KEY_GEOGRAPHIC_TYPE = 2048
+GEO_KEY_PROJECTED_CS_TYPE = 3072
+GEO_KEY_USER_DEFINED = 32767
 RASTER_PIXEL_IS_POINT = 2
 GEOTIFF_MODES = ("F", "I", "I;16", "L")
 
@@ -39,7 +43,7 @@ class PlanarRaster:
     nodata a float or None.  float32 and float64 data stay what they are; any other dtype becomes float64 (exact for uint8,
     uint16, int16 and int32)."""
 
-    def __init__(self, data, transform, nodata=None):
+    def __init__(self, data, transform, nodata=None, epsg=None):
         data = np.asarray(data)
         if data.ndim == 2:
             data = data[None]
@@ -54,6 +58,7 @@ class PlanarRaster:
         self.transform = transform
         self.inverse = invert_affine(transform)
         self.nodata = None if nodata is None else float(nodata)
+        self.epsg = None if epsg is None else int(epsg)   # read only: the CRS the file names, if it names one
 
     @property
     def shape(self):
@@ -103,7 +108,16 @@ class PlanarRaster:
             if isinstance(nodata, (tuple, list)):
                 nodata = nodata[0]
             nodata = float(str(nodata).strip().rstrip("\x00").strip())
-        return cls(data, transform, nodata)
+        epsg = None
+        if keys is not None:
+            for key in (GEO_KEY_PROJECTED_CS_TYPE, GEO_KEY_GEOGRAPHIC_TYPE):
+                code = _geo_key(keys, key)
+                if code is not None and 0 < code < GEO_KEY_USER_DEFINED:
+                    epsg = code
+                    break
+        raster = cls(data, transform, nodata)
+        raster.epsg = epsg
+        return raster
 
 
 def _geo_key(directory, key):

@@ -642,6 +642,54 @@ int gr_set_cover(gr_ctx *ctx, const int64_t *face_ptr, const int32_t *face_views
                  double min_observations, int flags, uint8_t *selected, int32_t *order, int64_t *gains, int32_t *pruned,
                  int64_t *stats, void *stream);
 
+/* CRS reprojection -- replaces the pyproj.Transformer of reproject_CRS and get_mesh_points_in_CRS (meshes/meshes.py:231-286,
+ * 752-783), get_camera_location (cameras/cameras.py:212-242) and convert_CRS_3D_points (utils/geospatial.py:60-71) for the systems
+ * on the WGS84 ellipsoid: points between ECEF (EPSG:4978), geographic coordinates and a transverse Mercator (the UTM zones); one
+ * ellipsoid, no datum shift.  The rule-set is DESIGN.md "CRS reprojection" (G1-G9).  Every operation is a float64 operation rounded
+ * on its own; the device library's trigonometric and hyperbolic functions are not correctly rounded, so the results are pinned by
+ * the tolerance of G9 (a few 1e-9 m), not bit for bit.
+ * A gr_crs names a system: kind GR_CRS_ECEF (X, Y, Z in metres), GR_CRS_GEOGRAPHIC (lon, lat in degrees, ellipsoidal height in
+ * metres -- longitude FIRST) or GR_CRS_TM (easting, northing, height; lon0 in degrees, k0 > 0, false easting and northing in metres,
+ * all finite; UTM zone z: lon0 = 6 z - 183, k0 = 0.9996, 500000, 0 north or 10000000 south).  The four parameters are read for
+ * GR_CRS_TM only.  from_h and to_h are HOST pointers.
+ * points: V x 3 float64 in `from`.  pre16_h (a HOST pointer, or NULL): a row-major 4 x 4 whose first three rows are applied to
+ * every input row first, ((m0 x + m1 y) + m2 z) + m3 per component -- the cameras' local_to_epsg_4978 --, with an ECEF source only.
+ * faces: F x 3 int32 -- an output row per face, ((p0 + p1) + p2) / 3.0 per component of its three REPROJECTED vertices, what
+ * cell_centers() of the reprojected mesh gives -- or NULL with F = 0: an output row per vertex.  N is F or V accordingly.
+ * out: N x 3 float64; without faces it may be `points` (in place).  Rows that cannot be converted are NaN in all three components
+ * and counted once, in the first of these that applies: GR_CRS_STAT_BAD_FACES, a face with a vertex index outside [0, V) (nothing
+ * is read through it); GR_CRS_STAT_NONFINITE, a non-finite coordinate (after the pre-transform), the ECEF origin or a latitude
+ * outside [-90, 90] (for a face: in any of its vertices); GR_CRS_STAT_BEYOND, 90 degrees or more from the central meridian of a
+ * transverse Mercator, source or target.  An ECEF point on the axis has longitude 0.  Longitudes come out in (-180, 180].
+ * stats: GR_CRS_STAT_WORDS uint64 on the device, written by the call.  GR_EINVAL (the message names the call): null points / out /
+ * from_h / to_h / stats, null faces with F > 0, negative sizes, V >= 2^31, an unknown kind, a k0 that is not > 0 or a parameter that
+ * is not finite, pre16_h with a source that is not ECEF, faces with out == points.  N = 0 is GR_OK.  Only enqueues work on `stream`
+ * (a grid-stride loop over at most GR_CRS_MAX_GROUPS workgroups of 256 lanes); needs no uploaded mesh and no context scratch.  Added
+ * without a GR_VERSION bump. */
+enum {
+  GR_CRS_ECEF = 0,
+  GR_CRS_GEOGRAPHIC = 1,
+  GR_CRS_TM = 2
+};
+enum {
+  GR_CRS_STAT_NONFINITE = 0,  /* rows with a non-finite coordinate, the ECEF origin, a latitude outside [-90, 90]         */
+  GR_CRS_STAT_BEYOND = 1,     /* rows 90 degrees or more from a central meridian                                          */
+  GR_CRS_STAT_BAD_FACES = 2,  /* faces with a vertex index outside [0, V)                                                 */
+  GR_CRS_STAT_WORDS = 4
+};
+enum {
+  GR_CRS_MAX_GROUPS = 8192    /* workgroups of the launch: 256 * GR_CRS_MAX_GROUPS rows per pass of the stride loop        */
+};
+typedef struct gr_crs {
+  int32_t kind;           /* GR_CRS_ECEF, GR_CRS_GEOGRAPHIC, GR_CRS_TM */
+  double lon0;            /* central meridian, degrees                 */
+  double k0;              /* scale on the central meridian             */
+  double false_easting;   /* metres                                    */
+  double false_northing;  /* metres                                    */
+} gr_crs;
+int gr_reproject_points(gr_ctx *ctx, const double *points, int64_t V, const int32_t *faces, int64_t F, const double *pre16_h,
+                        const gr_crs *from_h, const gr_crs *to_h, double *out, uint64_t *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
