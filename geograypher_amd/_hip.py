@@ -325,6 +325,39 @@ def _require_gpu():
         )
 
 
+def _ptr(t):
+    """The device address of a tensor; None (a null pointer) for None."""
+    return None if t is None else t.data_ptr()
+
+
+def _float_kind(array):
+    """float32 stays float32, everything else becomes float64: (the array, the name of that dtype, its GR_DTYPE_*).  A numpy
+    array of another dtype is converted here, on the host (exact for the integer dtypes of a DTM or a vote array); a tensor is
+    returned as it is, for `_dev` to convert."""
+    if not isinstance(array, _torch().Tensor):
+        array = np.asarray(array)
+        if array.dtype != np.float32:
+            array = array.astype(np.float64, copy=False)
+    if str(array.dtype).endswith("float32"):
+        return array, "float32", GR_DTYPE_F32
+    return array, "float64", GR_DTYPE_F64
+
+
+def _count_then_fill(name: str, attempt, cap: int, something_to_fill, check):
+    """The count-then-fill protocol of gr_ray_pairs and gr_class_outlines over `attempt(cap) -> (rc, total, result)`: the
+    library reports the total whatever room it was offered, so a first attempt that overflowed (GR_EOVERFLOW), or that offered
+    none (cap 0) where `something_to_fill(total)`, is repeated exactly once, at max(total, 1), where it fits.  Every other code
+    goes to `check(rc, name)` at once.  -> (the result of the attempt that fitted, the number of attempts)."""
+    for attempts in (1, 2):
+        rc, total, result = attempt(cap)
+        if rc != GR_EOVERFLOW and not (rc == GR_OK and cap == 0 and something_to_fill(total)):
+            check(rc, name)
+            return result, attempts
+        cap = max(int(total), 1)   # the library counted everything: the repeat fits exactly
+    check(rc, name)
+    raise RuntimeError(f"{name} reported two different totals for the same input")
+
+
 POLYGON_RING_CHUNK = 512  # ring records per LDS chunk of gr_project_polygon_pairs (PAIR_CHUNK, csrc/project.hip)
 
 
@@ -387,8 +420,8 @@ class PairAccumulator:
         self.flags = _flags(neg1_is_last_face) | GR_FLAG_DEFER_CHECK
         self._fixed_cap = cap is not None
         self.cap = max(int(cap), 1) if self._fixed_cap else max(8 * backend.n_faces, 1 << 20)
-        self.keys = torch.empty((self.cap,), dtype=torch.int64, device=backend.device)
-        self.key_count = torch.zeros((2,), dtype=torch.int64, device=backend.device)  # {pair count, error flag} (GR_FLAG_DEFER_CHECK)
+        self.keys = backend._empty((self.cap,), torch.int64)
+        self.key_count = backend._zeros((2,), torch.int64)  # {pair count, error flag} (GR_FLAG_DEFER_CHECK)
         self.bound = 0          # upper bound of the pairs in the buffer
         self.parts = []         # (keys, multiplicities) of earlier compactions, host
         self.compactions = 0
@@ -396,9 +429,7 @@ class PairAccumulator:
 
     def _views(self, ids):
         """ids (n, h, w) or (h, w) -> (contiguous int32 (n, h, w) tensor on the device, n, h, w)"""
-        ids_t = self.b._dev(ids, _torch().int32)
-        if ids_t.ndim == 2:
-            ids_t = ids_t[None]
+        ids_t, _ = self.b._view_batch(ids)
         return (ids_t, *(int(x) for x in ids_t.shape))
 
     def _upload(self, *tables):
@@ -470,7 +501,7 @@ class PairAccumulator:
             return
         table, (offs_ptr, voffs_ptr, boxes_ptr) = self._upload(poly_offsets, vert_offsets, boxes)
         verts_t = self.b._dev(verts, _torch().float64)
-        self._emit("gr_project_polygon_pairs", ids_t.data_ptr(), boxes_ptr, voffs_ptr, verts_t.data_ptr() if R else None,
+        self._emit("gr_project_polygon_pairs", ids_t.data_ptr(), boxes_ptr, voffs_ptr, _ptr(verts_t if R else None),
                    offs_ptr, n, h, w)
 
     def _make_room(self, n: int, add_view, bounds=None) -> bool:
@@ -488,7 +519,7 @@ class PairAccumulator:
                                   "(2 GiB) the pair buffer grows to")
             self._compact()
             self.cap = largest if self._fixed_cap else max(largest, 8 * F, 1 << 20)
-            self.keys = _torch().empty((self.cap,), dtype=_torch().int64, device=self.b.device)
+            self.keys = self.b._empty((self.cap,), _torch().int64)
             self.grown += 1
         total = sum(bounds)
         if total > self.cap:
@@ -564,6 +595,8 @@ class HipRaster:
         self._faces = None
         self.last_retries = 0
         self.last_stats = {}
+        self.last_ray_pair_calls = 0   # library calls of the last `ray_pair_edges` / `class_outlines`: 1, or 2 when the first
+        self.last_outline_calls = 0    # offer of room was too small (`_count_then_fill`)
         self.n_faces = 0
         self.n_verts = 0
         self.vertex_order = "r1"
@@ -595,17 +628,33 @@ class HipRaster:
             raise IndexError(f"{what}: {msg}")
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")
 
-    def _call(self, name: str, *args):
-        """lib.<name>(ctx, *args) with this backend's device current; a code other than GR_OK raises (`_check`)."""
+    def _rc(self, name: str, *args) -> int:
+        """lib.<name>(ctx, *args) with this backend's device current -> the library's code, whatever it is."""
         with _torch().cuda.device(self.device):
-            rc = getattr(self.lib, name)(self._ctx, *args)
-        self._check(rc, name)
+            return getattr(self.lib, name)(self._ctx, *args)
+
+    def _call(self, name: str, *args):
+        """`_rc`, and a code other than GR_OK raises (`_check`)."""
+        self._check(self._rc(name, *args), name)
+
+    def _empty(self, shape, dtype):
+        return _torch().empty(shape, dtype=dtype, device=self.device)
+
+    def _zeros(self, shape, dtype):
+        return _torch().zeros(shape, dtype=dtype, device=self.device)
+
+    def _full(self, shape, value, dtype):
+        return _torch().full(shape, value, dtype=dtype, device=self.device)
+
+    def _stats(self, words: int, zeroed: bool = False):
+        """The int64 statistics block of an entry point (GR_*_STAT_WORDS); `zeroed` where the call may be skipped."""
+        return (self._zeros if zeroed else self._empty)((words,), _torch().int64)
 
     def _count_pairs(self, keys, n: int):
         """gr_count_pairs over the first n > 0 pair keys of a device buffer: (distinct keys, multiplicities), int64 numpy."""
         torch = _torch()
-        uniq = torch.empty((n,), dtype=torch.int64, device=self.device)
-        mult = torch.empty((n,), dtype=torch.int32, device=self.device)
+        uniq = self._empty((n,), torch.int64)
+        mult = self._empty((n,), torch.int32)
         n_unique = ctypes.c_int64(0)
         self._call("gr_count_pairs", keys.data_ptr(), n, uniq.data_ptr(), mult.data_ptr(), ctypes.byref(n_unique),
                    self._stream())
@@ -623,30 +672,60 @@ class HipRaster:
         """The snapped ring table of `PlanarPolygons.snapped` on this device, checked: (ring vertices (N, 2) int64, offsets
         (R + 1,) int64, polygons (R,) int32, boxes (P, 4) int64, hole flags (R,) int32 or None, N, R, P)."""
         torch = _torch()
-        rv_t = self._dev(ring_vertices, torch.int64)
-        off_t = self._dev(ring_offsets, torch.int64)
+        rv_t = self._shaped(ring_vertices, torch.int64, ("N", 2), "ring vertices")
         rp_t = self._dev(ring_polygon, torch.int32)
-        rh_t = None if ring_is_hole is None else self._dev(ring_is_hole, torch.int32)
-        box_t = self._dev(polygon_boxes, torch.int64)
-        R, P = int(rp_t.shape[0]), int(box_t.shape[0])
-        if rv_t.ndim != 2 or rv_t.shape[1] != 2 or tuple(off_t.shape) != (R + 1,) or box_t.ndim != 2 or box_t.shape[1] != 4 or \
-                (rh_t is not None and tuple(rh_t.shape) != (R,)):
-            holes = () if rh_t is None else (rh_t,)
-            got = ", ".join(str(tuple(t.shape)) for t in (rv_t, off_t, rp_t) + holes)
-            raise ValueError(f"ring table must be (N, 2) vertices, (R + 1,) offsets, (R,) polygons{', (R,) hole flags' if holes else ''} "
-                             f"and (P, 4) boxes, got {got} and {tuple(box_t.shape)}")
-        return rv_t, off_t, rp_t, box_t, rh_t, int(rv_t.shape[0]), R, P
+        R = int(rp_t.shape[0])
+        off_t = self._shaped(ring_offsets, torch.int64, (R + 1,), "ring offsets (one more than ring polygons)")
+        rh_t = None if ring_is_hole is None else self._shaped(ring_is_hole, torch.int32, (R,), "ring hole flags (one per ring polygon)")
+        box_t = self._shaped(polygon_boxes, torch.int64, ("P", 4), "polygon boxes")
+        return rv_t, off_t, rp_t, box_t, rh_t, int(rv_t.shape[0]), R, int(box_t.shape[0])
+
+    def _shaped(self, array, dtype, pattern: tuple, name: str):
+        """numpy / tensor -> contiguous tensor of `dtype` on this device whose shape fits `pattern`: an int is the length an axis
+        must have, a letter stands for any length -- ("V", 3), (2, "H", "W"), (F,).  ValueError names the argument, the
+        pattern and the shape it got."""
+        t = self._dev(array, dtype)
+        shape = t.shape
+        fits = len(shape) == len(pattern)
+        for k, n in zip(pattern, shape) if fits else ():
+            if k != n and not isinstance(k, str):
+                fits = False
+        if not fits:
+            want = ", ".join(str(k) for k in pattern) + ("," if len(pattern) == 1 else "")
+            raise ValueError(f"{name} must be ({want}), got {tuple(shape)}")
+        return t
 
     def _mesh_2d(self, verts_q, faces):
         """(verts_q (V, 2) int64, faces (F, 3) int32) on this device, checked."""
         torch = _torch()
-        vq_t, f_t = self._dev(verts_q, torch.int64), self._dev(faces, torch.int32)
-        if vq_t.ndim != 2 or vq_t.shape[1] != 2 or f_t.ndim != 2 or f_t.shape[1] != 3:
-            raise ValueError(f"vertices must be (V, 2) and faces (F, 3), got {tuple(vq_t.shape)} and {tuple(f_t.shape)}")
-        return vq_t, f_t
+        return self._shaped(verts_q, torch.int64, ("V", 2), "vertices"), self._shaped(faces, torch.int32, ("F", 3), "faces")
 
-    @staticmethod
-    def _raise_bad_faces(name, n_bad, V):
+    def _points_faces(self, points, faces):
+        """points (V, 3) float64 and faces (F, 3) int, or None for a row per vertex -> (points, faces or None on this device,
+        checked; V; N, the rows of the result: F with faces, V without)."""
+        torch = _torch()
+        p_t = self._shaped(points, torch.float64, ("V", 3), "points")
+        f_t = None if faces is None else self._shaped(faces, torch.int32, ("F", 3), "faces")
+        V = int(p_t.shape[0])
+        return p_t, f_t, V, V if f_t is None else int(f_t.shape[0])
+
+    def _view_batch(self, ids, other=None, dtype=None, name: str = "", channels: bool = False):
+        """(h, w) means one view: ids (N, h, w) or (h, w), and a companion array of the same shape (`channels`: with one more
+        axis behind it) -> (ids (N, h, w) int32, the companion (N, h, w[, C]) in `dtype`, or None) on this device."""
+        ids_t = self._dev(ids, _torch().int32)
+        o_t = None if other is None else self._dev(other, dtype)
+        if ids_t.ndim == 2:
+            ids_t, o_t = ids_t[None], None if o_t is None else o_t[None]
+        if ids_t.ndim != 3:
+            raise ValueError(f"ids must be (N, h, w) or (h, w), got {tuple(ids_t.shape)}")
+        if o_t is not None and (o_t.ndim != 3 + channels or o_t.shape[:3] != ids_t.shape):
+            raise ValueError(f"ids {tuple(ids_t.shape)} and {name} {tuple(o_t.shape)} differ in shape")
+        return ids_t, o_t
+
+    def _check_faces(self, name: str, stats, word: int, V: int):
+        """The one bad-face rule: read word `word` of a call's statistics block back (which waits for the call, unless the block
+        is on the host already) and raise when it counted faces with a vertex index the kernel refused."""
+        n_bad = int(stats[word].item())
         if n_bad:
             raise ValueError(f"{name}: {n_bad} faces name a vertex outside [0, {V})")
 
@@ -677,10 +756,8 @@ class HipRaster:
     def upload_mesh(self, verts, faces):
         """verts (V,3) float, faces (F,3) int in the cameras' local frame (meshes.py:1641-1676 output)."""
         torch = _torch()
-        v = self._dev(verts, torch.float32)
-        f = self._dev(faces, torch.int32)
-        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
-            raise ValueError(f"mesh must be (V,3) vertices and (F,3) faces, got {tuple(v.shape)} and {tuple(f.shape)}")
+        v = self._shaped(verts, torch.float32, ("V", 3), "mesh vertices")
+        f = self._shaped(faces, torch.int32, ("F", 3), "mesh faces")
         self._call("gr_mesh_upload", v.data_ptr(), f.data_ptr(), v.shape[0], f.shape[0], self._stream())
         self._verts, self._faces = v, f  # borrowed by the library: keep alive
         self.n_verts, self.n_faces = int(v.shape[0]), int(f.shape[0])
@@ -695,18 +772,16 @@ class HipRaster:
         bins overflowed is INCOMPLETE until the caller asks `raster_status()`, which raises on overflow.  Use it only for
         repeats of a call that was sized with `check=True` on the same inputs."""
         torch = _torch()
-        cams_t = self._dev(cams, torch.float32)
-        if cams_t.ndim != 2 or cams_t.shape[1] != GR_CAM_FLOATS:
-            raise ValueError(f"camera records must be (N,{GR_CAM_FLOATS}), got {tuple(cams_t.shape)}")
+        cams_t = self._shaped(cams, torch.float32, ("N", GR_CAM_FLOATS), "camera records")
         n = int(cams_t.shape[0])
         if out is None:
-            out = torch.empty((n, h, w), dtype=torch.int32, device=self.device)
+            out = self._empty((n, h, w), torch.int32)
         elif tuple(out.shape) != (n, h, w) or out.dtype != torch.int32 or not out.is_contiguous():
             raise ValueError("out must be a contiguous int32 tensor of shape (N,h,w)")
-        depth = torch.empty((n, h, w), dtype=torch.float32, device=self.device) if want_depth else None
+        depth = self._empty((n, h, w), torch.float32) if want_depth else None
         self._checked_raster(n, check, lambda v0: self._call(
             "gr_raster_face_ids", cams_t[v0:].data_ptr(), n - v0, h, w, out[v0:].data_ptr(),
-            depth[v0:].data_ptr() if depth is not None else None, self._stream()))
+            _ptr(None if depth is None else depth[v0:]), self._stream()))
         return (out, depth) if want_depth else out
 
     def _checked_raster(self, n: int, check: bool, launch):
@@ -747,39 +822,28 @@ class HipRaster:
     # -- render_flat gather --------------------------------------------------------------------------------------
     def gather_texture(self, ids, face_texture):
         """ids (...,) int32 tensor, face_texture (F,C) -> (..., C) float64 tensor, NaN where ids == -1."""
-        torch = _torch()
-        ids_t = self._dev(ids, torch.int32)
-        tex = self._dev(face_texture, torch.float64)
-        F, C = int(tex.shape[0]), int(tex.shape[1])
-        out = torch.empty(tuple(ids_t.shape) + (C,), dtype=torch.float64, device=self.device)
-        self._call("gr_gather_texture_f64", ids_t.data_ptr(), ids_t.numel(), tex.data_ptr(), F, C, out.data_ptr(),
-                   self._stream())
-        return out
+        return self._gather("gr_gather_texture_f64", ids, face_texture, _torch().float64)
 
     def gather_texture_u8(self, ids, face_texture, null_value: int = 0):
         """save_renders epilogue: ids (...,) int32, face_texture (F,C) -> (..., C) uint8 tensor (meshes.py:2325-2337)."""
+        return self._gather("gr_gather_texture_u8", ids, face_texture, _torch().uint8, int(null_value))
+
+    def _gather(self, name: str, ids, face_texture, out_dtype, *null_value):
         torch = _torch()
         ids_t = self._dev(ids, torch.int32)
         tex = self._dev(face_texture, torch.float64)
         F, C = int(tex.shape[0]), int(tex.shape[1])
-        out = torch.empty(tuple(ids_t.shape) + (C,), dtype=torch.uint8, device=self.device)
-        self._call("gr_gather_texture_u8", ids_t.data_ptr(), ids_t.numel(), tex.data_ptr(), F, C, int(null_value),
-                   out.data_ptr(), self._stream())
+        out = self._empty(tuple(ids_t.shape) + (C,), out_dtype)
+        self._call(name, ids_t.data_ptr(), ids_t.numel(), tex.data_ptr(), F, C, *null_value, out.data_ptr(), self._stream())
         return out
 
     def _index_views(self, ids, img):
         """The inputs of the index-pair path: ids (N,h,w) or (h,w), the class-index image of the same shape (a channel axis of
         one is dropped) -> contiguous (N,h,w) int32 and float64 tensors on this device."""
-        torch = _torch()
-        ids_t = self._dev(ids, torch.int32)
-        img_t = self._dev(img, torch.float64)
-        if ids_t.ndim == 2:
-            ids_t, img_t = ids_t[None], img_t[None]
-        if img_t.ndim == 4 and img_t.shape[-1] == 1:
-            img_t = img_t[..., 0]
-        if ids_t.shape != img_t.shape:
-            raise ValueError(f"ids {tuple(ids_t.shape)} and index image {tuple(img_t.shape)} differ in shape")
-        return ids_t, img_t.contiguous()
+        img_t = self._dev(img, _torch().float64)
+        if img_t.ndim == np.ndim(ids) + 1 and img_t.shape[-1] == 1:
+            img_t = img_t[..., 0]   # (still contiguous: the axis had one element)
+        return self._view_batch(ids, img_t, _torch().float64, "index image")
 
     def project_index_pairs(self, ids, img, n_classes: int, counts, neg1_is_last_face: bool = True):
         """Sparse index aggregation step (derived_meshes.py:470-520) for N views: ids (N,h,w) int32, img (N,h,w) float64
@@ -789,8 +853,8 @@ class HipRaster:
         ids_t, img_t = self._index_views(ids, img)
         n, h, w = (int(x) for x in ids_t.shape)
         cap = n * self.n_faces
-        keys = torch.empty((max(cap, 1),), dtype=torch.int64, device=self.device)
-        key_count = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        keys = self._empty((max(cap, 1),), torch.int64)
+        key_count = self._zeros((1,), torch.int64)
         self._call("gr_project_index_pairs", ids_t.data_ptr(), img_t.data_ptr(), n, h, w, int(n_classes),
                    counts.data_ptr(), keys.data_ptr(), cap, key_count.data_ptr(), _flags(neg1_is_last_face), self._stream())
         m = int(key_count.item())
@@ -825,36 +889,25 @@ class HipRaster:
         torch = _torch()
         s_t, e_t, id_t = self._ray_inputs(starts, ends, ray_ids)
         n = int(s_t.shape[0])
-        cap = max(8 * n, 1 << 16) if capacity is None else int(capacity)
         total = ctypes.c_int64(0)
-        self.last_ray_pair_calls = 0
-        for _attempt in range(2):
-            ei = torch.empty((max(cap, 1),), dtype=torch.int32, device=self.device)
-            ej = torch.empty((max(cap, 1),), dtype=torch.int32, device=self.device)
-            ed = torch.empty((max(cap, 1),), dtype=torch.float64, device=self.device)
-            with torch.cuda.device(self.device):
-                rc = self.lib.gr_ray_pairs(self._ctx, s_t.data_ptr(), e_t.data_ptr(), id_t.data_ptr(), n, float(threshold),
-                                           ei.data_ptr() if cap else None, ej.data_ptr() if cap else None,
-                                           ed.data_ptr() if cap else None, cap, ctypes.byref(total), self._stream())
-            self.last_ray_pair_calls += 1
+
+        def attempt(cap):
+            ei, ej, ed = (self._empty((max(cap, 1),), dtype) for dtype in (torch.int32, torch.int32, torch.float64))
+            rc = self._rc("gr_ray_pairs", s_t.data_ptr(), e_t.data_ptr(), id_t.data_ptr(), n, float(threshold),
+                          *(_ptr(t if cap else None) for t in (ei, ej, ed)), cap, ctypes.byref(total), self._stream())
             m = int(total.value)
-            if rc == GR_EOVERFLOW or (rc == GR_OK and cap == 0 and m > 0):
-                cap = m   # the library counted every edge: the repeat fits exactly
-                continue
-            self._check(rc, "gr_ray_pairs")
-            return ei[:m], ej[:m], ed[:m]
-        self._check(rc, "gr_ray_pairs")
-        raise RuntimeError("gr_ray_pairs reported two different edge totals for the same input")
+            return rc, m, (ei[:m], ej[:m], ed[:m])
+
+        self.last_ray_pair_calls = 0
+        edges, self.last_ray_pair_calls = _count_then_fill(
+            "gr_ray_pairs", attempt, max(8 * n, 1 << 16) if capacity is None else int(capacity), lambda m: m > 0, self._check)
+        return edges
 
     def _ray_inputs(self, starts, ends, ray_ids):
         torch = _torch()
-        s_t = self._dev(starts, torch.float64)
-        e_t = self._dev(ends, torch.float64)
-        id_t = self._dev(ray_ids, torch.int32)
-        if s_t.ndim != 2 or s_t.shape[1] != 3 or s_t.shape != e_t.shape:
-            raise ValueError(f"starts and ends must both be (N, 3), got {tuple(s_t.shape)} and {tuple(e_t.shape)}")
-        if id_t.ndim != 1 or id_t.shape[0] != s_t.shape[0]:
-            raise ValueError(f"{s_t.shape[0]} rays need {s_t.shape[0]} ray ids, got shape {tuple(id_t.shape)}")
+        s_t = self._shaped(starts, torch.float64, ("N", 3), "starts")
+        e_t = self._shaped(ends, torch.float64, s_t.shape, "ends")
+        id_t = self._shaped(ray_ids, torch.int32, (s_t.shape[0],), "ray ids (one per ray)")
         return s_t, e_t, id_t
 
     def clip_rays(self, origins, directions, points, faces):
@@ -863,18 +916,14 @@ class HipRaster:
         int -> (hit bool (N,), t float64 (N,), hit points float64 (N, 3); NaN where nothing is hit).  More than
         CLIP_TRIANGLE_LIMIT triangles is a ValueError."""
         torch = _torch()
-        o_t = self._dev(origins, torch.float64)
-        d_t = self._dev(directions, torch.float64)
-        p_t = self._dev(points, torch.float64)
-        f_t = self._dev(faces, torch.int32)
-        if o_t.ndim != 2 or o_t.shape[1] != 3 or o_t.shape != d_t.shape:
-            raise ValueError(f"origins and directions must both be (N, 3), got {tuple(o_t.shape)} and {tuple(d_t.shape)}")
-        if p_t.ndim != 2 or p_t.shape[1] != 3 or f_t.ndim != 2 or f_t.shape[1] != 3:
-            raise ValueError(f"boundary must be (V, 3) points and (F, 3) faces, got {tuple(p_t.shape)} and {tuple(f_t.shape)}")
+        o_t = self._shaped(origins, torch.float64, ("N", 3), "origins")
+        d_t = self._shaped(directions, torch.float64, o_t.shape, "directions")
+        p_t = self._shaped(points, torch.float64, ("V", 3), "boundary points")
+        f_t = self._shaped(faces, torch.int32, ("F", 3), "boundary faces")
         n = int(o_t.shape[0])
-        hit = torch.zeros((n,), dtype=torch.int32, device=self.device)
-        t = torch.full((n,), float("nan"), dtype=torch.float64, device=self.device)
-        pts = torch.full((n, 3), float("nan"), dtype=torch.float64, device=self.device)
+        hit = self._zeros((n,), torch.int32)
+        t = self._full((n,), float("nan"), torch.float64)
+        pts = self._full((n, 3), float("nan"), torch.float64)
         self._call("gr_rays_clip", o_t.data_ptr(), d_t.data_ptr(), n, p_t.data_ptr(), int(p_t.shape[0]), f_t.data_ptr(),
                    int(f_t.shape[0]), hit.data_ptr(), t.data_ptr(), pts.data_ptr(), self._stream())
         return hit.to(torch.bool), t, pts
@@ -884,10 +933,7 @@ class HipRaster:
     COVER_LDS_N = 56     # ... up to which a workgroup keeps its accumulators in LDS (csrc/cover.hip)
 
     def _cover_points(self, points):
-        p_t = self._dev(points, _torch().float64)
-        if p_t.ndim != 2 or p_t.shape[1] != 3:
-            raise ValueError(f"points must be (V, 3), got {tuple(p_t.shape)}")
-        return p_t
+        return self._shaped(points, _torch().float64, ("V", 3), "points")
 
     def points_bounds(self, points, stride: int = 1):
         """gr_points_bounds: points (V, 3) float64, numpy or device tensor (a non-contiguous view is made contiguous), of which
@@ -895,8 +941,8 @@ class HipRaster:
         visited finite rows, nonfinite (1,) int64 tensor: the visited rows with a NaN or infinite coordinate).  Only enqueues."""
         torch = _torch()
         p_t = self._cover_points(points)
-        bounds = torch.empty((6,), dtype=torch.float64, device=self.device)
-        nonfinite = torch.empty((1,), dtype=torch.int64, device=self.device)
+        bounds = self._empty((6,), torch.float64)
+        nonfinite = self._empty((1,), torch.int64)
         self._call("gr_points_bounds", p_t.data_ptr(), int(p_t.shape[0]), int(stride), bounds.data_ptr(), nonfinite.data_ptr(),
                    self._stream())
         return bounds, nonfinite
@@ -912,9 +958,9 @@ class HipRaster:
         N = int(tabs[0].shape[0])
         if any(int(t.shape[0]) != N for t in tabs):
             raise ValueError(f"the four bound tables must have one length, got {[int(t.shape[0]) for t in tabs]}")
-        z_max = torch.empty((N, N), dtype=torch.float64, device=self.device)
-        z_min = torch.empty((N, N), dtype=torch.float64, device=self.device)
-        count = torch.empty((N, N), dtype=torch.int32, device=self.device)   # uint32 payload
+        z_max = self._empty((N, N), torch.float64)
+        z_min = self._empty((N, N), torch.float64)
+        count = self._empty((N, N), torch.int32)   # uint32 payload
         self._call("gr_cover_grid", p_t.data_ptr(), int(p_t.shape[0]), int(stride), N, *(t.data_ptr() for t in tabs),
                    z_max.data_ptr(), z_min.data_ptr(), count.data_ptr(), self._stream())
         return z_max, z_min, count
@@ -941,14 +987,12 @@ class HipRaster:
         if n_faces < 0 or n_views < 0 or int(ptr_t.shape[0]) != n_faces + 1:
             raise ValueError(f"face_ptr must hold n_faces + 1 = {n_faces + 1} offsets, got {int(ptr_t.shape[0])}")
         nnz = int(views_t.shape[0])
-        selected = torch.empty((max(n_views, 1),), dtype=torch.uint8, device=self.device)
-        order = torch.empty((max(n_views, 1),), dtype=torch.int32, device=self.device)
-        gains = torch.empty((max(n_views, 1),), dtype=torch.int64, device=self.device)
-        pruned = torch.empty((max(n_views, 1),), dtype=torch.int32, device=self.device)
-        stats = torch.empty((GR_SETCOVER_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        selected, order, gains, pruned = (self._empty((max(n_views, 1),), dtype)
+                                          for dtype in (torch.uint8, torch.int32, torch.int64, torch.int32))
+        stats = self._stats(GR_SETCOVER_STAT_WORDS)
         flags = (GR_SETCOVER_PRUNE if prune else 0) | (GR_SETCOVER_GLOBAL_ATOMICS if global_atomics else 0)
         try:
-            self._call("gr_set_cover", ptr_t.data_ptr(), views_t.data_ptr() if nnz else None, nnz, n_faces, n_views,
+            self._call("gr_set_cover", ptr_t.data_ptr(), _ptr(views_t if nnz else None), nnz, n_faces, n_views,
                        float(min_observations), flags, selected.data_ptr(), order.data_ptr(), gains.data_ptr(), pruned.data_ptr(),
                        stats.data_ptr(), self._stream())
         except IndexError as err:   # GR_EINDEX: the input is wrong, not a position the caller asked for
@@ -970,17 +1014,14 @@ class HipRaster:
         `PlanarPolygons.snapped` -> (weights (P, n_classes) float64 tensor, stats (GR_POLY_STAT_WORDS,) int64 tensor: pairs
         tested, pairs contributing, largest ring).  `within`: exact containment (sjoin), else clipped overlay.  Only enqueues."""
         torch = _torch()
-        tri_t = self._dev(tri, torch.int64)
         cls_t = self._dev(face_class, torch.int32)
-        w_t = self._dev(face_weight, torch.float64)
         F, C = int(cls_t.shape[0]), int(n_classes)
-        if tri_t.ndim != 2 or tuple(tri_t.shape) != (F, 6) or tuple(w_t.shape) != (F,):
-            raise ValueError(f"faces must be (F, 6) corners, (F,) classes and (F,) weights, got {tuple(tri_t.shape)}, "
-                             f"{tuple(cls_t.shape)} and {tuple(w_t.shape)}")
+        tri_t = self._shaped(tri, torch.int64, (F, 6), "face corners (a row per face class)")
+        w_t = self._shaped(face_weight, torch.float64, (F,), "face weights (one per face class)")
         rv_t, off_t, rp_t, box_t, rh_t, n_rv, R, P = self._ring_table(ring_vertices, ring_offsets, ring_polygon, polygon_boxes,
                                                                       ring_is_hole)
-        weights = torch.empty((P, C), dtype=torch.float64, device=self.device)
-        stats = torch.empty((GR_POLY_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        weights = self._empty((P, C), torch.float64)
+        stats = self._stats(GR_POLY_STAT_WORDS)
         self._call("gr_polygon_class_weights", tri_t.data_ptr(), cls_t.data_ptr(), w_t.data_ptr(), F, rv_t.data_ptr(),
                    n_rv, off_t.data_ptr(), rp_t.data_ptr(), rh_t.data_ptr(), R, box_t.data_ptr(), P,
                    GR_POLY_WITHIN if within else GR_POLY_OVERLAY, C, weights.data_ptr(), stats.data_ptr(), self._stream())
@@ -1012,13 +1053,13 @@ class HipRaster:
         if abs(nx) >= 2 ** 31 or abs(ny) >= 2 ** 31:
             raise ValueError(f"gr_face_polygon_index: bad cell grid nx={nx} ny={ny}")
         F = int(f_t.shape[0])
-        out = torch.empty((F,), dtype=torch.int32, device=self.device)
-        stats = torch.empty((GR_FPI_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        out = self._empty((F,), torch.int32)
+        stats = self._stats(GR_FPI_STAT_WORDS)
         self._call("gr_face_polygon_index", vq_t.data_ptr(), int(vq_t.shape[0]), f_t.data_ptr(), F, rv_t.data_ptr(),
                    n_rv, off_t.data_ptr(), rp_t.data_ptr(), R, box_t.data_ptr(), P, x0, y0, cw, ch, nx, ny,
                    co_t.data_ptr(), cp_t.data_ptr(), int(cp_t.shape[0]), out.data_ptr(), stats.data_ptr(), self._stream())
         if check:
-            self._raise_bad_faces("gr_face_polygon_index", int(stats[GR_FPI_STAT_BAD_FACES].item()), int(vq_t.shape[0]))
+            self._check_faces("gr_face_polygon_index", stats, GR_FPI_STAT_BAD_FACES, int(vq_t.shape[0]))
         return out, stats
 
     # -- region of interest: points in a buffered union of polygon rows, the sub-mesh they select ----------------------
@@ -1029,16 +1070,14 @@ class HipRaster:
         some ring; stats (GR_PIR_STAT_WORDS,) int64 tensor: points inside, inside by the buffer only, 256-bit comparisons
         formed).  Only enqueues."""
         torch = _torch()
-        pq_t = self._dev(points_q, torch.int64)
-        if pq_t.ndim != 2 or pq_t.shape[1] != 2:
-            raise ValueError(f"points must be (N, 2), got {tuple(pq_t.shape)}")
+        pq_t = self._shaped(points_q, torch.int64, ("N", 2), "points")
         rv_t, off_t, rp_t, box_t, _, n_rv, R, P = self._ring_table(ring_vertices, ring_offsets, ring_polygon, polygon_boxes)
         D = int(buffer_steps)
         if not 0 <= D < 2 ** 40:
             raise ValueError(f"gr_points_in_region: buffer D={D} outside [0, 2^40) grid steps")
         N = int(pq_t.shape[0])
-        mask = torch.empty((N,), dtype=torch.uint8, device=self.device)
-        stats = torch.empty((GR_PIR_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        mask = self._empty((N,), torch.uint8)
+        stats = self._stats(GR_PIR_STAT_WORDS)
         self._call("gr_points_in_region", pq_t.data_ptr(), N, rv_t.data_ptr(), n_rv, off_t.data_ptr(),
                    rp_t.data_ptr(), R, box_t.data_ptr(), P, D, mask.data_ptr(), stats.data_ptr(), self._stream())
         return mask.to(torch.bool), stats
@@ -1052,19 +1091,18 @@ class HipRaster:
         ValueError when a face names a vertex that does not exist."""
         torch = _torch()
         m_t = self._dev(mask, torch.bool).to(torch.uint8).reshape(-1)
-        f_t = self._dev(faces, torch.int32)
-        if f_t.ndim != 2 or f_t.shape[1] != 3:
-            raise ValueError(f"faces must be (F, 3), got {tuple(f_t.shape)}")
+        f_t = self._shaped(faces, torch.int32, ("F", 3), "faces")
         V, F = int(m_t.shape[0]), int(f_t.shape[0])
-        face_ids = torch.empty((F,), dtype=torch.int64, device=self.device)
-        point_ids = torch.empty((V,), dtype=torch.int64, device=self.device)
-        new_faces = torch.empty((F, 3), dtype=torch.int32, device=self.device)
-        counts = torch.empty((3,), dtype=torch.int64, device=self.device)
+        face_ids = self._empty((F,), torch.int64)
+        point_ids = self._empty((V,), torch.int64)
+        new_faces = self._empty((F, 3), torch.int32)
+        counts = self._empty((3,), torch.int64)
         self._call("gr_submesh_extract", m_t.data_ptr(), V, f_t.data_ptr(), F, face_ids.data_ptr(), point_ids.data_ptr(),
                    new_faces.data_ptr(), counts.data_ptr(), self._stream())
-        n_faces, n_points, n_bad = (int(v) for v in counts.cpu())
+        on_host = counts.cpu()   # the one read of all three counts
+        n_faces, n_points = int(on_host[0]), int(on_host[1])
         if check:
-            self._raise_bad_faces("gr_submesh_extract", n_bad, V)
+            self._check_faces("gr_submesh_extract", on_host, 2, V)
         return face_ids[:n_faces], point_ids[:n_points], new_faces[:n_faces], counts
 
     # -- class outlines: the rings around the faces of every class -------------------------------------------------
@@ -1084,34 +1122,28 @@ class HipRaster:
             raise ValueError(f"{F} faces need {F} classes, got {int(c_t.shape[0])}")
         if not 0 <= int(n_classes) <= GR_OUTL_MAX_CLASSES:
             raise ValueError(f"gr_class_outlines: n_classes={int(n_classes)} outside [0, {GR_OUTL_MAX_CLASSES}]")
-        cap = F + 64 if capacity is None else int(capacity)
-        stats = torch.empty((GR_OUTL_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        stats = self._stats(GR_OUTL_STAT_WORDS)
         n_edges, n_rings = ctypes.c_int64(0), ctypes.c_int64(0)
-        self.last_outline_calls = 0
-        for _attempt in range(2):
-            canon = torch.empty((V,), dtype=torch.int32, device=self.device)
-            ring_vertices = torch.empty((max(cap, 1),), dtype=torch.int32, device=self.device)
-            ring_offsets = torch.empty((cap // 3 + 1,), dtype=torch.int64, device=self.device)
-            ring_class = torch.empty((max(cap // 3, 1),), dtype=torch.int32, device=self.device)
-            with torch.cuda.device(self.device):
-                rc = self.lib.gr_class_outlines(
-                    self._ctx, vq_t.data_ptr(), V, f_t.data_ptr(), F, c_t.data_ptr(), int(n_classes),
-                    canon.data_ptr() if cap else None, ring_vertices.data_ptr() if cap else None,
-                    ring_offsets.data_ptr() if cap else None, ring_class.data_ptr() if cap else None, cap,
-                    ctypes.byref(n_edges), ctypes.byref(n_rings), stats.data_ptr(), self._stream())
-            self.last_outline_calls += 1
+
+        def attempt(cap):
+            canon = self._empty((V,), torch.int32)
+            ring_vertices = self._empty((max(cap, 1),), torch.int32)
+            ring_offsets = self._empty((cap // 3 + 1,), torch.int64)
+            ring_class = self._empty((max(cap // 3, 1),), torch.int32)
+            rc = self._rc("gr_class_outlines", vq_t.data_ptr(), V, f_t.data_ptr(), F, c_t.data_ptr(), int(n_classes),
+                          *(_ptr(t if cap else None) for t in (canon, ring_vertices, ring_offsets, ring_class)), cap,
+                          ctypes.byref(n_edges), ctypes.byref(n_rings), stats.data_ptr(), self._stream())
             E, R = int(n_edges.value), int(n_rings.value)
-            if rc == GR_EOVERFLOW or (rc == GR_OK and cap == 0 and (E > 0 or V > 0)):
-                cap = max(E, 1)   # the library counted every ring vertex: the repeat fits exactly
-                continue
-            self._check(rc, "gr_class_outlines")
-            if check:
-                self._raise_bad_faces("gr_class_outlines", int(stats[GR_OUTL_STAT_BAD_FACES].item()), V)
-            if cap == 0:
-                ring_offsets.zero_()
-            return canon, ring_vertices[:E], ring_offsets[:R + 1], ring_class[:R], stats
-        self._check(rc, "gr_class_outlines")
-        raise RuntimeError("gr_class_outlines reported two different totals for the same input")
+            return rc, E, (canon, ring_vertices[:E], ring_offsets[:R + 1], ring_class[:R], stats)
+
+        cap = F + 64 if capacity is None else int(capacity)
+        self.last_outline_calls = 0
+        result, self.last_outline_calls = _count_then_fill("gr_class_outlines", attempt, cap, lambda E: E > 0 or V > 0, self._check)
+        if check:
+            self._check_faces("gr_class_outlines", stats, GR_OUTL_STAT_BAD_FACES, V)
+        if cap == 0 and self.last_outline_calls == 1:
+            result[2].zero_()   # ring_offsets of a call that had nothing to fill and no room to write the one 0
+        return result
 
     # -- raster samples: the value of a raster under every face centre or vertex -----------------------------------
     def sample_raster(self, points, faces, raster_data, inverse6, nodata, fill, *, want_values: bool = True,
@@ -1126,24 +1158,9 @@ class HipRaster:
         returned, anything else is copied to the device first.  `check` (default) reads the statistics back and raises ValueError
         when a face names a vertex that does not exist; check=False only enqueues."""
         torch = _torch()
-        p_t = self._dev(points, torch.float64)
-        if p_t.ndim != 2 or p_t.shape[1] != 3:
-            raise ValueError(f"points must be (V, 3), got {tuple(p_t.shape)}")
-        V = int(p_t.shape[0])
-        f_t = None
-        if faces is not None:
-            f_t = self._dev(faces, torch.int32)
-            if f_t.ndim != 2 or f_t.shape[1] != 3:
-                raise ValueError(f"faces must be (F, 3), got {tuple(f_t.shape)}")
-        N = V if f_t is None else int(f_t.shape[0])
-        if isinstance(raster_data, torch.Tensor):
-            is_f32 = raster_data.dtype == torch.float32
-        else:
-            raster_data = np.asarray(raster_data)
-            is_f32 = raster_data.dtype == np.float32
-            if not is_f32:
-                raster_data = raster_data.astype(np.float64)   # on the host: exact for the integer dtypes of a DTM
-        r_t = self._dev(raster_data, torch.float32 if is_f32 else torch.float64)
+        p_t, f_t, V, N = self._points_faces(points, faces)
+        raster_data, dtype_name, raster_dtype = _float_kind(raster_data)
+        r_t = self._dev(raster_data, getattr(torch, dtype_name))
         if r_t.ndim == 2:
             r_t = r_t[None]
         if r_t.ndim != 3 or min(r_t.shape) < 1:
@@ -1160,19 +1177,18 @@ class HipRaster:
             lab_t = self._dev(labels, torch.float64)
             if lab_t.numel() != N or lab_t.ndim > 2:
                 raise ValueError(f"labels must be ({N},) or ({N}, 1), got {tuple(lab_t.shape)}")
-        values = torch.empty((N, B), dtype=torch.float64, device=self.device) if want_values else None
-        height = torch.empty((N,), dtype=torch.float64, device=self.device) if want_height else None
-        stats = torch.zeros((GR_RS_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        values = self._empty((N, B), torch.float64) if want_values else None
+        height = self._empty((N,), torch.float64) if want_height else None
+        stats = self._stats(GR_RS_STAT_WORDS, zeroed=True)
         if N > 0:   # (an empty tensor has no address: null faces would mean vertex mode)
-            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-            self._call("gr_sample_raster", p_t.data_ptr(), V, ptr(f_t), 0 if f_t is None else N, r_t.data_ptr(),
-                       GR_DTYPE_F32 if is_f32 else GR_DTYPE_F64, B, H, W, ctypes.addressof(inv_h), 0 if nodata is None else 1,
-                       0.0 if nodata is None else float(nodata), float(fill), ptr(values), ptr(height), ptr(lab_t),
+            self._call("gr_sample_raster", p_t.data_ptr(), V, _ptr(f_t), 0 if f_t is None else N, r_t.data_ptr(),
+                       raster_dtype, B, H, W, ctypes.addressof(inv_h), 0 if nodata is None else 1,
+                       0.0 if nodata is None else float(nodata), float(fill), _ptr(values), _ptr(height), _ptr(lab_t),
                        float("nan") if threshold is None else float(threshold),
                        float("nan") if ground_id is None else float(ground_id),
                        GR_RS_FLAG_ONLY_EXISTING if only_existing else 0, stats.data_ptr(), self._stream())
             if check:
-                self._raise_bad_faces("gr_sample_raster", int(stats[GR_RS_STAT_BAD_FACES].item()), V)
+                self._check_faces("gr_sample_raster", stats, GR_RS_STAT_BAD_FACES, V)
         return values, height, lab_t, stats
 
     # -- CRS reprojection: points between the WGS84 systems ------------------------------------------------------------
@@ -1187,18 +1203,7 @@ class HipRaster:
         from geograypher_amd.utils.geospatial import crs_tuple
 
         torch = _torch()
-        p_t = self._dev(points, torch.float64)
-        if p_t.ndim != 2 or p_t.shape[1] != 3:
-            raise ValueError(f"points must be (V, 3), got {tuple(p_t.shape)}")
-        p_t = p_t.contiguous()
-        V = int(p_t.shape[0])
-        f_t = None
-        if faces is not None:
-            f_t = self._dev(faces, torch.int32)
-            if f_t.ndim != 2 or f_t.shape[1] != 3:
-                raise ValueError(f"faces must be (F, 3), got {tuple(f_t.shape)}")
-            f_t = f_t.contiguous()
-        N = V if f_t is None else int(f_t.shape[0])
+        p_t, f_t, V, N = self._points_faces(points, faces)
         sides = [Crs(int(k), float(lon0), float(k0), float(fe), float(fn)) for k, lon0, k0, fe, fn in
                  (crs_tuple(from_crs), crs_tuple(to_crs))]
         pre_h = None
@@ -1208,63 +1213,49 @@ class HipRaster:
                 raise ValueError(f"pre_transform must be (4, 4), got {pre.shape}")
             pre_h = (ctypes.c_double * 16)(*pre.reshape(-1).tolist())
         if out is None:
-            out = torch.empty((N, 3), dtype=torch.float64, device=self.device)
+            out = self._empty((N, 3), torch.float64)
         elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (N, 3)
               or not out.is_contiguous() or out.device != p_t.device):
             raise ValueError(f"out must be a contiguous float64 ({N}, 3) tensor on {p_t.device}")
-        stats = torch.zeros((GR_CRS_STAT_WORDS,), dtype=torch.int64, device=self.device)
+        stats = self._stats(GR_CRS_STAT_WORDS, zeroed=True)
         if N > 0:   # (an empty tensor has no address: null faces would mean vertex mode)
-            self._call("gr_reproject_points", p_t.data_ptr() if V else None, V, None if f_t is None else f_t.data_ptr(),
-                       0 if f_t is None else N, None if pre_h is None else ctypes.addressof(pre_h), ctypes.byref(sides[0]),
-                       ctypes.byref(sides[1]), out.data_ptr(), stats.data_ptr(), self._stream())
+            self._call("gr_reproject_points", _ptr(p_t if V else None), V, _ptr(f_t), 0 if f_t is None else N,
+                       None if pre_h is None else ctypes.addressof(pre_h), ctypes.byref(sides[0]), ctypes.byref(sides[1]),
+                       out.data_ptr(), stats.data_ptr(), self._stream())
             if check and f_t is not None:
-                self._raise_bad_faces("gr_reproject_points", int(stats[GR_CRS_STAT_BAD_FACES].item()), V)
+                self._check_faces("gr_reproject_points", stats, GR_CRS_STAT_BAD_FACES, V)
         return out, stats
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):
         torch = _torch()
-        votes = torch.zeros((self.n_faces, C), dtype=torch.int32, device=self.device)  # uint32 payload
-        counts = torch.zeros((self.n_faces,), dtype=torch.int32, device=self.device)
+        votes = self._zeros((self.n_faces, C), torch.int32)  # uint32 payload
+        counts = self._zeros((self.n_faces,), torch.int32)
         return votes, counts
 
     def project_labels(self, ids, labels, C: int, votes, counts, neg1_is_last_face: bool = True):
         """ids (N,h,w) int32, labels (N,h,w) uint8 class indices; accumulates into votes (F,C), counts (F,)."""
-        torch = _torch()
-        ids_t = self._dev(ids, torch.int32)
-        lab_t = self._dev(labels, torch.uint8)
-        if ids_t.ndim == 2:
-            ids_t, lab_t = ids_t[None], lab_t[None]
-        if ids_t.shape != lab_t.shape:
-            raise ValueError(f"ids {tuple(ids_t.shape)} and labels {tuple(lab_t.shape)} differ in shape")
+        ids_t, lab_t = self._view_batch(ids, labels, _torch().uint8, "labels")
         n, h, w = (int(x) for x in ids_t.shape)
         self._call("gr_project_labels_u8", ids_t.data_ptr(), lab_t.data_ptr(), n, h, w, C, votes.data_ptr(),
                    counts.data_ptr(), _flags(neg1_is_last_face), self._stream())
 
     def project_values(self, ids, img, sums, counts, neg1_is_last_face: bool = True):
         """ids (N,h,w) int32, img (N,h,w,C) float64; accumulates nansum into sums (F,C) and counts (F,)."""
-        torch = _torch()
-        ids_t = self._dev(ids, torch.int32)
-        img_t = self._dev(img, torch.float64)
-        if ids_t.ndim == 2:
-            ids_t, img_t = ids_t[None], img_t[None]
+        ids_t, img_t = self._view_batch(ids, img, _torch().float64, "img", channels=True)
         n, h, w = (int(x) for x in ids_t.shape)
         C = int(img_t.shape[-1])
-        if tuple(img_t.shape) != (n, h, w, C):
-            raise ValueError(f"img {tuple(img_t.shape)} does not match ids {tuple(ids_t.shape)}")
         self._call("gr_project_values_f64", ids_t.data_ptr(), img_t.data_ptr(), n, h, w, C, sums.data_ptr(),
                    counts.data_ptr(), _flags(neg1_is_last_face), self._stream())
 
     def project_view(self, ids, img, neg1_is_last_face: bool = True):
         """One view of project_images: ids (h,w) int32, img (h,w,C) float64 -> (F,C) float64, NaN for unseen faces."""
         torch = _torch()
-        ids_t = self._dev(ids, torch.int32)
-        img_t = self._dev(img, torch.float64)
+        ids_t = self._shaped(ids, torch.int32, ("h", "w"), "ids")
         h, w = (int(x) for x in ids_t.shape)
+        img_t = self._shaped(img, torch.float64, (h, w, "C"), "img")
         C = int(img_t.shape[-1])
-        if tuple(img_t.shape) != (h, w, C):
-            raise ValueError(f"img {tuple(img_t.shape)} does not match ids {tuple(ids_t.shape)}")
-        tex = torch.empty((self.n_faces, C), dtype=torch.float64, device=self.device)
+        tex = self._empty((self.n_faces, C), torch.float64)
         self._call("gr_project_view_f64", ids_t.data_ptr(), img_t.data_ptr(), h, w, C, tex.data_ptr(), _flags(neg1_is_last_face),
                    self._stream())
         return tex
@@ -1285,7 +1276,7 @@ class HipRaster:
         # (after an overflow the votes of the first views_done views are in; the library skipped the rest on the device)
         self._checked_raster(n, check, lambda v0: self._call(
             "gr_raster_project_labels_u8", cams_t[v0:].data_ptr(), lab_t[v0:].data_ptr(), n - v0, h, w, C, votes.data_ptr(),
-            counts.data_ptr(), ids_out[v0:].data_ptr() if ids_out is not None else None, flags, self._stream()))
+            counts.data_ptr(), _ptr(None if ids_out is None else ids_out[v0:]), flags, self._stream()))
         return ids_out
 
     # -- get_image(image_scale) behind the file read (row a5) -----------------------------------------------------
@@ -1316,7 +1307,7 @@ class HipRaster:
         h_out, w_out = (h_in, w_in) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
         if divide_by_255 is None:
             divide_by_255 = name == "uint8"
-        out = torch.empty((h_out, w_out) + tuple(t.shape[2:]), dtype=torch.float64, device=self.device)
+        out = self._empty((h_out, w_out) + tuple(t.shape[2:]), torch.float64)
         self._call("gr_resize_image_f64", t.data_ptr(), self._RESIZE_DTYPES[name], h_in, w_in, C, 1 if divide_by_255 else 0,
                    h_out, w_out, out.data_ptr(), self._stream())
         return out
@@ -1386,22 +1377,21 @@ class HipRaster:
         native = os_ == 1
         res = []
         with torch.cuda.device(self.device):
-            mask = torch.zeros((H, W + 1), dtype=torch.uint8, device=self.device) if return_mask else None
-            dbg = torch.empty((2, len(y), len(x)), dtype=torch.float64, device=self.device) if return_debug else None
+            mask = self._zeros((H, W + 1), torch.uint8) if return_mask else None
+            dbg = self._empty((2, len(y), len(x)), torch.float64) if return_debug else None
             vrange, bounds = source.vrange, source.bounds
             if vrange == 0 and (return_mask or return_debug):   # the coordinates are still wanted: a unit range samples zeros
-                vrange, bounds = 1.0, torch.zeros((C, 2), dtype=torch.float64, device=self.device)
+                vrange, bounds = 1.0, self._zeros((C, 2), torch.float64)
             if vrange == 0:   # image.py:94-97: no variation, the fill everywhere; nothing to launch
-                out = torch.zeros((out_h, out_w, C), dtype=source.tensor.dtype if native else torch.float64, device=self.device)
+                out = self._zeros((out_h, out_w, C), source.tensor.dtype if native else torch.float64)
             else:
-                out = torch.empty((out_h, out_w, C), dtype=source.tensor.dtype if native else torch.float64, device=self.device)
+                out = self._empty((out_h, out_w, C), source.tensor.dtype if native else torch.float64)
                 xy = torch.as_tensor(np.concatenate([x, y])).to(self.device)
                 R = (ctypes.c_double * 9)(*[float(v) for v in np.asarray(rot, dtype=np.float64).reshape(9)])
                 dtype = GR_DTYPE_U8 if source.np_dtype == np.uint8 else GR_DTYPE_F64
                 self._call("gr_equirect_view", source.tensor.data_ptr(), dtype, H, W, C, xy.data_ptr(),
                            xy.data_ptr() + 8 * len(x), R, out_h, out_w, os_, int(order), source.vmin, vrange,
-                           bounds.data_ptr(), out.data_ptr(), mask.data_ptr() if mask is not None else None,
-                           dbg.data_ptr() if dbg is not None else None, self._stream())
+                           bounds.data_ptr(), out.data_ptr(), _ptr(mask), _ptr(dbg), self._stream())
             if mask is not None:   # image.py:261-265: the appended column belongs to column 0
                 mask[:, 0] |= mask[:, W]
                 mask = mask[:, :W]
@@ -1416,11 +1406,7 @@ class HipRaster:
     # -- distortion warp (row f1) --------------------------------------------------------------------------------
     def upload_map(self, inverse_map):
         """(2, H, W) float64 sampling map (rows, cols) -> device tensor."""
-        torch = _torch()
-        m = self._dev(inverse_map, torch.float64)
-        if m.ndim != 3 or m.shape[0] != 2:
-            raise ValueError(f"sampling map must be (2, H, W), got {tuple(m.shape)}")
-        return m
+        return self._shaped(inverse_map, _torch().float64, (2, "H", "W"), "sampling map")
 
     LENS_PARAMS = ("f", "cx", "cy", "image_width", "image_height", "k1", "k2", "k3", "k4", "p1", "p2", "b1", "b2")
 
@@ -1434,7 +1420,7 @@ class HipRaster:
         if unknown:
             raise ValueError(f"Unexpected distortion params found: {sorted(unknown)}")
         par = (ctypes.c_double * 13)(*[float(params.get(k, 0.0)) for k in self.LENS_PARAMS])
-        out = torch.empty((2, h, w), dtype=torch.float64, device=self.device)
+        out = self._empty((2, h, w), torch.float64)
         self._call("gr_invert_distortion_f64", par, int(h), int(w), float(image_scale), int(max_iters), float(fill),
                    out[0].data_ptr(), out[1].data_ptr(), self._stream())
         return out
@@ -1483,7 +1469,7 @@ class HipRaster:
                 outs = []
                 for ch in range(src.shape[2]):
                     plane = src[..., ch].contiguous()
-                    out = torch.empty((h_out, w_out), dtype=torch.int32, device=self.device)
+                    out = self._empty((h_out, w_out), torch.int32)
                     self._call("gr_warp_nearest_i32", plane.data_ptr(), h_in, w_in, map_t[0].data_ptr(), map_t[1].data_ptr(),
                                h_out, w_out, int(fill_value), 1 if reference_float_roundtrip else 0, lo, hi - lo,
                                out.data_ptr(), self._stream())
@@ -1496,7 +1482,7 @@ class HipRaster:
                     src = src[..., None]
                 src = src.contiguous()
                 C = int(src.shape[2])
-                res = torch.empty((h_out, w_out, C), dtype=torch.float64, device=self.device)
+                res = self._empty((h_out, w_out, C), torch.float64)
                 self._call("gr_warp_f64", src.data_ptr(), h_in, w_in, C, map_t[0].data_ptr(), map_t[1].data_ptr(), h_out,
                            w_out, int(order), float(fill_value), res.data_ptr(), self._stream())
                 if squeeze:
@@ -1509,9 +1495,9 @@ class HipRaster:
         """(votes, counts) -> average (F,C), summed (F,C), counts (F,) float64 tensors (meshes.py:2069-2082)."""
         torch = _torch()
         F, C = int(votes.shape[0]), int(votes.shape[1])
-        avg = torch.empty((F, C), dtype=torch.float64, device=self.device)
-        summed = torch.empty((F, C), dtype=torch.float64, device=self.device)
-        cnt = torch.empty((F,), dtype=torch.float64, device=self.device)
+        avg = self._empty((F, C), torch.float64)
+        summed = self._empty((F, C), torch.float64)
+        cnt = self._empty((F,), torch.float64)
         self._call("gr_finalize_votes", votes.data_ptr(), counts.data_ptr(), F, C, avg.data_ptr(), summed.data_ptr(),
                    cnt.data_ptr(), self._stream())
         return avg, summed, cnt
@@ -1519,8 +1505,8 @@ class HipRaster:
     def finalize_sums(self, sums, counts):
         torch = _torch()
         F, C = int(sums.shape[0]), int(sums.shape[1])
-        avg = torch.empty((F, C), dtype=torch.float64, device=self.device)
-        cnt = torch.empty((F,), dtype=torch.float64, device=self.device)
+        avg = self._empty((F, C), torch.float64)
+        cnt = self._empty((F,), torch.float64)
         self._call("gr_finalize_sums_f64", sums.data_ptr(), counts.data_ptr(), F, C, avg.data_ptr(), cnt.data_ptr(),
                    self._stream())
         return avg, sums, cnt
@@ -1531,14 +1517,9 @@ class HipRaster:
         below 2^53.  The row sum follows numpy's pairwise order for a C-contiguous array; a Fortran-ordered array (which
         numpy sums left to right) is made C-contiguous here and summed in that order."""
         torch = _torch()
-        if isinstance(array, torch.Tensor):
-            is_f32 = array.dtype == torch.float32
-        else:
-            array = np.asarray(array)
-            is_f32 = array.dtype == np.float32
-        arr = self._dev(array, torch.float32 if is_f32 else torch.float64)
-        dtype = GR_DTYPE_F32 if is_f32 else GR_DTYPE_F64
+        array, dtype_name, dtype = _float_kind(array)
+        arr = self._dev(array, getattr(torch, dtype_name))
         F, C = int(arr.shape[0]), int(arr.shape[1])
-        out = torch.empty((F,), dtype=torch.float64, device=self.device)
+        out = self._empty((F,), torch.float64)
         self._call("gr_argmax_nonzero", arr.data_ptr(), dtype, F, C, out.data_ptr(), self._stream())
         return out

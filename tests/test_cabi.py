@@ -19,6 +19,42 @@ def test_header_and_binding_agree():
     assert _declared_symbols() == sorted(_hip.EXPORTED_SYMBOLS)
 
 
+def _declarations():
+    """{symbol: [the C text of every argument]} of every function include/geograster.h declares, comments stripped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", (ROOT / "include" / "geograster.h").read_text(), flags=re.S)
+    found = {}
+    for name, args in re.findall(r"\b(gr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in found, name
+        args = " ".join(args.split())
+        found[name] = [] if args in ("", "void") else [a.strip() for a in args.split(",")]
+    return found
+
+
+def _kind(c_argument=None, ctype=None):
+    """The kind of a header argument, or of a ctypes argument type: pointer, int64, int, double."""
+    if ctype is not None:
+        if ctype in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ctype, ctypes._Pointer):
+            return "pointer"
+        return {ctypes.c_int64: "int64", ctypes.c_int: "int", ctypes.c_int32: "int", ctypes.c_double: "double"}[ctype]
+    if "*" in c_argument:
+        return "pointer"
+    words = [w for w in re.findall(r"\w+", c_argument) if w != "const"]
+    return {"int64_t": "int64", "int": "int", "int32_t": "int", "double": "double"}[words[0]]
+
+
+def test_every_signature_agrees_with_the_header_in_count_and_kind():
+    """All symbols at once: the binding hands the library as many arguments as the header declares, and each is of the declared
+    kind (a pointer, a 64-bit integer, an int, a double).  A short `argtypes` list, or an int where the library reads an
+    int64_t, is a bad pointer or a bad size in a kernel's arguments."""
+    declared = _declarations()
+    assert sorted(declared) == sorted(_hip._SIGNATURES) and len(declared) == 45
+    for name, arguments in declared.items():
+        argtypes = _hip._SIGNATURES[name]
+        assert len(arguments) == len(argtypes), f"{name}: the header declares {len(arguments)} arguments, the binding {len(argtypes)}"
+        for k, (argument, ctype) in enumerate(zip(arguments, argtypes)):
+            assert _kind(argument) == _kind(ctype=ctype), f"{name}, argument {k} ({argument!r}) is bound as {ctype.__name__}"
+
+
 def test_library_exports_every_declared_symbol_at_header_version_126():
     """Every declared symbol is exported, and the library reports the version the header declares (126: gr_warp_f64 reads
     `fill` at infinite coordinates) -- a stale build or a header bumped without the library fails here."""
