@@ -89,8 +89,10 @@ GR_OUTL_STAT_TURNED = 2
 GR_OUTL_STAT_CANCELLED = 3
 GR_OUTL_STAT_MULTI = 4
 GR_OUTL_STAT_BAD_FACES = 5
+GR_OUTL_STAT_BAD_ROWS = 6   # member_outlines alone
 GR_OUTL_STAT_WORDS = 8
 GR_OUTL_MAX_CLASSES = 65535
+GR_MEMBER_MAX_CLASSES = 2 ** 31 - 2   # member_outlines: the sentinel class n_classes fits int32
 # words of sample_raster's statistics block, its relabel flag
 GR_RS_STAT_INSIDE = 0
 GR_RS_STAT_NODATA = 1
@@ -222,6 +224,12 @@ _SIGNATURES = {
     "gr_reproject_points": [_vp, _vp, _i64, _vp, _i64, _vp, ctypes.POINTER(Crs), ctypes.POINTER(Crs), _vp, _vp, _vp],
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# ... and every symbol a companion header declares (include/geograster_outlines.h, which geograster.h includes): the same contract,
+# checked by the tests of the calls themselves.
+_COMPANION_SIGNATURES = {
+    "gr_member_outlines": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64p, _i64p, _vp, _vp],
+}
+COMPANION_SYMBOLS = tuple(_COMPANION_SIGNATURES)
 
 
 def library_path() -> Path:
@@ -244,7 +252,7 @@ def load_library() -> ctypes.CDLL:
     # library's runtime without devices and gr_ctx_create answers GR_ENODEVICE.
     _torch()
     lib = ctypes.CDLL(str(_LIB_PATH))
-    for name, argtypes in _SIGNATURES.items():
+    for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -1143,6 +1151,58 @@ class HipRaster:
             self._check_faces("gr_class_outlines", stats, GR_OUTL_STAT_BAD_FACES, V)
         if cap == 0 and self.last_outline_calls == 1:
             result[2].zero_()   # ring_offsets of a call that had nothing to fill and no room to write the one 0
+        return result
+
+    def member_outlines(self, verts_q, faces, face_ptr, face_members, n_classes: int, capacity: Optional[int] = None,
+                        check: bool = True):
+        """gr_member_outlines: verts_q (V, 2) int64 snapped vertices, faces (F, 3) int and the
+        face-major CSR of a face x class membership as `set_cover` takes it -- face_ptr (F + 1,) int64, face_members (nnz,) int32,
+        strictly ascending within a row; a member outside [0, n_classes) takes no part -- numpy or device tensors -> the 5-tuple of
+        `class_outlines`: the rings of every class, class after class, as `class_outlines` traces each class alone.  One library
+        call whatever the number of classes (count-then-fill; the default offer is 3 nnz ring vertices, which always fits --
+        a member contributes at most its 3 edges --: 20 bytes per member beside the 132 bytes of scratch the call takes per
+        member anyway, where an offer that proved too small would cost a second whole trace; `capacity` offers less).  `check`
+        (default) raises ValueError when a face names a vertex that does not exist or the table is malformed
+        (GR_OUTL_STAT_BAD_ROWS; the library then wrote nothing); with check=False a malformed table gives an empty result and
+        the non-zero word."""
+        torch = _torch()
+        vq_t, f_t = self._mesh_2d(verts_q, faces)
+        ptr_t = self._dev(face_ptr, torch.int64).reshape(-1)
+        mem_t = self._dev(face_members, torch.int32).reshape(-1)
+        V, F, nnz = int(vq_t.shape[0]), int(f_t.shape[0]), int(mem_t.shape[0])
+        if int(ptr_t.shape[0]) != F + 1:
+            raise ValueError(f"gr_member_outlines: face_ptr must hold F + 1 = {F + 1} offsets, got {int(ptr_t.shape[0])}")
+        if not 0 <= int(n_classes) <= GR_MEMBER_MAX_CLASSES:
+            raise ValueError(f"gr_member_outlines: n_classes={int(n_classes)} outside [0, {GR_MEMBER_MAX_CLASSES}]")
+        if 3 * nnz >= 2 ** 31:
+            raise ValueError(f"gr_member_outlines: {nnz} members, one call takes fewer than 2^31 / 3")
+        stats = self._stats(GR_OUTL_STAT_WORDS)
+        n_edges, n_rings = ctypes.c_int64(0), ctypes.c_int64(0)
+
+        def attempt(cap):
+            canon = self._empty((V,), torch.int32)
+            ring_vertices = self._empty((max(cap, 1),), torch.int32)
+            ring_offsets = self._empty((cap // 3 + 1,), torch.int64)
+            ring_class = self._empty((max(cap // 3, 1),), torch.int32)
+            rc = self._rc("gr_member_outlines", vq_t.data_ptr(), V, f_t.data_ptr(), F, ptr_t.data_ptr(),
+                          _ptr(mem_t if nnz else None), nnz, int(n_classes),
+                          *(_ptr(t if cap else None) for t in (canon, ring_vertices, ring_offsets, ring_class)), cap,
+                          ctypes.byref(n_edges), ctypes.byref(n_rings), stats.data_ptr(), self._stream())
+            E, R = int(n_edges.value), int(n_rings.value)
+            return rc, E, (canon, ring_vertices[:E], ring_offsets[:R + 1], ring_class[:R], stats)
+
+        cap = 3 * nnz if capacity is None else int(capacity)
+        self.last_outline_calls = 0
+        result, self.last_outline_calls = _count_then_fill("gr_member_outlines", attempt, cap, lambda E: E > 0 or V > 0, self._check)
+        on_host = stats.cpu()   # the one read of both words
+        if check:
+            self._check_faces("gr_member_outlines", on_host, GR_OUTL_STAT_BAD_FACES, V)
+            n_bad = int(on_host[GR_OUTL_STAT_BAD_ROWS])
+            if n_bad:
+                raise ValueError(f"gr_member_outlines: {n_bad} violations of a well-formed member table (face_ptr rises from 0 to "
+                                 f"{nnz}, the members of a row strictly ascend)")
+        if int(on_host[GR_OUTL_STAT_BAD_ROWS]) or (cap == 0 and self.last_outline_calls == 1):
+            result[2].zero_()   # ring_offsets of a call that wrote nothing: a malformed table, or nothing to fill and no room
         return result
 
     # -- raster samples: the value of a raster under every face centre or vertex -----------------------------------

@@ -32,7 +32,7 @@ def hipcc_path() -> str:
 
 
 def _newest_header() -> float:
-    return max(p.stat().st_mtime for p in HEADERS + [INCLUDE / "geograster.h", Path(__file__)])
+    return max(p.stat().st_mtime for p in HEADERS + [INCLUDE / "geograster.h", INCLUDE / "geograster_outlines.h", Path(__file__)])
 
 
 def needs_build() -> bool:

@@ -16,6 +16,7 @@ NULL_TEXTURE_INT_VALUE = 0
 
 # geograypher/constants.py:22, :25 -- the columns of export_face_labels_vector
 CLASS_ID_KEY = "class_ID"
+INSTANCE_ID_KEY = "instance_ID"   # the detection table's ID column (TabularRectangleSegmentor, project_detections)
 CLASS_NAMES_KEY = "class_names"
 
 # geograypher/constants.py:106-113

@@ -17,6 +17,8 @@
 //                    region of interest: points in a buffered union of rows (k_points_in_region), the sub-mesh they select (k_submesh_flags, k_submesh_write + two scans)
 //                    class outlines: canonical vertices (k_outline_canon), face edges (k_outline_face_edges), cancellation (k_outline_cancel), successors
 //                    (k_outline_successor), leader and rank rounds (k_outline_round), ring emit (k_outline_emit_rings) + radix sorts and scans
+//                    member outlines (detection footprints): the edges of the (face, class) members of a sparse table (k_outline_member_edges),
+//                    then the trace of the class outlines (outline_trace, which both calls share)
 //   terrain.hip      raster samples: the value of a raster under every face centre or vertex, height above it, ground relabel (k_sample_raster); no mesh needed
 //   select.hip       image selection: greedy set cover over a face x view incidence (k_sc_rows, k_sc_scan, k_sc_scatter, k_sc_pick, k_sc_apply,
 //                    k_sc_prune_test, k_sc_prune_apply); no mesh needed

@@ -3,7 +3,8 @@
 // every face CENTRE lies in (gr_face_polygon_index; DESIGN.md "Vector textures"), and the region of interest: which points lie in
 // a buffered union of polygon rows (gr_points_in_region) and the sub-mesh of the faces that touch them (gr_submesh_extract), at
 // the end of the file; DESIGN.md "Region of interest"; and the outline rings of every class of a per-face labelling
-// (gr_class_outlines; DESIGN.md "Class outlines"), behind them.  None needs an uploaded mesh: the caller hands over snapped integer
+// (gr_class_outlines; DESIGN.md "Class outlines") or of a sparse face x class membership (gr_member_outlines; DESIGN.md
+// "Detection footprints"), behind them.  None needs an uploaded mesh: the caller hands over snapped integer
 // coordinates.  The pieces the calls share are defined once: the ring span, the even-odd crossing rule, the checked face load and
 // the statistics reductions (one integer atomic per wave and word) in geom_dev.hpp, the host's check of a ring table
 // (check_ring_table) in front of the entry points.
@@ -20,6 +21,8 @@
 //   GR_POLY_OVERLAY  f64: the ring streamed vertex by vertex through the triangle's three half-planes (Sutherland-Hodgman with
 //                    O(1) state per stage, no per-lane vertex arrays) into a shoelace sum, in coordinates relative to the
 //                    triangle's first vertex
+#include <functional>
+
 #include <hipcub/hipcub.hpp>
 
 #include "geom_dev.hpp"
@@ -555,6 +558,85 @@ __global__ __launch_bounds__(256) void k_outline_face_edges(const int64_t *__res
   stat_count(stats, GR_OUTL_STAT_BAD_FACES, bad, lane);
 }
 
+// Y1-Y3 (gr_member_outlines).  pair [3 nnz], cl [3 nnz]: the directed edges of member m = (face, class) at 3 m .. 3 m + 2, as above.
+// A wave owns 64 consecutive faces.  First a face per lane: its row [lo, hi) of the table, clamped into [0, nnz] (Y2), the index
+// check, the canonical corners and the 128-bit orient -- once per face, however many classes it is in.  Then a member per lane over
+// the wave's stretch of the table, [lo of its first face, hi of its last): the owner is the last lane whose row starts at or before
+// m (six shuffles over the row starts, which rise in a well-formed table), its corners and state come by shuffle, and the stores of
+// a wave are consecutive.  Rows of any length cost the same per member; every loop is bounded by the clamped stretch.  In a
+// malformed table stretches may overlap or leave gaps: every index stays inside [0, nnz), the caller has pre-filled cl, the
+// violations are counted in GR_OUTL_STAT_BAD_ROWS and the host stops behind this kernel's counts.
+enum { MEMBER_BAD = 0, MEMBER_LIVE = 1, MEMBER_TURNED = 2, MEMBER_FLAT = 3 };
+__global__ __launch_bounds__(256) void k_outline_member_edges(const int64_t *__restrict__ vq, int64_t V, const int32_t *__restrict__ faces,
+                                                              int64_t F, const int64_t *__restrict__ face_ptr,
+                                                              const int32_t *__restrict__ members, int64_t nnz, int C,
+                                                              const int32_t *__restrict__ canon, unsigned long long *__restrict__ pair,
+                                                              uint32_t *__restrict__ cl, unsigned long long *__restrict__ stats) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  int32_t lo = 0, hi = 0, a = 0, b = 0, c = 0;
+  int state = MEMBER_BAD;
+  uint32_t bad_rows = 0, n_no_class = 0, n_flat = 0, n_turned = 0;
+  bool bad = false;
+  if (f == 0) bad_rows += (face_ptr[0] != 0) + (face_ptr[F] != nnz);
+  if (f < F) {
+    const int64_t p0 = face_ptr[f], p1 = face_ptr[f + 1];
+    bad_rows += p1 < p0;
+    const int64_t l = min(max(p0, (int64_t)0), nnz), h = min(max(p1, l), nnz);
+    lo = (int32_t)l; hi = (int32_t)h;   // 3 nnz < 2^31
+    int64_t v0, v1, v2;
+    bad = !load_face(faces, f, V, v0, v1, v2);
+    if (!bad) {
+      a = canon[v0]; b = canon[v1]; c = canon[v2];
+      const i128 o = orient(vq[(int64_t)a * 2], vq[(int64_t)a * 2 + 1], vq[(int64_t)b * 2], vq[(int64_t)b * 2 + 1], vq[(int64_t)c * 2],
+                            vq[(int64_t)c * 2 + 1]);
+      state = o == 0 ? MEMBER_FLAT : (o < 0 ? MEMBER_TURNED : MEMBER_LIVE);
+      if (o < 0) { const int32_t t = b; b = c; c = t; }
+    }
+  }
+  // the wave's stretch; a lane behind the last face owns the empty row at its end
+  const int64_t wave_f0 = f - lane;
+  const int n_valid = (int)min((int64_t)64, max(F - wave_f0, (int64_t)0));
+  const int32_t wlo = __builtin_amdgcn_readfirstlane(lo);
+  const int32_t last_hi = __shfl(hi, max(n_valid - 1, 0));
+  const int32_t whi = __builtin_amdgcn_readfirstlane(n_valid > 0 ? last_hi : wlo);
+  if (lane >= n_valid) { lo = whi; hi = whi; }
+  for (int32_t base = wlo; base < whi; base += 64) {
+    const int32_t m = base + lane;   // < 2^31 / 3 + 64
+    int j = 0;
+#pragma unroll
+    for (int step = 32; step > 0; step >>= 1) {
+      const int32_t start = __shfl(lo, j + step);   // j + step <= 63
+      if (start <= m) j += step;
+    }
+    const int32_t olo = __shfl(lo, j), ohi = __shfl(hi, j), oa = __shfl(a, j), ob = __shfl(b, j), oc = __shfl(c, j);
+    const int ostate = __shfl(state, j);
+    if (m < whi) {
+      const int32_t cls = members[m];
+      const bool in_row = m >= olo && m < ohi;   // always, in a well-formed table
+      if (in_row && m > olo) bad_rows += members[m - 1] >= cls;   // Y2: strictly ascending
+      bool live = false;
+      if (in_row && ostate != MEMBER_BAD) {
+        if (cls < 0 || cls >= C) ++n_no_class;
+        else if (ostate == MEMBER_FLAT) ++n_flat;
+        else { live = true; n_turned += ostate == MEMBER_TURNED; }
+      }
+      const uint32_t k = live ? (uint32_t)cls : (uint32_t)C;
+      const unsigned long long ua = (uint32_t)oa, ub = (uint32_t)ob, uc = (uint32_t)oc;
+      const int64_t e = (int64_t)m * 3;
+      pair[e] = live ? (ua << 31 | ub) : 0ull;
+      pair[e + 1] = live ? (ub << 31 | uc) : 0ull;
+      pair[e + 2] = live ? (uc << 31 | ua) : 0ull;
+      cl[e] = k; cl[e + 1] = k; cl[e + 2] = k;
+    }
+  }
+  stat_add_u32(stats, GR_OUTL_STAT_NO_CLASS, n_no_class, lane);   // every sum is at most nnz < 2^30
+  stat_add_u32(stats, GR_OUTL_STAT_ZERO_AREA, n_flat, lane);
+  stat_add_u32(stats, GR_OUTL_STAT_TURNED, n_turned, lane);
+  stat_count(stats, GR_OUTL_STAT_BAD_FACES, bad, lane);
+  stat_add_u32(stats, GR_OUTL_STAT_BAD_ROWS, bad_rows, lane);
+}
+
 // pair, cl [n] sorted by (class, from, to).  flag [n] = 1 where a run of equal real edges starts.
 __global__ __launch_bounds__(256) void k_outline_run_heads(const unsigned long long *__restrict__ pair, const uint32_t *__restrict__ cl,
                                                            int64_t n, int C, int32_t *__restrict__ flag) {
@@ -688,6 +770,24 @@ static int check_ring_table(gr_ctx *c, const char *name, int64_t n_rv, int64_t R
   if (((boxes_with_rings ? R : P) > 0 && !pbox) || (R > 0 && (!roff || !rpoly || (n_rv > 0 && !rv)))) return fail(c, GR_EINVAL, "%s: null ring table", name);
   return GR_OK;
 }
+
+// The trace both outline calls share, defined behind them (X2, X4-X6; DESIGN.md sections 8i and 8l): canonical vertices, then
+// `emit_edges(canon, pair, cl)` enqueues the one kernel in which they differ -- the N3 directed edges as from << 31 | to and the
+// class, n_classes for an edge that takes no part --, then the two-pass edge sort, runs, cancellation, scratch B, successors,
+// pointer doubling and the ring emit.
+// member_rows: the edges come from a member table (Y2): cl is pre-filled with 0xFFFFFFFF, which no class reaches, so that a gap of
+// a malformed table holds no uninitialised word, and GR_OUTL_STAT_BAD_ROWS is read at the first synchronisation: non-zero ends the
+// call there with GR_OK, both totals 0 and nothing written but the statistics.
+struct OutlineOut {
+  int32_t *canon, *ring_vertices;
+  int64_t *ring_offsets;
+  int32_t *ring_class;
+  int64_t cap, *n_edges_h, *n_rings_h;
+  unsigned long long *stats;
+};
+static int outline_trace(gr_ctx *c, const char *name, const int64_t *verts_q, int64_t V, int64_t N3, int n_classes, bool member_rows,
+                         const OutlineOut &out, hipStream_t s,
+                         const std::function<void(const int32_t *, unsigned long long *, uint32_t *)> &emit_edges);
 
 extern "C" {
 
@@ -835,7 +935,47 @@ int gr_class_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_
   GR_HIP(c, hipSetDevice(c->device));
   GR_HIP(c, hipMemsetAsync(stats, 0, sizeof(uint64_t) * GR_OUTL_STAT_WORDS, s));
   unsigned long long *st = (unsigned long long *)stats;
-  const int64_t N3 = 3 * F;
+  const OutlineOut out{canon, ring_vertices, ring_offsets, ring_class, ring_vertex_cap, n_edges_h, n_rings_h, st};
+  return outline_trace(c, "gr_class_outlines", verts_q, V, 3 * F, n_classes, false, out, s,
+                       [&](const int32_t *canon_d, unsigned long long *pair, uint32_t *cl) {
+                         hipLaunchKernelGGL(k_outline_face_edges, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, verts_q, V, faces, F,
+                                            face_class, n_classes, canon_d, pair, cl, st);
+                       });
+}
+
+int gr_member_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_t *faces, int64_t F, const int64_t *face_ptr,
+                       const int32_t *face_members, int64_t nnz, int32_t n_classes, int32_t *canon, int32_t *ring_vertices,
+                       int64_t *ring_offsets, int32_t *ring_class, int64_t ring_vertex_cap, int64_t *n_edges_h, int64_t *n_rings_h,
+                       uint64_t *stats, void *stream) {
+  if (!c) return GR_EINVAL;
+  if (V < 0 || F < 0 || nnz < 0 || ring_vertex_cap < 0 || V > 0x7FFFFFFFll || F > 0x7FFFFFFFll || nnz > 0x7FFFFFFFll / 3 ||
+      ring_vertex_cap > 0x7FFFFFFFll)
+    return fail(c, GR_EINVAL, "gr_member_outlines: bad shape V=%lld F=%lld nnz=%lld capacity=%lld (V, F < 2^31, 3 nnz < 2^31)",
+                (long long)V, (long long)F, (long long)nnz, (long long)ring_vertex_cap);
+  if (n_classes < 0 || n_classes > GR_MEMBER_MAX_CLASSES)
+    return fail(c, GR_EINVAL, "gr_member_outlines: n_classes=%d outside [0, %d]", n_classes, (int)GR_MEMBER_MAX_CLASSES);
+  if (!stats || !n_edges_h || !n_rings_h || !face_ptr || (V > 0 && !verts_q) || (F > 0 && !faces) || (nnz > 0 && !face_members) ||
+      (ring_vertex_cap > 0 && (!ring_vertices || !ring_offsets || !ring_class || (V > 0 && !canon))))
+    return fail(c, GR_EINVAL, "gr_member_outlines: null arrays");
+  *n_edges_h = 0; *n_rings_h = 0;
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
+  GR_HIP(c, hipMemsetAsync(stats, 0, sizeof(uint64_t) * GR_OUTL_STAT_WORDS, s));
+  unsigned long long *st = (unsigned long long *)stats;
+  const OutlineOut out{canon, ring_vertices, ring_offsets, ring_class, ring_vertex_cap, n_edges_h, n_rings_h, st};
+  return outline_trace(c, "gr_member_outlines", verts_q, V, 3 * nnz, n_classes, true, out, s,
+                       [&](const int32_t *canon_d, unsigned long long *pair, uint32_t *cl) {   // one block at least: the table's ends
+                         hipLaunchKernelGGL(k_outline_member_edges, dim3((unsigned)std::max<int64_t>(ceil_div(F, 256), 1)), dim3(256), 0,
+                                            s, verts_q, V, faces, F, face_ptr, face_members, nnz, n_classes, canon_d, pair, cl, st);
+                       });
+}
+
+}  // extern "C"
+
+static int outline_trace(gr_ctx *c, const char *name, const int64_t *verts_q, int64_t V, int64_t N3, int n_classes, bool member_rows,
+                         const OutlineOut &out, hipStream_t s,
+                         const std::function<void(const int32_t *, unsigned long long *, uint32_t *)> &emit_edges) {
+  unsigned long long *st = out.stats;
   const int vbits = std::max(bit_length(V - 1), 1), cbits = std::max(bit_length(n_classes), 1);
 
   size_t cub_a = 0;
@@ -844,7 +984,7 @@ int gr_class_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_
                                                             (int32_t *)nullptr, (int)V, 0, 64, s));
     GR_CUB_MAX(c, cub_a, hipcub::DeviceScan::InclusiveScan(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, hipcub::Max(), (int)V, s));
   }
-  if (F > 0) {
+  if (N3 > 0) {
     GR_CUB_MAX(c, cub_a, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
                                                             (uint32_t *)nullptr, (uint32_t *)nullptr, (int)N3, 0, 31 + vbits, s));
     GR_CUB_MAX(c, cub_a, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (uint32_t *)nullptr, (uint32_t *)nullptr,
@@ -852,7 +992,7 @@ int gr_class_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_
     GR_CUB_MAX(c, cub_a, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)N3, s));
     GR_CUB_MAX(c, cub_a, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)(N3 + 1), s));
   }
-  // scratch A, sized by V and F: head | canon [V] | the vertex sort or the edge sort and its runs | hipcub's temporaries
+  // scratch A, sized by V and N3: head | canon [V] | the vertex sort or the edge sort and its runs | hipcub's temporaries
   Carve ca;
   const size_t o_head = ca.array<unsigned long long>(GR_OUTL_HEAD_WORDS), o_canon = ca.array<int32_t>(V), phase = ca.mark();
   // vertex phase: key [V] i64 | key_s [V] i64 | idx [V] | idx_s [V] | hp [V] | hp_max [V]
@@ -892,10 +1032,16 @@ int gr_class_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_
   uint32_t *cl = Carve::at<uint32_t>(A, e_cl), *cl_s = Carve::at<uint32_t>(A, e_cl_s);
   int32_t *flag = Carve::at<int32_t>(A, e_flag), *ex = Carve::at<int32_t>(A, e_ex), *ustart = Carve::at<int32_t>(A, e_ustart);
   int32_t *surv = Carve::at<int32_t>(A, e_surv), *soff = Carve::at<int32_t>(A, e_soff);
-  if (F > 0) {   // X3, X4
-    const dim3 gf((unsigned)ceil_div(F, 256)), ge((unsigned)ceil_div(N3, 256));
-    hipLaunchKernelGGL(k_outline_face_edges, gf, dim3(256), 0, s, verts_q, V, faces, F, face_class, n_classes,
-                       (const int32_t *)canon_d, pair, cl, st);
+  if (member_rows && N3 > 0) {   // Y2: no word of a gap is uninitialised
+    GR_HIP(c, hipMemsetAsync(pair, 0, sizeof(unsigned long long) * (size_t)N3, s));
+    GR_HIP(c, hipMemsetAsync(cl, 0xFF, sizeof(uint32_t) * (size_t)N3, s));
+  }
+  if (member_rows || N3 > 0) {   // X3 or Y3
+    emit_edges((const int32_t *)canon_d, pair, cl);
+    GR_HIP(c, hipGetLastError());
+  }
+  if (N3 > 0) {   // X4
+    const dim3 ge((unsigned)ceil_div(N3, 256));
     GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub_a, pair, pair_s, cl, cl_s, (int)N3, 0, 31 + vbits, s));   // by (from, to)
     GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub_a, cl_s, cl, pair_s, pair, (int)N3, 0, cbits, s));        // then by class, stably
     hipLaunchKernelGGL(k_outline_run_heads, ge, dim3(256), 0, s, (const unsigned long long *)pair, (const uint32_t *)cl, N3,
@@ -909,21 +1055,27 @@ int gr_class_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_
                        (const int32_t *)ex, (const int32_t *)ustart, (const unsigned long long *)head, surv, st);
     GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, cub_a, surv, soff, (int)(N3 + 1), s));
     GR_HIP(c, hipGetLastError());
-    unsigned long long runs_h = 0;
-    int32_t edges_h = 0;
-    GR_HIP(c, hipMemcpyAsync(&runs_h, head + GR_OUTL_HEAD_RUNS, sizeof(runs_h), hipMemcpyDeviceToHost, s));
-    GR_HIP(c, hipMemcpyAsync(&edges_h, soff + N3, sizeof(edges_h), hipMemcpyDeviceToHost, s));   // surv is 0 behind the runs: the total
-    GR_HIP(c, hipStreamSynchronize(s));
-    runs = (int64_t)runs_h; E = (int64_t)edges_h;
-    if (runs < 0 || runs > N3 || E < 0 || E > N3) return fail(c, GR_EHIP, "gr_class_outlines: inconsistent edge counts");
   }
-  *n_edges_h = E;
+  if (member_rows || N3 > 0) {   // the first synchronisation
+    unsigned long long runs_h = 0, bad_rows_h = 0;
+    int32_t edges_h = 0;
+    if (N3 > 0) {
+      GR_HIP(c, hipMemcpyAsync(&runs_h, head + GR_OUTL_HEAD_RUNS, sizeof(runs_h), hipMemcpyDeviceToHost, s));
+      GR_HIP(c, hipMemcpyAsync(&edges_h, soff + N3, sizeof(edges_h), hipMemcpyDeviceToHost, s));   // surv is 0 behind the runs: the total
+    }
+    if (member_rows) GR_HIP(c, hipMemcpyAsync(&bad_rows_h, st + GR_OUTL_STAT_BAD_ROWS, sizeof(bad_rows_h), hipMemcpyDeviceToHost, s));
+    GR_HIP(c, hipStreamSynchronize(s));
+    if (bad_rows_h) return GR_OK;   // Y2: a malformed table ends here; the caller reads the word
+    runs = (int64_t)runs_h; E = (int64_t)edges_h;
+    if (runs < 0 || runs > N3 || E < 0 || E > N3) return fail(c, GR_EHIP, "%s: inconsistent edge counts", name);
+  }
+  *out.n_edges_h = E;
 
-  const bool fill = ring_vertex_cap > 0;
+  const bool fill = out.cap > 0;
   if (E == 0) {   // no outline: an empty table
     if (fill) {
-      GR_HIP(c, hipMemsetAsync(ring_offsets, 0, sizeof(int64_t), s));
-      if (V > 0) GR_HIP(c, hipMemcpyAsync(canon, canon_d, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, s));
+      GR_HIP(c, hipMemsetAsync(out.ring_offsets, 0, sizeof(int64_t), s));
+      if (V > 0) GR_HIP(c, hipMemcpyAsync(out.canon, canon_d, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, s));
     }
     GR_HIP(c, hipStreamSynchronize(s));   // the scratch is free on return
     return GR_OK;
@@ -971,19 +1123,18 @@ int gr_class_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_
   GR_HIP(c, hipMemcpyAsync(&total, ws + E, sizeof(total), hipMemcpyDeviceToHost, s));
   GR_HIP(c, hipStreamSynchronize(s));
   R = (int64_t)(total & 0xFFFFFFFFull);
-  *n_rings_h = R;
+  *out.n_rings_h = R;
   if ((int64_t)(total >> 32) != E || R < 1 || 3 * R > E)
-    return fail(c, GR_EHIP, "gr_class_outlines: the rings hold %llu of %lld edges in %lld rings", total >> 32, (long long)E, (long long)R);
+    return fail(c, GR_EHIP, "%s: the rings hold %llu of %lld edges in %lld rings", name, total >> 32, (long long)E, (long long)R);
   if (!fill) return GR_OK;
-  if (E > ring_vertex_cap)
-    return fail(c, GR_EOVERFLOW, "gr_class_outlines: %lld ring vertices in %lld rings, the buffers hold %lld: call again with that capacity",
-                (long long)E, (long long)R, (long long)ring_vertex_cap);
+  if (E > out.cap)
+    return fail(c, GR_EOVERFLOW, "%s: %lld ring vertices in %lld rings, the buffers hold %lld: call again with that capacity", name,
+                (long long)E, (long long)R, (long long)out.cap);
   hipLaunchKernelGGL(k_outline_emit_rings, gE, dim3(256), 0, s, mn, off, (const int32_t *)efrom, (const int32_t *)ecls,
-                     (const unsigned long long *)w, (const unsigned long long *)ws, E, ring_vertices, ring_offsets, ring_class);
+                     (const unsigned long long *)w, (const unsigned long long *)ws, E, out.ring_vertices, out.ring_offsets,
+                     out.ring_class);
   GR_HIP(c, hipGetLastError());
-  if (V > 0) GR_HIP(c, hipMemcpyAsync(canon, canon_d, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, s));
+  if (V > 0) GR_HIP(c, hipMemcpyAsync(out.canon, canon_d, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, s));
   GR_HIP(c, hipStreamSynchronize(s));   // the last use of the scratch: free on return, as for gr_ray_pairs
   return GR_OK;
 }
-
-}  // extern "C"

@@ -1392,12 +1392,16 @@ class TexturedPhotogrammetryMesh:
         return labeled_faces, all_values
 
     # -- class outlines (reference: meshes.py:1308-1445) -------------------------------------------------
-    def _outline_call(self, vq, faces, classes, n_classes, points):
+    def _outline_call(self, vq, faces, classes, n_classes, points, members=None):
         """One backend call and what the host adds to it: (ring_offsets, class index per ring, ring_vertex_ids, ring_xy,
-        ring_is_hole, stats words, twice the exact area per ring as Python integers) as host arrays."""
+        ring_is_hole, stats words, twice the exact area per ring as Python integers) as host arrays.  members = (face_ptr,
+        face_members): `member_outlines` on that table instead of `class_outlines` on `classes`."""
         from geograypher_amd.utils.geometric import ring_areas2_exact
 
-        _, ring_vertices, ring_offsets, ring_class, stats = self.backend.class_outlines(vq, faces, classes, n_classes)
+        if members is not None:
+            _, ring_vertices, ring_offsets, ring_class, stats = self.backend.member_outlines(vq, faces, *members, n_classes)
+        else:
+            _, ring_vertices, ring_offsets, ring_class, stats = self.backend.class_outlines(vq, faces, classes, n_classes)
         ring_vertices = np.array(_host_array(ring_vertices), dtype=np.int32)
         ring_offsets = np.array(_host_array(ring_offsets), dtype=np.int64)
         ring_class = np.array(_host_array(ring_class), dtype=np.int64)
@@ -1412,12 +1416,15 @@ class TexturedPhotogrammetryMesh:
 
         face_labels: (F,) or (F, 1) class ids, float or int, NaN = no label, numpy or a device tensor; None: the mesh's face
         texture; (F, C) with C > 1: many-hot, one call per column with a value > 0, a face takes part where its value is > 0 and
-        `ring_class` is the column.  points_in_export_CRS (required, keyword): the V vertices (V, 2 | 3) in the planar CRS of the
+        `ring_class` is the column; a `scipy.sparse` matrix or array (F, C) of any format and any C: many-hot too (duplicates are
+        summed, then the entries > 0 count), traced in ONE `member_outlines` call whatever C (at most 2^31 - 2 columns, fewer than
+        2^31 / 3 entries; a backend without `member_outlines` gets a call per non-empty column).  points_in_export_CRS (required, keyword): the V vertices (V, 2 | 3) in the planar CRS of the
         export, metres, or a CRS designator (`WGS84CRS.parse`: the vertices are then reprojected on the device); z is not used.  drop_nan=False: the faces without a label form one more class, reported with id NaN.
         A wrong number of labels is a ValueError.  Filled with the non-zero rule, the rings of a class are the union of its faces
         in plan view on the 1e-6 m grid; where a class overlaps itself in plan view its rings overlap too.  `return_tensor=True`
         returns the arrays as tensors on the backend's device.  The counters are also left in `self.last_outline_stats`."""
-        from geograypher_amd.utils.geometric import OUTLINE_MAX_CLASSES, FaceLabelOutlines, snap_points
+        from geograypher_amd.utils.geometric import (MEMBER_MAX_CLASSES, OUTLINE_MAX_CLASSES, FaceLabelOutlines, csr_members, is_sparse,
+                                                     snap_points)
 
         if face_labels is None:
             face_labels = self.get_texture(request_vertex_texture=False)
@@ -1436,10 +1443,28 @@ class TexturedPhotogrammetryMesh:
         vq = snap_points(points)   # X1
         faces = np.ascontiguousarray(self.faces, dtype=np.int32)
         on_device = hasattr(face_labels, "detach")
+        sparse_labels = is_sparse(face_labels)
         if face_labels.ndim > 2:
             raise ValueError(f"face labels must be (F,), (F, 1) or (F, C), got {tuple(face_labels.shape)}")
         parts = []
-        if face_labels.ndim == 2 and face_labels.shape[1] != 1:   # many-hot
+        if sparse_labels:   # a sparse many-hot (F, C): the members with a value > 0, traced in one call (section 8l)
+            face_ptr, face_members = csr_members(face_labels)
+            if hasattr(self.backend, "member_outlines"):
+                if face_labels.shape[1] > MEMBER_MAX_CLASSES or 3 * len(face_members) >= 2 ** 31:
+                    raise ValueError(f"a sparse ({n_faces}, {face_labels.shape[1]}) labelling with {len(face_members)} entries > 0: "
+                                     f"one call takes at most {MEMBER_MAX_CLASSES} columns and fewer than 2^31 / 3 entries")
+                out = self._outline_call(vq, faces, None, int(face_labels.shape[1]), points, members=(face_ptr, face_members))
+                parts.append((out, out[1].astype(np.float64)))
+            else:   # an older backend: a call per non-empty column, as for a dense array
+                face_of_member = np.repeat(np.arange(n_faces), np.diff(face_ptr))
+                order = np.argsort(face_members, kind="stable")
+                columns, starts = np.unique(face_members[order], return_index=True)
+                for column, rows in zip(columns.tolist(), np.split(face_of_member[order], starts[1:])):
+                    classes = np.full(n_faces, -1, dtype=np.int32)
+                    classes[rows] = 0
+                    out = self._outline_call(vq, faces, classes, 1, points)
+                    parts.append((out, np.full(len(out[1]), float(column))))
+        elif face_labels.ndim == 2 and face_labels.shape[1] != 1:   # many-hot
             for column in range(face_labels.shape[1]):
                 member = face_labels[:, column] > 0
                 if not bool(member.any()):

@@ -391,6 +391,33 @@ def points_in_region(backend, ROI, points, buffer_meters=0):
 
 # -- class outlines ---------------------------------------------------------------------------------------------
 OUTLINE_MAX_CLASSES = 65535    # GR_OUTL_MAX_CLASSES: classes of one gr_class_outlines call
+MEMBER_MAX_CLASSES = 2 ** 31 - 2   # GR_MEMBER_MAX_CLASSES: classes of one gr_member_outlines call
+
+
+def is_sparse(labels) -> bool:
+    """A scipy.sparse matrix or array (scipy is only imported where one can be about)."""
+    if not type(labels).__module__.startswith("scipy.sparse"):
+        return False
+    import scipy.sparse
+
+    return scipy.sparse.issparse(labels)
+
+
+def csr_members(labels):
+    """Rule Y1: a scipy.sparse (F, C) matrix or array of any format -> (face_ptr (F + 1,) int64, face_members (nnz,) int32): the
+    face-major CSR of its entries > 0, duplicates summed first, the members of a row strictly ascending.  C must fit int32."""
+    import scipy.sparse
+
+    csr = scipy.sparse.csr_matrix(labels)   # a new header; COO input is summed here
+    if csr is labels or csr.data is getattr(labels, "data", None):
+        csr = csr.copy()
+    csr.sum_duplicates()
+    csr.sort_indices()
+    keep = csr.data > 0   # NaN is not
+    kept_before = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(keep, dtype=np.int64)])
+    if csr.shape[1] > MEMBER_MAX_CLASSES:
+        raise ValueError(f"{csr.shape[1]} columns: a member table takes at most {MEMBER_MAX_CLASSES}")
+    return kept_before[csr.indptr], np.ascontiguousarray(csr.indices[keep], dtype=np.int32)
 
 
 def snap_points(points):

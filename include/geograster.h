@@ -560,10 +560,12 @@ enum {
   GR_OUTL_STAT_CANCELLED = 3,   /* pairs of opposite directed edges of one class that cancelled                       */
   GR_OUTL_STAT_MULTI = 4,       /* distinct (class, from, to) that survive in more than one copy                      */
   GR_OUTL_STAT_BAD_FACES = 5,   /* faces with a vertex index outside [0, V)                                           */
+  GR_OUTL_STAT_BAD_ROWS = 6,    /* gr_member_outlines: violations of a well-formed member table (Y2); else 0          */
   GR_OUTL_STAT_WORDS = 8
 };
 enum {
-  GR_OUTL_MAX_CLASSES = 65535
+  GR_OUTL_MAX_CLASSES = 65535,
+  GR_MEMBER_MAX_CLASSES = 2147483646   /* 2^31 - 2: the sentinel class n_classes fits int32 */
 };
 int gr_class_outlines(gr_ctx *ctx, const int64_t *verts_q, int64_t V, const int32_t *faces, int64_t F, const int32_t *face_class,
                       int n_classes, int32_t *canon, int32_t *ring_vertices, int64_t *ring_offsets, int32_t *ring_class,
@@ -689,6 +691,10 @@ typedef struct gr_crs {
 } gr_crs;
 int gr_reproject_points(gr_ctx *ctx, const double *points, int64_t V, const int32_t *faces, int64_t F, const double *pre16_h,
                         const gr_crs *from_h, const gr_crs *to_h, double *out, uint64_t *stats, void *stream);
+
+/* The calls that came after this header's function list was closed are declared in companion headers, which this one brings in:
+ * everything stays available through geograster.h. */
+#include "geograster_outlines.h"
 
 #ifdef __cplusplus
 }
