@@ -122,6 +122,28 @@ GR_CRS_STAT_BEYOND = 1
 GR_CRS_STAT_BAD_FACES = 2
 GR_CRS_STAT_WORDS = 4
 GR_CRS_MAX_GROUPS = 8192
+# the orthomosaic baseline: count types and stats words of gr_assemble_tiles, work items and stats words of gr_zonal_class_counts
+GR_COUNT_U8 = 0
+GR_COUNT_U16 = 1
+GR_COUNT_F64 = 2
+GR_ORTHO_STAT_WITH_CLASS = 0
+GR_ORTHO_STAT_WITHOUT = 1
+GR_ORTHO_STAT_LONGEST_LIST = 2
+GR_ORTHO_STAT_PAIRS = 3
+GR_ORTHO_STAT_WORDS = 4
+GR_ORTHO_MAX_CLASSES = 255
+GR_ZONAL_STAT_TESTED = 0
+GR_ZONAL_STAT_INSIDE = 1
+GR_ZONAL_STAT_NODATA = 2
+GR_ZONAL_STAT_OVER = 3
+GR_ZONAL_STAT_LARGEST_PLUS_1 = 4
+GR_ZONAL_STAT_LARGEST_RING = 5
+GR_ZONAL_STAT_RINGS_IGNORED = 6
+GR_ZONAL_STAT_WORDS = 8
+GR_ZONAL_MAX_CLASSES = 256
+GR_ZONAL_ITEM_INTS = 7
+GR_ZONAL_BLOCK_W = 64
+GR_ZONAL_BLOCK_H = 128
 
 
 class StageTimes(ctypes.Structure):
@@ -230,6 +252,13 @@ _COMPANION_SIGNATURES = {
     "gr_member_outlines": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64p, _i64p, _vp, _vp],
 }
 COMPANION_SYMBOLS = tuple(_COMPANION_SIGNATURES)
+# ... and the calls of include/geograster_ortho.h (the orthomosaic baseline), under the same contract.
+_ORTHO_SIGNATURES = {
+    "gr_assemble_tiles": [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64,
+                          _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "gr_zonal_class_counts": [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp],
+}
+ORTHO_SYMBOLS = tuple(_ORTHO_SIGNATURES)
 
 
 def library_path() -> Path:
@@ -252,7 +281,7 @@ def load_library() -> ctypes.CDLL:
     # library's runtime without devices and gr_ctx_create answers GR_ENODEVICE.
     _torch()
     lib = ctypes.CDLL(str(_LIB_PATH))
-    for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES}.items():
+    for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -388,6 +417,113 @@ def _check_offsets(offsets, n: int, total: int, owners: str, kind: str, rows: st
 def _check_int32(table, what: str):
     if table.size and (table.min() < np.iinfo(np.int32).min or table.max() > np.iinfo(np.int32).max):
         raise ValueError(f"{what} must fit in int32")
+
+
+# The checks of the tables of the orthomosaic baseline: plain functions of host arrays.
+def _count_kind(count_dtype):
+    """np.uint8 / np.uint16 / float (or np.float64) -> (GR_COUNT_*, the numpy dtype, the torch dtype)."""
+    torch = _torch()
+    if count_dtype is float:
+        count_dtype = np.float64
+    try:
+        dtype = np.dtype(count_dtype)
+    except TypeError:
+        dtype = None
+    kinds = {np.dtype(np.uint8): (GR_COUNT_U8, torch.uint8), np.dtype(np.uint16): (GR_COUNT_U16, torch.uint16),
+             np.dtype(np.float64): (GR_COUNT_F64, torch.float64)}
+    if dtype not in kinds:
+        raise ValueError(f"gr_assemble_tiles: count_dtype must be np.uint8, np.uint16 or float, got {count_dtype!r}")
+    return kinds[dtype][0], dtype, kinds[dtype][1]
+
+
+def check_assemble_tables(pred_offsets, windows, tile_table, weight_offsets, n_pred_bytes: int, n_weights: int, bin_ptr, bin_tiles,
+                          bin_side: int, bins_x: int, bins_y: int, width: int, height: int, row0: int, n_rows: int, num_classes: int,
+                          nodataval: int):
+    """O8: everything gr_assemble_tiles reads through is in range -- ValueError naming the call otherwise."""
+    name = "gr_assemble_tiles"
+    if not 1 <= num_classes <= GR_ORTHO_MAX_CLASSES:
+        raise ValueError(f"{name}: num_classes={num_classes} outside [1, {GR_ORTHO_MAX_CLASSES}]")
+    if not 0 <= nodataval <= 255:
+        raise ValueError(f"{name}: nodataval={nodataval} outside [0, 255]")
+    if width < 0 or height < 0 or row0 < 0 or n_rows < 0 or row0 + n_rows > height or width >= 2 ** 31 or height >= 2 ** 31:
+        raise ValueError(f"{name}: rows [{row0}, {row0 + n_rows}) of an extent of {height} rows x {width} columns")
+    windows = np.asarray(windows, dtype=np.int64)
+    tile_table = np.asarray(tile_table, dtype=np.int64).reshape(-1)
+    pred_offsets = np.asarray(pred_offsets, dtype=np.int64).reshape(-1)
+    weight_offsets = np.asarray(weight_offsets, dtype=np.int64).reshape(-1)
+    T = tile_table.shape[0]
+    if windows.shape != (T, 4):
+        raise ValueError(f"{name}: {T} tiles need windows of shape ({T}, 4), got {windows.shape}")
+    if weight_offsets.shape[0] < 1:
+        raise ValueError(f"{name}: the weight offsets need at least one entry")
+    _check_offsets(pred_offsets, T, n_pred_bytes, "tiles", f"{name}: prediction", "prediction bytes")
+    n_tables = weight_offsets.shape[0] - 1
+    _check_offsets(weight_offsets, n_tables, n_weights, "weight tables", f"{name}: weight", "weights")
+    if T:
+        col, row, w, h = windows.T
+        if np.any(w < 1) or np.any(h < 1) or np.any(col < 0) or np.any(row < 0) or np.any(col + w > width) or np.any(row + h > height):
+            bad = int(np.nonzero((w < 1) | (h < 1) | (col < 0) | (row < 0) | (col + w > width) | (row + h > height))[0][0])
+            raise ValueError(f"{name}: window {bad} {tuple(int(v) for v in windows[bad])} is empty or leaves the {height} x {width} extent")
+        if np.any(np.diff(pred_offsets) != w * h):
+            bad = int(np.nonzero(np.diff(pred_offsets) != w * h)[0][0])
+            raise ValueError(f"{name}: tile {bad} has {int(np.diff(pred_offsets)[bad])} prediction bytes for a window of {int(h[bad])} x {int(w[bad])}")
+        if np.any(tile_table < 0) or np.any(tile_table >= n_tables):
+            raise ValueError(f"{name}: a tile names a weight table outside [0, {n_tables})")
+        if np.any(np.diff(weight_offsets)[tile_table] != w * h):
+            bad = int(np.nonzero(np.diff(weight_offsets)[tile_table] != w * h)[0][0])
+            raise ValueError(f"{name}: the weight table of tile {bad} does not have the {int(h[bad])} x {int(w[bad])} values of its window")
+    if bin_side < 1 or bins_x < 1 or bins_y < 1 or bins_x * bin_side < width or bins_y * bin_side < height:
+        raise ValueError(f"{name}: {bins_x} x {bins_y} bins of side {bin_side} do not cover the {height} x {width} extent")
+    bin_ptr = np.asarray(bin_ptr, dtype=np.int64).reshape(-1)
+    bin_tiles = np.asarray(bin_tiles, dtype=np.int64).reshape(-1)
+    _check_offsets(bin_ptr, bins_x * bins_y, bin_tiles.shape[0], "bins", f"{name}: bin", "bin entries")
+    if bin_tiles.size:
+        if bin_tiles.min() < 0 or bin_tiles.max() >= T:
+            raise ValueError(f"{name}: a bin entry is outside [0, {T})")
+        rising = np.diff(bin_tiles) > 0
+        rising[bin_ptr[1:-1][(bin_ptr[1:-1] > 0) & (bin_ptr[1:-1] < bin_tiles.shape[0])] - 1] = True   # across two bins: any order
+        if not np.all(rising):
+            raise ValueError(f"{name}: the tiles of a bin must be listed in strictly ascending index")
+
+
+def zonal_nodata(nodata) -> int:
+    """Z5: the nodata argument of gr_zonal_class_counts -- the value, or -1 (no cell is nodata) for None and for a value that no
+    uint8 cell can hold."""
+    if nodata is None or not np.isfinite(nodata) or nodata != int(nodata) or not 0 <= int(nodata) <= 255:
+        return -1
+    return int(nodata)
+
+
+def check_zonal_tables(H: int, W: int, nodata, ring_vertices, ring_offsets, ring_polygon, n_polygons: int, items, num_classes: int):
+    """Z1 / Z6: everything gr_zonal_class_counts reads through is in range -- ValueError naming the call otherwise."""
+    name = "gr_zonal_class_counts"
+    if not (1 <= H < 2 ** 23 and 1 <= W < 2 ** 23):
+        raise ValueError(f"{name}: a raster of {H} x {W} cells is outside [1, 2^23) a side")
+    if not 1 <= num_classes <= GR_ZONAL_MAX_CLASSES:
+        raise ValueError(f"{name}: num_classes={num_classes} outside [1, {GR_ZONAL_MAX_CLASSES}]")
+    if n_polygons < 0 or n_polygons >= 2 ** 31:
+        raise ValueError(f"{name}: {n_polygons} polygon rows")
+    rv = np.asarray(ring_vertices)
+    if rv.ndim != 2 or rv.shape[1] != 2 or rv.dtype.kind not in "iu":
+        raise ValueError(f"{name}: ring vertices must be an (N, 2) integer array, got {rv.shape} {rv.dtype}")
+    if rv.size and np.abs(rv.astype(np.int64)).max() >= 2 ** 40:
+        raise ValueError(f"{name}: a ring vertex lies 2^40 / 65536 cells or more from the raster's corner")
+    rp = np.asarray(ring_polygon, dtype=np.int64).reshape(-1)
+    R = rp.shape[0]
+    _check_offsets(np.asarray(ring_offsets, dtype=np.int64).reshape(-1), R, rv.shape[0], "rings", f"{name}: ring", "ring vertices")
+    if R and (rp.min() < 0 or rp.max() >= n_polygons or np.any(np.diff(rp) < 0)):
+        raise ValueError(f"{name}: ring_polygon must be non-decreasing inside [0, {n_polygons})")
+    it = np.asarray(items, dtype=np.int64)
+    if it.ndim != 2 or it.shape[1] != GR_ZONAL_ITEM_INTS:
+        raise ValueError(f"{name}: work items must be (n, {GR_ZONAL_ITEM_INTS}), got {it.shape}")
+    if it.shape[0]:
+        p, c0, r0, w, h, lo, hi = it.T
+        bad = ((p < 0) | (p >= n_polygons) | (c0 < 0) | (r0 < 0) | (w < 1) | (h < 1) | (w > GR_ZONAL_BLOCK_W) | (h > GR_ZONAL_BLOCK_H)
+               | (c0 + w > W) | (r0 + h > H) | (lo < 0) | (hi < lo) | (hi > R))
+        if np.any(bad):
+            k = int(np.nonzero(bad)[0][0])
+            raise ValueError(f"{name}: work item {k} {tuple(int(v) for v in it[k])} names no polygon row, no block of at most "
+                             f"{GR_ZONAL_BLOCK_W} x {GR_ZONAL_BLOCK_H} cells inside the raster, or no ring range")
 
 
 def polygon_pair_bounds(boxes, poly_offsets, n_faces: int) -> np.ndarray:
@@ -1285,6 +1421,72 @@ class HipRaster:
             if check and f_t is not None:
                 self._check_faces("gr_reproject_points", stats, GR_CRS_STAT_BAD_FACES, V)
         return out, stats
+
+    # -- the orthomosaic baseline: tile assembly, zonal class counts ----------------------------------------------------
+    def assemble_tiles(self, preds, pred_offsets, windows, tile_table, weights, weight_offsets, count_dtype, bin_table,
+                       width: int, height: int, num_classes: int, nodataval: int, row0: int = 0, n_rows: Optional[int] = None,
+                       want_counts: bool = False):
+        """gr_assemble_tiles: preds uint8 concatenated tile predictions (values that are no class: 255),
+        pred_offsets (T + 1,) int64, windows (T, 4) int col_off row_off width height in extent coordinates, tile_table (T,) int,
+        weights: the tables concatenated in `count_dtype` (np.uint8, np.uint16 or float), weight_offsets (n_tables + 1,) int64,
+        bin_table = (bin_ptr, bin_tiles, bin_side, bins_x, bins_y) of `utils.geometric.tile_bin_table` -- numpy or device tensors
+        -> (classes (n_rows, width) uint8 tensor, counts (C, n_rows, width) tensor of the count type or None, stats
+        (GR_ORTHO_STAT_WORDS,) int64 tensor: pixels with a class, without, most tiles over a pixel, (tile, pixel) pairs read).
+        The rows are [row0, row0 + n_rows) of the `height` rows of the extent (default: all).  The tables are validated on the
+        host first (`check_assemble_tables`: ValueError).  Only enqueues."""
+        torch = _torch()
+        kind, np_dtype, t_dtype = _count_kind(count_dtype)
+        n_rows = int(height) - int(row0) if n_rows is None else int(n_rows)
+        bin_ptr, bin_tiles, bin_side, bins_x, bins_y = bin_table
+        po_h, win_h, tt_h, wo_h, bp_h, bt_h = (_host_array(x) for x in (pred_offsets, windows, tile_table, weight_offsets, bin_ptr,
+                                                                        bin_tiles))
+        p_t = self._dev(preds, torch.uint8).reshape(-1)
+        w_t = self._dev(weights, t_dtype).reshape(-1)
+        check_assemble_tables(po_h, win_h, tt_h, wo_h, int(p_t.shape[0]), int(w_t.shape[0]), bp_h, bt_h, int(bin_side), int(bins_x),
+                              int(bins_y), int(width), int(height), int(row0), n_rows, int(num_classes), int(nodataval))
+        T = int(tt_h.shape[0])
+        po_t, wo_t, bp_t = (self._dev(x, torch.int64).reshape(-1) for x in (pred_offsets, weight_offsets, bin_ptr))
+        win_t, tt_t, bt_t = (self._dev(x, torch.int32).reshape(-1) for x in (windows, tile_table, bin_tiles))
+        C = int(num_classes)
+        classes = self._empty((n_rows, int(width)), torch.uint8)
+        counts = self._empty((C, n_rows, int(width)), t_dtype) if want_counts else None
+        stats = self._stats(GR_ORTHO_STAT_WORDS)
+        self._call("gr_assemble_tiles", _ptr(p_t if p_t.numel() else None), int(p_t.shape[0]), po_t.data_ptr(),
+                   _ptr(win_t if T else None), _ptr(tt_t if T else None), T, _ptr(w_t if w_t.numel() else None), int(w_t.shape[0]),
+                   wo_t.data_ptr(), int(wo_t.shape[0]) - 1, kind, bp_t.data_ptr(), _ptr(bt_t if bt_t.numel() else None),
+                   int(bt_t.shape[0]), int(bin_side), int(bins_x), int(bins_y), int(width), int(row0), n_rows, C, int(nodataval),
+                   _ptr(classes if classes.numel() else None), _ptr(counts if counts is not None and counts.numel() else None),
+                   stats.data_ptr(), self._stream())
+        return classes, counts, stats
+
+    def zonal_class_counts(self, raster, nodata, ring_vertices, ring_offsets, ring_polygon, n_polygons: int, items, num_classes: int):
+        """gr_zonal_class_counts: raster (H, W) uint8, nodata an int in [0, 255] or None, the ring table in
+        pixel coordinates times 65536 (`utils.geospatial.rings_to_cell_units`: ring_vertices (N, 2) int64, ring_offsets (R + 1,)
+        int64, ring_polygon (R,) int non-decreasing), items (n, GR_ZONAL_ITEM_INTS) int32 of `utils.geometric.zonal_work_items` --
+        numpy or device tensors -> (counts (n_polygons, num_classes) int64 tensor, stats (GR_ZONAL_STAT_WORDS,) int64 tensor).
+        The tables are validated on the host first (`check_zonal_tables`: ValueError).  Only enqueues."""
+        torch = _torch()
+        if not isinstance(raster, torch.Tensor):
+            raster = np.asarray(raster)
+        if str(raster.dtype).split(".")[-1] != "uint8":
+            raise ValueError(f"gr_zonal_class_counts: the raster must be uint8, got {raster.dtype}")
+        r_t = self._shaped(raster, torch.uint8, ("H", "W"), "raster")
+        H, W = int(r_t.shape[0]), int(r_t.shape[1])
+        rv_h, off_h, rp_h, it_h = (_host_array(x) for x in (ring_vertices, ring_offsets, ring_polygon, items))
+        P, C = int(n_polygons), int(num_classes)
+        check_zonal_tables(H, W, nodata, rv_h, off_h, rp_h, P, it_h, C)
+        rv_t = self._shaped(ring_vertices, torch.int64, ("N", 2), "ring vertices")
+        rp_t = self._dev(ring_polygon, torch.int32).reshape(-1)
+        R = int(rp_t.shape[0])
+        off_t = self._shaped(ring_offsets, torch.int64, (R + 1,), "ring offsets (one more than ring polygons)")
+        it_t = self._shaped(items, torch.int32, ("n", GR_ZONAL_ITEM_INTS), "work items")
+        counts = self._empty((P, C), torch.int64)
+        stats = self._stats(GR_ZONAL_STAT_WORDS)
+        self._call("gr_zonal_class_counts", r_t.data_ptr(), H, W, zonal_nodata(nodata),
+                   _ptr(rv_t if rv_t.numel() else None), int(rv_t.shape[0]), off_t.data_ptr(), _ptr(rp_t if R else None), R, P,
+                   _ptr(it_t if it_t.numel() else None), int(it_t.shape[0]), C, _ptr(counts if P else None), stats.data_ptr(),
+                   self._stream())
+        return counts, stats
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):

@@ -24,7 +24,9 @@
 //                    k_sc_prune_test, k_sc_prune_apply); no mesh needed
 //   crs.hip          CRS reprojection: points between WGS84 ECEF, geographic and transverse Mercator coordinates (k_reproject_points; constants:
 //                    crs_constants.hpp, written by tools/make_crs_constants.py); no mesh needed
-//   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip and crs.hip: orient, ring_span, edge_crossing (THE even-odd rule of
+//   ortho.hip        orthomosaic baseline: tile predictions assembled into a class raster (k_assemble_tiles), class counts of the raster cells
+//                    under polygon rows (k_zonal_class_counts, k_zonal_ring_stats); no mesh needed
+//   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip, crs.hip and ortho.hip: orient, ring_span, edge_crossing (THE even-odd rule of
 //                    k_polygon_weights, k_face_polygon_index and k_points_in_region), load_face, stat_add / stat_add_u32 / stat_max / stat_count
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

@@ -671,3 +671,76 @@ def polygon_cell_table(polygon_boxes, grid=None):
     offsets = np.zeros(nx * ny + 1, dtype=np.int64)
     np.cumsum(np.bincount(cell, minlength=nx * ny), out=offsets[1:])
     return grid, offsets, np.ascontiguousarray(row[order], dtype=np.int32)
+
+
+# -- the orthomosaic baseline: the bin table of the tile assembly, the work items of the zonal counts ----------------
+ORTHO_BIN_SIDE = 64            # pixels a side of a bin of `tile_bin_table` unless told otherwise
+ZONAL_BLOCK = (64, 16)         # cells (width, height) of a work item of `zonal_work_items` unless told otherwise
+
+
+def tile_bin_table(windows, width: int, height: int, bin_side: int = ORTHO_BIN_SIDE):
+    """The bin table `HipRaster.assemble_tiles` takes, by count-then-fill as `polygon_cell_table`: windows (T, 4) int col_off
+    row_off width height inside a `height` x `width` extent -> (bin_ptr (bins_x bins_y + 1,) int64, bin_tiles int32, bin_side,
+    bins_x, bins_y).  Bin (bx, by) has index by bins_x + bx, covers the pixels [bx side, (bx + 1) side) x [by side, (by + 1) side)
+    and lists, in ASCENDING tile index, every tile whose window meets it.  Empty windows are listed nowhere."""
+    windows = np.asarray(windows, dtype=np.int64).reshape(-1, 4)
+    side = int(bin_side)
+    if side < 1:
+        raise ValueError(f"bin_side must be at least 1, got {bin_side}")
+    bins_x, bins_y = max(-(-int(width) // side), 1), max(-(-int(height) // side), 1)
+    tiles = np.nonzero((windows[:, 2] > 0) & (windows[:, 3] > 0))[0]
+    col, row, w, h = windows[tiles].T
+    ix0, ix1 = np.clip(col // side, 0, bins_x - 1), np.clip((col + w - 1) // side, 0, bins_x - 1)
+    iy0, iy1 = np.clip(row // side, 0, bins_y - 1), np.clip((row + h - 1) // side, 0, bins_y - 1)
+    nw, nh = ix1 - ix0 + 1, iy1 - iy0 + 1
+    n = nw * nh
+    owner = np.repeat(np.arange(len(tiles)), n)
+    k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+    cell = (iy0[owner] + k // nw[owner]) * bins_x + ix0[owner] + k % nw[owner]
+    tile = tiles[owner]
+    order = np.lexsort((tile, cell))
+    bin_ptr = np.zeros(bins_x * bins_y + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cell, minlength=bins_x * bins_y), out=bin_ptr[1:])
+    return bin_ptr, np.ascontiguousarray(tile[order], dtype=np.int32), side, bins_x, bins_y
+
+
+def zonal_work_items(ring_vertices, ring_offsets, ring_polygon, n_polygons: int, height: int, width: int, block=ZONAL_BLOCK):
+    """The work items `HipRaster.zonal_class_counts` takes (rule Z6), by count-then-fill from the rows' boxes: the ring table in
+    cell units (1 / 65536 of a cell, `utils.geospatial.rings_to_cell_units`) -> (n, 7) int32 rows (polygon row, col0, row0, width,
+    height, first ring, one past the last ring).  A row's box is the box of its rings of 3 or more vertices, clamped to the cells
+    whose CENTRE it can hold inside the `height` x `width` raster, and is cut into blocks of at most block = (width <= 64,
+    height <= 128) cells.  Rows whose box holds no centre have no item."""
+    bw, bh = int(block[0]), int(block[1])
+    if not (1 <= bw <= 64 and 1 <= bh <= 128):
+        raise ValueError(f"a block is at most 64 x 128 cells, got {bw} x {bh}")
+    rv = np.asarray(ring_vertices, dtype=np.int64).reshape(-1, 2)
+    off = np.asarray(ring_offsets, dtype=np.int64).reshape(-1)
+    rp = np.asarray(ring_polygon, dtype=np.int64).reshape(-1)
+    P = int(n_polygons)
+    big = np.iinfo(np.int64).max
+    lo = np.full((P, 2), big, dtype=np.int64)
+    hi = np.full((P, 2), -big, dtype=np.int64)
+    live = np.nonzero(np.diff(off) >= 3)[0]
+    if len(live) and len(rv):
+        owner = np.repeat(rp[live], np.diff(off)[live])
+        v = np.concatenate([rv[off[r]:off[r + 1]] for r in live])
+        np.minimum.at(lo, owner, v)
+        np.maximum.at(hi, owner, v)
+    ring_lo, ring_hi = np.searchsorted(rp, np.arange(P), "left"), np.searchsorted(rp, np.arange(P), "right")
+    rows = np.nonzero(lo[:, 0] <= hi[:, 0])[0]
+    # a centre 65536 c + 32768 lies in [lo, hi] iff ceil((lo - 32768) / 65536) <= c <= floor((hi - 32768) / 65536)
+    c0 = np.maximum(-((32768 - lo[rows, 0]) // 65536), 0)
+    c1 = np.minimum((hi[rows, 0] - 32768) // 65536, int(width) - 1)
+    r0 = np.maximum(-((32768 - lo[rows, 1]) // 65536), 0)
+    r1 = np.minimum((hi[rows, 1] - 32768) // 65536, int(height) - 1)
+    keep = (c0 <= c1) & (r0 <= r1)
+    rows, c0, c1, r0, r1 = rows[keep], c0[keep], c1[keep], r0[keep], r1[keep]
+    nx, ny = -(-(c1 - c0 + 1) // bw), -(-(r1 - r0 + 1) // bh)
+    n = nx * ny
+    owner = np.repeat(np.arange(len(rows)), n)
+    k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+    bx, by = k % nx[owner], k // nx[owner]
+    col0, row0 = c0[owner] + bx * bw, r0[owner] + by * bh
+    items = np.stack([rows[owner], col0, row0, np.minimum(bw, c1[owner] + 1 - col0), np.minimum(bh, r1[owner] + 1 - row0),
+                      ring_lo[rows[owner]], ring_hi[rows[owner]]], axis=1) if len(owner) else np.zeros((0, 7))
+    return np.ascontiguousarray(items, dtype=np.int32)

@@ -141,3 +141,118 @@ def points_or_CRS(file_name: str, points_file, crs_name: str, crs):
             crs = int(crs)
         return WGS84CRS.parse(crs)
     return np.load(points_file) if isinstance(points_file, (str, Path)) else points_file
+
+
+# -- the class counts of the raster cells under polygons (reference: utils/geospatial.py:150-211) ------------
+def rings_to_cell_units(rings, inverse):
+    """Rule Z1: ring vertices (x, y) in the raster's CRS -> int64 pixel coordinates times 65536, with the raster's `inverse`
+    (ia, ib, ic, id, ie, if) in float64, every operation rounded on its own in the order of rule T2: col = (ia x + ib y) + ic,
+    row = (id x + ie y) + if, q = rint(65536 value).  rings: a list of (n, 2) arrays -> (ring_vertices (N, 2) int64, ring_offsets
+    (R + 1,) int64).  ValueError for a value that is not finite or has |q| >= 2^40."""
+    ia, ib, ic, id_, ie, if_ = (np.float64(v) for v in inverse)
+    verts, offsets = [], [0]
+    for ring in rings:
+        ring = np.asarray(ring, dtype=np.float64).reshape(-1, 2)
+        x, y = ring[:, 0], ring[:, 1]
+        col = (x * ia + y * ib) + ic
+        row = (x * id_ + y * ie) + if_
+        q = np.rint(np.stack([col, row], axis=1) * 65536.0)
+        if q.size and not np.all(np.abs(q) < 2.0 ** 40):
+            raise ValueError("a polygon vertex is not finite or lies 2^40 / 65536 cells or more from the raster's corner")
+        verts.append(q.astype(np.int64))
+        offsets.append(offsets[-1] + len(q))
+    ring_vertices = np.concatenate(verts) if verts else np.zeros((0, 2), dtype=np.int64)
+    return np.ascontiguousarray(ring_vertices.reshape(-1, 2)), np.asarray(offsets, dtype=np.int64)
+
+
+def raster_to_uint8(data, nodata):
+    """Rule Z5: a band of a `PlanarRaster` -> (uint8 array, the nodata value as gr_zonal_class_counts takes it: an int in
+    [0, 255] or None).  ValueError for a value that is not an integer in [0, 255] and not `nodata`."""
+    from geograypher_amd._hip import zonal_nodata
+
+    data = np.asarray(data)
+    if data.dtype == np.uint8:
+        cells = data
+    else:
+        values = data.astype(np.float64)
+        is_nodata = np.zeros(values.shape, dtype=bool) if nodata is None else ((values == nodata) | (np.isnan(values) & bool(np.isnan(nodata))))
+        with np.errstate(invalid="ignore"):
+            fits = (values >= 0) & (values <= 255) & (values == np.floor(values))
+        if not np.all(fits | is_nodata):
+            raise ValueError(f"{int(np.sum(~(fits | is_nodata)))} raster cells hold a value that is not an integer in [0, 255] and not nodata")
+        cells = np.where(fits, values, 0).astype(np.uint8)
+        if zonal_nodata(nodata) < 0 and np.any(is_nodata):
+            # a nodata value no uint8 cell can hold: park those cells on a value the raster does not use
+            free = np.setdiff1d(np.arange(256), np.unique(cells[fits]))
+            if not len(free):
+                raise ValueError("the raster uses all 256 values and has nodata cells beside them")
+            cells[is_nodata] = free[-1]
+            return np.ascontiguousarray(cells), int(free[-1])
+    nd = zonal_nodata(nodata)
+    return np.ascontiguousarray(cells), None if nd < 0 else nd
+
+
+def _as_planar_polygons(polygons):
+    from geograypher_amd.utils.geometric import PlanarPolygons
+
+    if isinstance(polygons, PlanarPolygons):
+        return polygons
+    if isinstance(polygons, (str, bytes)) or hasattr(polygons, "__fspath__"):
+        if not str(polygons).lower().endswith((".geojson", ".json")):
+            raise NotImplementedError(f"{polygons}: polygon files are read as .geojson only")
+        return PlanarPolygons.from_geojson(polygons)[0]
+    return PlanarPolygons.from_sequence(polygons)
+
+
+def _as_planar_raster(raster):
+    from geograypher_amd.utils.raster import PlanarRaster
+
+    return raster if isinstance(raster, PlanarRaster) else PlanarRaster.from_geotiff(raster)
+
+
+def zonal_class_counts(polygons, classes_raster, num_classes=None, backend=None, block=None):
+    """The cells of every value under every polygon row, counted on the device (`HipRaster.zonal_class_counts`): polygons a
+    `PlanarPolygons`, a `.geojson` path or a sequence of ring arrays, in the raster's CRS; classes_raster a path or a
+    `PlanarRaster` whose band 0 holds integers in [0, 255] -> (counts (P, C) int64, stats dict).  num_classes=None: 1 + the
+    largest counted value (at least 1).  A counted value >= num_classes is a ValueError naming how many cells hold one.  A cell
+    belongs to a row iff its CENTRE lies in it under the half-open even-odd rule Z3 over all rings of the row; what GDAL's
+    rasterize(all_touched=False), behind rasterstats, decides for a centre exactly ON a boundary is not measured (GDAL is not
+    available here): the two can differ on those cells only."""
+    from geograypher_amd import _hip
+    from geograypher_amd.utils.geometric import ZONAL_BLOCK, zonal_work_items
+
+    polygons = _as_planar_polygons(polygons)
+    raster = _as_planar_raster(classes_raster)
+    cells, nodata = raster_to_uint8(raster.data[0], raster.nodata)
+    H, W = cells.shape
+    rv, off = rings_to_cell_units(polygons.rings, raster.inverse)
+    rp = np.asarray(polygons.ring_polygon, dtype=np.int32)
+    P = len(polygons)
+    items = zonal_work_items(rv, off, rp, P, H, W, ZONAL_BLOCK if block is None else block)
+    backend = backend if backend is not None else _default_backend()
+    C = _hip.GR_ZONAL_MAX_CLASSES if num_classes is None else int(num_classes)
+    counts, stats = backend.zonal_class_counts(cells, nodata, rv, off, rp, P, items, C)
+    counts = np.asarray(counts.cpu() if hasattr(counts, "cpu") else counts, dtype=np.int64)
+    stats = np.asarray(stats.cpu() if hasattr(stats, "cpu") else stats, dtype=np.int64)
+    names = ("tested", "inside", "nodata", "over", "largest_plus_1", "largest_ring", "rings_ignored")
+    stats = {k: int(stats[i]) for i, k in enumerate(names)}
+    if num_classes is None:
+        counts = counts[:, :max(stats["largest_plus_1"], 1)]
+    elif stats["over"]:
+        raise ValueError(f"{stats['over']} counted cells hold a value >= num_classes={C} (the largest is {stats['largest_plus_1'] - 1})")
+    return counts, stats
+
+
+def get_overlap_raster(unlabeled_df, classes_raster, num_classes=None, normalize: bool = False, backend=None):
+    """The class counts of the raster cells under every polygon (reference: utils/geospatial.py:150-211, which calls
+    rasterstats.zonal_stats per polygon) -> (counts_matrix (n_valid, C) float64, valid_IDs (n_valid,) int64): one row per VALID
+    polygon -- a polygon with at least one counted cell --, in ascending polygon index; `normalize` divides every row by its
+    sum.  The reference writes the counts of valid polygon k into row valid_IDs[k] of its n_valid-row matrix, which is out of
+    place (or out of bounds) whenever an invalid polygon precedes a valid one; this builds the matrix that was meant, row k for
+    valid polygon k.  Inputs, num_classes and the boundary rule as `zonal_class_counts`."""
+    counts, _ = zonal_class_counts(unlabeled_df, classes_raster, num_classes, backend=backend)
+    valid = np.nonzero(counts.sum(axis=1) > 0)[0].astype(np.int64)
+    matrix = counts[valid].astype(np.float64)
+    if normalize:
+        matrix = matrix / np.sum(matrix, axis=1, keepdims=True)
+    return matrix, valid

@@ -236,3 +236,15 @@ def select_covering_views(visibility, min_observations_to_be_included=1, prune: 
         backend = default_backend()
     return backend.set_cover(csr.indptr.astype(np.int64), csr.indices.astype(np.int32), n_faces, n_views,
                              min_observations=float(min_observations_to_be_included), prune=prune)
+
+
+def create_ramped_weighting(rectangle_shape: typing.Tuple[int, int], ramp_dist_frac: float) -> np.ndarray:
+    """The weight of every pixel of a (rows, columns) tile, float64 in [0, 1] (reference: utils/numeric.py:14-36; rule O2 of
+    DESIGN.md 8m): along each axis a ramp of n evenly spaced values from 0 to 1 / ramp_dist_frac, cut off at 1, and the same ramp
+    from the far edge; a pixel takes the smallest of its four ramp values.  Pixels further than `ramp_dist_frac` of the side from
+    every edge weigh 1, and the outermost ring weighs 0."""
+    ramps = []
+    for n in rectangle_shape[:2]:
+        ramp = np.clip(np.linspace(0, 1 / ramp_dist_frac, num=n), 0, 1)
+        ramps.append(np.minimum(ramp, ramp[::-1]))
+    return np.minimum(ramps[0][:, None], ramps[1][None, :])

@@ -79,45 +79,68 @@ class PlanarRaster:
                 raise ValueError(f"{path}: image mode {image.mode!r} is not one of {GEOTIFF_MODES} (float64 and multi-band "
                                  "rasters go through PlanarRaster.from_array)")
             tags = image.tag_v2 if hasattr(image, "tag_v2") else {}
-            scale = tags.get(TAG_MODEL_PIXEL_SCALE)
-            tie = tags.get(TAG_MODEL_TIEPOINT)
-            matrix = tags.get(TAG_MODEL_TRANSFORMATION)
-            keys = tags.get(TAG_GEO_KEY_DIRECTORY)
-            nodata = tags.get(TAG_GDAL_NODATA)
+            transform, nodata, epsg = georeference_from_tags(path, tags)
             data = np.array(image)
-        if scale is not None and tie is not None:
-            if len(tie) != 6:
-                raise ValueError(f"{path}: {len(tie) // 6} tiepoints beside a pixel scale: one is expected")
-            sx, sy = float(scale[0]), float(scale[1])
-            i, j, _k, X, Y, _Z = (float(v) for v in tie)
-            transform = [sx, 0.0, X - i * sx, 0.0, -sy, Y + j * sy]
-        elif matrix is not None:
-            if len(matrix) != 16:
-                raise ValueError(f"{path}: ModelTransformation has {len(matrix)} values, not 16")
-            transform = [float(matrix[k]) for k in (0, 1, 3, 4, 5, 7)]
-        elif tie is not None:
-            raise ValueError(f"{path}: tiepoints without a pixel scale (a warp through several tiepoints is not supported)")
-        else:
-            raise ValueError(f"{path}: no georeferencing (ModelPixelScale + ModelTiepoint or ModelTransformation)")
-        if keys is not None and _geo_key(keys, GEO_KEY_RASTER_TYPE) == RASTER_PIXEL_IS_POINT:
-            a, b, c, d, e, f = transform   # the tags place the CENTRE of pixel (0, 0): its corner lies half a pixel before
-            transform = [a, b, c - (0.5 * a + 0.5 * b), d, e, f - (0.5 * d + 0.5 * e)]
-        if nodata is not None:
-            if isinstance(nodata, bytes):
-                nodata = nodata.decode("ascii", "replace")
-            if isinstance(nodata, (tuple, list)):
-                nodata = nodata[0]
-            nodata = float(str(nodata).strip().rstrip("\x00").strip())
-        epsg = None
-        if keys is not None:
-            for key in (GEO_KEY_PROJECTED_CS_TYPE, GEO_KEY_GEOGRAPHIC_TYPE):
-                code = _geo_key(keys, key)
-                if code is not None and 0 < code < GEO_KEY_USER_DEFINED:
-                    epsg = code
-                    break
         raster = cls(data, transform, nodata)
         raster.epsg = epsg
         return raster
+
+
+def georeference_from_tags(path, tags):
+    """(transform (a, b, c, d, e, f), nodata or None, epsg or None) from the TIFF tags of a GeoTIFF: no pixel is decoded.
+    ValueError for a file without georeferencing tags, or with several tiepoints and no scale."""
+    scale = tags.get(TAG_MODEL_PIXEL_SCALE)
+    tie = tags.get(TAG_MODEL_TIEPOINT)
+    matrix = tags.get(TAG_MODEL_TRANSFORMATION)
+    keys = tags.get(TAG_GEO_KEY_DIRECTORY)
+    nodata = tags.get(TAG_GDAL_NODATA)
+    if scale is not None and tie is not None:
+        if len(tie) != 6:
+            raise ValueError(f"{path}: {len(tie) // 6} tiepoints beside a pixel scale: one is expected")
+        sx, sy = float(scale[0]), float(scale[1])
+        i, j, _k, X, Y, _Z = (float(v) for v in tie)
+        transform = [sx, 0.0, X - i * sx, 0.0, -sy, Y + j * sy]
+    elif matrix is not None:
+        if len(matrix) != 16:
+            raise ValueError(f"{path}: ModelTransformation has {len(matrix)} values, not 16")
+        transform = [float(matrix[k]) for k in (0, 1, 3, 4, 5, 7)]
+    elif tie is not None:
+        raise ValueError(f"{path}: tiepoints without a pixel scale (a warp through several tiepoints is not supported)")
+    else:
+        raise ValueError(f"{path}: no georeferencing (ModelPixelScale + ModelTiepoint or ModelTransformation)")
+    if keys is not None and _geo_key(keys, GEO_KEY_RASTER_TYPE) == RASTER_PIXEL_IS_POINT:
+        a, b, c, d, e, f = transform   # the tags place the CENTRE of pixel (0, 0): its corner lies half a pixel before
+        transform = [a, b, c - (0.5 * a + 0.5 * b), d, e, f - (0.5 * d + 0.5 * e)]
+    if nodata is not None:
+        if isinstance(nodata, bytes):
+            nodata = nodata.decode("ascii", "replace")
+        if isinstance(nodata, (tuple, list)):
+            nodata = nodata[0]
+        nodata = float(str(nodata).strip().rstrip("\x00").strip())
+    epsg = None
+    if keys is not None:
+        for key in (GEO_KEY_PROJECTED_CS_TYPE, GEO_KEY_GEOGRAPHIC_TYPE):
+            code = _geo_key(keys, key)
+            if code is not None and 0 < code < GEO_KEY_USER_DEFINED:
+                epsg = code
+                break
+    return transform, nodata, epsg
+
+
+def read_geotiff_header(path):
+    """(transform, nodata, epsg, height, width) of a GeoTIFF of ANY band count and sample type -- an RGB(A) orthomosaic, which
+    `PlanarRaster.from_geotiff` refuses, included: only the tags are read."""
+    from PIL import Image
+
+    limit, Image.MAX_IMAGE_PIXELS = Image.MAX_IMAGE_PIXELS, None   # an orthomosaic is large; nothing is decoded here
+    try:
+        with Image.open(Path(path)) as image:
+            tags = image.tag_v2 if hasattr(image, "tag_v2") else {}
+            transform, nodata, epsg = georeference_from_tags(path, tags)
+            width, height = image.size
+    finally:
+        Image.MAX_IMAGE_PIXELS = limit
+    return tuple(transform), nodata, epsg, int(height), int(width)
 
 
 def _geo_key(directory, key):

@@ -14,8 +14,14 @@ import numpy as np
 _TYPES = {np.dtype(np.uint8): 8, np.dtype(np.uint16): 16, np.dtype(np.uint32): 32}
 
 
-def write_tiff_deflate(path, array: np.ndarray, level: int = 6, strip_bytes: int = 1 << 20) -> None:
-    """(H, W) or (H, W, C) uint8 / uint16 / uint32 array -> deflate-compressed TIFF at `path`."""
+def write_tiff_deflate(path, array: np.ndarray, level: int = 6, strip_bytes: int = 1 << 20, transform=None, nodata=None,
+                       epsg=None) -> None:
+    """(H, W) or (H, W, C) uint8 / uint16 / uint32 array -> deflate-compressed TIFF at `path`.
+
+    Optional georeferencing makes it a GeoTIFF that `PlanarRaster.from_geotiff` and GDAL read: transform (a, b, c, d, e, f) with
+    x = a col + b row + c, y = d col + e row + f of pixel CORNERS -- ModelPixelScale + ModelTiepoint when b = d = 0 and a > 0 > e,
+    the 16-value ModelTransformation otherwise --, nodata (GDAL_NODATA, ASCII) and epsg (a GeoKeyDirectory with PixelIsArea and
+    the code as ProjectedCSTypeGeoKey, or GeographicTypeGeoKey for the codes 4000-4999)."""
     a = np.ascontiguousarray(array)
     if a.ndim == 2:
         a = a[:, :, None]
@@ -67,6 +73,28 @@ def write_tiff_deflate(path, array: np.ndarray, level: int = 6, strip_bytes: int
         tags.append(struct.pack("<HHIHH", 339, SHORT, 2, 1, 1))
     else:
         tags.append(entry(339, SHORT, c, out_of_line("H", [1] * c)))
+    DOUBLE, ASCII = 12, 2
+    if transform is not None:
+        ta, tb, tc, td, te, tf = (float(v) for v in transform)
+        if tb == 0.0 and td == 0.0 and ta > 0.0 and te < 0.0:
+            tags.append(entry(33550, DOUBLE, 3, out_of_line("d", [ta, -te, 0.0])))                    # ModelPixelScale
+            tags.append(entry(33922, DOUBLE, 6, out_of_line("d", [0.0, 0.0, 0.0, tc, tf, 0.0])))      # ModelTiepoint
+        else:
+            matrix = [ta, tb, 0.0, tc, td, te, 0.0, tf, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0]
+            tags.append(entry(34264, DOUBLE, 16, out_of_line("d", matrix)))                           # ModelTransformation
+    if transform is not None or epsg is not None:
+        keys = [(1025, 0, 1, 1)]                                                                      # GTRasterType: PixelIsArea
+        if epsg is not None:
+            geographic = 4000 <= int(epsg) <= 4999
+            keys = [(1024, 0, 1, 2 if geographic else 1)] + keys + [(2048 if geographic else 3072, 0, 1, int(epsg))]
+        directory = [1, 1, 0, len(keys)] + [v for key in keys for v in key]
+        tags.append(entry(34735, SHORT, len(directory), out_of_line("H", directory)))                 # GeoKeyDirectory
+    if nodata is not None:
+        text = (repr(int(nodata)) if float(nodata) == int(nodata) else repr(float(nodata))).encode("ascii") + b"\0"
+        if len(text) <= 4:
+            tags.append(struct.pack("<HHI4s", 42113, ASCII, len(text), text.ljust(4, b"\0")))         # GDAL_NODATA, in line
+        else:
+            tags.append(entry(42113, ASCII, len(text), out_of_line("B", list(text))))
     tags.sort(key=lambda e: struct.unpack("<H", e[:2])[0])
     ifd_offset = extra_base + len(extra)
     with open(Path(path), "wb") as f:

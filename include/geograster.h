@@ -696,6 +696,41 @@ int gr_reproject_points(gr_ctx *ctx, const double *points, int64_t V, const int3
  * everything stays available through geograster.h. */
 #include "geograster_outlines.h"
 
+/* The orthomosaic baseline (geograster_ortho.h): the count types of the tile assembly and the words of its
+ * statistics block, the work items and the statistics words of the zonal class counts. */
+enum {
+  GR_COUNT_U8 = 0,   /* counts and weights are uint8: sums modulo 2^8   */
+  GR_COUNT_U16 = 1,  /* uint16: sums modulo 2^16                        */
+  GR_COUNT_F64 = 2   /* float64: adds in ascending tile index           */
+};
+enum {
+  GR_ORTHO_STAT_WITH_CLASS = 0,    /* pixels that took a class                                  */
+  GR_ORTHO_STAT_WITHOUT = 1,       /* pixels written as nodataval                               */
+  GR_ORTHO_STAT_LONGEST_LIST = 2,  /* the most tiles that cover one pixel                       */
+  GR_ORTHO_STAT_PAIRS = 3,         /* (tile, pixel) pairs read                                  */
+  GR_ORTHO_STAT_WORDS = 4
+};
+enum {
+  GR_ORTHO_MAX_CLASSES = 255
+};
+enum {
+  GR_ZONAL_STAT_TESTED = 0,          /* cells of the work items                                 */
+  GR_ZONAL_STAT_INSIDE = 1,          /* (row, cell) pairs with the cell's centre in the row     */
+  GR_ZONAL_STAT_NODATA = 2,          /* ... of them nodata                                      */
+  GR_ZONAL_STAT_OVER = 3,            /* ... of them with a value >= C (counted nowhere else)    */
+  GR_ZONAL_STAT_LARGEST_PLUS_1 = 4,  /* 1 + the largest value of an inside cell that is not nodata; 0 without one */
+  GR_ZONAL_STAT_LARGEST_RING = 5,    /* the vertices of the largest ring                        */
+  GR_ZONAL_STAT_RINGS_IGNORED = 6,   /* rings of fewer than 3 vertices                          */
+  GR_ZONAL_STAT_WORDS = 8
+};
+enum {
+  GR_ZONAL_MAX_CLASSES = 256,
+  GR_ZONAL_ITEM_INTS = 7,    /* int32 values of a work item                                     */
+  GR_ZONAL_BLOCK_W = 64,     /* the widest and the tallest block of cells a work item may name  */
+  GR_ZONAL_BLOCK_H = 128
+};
+#include "geograster_ortho.h"
+
 #ifdef __cplusplus
 }
 #endif
