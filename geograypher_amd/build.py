@@ -11,7 +11,8 @@ CSRC = ROOT / "csrc"
 # translation units of the library (csrc/gr_internal.hpp says what lives where); raster_tile.hip holds the dominant kernel
 SOURCES = [CSRC / n for n in ("geograster.hip", "mesh_upload.hip", "binning.hip", "raster_tile.hip", "project.hip", "warp.hip",
                               "resize.hip", "rays.hip", "equirect.hip", "polygons.hip", "cover.hip", "terrain.hip", "select.hip", "crs.hip", "ortho.hip")]
-HEADERS = [CSRC / "gr_internal.hpp", CSRC / "dev_common.hpp", CSRC / "geom_dev.hpp", CSRC / "scratch_layout.hpp", CSRC / "crs_constants.hpp"]
+HEADERS = [CSRC / "gr_internal.hpp", CSRC / "dev_common.hpp", CSRC / "geom_dev.hpp", CSRC / "scratch_layout.hpp", CSRC / "device_buffer.hpp",
+           CSRC / "crs_constants.hpp"]
 SRC = CSRC / "raster_tile.hip"   # the tile kernel's source (tests/test_isa_waits.py compiles it to assembly)
 OUT = CSRC / "libgeograster.so"
 OBJ = CSRC / "_obj"

@@ -201,13 +201,14 @@ int ensure_bins(gr_ctx *c, int n_slots, int T) {
   const int Tcap = clg < 0 ? ((T + 3) & ~3) : (32 << clg);  // words per counter array; the arrays start 16-byte aligned (a chain reads four counters at once)
   const int64_t ctrl_stride = ((GR_CTRL_HDR + (direct ? 2 : 4) * (int64_t)Tcap) + 63) / 64 * 64;   // (exact binning: + offsets and cursors)
   const int64_t work_stride = ceil_div(F, GR_BLOCK) + 4;
-  int rc = grow(c, c->ctrl, c->ctrl_have, ctrl_stride * n_slots, "bin control");
-  if (!rc) rc = grow(c, c->comp, c->comp_have, GR_ENT_Q * cap * n_slots, "entry list");
-  if (!rc) rc = grow(c, c->nrow8, c->nrow_have, cap * n_slots + 64, "entry row counts");
-  if (!rc) rc = grow(c, c->work, c->work_have, work_stride * n_slots, "work list");
-  if (!rc) rc = grow(c, c->clip, c->clip_have, F * n_slots, "clip list");
+  DeviceMem mem{c};
+  int rc = reserve(mem, c->ctrl, ctrl_stride * n_slots, "bin control");
+  if (!rc) rc = reserve(mem, c->comp, GR_ENT_Q * cap * n_slots, "entry list");
+  if (!rc) rc = reserve(mem, c->nrow8, cap * n_slots + 64, "entry row counts");
+  if (!rc) rc = reserve(mem, c->work, work_stride * n_slots, "work list");
+  if (!rc) rc = reserve(mem, c->clip, F * n_slots, "clip list");
   const int64_t RF = std::max<int64_t>(F, c->rec_cap_request);  // records per view: a face each, a clipped face up to six
-  if (!rc && !direct) rc = grow(c, c->rec, c->rec_have, 4 * RF * n_slots, "record planes");  // exact path only
+  if (!rc && !direct) rc = reserve(mem, c->rec, 4 * RF * n_slots, "record planes");  // exact path only
   if (rc) return rc;
   c->slots = n_slots; c->Tcap = Tcap; c->clg = clg; c->ent_cap = cap; c->ctrl_stride = ctrl_stride; c->work_stride = work_stride;
   c->rec_F = RF; c->rec_stride = 4 * RF;
@@ -247,15 +248,13 @@ int raster_views(gr_ctx *c, const float *cams, int n_views, int h, int w, int32_
   const int tw = (int)ceil_div(ceil_div(F, 64), 4);
   const bool use_touched = labels != nullptr;
   if (labels) {
-    rc = ensure_winner(c, sizeof(uint32_t) * (size_t)F * B * (overlap ? 2 : 1), s);
+    DeviceMem mem{c};
+    rc = reserve_winner(c, F * B * (overlap ? 2 : 1), s);
+    if (!rc) rc = reserve(mem, c->touched, (int64_t)2 * B * tw, "winner group maps");
+    if (!rc) rc = reserve(mem, c->visits, ceil_div(F, 64) + 4, "visit counters");
     if (rc) return rc;
-    if (use_touched) {
-      rc = grow(c, c->touched, c->touched_have, (int64_t)2 * B * tw, "winner group maps");
-      if (!rc) rc = grow(c, c->visits, c->visits_have, ceil_div(F, 64) + 4, "visit counters");
-      if (rc) return rc;
-      if (again == 0) GR_HIP(c, hipMemsetAsync(c->visits, 0, sizeof(uint32_t) * (size_t)(ceil_div(F, 64) + 4), s));
-      c->visits_pending = true;
-    }
+    if (again == 0) GR_HIP(c, hipMemsetAsync(c->visits, 0, sizeof(uint32_t) * (size_t)(ceil_div(F, 64) + 4), s));
+    c->visits_pending = true;
     if (overlap && !c->side) {
       GR_HIP(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
       for (int i = 0; i < 2; ++i) {
@@ -304,7 +303,7 @@ int raster_views(gr_ctx *c, const float *cams, int n_views, int h, int w, int32_
       else learn(c, T, c->cur_cap, miss, micro);
       if (grow || miss || micro) return raster_views(c, cams, n_views, h, w, ids, depth, labels, C, votes, counts, flags, s, again + 1);
     }
-    uint32_t *win = labels ? (uint32_t *)c->winner + (int64_t)buf * F * B : nullptr;
+    uint32_t *win = labels ? c->winner + (int64_t)buf * F * B : nullptr;
     RasterOut out;
     out.ids = ids ? ids + v0 * P : nullptr;
     out.depth = depth ? depth + v0 * P : nullptr;
@@ -350,16 +349,13 @@ int gr_ctx_create(int device, gr_ctx **out) {
   gr_ctx *c = new (std::nothrow) gr_ctx();
   if (!c) return GR_ENOMEM;
   c->device = device;
-  if (hipMalloc(&c->stats, sizeof(unsigned long long) * GR_ST_ALLOC) != hipSuccess ||
-      hipMalloc(&c->flag, sizeof(int) * 8) != hipSuccess) {  // flag word + upload scratch (vertex bounds)
-    delete c;
-    return GR_ENOMEM;
-  }
+  DeviceMem mem{c};
+  if (reserve_group(mem, want(c->stats, GR_ST_ALLOC, "statistics"), want(c->flag, 8, "flag word")) != GR_OK) { delete c; return GR_ENOMEM; }
   (void)hipMemset(c->stats, 0, sizeof(unsigned long long) * GR_ST_ALLOC);
-  (void)hipDeviceSynchronize();   // (the null stream's memset: a non-blocking stream of the first call would not wait for it)
 #ifdef GR_STAMPS
-  if (hipMalloc(&c->stamps, sizeof(unsigned long long) * 32 * 1024) == hipSuccess) (void)hipMemset(c->stamps, 0, sizeof(unsigned long long) * 32 * 1024);
+  if (reserve(mem, c->stamps, 32 * 1024, "phase stamps") == GR_OK) (void)hipMemset(c->stamps, 0, sizeof(unsigned long long) * 32 * 1024);
 #endif
+  (void)hipDeviceSynchronize();   // (the null stream's memsets: a non-blocking stream of the first call would not wait for them)
   *out = c;
   return GR_OK;
 }
@@ -375,10 +371,8 @@ int gr_ctx_destroy(gr_ctx *c) {
     if (c->ev_vote[i]) (void)hipEventDestroy(c->ev_vote[i]);
   }
   if (c->side) (void)hipStreamDestroy(c->side);
-  for (void *p : {(void *)c->ctrl, (void *)c->rec, (void *)c->comp, (void *)c->nrow8, (void *)c->work, (void *)c->clip, c->winner,
-                  (void *)c->stage.ptr, (void *)c->stage_b.ptr, (void *)c->blk, (void *)c->visits, (void *)c->touched, (void *)c->soup,
-                  (void *)c->bvert, (void *)c->bidx, (void *)c->orig, (void *)c->stats, (void *)c->flag})
-    if (p) (void)hipFree(p);
+  DeviceMem mem{c};
+  release_all(mem, *c);
   delete c;
   return GR_OK;
 }

@@ -1,7 +1,8 @@
 #pragma once
 // geograypher_amd/csrc/gr_internal.hpp -- what the translation units of libgeograster share: constants, the kernel
-// argument blocks, the context, and the host-side helpers (error text, HIP-event spans, grow-only scratch, the stage arena:
-// Scratch, stage_acquire, GR_CUB_MAX; its layouts come from scratch_layout.hpp).
+// argument blocks, the context, and the host-side helpers (error text, HIP-event spans, the context's device memory: Buf, reserve,
+// release_all from device_buffer.hpp, instantiated here with DeviceMem; the stage arena: Scratch, stage_acquire, GR_CUB_MAX; its
+// layouts come from scratch_layout.hpp).
 //   geograster.hip   context, options, learned binning table, the raster call (launch groups, side stream), status
 //   mesh_upload.hip  gr_mesh_upload: Morton order, de-indexed soup, block bounds            (per upload)
 //   binning.hip      k_cull_blocks, k_setup_cull, k_clip_faces, entry compilation, exact-path scan / fill  (per view)
@@ -40,6 +41,7 @@
 #include <vector>
 
 #include "geograster.h"
+#include "device_buffer.hpp"
 #include "scratch_layout.hpp"
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -174,7 +176,7 @@ struct RasterOut {
 };
 
 // A block of per-call device scratch and the stream of its last user (stage_acquire below).
-struct Scratch { uint8_t *ptr = nullptr; int64_t have = 0; hipStream_t last = nullptr; };
+struct Scratch : Buf<uint8_t> { hipStream_t last = nullptr; };
 
 }  // namespace grimpl
 
@@ -183,34 +185,26 @@ struct gr_ctx {
   const float *verts = nullptr;
   const int32_t *faces = nullptr;
   int64_t V = 0, F = 0;
+  // Device memory: every buffer is a Buf (device_buffer.hpp: pointer and element count), grown by reserve, named in each_buffer.
   // bin scratch
-  uint32_t *ctrl = nullptr;
-  int4 *rec = nullptr;
-  int4 *comp = nullptr;
-  uint8_t *nrow8 = nullptr;
-  int64_t nrow_have = 0;
-  uint32_t *work = nullptr;
-  int64_t work_stride = 0;
-  uint32_t *clip = nullptr;   // [slot][F] clip lists (R7)
-  int64_t clip_have = 0;
-  float4 *blk = nullptr;
-  uint32_t *touched = nullptr;     // fused aggregation: [2][slots][tw] group maps (a byte per 64 faces) of the launch groups in flight
-  uint32_t *visits = nullptr;      // ... [F / 64] (view, group) pairs the vote passes of the current call visited (gr_raster_stats.chunk_visits)
-  int64_t visits_have = 0;
+  grimpl::Buf<uint32_t> ctrl, work;
+  grimpl::Buf<int4> rec, comp;
+  grimpl::Buf<uint8_t> nrow8;
+  grimpl::Buf<uint32_t> clip;      // [slot][F] clip lists (R7)
+  grimpl::Buf<uint32_t> touched;   // fused aggregation: [2][slots][tw] group maps (a byte per 64 faces) of the launch groups in flight
+  grimpl::Buf<uint32_t> visits;    // ... [F / 64] (view, group) pairs the vote passes of the current call visited (gr_raster_stats.chunk_visits)
   bool visits_pending = false;     // ... not added into the call's statistics yet (gr_raster_status does)
-  int64_t touched_have = 0;
   uint32_t *cur_touched = nullptr; // the bitmap the next bin_batch fills (null: none)
   int cur_tw = 0;
-  int64_t blk_cap = 0;
-  float *soup = nullptr;
-  float *bvert = nullptr;    // distinct vertices per 64-face block (k_block_vertices)
-  uint32_t *bidx = nullptr;  // per soup face: its vertices' positions in the block's list
-  int32_t *orig = nullptr;   // soup position -> caller's face id (Morton order)
-  int64_t soup_cap = 0;
-  unsigned long long *stats = nullptr;
-  int *flag = nullptr;
-  int64_t ctrl_stride = 0, rec_stride = 0, ent_cap = 0, ent_cap_request = 0;
-  int64_t ctrl_have = 0, comp_have = 0, work_have = 0, rec_have = 0;  // allocated element counts
+  // the mesh buffers: one group (gr_mesh_upload: reserve_group), all five hold at least these lengths or all are empty
+  grimpl::Buf<float4> blk;         // [ceil(F / GR_BLOCK)]
+  grimpl::Buf<float> soup;         // [9 F]
+  grimpl::Buf<float> bvert;        // [3 GR_BLOCK_VERTS ceil(F / GR_BLOCK)] distinct vertices per 64-face block (k_block_vertices)
+  grimpl::Buf<uint32_t> bidx;      // [F] per soup face: its vertices' positions in the block's list
+  grimpl::Buf<int32_t> orig;       // [F] soup position -> caller's face id (Morton order)
+  grimpl::Buf<unsigned long long> stats;   // [GR_ST_ALLOC]
+  grimpl::Buf<int> flag;           // [8] flag word + upload scratch (vertex bounds)
+  int64_t ctrl_stride = 0, rec_stride = 0, work_stride = 0, ent_cap = 0, ent_cap_request = 0;
   int Tcap = 0, slots = 0, clg = -1;
   int64_t rec_F = 0;                   // records per plane and slot of the exact path (>= F)
   int64_t rec_cap_request = 0;         // ... asked for by a call whose clipped faces outgrew F records (gr_raster_status)
@@ -250,15 +244,11 @@ struct gr_ctx {
   int last_n_views = 0;
   bool direct_ok = true;     // cleared when a tile overflowed its slots: later calls take the exact path
   bool last_direct = false;
-  // winner scratch
-  void *winner = nullptr;
-  size_t winner_bytes = 0;
+  grimpl::Buf<uint32_t> winner;   // winner scratch (reserve_winner)
   // fused aggregation: the vote kernel of launch group g runs on a side stream beside the binning of group g + 1
   hipStream_t side = nullptr;
   hipEvent_t ev_raster[2] = {nullptr, nullptr}, ev_vote[2] = {nullptr, nullptr};
-#ifdef GR_STAMPS
-  unsigned long long *stamps = nullptr;  // diagnostic build: phase cycles of the tile kernel, summed since the last read
-#endif
+  grimpl::Buf<unsigned long long> stamps;  // GR_STAMPS (diagnostic build) only: phase cycles of the tile kernel, summed since the last read
   // The stage arena: the per-call scratch of every stage call (the mesh upload's sort, pair counts, ray pairs, resize, point
   // bounds, region, sub-mesh, class outlines, set cover), one call at a time, each carving what it needs from offset 0.
   grimpl::Scratch stage;
@@ -274,6 +264,10 @@ struct gr_ctx {
   std::vector<hipEvent_t> pool;
   int prof_views = 0, prof_raster_launches = 0;
   char err[512] = {0};
+  template <class V> void each_buffer(V &&v) {   // THE list of the context's device buffers (release_all in gr_ctx_destroy)
+    v(ctrl); v(rec); v(comp); v(nrow8); v(work); v(clip); v(touched); v(visits); v(blk); v(soup); v(bvert); v(bidx); v(orig);
+    v(stats); v(flag); v(winner); v(stamps); v(stage); v(stage_b);
+  }
 };
 
 namespace grimpl {
@@ -351,8 +345,6 @@ inline void release_spans(gr_ctx *c) {   // events back to the pool
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Grow-only scratch: every buffer keeps its own capacity and is re-allocated only when it is too small (a new mesh or
-// image size does not touch buffers that are already large enough).
 // Before scratch is freed: wait for the work that can still use it -- the stream of the context's last call and its side
 // stream -- not for the whole device (other contexts, the caller's own streams keep running).
 inline void quiesce(gr_ctx *c) {
@@ -367,25 +359,24 @@ inline void note_stream(gr_ctx *c, hipStream_t s) {
   c->used_streams.push_back(s);
 }
 
-template <typename T>
-int grow(gr_ctx *c, T *&ptr, int64_t &have, int64_t want, const char *what) {
-  if (ptr && have >= want) return GR_OK;
-  if (ptr) quiesce(c);
-  if (ptr) (void)hipFree(ptr);
-  ptr = nullptr; have = 0;
-  if (hipMalloc(&ptr, sizeof(T) * (size_t)want) != hipSuccess)
-    return fail(c, GR_ENOMEM, "%s scratch allocation failed (%lld bytes)", what, (long long)(sizeof(T) * (size_t)want));
-  have = want;
-  return GR_OK;
-}
+struct DeviceMem {   // the allocator policy of device_buffer.hpp for a context: the library's ONE allocation and ONE free
+  gr_ctx *c;
+  void *alloc(size_t bytes, const char *what) {
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) { p = nullptr; (void)fail(c, GR_ENOMEM, "%s scratch allocation failed (%lld bytes)", what, (long long)bytes); }
+    return p;
+  }
+  void free(void *p) { (void)hipFree(p); }
+  void quiesce() { grimpl::quiesce(c); }
+};
 
 // The only way to stage scratch: `bytes` of `sc` for work that the caller enqueues on `s`.  The block's last user may have been
 // another stream of the context and may have returned without waiting (gr_resize_image_f64, gr_mesh_upload, ...): it is waited
 // for here, so calls of one context on different streams use the block in turn.  On one stream this adds nothing.
 inline int stage_acquire(gr_ctx *c, Scratch &sc, size_t bytes, hipStream_t s, const char *what) {
   if (sc.ptr && sc.last != s) (void)hipStreamSynchronize(sc.last);   // (a block that was used: the null stream is a stream too)
-  const int rc = grow(c, sc.ptr, sc.have, (int64_t)bytes, what);
-  if (rc != GR_OK) return rc;
+  DeviceMem mem{c};
+  if (const int rc = reserve(mem, sc, (int64_t)bytes, what)) return rc;
   note_stream(c, s);
   sc.last = s;
   return GR_OK;
@@ -398,15 +389,13 @@ inline int stage_acquire(gr_ctx *c, Scratch &sc, size_t bytes, hipStream_t s, co
 // (the zeroes go out on the CALL's stream: a plain hipMemset runs on the null stream, which a non-blocking stream -- torch's
 // side streams, one per device thread of a devices=[...] mesh -- does not wait for: the first view's winners could be wiped
 // after they were written; found by tests/test_devices_kwarg.py with three contexts on one GPU)
-inline int ensure_winner(gr_ctx *c, size_t bytes, hipStream_t s) {
-  if (c->winner && c->winner_bytes >= bytes) return GR_OK;
-  if (c->winner) quiesce(c);
-  if (c->winner) (void)hipFree(c->winner);
-  c->winner = nullptr; c->winner_bytes = 0;
-  if (hipMalloc(&c->winner, bytes) != hipSuccess) return fail(c, GR_ENOMEM, "winner scratch allocation failed");
-  if (hipMemsetAsync(c->winner, 0, bytes, s) != hipSuccess) return fail(c, GR_EHIP, "winner memset failed");
-  c->winner_bytes = bytes;
-  return GR_OK;
+inline int reserve_winner(gr_ctx *c, int64_t n, hipStream_t s) {
+  DeviceMem mem{c};
+  bool fresh;
+  const int rc = reserve(mem, c->winner, n, "winner", &fresh);
+  if (rc != GR_OK || !fresh || hipMemsetAsync(c->winner, 0, sizeof(uint32_t) * (size_t)n, s) == hipSuccess) return rc;
+  release(mem, c->winner);   // (never a block that was not zeroed)
+  return fail(c, GR_EHIP, "winner memset failed");
 }
 
 inline BinArgs make_args(gr_ctx *c, int h, int w, int slot0) {

@@ -185,7 +185,7 @@ int gr_mesh_upload(gr_ctx *c, const float *verts, const int32_t *faces, int64_t 
   GR_HIP(c, hipSetDevice(c->device));
   // scratch of the upload: [0] bad-index flag, [1..6] vertex bounds (ordered-uint min x3, max x3)
   uint32_t init[8] = {0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0, 0};
-  uint32_t *up = reinterpret_cast<uint32_t *>(c->flag);
+  uint32_t *up = reinterpret_cast<uint32_t *>(c->flag.ptr);
   GR_HIP(c, hipMemcpyAsync(up, init, sizeof(init), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_validate_faces, dim3((unsigned)ceil_div(3 * F, 256)), dim3(256), 0, s, faces, 3 * F, V, c->flag);
   // few blocks: every wave ends with six atomics on the same six words (2048 blocks spent 0.56 ms queueing on them)
@@ -216,28 +216,16 @@ int gr_mesh_upload(gr_ctx *c, const float *verts, const int32_t *faces, int64_t 
   const float inv0 = ext[ax0] > 0.0f ? 65535.0f / ext[ax0] : 0.0f, inv1 = ext[ax1] > 0.0f ? 65535.0f / ext[ax1] : 0.0f;
 
   const int64_t nblk = ceil_div(F, GR_BLOCK);
-  if (c->blk_cap < nblk || c->soup_cap < F) quiesce(c);  // nothing may still read the buffers that are replaced below
+  // From here the mesh buffers may be replaced: the context has NO mesh until the call succeeds (a raster or project call behind
+  // a failed upload answers GR_ENOMESH and never walks the old face count through new, or released, buffers).
+  c->verts = nullptr; c->faces = nullptr; c->V = 0; c->F = 0;
+  c->stats_deferred = false;   // (view totals a raster call on the old mesh left for the status call: void)
+  c->visits_pending = false;   // (... and the visit counters of its vote passes: sized for the old mesh)
+  DeviceMem mem{c};
+  int rc = reserve_group(mem, want(c->blk, nblk, "block bounds"), want(c->soup, 9 * F, "face soup"), want(c->orig, F, "face order"),
+                         want(c->bvert, 3 * GR_BLOCK_VERTS * nblk, "block vertex"), want(c->bidx, F, "block index"));
+  if (rc != GR_OK) return rc;
   note_stream(c, s);
-  if (c->blk_cap < nblk) {
-    if (c->blk) (void)hipFree(c->blk);
-    c->blk = nullptr; c->blk_cap = 0;
-    if (hipMalloc(&c->blk, sizeof(float4) * nblk) != hipSuccess) return fail(c, GR_ENOMEM, "block bounds allocation failed");
-    c->blk_cap = nblk;
-  }
-  if (c->soup_cap < F) {
-    if (c->soup) (void)hipFree(c->soup);
-    if (c->orig) (void)hipFree(c->orig);
-    c->soup = nullptr; c->orig = nullptr; c->soup_cap = 0;
-    if (c->bvert) (void)hipFree(c->bvert);
-    if (c->bidx) (void)hipFree(c->bidx);
-    c->bvert = nullptr; c->bidx = nullptr;
-    if (hipMalloc(&c->soup, sizeof(float) * 9 * F) != hipSuccess) return fail(c, GR_ENOMEM, "face soup allocation failed");
-    if (hipMalloc(&c->orig, sizeof(int32_t) * F) != hipSuccess) return fail(c, GR_ENOMEM, "face order allocation failed");
-    if (hipMalloc(&c->bvert, sizeof(float) * 3 * GR_BLOCK_VERTS * ceil_div(F, GR_BLOCK)) != hipSuccess)
-      return fail(c, GR_ENOMEM, "block vertex allocation failed");
-    if (hipMalloc(&c->bidx, sizeof(uint32_t) * F) != hipSuccess) return fail(c, GR_ENOMEM, "block index allocation failed");
-    c->soup_cap = F;
-  }
   // Morton codes -> stable radix sort of (code, face) pairs (rocPRIM through hipcub) -> orig[]
   size_t cub = 0;
   GR_CUB_MAX(c, cub, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr,
@@ -245,21 +233,19 @@ int gr_mesh_upload(gr_ctx *c, const float *verts, const int32_t *faces, int64_t 
   // scratch: code_in [F] | code_out [F] | idx_in [F] | rocPRIM
   Carve cv;
   const size_t o_code_in = cv.array<uint32_t>(F), o_code_out = cv.array<uint32_t>(F), o_idx_in = cv.array<int32_t>(F), o_tmp = cv.bytes(cub);
-  int rc = stage_acquire(c, c->stage, cv.total(), s, "sort");
+  rc = stage_acquire(c, c->stage, cv.total(), s, "sort");
   if (rc != GR_OK) return rc;
   uint8_t *base = c->stage.ptr;
   uint32_t *code_in = Carve::at<uint32_t>(base, o_code_in), *code_out = Carve::at<uint32_t>(base, o_code_out);
   int32_t *idx_in = Carve::at<int32_t>(base, o_idx_in);
   hipLaunchKernelGGL(k_face_codes, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, verts, faces, F, ax0, ax1, lo[ax0], inv0,
                      lo[ax1], inv1, code_in, idx_in);
-  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, cub, code_in, code_out, idx_in, c->orig, (int)F, 0, 32, s));
+  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, cub, code_in, code_out, idx_in, c->orig.ptr, (int)F, 0, 32, s));
   hipLaunchKernelGGL(k_build_soup, dim3((unsigned)ceil_div(3 * F, 256)), dim3(256), 0, s, verts, faces, c->orig, F, c->soup);
   hipLaunchKernelGGL(k_block_bounds, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, c->soup, F, c->blk);
   hipLaunchKernelGGL(k_block_vertices, dim3((unsigned)ceil_div(nblk, 4)), dim3(256), 0, s, verts, faces, c->orig, F, c->bvert, c->bidx);
   GR_HIP(c, hipGetLastError());
   c->verts = verts; c->faces = faces; c->V = V; c->F = F;
-  c->stats_deferred = false;   // (view totals a raster call on the old mesh left for the status call: void)
-  c->visits_pending = false;   // (... and the visit counters of its vote passes: sized for the old mesh)
   return GR_OK;
 }
 

@@ -609,10 +609,10 @@ int project_groups(gr_ctx *c, const int32_t *ids, int n_views, int h, int w, int
   GR_HIP(c, hipSetDevice(c->device));
   const int64_t P = (int64_t)h * w, F = c->F;
   const int B = n_views < GR_MAX_BATCH ? n_views : GR_MAX_BATCH;
-  int rc = ensure_winner(c, sizeof(uint32_t) * (size_t)F * B, s);
+  int rc = reserve_winner(c, F * B, s);
   if (rc) return rc;
   note_stream(c, s);
-  uint32_t *win = (uint32_t *)c->winner;
+  uint32_t *win = c->winner;
   const int compat = (flags & GR_FLAG_NEG1_IS_LAST_FACE) ? 1 : 0;
   if (check && !check->defer) GR_HIP(c, hipMemsetAsync(c->flag, 0, sizeof(int), s));
   for (int v0 = 0; v0 < n_views; v0 += B) {
