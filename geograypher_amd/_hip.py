@@ -206,6 +206,7 @@ _SIGNATURES = {
     "gr_learned_cache_clear": [],
     "gr_get_stage_times": [_vp, ctypes.POINTER(StageTimes)],
     "gr_mesh_upload": [_vp, _vp, _vp, _i64, _i64, _vp],
+    "gr_debug_read_upload": [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_uint64), _vp],
     "gr_raster_face_ids": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "gr_raster_status": [_vp, ctypes.POINTER(RasterStats)],
     "gr_raster_overflow_causes": [_vp],
@@ -905,6 +906,20 @@ class HipRaster:
         self._call("gr_mesh_upload", v.data_ptr(), f.data_ptr(), v.shape[0], f.shape[0], self._stream())
         self._verts, self._faces = v, f  # borrowed by the library: keep alive
         self.n_verts, self.n_faces = int(v.shape[0]), int(f.shape[0])
+
+    def debug_upload(self) -> dict:
+        """For tests: what the last upload left on the device (gr_debug_read_upload) -- {"orig": (F,) int32, "blk": (B, 4)
+        float32, "bvert": (B, 192, 3) float32, "bidx": (F,) int32 holding the library's uint32 words bit for bit, "mesh_sig":
+        int}, B = ceil(F / 64).  RuntimeError (GR_ENOMESH) without a mesh."""
+        torch = _torch()
+        F = max(self.n_faces, 1)
+        B = (F + 63) // 64
+        orig, bidx = self._empty((F,), torch.int32), self._empty((F,), torch.int32)
+        blk, bvert = self._empty((B, 4), torch.float32), self._empty((B, 192, 3), torch.float32)
+        sig = ctypes.c_uint64(0)
+        self._call("gr_debug_read_upload", orig.data_ptr(), blk.data_ptr(), bvert.data_ptr(), bidx.data_ptr(), ctypes.byref(sig),
+                   self._stream())
+        return {"orig": orig, "blk": blk, "bvert": bvert, "bidx": bidx, "mesh_sig": int(sig.value)}
 
     # -- pix2face ------------------------------------------------------------------------------------------------
     def raster_face_ids(self, cams, h: int, w: int, out=None, want_depth: bool = False, check: bool = True):

@@ -104,8 +104,17 @@ __global__ __launch_bounds__(256) void k_block_bounds(const float *__restrict__ 
       const float e = 0.5f * (hi[d] - lo[d]);
       r2 += e * e;
     }
-    // NaN / inf vertices give a NaN radius: the cull test below is written so that NaN never culls
-    blk[b] = make_float4(c[0], c[1], c[2], sqrtf(r2) * 1.0001f + 1e-6f);
+    // The sphere must hold every vertex of the block around the centre AS STORED.  The sum lo + hi is rounded, by at most
+    // 2^-24 |lo + hi|, and the halving is exact: c[d] lies within 2^-24 |c_exact| <= 2^-24 |c[d]| (1 + 2^-23) of the box's
+    // centre on its axis, and the stored centre within the sum of that over the three axes (1-norm >= 2-norm) of the exact
+    // one.  The factor 1.0001 pays for the roundings of the half diagonal alone (five operations, 2^-24 relative each): a
+    // block that is thin on two axes, or a single point, has no diagonal to hide the centre's error in -- 3.9 mm at a
+    // coordinate of 1e5, where the cull dropped slivers whose end was inside the window.  So the bound is added, doubled to
+    // pay for its own roundings: (|c0| + |c1| + |c2|) 2^-23.
+    // fminf / fmaxf drop NaN: a NaN coordinate is ignored and the block is bounded by its other coordinates (all NaN on an
+    // axis: NaN centre, infinite radius).  An infinite coordinate gives an infinite or NaN centre and an infinite or NaN
+    // radius.  k_cull_blocks rejects on `<` alone, which is false for NaN and against -inf: such a block is always kept.
+    blk[b] = make_float4(c[0], c[1], c[2], sqrtf(r2) * 1.0001f + 1e-6f + (fabsf(c[0]) + fabsf(c[1]) + fabsf(c[2])) * 0x1p-23f);
   }
 }
 
@@ -246,6 +255,22 @@ int gr_mesh_upload(gr_ctx *c, const float *verts, const int32_t *faces, int64_t 
   hipLaunchKernelGGL(k_block_vertices, dim3((unsigned)ceil_div(nblk, 4)), dim3(256), 0, s, verts, faces, c->orig, F, c->bvert, c->bidx);
   GR_HIP(c, hipGetLastError());
   c->verts = verts; c->faces = faces; c->V = V; c->F = F;
+  return GR_OK;
+}
+
+int gr_debug_read_upload(gr_ctx *c, int32_t *orig, float *blk4, float *bvert, uint32_t *bidx, uint64_t *mesh_sig_h, void *stream) {
+  if (!c) return GR_EINVAL;
+  if (!c->verts) return fail(c, GR_ENOMESH, "gr_mesh_upload has not been called");
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
+  const size_t F = (size_t)c->F, nblk = (size_t)ceil_div(c->F, GR_BLOCK);
+  note_stream(c, s);
+  if (orig) GR_HIP(c, hipMemcpyAsync(orig, c->orig.ptr, sizeof(int32_t) * F, hipMemcpyDeviceToDevice, s));
+  if (blk4) GR_HIP(c, hipMemcpyAsync(blk4, c->blk.ptr, sizeof(float4) * nblk, hipMemcpyDeviceToDevice, s));
+  if (bvert) GR_HIP(c, hipMemcpyAsync(bvert, c->bvert.ptr, sizeof(float) * 3 * GR_BLOCK_VERTS * nblk, hipMemcpyDeviceToDevice, s));
+  if (bidx) GR_HIP(c, hipMemcpyAsync(bidx, c->bidx.ptr, sizeof(uint32_t) * F, hipMemcpyDeviceToDevice, s));
+  if (mesh_sig_h) *mesh_sig_h = c->mesh_sig;
+  GR_HIP(c, hipStreamSynchronize(s));
   return GR_OK;
 }
 

@@ -198,6 +198,12 @@ int gr_get_stage_times(gr_ctx *ctx, gr_stage_times *out_h);
  * After GR_EINVAL or GR_EINDEX the previous mesh stays in use; an upload that fails later (GR_ENOMEM, GR_EHIP) leaves the context
  * WITHOUT a mesh: raster and project calls answer GR_ENOMESH until an upload succeeds. */
 int gr_mesh_upload(gr_ctx *ctx, const float *verts, const int32_t *faces, int64_t V, int64_t F, void *stream);
+/* For tests: what the last upload left behind, copied device to device into the caller's buffers (a null pointer skips that
+ * product): orig [F] soup position -> caller's face; blk4 [ceil(F / 64)][4] the bounding sphere (centre, radius) of each block
+ * of 64 soup faces; bvert [ceil(F / 64)][192][3] the distinct vertices of each block in order of first use (rows behind a
+ * block's count are unspecified); bidx [F] a face's three positions in its block's list, 8 bits each, and the block's count - 1
+ * in the top byte.  mesh_sig_h: the mesh signature, to a host word.  GR_ENOMESH without a mesh.  Synchronises `stream`. */
+int gr_debug_read_upload(gr_ctx *ctx, int32_t *orig, float *blk4, float *bvert, uint32_t *bidx, uint64_t *mesh_sig_h, void *stream);
 
 /* pix2face -- replaces meshes.py:1776-1836 (encode ids, VTK render, decode, background mask) for n_views
  * cameras of equal image size.  ids: n_views x h x w int32, background -1.  depth (may be NULL): n_views x h x w
