@@ -144,6 +144,15 @@ GR_ZONAL_MAX_CLASSES = 256
 GR_ZONAL_ITEM_INTS = 7
 GR_ZONAL_BLOCK_W = 64
 GR_ZONAL_BLOCK_H = 128
+# mesh decimation by vertex clustering: stats words of gr_cluster_decimate (the first three in submesh_extract's order)
+GR_DECIM_STAT_KEPT_FACES = 0
+GR_DECIM_STAT_KEPT_VERTICES = 1
+GR_DECIM_STAT_BAD_FACES = 2
+GR_DECIM_STAT_CELLS = 3
+GR_DECIM_STAT_COLLAPSED = 4
+GR_DECIM_STAT_DUPLICATES = 5
+GR_DECIM_STAT_OUTSIDE = 6
+GR_DECIM_STAT_WORDS = 8
 
 
 class StageTimes(ctypes.Structure):
@@ -260,6 +269,12 @@ _ORTHO_SIGNATURES = {
     "gr_zonal_class_counts": [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp],
 }
 ORTHO_SYMBOLS = tuple(_ORTHO_SIGNATURES)
+# ... and the calls of include/geograster_decimate.h (mesh decimation by vertex clustering), under the same contract.
+_DECIMATE_SIGNATURES = {
+    "gr_cluster_count": [_vp, _vp, _i64, _i64, _vp, _vp],
+    "gr_cluster_decimate": [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+}
+DECIMATE_SYMBOLS = tuple(_DECIMATE_SIGNATURES)
 
 
 def library_path() -> Path:
@@ -282,7 +297,7 @@ def load_library() -> ctypes.CDLL:
     # library's runtime without devices and gr_ctx_create answers GR_ENODEVICE.
     _torch()
     lib = ctypes.CDLL(str(_LIB_PATH))
-    for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES}.items():
+    for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -1263,6 +1278,47 @@ class HipRaster:
         if check:
             self._check_faces("gr_submesh_extract", on_host, 2, V)
         return face_ids[:n_faces], point_ids[:n_points], new_faces[:n_faces], counts
+
+    # -- mesh decimation: vertex clustering on a uniform grid ---------------------------------
+    def to_device(self, array, dtype: str):
+        """numpy / tensor -> contiguous tensor of the torch dtype named `dtype` ("int64", "int32", ...) on this device: what a
+        caller that hands the same array to several calls uploads once."""
+        return self._dev(array, getattr(_torch(), dtype))
+
+    def cluster_count(self, verts_q, s: int) -> int:
+        """gr_cluster_count: verts_q (V, 3) int64 snapped vertices behind their per-axis minimum -- numpy
+        or a device tensor --, s the cell side in grid steps -> the number of occupied cells, read back (8 bytes): one probe of
+        the search of `utils.geometric.cluster_cell_size`."""
+        torch = _torch()
+        vq_t = self._shaped(verts_q, torch.int64, ("V", 3), "vertices")
+        cells = self._empty((1,), torch.int64)
+        self._call("gr_cluster_count", vq_t.data_ptr(), int(vq_t.shape[0]), int(s), cells.data_ptr(), self._stream())
+        return int(cells.item())
+
+    def cluster_decimate(self, verts_q, faces, s: int, check: bool = True):
+        """gr_cluster_decimate: verts_q (V, 3) int64 snapped vertices behind their per-axis minimum,
+        faces (F, 3) int -- numpy or device tensors --, s the cell side in grid steps -> (rep (V,) int32: the representative of
+        every vertex' cell, -1 outside the key range; face_ids (n_faces,) int64, point_ids (n_points,) int64, new_faces (n_faces,
+        3) int32 tensors; stats (GR_DECIM_STAT_WORDS,) int64 tensor).  A face is dropped when two of its corners share a cell, or
+        behind an earlier face with the same three cells; a representative is kept iff a kept face uses it; the ids are the
+        ascending original indices and new_faces indexes the kept vertices.  Reads the statistics back once (the results are cut
+        to its counts); `check` (default) raises ValueError when a face names a vertex that does not exist or that has no cell."""
+        torch = _torch()
+        vq_t = self._shaped(verts_q, torch.int64, ("V", 3), "vertices")
+        f_t = self._shaped(faces, torch.int32, ("F", 3), "faces")
+        V, F = int(vq_t.shape[0]), int(f_t.shape[0])
+        rep = self._empty((V,), torch.int32)
+        face_ids = self._empty((F,), torch.int64)
+        point_ids = self._empty((V,), torch.int64)
+        new_faces = self._empty((F, 3), torch.int32)
+        stats = self._stats(GR_DECIM_STAT_WORDS)
+        self._call("gr_cluster_decimate", vq_t.data_ptr(), V, f_t.data_ptr(), F, int(s), rep.data_ptr(), face_ids.data_ptr(),
+                   point_ids.data_ptr(), new_faces.data_ptr(), stats.data_ptr(), self._stream())
+        on_host = stats.cpu()   # the one read of all the words
+        n_faces, n_points = int(on_host[GR_DECIM_STAT_KEPT_FACES]), int(on_host[GR_DECIM_STAT_KEPT_VERTICES])
+        if check:
+            self._check_faces("gr_cluster_decimate", on_host, GR_DECIM_STAT_BAD_FACES, V)
+        return rep, face_ids[:n_faces], point_ids[:n_points], new_faces[:n_faces], on_host
 
     # -- class outlines: the rings around the faces of every class -------------------------------------------------
     def class_outlines(self, verts_q, faces, face_class, n_classes: int, capacity: Optional[int] = None, check: bool = True):

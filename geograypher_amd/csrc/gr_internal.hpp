@@ -27,6 +27,10 @@
 //                    crs_constants.hpp, written by tools/make_crs_constants.py); no mesh needed
 //   ortho.hip        orthomosaic baseline: tile predictions assembled into a class raster (k_assemble_tiles), class counts of the raster cells
 //                    under polygon rows (k_zonal_class_counts, k_zonal_ring_stats); no mesh needed
+//   decimate.hip     mesh decimation by vertex clustering: cell keys and centre distances (k_decim_keys), cell heads (k_decim_heads),
+//                    representatives (k_decim_scatter_rep), remapped faces (k_decim_faces), first face per triple (k_decim_face_flags)
+//                    + radix sorts and scans; compacts with k_submesh_write; no mesh needed
+//   compact_dev.hpp  k_submesh_write, the write kernel of polygons.hip's sub-mesh and of decimate.hip
 //   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip, crs.hip and ortho.hip: orient, ring_span, edge_crossing (THE even-odd rule of
 //                    k_polygon_weights, k_face_polygon_index and k_points_in_region), load_face, stat_add / stat_add_u32 / stat_max / stat_count
 #include <hip/hip_runtime.h>

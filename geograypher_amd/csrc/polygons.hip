@@ -25,6 +25,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "compact_dev.hpp"
 #include "geom_dev.hpp"
 #include "gr_internal.hpp"
 
@@ -458,24 +459,7 @@ __global__ __launch_bounds__(256) void k_submesh_flags(const uint8_t *__restrict
   stat_count(counts, 2, bad, lane);
 }
 
-// fpos, vpos: the exclusive sums of fflag, vused.  One thread per face and per vertex.
-__global__ __launch_bounds__(256) void k_submesh_write(const int32_t *__restrict__ faces, int64_t F, int64_t V,
-                                                       const int32_t *__restrict__ fflag, const int32_t *__restrict__ fpos,
-                                                       const int32_t *__restrict__ vused, const int32_t *__restrict__ vpos,
-                                                       int64_t *__restrict__ face_ids, int64_t *__restrict__ point_ids,
-                                                       int32_t *__restrict__ new_faces, unsigned long long *__restrict__ counts) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < F && fflag[i]) {   // a kept face's vertices are in range and used
-    const int64_t j = fpos[i];
-    face_ids[j] = i;
-    for (int k = 0; k < 3; ++k) new_faces[j * 3 + k] = vpos[faces[i * 3 + k]];
-  }
-  if (i < V && vused[i]) point_ids[vpos[i]] = i;
-  if (i == 0) {
-    counts[0] = F > 0 ? (unsigned long long)(fpos[F - 1] + fflag[F - 1]) : 0ull;
-    counts[1] = V > 0 ? (unsigned long long)(vpos[V - 1] + vused[V - 1]) : 0ull;
-  }
-}
+// (k_submesh_write, the write kernel behind the two scans, is compact_dev.hpp's: gr_cluster_decimate compacts with it too)
 
 
 // ---- gr_class_outlines: the outline rings of every class of a per-face labelling ---------------------

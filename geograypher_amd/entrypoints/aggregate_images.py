@@ -8,8 +8,9 @@ the same distance (`select_mesh_ROI`, on the device), which needs `ROI_points_fi
 face values (`aggregate_projected_images`) and the class per face (`argmax_nonzero`, NaN where nothing was seen) are written as
 `.npy`; with `DTM_file`, `DTM_points_file` and `height_above_ground_threshold` the faces near the terrain lose their class first
 (`label_ground_class`); with `top_down_vector_projection_savefile` and `top_down_points_file` the classes are then written as a
-top-down vector map, one multipolygon per class (`export_face_labels_vector`, traced on the device).  Not carried over: mesh
-decimation and the visualisations."""
+top-down vector map, one multipolygon per class (`export_face_labels_vector`, traced on the device).  With `mesh_downsample` and
+`mesh_downsample_method="cluster"` the mesh is decimated by vertex clustering behind the crop (`TexturedPhotogrammetryMesh.decimate`,
+on the device).  Not carried over: the reference's quadric decimation and the visualisations."""
 import argparse
 import json
 import math
@@ -54,16 +55,20 @@ def aggregate_images(
     ROI_camera_CRS=None,
     DTM_CRS=None,
     top_down_CRS=None,
+    mesh_downsample_method: typing.Union[str, None] = None,
 ):
     """Aggregate the labels under `label_folder` onto the mesh (see the module docstring).  The reference's arguments and defaults;
-    `mesh_downsample != 1`, `vis`, `ROI` without `ROI_points_file`, `DTM_file` without `DTM_points_file` and
+    `mesh_downsample != 1` without `mesh_downsample_method`, `vis`, `ROI` without `ROI_points_file`, `DTM_file` without `DTM_points_file` and
     `top_down_vector_projection_savefile` without `top_down_points_file` raise NotImplementedError.  Beyond the reference:
     `ROI_points_file`, `DTM_points_file` and `top_down_points_file` (`.npy` paths or arrays: the V ORIGINAL vertices in the ROI's / the
     DTM's / the export's planar CRS; with the last, the class per face is written as a `.geojson` map, `export_face_labels_vector`), `ROI_camera_points_file` (the positions of the cameras of the full
     set in the ROI's CRS; without it the camera set is not cut to the ROI, with a log line), and `camera_set` and `backend`, which
     replace the objects built from `cameras_file` and the device.  Each `*_points_file` has a sibling `ROI_CRS`, `ROI_camera_CRS`,
     `DTM_CRS`, `top_down_CRS`: the CRS of the ROI / the DTM / the map (e.g. "EPSG:32610") in place of the points, which are then
-    reprojected on the device; giving both is a ValueError.  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
+    reprojected on the device; giving both is a ValueError.  `mesh_downsample_method="cluster"`
+    decimates the mesh to about `mesh_downsample` of its vertices behind the ROI crop (`TexturedPhotogrammetryMesh.decimate`: vertex
+    clustering, not the reference's quadric decimation); the `*_points_file` arrays stay those of the ORIGINAL mesh and the results
+    are per face of the decimated mesh (`mesh.decimated_face_IDs`).  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
     from geograypher_amd.cameras.segmentor import SegmentorPhotogrammetryCameraSet
     from geograypher_amd.meshes import TexturedPhotogrammetryMesh, TexturedPhotogrammetryMeshChunked
     from geograypher_amd.predictors.derived_segmentors import LookUpSegmentor
@@ -86,7 +91,7 @@ def aggregate_images(
             raise NotImplementedError(f"{name}: {why}, which is outside the projection path")
     if vis:
         raise NotImplementedError("vis: visualisations need pyvista, which is outside the projection path")
-    if mesh_downsample != 1:
+    if mesh_downsample != 1 and mesh_downsample_method is None:
         raise NotImplementedError("mesh_downsample: mesh decimation is outside the projection path (meshes.py:215-226)")
 
     if isinstance(IDs_to_labels, (str, Path)):
@@ -131,7 +136,10 @@ def aggregate_images(
     if ROI is not None:
         roi_kwargs = {"ROI": ROI, "ROI_buffer_meters": 0 if ROI_buffer_radius_meters is None else ROI_buffer_radius_meters,
                       "points_in_ROI_CRS": ROI_points}
+    if mesh_downsample_method is not None:   # behind the crop (aggregate_images.py:140-148)
+        roi_kwargs.update(downsample_target=mesh_downsample, downsample_method=mesh_downsample_method)
     mesh = MeshClass(mesh_file, input_CRS=mesh_CRS, IDs_to_labels=IDs_to_labels, backend=backend, **roi_kwargs)
+    kept_point_IDs = mesh.original_point_IDs()   # of the ORIGINAL vertices: what the crop and the decimation kept, or None
 
     if top_down_vector_projection_savefile is not None:   # fail before the aggregation, not behind it
         if Path(top_down_vector_projection_savefile).suffix != ".geojson":
@@ -139,10 +147,10 @@ def aggregate_images(
                                       ".geojson need geopandas, which is outside the projection path")
     if top_down_vector_projection_savefile is not None and not is_CRS_designator(top_down_points):
         top_down_points = np.asarray(top_down_points, dtype=np.float64)
-        n_original = top_down_points.shape[0] if mesh.ROI_point_IDs is None else None
+        n_original = top_down_points.shape[0] if kept_point_IDs is None else None
         if top_down_points.ndim != 2 or top_down_points.shape[1] not in (2, 3) or \
                 (n_original is not None and n_original != mesh.points.shape[0]) or \
-                (mesh.ROI_point_IDs is not None and len(mesh.ROI_point_IDs) and top_down_points.shape[0] <= int(np.max(mesh.ROI_point_IDs))):
+                (kept_point_IDs is not None and len(kept_point_IDs) and top_down_points.shape[0] <= int(np.max(kept_point_IDs))):
             raise ValueError(f"top_down_points_file must hold the (V, 2) or (V, 3) ORIGINAL vertices, got {top_down_points.shape}")
 
     if ROI is not None and ROI_buffer_radius_meters is not None:
@@ -175,8 +183,8 @@ def aggregate_images(
 
     if DTM_file is not None and height_above_ground_threshold is not None:   # reference: aggregate_images.py:198-206
         points_in_raster_CRS = DTM_points
-        if mesh.ROI_point_IDs is not None and not is_CRS_designator(points_in_raster_CRS):
-            points_in_raster_CRS = np.asarray(points_in_raster_CRS)[mesh.ROI_point_IDs]
+        if kept_point_IDs is not None and not is_CRS_designator(points_in_raster_CRS):
+            points_in_raster_CRS = np.asarray(points_in_raster_CRS)[kept_point_IDs]
         predicted_face_classes = mesh.label_ground_class(labels=predicted_face_classes,
                                                          height_above_ground_threshold=height_above_ground_threshold,
                                                          DTM_file=DTM_file, ground_ID=np.nan, set_mesh_texture=False,
@@ -188,8 +196,8 @@ def aggregate_images(
 
     if top_down_vector_projection_savefile is not None:   # reference: aggregate_images.py:216-231, behind the ground step
         points_in_export_CRS = top_down_points
-        if mesh.ROI_point_IDs is not None and not is_CRS_designator(points_in_export_CRS):
-            points_in_export_CRS = points_in_export_CRS[mesh.ROI_point_IDs]
+        if kept_point_IDs is not None and not is_CRS_designator(points_in_export_CRS):
+            points_in_export_CRS = points_in_export_CRS[kept_point_IDs]
         IDs = mesh.get_IDs_to_labels()
         label_names = None if IDs is None else [IDs.get(i, None) for i in range(max(list(IDs.keys())) + 1)]
         mesh.export_face_labels_vector(face_labels=np.squeeze(predicted_face_classes, axis=1),
@@ -226,7 +234,11 @@ def parse_args(argv=None):
     parser.add_argument("--ROI-camera-CRS", help="CRS of --ROI instead of --ROI-camera-points-file: the camera set is cut to the ROI")
     parser.add_argument("--ROI-buffer-radius-meters", default=50, type=float, help="Only applies with --ROI")
     parser.add_argument("--IDs-to-labels", type=Path, required=True, help="JSON file {ID: label}")
-    parser.add_argument("--mesh-downsample", type=float, default=1.0, help="Only 1 is available here")
+    parser.add_argument("--mesh-downsample", type=float, default=1.0,
+                        help="Fraction of the mesh vertices to keep, in (0, 1]; anything but 1 needs --mesh-downsample-method")
+    parser.add_argument("--mesh-downsample-method", choices=["cluster"],
+                        help="How --mesh-downsample decimates: cluster = vertex clustering on a uniform grid, on the device (not "
+                        "the quadric decimation of the reference, which is not available here)")
     parser.add_argument("--aggregate-image-scale", type=float, default=0.25, help="Aggregate at this fraction of the image size")
     parser.add_argument("--n-aggregation-clusters", type=int, help="Selects the chunked mesh class, as in the reference")
     parser.add_argument("--aggregated-face-values-savefile", type=Path, help="Where the (F, classes) values are saved (.npy)")

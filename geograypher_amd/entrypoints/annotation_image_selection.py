@@ -14,7 +14,9 @@ over through files as in the reference:
   then redundant views pruned; deterministic.  The (views,) bool mask is written with `np.save`.
 * `save_selected_images`: the images of the mask are linked into `selected_images_save_folder` (`save_images`).
 
-Not carried over: mesh decimation and the visualisations."""
+With `downsample_target` and `downsample_method="cluster"` the mesh of `compute_projection` is decimated by vertex clustering behind
+the crop (`TexturedPhotogrammetryMesh.decimate`, on the device).  Not carried over: the reference's quadric decimation and the
+visualisations."""
 import argparse
 import typing
 from pathlib import Path
@@ -46,14 +48,17 @@ def determine_minimum_overlapping_images(
     backend=None,
     ROI_CRS=None,
     ROI_camera_CRS=None,
+    downsample_method: typing.Union[str, None] = None,
 ):
     """Determine a subset of images that together observe the entire scene (see the module docstring).  The reference's arguments
-    and defaults; `downsample_target != 1`, `vis` and `ROI` without `ROI_points_file` raise NotImplementedError.  Beyond the
+    and defaults; `downsample_target != 1` without `downsample_method`, `vis` and `ROI` without `ROI_points_file` raise NotImplementedError.  Beyond the
     reference: `ROI_points_file` (a `.npy` path or array: the V ORIGINAL vertices in the ROI's CRS), `ROI_camera_points_file` (the
     positions of the cameras in that CRS; without it the camera set is not cut to the ROI, with a log line), and `camera_set`
     and `backend`, which replace the objects built from `cameras_file` and the device; `ROI_CRS` and `ROI_camera_CRS`: the CRS of
     the ROI (e.g. "EPSG:32610") in place of the two points files -- the vertices and camera positions are then reprojected on the
-    device --, giving a file and its CRS sibling is a ValueError.  `min_observations_to_be_included`: a
+    device --, giving a file and its CRS sibling is a ValueError.  `downsample_method="cluster"` decimates the
+    mesh of `compute_projection` to about `downsample_target` of its vertices behind the ROI crop (`TexturedPhotogrammetryMesh.decimate`:
+    vertex clustering, not the reference's quadric decimation).  `min_observations_to_be_included`: a
     selected set need only see the faces that at least this many cameras see.  Returns a dict with what the stages that ran
     produced: "summed_projections", "selected_images" (the mask), "selection" (the record of `select_covering_views`),
     "subset_camera_set"."""
@@ -66,7 +71,7 @@ def determine_minimum_overlapping_images(
                                   "which is outside the projection path")
     if vis:
         raise NotImplementedError("vis: visualisations need pyvista, which is outside the projection path")
-    if downsample_target != 1:
+    if downsample_target != 1 and downsample_method is None:
         raise NotImplementedError("downsample_target: mesh decimation is outside the projection path (meshes.py:215-226)")
     if isinstance(mesh_CRS, int) or (isinstance(mesh_CRS, str) and mesh_CRS.isdigit()):
         mesh_CRS = f"EPSG:{int(mesh_CRS)}"   # the reference's --mesh-CRS is an EPSG code
@@ -99,6 +104,8 @@ def determine_minimum_overlapping_images(
         roi_kwargs = {}
         if ROI is not None:
             roi_kwargs = {"ROI": ROI, "ROI_buffer_meters": ROI_buffer_meters, "points_in_ROI_CRS": ROI_points}
+        if downsample_method is not None:   # behind the crop (annotation_image_selection.py:96-104)
+            roi_kwargs.update(downsample_target=downsample_target, downsample_method=downsample_method)
         mesh = TexturedPhotogrammetryMeshIndexPredictions(mesh_file, input_CRS=mesh_CRS, backend=backend, **roi_kwargs)
         cameras = load_cameras(mesh.backend)
         segmentor = ImageIDSegmentor(image_filenames=cameras.get_image_filename(index=None, absolute=True))
@@ -157,7 +164,11 @@ def parse_args(argv=None):
     parser.add_argument("--projections-filename", help="The (faces, views) visibility matrix (.npz, scipy sparse)")
     parser.add_argument("--selected-images-mask-filename", help="The (views,) bool mask of the chosen images (.npy)")
     parser.add_argument("--selected-images-save-folder", help="Where the chosen images are linked")
-    parser.add_argument("--downsample-target", default=1.0, type=float, help="Only 1 is available here")
+    parser.add_argument("--downsample-target", default=1.0, type=float,
+                        help="Fraction of the mesh vertices to keep, in (0, 1]; anything but 1 needs --downsample-method")
+    parser.add_argument("--downsample-method", choices=["cluster"],
+                        help="How --downsample-target decimates: cluster = vertex clustering on a uniform grid, on the device (not "
+                        "the quadric decimation of the reference, which is not available here)")
     parser.add_argument("--min-observations-to-be-included", default=1, type=float,
                         help="Only faces that at least this many images see must be seen by the chosen images")
     parser.add_argument("--vis", action="store_true", help="Not available here")

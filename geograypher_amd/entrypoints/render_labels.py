@@ -12,8 +12,9 @@ relabelled before rendering (`label_ground_class`, on the device): to a new clas
 this needs `DTM_points_file`, the vertices in the DTM's CRS.  With `ROI` (a `.geojson`, a `PlanarPolygons` or ring arrays) and
 `ROI_points_file`, the vertices in the ROI's CRS, the mesh is cropped to the ROI grown by `mesh_ROI_buffer_radius_meters` before
 anything else (`select_mesh_ROI`, on the device); the camera set is cut to `cameras_ROI_buffer_radius_meters` when
-`ROI_camera_points_file` gives the camera positions in the same CRS.  Not carried over: mesh decimation, saving the image subset or
-the textured mesh, and the visualisations (geopandas, pyvista, matplotlib)."""
+`ROI_camera_points_file` gives the camera positions in the same CRS.  With `mesh_downsample` and `mesh_downsample_method="cluster"`
+the mesh is then decimated by vertex clustering (`TexturedPhotogrammetryMesh.decimate`, on the device).  Not carried over: the
+reference's quadric decimation, saving the image subset or the textured mesh, and the visualisations (geopandas, pyvista, matplotlib)."""
 import argparse
 import json
 import typing
@@ -62,9 +63,10 @@ def render_labels(
     DTM_CRS=None,
     ROI_CRS=None,
     ROI_camera_CRS=None,
+    mesh_downsample_method: typing.Union[str, None] = None,
 ):
     """Render the labels of `texture` into every camera's view (see the module docstring for inputs and files).  The reference's
-    arguments and defaults; `DTM_file` without `DTM_points_file`, `ROI` without `ROI_points_file`, `mesh_downsample != 1`, `subset_images_savefolder`, `textured_mesh_savefile`, `vis`,
+    arguments and defaults; `DTM_file` without `DTM_points_file`, `ROI` without `ROI_points_file`, `mesh_downsample != 1` without `mesh_downsample_method`, `subset_images_savefolder`, `textured_mesh_savefile`, `vis`,
     `mesh_vis_file` and `labels_vis_folder` raise NotImplementedError.  `n_cameras_per_chunk` selects
     `TexturedPhotogrammetryMeshChunked` with ceil(cameras / n_cameras_per_chunk) clusters, as in the reference (the GPU path
     renders the whole mesh either way).  Beyond the reference: `texture_points_file` (a `.npy` path or the array itself, required
@@ -73,8 +75,10 @@ def render_labels(
     required with `ROI`) and `ROI_camera_points_file` (the camera positions in that CRS; without it the camera set is not cut, with a
     log line).  `texture_points_file` and `DTM_points_file` are given for the ORIGINAL mesh and indexed by the kept vertices.  Each
     `*_points_file` has a sibling `texture_CRS`, `DTM_CRS`, `ROI_CRS`, `ROI_camera_CRS`: the CRS of the texture / DTM / ROI (e.g.
-    "EPSG:32610") in place of the points, which are then reprojected on the device; giving both is a ValueError.  Returns
-    the textured mesh."""
+    "EPSG:32610") in place of the points, which are then reprojected on the device; giving both is a ValueError.
+    `mesh_downsample_method="cluster"` decimates the mesh to about `mesh_downsample` of its vertices behind the ROI crop
+    (`TexturedPhotogrammetryMesh.decimate`: vertex clustering, not the reference's quadric decimation); the `*_points_file` arrays
+    and a texture array stay those of the ORIGINAL mesh.  Returns the textured mesh."""
     from geograypher_amd.meshes import TexturedPhotogrammetryMesh, TexturedPhotogrammetryMeshChunked
     from geograypher_amd.utils.geospatial import is_CRS_designator, points_or_CRS
 
@@ -97,7 +101,7 @@ def render_labels(
             raise NotImplementedError(f"{name}: {why}, which is outside the projection path")
     if vis:
         raise NotImplementedError("vis: visualisations need pyvista, which is outside the projection path")
-    if mesh_downsample != 1:
+    if mesh_downsample != 1 and mesh_downsample_method is None:
         raise NotImplementedError("mesh_downsample: mesh decimation is outside the projection path (meshes.py:215-226)")
 
     if camera_set is None:
@@ -110,6 +114,8 @@ def render_labels(
     roi_kwargs = {}
     if ROI is not None:   # reference: render_labels.py:120-131 (cameras), 141-149 (mesh)
         roi_kwargs = {"ROI": ROI, "ROI_buffer_meters": mesh_ROI_buffer_radius_meters, "points_in_ROI_CRS": ROI_points}
+    if mesh_downsample_method is not None:   # behind the crop, before the texture (render_labels.py:141-149)
+        roi_kwargs.update(downsample_target=mesh_downsample, downsample_method=mesh_downsample_method)
     mesh = MeshClass(mesh_file, input_CRS=mesh_CRS, IDs_to_labels=IDs_to_labels, backend=backend, **roi_kwargs)
     if ROI is not None:
         if ROI_camera_points is not None:
@@ -119,14 +125,14 @@ def render_labels(
             mesh.logger.info("ROI without ROI_camera_points_file: the camera set is not cut to the ROI")
     n_render_chunks = None if n_cameras_per_chunk is None else int(ceil(len(camera_set) / n_cameras_per_chunk))
 
-    def kept(points):   # the rows of the vertices the ROI kept (a CRS names the points of the cropped mesh already)
-        if points is None or mesh.ROI_point_IDs is None or is_CRS_designator(points):
+    def kept(points):   # the rows of the vertices the ROI and the decimation kept (a CRS names the points of the current mesh already)
+        if points is None or mesh.original_point_IDs() is None or is_CRS_designator(points):
             return points
-        return np.asarray(points)[mesh.ROI_point_IDs]
+        return np.asarray(points)[mesh.original_point_IDs()]
 
     points_in_polygon_CRS = kept(texture_points)
     if isinstance(texture, np.ndarray):   # an array for the original mesh is cut like the mesh
-        texture = mesh.crop_to_ROI(texture)
+        texture = mesh.to_current_mesh(texture)
     mesh.load_texture(texture, texture_column_name=texture_column_name, IDs_to_labels=mesh.IDs_to_labels,
                       points_in_polygon_CRS=points_in_polygon_CRS)
 
@@ -182,7 +188,11 @@ def parse_args(argv=None):
     parser.add_argument("--mesh-ROI-buffer-radius-meters", default=50, type=float, help="Only applies with --ROI")
     parser.add_argument("--cameras-ROI-buffer-radius-meters", default=100, type=float, help="Only applies with --ROI")
     parser.add_argument("--render-image-scale", type=float, default=1, help="Render at this fraction of the image size")
-    parser.add_argument("--mesh-downsample", type=float, default=1, help="Only 1 is available here")
+    parser.add_argument("--mesh-downsample", type=float, default=1,
+                        help="Fraction of the mesh vertices to keep, in (0, 1]; anything but 1 needs --mesh-downsample-method")
+    parser.add_argument("--mesh-downsample-method", choices=["cluster"],
+                        help="How --mesh-downsample decimates: cluster = vertex clustering on a uniform grid, on the device (not "
+                        "the quadric decimation of the reference, which is not available here)")
     parser.add_argument("--IDs-to-labels", type=Path, help="JSON file {ID: label}")
     parser.add_argument("--n-cameras-per-chunk", type=int, help="Selects the chunked mesh class, as in the reference")
     parser.add_argument("--cast-to-uint8", action="store_true", help="Write uint8 labels (else uint16 / uint32)")

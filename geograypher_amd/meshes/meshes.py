@@ -134,6 +134,7 @@ class TexturedPhotogrammetryMesh:
         devices: typing.Optional[typing.Sequence[int]] = None,
         vertex_order: str = "r1",
         points_in_ROI_CRS: typing.Optional[np.ndarray] = None,
+        downsample_method: typing.Optional[str] = None,
     ):
         """A textured mesh that renders to / aggregates from camera views on an MI355X.
 
@@ -142,7 +143,8 @@ class TexturedPhotogrammetryMesh:
         interpreted in `input_CRS`: EPSG:4978 (the frame the reference reprojects every mesh into, meshes.py:1659) or
         another WGS84 system `geograypher_amd.utils.geospatial.WGS84CRS.parse` takes (EPSG:4326 / 4979 in the authority's
         axis order lat, lon, h; the UTM zones), whose vertices are brought to EPSG:4978 on the device here; any other CRS
-        needs pyproj and raises NotImplementedError.  Decimation and
+        needs pyproj and raises NotImplementedError.  The reference's quadric decimation (`downsample_target != 1` without
+        `downsample_method`) and
         vector/raster texture files are likewise outside it and raise NotImplementedError (a `.geojson` texture is
         loaded afterwards, by `load_texture(..., points_in_polygon_CRS=...)`).  `ROI` with `ROI_buffer_meters` crops
         the mesh before the texture is loaded (`select_mesh_ROI`; needs `points_in_ROI_CRS`) and leaves the kept
@@ -168,9 +170,20 @@ class TexturedPhotogrammetryMesh:
             points_in_ROI_CRS: the mesh vertices (V, 2) or (V, 3) in the ROI's planar CRS, or the name of that CRS ("EPSG:32610",
                 32610, a `WGS84CRS`: the vertices are then reprojected on the device), required with `ROI` (the reference
                 reprojects them with pyproj); without it `ROI` raises NotImplementedError.
+            downsample_method: None (default) -- `downsample_target != 1` raises NotImplementedError: the reference's quadric
+                decimation (VTK) is not built --, or "cluster": the mesh is decimated to about `downsample_target` of its vertices,
+                0 < downsample_target <= 1, by vertex clustering on a uniform grid (`decimate`; DESIGN.md section 8n: NOT the
+                reference's algorithm), on the device, after the reprojection and the ROI crop and before the texture.  The kept
+                indices, into the mesh after the crop, are left in `self.decimated_point_IDs` and `self.decimated_face_IDs`; a
+                texture array of an earlier vertex or face count is indexed by them (`to_current_mesh`).
         """
-        if downsample_target != 1.0:
-            raise NotImplementedError("mesh decimation is outside the projection path (meshes.py:215-226)")
+        if downsample_method is None:
+            if downsample_target != 1.0:
+                raise NotImplementedError("mesh decimation is outside the projection path (meshes.py:215-226)")
+        elif downsample_method != "cluster":
+            raise ValueError(f"downsample_method must be None or 'cluster', got {downsample_method!r}")
+        elif not 0 < downsample_target <= 1:
+            raise ValueError(f"downsample_target must lie in (0, 1], got {downsample_target!r}")
         if ROI is not None and points_in_ROI_CRS is None:
             raise NotImplementedError("ROI cropping is outside the projection path (meshes.py:646-731) unless the vertices "
                                       "in the ROI's CRS are given: points_in_ROI_CRS")
@@ -244,6 +257,14 @@ class TexturedPhotogrammetryMesh:
             (self.points, self.faces), self.ROI_point_IDs, self.ROI_face_IDs = self.select_mesh_ROI(
                 ROI, buffer_meters=ROI_buffer_meters, return_original_IDs=True, points_in_ROI_CRS=points_in_ROI_CRS)
 
+        self.downsample_method = downsample_method
+        self.decimated_point_IDs = None
+        self.decimated_face_IDs = None
+        self._n_before_decimation = (self.points.shape[0], self.faces.shape[0])   # vertices, faces behind the crop
+        if downsample_method == "cluster":   # in EPSG:4978, behind the crop: where the reference decimates (meshes.py:215-226)
+            (self.points, self.faces), self.decimated_point_IDs, self.decimated_face_IDs = self.decimate(
+                downsample_target, return_original_IDs=True)
+
         self.logger.info("Loading texture")
         if isinstance(IDs_to_labels, (str, Path)):
             import json
@@ -257,7 +278,7 @@ class TexturedPhotogrammetryMesh:
                                           "its CRS: load_texture(..., points_in_polygon_CRS=...)")
             texture = np.load(texture)
         if texture is not None:
-            self.set_texture(self.crop_to_ROI(np.asarray(texture)))
+            self.set_texture(self.to_current_mesh(np.asarray(texture)))
 
     # -- region of interest (DESIGN.md "Region of interest"; reference: meshes.py:646-731) -------------------------
     def crop_to_ROI(self, values: np.ndarray):
@@ -314,6 +335,93 @@ class TexturedPhotogrammetryMesh:
         point_IDs = np.array(point_IDs, dtype=np.int64).reshape(-1)
         self.last_ROI_stats = {"points_inside": int(stats[0]), "points_inside_by_buffer_only": int(stats[1]),
                                "wide_comparisons": int(stats[2]), "faces_kept": len(face_IDs), "points_kept": len(point_IDs)}
+        subset = (self.points[point_IDs], np.array(new_faces, dtype=np.int64).reshape(-1, 3))
+        if return_original_IDs:
+            return subset, point_IDs, face_IDs
+        return subset
+
+    # -- decimation (stands where the reference decimates: meshes.py:215-226, 288-323) ---------
+    def to_current_mesh(self, values: np.ndarray):
+        """A per-vertex or per-face array of the mesh as it was passed in, or as the ROI crop left it -> the rows of the vertices
+        or faces of the mesh as it is now: `crop_to_ROI`, then the rows `decimated_point_IDs` / `decimated_face_IDs` (rule D9: a
+        kept vertex IS an input vertex, so the reference's nearest-neighbour transfer is this gather; face arrays are carried
+        over too).  The count-matching rules of `crop_to_ROI`: an array with a current count (or any other) is returned as it is;
+        one that fits vertices and faces alike is a ValueError.  Without a decimation this is `crop_to_ROI`."""
+        values = self.crop_to_ROI(values)
+        if self.decimated_point_IDs is None or values.ndim == 0:
+            return values
+        n_points, n_faces = self._n_before_decimation
+        n = values.shape[0]
+        if n in (self.points.shape[0], self.faces.shape[0]):
+            return values
+        if n == n_points == n_faces:
+            raise ValueError("Cannot infer whether the array belongs to vertices or faces because the number is the same")
+        if n == n_points:
+            return values[self.decimated_point_IDs]
+        if n == n_faces:
+            return values[self.decimated_face_IDs]
+        return values
+
+    def original_point_IDs(self):
+        """The indices of the current vertices in the mesh as it was passed in: `ROI_point_IDs`, `decimated_point_IDs`, or the
+        one through the other; None when the mesh was neither cropped nor decimated."""
+        ids = self.ROI_point_IDs
+        if getattr(self, "decimated_point_IDs", None) is not None:
+            ids = self.decimated_point_IDs if ids is None else np.asarray(ids)[self.decimated_point_IDs]
+        return ids
+
+    def decimate(self, downsample_target: typing.Optional[float] = None, *, cell_size_meters: typing.Optional[float] = None,
+                 return_original_IDs: bool = False):
+        """The mesh decimated by vertex clustering on a uniform grid (rules D1-D9 of DESIGN.md section 8n), on the device.
+
+        The vertices are snapped to the 1e-6 m grid; every occupied cell of side s keeps ONE of its vertices, the one nearest
+        the cell's centre (ties: the lowest index); a face with two corners in one cell is dropped, and so is every face behind an
+        earlier one with the same three cells.  Exactly one of: downsample_target, 0 < target <= 1 -- s is searched so that at
+        most floor(target V) cells are occupied (`utils.geometric.cluster_cell_size`: one device probe per step) --, or
+        cell_size_meters, the cell side itself (ValueError outside the range the mesh's extent allows).  Everything is integer
+        arithmetic: the result is exact and the same on every run and device.
+
+        Returns (points, faces) -- the points are rows of `self.points`, faces index them --, or with `return_original_IDs`
+        ((points, faces), point_IDs, face_IDs): the ascending int64 indices into the mesh as it is.  The mesh itself is not
+        changed.  A result without faces is a ValueError.  The call's figures are left in `self.last_decimation_stats`.
+
+        Out of scope: quadric-error vertex placement (float accumulation in a fixed order, vertices off the input set), parity
+        with VTK's decimation, topology repair, and `face_to_vert_texture`."""
+        from geograypher_amd._hip import (GR_DECIM_STAT_BAD_FACES, GR_DECIM_STAT_CELLS, GR_DECIM_STAT_COLLAPSED,
+                                          GR_DECIM_STAT_DUPLICATES, GR_DECIM_STAT_OUTSIDE)
+        from geograypher_amd.utils.geometric import SNAP_GRID_METERS, cluster_cell_range, cluster_cell_size, snap_points_3d
+
+        if (downsample_target is None) == (cell_size_meters is None):
+            raise ValueError("decimate takes exactly one of downsample_target and cell_size_meters")
+        if downsample_target is not None and not 0 < downsample_target <= 1:
+            raise ValueError(f"downsample_target must lie in (0, 1], got {downsample_target!r}")
+        verts_q = snap_points_3d(self.points)
+        s_min, s_max = cluster_cell_range(verts_q)
+        backend = self.backend
+        held = backend.to_device(verts_q, "int64") if hasattr(backend, "to_device") else verts_q
+        if cell_size_meters is not None:
+            s, probes = int(np.rint(float(cell_size_meters) / SNAP_GRID_METERS)), 0
+            if not s_min <= s <= s_max:
+                raise ValueError(f"cell_size_meters={cell_size_meters} is outside [{s_min * SNAP_GRID_METERS:g}, "
+                                 f"{s_max * SNAP_GRID_METERS:g}] m, the cell sides this mesh allows")
+        else:
+            s, _, probes = cluster_cell_size(backend, verts_q, downsample_target, held=held)
+        _, face_IDs, point_IDs, new_faces, stats = backend.cluster_decimate(held, self.faces.astype(np.int32), s)
+        face_IDs, point_IDs, new_faces, stats = (np.asarray(_to_host(a) if hasattr(a, "detach") else a)
+                                                 for a in (face_IDs, point_IDs, new_faces, stats))
+        face_IDs = np.array(face_IDs, dtype=np.int64).reshape(-1)
+        point_IDs = np.array(point_IDs, dtype=np.int64).reshape(-1)
+        n_points, n_faces = self.points.shape[0], self.faces.shape[0]
+        self.last_decimation_stats = {
+            "requested_vertex_fraction": None if downsample_target is None else float(downsample_target),
+            "achieved_vertex_fraction": len(point_IDs) / max(n_points, 1), "achieved_face_fraction": len(face_IDs) / max(n_faces, 1),
+            "cell_size_meters": s * SNAP_GRID_METERS, "cell_size_steps": s, "probes": probes,
+            "cells": int(stats[GR_DECIM_STAT_CELLS]), "points_kept": len(point_IDs), "faces_kept": len(face_IDs),
+            "faces_collapsed": int(stats[GR_DECIM_STAT_COLLAPSED]), "faces_duplicate": int(stats[GR_DECIM_STAT_DUPLICATES]),
+            "bad_faces": int(stats[GR_DECIM_STAT_BAD_FACES]), "points_outside": int(stats[GR_DECIM_STAT_OUTSIDE])}
+        if len(face_IDs) == 0:
+            raise ValueError(f"the decimation left no face: every face has two corners in one cell of {s * SNAP_GRID_METERS:g} m "
+                             "(a larger downsample_target or a smaller cell_size_meters keeps some)")
         subset = (self.points[point_IDs], np.array(new_faces, dtype=np.int64).reshape(-1, 3))
         if return_original_IDs:
             return subset, point_IDs, face_IDs

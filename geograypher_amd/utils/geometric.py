@@ -7,6 +7,7 @@ meshes themselves come from `covering_meshes` (`HipRaster.points_bounds`, `HipRa
 """
 from __future__ import annotations
 
+import math
 import typing
 from pathlib import Path
 
@@ -389,8 +390,70 @@ def points_in_region(backend, ROI, points, buffer_meters=0):
     return backend.points_in_region(vq, *table, steps)
 
 
+# -- mesh decimation by vertex clustering ---------------------------------------------------------------------
+CLUSTER_COORD_LIMIT = 1 << 41   # D1: snapped coordinates behind their minimum stay below this
+CLUSTER_CELLS_PER_AXIS = 1 << 21   # D2: a cell component fits 21 bits of the key
+CLUSTER_MAX_CELL_SIDE = 1 << 30    # D2: ... and the doubled offset to the cell's centre 31
+
+
+def snap_points_3d(points) -> np.ndarray:
+    """Rule D1: (V, 3) float64 metres -> (V, 3) int64 on the 1e-6 m grid (`snap_to_grid`, all three columns) behind the per-axis
+    minimum, so every value is >= 0.  A coordinate of 2^41 steps (2 199 023 m) or more behind the minimum is a ValueError."""
+    points = np.asarray(points, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be (V, 3), got {points.shape}")
+    q = snap_to_grid(points)
+    if len(q):
+        q = q - q.min(axis=0)
+        if int(q.max()) >= CLUSTER_COORD_LIMIT:
+            raise ValueError("the mesh spans 2^41 grid steps (2 199 023 m) or more along an axis: too large to decimate on the 1e-6 m grid")
+    return np.ascontiguousarray(q)
+
+
+def cluster_cell_range(verts_q) -> typing.Tuple[int, int]:
+    """Rule D2: (s_min, s_max), the cell sides in grid steps the snapped vertices of `snap_points_3d` allow: s_min keeps every cell
+    component below 2^21, s_max is a cell that holds the whole mesh, at most 2^30."""
+    verts_q = np.asarray(verts_q)
+    extent = int(verts_q.max()) if verts_q.size else 0
+    s_min = max(1, -(-(extent + 1) // CLUSTER_CELLS_PER_AXIS))
+    return s_min, max(s_min, min(extent + 1, CLUSTER_MAX_CELL_SIDE))
+
+
+def cluster_cell_size(backend, verts_q, target: float, held=None) -> typing.Tuple[int, int, int]:
+    """Rule D4 through `backend.cluster_count`: the cell side for a target fraction of the vertices -> (s, cells(s), probes).
+    T = max(1, floor(target V)); s_min when it already gives at most T cells, else the bisection of [s_min, s_max] as D4
+    states it (cells(s) is not strictly monotone: the rule is the procedure).  One probe per step: the first at s_min, at most 30
+    of the bisection, and one at s_max when no step reached it.  The vertices go to the device once (`backend.to_device`; `held`:
+    the caller's copy of them there)."""
+    verts_q = np.asarray(verts_q)
+    V = int(verts_q.shape[0])
+    want = max(1, int(math.floor(float(target) * V)))
+    lo, hi = cluster_cell_range(verts_q)
+    if held is not None:
+        verts_q = held
+    elif hasattr(backend, "to_device"):
+        verts_q = backend.to_device(verts_q, "int64")
+    probes = 1
+    cells = int(backend.cluster_count(verts_q, lo))
+    if cells <= want:
+        return lo, cells, probes
+    cells_hi = None   # cells(hi) once hi has been probed
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        probes += 1
+        cells_mid = int(backend.cluster_count(verts_q, mid))
+        if cells_mid <= want:
+            hi, cells_hi = mid, cells_mid
+        else:
+            lo = mid
+    if cells_hi is None:   # s_max was never probed (one cell, unless the mesh is wider than 2^30 steps)
+        probes += 1
+        cells_hi = int(backend.cluster_count(verts_q, hi))
+    return hi, cells_hi, probes
+
+
 # -- class outlines (DESIGN.md section 8i) ---------------------------------------------------------------------------------------------
-OUTLINE_MAX_CLASSES = 65535    # GR_OUTL_MAX_CLASSES: classes of one gr_class_outlines call
+OUTLINE_MAX_CLASSES = 65535   # GR_OUTL_MAX_CLASSES: classes of one gr_class_outlines call
 MEMBER_MAX_CLASSES = 2 ** 31 - 2   # GR_MEMBER_MAX_CLASSES: classes of one gr_member_outlines call (DESIGN.md section 8l)
 
 

@@ -739,6 +739,20 @@ enum {
 };
 #include "geograster_ortho.h"
 
+/* Mesh decimation by vertex clustering (geograster_decimate.h): the words of its statistics block.  The first
+ * three are the counts of the sub-mesh extraction, in its order. */
+enum {
+  GR_DECIM_STAT_KEPT_FACES = 0,     /* faces of the decimated mesh                                            */
+  GR_DECIM_STAT_KEPT_VERTICES = 1,  /* vertices of the decimated mesh                                         */
+  GR_DECIM_STAT_BAD_FACES = 2,      /* faces with a vertex index outside [0, V) or a vertex without a cell    */
+  GR_DECIM_STAT_CELLS = 3,          /* occupied cells                                                         */
+  GR_DECIM_STAT_COLLAPSED = 4,      /* faces with two corners in one cell                                     */
+  GR_DECIM_STAT_DUPLICATES = 5,     /* faces dropped behind an earlier face with the same three cells         */
+  GR_DECIM_STAT_OUTSIDE = 6,        /* vertices outside the key range: q < 0 or a cell component >= 2^21      */
+  GR_DECIM_STAT_WORDS = 8
+};
+#include "geograster_decimate.h"
+
 #ifdef __cplusplus
 }
 #endif
