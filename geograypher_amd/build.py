@@ -13,7 +13,7 @@ SOURCES = [CSRC / n for n in ("geograster.hip", "mesh_upload.hip", "binning.hip"
                               "resize.hip", "rays.hip", "equirect.hip", "polygons.hip", "cover.hip", "terrain.hip", "select.hip", "crs.hip", "ortho.hip",
                               "decimate.hip")]
 HEADERS = [CSRC / "gr_internal.hpp", CSRC / "dev_common.hpp", CSRC / "geom_dev.hpp", CSRC / "scratch_layout.hpp", CSRC / "device_buffer.hpp",
-           CSRC / "crs_constants.hpp", CSRC / "compact_dev.hpp"]
+           CSRC / "crs_constants.hpp", CSRC / "compact_dev.hpp", CSRC / "cub_steps.hpp"]
 SRC = CSRC / "raster_tile.hip"   # the tile kernel's source (tests/test_isa_waits.py compiles it to assembly)
 OUT = CSRC / "libgeograster.so"
 OBJ = CSRC / "_obj"

@@ -235,10 +235,11 @@ int gr_points_bounds(gr_ctx *c, const double *points, int64_t V, int64_t stride,
   const int grid = (int)std::min<int64_t>(ceil_div(n, GR_BOUNDS_BLOCK * GR_BOUNDS_ROWS_PER_LANE), GR_BOUNDS_MAX_GRID);
   // scratch: part [GR_BOUNDS_MAX_GRID]
   Carve cv;
-  const size_t o_part = cv.array<BoundsPart>(GR_BOUNDS_MAX_GRID);
+  const auto o_part = cv.array<BoundsPart>(GR_BOUNDS_MAX_GRID);
   int rc = stage_acquire(c, c->stage, cv.total(), s, "point-bounds");
   if (rc != GR_OK) return rc;
-  BoundsPart *part = Carve::at<BoundsPart>(c->stage.ptr, o_part);
+  cv.base = c->stage.ptr;
+  BoundsPart *part = o_part();
   hipLaunchKernelGGL(k_points_bounds, dim3((unsigned)grid), dim3(GR_BOUNDS_BLOCK), 0, s, points, n, stride, part);
   hipLaunchKernelGGL(k_points_bounds_combine, dim3(1), dim3(64), 0, s, (const BoundsPart *)part, grid, bounds6,
                      (u64 *)nonfinite);

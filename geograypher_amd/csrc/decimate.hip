@@ -17,9 +17,8 @@
 // Compaction (D7, D8): the two exclusive scans and the write kernel of gr_submesh_extract (k_submesh_write, compact_dev.hpp) over the
 // remapped faces.
 // One lane per vertex or face, 256-lane workgroups, no LDS; every index is checked before it is used.
-#include <hipcub/hipcub.hpp>
-
 #include "compact_dev.hpp"
+#include "cub_steps.hpp"
 #include "geom_dev.hpp"
 #include "gr_internal.hpp"
 
@@ -163,19 +162,17 @@ int gr_cluster_count(gr_ctx *c, const int64_t *verts_q, int64_t V, int64_t s, ui
   GR_HIP(c, hipSetDevice(c->device));
   GR_HIP(c, hipMemsetAsync(cells, 0, sizeof(uint64_t), st));
   if (V == 0) return GR_OK;
-  size_t cub = 0;
-  GR_CUB_MAX(c, cub, hipcub::DeviceRadixSort::SortKeys(nullptr, cub_q, (u64 *)nullptr, (u64 *)nullptr, (int)V, 0, 64, st));
   // scratch: key [V] | key_s [V] | the sort's temporaries
-  Carve cv;
-  const size_t o_key = cv.array<u64>(V), o_key_s = cv.array<u64>(V), o_tmp = cv.bytes(cub);
-  rc = stage_acquire(c, c->stage, cv.total(), st, "cluster-count");
+  Plan p;
+  const auto key = p.array<u64>(V), key_s = p.array<u64>(V);
+  const SortKeys<u64> sort(c, p, V, 64);
+  rc = stage_acquire(c, c->stage, p.finish(), st, "cluster-count");
   if (rc != GR_OK) return rc;
-  uint8_t *base = c->stage.ptr;
-  u64 *key = Carve::at<u64>(base, o_key), *key_s = Carve::at<u64>(base, o_key_s);
+  p.base = c->stage.ptr;
   const dim3 grid((unsigned)ceil_div(V, 256));
-  hipLaunchKernelGGL(k_decim_keys, grid, dim3(256), 0, st, verts_q, V, s, key, (u64 *)nullptr, (int32_t *)nullptr, (u64 *)nullptr);
-  GR_HIP(c, hipcub::DeviceRadixSort::SortKeys(base + o_tmp, cub, key, key_s, (int)V, 0, 64, st));
-  hipLaunchKernelGGL(k_decim_heads, grid, dim3(256), 0, st, (const u64 *)key_s, V, (int32_t *)nullptr, (u64 *)cells);
+  hipLaunchKernelGGL(k_decim_keys, grid, dim3(256), 0, st, verts_q, V, s, key(), (u64 *)nullptr, (int32_t *)nullptr, (u64 *)nullptr);
+  GR_TRY(sort.run(key(), key_s(), st));
+  hipLaunchKernelGGL(k_decim_heads, grid, dim3(256), 0, st, (const u64 *)key_s(), V, (int32_t *)nullptr, (u64 *)cells);
   GR_HIP(c, hipGetLastError());
   return GR_OK;
 }
@@ -195,77 +192,52 @@ int gr_cluster_decimate(gr_ctx *c, const int64_t *verts_q, int64_t V, const int3
   if (V == 0 && F == 0) return GR_OK;
   const int vbits = std::max(bit_length(V - 1), 1), dbits = d2_bits(s);
 
-  size_t cub = 0;
-  if (V > 0) {
-    GR_CUB_MAX(c, cub, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (u64 *)nullptr, (u64 *)nullptr, (int32_t *)nullptr,
-                                                          (int32_t *)nullptr, (int)V, 0, 64, st));
-    GR_CUB_MAX(c, cub, hipcub::DeviceScan::InclusiveScan(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, hipcub::Max(), (int)V, st));
-    GR_CUB_MAX(c, cub, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)V, st));
-  }
-  if (F > 0) {
-    GR_CUB_MAX(c, cub, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr,
-                                                          (int32_t *)nullptr, (int)F, 0, vbits, st));
-    GR_CUB_MAX(c, cub, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (u64 *)nullptr, (u64 *)nullptr, (int32_t *)nullptr,
-                                                          (int32_t *)nullptr, (int)F, 0, 2 * vbits + 1, st));
-    GR_CUB_MAX(c, cub, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)F, st));
-  }
   // scratch: vused [V] | vpos [V] | then the vertex phase: key, d2, alt [V] u64 | idx, idx_a, hp, hpm [V]
   //                                 or the face phase: rf [3 F] | major, major_a, major_s [F] u64 | minor, minor_s [F] | fidx, fidx_a,
   //                                                    fidx_s, fflag, fpos [F]               | hipcub's temporaries behind both
-  Carve cv;
-  const size_t o_vused = cv.array<int32_t>(V), o_vpos = cv.array<int32_t>(V), phase = cv.mark();
-  const size_t v_key = cv.array<u64>(V), v_d2 = cv.array<u64>(V), v_alt = cv.array<u64>(V);
-  const size_t v_idx = cv.array<int32_t>(V), v_idx_a = cv.array<int32_t>(V), v_hp = cv.array<int32_t>(V), v_hpm = cv.array<int32_t>(V);
-  cv.rewind(phase);
-  const size_t f_rf = cv.array<int32_t>(3 * F), f_major = cv.array<u64>(F), f_major_a = cv.array<u64>(F), f_major_s = cv.array<u64>(F);
-  const size_t f_minor = cv.array<uint32_t>(F), f_minor_s = cv.array<uint32_t>(F);
-  const size_t f_fidx = cv.array<int32_t>(F), f_fidx_a = cv.array<int32_t>(F), f_fidx_s = cv.array<int32_t>(F);
-  const size_t f_fflag = cv.array<int32_t>(F), f_fpos = cv.array<int32_t>(F);
-  cv.rewind(cv.total());   // behind both phases
-  const size_t o_tmp = cv.bytes(cub);
-  rc = stage_acquire(c, c->stage, cv.total(), st, "cluster-decimate");
+  Plan p;
+  const FlagScan vs(c, p, V);
+  const size_t phase = p.mark();
+  const auto key = p.array<u64>(V), d2 = p.array<u64>(V), alt = p.array<u64>(V);
+  const auto idx = p.array<int32_t>(V), idx_a = p.array<int32_t>(V), hp = p.array<int32_t>(V), hpm = p.array<int32_t>(V);
+  const SortPairs<u64, int32_t> sort_d2(c, p, V, dbits), sort_key(c, p, V, 64);
+  const InclusiveMax<int32_t> head_max(c, p, V);
+  p.rewind(phase);
+  const auto rf = p.array<int32_t>(3 * F);
+  const auto major = p.array<u64>(F), major_a = p.array<u64>(F), major_s = p.array<u64>(F);
+  const auto minor = p.array<uint32_t>(F), minor_s = p.array<uint32_t>(F);
+  const auto fidx = p.array<int32_t>(F), fidx_a = p.array<int32_t>(F), fidx_s = p.array<int32_t>(F);
+  const SortPairs<uint32_t, int32_t> sort_minor(c, p, F, vbits);
+  const SortPairs<u64, int32_t> sort_major(c, p, F, 2 * vbits + 1);
+  const FlagScan fs(c, p, F);
+  rc = stage_acquire(c, c->stage, p.finish(), st, "cluster-decimate");
   if (rc != GR_OK) return rc;
-  uint8_t *base = c->stage.ptr;
-  void *tmp = base + o_tmp;
-  int32_t *vused = Carve::at<int32_t>(base, o_vused), *vpos = Carve::at<int32_t>(base, o_vpos);
+  p.base = c->stage.ptr;
 
   if (V > 0) {   // D2, D3
-    u64 *key = Carve::at<u64>(base, v_key), *d2 = Carve::at<u64>(base, v_d2), *alt = Carve::at<u64>(base, v_alt);
-    int32_t *idx = Carve::at<int32_t>(base, v_idx), *idx_a = Carve::at<int32_t>(base, v_idx_a);
-    int32_t *hp = Carve::at<int32_t>(base, v_hp), *hpm = Carve::at<int32_t>(base, v_hpm);
     const dim3 grid((unsigned)ceil_div(V, 256));
-    hipLaunchKernelGGL(k_decim_keys, grid, dim3(256), 0, st, verts_q, V, s, key, d2, idx, stw + GR_DECIM_STAT_OUTSIDE);
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub, d2, alt, idx, idx_a, (int)V, 0, dbits, st));   // by d2 (ties: by index)
-    hipLaunchKernelGGL(k_decim_gather, grid, dim3(256), 0, st, (const u64 *)key, (const int32_t *)idx_a, V, d2);
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub, d2, alt, idx_a, idx, (int)V, 0, 64, st));      // then by cell, stably
-    hipLaunchKernelGGL(k_decim_heads, grid, dim3(256), 0, st, (const u64 *)alt, V, hp, stw + GR_DECIM_STAT_CELLS);
-    GR_HIP(c, hipcub::DeviceScan::InclusiveScan(tmp, cub, hp, hpm, hipcub::Max(), (int)V, st));
-    hipLaunchKernelGGL(k_decim_scatter_rep, grid, dim3(256), 0, st, (const u64 *)alt, (const int32_t *)idx, (const int32_t *)hpm, V, rep);
+    hipLaunchKernelGGL(k_decim_keys, grid, dim3(256), 0, st, verts_q, V, s, key(), d2(), idx(), stw + GR_DECIM_STAT_OUTSIDE);
+    GR_TRY(sort_d2.run(d2(), alt(), idx(), idx_a(), st));     // by d2 (ties: by index)
+    hipLaunchKernelGGL(k_decim_gather, grid, dim3(256), 0, st, (const u64 *)key(), (const int32_t *)idx_a(), V, d2());
+    GR_TRY(sort_key.run(d2(), alt(), idx_a(), idx(), st));    // then by cell, stably
+    hipLaunchKernelGGL(k_decim_heads, grid, dim3(256), 0, st, (const u64 *)alt(), V, hp(), stw + GR_DECIM_STAT_CELLS);
+    GR_TRY(head_max.run(hp(), hpm(), st));
+    hipLaunchKernelGGL(k_decim_scatter_rep, grid, dim3(256), 0, st, (const u64 *)alt(), (const int32_t *)idx(), (const int32_t *)hpm(), V, rep);
     GR_HIP(c, hipGetLastError());
   }
   if (F == 0) return GR_OK;   // no face: nothing is kept (D8)
 
-  int32_t *rf = Carve::at<int32_t>(base, f_rf);
-  u64 *major = Carve::at<u64>(base, f_major), *major_a = Carve::at<u64>(base, f_major_a), *major_s = Carve::at<u64>(base, f_major_s);
-  uint32_t *minor = Carve::at<uint32_t>(base, f_minor), *minor_s = Carve::at<uint32_t>(base, f_minor_s);
-  int32_t *fidx = Carve::at<int32_t>(base, f_fidx), *fidx_a = Carve::at<int32_t>(base, f_fidx_a), *fidx_s = Carve::at<int32_t>(base, f_fidx_s);
-  int32_t *fflag = Carve::at<int32_t>(base, f_fflag), *fpos = Carve::at<int32_t>(base, f_fpos);
   const dim3 gf((unsigned)ceil_div(F, 256));
-  if (V > 0) GR_HIP(c, hipMemsetAsync(vused, 0, sizeof(int32_t) * (size_t)V, st));
-  GR_HIP(c, hipMemsetAsync(fflag, 0, sizeof(int32_t) * (size_t)F, st));
-  hipLaunchKernelGGL(k_decim_faces, gf, dim3(256), 0, st, faces, F, V, (const int32_t *)rep, vbits, rf, major, minor, fidx, stw);   // D5
-  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub, minor, minor_s, fidx, fidx_a, (int)F, 0, vbits, st));             // by hi
-  hipLaunchKernelGGL(k_decim_gather, gf, dim3(256), 0, st, (const u64 *)major, (const int32_t *)fidx_a, F, major_a);
-  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub, major_a, major_s, fidx_a, fidx_s, (int)F, 0, 2 * vbits + 1, st));  // then by (lo, mid), stably
-  hipLaunchKernelGGL(k_decim_face_flags, gf, dim3(256), 0, st, (const u64 *)major_s, (const int32_t *)fidx_s, (const uint32_t *)minor,
-                     (const int32_t *)rf, F, vbits, fflag, vused, stw);                                                     // D6
-  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, cub, fflag, fpos, (int)F, st));
-  if (V > 0) GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, cub, vused, vpos, (int)V, st));
-  hipLaunchKernelGGL(k_submesh_write, dim3((unsigned)ceil_div(std::max(F, V), 256)), dim3(256), 0, st, (const int32_t *)rf, F, V,
-                     (const int32_t *)fflag, (const int32_t *)fpos, (const int32_t *)vused, (const int32_t *)vpos, face_ids, point_ids,
-                     new_faces, stw);   // D7, D8; words GR_DECIM_STAT_KEPT_FACES, GR_DECIM_STAT_KEPT_VERTICES
-  GR_HIP(c, hipGetLastError());
-  return GR_OK;
+  GR_TRY(compact_begin(c, vs, st));
+  GR_HIP(c, hipMemsetAsync(fs.flag(), 0, sizeof(int32_t) * (size_t)F, st));
+  hipLaunchKernelGGL(k_decim_faces, gf, dim3(256), 0, st, faces, F, V, (const int32_t *)rep, vbits, rf(), major(), minor(), fidx(), stw);   // D5
+  GR_TRY(sort_minor.run(minor(), minor_s(), fidx(), fidx_a(), st));          // by hi
+  hipLaunchKernelGGL(k_decim_gather, gf, dim3(256), 0, st, (const u64 *)major(), (const int32_t *)fidx_a(), F, major_a());
+  GR_TRY(sort_major.run(major_a(), major_s(), fidx_a(), fidx_s(), st));      // then by (lo, mid), stably
+  hipLaunchKernelGGL(k_decim_face_flags, gf, dim3(256), 0, st, (const u64 *)major_s(), (const int32_t *)fidx_s(), (const uint32_t *)minor(),
+                     (const int32_t *)rf(), F, vbits, fs.flag(), vs.flag(), stw);                                            // D6
+  // D7, D8; words GR_DECIM_STAT_KEPT_FACES, GR_DECIM_STAT_KEPT_VERTICES
+  return compact_write(c, fs, vs, st, (const int32_t *)rf(), face_ids, point_ids, new_faces, stw);
 }
 
 }  // extern "C"

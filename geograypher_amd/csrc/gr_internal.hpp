@@ -1,8 +1,8 @@
 #pragma once
 // geograypher_amd/csrc/gr_internal.hpp -- what the translation units of libgeograster share: constants, the kernel
 // argument blocks, the context, and the host-side helpers (error text, HIP-event spans, the context's device memory: Buf, reserve,
-// release_all from device_buffer.hpp, instantiated here with DeviceMem; the stage arena: Scratch, stage_acquire, GR_CUB_MAX; its
-// layouts come from scratch_layout.hpp).
+// release_all from device_buffer.hpp, instantiated here with DeviceMem; the stage arena: Scratch, stage_acquire; its layouts come
+// from scratch_layout.hpp, the sorts and scans that run in it from cub_steps.hpp).
 //   geograster.hip   context, options, learned binning table, the raster call (launch groups, side stream), status
 //   mesh_upload.hip  gr_mesh_upload: Morton order, de-indexed soup, block bounds            (per upload)
 //   binning.hip      k_cull_blocks, k_setup_cull, k_clip_faces, entry compilation, exact-path scan / fill  (per view)
@@ -30,7 +30,9 @@
 //   decimate.hip     mesh decimation by vertex clustering: cell keys and centre distances (k_decim_keys), cell heads (k_decim_heads),
 //                    representatives (k_decim_scatter_rep), remapped faces (k_decim_faces), first face per triple (k_decim_face_flags)
 //                    + radix sorts and scans; compacts with k_submesh_write; no mesh needed
-//   compact_dev.hpp  k_submesh_write, the write kernel of polygons.hip's sub-mesh and of decimate.hip
+//   cub_steps.hpp    the hipcub calls of the stage calls, each declared once against the call's Plan: SortPairs, SortKeys, ExclusiveSum,
+//                    InclusiveMax, RunLengthEncode (size query on construction, typed pointers on run)
+//   compact_dev.hpp  FlagScan, compact_begin, compact_write, k_submesh_write: the scans and the write kernel of polygons.hip's sub-mesh and of decimate.hip
 //   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip, crs.hip and ortho.hip: orient, ring_span, edge_crossing (THE even-odd rule of
 //                    k_polygon_weights, k_face_polygon_index and k_points_in_region), load_face, stat_add / stat_add_u32 / stat_max / stat_count
 #include <hip/hip_runtime.h>
@@ -386,9 +388,8 @@ inline int stage_acquire(gr_ctx *c, Scratch &sc, size_t bytes, hipStream_t s, co
   return GR_OK;
 }
 
-// A hipcub size query (null temporary storage, its size argument named cub_q): MAXB keeps the largest answer of a scratch block.
-// The real calls pass MAXB: hipcub takes more than it asked for.
-#define GR_CUB_MAX(ctx, MAXB, QUERY) do { size_t cub_q = 0; GR_HIP(ctx, QUERY); if (cub_q > (MAXB)) (MAXB) = cub_q; } while (0)
+// a step that answers GR_OK or has left its message in the context (cub_steps.hpp, compact_dev.hpp)
+#define GR_TRY(step) do { const int rc_ = (step); if (rc_ != GR_OK) return rc_; } while (0)
 
 // (the zeroes go out on the CALL's stream: a plain hipMemset runs on the null stream, which a non-blocking stream -- torch's
 // side streams, one per device thread of a devices=[...] mesh -- does not wait for: the first view's winners could be wiped

@@ -1,7 +1,6 @@
 // geograypher_amd/csrc/mesh_upload.hip -- gr_mesh_upload: once per mesh, the faces are ordered along a Morton curve of their
 // centroids and de-indexed (soup), with a bounding sphere and a chunk list per block of 64 faces.
-#include <hipcub/hipcub.hpp>
-
+#include "cub_steps.hpp"
 #include "gr_internal.hpp"
 
 using namespace grimpl;
@@ -236,20 +235,17 @@ int gr_mesh_upload(gr_ctx *c, const float *verts, const int32_t *faces, int64_t 
   if (rc != GR_OK) return rc;
   note_stream(c, s);
   // Morton codes -> stable radix sort of (code, face) pairs (rocPRIM through hipcub) -> orig[]
-  size_t cub = 0;
-  GR_CUB_MAX(c, cub, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr,
-                                                        (int32_t *)nullptr, (int)F, 0, 32, s));
   // scratch: code_in [F] | code_out [F] | idx_in [F] | rocPRIM
-  Carve cv;
-  const size_t o_code_in = cv.array<uint32_t>(F), o_code_out = cv.array<uint32_t>(F), o_idx_in = cv.array<int32_t>(F), o_tmp = cv.bytes(cub);
-  rc = stage_acquire(c, c->stage, cv.total(), s, "sort");
+  Plan p;
+  const auto code_in = p.array<uint32_t>(F), code_out = p.array<uint32_t>(F);
+  const auto idx_in = p.array<int32_t>(F);
+  const SortPairs<uint32_t, int32_t> sort(c, p, F, 32);
+  rc = stage_acquire(c, c->stage, p.finish(), s, "sort");
   if (rc != GR_OK) return rc;
-  uint8_t *base = c->stage.ptr;
-  uint32_t *code_in = Carve::at<uint32_t>(base, o_code_in), *code_out = Carve::at<uint32_t>(base, o_code_out);
-  int32_t *idx_in = Carve::at<int32_t>(base, o_idx_in);
+  p.base = c->stage.ptr;
   hipLaunchKernelGGL(k_face_codes, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, verts, faces, F, ax0, ax1, lo[ax0], inv0,
-                     lo[ax1], inv1, code_in, idx_in);
-  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, cub, code_in, code_out, idx_in, c->orig.ptr, (int)F, 0, 32, s));
+                     lo[ax1], inv1, code_in(), idx_in());
+  GR_TRY(sort.run(code_in(), code_out(), idx_in(), c->orig.ptr, s));
   hipLaunchKernelGGL(k_build_soup, dim3((unsigned)ceil_div(3 * F, 256)), dim3(256), 0, s, verts, faces, c->orig, F, c->soup);
   hipLaunchKernelGGL(k_block_bounds, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, c->soup, F, c->blk);
   hipLaunchKernelGGL(k_block_vertices, dim3((unsigned)ceil_div(nblk, 4)), dim3(256), 0, s, verts, faces, c->orig, F, c->bvert, c->bidx);

@@ -23,9 +23,8 @@
 //                    triangle's first vertex
 #include <functional>
 
-#include <hipcub/hipcub.hpp>
-
 #include "compact_dev.hpp"
+#include "cub_steps.hpp"
 #include "geom_dev.hpp"
 #include "gr_internal.hpp"
 
@@ -854,10 +853,11 @@ int gr_points_in_region(gr_ctx *c, const int64_t *points_q, int64_t N, const int
   }
   // scratch: joint box [4] i64
   Carve cv;
-  const size_t o_joint = cv.array<int64_t>(4);
+  const auto o_joint = cv.array<int64_t>(4);
   rc = stage_acquire(c, c->stage, cv.total(), s, "region");
   if (rc != GR_OK) return rc;
-  int64_t *joint = Carve::at<int64_t>(c->stage.ptr, o_joint);
+  cv.base = c->stage.ptr;
+  int64_t *joint = o_joint();
   hipLaunchKernelGGL(k_region_joint_box, dim3(1), dim3(256), 0, s, polygon_boxes, (int)P, joint);
   RegionArgs a;
   a.N = N; a.n_rv = n_ring_vertices; a.D = D; a.R = (int)R; a.P = (int)P;
@@ -878,28 +878,16 @@ int gr_submesh_extract(gr_ctx *c, const uint8_t *mask, int64_t V, const int32_t 
   GR_HIP(c, hipSetDevice(c->device));
   GR_HIP(c, hipMemsetAsync(counts, 0, sizeof(uint64_t) * 3, s));
   if (F == 0) return GR_OK;   // no face: nothing is kept (a vertex no face uses is dropped)
-  size_t cub = 0;
-  GR_CUB_MAX(c, cub, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)F, s));
-  GR_CUB_MAX(c, cub, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)V, s));
   // scratch: fflag [F] | fpos [F] | vused [V] | vpos [V] | the scans' temporaries
-  Carve cv;
-  const size_t o_ff = cv.array<int32_t>(F), o_fp = cv.array<int32_t>(F), o_vu = cv.array<int32_t>(V), o_vp = cv.array<int32_t>(V), o_tmp = cv.bytes(cub);
-  int rc = stage_acquire(c, c->stage, cv.total(), s, "sub-mesh");
+  Plan p;
+  const FlagScan fs(c, p, F), vs(c, p, V);
+  int rc = stage_acquire(c, c->stage, p.finish(), s, "sub-mesh");
   if (rc != GR_OK) return rc;
-  uint8_t *base = c->stage.ptr;
-  int32_t *fflag = Carve::at<int32_t>(base, o_ff), *fpos = Carve::at<int32_t>(base, o_fp);
-  int32_t *vused = Carve::at<int32_t>(base, o_vu), *vpos = Carve::at<int32_t>(base, o_vp);
-  void *tmp = base + o_tmp;
-  GR_HIP(c, hipMemsetAsync(vused, 0, sizeof(int32_t) * (size_t)V, s));
-  hipLaunchKernelGGL(k_submesh_flags, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, mask, V, faces, F, fflag, vused,
+  p.base = c->stage.ptr;
+  GR_TRY(compact_begin(c, vs, s));
+  hipLaunchKernelGGL(k_submesh_flags, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, s, mask, V, faces, F, fs.flag(), vs.flag(),
                      (unsigned long long *)counts);
-  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, cub, fflag, fpos, (int)F, s));
-  if (V > 0) GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, cub, vused, vpos, (int)V, s));
-  hipLaunchKernelGGL(k_submesh_write, dim3((unsigned)ceil_div(std::max(F, V), 256)), dim3(256), 0, s, faces, F, V,
-                     (const int32_t *)fflag, (const int32_t *)fpos, (const int32_t *)vused, (const int32_t *)vpos, face_ids, point_ids,
-                     new_faces, (unsigned long long *)counts);
-  GR_HIP(c, hipGetLastError());
-  return GR_OK;
+  return compact_write(c, fs, vs, s, faces, face_ids, point_ids, new_faces, (unsigned long long *)counts);
 }
 
 int gr_class_outlines(gr_ctx *c, const int64_t *verts_q, int64_t V, const int32_t *faces, int64_t F, const int32_t *face_class,
@@ -962,60 +950,48 @@ static int outline_trace(gr_ctx *c, const char *name, const int64_t *verts_q, in
   unsigned long long *st = out.stats;
   const int vbits = std::max(bit_length(V - 1), 1), cbits = std::max(bit_length(n_classes), 1);
 
-  size_t cub_a = 0;
-  if (V > 0) {
-    GR_CUB_MAX(c, cub_a, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (int64_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr,
-                                                            (int32_t *)nullptr, (int)V, 0, 64, s));
-    GR_CUB_MAX(c, cub_a, hipcub::DeviceScan::InclusiveScan(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, hipcub::Max(), (int)V, s));
-  }
-  if (N3 > 0) {
-    GR_CUB_MAX(c, cub_a, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                                            (uint32_t *)nullptr, (uint32_t *)nullptr, (int)N3, 0, 31 + vbits, s));
-    GR_CUB_MAX(c, cub_a, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                                            (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)N3, 0, cbits, s));
-    GR_CUB_MAX(c, cub_a, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)N3, s));
-    GR_CUB_MAX(c, cub_a, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (int32_t *)nullptr, (int32_t *)nullptr, (int)(N3 + 1), s));
-  }
   // scratch A, sized by V and N3: head | canon [V] | the vertex sort or the edge sort and its runs | hipcub's temporaries
-  Carve ca;
-  const size_t o_head = ca.array<unsigned long long>(GR_OUTL_HEAD_WORDS), o_canon = ca.array<int32_t>(V), phase = ca.mark();
+  Plan pa;
+  const auto o_head = pa.array<unsigned long long>(GR_OUTL_HEAD_WORDS);
+  const auto o_canon = pa.array<int32_t>(V);
+  const size_t phase = pa.mark();
   // vertex phase: key [V] i64 | key_s [V] i64 | idx [V] | idx_s [V] | hp [V] | hp_max [V]
-  const size_t v_key = ca.array<int64_t>(V), v_key_s = ca.array<int64_t>(V), v_idx = ca.array<int32_t>(V), v_idx_s = ca.array<int32_t>(V);
-  const size_t v_hp = ca.array<int32_t>(V), v_hpm = ca.array<int32_t>(V);
-  ca.rewind(phase);
+  const auto key = pa.array<int64_t>(V), key_s = pa.array<int64_t>(V);
+  const auto idx = pa.array<int32_t>(V), idx_s = pa.array<int32_t>(V), hp = pa.array<int32_t>(V), hpm = pa.array<int32_t>(V);
+  const SortPairs<int64_t, int32_t> sort_vertex(c, pa, V, 64);   // both passes: by y, then by x
+  const InclusiveMax<int32_t> head_max(c, pa, V);
+  pa.rewind(phase);
   // edge phase: pair [N3] u64 | pair_s [N3] u64 | cl [N3] | cl_s [N3] | flag [N3] | ex [N3] | ustart, surv, soff [N3 + 1]
-  const size_t e_pair = ca.array<unsigned long long>(N3), e_pair_s = ca.array<unsigned long long>(N3);
-  const size_t e_cl = ca.array<uint32_t>(N3), e_cl_s = ca.array<uint32_t>(N3), e_flag = ca.array<int32_t>(N3), e_ex = ca.array<int32_t>(N3);
-  const size_t e_ustart = ca.array<int32_t>(N3 + 1), e_surv = ca.array<int32_t>(N3 + 1), e_soff = ca.array<int32_t>(N3 + 1);
-  ca.rewind(ca.total());   // behind both phases
-  const size_t o_tmp_a = ca.bytes(cub_a);
-  int rc = stage_acquire(c, c->stage, ca.total(), s, "class-outline");
+  const auto e_pair = pa.array<unsigned long long>(N3), e_pair_s = pa.array<unsigned long long>(N3);
+  const auto e_cl = pa.array<uint32_t>(N3), e_cl_s = pa.array<uint32_t>(N3);
+  const auto e_flag = pa.array<int32_t>(N3), e_ex = pa.array<int32_t>(N3);
+  const auto e_ustart = pa.array<int32_t>(N3 + 1), e_surv = pa.array<int32_t>(N3 + 1), e_soff = pa.array<int32_t>(N3 + 1);
+  const SortPairs<unsigned long long, uint32_t> sort_pair(c, pa, N3, 31 + vbits);
+  const SortPairs<uint32_t, unsigned long long> sort_class(c, pa, N3, cbits);
+  const ExclusiveSum<int32_t> scan_flag(c, pa, N3), scan_surv(c, pa, N3 > 0 ? N3 + 1 : 0);   // (no edge: no scan)
+  int rc = stage_acquire(c, c->stage, pa.finish(), s, "class-outline");
   if (rc != GR_OK) return rc;
-  uint8_t *A = c->stage.ptr;
-  unsigned long long *head = Carve::at<unsigned long long>(A, o_head);
-  int32_t *canon_d = Carve::at<int32_t>(A, o_canon);
-  void *tmp = A + o_tmp_a;
+  pa.base = c->stage.ptr;
+  unsigned long long *head = o_head();
+  int32_t *canon_d = o_canon();
   GR_HIP(c, hipMemsetAsync(head, 0, sizeof(unsigned long long) * GR_OUTL_HEAD_WORDS, s));
 
   if (V > 0) {   // X2
-    int64_t *key = Carve::at<int64_t>(A, v_key), *key_s = Carve::at<int64_t>(A, v_key_s);
-    int32_t *idx = Carve::at<int32_t>(A, v_idx), *idx_s = Carve::at<int32_t>(A, v_idx_s), *hp = Carve::at<int32_t>(A, v_hp), *hpm = Carve::at<int32_t>(A, v_hpm);
     const dim3 grid((unsigned)ceil_div(V, 256));
-    hipLaunchKernelGGL(k_outline_vertex_keys, grid, dim3(256), 0, s, verts_q, V, key, idx);
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub_a, key, key_s, idx, idx_s, (int)V, 0, 64, s));           // by y
-    hipLaunchKernelGGL(k_outline_vertex_gather, grid, dim3(256), 0, s, verts_q, V, (const int32_t *)idx_s, key);
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub_a, key, key_s, idx_s, idx, (int)V, 0, 64, s));           // then by x, stably
-    hipLaunchKernelGGL(k_outline_vertex_heads, grid, dim3(256), 0, s, verts_q, V, (const int32_t *)idx, hp);
-    GR_HIP(c, hipcub::DeviceScan::InclusiveScan(tmp, cub_a, hp, hpm, hipcub::Max(), (int)V, s));
-    hipLaunchKernelGGL(k_outline_canon, grid, dim3(256), 0, s, V, (const int32_t *)idx, (const int32_t *)hpm, canon_d);
+    hipLaunchKernelGGL(k_outline_vertex_keys, grid, dim3(256), 0, s, verts_q, V, key(), idx());
+    GR_TRY(sort_vertex.run(key(), key_s(), idx(), idx_s(), s));   // by y
+    hipLaunchKernelGGL(k_outline_vertex_gather, grid, dim3(256), 0, s, verts_q, V, (const int32_t *)idx_s(), key());
+    GR_TRY(sort_vertex.run(key(), key_s(), idx_s(), idx(), s));   // then by x, stably
+    hipLaunchKernelGGL(k_outline_vertex_heads, grid, dim3(256), 0, s, verts_q, V, (const int32_t *)idx(), hp());
+    GR_TRY(head_max.run(hp(), hpm(), s));
+    hipLaunchKernelGGL(k_outline_canon, grid, dim3(256), 0, s, V, (const int32_t *)idx(), (const int32_t *)hpm(), canon_d);
     GR_HIP(c, hipGetLastError());
   }
 
   int64_t E = 0, R = 0, runs = 0;
-  unsigned long long *pair = Carve::at<unsigned long long>(A, e_pair), *pair_s = Carve::at<unsigned long long>(A, e_pair_s);
-  uint32_t *cl = Carve::at<uint32_t>(A, e_cl), *cl_s = Carve::at<uint32_t>(A, e_cl_s);
-  int32_t *flag = Carve::at<int32_t>(A, e_flag), *ex = Carve::at<int32_t>(A, e_ex), *ustart = Carve::at<int32_t>(A, e_ustart);
-  int32_t *surv = Carve::at<int32_t>(A, e_surv), *soff = Carve::at<int32_t>(A, e_soff);
+  unsigned long long *pair = e_pair(), *pair_s = e_pair_s();
+  uint32_t *cl = e_cl(), *cl_s = e_cl_s();
+  int32_t *flag = e_flag(), *ex = e_ex(), *ustart = e_ustart(), *surv = e_surv(), *soff = e_soff();
   if (member_rows && N3 > 0) {   // Y2: no word of a gap is uninitialised
     GR_HIP(c, hipMemsetAsync(pair, 0, sizeof(unsigned long long) * (size_t)N3, s));
     GR_HIP(c, hipMemsetAsync(cl, 0xFF, sizeof(uint32_t) * (size_t)N3, s));
@@ -1026,18 +1002,18 @@ static int outline_trace(gr_ctx *c, const char *name, const int64_t *verts_q, in
   }
   if (N3 > 0) {   // X4
     const dim3 ge((unsigned)ceil_div(N3, 256));
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub_a, pair, pair_s, cl, cl_s, (int)N3, 0, 31 + vbits, s));   // by (from, to)
-    GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, cub_a, cl_s, cl, pair_s, pair, (int)N3, 0, cbits, s));        // then by class, stably
+    GR_TRY(sort_pair.run(pair, pair_s, cl, cl_s, s));    // by (from, to)
+    GR_TRY(sort_class.run(cl_s, cl, pair_s, pair, s));   // then by class, stably
     hipLaunchKernelGGL(k_outline_run_heads, ge, dim3(256), 0, s, (const unsigned long long *)pair, (const uint32_t *)cl, N3,
                        n_classes, flag);
-    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, cub_a, flag, ex, (int)N3, s));
+    GR_TRY(scan_flag.run(flag, ex, s));
     GR_HIP(c, hipMemsetAsync(ustart, 0, sizeof(int32_t) * (size_t)(N3 + 1), s));
     GR_HIP(c, hipMemsetAsync(surv, 0, sizeof(int32_t) * (size_t)(N3 + 1), s));
     hipLaunchKernelGGL(k_outline_run_starts, ge, dim3(256), 0, s, (const uint32_t *)cl, N3, n_classes, (const int32_t *)flag,
                        (const int32_t *)ex, ustart, head);
     hipLaunchKernelGGL(k_outline_cancel, ge, dim3(256), 0, s, (const unsigned long long *)pair, (const uint32_t *)cl,
                        (const int32_t *)ex, (const int32_t *)ustart, (const unsigned long long *)head, surv, st);
-    GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, cub_a, surv, soff, (int)(N3 + 1), s));
+    GR_TRY(scan_surv.run(surv, soff, s));
     GR_HIP(c, hipGetLastError());
   }
   if (member_rows || N3 > 0) {   // the first synchronisation
@@ -1065,30 +1041,27 @@ static int outline_trace(gr_ctx *c, const char *name, const int64_t *verts_q, in
     return GR_OK;
   }
 
-  size_t cub_b = 0;
-  GR_CUB_MAX(c, cub_b, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                                          (int32_t *)nullptr, (int32_t *)nullptr, (int)E, 0, 31 + cbits, s));
-  GR_CUB_MAX(c, cub_b, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_q, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)(E + 1), s));
   // scratch B, sized by E: efrom | ecls | succ | two sets of (nxt, mn, off) | kin, kin_s [E + 1] u64 | hipcub's temporaries
-  Carve cb;
-  const size_t b_from = cb.array<int32_t>(E), b_cls = cb.array<int32_t>(E), b_succ = cb.array<int32_t>(E);
-  size_t b_set[2][3];
-  for (int k = 0; k < 6; ++k) b_set[k / 3][k % 3] = cb.array<int32_t>(E);
-  const size_t b_kin = cb.array<unsigned long long>(E + 1), b_kin_s = cb.array<unsigned long long>(E + 1), b_tmp = cb.bytes(cub_b);
-  rc = stage_acquire(c, c->stage_b, cb.total(), s, "class-outline ring");
+  Plan pb;
+  const auto b_from = pb.array<int32_t>(E), b_cls = pb.array<int32_t>(E), b_succ = pb.array<int32_t>(E);
+  Slot<int32_t> b_set[2][3];
+  for (int k = 0; k < 6; ++k) b_set[k / 3][k % 3] = pb.array<int32_t>(E);
+  const auto b_kin = pb.array<unsigned long long>(E + 1), b_kin_s = pb.array<unsigned long long>(E + 1);
+  const SortPairs<unsigned long long, int32_t> sort_edge(c, pb, E, 31 + cbits);
+  const ExclusiveSum<unsigned long long> scan_words(c, pb, E + 1);
+  rc = stage_acquire(c, c->stage_b, pb.finish(), s, "class-outline ring");
   if (rc != GR_OK) return rc;
-  uint8_t *B = c->stage_b.ptr;
-  int32_t *efrom = Carve::at<int32_t>(B, b_from), *ecls = Carve::at<int32_t>(B, b_cls), *succ = Carve::at<int32_t>(B, b_succ);
+  pb.base = c->stage_b.ptr;
+  int32_t *efrom = b_from(), *ecls = b_cls(), *succ = b_succ();
   int32_t *set[2][3];
-  for (int k = 0; k < 6; ++k) set[k / 3][k % 3] = Carve::at<int32_t>(B, b_set[k / 3][k % 3]);
-  unsigned long long *kin = Carve::at<unsigned long long>(B, b_kin), *kin_s = Carve::at<unsigned long long>(B, b_kin_s);
+  for (int k = 0; k < 6; ++k) set[k / 3][k % 3] = b_set[k / 3][k % 3]();
+  unsigned long long *kin = b_kin(), *kin_s = b_kin_s();
   int32_t *vin = set[1][0], *vin_s = set[1][1];   // free until the first round writes the second set
-  void *tmp2 = B + b_tmp;
   const dim3 gE((unsigned)ceil_div(E, 256)), gE1((unsigned)ceil_div(E + 1, 256));
   hipLaunchKernelGGL(k_outline_emit_edges, dim3((unsigned)ceil_div(runs, 256)), dim3(256), 0, s, (const unsigned long long *)pair,
                      (const uint32_t *)cl, (const int32_t *)ustart, (const int32_t *)surv, (const int32_t *)soff, runs, efrom, ecls,
                      kin, vin);
-  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp2, cub_b, kin, kin_s, vin, vin_s, (int)E, 0, 31 + cbits, s));   // X5
+  GR_TRY(sort_edge.run(kin, kin_s, vin, vin_s, s));   // X5
   hipLaunchKernelGGL(k_outline_successor, gE, dim3(256), 0, s, (const int32_t *)vin_s, E, succ, set[0][1], set[0][2]);
   // X6: round r reads the successor table first, then its own doubled pointers
   int cur = 0;
@@ -1101,7 +1074,7 @@ static int outline_trace(gr_ctx *c, const char *name, const int64_t *verts_q, in
   const int32_t *mn = set[cur][1], *off = set[cur][2];
   unsigned long long *w = kin, *ws = kin_s;
   hipLaunchKernelGGL(k_outline_ring_words, gE1, dim3(256), 0, s, (const int32_t *)succ, mn, off, E, w);
-  GR_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp2, cub_b, w, ws, (int)(E + 1), s));
+  GR_TRY(scan_words.run(w, ws, s));
   GR_HIP(c, hipGetLastError());
   unsigned long long total = 0;
   GR_HIP(c, hipMemcpyAsync(&total, ws + E, sizeof(total), hipMemcpyDeviceToHost, s));

@@ -1,7 +1,6 @@
 // geograypher_amd/csrc/project.hip -- everything behind the rasterizer: last-writer-wins winners from id images, per-face
 // votes / nansums, per-view textures, texture gathers, sparse (face, class) pairs (from label images, rectangles, polygon rings), finalize, argmax -- kernels and entry points.
-#include <hipcub/hipcub.hpp>
-
+#include "cub_steps.hpp"
 #include "gr_internal.hpp"
 #include "dev_common.hpp"
 
@@ -786,19 +785,17 @@ int gr_count_pairs(gr_ctx *c, uint64_t *keys, int64_t n, uint64_t *unique_keys, 
   hipStream_t s = (hipStream_t)stream;
   GR_HIP(c, hipSetDevice(c->device));
   // radix sort (keys -> sorted copy in context scratch) + run-length encode, both rocPRIM through hipcub
-  size_t cub = 0;
   unsigned long long *kin = (unsigned long long *)keys, *uo = (unsigned long long *)unique_keys;
-  GR_CUB_MAX(c, cub, hipcub::DeviceRadixSort::SortKeys(nullptr, cub_q, kin, kin, (int)n, 0, 64, s));
-  GR_CUB_MAX(c, cub, hipcub::DeviceRunLengthEncode::Encode(nullptr, cub_q, kin, uo, pair_counts, (int *)nullptr, (int)n, s));
   // scratch: sorted [n] | rocPRIM
-  Carve cv;
-  const size_t o_sorted = cv.array<unsigned long long>(n), o_tmp = cv.bytes(cub);
-  int rc = stage_acquire(c, c->stage, cv.total(), s, "sort");
+  Plan p;
+  const auto sorted = p.array<unsigned long long>(n);
+  const SortKeys<unsigned long long> sort(c, p, n, 64);
+  const RunLengthEncode<unsigned long long, uint32_t> encode(c, p, n);
+  int rc = stage_acquire(c, c->stage, p.finish(), s, "sort");
   if (rc != GR_OK) return rc;
-  unsigned long long *sorted = Carve::at<unsigned long long>(c->stage.ptr, o_sorted);
-  void *tmp = c->stage.ptr + o_tmp;
-  GR_HIP(c, hipcub::DeviceRadixSort::SortKeys(tmp, cub, kin, sorted, (int)n, 0, 64, s));
-  GR_HIP(c, hipcub::DeviceRunLengthEncode::Encode(tmp, cub, sorted, uo, pair_counts, (int *)c->flag, (int)n, s));
+  p.base = c->stage.ptr;
+  GR_TRY(sort.run(kin, sorted(), s));
+  GR_TRY(encode.run(sorted(), uo, pair_counts, (int *)c->flag, s));
   int runs = 0;
   GR_HIP(c, hipMemcpyAsync(&runs, c->flag, sizeof(int), hipMemcpyDeviceToHost, s));
   GR_HIP(c, hipStreamSynchronize(s));

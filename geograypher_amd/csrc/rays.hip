@@ -3,8 +3,7 @@
 // boundary mesh.  Needs no uploaded mesh.  Everything is float64 and, like the rest of the library, compiled without
 // contraction: the exact `denom == 0` test for parallel rays relies on a1 * b2 - a2 * b1 of two identical directions being
 // exactly zero, which a fused multiply-add would break.
-#include <hipcub/hipcub.hpp>
-
+#include "cub_steps.hpp"
 #include "gr_internal.hpp"
 #include "dev_common.hpp"
 
@@ -266,27 +265,23 @@ int gr_ray_pairs(gr_ctx *c, const double *starts, const double *ends, const int3
   GR_HIP(c, hipSetDevice(c->device));
   const int64_t T = ceil_div(n, GR_RAY_TILE), tiles = tri_off(T, T);
   const int64_t cap = fill ? edge_cap : 0;
-  size_t cub = 0;
-  int end_bit = 64;
-  if (fill) {
-    int nbits = 1;
-    while (((int64_t)1 << nbits) < n) ++nbits;
-    end_bit = 32 + nbits;   // i < n sits above bit 32
-    GR_CUB_MAX(c, cub, hipcub::DeviceRadixSort::SortPairs(nullptr, cub_q, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                                          (double *)nullptr, (double *)nullptr, (int)cap, 0, end_bit, s));
-  }
+  int nbits = 1;
+  while (((int64_t)1 << nbits) < n) ++nbits;
   // scratch: edge counter | rec [n] | keys [cap] | dist [cap] | sorted [cap] | rocPRIM
-  Carve cv;
-  const size_t o_counter = cv.array<unsigned long long>(1), o_rec = cv.array<RayRec>(n);
-  const size_t o_keys = cv.array<unsigned long long>(cap), o_dist = cv.array<double>(cap), o_sorted = cv.array<unsigned long long>(cap), o_tmp = cv.bytes(cub);
-  int rc = stage_acquire(c, c->stage, cv.total(), s, "ray-pair");
+  Plan p;
+  const auto o_counter = p.array<unsigned long long>(1);
+  const auto o_rec = p.array<RayRec>(n);
+  const auto o_keys = p.array<unsigned long long>(cap);
+  const auto o_dist = p.array<double>(cap);
+  const auto o_sorted = p.array<unsigned long long>(cap);
+  const SortPairs<unsigned long long, double> sort(c, p, cap, 32 + nbits);   // i < n sits above bit 32; cap is 0 without edge buffers
+  int rc = stage_acquire(c, c->stage, p.finish(), s, "ray-pair");
   if (rc != GR_OK) return rc;
-  uint8_t *base = c->stage.ptr;
-  if (c->opt_dbg & GR_DBG_POISON_RAYS) GR_HIP(c, hipMemsetAsync(base, 0xFF, (size_t)c->stage.have, s));   // test hook: nothing survives between calls
-  unsigned long long *counter = Carve::at<unsigned long long>(base, o_counter);
-  RayRec *rec = Carve::at<RayRec>(base, o_rec);
-  unsigned long long *keys = Carve::at<unsigned long long>(base, o_keys), *sorted = Carve::at<unsigned long long>(base, o_sorted);
-  double *dist = Carve::at<double>(base, o_dist);
+  p.base = c->stage.ptr;
+  if (c->opt_dbg & GR_DBG_POISON_RAYS) GR_HIP(c, hipMemsetAsync(p.base, 0xFF, (size_t)c->stage.have, s));   // test hook: nothing survives between calls
+  unsigned long long *counter = o_counter(), *keys = o_keys(), *sorted = o_sorted();
+  RayRec *rec = o_rec();
+  double *dist = o_dist();
   GR_HIP(c, hipMemsetAsync(counter, 0, sizeof(unsigned long long), s));
   if (tiles > 0) {
     hipLaunchKernelGGL(k_ray_prep, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, starts, ends, ray_ids, n, rec);
@@ -308,7 +303,7 @@ int gr_ray_pairs(gr_ctx *c, const double *starts, const double *ends, const int3
   if ((int64_t)total > cap)
     return fail(c, GR_EOVERFLOW, "%llu ray pairs within the threshold, the edge buffers hold %lld: call again with that capacity",
                 total, (long long)cap);
-  GR_HIP(c, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, cub, keys, sorted, dist, edge_d, (int)total, 0, end_bit, s));
+  GR_TRY(sort.run(keys, sorted, dist, edge_d, s, (int64_t)total));   // total <= cap of the declared elements
   hipLaunchKernelGGL(k_ray_split_keys, dim3((unsigned)ceil_div((int64_t)total, 256)), dim3(256), 0, s, sorted, (int64_t)total,
                      edge_i, edge_j);
   GR_HIP(c, hipGetLastError());

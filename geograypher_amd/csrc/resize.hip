@@ -157,10 +157,11 @@ int gr_resize_image_f64(gr_ctx *c, const void *src, int dtype, int h_in, int w_i
                 std::max(rr, rc), GR_RESIZE_MAX_RADIUS);
   // scratch: rows [2 h_out][w_in * C] f64
   Carve cv;
-  const size_t o_rows = cv.array<double>((int64_t)2 * h_out * E);
+  const auto o_rows = cv.array<double>((int64_t)2 * h_out * E);
   int rc_ = stage_acquire(c, c->stage, cv.total(), s, "resize rows");
   if (rc_) return rc_;
-  double *rows = Carve::at<double>(c->stage.ptr, o_rows);
+  cv.base = c->stage.ptr;
+  double *rows = o_rows();
   {
     const dim3 g((unsigned)ceil_div(E, 256), (unsigned)(2 * h_out)), b(256);
     const size_t lds = sizeof(double) * (size_t)(rr + 1 + 256);

@@ -328,18 +328,22 @@ int gr_set_cover(gr_ctx *c, const int64_t *face_ptr, const int32_t *face_views, 
   }
   // scratch: ctl | gain [N] | vcount [N] | red [N] | vptr [N + 1] | cursor [N] | m [F] | vfaces [nnz] | req [F]
   Carve cv;
-  const size_t o_ctl = cv.array<uint32_t>(GR_SC_CTL_WORDS), o_gain = cv.array<int32_t>(N), o_vcount = cv.array<uint32_t>(N);
-  const size_t o_red = cv.array<int32_t>(N), o_vptr = cv.array<int64_t>((int64_t)N + 1), o_cursor = cv.array<u64>(N);
-  const size_t o_m = cv.array<int32_t>(F), o_vfaces = cv.array<int32_t>(nnz), o_req = cv.array<uint8_t>(F);
+  const auto o_ctl = cv.array<uint32_t>(GR_SC_CTL_WORDS);
+  const auto o_gain = cv.array<int32_t>(N);
+  const auto o_vcount = cv.array<uint32_t>(N);
+  const auto o_red = cv.array<int32_t>(N);
+  const auto o_vptr = cv.array<int64_t>((int64_t)N + 1);
+  const auto o_cursor = cv.array<u64>(N);
+  const auto o_m = cv.array<int32_t>(F), o_vfaces = cv.array<int32_t>(nnz);
+  const auto o_req = cv.array<uint8_t>(F);
   int rc = stage_acquire(c, c->stage, cv.total(), s, "set-cover");
   if (rc != GR_OK) return rc;
-  uint8_t *base = c->stage.ptr;
-  uint32_t *ctl = Carve::at<uint32_t>(base, o_ctl), *vcount = Carve::at<uint32_t>(base, o_vcount);
-  int32_t *gain = Carve::at<int32_t>(base, o_gain), *red = Carve::at<int32_t>(base, o_red), *m = Carve::at<int32_t>(base, o_m);
-  int64_t *vptr = Carve::at<int64_t>(base, o_vptr);
-  u64 *cursor = Carve::at<u64>(base, o_cursor);
-  int32_t *vfaces = Carve::at<int32_t>(base, o_vfaces);
-  uint8_t *req = base + o_req;
+  cv.base = c->stage.ptr;
+  uint32_t *ctl = o_ctl(), *vcount = o_vcount();
+  int32_t *gain = o_gain(), *red = o_red(), *m = o_m(), *vfaces = o_vfaces();
+  int64_t *vptr = o_vptr();
+  u64 *cursor = o_cursor();
+  uint8_t *req = o_req();
 
   const double threshold = min_observations > 1.0 ? min_observations : 1.0;   // M2
   const unsigned setup_grid = (unsigned)std::min<int64_t>(ceil_div(F, GR_SC_BLOCK), GR_SC_MAX_GRID);

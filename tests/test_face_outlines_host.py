@@ -320,7 +320,9 @@ def test_header_binding_and_source_name_the_new_call():
     assert "stage_acquire(c, c->stage, " in call and "stage_acquire(c, c->stage_b, " in call
     assert (_hip.GR_OUTL_STAT_NO_CLASS, _hip.GR_OUTL_STAT_ZERO_AREA, _hip.GR_OUTL_STAT_TURNED, _hip.GR_OUTL_STAT_CANCELLED,
             _hip.GR_OUTL_STAT_MULTI, _hip.GR_OUTL_STAT_BAD_FACES, _hip.GR_OUTL_STAT_WORDS, _hip.GR_OUTL_MAX_CLASSES) == (0, 1, 2, 3, 4, 5, 8, 65535)
-    assert "hipcub::DeviceRadixSort::SortPairs" in source and "hipcub::DeviceScan::ExclusiveSum" in source
+    steps = (ROOT / "geograypher_amd" / "csrc" / "cub_steps.hpp").read_text()      # the sorts and scans: steps of cub_steps.hpp
+    assert "SortPairs<int64_t, int32_t> sort_vertex(c, pa, V, 64);" in call and "ExclusiveSum<int32_t> scan_flag(c, pa, N3)" in call
+    assert "hipcub::DeviceRadixSort::SortPairs(" in steps and "hipcub::DeviceScan::ExclusiveSum(" in steps
     outline_start = source.index("gr_class_outlines: the outline rings")
     outline_part = source[outline_start:source.index('extern "C" {', outline_start)]       # every outline kernel and device helper
     assert all(outline_part.count(k + "(") >= 1 for k in kernels) and "k_outline_ring_words(" in outline_part

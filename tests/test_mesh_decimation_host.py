@@ -352,7 +352,9 @@ def test_header_binding_and_source_name_the_new_calls():
     assert "meshes/meshes.py:215-226" in companion and "without a GR_VERSION bump" in companion
     assert (_hip.GR_DECIM_STAT_KEPT_FACES, _hip.GR_DECIM_STAT_KEPT_VERTICES, _hip.GR_DECIM_STAT_BAD_FACES, _hip.GR_DECIM_STAT_CELLS,
             _hip.GR_DECIM_STAT_COLLAPSED, _hip.GR_DECIM_STAT_DUPLICATES, _hip.GR_DECIM_STAT_OUTSIDE, _hip.GR_DECIM_STAT_WORDS) == (0, 1, 2, 3, 4, 5, 6, 8)
-    assert "hipcub::DeviceRadixSort::SortPairs" in source and "hipcub::DeviceScan::ExclusiveSum" in source and "stage_acquire" in source
+    steps = (ROOT / "geograypher_amd" / "csrc" / "cub_steps.hpp").read_text()      # the sorts and scans: steps of cub_steps.hpp
+    assert "SortPairs<u64, int32_t> sort_d2(c, p, V, dbits), sort_key(c, p, V, 64);" in source and "compact_write(" in source and "stage_acquire" in source
+    assert "hipcub::DeviceRadixSort::SortPairs(" in steps and "hipcub::DeviceScan::ExclusiveSum(" in steps
     assert "asm" not in re.sub(r"//[^\n]*", "", source)
     assert any(p.name == "decimate.hip" for p in build.SOURCES) and any(p.name == "compact_dev.hpp" for p in build.HEADERS)
     assert callable(_hip.HipRaster.cluster_count) and callable(_hip.HipRaster.cluster_decimate)

@@ -334,6 +334,9 @@ def test_header_binding_and_source_name_the_new_calls():
         assert all(k in source and k in internal for k in kernels)
     assert "#define GR_VERSION 126" in header and "meshes/meshes.py:646-731" in header and "cameras/cameras.py:1207-1273" in header
     assert (_hip.GR_PIR_STAT_INSIDE, _hip.GR_PIR_STAT_BUFFER_ONLY, _hip.GR_PIR_STAT_WIDE, _hip.GR_PIR_STAT_WORDS) == (0, 1, 2, 4)
-    assert "__umul64hi" in source and "hipcub::DeviceScan::ExclusiveSum" in source
+    csrc = ROOT / "geograypher_amd" / "csrc"      # the scans: a step of cub_steps.hpp, declared and run by the shared compaction
+    assert "__umul64hi" in source and "const FlagScan fs(c, p, F), vs(c, p, V);" in source and "compact_write(" in source
+    assert "ExclusiveSum<int32_t> scan;" in (csrc / "compact_dev.hpp").read_text()
+    assert "hipcub::DeviceScan::ExclusiveSum(" in (csrc / "cub_steps.hpp").read_text()
     assert any(p.name == "polygons.hip" for p in build.SOURCES)
     assert callable(_hip.HipRaster.points_in_region) and callable(_hip.HipRaster.submesh_extract)

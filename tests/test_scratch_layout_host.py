@@ -30,6 +30,18 @@ def test_layout_header_includes_no_hip_and_is_a_build_header():
     assert CSRC / "scratch_layout.hpp" in build.HEADERS
     units = "".join(p.read_text() for p in build.SOURCES) + (CSRC / "gr_internal.hpp").read_text()
     assert units.count("size_t up256(") == 0 and text.count("size_t up256(") == 1 and text.count("int bit_length(") == 1
+    # the sorts and scans that run in a layout are stated in one header: no size-query macro, no hipcub call anywhere else
+    assert CSRC / "cub_steps.hpp" in build.HEADERS
+    steps = code_lines(CSRC / "cub_steps.hpp")
+    assert "hipcub::DeviceRadixSort::SortPairs(" in steps and "hipcub::DeviceScan::ExclusiveSum(" in steps
+    for path in list(build.SOURCES) + [h for h in build.HEADERS if h.name != "cub_steps.hpp"]:
+        code = code_lines(path)
+        assert "GR_CUB_MAX" not in code and "hipcub::" not in code and "<hipcub/" not in code, path.name
+
+
+def code_lines(path):
+    """The file without its // comments."""
+    return "\n".join(line.split("//")[0] for line in path.read_text().splitlines())
 
 
 def test_layout_program_runs_clean_under_asan_and_ubsan(tmp_path):
