@@ -153,6 +153,14 @@ GR_DECIM_STAT_COLLAPSED = 4
 GR_DECIM_STAT_DUPLICATES = 5
 GR_DECIM_STAT_OUTSIDE = 6
 GR_DECIM_STAT_WORDS = 8
+# polygon rows burned into a label raster: stats words of gr_burn_polygons, the workgroup cap of its value pass
+GR_BURN_STAT_TESTED = 0
+GR_BURN_STAT_INSIDE = 1
+GR_BURN_STAT_BURNED = 2
+GR_BURN_STAT_LARGEST_RING = 3
+GR_BURN_STAT_RINGS_IGNORED = 4
+GR_BURN_STAT_WORDS = 8
+GR_BURN_MAX_GROUPS = 8192
 
 
 class StageTimes(ctypes.Structure):
@@ -275,6 +283,11 @@ _DECIMATE_SIGNATURES = {
     "gr_cluster_decimate": [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 DECIMATE_SYMBOLS = tuple(_DECIMATE_SIGNATURES)
+# ... and the call of include/geograster_burn.h (polygon rows burned into a label raster), under the same contract.
+_BURN_SIGNATURES = {
+    "gr_burn_polygons": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+}
+BURN_SYMBOLS = tuple(_BURN_SIGNATURES)
 
 
 def library_path() -> Path:
@@ -297,7 +310,7 @@ def load_library() -> ctypes.CDLL:
     # library's runtime without devices and gr_ctx_create answers GR_ENODEVICE.
     _torch()
     lib = ctypes.CDLL(str(_LIB_PATH))
-    for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES}.items():
+    for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES, **_BURN_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -517,6 +530,25 @@ def check_zonal_tables(H: int, W: int, nodata, ring_vertices, ring_offsets, ring
         raise ValueError(f"{name}: a raster of {H} x {W} cells is outside [1, 2^23) a side")
     if not 1 <= num_classes <= GR_ZONAL_MAX_CLASSES:
         raise ValueError(f"{name}: num_classes={num_classes} outside [1, {GR_ZONAL_MAX_CLASSES}]")
+    R = _check_ring_table(name, ring_vertices, ring_offsets, ring_polygon, n_polygons)
+    it = np.asarray(items, dtype=np.int64)
+    if it.ndim != 2 or it.shape[1] != GR_ZONAL_ITEM_INTS:
+        raise ValueError(f"{name}: work items must be (n, {GR_ZONAL_ITEM_INTS}), got {it.shape}")
+    if it.shape[0]:
+        p, c0, r0, w, h, lo, hi = it.T
+        bad = ((p < 0) | (p >= n_polygons) | (c0 < 0) | (r0 < 0) | (w < 1) | (h < 1) | (w > GR_ZONAL_BLOCK_W) | (h > GR_ZONAL_BLOCK_H)
+               | (c0 + w > W) | (r0 + h > H) | (lo < 0) | (hi < lo) | (hi > R))
+        if np.any(bad):
+            k = int(np.nonzero(bad)[0][0])
+            raise ValueError(f"{name}: work item {k} {tuple(int(v) for v in it[k])} names no polygon row, no block of at most "
+                             f"{GR_ZONAL_BLOCK_W} x {GR_ZONAL_BLOCK_H} cells inside the raster, or no ring range")
+
+
+BURN_WINDOW_LIMIT = 1 << 23   # B1: |offsets| of a burn window stay below it, its far edges at or below it
+
+
+def _check_ring_table(name: str, ring_vertices, ring_offsets, ring_polygon, n_polygons: int) -> int:
+    """Z1: the ring table of gr_zonal_class_counts and gr_burn_polygons is in range -- ValueError naming the call; -> R."""
     if n_polygons < 0 or n_polygons >= 2 ** 31:
         raise ValueError(f"{name}: {n_polygons} polygon rows")
     rv = np.asarray(ring_vertices)
@@ -529,17 +561,77 @@ def check_zonal_tables(H: int, W: int, nodata, ring_vertices, ring_offsets, ring
     _check_offsets(np.asarray(ring_offsets, dtype=np.int64).reshape(-1), R, rv.shape[0], "rings", f"{name}: ring", "ring vertices")
     if R and (rp.min() < 0 or rp.max() >= n_polygons or np.any(np.diff(rp) < 0)):
         raise ValueError(f"{name}: ring_polygon must be non-decreasing inside [0, {n_polygons})")
-    it = np.asarray(items, dtype=np.int64)
-    if it.ndim != 2 or it.shape[1] != GR_ZONAL_ITEM_INTS:
-        raise ValueError(f"{name}: work items must be (n, {GR_ZONAL_ITEM_INTS}), got {it.shape}")
+    return R
+
+
+def check_burn_tables(ring_vertices, ring_offsets, ring_polygon, n_polygons: int, values=None):
+    """B1 / B7: the ring table and the values of a `PolygonBurner` are in range -- ValueError naming gr_burn_polygons; -> R."""
+    name = "gr_burn_polygons"
+    R = _check_ring_table(name, ring_vertices, ring_offsets, ring_polygon, int(n_polygons))
+    if values is not None:
+        v = np.asarray(values)
+        if v.shape != (int(n_polygons),) or v.dtype.kind not in "iu" or (v.size and (v.min() < 0 or v.max() > 255)):
+            raise ValueError(f"{name}: values must be ({int(n_polygons)},) integers in [0, 255], got {v.shape} {v.dtype}")
+    return R
+
+
+def check_burn_window(col_off: int, row_off: int, width: int, height: int, items, n_polygons: int, n_rings: int, fill: int = 255):
+    """B1 / B5 / B7: the window is inside the bounds and every work item inside the window -- ValueError naming gr_burn_polygons."""
+    name, lim = "gr_burn_polygons", BURN_WINDOW_LIMIT
+    if not (width >= 1 and height >= 1 and -lim < col_off < lim and -lim < row_off < lim and col_off + width <= lim and row_off + height <= lim):
+        raise ValueError(f"{name}: a window of {width} x {height} cells at ({col_off}, {row_off}) is empty or leaves (-2^23, 2^23]")
+    if not 0 <= fill <= 255:
+        raise ValueError(f"{name}: fill={fill} outside [0, 255]")
+    it = np.asarray(items)
+    if it.ndim != 2 or it.shape[1] != GR_ZONAL_ITEM_INTS or it.dtype.kind not in "iu":
+        raise ValueError(f"{name}: work items must be (n, {GR_ZONAL_ITEM_INTS}) integers, got {it.shape} {it.dtype}")
     if it.shape[0]:
-        p, c0, r0, w, h, lo, hi = it.T
-        bad = ((p < 0) | (p >= n_polygons) | (c0 < 0) | (r0 < 0) | (w < 1) | (h < 1) | (w > GR_ZONAL_BLOCK_W) | (h > GR_ZONAL_BLOCK_H)
-               | (c0 + w > W) | (r0 + h > H) | (lo < 0) | (hi < lo) | (hi > R))
+        p, c0, r0, w, h, lo, hi = it.astype(np.int64).T
+        bad = ((p < 0) | (p >= n_polygons) | (w < 1) | (h < 1) | (w > GR_ZONAL_BLOCK_W) | (h > GR_ZONAL_BLOCK_H) | (c0 < col_off) | (r0 < row_off)
+               | (c0 + w > col_off + width) | (r0 + h > row_off + height) | (lo < 0) | (hi < lo) | (hi > n_rings))
         if np.any(bad):
             k = int(np.nonzero(bad)[0][0])
             raise ValueError(f"{name}: work item {k} {tuple(int(v) for v in it[k])} names no polygon row, no block of at most "
-                             f"{GR_ZONAL_BLOCK_W} x {GR_ZONAL_BLOCK_H} cells inside the raster, or no ring range")
+                             f"{GR_ZONAL_BLOCK_W} x {GR_ZONAL_BLOCK_H} cells inside the window, or no ring range")
+
+
+class PolygonBurner:
+    """One ring table on the device, burned into any number of windows of its parent grid (gr_burn_polygons).
+    Made by `HipRaster.polygon_burner`, which checks the tables (`check_burn_tables`) and uploads them once."""
+
+    def __init__(self, backend: "HipRaster", ring_vertices, ring_offsets, ring_polygon, n_polygons: int, values=None):
+        torch = _torch()
+        rv_h, off_h, rp_h = (_host_array(x) for x in (ring_vertices, ring_offsets, ring_polygon))
+        val_h = None if values is None else _host_array(values)
+        self.backend = backend
+        self.n_polygons = int(n_polygons)
+        self.n_rings = check_burn_tables(rv_h, off_h, rp_h, self.n_polygons, val_h)
+        self._rv = backend._shaped(ring_vertices, torch.int64, ("N", 2), "ring vertices")
+        self._rp = backend._dev(ring_polygon, torch.int32).reshape(-1)
+        self._off = backend._shaped(ring_offsets, torch.int64, (self.n_rings + 1,), "ring offsets (one more than ring polygons)")
+        self._values = None if values is None else backend._dev(values, torch.uint8).reshape(-1)
+
+    def window(self, col_off: int, row_off: int, width: int, height: int, items, fill: int = 255, want_values: bool = True):
+        """The window (col_off, row_off, width, height) of the parent grid; items (n, GR_ZONAL_ITEM_INTS) int32 of
+        `utils.geometric.burn_work_items` for that window -> (rows (height, width) int32 tensor: the highest row that holds the
+        cell's centre, -1 for none; out (height, width) uint8 tensor = values[rows], `fill` where none, or None without
+        `want_values`; stats (GR_BURN_STAT_WORDS,) int64 tensor).  The items are validated on the host first (`check_burn_window`:
+        ValueError).  Only enqueues."""
+        torch = _torch()
+        hip = self.backend
+        col_off, row_off, width, height, fill = int(col_off), int(row_off), int(width), int(height), int(fill)
+        check_burn_window(col_off, row_off, width, height, _host_array(items), self.n_polygons, self.n_rings, fill)
+        if want_values and self._values is None:
+            raise ValueError("gr_burn_polygons: this burner was made without values; ask for the rows alone (want_values=False)")
+        it_t = hip._shaped(items, torch.int32, ("n", GR_ZONAL_ITEM_INTS), "work items")
+        rows = hip._empty((height, width), torch.int32)
+        out = hip._empty((height, width), torch.uint8) if want_values else None
+        stats = hip._stats(GR_BURN_STAT_WORDS)
+        hip._call("gr_burn_polygons", _ptr(self._rv if self._rv.numel() else None), int(self._rv.shape[0]), self._off.data_ptr(),
+                  _ptr(self._rp if self.n_rings else None), self.n_rings, self.n_polygons,
+                  _ptr(self._values if want_values and self.n_polygons else None), _ptr(it_t if it_t.numel() else None),
+                  int(it_t.shape[0]), col_off, row_off, width, height, fill, rows.data_ptr(), _ptr(out), stats.data_ptr(), hip._stream())
+        return rows, out, stats
 
 
 def polygon_pair_bounds(boxes, poly_offsets, n_faces: int) -> np.ndarray:
@@ -1558,6 +1650,12 @@ class HipRaster:
                    _ptr(it_t if it_t.numel() else None), int(it_t.shape[0]), C, _ptr(counts if P else None), stats.data_ptr(),
                    self._stream())
         return counts, stats
+
+    def polygon_burner(self, ring_vertices, ring_offsets, ring_polygon, n_polygons: int, values=None) -> "PolygonBurner":
+        """A `PolygonBurner` over the ring table in cell units of a parent raster grid (`utils.geospatial.rings_to_cell_units`) and
+        `values` (n_polygons,) integers in [0, 255], or None for a burner of row planes only: the tables are checked
+        (`check_burn_tables`: ValueError naming gr_burn_polygons) and uploaded once; every `.window` call burns one window."""
+        return PolygonBurner(self, ring_vertices, ring_offsets, ring_polygon, n_polygons, values)
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):

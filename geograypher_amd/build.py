@@ -34,7 +34,8 @@ def hipcc_path() -> str:
 
 
 def _newest_header() -> float:
-    public = [INCLUDE / n for n in ("geograster.h", "geograster_outlines.h", "geograster_ortho.h", "geograster_decimate.h")]
+    public = [INCLUDE / n for n in ("geograster.h", "geograster_outlines.h", "geograster_ortho.h", "geograster_decimate.h",
+                                   "geograster_burn.h")]
     return max(p.stat().st_mtime for p in HEADERS + public + [Path(__file__)])
 
 

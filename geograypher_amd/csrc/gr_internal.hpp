@@ -26,7 +26,8 @@
 //   crs.hip          CRS reprojection: points between WGS84 ECEF, geographic and transverse Mercator coordinates (k_reproject_points; constants:
 //                    crs_constants.hpp, written by tools/make_crs_constants.py); no mesh needed
 //   ortho.hip        orthomosaic baseline: tile predictions assembled into a class raster (k_assemble_tiles), class counts of the raster cells
-//                    under polygon rows (k_zonal_class_counts, k_zonal_ring_stats); no mesh needed
+//                    under polygon rows (k_zonal_class_counts, k_zonal_ring_stats), polygon rows burned into a label raster (k_burn_rows,
+//                    k_burn_values; one ring walk with the counts, zonal_parity_walk); no mesh needed
 //   decimate.hip     mesh decimation by vertex clustering: cell keys and centre distances (k_decim_keys), cell heads (k_decim_heads),
 //                    representatives (k_decim_scatter_rep), remapped faces (k_decim_faces), first face per triple (k_decim_face_flags)
 //                    + radix sorts and scans; compacts with k_submesh_write; no mesh needed

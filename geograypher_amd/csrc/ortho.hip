@@ -1,6 +1,7 @@
 // geograypher_amd/csrc/ortho.hip -- the orthomosaic baseline: overlapping tile predictions assembled into one class raster
-// (gr_assemble_tiles, rules O1-O8) and the class counts of the raster cells under every polygon row (gr_zonal_class_counts,
-// rules Z1-Z7); the rule-sets are DESIGN.md section 8m.  Needs no uploaded mesh and no context scratch.
+// (gr_assemble_tiles, rules O1-O8), the class counts of the raster cells under every polygon row (gr_zonal_class_counts, rules
+// Z1-Z7) and polygon rows burned into a label raster (gr_burn_polygons, rules B1-B7); the rule-sets are DESIGN.md section 8m.
+// Needs no uploaded mesh and no context scratch.
 //
 // Assembly.  One lane per output pixel; a workgroup covers 64 x 4 pixels inside ONE bin of the host's bin table and stages that
 // bin's tile records in LDS, ORTHO_CHUNK at a time, so a bin may list any number of tiles.  A lane keeps no per-class array (the
@@ -18,6 +19,12 @@
 // per lane is kept in one word.
 // Inside cells go into an LDS histogram of C words, then one 64-bit atomicAdd per class with a non-zero count: integers, so the
 // order does not matter.  All integer; no floating point in that kernel.
+//
+// Polygon burn (gr_burn_polygons, rules B1-B7).  k_burn_rows is the zonal kernel up to the parity word -- the two share ONE ring
+// walk, zonal_parity_walk --, over items in the coordinates of the parent grid restricted to a window of it.  A lane whose parity
+// bit is set does one non-returning atomicMax of the row index into the window's row plane (set to -1 at the head of the call):
+// the cells of an item are distinct, so nothing contends inside a workgroup, and an integer maximum does not depend on the order
+// in which the rows arrive (B3: the highest row wins).  k_burn_values maps the row plane to bytes, one lane per cell.  All integer.
 #include "geom_dev.hpp"
 #include "gr_internal.hpp"
 
@@ -146,15 +153,16 @@ __global__ __launch_bounds__(256) void k_assemble_tiles(const uint8_t *__restric
   stat_add(stats, GR_ORTHO_STAT_PAIRS, covering, lane);
 }
 
-// The ring statistics of a ring table: one lane per ring.
+// The ring statistics of a ring table: one lane per ring.  The two words are the caller's (GR_ZONAL_STAT_* or GR_BURN_STAT_*).
+template <int LARGEST_RING, int RINGS_IGNORED>
 __global__ __launch_bounds__(256) void k_zonal_ring_stats(const int64_t *__restrict__ roff, int64_t R, int64_t n_rv,
                                                           unsigned long long *__restrict__ stats) {
   const int lane = (int)(threadIdx.x & 63);
   const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
   int64_t i0, n = 0;
   if (r < R) n = ring_span(roff, (int)r, n_rv, i0);
-  stat_max(stats, GR_ZONAL_STAT_LARGEST_RING, (unsigned long long)n, lane);
-  stat_count(stats, GR_ZONAL_STAT_RINGS_IGNORED, r < R && n < 3, lane);
+  stat_max(stats, LARGEST_RING, (unsigned long long)n, lane);
+  stat_count(stats, RINGS_IGNORED, r < R && n < 3, lane);
 }
 
 // Rule Z3: edge_crossing<false> of geom_dev.hpp with ONE difference.  That walk counts a point exactly ON an edge that runs
@@ -168,6 +176,48 @@ __device__ __forceinline__ void edge_crossing_strict(int64_t ax, int64_t ay, int
     const i128 o = orient(ax, ay, bx, by, px, py);
     if (by > ay ? o > 0 : o < 0) parity ^= 1;
   }
+}
+
+// THE ring walk of the zonal counts and of the polygon burn (Z2, Z3 = B2): the parity word of this lane's cells of a block of
+// `bh` <= 128 rows from (col0, row0) -- bit k: the centre of cell (row0 + wave + 4 k, col0 + lane) lies in row p under the even-odd
+// rule over the rings [r_lo, r_hi) that belong to p.  Called by the whole workgroup of 256 (it holds barriers); the ring vertices
+// are staged in vx, vy (ZONAL_CHUNK + 1 words each), a chunk at a time.  The caller waits at a barrier before it reuses the LDS.
+__device__ __forceinline__ uint32_t zonal_parity_walk(const int64_t *__restrict__ rv, const int64_t *__restrict__ roff,
+                                                      const int32_t *__restrict__ rpoly, int64_t p, int64_t r_lo, int64_t r_hi,
+                                                      int64_t n_rv, int col0, int row0, int bh, int64_t *vx, int64_t *vy) {
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t px = 65536ll * (col0 + lane) + 32768;   // Z2
+  uint32_t parity = 0;
+  for (int64_t r = r_lo; r < r_hi; ++r) {
+    if ((int64_t)rpoly[r] != p) continue;
+    int64_t i0;
+    const int64_t n = ring_span(roff, (int)r, n_rv, i0);
+    if (n < 3) continue;
+    for (int64_t k0 = 0; k0 < n; k0 += ZONAL_CHUNK) {
+      const int n_chunk = (int)min((int64_t)ZONAL_CHUNK, n - k0);   // edges k0 + j -> k0 + j + 1 (the last one closes the ring)
+      __syncthreads();
+      if (tid <= n_chunk) {
+        int64_t at = k0 + tid;
+        if (at >= n) at -= n;   // only k0 + n_chunk == n wraps, to vertex 0
+        vx[tid] = rv[(i0 + at) * 2];
+        vy[tid] = rv[(i0 + at) * 2 + 1];
+      }
+      if (tid == 0 && n_chunk == ZONAL_CHUNK) {
+        int64_t at = k0 + ZONAL_CHUNK;
+        if (at >= n) at -= n;
+        vx[ZONAL_CHUNK] = rv[(i0 + at) * 2];
+        vy[ZONAL_CHUNK] = rv[(i0 + at) * 2 + 1];
+      }
+      __syncthreads();
+      for (int k = 0; wave + 4 * k < bh; ++k) {
+        const int64_t py = 65536ll * (row0 + wave + 4 * k) + 32768;
+        int flips = 0;
+        for (int j = 0; j < n_chunk; ++j) edge_crossing_strict(vx[j], vy[j], vx[j + 1], vy[j + 1], px, py, flips);
+        parity ^= (uint32_t)(flips & 1) << k;
+      }
+    }
+  }
+  return parity;
 }
 
 struct ZonalArgs {
@@ -194,37 +244,8 @@ __global__ __launch_bounds__(256) void k_zonal_class_counts(const uint8_t *__res
     return;
   const int64_t r_lo = min(max((int64_t)it[5], (int64_t)0), a.R), r_hi = min(max((int64_t)it[6], r_lo), a.R);
   if (tid < a.C) hist[tid] = 0;   // C <= 256 = the workgroup
-  const int64_t px = 65536ll * (col0 + lane) + 32768;   // Z2
-  uint32_t parity = 0;   // bit k: the row row0 + wave + 4 k
-  for (int64_t r = r_lo; r < r_hi; ++r) {
-    if ((int64_t)rpoly[r] != p) continue;
-    int64_t i0;
-    const int64_t n = ring_span(roff, (int)r, a.n_rv, i0);
-    if (n < 3) continue;
-    for (int64_t k0 = 0; k0 < n; k0 += ZONAL_CHUNK) {
-      const int n_chunk = (int)min((int64_t)ZONAL_CHUNK, n - k0);   // edges k0 + j -> k0 + j + 1 (the last one closes the ring)
-      __syncthreads();
-      if (tid <= n_chunk) {
-        int64_t at = k0 + tid;
-        if (at >= n) at -= n;   // only k0 + n_chunk == n wraps, to vertex 0
-        vx[tid] = rv[(i0 + at) * 2];
-        vy[tid] = rv[(i0 + at) * 2 + 1];
-      }
-      if (tid == 0 && n_chunk == ZONAL_CHUNK) {
-        int64_t at = k0 + ZONAL_CHUNK;
-        if (at >= n) at -= n;
-        vx[ZONAL_CHUNK] = rv[(i0 + at) * 2];
-        vy[ZONAL_CHUNK] = rv[(i0 + at) * 2 + 1];
-      }
-      __syncthreads();
-      for (int k = 0; wave + 4 * k < bh; ++k) {
-        const int64_t py = 65536ll * (row0 + wave + 4 * k) + 32768;
-        int flips = 0;
-        for (int j = 0; j < n_chunk; ++j) edge_crossing_strict(vx[j], vy[j], vx[j + 1], vy[j + 1], px, py, flips);
-        parity ^= (uint32_t)(flips & 1) << k;
-      }
-    }
-  }
+  // bit k: the row row0 + wave + 4 k
+  const uint32_t parity = zonal_parity_walk(rv, roff, rpoly, p, r_lo, r_hi, a.n_rv, col0, row0, bh, vx, vy);
   __syncthreads();   // the histogram is zeroed; the last chunk is read
   unsigned int n_in = 0, n_nodata = 0, n_over = 0, largest = 0;
   if (lane < bw) {
@@ -245,6 +266,60 @@ __global__ __launch_bounds__(256) void k_zonal_class_counts(const uint8_t *__res
   stat_add_u32(stats, GR_ZONAL_STAT_NODATA, n_nodata, lane);
   stat_add_u32(stats, GR_ZONAL_STAT_OVER, n_over, lane);
   stat_max(stats, GR_ZONAL_STAT_LARGEST_PLUS_1, largest, lane);
+}
+
+struct BurnArgs {
+  int64_t n_rv, R, P, n_cells;
+  int32_t col_off, row_off, width, height, fill;
+};
+
+// The ring table as k_zonal_class_counts takes it; items in the coordinates of the PARENT grid (col0, row0 may be negative), each
+// inside the window [col_off, col_off + width) x [row_off, row_off + height) (B1, B5); rows [height][width], -1 on entry;
+// stats [GR_BURN_STAT_WORDS].
+__global__ __launch_bounds__(256) void k_burn_rows(const int64_t *__restrict__ rv, const int64_t *__restrict__ roff,
+                                                   const int32_t *__restrict__ rpoly, const int32_t *__restrict__ items,
+                                                   int32_t *__restrict__ rows, unsigned long long *__restrict__ stats, BurnArgs a) {
+  __shared__ int64_t vx[ZONAL_CHUNK + 1], vy[ZONAL_CHUNK + 1];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int32_t *it = items + (int64_t)blockIdx.x * GR_ZONAL_ITEM_INTS;
+  const int64_t p = it[0];
+  const int col0 = it[1], row0 = it[2], bw = it[3], bh = it[4];
+  // B7: an item that is malformed or leaves the window is skipped whole (workgroup-uniform); the sums are taken in 64 bits
+  if (p < 0 || p >= a.P || bw < 1 || bh < 1 || bw > GR_ZONAL_BLOCK_W || bh > GR_ZONAL_BLOCK_H || col0 < a.col_off || row0 < a.row_off ||
+      (int64_t)col0 + bw > (int64_t)a.col_off + a.width || (int64_t)row0 + bh > (int64_t)a.row_off + a.height)
+    return;
+  const int64_t r_lo = min(max((int64_t)it[5], (int64_t)0), a.R), r_hi = min(max((int64_t)it[6], r_lo), a.R);
+  const uint32_t parity = zonal_parity_walk(rv, roff, rpoly, p, r_lo, r_hi, a.n_rv, col0, row0, bh, vx, vy);
+  unsigned int n_in = 0;
+  if (lane < bw) {
+    const int64_t x = (int64_t)col0 + lane - a.col_off;   // in [0, width)
+    for (int k = 0; wave + 4 * k < bh; ++k) {
+      if (!((parity >> k) & 1u)) continue;
+      const int64_t y = (int64_t)row0 + wave + 4 * k - a.row_off;   // in [0, height)
+      atomicMax(&rows[y * a.width + x], (int)p);   // the result is not used: B3, the highest row, whatever the order
+      ++n_in;
+    }
+  }
+  if (tid == 0) atomicAdd(&stats[GR_BURN_STAT_TESTED], (unsigned long long)bw * (unsigned long long)bh);
+  stat_add_u32(stats, GR_BURN_STAT_INSIDE, n_in, lane);
+}
+
+// B4: out = values[rows], `fill` where rows < 0 (or names no row); one lane per cell, the grid capped.  Counts the burned cells.
+__global__ __launch_bounds__(256) void k_burn_values(const int32_t *__restrict__ rows, const uint8_t *__restrict__ values,
+                                                     uint8_t *__restrict__ out, unsigned long long *__restrict__ stats, BurnArgs a) {
+  const int lane = (int)(threadIdx.x & 63);
+  unsigned long long burned = 0;   // wave-uniform
+  for (int64_t base = (int64_t)blockIdx.x * 256; base < a.n_cells; base += (int64_t)gridDim.x * 256) {   // workgroup-uniform
+    const int64_t i = base + threadIdx.x;
+    bool hit = false;
+    if (i < a.n_cells) {
+      const int64_t p = rows[i];
+      hit = p >= 0 && p < a.P;
+      out[i] = hit ? values[p] : (uint8_t)a.fill;
+    }
+    burned += (unsigned long long)__popcll(__ballot(hit));
+  }
+  if (lane == 0 && burned) atomicAdd(&stats[GR_BURN_STAT_BURNED], burned);
 }
 
 }  // namespace
@@ -319,7 +394,8 @@ int gr_zonal_class_counts(gr_ctx *c, const uint8_t *raster, int32_t H, int32_t W
   if (P > 0) GR_HIP(c, hipMemsetAsync(counts, 0, sizeof(uint64_t) * (size_t)P * (size_t)C, s));
   unsigned long long *st = (unsigned long long *)stats;
   if (R > 0) {
-    hipLaunchKernelGGL(k_zonal_ring_stats, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, s, ring_offsets, R, n_ring_vertices, st);
+    hipLaunchKernelGGL((k_zonal_ring_stats<GR_ZONAL_STAT_LARGEST_RING, GR_ZONAL_STAT_RINGS_IGNORED>), dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, s,
+                       ring_offsets, R, n_ring_vertices, st);
     GR_HIP(c, hipGetLastError());
   }
   if (n_items == 0 || R == 0) return GR_OK;
@@ -328,6 +404,46 @@ int gr_zonal_class_counts(gr_ctx *c, const uint8_t *raster, int32_t H, int32_t W
   hipLaunchKernelGGL(k_zonal_class_counts, dim3((unsigned)n_items), dim3(256), 0, s, raster, ring_vertices, ring_offsets, ring_polygon,
                      items, (unsigned long long *)counts, st, a);
   GR_HIP(c, hipGetLastError());
+  return GR_OK;
+}
+
+int gr_burn_polygons(gr_ctx *c, const int64_t *ring_vertices, int64_t n_ring_vertices, const int64_t *ring_offsets,
+                     const int32_t *ring_polygon, int64_t R, int64_t P, const uint8_t *values, const int32_t *items, int64_t n_items,
+                     int32_t col_off, int32_t row_off, int32_t width, int32_t height, int32_t fill, int32_t *rows, uint8_t *out,
+                     uint64_t *stats, void *stream) {
+  if (!c) return GR_EINVAL;
+  const int32_t lim = 1 << 23;
+  if (width < 1 || height < 1 || col_off <= -lim || row_off <= -lim || col_off >= lim || row_off >= lim ||
+      (int64_t)col_off + width > lim || (int64_t)row_off + height > lim)
+    return fail(c, GR_EINVAL, "gr_burn_polygons: window %d x %d at (%d, %d) is empty or leaves (-2^23, 2^23]", width, height, col_off, row_off);
+  if (n_ring_vertices < 0 || R < 0 || P < 0 || n_items < 0 || R > 0x7FFFFFFFll || P > 0x7FFFFFFFll || n_items > 0x7FFFFFFFll)
+    return fail(c, GR_EINVAL, "gr_burn_polygons: a size is negative or not below 2^31");
+  if (fill < 0 || fill > 255) return fail(c, GR_EINVAL, "gr_burn_polygons: fill=%d outside [0, 255]", fill);
+  if (!rows || !stats || !ring_offsets || (R > 0 && !ring_polygon) || (n_ring_vertices > 0 && !ring_vertices) || (n_items > 0 && !items))
+    return fail(c, GR_EINVAL, "gr_burn_polygons: null arrays");
+  if (out && P > 0 && !values) return fail(c, GR_EINVAL, "gr_burn_polygons: null values with an output plane");
+  hipStream_t s = (hipStream_t)stream;
+  BurnArgs a;
+  a.n_rv = n_ring_vertices; a.R = R; a.P = P; a.n_cells = (int64_t)width * height;
+  a.col_off = col_off; a.row_off = row_off; a.width = width; a.height = height; a.fill = fill;
+  GR_HIP(c, hipSetDevice(c->device));
+  GR_HIP(c, hipMemsetAsync(stats, 0, sizeof(uint64_t) * GR_BURN_STAT_WORDS, s));
+  GR_HIP(c, hipMemsetAsync(rows, 0xFF, sizeof(int32_t) * (size_t)a.n_cells, s));   // -1: no row
+  unsigned long long *st = (unsigned long long *)stats;
+  if (R > 0) {
+    hipLaunchKernelGGL((k_zonal_ring_stats<GR_BURN_STAT_LARGEST_RING, GR_BURN_STAT_RINGS_IGNORED>), dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, s,
+                       ring_offsets, R, n_ring_vertices, st);
+    GR_HIP(c, hipGetLastError());
+  }
+  if (n_items > 0 && R > 0) {
+    hipLaunchKernelGGL(k_burn_rows, dim3((unsigned)n_items), dim3(256), 0, s, ring_vertices, ring_offsets, ring_polygon, items, rows, st, a);
+    GR_HIP(c, hipGetLastError());
+  }
+  if (out) {
+    const unsigned groups = (unsigned)min(ceil_div(a.n_cells, (int64_t)256), (int64_t)GR_BURN_MAX_GROUPS);
+    hipLaunchKernelGGL(k_burn_values, dim3(groups), dim3(256), 0, s, rows, values, out, st, a);
+    GR_HIP(c, hipGetLastError());
+  }
   return GR_OK;
 }
 

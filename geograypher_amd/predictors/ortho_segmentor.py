@@ -10,8 +10,9 @@ or an object with the same `assemble_tiles` method.
 
 Stated divergences: the counts are saved as `.npy` (C, H, W), not as a C-band GeoTIFF; every pixel of the extent is written
 (the reference skips blocks that are all nodata, so what such a block reads back as is GDAL's choice); prediction files are
-taken in sorted order (the reference's glob order is arbitrary, which matters to the float sums only); `write_chips` writes
-imagery only."""
+taken in sorted order (the reference's glob order is arbitrary, which matters to the float sums only); a label value of
+`write_chips` outside [0, 255] is an error (the reference wraps it), and what GDAL burns for a pixel centre exactly ON a polygon
+boundary is not measured."""
 import os
 import shutil
 from collections import namedtuple
@@ -232,6 +233,75 @@ def assemble_tiled_predictions(
     return classes, extent
 
 
+class _ChipLabels:
+    """The label polygons of `write_chips` on the device: one ring table in the cell units of the raster's grid, one `PolygonBurner`."""
+
+    def __init__(self, label_vector_file, label_column, label_remap, transform, epsg, backend):
+        from geograypher_amd.utils.geometric import PlanarPolygons, row_centre_boxes, row_ring_ranges
+        from geograypher_amd.utils.geospatial import burn_values, rings_in_raster_CRS, rings_to_cell_units
+        from geograypher_amd.utils.raster import invert_affine
+
+        polygons, properties = PlanarPolygons.from_geojson(label_vector_file)
+        P = len(polygons)
+        if label_column is None:
+            values = list(range(P))            # the reference's index: the feature number
+        elif label_column in properties:
+            values = properties[label_column].tolist()
+        else:
+            raise ValueError(f"label_vector_file {label_vector_file} has no column {label_column!r} (it has {sorted(properties)})")
+        if label_remap is not None:
+            missing = [v for v in values if v not in label_remap]
+            if missing:
+                raise ValueError(f"label_remap has no entry for {missing[0]!r}")
+            values = [label_remap[v] for v in values]
+        values = burn_values(values, P)
+        if backend is None:
+            from geograypher_amd._hip import HipRaster
+
+            backend = HipRaster()
+        rv, off = rings_to_cell_units(rings_in_raster_CRS(polygons, epsg, backend), invert_affine(transform))
+        rp = np.asarray(polygons.ring_polygon, dtype=np.int32)
+        self.burner = backend.polygon_burner(rv, off, rp, P, values)
+        self.boxes, self.ranges = row_centre_boxes(rv, off, rp, P), row_ring_ranges(rp, P)
+
+    def label(self, window, background_ind: int, keep_empty: bool):
+        """The (height, width) uint8 label of a window, or None for one that is all NULL_TEXTURE_INT_VALUE unless `keep_empty`.
+        Where the background is that constant, a window without a burned cell is known empty from the statistics word alone and
+        its plane is not copied back."""
+        from geograypher_amd._hip import GR_BURN_STAT_BURNED
+        from geograypher_amd.utils.geometric import burn_work_items
+        from geograypher_amd.utils.geospatial import _to_host
+
+        items = burn_work_items(self.boxes, self.ranges, tuple(window))
+        _rows, out, stats = self.burner.window(*window, items, fill=background_ind, want_values=True)
+        if not keep_empty and background_ind == NULL_TEXTURE_INT_VALUE and int(_to_host(stats)[GR_BURN_STAT_BURNED]) == 0:
+            return None
+        label = _to_host(out).astype(np.uint8, copy=False)
+        if not keep_empty and np.all(label == NULL_TEXTURE_INT_VALUE):
+            return None
+        return label
+
+
+class _ChipRegion:
+    """The region of interest of `write_chips`: the edges of its polygons in the cell units of the raster's grid (Z1)."""
+
+    def __init__(self, ROI_file, transform, epsg, backend):
+        from geograypher_amd.utils.geometric import PlanarPolygons, ring_edges
+        from geograypher_amd.utils.geospatial import rings_in_raster_CRS, rings_to_cell_units
+        from geograypher_amd.utils.raster import invert_affine
+
+        polygons, _ = PlanarPolygons.from_geojson(ROI_file)
+        rv, off = rings_to_cell_units(rings_in_raster_CRS(polygons, epsg, backend), invert_affine(transform))
+        self.edges, self.edge_row = ring_edges(rv, off, polygons.ring_polygon)
+
+    def meets(self, window) -> bool:
+        from geograypher_amd.utils.geometric import rectangle_meets_rows
+
+        return rectangle_meets_rows(self.edges, self.edge_row, (65536 * window.col_off, 65536 * window.row_off,
+                                                                65536 * (window.col_off + window.width),
+                                                                65536 * (window.row_off + window.height)))
+
+
 def write_chips(
     raster_file: PATH_TYPE,
     output_folder: PATH_TYPE,
@@ -246,20 +316,56 @@ def write_chips(
     output_suffix: str = ".JPG",
     ROI_file: Optional[PATH_TYPE] = None,
     background_ind: int = NULL_TEXTURE_INT_VALUE,
+    backend=None,
 ):
     """Cut the image `raster_file` into square chips of `chip_size` every `chip_stride` pixels and write them to `output_folder`,
     named by their window (`get_str_from_window`).  Chips at the far edges are zero-padded to full size.  With
     `drop_transparency` a fourth band is dropped, its transparent pixels turned black, and a chip that is all transparent is
-    not written.  `remove_old` removes `output_folder` first.  Imagery only: `label_vector_file` and `ROI_file` raise
-    NotImplementedError (chip label rasters need a polygon burn).  No device work.  Returns the files written."""
+    not written.  `remove_old` removes `output_folder` first.  Returns the image files written.
+
+    label_vector_file (a `.geojson`; the raster must then be a georeferenced GeoTIFF): training data as the reference writes it --
+    the imagery goes to `output_folder/imgs`, and beside it `output_folder/anns/<window name>.png` holds the polygons burned into
+    the chip's window on the device (one `PolygonBurner` for the file, one window call per chip; rules B1-B7 of DESIGN.md 8m in
+    place of rasterio.features.rasterize): the value of the last feature that holds a pixel's centre, `background_ind` elsewhere,
+    past the raster's edge too.  The values are `label_column` of the features, else the feature number, mapped through
+    `label_remap` when given; every value must be an integer in [0, 255] (ValueError: the reference's astype(np.uint8) wraps).
+    Labels in another CRS than the raster's are reprojected vertex by vertex.  Without `write_empty_tiles` a chip whose label is
+    all NULL_TEXTURE_INT_VALUE is skipped (the reference compares with the constant, not with `background_ind`).
+    ROI_file (a `.geojson`): a chip is written iff its window rectangle intersects the union of the ROI's polygons, touching
+    included (`rectangle_meets_rows`: exact, on the host).  As in the reference the labels are NOT clipped to the ROI: it builds
+    its label shapes before its clip takes effect.
+    A vector file that is no `.geojson`, or a raster that is no georeferenced GeoTIFF beside one, is a NotImplementedError before
+    anything is removed or read.  `backend`: a `HipRaster` (default: one on the current device) or an object with its
+    `polygon_burner` (and `reproject_points`) method; without labels there is no device work."""
     from PIL import Image
 
-    if label_vector_file is not None:
-        raise NotImplementedError("label_vector_file: chip label rasters need a polygon burn, which is not available")
-    if ROI_file is not None:
-        raise NotImplementedError("ROI_file: restricting the chips to a region is not available")
+    vector_files = [(name, file) for name, file in (("label_vector_file", label_vector_file), ("ROI_file", ROI_file)) if file is not None]
+    burner = roi = None
+    if vector_files:
+        names = " / ".join(name for name, _ in vector_files)
+        for name, file in vector_files:
+            if Path(file).suffix.lower() != ".geojson":
+                raise NotImplementedError(f"{name} {file}: vector files are read as .geojson only")
+        if Path(raster_file).suffix.lower() not in (".tif", ".tiff"):
+            raise NotImplementedError(f"{names}: {raster_file} is not a GeoTIFF; labels and regions need a georeferenced raster")
+        from geograypher_amd.utils.raster import read_geotiff_header
+
+        try:
+            transform, _nodata, epsg, _height, _width = read_geotiff_header(raster_file)
+        except ValueError as error:
+            raise NotImplementedError(f"{names}: labels and regions need a georeferenced raster ({error})") from error
+        if not 0 <= int(background_ind) <= 255:
+            raise ValueError(f"background_ind={background_ind} does not fit the uint8 label raster")
+        if label_vector_file is not None:
+            burner = _ChipLabels(label_vector_file, label_column, label_remap, transform, epsg, backend)
+        if ROI_file is not None:
+            roi = _ChipRegion(ROI_file, transform, epsg, backend)
     if remove_old and os.path.isdir(output_folder):
         shutil.rmtree(output_folder)
+    labels_folder = None
+    if burner is not None:
+        labels_folder, output_folder = Path(output_folder, "anns"), Path(output_folder, "imgs")
+        labels_folder.mkdir(parents=True, exist_ok=True)
     Path(output_folder).mkdir(parents=True, exist_ok=True)
     limit, Image.MAX_IMAGE_PIXELS = Image.MAX_IMAGE_PIXELS, None
     try:
@@ -271,6 +377,13 @@ def write_chips(
         img = img[:, :, None]
     written = []
     for window in create_windows(img.shape[:2], chip_size, chip_stride):
+        if roi is not None and not roi.meets(window):
+            continue
+        if burner is not None:
+            label = burner.label(window, int(background_ind), keep_empty=write_empty_tiles)
+            if label is None:
+                continue
+            Image.fromarray(label).save(Path(labels_folder, get_str_from_window(window, raster_file, ".png")), format="PNG")
         chip = img[window.row_off:window.row_off + window.height, window.col_off:window.col_off + window.width].copy()
         if drop_transparency and chip.shape[2] == 4:
             transparent = chip[..., 3] == 0

@@ -285,7 +285,8 @@ class PlanarPolygons:
         has no rings.  A third coordinate is dropped.  properties: {name: (n_features,) array} over the union of the features'
         property names, None where a feature lacks one: int64 when every value is an int, float64 when every value is a
         number (bool is neither), otherwise object.  The coordinates are taken as they stand: planar metres, no CRS handling; the
-        EPSG code of a `crs` member is recorded as `.epsg` of the polygons (None without one) and nothing consults it."""
+        EPSG code of a `crs` member is recorded as `.epsg` of the polygons (None without one); only the polygon burn
+        (`utils.geospatial.burn_polygons`, `write_chips`) consults it."""
         import json
 
         with open(path, "r") as file:
@@ -807,3 +808,111 @@ def zonal_work_items(ring_vertices, ring_offsets, ring_polygon, n_polygons: int,
     items = np.stack([rows[owner], col0, row0, np.minimum(bw, c1[owner] + 1 - col0), np.minimum(bh, r1[owner] + 1 - row0),
                       ring_lo[rows[owner]], ring_hi[rows[owner]]], axis=1) if len(owner) else np.zeros((0, 7))
     return np.ascontiguousarray(items, dtype=np.int32)
+
+
+# -- polygon rows burned into windows of a raster grid ---------------------------------------------------------
+def row_centre_boxes(ring_vertices, ring_offsets, ring_polygon, n_polygons: int) -> np.ndarray:
+    """(P, 4) int64 col0, row0, col1, row1: the inclusive, UNCLAMPED box of the cell indices whose centre the row's rings of 3 or
+    more vertices can hold, from the ring table in cell units (`utils.geospatial.rings_to_cell_units`); a row that can hold none
+    has the empty box (1, 1, 0, 0).  Computed once per ring table: `burn_work_items` cuts it to each window."""
+    rv = np.asarray(ring_vertices, dtype=np.int64).reshape(-1, 2)
+    off = np.asarray(ring_offsets, dtype=np.int64).reshape(-1)
+    rp = np.asarray(ring_polygon, dtype=np.int64).reshape(-1)
+    P = int(n_polygons)
+    big = np.iinfo(np.int64).max
+    lo = np.full((P, 2), big, dtype=np.int64)
+    hi = np.full((P, 2), -big, dtype=np.int64)
+    n = np.diff(off)
+    if len(rv) and len(n):
+        of_ring = np.repeat(np.arange(len(n)), n)          # the ring of every vertex
+        live = n[of_ring] >= 3
+        np.minimum.at(lo, rp[of_ring[live]], rv[live])
+        np.maximum.at(hi, rp[of_ring[live]], rv[live])
+    boxes = np.tile(np.array([1, 1, 0, 0], dtype=np.int64), (P, 1))
+    rows = np.nonzero(lo[:, 0] <= hi[:, 0])[0]
+    # a centre 65536 c + 32768 lies in [lo, hi] iff ceil((lo - 32768) / 65536) <= c <= floor((hi - 32768) / 65536)
+    c0, c1 = -((32768 - lo[rows, 0]) // 65536), (hi[rows, 0] - 32768) // 65536
+    r0, r1 = -((32768 - lo[rows, 1]) // 65536), (hi[rows, 1] - 32768) // 65536
+    keep = (c0 <= c1) & (r0 <= r1)
+    boxes[rows[keep]] = np.stack([c0, r0, c1, r1], axis=1)[keep]
+    return boxes
+
+
+def row_ring_ranges(ring_polygon, n_polygons: int) -> np.ndarray:
+    """(P, 2) int64: the first ring of every row and one past its last, from the non-decreasing `ring_polygon`."""
+    rp = np.asarray(ring_polygon, dtype=np.int64).reshape(-1)
+    rows = np.arange(int(n_polygons))
+    return np.stack([np.searchsorted(rp, rows, "left"), np.searchsorted(rp, rows, "right")], axis=1).astype(np.int64)
+
+
+def burn_work_items(boxes, ring_ranges, window, block=ZONAL_BLOCK) -> np.ndarray:
+    """The work items `PolygonBurner.window` takes for one window (rule B5), by count-then-fill: boxes (P, 4) of
+    `row_centre_boxes`, ring_ranges (P, 2) of `row_ring_ranges`, window = (col_off, row_off, width, height) in cells of the parent
+    grid -> (n, 7) int32 rows (polygon row, col0, row0, width, height, first ring, one past the last ring) in PARENT coordinates:
+    every row's box cut to the window and then into blocks of at most block = (width <= 64, height <= 128) cells.  Rows whose box
+    misses the window have no item; no vertex is looked at."""
+    bw, bh = int(block[0]), int(block[1])
+    if not (1 <= bw <= 64 and 1 <= bh <= 128):
+        raise ValueError(f"a block is at most 64 x 128 cells, got {bw} x {bh}")
+    boxes = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
+    ring_ranges = np.asarray(ring_ranges, dtype=np.int64).reshape(-1, 2)
+    col_off, row_off, width, height = (int(v) for v in window)
+    c0, c1 = np.maximum(boxes[:, 0], col_off), np.minimum(boxes[:, 2], col_off + width - 1)
+    r0, r1 = np.maximum(boxes[:, 1], row_off), np.minimum(boxes[:, 3], row_off + height - 1)
+    rows = np.nonzero((c0 <= c1) & (r0 <= r1))[0]
+    c0, c1, r0, r1 = c0[rows], c1[rows], r0[rows], r1[rows]
+    nx, ny = -(-(c1 - c0 + 1) // bw), -(-(r1 - r0 + 1) // bh)
+    n = nx * ny
+    owner = np.repeat(np.arange(len(rows)), n)
+    if not len(owner):
+        return np.zeros((0, 7), dtype=np.int32)
+    k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+    bx, by = k % nx[owner], k // nx[owner]
+    col0, row0 = c0[owner] + bx * bw, r0[owner] + by * bh
+    items = np.stack([rows[owner], col0, row0, np.minimum(bw, c1[owner] + 1 - col0), np.minimum(bh, r1[owner] + 1 - row0),
+                      ring_ranges[rows[owner], 0], ring_ranges[rows[owner], 1]], axis=1)
+    return np.ascontiguousarray(items, dtype=np.int32)
+
+
+def ring_edges(ring_vertices, ring_offsets, ring_polygon):
+    """(edges (E, 4) int64 ax ay bx by, edge_row (E,) int64): every edge, the closing one included, of the rings of 3 or more
+    vertices of a ring table, and the row each belongs to -- what `rectangle_meets_rows` walks."""
+    rv = np.asarray(ring_vertices, dtype=np.int64).reshape(-1, 2)
+    off = np.asarray(ring_offsets, dtype=np.int64).reshape(-1)
+    rp = np.asarray(ring_polygon, dtype=np.int64).reshape(-1)
+    edges, rows = [], []
+    for r in range(len(rp)):
+        ring = rv[off[r]:off[r + 1]]
+        if len(ring) >= 3:
+            edges.append(np.concatenate([ring, np.roll(ring, -1, axis=0)], axis=1))
+            rows.append(np.full(len(ring), rp[r], dtype=np.int64))
+    if not edges:
+        return np.zeros((0, 4), dtype=np.int64), np.zeros(0, dtype=np.int64)
+    return np.concatenate(edges), np.concatenate(rows)
+
+
+def rectangle_meets_rows(edges, edge_row, rectangle) -> bool:
+    """Whether the CLOSED rectangle (x0, y0, x1, y1), x0 <= x1, y0 <= y1, intersects the union of the polygon rows behind `edges`
+    (`ring_edges`), touching included; every row is the even-odd region of all its rings (Z3), all in one integer unit.  Exact:
+    the boxes are compared in int64, the determinants are Python integers.  The rectangle meets a row iff a ring edge meets it
+    (which covers a ring vertex inside it: an edge meets a box iff their boxes overlap and the box's corners do not all lie
+    strictly on one side of the edge's line) or, when no edge does, iff the rectangle lies inside the row whole -- then all four
+    corners agree and the corner (x0, y0) is asked.  This is no centre test: a thin row selects every rectangle it crosses."""
+    x0, y0, x1, y1 = (int(v) for v in rectangle)
+    edges = np.asarray(edges, dtype=np.int64).reshape(-1, 4)
+    ax, ay, bx, by = edges.T
+    near = np.nonzero((np.minimum(ax, bx) <= x1) & (np.maximum(ax, bx) >= x0) & (np.minimum(ay, by) <= y1) & (np.maximum(ay, by) >= y0))[0]
+    for k in near:
+        axk, ayk, bxk, byk = (int(v) for v in edges[k])
+        side = [(bxk - axk) * (cy - ayk) - (byk - ayk) * (cx - axk) for cx, cy in ((x0, y0), (x1, y0), (x1, y1), (x0, y1))]
+        if not (all(s > 0 for s in side) or all(s < 0 for s in side)):
+            return True
+    # no edge meets the rectangle: the parity of the corner (x0, y0) per row, half-open in y, strictly left of the upward edge
+    inside = {}
+    for k in np.nonzero((ay > y0) != (by > y0))[0]:
+        axk, ayk, bxk, byk = (int(v) for v in edges[k])
+        o = (bxk - axk) * (y0 - ayk) - (byk - ayk) * (x0 - axk)
+        if (o > 0) if byk > ayk else (o < 0):
+            row = int(edge_row[k])
+            inside[row] = not inside.get(row, False)
+    return any(inside.values())

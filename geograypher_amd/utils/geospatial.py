@@ -256,3 +256,92 @@ def get_overlap_raster(unlabeled_df, classes_raster, num_classes=None, normalize
     if normalize:
         matrix = matrix / np.sum(matrix, axis=1, keepdims=True)
     return matrix, valid
+
+
+# -- polygon rows burned into a label raster (reference: rasterio.features.rasterize in write_chips) ------------
+def _to_host(x) -> np.ndarray:
+    return np.asarray(x.cpu() if hasattr(x, "cpu") else x)
+
+
+def rings_in_raster_CRS(polygons, raster_epsg, backend=None):
+    """The rings of a `PlanarPolygons` in the CRS of a raster: as they stand unless `polygons.epsg` and `raster_epsg` are both
+    known and differ; then every vertex is reprojected on its own with `backend.reproject_points` at height 0 (what geopandas'
+    to_crs does: edges are not densified).  GeoJSON coordinates are (easting, northing) / (lon, lat) whatever the authority's
+    axis order.  NotImplementedError where `WGS84CRS.parse` refuses one of the two."""
+    if polygons.epsg is None or raster_epsg is None or int(polygons.epsg) == int(raster_epsg) or not polygons.rings:
+        return polygons.rings
+    src, dst = WGS84CRS.parse(int(polygons.epsg)), WGS84CRS.parse(int(raster_epsg))
+    xy = np.concatenate(polygons.rings)
+    points = np.concatenate([xy, np.zeros((len(xy), 1))], axis=1)
+    out, _ = (backend if backend is not None else _default_backend()).reproject_points(points, src, dst)
+    out = _to_host(out).astype(np.float64)[:, :2]
+    return np.split(out, np.cumsum([len(r) for r in polygons.rings])[:-1])
+
+
+def burn_values(values, n_polygons: int) -> np.ndarray:
+    """(P,) uint8 from one value per polygon row: every value must be an integer in [0, 255], else ValueError (the reference's
+    astype(np.uint8) wraps such values silently)."""
+    values = list(values) if not isinstance(values, np.ndarray) else values.tolist()
+    if len(values) != int(n_polygons):
+        raise ValueError(f"{n_polygons} polygon rows need as many values, got {len(values)}")
+    out = np.zeros(len(values), dtype=np.uint8)
+    for k, v in enumerate(values):
+        is_number = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+        if not is_number or not np.isfinite(v) or v != int(v) or not 0 <= int(v) <= 255:
+            raise ValueError(f"the value {v!r} of polygon row {k} is not an integer in [0, 255]")
+        out[k] = int(v)
+    return out
+
+
+def _grid_like(like):
+    """(height, width, transform, epsg) of a `PlanarRaster`, a GeoTIFF path (header only) or ((height, width), transform)."""
+    from geograypher_amd.utils.raster import PlanarRaster, read_geotiff_header
+
+    if isinstance(like, PlanarRaster):
+        return like.data.shape[1], like.data.shape[2], like.transform, like.epsg
+    if isinstance(like, (str, bytes)) or hasattr(like, "__fspath__"):
+        transform, _nodata, epsg, height, width = read_geotiff_header(like)
+        return height, width, transform, epsg
+    (height, width), transform = like
+    return int(height), int(width), tuple(float(v) for v in transform), None
+
+
+def burn_polygons(polygons, values, like, fill: int = 255, backend=None, max_device_bytes=None, rows: bool = False):
+    """Polygon rows burned into a raster grid on the device (`HipRaster.polygon_burner`, gr_burn_polygons; rules B1-B7 of
+    DESIGN.md 8m), in place of rasterio.features.rasterize(zip(shapes, values), out_shape, transform=..., fill=fill).
+
+    polygons: a `PlanarPolygons`, a `.geojson` path or a sequence of ring arrays; when their EPSG code and the raster's are both
+    known and differ the vertices are reprojected (`rings_in_raster_CRS`).  values: one integer in [0, 255] per row (ValueError
+    otherwise); may be None with `rows`.  like: the grid -- a `PlanarRaster`, a GeoTIFF path (only its header is read) or
+    ((height, width), transform).  A cell takes the value of the HIGHEST row that holds its centre (later rows overwrite earlier
+    ones, rasterize's merge_alg=replace) and `fill` where none does; the centre rule is Z3 of `zonal_class_counts`, so a burned
+    raster and its zonal counts agree cell for cell, and what GDAL decides for a centre exactly ON a boundary is as unmeasured
+    here as there.  Returns the (height, width) uint8 raster, or with `rows` the int32 plane of winning rows (-1: none).
+    The grid is burned in bands of rows that take at most `max_device_bytes` of device memory, 5 bytes a cell (default: the
+    assembly's); the bands do not change a byte."""
+    from geograypher_amd.predictors.ortho_segmentor import DEFAULT_MAX_DEVICE_BYTES, MAX_BAND_ROWS
+    from geograypher_amd.utils.geometric import burn_work_items, row_centre_boxes, row_ring_ranges
+    from geograypher_amd.utils.raster import invert_affine
+
+    polygons = _as_planar_polygons(polygons)
+    height, width, transform, epsg = _grid_like(like)
+    P = len(polygons)
+    if values is None and not rows:
+        raise ValueError("burn_polygons needs one value per polygon row unless the row plane is asked for (rows=True)")
+    values = None if values is None else burn_values(values, P)
+    if not 0 <= int(fill) <= 255:
+        raise ValueError(f"fill={fill} does not fit the uint8 raster")
+    backend = backend if backend is not None else _default_backend()
+    rv, off = rings_to_cell_units(rings_in_raster_CRS(polygons, epsg, backend), invert_affine(transform))
+    rp = np.asarray(polygons.ring_polygon, dtype=np.int32)
+    burner = backend.polygon_burner(rv, off, rp, P, values)
+    boxes, ranges = row_centre_boxes(rv, off, rp, P), row_ring_ranges(rp, P)
+    budget = DEFAULT_MAX_DEVICE_BYTES if max_device_bytes is None else int(max_device_bytes)
+    band = int(max(1, min(height, MAX_BAND_ROWS, budget // (5 * max(width, 1)))))
+    result = np.empty((height, width), dtype=np.int32 if rows else np.uint8)
+    for row0 in range(0, height, band):
+        n = min(band, height - row0)
+        window = (0, row0, width, n)
+        rows_t, out_t, _stats = burner.window(*window, burn_work_items(boxes, ranges, window), fill=int(fill), want_values=not rows)
+        result[row0:row0 + n] = _to_host(rows_t if rows else out_t)
+    return result

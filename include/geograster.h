@@ -753,6 +753,22 @@ enum {
 };
 #include "geograster_decimate.h"
 
+/* Polygon rows burned into a label raster (geograster_burn.h): the words of the statistics block of the
+ * burn and the workgroup cap of its value pass.  The work items are those of the zonal class counts (GR_ZONAL_ITEM_INTS,
+ * GR_ZONAL_BLOCK_W, GR_ZONAL_BLOCK_H). */
+enum {
+  GR_BURN_STAT_TESTED = 0,         /* cells of the work items                                              */
+  GR_BURN_STAT_INSIDE = 1,         /* (row, cell) memberships: the cell's centre lies in the row           */
+  GR_BURN_STAT_BURNED = 2,         /* cells that took a row, counted by the value pass: 0 without `out`    */
+  GR_BURN_STAT_LARGEST_RING = 3,   /* the vertices of the largest ring                                     */
+  GR_BURN_STAT_RINGS_IGNORED = 4,  /* rings of fewer than 3 vertices                                       */
+  GR_BURN_STAT_WORDS = 8
+};
+enum {
+  GR_BURN_MAX_GROUPS = 8192        /* workgroups of the value pass: beyond it the lanes stride the plane   */
+};
+#include "geograster_burn.h"
+
 #ifdef __cplusplus
 }
 #endif
