@@ -161,6 +161,18 @@ GR_BURN_STAT_LARGEST_RING = 3
 GR_BURN_STAT_RINGS_IGNORED = 4
 GR_BURN_STAT_WORDS = 8
 GR_BURN_MAX_GROUPS = 8192
+# polygon-on-polygon overlap areas: stats words of gr_polygon_overlap_areas, the integers of a work item, the largest tiles
+GR_OVERLAP_STAT_PAIRS = 0
+GR_OVERLAP_STAT_ITEMS = 1
+GR_OVERLAP_STAT_EDGE_PAIRS = 2
+GR_OVERLAP_STAT_VERTICAL = 3
+GR_OVERLAP_STAT_RINGS_IGNORED = 4
+GR_OVERLAP_STAT_LARGEST_RING = 5
+GR_OVERLAP_STAT_BAD_ITEMS = 6
+GR_OVERLAP_STAT_WORDS = 8
+GR_OVERLAP_ITEM_INTS = 5
+GR_OVERLAP_TILE_A = 256
+GR_OVERLAP_TILE_B = 4096
 
 
 class StageTimes(ctypes.Structure):
@@ -288,6 +300,14 @@ _BURN_SIGNATURES = {
     "gr_burn_polygons": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
 }
 BURN_SYMBOLS = tuple(_BURN_SIGNATURES)
+# ... and the calls of include/geograster_overlap.h (polygon-on-polygon overlap areas), under the same contract.
+_OVERLAP_TABLE = [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64]   # one ring table: vertices, their number, offsets, polygons, holes, R, boxes, P
+_OVERLAP_SIGNATURES = {
+    "gr_polygon_box_pairs_count": [_vp, _vp, _i64, _vp, _i64, _vp, _vp],
+    "gr_polygon_box_pairs_fill": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp],
+    "gr_polygon_overlap_areas": [_vp, *_OVERLAP_TABLE, *_OVERLAP_TABLE, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
+}
+OVERLAP_SYMBOLS = tuple(_OVERLAP_SIGNATURES)
 
 
 def library_path() -> Path:
@@ -310,7 +330,8 @@ def load_library() -> ctypes.CDLL:
     # library's runtime without devices and gr_ctx_create answers GR_ENODEVICE.
     _torch()
     lib = ctypes.CDLL(str(_LIB_PATH))
-    for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES, **_BURN_SIGNATURES}.items():
+    for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES, **_BURN_SIGNATURES,
+                           **_OVERLAP_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -632,6 +653,145 @@ class PolygonBurner:
                   _ptr(self._values if want_values and self.n_polygons else None), _ptr(it_t if it_t.numel() else None),
                   int(it_t.shape[0]), col_off, row_off, width, height, fill, rows.data_ptr(), _ptr(out), stats.data_ptr(), hip._stream())
         return rows, out, stats
+
+
+OVERLAP_COORD_LIMIT = 1 << 40   # A1: |snapped coordinate| behind the common origin (utils.geometric.SNAP_LIMIT)
+
+
+def _check_overlap_table(name: str, side: str, table) -> int:
+    """A1 for one ring table (ring vertices, ring offsets, ring polygon, ring is hole, polygon boxes) -- ValueError naming the call; -> R."""
+    if len(table) != 5:
+        raise ValueError(f"{name}: table {side} must be (ring vertices, ring offsets, ring polygon, ring is hole, polygon boxes)")
+    rv, off, rp, rh, box = (np.asarray(x) for x in table)
+    if box.ndim != 2 or box.shape[1] != 4 or box.dtype.kind not in "iu":
+        raise ValueError(f"{name}: the polygon boxes of table {side} must be a (P, 4) integer array, got {box.shape} {box.dtype}")
+    if rv.ndim != 2 or rv.shape[1] != 2 or rv.dtype.kind not in "iu":
+        raise ValueError(f"{name}: the ring vertices of table {side} must be an (N, 2) integer array, got {rv.shape} {rv.dtype}")
+    if rv.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name}: table {side} has {rv.shape[0]} ring vertices, not below 2^31")
+    P = box.shape[0]
+    R = rp.reshape(-1).shape[0]
+    if P >= 2 ** 31 - 1:
+        raise ValueError(f"{name}: table {side} has {P} polygon rows")
+    for what, values in (("ring vertex", rv), ("polygon box", box)):
+        if values.size and np.abs(values.astype(np.int64)).max() > OVERLAP_COORD_LIMIT:
+            raise ValueError(f"{name}: a {what} of table {side} lies more than 2^40 grid steps from the common origin")
+    rp = rp.astype(np.int64).reshape(-1)
+    _check_offsets(np.asarray(off, dtype=np.int64).reshape(-1), R, rv.shape[0], "rings", f"{name}: table {side}: ring", "ring vertices")
+    if R and (rp.min() < 0 or rp.max() >= P or np.any(np.diff(rp) < 0)):
+        raise ValueError(f"{name}: the ring_polygon of table {side} must be non-decreasing inside [0, {P})")
+    if rh.reshape(-1).shape[0] != R or rh.dtype.kind not in "iub":
+        raise ValueError(f"{name}: table {side} needs one integer hole flag per ring, got {rh.shape} {rh.dtype}")
+    if rv.shape[0]:   # A3: the box of a row holds every vertex of the row (the baseline Y lies at or below both rows)
+        row = np.repeat(rp, np.diff(np.asarray(off, dtype=np.int64).reshape(-1)))
+        b = box.astype(np.int64)[row]
+        q = rv.astype(np.int64)
+        if np.any((q[:, 0] < b[:, 0]) | (q[:, 1] < b[:, 1]) | (q[:, 0] > b[:, 2]) | (q[:, 1] > b[:, 3])):
+            raise ValueError(f"{name}: a polygon box of table {side} does not hold every ring vertex of its row")
+    return R
+
+
+def check_overlap_tables(table_a, table_b):
+    """A1: the two ring tables of a `PolygonOverlap`, each (ring vertices (N, 2), ring offsets (R + 1,), ring polygon (R,), ring is
+    hole (R,), polygon boxes (P, 4)) as `PlanarPolygons.snapped` gives them behind ONE origin, are in range -- ValueError naming
+    gr_polygon_overlap_areas; -> (R_a, R_b)."""
+    name = "gr_polygon_overlap_areas"
+    return _check_overlap_table(name, "a", table_a), _check_overlap_table(name, "b", table_b)
+
+
+def _row_slot_ranges(ring_offsets, ring_polygon, n_polygons: int) -> np.ndarray:
+    """(P, 2) int64: the first edge slot (= ring vertex) of every row and one past its last."""
+    off = np.asarray(ring_offsets, dtype=np.int64).reshape(-1)
+    rp = np.asarray(ring_polygon, dtype=np.int64).reshape(-1)
+    rows = np.arange(int(n_polygons))
+    return np.stack([off[np.searchsorted(rp, rows, "left")], off[np.searchsorted(rp, rows, "right")]], axis=1)
+
+
+def check_overlap_items(pairs, items, offsets_a, rows_a, n_a: int, offsets_b, rows_b, n_b: int):
+    """A8: the pairs name rows of both tables, and every work item names a pair -- the pairs in non-decreasing order --, 1 ..
+    GR_OVERLAP_TILE_A consecutive edge slots of the pair's row of a and 1 .. GR_OVERLAP_TILE_B of its row of b -- ValueError naming
+    gr_polygon_overlap_areas."""
+    name = "gr_polygon_overlap_areas"
+    pr = np.asarray(pairs)
+    if pr.ndim != 2 or pr.shape[1] != 2 or pr.dtype.kind not in "iu":
+        raise ValueError(f"{name}: pairs must be (n, 2) integers, got {pr.shape} {pr.dtype}")
+    if pr.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name}: {pr.shape[0]} pairs, not below 2^31")
+    pr = pr.astype(np.int64)
+    if pr.shape[0] and (pr.min() < 0 or pr[:, 0].max() >= n_a or pr[:, 1].max() >= n_b):
+        k = int(np.nonzero((pr[:, 0] < 0) | (pr[:, 0] >= n_a) | (pr[:, 1] < 0) | (pr[:, 1] >= n_b))[0][0])
+        raise ValueError(f"{name}: pair {k} {tuple(int(v) for v in pr[k])} names no row of the {n_a} x {n_b} tables")
+    it = np.asarray(items)
+    if it.ndim != 2 or it.shape[1] != GR_OVERLAP_ITEM_INTS or it.dtype.kind not in "iu":
+        raise ValueError(f"{name}: work items must be (n, {GR_OVERLAP_ITEM_INTS}) integers, got {it.shape} {it.dtype}")
+    if it.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name}: {it.shape[0]} work items, not below 2^31")
+    if not it.shape[0]:
+        return
+    p, a0, na, b0, nb = it.astype(np.int64).T
+    bad = (p < 0) | (p >= pr.shape[0]) | (na < 1) | (na > GR_OVERLAP_TILE_A) | (nb < 1) | (nb > GR_OVERLAP_TILE_B)
+    bad[1:] |= p[1:] < np.maximum.accumulate(p)[:-1]
+    ok = np.nonzero(~bad)[0]
+    ra, rb = _row_slot_ranges(offsets_a, rows_a, n_a)[pr[p[ok], 0]], _row_slot_ranges(offsets_b, rows_b, n_b)[pr[p[ok], 1]]
+    bad[ok] = (a0[ok] < ra[:, 0]) | (a0[ok] + na[ok] > ra[:, 1]) | (b0[ok] < rb[:, 0]) | (b0[ok] + nb[ok] > rb[:, 1])
+    if np.any(bad):
+        k = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"{name}: work item {k} {tuple(int(v) for v in it[k])} names no pair, a pair below one in front of it, or no tile "
+                         f"of at most {GR_OVERLAP_TILE_A} x {GR_OVERLAP_TILE_B} edge slots inside the pair's rows")
+
+
+class PolygonOverlap:
+    """Two ring tables on the device, behind one origin (gr_polygon_box_pairs_count / _fill, gr_polygon_overlap_areas; DESIGN.md 8o,
+    A1-A9).  Made by `HipRaster.polygon_overlap`, which checks the tables (`check_overlap_tables`) and uploads them once."""
+
+    def __init__(self, backend: "HipRaster", table_a, table_b):
+        host = [[_host_array(x) for x in table] for table in (table_a, table_b)]
+        check_overlap_tables(*host)
+        self.backend = backend
+        self.host = host                      # the host copies the item check walks (offsets and rows)
+        self._a = backend._ring_table(table_a[0], table_a[1], table_a[2], table_a[4], table_a[3])
+        self._b = backend._ring_table(table_b[0], table_b[1], table_b[2], table_b[4], table_b[3])
+
+    def pairs(self):
+        """(n, 2) int32 tensor: the candidate pairs (row of a, row of b) of rule A2, ascending by (a, b).  Reads the count back."""
+        torch = _torch()
+        hip = self.backend
+        box_a, box_b, Pa, Pb = self._a[3], self._b[3], self._a[7], self._b[7]
+        offsets = hip._empty((Pa + 1,), torch.int64)
+        hip._call("gr_polygon_box_pairs_count", _ptr(box_a if Pa else None), Pa, _ptr(box_b if Pb else None), Pb, offsets.data_ptr(),
+                  hip._stream())
+        n = int(offsets[Pa].item())
+        if n >= 2 ** 31:
+            raise ValueError(f"gr_polygon_box_pairs_fill: {n} candidate pairs, not below 2^31: split a table")
+        pairs = hip._empty((n, 2), torch.int32)
+        hip._call("gr_polygon_box_pairs_fill", _ptr(box_a if Pa else None), Pa, _ptr(box_b if Pb else None), Pb, offsets.data_ptr(),
+                  _ptr(pairs if n else None), n, hip._stream())
+        return pairs
+
+    def areas(self, pairs, items):
+        """pairs (n, 2) int32 (row of a, row of b), items (m, GR_OVERLAP_ITEM_INTS) int32 of `utils.geometric.overlap_work_items`
+        for those pairs -> (area (n,) float64 tensor in grid steps squared, area_abs (n,) float64 tensor: the sum of the magnitudes
+        of the terms, the scale of the bound of A6; stats (GR_OVERLAP_STAT_WORDS,) int64 tensor).  Pairs and items are validated on
+        the host first (`check_overlap_items`: ValueError).  Only enqueues."""
+        torch = _torch()
+        hip = self.backend
+        (_, off_a, rp_a, _, _), (_, off_b, rp_b, _, _) = self.host
+        check_overlap_items(_host_array(pairs), _host_array(items), off_a, rp_a, self._a[7], off_b, rp_b, self._b[7])
+        pr_t = hip._shaped(pairs, torch.int32, ("n", 2), "pairs")
+        it_t = hip._shaped(items, torch.int32, ("m", GR_OVERLAP_ITEM_INTS), "work items")
+        n = int(pr_t.shape[0])
+        area, area_abs = hip._empty((n,), torch.float64), hip._empty((n,), torch.float64)
+        stats = hip._stats(GR_OVERLAP_STAT_WORDS)
+        hip._call("gr_polygon_overlap_areas", *self._table_args(self._a), *self._table_args(self._b), _ptr(pr_t if n else None), n,
+                  _ptr(it_t if it_t.numel() else None), int(it_t.shape[0]), _ptr(area if n else None), _ptr(area_abs if n else None),
+                  stats.data_ptr(), hip._stream())
+        return area, area_abs, stats
+
+    @staticmethod
+    def _table_args(t):
+        rv_t, off_t, rp_t, box_t, rh_t, N, R, P = t
+        return (_ptr(rv_t if N else None), N, off_t.data_ptr(), _ptr(rp_t if R else None), _ptr(rh_t if R else None), R,
+                _ptr(box_t if P else None), P)
 
 
 def polygon_pair_bounds(boxes, poly_offsets, n_faces: int) -> np.ndarray:
@@ -1656,6 +1816,12 @@ class HipRaster:
         `values` (n_polygons,) integers in [0, 255], or None for a burner of row planes only: the tables are checked
         (`check_burn_tables`: ValueError naming gr_burn_polygons) and uploaded once; every `.window` call burns one window."""
         return PolygonBurner(self, ring_vertices, ring_offsets, ring_polygon, n_polygons, values)
+
+    def polygon_overlap(self, table_a, table_b) -> "PolygonOverlap":
+        """A `PolygonOverlap` over two ring tables behind ONE origin (`utils.geometric.snap_polygon_pair`), each the five arrays of
+        `PlanarPolygons.snapped`: the tables are checked (`check_overlap_tables`: ValueError naming gr_polygon_overlap_areas) and
+        uploaded once; `.pairs()` lists the candidate pairs, `.areas(pairs, items)` gives the overlap area of every pair."""
+        return PolygonOverlap(self, table_a, table_b)
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):

@@ -31,10 +31,14 @@
 //   decimate.hip     mesh decimation by vertex clustering: cell keys and centre distances (k_decim_keys), cell heads (k_decim_heads),
 //                    representatives (k_decim_scatter_rep), remapped faces (k_decim_faces), first face per triple (k_decim_face_flags)
 //                    + radix sorts and scans; compacts with k_submesh_write; no mesh needed
+//   overlap.hip      polygon-on-polygon overlap areas: candidate pairs of two box tables, count then fill (k_overlap_pairs_count,
+//                    k_overlap_pairs_fill + a scan), the area of every pair as a signed sum over edge pairs (k_overlap_areas: one work item per
+//                    workgroup, the a-tile as edge records in LDS), its partials added in item order (k_overlap_item_keys + a running
+//                    maximum, k_overlap_reduce), table statistics (k_overlap_table_stats); float64, no atomics on it; no mesh needed
 //   cub_steps.hpp    the hipcub calls of the stage calls, each declared once against the call's Plan: SortPairs, SortKeys, ExclusiveSum,
 //                    InclusiveMax, RunLengthEncode (size query on construction, typed pointers on run)
 //   compact_dev.hpp  FlagScan, compact_begin, compact_write, k_submesh_write: the scans and the write kernel of polygons.hip's sub-mesh and of decimate.hip
-//   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip, crs.hip and ortho.hip: orient, ring_span, edge_crossing (THE even-odd rule of
+//   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip, crs.hip, ortho.hip and overlap.hip: orient, ring_span, edge_crossing (THE even-odd rule of
 //                    k_polygon_weights, k_face_polygon_index and k_points_in_region), load_face, stat_add / stat_add_u32 / stat_max / stat_count
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

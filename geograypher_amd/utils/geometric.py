@@ -916,3 +916,51 @@ def rectangle_meets_rows(edges, edge_row, rectangle) -> bool:
             row = int(edge_row[k])
             inside[row] = not inside.get(row, False)
     return any(inside.values())
+
+
+# -- polygon-on-polygon overlap areas --------------------------------------------------------------------------
+OVERLAP_TILE = (256, 4096)   # GR_OVERLAP_TILE_A, GR_OVERLAP_TILE_B: the edge slots of row a and of row b in one work item
+
+
+def snap_polygon_pair(polygons_a, polygons_b):
+    """Rule A1: (table_a, table_b, origin) -- the snapped ring tables (`PlanarPolygons.snapped`) of two `PlanarPolygons`, both on the
+    1e-6 m grid behind ONE integer origin, the middle of their joint bounds, as `snap_with_polygons` does for points and polygons.
+    ValueError (from `snapped`) when a vertex lies more than 2^40 grid steps from it."""
+    bounds = [b for b in (polygons_a.bounds_snapped(), polygons_b.bounds_snapped()) if b is not None]
+    if bounds:
+        lo, hi = np.min([b[0] for b in bounds], axis=0), np.max([b[1] for b in bounds], axis=0)
+        origin = lo + (hi - lo) // 2
+    else:
+        origin = np.zeros(2, dtype=np.int64)
+    return polygons_a.snapped(origin), polygons_b.snapped(origin), origin
+
+
+def overlap_work_items(offsets_a, rows_a, offsets_b, rows_b, pairs, tile=OVERLAP_TILE) -> np.ndarray:
+    """The work items `PolygonOverlap.areas` takes (rule A8), by count-then-fill: the ring offsets (R + 1,) and the non-decreasing
+    ring rows (R,) of both tables, pairs (n, 2) rows (a, b) -> (m, 5) int32 rows (pair index, first edge slot and slots of row a,
+    first slot and slots of row b).  The edge slots of a row are its ring vertices, consecutive because its rings are; they are
+    cut into tiles of at most tile = (slots of a <= 256, slots of b <= 4096), a tile may start or end inside a ring, and a pair
+    gets one item per (tile of a, tile of b), the tiles of b running fastest.  Pairs are listed in their own order; a pair with a
+    row without vertices has no item (its area is 0)."""
+    ta, tb = int(tile[0]), int(tile[1])
+    if not (1 <= ta <= OVERLAP_TILE[0] and 1 <= tb <= OVERLAP_TILE[1]):
+        raise ValueError(f"a tile is at most {OVERLAP_TILE[0]} x {OVERLAP_TILE[1]} edge slots, got {ta} x {tb}")
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+
+    def spans(offsets, rows, which):
+        off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        rp = np.asarray(rows, dtype=np.int64).reshape(-1)
+        return off[np.searchsorted(rp, which, "left")], off[np.searchsorted(rp, which, "right")]
+
+    a_lo, a_hi = spans(offsets_a, rows_a, pairs[:, 0])
+    b_lo, b_hi = spans(offsets_b, rows_b, pairs[:, 1])
+    n_a, n_b = -(-(a_hi - a_lo) // ta), -(-(b_hi - b_lo) // tb)
+    n = n_a * n_b
+    owner = np.repeat(np.arange(len(pairs)), n)
+    if not len(owner):
+        return np.zeros((0, 5), dtype=np.int32)
+    k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+    ka, kb = k // n_b[owner], k % n_b[owner]
+    a0, b0 = a_lo[owner] + ka * ta, b_lo[owner] + kb * tb
+    items = np.stack([owner, a0, np.minimum(ta, a_hi[owner] - a0), b0, np.minimum(tb, b_hi[owner] - b0)], axis=1)
+    return np.ascontiguousarray(items, dtype=np.int32)

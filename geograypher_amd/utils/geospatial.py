@@ -345,3 +345,122 @@ def burn_polygons(polygons, values, like, fill: int = 255, backend=None, max_dev
         rows_t, out_t, _stats = burner.window(*window, burn_work_items(boxes, ranges, window), fill=int(fill), want_values=not rows)
         result[row0:row0 + n] = _to_host(rows_t if rows else out_t)
     return result
+
+
+# -- polygon-on-polygon overlap areas (reference: utils/geospatial.py:221-329, gpd.overlay) ------------------------
+# A6: the device's area of a pair lies within OVERLAP_BOUND_K 2^-53 area_abs of the exact one.  K = 4 x the largest ratio the numpy
+# restatement of A5 reached over every pair of every scene of the tests, rounded up to a power of two (tests/overlap_standin.py
+# holds the measurement and the largest ratio the device reached).
+OVERLAP_BOUND_K = 32.0
+GRID_STEP_AREA = 1e-12     # m^2 of one square grid step (SNAP_GRID_METERS squared)
+
+
+def overlap_bound(area_abs):
+    """A6: the error bound of a pair's area from its area_abs, in the same unit."""
+    return OVERLAP_BOUND_K * 2.0 ** -53 * np.asarray(area_abs, dtype=np.float64)
+
+
+def polygon_source(source):
+    """A `.geojson` path or a (PlanarPolygons, {column: values}) pair -> (PlanarPolygons, properties): the convention of
+    `get_values_for_faces_from_vector`.  A bare PlanarPolygons has no properties."""
+    from geograypher_amd.utils.geometric import PlanarPolygons
+
+    if isinstance(source, PlanarPolygons):
+        return source, {}
+    if isinstance(source, tuple) and len(source) == 2 and isinstance(source[0], PlanarPolygons):
+        return source[0], {k: np.asarray(v) for k, v in dict(source[1]).items()}
+    if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__"):
+        if not str(source).lower().endswith((".geojson", ".json")):
+            raise NotImplementedError(f"{source}: polygon files are read as .geojson only")
+        return PlanarPolygons.from_geojson(source)
+    raise TypeError("a polygon source is a .geojson path or a (PlanarPolygons, {column: values}) pair")
+
+
+def _same_planar_CRS(a, b, what: str):
+    if a.epsg is not None and b.epsg is not None and int(a.epsg) != int(b.epsg):
+        raise ValueError(f"{what}: the two sources are in EPSG:{a.epsg} and EPSG:{b.epsg}; polygons are not reprojected here, "
+                         "bring both into one planar CRS first")
+
+
+def overlap_pairs(A, B, backend=None):
+    """The candidate pairs of two `PlanarPolygons` and their overlap on the device (`HipRaster.polygon_overlap`): (pairs (n, 2) int64
+    ascending by (row of A, row of B), area (n,), area_abs (n,) float64 in m^2).  The table with the longer rows goes to the lane
+    side of the kernel (table b of the call) and the answer is transposed back."""
+    from geograypher_amd.utils.geometric import overlap_work_items, snap_polygon_pair
+
+    backend = backend if backend is not None else _default_backend()
+    table_a, table_b, _ = snap_polygon_pair(A, B)
+    mean_row = lambda t, P: len(t[0]) / max(P, 1)   # noqa: E731
+    swap = mean_row(table_a, len(A)) > mean_row(table_b, len(B))
+    if swap:
+        table_a, table_b = table_b, table_a
+    overlap = backend.polygon_overlap(table_a, table_b)
+    pairs = _to_host(overlap.pairs()).astype(np.int64).reshape(-1, 2)
+    items = overlap_work_items(table_a[1], table_a[2], table_b[1], table_b[2], pairs)
+    area, area_abs, _stats = overlap.areas(pairs.astype(np.int32), items)
+    area, area_abs = _to_host(area).astype(np.float64) * GRID_STEP_AREA, _to_host(area_abs).astype(np.float64) * GRID_STEP_AREA
+    if swap:
+        pairs = pairs[:, ::-1]
+        order = np.lexsort((pairs[:, 1], pairs[:, 0]))
+        pairs, area, area_abs = pairs[order], area[order], area_abs[order]
+    return np.ascontiguousarray(pairs), area, area_abs
+
+
+def polygon_overlap_areas(A, B, backend=None):
+    """area(row a of A n row b of B) for every pair of rows, on the device (gr_polygon_overlap_areas; rules A1-A9 of DESIGN.md 8o)
+    -> a scipy CSR matrix (n_A, n_B) in m^2.  A, B: `PlanarPolygons` in one planar CRS (a differing `.epsg` is a ValueError).  An
+    entry whose area does not exceed its bound (`overlap_bound` of its area_abs: rounding alone could have produced it) is dropped,
+    so rows that only touch, or lie in each other's holes, have no entry."""
+    import scipy.sparse
+
+    _same_planar_CRS(A, B, "polygon_overlap_areas")
+    pairs, area, area_abs = overlap_pairs(A, B, backend)
+    keep = area > overlap_bound(area_abs)
+    return scipy.sparse.csr_matrix((area[keep], (pairs[keep, 0], pairs[keep, 1])), shape=(len(A), len(B)))
+
+
+def get_overlap_vector(unlabeled, classes, class_column: str, normalize: bool = False, backend=None):
+    """For every unlabeled polygon its overlap area with every class (reference: utils/geospatial.py:221-329, which goes through
+    gpd.overlay) -> (counts_matrix (n_valid, n_classes) float64 in m^2, intersection_IDs (n_valid,) int64, unique_class_names: the
+    sorted distinct values of `class_column`).
+
+    unlabeled, classes: a `.geojson` path or a (PlanarPolygons, {column: values}) pair.  counts_matrix[k][c] is the sum of
+    area(unlabeled row intersection_IDs[k] n class row) over the class rows of class c -- what the reference's overlay of the
+    UNDISSOLVED class rows sums; class rows of one class that overlap each other count twice there and here.  intersection_IDs
+    are the unlabeled rows with a pair area above its bound (`polygon_overlap_areas`).  `normalize` divides every row by its sum.
+    Differences from the reference: its simplify(0.01) of both sources is not applied; rows that only touch do not count as
+    intersecting (GEOS' intersects counts them, with rows of zeros); nothing is reprojected: both sources share one planar CRS,
+    and a differing `.epsg` is a ValueError."""
+    A, _ = polygon_source(unlabeled)
+    B, properties = polygon_source(classes)
+    if class_column not in properties:
+        raise ValueError(f"Class column `{class_column}` not in {sorted(properties)}")
+    _same_planar_CRS(A, B, "get_overlap_vector")
+    names = np.asarray(properties[class_column]).tolist()
+    if len(names) != len(B):
+        raise ValueError(f"{len(B)} class rows need as many values of {class_column!r}, got {len(names)}")
+    unique_class_names = sorted(set(names))
+    class_of_row = np.array([unique_class_names.index(v) for v in names], dtype=np.int64)
+    pairs, area, area_abs = overlap_pairs(A, B, backend)
+    keep = area > overlap_bound(area_abs)
+    pairs, area = pairs[keep], area[keep]
+    intersection_IDs = np.unique(pairs[:, 0])
+    counts_matrix = np.zeros((len(intersection_IDs), len(unique_class_names)), dtype=np.float64)
+    np.add.at(counts_matrix, (np.searchsorted(intersection_IDs, pairs[:, 0]), class_of_row[pairs[:, 1]]), area)
+    if normalize:
+        counts_matrix = counts_matrix / np.sum(counts_matrix, axis=1, keepdims=True)
+    return counts_matrix, intersection_IDs, unique_class_names
+
+
+def row_areas(polygons) -> np.ndarray:
+    """(P,) float64 m^2: the area of every row of a `PlanarPolygons` on the 1e-6 m grid, exteriors minus holes, from the exact
+    integer shoelace sums of its snapped rings."""
+    from geograypher_amd.utils.geometric import _signed_area2_exact
+
+    bounds = polygons.bounds_snapped()
+    rv, off, rp, rh, _ = polygons.snapped((0, 0) if bounds is None else bounds[0] + (bounds[1] - bounds[0]) // 2)
+    twice = [0] * len(polygons)
+    for r in range(len(rp)):
+        a2 = _signed_area2_exact(rv[off[r]:off[r + 1]])
+        twice[int(rp[r])] += -a2 if rh[r] else a2
+    return np.array([t / 2 for t in twice], dtype=np.float64) * GRID_STEP_AREA

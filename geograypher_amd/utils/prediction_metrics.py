@@ -1,7 +1,9 @@
 """Scores of the orthomosaic baseline: the confusion matrix of a class raster against ground-truth polygons, and the metrics of a
 confusion matrix (reference: geograypher/utils/prediction_metrics.py).  The cells under every truth polygon are counted on the
 device (`utils.geospatial.zonal_class_counts`, gr_zonal_class_counts) in place of rasterstats.zonal_stats;
-the confusion matrix of two label lists is plain numpy in place of scikit-learn.  Not carried over: the plots."""
+the confusion matrix of two label lists is plain numpy in place of scikit-learn.  Two class VECTOR maps are scored by area with the
+polygon-on-polygon overlap of the device (`cf_from_vector_vector`, gr_polygon_overlap_areas) in place of
+geopandas' dissolve and shapely's intersection.  Not carried over: the plots."""
 import typing
 from pathlib import Path
 
@@ -17,6 +19,59 @@ def check_if_raster(filename) -> bool:
     if extension in (".geojson", ".shp"):
         return False
     raise ValueError("Unknown extension")
+
+
+def cf_from_vector_vector(predicted, true, column_name: str, column_values=None, include_unlabeled_class: bool = True, backend=None):
+    """The confusion matrix of two class maps by area (reference: utils/prediction_metrics.py:95-144, which dissolves both maps by
+    class and intersects the multipolygons with shapely) -> (confusion_matrix float64 in m^2, column_values).
+
+    predicted, true: a `.geojson` path or a (PlanarPolygons, {column: values}) pair, both with the property `column_name`, in one
+    planar CRS (a differing `.epsg` is a ValueError; nothing is reprojected).  column_values=None: the sorted truth classes.
+    cf[i][j] = area(true class column_values[i] n predicted class column_values[j]), the pair areas of the device call
+    (`utils.geospatial.overlap_pairs`) summed over the rows of the two classes; a class that the prediction (or
+    the truth) lacks gives a column (a row) of zeros, where the reference fails.  With `include_unlabeled_class` a last column
+    holds the class's own area minus its row sum, and a last row of zeros, as in the reference.
+    The reference dissolves each class first; summing rows equals that iff the rows of one class do not overlap each other.  That
+    is checked with the same device call, each map against itself, on the pairs a < a' of one class: a self-overlap above its
+    bound is a ValueError that says to dissolve the map."""
+    from geograypher_amd.utils.geospatial import (_same_planar_CRS, _default_backend, overlap_bound, overlap_pairs, polygon_source,
+                                                  row_areas)
+
+    (P, p_props), (T, t_props) = polygon_source(predicted), polygon_source(true)
+    for what, props in (("predicted", p_props), ("true", t_props)):
+        if column_name not in props:
+            raise ValueError(f"the {what} map has no property {column_name!r}")
+    _same_planar_CRS(P, T, "cf_from_vector_vector")
+    p_names, t_names = np.asarray(p_props[column_name]).tolist(), np.asarray(t_props[column_name]).tolist()
+    if column_values is None:
+        column_values = sorted(set(t_names))
+    column_values = list(column_values)
+    index = {v: k for k, v in enumerate(column_values)}
+    p_class = np.array([index.get(v, -1) for v in p_names], dtype=np.int64)
+    t_class = np.array([index.get(v, -1) for v in t_names], dtype=np.int64)
+    backend = backend if backend is not None else _default_backend()
+    for what, polygons, names in (("predicted", P, p_names), ("true", T, t_names)):
+        pairs, area, area_abs = overlap_pairs(polygons, polygons, backend)
+        distinct = list(dict.fromkeys(names))
+        classes = np.array([distinct.index(v) for v in names], dtype=np.int64)
+        same =(pairs[:, 0] < pairs[:, 1]) & (classes[pairs[:, 0]] == classes[pairs[:, 1]]) & (area > overlap_bound(area_abs))
+        if np.any(same):
+            a, b = (int(v) for v in pairs[np.nonzero(same)[0][0]])
+            raise ValueError(f"rows {a} and {b} of the {what} map are both {names[a]!r} and overlap by {area[np.nonzero(same)[0][0]]:.6g} m^2: "
+                             f"dissolve the map by {column_name!r} first, so that the rows of a class do not overlap")
+    n = len(column_values)
+    confusion_matrix = np.zeros((n, n), dtype=np.float64)
+    pairs, area, area_abs = overlap_pairs(T, P, backend)
+    keep = (area > overlap_bound(area_abs)) & (t_class[pairs[:, 0]] >= 0) & (p_class[pairs[:, 1]] >= 0)
+    np.add.at(confusion_matrix, (t_class[pairs[keep, 0]], p_class[pairs[keep, 1]]), area[keep])
+    if include_unlabeled_class:
+        total_areas = np.zeros(n, dtype=np.float64)
+        np.add.at(total_areas, t_class[t_class >= 0], row_areas(T)[t_class >= 0])
+        with_unlabeled = np.zeros((n + 1, n + 1), dtype=np.float64)
+        with_unlabeled[:-1, :-1] = confusion_matrix
+        with_unlabeled[:-1, -1] = total_areas - confusion_matrix.sum(axis=1)
+        confusion_matrix = with_unlabeled
+    return confusion_matrix, column_values
 
 
 def compute_confusion_matrix_from_geospatial(
@@ -47,7 +102,8 @@ def compute_confusion_matrix_from_geospatial(
     if vis or vis_raster_file is not None or vis_savefile is not None:
         raise NotImplementedError("vis: the plots need matplotlib, which is outside the device path")
     if not isinstance(prediction_file, PlanarRaster) and not check_if_raster(prediction_file):
-        raise NotImplementedError("a vector prediction needs polygon intersections, which are not available: predict a class raster")
+        raise NotImplementedError("a vector prediction is scored against vector truth by cf_from_vector_vector: this function "
+                                  "takes a class raster")
     if check_if_raster(groundtruth_file):
         raise NotImplementedError("a raster ground truth is not supported (nor is it by the reference)")
     if Path(groundtruth_file).suffix.lower() != ".geojson":

@@ -769,6 +769,25 @@ enum {
 };
 #include "geograster_burn.h"
 
+/* Polygon-on-polygon overlap areas (geograster_overlap.h): the words of the statistics block, the
+ * integers of a work item and the largest tiles an item may name. */
+enum {
+  GR_OVERLAP_STAT_PAIRS = 0,          /* pairs handed in                                                      */
+  GR_OVERLAP_STAT_ITEMS = 1,          /* work items that ran                                                  */
+  GR_OVERLAP_STAT_EDGE_PAIRS = 2,     /* edge pairs that took part: a common x-range of positive width (A3)   */
+  GR_OVERLAP_STAT_VERTICAL = 3,       /* vertical edges of both tables, in rings of 3 or more vertices (A4)   */
+  GR_OVERLAP_STAT_RINGS_IGNORED = 4,  /* rings of fewer than 3 vertices, both tables                          */
+  GR_OVERLAP_STAT_LARGEST_RING = 5,   /* the vertices of the largest ring of either table                     */
+  GR_OVERLAP_STAT_BAD_ITEMS = 6,      /* work items skipped whole (A8)                                        */
+  GR_OVERLAP_STAT_WORDS = 8
+};
+enum {
+  GR_OVERLAP_ITEM_INTS = 5,           /* pair, first edge slot and slots of row a, first slot and slots of row b */
+  GR_OVERLAP_TILE_A = 256,            /* edge slots of row a in one item: the records of a workgroup's LDS    */
+  GR_OVERLAP_TILE_B = 4096            /* edge slots of row b in one item: 16 per lane                         */
+};
+#include "geograster_overlap.h"
+
 #ifdef __cplusplus
 }
 #endif
