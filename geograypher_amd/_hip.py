@@ -113,6 +113,27 @@ GR_SETCOVER_STAT_PRUNED = 3
 GR_SETCOVER_STAT_BATCHES = 4
 GR_SETCOVER_STAT_LDS_HISTOGRAM = 5
 GR_SETCOVER_STAT_WORDS = 8
+# gr_louvain_communities: flags, limits, stats words
+GR_COMM_FORCE_GROUP = 1
+GR_COMM_FORCE_KEY = 2
+GR_COMM_MAX_VERTICES = 1 << 23
+GR_COMM_MAX_EDGES = (1 << 30) - (1 << 22)
+GR_COMM_MAX_LEVELS = 64
+GR_COMM_LDS_ROW = 1024
+GR_COMM_CAP_SWEEPS = 1
+GR_COMM_CAP_LEVELS = 2
+GR_COMM_STAT_LEVELS = 0
+GR_COMM_STAT_LEVELS_RUN = 1
+GR_COMM_STAT_CAPS = 2
+GR_COMM_STAT_ROWS_WAVE = 3
+GR_COMM_STAT_ROWS_GROUP = 4
+GR_COMM_STAT_ROWS_KEY = 5
+GR_COMM_STAT_BAD_EDGES = 6
+GR_COMM_STAT_COMMUNITIES = 7
+GR_COMM_STAT_M2 = 8
+GR_COMM_STAT_SWEEPS = 16
+GR_COMM_STAT_MOVES = 80
+GR_COMM_STAT_WORDS = 144
 # gr_reproject_points: coordinate kinds, stats words, the launch's workgroup cap
 GR_CRS_ECEF = 0
 GR_CRS_GEOGRAPHIC = 1
@@ -308,6 +329,12 @@ _OVERLAP_SIGNATURES = {
     "gr_polygon_overlap_areas": [_vp, *_OVERLAP_TABLE, *_OVERLAP_TABLE, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
 }
 OVERLAP_SYMBOLS = tuple(_OVERLAP_SIGNATURES)
+# ... and the calls of include/geograster_communities.h (communities of the ray graph), under the same contract.
+_COMMUNITIES_SIGNATURES = {
+    "gr_louvain_communities": [_vp, _vp, _vp, _vp, _i64, _i64, _f64, ctypes.c_int32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gr_community_points": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
+}
+COMMUNITIES_SYMBOLS = tuple(_COMMUNITIES_SIGNATURES)
 
 
 def library_path() -> Path:
@@ -331,7 +358,7 @@ def load_library() -> ctypes.CDLL:
     _torch()
     lib = ctypes.CDLL(str(_LIB_PATH))
     for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES, **_BURN_SIGNATURES,
-                           **_OVERLAP_SIGNATURES}.items():
+                           **_OVERLAP_SIGNATURES, **_COMMUNITIES_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -792,6 +819,62 @@ class PolygonOverlap:
         rv_t, off_t, rp_t, box_t, rh_t, N, R, P = t
         return (_ptr(rv_t if N else None), N, off_t.data_ptr(), _ptr(rp_t if R else None), _ptr(rh_t if R else None), R,
                 _ptr(box_t if P else None), P)
+
+
+class RayCommunities:
+    """The two community calls of the multiview-detection workflow on one backend (include/geograster_communities.h; DESIGN.md
+    section 8p), behind `HipRaster.louvain_communities` and `HipRaster.community_points`, which document them.  Every output is
+    allocated through the backend (`_empty`, `_stats`)."""
+
+    def __init__(self, backend: "HipRaster"):
+        self.backend = backend
+
+    def louvain(self, i, j, q, n: int, resolution: float, max_sweeps: int, force_path):
+        b = self.backend
+        torch = _torch()
+        n = int(n)
+        if force_path not in b._COMM_FORCE:
+            raise ValueError(f"force_path must be None, 'group' or 'key', got {force_path!r}")
+        if n < 0 or n > GR_COMM_MAX_VERTICES:
+            raise ValueError(f"n must be in [0, {GR_COMM_MAX_VERTICES}], got {n}")
+        i_t = b._edge_index(i, n, "edge i")
+        E = int(i_t.shape[0])
+        j_t = b._shaped(b._edge_index(j, n, "edge j"), torch.int32, (E,), "edge j (one per edge)")
+        q_t = b._shaped(q, torch.int64, (E,), "edge weights (one per edge)")
+        community = b._empty((max(n, 1),), torch.int32)
+        size = b._empty((max(n, 1),), torch.int32)
+        c_in, c_tot = b._empty((max(n, 1),), torch.int64), b._empty((max(n, 1),), torch.int64)
+        stats = b._stats(GR_COMM_STAT_WORDS, zeroed=True)
+        rc = b._rc("gr_louvain_communities", _ptr(i_t if E else None), _ptr(j_t if E else None), _ptr(q_t if E else None), E, n,
+                      float(resolution), int(max_sweeps), b._COMM_FORCE[force_path], community.data_ptr(), size.data_ptr(),
+                      c_in.data_ptr(), c_tot.data_ptr(), stats.data_ptr(), b._stream())
+        st = [int(x) for x in stats.cpu().tolist()]
+        b.last_bad_edges = st[GR_COMM_STAT_BAD_EDGES]
+        if rc == GR_EINDEX:   # the input is wrong, not a position the caller asked for
+            raise ValueError(f"gr_louvain_communities: {b.last_bad_edges} bad edges: " + b.lib.gr_last_error(b._ctx).decode("utf-8", "replace"))
+        b._check(rc, "gr_louvain_communities")
+        m, run = st[GR_COMM_STAT_COMMUNITIES], st[GR_COMM_STAT_LEVELS_RUN]
+        record = {"community": community[:n].cpu().numpy(), "size": size[:m].cpu().numpy(), "in": c_in[:m].cpu().numpy(),
+                  "tot": c_tot[:m].cpu().numpy()}
+        record.update(n_communities=m, M2=st[GR_COMM_STAT_M2], levels=st[GR_COMM_STAT_LEVELS],
+                      sweeps=st[GR_COMM_STAT_SWEEPS:GR_COMM_STAT_SWEEPS + run], moves=st[GR_COMM_STAT_MOVES:GR_COMM_STAT_MOVES + run],
+                      caps_hit=st[GR_COMM_STAT_CAPS], bad_edges=st[GR_COMM_STAT_BAD_EDGES],
+                      rows_per_path=[st[GR_COMM_STAT_ROWS_WAVE], st[GR_COMM_STAT_ROWS_GROUP], st[GR_COMM_STAT_ROWS_KEY]])
+        return record
+
+    def points(self, starts, ends, community, n_communities: int):
+        b = self.backend
+        torch = _torch()
+        s_t = b._shaped(starts, torch.float64, ("N", 3), "starts")
+        e_t = b._shaped(ends, torch.float64, s_t.shape, "ends")
+        n, m = int(s_t.shape[0]), int(n_communities)
+        c_t = b._shaped(b._edge_index(community, n, "community"), torch.int32, (n,), "community (one per ray)")
+        if m < 0 or m > n:
+            raise ValueError(f"n_communities must be in [0, {n}], got {m}")
+        points = b._empty((m, 3), torch.float64)
+        b._call("gr_community_points", _ptr(s_t if n else None), _ptr(e_t if n else None), _ptr(c_t if n else None), n, m,
+                   _ptr(points if m else None), b._stream())
+        return points
 
 
 def polygon_pair_bounds(boxes, poly_offsets, n_faces: int) -> np.ndarray:
@@ -1353,6 +1436,40 @@ class HipRaster:
         self._call("gr_rays_clip", o_t.data_ptr(), d_t.data_ptr(), n, p_t.data_ptr(), int(p_t.shape[0]), f_t.data_ptr(),
                    int(f_t.shape[0]), hit.data_ptr(), t.data_ptr(), pts.data_ptr(), self._stream())
         return hit.to(torch.bool), t, pts
+
+    # -- multiview detections: communities of the ray graph --------------------------------------------------------
+    COMM_MAX_VERTICES = GR_COMM_MAX_VERTICES   # n limit of gr_louvain_communities
+    COMM_LDS_ROW = GR_COMM_LDS_ROW             # entries of the longest row its workgroup path takes (csrc/communities.hip)
+    _COMM_FORCE = {None: 0, "group": GR_COMM_FORCE_GROUP, "key": GR_COMM_FORCE_KEY}
+
+    def _edge_index(self, array, n: int, name: str):
+        """An edge index array -> (E,) int32 on this device.  Wider integers are clamped to [-1, n] first, so that a value the
+        cast would wrap stays outside [0, n) and is found by the device check."""
+        torch = _torch()
+        if not isinstance(array, torch.Tensor):
+            array = torch.as_tensor(np.ascontiguousarray(array))
+        if array.dtype != torch.int32:
+            if array.dtype.is_floating_point or array.dtype == torch.bool:
+                raise ValueError(f"{name} must be integers, got {array.dtype}")
+            array = array.to(self.device).clamp(-1, n)
+        return self._shaped(array, torch.int32, ("E",), name)
+
+    def louvain_communities(self, i, j, q, n: int, resolution: float = 1.0, max_sweeps: int = 32, *, force_path=None):
+        """gr_louvain_communities: the undirected edges i, j (E,) int, q (E,) int64 weights in
+        [1, 2^31 - 1] of a graph of n vertices; numpy or device tensors, not modified -> the record {"community" (n,) int32, -1
+        for a vertex without an edge; "size" (M,) int32, "in", "tot" (M,) int64 per community, by falling size, ties by the
+        lowest member; "n_communities" M, "M2", "levels", "sweeps", "moves" (lists, one entry per level that ran: the last one
+        moved nothing unless the level cap was hit), "caps_hit" (the OR of GR_COMM_CAP_*), "rows_per_path" [wave, workgroup,
+        key], "bad_edges"} as numpy arrays and ints.  `force_path`: None, "group" or "key" sends every row the path can take
+        through it (tests: same results).  A bad edge (i == j, an index outside [0, n), a weight outside the range) is found on
+        the device and is a ValueError that names their number (`last_bad_edges`).  Waits for the device."""
+        return RayCommunities(self).louvain(i, j, q, n, resolution, max_sweeps, force_path)
+
+    def community_points(self, starts, ends, community, n_communities: int):
+        """gr_community_points (L14): starts, ends (N, 3) float64, community (N,) int, -1 for a ray of no community -> (M, 3)
+        float64 tensor: per community the mean of the closest points over all ordered pairs of distinct member segments (the
+        reference's `intersection_average`), NaN for a community of one segment.  Two runs are bit-equal.  Waits for the device."""
+        return RayCommunities(self).points(starts, ends, community, n_communities)
 
     # -- covering meshes: bounds of the points, extremes per grid cell ---------------------------------------------
     COVER_MAX_N = 1024   # grid points a side of gr_cover_grid

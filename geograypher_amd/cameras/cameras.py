@@ -624,16 +624,23 @@ class PhotogrammetryCameraSet:
     def triangulate_detections(self, detector, ray_length_meters: float = 1e3, boundaries=None,
                                limit_ray_length_meters: Optional[float] = None, limit_angle_from_vert: Optional[float] = None,
                                similarity_threshold_meters: float = 0.1, transform=None, louvain_resolution: float = 1.0,
-                               out_dir: Optional[PATH_TYPE] = None, seed=None, backend=None) -> np.ndarray:
+                               out_dir: Optional[PATH_TYPE] = None, seed=None, backend=None,
+                               community_method: str = "networkx") -> np.ndarray:
         """Per-image detections -> 3D locations (cameras.py:1275-1398): rays through the detection centres
         (`calc_line_segments`), the graph of rays from different images that pass within `similarity_threshold_meters` of each
         other (`calc_graph_weights`: the ray-pair kernel on the device), Louvain communities and one point per community
         (`calc_communities`).  Lengths in metres are scaled to local units by the local -> EPSG:4978 transform.  With `out_dir`
         each stage saves its file there (`line_segments.npz`, `edge_weights.json`, `communities.npz`) and a stage whose file
         exists is not computed again.  Returns (M, 3): lat / lon / alt when a transform and pyproj are at hand, local
-        coordinates otherwise.  Beyond the reference's keywords: `seed` (Louvain) and `backend` (the device backend)."""
+        coordinates otherwise.  Beyond the reference's keywords: `seed` (Louvain), `backend` (the device backend) and
+        `community_method`: "networkx" as in the reference, or "device" for the deterministic Louvain and the community points of
+        DESIGN.md section 8p, which ignore `seed`; without `out_dir` the edge arrays then go straight from the ray-pair kernel to
+        the community kernel: no tuple list, no JSON."""
         from geograypher_amd.utils.geometric import get_scale_from_transform
-        from geograypher_amd.utils.numeric import calc_communities, calc_graph_weights
+        from geograypher_amd.utils.numeric import calc_communities, calc_graph_weights, ray_pair_edges
+
+        if community_method not in ("networkx", "device"):
+            raise ValueError(f"community_method must be 'networkx' or 'device', got {community_method!r}")
 
         if out_dir is not None:
             out_dir = Path(out_dir)
@@ -663,6 +670,10 @@ class PhotogrammetryCameraSet:
 
         if check_exists("edge_weights.json"):
             weight_results = out_dir / "edge_weights.json"
+        elif community_method == "device" and out_dir is None:
+            weight_results = ray_pair_edges(
+                line_results["ray_starts"], line_results["ray_ends"], line_results["ray_IDs"], similarity_threshold_local,
+                step=5000, transform=transform, backend=backend)
         else:
             weight_results = calc_graph_weights(
                 starts=line_results["ray_starts"], ends=line_results["ray_ends"], ray_IDs=line_results["ray_IDs"],
@@ -678,7 +689,7 @@ class PhotogrammetryCameraSet:
             community_results = calc_communities(
                 starts=line_results["ray_starts"], ends=line_results["ray_ends"], edge_weights=weight_results,
                 louvain_resolution=louvain_resolution, out_dir=out_dir, transform_to_epsg_4978=transform_to_epsg_4978,
-                seed=seed)
+                seed=seed, **({"method": "device", "backend": backend} if community_method == "device" else {}))
         if check_exists(community_results):
             with np.load(community_results) as d:
                 community_results = {k: d[k] for k in d.files}

@@ -83,6 +83,19 @@ template <class K, class Count> struct RunLengthEncode : CubStep {   // the runs
   }
 };
 
+using Sum = hipcub::Sum;   // the Op of a ReduceByKey that adds
+
+// the runs of equal keys: each key once, the values of its run folded with Op (associative; in run order), *n_runs
+template <class K, class V, class Op> struct ReduceByKey : CubStep {
+  ReduceByKey(gr_ctx *ctx, Plan &p, int64_t n_) : CubStep(ctx, p, n_) {
+    GR_CUB_DECLARE(hipcub::DeviceReduce::ReduceByKey(nullptr, cub_q, (const K *)nullptr, (K *)nullptr, (const V *)nullptr, (V *)nullptr,
+                                                     (int *)nullptr, Op(), n));
+  }
+  int run(const K *keys, K *unique, const V *values, V *folded, int *n_runs, hipStream_t s, int64_t count = -1) const {
+    GR_CUB_RUN("ReduceByKey", hipcub::DeviceReduce::ReduceByKey(tmp, tmp_bytes, keys, unique, values, folded, n_runs, Op(), m, s));
+  }
+};
+
 #undef GR_CUB_DECLARE
 #undef GR_CUB_RUN
 

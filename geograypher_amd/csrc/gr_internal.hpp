@@ -35,9 +35,15 @@
 //                    k_overlap_pairs_fill + a scan), the area of every pair as a signed sum over edge pairs (k_overlap_areas: one work item per
 //                    workgroup, the a-tile as edge records in LDS), its partials added in item order (k_overlap_item_keys + a running
 //                    maximum, k_overlap_reduce), table statistics (k_overlap_table_stats); float64, no atomics on it; no mesh needed
+//   communities.hip  communities of the ray graph: a synchronous Louvain on integer weights -- directed entries (k_comm_edges), rows (k_comm_rows),
+//                    the move kernel's three paths by row length (k_comm_move_wave, k_comm_move_group, k_comm_key_emit / _scores / _apply),
+//                    tot and size (k_comm_tot_size), dense ranks and the coarse entries (k_comm_alive, k_comm_relabel), the ordered result
+//                    (k_comm_members, k_comm_order_keys, k_comm_write_communities, k_comm_write_labels) + radix sorts, sums by key and scans;
+//                    int64 sums only; no mesh needed
 //   cub_steps.hpp    the hipcub calls of the stage calls, each declared once against the call's Plan: SortPairs, SortKeys, ExclusiveSum,
-//                    InclusiveMax, RunLengthEncode (size query on construction, typed pointers on run)
-//   compact_dev.hpp  FlagScan, compact_begin, compact_write, k_submesh_write: the scans and the write kernel of polygons.hip's sub-mesh and of decimate.hip
+//                    InclusiveMax, RunLengthEncode, ReduceByKey (size query on construction, typed pointers on run)
+//   compact_dev.hpp  FlagScan, compact_begin, compact_write, k_submesh_write: the scans and the write kernel of polygons.hip's sub-mesh and of decimate.hip;
+//                    communities.hip ranks its surviving communities with FlagScan
 //   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip, crs.hip, ortho.hip and overlap.hip: orient, ring_span, edge_crossing (THE even-odd rule of
 //                    k_polygon_weights, k_face_polygon_index and k_points_in_region), load_face, stat_add / stat_add_u32 / stat_max / stat_count
 #include <hip/hip_runtime.h>

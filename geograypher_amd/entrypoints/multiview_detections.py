@@ -42,10 +42,12 @@ def multiview_detections(
     camera_set=None,
     detector=None,
     backend=None,
+    community_method: str = "networkx",
 ) -> np.ndarray:
     """Triangulate object locations from detections in many images (see the module docstring for inputs and files).
     `mesh_file`: a `.npz` path or a (points, faces) pair.  Beyond the reference's arguments: `seed` (Louvain), and `camera_set`,
-    `detector` and `backend`, which replace the objects built from `camera_file`, `detections_dir` and the device.  Returns the
+    `detector` and `backend`, which replace the objects built from `camera_file`, `detections_dir` and the device, and
+    `community_method` ("networkx", or "device": the deterministic Louvain of `triangulate_detections`).  Returns the
     (M, 3) points that `tree_locations.npy` holds."""
     from geograypher_amd.meshes.meshes import TexturedPhotogrammetryMesh
 
@@ -80,7 +82,8 @@ def multiview_detections(
     points = camera_set.triangulate_detections(
         detector=detector, boundaries=(ceiling, floor), limit_ray_length_meters=LIMIT_RAY_LENGTH_METERS,
         limit_angle_from_vert=LIMIT_ANGLE_FROM_VERT, similarity_threshold_meters=similarity_threshold_meters,
-        transform=transform, louvain_resolution=louvain_resolution, out_dir=output_dir, seed=seed, backend=backend)
+        transform=transform, louvain_resolution=louvain_resolution, out_dir=output_dir, seed=seed, backend=backend,
+        community_method=community_method)
     np.save(output_dir / "tree_locations.npy", points)
     logger.info("Saved %d triangulated locations to %s", len(points), output_dir / "tree_locations.npy")
     return points
@@ -104,6 +107,8 @@ def parse_args(argv=None):
     parser.add_argument("--nonlinearity", choices=[k for k in TRANSFORMS if k], default=None,
                         help="Transform of the intersection distance x before the graph weight 1 / x is formed")
     parser.add_argument("--seed", type=int, help="Seed of the Louvain communities")
+    parser.add_argument("--community-method", choices=["networkx", "device"], default="networkx",
+                        help="networkx's randomised Louvain, or the deterministic Louvain on the device (ignores --seed)")
     args = parser.parse_args(argv)
     for path, kind in ((args.images_dir, "is_dir"), (args.detections_dir, "is_dir"), (args.camera_file, "is_file"),
                        (args.mesh_file, "is_file")):
@@ -119,7 +124,8 @@ def main(argv=None):
         images_dir=args.images_dir, detections_dir=args.detections_dir, camera_file=args.camera_file, mesh_file=args.mesh_file,
         output_dir=args.output_dir, original_image_folder=args.original_image_folder,
         similarity_threshold_meters=args.similarity_threshold_meters, louvain_resolution=args.louvain_resolution,
-        transform=TRANSFORMS[args.nonlinearity], geo_file_extension=args.geo_file_extension, seed=args.seed)
+        transform=TRANSFORMS[args.nonlinearity], geo_file_extension=args.geo_file_extension, seed=args.seed,
+        community_method=args.community_method)
 
 
 if __name__ == "__main__":

@@ -2,7 +2,9 @@
 
 The quadratic part -- the clamped segment-to-segment distance of every pair of rays -- runs on the device
 (`HipRaster.ray_pair_edges`, gr_ray_pairs); what is left on the host works on the kept edges only: the `min_dist` floor, the
-optional transform, the 1 / d weight, the reference's edge order, and the Louvain communities (networkx).  There is no CPU
+optional transform, the 1 / d weight, the reference's edge order, and the Louvain communities: networkx as in the reference
+(the default), or `method="device"`: a deterministic Louvain and the community points on the device (`ray_communities`,
+gr_louvain_communities, gr_community_points).  There is no CPU
 fallback for the distance stage: `backend` is a `HipRaster` (default: the shared one of the current device) or any object with
 the same `ray_pair_edges(starts, ends, ray_ids, threshold)` method.
 
@@ -150,18 +152,126 @@ def calc_graph_weights(starts, ends, ray_IDs, similarity_threshold: float, out_d
     return path
 
 
+COMMUNITY_WEIGHT_SCALE = 1024   # L1 of DESIGN.md section 8p: the device sees q = max(1, rint(w * 1024))
+
+
+def quantise_weights(w) -> np.ndarray:
+    """L1: float edge weights -> the int64 weights the device works on, q = max(1, rint(w * COMMUNITY_WEIGHT_SCALE)).  ValueError:
+    a weight that is not finite or not positive, a q above 2^31 - 1, or twice the sum of the q at or above 2^53 (below it every
+    sum of the rule-set is exact in int64 and converts to float64 exactly)."""
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    if not np.all(np.isfinite(w) & (w > 0)):
+        raise ValueError("edge weights must be finite and positive")
+    scaled = np.rint(w * COMMUNITY_WEIGHT_SCALE)
+    if scaled.size and float(scaled.max()) > 2**31 - 1:
+        raise ValueError(f"an edge weight of {float(w.max())} exceeds 2^31 - 1 after quantisation (x {COMMUNITY_WEIGHT_SCALE})")
+    q = np.maximum(scaled.astype(np.int64), 1)
+    if 2 * int(q.sum(dtype=np.int64)) >= 2**53:   # (q <= 2^31 - 1 each: the int64 sum itself cannot overflow)
+        raise ValueError("twice the sum of the quantised edge weights reaches 2^53")
+    return q
+
+
+def community_modularity(record: dict, resolution: float = 1.0) -> float:
+    """L13: Q = sum over the communities of in_c / M2 - resolution (tot_c / M2)^2, from the record of `louvain_communities`."""
+    M2 = float(record["M2"])
+    if M2 == 0:
+        return 0.0
+    c_in, c_tot = np.asarray(record["in"], dtype=np.float64), np.asarray(record["tot"], dtype=np.float64)
+    return float(np.sum(c_in / M2 - float(resolution) * (c_tot / M2) ** 2))
+
+
+def ray_communities(i, j, w, n_rays: int, resolution: float = 1.0, backend=None, max_sweeps: int = 32) -> dict:
+    """Communities of the ray graph on the device (gr_louvain_communities): the edges as arrays -- i, j
+    (E,) int, w (E,) float weights, as `ray_pair_edges` returns them -- of a graph of `n_rays` vertices.  The weights are
+    quantised (`quantise_weights`, L1); the indices are checked on the device.  Returns the record of
+    `HipRaster.louvain_communities` plus "modularity".  Deterministic: the same edges give the same record in every run."""
+    if backend is None:
+        from geograypher_amd._hip import default_backend
+
+        backend = default_backend()
+    q = quantise_weights(_host(w))
+    record = dict(backend.louvain_communities(i, j, q, int(n_rays), resolution=float(resolution), max_sweeps=int(max_sweeps)))
+    record["modularity"] = community_modularity(record, resolution)
+    return record
+
+
+def _edge_arrays(edge_weights):
+    """The tuple list of `calc_graph_weights` (or what json made of it), or an (i, j, w) triple of arrays -> (i, j, w) arrays."""
+    if isinstance(edge_weights, tuple) and len(edge_weights) == 3 and all(hasattr(x, "shape") for x in edge_weights):
+        return edge_weights
+    i = np.fromiter((int(e[0]) for e in edge_weights), dtype=np.int64, count=len(edge_weights))
+    j = np.fromiter((int(e[1]) for e in edge_weights), dtype=np.int64, count=len(edge_weights))
+    w = np.fromiter((float(e[2]["weight"]) for e in edge_weights), dtype=np.float64, count=len(edge_weights))
+    return i, j, w
+
+
+def _device_communities(starts, ends, edge_weights, resolution, backend):
+    """("ray_IDs", "community_points") of calc_communities(method="device"); None where the graph has no edge."""
+    i, j, w = _edge_arrays(edge_weights)
+    if int(np.shape(i)[0]) == 0:
+        return None
+    if backend is None:
+        from geograypher_amd._hip import default_backend
+
+        backend = default_backend()
+    record = ray_communities(i, j, w, starts.shape[0], resolution=resolution, backend=backend)
+    community = np.asarray(record["community"])
+    ray_IDs = np.where(community < 0, np.nan, community.astype(np.float64))
+    points = _host(backend.community_points(starts, ends, community, int(record["n_communities"])))
+    return ray_IDs, np.asarray(points, dtype=np.float64).reshape(-1, 3)
+
+
+def _finish_communities(found, transform_to_epsg_4978, out_dir):
+    """The result of calc_communities(method="device") from ("ray_IDs", "community_points") or None: the keys, the optional
+    transform and the file of the networkx path, restated here so that that path stays as it is."""
+    ecef = None
+    if found is not None:
+        ray_IDs, community_points = found
+        result = {"ray_IDs": ray_IDs, "community_points": community_points}
+        if transform_to_epsg_4978 is not None:
+            homogenous = np.concatenate([community_points, np.ones_like(community_points[:, 0:1])], axis=1)
+            ecef = (np.asarray(transform_to_epsg_4978) @ homogenous.T).T
+    else:
+        result = {"ray_IDs": np.zeros((0,), dtype=int), "community_points": np.zeros((0, 3))}
+        if transform_to_epsg_4978 is not None:
+            ecef = np.zeros((0, 4))
+    if ecef is not None:
+        try:
+            import pyproj
+        except ImportError:
+            result["community_points_epsg_4978"] = ecef[:, :3]
+        else:
+            tr = pyproj.Transformer.from_crs(pyproj.CRS.from_epsg(4978), pyproj.CRS.from_epsg(4326))
+            lat, lon, alt = tr.transform(ecef[:, 0], ecef[:, 1], ecef[:, 2])
+            result["community_points_latlon"] = np.vstack([lat, lon, alt]).T
+    if out_dir is not None:
+        path = Path(out_dir) / "communities.npz"
+        np.savez(path, **result)
+        return path
+    return result
+
+
 def calc_communities(starts, ends, edge_weights, louvain_resolution: float = 1.0, out_dir: typing.Optional[PATH_TYPE] = None,
-                     transform_to_epsg_4978: typing.Optional[np.ndarray] = None, seed=None):
+                     transform_to_epsg_4978: typing.Optional[np.ndarray] = None, seed=None, method: str = "networkx", backend=None):
     """Louvain communities of the ray graph and one 3D point per community (numeric.py:509-619).  Returns, or with `out_dir`
     saves as `communities.npz`, a dict with "ray_IDs" ((N,) float: community of every ray, NaN for a ray without an edge) and
     "community_points" ((M, 3): `intersection_average` of the community's rays), communities ordered by falling size.
 
     `seed` goes to networkx.community.louvain_communities (the reference is unseeded).  With `transform_to_epsg_4978` the
     reference adds "community_points_latlon" through pyproj.  Where pyproj is missing the transformed points are returned as
-    "community_points_epsg_4978" instead and no lat/lon key is written: the conversion is not approximated."""
+    "community_points_epsg_4978" instead and no lat/lon key is written: the conversion is not approximated.
+
+    `method="device"` computes both on the device instead (`ray_communities`, `HipRaster.community_points`; DESIGN.md section
+    8p): a deterministic rule-set, so `seed` is ignored and the partition is not the one networkx would draw; `edge_weights`
+    may then also be an (i, j, w) triple of arrays; `backend` as for `ray_pair_edges`.  The keys, shapes and dtypes are the same."""
+    if method not in ("networkx", "device"):
+        raise ValueError(f"method must be 'networkx' or 'device', got {method!r}")
+    starts, ends = np.asarray(starts, dtype=np.float64), np.asarray(ends, dtype=np.float64)
+    if method == "device":
+        found = _device_communities(starts, ends, edge_weights, louvain_resolution, backend)
+        return _finish_communities(found, transform_to_epsg_4978, out_dir)
     import networkx
 
-    starts, ends = np.asarray(starts, dtype=np.float64), np.asarray(ends, dtype=np.float64)
     graph = networkx.Graph([(int(e[0]), int(e[1]), dict(e[2])) for e in edge_weights])
     ecef = None
     if len(graph) > 0:

@@ -788,6 +788,38 @@ enum {
 };
 #include "geograster_overlap.h"
 
+/* Communities of the ray graph (geograster_communities.h): flags, limits and the words of the
+ * statistics block. */
+enum {
+  GR_COMM_FORCE_GROUP = 1,            /* every row that fits goes through the workgroup path (tests; same results)  */
+  GR_COMM_FORCE_KEY = 2               /* every row goes through the key path (tests; same results)                  */
+};
+enum {
+  GR_COMM_MAX_VERTICES = 8388608,     /* n limit, 2^23: that of gr_ray_pairs                                        */
+  GR_COMM_MAX_EDGES = 1069547520,     /* 2^30 - 2^22; E stays below it: 2 E + n entries fit a 32-bit count          */
+  GR_COMM_MAX_LEVELS = 64,            /* L11                                                                        */
+  GR_COMM_LDS_ROW = 1024              /* entries of the longest row the workgroup path sorts in LDS                 */
+};
+enum {
+  GR_COMM_CAP_SWEEPS = 1,             /* GR_COMM_STAT_CAPS: a level was ended by max_sweeps                         */
+  GR_COMM_CAP_LEVELS = 2              /* ... the run was ended by GR_COMM_MAX_LEVELS                                */
+};
+enum {
+  GR_COMM_STAT_LEVELS = 0,            /* levels that moved a vertex: those the labels are composed of               */
+  GR_COMM_STAT_LEVELS_RUN = 1,        /* levels that ran: the one without a move, which is discarded, included      */
+  GR_COMM_STAT_CAPS = 2,              /* the OR of GR_COMM_CAP_*                                                    */
+  GR_COMM_STAT_ROWS_WAVE = 3,         /* rows the wave path handled, summed over all sweeps                         */
+  GR_COMM_STAT_ROWS_GROUP = 4,        /* ... the workgroup path                                                     */
+  GR_COMM_STAT_ROWS_KEY = 5,          /* ... the key path                                                           */
+  GR_COMM_STAT_BAD_EDGES = 6,         /* edges that break L2                                                        */
+  GR_COMM_STAT_COMMUNITIES = 7,       /* n_communities                                                              */
+  GR_COMM_STAT_M2 = 8,                /* the sum of all directed entries: twice the sum of the weights              */
+  GR_COMM_STAT_SWEEPS = 16,           /* GR_COMM_MAX_LEVELS words: sweeps of every level that ran                   */
+  GR_COMM_STAT_MOVES = 80,            /* GR_COMM_MAX_LEVELS words: moves of every level that ran                    */
+  GR_COMM_STAT_WORDS = 144
+};
+#include "geograster_communities.h"
+
 #ifdef __cplusplus
 }
 #endif
