@@ -59,6 +59,8 @@ GR_VAR_PACKED_COUNTERS = 131072
 GR_DBG_POISON_SLOTS = 512
 GR_DBG_POISON_RAYS = 1024
 GR_DBG_RAY_GRID_7 = 2048
+GR_DBG_POISON_STAGE = 4096      # every stage call fills the whole block of stage scratch it was given with 0xFF first
+GR_DBG_POISON_STAGE_7F = 8192   # ... with 0x7F (0xFF wins when both are set)
 # bits of overflow_causes()
 GR_CAUSE_LIST_OUTGREW = 1
 GR_CAUSE_SHORT_MISS = 2
@@ -257,6 +259,7 @@ _SIGNATURES = {
     "gr_get_stage_times": [_vp, ctypes.POINTER(StageTimes)],
     "gr_mesh_upload": [_vp, _vp, _vp, _i64, _i64, _vp],
     "gr_debug_read_upload": [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_uint64), _vp],
+    "gr_debug_read_stage": [_vp, _i32, _i64, _i64, _vp, _i64p, _vp],
     "gr_raster_face_ids": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "gr_raster_status": [_vp, ctypes.POINTER(RasterStats)],
     "gr_raster_overflow_causes": [_vp],
@@ -1270,6 +1273,19 @@ class HipRaster:
         self._call("gr_debug_read_upload", orig.data_ptr(), blk.data_ptr(), bvert.data_ptr(), bidx.data_ptr(), ctypes.byref(sig),
                    self._stream())
         return {"orig": orig, "blk": blk, "bvert": bvert, "bidx": bidx, "mesh_sig": int(sig.value)}
+
+    def debug_stage(self, block: int = 0, offset: int = 0, n: int = 0):
+        """For tests: (`n` bytes at `offset` of the stage scratch as a (n,) uint8 tensor, the bytes the block holds now)
+        (gr_debug_read_stage) -- block 0 is the stage arena, block 1 the second block of the outline calls; a negative `offset`
+        counts from the block's end.  n = 0 asks for the size alone."""
+        size = ctypes.c_int64(0)
+        self._call("gr_debug_read_stage", int(block), 0, 0, None, ctypes.byref(size), self._stream())
+        if offset < 0:
+            offset += int(size.value)
+        out = self._empty((int(n),), _torch().uint8)
+        self._call("gr_debug_read_stage", int(block), int(offset), int(n), out.data_ptr() if n else None, ctypes.byref(size),
+                   self._stream())
+        return out, int(size.value)
 
     # -- pix2face ------------------------------------------------------------------------------------------------
     def raster_face_ids(self, cams, h: int, w: int, out=None, want_depth: bool = False, check: bool = True):

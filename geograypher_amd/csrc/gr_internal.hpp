@@ -4,7 +4,8 @@
 // release_all from device_buffer.hpp, instantiated here with DeviceMem; the stage arena: Scratch, stage_acquire; its layouts come
 // from scratch_layout.hpp, the sorts and scans that run in it from cub_steps.hpp).
 //   geograster.hip   context, options, learned binning table, the raster call (launch groups, side stream), status
-//   mesh_upload.hip  gr_mesh_upload: Morton order, de-indexed soup, block bounds            (per upload)
+//   mesh_upload.hip  gr_mesh_upload: Morton order, de-indexed soup, block bounds            (per upload); the tests' read-backs
+//                    (gr_debug_read_upload, gr_debug_read_stage)
 //   binning.hip      k_cull_blocks, k_setup_cull, k_clip_faces, entry compilation, exact-path scan / fill  (per view)
 //   raster_tile.hip  k_raster_tile: the dominant kernel
 //   project.hip      winners, votes, gathers, sparse pairs (label images, rectangle tables, polygon rings), finalize, argmax + their entry points
@@ -396,6 +397,13 @@ inline int stage_acquire(gr_ctx *c, Scratch &sc, size_t bytes, hipStream_t s, co
   if (const int rc = reserve(mem, sc, (int64_t)bytes, what)) return rc;
   note_stream(c, s);
   sc.last = s;
+  // test hook (GR_DBG_POISON_STAGE, GR_DBG_POISON_STAGE_7F; 0xFF wins when both are set): the WHOLE block, not only `bytes` of it,
+  // starts as garbage on the call's stream -- every word a stage reads is one it wrote itself, or the results show it
+  if (c->opt_dbg & (GR_DBG_POISON_STAGE | GR_DBG_POISON_STAGE_7F)) {
+    const int byte = (c->opt_dbg & GR_DBG_POISON_STAGE) ? 0xFF : 0x7F;
+    if (sc.ptr && sc.have > 0 && hipMemsetAsync(sc.ptr, byte, (size_t)sc.have, s) != hipSuccess)
+      return fail(c, GR_EHIP, "%s scratch: the poison memset failed", what);
+  }
   return GR_OK;
 }
 

@@ -270,4 +270,24 @@ int gr_debug_read_upload(gr_ctx *c, int32_t *orig, float *blk4, float *bvert, ui
   return GR_OK;
 }
 
+int gr_debug_read_stage(gr_ctx *c, int block, int64_t offset, int64_t n, uint8_t *out, int64_t *size_h, void *stream) {
+  if (!c) return GR_EINVAL;
+  if (!size_h || (block != 0 && block != 1))
+    return fail(c, GR_EINVAL, "gr_debug_read_stage: block %d is neither 0 (stage) nor 1 (stage_b), or no size word", block);
+  Scratch &sc = block == 0 ? c->stage : c->stage_b;
+  *size_h = sc.ptr ? sc.have : 0;
+  if (offset < 0 || n < 0 || offset > *size_h || n > *size_h - offset)
+    return fail(c, GR_EINVAL, "gr_debug_read_stage: bytes [%lld, %lld + %lld) of a block of %lld", (long long)offset, (long long)offset,
+                (long long)n, (long long)*size_h);
+  hipStream_t s = (hipStream_t)stream;
+  GR_HIP(c, hipSetDevice(c->device));
+  if (sc.ptr && sc.last != s) GR_HIP(c, hipStreamSynchronize(sc.last));   // the block's last user, as stage_acquire waits for it
+  if (out && n > 0) {
+    note_stream(c, s);
+    GR_HIP(c, hipMemcpyAsync(out, sc.ptr + offset, (size_t)n, hipMemcpyDeviceToDevice, s));
+  }
+  GR_HIP(c, hipStreamSynchronize(s));
+  return GR_OK;
+}
+
 }  // extern "C"

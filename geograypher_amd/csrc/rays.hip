@@ -64,14 +64,15 @@ __global__ void __launch_bounds__(GR_RAY_TILE) k_ray_pairs(const RayRec *__restr
     if (tid < nb) tile[tid] = rec[j0 + tid];
     const int64_t i = row * GR_RAY_TILE + tid;
     const bool have_a = i < n;
-    const RayRec a = rec[have_a ? i : n - 1];
+    const int64_t ia = have_a ? i : n - 1;   // a padded lane is ray n - 1 throughout: segment_closest_points loads ends[3 * ia]
+    const RayRec a = rec[ia];
     __syncthreads();
     // a tile on the diagonal: the wave's first ray is row * TILE + (tid - lane); nothing at or before it can be a j > i
     const int jj0 = row == col ? (tid - lane) + 1 : 0;
     for (int jj = jj0; jj < nb; ++jj) {
       const RayRec b = tile[jj];
       const int64_t j = j0 + jj;
-      const double d = segment_distance(a, b, ends, i, j);
+      const double d = segment_distance(a, b, ends, ia, j);
       const bool hit = have_a & (i < j) & (a.id != b.id) & (d <= threshold);
       const unsigned long long mask = __ballot(hit);
       if (mask == 0) continue;

@@ -172,8 +172,10 @@ enum {
   GR_DBG_POISON_SLOTS = 512,  /* entry slots and row counts are poisoned with 0xFF before every launch group is binned
                                  (tests/test_overflow_protocol.py)                                                         */
   GR_DBG_POISON_RAYS = 1024,  /* gr_ray_pairs poisons its scratch with 0xFF at the start of every call                      */
-  GR_DBG_RAY_GRID_7 = 2048    /* gr_ray_pairs' grid is capped at 7 workgroups, which stride over all tiles as a launch beyond
+  GR_DBG_RAY_GRID_7 = 2048,   /* gr_ray_pairs' grid is capped at 7 workgroups, which stride over all tiles as a launch beyond
                                  2^20 tiles does (tests/test_ray_pairs.py)                                                 */
+  GR_DBG_POISON_STAGE = 4096, /* every stage call fills the whole block of stage scratch it was given with 0xFF first      */
+  GR_DBG_POISON_STAGE_7F = 8192 /* ... with 0x7F (0xFF wins when both are set; tests/test_stage_poison_gpu.py)            */
 };
 int gr_set_option(gr_ctx *ctx, int key, int value);
 
@@ -204,6 +206,10 @@ int gr_mesh_upload(gr_ctx *ctx, const float *verts, const int32_t *faces, int64_
  * block's count are unspecified); bidx [F] a face's three positions in its block's list, 8 bits each, and the block's count - 1
  * in the top byte.  mesh_sig_h: the mesh signature, to a host word.  GR_ENOMESH without a mesh.  Synchronises `stream`. */
 int gr_debug_read_upload(gr_ctx *ctx, int32_t *orig, float *blk4, float *bvert, uint32_t *bidx, uint64_t *mesh_sig_h, void *stream);
+/* For tests: `n` bytes at `offset` of the context's stage scratch -- block 0: the stage arena, block 1: the second block of the
+ * outline calls -- copied device to device into `out` (null, or n = 0: the size alone); size_h: the bytes the block holds now, to
+ * a host word (0: never used).  GR_EINVAL for another block or a range outside it.  Synchronises `stream`. */
+int gr_debug_read_stage(gr_ctx *ctx, int block, int64_t offset, int64_t n, uint8_t *out, int64_t *size_h, void *stream);
 
 /* pix2face -- replaces meshes.py:1776-1836 (encode ids, VTK render, decode, background mask) for n_views
  * cameras of equal image size.  ids: n_views x h x w int32, background -1.  depth (may be NULL): n_views x h x w

@@ -47,7 +47,7 @@ def test_every_signature_agrees_with_the_header_in_count_and_kind():
     kind (a pointer, a 64-bit integer, an int, a double).  A short `argtypes` list, or an int where the library reads an
     int64_t, is a bad pointer or a bad size in a kernel's arguments."""
     declared = _declarations()
-    assert sorted(declared) == sorted(_hip._SIGNATURES) and len(declared) == 46
+    assert sorted(declared) == sorted(_hip._SIGNATURES) and len(declared) == 47
     for name, arguments in declared.items():
         argtypes = _hip._SIGNATURES[name]
         assert len(arguments) == len(argtypes), f"{name}: the header declares {len(arguments)} arguments, the binding {len(argtypes)}"

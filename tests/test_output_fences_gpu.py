@@ -36,6 +36,7 @@ import raster_standin as rs  # noqa: E402
 import vector_standin as vs  # noqa: E402
 from region_standin import points_in_region_np  # noqa: E402
 
+from geograypher_amd import _hip  # noqa: E402
 from geograypher_amd.utils import synthetic  # noqa: E402
 from geograypher_amd.utils.geometric import PlanarPolygons  # noqa: E402
 from geograypher_amd.utils.raster import PlanarRaster  # noqa: E402
@@ -72,6 +73,7 @@ COVERED = {
     "raster_project_labels": ["test_raster_project_labels"],
     "new_vote_buffers": ["test_raster_project_labels", "test_projection_stages"],
     "debug_upload": ["test_debug_upload"],
+    "debug_stage": ["test_debug_stage"],
     "gather_texture": ["test_projection_stages"],
     "gather_texture_u8": ["test_projection_stages"],
     "project_view": ["test_projection_stages"],
@@ -218,6 +220,23 @@ def test_debug_upload(ctx, name):
         got = t_upload._read(ctx)
         t_upload._assert_properties(got, verts, faces)
         t_upload._assert_same_products(got, want, want["counts"])
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_debug_stage(ctx, grid, n):
+    """gr_debug_read_stage copies exactly n bytes.  The stage scratch is filled with 0xFF first (GR_DBG_POISON_STAGE, under
+    gr_points_bounds, which plans 65 536 bytes and writes one record at their front), so every byte of the copy differs from the
+    poison of the output buffer."""
+    ctx.set_option(_hip.GR_OPT_DEBUG, _hip.GR_DBG_POISON_STAGE)
+    try:
+        ctx.points_bounds(np.array(grid["points"]))
+    finally:
+        ctx.set_option(_hip.GR_OPT_DEBUG, 0)
+    with fenced(ctx):
+        tail, size = ctx.debug_stage(0, -n, n)
+        assert size >= 65536 and tail.shape == (n,) and bool((tail == 0xFF).all())
+        front, _ = ctx.debug_stage(0, 4096, n)   # behind the one record, inside the plan
+        assert bool((front == 0xFF).all())
 
 
 # ---- the kernels behind the rasterizer ----------------------------------------------------------------------------------------
