@@ -196,6 +196,13 @@ GR_OVERLAP_STAT_WORDS = 8
 GR_OVERLAP_ITEM_INTS = 5
 GR_OVERLAP_TILE_A = 256
 GR_OVERLAP_TILE_B = 4096
+# ring simplification: stats words of gr_simplify_rings (include/geograster_simplify.h)
+GR_SIMPLIFY_STAT_KEPT = 0
+GR_SIMPLIFY_STAT_COLLAPSED = 1
+GR_SIMPLIFY_STAT_PASSES = 2
+GR_SIMPLIFY_STAT_WIDE = 3
+GR_SIMPLIFY_STAT_SHORT_RINGS = 4
+GR_SIMPLIFY_STAT_WORDS = 8
 
 
 class StageTimes(ctypes.Structure):
@@ -338,6 +345,11 @@ _COMMUNITIES_SIGNATURES = {
     "gr_community_points": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
 }
 COMMUNITIES_SYMBOLS = tuple(_COMMUNITIES_SIGNATURES)
+# ... and the call of include/geograster_simplify.h (exact Douglas-Peucker on polygon rings), under the same contract.
+_SIMPLIFY_SIGNATURES = {
+    "gr_simplify_rings": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+}
+SIMPLIFY_SYMBOLS = tuple(_SIMPLIFY_SIGNATURES)
 
 
 def library_path() -> Path:
@@ -361,7 +373,7 @@ def load_library() -> ctypes.CDLL:
     _torch()
     lib = ctypes.CDLL(str(_LIB_PATH))
     for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES, **_BURN_SIGNATURES,
-                           **_OVERLAP_SIGNATURES, **_COMMUNITIES_SIGNATURES}.items():
+                           **_OVERLAP_SIGNATURES, **_COMMUNITIES_SIGNATURES, **_SIMPLIFY_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -822,6 +834,77 @@ class PolygonOverlap:
         rv_t, off_t, rp_t, box_t, rh_t, N, R, P = t
         return (_ptr(rv_t if N else None), N, off_t.data_ptr(), _ptr(rp_t if R else None), _ptr(rh_t if R else None), R,
                 _ptr(box_t if P else None), P)
+
+
+SIMPLIFY_COORD_LIMIT = 1 << 40   # S1: |snapped coordinate| <= 2^40 (utils.geometric.SNAP_LIMIT); the tolerance stays below it
+SIMPLIFY_GRID = 1e-6             # metres per grid step
+
+
+def simplify_tol_steps(tol_meters) -> int:
+    """S1: the tolerance in grid steps, T = rint(tol_meters / 1e-6) with 0 <= T < 2^40 -- ValueError naming gr_simplify_rings."""
+    name = "gr_simplify_rings"
+    try:
+        tol = float(tol_meters)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: the tolerance must be a number of metres, got {tol_meters!r}") from None
+    if not np.isfinite(tol) or tol < 0 or np.rint(tol / SIMPLIFY_GRID) >= SIMPLIFY_COORD_LIMIT:
+        raise ValueError(f"{name}: the tolerance must be in [0, 2^40) grid steps of 1e-6 m, got {tol_meters!r} m")
+    return int(np.rint(tol / SIMPLIFY_GRID))
+
+
+def check_simplify_tables(ring_vertices, ring_offsets, tol_meters, fixed=None):
+    """S1: the ring table, the fixed flags and the tolerance of `RingSimplifier.simplify` are in range -- ValueError naming
+    gr_simplify_rings; -> (N, R, T)."""
+    name = "gr_simplify_rings"
+    rv = np.asarray(ring_vertices)
+    if rv.ndim != 2 or rv.shape[1] != 2 or rv.dtype.kind not in "iu":
+        raise ValueError(f"{name}: ring vertices must be an (N, 2) integer array, got {rv.shape} {rv.dtype}")
+    N = int(rv.shape[0])
+    if N >= 2 ** 31 - 1:
+        raise ValueError(f"{name}: {N} ring vertices, not below 2^31 - 1")
+    if rv.size and (int(rv.max()) > SIMPLIFY_COORD_LIMIT or int(rv.min()) < -SIMPLIFY_COORD_LIMIT):
+        raise ValueError(f"{name}: a ring vertex lies more than 2^40 grid steps from the origin")
+    off = np.asarray(ring_offsets)
+    if off.ndim != 1 or off.shape[0] < 1 or off.dtype.kind not in "iu":
+        raise ValueError(f"{name}: ring offsets must be an (R + 1,) integer array, got {off.shape} {off.dtype}")
+    off = off.astype(np.int64)
+    R = int(off.shape[0]) - 1
+    if off[0] != 0 or off[-1] != N or np.any(np.diff(off) < 0):
+        raise ValueError(f"{name}: ring offsets must rise from 0 to {N} (the number of ring vertices)")
+    if fixed is not None:
+        fx = np.asarray(fixed)
+        if fx.shape != (N,) or fx.dtype.kind not in "iub":
+            raise ValueError(f"{name}: fixed must be ({N},) flags, one per ring vertex, got {fx.shape} {fx.dtype}")
+    return N, R, simplify_tol_steps(tol_meters)
+
+
+class RingSimplifier:
+    """Exact Douglas-Peucker on the rings of a snapped ring table (gr_simplify_rings).  Made by
+    `HipRaster.ring_simplifier`.  Every output is allocated through the backend (`_empty`, `_stats`)."""
+
+    def __init__(self, backend: "HipRaster"):
+        self.backend = backend
+
+    def simplify(self, ring_vertices, ring_offsets, tol_meters, fixed=None):
+        """ring_vertices (N, 2) int64 on the 1e-6 m grid and ring_offsets (R + 1,) as `PlanarPolygons.snapped` gives them,
+        tol_meters, fixed (N,) flags or None (S2) -> (keep (N,) uint8 tensor, kept_index (M,) int32 tensor: the kept vertices,
+        ring after ring in input order, out_offsets (R + 1,) int64 tensor, stats (GR_SIMPLIFY_STAT_WORDS,) int64 tensor).  The
+        tables are validated on the host first (`check_simplify_tables`: ValueError).  Reads M back."""
+        torch = _torch()
+        hip = self.backend
+        N, R, T = check_simplify_tables(_host_array(ring_vertices), _host_array(ring_offsets), tol_meters,
+                                        None if fixed is None else _host_array(fixed))
+        rv_t = hip._shaped(ring_vertices, torch.int64, (N, 2), "ring vertices")
+        off_t = hip._shaped(ring_offsets, torch.int64, (R + 1,), "ring offsets")
+        fx_t = None if fixed is None else hip._shaped(fixed, torch.uint8, (N,), "fixed (one per ring vertex)")
+        keep = hip._empty((N,), torch.uint8)
+        kept_index = hip._empty((N,), torch.int32)
+        out_offsets = hip._empty((R + 1,), torch.int64)
+        stats = hip._stats(GR_SIMPLIFY_STAT_WORDS)
+        hip._call("gr_simplify_rings", _ptr(rv_t if N else None), N, off_t.data_ptr(), R, _ptr(fx_t if N else None), T,
+                  _ptr(keep if N else None), _ptr(kept_index if N else None), out_offsets.data_ptr(), stats.data_ptr(), hip._stream())
+        M = int(out_offsets[R].item())
+        return keep, kept_index[:M], out_offsets, stats
 
 
 class RayCommunities:
@@ -1955,6 +2038,11 @@ class HipRaster:
         `PlanarPolygons.snapped`: the tables are checked (`check_overlap_tables`: ValueError naming gr_polygon_overlap_areas) and
         uploaded once; `.pairs()` lists the candidate pairs, `.areas(pairs, items)` gives the overlap area of every pair."""
         return PolygonOverlap(self, table_a, table_b)
+
+    def ring_simplifier(self) -> "RingSimplifier":
+        """A `RingSimplifier` on this backend: `.simplify(ring_vertices, ring_offsets, tol_meters, fixed=None)` is the exact
+        Douglas-Peucker of DESIGN.md 8q (`utils.geometric.simplify_rings` and the `simplified` methods go through it)."""
+        return RingSimplifier(self)
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):

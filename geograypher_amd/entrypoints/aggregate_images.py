@@ -56,6 +56,8 @@ def aggregate_images(
     DTM_CRS=None,
     top_down_CRS=None,
     mesh_downsample_method: typing.Union[str, None] = None,
+    top_down_simplify_tol: float = 0.0,
+    top_down_simplify_method: typing.Union[str, None] = None,
 ):
     """Aggregate the labels under `label_folder` onto the mesh (see the module docstring).  The reference's arguments and defaults;
     `mesh_downsample != 1` without `mesh_downsample_method`, `vis`, `ROI` without `ROI_points_file`, `DTM_file` without `DTM_points_file` and
@@ -68,7 +70,10 @@ def aggregate_images(
     reprojected on the device; giving both is a ValueError.  `mesh_downsample_method="cluster"`
     decimates the mesh to about `mesh_downsample` of its vertices behind the ROI crop (`TexturedPhotogrammetryMesh.decimate`: vertex
     clustering, not the reference's quadric decimation); the `*_points_file` arrays stay those of the ORIGINAL mesh and the results
-    are per face of the decimated mesh (`mesh.decimated_face_IDs`).  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
+    are per face of the decimated mesh (`mesh.decimated_face_IDs`).  `top_down_simplify_method="douglas-peucker"` simplifies the rings
+    of the top-down map at `top_down_simplify_tol` metres on the device (`export_face_labels_vector(simplify_tol=...,
+    simplify_method=...)`: exact Douglas-Peucker, shared borders kept consistent); a tolerance without the method raises
+    NotImplementedError and another method name ValueError, both before the aggregation.  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
     from geograypher_amd.cameras.segmentor import SegmentorPhotogrammetryCameraSet
     from geograypher_amd.meshes import TexturedPhotogrammetryMesh, TexturedPhotogrammetryMeshChunked
     from geograypher_amd.predictors.derived_segmentors import LookUpSegmentor
@@ -78,6 +83,13 @@ def aggregate_images(
     camera_points = points_or_CRS("ROI_camera_points_file", ROI_camera_points_file, "ROI_camera_CRS", ROI_camera_CRS)
     DTM_points = points_or_CRS("DTM_points_file", DTM_points_file, "DTM_CRS", DTM_CRS)
     top_down_points = points_or_CRS("top_down_points_file", top_down_points_file, "top_down_CRS", top_down_CRS)
+    if top_down_simplify_method is not None:
+        from geograypher_amd.utils.geometric import check_simplify_method
+
+        check_simplify_method(top_down_simplify_method, "top_down_simplify_method")
+    elif top_down_simplify_tol > 0:
+        raise NotImplementedError("top_down_simplify_tol: shapely's simplification is outside the projection path; ask for the "
+                                  "exact Douglas-Peucker by name: top_down_simplify_method='douglas-peucker'")
 
     for name, value, why in (
         ("DTM_file", DTM_file if DTM_points is None else None,
@@ -202,7 +214,8 @@ def aggregate_images(
         label_names = None if IDs is None else [IDs.get(i, None) for i in range(max(list(IDs.keys())) + 1)]
         mesh.export_face_labels_vector(face_labels=np.squeeze(predicted_face_classes, axis=1),
                                        export_file=top_down_vector_projection_savefile, label_names=label_names,
-                                       points_in_export_CRS=points_in_export_CRS)
+                                       points_in_export_CRS=points_in_export_CRS, simplify_tol=top_down_simplify_tol,
+                                       simplify_method=top_down_simplify_method)
     return mesh, aggregated_face_labels, predicted_face_classes
 
 
@@ -248,6 +261,11 @@ def parse_args(argv=None):
     parser.add_argument("--top-down-points-file", type=Path,
                         help=".npy with the mesh vertices (V, 2) or (V, 3) in the planar CRS of the map (required with it)")
     parser.add_argument("--top-down-CRS", help="Planar CRS of the map instead of --top-down-points-file")
+    parser.add_argument("--top-down-simplify-tol", type=float, default=0.0,
+                        help="Simplify the rings of the top-down map at this tolerance in metres; needs --top-down-simplify-method")
+    parser.add_argument("--top-down-simplify-method", choices=["douglas-peucker"],
+                        help="How --top-down-simplify-tol simplifies: douglas-peucker = the exact Douglas-Peucker on the 1e-6 m "
+                        "grid, on the device, with the borders two classes share kept identical")
     parser.add_argument("--vis", action="store_true", help="Not available here")
     args = parser.parse_args(argv)
     args.IDs_to_labels = str(args.IDs_to_labels)

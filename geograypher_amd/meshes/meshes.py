@@ -135,6 +135,8 @@ class TexturedPhotogrammetryMesh:
         vertex_order: str = "r1",
         points_in_ROI_CRS: typing.Optional[np.ndarray] = None,
         downsample_method: typing.Optional[str] = None,
+        ROI_simplify_tol_meters: float = 0,
+        ROI_simplify_method: typing.Optional[str] = None,
     ):
         """A textured mesh that renders to / aggregates from camera views on an MI355X.
 
@@ -152,6 +154,9 @@ class TexturedPhotogrammetryMesh:
         count is indexed by them, one of the cropped count is taken as it is.
 
         Extra keyword arguments (defaults keep reference behaviour):
+            ROI_simplify_tol_meters, ROI_simplify_method: `select_mesh_ROI`'s simplify_tol_meters and simplify_method: the ROI is
+                simplified by the exact Douglas-Peucker of DESIGN.md section 8q when the method "douglas-peucker" is named
+                (the reference's load_mesh simplifies every ROI at 2 m with shapely, meshes.py:695).
             device: GPU index for the HIP backend (default: current torch device).
             devices: several GPU indices, e.g. `[0, 1, 2, 3, 4, 5, 6, 7]`: `aggregate_projected_images` deals its views round-robin to
                 one libgeograster context + host thread per entry (the mesh is uploaded to each), adds the per-device partial
@@ -255,7 +260,8 @@ class TexturedPhotogrammetryMesh:
         self._n_original = (self.points.shape[0], self.faces.shape[0])   # vertices, faces before the crop
         if ROI is not None:   # before the texture, as the reference does (meshes.py:200-213)
             (self.points, self.faces), self.ROI_point_IDs, self.ROI_face_IDs = self.select_mesh_ROI(
-                ROI, buffer_meters=ROI_buffer_meters, return_original_IDs=True, points_in_ROI_CRS=points_in_ROI_CRS)
+                ROI, buffer_meters=ROI_buffer_meters, simplify_tol_meters=ROI_simplify_tol_meters, return_original_IDs=True,
+                points_in_ROI_CRS=points_in_ROI_CRS, simplify_method=ROI_simplify_method)
 
         self.downsample_method = downsample_method
         self.decimated_point_IDs = None
@@ -299,12 +305,17 @@ class TexturedPhotogrammetryMesh:
         return values
 
     def select_mesh_ROI(self, region_of_interest, buffer_meters: float = 0, simplify_tol_meters: float = 0, default_CRS=None,
-                        return_original_IDs: bool = False, *, points_in_ROI_CRS=None):
+                        return_original_IDs: bool = False, *, points_in_ROI_CRS=None, simplify_method: typing.Optional[str] = None):
         """The part of the mesh in a region of interest (reference: meshes.py:646-731; rules Q1-Q6).
 
         region_of_interest: a `PlanarPolygons`, a sequence its `from_sequence` takes or a `.geojson` path; all rows together
         are the region.  None returns the mesh unchanged.  buffer_meters: a vertex within this distance of the region is in
-        it too.  simplify_tol_meters: only 0 (polygon simplification is not built: NotImplementedError).  default_CRS:
+        it too.  simplify_tol_meters: 0, or any tolerance s together with simplify_method="douglas-peucker" (another name:
+        ValueError; a tolerance without the method: NotImplementedError): the ROI's rings are simplified at s by the exact
+        Douglas-Peucker of DESIGN.md section 8q (`PlanarPolygons.simplified`) and the region test runs with the buffer
+        buffer_meters + s.  The reference buffers first and simplifies the buffered polygon (meshes.py:695); here the order is
+        the other way round, with a guarantee in its place: every point within buffer_meters of the original region is within
+        buffer_meters + s of the simplified one, so the selection is a superset of the unsimplified one.  default_CRS:
         accepted and unused (coordinates are taken as they stand).  points_in_ROI_CRS (required, keyword): the mesh vertices
         (V, 2) or (V, 3) in the ROI's planar CRS, or a CRS designator (`WGS84CRS.parse`: the vertices are then reprojected on the device).
 
@@ -312,12 +323,15 @@ class TexturedPhotogrammetryMesh:
         face uses it; both keep their order.  Returns (points, faces) -- faces index the kept points --, or with
         `return_original_IDs` ((points, faces), point_IDs, face_IDs): the ascending int64 indices into the original mesh.
         The point query and the compaction run on the device; the call's figures are left in `self.last_ROI_stats`."""
-        from geograypher_amd.utils.geometric import points_in_region
+        from geograypher_amd.utils.geometric import check_simplify_method, points_in_region, region_polygons
 
         if region_of_interest is None:
             return self.points, self.faces
-        if simplify_tol_meters != 0:
-            raise NotImplementedError("simplify_tol_meters: polygon simplification (Douglas-Peucker) is not built")
+        if simplify_method is not None:
+            check_simplify_method(simplify_method)
+        elif simplify_tol_meters != 0:
+            raise NotImplementedError("simplify_tol_meters: shapely's simplification is outside the projection path; ask for the "
+                                      "exact Douglas-Peucker by name: simplify_method='douglas-peucker'")
         if points_in_ROI_CRS is None:
             raise NotImplementedError(
                 "select_mesh_ROI needs points_in_ROI_CRS: the mesh vertices in the ROI's planar CRS (CRS reprojection needs "
@@ -327,6 +341,9 @@ class TexturedPhotogrammetryMesh:
             raise ValueError(f"points_in_ROI_CRS must be ({self.points.shape[0]}, 2) or ({self.points.shape[0]}, 3), got "
                              f"{verts.shape}")
         backend = self.backend
+        if simplify_method is not None:
+            region_of_interest = region_polygons(region_of_interest).simplified(simplify_tol_meters, backend)
+            buffer_meters = buffer_meters + simplify_tol_meters
         mask, stats = points_in_region(backend, region_of_interest, verts, buffer_meters)
         face_IDs, point_IDs, new_faces, counts = backend.submesh_extract(mask, self.faces.astype(np.int32))
         face_IDs, point_IDs, new_faces, stats = (np.asarray(_to_host(a) if hasattr(a, "detach") else a)
@@ -1631,7 +1648,7 @@ class TexturedPhotogrammetryMesh:
 
     def export_face_labels_vector(self, face_labels=None, export_file: PATH_TYPE = None, export_crs=None, label_names=None,
                                   ensure_non_overlapping: bool = False, simplify_tol: float = 0.0, drop_nan: bool = True,
-                                  vis: bool = False, *, points_in_export_CRS):
+                                  vis: bool = False, *, points_in_export_CRS, simplify_method: typing.Optional[str] = None):
         """Export the labels per face as one multipolygon per class (reference: meshes.py:1308-1445; rules X1-X8 of DESIGN.md
         section 8i): `(PlanarPolygons, columns)` in the shape `PlanarPolygons.from_geojson` returns -- one row per present class in
         ascending order (the NaN class last), every hole behind the exterior it lies in; a hole no exterior of its class holds
@@ -1639,16 +1656,28 @@ class TexturedPhotogrammetryMesh:
         NaN class) and, with `label_names`, CLASS_NAMES_KEY (`label_names[int(id)]`, "nan" for NaN).  The coordinates are those
         of `points_in_export_CRS`, which also names the CRS: `export_crs` must be None or equal what the caller passes the points
         in.  `export_file` ending in `.geojson` is written as a FeatureCollection of MultiPolygon features (`json`).  Other
-        extensions, ensure_non_overlapping, simplify_tol > 0, vis and a reprojection raise NotImplementedError.  Where a class
+        extensions, ensure_non_overlapping, vis and a reprojection raise NotImplementedError.  Where a class
         overlaps itself in plan view (a crown above ground of the same class) its rings overlap: the output is then right under
-        the non-zero fill rule only and is not an OGC-valid polygon."""
-        from geograypher_amd.utils.geometric import PlanarPolygons, nest_outline_rings, write_geojson_multipolygons
+        the non-zero fill rule only and is not an OGC-valid polygon.
+
+        simplify_method="douglas-peucker" (any other name: ValueError) simplifies the rings at `simplify_tol` metres with the
+        exact Douglas-Peucker of DESIGN.md section 8q, on the device, where the reference calls `geometry.simplify`
+        (meshes.py:1417): the rings are nested first (X8), then simplified with the junctions of the class map fixed (S9), so
+        two classes keep the same vertices along a shared border; a ring that collapses (S6) is left out, the holes of a
+        collapsed exterior with it, and a class left without rings loses its row.  `self.last_outline_stats` gains the words
+        of the call (simplify_kept_vertices, simplify_collapsed_rings, simplify_passes, ...).  Without simplify_method,
+        simplify_tol > 0 raises NotImplementedError: GEOS's topology-preserving simplifier is not built."""
+        from geograypher_amd.utils.geometric import (PlanarPolygons, check_simplify_method, nest_outline_rings,
+                                                     write_geojson_multipolygons)
 
         if ensure_non_overlapping:
             raise NotImplementedError("ensure_non_overlapping: resolving classes that overlap in plan view needs a polygon overlay "
                                       "(geopandas), which is outside the projection path")
-        if simplify_tol > 0:
-            raise NotImplementedError("simplify_tol: simplification needs shapely, which is outside the projection path")
+        if simplify_method is not None:
+            check_simplify_method(simplify_method)
+        elif simplify_tol > 0:
+            raise NotImplementedError("simplify_tol: shapely's simplification is outside the projection path; ask for the exact "
+                                      "Douglas-Peucker by name: simplify_method='douglas-peucker'")
         if vis:
             raise NotImplementedError("vis: plotting needs geopandas and matplotlib, which are outside the projection path")
         if export_crs is not None:
@@ -1667,19 +1696,28 @@ class TexturedPhotogrammetryMesh:
         holes_of = {}
         for r in np.nonzero(home >= 0)[0]:
             holes_of.setdefault(int(home[r]), []).append(int(r))
+        shown = outlines   # the rings that are written: the traced ones, or (S9) their simplification -- same rings, fewer vertices
+        if simplify_method is not None:
+            shown = outlines.simplified(simplify_tol, self.backend, shared_borders=True)
+        s_off = shown.ring_offsets
         rings, rows, holes, row_class = [], [], [], list(order)
         for r in range(len(ids)):   # every exterior, followed by its holes; an orphan hole: a row of its own behind the class rows
             is_orphan = areas2[r] < 0 and home[r] < 0
-            if areas2[r] > 0 or is_orphan:
+            if (areas2[r] > 0 or is_orphan) and s_off[r + 1] > s_off[r]:   # (a collapsed exterior takes its holes with it)
                 row = int(class_row[r])
                 if is_orphan:
                     row = len(row_class)
                     row_class.append(order[int(class_row[r])])
                 for k, ring in enumerate([r] + holes_of.get(r, [])):
-                    rings.append(outlines.ring_xy[off[ring]:off[ring + 1]])
-                    rows.append(row)
-                    holes.append(k > 0)
-        n_orphans = len(row_class) - len(order)
+                    if s_off[ring + 1] > s_off[ring]:
+                        rings.append(shown.ring_xy[s_off[ring]:s_off[ring + 1]])
+                        rows.append(row)
+                        holes.append(k > 0)
+        n_orphans = len(row_class) - len(order)   # (an orphan's row is made for a ring that is written)
+        if simplify_method is not None:   # a class left without rings loses its row
+            used = np.unique(np.asarray(rows, dtype=np.int64))
+            rows = np.searchsorted(used, rows).tolist()
+            row_class = [row_class[k] for k in used.tolist()]
         polygons = PlanarPolygons(rings, rows, holes, n_polygons=len(row_class))
         class_ids = np.array(row_class, dtype=np.float64)
         columns = {CLASS_ID_KEY: class_ids}
@@ -1687,7 +1725,7 @@ class TexturedPhotogrammetryMesh:
             names = np.empty(len(row_class), dtype=object)
             names[:] = [(label_names[int(v)] if np.isfinite(v) else "nan") for v in class_ids.tolist()]
             columns[CLASS_NAMES_KEY] = names
-        self.last_outline_stats = dict(outlines.stats, orphan_holes=n_orphans, rows=len(row_class))
+        self.last_outline_stats = dict(shown.stats, orphan_holes=n_orphans, rows=len(row_class))
         if export_file is not None:
             write_geojson_multipolygons(export_file, polygons, columns)
         return polygons, columns

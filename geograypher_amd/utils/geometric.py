@@ -327,6 +327,32 @@ class PlanarPolygons:
         q = [snap_to_grid(r) for r in self.rings]
         return np.min([v.min(axis=0) for v in q], axis=0), np.max([v.max(axis=0) for v in q], axis=0)
 
+    def simplified(self, tol_meters, backend=None, fixed=None) -> "PlanarPolygons":
+        """These polygons with every ring simplified by the exact Douglas-Peucker of DESIGN.md section 8q (rules S1-S8) at
+        `tol_meters`, on the device: the rings are snapped to the 1e-6 m grid behind the middle of their bounds, `simplify_rings`
+        keeps a subset of their vertices, and the kept ones come back in metres.  The rows keep their numbers.  S8: a hole stays
+        unless it collapses itself; a row whose exterior rings all collapse loses its holes too and is a row without rings.
+        fixed: (N,) flags over the vertices of `self.snapped(origin)` that must stay (S2), or None.  The call's figures are left
+        in `.last_simplify_stats` of the result.  Like `shapely.simplify(preserve_topology=False)`, a simplified ring may touch
+        or cross itself or a neighbour (S10)."""
+        bounds = self.bounds_snapped()
+        origin = np.zeros(2, dtype=np.int64) if bounds is None else bounds[0] + (bounds[1] - bounds[0]) // 2
+        rv, off, rows, holes, _ = self.snapped(origin)
+        keep, kept_index, out_off, stats = simplify_rings(backend, rv, off, tol_meters, fixed)
+        alive = np.diff(out_off) > 0
+        row_alive = np.zeros(self.n_polygons, dtype=bool)
+        row_alive[rows[alive & (holes == 0)]] = True
+        rings, ring_rows, ring_holes = [], [], []
+        for r in np.nonzero(alive & row_alive[rows])[0]:
+            q = rv[kept_index[out_off[r]:out_off[r + 1]]] + origin
+            rings.append(q.astype(np.float64) * SNAP_GRID_METERS)
+            ring_rows.append(int(rows[r]))
+            ring_holes.append(bool(holes[r]))
+        out = PlanarPolygons(rings, ring_rows, ring_holes, n_polygons=self.n_polygons)
+        out.epsg = self.epsg
+        out.last_simplify_stats = stats
+        return out
+
 
 def _geojson_epsg(crs):
     """The EPSG code of a GeoJSON `crs` member ({"type": "name", "properties": {"name": "urn:ogc:def:crs:EPSG::32610"}} or
@@ -389,6 +415,61 @@ def points_in_region(backend, ROI, points, buffer_meters=0):
     steps = region_buffer_steps(buffer_meters)
     vq, table = snap_with_polygons(points, polygons)
     return backend.points_in_region(vq, *table, steps)
+
+
+# -- ring simplification: exact Douglas-Peucker -------------------------------------------------------------
+SIMPLIFY_METHODS = ("douglas-peucker",)
+SIMPLIFY_STAT_NAMES = ("kept_vertices", "collapsed_rings", "passes", "wide_comparisons", "short_rings")   # GR_SIMPLIFY_STAT_*
+
+
+def check_simplify_method(method, what: str = "simplify_method"):
+    """The one simplification this package has is asked for by name: anything but "douglas-peucker" is a ValueError."""
+    if method not in SIMPLIFY_METHODS:
+        raise ValueError(f"{what} must be one of {SIMPLIFY_METHODS} (or None: no simplification), got {method!r}")
+    return method
+
+
+def simplify_rings(backend, ring_vertices, ring_offsets, tol_meters, fixed=None):
+    """Rules S1-S7 through `backend.ring_simplifier()`: ring_vertices (N, 2) int64 on the 1e-6 m grid and ring_offsets (R + 1,) as
+    `PlanarPolygons.snapped` gives them, fixed (N,) flags or None -> (keep (N,) uint8, kept_index (M,) int32: the kept vertices,
+    ring after ring in input order, out_offsets (R + 1,) int64, stats: a dict over SIMPLIFY_STAT_NAMES), all on the host.
+    `backend`: a `HipRaster` (None: the shared one) or an object with its `ring_simplifier` method."""
+    if backend is None:
+        from geograypher_amd._hip import default_backend
+
+        backend = default_backend()
+    keep, kept_index, out_offsets, stats = backend.ring_simplifier().simplify(ring_vertices, ring_offsets, tol_meters, fixed)
+    keep, kept_index, out_offsets, stats = (_host(a) for a in (keep, kept_index, out_offsets, stats))
+    return (keep.astype(np.uint8), kept_index.astype(np.int32), out_offsets.astype(np.int64),
+            {name: int(stats[k]) for k, name in enumerate(SIMPLIFY_STAT_NAMES)})
+
+
+def shared_border_fixed(ring_q, ring_offsets) -> np.ndarray:
+    """Rule S9: (N,) uint8, 1 at every ring vertex whose POSITION must stay when the rings of a class map are simplified: over
+    all its occurrences in all rings, the position has more than one distinct unordered pair of neighbour positions.  The interior
+    vertices of a border that two classes share have the same two neighbours in both rings and stay free; where a third class
+    joins, or a ring touches another in one point, the position is fixed.  A host sort over (position, neighbour pair) keys."""
+    q = np.asarray(ring_q, dtype=np.int64).reshape(-1, 2)
+    off = np.asarray(ring_offsets, dtype=np.int64).reshape(-1)
+    N = len(q)
+    if N == 0:
+        return np.zeros(0, dtype=np.uint8)
+    n = np.diff(off)
+    idx = np.arange(N, dtype=np.int64)
+    start, length = np.repeat(off[:-1], n), np.repeat(n, n)
+    a, b = q[start + (idx - start - 1) % length], q[start + (idx - start + 1) % length]
+    swap = (a[:, 0] > b[:, 0]) | ((a[:, 0] == b[:, 0]) & (a[:, 1] > b[:, 1]))
+    keys = np.column_stack([q, np.where(swap[:, None], b, a), np.where(swap[:, None], a, b)])
+    order = np.lexsort(keys.T[::-1])
+    s = keys[order]
+    new_position, new_key = np.ones(N, dtype=bool), np.ones(N, dtype=bool)
+    new_position[1:] = np.any(s[1:, :2] != s[:-1, :2], axis=1)
+    new_key[1:] = np.any(s[1:] != s[:-1], axis=1)
+    group = np.cumsum(new_position) - 1
+    distinct = np.bincount(group, weights=new_key)
+    fixed = np.zeros(N, dtype=np.uint8)
+    fixed[order] = distinct[group] > 1
+    return fixed
 
 
 # -- mesh decimation by vertex clustering (DESIGN.md section 8n) ---------------------------------------------------------------------
@@ -513,6 +594,27 @@ class FaceLabelOutlines:
 
     def __len__(self):
         return int(self.ring_offsets.shape[0]) - 1
+
+    def simplified(self, tol_meters, backend, shared_borders: bool = True) -> "FaceLabelOutlines":
+        """These outlines with every ring simplified by the exact Douglas-Peucker of DESIGN.md section 8q at `tol_meters`, on the
+        device (host arrays out).  The R rings keep their numbers, classes and hole flags: a ring that collapses (S6) has no
+        vertices left.  `ring_vertex_ids` and `ring_xy` are carried over through the kept indices.  shared_borders (S9): the
+        positions where the borders of the class map meet are fixed (`shared_border_fixed`), so two classes keep the same
+        vertices along the border they share.  `stats` gains the words of the call as simplify_<name> (SIMPLIFY_STAT_NAMES)."""
+        if self.snapped is None:
+            raise ValueError("these outlines carry no snapped rings to simplify")
+        q = np.asarray(self.snapped[0], dtype=np.int64).reshape(-1, 2)
+        off = _host(self.ring_offsets).astype(np.int64)
+        fixed = shared_border_fixed(q, off) if shared_borders else None
+        _, kept, out_off, words = simplify_rings(backend, q, off, tol_meters, fixed)
+        kept = kept.astype(np.int64)
+        alive = np.nonzero(np.diff(out_off) > 0)[0]
+        areas2 = [0] * len(self)
+        for r, a in zip(alive.tolist(), ring_areas2_exact(q[kept], np.concatenate([out_off[alive], out_off[-1:]]))):
+            areas2[r] = a
+        stats = dict(self.stats, **{f"simplify_{name}": value for name, value in words.items()})
+        return FaceLabelOutlines(out_off, _host(self.ring_class), _host(self.ring_vertex_ids)[kept], _host(self.ring_xy)[kept],
+                                 _host(self.ring_is_hole), stats, (q[kept], areas2))
 
 
 def ring_areas2_exact(ring_q, ring_offsets):

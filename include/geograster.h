@@ -826,6 +826,18 @@ enum {
 };
 #include "geograster_communities.h"
 
+/* Exact Douglas-Peucker on polygon rings (geograster_simplify.h): the words of the statistics block. */
+enum {
+  GR_SIMPLIFY_STAT_KEPT = 0,          /* vertices kept: M = out_offsets[R]                                          */
+  GR_SIMPLIFY_STAT_COLLAPSED = 1,     /* rings of 3 or more vertices that came out empty (S6)                       */
+  GR_SIMPLIFY_STAT_PASSES = 2,        /* passes: the depth of the deepest chain that had an interior vertex         */
+  GR_SIMPLIFY_STAT_WIDE = 3,          /* distances compared beyond 128 bits: interior vertices whose foot lay       */
+                                      /* strictly inside their chord (S3: the squared cross product), over all passes */
+  GR_SIMPLIFY_STAT_SHORT_RINGS = 4,   /* input rings of fewer than 3 vertices, which come out empty                 */
+  GR_SIMPLIFY_STAT_WORDS = 8
+};
+#include "geograster_simplify.h"
+
 #ifdef __cplusplus
 }
 #endif
