@@ -203,6 +203,18 @@ GR_SIMPLIFY_STAT_PASSES = 2
 GR_SIMPLIFY_STAT_WIDE = 3
 GR_SIMPLIFY_STAT_SHORT_RINGS = 4
 GR_SIMPLIFY_STAT_WORDS = 8
+# top-down raster of a mesh: stats words of gr_nadir_raster (include/geograster_nadir.h)
+GR_NADIR_STAT_FACES = 0
+GR_NADIR_STAT_BAD_INDEX = 1
+GR_NADIR_STAT_ZERO_AREA = 2
+GR_NADIR_STAT_NONFINITE_Z = 3
+GR_NADIR_STAT_EMPTY_BOX = 4
+GR_NADIR_STAT_ITEMS = 5
+GR_NADIR_STAT_TESTS = 6
+GR_NADIR_STAT_INSIDE = 7
+GR_NADIR_STAT_SKIPPED = 8
+GR_NADIR_STAT_COVERED = 9
+GR_NADIR_STAT_WORDS = 10
 
 
 class StageTimes(ctypes.Structure):
@@ -350,6 +362,11 @@ _SIMPLIFY_SIGNATURES = {
     "gr_simplify_rings": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
 }
 SIMPLIFY_SYMBOLS = tuple(_SIMPLIFY_SIGNATURES)
+# ... and the call of include/geograster_nadir.h (the top-down raster of a mesh), under the same contract.
+_NADIR_SIGNATURES = {
+    "gr_nadir_raster": [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+}
+NADIR_SYMBOLS = tuple(_NADIR_SIGNATURES)
 
 
 def library_path() -> Path:
@@ -373,7 +390,7 @@ def load_library() -> ctypes.CDLL:
     _torch()
     lib = ctypes.CDLL(str(_LIB_PATH))
     for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES, **_BURN_SIGNATURES,
-                           **_OVERLAP_SIGNATURES, **_COMMUNITIES_SIGNATURES, **_SIMPLIFY_SIGNATURES}.items():
+                           **_OVERLAP_SIGNATURES, **_COMMUNITIES_SIGNATURES, **_SIMPLIFY_SIGNATURES, **_NADIR_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -905,6 +922,76 @@ class RingSimplifier:
                   _ptr(keep if N else None), _ptr(kept_index if N else None), out_offsets.data_ptr(), stats.data_ptr(), hip._stream())
         M = int(out_offsets[R].item())
         return keep, kept_index[:M], out_offsets, stats
+
+
+NADIR_COORD_LIMIT = 1 << 40      # N2: |vertex coordinate in 1/65536 of a cell| stays below it
+NADIR_SMALL_CELLS_MAX = 65536    # N8: the largest small_cells and item_rows gr_nadir_raster takes (0: its defaults, 256 and 16)
+NADIR_ITEM_ROWS_MAX = 1024
+
+
+def check_nadir_tables(verts_q, z, faces):
+    """N1 / N2: the vertex table and the faces of a `NadirRasterizer` are in shape and range -- ValueError naming gr_nadir_raster;
+    -> (V, F).  Face indices are not looked at: the kernel counts the faces it refuses (N3) and `window` raises on them."""
+    name = "gr_nadir_raster"
+    vq, zz, ff = np.asarray(verts_q), np.asarray(z), np.asarray(faces)
+    if vq.ndim != 2 or vq.shape[1] != 2 or vq.dtype.kind not in "iu":
+        raise ValueError(f"{name}: vertices must be a (V, 2) integer array in 1/65536 of a cell, got {vq.shape} {vq.dtype}")
+    V = int(vq.shape[0])
+    if zz.shape != (V,) or zz.dtype.kind != "f":
+        raise ValueError(f"{name}: z must be ({V},) floats, one per vertex, got {zz.shape} {zz.dtype}")
+    if ff.ndim != 2 or ff.shape[1] != 3 or ff.dtype.kind not in "iu":
+        raise ValueError(f"{name}: faces must be an (F, 3) integer array, got {ff.shape} {ff.dtype}")
+    F = int(ff.shape[0])
+    if V >= 2 ** 31 - 1 or F >= 2 ** 31 - 1:
+        raise ValueError(f"{name}: {V} vertices and {F} faces, not both below 2^31 - 1")
+    if vq.size and np.abs(vq.astype(np.int64)).max() >= NADIR_COORD_LIMIT:
+        raise ValueError(f"{name}: a mesh vertex lies 2^40 / 65536 cells or more from the raster's corner")
+    return V, F
+
+
+def check_nadir_window(col_off: int, row_off: int, width: int, height: int, small_cells: int = 0, item_rows: int = 0):
+    """N7 / N8: the window is inside B1's bounds, small_cells and item_rows inside theirs -- ValueError naming gr_nadir_raster."""
+    name, lim = "gr_nadir_raster", BURN_WINDOW_LIMIT
+    if not (width >= 1 and height >= 1 and -lim < col_off < lim and -lim < row_off < lim and col_off + width <= lim and row_off + height <= lim):
+        raise ValueError(f"{name}: a window of {width} x {height} cells at ({col_off}, {row_off}) is empty or leaves (-2^23, 2^23]")
+    if not 0 <= small_cells <= NADIR_SMALL_CELLS_MAX:
+        raise ValueError(f"{name}: small_cells={small_cells} outside [0, {NADIR_SMALL_CELLS_MAX}]")
+    if not 0 <= item_rows <= NADIR_ITEM_ROWS_MAX:
+        raise ValueError(f"{name}: item_rows={item_rows} outside [0, {NADIR_ITEM_ROWS_MAX}]")
+
+
+class NadirRasterizer:
+    """One mesh on the device -- vertices in cell units of a parent grid, their heights, the faces --, rastered from above into any
+    number of windows of that grid (gr_nadir_raster).  Made by `HipRaster.nadir_rasterizer`, which checks
+    the tables (`check_nadir_tables`) and uploads them once."""
+
+    def __init__(self, backend: "HipRaster", verts_q, z, faces):
+        torch = _torch()
+        self.backend = backend
+        self.V, self.F = check_nadir_tables(_host_array(verts_q), _host_array(z), _host_array(faces))
+        self._vq = backend._shaped(verts_q, torch.int64, (self.V, 2), "vertices")
+        self._z = backend._shaped(z, torch.float64, (self.V,), "z (one per vertex)")
+        self._faces = backend._shaped(faces, torch.int32, (self.F, 3), "faces")
+
+    def window(self, col_off: int, row_off: int, width: int, height: int, small_cells: int = 0, item_rows: int = 0):
+        """The window (col_off, row_off, width, height) of the parent grid -> (face (height, width) int32 tensor: the face whose
+        surface is highest at the cell's centre, -1 for none; z (height, width) float64 tensor: that height, NaN for none; stats
+        (GR_NADIR_STAT_WORDS,) int64 tensor).  small_cells and item_rows steer the work decomposition alone (0: the defaults);
+        the planes do not depend on them.  The window is validated on the host first (`check_nadir_window`: ValueError); a face
+        that names a vertex outside [0, V) is a ValueError behind the call.  Waits for the call."""
+        torch = _torch()
+        hip = self.backend
+        col_off, row_off, width, height = int(col_off), int(row_off), int(width), int(height)
+        small_cells, item_rows = int(small_cells), int(item_rows)
+        check_nadir_window(col_off, row_off, width, height, small_cells, item_rows)
+        face = hip._empty((height, width), torch.int32)
+        z = hip._empty((height, width), torch.float64)
+        stats = hip._stats(GR_NADIR_STAT_WORDS)
+        hip._call("gr_nadir_raster", _ptr(self._vq if self.V else None), _ptr(self._z if self.V else None), self.V,
+                  _ptr(self._faces if self.F else None), self.F, col_off, row_off, width, height, small_cells, item_rows,
+                  face.data_ptr(), z.data_ptr(), stats.data_ptr(), hip._stream())
+        hip._check_faces("gr_nadir_raster", stats, GR_NADIR_STAT_BAD_INDEX, self.V)
+        return face, z, stats
 
 
 class RayCommunities:
@@ -2043,6 +2130,13 @@ class HipRaster:
         """A `RingSimplifier` on this backend: `.simplify(ring_vertices, ring_offsets, tol_meters, fixed=None)` is the exact
         Douglas-Peucker of DESIGN.md 8q (`utils.geometric.simplify_rings` and the `simplified` methods go through it)."""
         return RingSimplifier(self)
+
+    def nadir_rasterizer(self, verts_q, z, faces) -> "NadirRasterizer":
+        """A `NadirRasterizer` over a mesh seen from above: verts_q (V, 2) int64, the vertices' x, y in 1/65536 of a cell of a
+        parent raster grid (`utils.geospatial.points_to_cell_units`), z (V,) float64 and faces (F, 3) int32.  The tables are
+        validated on the host (`check_nadir_tables`: ValueError naming gr_nadir_raster) and uploaded once; every
+        `.window(col_off, row_off, width, height, small_cells=0, item_rows=0)` call rasters one window."""
+        return NadirRasterizer(self, verts_q, z, faces)
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):

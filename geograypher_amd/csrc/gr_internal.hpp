@@ -45,11 +45,15 @@
 //                    k_simp_anchor_low, k_simp_rotate, k_simp_chains + two running maxima), a pass over all open chains (k_simp_round<0..4>:
 //                    64-bit atomicMax rounds over the limbs of w and the tie-break, k_simp_publish, k_simp_apply; one word read back),
 //                    collapse and output (k_simp_ring_sums, k_simp_flags, a FlagScan, k_simp_write); integers only; no mesh needed
+//   nadir.hip        the top-down raster of a mesh (gr_nadir_raster): two walks over the (face, cell) pairs -- k_nadir_faces<0, 1>, a lane per face:
+//                    N3, the clipped box of centres, the cells of the small faces, the list of the larger ones; k_nadir_items<0, 1>, a wave per
+//                    item of a listed face -- a 64-bit atomicMax of the height's key, then an atomicMin of the face index where the key is the
+//                    cell's maximum; k_nadir_finish decodes the keys in place; exact integer membership, float64 heights; no mesh needed
 //   cub_steps.hpp    the hipcub calls of the stage calls, each declared once against the call's Plan: SortPairs, SortKeys, ExclusiveSum,
 //                    InclusiveMax, RunLengthEncode, ReduceByKey (size query on construction, typed pointers on run)
 //   compact_dev.hpp  FlagScan, compact_begin, compact_write, k_submesh_write: the scans and the write kernel of polygons.hip's sub-mesh and of decimate.hip;
 //                    communities.hip ranks its surviving communities with FlagScan, simplify.hip compacts its kept ring vertices with it
-//   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip, crs.hip, ortho.hip, overlap.hip and simplify.hip: orient, ring_span, edge_crossing (THE even-odd rule of
+//   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip, crs.hip, ortho.hip, overlap.hip, simplify.hip and nadir.hip: orient, ring_span, edge_crossing (THE even-odd rule of
 //                    k_polygon_weights, k_face_polygon_index and k_points_in_region), load_face, stat_add / stat_add_u32 / stat_max / stat_count
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

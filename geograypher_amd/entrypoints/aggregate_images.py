@@ -58,6 +58,8 @@ def aggregate_images(
     mesh_downsample_method: typing.Union[str, None] = None,
     top_down_simplify_tol: float = 0.0,
     top_down_simplify_method: typing.Union[str, None] = None,
+    top_down_raster_projection_savefile: typing.Union[PATH_TYPE, None] = None,
+    top_down_raster_resolution: typing.Union[float, None] = None,
 ):
     """Aggregate the labels under `label_folder` onto the mesh (see the module docstring).  The reference's arguments and defaults;
     `mesh_downsample != 1` without `mesh_downsample_method`, `vis`, `ROI` without `ROI_points_file`, `DTM_file` without `DTM_points_file` and
@@ -73,7 +75,11 @@ def aggregate_images(
     are per face of the decimated mesh (`mesh.decimated_face_IDs`).  `top_down_simplify_method="douglas-peucker"` simplifies the rings
     of the top-down map at `top_down_simplify_tol` metres on the device (`export_face_labels_vector(simplify_tol=...,
     simplify_method=...)`: exact Douglas-Peucker, shared borders kept consistent); a tolerance without the method raises
-    NotImplementedError and another method name ValueError, both before the aggregation.  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
+    NotImplementedError and another method name ValueError, both before the aggregation.
+    `top_down_raster_projection_savefile` (.tif / .tiff) writes the classes as a uint8 GeoTIFF seen from above, cells of
+    `top_down_raster_resolution` map units on a north-up grid over the vertices (`export_face_labels_raster`: where surfaces
+    overlap in plan view the upper one wins; nodata 255); it uses the same `top_down_points_file` (here (V, 3): z decides) or
+    `top_down_CRS` as the vector map and may be given with or without it.  Its arguments are checked before the aggregation.  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
     from geograypher_amd.cameras.segmentor import SegmentorPhotogrammetryCameraSet
     from geograypher_amd.meshes import TexturedPhotogrammetryMesh, TexturedPhotogrammetryMeshChunked
     from geograypher_amd.predictors.derived_segmentors import LookUpSegmentor
@@ -91,6 +97,16 @@ def aggregate_images(
         raise NotImplementedError("top_down_simplify_tol: shapely's simplification is outside the projection path; ask for the "
                                   "exact Douglas-Peucker by name: top_down_simplify_method='douglas-peucker'")
 
+    if top_down_raster_projection_savefile is None and top_down_raster_resolution is not None:
+        raise ValueError("top_down_raster_resolution is given but top_down_raster_projection_savefile is not: there is no raster to write")
+    if top_down_raster_projection_savefile is not None:
+        if Path(top_down_raster_projection_savefile).suffix.lower() not in (".tif", ".tiff"):
+            raise NotImplementedError(f"top_down_raster_projection_savefile {top_down_raster_projection_savefile}: rasters are "
+                                      "written as .tif / .tiff only")
+        if top_down_raster_resolution is None or not np.isfinite(float(top_down_raster_resolution)) or float(top_down_raster_resolution) <= 0:
+            raise ValueError(f"top_down_raster_projection_savefile needs top_down_raster_resolution, a positive cell size in map "
+                             f"units, got {top_down_raster_resolution!r}")
+
     for name, value, why in (
         ("DTM_file", DTM_file if DTM_points is None else None,
          "the vertices in the DTM's CRS are needed (DTM_points_file); reprojecting them needs pyproj"),
@@ -98,6 +114,8 @@ def aggregate_images(
          "the vertices in the ROI's CRS are needed (ROI_points_file); reprojecting them needs pyproj"),
         ("top_down_vector_projection_savefile", top_down_vector_projection_savefile if top_down_points is None else None,
          "the vector export needs geopandas"),
+        ("top_down_raster_projection_savefile", top_down_raster_projection_savefile if top_down_points is None else None,
+         "the vertices in the map's CRS are needed (top_down_points_file or top_down_CRS); reprojecting them needs pyproj"),
     ):
         if value is not None:
             raise NotImplementedError(f"{name}: {why}, which is outside the projection path")
@@ -138,7 +156,7 @@ def aggregate_images(
     if take_every_nth_camera is not None:
         subset(range(0, len(camera_set), take_every_nth_camera))
 
-    if top_down_points is not None and top_down_vector_projection_savefile is None:
+    if top_down_points is not None and top_down_vector_projection_savefile is None and top_down_raster_projection_savefile is None:
         raise ValueError(f"{'top_down_CRS' if is_CRS_designator(top_down_points) else 'top_down_points_file'} is given but "
                          "top_down_vector_projection_savefile is not: there is no map to write")
 
@@ -157,13 +175,17 @@ def aggregate_images(
         if Path(top_down_vector_projection_savefile).suffix != ".geojson":
             raise NotImplementedError(f"top_down_vector_projection_savefile {top_down_vector_projection_savefile}: files other than "
                                       ".geojson need geopandas, which is outside the projection path")
-    if top_down_vector_projection_savefile is not None and not is_CRS_designator(top_down_points):
+    any_top_down_savefile = top_down_vector_projection_savefile is not None or top_down_raster_projection_savefile is not None
+    if any_top_down_savefile and not is_CRS_designator(top_down_points):
         top_down_points = np.asarray(top_down_points, dtype=np.float64)
         n_original = top_down_points.shape[0] if kept_point_IDs is None else None
         if top_down_points.ndim != 2 or top_down_points.shape[1] not in (2, 3) or \
                 (n_original is not None and n_original != mesh.points.shape[0]) or \
                 (kept_point_IDs is not None and len(kept_point_IDs) and top_down_points.shape[0] <= int(np.max(kept_point_IDs))):
             raise ValueError(f"top_down_points_file must hold the (V, 2) or (V, 3) ORIGINAL vertices, got {top_down_points.shape}")
+        if top_down_raster_projection_savefile is not None and top_down_points.shape[1] != 3:
+            raise ValueError(f"top_down_raster_projection_savefile needs the (V, 3) ORIGINAL vertices in top_down_points_file (z "
+                             f"decides which surface is seen from above), got {top_down_points.shape}")
 
     if ROI is not None and ROI_buffer_radius_meters is not None:
         if camera_points is not None or camera_CRS is not None:
@@ -216,6 +238,14 @@ def aggregate_images(
                                        export_file=top_down_vector_projection_savefile, label_names=label_names,
                                        points_in_export_CRS=points_in_export_CRS, simplify_tol=top_down_simplify_tol,
                                        simplify_method=top_down_simplify_method)
+    if top_down_raster_projection_savefile is not None:   # beside the vector map: the same classes, the upper surface wins
+        points_in_raster_CRS = top_down_points
+        if kept_point_IDs is not None and not is_CRS_designator(points_in_raster_CRS):
+            points_in_raster_CRS = points_in_raster_CRS[kept_point_IDs]
+        Path(top_down_raster_projection_savefile).parent.mkdir(parents=True, exist_ok=True)
+        mesh.export_face_labels_raster(face_labels=np.squeeze(predicted_face_classes, axis=1),
+                                       export_file=top_down_raster_projection_savefile,
+                                       resolution=float(top_down_raster_resolution), points_in_raster_CRS=points_in_raster_CRS)
     return mesh, aggregated_face_labels, predicted_face_classes
 
 
@@ -266,6 +296,11 @@ def parse_args(argv=None):
     parser.add_argument("--top-down-simplify-method", choices=["douglas-peucker"],
                         help="How --top-down-simplify-tol simplifies: douglas-peucker = the exact Douglas-Peucker on the 1e-6 m "
                         "grid, on the device, with the borders two classes share kept identical")
+    parser.add_argument("--top-down-raster-projection-savefile", type=Path,
+                        help="Where the top-down class raster is saved (.tif): per cell the class of the surface seen from above; "
+                        "needs --top-down-raster-resolution and --top-down-points-file (V, 3) or --top-down-CRS")
+    parser.add_argument("--top-down-raster-resolution", type=float,
+                        help="Cell size of --top-down-raster-projection-savefile in map units")
     parser.add_argument("--vis", action="store_true", help="Not available here")
     args = parser.parse_args(argv)
     args.IDs_to_labels = str(args.IDs_to_labels)

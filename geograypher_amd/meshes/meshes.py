@@ -1672,7 +1672,8 @@ class TexturedPhotogrammetryMesh:
 
         if ensure_non_overlapping:
             raise NotImplementedError("ensure_non_overlapping: resolving classes that overlap in plan view needs a polygon overlay "
-                                      "(geopandas), which is outside the projection path")
+                                      "(geopandas), which is outside the projection path; export_face_labels_raster answers it "
+                                      "in raster form (the surface seen from above wins)")
         if simplify_method is not None:
             check_simplify_method(simplify_method)
         elif simplify_tol > 0:
@@ -1729,6 +1730,110 @@ class TexturedPhotogrammetryMesh:
         if export_file is not None:
             write_geojson_multipolygons(export_file, polygons, columns)
         return polygons, columns
+
+    # -- the mesh seen from above on a raster grid (rules N1-N9; the reference has no counterpart) -----
+    def _top_down_grid(self, like, resolution, points_in_raster_CRS, what: str):
+        """(points (V, 3) float64 in the grid's CRS, (height, width, transform), the EPSG code to write or None) of the three
+        top-down raster methods: the grid is `like` or, with `resolution`, `grid_from_bounds` over the vertices -- exactly one of
+        the two.  The code is the grid's; without one, that of a CRS designator given for the points."""
+        from geograypher_amd.utils.geospatial import WGS84CRS, _grid_like, grid_from_bounds, is_CRS_designator
+
+        if (like is None) == (resolution is None):
+            raise ValueError(f"{what} takes the grid (like=) or a cell size (resolution=), exactly one of the two")
+        if points_in_raster_CRS is None:
+            raise NotImplementedError(
+                f"{what} needs points_in_raster_CRS: the mesh vertices (V, 3) in the grid's CRS, or a CRS designator")
+        points = np.ascontiguousarray(self._points_in_CRS(points_in_raster_CRS), dtype=np.float64)
+        if points.shape != (self.points.shape[0], 3):
+            raise ValueError(f"points_in_raster_CRS must be ({self.points.shape[0]}, 3), got {points.shape}")
+        if like is None:
+            like = grid_from_bounds(points[:, :2], resolution)
+        height, width, transform, epsg = _grid_like(like)
+        if epsg is None and is_CRS_designator(points_in_raster_CRS):
+            epsg = WGS84CRS.parse(points_in_raster_CRS).epsg
+        return points, (height, width, tuple(transform)), epsg
+
+    def top_down_face_raster(self, like=None, *, resolution=None, points_in_raster_CRS, return_tensor: bool = False):
+        """The mesh seen from above on a raster grid, on the device (`utils.geospatial.top_down_raster`; rules N1-N9 of DESIGN.md
+        section 8r): (face_ids (H, W) int32, the face whose surface is highest at the cell's centre, -1 where there is none;
+        heights (H, W) float64, that height in the units of the points' z, NaN there; transform (a, b, c, d, e, f) of the grid).
+        like: the grid -- a `PlanarRaster`, a GeoTIFF path (header only) or ((H, W), transform) --, or resolution: the cell size of
+        a north-up grid over the vertices' bounds (`grid_from_bounds`).  points_in_raster_CRS (required, keyword): the mesh
+        vertices (V, 3) in the grid's CRS, or a CRS designator (the vertices are then reprojected on the device).  The statistics
+        of the call are left in `self.last_top_down_stats`."""
+        from geograypher_amd.utils.geospatial import top_down_raster
+
+        points, (height, width, transform), _epsg = self._top_down_grid(like, resolution, points_in_raster_CRS, "top_down_face_raster")
+        face_ids, heights, stats = top_down_raster(points, np.ascontiguousarray(self.faces, dtype=np.int32), ((height, width), transform),
+                                                   backend=self.backend, return_tensor=return_tensor)
+        self.last_top_down_stats = stats
+        return face_ids, heights, transform
+
+    def export_surface_height_raster(self, export_file: PATH_TYPE = None, *, like=None, resolution=None, points_in_raster_CRS,
+                                     nodata: float = -9999.0):
+        """The digital surface model of the mesh: a float64 `PlanarRaster` of the highest surface at every cell centre (arguments
+        as `top_down_face_raster`), `nodata` where no face holds the centre.  `export_file` (.tif / .tiff) is written as a float32
+        GeoTIFF with the transform, nodata and, where known, the EPSG code, which `PlanarRaster.from_geotiff` reads back."""
+        from geograypher_amd.utils.raster import PlanarRaster
+        from geograypher_amd.utils.tiff import write_tiff_deflate
+
+        nodata = float(nodata)
+        if not np.isfinite(nodata) or np.float64(np.float32(nodata)) != nodata:
+            raise ValueError(f"nodata={nodata!r} is not a finite value a float32 file can hold")
+        _check_tiff_suffix(export_file)
+        points, (height, width, transform), epsg = self._top_down_grid(like, resolution, points_in_raster_CRS,
+                                                                        "export_surface_height_raster")
+        from geograypher_amd.utils.geospatial import top_down_raster
+
+        _ids, heights, stats = top_down_raster(points, np.ascontiguousarray(self.faces, dtype=np.int32), ((height, width), transform),
+                                               backend=self.backend)
+        self.last_top_down_stats = stats
+        heights = np.where(np.isnan(heights), nodata, heights)
+        if export_file is not None:
+            write_tiff_deflate(export_file, heights.astype(np.float32), transform=transform, nodata=nodata, epsg=epsg)
+        return PlanarRaster(heights, transform, nodata, epsg)
+
+    def export_face_labels_raster(self, face_labels=None, export_file: PATH_TYPE = None, *, like=None, resolution=None,
+                                  points_in_raster_CRS, nodata: int = 255, drop_nan: bool = True):
+        """The per-face classes as a class raster seen from above: a `PlanarRaster` whose band holds the class of the face whose
+        surface is highest at every cell centre (uint8 values), `nodata` where no face holds the centre or -- with `drop_nan` --
+        the winning face has no label; drop_nan=False is a ValueError when such a face wins a cell (a uint8 raster has no NaN
+        class).  Where classes overlap in plan view the upper surface wins: this is the raster answer to what
+        `export_face_labels_vector(ensure_non_overlapping=True)` asks.  face_labels: (F,) or (F, 1) class ids, NaN = no label;
+        None: the mesh's face texture.  A class above 254 or equal to `nodata`, a `nodata` outside [0, 255]: ValueError.  Grid
+        and points as `top_down_face_raster`.  `export_file` (.tif / .tiff) is written as a uint8 GeoTIFF with the transform,
+        nodata and, where known, the EPSG code."""
+        from geograypher_amd.utils.geospatial import top_down_raster
+        from geograypher_amd.utils.raster import PlanarRaster
+        from geograypher_amd.utils.tiff import write_tiff_deflate
+
+        if isinstance(nodata, bool) or nodata != int(nodata) or not 0 <= int(nodata) <= 255:
+            raise ValueError(f"nodata={nodata!r} is not an integer in [0, 255]")
+        nodata = int(nodata)
+        _check_tiff_suffix(export_file)
+        if face_labels is None:
+            face_labels = self.get_texture(request_vertex_texture=False)
+            if face_labels is None:
+                raise ValueError("export_face_labels_raster: no face labels given and the mesh has no face texture")
+        classes, n_classes = self._face_classes(self._squeezed_1d(face_labels))
+        classes = _host_array(classes).astype(np.int64)
+        if n_classes - 1 > 254:
+            raise ValueError(f"class id {n_classes - 1} does not fit a uint8 class raster (at most 254)")
+        if np.any(classes == nodata):
+            raise ValueError(f"class id {nodata} is the raster's nodata value; choose another nodata")
+        points, (height, width, transform), epsg = self._top_down_grid(like, resolution, points_in_raster_CRS,
+                                                                        "export_face_labels_raster")
+        face_ids, _heights, stats = top_down_raster(points, np.ascontiguousarray(self.faces, dtype=np.int32), ((height, width), transform),
+                                                    backend=self.backend)
+        self.last_top_down_stats = stats
+        cell_class = np.where(face_ids >= 0, classes[np.maximum(face_ids, 0)] if len(classes) else -1, -2)   # -1: no label, -2: no face
+        if not drop_nan and np.any(cell_class == -1):
+            raise ValueError(f"{int(np.sum(cell_class == -1))} cells are won by a face without a label, and a uint8 class raster has "
+                             "no NaN class: keep drop_nan=True (they become nodata)")
+        out = np.where(cell_class >= 0, cell_class, nodata).astype(np.uint8)
+        if export_file is not None:
+            write_tiff_deflate(export_file, out, transform=transform, nodata=nodata, epsg=epsg)
+        return PlanarRaster(out, transform, nodata, epsg)
 
     # -- raster samples (DESIGN.md "Raster samples"; reference: meshes.py:1449-1629) ---------------------------------------------
     def add_label(self, label_name, label_ID):
@@ -2154,6 +2259,12 @@ def _to_host(t) -> np.ndarray:
     host.copy_(t, non_blocking=True)
     torch.cuda.current_stream(t.device).synchronize()
     return host.numpy()
+
+
+def _check_tiff_suffix(export_file):
+    """The raster exports write GeoTIFF only: NotImplementedError for another extension."""
+    if export_file is not None and Path(export_file).suffix.lower() not in (".tif", ".tiff"):
+        raise NotImplementedError(f"export_file {export_file}: rasters are written as .tif / .tiff only")
 
 
 def _host_array(x) -> np.ndarray:

@@ -144,22 +144,31 @@ def points_or_CRS(file_name: str, points_file, crs_name: str, crs):
 
 
 # -- the class counts of the raster cells under polygons (reference: utils/geospatial.py:150-211) ------------
+def points_to_cell_units(xy, inverse, what: str = "point"):
+    """THE arithmetic of rule Z1 (and N2): xy (n, 2) float64 in the raster's CRS -> (n, 2) int64 pixel coordinates times 65536,
+    with the raster's `inverse` (ia, ib, ic, id, ie, if) in float64, every operation rounded on its own in the order of rule T2:
+    col = (ia x + ib y) + ic, row = (id x + ie y) + if, q = rint(65536 value).  ValueError naming `what` for a value that is
+    not finite or has |q| >= 2^40."""
+    ia, ib, ic, id_, ie, if_ = (np.float64(v) for v in inverse)
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    x, y = xy[:, 0], xy[:, 1]
+    col = (x * ia + y * ib) + ic
+    row = (x * id_ + y * ie) + if_
+    q = np.rint(np.stack([col, row], axis=1) * 65536.0)
+    if q.size and not np.all(np.abs(q) < 2.0 ** 40):
+        raise ValueError(f"a {what} is not finite or lies 2^40 / 65536 cells or more from the raster's corner")
+    return q.astype(np.int64)
+
+
 def rings_to_cell_units(rings, inverse):
     """Rule Z1: ring vertices (x, y) in the raster's CRS -> int64 pixel coordinates times 65536, with the raster's `inverse`
     (ia, ib, ic, id, ie, if) in float64, every operation rounded on its own in the order of rule T2: col = (ia x + ib y) + ic,
     row = (id x + ie y) + if, q = rint(65536 value).  rings: a list of (n, 2) arrays -> (ring_vertices (N, 2) int64, ring_offsets
     (R + 1,) int64).  ValueError for a value that is not finite or has |q| >= 2^40."""
-    ia, ib, ic, id_, ie, if_ = (np.float64(v) for v in inverse)
     verts, offsets = [], [0]
     for ring in rings:
-        ring = np.asarray(ring, dtype=np.float64).reshape(-1, 2)
-        x, y = ring[:, 0], ring[:, 1]
-        col = (x * ia + y * ib) + ic
-        row = (x * id_ + y * ie) + if_
-        q = np.rint(np.stack([col, row], axis=1) * 65536.0)
-        if q.size and not np.all(np.abs(q) < 2.0 ** 40):
-            raise ValueError("a polygon vertex is not finite or lies 2^40 / 65536 cells or more from the raster's corner")
-        verts.append(q.astype(np.int64))
+        q = points_to_cell_units(np.asarray(ring, dtype=np.float64).reshape(-1, 2), inverse, "polygon vertex")
+        verts.append(q)
         offsets.append(offsets[-1] + len(q))
     ring_vertices = np.concatenate(verts) if verts else np.zeros((0, 2), dtype=np.int64)
     return np.ascontiguousarray(ring_vertices.reshape(-1, 2)), np.asarray(offsets, dtype=np.int64)
@@ -345,6 +354,80 @@ def burn_polygons(polygons, values, like, fill: int = 255, backend=None, max_dev
         rows_t, out_t, _stats = burner.window(*window, burn_work_items(boxes, ranges, window), fill=int(fill), want_values=not rows)
         result[row0:row0 + n] = _to_host(rows_t if rows else out_t)
     return result
+
+
+# -- the mesh seen from above on a raster grid (the reference has no counterpart) ------------------------------
+TOP_DOWN_STAT_NAMES = ("faces", "bad_index", "zero_area", "nonfinite_z", "empty_box", "items", "tests", "inside", "skipped", "covered")
+GRID_SIDE_LIMIT = 1 << 23   # Z2: H, W stay below it
+
+
+def grid_from_bounds(points_xy, resolution):
+    """A north-up grid of square cells of `resolution` CRS units that holds the points (n, 2+): ((H, W), transform) with transform
+    (a, b, c, d, e, f) = (res, 0, floor(xmin / res) res, 0, -res, ceil(ymax / res) res), W = ceil((xmax - c) / res), H =
+    ceil((f - ymin) / res), both at least 1.  ValueError for a resolution that is not positive and finite, points that are not
+    finite (or none), or H, W >= 2^23."""
+    res = float(resolution)
+    if not np.isfinite(res) or res <= 0:
+        raise ValueError(f"resolution={resolution!r} is not a positive, finite cell size")
+    xy = np.asarray(points_xy, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] < 2 or xy.shape[0] < 1 or not np.all(np.isfinite(xy[:, :2])):
+        raise ValueError("grid_from_bounds needs at least one point, (n, 2) or (n, 3), all finite")
+    xmin, xmax, ymin, ymax = xy[:, 0].min(), xy[:, 0].max(), xy[:, 1].min(), xy[:, 1].max()
+    c, f = float(np.floor(xmin / res) * res), float(np.ceil(ymax / res) * res)
+    W, H = max(int(np.ceil((xmax - c) / res)), 1), max(int(np.ceil((f - ymin) / res)), 1)
+    if H >= GRID_SIDE_LIMIT or W >= GRID_SIDE_LIMIT:
+        raise ValueError(f"resolution={res}: the grid would have {H} x {W} cells, not below 2^23 on both sides")
+    return (H, W), (res, 0.0, c, 0.0, -res, f)
+
+
+def top_down_raster(points, faces, like, backend=None, max_device_bytes=None, return_tensor: bool = False):
+    """The mesh seen from above on a raster grid, on the device (`HipRaster.nadir_rasterizer`, gr_nadir_raster; rules N1-N9 of
+    DESIGN.md 8r): points (V, 3) float64 in the grid's CRS, faces (F, 3) integers, like: the grid -- a `PlanarRaster`, a GeoTIFF
+    path (only its header is read) or ((height, width), transform) -> (face_ids (height, width) int32: the face whose surface is
+    HIGHEST at the cell's centre, -1 where no face holds it; heights (height, width) float64: that height, NaN there; stats: a
+    dict of `TOP_DOWN_STAT_NAMES`, summed over the bands).  A centre exactly on an edge or a vertex belongs to one face (rule
+    Z3 of `zonal_class_counts`, on the triangle), so faces that tile a region partition its cells; vertical faces take no part.
+    Equal heights go to the lower face index.  ValueError for a vertex that is not finite or lies 2^40 / 65536 cells or more from
+    the grid's corner, a face that names no vertex, H or W >= 2^23.  The grid is rastered in bands of rows that take at most
+    `max_device_bytes` of device memory, 12 bytes a cell (default: the assembly's); the bands do not change a byte.  Host
+    arrays unless `return_tensor` (then the two planes are tensors on the backend's device)."""
+    from geograypher_amd.predictors.ortho_segmentor import DEFAULT_MAX_DEVICE_BYTES, MAX_BAND_ROWS
+    from geograypher_amd.utils.raster import invert_affine
+
+    height, width, transform, _epsg = _grid_like(like)
+    if not (1 <= height < GRID_SIDE_LIMIT and 1 <= width < GRID_SIDE_LIMIT):
+        raise ValueError(f"the grid has {height} x {width} cells, not inside [1, 2^23) on both sides")
+    points = np.asarray(points.cpu() if hasattr(points, "cpu") else points, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be (V, 3), got {points.shape}")
+    faces = np.asarray(faces.cpu() if hasattr(faces, "cpu") else faces)
+    if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in "iu":
+        raise ValueError(f"faces must be an (F, 3) integer array, got {faces.shape} {faces.dtype}")
+    verts_q = points_to_cell_units(points[:, :2], invert_affine(transform), "mesh vertex")
+    backend = backend if backend is not None else _default_backend()
+    rasterizer = backend.nadir_rasterizer(verts_q, np.ascontiguousarray(points[:, 2]), faces.astype(np.int32))
+    budget = DEFAULT_MAX_DEVICE_BYTES if max_device_bytes is None else int(max_device_bytes)
+    band = int(max(1, min(height, MAX_BAND_ROWS, budget // (12 * max(width, 1)))))
+    face_parts, z_parts, totals = [], [], np.zeros(len(TOP_DOWN_STAT_NAMES), dtype=np.int64)
+    for row0 in range(0, height, band):
+        face_t, z_t, stats = rasterizer.window(0, row0, width, min(band, height - row0))
+        if not return_tensor:
+            face_t, z_t = _to_host(face_t), _to_host(z_t)
+        face_parts.append(face_t)
+        z_parts.append(z_t)
+        s = _to_host(stats).astype(np.int64)
+        totals += s[:len(totals)]
+        # the words about the faces themselves are the same in every band
+        totals[:4] = s[:4]
+    if len(face_parts) == 1:
+        face_ids, heights = face_parts[0], z_parts[0]
+    elif return_tensor and hasattr(face_parts[0], "device"):
+        import torch
+
+        face_ids, heights = torch.cat(face_parts), torch.cat(z_parts)
+    else:
+        face_ids, heights = np.concatenate(face_parts), np.concatenate(z_parts)
+    return face_ids, heights, {k: int(v) for k, v in zip(TOP_DOWN_STAT_NAMES, totals)}
 
 
 # -- polygon-on-polygon overlap areas (DESIGN.md 8o, A1-A9; reference: utils/geospatial.py:221-329, gpd.overlay) ------------------------

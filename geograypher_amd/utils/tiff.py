@@ -11,12 +11,13 @@ from pathlib import Path
 
 import numpy as np
 
-_TYPES = {np.dtype(np.uint8): 8, np.dtype(np.uint16): 16, np.dtype(np.uint32): 32}
+_TYPES = {np.dtype(np.uint8): 8, np.dtype(np.uint16): 16, np.dtype(np.uint32): 32, np.dtype(np.float32): 32}
 
 
 def write_tiff_deflate(path, array: np.ndarray, level: int = 6, strip_bytes: int = 1 << 20, transform=None, nodata=None,
                        epsg=None) -> None:
-    """(H, W) or (H, W, C) uint8 / uint16 / uint32 array -> deflate-compressed TIFF at `path`.
+    """(H, W) or (H, W, C) uint8 / uint16 / uint32 / float32 array -> deflate-compressed TIFF at `path` (SampleFormat 1, unsigned
+    integer, or 3, IEEE floating point: a height raster).
 
     Optional georeferencing makes it a GeoTIFF that `PlanarRaster.from_geotiff` and GDAL read: transform (a, b, c, d, e, f) with
     x = a col + b row + c, y = d col + e row + f of pixel CORNERS -- ModelPixelScale + ModelTiepoint when b = d = 0 and a > 0 > e,
@@ -30,6 +31,7 @@ def write_tiff_deflate(path, array: np.ndarray, level: int = 6, strip_bytes: int
     a = a.astype(a.dtype.newbyteorder("<"), copy=False)
     h, w, c = a.shape
     bits = _TYPES[np.dtype(array.dtype)]
+    sample_format = 3 if a.dtype.kind == "f" else 1               # IEEE floating point / unsigned integer
     row_bytes = w * c * (bits // 8)
     rows_per_strip = max(1, min(h, strip_bytes // max(row_bytes, 1)))
     strips = [zlib.compress(a[r0 : r0 + rows_per_strip].tobytes(), level) for r0 in range(0, h, rows_per_strip)]
@@ -68,11 +70,11 @@ def write_tiff_deflate(path, array: np.ndarray, level: int = 6, strip_bytes: int
     tags.append(entry(279, LONG, n, counts[0] if n == 1 else out_of_line("I", counts)))
     tags.append(entry(284, SHORT, 1, 1))                          # PlanarConfiguration: chunky
     if c == 1:
-        tags.append(entry(339, SHORT, 1, 1))                      # SampleFormat: unsigned integer
+        tags.append(entry(339, SHORT, 1, sample_format))          # SampleFormat
     elif c == 2:
-        tags.append(struct.pack("<HHIHH", 339, SHORT, 2, 1, 1))
+        tags.append(struct.pack("<HHIHH", 339, SHORT, 2, sample_format, sample_format))
     else:
-        tags.append(entry(339, SHORT, c, out_of_line("H", [1] * c)))
+        tags.append(entry(339, SHORT, c, out_of_line("H", [sample_format] * c)))
     DOUBLE, ASCII = 12, 2
     if transform is not None:
         ta, tb, tc, td, te, tf = (float(v) for v in transform)

@@ -838,6 +838,22 @@ enum {
 };
 #include "geograster_simplify.h"
 
+/* Top-down raster of a mesh (geograster_nadir.h): the words of the statistics block. */
+enum {
+  GR_NADIR_STAT_FACES = 0,            /* faces taking part (N3)                                                     */
+  GR_NADIR_STAT_BAD_INDEX = 1,        /* faces that name a vertex outside [0, V)                                    */
+  GR_NADIR_STAT_ZERO_AREA = 2,        /* faces whose snapped triangle has no area: vertical walls, needles          */
+  GR_NADIR_STAT_NONFINITE_Z = 3,      /* faces with a z that is not finite                                          */
+  GR_NADIR_STAT_EMPTY_BOX = 4,        /* faces taking part whose box holds no cell centre of the window             */
+  GR_NADIR_STAT_ITEMS = 5,            /* items of the faces above small_cells (64 columns x item_rows rows each)    */
+  GR_NADIR_STAT_TESTS = 6,            /* (face, cell) tests: the centres of the clipped boxes                       */
+  GR_NADIR_STAT_INSIDE = 7,           /* (face, cell) memberships (N4)                                              */
+  GR_NADIR_STAT_SKIPPED = 8,          /* memberships skipped by N5: denominator 0 or a height that is not finite    */
+  GR_NADIR_STAT_COVERED = 9,          /* cells of the window that a face covers                                     */
+  GR_NADIR_STAT_WORDS = 10
+};
+#include "geograster_nadir.h"
+
 #ifdef __cplusplus
 }
 #endif
