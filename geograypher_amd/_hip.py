@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import threading
+from collections import namedtuple
 from pathlib import Path
 from typing import Optional
 
@@ -507,6 +508,10 @@ def _count_then_fill(name: str, attempt, cap: int, something_to_fill, check):
 POLYGON_RING_CHUNK = 512  # ring records per LDS chunk of gr_project_polygon_pairs (PAIR_CHUNK, csrc/project.hip)
 
 
+# A ring table on the device (`HipRaster._ring_table`): tensors, `box` and `rh` None where the call takes none, and the counts.
+RingTable = namedtuple("RingTable", "rv off rp box rh N R P")
+
+
 # The checks of the tables `PairAccumulator` takes: plain functions of host arrays (no device, no library).
 def _host_array(a) -> np.ndarray:
     """tensor or array -> host array"""
@@ -610,58 +615,54 @@ def check_zonal_tables(H: int, W: int, nodata, ring_vertices, ring_offsets, ring
         raise ValueError(f"{name}: a raster of {H} x {W} cells is outside [1, 2^23) a side")
     if not 1 <= num_classes <= GR_ZONAL_MAX_CLASSES:
         raise ValueError(f"{name}: num_classes={num_classes} outside [1, {GR_ZONAL_MAX_CLASSES}]")
-    R = _check_ring_table(name, ring_vertices, ring_offsets, ring_polygon, n_polygons)
-    it = np.asarray(items, dtype=np.int64)
-    if it.ndim != 2 or it.shape[1] != GR_ZONAL_ITEM_INTS:
-        raise ValueError(f"{name}: work items must be (n, {GR_ZONAL_ITEM_INTS}), got {it.shape}")
-    if it.shape[0]:
-        p, c0, r0, w, h, lo, hi = it.T
-        bad = ((p < 0) | (p >= n_polygons) | (c0 < 0) | (r0 < 0) | (w < 1) | (h < 1) | (w > GR_ZONAL_BLOCK_W) | (h > GR_ZONAL_BLOCK_H)
-               | (c0 + w > W) | (r0 + h > H) | (lo < 0) | (hi < lo) | (hi > R))
-        if np.any(bad):
-            k = int(np.nonzero(bad)[0][0])
-            raise ValueError(f"{name}: work item {k} {tuple(int(v) for v in it[k])} names no polygon row, no block of at most "
-                             f"{GR_ZONAL_BLOCK_W} x {GR_ZONAL_BLOCK_H} cells inside the raster, or no ring range")
+    _, R = _check_ring_table(name, ring_vertices, ring_offsets, ring_polygon, n_polygons)
+    _check_cell_items(name, items, n_polygons, R, (0, 0, W, H), "raster")
 
 
 BURN_WINDOW_LIMIT = 1 << 23   # B1: |offsets| of a burn window stay below it, its far edges at or below it
 
 
-def _check_ring_table(name: str, ring_vertices, ring_offsets, ring_polygon, n_polygons: int) -> int:
-    """Z1: the ring table of gr_zonal_class_counts and gr_burn_polygons is in range -- ValueError naming the call; -> R."""
-    if n_polygons < 0 or n_polygons >= 2 ** 31:
-        raise ValueError(f"{name}: {n_polygons} polygon rows")
+def _check_ring_table(name: str, ring_vertices, ring_offsets, ring_polygon, n_polygons: int, side: Optional[str] = None,
+                      inclusive: bool = False):
+    """What every ring table holds (Z1, B1, A1, S1) -- ValueError naming the call and the table's `side`, if any; -> (N, R).
+    (N, 2) integer vertices with |coordinate| below 2^40 (cell units) or, `inclusive`, at or below it (the 1e-6 m grid), offsets
+    rising from 0 to N, rows non-decreasing in [0, n_polygons) unless `ring_polygon` is None; N, R, P below 2^31."""
+    of_table = f" of table {side}" if side else ""
+    if not 0 <= n_polygons < 2 ** 31:
+        raise ValueError(f"{name}: {n_polygons} polygon rows{of_table}")
     rv = np.asarray(ring_vertices)
     if rv.ndim != 2 or rv.shape[1] != 2 or rv.dtype.kind not in "iu":
-        raise ValueError(f"{name}: ring vertices must be an (N, 2) integer array, got {rv.shape} {rv.dtype}")
-    if rv.size and np.abs(rv.astype(np.int64)).max() >= 2 ** 40:
-        raise ValueError(f"{name}: a ring vertex lies 2^40 / 65536 cells or more from the raster's corner")
-    rp = np.asarray(ring_polygon, dtype=np.int64).reshape(-1)
-    R = rp.shape[0]
-    _check_offsets(np.asarray(ring_offsets, dtype=np.int64).reshape(-1), R, rv.shape[0], "rings", f"{name}: ring", "ring vertices")
-    if R and (rp.min() < 0 or rp.max() >= n_polygons or np.any(np.diff(rp) < 0)):
-        raise ValueError(f"{name}: ring_polygon must be non-decreasing inside [0, {n_polygons})")
-    return R
+        raise ValueError(f"{name}: {'the ring vertices' + of_table if side else 'ring vertices'} must be an (N, 2) integer array, "
+                         f"got {rv.shape} {rv.dtype}")
+    N = int(rv.shape[0])
+    if N >= 2 ** 31:
+        raise ValueError(f"{name}: {N} ring vertices{of_table}, not below 2^31")
+    if rv.size:
+        far = max(int(rv.max()), -int(rv.min()))
+        if far > 2 ** 40 and inclusive:
+            raise ValueError(f"{name}: a ring vertex{of_table} lies more than 2^40 grid steps from the {'common ' if side else ''}origin")
+        if far >= 2 ** 40 and not inclusive:
+            raise ValueError(f"{name}: a ring vertex{of_table} lies 2^40 / 65536 cells or more from the raster's corner")
+    off = np.asarray(ring_offsets, dtype=np.int64).reshape(-1)
+    rp = None if ring_polygon is None else np.asarray(ring_polygon, dtype=np.int64).reshape(-1)
+    R = off.shape[0] - 1 if rp is None else rp.shape[0]
+    _check_offsets(off, R, N, "rings", f"{name}: table {side}: ring" if side else f"{name}: ring", "ring vertices")
+    if rp is not None and R and (rp.min() < 0 or rp.max() >= n_polygons or np.any(np.diff(rp) < 0)):
+        raise ValueError(f"{name}: {'the ring_polygon' + of_table if side else 'ring_polygon'} must be non-decreasing inside [0, {n_polygons})")
+    return N, R
 
 
-def check_burn_tables(ring_vertices, ring_offsets, ring_polygon, n_polygons: int, values=None):
-    """B1 / B7: the ring table and the values of a `PolygonBurner` are in range -- ValueError naming gr_burn_polygons; -> R."""
-    name = "gr_burn_polygons"
-    R = _check_ring_table(name, ring_vertices, ring_offsets, ring_polygon, int(n_polygons))
-    if values is not None:
-        v = np.asarray(values)
-        if v.shape != (int(n_polygons),) or v.dtype.kind not in "iu" or (v.size and (v.min() < 0 or v.max() > 255)):
-            raise ValueError(f"{name}: values must be ({int(n_polygons)},) integers in [0, 255], got {v.shape} {v.dtype}")
-    return R
-
-
-def check_burn_window(col_off: int, row_off: int, width: int, height: int, items, n_polygons: int, n_rings: int, fill: int = 255):
-    """B1 / B5 / B7: the window is inside the bounds and every work item inside the window -- ValueError naming gr_burn_polygons."""
-    name, lim = "gr_burn_polygons", BURN_WINDOW_LIMIT
+def _check_window(name: str, col_off: int, row_off: int, width: int, height: int):
+    """B1: a window of a cell grid is not empty and stays inside (-2^23, 2^23] -- ValueError naming the call."""
+    lim = BURN_WINDOW_LIMIT
     if not (width >= 1 and height >= 1 and -lim < col_off < lim and -lim < row_off < lim and col_off + width <= lim and row_off + height <= lim):
         raise ValueError(f"{name}: a window of {width} x {height} cells at ({col_off}, {row_off}) is empty or leaves (-2^23, 2^23]")
-    if not 0 <= fill <= 255:
-        raise ValueError(f"{name}: fill={fill} outside [0, 255]")
+
+
+def _check_cell_items(name: str, items, n_polygons: int, n_rings: int, window, inside: str):
+    """Z6 / B5 / B7: every work item names a row, a block of at most GR_ZONAL_BLOCK_W x GR_ZONAL_BLOCK_H cells inside `window`
+    (col_off, row_off, width, height; `inside` is its word in the message) and a ring range -- ValueError naming the call."""
+    col_off, row_off, width, height = window
     it = np.asarray(items)
     if it.ndim != 2 or it.shape[1] != GR_ZONAL_ITEM_INTS or it.dtype.kind not in "iu":
         raise ValueError(f"{name}: work items must be (n, {GR_ZONAL_ITEM_INTS}) integers, got {it.shape} {it.dtype}")
@@ -672,7 +673,27 @@ def check_burn_window(col_off: int, row_off: int, width: int, height: int, items
         if np.any(bad):
             k = int(np.nonzero(bad)[0][0])
             raise ValueError(f"{name}: work item {k} {tuple(int(v) for v in it[k])} names no polygon row, no block of at most "
-                             f"{GR_ZONAL_BLOCK_W} x {GR_ZONAL_BLOCK_H} cells inside the window, or no ring range")
+                             f"{GR_ZONAL_BLOCK_W} x {GR_ZONAL_BLOCK_H} cells inside the {inside}, or no ring range")
+
+
+def check_burn_tables(ring_vertices, ring_offsets, ring_polygon, n_polygons: int, values=None):
+    """B1 / B7: the ring table and the values of a `PolygonBurner` are in range -- ValueError naming gr_burn_polygons; -> R."""
+    name = "gr_burn_polygons"
+    _, R = _check_ring_table(name, ring_vertices, ring_offsets, ring_polygon, int(n_polygons))
+    if values is not None:
+        v = np.asarray(values)
+        if v.shape != (int(n_polygons),) or v.dtype.kind not in "iu" or (v.size and (v.min() < 0 or v.max() > 255)):
+            raise ValueError(f"{name}: values must be ({int(n_polygons)},) integers in [0, 255], got {v.shape} {v.dtype}")
+    return R
+
+
+def check_burn_window(col_off: int, row_off: int, width: int, height: int, items, n_polygons: int, n_rings: int, fill: int = 255):
+    """B1 / B5 / B7: the window is inside the bounds and every work item inside the window -- ValueError naming gr_burn_polygons."""
+    name = "gr_burn_polygons"
+    _check_window(name, col_off, row_off, width, height)
+    if not 0 <= fill <= 255:
+        raise ValueError(f"{name}: fill={fill} outside [0, 255]")
+    _check_cell_items(name, items, n_polygons, n_rings, (col_off, row_off, width, height), "window")
 
 
 class PolygonBurner:
@@ -680,16 +701,13 @@ class PolygonBurner:
     Made by `HipRaster.polygon_burner`, which checks the tables (`check_burn_tables`) and uploads them once."""
 
     def __init__(self, backend: "HipRaster", ring_vertices, ring_offsets, ring_polygon, n_polygons: int, values=None):
-        torch = _torch()
         rv_h, off_h, rp_h = (_host_array(x) for x in (ring_vertices, ring_offsets, ring_polygon))
         val_h = None if values is None else _host_array(values)
         self.backend = backend
         self.n_polygons = int(n_polygons)
         self.n_rings = check_burn_tables(rv_h, off_h, rp_h, self.n_polygons, val_h)
-        self._rv = backend._shaped(ring_vertices, torch.int64, ("N", 2), "ring vertices")
-        self._rp = backend._dev(ring_polygon, torch.int32).reshape(-1)
-        self._off = backend._shaped(ring_offsets, torch.int64, (self.n_rings + 1,), "ring offsets (one more than ring polygons)")
-        self._values = None if values is None else backend._dev(values, torch.uint8).reshape(-1)
+        self._rv, self._off, self._rp = backend._ring_table(ring_vertices, ring_offsets, ring_polygon, n_polygons=self.n_polygons)[:3]
+        self._values = None if values is None else backend._dev(values, _torch().uint8).reshape(-1)
 
     def window(self, col_off: int, row_off: int, width: int, height: int, items, fill: int = 255, want_values: bool = True):
         """The window (col_off, row_off, width, height) of the parent grid; items (n, GR_ZONAL_ITEM_INTS) int32 of
@@ -724,25 +742,16 @@ def _check_overlap_table(name: str, side: str, table) -> int:
     rv, off, rp, rh, box = (np.asarray(x) for x in table)
     if box.ndim != 2 or box.shape[1] != 4 or box.dtype.kind not in "iu":
         raise ValueError(f"{name}: the polygon boxes of table {side} must be a (P, 4) integer array, got {box.shape} {box.dtype}")
-    if rv.ndim != 2 or rv.shape[1] != 2 or rv.dtype.kind not in "iu":
-        raise ValueError(f"{name}: the ring vertices of table {side} must be an (N, 2) integer array, got {rv.shape} {rv.dtype}")
-    if rv.shape[0] >= 2 ** 31:
-        raise ValueError(f"{name}: table {side} has {rv.shape[0]} ring vertices, not below 2^31")
     P = box.shape[0]
-    R = rp.reshape(-1).shape[0]
     if P >= 2 ** 31 - 1:
         raise ValueError(f"{name}: table {side} has {P} polygon rows")
-    for what, values in (("ring vertex", rv), ("polygon box", box)):
-        if values.size and np.abs(values.astype(np.int64)).max() > OVERLAP_COORD_LIMIT:
-            raise ValueError(f"{name}: a {what} of table {side} lies more than 2^40 grid steps from the common origin")
-    rp = rp.astype(np.int64).reshape(-1)
-    _check_offsets(np.asarray(off, dtype=np.int64).reshape(-1), R, rv.shape[0], "rings", f"{name}: table {side}: ring", "ring vertices")
-    if R and (rp.min() < 0 or rp.max() >= P or np.any(np.diff(rp) < 0)):
-        raise ValueError(f"{name}: the ring_polygon of table {side} must be non-decreasing inside [0, {P})")
+    _, R = _check_ring_table(name, rv, off, rp, P, side, inclusive=True)
+    if box.size and np.abs(box.astype(np.int64)).max() > OVERLAP_COORD_LIMIT:
+        raise ValueError(f"{name}: a polygon box of table {side} lies more than 2^40 grid steps from the common origin")
     if rh.reshape(-1).shape[0] != R or rh.dtype.kind not in "iub":
         raise ValueError(f"{name}: table {side} needs one integer hole flag per ring, got {rh.shape} {rh.dtype}")
     if rv.shape[0]:   # A3: the box of a row holds every vertex of the row (the baseline Y lies at or below both rows)
-        row = np.repeat(rp, np.diff(np.asarray(off, dtype=np.int64).reshape(-1)))
+        row = np.repeat(rp.astype(np.int64).reshape(-1), np.diff(np.asarray(off, dtype=np.int64).reshape(-1)))
         b = box.astype(np.int64)[row]
         q = rv.astype(np.int64)
         if np.any((q[:, 0] < b[:, 0]) | (q[:, 1] < b[:, 1]) | (q[:, 0] > b[:, 2]) | (q[:, 1] > b[:, 3])):
@@ -815,7 +824,7 @@ class PolygonOverlap:
         """(n, 2) int32 tensor: the candidate pairs (row of a, row of b) of rule A2, ascending by (a, b).  Reads the count back."""
         torch = _torch()
         hip = self.backend
-        box_a, box_b, Pa, Pb = self._a[3], self._b[3], self._a[7], self._b[7]
+        box_a, box_b, Pa, Pb = self._a.box, self._b.box, self._a.P, self._b.P
         offsets = hip._empty((Pa + 1,), torch.int64)
         hip._call("gr_polygon_box_pairs_count", _ptr(box_a if Pa else None), Pa, _ptr(box_b if Pb else None), Pb, offsets.data_ptr(),
                   hip._stream())
@@ -835,7 +844,7 @@ class PolygonOverlap:
         torch = _torch()
         hip = self.backend
         (_, off_a, rp_a, _, _), (_, off_b, rp_b, _, _) = self.host
-        check_overlap_items(_host_array(pairs), _host_array(items), off_a, rp_a, self._a[7], off_b, rp_b, self._b[7])
+        check_overlap_items(_host_array(pairs), _host_array(items), off_a, rp_a, self._a.P, off_b, rp_b, self._b.P)
         pr_t = hip._shaped(pairs, torch.int32, ("n", 2), "pairs")
         it_t = hip._shaped(items, torch.int32, ("m", GR_OVERLAP_ITEM_INTS), "work items")
         n = int(pr_t.shape[0])
@@ -848,9 +857,8 @@ class PolygonOverlap:
 
     @staticmethod
     def _table_args(t):
-        rv_t, off_t, rp_t, box_t, rh_t, N, R, P = t
-        return (_ptr(rv_t if N else None), N, off_t.data_ptr(), _ptr(rp_t if R else None), _ptr(rh_t if R else None), R,
-                _ptr(box_t if P else None), P)
+        return (_ptr(t.rv if t.N else None), t.N, t.off.data_ptr(), _ptr(t.rp if t.R else None), _ptr(t.rh if t.R else None), t.R,
+                _ptr(t.box if t.P else None), t.P)
 
 
 SIMPLIFY_COORD_LIMIT = 1 << 40   # S1: |snapped coordinate| <= 2^40 (utils.geometric.SNAP_LIMIT); the tolerance stays below it
@@ -873,21 +881,12 @@ def check_simplify_tables(ring_vertices, ring_offsets, tol_meters, fixed=None):
     """S1: the ring table, the fixed flags and the tolerance of `RingSimplifier.simplify` are in range -- ValueError naming
     gr_simplify_rings; -> (N, R, T)."""
     name = "gr_simplify_rings"
-    rv = np.asarray(ring_vertices)
-    if rv.ndim != 2 or rv.shape[1] != 2 or rv.dtype.kind not in "iu":
-        raise ValueError(f"{name}: ring vertices must be an (N, 2) integer array, got {rv.shape} {rv.dtype}")
-    N = int(rv.shape[0])
-    if N >= 2 ** 31 - 1:
-        raise ValueError(f"{name}: {N} ring vertices, not below 2^31 - 1")
-    if rv.size and (int(rv.max()) > SIMPLIFY_COORD_LIMIT or int(rv.min()) < -SIMPLIFY_COORD_LIMIT):
-        raise ValueError(f"{name}: a ring vertex lies more than 2^40 grid steps from the origin")
     off = np.asarray(ring_offsets)
     if off.ndim != 1 or off.shape[0] < 1 or off.dtype.kind not in "iu":
         raise ValueError(f"{name}: ring offsets must be an (R + 1,) integer array, got {off.shape} {off.dtype}")
-    off = off.astype(np.int64)
-    R = int(off.shape[0]) - 1
-    if off[0] != 0 or off[-1] != N or np.any(np.diff(off) < 0):
-        raise ValueError(f"{name}: ring offsets must rise from 0 to {N} (the number of ring vertices)")
+    N, R = _check_ring_table(name, ring_vertices, off, None, 0, inclusive=True)
+    if N >= 2 ** 31 - 1:
+        raise ValueError(f"{name}: {N} ring vertices, not below 2^31 - 1")
     if fixed is not None:
         fx = np.asarray(fixed)
         if fx.shape != (N,) or fx.dtype.kind not in "iub":
@@ -951,9 +950,8 @@ def check_nadir_tables(verts_q, z, faces):
 
 def check_nadir_window(col_off: int, row_off: int, width: int, height: int, small_cells: int = 0, item_rows: int = 0):
     """N7 / N8: the window is inside B1's bounds, small_cells and item_rows inside theirs -- ValueError naming gr_nadir_raster."""
-    name, lim = "gr_nadir_raster", BURN_WINDOW_LIMIT
-    if not (width >= 1 and height >= 1 and -lim < col_off < lim and -lim < row_off < lim and col_off + width <= lim and row_off + height <= lim):
-        raise ValueError(f"{name}: a window of {width} x {height} cells at ({col_off}, {row_off}) is empty or leaves (-2^23, 2^23]")
+    name = "gr_nadir_raster"
+    _check_window(name, col_off, row_off, width, height)
     if not 0 <= small_cells <= NADIR_SMALL_CELLS_MAX:
         raise ValueError(f"{name}: small_cells={small_cells} outside [0, {NADIR_SMALL_CELLS_MAX}]")
     if not 0 <= item_rows <= NADIR_ITEM_ROWS_MAX:
@@ -1336,17 +1334,17 @@ class HipRaster:
             return array.to(device=self.device, dtype=dtype).contiguous()
         return torch.as_tensor(np.ascontiguousarray(array)).to(device=self.device, dtype=dtype).contiguous()
 
-    def _ring_table(self, ring_vertices, ring_offsets, ring_polygon, polygon_boxes, ring_is_hole=None):
-        """The snapped ring table of `PlanarPolygons.snapped` on this device, checked: (ring vertices (N, 2) int64, offsets
-        (R + 1,) int64, polygons (R,) int32, boxes (P, 4) int64, hole flags (R,) int32 or None, N, R, P)."""
+    def _ring_table(self, ring_vertices, ring_offsets, ring_polygon, polygon_boxes=None, ring_is_hole=None, n_polygons: int = 0):
+        """A ring table on this device, its shapes checked: `RingTable` (ring vertices (N, 2) int64, offsets (R + 1,) int64, polygons
+        (R,) int32, boxes (P, 4) int64 or None, hole flags (R,) int32 or None, N, R, P); without boxes P is `n_polygons`."""
         torch = _torch()
         rv_t = self._shaped(ring_vertices, torch.int64, ("N", 2), "ring vertices")
-        rp_t = self._dev(ring_polygon, torch.int32)
+        rp_t = self._dev(ring_polygon, torch.int32).reshape(-1)
         R = int(rp_t.shape[0])
         off_t = self._shaped(ring_offsets, torch.int64, (R + 1,), "ring offsets (one more than ring polygons)")
         rh_t = None if ring_is_hole is None else self._shaped(ring_is_hole, torch.int32, (R,), "ring hole flags (one per ring polygon)")
-        box_t = self._shaped(polygon_boxes, torch.int64, ("P", 4), "polygon boxes")
-        return rv_t, off_t, rp_t, box_t, rh_t, int(rv_t.shape[0]), R, int(box_t.shape[0])
+        box_t = None if polygon_boxes is None else self._shaped(polygon_boxes, torch.int64, ("P", 4), "polygon boxes")
+        return RingTable(rv_t, off_t, rp_t, box_t, rh_t, int(rv_t.shape[0]), R, int(n_polygons if box_t is None else box_t.shape[0]))
 
     def _shaped(self, array, dtype, pattern: tuple, name: str):
         """numpy / tensor -> contiguous tensor of `dtype` on this device whose shape fits `pattern`: an int is the length an axis
@@ -2101,15 +2099,12 @@ class HipRaster:
         rv_h, off_h, rp_h, it_h = (_host_array(x) for x in (ring_vertices, ring_offsets, ring_polygon, items))
         P, C = int(n_polygons), int(num_classes)
         check_zonal_tables(H, W, nodata, rv_h, off_h, rp_h, P, it_h, C)
-        rv_t = self._shaped(ring_vertices, torch.int64, ("N", 2), "ring vertices")
-        rp_t = self._dev(ring_polygon, torch.int32).reshape(-1)
-        R = int(rp_t.shape[0])
-        off_t = self._shaped(ring_offsets, torch.int64, (R + 1,), "ring offsets (one more than ring polygons)")
+        t = self._ring_table(ring_vertices, ring_offsets, ring_polygon, n_polygons=P)
         it_t = self._shaped(items, torch.int32, ("n", GR_ZONAL_ITEM_INTS), "work items")
         counts = self._empty((P, C), torch.int64)
         stats = self._stats(GR_ZONAL_STAT_WORDS)
         self._call("gr_zonal_class_counts", r_t.data_ptr(), H, W, zonal_nodata(nodata),
-                   _ptr(rv_t if rv_t.numel() else None), int(rv_t.shape[0]), off_t.data_ptr(), _ptr(rp_t if R else None), R, P,
+                   _ptr(t.rv if t.N else None), t.N, t.off.data_ptr(), _ptr(t.rp if t.R else None), t.R, P,
                    _ptr(it_t if it_t.numel() else None), int(it_t.shape[0]), C, _ptr(counts if P else None), stats.data_ptr(),
                    self._stream())
         return counts, stats

@@ -1,7 +1,8 @@
 #pragma once
 // geograypher_amd/csrc/geom_dev.hpp -- device helpers shared by the polygon, terrain and selection kernels (gfx950, wave64):
-// the exact orientation sign, the walk of a ring table (ring_span, edge_crossing), the checked face load, and the integer wave
-// reductions behind every statistics word (stat_add, stat_add_u32, stat_max, stat_count).  HIP only; no floating point.
+// the exact orientation sign, the ring table and its walk (RingTable, ring_span, ring_of_slot, edge_crossing and rule Z3's
+// edge_crossing_strict), the checked face load, and the integer wave reductions behind every statistics word (stat_add,
+// stat_add_u32, stat_max, stat_count, ring_stats).  HIP only; no floating point.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -41,6 +42,45 @@ __device__ __forceinline__ bool edge_crossing(int64_t ax, int64_t ay, int64_t bx
     if (cross && (o > 0) == (by > ay)) parity ^= 1;
   }
   return on;
+}
+
+// Rule Z3: edge_crossing<false> with ONE difference.  That walk counts a point exactly ON an edge that runs
+// downwards (determinant 0 is "not strictly right") and not one on an edge that runs upwards, so a cell centre on a vertical
+// edge shared by two rows belongs to both of them or to neither.  Here a candidate counts only when the point is STRICTLY left
+// of the edge taken upwards, whichever way the ring runs: the ray along +x meets an edge through the point itself never, a
+// centre on a shared edge belongs to exactly one row, and rows that tile a region partition its cells.  Candidates are
+// half-open in y exactly as there; the determinant is formed for candidates only.  NARROW: the caller's differences are all
+// below 2^26, so the determinant fits int64; otherwise it is the 128-bit `orient`.  Both are exact.
+template <bool NARROW = false>
+__device__ __forceinline__ void edge_crossing_strict(int64_t ax, int64_t ay, int64_t bx, int64_t by, int64_t px, int64_t py, int &parity) {
+  if ((ay > py) != (by > py)) {
+    int s;
+    if (NARROW) {
+      const int64_t o = (bx - ax) * (py - ay) - (by - ay) * (px - ax);
+      s = o > 0 ? 1 : (o < 0 ? -1 : 0);
+    } else {
+      s = sgn(orient(ax, ay, bx, by, px, py));
+    }
+    if (by > ay ? s > 0 : s < 0) parity ^= 1;
+  }
+}
+
+// One ring table on the device (A1; Z1 and B1 without hole flags and boxes: both null there).
+struct RingTable {
+  const int64_t *rv, *roff, *pbox;
+  const int32_t *rpoly, *rhole;
+  int64_t n_rv, R, P;
+};
+
+// The ring that holds vertex slot i among the rings [r_lo, r_hi): the last ring whose first vertex is at or before i (rings of no
+// vertex in front of it are passed over); the caller checks that the slot lies inside the span it then reads.
+__device__ __forceinline__ int64_t ring_of_slot(const int64_t *__restrict__ roff, int64_t r_lo, int64_t r_hi, int64_t i) {
+  int64_t lo = r_lo, hi = r_hi;   // the answer is in [lo, hi); roff[lo] <= i is the caller's
+  while (hi - lo > 1) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (roff[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
 }
 
 // The three vertex indices of face f; false when one is outside [0, V): such a face is reported, never dereferenced.  V < 2^31
@@ -86,6 +126,17 @@ __device__ __forceinline__ void stat_max(unsigned long long *stats, int word, un
 __device__ __forceinline__ void stat_count(unsigned long long *stats, int word, bool one, int lane) {
   const unsigned long long m = __ballot(one);
   if (lane == 0 && m) atomicAdd(&stats[word], (unsigned long long)__popcll(m));
+}
+
+// The ring words of a ring table's statistics, one lane per ring r (lanes with r >= R report nothing): the largest ring and the
+// rings of fewer than 3 vertices, which take no part.  The two words are the caller's.  Called by all 64 lanes.
+template <int LARGEST_RING, int RINGS_IGNORED>
+__device__ __forceinline__ void ring_stats(const int64_t *__restrict__ roff, int64_t R, int64_t n_rv, int64_t r,
+                                           unsigned long long *stats, int lane) {
+  int64_t i0, n = 0;
+  if (r < R) n = ring_span(roff, (int)r, n_rv, i0);
+  stat_max(stats, LARGEST_RING, (unsigned long long)n, lane);
+  stat_count(stats, RINGS_IGNORED, r < R && n < 3, lane);
 }
 
 }  // namespace

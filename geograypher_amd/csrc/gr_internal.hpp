@@ -28,7 +28,7 @@
 //                    crs_constants.hpp, written by tools/make_crs_constants.py); no mesh needed
 //   ortho.hip        orthomosaic baseline: tile predictions assembled into a class raster (k_assemble_tiles), class counts of the raster cells
 //                    under polygon rows (k_zonal_class_counts, k_zonal_ring_stats), polygon rows burned into a label raster (k_burn_rows,
-//                    k_burn_values; one ring walk with the counts, zonal_parity_walk); no mesh needed
+//                    k_burn_values; one ring walk with the counts, zonal_parity_walk, and one item decode, load_cell_item); no mesh needed
 //   decimate.hip     mesh decimation by vertex clustering: cell keys and centre distances (k_decim_keys), cell heads (k_decim_heads),
 //                    representatives (k_decim_scatter_rep), remapped faces (k_decim_faces), first face per triple (k_decim_face_flags)
 //                    + radix sorts and scans; compacts with k_submesh_write; no mesh needed
@@ -54,7 +54,9 @@
 //   compact_dev.hpp  FlagScan, compact_begin, compact_write, k_submesh_write: the scans and the write kernel of polygons.hip's sub-mesh and of decimate.hip;
 //                    communities.hip ranks its surviving communities with FlagScan, simplify.hip compacts its kept ring vertices with it
 //   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip, crs.hip, ortho.hip, overlap.hip, simplify.hip and nadir.hip: orient, ring_span, edge_crossing (THE even-odd rule of
-//                    k_polygon_weights, k_face_polygon_index and k_points_in_region), load_face, stat_add / stat_add_u32 / stat_max / stat_count
+//                    k_polygon_weights, k_face_polygon_index and k_points_in_region), edge_crossing_strict (rule Z3: ortho.hip's ring walk, nadir.hip's faces),
+//                    RingTable (ortho.hip, overlap.hip), ring_of_slot (overlap.hip, simplify.hip), load_face, stat_add / stat_add_u32 / stat_max / stat_count / ring_stats
+//   (below)          the entry checks of the ring-table and grid-window calls: check_ring_table (ortho.hip, overlap.hip), check_window (ortho.hip, nadir.hip)
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -369,7 +371,28 @@ inline void release_spans(gr_ctx *c) {   // events back to the pool
     else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, SHMEM, STREAM, __VA_ARGS__);                                  \
   } while (0)
 
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+__host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }   // a >= 0, b > 0
+
+// The sizes and pointers of ONE ring table at an entry point (`side`: "a" or "b" where the call takes two, else null): every count
+// in [0, 2^31), no null array that a count says is read; hole flags and boxes are asked for with `with_holes_and_boxes` alone.
+inline int check_ring_table(gr_ctx *c, const char *name, const char *side, const int64_t *rv, int64_t n_rv, const int64_t *roff,
+                            const int32_t *rpoly, const int32_t *rhole, int64_t R, const int64_t *pbox, int64_t P, bool with_holes_and_boxes) {
+  const char *of_table = side ? " of table " : "", *in_table = side ? " in table " : "";
+  if (n_rv < 0 || R < 0 || P < 0 || n_rv > 0x7FFFFFFFll || R > 0x7FFFFFFFll || P > 0x7FFFFFFFll)
+    return fail(c, GR_EINVAL, "%s: a size%s%s is negative or not below 2^31", name, of_table, side ? side : "");
+  if (!roff || (n_rv > 0 && !rv) || (R > 0 && !rpoly) || (with_holes_and_boxes && ((R > 0 && !rhole) || (P > 0 && !pbox))))
+    return fail(c, GR_EINVAL, "%s: null arrays%s%s", name, in_table, side ? side : "");
+  return GR_OK;
+}
+
+// B1: a window of a cell grid -- not empty, its offsets inside (-2^23, 2^23), its far edges at or below 2^23.
+inline int check_window(gr_ctx *c, const char *name, int32_t col_off, int32_t row_off, int32_t width, int32_t height) {
+  const int32_t lim = 1 << 23;
+  if (width < 1 || height < 1 || col_off <= -lim || row_off <= -lim || col_off >= lim || row_off >= lim ||
+      (int64_t)col_off + width > lim || (int64_t)row_off + height > lim)
+    return fail(c, GR_EINVAL, "%s: window %d x %d at (%d, %d) is empty or leaves (-2^23, 2^23]", name, width, height, col_off, row_off);
+  return GR_OK;
+}
 
 // Before scratch is freed: wait for the work that can still use it -- the stream of the context's last call and its side
 // stream -- not for the whole device (other contexts, the caller's own streams keep running).

@@ -15,12 +15,10 @@
 // rows to a wave, one column per lane: item -> face by binary search in the scanned counts.  No lane loops over more than
 // max(small_cells, item_rows) cells.
 //
-// Membership (N4) is Z3 on the triangle as a ring of three vertices: the sign of an exact determinant, in int64 where the face
-// spans fewer than 2^26 units on both axes (every product below 2^52) and through the 128-bit orient otherwise; both are exact,
-// so the planes do not depend on small_cells, item_rows or the path.  The height (N5) is float64, every operation rounded on its
-// own (the library is built without contraction), the division correctly rounded.
-//
-// edge_crossing_strict is this unit's own copy of ortho.hip's (a test reads that unit's text for its one definition).
+// Membership (N4) is Z3 (edge_crossing_strict of geom_dev.hpp) on the triangle as a ring of three vertices: the sign of an exact
+// determinant, in int64 where the face spans fewer than 2^26 units on both axes (every product below 2^52) and through the
+// 128-bit orient otherwise; both are exact, so the planes do not depend on small_cells, item_rows or the path.  The height (N5)
+// is float64, every operation rounded on its own (the library is built without contraction), the division correctly rounded.
 #include "cub_steps.hpp"
 #include "geom_dev.hpp"
 #include "gr_internal.hpp"
@@ -61,8 +59,6 @@ struct Tri {
   bool narrow;
 };
 
-__device__ __forceinline__ int64_t dev_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }   // a >= 0, b > 0
-
 enum { NADIR_TAKES = 0, NADIR_BAD_INDEX, NADIR_NONFINITE, NADIR_ZERO_AREA, NADIR_EMPTY_BOX };
 
 // N3 and the clipped box of face f < F.  Only NADIR_TAKES fills the whole of `t`.
@@ -86,22 +82,7 @@ __device__ __forceinline__ int nadir_classify(const NadirArgs &a, int64_t f, Tri
   return NADIR_TAKES;
 }
 
-// Rule Z3 on one edge, as edge_crossing_strict of ortho.hip: a candidate is half-open in y and counts when the centre is STRICTLY
-// left of the edge taken upwards.  NARROW: every difference is below 2^26, the determinant fits int64.
-template <bool NARROW>
-__device__ __forceinline__ void edge_crossing_strict(int64_t ax, int64_t ay, int64_t bx, int64_t by, int64_t px, int64_t py, int &parity) {
-  if ((ay > py) != (by > py)) {
-    int s;
-    if (NARROW) {
-      const int64_t o = (bx - ax) * (py - ay) - (by - ay) * (px - ax);
-      s = o > 0 ? 1 : (o < 0 ? -1 : 0);
-    } else {
-      s = sgn(orient(ax, ay, bx, by, px, py));
-    }
-    if (by > ay ? s > 0 : s < 0) parity ^= 1;
-  }
-}
-
+// N4: Z3 over the face's three edges.  NARROW: every difference is below 2^26, the determinants fit int64.
 template <bool NARROW> __device__ __forceinline__ bool nadir_inside(const Tri &t, int64_t px, int64_t py) {
   int parity = 0;
   edge_crossing_strict<NARROW>(t.ax, t.ay, t.bx, t.by, px, py, parity);
@@ -146,7 +127,7 @@ template <int WALK> __global__ __launch_bounds__(256) void k_nadir_faces(NadirAr
   if (what == NADIR_TAKES) {
     const int64_t w = (int64_t)t.c1 - t.c0 + 1, h = (int64_t)t.r1 - t.r0 + 1;
     cells = w * h;
-    if (cells > a.small_cells) items = dev_ceil_div(w, NADIR_ITEM_COLS) * dev_ceil_div(h, a.item_rows);
+    if (cells > a.small_cells) items = ceil_div(w, NADIR_ITEM_COLS) * ceil_div(h, a.item_rows);
   }
   u64 n_in = 0, n_skip = 0;
   if (what == NADIR_TAKES && items == 0) {   // at most small_cells cells
@@ -196,7 +177,7 @@ template <int WALK> __global__ __launch_bounds__(256) void k_nadir_items(NadirAr
     const int64_t f = a.big_face[lo];
     Tri t;
     if (f < 0 || f >= a.F || nadir_classify(a, f, t) != NADIR_TAKES) continue;   // (never: the list holds faces that take part)
-    const int64_t items_x = dev_ceil_div((int64_t)t.c1 - t.c0 + 1, NADIR_ITEM_COLS), local = item - a.big_off[lo];
+    const int64_t items_x = ceil_div((int64_t)t.c1 - t.c0 + 1, NADIR_ITEM_COLS), local = item - a.big_off[lo];
     const int64_t col = (int64_t)t.c0 + (local % items_x) * NADIR_ITEM_COLS + lane;
     const int64_t row0 = (int64_t)t.r0 + (local / items_x) * a.item_rows;
     if (col > t.c1) continue;
@@ -238,10 +219,7 @@ int gr_nadir_raster(gr_ctx *c, const int64_t *verts_q, const double *z, int64_t 
                     int32_t row_off, int32_t width, int32_t height, int32_t small_cells, int32_t item_rows, int32_t *face_out,
                     double *z_out, uint64_t *stats, void *stream) {
   if (!c) return GR_EINVAL;
-  const int32_t lim = 1 << 23;
-  if (width < 1 || height < 1 || col_off <= -lim || row_off <= -lim || col_off >= lim || row_off >= lim ||
-      (int64_t)col_off + width > lim || (int64_t)row_off + height > lim)
-    return fail(c, GR_EINVAL, "gr_nadir_raster: window %d x %d at (%d, %d) is empty or leaves (-2^23, 2^23]", width, height, col_off, row_off);
+  GR_TRY(check_window(c, "gr_nadir_raster", col_off, row_off, width, height));
   if (V < 0 || F < 0 || V > 0x7FFFFFFFll - 1 || F > 0x7FFFFFFFll - 1)
     return fail(c, GR_EINVAL, "gr_nadir_raster: bad shape V=%lld F=%lld (both below 2^31 - 1)", (long long)V, (long long)F);
   if (small_cells < 0 || small_cells > NADIR_SMALL_MAX || item_rows < 0 || item_rows > NADIR_ITEM_ROWS_MAX)

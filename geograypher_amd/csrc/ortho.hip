@@ -14,9 +14,9 @@
 //
 // Zonal counts.  A workgroup takes one work item: a polygon row and a block of at most 64 x 128 cells of its box.  Wave w owns
 // the block's rows w, w + 4, ...: a row segment is one cell per lane, so every lane of a wave has the same py, the candidate test
-// of the ring walk is wave-uniform and the 128-bit determinant is formed for candidate edges only (edge_crossing_strict below).
-// The row's ring vertices are staged in LDS, ZONAL_CHUNK at a time (a ring of any length works); the parity of up to 32 rows
-// per lane is kept in one word.
+// of the ring walk is wave-uniform and the 128-bit determinant is formed for candidate edges only (edge_crossing_strict of
+// geom_dev.hpp).  The row's ring vertices are staged in LDS, ZONAL_CHUNK at a time (a ring of any length works); the parity of
+// up to 32 rows per lane is kept in one word.
 // Inside cells go into an LDS histogram of C words, then one 64-bit atomicAdd per class with a non-zero count: integers, so the
 // order does not matter.  All integer; no floating point in that kernel.
 //
@@ -153,45 +153,45 @@ __global__ __launch_bounds__(256) void k_assemble_tiles(const uint8_t *__restric
   stat_add(stats, GR_ORTHO_STAT_PAIRS, covering, lane);
 }
 
-// The ring statistics of a ring table: one lane per ring.  The two words are the caller's (GR_ZONAL_STAT_* or GR_BURN_STAT_*).
+// The ring statistics of a ring table: one lane per ring (ring_stats of geom_dev.hpp); the words are GR_ZONAL_STAT_* or GR_BURN_STAT_*.
 template <int LARGEST_RING, int RINGS_IGNORED>
 __global__ __launch_bounds__(256) void k_zonal_ring_stats(const int64_t *__restrict__ roff, int64_t R, int64_t n_rv,
                                                           unsigned long long *__restrict__ stats) {
-  const int lane = (int)(threadIdx.x & 63);
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  int64_t i0, n = 0;
-  if (r < R) n = ring_span(roff, (int)r, n_rv, i0);
-  stat_max(stats, LARGEST_RING, (unsigned long long)n, lane);
-  stat_count(stats, RINGS_IGNORED, r < R && n < 3, lane);
+  ring_stats<LARGEST_RING, RINGS_IGNORED>(roff, R, n_rv, (int64_t)blockIdx.x * 256 + threadIdx.x, stats, (int)(threadIdx.x & 63));
 }
 
-// Rule Z3: edge_crossing<false> of geom_dev.hpp with ONE difference.  That walk counts a point exactly ON an edge that runs
-// downwards (determinant 0 is "not strictly right") and not one on an edge that runs upwards, so a cell centre on a vertical
-// edge shared by two rows belongs to both of them or to neither.  Here a candidate counts only when the point is STRICTLY left
-// of the edge taken upwards, whichever way the ring runs: the ray along +x meets an edge through the point itself never, a
-// centre on a shared edge belongs to exactly one row, and rows that tile a region partition its cells.  Candidates are
-// half-open in y exactly as there; the 128-bit determinant is formed for candidates only.
-__device__ __forceinline__ void edge_crossing_strict(int64_t ax, int64_t ay, int64_t bx, int64_t by, int64_t px, int64_t py, int &parity) {
-  if ((ay > py) != (by > py)) {
-    const i128 o = orient(ax, ay, bx, by, px, py);
-    if (by > ay ? o > 0 : o < 0) parity ^= 1;
-  }
+// One work item of the zonal counts and of the burn, decoded: row p, the block of bw x bh cells from (col0, row0) in the
+// coordinates of the parent grid, the rings [r_lo, r_hi) clamped to the rings there are.
+struct CellItem { int64_t p; int col0, row0, bw, bh; int64_t r_lo, r_hi; };
+
+// Item `index` of items [n][GR_ZONAL_ITEM_INTS]: polygon, col0, row0, width, height, first ring, one past the last ring.  False
+// for an item that is malformed or leaves the window [col_off, col_off + width) x [row_off, row_off + height) (B7; the zonal
+// counts' window is the raster, (0, 0, W, H)): the caller skips it whole, workgroup-uniform -- the host validates, the kernel
+// reads nothing out of bounds (O8's rule).  The sums are taken in 64 bits.
+__device__ __forceinline__ bool load_cell_item(const int32_t *__restrict__ items, int64_t index, int64_t P, int64_t R, int col_off,
+                                               int row_off, int width, int height, CellItem &it) {
+  const int32_t *w = items + index * GR_ZONAL_ITEM_INTS;
+  it.p = w[0]; it.col0 = w[1]; it.row0 = w[2]; it.bw = w[3]; it.bh = w[4];
+  it.r_lo = min(max((int64_t)w[5], (int64_t)0), R);
+  it.r_hi = min(max((int64_t)w[6], it.r_lo), R);
+  return it.p >= 0 && it.p < P && it.bw >= 1 && it.bh >= 1 && it.bw <= GR_ZONAL_BLOCK_W && it.bh <= GR_ZONAL_BLOCK_H &&
+         it.col0 >= col_off && it.row0 >= row_off && (int64_t)it.col0 + it.bw <= (int64_t)col_off + width &&
+         (int64_t)it.row0 + it.bh <= (int64_t)row_off + height;
 }
 
-// THE ring walk of the zonal counts and of the polygon burn (Z2, Z3 = B2): the parity word of this lane's cells of a block of
-// `bh` <= 128 rows from (col0, row0) -- bit k: the centre of cell (row0 + wave + 4 k, col0 + lane) lies in row p under the even-odd
-// rule over the rings [r_lo, r_hi) that belong to p.  Called by the whole workgroup of 256 (it holds barriers); the ring vertices
-// are staged in vx, vy (ZONAL_CHUNK + 1 words each), a chunk at a time.  The caller waits at a barrier before it reuses the LDS.
-__device__ __forceinline__ uint32_t zonal_parity_walk(const int64_t *__restrict__ rv, const int64_t *__restrict__ roff,
-                                                      const int32_t *__restrict__ rpoly, int64_t p, int64_t r_lo, int64_t r_hi,
-                                                      int64_t n_rv, int col0, int row0, int bh, int64_t *vx, int64_t *vy) {
+// THE ring walk of the zonal counts and of the polygon burn (Z2, Z3 = B2): the parity word of this lane's cells of the item's
+// block of bh <= 128 rows -- bit k: the centre of cell (row0 + wave + 4 k, col0 + lane) lies in row p under the even-odd rule
+// (edge_crossing_strict of geom_dev.hpp, the 128-bit one) over the rings [r_lo, r_hi) that belong to p.  Called by the whole
+// workgroup of 256 (it holds barriers); the ring vertices are staged in vx, vy (ZONAL_CHUNK + 1 words each), a chunk at a time.
+// The caller waits at a barrier before it reuses the LDS.
+__device__ __forceinline__ uint32_t zonal_parity_walk(const RingTable &t, const CellItem &it, int64_t *vx, int64_t *vy) {
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t px = 65536ll * (col0 + lane) + 32768;   // Z2
+  const int64_t px = 65536ll * (it.col0 + lane) + 32768;   // Z2
   uint32_t parity = 0;
-  for (int64_t r = r_lo; r < r_hi; ++r) {
-    if ((int64_t)rpoly[r] != p) continue;
+  for (int64_t r = it.r_lo; r < it.r_hi; ++r) {
+    if ((int64_t)t.rpoly[r] != it.p) continue;
     int64_t i0;
-    const int64_t n = ring_span(roff, (int)r, n_rv, i0);
+    const int64_t n = ring_span(t.roff, (int)r, t.n_rv, i0);
     if (n < 3) continue;
     for (int64_t k0 = 0; k0 < n; k0 += ZONAL_CHUNK) {
       const int n_chunk = (int)min((int64_t)ZONAL_CHUNK, n - k0);   // edges k0 + j -> k0 + j + 1 (the last one closes the ring)
@@ -199,18 +199,18 @@ __device__ __forceinline__ uint32_t zonal_parity_walk(const int64_t *__restrict_
       if (tid <= n_chunk) {
         int64_t at = k0 + tid;
         if (at >= n) at -= n;   // only k0 + n_chunk == n wraps, to vertex 0
-        vx[tid] = rv[(i0 + at) * 2];
-        vy[tid] = rv[(i0 + at) * 2 + 1];
+        vx[tid] = t.rv[(i0 + at) * 2];
+        vy[tid] = t.rv[(i0 + at) * 2 + 1];
       }
       if (tid == 0 && n_chunk == ZONAL_CHUNK) {
         int64_t at = k0 + ZONAL_CHUNK;
         if (at >= n) at -= n;
-        vx[ZONAL_CHUNK] = rv[(i0 + at) * 2];
-        vy[ZONAL_CHUNK] = rv[(i0 + at) * 2 + 1];
+        vx[ZONAL_CHUNK] = t.rv[(i0 + at) * 2];
+        vy[ZONAL_CHUNK] = t.rv[(i0 + at) * 2 + 1];
       }
       __syncthreads();
-      for (int k = 0; wave + 4 * k < bh; ++k) {
-        const int64_t py = 65536ll * (row0 + wave + 4 * k) + 32768;
+      for (int k = 0; wave + 4 * k < it.bh; ++k) {
+        const int64_t py = 65536ll * (it.row0 + wave + 4 * k) + 32768;
         int flips = 0;
         for (int j = 0; j < n_chunk; ++j) edge_crossing_strict(vx[j], vy[j], vx[j + 1], vy[j + 1], px, py, flips);
         parity ^= (uint32_t)(flips & 1) << k;
@@ -221,31 +221,25 @@ __device__ __forceinline__ uint32_t zonal_parity_walk(const int64_t *__restrict_
 }
 
 struct ZonalArgs {
-  int64_t n_rv, R, P;
   int32_t H, W, nodata, C;
 };
 
-// raster [H][W]; rv [n_rv][2] in 1/65536 of a cell (Z1); roff [R + 1]; rpoly [R] non-decreasing; items [n][GR_ZONAL_ITEM_INTS]:
-// polygon, col0, row0, width, height, first ring, one past the last ring; counts [P][C]; stats [GR_ZONAL_STAT_WORDS].
-__global__ __launch_bounds__(256) void k_zonal_class_counts(const uint8_t *__restrict__ raster, const int64_t *__restrict__ rv,
-                                                            const int64_t *__restrict__ roff, const int32_t *__restrict__ rpoly,
+// raster [H][W]; t: the ring table, rv [n_rv][2] in 1/65536 of a cell (Z1), roff [R + 1], rpoly [R] non-decreasing, no hole flags
+// and no boxes; items [n][GR_ZONAL_ITEM_INTS] (load_cell_item); counts [P][C]; stats [GR_ZONAL_STAT_WORDS].
+__global__ __launch_bounds__(256) void k_zonal_class_counts(const uint8_t *__restrict__ raster, RingTable t,
                                                             const int32_t *__restrict__ items,
                                                             unsigned long long *__restrict__ counts,
                                                             unsigned long long *__restrict__ stats, ZonalArgs a) {
   __shared__ int64_t vx[ZONAL_CHUNK + 1], vy[ZONAL_CHUNK + 1];
   __shared__ uint32_t hist[GR_ZONAL_MAX_CLASSES];
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int32_t *it = items + (int64_t)blockIdx.x * GR_ZONAL_ITEM_INTS;
-  const int64_t p = it[0];
-  const int col0 = it[1], row0 = it[2], bw = it[3], bh = it[4];
-  // a malformed item is skipped whole (workgroup-uniform): the host validates, the kernel reads nothing out of bounds (O8's rule)
-  if (p < 0 || p >= a.P || col0 < 0 || row0 < 0 || bw < 1 || bh < 1 || bw > GR_ZONAL_BLOCK_W || bh > GR_ZONAL_BLOCK_H ||
-      col0 > a.W - bw || row0 > a.H - bh)
-    return;
-  const int64_t r_lo = min(max((int64_t)it[5], (int64_t)0), a.R), r_hi = min(max((int64_t)it[6], r_lo), a.R);
+  CellItem it;
+  if (!load_cell_item(items, blockIdx.x, t.P, t.R, 0, 0, a.W, a.H, it)) return;
+  const int64_t p = it.p;
+  const int col0 = it.col0, row0 = it.row0, bw = it.bw, bh = it.bh;
   if (tid < a.C) hist[tid] = 0;   // C <= 256 = the workgroup
   // bit k: the row row0 + wave + 4 k
-  const uint32_t parity = zonal_parity_walk(rv, roff, rpoly, p, r_lo, r_hi, a.n_rv, col0, row0, bh, vx, vy);
+  const uint32_t parity = zonal_parity_walk(t, it, vx, vy);
   __syncthreads();   // the histogram is zeroed; the last chunk is read
   unsigned int n_in = 0, n_nodata = 0, n_over = 0, largest = 0;
   if (lane < bw) {
@@ -269,27 +263,22 @@ __global__ __launch_bounds__(256) void k_zonal_class_counts(const uint8_t *__res
 }
 
 struct BurnArgs {
-  int64_t n_rv, R, P, n_cells;
+  int64_t P, n_cells;
   int32_t col_off, row_off, width, height, fill;
 };
 
 // The ring table as k_zonal_class_counts takes it; items in the coordinates of the PARENT grid (col0, row0 may be negative), each
 // inside the window [col_off, col_off + width) x [row_off, row_off + height) (B1, B5); rows [height][width], -1 on entry;
 // stats [GR_BURN_STAT_WORDS].
-__global__ __launch_bounds__(256) void k_burn_rows(const int64_t *__restrict__ rv, const int64_t *__restrict__ roff,
-                                                   const int32_t *__restrict__ rpoly, const int32_t *__restrict__ items,
-                                                   int32_t *__restrict__ rows, unsigned long long *__restrict__ stats, BurnArgs a) {
+__global__ __launch_bounds__(256) void k_burn_rows(RingTable t, const int32_t *__restrict__ items, int32_t *__restrict__ rows,
+                                                   unsigned long long *__restrict__ stats, BurnArgs a) {
   __shared__ int64_t vx[ZONAL_CHUNK + 1], vy[ZONAL_CHUNK + 1];
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int32_t *it = items + (int64_t)blockIdx.x * GR_ZONAL_ITEM_INTS;
-  const int64_t p = it[0];
-  const int col0 = it[1], row0 = it[2], bw = it[3], bh = it[4];
-  // B7: an item that is malformed or leaves the window is skipped whole (workgroup-uniform); the sums are taken in 64 bits
-  if (p < 0 || p >= a.P || bw < 1 || bh < 1 || bw > GR_ZONAL_BLOCK_W || bh > GR_ZONAL_BLOCK_H || col0 < a.col_off || row0 < a.row_off ||
-      (int64_t)col0 + bw > (int64_t)a.col_off + a.width || (int64_t)row0 + bh > (int64_t)a.row_off + a.height)
-    return;
-  const int64_t r_lo = min(max((int64_t)it[5], (int64_t)0), a.R), r_hi = min(max((int64_t)it[6], r_lo), a.R);
-  const uint32_t parity = zonal_parity_walk(rv, roff, rpoly, p, r_lo, r_hi, a.n_rv, col0, row0, bh, vx, vy);
+  CellItem it;
+  if (!load_cell_item(items, blockIdx.x, t.P, t.R, a.col_off, a.row_off, a.width, a.height, it)) return;   // B7
+  const int64_t p = it.p;
+  const int col0 = it.col0, row0 = it.row0, bw = it.bw, bh = it.bh;
+  const uint32_t parity = zonal_parity_walk(t, it, vx, vy);
   unsigned int n_in = 0;
   if (lane < bw) {
     const int64_t x = (int64_t)col0 + lane - a.col_off;   // in [0, width)
@@ -382,12 +371,11 @@ int gr_zonal_class_counts(gr_ctx *c, const uint8_t *raster, int32_t H, int32_t W
   if (!c) return GR_EINVAL;
   if (H < 1 || W < 1 || H >= (1 << 23) || W >= (1 << 23))
     return fail(c, GR_EINVAL, "gr_zonal_class_counts: raster %d x %d outside [1, 2^23)", H, W);
-  if (n_ring_vertices < 0 || R < 0 || P < 0 || n_items < 0 || R > 0x7FFFFFFFll || P > 0x7FFFFFFFll || n_items > 0x7FFFFFFFll)
-    return fail(c, GR_EINVAL, "gr_zonal_class_counts: a size is negative or not below 2^31");
+  GR_TRY(check_ring_table(c, "gr_zonal_class_counts", nullptr, ring_vertices, n_ring_vertices, ring_offsets, ring_polygon, nullptr, R,
+                          nullptr, P, false));
+  if (n_items < 0 || n_items > 0x7FFFFFFFll) return fail(c, GR_EINVAL, "gr_zonal_class_counts: a size is negative or not below 2^31");
   if (C < 1 || C > GR_ZONAL_MAX_CLASSES) return fail(c, GR_EINVAL, "gr_zonal_class_counts: C=%d outside [1, %d]", C, GR_ZONAL_MAX_CLASSES);
-  if (!raster || !stats || !ring_offsets || (P > 0 && !counts) || (R > 0 && !ring_polygon) || (n_ring_vertices > 0 && !ring_vertices) ||
-      (n_items > 0 && !items))
-    return fail(c, GR_EINVAL, "gr_zonal_class_counts: null arrays");
+  if (!raster || !stats || (P > 0 && !counts) || (n_items > 0 && !items)) return fail(c, GR_EINVAL, "gr_zonal_class_counts: null arrays");
   hipStream_t s = (hipStream_t)stream;
   GR_HIP(c, hipSetDevice(c->device));
   GR_HIP(c, hipMemsetAsync(stats, 0, sizeof(uint64_t) * GR_ZONAL_STAT_WORDS, s));
@@ -400,9 +388,9 @@ int gr_zonal_class_counts(gr_ctx *c, const uint8_t *raster, int32_t H, int32_t W
   }
   if (n_items == 0 || R == 0) return GR_OK;
   ZonalArgs a;
-  a.n_rv = n_ring_vertices; a.R = R; a.P = P; a.H = H; a.W = W; a.nodata = nodata; a.C = C;
-  hipLaunchKernelGGL(k_zonal_class_counts, dim3((unsigned)n_items), dim3(256), 0, s, raster, ring_vertices, ring_offsets, ring_polygon,
-                     items, (unsigned long long *)counts, st, a);
+  a.H = H; a.W = W; a.nodata = nodata; a.C = C;
+  const RingTable t{ring_vertices, ring_offsets, nullptr, ring_polygon, nullptr, n_ring_vertices, R, P};
+  hipLaunchKernelGGL(k_zonal_class_counts, dim3((unsigned)n_items), dim3(256), 0, s, raster, t, items, (unsigned long long *)counts, st, a);
   GR_HIP(c, hipGetLastError());
   return GR_OK;
 }
@@ -412,19 +400,17 @@ int gr_burn_polygons(gr_ctx *c, const int64_t *ring_vertices, int64_t n_ring_ver
                      int32_t col_off, int32_t row_off, int32_t width, int32_t height, int32_t fill, int32_t *rows, uint8_t *out,
                      uint64_t *stats, void *stream) {
   if (!c) return GR_EINVAL;
-  const int32_t lim = 1 << 23;
-  if (width < 1 || height < 1 || col_off <= -lim || row_off <= -lim || col_off >= lim || row_off >= lim ||
-      (int64_t)col_off + width > lim || (int64_t)row_off + height > lim)
-    return fail(c, GR_EINVAL, "gr_burn_polygons: window %d x %d at (%d, %d) is empty or leaves (-2^23, 2^23]", width, height, col_off, row_off);
-  if (n_ring_vertices < 0 || R < 0 || P < 0 || n_items < 0 || R > 0x7FFFFFFFll || P > 0x7FFFFFFFll || n_items > 0x7FFFFFFFll)
-    return fail(c, GR_EINVAL, "gr_burn_polygons: a size is negative or not below 2^31");
+  GR_TRY(check_window(c, "gr_burn_polygons", col_off, row_off, width, height));
+  GR_TRY(check_ring_table(c, "gr_burn_polygons", nullptr, ring_vertices, n_ring_vertices, ring_offsets, ring_polygon, nullptr, R, nullptr,
+                          P, false));
+  if (n_items < 0 || n_items > 0x7FFFFFFFll) return fail(c, GR_EINVAL, "gr_burn_polygons: a size is negative or not below 2^31");
   if (fill < 0 || fill > 255) return fail(c, GR_EINVAL, "gr_burn_polygons: fill=%d outside [0, 255]", fill);
-  if (!rows || !stats || !ring_offsets || (R > 0 && !ring_polygon) || (n_ring_vertices > 0 && !ring_vertices) || (n_items > 0 && !items))
-    return fail(c, GR_EINVAL, "gr_burn_polygons: null arrays");
+  if (!rows || !stats || (n_items > 0 && !items)) return fail(c, GR_EINVAL, "gr_burn_polygons: null arrays");
   if (out && P > 0 && !values) return fail(c, GR_EINVAL, "gr_burn_polygons: null values with an output plane");
   hipStream_t s = (hipStream_t)stream;
+  const RingTable t{ring_vertices, ring_offsets, nullptr, ring_polygon, nullptr, n_ring_vertices, R, P};
   BurnArgs a;
-  a.n_rv = n_ring_vertices; a.R = R; a.P = P; a.n_cells = (int64_t)width * height;
+  a.P = P; a.n_cells = (int64_t)width * height;
   a.col_off = col_off; a.row_off = row_off; a.width = width; a.height = height; a.fill = fill;
   GR_HIP(c, hipSetDevice(c->device));
   GR_HIP(c, hipMemsetAsync(stats, 0, sizeof(uint64_t) * GR_BURN_STAT_WORDS, s));
@@ -436,7 +422,7 @@ int gr_burn_polygons(gr_ctx *c, const int64_t *ring_vertices, int64_t n_ring_ver
     GR_HIP(c, hipGetLastError());
   }
   if (n_items > 0 && R > 0) {
-    hipLaunchKernelGGL(k_burn_rows, dim3((unsigned)n_items), dim3(256), 0, s, ring_vertices, ring_offsets, ring_polygon, items, rows, st, a);
+    hipLaunchKernelGGL(k_burn_rows, dim3((unsigned)n_items), dim3(256), 0, s, t, items, rows, st, a);
     GR_HIP(c, hipGetLastError());
   }
   if (out) {

@@ -65,35 +65,15 @@ __global__ __launch_bounds__(256) void k_overlap_pairs_fill(const int64_t *__res
   }
 }
 
-// One ring table (A1) on the device.
-struct RingTable {
-  const int64_t *rv, *roff, *pbox;
-  const int32_t *rpoly, *rhole;
-  int64_t n_rv, R, P;
-};
-
-// The ring that holds vertex slot i among the rings [r_lo, r_hi): the last ring whose first vertex is at or before i (rings of no
-// vertex in front of it are passed over); the caller checks that the slot lies inside the span it then reads.
-__device__ __forceinline__ int64_t ring_of_slot(const int64_t *__restrict__ roff, int64_t r_lo, int64_t r_hi, int64_t i) {
-  int64_t lo = r_lo, hi = r_hi;   // the answer is in [lo, hi); roff[lo] <= i is the caller's
-  while (hi - lo > 1) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    if (roff[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// The statistics of a ring table: one lane per ring (the largest ring, rings ignored) and per vertex slot (vertical edges of the
-// rings that take part).
+// The statistics of a ring table (RingTable, ring_of_slot: geom_dev.hpp): one lane per ring (ring_stats: the largest ring, rings
+// ignored) and per vertex slot (vertical edges of the rings that take part).
 __global__ __launch_bounds__(256) void k_overlap_table_stats(RingTable t, u64 *__restrict__ stats) {
   const int lane = (int)(threadIdx.x & 63);
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  int64_t i0, n = 0;
-  if (i < t.R) n = ring_span(t.roff, (int)i, t.n_rv, i0);
-  stat_max(stats, GR_OVERLAP_STAT_LARGEST_RING, (u64)n, lane);
-  stat_count(stats, GR_OVERLAP_STAT_RINGS_IGNORED, i < t.R && n < 3, lane);
+  ring_stats<GR_OVERLAP_STAT_LARGEST_RING, GR_OVERLAP_STAT_RINGS_IGNORED>(t.roff, t.R, t.n_rv, i, stats, lane);
   bool vertical = false;
   if (i < t.n_rv && t.R > 0) {
+    int64_t i0;
     const int64_t r = ring_of_slot(t.roff, 0, t.R, i);
     const int64_t m = ring_span(t.roff, (int)r, t.n_rv, i0);
     if (m >= 3 && i >= i0 && i < i0 + m) {
@@ -280,15 +260,6 @@ int check_boxes(gr_ctx *c, const char *name, const int64_t *boxes_a, int64_t Pa,
   return GR_OK;
 }
 
-int check_table(gr_ctx *c, const char *side, const int64_t *rv, int64_t n_rv, const int64_t *roff, const int32_t *rpoly, const int32_t *rhole,
-                int64_t R, const int64_t *pbox, int64_t P) {
-  if (n_rv < 0 || R < 0 || P < 0 || n_rv > 0x7FFFFFFFll || R > 0x7FFFFFFFll || P > 0x7FFFFFFFll)
-    return fail(c, GR_EINVAL, "gr_polygon_overlap_areas: a size of table %s is negative or not below 2^31", side);
-  if (!roff || (n_rv > 0 && !rv) || (R > 0 && (!rpoly || !rhole)) || (P > 0 && !pbox))
-    return fail(c, GR_EINVAL, "gr_polygon_overlap_areas: null arrays in table %s", side);
-  return GR_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -336,10 +307,10 @@ int gr_polygon_overlap_areas(gr_ctx *c, const int64_t *ring_vertices_a, int64_t 
                              int64_t P_b, const int32_t *pairs, int64_t n_pairs, const int32_t *items, int64_t n_items, double *area,
                              double *area_abs, uint64_t *stats, void *stream) {
   if (!c) return GR_EINVAL;
-  int rc = check_table(c, "a", ring_vertices_a, n_ring_vertices_a, ring_offsets_a, ring_polygon_a, ring_is_hole_a, R_a, polygon_boxes_a, P_a);
-  if (rc != GR_OK) return rc;
-  rc = check_table(c, "b", ring_vertices_b, n_ring_vertices_b, ring_offsets_b, ring_polygon_b, ring_is_hole_b, R_b, polygon_boxes_b, P_b);
-  if (rc != GR_OK) return rc;
+  GR_TRY(check_ring_table(c, "gr_polygon_overlap_areas", "a", ring_vertices_a, n_ring_vertices_a, ring_offsets_a, ring_polygon_a, ring_is_hole_a,
+                          R_a, polygon_boxes_a, P_a, true));
+  GR_TRY(check_ring_table(c, "gr_polygon_overlap_areas", "b", ring_vertices_b, n_ring_vertices_b, ring_offsets_b, ring_polygon_b, ring_is_hole_b,
+                          R_b, polygon_boxes_b, P_b, true));
   if (n_pairs < 0 || n_items < 0 || n_pairs > 0x7FFFFFFFll || n_items > 0x7FFFFFFFll)
     return fail(c, GR_EINVAL, "gr_polygon_overlap_areas: n_pairs=%lld or n_items=%lld is negative or not below 2^31", (long long)n_pairs,
                 (long long)n_items);
@@ -369,8 +340,7 @@ int gr_polygon_overlap_areas(gr_ctx *c, const int64_t *ring_vertices_a, int64_t 
   const auto key = p.array<int32_t>(n_items), runmax = p.array<int32_t>(n_items);
   const auto partial = p.array<double>(2 * n_items);
   const InclusiveMax<int32_t> scan(c, p, n_items);
-  rc = stage_acquire(c, c->stage, p.finish(), s, "polygon-overlap");
-  if (rc != GR_OK) return rc;
+  GR_TRY(stage_acquire(c, c->stage, p.finish(), s, "polygon-overlap"));
   p.base = c->stage.ptr;
   const dim3 per_item((unsigned)ceil_div(n_items, 256));
   hipLaunchKernelGGL(k_overlap_item_keys, per_item, dim3(256), 0, s, items, n_items, n_pairs, key());

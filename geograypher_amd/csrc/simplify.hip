@@ -110,11 +110,7 @@ __global__ __launch_bounds__(256) void k_simp_rings(const int64_t *__restrict__ 
   bool fix = false;
   u64 ka = 0;
   if (i < N) {
-    int lo = 0, hi = R;   // the last ring whose offset is <= i
-    while (hi - lo > 1) {
-      const int mid = lo + (hi - lo) / 2;
-      if (roff[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int lo = (int)ring_of_slot(roff, 0, R, i);   // the last ring whose offset is <= i
     int64_t s, e;
     if (simp_ring(roff, lo, N, s, e) && i >= s && i < e) r = lo;
     ring[i] = r;

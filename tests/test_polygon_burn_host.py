@@ -153,6 +153,88 @@ def test_malformed_tables_are_refused():
     assert burn_values([0, 255.0, np.int64(7)], 3).tolist() == [0, 255, 7]
 
 
+# -- one ring-table check, one cell-item check behind the four table checks ------------------------------------------------------------
+LIMIT = 1 << 40
+RING_TABLE = dict(rv=np.array(q(square(1, 1, 8, 8)) + q(square(2, 2, 3, 3)), dtype=np.int64), off=np.array([0, 4, 8]), rp=np.array([0, 1]), P=2)
+WIDE_BOXES = np.array([[-LIMIT, -LIMIT, LIMIT, LIMIT]] * 2, dtype=np.int64)      # they hold every vertex a table may have
+
+
+def at(value):
+    rv = RING_TABLE["rv"].copy()
+    rv[5, 1] = value
+    return rv
+
+
+RING_TABLE_CHECKS = {
+    "gr_zonal_class_counts": lambda rv, off, rp, P: _hip.check_zonal_tables(9, 9, None, rv, off, rp, P, np.zeros((0, 7), dtype=np.int32), 3),
+    "gr_burn_polygons": lambda rv, off, rp, P: _hip.check_burn_tables(rv, off, rp, P),
+    "gr_polygon_overlap_areas": lambda rv, off, rp, P: _hip.check_overlap_tables((rv, off, rp, np.zeros(len(rp), dtype=np.int32), WIDE_BOXES[:P]),
+                                                                                   (RING_TABLE["rv"], RING_TABLE["off"], RING_TABLE["rp"],
+                                                                                    np.zeros(2, dtype=np.int32), WIDE_BOXES)),
+    "gr_simplify_rings": lambda rv, off, rp, P: _hip.check_simplify_tables(rv, off, 0.5),
+}
+# (what is wrong, the change, refused by the checks that take no ring_polygon too, accepted by those whose limit is inclusive)
+BAD_RING_TABLES = [
+    ("offsets do not start at 0", dict(off=np.array([1, 4, 8])), True, False),
+    ("offsets fall", dict(off=np.array([0, 9, 8])), True, False),
+    ("offsets do not end at N", dict(off=np.array([0, 4, 7])), True, False),
+    ("ring_polygon falls", dict(rp=np.array([1, 0])), False, False),
+    ("ring_polygon names row P", dict(rp=np.array([0, 2])), False, False),
+    ("ring_polygon names row -1", dict(rp=np.array([-1, 0])), False, False),
+    ("vertices are flat", dict(rv=RING_TABLE["rv"].reshape(-1)), True, False),
+    ("vertices are (N, 3)", dict(rv=np.zeros((8, 3), dtype=np.int64)), True, False),
+    ("vertices are floats", dict(rv=RING_TABLE["rv"].astype(np.float64)), True, False),
+    ("a coordinate at the limit", dict(rv=at(LIMIT)), True, True),
+    ("a coordinate at minus the limit", dict(rv=at(-LIMIT)), True, True),
+    ("a coordinate past the limit", dict(rv=at(LIMIT + 1)), True, False),
+    ("a coordinate past minus the limit", dict(rv=at(-LIMIT - 1)), True, False),
+]
+
+
+@pytest.mark.parametrize("name", list(RING_TABLE_CHECKS))
+@pytest.mark.parametrize("what, change, without_rows, at_the_limit", BAD_RING_TABLES, ids=[b[0] for b in BAD_RING_TABLES])
+def test_one_list_of_malformed_ring_tables_for_the_four_checks(name, what, change, without_rows, at_the_limit):
+    """Every check refuses the same tables under its own name; the ONE intended difference: at exactly 2^40 the tables in cell
+    units (zonal counts, burn) are refused, the snapped tables of the 1e-6 m grid (overlap, simplify) are accepted."""
+    check = RING_TABLE_CHECKS[name]
+    check(**RING_TABLE)                                                             # the table itself is fine
+    assert _hip.SIMPLIFY_COORD_LIMIT == _hip.OVERLAP_COORD_LIMIT == LIMIT
+    inclusive = name in ("gr_polygon_overlap_areas", "gr_simplify_rings")
+    if (name == "gr_simplify_rings" and not without_rows) or (at_the_limit and inclusive):
+        check(**{**RING_TABLE, **change})
+        return
+    with pytest.raises(ValueError, match=f"^{name}: "):
+        check(**{**RING_TABLE, **change})
+
+
+BAD_CELL_ITEMS = {"p = P": [2, 0, 0, 1, 1, 0, 1], "p = -1": [-1, 0, 0, 1, 1, 0, 1], "no column": [0, 0, 0, 0, 1, 0, 1], "no row": [0, 0, 0, 1, 0, 0, 1],
+                  "a negative side": [0, 5, 5, -1, 1, 0, 1], "65 columns": [0, 0, 0, 65, 1, 0, 1], "129 rows": [0, 0, 0, 1, 129, 0, 1],
+                  "a cell left of the window": [0, -1, 0, 2, 1, 0, 1], "a cell above it": [0, 0, -1, 1, 2, 0, 1],
+                  "a cell right of it": [0, 98, 0, 3, 1, 0, 1], "a cell below it": [0, 0, 197, 1, 4, 0, 1], "hi < lo": [0, 0, 0, 1, 1, 1, 0],
+                  "hi > R": [0, 0, 0, 1, 1, 0, 3], "lo < 0": [0, 0, 0, 1, 1, -1, 1]}
+
+
+@pytest.mark.parametrize("bad", list(BAD_CELL_ITEMS.values()), ids=list(BAD_CELL_ITEMS))
+def test_one_list_of_malformed_cell_items_for_the_zonal_counts_and_the_burn(bad):
+    """The zonal counts check their items against the window (0, 0, W, H); the burn, given that window, refuses the same items
+    and both name the first bad one."""
+    W, H = 100, 200
+    good = [[1, 36, 72, 64, 128, 0, 2], [0, 99, 199, 1, 1, 2, 2]]
+    rv, off, rp = RING_TABLE["rv"], RING_TABLE["off"], RING_TABLE["rp"]
+    said = []
+    for items in (good, good + [bad, bad]):
+        items = np.array(items, dtype=np.int32)
+        for name, check in (("gr_zonal_class_counts", lambda: _hip.check_zonal_tables(H, W, None, rv, off, rp, 2, items, 3)),
+                            ("gr_burn_polygons", lambda: _hip.check_burn_window(0, 0, W, H, items, 2, 2))):
+            if len(items) == 2:
+                check()
+                continue
+            with pytest.raises(ValueError, match=f"^{name}: work item 2 ") as refusal:
+                check()
+            said.append(re.search(r"work item 2 (\(.*?\)) names no polygon row, no block of at most 64 x 128 cells", str(refusal.value)).group(1))
+    assert said == [str(tuple(bad))] * 2
+
+
 # -- the companion header -----------------------------------------------------------------------------------------------------------------
 def test_companion_header_binding_and_library_agree():
     main = (ROOT / "include" / "geograster.h").read_text()
@@ -184,6 +266,14 @@ def test_companion_header_binding_and_library_agree():
     # one ring walk: both kernels call it, and the nest stands once in the unit; the burn kernels are integer only
     source = (ROOT / "geograypher_amd" / "csrc" / "ortho.hip").read_text()
     assert source.count("zonal_parity_walk(") == 3 and source.count("edge_crossing_strict(vx[j]") == 1
+    # ... and Z3, the slot search and the device ring table are DEFINED once, in the shared header; the units only call them
+    units = {p.name: p.read_text() for p in build.SOURCES + build.HEADERS}
+    for pattern in (r"\bvoid edge_crossing_strict\(", r"\bint64_t ring_of_slot\(", r"\bstruct RingTable\b(?! \*)"):
+        assert [name for name, text in units.items() if re.search(pattern, text)] == ["geom_dev.hpp"], pattern
+        assert len(re.findall(pattern, units["geom_dev.hpp"])) == 1, pattern
+    for unit, calls in (("ortho.hip", ("edge_crossing_strict(",)), ("nadir.hip", ("edge_crossing_strict<NARROW>(",)),
+                        ("overlap.hip", ("ring_of_slot(", "RingTable")), ("simplify.hip", ("ring_of_slot(",))):
+        assert all(call in units[unit] for call in calls) and "dev_ceil_div" not in units[unit], unit
     burn = source[source.index("void k_burn_rows("):source.index("}  // namespace")]
     assert not re.search(r"\b(double|float)\b", burn) and burn.count("atomicMax(") == 1
     fn = lib.gr_burn_polygons
