@@ -736,9 +736,9 @@ class PhotogrammetryCameraSet:
             warp_rows = warp_rows * image_scale
         dkey = self.distortion_key(camera.distortion_params, image_scale)
         self._maps_ideal_to_warped[dkey] = np.stack([warp_rows, warp_cols], axis=0)
-        self._maps_device = getattr(self, "_maps_device", {})
-        self._maps_device.pop((dkey, True), None)
-        self._maps_device.pop((dkey, False), None)
+        maps_device = self.__dict__.setdefault("_maps_device", {})
+        for mkey in [mkey for mkey in maps_device if mkey[0] == dkey]:  # the key's uploads, on every backend
+            del maps_device[mkey]
         if backend is None and not reference_inverse:
             import torch
 
@@ -752,7 +752,7 @@ class PhotogrammetryCameraSet:
             self._maps_warped_to_ideal[dkey] = inverse_map_interpolation(self._maps_ideal_to_warped[dkey], inversion_downsample)
             return
         inv = backend.invert_distortion(self.distortion_model(camera), len(h_range), len(w_range), image_scale)
-        self._maps_device[(dkey, False)] = (backend, inv)  # already where the warp kernels want it
+        maps_device[(dkey, False, id(backend))] = (backend, inv)  # already where the warp kernels want it
         self._maps_warped_to_ideal[dkey] = inv.cpu().numpy()
 
     def distortion_model(self, camera: PhotogrammetryCamera) -> Dict[str, float]:
@@ -790,29 +790,36 @@ class PhotogrammetryCameraSet:
             True reproduces the reference's arithmetic bit for bit for `interpolation_order=0` on an integer image within
             the int32 range with an integer `fill_value`, and raises NotImplementedError for every other combination.
         """
-        dkey = self.distortion_key(camera.distortion_params, image_scale)
-        if dkey not in self._maps_ideal_to_warped:  # a set without a lens model raises NotImplementedError here
-            self.make_distortion_map(camera, inversion_downsample, image_scale, backend=backend)
-        inverse_map = self._maps_ideal_to_warped[dkey] if warped_to_ideal else self._maps_warped_to_ideal[dkey]
+        dkey = self.ensure_distortion_map(camera, inversion_downsample, image_scale, backend=backend)
         if backend is None:
             from geograypher_amd._hip import default_backend
 
             backend = default_backend()
-        self._maps_device = getattr(self, "_maps_device", {})
-        mkey = (dkey, bool(warped_to_ideal))
-        if mkey not in self._maps_device or self._maps_device[mkey][0] is not backend:
-            self._maps_device[mkey] = (backend, backend.upload_map(inverse_map))
+        # one upload per (key, direction, backend); the entry holds the backend, so its id() is not reused while the entry
+        # lives.  Threads that drive different backends write different entries, and each reads only what it looked up here
+        mkey = (dkey, bool(warped_to_ideal), id(backend))
+        held = self.__dict__.setdefault("_maps_device", {}).get(mkey)
+        if held is None:
+            inverse_map = self._maps_ideal_to_warped[dkey] if warped_to_ideal else self._maps_warped_to_ideal[dkey]
+            held = self._maps_device[mkey] = (backend, backend.upload_map(inverse_map))
         return backend.warp_image(
-            input_image, self._maps_device[mkey][1], order=interpolation_order, fill_value=fill_value,
+            input_image, held[1], order=interpolation_order, fill_value=fill_value,
             reference_float_roundtrip=reference_float_roundtrip,
         )
+
+    def ensure_distortion_map(self, camera: PhotogrammetryCamera, inversion_downsample: int = 8, image_scale: float = 1.0,
+                              backend=None) -> str:
+        """The camera's distortion key, its two host maps built (`make_distortion_map`) unless they are there already.  The
+        device-list driver calls this for all its cameras before its device threads start: they then only read the maps."""
+        dkey = self.distortion_key(camera.distortion_params, image_scale)
+        if dkey not in self._maps_ideal_to_warped:  # a set without a lens model raises NotImplementedError here
+            self.make_distortion_map(camera, inversion_downsample, image_scale, backend=backend)
+        return dkey
 
     def warp_dewarp_pixels(self, camera: PhotogrammetryCamera, pixels: np.ndarray, inversion_downsample: int = 8,
                            warped_to_ideal: bool = True, backend=None):
         """(N,2) integer (i,j) pixels -> their float positions in the other image (reference: cameras.py:1158-1205)."""
-        dkey = self.distortion_key(camera.distortion_params)
-        if dkey not in self._maps_ideal_to_warped:
-            self.make_distortion_map(camera, inversion_downsample, backend=backend)
+        dkey = self.ensure_distortion_map(camera, inversion_downsample, backend=backend)
         rowmap, colmap = self._maps_warped_to_ideal[dkey] if warped_to_ideal else self._maps_ideal_to_warped[dkey]
         rows = rowmap[pixels[:, 0], pixels[:, 1]]
         cols = colmap[pixels[:, 0], pixels[:, 1]]

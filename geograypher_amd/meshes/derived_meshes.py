@@ -21,7 +21,7 @@ import typing
 import numpy as np
 
 from geograypher_amd.cameras.cameras import PhotogrammetryCamera, PhotogrammetryCameraSet
-from geograypher_amd.meshes.meshes import TexturedPhotogrammetryMesh, _torch, tqdm
+from geograypher_amd.meshes.meshes import TexturedPhotogrammetryMesh, _batched_views, _torch, tqdm
 
 CHUNKED_MESH_BUFFER_DIST_METERS = 125  # geograypher/constants.py:130
 
@@ -97,30 +97,30 @@ class TexturedPhotogrammetryMeshIndexPredictions(TexturedPhotogrammetryMesh):
         n_faces = self.faces.shape[0]
         kwargs.pop("check_null_image", None)
         all_projections = [] if return_all else None
-        counts = torch.zeros((n_faces,), dtype=torch.int32, device=self.backend.device)
+        backend = self.backend
+        counts = torch.zeros((n_faces,), dtype=torch.int32, device=backend.device)
         # the (face, class) pair keys of all views stay on the device; ONE sort + run-length count at the end
-        acc = self.backend.new_pair_accumulator(n_classes, counts, neg1_is_last_face=self.neg1_is_last_face)
-        batch_stop = max(len(cameras) - batch_size + 1, 1)  # trailing views that do not fill a batch are dropped
+        acc = backend.new_pair_accumulator(n_classes, counts, neg1_is_last_face=self.neg1_is_last_face)
+        batch_stop, view_inds = _batched_views(len(cameras), batch_size)
         # a camera set whose segmentor describes every used view as rectangles, or as polygon rings, is aggregated from those
         # tables: no label image is loaded or built
         tables = None
-        n_used = len(range(0, batch_stop, batch_size)) * batch_size
         for supplier, consumer, add_tables in (("get_label_rectangles", "add_rects", self._add_rectangle_tables),
                                                ("get_label_regions", "add_polygons", self._add_region_tables)):
             if tables is None and not return_all and hasattr(acc, consumer) and hasattr(cameras, supplier):
-                tables = [getattr(cameras, supplier)(i, aggregate_img_scale) for i in range(n_used)]
+                tables = [getattr(cameras, supplier)(i, aggregate_img_scale) for i in view_inds]
                 if any(t is None for t in tables):
                     tables = None
                 else:
                     self._add_table_pairs(acc, add_tables, cameras, tables, batch_size, batch_stop, aggregate_img_scale, kwargs)
-        gen = () if tables is not None else self._iter_view_inputs(cameras, batch_size, aggregate_img_scale, True, kwargs)
+        gen = () if tables is not None else self._iter_view_inputs(backend, cameras, batch_size, aggregate_img_scale, True, kwargs)
         for _, ids, img, n_channels in tqdm(gen, total=len(cameras), desc="Aggregating projected viewpoints"):
             if return_all:
                 if img is None:
                     all_projections.append(np.full((n_faces, n_channels), fill_value=np.nan))
                 else:
                     all_projections.append(
-                        self.backend.project_view(ids, img, neg1_is_last_face=self.neg1_is_last_face).cpu().numpy()
+                        backend.project_view(ids, img, neg1_is_last_face=self.neg1_is_last_face).cpu().numpy()
                     )
             if img is None:  # null image: nothing to project (check_null_image=True, derived_meshes.py:465)
                 continue
@@ -166,19 +166,13 @@ class TexturedPhotogrammetryMeshIndexPredictions(TexturedPhotogrammetryMesh):
         return record["selected"], record, summed_projections
 
     def _add_table_pairs(self, acc, add_tables, cameras, tables, batch_size, batch_stop, aggregate_img_scale, pix2face_kwargs):
-        """The table paths of `aggregate_projected_images` (label rectangles, polygon rings): ids come from pix2face exactly as
-        on the image path (same batches, mesh, distortion and keywords); `add_tables(acc, ids, [table of each view])` sends the
-        batch's tables to the device, where the label(s) of each face's winning pixel are looked up."""
-        torch = _torch()
-        mesh = self.get_mesh_in_cameras_coords(cameras)
+        """The table paths of `aggregate_projected_images` (label rectangles, polygon rings): ids come from `_driver_ids` exactly
+        as on the image path (same batches, mesh, distortion and keywords); `add_tables(acc, ids, [table of each view])` sends
+        the batch's tables to the device, where the label(s) of each face's winning pixel are looked up."""
+        backend, mesh = self.backend, self.get_mesh_in_cameras_coords(cameras)
         for batch_start in tqdm(range(0, batch_stop, batch_size), desc="Aggregating projected viewpoints"):
             batch_cameras = cameras.get_subset_cameras(list(range(batch_start, batch_start + batch_size)))
-            ids = self.pix2face(
-                cameras=batch_cameras, mesh=mesh, render_img_scale=aggregate_img_scale, return_tensor=True,
-                **pix2face_kwargs,
-            )
-            if isinstance(ids, np.ndarray):  # distortion applied on the host
-                ids = self.backend._dev(ids.astype(np.int32), torch.int32)
+            ids = self._driver_ids(backend, batch_cameras, mesh, aggregate_img_scale, pix2face_kwargs)
             batch = tables[batch_start:batch_start + batch_size]
             for _, hw in batch:
                 if tuple(hw) != tuple(ids.shape[1:]):

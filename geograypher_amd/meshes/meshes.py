@@ -714,8 +714,7 @@ class TexturedPhotogrammetryMesh:
     def _raster_records(self, cameras, mesh, render_img_scale, near=None, principal_point="center", focal_scaling="scaled",
                         backend=None):
         """Upload the local mesh if needed and pack the (N,16) camera records; returns (records, (h, w))."""
-        if isinstance(cameras, PhotogrammetryCamera):
-            cameras = PhotogrammetryCameraSet([cameras], local_to_epsg_4978_transform=cameras._local_to_epsg_4978_transform)
+        cameras = _as_camera_set(cameras)
         if mesh is None:
             mesh = self.get_mesh_in_cameras_coords(cameras)
         elif not isinstance(mesh, LocalMesh):
@@ -732,11 +731,38 @@ class TexturedPhotogrammetryMesh:
                                              origin=mesh.origin(), focal_scaling=focal_scaling)
         return records, cameras.cameras[0].get_image_size(render_img_scale)
 
-    def _pix2face_device(self, cameras, mesh, render_img_scale, near=None, principal_point="center", focal_scaling="scaled"):
-        """(N,h,w) int32 device tensor of face ids for a camera or camera set."""
-        records, (h, w) = self._raster_records(cameras, mesh, render_img_scale, near=near, principal_point=principal_point,
-                                               focal_scaling=focal_scaling)
-        return self.backend.raster_face_ids(records, h, w)
+    def _view_ids(self, backend, cameras, mesh, scale, *, near=None, principal_point="center", focal_scaling="scaled",
+                  distortion_set=None, apply_distortion=True):
+        """(N, h, w) int32 face ids of a camera or camera set, rasterized -- and, with a `distortion_set` and
+        `apply_distortion`, warped -- by `backend`, on `backend.device`.  Everything here that touches a device names
+        `backend`: the thread that drives it is the only one that does."""
+        records, (h, w) = self._raster_records(cameras, mesh, scale, near=near, principal_point=principal_point,
+                                               focal_scaling=focal_scaling, backend=backend)
+        ids = backend.raster_face_ids(records, h, w)
+        if distortion_set is None or not apply_distortion:
+            return ids
+        # reference: meshes.py:1842-1854.  A base camera set raises NotImplementedError here, as the reference does
+        torch = _torch()
+        warped = []
+        for i, cam in enumerate(_as_camera_set(cameras).cameras):
+            # the id image stays on the device: tensor in, tensor out (gr_warp_nearest_i32)
+            out_i = distortion_set.warp_dewarp_image(camera=cam, input_image=ids[i], warped_to_ideal=False, fill_value=-1,
+                                                     interpolation_order=0, image_scale=scale, backend=backend)
+            warped.append(out_i if isinstance(out_i, torch.Tensor) else torch.as_tensor(np.asarray(out_i)))
+        return torch.stack([w.to(torch.int32) for w in warped], dim=0)
+
+    def _driver_ids(self, backend, cameras, mesh, scale, pix2face_kwargs):
+        """`_view_ids` for the drivers (render_flat, the view loop, the label path, the table paths), which hold pix2face's
+        keywords as their caller gave them; `mesh` is the driver's local mesh, which an explicit `mesh=` keyword replaces.
+        A subclass that overrides `pix2face` decides what its views see, so the drivers still ask it -- that route goes
+        through `self.backend` whatever `backend` is, and only moves the ids over."""
+        _check_pix2face_kwargs(pix2face_kwargs)
+        kwargs = {"mesh": mesh, **pix2face_kwargs}
+        if type(self).pix2face is not TexturedPhotogrammetryMesh.pix2face:
+            ids = self.pix2face(cameras=cameras, render_img_scale=scale, return_tensor=True, **kwargs)
+            return backend._dev(ids, _torch().int32)
+        return self._view_ids(backend, cameras, kwargs["mesh"], scale, distortion_set=kwargs.get("distortion_set"),
+                              apply_distortion=kwargs.get("apply_distortion", True), **_raster_kwargs(kwargs))
 
     def pix2face(
         self,
@@ -770,34 +796,11 @@ class TexturedPhotogrammetryMesh:
         single = isinstance(cameras, PhotogrammetryCamera)
         if not single and not isinstance(cameras, PhotogrammetryCameraSet):
             raise TypeError()
-        ids = self._pix2face_device(cameras, mesh, render_img_scale, near=near, principal_point=principal_point,
-                                    focal_scaling=focal_scaling)
-        if apply_distortion:
-            # reference: meshes.py:1842-1854.  A base camera set raises NotImplementedError here, as the reference does
-            cams = [cameras] if single else cameras.cameras
-            torch = _torch()
-            warped = []
-            for i, cam in enumerate(cams):
-                # the id image stays on the device: tensor in, tensor out (gr_warp_nearest_i32)
-                out_i = distortion_set.warp_dewarp_image(
-                    camera=cam,
-                    input_image=ids[i],
-                    warped_to_ideal=False,
-                    fill_value=-1,
-                    interpolation_order=0,
-                    image_scale=render_img_scale,
-                    backend=self.backend,
-                )
-                warped.append(out_i if isinstance(out_i, torch.Tensor) else torch.as_tensor(np.asarray(out_i)))
-            out = torch.stack([w.to(torch.int32) for w in warped], dim=0)
-            if return_tensor:
-                return out[0] if single else out
-            out = _ids_to_host_int64(out)
-            return out[0] if single else out
-        if return_tensor:
-            return ids[0] if single else ids
-        out = _ids_to_host_int64(ids)  # int64 like the reference (meshes.py:1804)
-        return out[0] if single else out
+        ids = self._view_ids(self.backend, cameras, mesh, render_img_scale, near=near, principal_point=principal_point,
+                             focal_scaling=focal_scaling, distortion_set=distortion_set, apply_distortion=apply_distortion)
+        if not return_tensor:
+            ids = _ids_to_host_int64(ids)  # int64 like the reference (meshes.py:1804)
+        return ids[0] if single else ids
 
     # -- render_flat ---------------------------------------------------------------------------------------------
     def render_flat(
@@ -813,26 +816,19 @@ class TexturedPhotogrammetryMesh:
         (reference: meshes.py:1858-1942, including its batch arithmetic).  `return_tensor=True` yields the renders as
         device tensors instead (no 96 MB host copy per 4000 x 3000 channel: the numpy path is bound by the link)."""
         mesh = self.get_mesh_in_cameras_coords(cameras)
-        if isinstance(cameras, PhotogrammetryCamera):
-            cameras = PhotogrammetryCameraSet([cameras], local_to_epsg_4978_transform=cameras._local_to_epsg_4978_transform)
-        elif not isinstance(cameras, PhotogrammetryCameraSet):
+        cameras = _as_camera_set(cameras)
+        if not isinstance(cameras, PhotogrammetryCameraSet):
             raise TypeError()
         face_texture = self.get_texture(request_vertex_texture=False, try_verts_faces_conversion=True)
         face_texture = np.asarray(face_texture, dtype=np.float64)
-        tex_dev = None
+        backend, tex_dev = self.backend, None
 
-        batch_stop = max(len(cameras) - batch_size + 1, 1)
-        for batch_start in range(0, batch_stop, batch_size):
+        for batch_start in range(0, _batched_views(len(cameras), batch_size)[0], batch_size):
             batch_cameras = cameras[batch_start : batch_start + batch_size]
-            batch_pix2face = self.pix2face(
-                cameras=batch_cameras, mesh=mesh, render_img_scale=render_img_scale, return_tensor=True,
-                **pix2face_kwargs,
-            )
-            if isinstance(batch_pix2face, np.ndarray):  # distortion applied on the host
-                batch_pix2face = self.backend._dev(batch_pix2face.astype(np.int32), _torch().int32)
+            batch_pix2face = self._driver_ids(backend, batch_cameras, mesh, render_img_scale, pix2face_kwargs)
             if tex_dev is None:
-                tex_dev = self.backend._dev(face_texture, _torch().float64)
-            rendered = self.backend.gather_texture(batch_pix2face, tex_dev)
+                tex_dev = backend._dev(face_texture, _torch().float64)
+            rendered = backend.gather_texture(batch_pix2face, tex_dev)
             if not return_tensor:
                 rendered = _to_host(rendered)
             for i in range(rendered.shape[0]):
@@ -842,10 +838,12 @@ class TexturedPhotogrammetryMesh:
                     yield rendered[i]
 
     # -- project_images ------------------------------------------------------------------------------------------
-    def _iter_view_inputs(self, cameras, batch_size, aggregate_img_scale, check_null_image, pix2face_kwargs, loader_threads=None):
-        """Shared view loop of project_images / aggregate_projected_images (reference: meshes.py:1970-1996):
-        yields (view index, ids (h,w) int32 device tensor, image (h,w,C) device tensor or None for a null image,
-        n_channels).  Trailing cameras that do not fill a batch are dropped, as in the reference (1976-1977).
+    def _iter_view_inputs(self, backend, cameras, batch_size, aggregate_img_scale, check_null_image, pix2face_kwargs,
+                          loader_threads=None, lookups=None):
+        """Shared view loop of project_images / aggregate_projected_images (reference: meshes.py:1970-1996) on ONE backend,
+        driven by the calling thread: yields (view index, ids (h,w) int32 device tensor, image (h,w,C) device tensor or None
+        for a null image, n_channels).  Trailing cameras that do not fill a batch are dropped, as in the reference (1976-1977).
+        `lookups` is the call's `_lookup_rule` (default: that of `cameras`, one device thread).
 
         Input pipeline: the reference converts every image to float64 on the host and the first versions here uploaded that
         (a 4000 x 3000 RGB photo: 36 MB of uint8 blown up to 288 MB, copied from pageable memory, synchronously).  Now the
@@ -857,28 +855,19 @@ class TexturedPhotogrammetryMesh:
         torch = _torch()
         from concurrent.futures import ThreadPoolExecutor
 
-        on_gpu = self.backend.device.type == "cuda"
-        batch_stop = max(len(cameras) - batch_size + 1, 1)
-        order = [b + i for b in range(0, batch_stop, batch_size) for i in range(batch_size)]
+        on_gpu = backend.device.type == "cuda"
+        batch_stop, order = _batched_views(len(cameras), batch_size)
         slots = [None, None]        # pinned staging tensors
         slot_free = [None, None]    # event after the last copy out of the slot
         # File-backed photos of a plain camera set (cameras.py:154-174 not overridden): the image is staged in its FILE dtype
         # and `get_image`'s own arithmetic -- / 255.0 for uint8, skimage's resize for aggregate_img_scale != 1 -- runs on the
         # device (HipRaster.resize_image): a 4000 x 3000 RGB photo crosses the link as 36 MB of uint8 instead of a float64
         # image, and no CPU resizer exists in the product.
-        native_files = (
-            type(cameras).get_image_by_index is PhotogrammetryCameraSet.get_image_by_index
-            and len(cameras.cameras) > 0
-            and all(type(cam).get_image is PhotogrammetryCamera.get_image for cam in cameras.cameras)
-            and hasattr(self.backend, "resize_image")
-        )
+        native_files = _plain_files(cameras) and hasattr(backend, "resize_image")
         # a loader thread stages view i + 1 while the device works on view i -- only where look-ups are known to be
-        # independent (file reads; a camera set or segmentor that says so): an arbitrary segmentor may run its own GPU work
-        # or keep state that must not run beside pix2face on another thread
-        threaded = native_files or bool(
-            getattr(cameras, "thread_safe_lookup", False)
-            or getattr(getattr(cameras, "segmentor", None), "thread_safe_lookup", False)
-        )
+        # independent (`_lookup_rule`): an arbitrary segmentor may run its own GPU work or keep state that must not run
+        # beside pix2face on another thread
+        threaded, lookup_lock = lookups or _lookup_rule(cameras)
         native = {"uint8": torch.uint8, "int8": torch.int8, "int16": torch.int16, "int32": torch.int32, "int64": torch.int64,
                   "float16": torch.float16, "float32": torch.float32, "float64": torch.float64}
 
@@ -905,7 +894,7 @@ class TexturedPhotogrammetryMesh:
                 if aggregate_img_scale != 1.0 or img.dtype == np.uint8:
                     resize_to = (out_hw, img.dtype == np.uint8)  # target size, `/ 255.0` first (cameras.py:158-159)
             else:
-                img = np.asarray(cameras.get_image_by_index(order[pos], aggregate_img_scale))
+                img = np.asarray(_locked(lookup_lock, cameras.get_image_by_index, order[pos], aggregate_img_scale))
             n_channels = 1 if img.ndim == 2 else img.shape[-1]
             flat = np.reshape(img, (img.shape[0], img.shape[1], -1))
             if flat.dtype == np.bool_:
@@ -952,12 +941,7 @@ class TexturedPhotogrammetryMesh:
             for batch_start in range(0, batch_stop, batch_size):
                 batch_inds = list(range(batch_start, batch_start + batch_size))
                 batch_cameras = cameras.get_subset_cameras(batch_inds)
-                batch_pix2face = self.pix2face(
-                    cameras=batch_cameras, mesh=mesh, render_img_scale=aggregate_img_scale, return_tensor=True,
-                    **pix2face_kwargs,
-                )
-                if isinstance(batch_pix2face, np.ndarray):  # distortion applied on the host
-                    batch_pix2face = self.backend._dev(batch_pix2face.astype(np.int32), torch.int32)
+                batch_pix2face = self._driver_ids(backend, batch_cameras, mesh, aggregate_img_scale, pix2face_kwargs)
                 for i in range(batch_pix2face.shape[0]):
                     if pending is None:  # not threaded: the view is fetched when it is consumed, like the reference does
                         pending = _Now(stage(pos & 1, pos, copy_pool))
@@ -966,14 +950,14 @@ class TexturedPhotogrammetryMesh:
                     pos += 1
                     pending = submit(pos & 1, pos)
                     if on_gpu:
-                        dev_img = host.to(self.backend.device, non_blocking=True)
+                        dev_img = host.to(backend.device, non_blocking=True)
                         if host.is_pinned():
                             slot_free[k] = torch.cuda.Event()
-                            slot_free[k].record(torch.cuda.current_stream(self.backend.device))
+                            slot_free[k].record(torch.cuda.current_stream(backend.device))
                     else:
                         dev_img = host
                     if resize_to is not None:  # get_image's own arithmetic, on the device (cameras.py:158-172)
-                        dev_img = self.backend.resize_image(dev_img, resize_to[0], divide_by_255=resize_to[1])
+                        dev_img = backend.resize_image(dev_img, resize_to[0], divide_by_255=resize_to[1])
                     if check_null_image and dev_img.is_floating_point() and not bool(torch.isfinite(dev_img).any()):
                         yield batch_start + i, batch_pix2face[i], None, n_channels
                         continue
@@ -992,13 +976,14 @@ class TexturedPhotogrammetryMesh:
         with `neg1_is_last_face` background pixels address the last face exactly like numpy's index -1 does."""
         n_faces = self.faces.shape[0]
         loader_threads = pix2face_kwargs.pop("loader_threads", None)
+        backend = self.backend
         for _, ids, img, n_channels in self._iter_view_inputs(
-            cameras, batch_size, aggregate_img_scale, check_null_image, pix2face_kwargs, loader_threads
+            backend, cameras, batch_size, aggregate_img_scale, check_null_image, pix2face_kwargs, loader_threads
         ):
             if img is None:
                 yield np.full((n_faces, n_channels), fill_value=np.nan)
             else:
-                yield _to_host(self.backend.project_view(ids, img, neg1_is_last_face=self.neg1_is_last_face))
+                yield _to_host(backend.project_view(ids, img, neg1_is_last_face=self.neg1_is_last_face))
 
     @staticmethod
     @contextlib.contextmanager
@@ -1074,16 +1059,13 @@ class TexturedPhotogrammetryMesh:
         n_faces = self.faces.shape[0]
         check_null_image = bool(kwargs.pop("check_null_image", False))
 
-        batch_stop = max(len(cameras) - batch_size + 1, 1)
-        view_inds = [i for s in range(0, batch_stop, batch_size) for i in range(s, s + batch_size)]
+        _, view_inds = _batched_views(len(cameras), batch_size)
 
         loader_threads = kwargs.pop("loader_threads", None)
-        unknown = [k for k in kwargs if k not in _PIX2FACE_KWARGS]
-        if unknown:
-            raise TypeError(f"pix2face() got an unexpected keyword argument {unknown[0]!r}")
+        _check_pix2face_kwargs(kwargs)
         # The fused path rasterizes with the plain pinhole records.  Whatever else pix2face honours -- a distortion set
-        # (unless explicitly switched off), an explicit mesh -- goes through pix2face itself: ids per chunk from
-        # `pix2face(return_tensor=True, **kwargs)`, then the unfused winner + vote kernels.
+        # (unless explicitly switched off), an explicit mesh -- takes the ids of each chunk from `_driver_ids(backend, ...)`,
+        # then the unfused winner + vote kernels.
         wants_warp = kwargs.get("distortion_set") is not None and kwargs.get("apply_distortion", True)
         fused_ok = not wants_warp and kwargs.get("mesh") is None
         label_fn = getattr(cameras, "get_label_index_image", None) if not return_all else None
@@ -1091,89 +1073,79 @@ class TexturedPhotogrammetryMesh:
             label_fn = None  # class indices do not fit the uint8 label images of the fast path
         first_label = label_fn(view_inds[0], aggregate_img_scale) if label_fn is not None else None
 
+        # devices=[...]: a backend is driven by ONE host thread, and everything that touches a device names its backend.  What
+        # the device threads share is settled here, on the caller's thread, before `_on_each_device` starts them: the local
+        # mesh (cached), the host distortion maps of every lens among the views (built with the first backend, as the first
+        # warp would; afterwards each thread only adds the uploads of its own backend) and the call's one look-up rule
+        single_view = len(view_inds) == 1
+        backends = self.backends if first_label is not None or not (return_all or single_view) else self.backends[:1]
+        mesh = self.get_mesh_in_cameras_coords(cameras)
+        if wants_warp:
+            for i in view_inds:
+                kwargs["distortion_set"].ensure_distortion_map(cameras.cameras[i], image_scale=aggregate_img_scale,
+                                                               backend=backends[0])
+        lookups = _lookup_rule(cameras, n_device_threads=len(backends))
+
         if first_label is not None:
             # ---- index-label fast path: uint32 votes on device --------------------------------------------------------
-            my_inds = view_inds[rank::world]
-            mesh = self.get_mesh_in_cameras_coords(cameras)
             C = int(cameras.n_image_channels())
-            backends = self.backends
             labels_known = {view_inds[0]: first_label}
 
-            def run(k):
-                return self._aggregate_label_views(backends[k], cameras, my_inds[k::len(backends)], mesh, C, label_fn, labels_known,
-                                                   batch_size, aggregate_img_scale, loader_threads, fused_ok, kwargs,
-                                                   progress=(k == 0), own_stream=len(backends) > 1)
+            def run(backend, inds, first):
+                return self._aggregate_label_views(backend, cameras, inds, mesh, C, label_fn, labels_known, batch_size,
+                                                   aggregate_img_scale, loader_threads, fused_ok, kwargs, lookups, progress=first)
 
-            if len(backends) == 1:
-                votes, counts = run(0)
-            else:
-                # one host thread per device (the C calls and torch's copies release the interpreter lock); the partial votes
-                # come home to the first device -- peer copies -- and are added there: integer sums, so the result is the
-                # single-device one bit for bit, whatever the number of devices
-                from concurrent.futures import ThreadPoolExecutor
-
-                with ThreadPoolExecutor(max_workers=len(backends)) as dev_pool:
-                    parts = list(dev_pool.map(run, range(len(backends))))
-                votes, counts = _add_on_first(parts)
+            # integer sums: the result is the single-device one bit for bit, whatever the number of devices
+            votes, counts = _add_on_first(_on_each_device(backends, view_inds[rank::world], run))
             if distributed and world > 1:
                 dist_utils.all_reduce_votes(votes, counts)
-            avg, summed, cnt = self.backend.finalize_votes(votes, counts)
+            avg, summed, cnt = backends[0].finalize_votes(votes, counts)
             return _to_host(avg), {
                 "projection_counts": _to_host(cnt),
                 "summed_projections": _to_host(summed),
             }
 
         # ---- general path: float images; nansum + finite-row counts accumulate on device (meshes.py:2057-2067) ----------
-        single_view = len(view_inds) == 1
         shard = distributed and world > 1 and not single_view
         if shard and return_all:
             raise NotImplementedError("return_all keeps every view's projection: not available with distributed=True")
-        projections = []   # every view's own projection, for return_all and for the single view
+        projections = []   # every view's own projection, for return_all and for the single view: first device only
         mine = view_inds[rank::world] if shard else view_inds   # the per-view arithmetic does not depend on the other views
-        if len(self.backends) > 1 and not return_all and not single_view:
-            # devices=[...]: this rank's views dealt round-robin to the devices, each running the per-view recurrence over its own
-            # views on a host thread of its own; the partial sums and counts are added on the first device.  The float contract
-            # is that of views sharded over processes (include/geograster.h, gr_project_values_f64): counts exact, sums of finite
-            # inputs within 1e-12 relative of the serial result
-            import copy
-            from concurrent.futures import ThreadPoolExecutor
+        whole = len(backends) == 1 and not shard   # the caller's set in the caller's batches; a share of it goes view by view
 
-            self.get_mesh_in_cameras_coords(cameras)   # the local mesh, cached before the workers ask for it
-
-            def run(k):
-                inds_k = mine[k::len(self.backends)]
-                if not inds_k:
-                    return None
-                worker = copy.copy(self)   # same arrays, caches and upload table; its own backend
-                worker._backend, worker._backends = self.backends[k], [self.backends[k]]
-                with _driving(self.backends[k], own_stream=True):
-                    return self._nansum_views(self.backends[k], (view[1:] for view in worker._iter_view_inputs(
-                        cameras.get_subset_cameras(inds_k), 1, aggregate_img_scale, check_null_image, dict(kwargs), loader_threads)))
-
-            with ThreadPoolExecutor(max_workers=len(self.backends)) as dev_pool:
-                parts = [p for p in dev_pool.map(run, range(len(self.backends))) if p is not None and p[0] is not None]
-            sums, counts, n_channels = (*_add_on_first([p[:2] for p in parts]), parts[0][2]) if parts else (None, None, None)
-        else:
-            my_cams, per_batch = (cameras.get_subset_cameras(mine), 1) if shard else (cameras, batch_size)
-            gen = self._iter_view_inputs(my_cams, per_batch, aggregate_img_scale, check_null_image, kwargs, loader_threads) if len(my_cams) else iter(())
+        def run(backend, inds, first):
+            """The per-view recurrence over `inds` on one device.  The float contract of several devices is that of views
+            sharded over processes (include/geograster.h, gr_project_values_f64): counts exact, sums of finite inputs within
+            1e-12 relative of the serial result."""
+            if not inds:
+                return None, None, None
+            my_cams, per_batch = (cameras, batch_size) if whole else (cameras.get_subset_cameras(inds), 1)
+            gen = self._iter_view_inputs(backend, my_cams, per_batch, aggregate_img_scale, check_null_image, kwargs,
+                                         loader_threads, lookups)
+            if len(backends) == 1:
+                gen = tqdm(gen, total=len(my_cams), desc="Aggregating projected viewpoints")
 
             def views():
-                for _, ids, img, nch in tqdm(gen, total=len(my_cams), desc="Aggregating projected viewpoints"):
+                for _, ids, img, nch in gen:
                     if return_all or single_view:
                         if img is None:
                             projections.append(np.full((n_faces, nch), fill_value=np.nan))
                         else:
-                            projections.append(_to_host(self.backend.project_view(ids, img, neg1_is_last_face=self.neg1_is_last_face)))
+                            projections.append(_to_host(backend.project_view(ids, img, neg1_is_last_face=self.neg1_is_last_face)))
                     yield ids, img, nch
 
-            sums, counts, n_channels = self._nansum_views(self.backend, views())
+            return self._nansum_views(backend, views())
+
+        parts = [p for p in _on_each_device(backends, mine, run) if p[0] is not None]   # a device without views: nothing
+        sums, counts = _add_on_first([p[:2] for p in parts]) if parts else (None, None)
+        n_channels = parts[0][2] if parts else None
         if shard:
             if sums is None:  # a rank without views still takes part in the collective
                 n_channels = int(np.asarray(cameras.get_image_by_index(view_inds[0], aggregate_img_scale)).reshape(
                     cameras.cameras[view_inds[0]].get_image_size(aggregate_img_scale) + (-1,)).shape[-1])
-                sums, counts = self._zero_sums(self.backend, n_channels)
+                sums, counts = self._zero_sums(backends[0], n_channels)
             dist_utils.all_reduce_sums(sums, counts)
-        avg, summed, cnt = self.backend.finalize_sums(sums, counts)
+        avg, summed, cnt = backends[0].finalize_sums(sums, counts)
         avg, summed, cnt = _to_host(avg), _to_host(summed), _to_host(cnt)
         if single_view:
             # the reference keeps the first projection as is (meshes.py:2057-2058): a NaN channel of a seen face survives
@@ -1208,97 +1180,89 @@ class TexturedPhotogrammetryMesh:
         return sums, counts, n_channels
 
     def _aggregate_label_views(self, backend, cameras, inds, mesh, C, label_fn, labels_known, batch_size, aggregate_img_scale,
-                               loader_threads, fused_ok, kwargs, progress=True, own_stream=False):
-        """The index-label fast path of aggregate_projected_images for the views `inds` on ONE backend: returns that device's
-        (votes (F,C), counts (F,)) int32 tensors.  Called once for a single-device mesh, once per device -- each on a host
-        thread of its own -- for `devices=[...]`."""
+                               loader_threads, fused_ok, kwargs, lookups, progress=True):
+        """The index-label fast path of aggregate_projected_images for the views `inds` on ONE backend, driven by the calling
+        thread (a `run` of `_on_each_device`): returns that device's (votes (F,C), counts (F,)) int32 tensors.  `lookups` is
+        the call's `_lookup_rule`."""
         torch = _torch()
         import os
         from concurrent.futures import ThreadPoolExecutor
 
         on_gpu = backend.device.type == "cuda"
-        with _driving(backend, own_stream):
-            self._ensure_uploaded(mesh, backend)
-            votes, counts = backend.new_vote_buffers(C)
-            if len(inds) == 0:
-                return votes, counts
-            # launch groups of up to 32 views; a short run is still cut into at least four chunks, so that the loader stages
-            # chunk i + 1 while chunk i crosses the link (16 views in ONE chunk ran staging, copy and kernels back to back)
-            chunk = max(int(batch_size), min(32, max(1, -(-len(inds) // 4))))
-            chunks = [inds[c0 : c0 + chunk] for c0 in range(0, len(inds), chunk)]
-
-            # Input pipeline (row f4).  The label images of a chunk are decoded straight into ONE pinned (n,h,w) uint8
-            # staging tensor (no stack / pin copies), by `loader_threads` workers when the segmentor says its lookups
-            # are thread safe (file look-ups and in-memory arrays are; an arbitrary model may not be), while the GPU
-            # works on the previous chunk.
-            thread_safe = bool(getattr(getattr(cameras, "segmentor", None), "thread_safe_lookup", False))
-            n_workers = int(loader_threads if loader_threads is not None else (min(16, os.cpu_count() or 1) if thread_safe else 1))
-            # the label images must have the size the camera records are built for (the reference fails with a shape
-            # error in `textured_faces[flat_pix2face] = flat_img` otherwise, meshes.py:1998-2001)
-            h0, w0 = cameras.cameras[inds[0]].get_image_size(aggregate_img_scale)
-
-            def check_shape(shape, i):
-                if tuple(shape[:2]) != (h0, w0):
-                    raise ValueError(
-                        f"label image of view {i} has shape {tuple(shape[:2])}, but the camera renders {(h0, w0)} at "
-                        f"aggregate_img_scale={aggregate_img_scale}"
-                    )
-
-            def one_label(i):
-                return labels_known[i] if i in labels_known else label_fn(i, aggregate_img_scale)
-
-            probe = next(iter(labels_known.values()))
-
-            def load_chunk(chunk_inds, img_pool):
-                if isinstance(probe, torch.Tensor):  # the segmentor already produces tensors
-                    labs = [one_label(i) for i in chunk_inds]
-                    for i, lab in zip(chunk_inds, labs):
-                        check_shape(lab.shape, i)
-                    labs = [torch.where((lab < 0) | (lab > 255), torch.full_like(lab, 255), lab)
-                            if lab.dtype != torch.uint8 else lab for lab in labs]
-                    return torch.stack([lab.to(backend.device, torch.uint8) for lab in labs], dim=0)
-                stage = torch.empty((len(chunk_inds), h0, w0), dtype=torch.uint8, pin_memory=on_gpu)
-                view = stage.numpy()
-
-                def fill(k):
-                    lab = np.asarray(one_label(chunk_inds[k]))
-                    check_shape(lab.shape, chunk_inds[k])
-                    if lab.dtype != np.uint8:  # an index outside [0, 255] is no class: the ignore value, not a wrapped class
-                        lab = np.where((lab < 0) | (lab > 255), 255, lab)
-                    view[k] = lab  # casts to uint8 while copying
-
-                list(img_pool.map(fill, range(len(chunk_inds))))
-                return stage
-
-            steps = range(len(chunks))
-            if progress:
-                steps = tqdm(steps, total=len(chunks), desc="Aggregating projected viewpoints")
-            with ThreadPoolExecutor(max_workers=1) as pool, ThreadPoolExecutor(max_workers=max(n_workers, 1)) as img_pool:
-                pending = pool.submit(load_chunk, chunks[0], img_pool)
-                for ci in steps:
-                    lab = pending.result()
-                    pending = pool.submit(load_chunk, chunks[ci + 1], img_pool) if ci + 1 < len(chunks) else None
-                    # the chunk's cameras only: a subset of the segmentor wrapper would deep-copy the segmentor with it
-                    # (segmentor.py:49-55) -- every in-memory label image of an ArrayLabelSegmentor, per chunk
-                    sub = getattr(cameras, "base_camera_set", cameras).get_subset_cameras(chunks[ci])
-                    if lab.device.type != backend.device.type:
-                        lab = lab.to(backend.device, non_blocking=True)
-                    if fused_ok:
-                        # fused: face ids stay in the rasterizer's LDS tiles, only per-face winners reach HBM
-                        records, _ = self._raster_records(sub, mesh, aggregate_img_scale, backend=backend, **_raster_kwargs(kwargs))
-                        backend.raster_project_labels(records, lab, C, votes, counts, neg1_is_last_face=self.neg1_is_last_face)
-                    else:
-                        p2f_kwargs = {k: v for k, v in kwargs.items() if k in _PIX2FACE_KWARGS}
-                        p2f_kwargs.setdefault("mesh", mesh)
-                        ids = self.pix2face(cameras=sub, render_img_scale=aggregate_img_scale, return_tensor=True, **p2f_kwargs)
-                        if isinstance(ids, np.ndarray):
-                            ids = backend._dev(ids.astype(np.int32), torch.int32)
-                        elif ids.device != backend.device:
-                            ids = ids.to(backend.device)
-                        if tuple(ids.shape[-2:]) != (h0, w0):
-                            raise ValueError(f"pix2face returned {tuple(ids.shape[-2:])} ids for {(h0, w0)} label images")
-                        backend.project_labels(ids, lab, C, votes, counts, neg1_is_last_face=self.neg1_is_last_face)
+        thread_safe, lookup_lock = lookups
+        self._ensure_uploaded(mesh, backend)
+        votes, counts = backend.new_vote_buffers(C)
+        if len(inds) == 0:
             return votes, counts
+        # launch groups of up to 32 views; a short run is still cut into at least four chunks, so that the loader stages
+        # chunk i + 1 while chunk i crosses the link (16 views in ONE chunk ran staging, copy and kernels back to back)
+        chunk = max(int(batch_size), min(32, max(1, -(-len(inds) // 4))))
+        chunks = [inds[c0 : c0 + chunk] for c0 in range(0, len(inds), chunk)]
+
+        # Input pipeline (row f4).  The label images of a chunk are decoded straight into ONE pinned (n,h,w) uint8
+        # staging tensor (no stack / pin copies), by `loader_threads` workers when the look-ups are thread safe (file
+        # look-ups and in-memory arrays are; an arbitrary model may not be), while the GPU works on the previous chunk.
+        n_workers = int(loader_threads if loader_threads is not None else (min(16, os.cpu_count() or 1) if thread_safe else 1))
+        # the label images must have the size the camera records are built for (the reference fails with a shape
+        # error in `textured_faces[flat_pix2face] = flat_img` otherwise, meshes.py:1998-2001)
+        h0, w0 = cameras.cameras[inds[0]].get_image_size(aggregate_img_scale)
+
+        def check_shape(shape, i):
+            if tuple(shape[:2]) != (h0, w0):
+                raise ValueError(
+                    f"label image of view {i} has shape {tuple(shape[:2])}, but the camera renders {(h0, w0)} at "
+                    f"aggregate_img_scale={aggregate_img_scale}"
+                )
+
+        def one_label(i):
+            return labels_known[i] if i in labels_known else _locked(lookup_lock, label_fn, i, aggregate_img_scale)
+
+        probe = next(iter(labels_known.values()))
+
+        def load_chunk(chunk_inds, img_pool):
+            if isinstance(probe, torch.Tensor):  # the segmentor already produces tensors
+                labs = [one_label(i) for i in chunk_inds]
+                for i, lab in zip(chunk_inds, labs):
+                    check_shape(lab.shape, i)
+                labs = [torch.where((lab < 0) | (lab > 255), torch.full_like(lab, 255), lab)
+                        if lab.dtype != torch.uint8 else lab for lab in labs]
+                return torch.stack([lab.to(backend.device, torch.uint8) for lab in labs], dim=0)
+            stage = torch.empty((len(chunk_inds), h0, w0), dtype=torch.uint8, pin_memory=on_gpu)
+            view = stage.numpy()
+
+            def fill(k):
+                lab = np.asarray(one_label(chunk_inds[k]))
+                check_shape(lab.shape, chunk_inds[k])
+                if lab.dtype != np.uint8:  # an index outside [0, 255] is no class: the ignore value, not a wrapped class
+                    lab = np.where((lab < 0) | (lab > 255), 255, lab)
+                view[k] = lab  # casts to uint8 while copying
+
+            list(img_pool.map(fill, range(len(chunk_inds))))
+            return stage
+
+        steps = range(len(chunks))
+        if progress:
+            steps = tqdm(steps, total=len(chunks), desc="Aggregating projected viewpoints")
+        with ThreadPoolExecutor(max_workers=1) as pool, ThreadPoolExecutor(max_workers=max(n_workers, 1)) as img_pool:
+            pending = pool.submit(load_chunk, chunks[0], img_pool)
+            for ci in steps:
+                lab = pending.result()
+                pending = pool.submit(load_chunk, chunks[ci + 1], img_pool) if ci + 1 < len(chunks) else None
+                # the chunk's cameras only: a subset of the segmentor wrapper would deep-copy the segmentor with it
+                # (segmentor.py:49-55) -- every in-memory label image of an ArrayLabelSegmentor, per chunk
+                sub = getattr(cameras, "base_camera_set", cameras).get_subset_cameras(chunks[ci])
+                if lab.device.type != backend.device.type:
+                    lab = lab.to(backend.device, non_blocking=True)
+                if fused_ok:
+                    # fused: face ids stay in the rasterizer's LDS tiles, only per-face winners reach HBM
+                    records, _ = self._raster_records(sub, mesh, aggregate_img_scale, backend=backend, **_raster_kwargs(kwargs))
+                    backend.raster_project_labels(records, lab, C, votes, counts, neg1_is_last_face=self.neg1_is_last_face)
+                else:
+                    ids = self._driver_ids(backend, sub, mesh, aggregate_img_scale, kwargs)
+                    if tuple(ids.shape[-2:]) != (h0, w0):
+                        raise ValueError(f"pix2face returned {tuple(ids.shape[-2:])} ids for {(h0, w0)} label images")
+                    backend.project_labels(ids, lab, C, votes, counts, neg1_is_last_face=self.neg1_is_last_face)
+        return votes, counts
 
     # the north star's name for the same method
     aggregate_viewpoints = aggregate_projected_images
@@ -2165,6 +2129,71 @@ def _driving(backend, own_stream=False):
         yield
         if on_gpu and own_stream:
             torch.cuda.current_stream(backend.device).synchronize()
+
+
+def _on_each_device(backends, inds, run):
+    """The `devices=[...]` fan-out: the views `inds` dealt round-robin, `run(backend, inds[k::n], first=k == 0)` for every
+    backend on a host thread of its own (the C calls and torch's copies release the interpreter lock) -- the only thread that
+    drives that backend during the call.  One backend runs on the caller's thread.  Returns the partials in device order;
+    `_add_on_first` is where they meet."""
+    n = len(backends)
+
+    def drive(k):
+        with _driving(backends[k], own_stream=n > 1):
+            return run(backends[k], inds[k::n], first=k == 0)
+
+    if n == 1:
+        return [drive(0)]
+    from concurrent.futures import ThreadPoolExecutor
+
+    with ThreadPoolExecutor(max_workers=len(backends)) as dev_pool:
+        return list(dev_pool.map(drive, range(n)))
+
+
+def _plain_files(cameras) -> bool:
+    """File-backed photos of a plain camera set: neither the set's nor its cameras' image look-up is overridden."""
+    return (type(cameras).get_image_by_index is PhotogrammetryCameraSet.get_image_by_index and len(cameras.cameras) > 0
+            and all(type(cam).get_image is PhotogrammetryCamera.get_image for cam in cameras.cameras))
+
+
+def _lookup_rule(cameras, n_device_threads: int = 1):
+    """(thread_safe, lock) -- how a call fetches the images / labels of `cameras`.  thread_safe: file reads, or a camera set
+    or segmentor that says so (`thread_safe_lookup`); only then are look-ups made ahead on loader threads.  Otherwise one
+    caller at a time: with several device threads every look-up goes through the one lock (`_locked`); one thread needs none."""
+    thread_safe = _plain_files(cameras) or bool(getattr(cameras, "thread_safe_lookup", False)
+                                                or getattr(getattr(cameras, "segmentor", None), "thread_safe_lookup", False))
+    if thread_safe or n_device_threads == 1:
+        return thread_safe, None
+    import threading
+
+    return thread_safe, threading.Lock()
+
+
+def _locked(lock, fn, *args):
+    if lock is None:
+        return fn(*args)
+    with lock:
+        return fn(*args)
+
+
+def _as_camera_set(cameras):
+    """A single camera as the one-element set the raster calls walk; a set as it is."""
+    if isinstance(cameras, PhotogrammetryCamera):
+        return PhotogrammetryCameraSet([cameras], local_to_epsg_4978_transform=cameras._local_to_epsg_4978_transform)
+    return cameras
+
+
+def _batched_views(n_views: int, batch_size: int):
+    """(batch_stop, the views that batches of `batch_size` use, in order): trailing views that do not fill a batch are
+    dropped, and a batch larger than the set still names its views, as in the reference (meshes.py:1976-1977)."""
+    batch_stop = max(n_views - batch_size + 1, 1)
+    return batch_stop, [start + i for start in range(0, batch_stop, batch_size) for i in range(batch_size)]
+
+
+def _check_pix2face_kwargs(kwargs: dict) -> None:
+    unknown = [k for k in kwargs if k not in _PIX2FACE_KWARGS]
+    if unknown:
+        raise TypeError(f"pix2face() got an unexpected keyword argument {unknown[0]!r}")
 
 
 def _add_on_first(parts):

@@ -306,6 +306,44 @@ def test_mask_image(kind, request, tmp_path, k1, w2i):
     assert sorted(np.unique(dewarped)) == [0, 1, 2]
 
 
+def test_device_maps_are_kept_per_backend(tmp_path, oracle_backend_cls):
+    """The uploaded sampling maps are cached per (key, direction, BACKEND): two backends that take turns on one set -- the
+    device threads of `devices=[...]` -- upload once each, not once per turn, and every warp is handed the tensor its own
+    backend uploaded.  Rebuilding the key's maps drops the uploads of every backend."""
+    class Recording(oracle_backend_cls):
+        def __init__(self):
+            super().__init__()
+            self.uploaded, self.handed = [], []
+
+        def upload_map(self, inverse_map):
+            self.uploaded.append(super().upload_map(inverse_map))
+            return self.uploaded[-1]
+
+        def warp_image(self, input_image, map_t, *args, **kwargs):
+            self.handed.append(map_t)
+            return super().warp_image(input_image, map_t, *args, **kwargs)
+
+    image = np.arange(21 * 21, dtype=np.int32).reshape(21, 21)
+    cameras = _metashape_set(tmp_path)
+    camera = simplify_camera(cameras.cameras[0], image)
+    camera.distortion_params["k1"] = -0.5
+    a, b = Recording(), Recording()
+    outs = {id(a): [], id(b): []}
+    for _ in range(3):
+        for be in (a, b):
+            outs[id(be)].append(cameras.warp_dewarp_image(camera, image, warped_to_ideal=True, interpolation_order=0, backend=be))
+    for be in (a, b):
+        assert len(be.uploaded) == 1 and len(be.handed) == 3
+        assert all(m is be.uploaded[0] for m in be.handed)
+        for out in outs[id(be)]:
+            np.testing.assert_array_equal(out, outs[id(a)][0])
+    assert a.uploaded[0] is not b.uploaded[0]
+    cameras.make_distortion_map(camera, backend=a)
+    for be in (a, b):
+        cameras.warp_dewarp_image(camera, image, warped_to_ideal=True, interpolation_order=0, backend=be)
+        assert len(be.uploaded) == 2 and be.handed[-1] is be.uploaded[1]
+
+
 @pytest.mark.parametrize("w2i,k1,relationship", [(True, 0, operator.eq), (True, 0.5, operator.lt), (True, -0.5, operator.gt),
                                                  (False, 0, operator.eq), (False, 0.5, operator.gt), (False, -0.5, operator.lt)])
 def test_warp_dewarp_pixels(tmp_path, oracle_backend_cls, w2i, k1, relationship):
