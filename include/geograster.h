@@ -12,13 +12,20 @@
  *  - The caller allocates and owns all inputs and outputs.  The library allocates only per-context scratch
  *    (bin lists, per-face winners, one arena for the stage calls), grown lazily, freed by gr_ctx_destroy.
  *  - All work is enqueued on `stream` (a hipStream_t passed as void*; NULL = the default stream) and is
- *    asynchronous.  No hidden synchronisation except: gr_ctx_destroy, gr_mesh_upload (index validation) and
- *    scratch growth (hipMalloc/hipFree when a larger batch, image or mesh is first seen).
+ *    asynchronous.  No hidden synchronisation except: gr_ctx_create and gr_ctx_destroy (the whole device), gr_mesh_upload
+ *    (index validation), scratch growth (hipMalloc/hipFree when a larger batch, image or mesh is first seen), the first
+ *    launch group of a raster call on a (mesh, image size) the context has learned nothing about (its counts are read back
+ *    once, GR_VAR_NO_LOOK switches that off), and the calls whose comment says "Synchronises `stream`": they read a count or
+ *    a flag back, or return with their scratch free.  Such a call waits for `stream` alone, never for the device or for the
+ *    null stream (tests/test_stream_contract_gpu.py runs every call with the null stream held).
  *  - Return value: 0 (GR_OK) or a negative GR_E* code; text via gr_last_error().  No C++ exception crosses the ABI.
  *  - A context belongs to one (device, host thread); distinct contexts are independent.
  *  - Calls of one context on different streams may be issued back to back: the stage calls share one scratch arena per
  *    context ("context scratch" below), and the library orders their use of it -- a call that finds the arena's last user
- *    on another stream waits for that stream first.  On one stream nothing is added.
+ *    on another stream waits for that stream first.  On one stream nothing is added.  The promise covers the stage arena
+ *    ONLY: two raster calls (gr_raster_face_ids, gr_raster_project_labels_u8) of one context on two streams share the bin
+ *    lists, the per-face winners and the statistics block, and nothing orders them -- the caller does, or uses a context
+ *    per stream.
  */
 #ifndef GEOGRASTER_H
 #define GEOGRASTER_H

@@ -37,8 +37,8 @@ int gr_louvain_communities(gr_ctx *ctx, const int32_t *edge_i, const int32_t *ed
  * starts, ends (n x 3 f64), community (n int32: a value outside [0, n_communities) names no community, as the -1 of
  * gr_louvain_communities), n <= GR_COMM_MAX_VERTICES, n_communities <= n.  points (n_communities x 3 f64), every word written: NaN
  * for a community of fewer than two segments.  One workgroup per community; the order of the sum is fixed (lane-strided pairs,
- * then a fixed tree), so two runs are bit-equal.  Returns with `stream` idle.  GR_EINVAL (the message names the call), before any
- * device work: null arrays, sizes outside their limits. */
+ * then a fixed tree), so two runs are bit-equal.  Synchronises `stream` behind its kernel: the scratch is free on return.
+ * GR_EINVAL (the message names the call), before any device work: null arrays, sizes outside their limits. */
 int gr_community_points(gr_ctx *ctx, const double *starts, const double *ends, const int32_t *community, int64_t n, int64_t n_communities,
                         double *points, void *stream);
 

@@ -28,9 +28,9 @@
  * face_out: height x width int32, every word written: the winning face, -1 where no face holds the centre.  z_out: height x width
  * float64, every word written: the winning height, NaN (0x7FF8000000000000) where face_out is -1; 8-byte aligned -- the call keeps
  * the keys in it between its passes.  stats: GR_NADIR_STAT_WORDS uint64, written by the call (N9).
- * The call returns with its last kernels enqueued on `stream`.  GR_EINVAL (the message names gr_nadir_raster), before any device
- * work: null arrays, negative sizes, V or F >= 2^31 - 1, a window outside the bounds above, small_cells or item_rows outside their
- * ranges. */
+ * Synchronises `stream` once, between its passes, to read two words back, and returns with its last kernels enqueued on it.
+ * GR_EINVAL (the message names gr_nadir_raster), before any device work: null arrays, negative sizes, V or F >= 2^31 - 1, a window
+ * outside the bounds above, small_cells or item_rows outside their ranges. */
 int gr_nadir_raster(gr_ctx *ctx, const int64_t *verts_q, const double *z, int64_t V, const int32_t *faces, int64_t F, int32_t col_off,
                     int32_t row_off, int32_t width, int32_t height, int32_t small_cells, int32_t item_rows, int32_t *face_out,
                     double *z_out, uint64_t *stats, void *stream);

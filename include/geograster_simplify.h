@@ -20,9 +20,10 @@
  * comes out empty (S6).
  * keep: n_ring_vertices uint8, 1 where the vertex is in the output.  kept_index: n_ring_vertices int32: the first M entries are
  * the kept vertices, ring after ring in input order, the others -1.  out_offsets: R + 1 int64, the output rings in kept_index; M =
- * out_offsets[R].  stats: GR_SIMPLIFY_STAT_WORDS uint64.  Every word of the four is written.  The call returns with the passes
- * done and the last kernels enqueued on `stream`.  GR_EINVAL (the message names gr_simplify_rings), before any device work: null
- * arrays, negative sizes, n_ring_vertices or R >= 2^31 - 1, T outside [0, 2^40). */
+ * out_offsets[R].  stats: GR_SIMPLIFY_STAT_WORDS uint64.  Every word of the four is written.
+ * Synchronises `stream` once per pass, to read one word back (S4), and returns with the passes done and the last kernels enqueued
+ * on it.  GR_EINVAL (the message names gr_simplify_rings), before any device work: null arrays, negative sizes, n_ring_vertices or
+ * R >= 2^31 - 1, T outside [0, 2^40). */
 int gr_simplify_rings(gr_ctx *ctx, const int64_t *ring_vertices, int64_t n_ring_vertices, const int64_t *ring_offsets, int64_t R,
                       const uint8_t *fixed, int64_t tol_steps, uint8_t *keep, int32_t *kept_index, int64_t *out_offsets,
                       uint64_t *stats, void *stream);

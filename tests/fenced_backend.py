@@ -113,8 +113,8 @@ class FencedHipRaster(HipRaster):
 
 @contextlib.contextmanager
 def fenced(backend):
-    """The calls of the body run on fresh records; on exit the device is waited for and every fence checked.  A body that
-    raises keeps its own error (the records are dropped)."""
+    """The calls of the body run on fresh records; on exit the device is waited for (a backend with a `wait_before_fence_check`
+    of its own waits that way instead) and every fence checked.  A body that raises keeps its own error (the records are dropped)."""
     fences = getattr(backend, "fences", backend)
     fences.forget()
     try:
@@ -122,6 +122,9 @@ def fenced(backend):
     except BaseException:
         fences.forget()
         raise
-    if fences.device.type == "cuda":
+    wait = getattr(backend, "wait_before_fence_check", None)   # tests/stream_probe.py: the stream of the body, the device may be held
+    if wait is not None:
+        wait()
+    elif fences.device.type == "cuda":
         torch.cuda.synchronize(fences.device)
     fences.check_fences()
