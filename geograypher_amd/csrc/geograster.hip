@@ -71,8 +71,8 @@ int read_stats(gr_ctx *c, hipStream_t s, CallStats &st) {
   return GR_OK;
 }
 
-void put_global_locked(const gr_ctx::Learned &v);
-void read_learned_file_locked(const char *path);
+void put_global_locked(const gr_ctx::Learned &v, bool may_evict = true);
+void read_learned_file_locked(const char *path, bool may_evict = true);
 
 bool parse_learned_line(const char *line, gr_ctx::Learned &v) {
   unsigned long long m; int T, cap, full, micro = 0;
@@ -85,8 +85,11 @@ bool parse_learned_line(const char *line, gr_ctx::Learned &v) {
 void save_learned_locked() {
   if (!g_learned_path[0]) return;
   // several processes (the ranks of one job) share the file: what the others wrote since this process read it is merged
-  // in before the rewrite (entry-wise maximum), so that no rank's lesson is lost to another's rename
-  read_learned_file_locked(g_learned_path);
+  // in before the rewrite (entry-wise maximum), so that no rank's lesson is lost to another's rename.  The file's lines take
+  // free slots only: once the ring is full, the entry the newest lesson replaced is still in the file, and put back it would
+  // replace the next entry, whose line would replace the one after it ... down the file, until the last line landed on the
+  // newest lesson itself and the file was written without it.  A lesson survives its own save.
+  read_learned_file_locked(g_learned_path, false);
   char tmp[1100];
   snprintf(tmp, sizeof(tmp), "%s.tmp.%d", g_learned_path, (int)getpid());
   FILE *f = fopen(tmp, "w");
@@ -99,19 +102,23 @@ void save_learned_locked() {
   if (rename(tmp, g_learned_path) != 0) (void)remove(tmp);
 }
 
-void read_learned_file_locked(const char *path) {   // a missing file is fine: it appears with the first overflow
+void read_learned_file_locked(const char *path, bool may_evict) {   // a missing file is fine: it appears with the first overflow
   FILE *f = fopen(path, "r");
   if (!f) return;
   char line[256];
   gr_ctx::Learned v;
   while (fgets(line, sizeof(line), f))
-    if (parse_learned_line(line, v)) put_global_locked(v);
+    if (parse_learned_line(line, v)) put_global_locked(v, may_evict);
   fclose(f);
 }
 
-void put_global_locked(const gr_ctx::Learned &v) {
+// may_evict = false: a new key takes a free slot or none (save_learned_locked)
+void put_global_locked(const gr_ctx::Learned &v, bool may_evict) {
   gr_ctx::Learned *e = find_learned(g_learned, std::min(g_n_learned, 64), v.mesh, v.T);
-  if (!e) { g_learned[g_n_learned % 64] = v; g_n_learned += 1; return; }
+  if (!e) {
+    if (!may_evict && g_n_learned >= 64) return;
+    g_learned[g_n_learned % 64] = v; g_n_learned += 1; return;
+  }
   e->cap = merge_cap(e->cap, v.cap);
   e->full = e->full || v.full;
   e->micro = e->micro || v.micro;

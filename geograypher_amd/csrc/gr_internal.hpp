@@ -249,7 +249,7 @@ struct gr_ctx {
                                        // form cannot hold --, per (mesh signature, tile count); [n_learned % 8] is replaced next
   int n_learned = 0;
   bool share_learned = true;           // consult / feed the process-wide table (off once GR_OPT_DIRECT_CAP was set by hand, on
-                                       // again with the next gr_mesh_upload)
+                                       // again only with GR_OPT_SHARE_LEARNED)
   uint64_t mesh_sig = 0;               // signature of the uploaded mesh: face count, vertex count, vertex bounds (gr_mesh_upload)
   // The binning configuration of the CURRENT raster call, resolved once at its top (resolve_binning): the process-wide table
   // can change under a running call (another context, another thread) -- sizing, allocation, the bin pass and the tile pass
