@@ -370,6 +370,42 @@ _NADIR_SIGNATURES = {
 NADIR_SYMBOLS = tuple(_NADIR_SIGNATURES)
 
 
+# ... and the two picture calls of include/geograster_vis.h, each of which takes ONE descriptor in host memory, the stream a field
+# of it (tests/test_vis_host.py compares the two mirrors with the header field by field).
+class ShadeArgs(ctypes.Structure):
+    """gr_shade_args"""
+    _fields_ = [
+        ("ids", _vp), ("depth", _vp), ("face_rgb", _vp), ("face_light", _vp), ("verts", _vp), ("faces", _vp), ("out", _vp),
+        ("stream", _vp),
+        ("F", ctypes.c_int64), ("V", ctypes.c_int64),
+        ("dir_x", ctypes.c_double), ("dir_y", ctypes.c_double), ("dir_z", ctypes.c_double), ("ambient", ctypes.c_double),
+        ("strength", ctypes.c_float),
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("supersample", ctypes.c_int32), ("radius", ctypes.c_int32),
+        ("bg_r", ctypes.c_int32), ("bg_g", ctypes.c_int32), ("bg_b", ctypes.c_int32),
+    ]
+
+
+class CompositeArgs(ctypes.Structure):
+    """gr_composite_args"""
+    _fields_ = [
+        ("photo", _vp), ("label", _vp), ("table", _vp), ("out", _vp), ("stream", _vp),
+        ("shift", ctypes.c_double), ("scale", ctypes.c_double), ("weight", ctypes.c_double),
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("table_rows", ctypes.c_int32), ("photo_dtype", ctypes.c_int32),
+        ("label_dtype", ctypes.c_int32), ("label_channels", ctypes.c_int32), ("discrete", ctypes.c_int32),
+        ("grey_overlay", ctypes.c_int32),
+    ]
+
+
+_VIS_SIGNATURES = {
+    "gr_shade_view": [_vp, ctypes.POINTER(ShadeArgs)],
+    "gr_composite_labels": [_vp, ctypes.POINTER(CompositeArgs)],
+}
+VIS_SYMBOLS = tuple(_VIS_SIGNATURES)
+SHADE_MAX_SUPERSAMPLE = 4     # V1: the ranges gr_shade_view takes
+SHADE_MAX_RADIUS = 16
+SHADE_MAX_SIDE = 32768
+
+
 def library_path() -> Path:
     return _LIB_PATH
 
@@ -391,7 +427,8 @@ def load_library() -> ctypes.CDLL:
     _torch()
     lib = ctypes.CDLL(str(_LIB_PATH))
     for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES, **_BURN_SIGNATURES,
-                           **_OVERLAP_SIGNATURES, **_COMMUNITIES_SIGNATURES, **_SIMPLIFY_SIGNATURES, **_NADIR_SIGNATURES}.items():
+                           **_OVERLAP_SIGNATURES, **_COMMUNITIES_SIGNATURES, **_SIMPLIFY_SIGNATURES, **_NADIR_SIGNATURES,
+                           **_VIS_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -990,6 +1027,79 @@ class NadirRasterizer:
                   face.data_ptr(), z.data_ptr(), stats.data_ptr(), hip._stream())
         hip._check_faces("gr_nadir_raster", stats, GR_NADIR_STAT_BAD_INDEX, self.V)
         return face, z, stats
+
+
+class PictureCalls:
+    """The two picture calls on one backend (include/geograster_vis.h), behind `HipRaster.face_light`,
+    `HipRaster.shade_view` and `HipRaster.composite_labels`, which document them.  Every output is allocated through the backend
+    (`_empty`), every input goes through `_shaped`."""
+
+    def __init__(self, backend: "HipRaster"):
+        self.backend = backend
+
+    def face_light(self, verts, faces, view_dir, ambient: float = 0.3):
+        torch = _torch()
+        hip = self.backend
+        v = hip._shaped(verts, torch.float32, ("V", 3), "vertices")
+        f = hip._shaped(faces, torch.int32, ("F", 3), "faces")
+        d = [float(x) for x in np.asarray(view_dir, dtype=np.float64).reshape(3)]
+        light = hip._empty((int(f.shape[0]),), torch.uint8)
+        if f.shape[0]:
+            args = ShadeArgs(face_light=light.data_ptr(), verts=_ptr(v if v.shape[0] else None), faces=f.data_ptr(),
+                             stream=hip._stream().value, F=int(f.shape[0]), V=int(v.shape[0]), dir_x=d[0], dir_y=d[1], dir_z=d[2],
+                             ambient=float(ambient))
+            hip._call("gr_shade_view", ctypes.byref(args))
+        return light
+
+    def shade_view(self, ids, depth, face_rgb, face_light, supersample: int = 1, radius: Optional[int] = None, strength: float = 0.0,
+                   background=(255, 255, 255)):
+        torch = _torch()
+        hip = self.backend
+        s = int(supersample)
+        if not 1 <= s <= SHADE_MAX_SUPERSAMPLE:
+            raise ValueError(f"gr_shade_view: supersample={supersample} outside [1, {SHADE_MAX_SUPERSAMPLE}]")
+        ids_t = hip._shaped(ids, torch.int32, ("Hs", "Ws"), "ids")
+        depth_t = hip._shaped(depth, torch.float32, tuple(ids_t.shape), "depth (as ids)")
+        if ids_t.shape[0] % s or ids_t.shape[1] % s or not ids_t.numel():
+            raise ValueError(f"gr_shade_view: planes of {tuple(ids_t.shape)} samples are no picture at supersample={s}")
+        rgb = hip._shaped(face_rgb, torch.uint8, ("F", 3), "face_rgb")
+        light = hip._shaped(face_light, torch.uint8, (int(rgb.shape[0]),), "face_light (one per face)")
+        H, W, F = int(ids_t.shape[0]) // s, int(ids_t.shape[1]) // s, int(rgb.shape[0])
+        out = hip._empty((H, W, 3), torch.uint8)
+        bg = [int(x) for x in background]
+        args = ShadeArgs(ids=ids_t.data_ptr(), depth=depth_t.data_ptr(), face_rgb=_ptr(rgb if F else None),
+                         face_light=_ptr(light if F else None), out=out.data_ptr(), stream=hip._stream().value, F=F, strength=float(strength),
+                         width=W, height=H, supersample=s, radius=s if radius is None else int(radius), bg_r=bg[0], bg_g=bg[1],
+                         bg_b=bg[2])
+        hip._call("gr_shade_view", ctypes.byref(args))
+        return out
+
+    def composite_labels(self, photo, label, table=None, discrete: bool = False, shift: float = 0.0, scale: float = 1.0,
+                         weight: float = 0.5, grey_overlay: bool = True):
+        torch = _torch()
+        hip = self.backend
+
+        def kind(a):
+            return torch.uint8 if str(a.dtype).endswith("uint8") else torch.float64
+
+        photo_t = hip._shaped(photo, kind(photo), ("h", "w", 3), "photo")
+        h, w = int(photo_t.shape[0]), int(photo_t.shape[1])
+        channels = 3 if len(label.shape) == 3 else 1
+        label_t = hip._shaped(label, kind(label), (h, w, 3) if channels == 3 else (h, w), "label (as the photo)")
+        if channels == 3 and label_t.dtype == torch.uint8 and discrete:
+            raise ValueError("gr_composite_labels: a uint8 colour label with discrete classes is not supported")
+        if not h * w:
+            raise ValueError(f"gr_composite_labels: an empty image {h} x {w}")
+        table_t = None if channels == 3 else hip._shaped(table, torch.float64, ("N", 3), "colour table")
+        out = hip._empty((h, 3 * w, 3), torch.uint8)
+        args = CompositeArgs(photo=photo_t.data_ptr(), label=label_t.data_ptr(), table=_ptr(table_t), out=out.data_ptr(),
+                             stream=hip._stream().value, shift=float(shift), scale=float(scale), weight=float(weight), width=w, height=h,
+                             table_rows=0 if table_t is None else int(table_t.shape[0]),
+                             photo_dtype=GR_DTYPE_U8 if photo_t.dtype == torch.uint8 else GR_DTYPE_F64,
+                             label_dtype=GR_DTYPE_U8 if label_t.dtype == torch.uint8 else GR_DTYPE_F64, label_channels=channels,
+                             discrete=int(bool(discrete)), grey_overlay=int(bool(grey_overlay)))
+        hip._call("gr_composite_labels", ctypes.byref(args))
+        return out
 
 
 class RayCommunities:
@@ -2132,6 +2242,28 @@ class HipRaster:
         validated on the host (`check_nadir_tables`: ValueError naming gr_nadir_raster) and uploaded once; every
         `.window(col_off, row_off, width, height, small_cells=0, item_rows=0)` call rasters one window."""
         return NadirRasterizer(self, verts_q, z, faces)
+
+    # -- pictures (include/geograster_vis.h; DESIGN.md 8s, V1-V12) --------------------------------------------------------
+    def face_light(self, verts, faces, view_dir, ambient: float = 0.3):
+        """The two-sided headlight per face (V3): verts (V, 3) float32, faces (F, 3) int32, view_dir a unit vector in the
+        vertices' frame -> (F,) uint8 tensor, floor((ambient + (1 - ambient) |n.d| / |n|) 255 + 0.5); 255 for a face without area."""
+        return PictureCalls(self).face_light(verts, faces, view_dir, ambient)
+
+    def shade_view(self, ids, depth, face_rgb, face_light, supersample: int = 1, radius: Optional[int] = None, strength: float = 0.0,
+                   background=(255, 255, 255)):
+        """One shaded, anti-aliased picture (V4-V7): ids (H s, W s) int32 and depth (H s, W s) float32 as `raster_face_ids(...,
+        want_depth=True)` gives them for one view, face_rgb (F, 3) uint8, face_light (F,) uint8, s = supersample in 1 .. 4, the
+        neighbour radius in samples (default: s), the occlusion strength (0: none) -> (H, W, 3) uint8 tensor.  ValueError
+        for planes whose sides are no multiple of s, and for what the library refuses."""
+        return PictureCalls(self).shade_view(ids, depth, face_rgb, face_light, supersample, radius, strength, background)
+
+    def composite_labels(self, photo, label, table=None, discrete: bool = False, shift: float = 0.0, scale: float = 1.0,
+                         weight: float = 0.5, grey_overlay: bool = True):
+        """The three-panel composite (V8-V12): photo (h, w, 3) uint8 or float64, label (h, w) or (h, w, 3) uint8 or float64 (other
+        dtypes become float64), table (N, 3) float64 for a one-channel label -> (h, 3 w, 3) uint8 tensor [label colours | photo |
+        overlay].  `shift` and `scale` are the two scalars of a continuous label (`utils.visualization.create_composite` computes
+        them).  ValueError for a uint8 colour label with discrete classes, and for shapes that do not fit."""
+        return PictureCalls(self).composite_labels(photo, label, table, discrete, shift, scale, weight, grey_overlay)
 
     # -- projection / aggregation --------------------------------------------------------------------------------
     def new_vote_buffers(self, C: int):

@@ -268,6 +268,25 @@ class PhotogrammetryCamera:
         view_angle = np.rad2deg(2 * np.arctan((self.image_height / 2) / self.f))
         return {"position": position, "focal_point": focal_point, "up": up, "view_angle": view_angle}
 
+    def get_vis_mesh(self, frustum_scale: float = 0.1):
+        """This camera as a frustum (reference: cameras.py:479-553): -> (points (5, 3) float64 in the chunk-local frame: the
+        centre and the four corners of the image plane at distance `frustum_scale`; faces (6, 3) int64: four sides and the two
+        triangles of the end cap; face_rgb (6, 3) uint8: blue, the side at the image's top (-Y) red) in place of the
+        reference's pv.PolyData."""
+        halfwidth, halfheight = self.image_width / (self.f * 2), self.image_height / (self.f * 2)
+        scaled_cx, scaled_cy = self.cx / self.f, self.cy / self.f
+        right, left = scaled_cx + halfwidth, scaled_cx - halfwidth
+        top, bottom = scaled_cy + halfheight, scaled_cy - halfheight
+        vertices = np.array([[0, 0, 0], [right, top, 1], [right, bottom, 1], [left, bottom, 1], [left, top, 1]],
+                            dtype=np.float64).T * frustum_scale
+        transform = np.asarray(self.cam_to_world_transform, dtype=np.float64)
+        projected = transform @ np.vstack((vertices, np.ones((1, 5))))
+        if transform[3, 3] != 1.0:
+            projected = projected / transform[3, 3]
+        faces = np.array([[0, 1, 2], [0, 2, 3], [0, 3, 4], [0, 4, 1], [1, 2, 3], [3, 4, 1]], dtype=np.int64)
+        face_rgb = np.array([[0, 0, 255], [255, 0, 0], [0, 0, 255], [0, 0, 255], [0, 0, 255], [0, 0, 255]], dtype=np.uint8)
+        return np.ascontiguousarray(projected[:3].T), faces, face_rgb
+
     def get_raster_record(
         self, image_scale: float = 1.0, near: float = 1e-3, principal_point: str = "center", origin=None,
         focal_scaling: str = "scaled",
@@ -565,6 +584,23 @@ class PhotogrammetryCameraSet:
                     logging.warning(f"Could not find {src_file}")
             else:
                 os.symlink(src_file, output_file)
+
+    def get_vis_mesh(self, frustum_scale: Optional[float] = 2, correct_for_scale: bool = True):
+        """The frusta of all cameras as one mesh in the chunk-local frame: (points (5 N, 3), faces (6 N, 3) int64, face_rgb
+        (6 N, 3) uint8), `PhotogrammetryCamera.get_vis_mesh` per camera.  `correct_for_scale`: `frustum_scale` is in world units
+        and divided by the cube root of the determinant of local_to_epsg_4978's upper-left 3 x 3, as the reference's mesh.vis
+        does (meshes.py:2212-2220).  frustum_scale None: the camera's own default, 0.1 local units."""
+        transform = self.get_local_to_epsg_4978_transform()
+        if frustum_scale is None:
+            frustum_scale = 0.1
+        elif correct_for_scale and transform is not None:
+            frustum_scale = frustum_scale / np.cbrt(np.linalg.det(np.asarray(transform, dtype=np.float64)[:3, :3]))
+        parts = [camera.get_vis_mesh(frustum_scale) for camera in self.cameras]
+        if not parts:
+            return np.zeros((0, 3)), np.zeros((0, 3), dtype=np.int64), np.zeros((0, 3), dtype=np.uint8)
+        points = np.concatenate([p for p, _, _ in parts])
+        faces = np.concatenate([f + 5 * k for k, (_, f, _) in enumerate(parts)])
+        return points, faces, np.concatenate([c for _, _, c in parts])
 
     def get_raster_records(
         self, image_scale: float = 1.0, near: Union[float, List[float]] = 1e-3, principal_point: str = "center",

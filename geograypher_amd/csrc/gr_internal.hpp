@@ -49,6 +49,9 @@
 //                    N3, the clipped box of centres, the cells of the small faces, the list of the larger ones; k_nadir_items<0, 1>, a wave per
 //                    item of a listed face -- a 64-bit atomicMax of the height's key, then an atomicMin of the face index where the key is the
 //                    cell's maximum; k_nadir_finish decodes the keys in place; exact integer membership, float64 heights; no mesh needed
+//   vis.hip          the pictures (gr_shade_view, gr_composite_labels): k_face_light, a lane per face; k_shade, a workgroup per 16 x 16 output pixels
+//                    with the depth window and its halo in LDS, float32; k_composite, a workgroup per 1024 pixels of a row, byte strips through
+//                    LDS by 16-byte words, float64; one host descriptor a call, no mesh, no scratch, no read-back
 //   cub_steps.hpp    the hipcub calls of the stage calls, each declared once against the call's Plan: SortPairs, SortKeys, ExclusiveSum,
 //                    InclusiveMax, RunLengthEncode, ReduceByKey (size query on construction, typed pointers on run)
 //   compact_dev.hpp  FlagScan, compact_begin, compact_write, k_submesh_write: the scans and the write kernel of polygons.hip's sub-mesh and of decimate.hip;

@@ -10,7 +10,8 @@ face values (`aggregate_projected_images`) and the class per face (`argmax_nonze
 (`label_ground_class`); with `top_down_vector_projection_savefile` and `top_down_points_file` the classes are then written as a
 top-down vector map, one multipolygon per class (`export_face_labels_vector`, traced on the device).  With `mesh_downsample` and
 `mesh_downsample_method="cluster"` the mesh is decimated by vertex clustering behind the crop (`TexturedPhotogrammetryMesh.decimate`,
-on the device).  Not carried over: the reference's quadric decimation and the visualisations."""
+on the device).  With `vis_folder` the two pictures the reference shows in a window are written as PNGs, rendered off-screen on the
+device (`TexturedPhotogrammetryMesh.vis`).  Not carried over: the reference's quadric decimation and `vis=True` (there is no window)."""
 import argparse
 import json
 import math
@@ -60,6 +61,7 @@ def aggregate_images(
     top_down_simplify_method: typing.Union[str, None] = None,
     top_down_raster_projection_savefile: typing.Union[PATH_TYPE, None] = None,
     top_down_raster_resolution: typing.Union[float, None] = None,
+    vis_folder: typing.Union[PATH_TYPE, None] = None,
 ):
     """Aggregate the labels under `label_folder` onto the mesh (see the module docstring).  The reference's arguments and defaults;
     `mesh_downsample != 1` without `mesh_downsample_method`, `vis`, `ROI` without `ROI_points_file`, `DTM_file` without `DTM_points_file` and
@@ -199,6 +201,8 @@ def aggregate_images(
 
     if mesh.get_IDs_to_labels() is None:
         raise ValueError("aggregate_images needs IDs_to_labels: the number of classes is its largest ID + 1")
+    if vis_folder is not None:   # the picture the reference shows at aggregate_images.py:163: the mesh and the cameras in use
+        mesh.vis(camera_set=camera_set, screenshot_filename=Path(vis_folder, "mesh_and_cameras.png"))
     segmentor = LookUpSegmentor(base_folder=image_folder, lookup_folder=label_folder,
                                 num_classes=int(np.max(list(mesh.get_IDs_to_labels().keys()))) + 1)
     segmentor_camera_set = SegmentorPhotogrammetryCameraSet(camera_set, segmentor=segmentor)
@@ -227,6 +231,9 @@ def aggregate_images(
     if predicted_face_classes_savefile is not None:
         Path(predicted_face_classes_savefile).parent.mkdir(parents=True, exist_ok=True)
         np.save(predicted_face_classes_savefile, predicted_face_classes)
+
+    if vis_folder is not None:   # ... and the one at aggregate_images.py:214: the class per face, behind the ground step
+        mesh.vis(screenshot_filename=Path(vis_folder, "predicted_classes.png"), vis_scalars=predicted_face_classes)
 
     if top_down_vector_projection_savefile is not None:   # reference: aggregate_images.py:216-231, behind the ground step
         points_in_export_CRS = top_down_points
@@ -302,6 +309,9 @@ def parse_args(argv=None):
     parser.add_argument("--top-down-raster-resolution", type=float,
                         help="Cell size of --top-down-raster-projection-savefile in map units")
     parser.add_argument("--vis", action="store_true", help="Not available here")
+    parser.add_argument("--vis-folder", type=Path,
+                        help="Write mesh_and_cameras.png and predicted_classes.png (each with its .legend.json) here: the two pictures "
+                             "the reference shows in a window, rendered off-screen on the device")
     args = parser.parse_args(argv)
     args.IDs_to_labels = str(args.IDs_to_labels)
     return args

@@ -1935,6 +1935,37 @@ class TexturedPhotogrammetryMesh:
         else:
             self.logger.warning("non-discrete texture, not saving classes")
 
+    def vis(self, camera_set=None, screenshot_filename: typing.Optional[PATH_TYPE] = None, vis_scalars=None,
+            IDs_to_labels: typing.Union[None, dict] = None, frustum_scale: float = 2, enable_ssao: bool = True, *, view=None,
+            window_size=(1024, 768), supersample: int = 2, return_image: bool = False, mesh_kwargs=None, **ignored):
+        """A picture of the mesh and the cameras (reference: meshes.py:2087-2246) without VTK: the scene is rastered by the
+        projection path at window_size x supersample and shaded on the device (`gr_shade_view`) -- flat colours
+        under a two-sided headlight, darkened where neighbouring samples are closer (`enable_ssao`), averaged to the window.
+
+        camera_set: drawn as frusta of `frustum_scale` world units, the image's top side red (`get_vis_mesh`).  vis_scalars: per
+        face or per vertex (default: the mesh's texture); one column with `IDs_to_labels` (default: the mesh's) whose largest ID
+        is below 20 takes tab10 / tab20 by class, any other single column viridis over [nanmin, nanmax], several columns are RGB
+        (bytes where the maximum exceeds 1), NaN is (169, 169, 169); the background is white.  No scalar bar is drawn: the
+        legend {label: [r, g, b]} is written beside the picture as `<name>.legend.json`.
+        view: None -- from the south-west (azimuth 225 degrees, clockwise from north) at 35.264 degrees elevation, 30 degrees
+        vertical view angle, the whole scene in the window; a dict with any of azimuth_deg, elevation_deg, view_angle_deg; or a
+        `PhotogrammetryCamera`, whose view the picture then is.  The frame is east-north-up at the centre of the mesh's bounds
+        (`meshes.vis.picture_frame`).  -> the (H, W, 3) uint8 picture with `return_image`, else None; without a
+        `screenshot_filename` and without `return_image` NotImplementedError: there is no window.  `plotter`, `interactive`,
+        `interactive_jupyter`, `plotter_kwargs` and `force_xvfb` are accepted and ignored, any other keyword is a TypeError.
+        The scene (mesh and frusta) is uploaded as one mesh; the mesh the device held before is uploaded again afterwards."""
+        from geograypher_amd.meshes import vis as _vis
+
+        unknown = sorted(set(ignored) - set(_vis.IGNORED))
+        if unknown:
+            raise TypeError(f"vis() got unexpected keyword arguments {unknown}")
+        if ignored:
+            self.logger.info(f"vis: {sorted(ignored)} are ignored -- there is no plotter and no window, the picture is rendered "
+                             "off-screen on the device")
+        return _vis.render(self, camera_set=camera_set, screenshot_filename=screenshot_filename, vis_scalars=vis_scalars,
+                           IDs_to_labels=IDs_to_labels, frustum_scale=frustum_scale, enable_ssao=enable_ssao, view=view,
+                           window_size=window_size, supersample=supersample, return_image=return_image, mesh_kwargs=mesh_kwargs)
+
     @staticmethod
     def _resize_map(src_hw, dst_hw):
         """(2, H, W) sampling map of skimage.transform.resize: destination pixel centres mapped into the source grid,
@@ -1968,7 +1999,10 @@ class TexturedPhotogrammetryMesh:
         leaves the GPU as 12 MB instead of the reference's 96 MB float64 image; the optional native-resolution
         upsampling (nearest for discrete textures, bilinear otherwise) is the warp kernel with a resize map.
         Like the reference this renders with `distortion_set=camera_set` (a camera set without a distortion model
-        needs `apply_distortion=False`).  `make_composites` (matplotlib visualisation) is outside the projection path.
+        needs `apply_distortion=False`).  With `make_composites` every file is the three-panel composite [label colours | photo
+        | overlay] of `utils.visualization.create_composite` as a 3-channel image (meshes.py:2336-2344): the photo is
+        `camera.get_image` at the render's scale (1.0 with `save_native_resolution`), the label image stays on the device and the
+        composite kernel is the only extra device work of a view.
 
         Extra keywords (not forwarded to pix2face): `writer_threads` (default min(16, cores)) host threads that deflate
         and write while the GPU renders the next views -- results travel through a ring of pinned buffers, one
@@ -1980,8 +2014,6 @@ class TexturedPhotogrammetryMesh:
 
         from geograypher_amd.utils.tiff import write_tiff_deflate
 
-        if make_composites:
-            raise NotImplementedError("composite visualisations are outside the projection path (utils/visualization.py)")
         torch = _torch()
         writer_threads = int(render_kwargs.pop("writer_threads", min(16, __import__("os").cpu_count() or 1)))
         views_per_group = int(render_kwargs.pop("views_per_group", 8))
@@ -2022,7 +2054,7 @@ class TexturedPhotogrammetryMesh:
             if event is not None:
                 event.synchronize()
             rendered = host.numpy() if hasattr(host, "numpy") else host
-            if rendered.dtype != np.uint8 and cast_to_uint8:
+            if rendered.dtype != np.uint8 and cast_to_uint8 and not make_composites:
                 rendered = rendered.copy()
                 mask = np.logical_or.reduce([rendered < 0, rendered > 255, np.logical_not(np.isfinite(rendered))])
                 rendered[mask] = uint8_value_for_null_texture
@@ -2034,7 +2066,7 @@ class TexturedPhotogrammetryMesh:
             if save_as_npy is True:
                 np.save(str(output_filename.with_suffix(".npy")), rendered)
             else:
-                if cast_to_uint8 is False:
+                if cast_to_uint8 is False and not make_composites:
                     with np.errstate(invalid="ignore"):
                         if np.nanmax(rendered) <= np.iinfo(np.uint16).max:
                             rendered = rendered.astype(np.uint16)
@@ -2083,6 +2115,15 @@ class TexturedPhotogrammetryMesh:
                         if native:
                             rendered = self.backend.warp_image(rendered, resize_maps[key], order=0 if discrete else 1,
                                                                fill_value=float("nan"))
+                    if make_composites:
+                        from geograypher_amd.utils.visualization import create_composite
+
+                        photo = camera.get_image(image_scale=(1.0 if save_native_resolution else render_image_scale),
+                                                 backend=self.backend)
+                        photo = photo[..., :3] if photo.ndim == 3 else photo
+                        label = rendered if isinstance(rendered, torch.Tensor) else torch.as_tensor(np.asarray(rendered))
+                        label = label[..., 0] if label.ndim == 3 and label.shape[-1] == 1 else label
+                        rendered = create_composite(photo, label, IDs_to_labels=self.get_IDs_to_labels(), backend=self.backend)
                     frame_bytes = rendered.numel() * rendered.element_size() if hasattr(rendered, "numel") else rendered.nbytes
                     slots_now = max(2, min(ring_slots, ring_budget // max(frame_bytes, 1)))
                     slot = i % slots_now

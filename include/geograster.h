@@ -861,6 +861,10 @@ enum {
 };
 #include "geograster_nadir.h"
 
+/* Pictures (geograster_vis.h): a shaded view from an id and a depth plane, the three-panel composite
+ * of a photo and a label image.  Both calls take one descriptor, declared there. */
+#include "geograster_vis.h"
+
 #ifdef __cplusplus
 }
 #endif
