@@ -216,6 +216,17 @@ GR_NADIR_STAT_INSIDE = 7
 GR_NADIR_STAT_SKIPPED = 8
 GR_NADIR_STAT_COVERED = 9
 GR_NADIR_STAT_WORDS = 10
+# the raster -> raster warp of include/geograster_warp.h (gr_warp_raster)
+GR_WARP_NEAREST = 0
+GR_WARP_BILINEAR = 1
+GR_WARP_STAT_CELLS = 0
+GR_WARP_STAT_OUTSIDE = 1
+GR_WARP_STAT_NONFINITE = 2
+GR_WARP_STAT_BEYOND = 3
+GR_WARP_STAT_NODATA = 4
+GR_WARP_STAT_DEN_ZERO = 5
+GR_WARP_STAT_WORDS = 8
+GR_WARP_MAX_BANDS = 16
 
 
 class StageTimes(ctypes.Structure):
@@ -406,6 +417,29 @@ SHADE_MAX_RADIUS = 16
 SHADE_MAX_SIDE = 32768
 
 
+# ... and the raster -> raster call of include/geograster_warp.h, under the same rule: ONE descriptor in host memory, the stream a field
+# of it (tests/test_raster_warp_host.py compares the mirror with the header field by field).
+class WarpRasterArgs(ctypes.Structure):
+    """gr_warp_raster_args"""
+    _fields_ = [
+        ("data", _vp), ("out", _vp), ("stats", _vp), ("stream", _vp), ("src_inverse6_h", _vp), ("dst_transform6_h", _vp),
+        ("src_crs_h", _vp), ("dst_crs_h", _vp),
+        ("src_nodata", ctypes.c_double), ("dst_nodata", ctypes.c_double),
+        ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("src_dtype", ctypes.c_int32), ("dst_dtype", ctypes.c_int32),
+        ("has_src_nodata", ctypes.c_int32), ("col_off", ctypes.c_int32), ("row_off", ctypes.c_int32), ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32), ("resampling", ctypes.c_int32), ("same_crs", ctypes.c_int32),
+    ]
+
+
+_WARP_SIGNATURES = {
+    "gr_warp_raster": [_vp, ctypes.POINTER(WarpRasterArgs)],
+}
+WARP_SYMBOLS = tuple(_WARP_SIGNATURES)
+WARP_SIDE_LIMIT = 1 << 23     # W1: H, W of the source stay below it
+WARP_RESAMPLING = {"nearest": GR_WARP_NEAREST, "bilinear": GR_WARP_BILINEAR}
+WARP_STAT_NAMES = ("cells", "outside", "nonfinite", "beyond", "nodata", "den_zero")
+
+
 def library_path() -> Path:
     return _LIB_PATH
 
@@ -428,7 +462,7 @@ def load_library() -> ctypes.CDLL:
     lib = ctypes.CDLL(str(_LIB_PATH))
     for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES, **_BURN_SIGNATURES,
                            **_OVERLAP_SIGNATURES, **_COMMUNITIES_SIGNATURES, **_SIMPLIFY_SIGNATURES, **_NADIR_SIGNATURES,
-                           **_VIS_SIGNATURES}.items():
+                           **_VIS_SIGNATURES, **_WARP_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -995,6 +1029,49 @@ def check_nadir_window(col_off: int, row_off: int, width: int, height: int, smal
         raise ValueError(f"{name}: item_rows={item_rows} outside [0, {NADIR_ITEM_ROWS_MAX}]")
 
 
+WARP_DTYPES = {"uint8": GR_DTYPE_U8, "float32": GR_DTYPE_F32, "float64": GR_DTYPE_F64}   # numpy / torch dtype name -> GR_DTYPE_*
+
+
+def warp_numpy_dtype(dtype) -> np.dtype:
+    """A numpy or torch dtype, or its name -> the numpy dtype, one of uint8, float32, float64 (W1); anything else: ValueError
+    naming gr_warp_raster."""
+    try:
+        name = np.dtype(dtype).name
+    except TypeError:
+        name = str(dtype).replace("torch.", "")
+    if name not in WARP_DTYPES:
+        raise ValueError(f"gr_warp_raster: dtype {dtype} is not one of uint8, float32, float64")
+    return np.dtype(name)
+
+
+def warp_dst_nodata(dst_nodata, src_nodata, dst_dtype) -> float:
+    """W1: the destination's nodata value: `dst_nodata`, else the source's, else NaN for a float destination and 0 for uint8.
+    A uint8 destination needs an integer in [0, 255]: ValueError naming gr_warp_raster."""
+    value = dst_nodata if dst_nodata is not None else src_nodata
+    if value is None:
+        value = 0.0 if np.dtype(dst_dtype) == np.uint8 else float("nan")
+    value = float(value)
+    if np.dtype(dst_dtype) == np.uint8 and not (0 <= value <= 255 and value == int(value)):
+        raise ValueError(f"gr_warp_raster: dst_nodata={value!r} does not fit the uint8 destination (an integer in [0, 255])")
+    return value
+
+
+def check_warp_window(src_shape, col_off: int, row_off: int, width: int, height: int, dst_dtype=None):
+    """W1: the source is (B, H, W) with 1 <= B <= GR_WARP_MAX_BANDS and 1 <= H, W < 2^23, the destination window inside B1's
+    bounds and of at most 2^31 - 1 (row, 256 column) strips -- ValueError naming gr_warp_raster."""
+    name = "gr_warp_raster"
+    if len(src_shape) != 3:
+        raise ValueError(f"{name}: the source must be (B, H, W) or (H, W), got {tuple(src_shape)}")
+    B, H, W = (int(k) for k in src_shape)
+    if not (1 <= B <= GR_WARP_MAX_BANDS and 1 <= H < WARP_SIDE_LIMIT and 1 <= W < WARP_SIDE_LIMIT):
+        raise ValueError(f"{name}: a source of {B} x {H} x {W} is outside 1 <= B <= {GR_WARP_MAX_BANDS}, 1 <= H, W < 2^23")
+    _check_window(name, int(col_off), int(row_off), int(width), int(height))
+    if -(-int(width) // 256) * int(height) > 2 ** 31 - 1:
+        raise ValueError(f"{name}: a window of {width} x {height} cells is too large for one call")
+    if dst_dtype is not None:
+        warp_numpy_dtype(dst_dtype)
+
+
 class NadirRasterizer:
     """One mesh on the device -- vertices in cell units of a parent grid, their heights, the faces --, rastered from above into any
     number of windows of that grid (gr_nadir_raster).  Made by `HipRaster.nadir_rasterizer`, which checks
@@ -1100,6 +1177,63 @@ class PictureCalls:
                              discrete=int(bool(discrete)), grey_overlay=int(bool(grey_overlay)))
         hip._call("gr_composite_labels", ctypes.byref(args))
         return out
+
+
+class RasterWarper:
+    """The raster -> raster call on one backend (include/geograster_warp.h), behind `HipRaster.warp_raster`,
+    which documents it.  Every output is allocated through the backend (`_empty`, `_stats`), the source goes through `_dev`."""
+
+    def __init__(self, backend: "HipRaster"):
+        self.backend = backend
+
+    def warp(self, data, src_inverse, src_nodata, dst_transform, window, src_crs, dst_crs, resampling, dst_nodata, dst_dtype, out):
+        from geograypher_amd.utils.geospatial import KIND_ECEF, crs_tuple
+
+        torch = _torch()
+        hip = self.backend
+        if resampling not in WARP_RESAMPLING:
+            raise ValueError(f"gr_warp_raster: resampling={resampling!r} is neither 'nearest' nor 'bilinear'")
+        name = str(data.dtype).replace("torch.", "")
+        d_t = hip._dev(data, getattr(torch, name if name in WARP_DTYPES else "float64"))
+        if d_t.ndim == 2:
+            d_t = d_t[None]
+        src_name = str(d_t.dtype).replace("torch.", "")
+        dst_np = np.dtype(src_name) if dst_dtype is None else warp_numpy_dtype(dst_dtype)
+        col_off, row_off, width, height = (int(k) for k in window)
+        check_warp_window(tuple(d_t.shape), col_off, row_off, width, height, dst_np)
+        B, H, W = (int(k) for k in d_t.shape)
+        nd = warp_dst_nodata(dst_nodata, src_nodata, dst_np)
+        coeffs = []
+        for what, six in (("src_inverse", src_inverse), ("dst_transform", dst_transform)):
+            six = [float(k) for k in np.asarray(six, dtype=np.float64).reshape(-1)]
+            if len(six) != 6 or not np.all(np.isfinite(six)):
+                raise ValueError(f"gr_warp_raster: {what} has six finite coefficients, got {six}")
+            coeffs.append((ctypes.c_double * 6)(*six))
+        if (src_crs is None) != (dst_crs is None):
+            raise ValueError("gr_warp_raster: src_crs and dst_crs are given together or not at all")
+        sides = None
+        if src_crs is not None:
+            sides = [Crs(int(k), float(lon0), float(k0), float(fe), float(fn)) for k, lon0, k0, fe, fn in
+                     (crs_tuple(src_crs), crs_tuple(dst_crs))]
+            if KIND_ECEF in (sides[0].kind, sides[1].kind):
+                raise ValueError("gr_warp_raster: an ECEF side: a raster is planar or geographic")
+        dst_torch = getattr(torch, dst_np.name)
+        if out is None:
+            out = hip._empty((B, height, width), dst_torch)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != dst_torch or tuple(out.shape) != (B, height, width)
+              or not out.is_contiguous() or out.device != d_t.device):
+            raise ValueError(f"out must be a contiguous {dst_np.name} ({B}, {height}, {width}) tensor on {d_t.device}")
+        stats = hip._stats(GR_WARP_STAT_WORDS)
+        args = WarpRasterArgs(data=d_t.data_ptr(), out=out.data_ptr(), stats=stats.data_ptr(), stream=hip._stream().value,
+                              src_inverse6_h=ctypes.addressof(coeffs[0]), dst_transform6_h=ctypes.addressof(coeffs[1]),
+                              src_crs_h=None if sides is None else ctypes.addressof(sides[0]),
+                              dst_crs_h=None if sides is None else ctypes.addressof(sides[1]),
+                              src_nodata=0.0 if src_nodata is None else float(src_nodata), dst_nodata=nd, B=B, H=H, W=W,
+                              src_dtype=WARP_DTYPES[src_name], dst_dtype=WARP_DTYPES[dst_np.name],
+                              has_src_nodata=0 if src_nodata is None else 1, col_off=col_off, row_off=row_off, width=width,
+                              height=height, resampling=WARP_RESAMPLING[resampling], same_crs=1 if sides is None else 0)
+        hip._call("gr_warp_raster", ctypes.byref(args))
+        return out, stats
 
 
 class RayCommunities:
@@ -2155,6 +2289,21 @@ class HipRaster:
             if check and f_t is not None:
                 self._check_faces("gr_reproject_points", stats, GR_CRS_STAT_BAD_FACES, V)
         return out, stats
+
+    # -- raster -> raster: a window of a destination grid resampled from a source raster (include/geograster_warp.h) --
+    def warp_raster(self, data, src_inverse, src_nodata, dst_transform, window, *, src_crs=None, dst_crs=None,
+                    resampling: str = "nearest", dst_nodata=None, dst_dtype=None, out=None):
+        """gr_warp_raster (W1-W9): data (B, H, W) or (H, W), uint8, float32 or float64 (anything else is converted to float64),
+        numpy or a device tensor; src_inverse: the six coefficients of the source's INVERSE transform (`PlanarRaster.inverse`);
+        src_nodata a float or None; dst_transform: the six coefficients of the destination's parent grid; window (col_off, row_off,
+        width, height) of it -> (out (B, height, width) device tensor of `dst_dtype` (default: the source's), stats
+        (GR_WARP_STAT_WORDS,) int64 tensor).  src_crs, dst_crs: what `utils.geospatial.WGS84CRS.parse` takes, given together for a
+        cross-CRS warp (geographic grids are lon, lat: x is the longitude) or both None where the grids share a CRS.  resampling
+        "nearest" or "bilinear" (four taps, nodata taps left out and the rest renormalised).  dst_nodata: what a cell without a
+        sample becomes (default: src_nodata, else NaN, 0 for uint8).  out: a contiguous device tensor of the result's shape and
+        dtype to write.  Only enqueues."""
+        return RasterWarper(self).warp(data, src_inverse, src_nodata, dst_transform, window, src_crs, dst_crs, resampling, dst_nodata,
+                                       dst_dtype, out)
 
     # -- the orthomosaic baseline: tile assembly, zonal class counts ----------------------------------------------------
     def assemble_tiles(self, preds, pred_offsets, windows, tile_table, weights, weight_offsets, count_dtype, bin_table,

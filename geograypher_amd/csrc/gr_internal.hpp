@@ -24,8 +24,8 @@
 //   terrain.hip      raster samples: the value of a raster under every face centre or vertex, height above it, ground relabel (k_sample_raster); no mesh needed
 //   select.hip       image selection: greedy set cover over a face x view incidence (k_sc_rows, k_sc_scan, k_sc_scatter, k_sc_pick, k_sc_apply,
 //                    k_sc_prune_test, k_sc_prune_apply); no mesh needed
-//   crs.hip          CRS reprojection: points between WGS84 ECEF, geographic and transverse Mercator coordinates (k_reproject_points; constants:
-//                    crs_constants.hpp, written by tools/make_crs_constants.py); no mesh needed
+//   crs.hip          CRS reprojection: points between WGS84 ECEF, geographic and transverse Mercator coordinates (k_reproject_points; the conversion
+//                    of one point is crs_dev.hpp's, the constants crs_constants.hpp's, written by tools/make_crs_constants.py); no mesh needed
 //   ortho.hip        orthomosaic baseline: tile predictions assembled into a class raster (k_assemble_tiles), class counts of the raster cells
 //                    under polygon rows (k_zonal_class_counts, k_zonal_ring_stats), polygon rows burned into a label raster (k_burn_rows,
 //                    k_burn_values; one ring walk with the counts, zonal_parity_walk, and one item decode, load_cell_item); no mesh needed
@@ -52,6 +52,11 @@
 //   vis.hip          the pictures (gr_shade_view, gr_composite_labels): k_face_light, a lane per face; k_shade, a workgroup per 16 x 16 output pixels
 //                    with the depth window and its halo in LDS, float32; k_composite, a workgroup per 1024 pixels of a row, byte strips through
 //                    LDS by 16-byte words, float64; one host descriptor a call, no mesh, no scratch, no read-back
+//   raster_warp.hip  raster -> raster (gr_warp_raster): k_warp_raster<cross-CRS, bilinear>, a lane per destination cell, a workgroup per 256 columns of a
+//                    row; the cell centre through crs_dev.hpp's convert where the CRSs differ, a nearest sample or four taps per band; uint8, float32
+//                    and float64 on either side; one host descriptor, no mesh, no scratch, no read-back
+//   crs_dev.hpp      the conversion of one point between the WGS84 systems (G1-G8): CrsSide, CrsArgs, wrap_pi, clenshaw, taup_of, convert, crs_side
+//                    (crs.hip, raster_warp.hip)
 //   cub_steps.hpp    the hipcub calls of the stage calls, each declared once against the call's Plan: SortPairs, SortKeys, ExclusiveSum,
 //                    InclusiveMax, RunLengthEncode, ReduceByKey (size query on construction, typed pointers on run)
 //   compact_dev.hpp  FlagScan, compact_begin, compact_write, k_submesh_write: the scans and the write kernel of polygons.hip's sub-mesh and of decimate.hip;
@@ -59,7 +64,7 @@
 //   geom_dev.hpp     device helpers of polygons.hip, terrain.hip, select.hip, crs.hip, ortho.hip, overlap.hip, simplify.hip and nadir.hip: orient, ring_span, edge_crossing (THE even-odd rule of
 //                    k_polygon_weights, k_face_polygon_index and k_points_in_region), edge_crossing_strict (rule Z3: ortho.hip's ring walk, nadir.hip's faces),
 //                    RingTable (ortho.hip, overlap.hip), ring_of_slot (overlap.hip, simplify.hip), load_face, stat_add / stat_add_u32 / stat_max / stat_count / ring_stats
-//   (below)          the entry checks of the ring-table and grid-window calls: check_ring_table (ortho.hip, overlap.hip), check_window (ortho.hip, nadir.hip)
+//   (below)          the entry checks of the ring-table and grid-window calls: check_ring_table (ortho.hip, overlap.hip), check_window (ortho.hip, nadir.hip, raster_warp.hip)
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 

@@ -430,6 +430,216 @@ def top_down_raster(points, faces, like, backend=None, max_device_bytes=None, re
     return face_ids, heights, {k: int(v) for k, v in zip(TOP_DOWN_STAT_NAMES, totals)}
 
 
+# -- raster -> raster: any raster on any grid in any supported CRS (reference: utils/geospatial.py:333-392) ----
+WARP_OUTLINE_POINTS = 21   # points per edge of the source outline, corners aside, that `default_warp_grid` reprojects
+
+
+def _crs_or_none(crs):
+    return None if crs is None else WGS84CRS.parse(crs)
+
+
+def _crs_epsg(crs):
+    return None if crs is None else crs.epsg
+
+
+def default_warp_grid(raster, src_crs, dst_crs, backend=None):
+    """The grid a raster takes in another CRS when nothing else is asked for -> ((H', W'), transform).  The source outline -- its
+    corners and `WARP_OUTLINE_POINTS` points along every edge -- goes through `backend.reproject_points`; with its bounds xmin, xmax, ymin,
+    ymax: res = hypot(xmax - xmin, ymax - ymin) / hypot(W, H), W' = max(1, floor((xmax - xmin) / res + 0.5)), H' likewise, the grid
+    north-up with its corner at (xmin, ymax).  This is the rule GDAL documents for its suggested warp output (the diagonal keeps
+    its count of cells); parity with GDAL's numbers is not measured.  raster: a `PlanarRaster` or ((H, W), transform).  Geographic
+    grids are (lon, lat): x is the longitude."""
+    from geograypher_amd.utils.raster import PlanarRaster
+
+    if isinstance(raster, PlanarRaster):
+        H, W, transform = raster.data.shape[1], raster.data.shape[2], raster.transform
+    else:
+        (H, W), transform = raster
+    a, b, c, d, e, f = (float(v) for v in transform)
+    n = WARP_OUTLINE_POINTS + 1
+    t = np.arange(n, dtype=np.float64) / n
+    cols = np.concatenate([t * W, np.full(n, float(W)), (1.0 - t) * W, np.zeros(n)])
+    rows = np.concatenate([np.zeros(n), t * H, np.full(n, float(H)), (1.0 - t) * H])
+    outline = np.stack([(a * cols + b * rows) + c, (d * cols + e * rows) + f, np.zeros(4 * n)], axis=1)
+    # (the backend's own call: rows are (x, y) = (lon, lat) on both sides, whatever the authority's axis order)
+    out, _ = (backend if backend is not None else _default_backend()).reproject_points(outline, WGS84CRS.parse(src_crs),
+                                                                                       WGS84CRS.parse(dst_crs))
+    out = _to_host(out).astype(np.float64)
+    if not np.all(np.isfinite(out[:, :2])):
+        raise ValueError(f"default_warp_grid: the raster's outline cannot be taken from {src_crs} to {dst_crs}")
+    xmin, xmax, ymin, ymax = out[:, 0].min(), out[:, 0].max(), out[:, 1].min(), out[:, 1].max()
+    res = float(np.hypot(xmax - xmin, ymax - ymin) / np.hypot(float(W), float(H)))
+    if not res > 0.0:
+        raise ValueError("default_warp_grid: the reprojected outline has no extent")
+    Wd, Hd = max(1, int(np.floor((xmax - xmin) / res + 0.5))), max(1, int(np.floor((ymax - ymin) / res + 0.5)))
+    if Hd >= GRID_SIDE_LIMIT or Wd >= GRID_SIDE_LIMIT:
+        raise ValueError(f"default_warp_grid: the grid would have {Hd} x {Wd} cells, not below 2^23 on both sides")
+    return (Hd, Wd), (res, 0.0, float(xmin), 0.0, -res, float(ymax))
+
+
+def _warp_sides(src_crs, dst_crs):
+    """The CRS-known/unknown matrix of `warp_raster` -> (src, dst) as WGS84CRS for a cross-CRS warp, (None, None) for a same-CRS one."""
+    if (src_crs is None) != (dst_crs is None):
+        missing, known = ("src_crs=", "dst_crs=") if src_crs is None else ("dst_crs=", "src_crs=")
+        raise ValueError(f"warp_raster: {known[:-1]} is known and {missing[:-1]} is not; name the other CRS with {missing} (or neither: "
+                         "both grids are then taken to share one CRS)")
+    src, dst = _crs_or_none(src_crs), _crs_or_none(dst_crs)   # NotImplementedError for a CRS that is not reprojected here
+    if src is None or src == dst or (src.epsg is not None and src.epsg == dst.epsg):
+        return None, None
+    if KIND_ECEF in (src.kind, dst.kind):
+        raise ValueError(f"warp_raster: {src} -> {dst}: an ECEF side: a raster is planar or geographic")
+    return src, dst
+
+
+def warp_raster(raster, like=None, *, resolution=None, dst_crs=None, src_crs=None, resampling: str = "nearest", dst_nodata=None,
+                backend=None, max_device_bytes=None, return_tensor: bool = False):
+    """A raster on another grid, in the same or in another WGS84 CRS, resampled on the device (`HipRaster.warp_raster`,
+    gr_warp_raster; rules W1-W9 of DESIGN.md 8t), in place of rasterio.warp.reproject -> a `PlanarRaster` of the source's dtype (with
+    `return_tensor` its `.data` is the (B, H', W') tensor on the backend's device).
+
+    raster: a `PlanarRaster` or a single-band GeoTIFF path.  like: the destination grid -- a `PlanarRaster`, a GeoTIFF path (only its
+    header is read) or ((height, width), transform); None: `default_warp_grid` in `dst_crs`, or with `resolution` a north-up grid of
+    square cells of that size over the reprojected outline (`grid_from_bounds`).  src_crs defaults to `raster.epsg`, dst_crs to the
+    EPSG code of `like`.  Both known and different: a cross-CRS warp; both known and equal, or both unknown: the grids share a CRS;
+    exactly one known: ValueError naming the keyword to give.  A CRS that `WGS84CRS.parse` refuses: NotImplementedError.
+    resampling: "nearest" (the cell the centre falls into) or "bilinear" (four taps; GDAL widens its kernel when it decimates, this
+    does not).  dst_nodata: default the source's, else NaN.  The source goes to the device once; the destination is produced in
+    bands of rows that take at most `max_device_bytes` (default: the assembly's); the bands do not change a byte.
+    `.last_warp_stats` of the result: the statistics summed over the bands (`_hip.WARP_STAT_NAMES`)."""
+    from geograypher_amd import _hip
+    from geograypher_amd.predictors.ortho_segmentor import DEFAULT_MAX_DEVICE_BYTES, MAX_BAND_ROWS
+    from geograypher_amd.utils.raster import PlanarRaster
+
+    raster = _as_planar_raster(raster)
+    backend = backend if backend is not None else _default_backend()
+    like_epsg = None
+    if like is not None:
+        height, width, transform, like_epsg = _grid_like(like)
+    src_crs = raster.epsg if src_crs is None else src_crs
+    dst_crs = like_epsg if dst_crs is None else dst_crs
+    src, dst = _warp_sides(src_crs, dst_crs)
+    if like is None:
+        if src is None and resolution is None:
+            raise ValueError("warp_raster: no destination: give like=, resolution= or a dst_crs= that differs from the source's")
+        if src is None:
+            (height, width), transform = default_warp_grid_same(raster, resolution)
+        elif resolution is None:
+            (height, width), transform = default_warp_grid(raster, src, dst, backend)
+        else:
+            (Hd, Wd), t = default_warp_grid(raster, src, dst, backend)
+            corners = np.array([[t[2], t[5]], [t[2] + Wd * t[0], t[5] + Hd * t[4]]])
+            (height, width), transform = grid_from_bounds(corners, resolution)
+    elif resolution is not None:
+        raise ValueError("warp_raster: like= and resolution= are both given: the grid is either named or built, not both")
+    if not (1 <= height < GRID_SIDE_LIMIT and 1 <= width < GRID_SIDE_LIMIT):
+        raise ValueError(f"the grid has {height} x {width} cells, not inside [1, 2^23) on both sides")
+    B = raster.data.shape[0]
+    item = raster.data.dtype.itemsize
+    nd = _hip.warp_dst_nodata(dst_nodata, raster.nodata, raster.data.dtype)
+    budget = DEFAULT_MAX_DEVICE_BYTES if max_device_bytes is None else int(max_device_bytes)
+    band = int(max(1, min(height, MAX_BAND_ROWS, budget // (B * item * max(width, 1)))))
+    data_t = backend.to_device(raster.data, raster.data.dtype.name) if hasattr(backend, "to_device") else raster.data
+    parts, totals = [], np.zeros(len(_hip.WARP_STAT_NAMES), dtype=np.int64)
+    for row0 in range(0, height, band):
+        out_t, stats = backend.warp_raster(data_t, raster.inverse, raster.nodata, transform, (0, row0, width, min(band, height - row0)),
+                                           src_crs=src, dst_crs=dst, resampling=resampling, dst_nodata=nd)
+        parts.append(out_t if return_tensor else _to_host(out_t))
+        totals += _to_host(stats).astype(np.int64)[:len(totals)]
+    if len(parts) == 1:
+        data = parts[0]
+    elif return_tensor and hasattr(parts[0], "device"):
+        import torch
+
+        data = torch.cat(parts, dim=1)
+    else:
+        data = np.concatenate(parts, axis=1)
+    epsg = _crs_epsg(dst) if dst is not None else (like_epsg if like_epsg is not None else raster.epsg)
+    result = PlanarRaster(np.zeros((1, 1, 1), dtype=raster.data.dtype), transform, None if np.isnan(nd) else nd, epsg)
+    result.data = data   # (set behind the constructor, which widens uint8: the warp keeps the source's dtype)
+    result.last_warp_stats = {k: int(v) for k, v in zip(_hip.WARP_STAT_NAMES, totals)}
+    return result
+
+
+def default_warp_grid_same(raster, resolution):
+    """The north-up grid of square cells of `resolution` over the outline of a raster, in the raster's own CRS."""
+    H, W = raster.data.shape[1], raster.data.shape[2]
+    a, b, c, d, e, f = raster.transform
+    cols, rows = np.array([0.0, W, W, 0.0]), np.array([0.0, 0.0, H, H])
+    return grid_from_bounds(np.stack([(a * cols + b * rows) + c, (d * cols + e * rows) + f], axis=1), resolution)
+
+
+def read_raster_bands(path):
+    """All bands of a GeoTIFF as a `PlanarRaster` whose data keep the file's sample type where the warp takes it (uint8, float32;
+    anything else becomes float64): (raster, the file's numpy dtype).  Read with PIL: single-band files of `GEOTIFF_MODES`, RGB and
+    RGBA."""
+    from PIL import Image
+
+    from geograypher_amd.utils.raster import PlanarRaster, georeference_from_tags
+
+    limit, Image.MAX_IMAGE_PIXELS = Image.MAX_IMAGE_PIXELS, None
+    try:
+        with Image.open(path) as image:
+            tags = image.tag_v2 if hasattr(image, "tag_v2") else {}
+            transform, nodata, epsg = georeference_from_tags(path, tags)
+            data = np.array(image)
+    finally:
+        Image.MAX_IMAGE_PIXELS = limit
+    file_dtype = data.dtype
+    data = data[None] if data.ndim == 2 else np.ascontiguousarray(np.moveaxis(data, 2, 0))
+    raster = PlanarRaster(np.zeros((1, 1, 1)), transform, nodata, epsg)
+    raster.data = np.ascontiguousarray(data if data.dtype in (np.uint8, np.float32, np.float64) else data.astype(np.float64))
+    return raster, file_dtype
+
+
+def reproject_raster(in_path, out_path, out_crs="EPSG:4326", *, resampling: str = "nearest", like=None, resolution=None, backend=None):
+    """A GeoTIFF in another CRS, all bands, file to file (reference: utils/geospatial.py:333-359, rasterio.warp.reproject with
+    nearest resampling on calculate_default_transform's grid).  The grid is `default_warp_grid` unless `like` or `resolution` names
+    one; a geographic grid is (lon, lat).  The file is written with `write_tiff_deflate` and records the destination's EPSG code,
+    transform and nodata.  NotImplementedError for a CRS `WGS84CRS.parse` refuses, a file that names no CRS, and a sample type or
+    band count the writer cannot hold (it names them).  Returns the `PlanarRaster` that was written."""
+    from geograypher_amd.utils.tiff import _TYPES, write_tiff_deflate
+
+    raster, file_dtype = read_raster_bands(in_path)
+    if raster.epsg is None:
+        raise NotImplementedError(f"{in_path}: the file names no EPSG code; its CRS cannot be told")
+    if np.dtype(file_dtype) not in _TYPES or raster.data.dtype != file_dtype:
+        raise NotImplementedError(f"{in_path}: samples of dtype {file_dtype} are not written by the TIFF writer here "
+                                  f"({', '.join(str(t) for t in _TYPES)} that the warp keeps: uint8, float32)")
+    if raster.data.shape[0] not in (1, 3):
+        raise NotImplementedError(f"{in_path}: {raster.data.shape[0]} bands are not written by the TIFF writer here (1 or 3)")
+    dst = WGS84CRS.parse(out_crs)
+    out = warp_raster(raster, like, resolution=resolution, dst_crs=dst, resampling=resampling, backend=backend)
+    out.epsg = dst.epsg if dst.epsg is not None else out.epsg
+    image = out.data[0] if out.data.shape[0] == 1 else np.moveaxis(out.data, 0, 2)
+    write_tiff_deflate(out_path, np.ascontiguousarray(image), transform=out.transform, nodata=out.nodata, epsg=out.epsg)
+    return out
+
+
+def load_downsampled_raster_data(dataset_filename, downsample_factor: float, *, backend=None):
+    """A raster read at 1 / downsample_factor of its size (reference: utils/geospatial.py:362-392, a rasterio read with
+    out_shape and bilinear resampling) -> (data (B, H', W'), the `PlanarRaster` of the source as the file holds it, the updated
+    transform): H' = int(H / factor), W' = int(W / factor), the transform scaled by (W / W', H / H').  Sampling is the four-tap
+    bilinear rule W6 at the centres of the new cells; GDAL widens its kernel when it decimates, this does not, so at factors above
+    2 the two differ (this one aliases where GDAL averages)."""
+    factor = float(downsample_factor)
+    if not np.isfinite(factor) or factor <= 0:
+        raise ValueError(f"downsample_factor={downsample_factor!r} is not a positive, finite number")
+    raster, _ = read_raster_bands(dataset_filename)
+    H, W = raster.data.shape[1], raster.data.shape[2]
+    Hd, Wd = int(H / factor), int(W / factor)
+    if Hd < 1 or Wd < 1:
+        raise ValueError(f"downsample_factor={factor}: a raster of {H} x {W} cells would have no cell left")
+    a, b, c, d, e, f = raster.transform
+    sx, sy = W / Wd, H / Hd
+    updated = (a * sx, b * sy, c, d * sx, e * sy, f)
+    src_epsg, raster.epsg = raster.epsg, None     # the grids share the file's CRS, whatever it is
+    try:
+        out = warp_raster(raster, ((Hd, Wd), updated), resampling="bilinear", backend=backend)
+    finally:
+        raster.epsg = src_epsg
+    return out.data, raster, updated
+
+
 # -- polygon-on-polygon overlap areas (DESIGN.md 8o, A1-A9; reference: utils/geospatial.py:221-329, gpd.overlay) ------------------------
 # A6: the device's area of a pair lies within OVERLAP_BOUND_K 2^-53 area_abs of the exact one.  K = 4 x the largest ratio the numpy
 # restatement of A5 reached over every pair of every scene of the tests, rounded up to a power of two (tests/overlap_standin.py

@@ -68,6 +68,13 @@ class PlanarRaster:
     def from_array(cls, data, transform, nodata=None):
         return cls(data, transform, nodata)
 
+    def warped(self, like=None, **kwargs):
+        """This raster on another grid, in the same or in another WGS84 CRS: `utils.geospatial.warp_raster(self, like, ...)`, which
+        documents the keywords (resolution, dst_crs, src_crs, resampling, dst_nodata, backend, max_device_bytes, return_tensor)."""
+        from geograypher_amd.utils.geospatial import warp_raster
+
+        return warp_raster(self, like, **kwargs)
+
     @classmethod
     def from_geotiff(cls, path):
         """A single-band GeoTIFF of mode F (float32), I (int32), I;16 (uint16) or L (uint8); strips or tiles, deflate / LZW as

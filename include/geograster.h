@@ -865,6 +865,26 @@ enum {
  * of a photo and a label image.  Both calls take one descriptor, declared there. */
 #include "geograster_vis.h"
 
+/* Raster -> raster warp (geograster_warp.h): the resampling rules, the words of the statistics block
+ * and the largest band count.  The call takes one descriptor, declared there. */
+enum {
+  GR_WARP_NEAREST = 0,
+  GR_WARP_BILINEAR = 1
+};
+enum {
+  GR_WARP_STAT_CELLS = 0,             /* cells of the window                                                        */
+  GR_WARP_STAT_OUTSIDE = 1,           /* cells whose centre (nearest) or whose four taps (bilinear) miss the source */
+  GR_WARP_STAT_NONFINITE = 2,         /* centres the CRS step refuses as not finite (GR_CRS_STAT_NONFINITE's rule)  */
+  GR_WARP_STAT_BEYOND = 3,            /* centres 90 degrees or more from a central meridian                         */
+  GR_WARP_STAT_NODATA = 4,            /* cells that met the source's nodata value or a NaN, in any band             */
+  GR_WARP_STAT_DEN_ZERO = 5,          /* bilinear cells whose participating weights sum to 0, in any band           */
+  GR_WARP_STAT_WORDS = 8
+};
+enum {
+  GR_WARP_MAX_BANDS = 16
+};
+#include "geograster_warp.h"
+
 #ifdef __cplusplus
 }
 #endif
