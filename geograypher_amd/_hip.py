@@ -227,6 +227,17 @@ GR_WARP_STAT_NODATA = 4
 GR_WARP_STAT_DEN_ZERO = 5
 GR_WARP_STAT_WORDS = 8
 GR_WARP_MAX_BANDS = 16
+# the face sieve of include/geograster_components.h (gr_face_sieve)
+GR_SIEVE_STAT_ROUNDS = 0
+GR_SIEVE_STAT_COMPONENTS_BEFORE = 1
+GR_SIEVE_STAT_COMPONENTS_AFTER = 2
+GR_SIEVE_STAT_FACES_CHANGED = 3
+GR_SIEVE_STAT_SMALL_LEFT = 4
+GR_SIEVE_STAT_DEGENERATE = 5
+GR_SIEVE_STAT_FAN_EDGES = 6
+GR_SIEVE_STAT_ROUND_CAP = 7
+GR_SIEVE_STAT_BAD_FACES = 8
+GR_SIEVE_STAT_WORDS = 9
 
 
 class StageTimes(ctypes.Structure):
@@ -440,6 +451,28 @@ WARP_RESAMPLING = {"nearest": GR_WARP_NEAREST, "bilinear": GR_WARP_BILINEAR}
 WARP_STAT_NAMES = ("cells", "outside", "nonfinite", "beyond", "nodata", "den_zero")
 
 
+# ... and the face-sieve call of include/geograster_components.h, under the same rule (tests/test_face_sieve_host.py compares the
+# mirror with the header field by field).
+class FaceSieveArgs(ctypes.Structure):
+    """gr_face_sieve_args"""
+    _fields_ = [
+        ("faces", _vp), ("face_class", _vp), ("weights", _vp), ("vertex_canon", _vp), ("class_out", _vp), ("comp", _vp), ("stats", _vp),
+        ("stream", _vp),
+        ("F", ctypes.c_int64), ("V", ctypes.c_int64), ("min_measure", ctypes.c_int64),
+        ("has_canon", ctypes.c_int32), ("fill_unlabelled", ctypes.c_int32), ("max_rounds", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+_COMPONENTS_SIGNATURES = {
+    "gr_face_sieve": [_vp, ctypes.POINTER(FaceSieveArgs)],
+}
+COMPONENTS_SYMBOLS = tuple(_COMPONENTS_SIGNATURES)
+SIEVE_SIZE_LIMIT = 2 ** 31 - 1      # F, V below it; 3 F at or below it
+SIEVE_MEASURE_LIMIT = 2 ** 62       # I5: the sum of all weights stays below it
+SIEVE_STAT_NAMES = ("rounds", "components_before", "components_after", "faces_changed", "small_left", "degenerate", "fan_edges",
+                    "round_cap", "bad_faces")
+
+
 def library_path() -> Path:
     return _LIB_PATH
 
@@ -462,7 +495,7 @@ def load_library() -> ctypes.CDLL:
     lib = ctypes.CDLL(str(_LIB_PATH))
     for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES, **_BURN_SIGNATURES,
                            **_OVERLAP_SIGNATURES, **_COMMUNITIES_SIGNATURES, **_SIMPLIFY_SIGNATURES, **_NADIR_SIGNATURES,
-                           **_VIS_SIGNATURES, **_WARP_SIGNATURES}.items():
+                           **_VIS_SIGNATURES, **_WARP_SIGNATURES, **_COMPONENTS_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -1072,6 +1105,32 @@ def check_warp_window(src_shape, col_off: int, row_off: int, width: int, height:
         warp_numpy_dtype(dst_dtype)
 
 
+def check_sieve_arguments(F: int, V: int, weights, min_measure, max_rounds) -> int:
+    """The host checks of gr_face_sieve (I1, I5): sizes inside the call's limits, min_measure >= 0, max_rounds >= 1, `weights` (a
+    host array or None) F integers, none negative, their sum below 2^62 -- ValueError naming gr_face_sieve.  -> min_measure as an
+    int."""
+    name = "gr_face_sieve"
+    if not (0 <= F < SIEVE_SIZE_LIMIT and 0 <= V < SIEVE_SIZE_LIMIT and 3 * F <= SIEVE_SIZE_LIMIT):
+        raise ValueError(f"{name}: F={F}, V={V}: each in [0, 2^31 - 1), and 3 F <= 2^31 - 1")
+    if int(min_measure) != min_measure or int(min_measure) < 0 or int(min_measure) >= 2 ** 63:
+        raise ValueError(f"{name}: min_measure={min_measure!r} is not an integer in [0, 2^63)")
+    if int(max_rounds) < 1:
+        raise ValueError(f"{name}: max_rounds={max_rounds!r} is below 1")
+    if weights is not None:
+        w = np.asarray(weights)
+        if w.dtype.kind not in "iu" or w.shape != (F,):
+            raise ValueError(f"{name}: weights must be ({F},) integers, got {w.shape} {w.dtype}")
+        if F and int(w.min()) < 0:
+            raise ValueError(f"{name}: a weight is negative")
+        if F and int(w.max()) >= SIEVE_MEASURE_LIMIT:
+            raise ValueError(f"{name}: a weight is not below 2^62")
+        w = w.astype(np.int64)
+        total = (int((w >> 32).sum()) << 32) + int((w & 0xFFFFFFFF).sum())      # exact: neither part sum leaves int64
+        if total >= SIEVE_MEASURE_LIMIT:
+            raise ValueError(f"{name}: the weights sum to {total}, not below 2^62")
+    return int(min_measure)
+
+
 class NadirRasterizer:
     """One mesh on the device -- vertices in cell units of a parent grid, their heights, the faces --, rastered from above into any
     number of windows of that grid (gr_nadir_raster).  Made by `HipRaster.nadir_rasterizer`, which checks
@@ -1234,6 +1293,47 @@ class RasterWarper:
                               height=height, resampling=WARP_RESAMPLING[resampling], same_crs=1 if sides is None else 0)
         hip._call("gr_warp_raster", ctypes.byref(args))
         return out, stats
+
+
+class FaceSieve:
+    """The face-sieve call on one backend (include/geograster_components.h), behind `HipRaster.face_sieve`,
+    which documents it.  Every output is allocated through the backend (`_empty`, `_stats`), the inputs go through `_shaped` and `_dev`."""
+
+    def __init__(self, backend: "HipRaster"):
+        self.backend = backend
+
+    def sieve(self, faces, classes, weights, min_measure, fill_unlabelled, vertex_canon, max_rounds, n_vertices, out):
+        torch = _torch()
+        hip = self.backend
+        f_t = hip._shaped(faces, torch.int32, ("F", 3), "faces")
+        F = int(f_t.shape[0])
+        c_t = hip._shaped(classes, torch.int32, (F,), "classes (one per face)")
+        canon_t = None if vertex_canon is None else hip._dev(vertex_canon, torch.int32).reshape(-1)
+        if canon_t is not None:
+            V = int(canon_t.shape[0])
+        elif n_vertices is not None:
+            V = int(n_vertices)
+        else:
+            V = int(f_t.max().item()) + 1 if F else 0
+            if V < 0 or V >= SIEVE_SIZE_LIMIT:
+                raise ValueError(f"gr_face_sieve: the faces name vertex {V - 1}")
+        w_host = None
+        if weights is not None:
+            w_host = weights.detach().cpu().numpy() if isinstance(weights, torch.Tensor) else np.asarray(weights)
+        min_measure = check_sieve_arguments(F, V, w_host, min_measure, max_rounds)
+        w_t = None if weights is None else hip._shaped(weights, torch.int64, (F,), "weights (one per face)")
+        if out is not None and (not isinstance(out, torch.Tensor) or out.data_ptr() != c_t.data_ptr()):
+            raise ValueError("out must be the classes themselves, a contiguous int32 tensor on the device (in place), or None")
+        class_out = c_t if out is not None else hip._empty((F,), torch.int32)
+        comp = hip._empty((F,), torch.int32)
+        stats = hip._stats(GR_SIEVE_STAT_WORDS)
+        args = FaceSieveArgs(faces=_ptr(f_t if F else None), face_class=_ptr(c_t if F else None), weights=_ptr(w_t if F else None),
+                             vertex_canon=_ptr(canon_t if canon_t is not None and V else None), class_out=_ptr(class_out if F else None),
+                             comp=_ptr(comp if F else None), stats=stats.data_ptr(), stream=hip._stream().value, F=F, V=V,
+                             min_measure=min_measure, has_canon=0 if canon_t is None else 1, fill_unlabelled=1 if fill_unlabelled else 0,
+                             max_rounds=int(max_rounds), reserved=0)
+        hip._call("gr_face_sieve", ctypes.byref(args))
+        return class_out, comp, stats
 
 
 class RayCommunities:
@@ -2304,6 +2404,18 @@ class HipRaster:
         dtype to write.  Only enqueues."""
         return RasterWarper(self).warp(data, src_inverse, src_nodata, dst_transform, window, src_crs, dst_crs, resampling, dst_nodata,
                                        dst_dtype, out)
+
+    # -- the face sieve: components of equally labelled faces, small ones merged into their greatest neighbour (DESIGN.md 8u) --
+    def face_sieve(self, faces, classes, weights=None, min_measure=0, fill_unlabelled: bool = False, vertex_canon=None,
+                   max_rounds: int = 64, n_vertices: Optional[int] = None, out=None):
+        """gr_face_sieve (I1-I10): faces (F, 3) int, classes (F,) int (< 0: unlabelled), weights (F,) int64 >= 0 or None for 1 per
+        face, numpy or device tensors -> (class_out (F,) int32 tensor, comp (F,) int32 tensor: the smallest face of the face's
+        component in the final labelling, -1 for a face that takes no part, stats (GR_SIEVE_STAT_WORDS,) int64 tensor), on the
+        call's stream.  min_measure = 0: the component labelling alone.  vertex_canon (V,) int: corner v stands for vertex_canon[v].
+        V is len(vertex_canon), else `n_vertices`, else the largest corner + 1 (which reads the faces back).  out: the classes
+        tensor itself, to sieve in place.  The weights are checked on the host first (none negative, sum < 2^62: ValueError).
+        Waits for the stream once per round."""
+        return FaceSieve(self).sieve(faces, classes, weights, min_measure, fill_unlabelled, vertex_canon, max_rounds, n_vertices, out)
 
     # -- the orthomosaic baseline: tile assembly, zonal class counts ----------------------------------------------------
     def assemble_tiles(self, preds, pred_offsets, windows, tile_table, weights, weight_offsets, count_dtype, bin_table,

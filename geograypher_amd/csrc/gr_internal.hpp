@@ -55,6 +55,9 @@
 //   raster_warp.hip  raster -> raster (gr_warp_raster): k_warp_raster<cross-CRS, bilinear>, a lane per destination cell, a workgroup per 256 columns of a
 //                    row; the cell centre through crs_dev.hpp's convert where the CRSs differ, a nearest sample or four taps per band; uint8, float32
 //                    and float64 on either side; one host descriptor, no mesh, no scratch, no read-back
+//   components.hip   the face sieve (gr_face_sieve): k_sieve_keys and one sort put the faces of an edge side by side; per round a union-find over the
+//                    same-class pairs (k_cc_hook, k_cc_compress), integer measures (k_measure, k_count_small), the greatest labelled neighbour in
+//                    two atomic passes (k_target), k_pointers, k_jump, k_relabel; one host descriptor, one word read back per round; no mesh needed
 //   crs_dev.hpp      the conversion of one point between the WGS84 systems (G1-G8): CrsSide, CrsArgs, wrap_pi, clenshaw, taup_of, convert, crs_side
 //                    (crs.hip, raster_warp.hip)
 //   cub_steps.hpp    the hipcub calls of the stage calls, each declared once against the call's Plan: SortPairs, SortKeys, ExclusiveSum,

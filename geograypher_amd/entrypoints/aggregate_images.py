@@ -62,6 +62,9 @@ def aggregate_images(
     top_down_raster_projection_savefile: typing.Union[PATH_TYPE, None] = None,
     top_down_raster_resolution: typing.Union[float, None] = None,
     vis_folder: typing.Union[PATH_TYPE, None] = None,
+    sieve_min_area_m2: typing.Union[float, None] = None,
+    sieve_min_faces: typing.Union[int, None] = None,
+    sieve_fill_unseen: bool = False,
 ):
     """Aggregate the labels under `label_folder` onto the mesh (see the module docstring).  The reference's arguments and defaults;
     `mesh_downsample != 1` without `mesh_downsample_method`, `vis`, `ROI` without `ROI_points_file`, `DTM_file` without `DTM_points_file` and
@@ -81,7 +84,12 @@ def aggregate_images(
     `top_down_raster_projection_savefile` (.tif / .tiff) writes the classes as a uint8 GeoTIFF seen from above, cells of
     `top_down_raster_resolution` map units on a north-up grid over the vertices (`export_face_labels_raster`: where surfaces
     overlap in plan view the upper one wins; nodata 255); it uses the same `top_down_points_file` (here (V, 3): z decides) or
-    `top_down_CRS` as the vector map and may be given with or without it.  Its arguments are checked before the aggregation.  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
+    `top_down_CRS` as the vector map and may be given with or without it.  Its arguments are checked before the aggregation.
+    `sieve_min_area_m2` or `sieve_min_faces` (one of them at most) removes the speckle of the class per face on the device before the
+    ground step, the saved file and the maps: connected regions of one class below that surface area / face count join their
+    greatest neighbour region (`TexturedPhotogrammetryMesh.sieve_face_labels`); `sieve_fill_unseen` also
+    fills small regions of unseen faces and needs one of the two.  With the three at their defaults every output is what it is
+    without them.  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
     from geograypher_amd.cameras.segmentor import SegmentorPhotogrammetryCameraSet
     from geograypher_amd.meshes import TexturedPhotogrammetryMesh, TexturedPhotogrammetryMeshChunked
     from geograypher_amd.predictors.derived_segmentors import LookUpSegmentor
@@ -108,6 +116,11 @@ def aggregate_images(
         if top_down_raster_resolution is None or not np.isfinite(float(top_down_raster_resolution)) or float(top_down_raster_resolution) <= 0:
             raise ValueError(f"top_down_raster_projection_savefile needs top_down_raster_resolution, a positive cell size in map "
                              f"units, got {top_down_raster_resolution!r}")
+
+    if sieve_min_area_m2 is not None and sieve_min_faces is not None:
+        raise ValueError("sieve_min_area_m2 and sieve_min_faces are both given: the sieve has one threshold")
+    if sieve_fill_unseen and sieve_min_area_m2 is None and sieve_min_faces is None:
+        raise ValueError("sieve_fill_unseen needs a threshold: sieve_min_area_m2 or sieve_min_faces")
 
     for name, value, why in (
         ("DTM_file", DTM_file if DTM_points is None else None,
@@ -219,6 +232,11 @@ def aggregate_images(
         predicted_face_classes = predicted_face_classes.cpu().numpy()
     predicted_face_classes = np.array(predicted_face_classes, dtype=np.float64).reshape(-1, 1)
 
+    if sieve_min_area_m2 is not None or sieve_min_faces is not None:   # before the ground step, which the sieve must not undo
+        predicted_face_classes = np.asarray(mesh.sieve_face_labels(predicted_face_classes, min_faces=sieve_min_faces,
+                                                                   min_area_m2=sieve_min_area_m2, fill_unseen=sieve_fill_unseen),
+                                            dtype=np.float64).reshape(-1, 1)
+
     if DTM_file is not None and height_above_ground_threshold is not None:   # reference: aggregate_images.py:198-206
         points_in_raster_CRS = DTM_points
         if kept_point_IDs is not None and not is_CRS_designator(points_in_raster_CRS):
@@ -308,6 +326,12 @@ def parse_args(argv=None):
                         "needs --top-down-raster-resolution and --top-down-points-file (V, 3) or --top-down-CRS")
     parser.add_argument("--top-down-raster-resolution", type=float,
                         help="Cell size of --top-down-raster-projection-savefile in map units")
+    parser.add_argument("--sieve-min-area-m2", type=float,
+                        help="Sieve the class per face: connected regions of one class below this surface area join their greatest "
+                        "neighbour region, on the device")
+    parser.add_argument("--sieve-min-faces", type=int, help="... below this number of faces instead (one of the two at most)")
+    parser.add_argument("--sieve-fill-unseen", action="store_true",
+                        help="The sieve also fills small regions of unseen faces; needs one of the two thresholds")
     parser.add_argument("--vis", action="store_true", help="Not available here")
     parser.add_argument("--vis-folder", type=Path,
                         help="Write mesh_and_cameras.png and predicted_classes.png (each with its .legend.json) here: the two pictures "

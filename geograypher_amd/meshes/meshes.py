@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import hashlib
 import logging
+import math
 import sys
 import contextlib
 import typing
@@ -1304,6 +1305,61 @@ class TexturedPhotogrammetryMesh:
         if top >= 2 ** 31 - 1:
             raise ValueError(f"class id {top:.0f} does not fit the int32 class table")
         return to_int(classes), int(top) + 1
+
+    # -- the face sieve --------------------------------------------------------------------------
+    def _labels_like(self, classes, face_labels, return_tensor: bool):
+        """int32 classes (-1: unseen) back in the convention of `face_labels`: float64, NaN for unseen, its shape."""
+        if hasattr(classes, "detach"):
+            torch = _torch()
+            labels = torch.where(classes < 0, torch.full((), float("nan"), dtype=torch.float64, device=classes.device),
+                                 classes.to(torch.float64)).reshape(tuple(face_labels.shape))
+            return labels if return_tensor else labels.cpu().numpy()
+        labels = np.where(classes < 0, np.nan, classes.astype(np.float64)).reshape(tuple(face_labels.shape))
+        return _torch().as_tensor(labels).to(self.backend.device) if return_tensor else labels
+
+    def face_label_components(self, face_labels, weld_vertices: bool = False, return_tensor: bool = False):
+        """The connected regions of a per-face class map (rule I4): (comp (F,) int32 -- the smallest face index of the face's
+        component of edge-neighbours of equal label, unseen (NaN) faces forming components of their own kind, -1 for a degenerate
+        face --, stats: a dict over `utils.geometric.SIEVE_STAT_NAMES`).  face_labels as `_face_classes` takes them.
+        weld_vertices: vertices with bit-equal coordinates count as one (`utils.geometric.weld_canon`), which closes split seams."""
+        from geograypher_amd.utils.geometric import face_components, weld_canon
+
+        classes, _ = self._face_classes(self._squeezed_1d(face_labels))
+        canon = weld_canon(self.points) if weld_vertices else None
+        comp, stats = face_components(np.ascontiguousarray(self.faces, dtype=np.int32), classes, self.backend, canon,
+                                      n_vertices=int(self.points.shape[0]), return_tensor=return_tensor)
+        self.last_sieve_stats = stats
+        return comp, stats
+
+    def sieve_face_labels(self, face_labels, *, min_faces=None, min_area_m2=None, fill_unseen: bool = False, weld_vertices: bool = False,
+                          max_rounds: int = 64, return_tensor: bool = False):
+        """A per-face class map with its speckle removed (rules I1-I10): every connected region of equal label that is smaller
+        than the threshold joins its greatest labelled neighbour region, round after round, until none is left that has one.
+        Exactly one threshold: min_faces (a region of fewer faces is small) or min_area_m2 (a region of less surface area, counted
+        in mm^2 per face by `utils.geometric.face_area_weights`; the threshold is ceil(min_area_m2 * 1e6)).  fill_unseen: small
+        regions of unseen (NaN) faces are filled from their neighbours too; without it they stay and separate what they separate.
+        Labels go in and come out in the convention of `_face_classes` and `argmax_nonzero`: float, NaN unseen, (F,) or (F, 1),
+        array or device tensor (out: float64; a device tensor with `return_tensor`).  The call's figures are kept in
+        `last_sieve_stats`."""
+        from geograypher_amd.utils.geometric import SIEVE_AREA_UNITS_PER_M2, face_area_weights, sieve_face_classes, weld_canon
+
+        if (min_faces is None) == (min_area_m2 is None):
+            raise ValueError("exactly one of min_faces and min_area_m2 must be given")
+        classes, _ = self._face_classes(self._squeezed_1d(face_labels))
+        faces = np.ascontiguousarray(self.faces, dtype=np.int32)
+        if min_faces is not None:
+            if int(min_faces) != min_faces or min_faces < 0:
+                raise ValueError(f"min_faces={min_faces!r} is not a whole number >= 0")
+            weights, min_measure = None, int(min_faces)
+        else:
+            if not (min_area_m2 >= 0 and math.isfinite(min_area_m2)):
+                raise ValueError(f"min_area_m2={min_area_m2!r} is not a finite area >= 0")
+            weights, min_measure = face_area_weights(self.points, faces), int(math.ceil(min_area_m2 * SIEVE_AREA_UNITS_PER_M2))
+        canon = weld_canon(self.points) if weld_vertices else None
+        class_out, _comp, stats = sieve_face_classes(faces, classes, weights, min_measure, fill_unseen, canon, max_rounds, self.backend,
+                                                     n_vertices=int(self.points.shape[0]), return_tensor=True)
+        self.last_sieve_stats = stats
+        return self._labels_like(class_out, face_labels, return_tensor)
 
     @staticmethod
     def _snap_with_polygons(verts, polygons):

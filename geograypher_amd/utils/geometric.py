@@ -472,6 +472,74 @@ def shared_border_fixed(ring_q, ring_offsets) -> np.ndarray:
     return fixed
 
 
+# -- the face sieve: components of equally labelled faces, small ones merged into their greatest neighbour --------
+SIEVE_STAT_NAMES = ("rounds", "components_before", "components_after", "faces_changed", "small_left", "degenerate", "fan_edges",
+                    "round_cap", "bad_faces")   # GR_SIEVE_STAT_*
+SIEVE_AREA_UNITS_PER_M2 = 1e6   # face_area_weights counts mm^2
+
+
+def face_area_weights(points, faces) -> np.ndarray:
+    """(F,) int64: the area of every face in mm^2, w = floor(0.5 * |(p1 - p0) x (p2 - p0)| * 1e6 + 0.5) -- ONE float64 expression,
+    computed once on the host; the device sees the integers only (I5)."""
+    p = np.asarray(_host(points), dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(_host(faces), dtype=np.int64).reshape(-1, 3)
+    p0, p1, p2 = p[f[:, 0]], p[f[:, 1]], p[f[:, 2]]
+    return np.floor(0.5 * np.linalg.norm(np.cross(p1 - p0, p2 - p0), axis=1) * SIEVE_AREA_UNITS_PER_M2 + 0.5).astype(np.int64)
+
+
+def weld_canon(points) -> np.ndarray:
+    """(V,) int32 for I1's `vertex_canon`: vertices whose float64 coordinates are bit-equal map to the smallest index of their
+    group (-0.0 and 0.0 differ in a bit and are not welded; neither are NaNs of different payloads).  A host sort."""
+    p = np.ascontiguousarray(np.asarray(_host(points), dtype=np.float64).reshape(-1, 3))
+    V = len(p)
+    if V == 0:
+        return np.zeros(0, dtype=np.int32)
+    bits = p.view(np.uint64).reshape(V, 3)
+    order = np.lexsort((np.arange(V), bits[:, 2], bits[:, 1], bits[:, 0]))
+    s = bits[order]
+    head = np.ones(V, dtype=bool)
+    head[1:] = np.any(s[1:] != s[:-1], axis=1)
+    first = order[head][np.cumsum(head) - 1]      # the group's first vertex in the sorted order: its smallest index
+    canon = np.empty(V, dtype=np.int32)
+    canon[order] = first
+    return canon
+
+
+def sieve_face_classes(faces, classes, weights=None, min_measure=0, fill_unlabelled: bool = False, vertex_canon=None, max_rounds: int = 64,
+                       backend=None, n_vertices=None, return_tensor: bool = False):
+    """Rules I1-I10 through `backend.face_sieve`: faces (F, 3), classes (F,) integers (< 0: unlabelled), weights (F,) int64 >= 0 or
+    None for 1 per face, arrays or device tensors -> (class_out (F,) int32, comp (F,) int32: the smallest face of the face's
+    component in the final labelling, -1 for a face that takes no part, stats: a dict over SIEVE_STAT_NAMES).  A component whose
+    measure is below `min_measure` joins its greatest labelled neighbour; min_measure = 0 only labels the components.  A face that
+    names a vertex outside the mesh is a ValueError.  `backend`: a `HipRaster` (None: the shared one) or an object with its
+    `face_sieve` method.  With `return_tensor` the two arrays stay on the device."""
+    if backend is None:
+        from geograypher_amd._hip import default_backend
+
+        backend = default_backend()
+    classes_flat = classes.reshape(-1)
+    n_faces = int(faces.shape[0])
+    if int(classes_flat.shape[0]) != n_faces:
+        raise ValueError(f"{int(classes_flat.shape[0])} face classes for {n_faces} faces")
+    class_out, comp, stats = backend.face_sieve(faces, classes_flat, weights, min_measure, fill_unlabelled, vertex_canon, max_rounds,
+                                                **({} if n_vertices is None else {"n_vertices": n_vertices}))
+    stats_h = _host(stats)
+    named = {name: int(stats_h[k]) for k, name in enumerate(SIEVE_STAT_NAMES)}
+    if named["bad_faces"]:
+        raise ValueError(f"gr_face_sieve: {named['bad_faces']} faces name a vertex (or a vertex_canon entry) outside the mesh")
+    if return_tensor:
+        return class_out, comp, named
+    return _host(class_out).astype(np.int32), _host(comp).astype(np.int32), named
+
+
+def face_components(faces, classes, backend=None, vertex_canon=None, n_vertices=None, return_tensor: bool = False):
+    """Rule I4 alone: (comp (F,) int32: the smallest face of the face's component of edge-neighbours of equal class -- unlabelled,
+    any class < 0, is a class here --, -1 for a degenerate face; stats: a dict over SIEVE_STAT_NAMES, `components_before` the
+    number of components).  `sieve_face_classes` with min_measure = 0."""
+    _, comp, stats = sieve_face_classes(faces, classes, None, 0, False, vertex_canon, 64, backend, n_vertices, return_tensor)
+    return comp, stats
+
+
 # -- mesh decimation by vertex clustering (DESIGN.md section 8n) ---------------------------------------------------------------------
 CLUSTER_COORD_LIMIT = 1 << 41   # D1: snapped coordinates behind their minimum stay below this
 CLUSTER_CELLS_PER_AXIS = 1 << 21   # D2: a cell component fits 21 bits of the key

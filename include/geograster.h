@@ -885,6 +885,22 @@ enum {
 };
 #include "geograster_warp.h"
 
+/* Face sieve (geograster_components.h): the words of the statistics block.  The call takes one
+ * descriptor, declared there. */
+enum {
+  GR_SIEVE_STAT_ROUNDS = 0,             /* rounds that changed a face                                                  */
+  GR_SIEVE_STAT_COMPONENTS_BEFORE = 1,  /* components of the input labelling                                           */
+  GR_SIEVE_STAT_COMPONENTS_AFTER = 2,   /* components of the final labelling (comp)                                    */
+  GR_SIEVE_STAT_FACES_CHANGED = 3,      /* faces whose class a round changed, summed over the rounds                   */
+  GR_SIEVE_STAT_SMALL_LEFT = 4,         /* small components (I7) of the final labelling                                */
+  GR_SIEVE_STAT_DEGENERATE = 5,         /* faces with two equal corners                                                */
+  GR_SIEVE_STAT_FAN_EDGES = 6,          /* edges shared by more than two faces                                         */
+  GR_SIEVE_STAT_ROUND_CAP = 7,          /* 1: max_rounds rounds changed a face, the labelling may not be final         */
+  GR_SIEVE_STAT_BAD_FACES = 8,          /* faces with a corner or a vertex_canon entry outside [0, V)                  */
+  GR_SIEVE_STAT_WORDS = 9
+};
+#include "geograster_components.h"
+
 #ifdef __cplusplus
 }
 #endif
