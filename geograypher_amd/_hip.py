@@ -238,6 +238,17 @@ GR_SIEVE_STAT_FAN_EDGES = 6
 GR_SIEVE_STAT_ROUND_CAP = 7
 GR_SIEVE_STAT_BAD_FACES = 8
 GR_SIEVE_STAT_WORDS = 9
+# the nearest-point call of include/geograster_nearest.h (gr_nearest_points)
+GR_NN_STAT_REF_NONFINITE = 0
+GR_NN_STAT_QUERY_NONFINITE = 1
+GR_NN_STAT_NO_ANSWER = 2
+GR_NN_STAT_LEVELS = 3
+GR_NN_STAT_CARRIED = 4
+GR_NN_STAT_CELLS_PROBED = 5
+GR_NN_STAT_CANDIDATES = 6
+GR_NN_STAT_CELL_BITS = 7
+GR_NN_STAT_RING_CAP = 8
+GR_NN_STAT_WORDS = 9
 
 
 class StageTimes(ctypes.Structure):
@@ -473,6 +484,26 @@ SIEVE_STAT_NAMES = ("rounds", "components_before", "components_after", "faces_ch
                     "round_cap", "bad_faces")
 
 
+# ... and the nearest-point call of include/geograster_nearest.h, under the same rule (tests/test_nearest_points_host.py compares
+# the mirror with the header field by field).
+class NearestArgs(ctypes.Structure):
+    """gr_nearest_args"""
+    _fields_ = [
+        ("ref", _vp), ("query", _vp), ("index_out", _vp), ("dist2_out", _vp), ("stats", _vp), ("stream", _vp),
+        ("R", ctypes.c_int64), ("Q", ctypes.c_int64), ("cell", ctypes.c_double), ("max_distance", ctypes.c_double),
+        ("max_rings", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+_NEAREST_SIGNATURES = {
+    "gr_nearest_points": [_vp, ctypes.POINTER(NearestArgs)],
+}
+NEAREST_SYMBOLS = tuple(_NEAREST_SIGNATURES)
+NEAREST_SIZE_LIMIT = 2 ** 31 - 1      # R, Q below it
+NEAREST_STAT_NAMES = ("ref_nonfinite", "query_nonfinite", "no_answer", "levels", "carried", "cells_probed", "candidates", "cell_bits",
+                      "ring_cap")
+
+
 def library_path() -> Path:
     return _LIB_PATH
 
@@ -495,7 +526,7 @@ def load_library() -> ctypes.CDLL:
     lib = ctypes.CDLL(str(_LIB_PATH))
     for name, argtypes in {**_SIGNATURES, **_COMPANION_SIGNATURES, **_ORTHO_SIGNATURES, **_DECIMATE_SIGNATURES, **_BURN_SIGNATURES,
                            **_OVERLAP_SIGNATURES, **_COMMUNITIES_SIGNATURES, **_SIMPLIFY_SIGNATURES, **_NADIR_SIGNATURES,
-                           **_VIS_SIGNATURES, **_WARP_SIGNATURES, **_COMPONENTS_SIGNATURES}.items():
+                           **_VIS_SIGNATURES, **_WARP_SIGNATURES, **_COMPONENTS_SIGNATURES, **_NEAREST_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if name == "gr_last_error" else _i32
         fn.argtypes = argtypes
@@ -1334,6 +1365,49 @@ class FaceSieve:
                              max_rounds=int(max_rounds), reserved=0)
         hip._call("gr_face_sieve", ctypes.byref(args))
         return class_out, comp, stats
+
+
+def check_nearest_arguments(R: int, Q: int, max_distance, cell, max_rings) -> tuple:
+    """The host checks of gr_nearest_points (K4, K8): sizes inside the call's limits, max_distance None or >= 0 (not NaN), cell a
+    finite size >= 0, max_rings >= 1 -- ValueError naming gr_nearest_points.  -> (max_distance as a float, +inf for None, cell,
+    max_rings)."""
+    name = "gr_nearest_points"
+    if not (0 <= R < NEAREST_SIZE_LIMIT and 0 <= Q < NEAREST_SIZE_LIMIT):
+        raise ValueError(f"{name}: R={R}, Q={Q}: each in [0, 2^31 - 1)")
+    md = float("inf") if max_distance is None else float(max_distance)
+    if not md >= 0:
+        raise ValueError(f"{name}: max_distance={max_distance!r} is not a distance >= 0 (None: no limit)")
+    cell = float(cell)
+    if not (cell >= 0 and cell != float("inf")):
+        raise ValueError(f"{name}: cell={cell!r} is not a finite size >= 0 (0: chosen by the call)")
+    if int(max_rings) != max_rings or int(max_rings) < 1 or int(max_rings) >= 2 ** 31:
+        raise ValueError(f"{name}: max_rings={max_rings!r} is not a whole number in [1, 2^31)")
+    return md, cell, int(max_rings)
+
+
+class NearestPoints:
+    """The nearest-point call on one backend (include/geograster_nearest.h), behind
+    `HipRaster.nearest_points`, which documents it.  Every output is allocated through the backend (`_empty`, `_stats`), the inputs
+    go through `_shaped`."""
+
+    def __init__(self, backend: "HipRaster"):
+        self.backend = backend
+
+    def query(self, ref, query, max_distance, cell, max_rings, return_dist2):
+        torch = _torch()
+        hip = self.backend
+        r_t = hip._shaped(ref, torch.float64, ("R", 3), "ref")
+        q_t = hip._shaped(query, torch.float64, ("Q", 3), "query")
+        R, Q = int(r_t.shape[0]), int(q_t.shape[0])
+        md, cell, max_rings = check_nearest_arguments(R, Q, max_distance, cell, max_rings)
+        index = hip._empty((Q,), torch.int32)
+        dist2 = hip._empty((Q,), torch.float64) if return_dist2 else None
+        stats = hip._stats(GR_NN_STAT_WORDS)
+        args = NearestArgs(ref=_ptr(r_t if R else None), query=_ptr(q_t if Q else None), index_out=_ptr(index if Q else None),
+                           dist2_out=_ptr(dist2 if Q else None), stats=stats.data_ptr(), stream=hip._stream().value, R=R, Q=Q,
+                           cell=cell, max_distance=md, max_rings=max_rings, reserved=0)
+        hip._call("gr_nearest_points", ctypes.byref(args))
+        return (index, dist2, stats) if return_dist2 else (index, stats)
 
 
 class RayCommunities:
@@ -2416,6 +2490,16 @@ class HipRaster:
         tensor itself, to sieve in place.  The weights are checked on the host first (none negative, sum < 2^62: ValueError).
         Waits for the stream once per round."""
         return FaceSieve(self).sieve(faces, classes, weights, min_measure, fill_unlabelled, vertex_canon, max_rounds, n_vertices, out)
+
+    # -- nearest points: for every query row the nearest ref row, exact (DESIGN.md 8v) ---------------------------------------
+    def nearest_points(self, ref, query, *, max_distance=None, cell: float = 0.0, max_rings: int = 2, return_dist2: bool = False):
+        """gr_nearest_points (K1-K9): ref (R, 3), query (Q, 3) float64, numpy or device tensors -> (index (Q,) int32 tensor: the
+        row of the nearest ref, the lowest among equally near ones, -1 where there is none; [dist2 (Q,) float64 tensor with
+        `return_dist2`: K2's squared distance, NaN beside -1;] stats (GR_NN_STAT_WORDS,) int64 tensor), on the call's stream.
+        Rows with a NaN or infinite coordinate take no part (ref) or get -1 (query).  max_distance: answers farther than it
+        become -1 (one exactly at it stays).  cell (0: chosen by the call) and max_rings steer the search only, never the answer.
+        Waits for the stream once for the bounds and once per grid level."""
+        return NearestPoints(self).query(ref, query, max_distance, cell, max_rings, return_dist2)
 
     # -- the orthomosaic baseline: tile assembly, zonal class counts ----------------------------------------------------
     def assemble_tiles(self, preds, pred_offsets, windows, tile_table, weights, weight_offsets, count_dtype, bin_table,

@@ -12,7 +12,7 @@ CSRC = ROOT / "csrc"
 SOURCES = [CSRC / n for n in ("geograster.hip", "mesh_upload.hip", "binning.hip", "raster_tile.hip", "project.hip", "warp.hip",
                               "resize.hip", "rays.hip", "equirect.hip", "polygons.hip", "cover.hip", "terrain.hip", "select.hip", "crs.hip", "ortho.hip",
                               "decimate.hip", "overlap.hip", "communities.hip", "simplify.hip", "nadir.hip", "vis.hip", "raster_warp.hip",
-                              "components.hip")]
+                              "components.hip", "nearest.hip")]
 HEADERS = [CSRC / "gr_internal.hpp", CSRC / "dev_common.hpp", CSRC / "geom_dev.hpp", CSRC / "scratch_layout.hpp", CSRC / "device_buffer.hpp",
            CSRC / "crs_constants.hpp", CSRC / "compact_dev.hpp", CSRC / "cub_steps.hpp", CSRC / "ray_dev.hpp", CSRC / "crs_dev.hpp"]
 SRC = CSRC / "raster_tile.hip"   # the tile kernel's source (tests/test_isa_waits.py compiles it to assembly)
@@ -37,7 +37,8 @@ def hipcc_path() -> str:
 def _newest_header() -> float:
     public = [INCLUDE / n for n in ("geograster.h", "geograster_outlines.h", "geograster_ortho.h", "geograster_decimate.h",
                                    "geograster_burn.h", "geograster_overlap.h", "geograster_communities.h", "geograster_simplify.h",
-                                   "geograster_nadir.h", "geograster_vis.h", "geograster_warp.h", "geograster_components.h")]
+                                   "geograster_nadir.h", "geograster_vis.h", "geograster_warp.h", "geograster_components.h",
+                                   "geograster_nearest.h")]
     return max(p.stat().st_mtime for p in HEADERS + public + [Path(__file__)])
 
 

@@ -58,6 +58,10 @@
 //   components.hip   the face sieve (gr_face_sieve): k_sieve_keys and one sort put the faces of an edge side by side; per round a union-find over the
 //                    same-class pairs (k_cc_hook, k_cc_compress), integer measures (k_measure, k_count_small), the greatest labelled neighbour in
 //                    two atomic passes (k_target), k_pointers, k_jump, k_relabel; one host descriptor, one word read back per round; no mesh needed
+//   nearest.hip      nearest points (gr_nearest_points): k_nn_bounds, then per level k_nn_keys and one sort put the refs of a grid cell side by side,
+//                    k_nn_gather lays their coordinates out in that order, k_nn_query walks the shells of cells round each query (a lower bound
+//                    in the sorted keys per run of cells, no cell table) and lists the queries it could not settle for the next, coarser
+//                    level; one host descriptor, the bounds and one word per level read back; no mesh needed
 //   crs_dev.hpp      the conversion of one point between the WGS84 systems (G1-G8): CrsSide, CrsArgs, wrap_pi, clenshaw, taup_of, convert, crs_side
 //                    (crs.hip, raster_warp.hip)
 //   cub_steps.hpp    the hipcub calls of the stage calls, each declared once against the call's Plan: SortPairs, SortKeys, ExclusiveSum,

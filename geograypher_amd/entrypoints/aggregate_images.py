@@ -65,6 +65,8 @@ def aggregate_images(
     sieve_min_area_m2: typing.Union[float, None] = None,
     sieve_min_faces: typing.Union[int, None] = None,
     sieve_fill_unseen: bool = False,
+    full_mesh_face_classes_savefile: typing.Union[PATH_TYPE, None] = None,
+    transfer_max_distance_meters: typing.Union[float, None] = None,
 ):
     """Aggregate the labels under `label_folder` onto the mesh (see the module docstring).  The reference's arguments and defaults;
     `mesh_downsample != 1` without `mesh_downsample_method`, `vis`, `ROI` without `ROI_points_file`, `DTM_file` without `DTM_points_file` and
@@ -89,7 +91,13 @@ def aggregate_images(
     ground step, the saved file and the maps: connected regions of one class below that surface area / face count join their
     greatest neighbour region (`TexturedPhotogrammetryMesh.sieve_face_labels`); `sieve_fill_unseen` also
     fills small regions of unseen faces and needs one of the two.  With the three at their defaults every output is what it is
-    without them.  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
+    without them.
+    `full_mesh_face_classes_savefile` (.npy; needs `mesh_downsample_method`) also brings the predicted classes, as they are saved,
+    from the faces of the decimated mesh onto the faces of the mesh as it is behind the ROI crop and before the decimation -- that mesh
+    is built a second time, without the decimation --: every full-resolution face takes the class of the decimated face whose centre
+    is nearest its own (`TexturedPhotogrammetryMesh.values_from_mesh`), NaN where none lies within
+    `transfer_max_distance_meters` (None: no limit), and the (F_full, 1) array is saved.  Without a decimation it is a ValueError,
+    and so is the distance without the file.  Returns (mesh, aggregated face values, predicted face classes (F, 1))."""
     from geograypher_amd.cameras.segmentor import SegmentorPhotogrammetryCameraSet
     from geograypher_amd.meshes import TexturedPhotogrammetryMesh, TexturedPhotogrammetryMeshChunked
     from geograypher_amd.predictors.derived_segmentors import LookUpSegmentor
@@ -121,6 +129,15 @@ def aggregate_images(
         raise ValueError("sieve_min_area_m2 and sieve_min_faces are both given: the sieve has one threshold")
     if sieve_fill_unseen and sieve_min_area_m2 is None and sieve_min_faces is None:
         raise ValueError("sieve_fill_unseen needs a threshold: sieve_min_area_m2 or sieve_min_faces")
+
+    if full_mesh_face_classes_savefile is not None and mesh_downsample_method is None:
+        raise ValueError("full_mesh_face_classes_savefile is given without mesh_downsample_method: the mesh is not decimated, "
+                         "predicted_face_classes_savefile holds the classes of the full mesh")
+    if transfer_max_distance_meters is not None:
+        if full_mesh_face_classes_savefile is None:
+            raise ValueError("transfer_max_distance_meters is given but full_mesh_face_classes_savefile is not: nothing is transferred")
+        if not float(transfer_max_distance_meters) >= 0:
+            raise ValueError(f"transfer_max_distance_meters={transfer_max_distance_meters!r} is not a distance >= 0")
 
     for name, value, why in (
         ("DTM_file", DTM_file if DTM_points is None else None,
@@ -250,6 +267,14 @@ def aggregate_images(
         Path(predicted_face_classes_savefile).parent.mkdir(parents=True, exist_ok=True)
         np.save(predicted_face_classes_savefile, predicted_face_classes)
 
+    if full_mesh_face_classes_savefile is not None:   # the same classes on the faces of the mesh before the decimation
+        full_kwargs = {k: v for k, v in roi_kwargs.items() if k not in ("downsample_target", "downsample_method")}
+        full_mesh = MeshClass(mesh_file, input_CRS=mesh_CRS, IDs_to_labels=IDs_to_labels, backend=mesh.backend, **full_kwargs)
+        full_classes = full_mesh.values_from_mesh(mesh, predicted_face_classes, on="faces", max_distance=transfer_max_distance_meters)
+        mesh.last_transfer_stats = full_mesh.last_transfer_stats
+        Path(full_mesh_face_classes_savefile).parent.mkdir(parents=True, exist_ok=True)
+        np.save(full_mesh_face_classes_savefile, np.asarray(full_classes, dtype=np.float64).reshape(-1, 1))
+
     if vis_folder is not None:   # ... and the one at aggregate_images.py:214: the class per face, behind the ground step
         mesh.vis(screenshot_filename=Path(vis_folder, "predicted_classes.png"), vis_scalars=predicted_face_classes)
 
@@ -332,6 +357,11 @@ def parse_args(argv=None):
     parser.add_argument("--sieve-min-faces", type=int, help="... below this number of faces instead (one of the two at most)")
     parser.add_argument("--sieve-fill-unseen", action="store_true",
                         help="The sieve also fills small regions of unseen faces; needs one of the two thresholds")
+    parser.add_argument("--full-mesh-face-classes-savefile", type=Path,
+                        help="With --mesh-downsample-method: where the (F, 1) classes on the faces of the mesh before the decimation are "
+                        "saved (.npy), each face taking the class of the decimated face with the nearest centre, on the device")
+    parser.add_argument("--transfer-max-distance-meters", type=float,
+                        help="Faces of the full mesh with no decimated face centre within this distance stay unlabelled (NaN)")
     parser.add_argument("--vis", action="store_true", help="Not available here")
     parser.add_argument("--vis-folder", type=Path,
                         help="Write mesh_and_cameras.png and predicted_classes.png (each with its .legend.json) here: the two pictures "

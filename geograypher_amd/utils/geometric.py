@@ -540,6 +540,77 @@ def face_components(faces, classes, backend=None, vertex_canon=None, n_vertices=
     return comp, stats
 
 
+# -- nearest points: for every query row the nearest ref row, exact -----------------------------------------------
+NEAREST_STAT_NAMES = ("ref_nonfinite", "query_nonfinite", "no_answer", "levels", "carried", "cells_probed", "candidates", "cell_bits",
+                      "ring_cap")   # GR_NN_STAT_*
+
+
+def points_3d(points, name: str = "points"):
+    """(n, 3) float64 of an (n, 3) array, or of an (n, 2) one with z = 0; numpy stays numpy, a tensor stays a tensor on its
+    device.  Any other shape is a ValueError naming `name`."""
+    shape = tuple(points.shape) if hasattr(points, "shape") else np.asarray(points).shape
+    if len(shape) != 2 or shape[1] not in (2, 3):
+        raise ValueError(f"{name} must be (n, 3), or (n, 2) for z = 0, got {shape}")
+    if hasattr(points, "detach"):
+        import torch
+
+        p = points.to(torch.float64)
+        return p if shape[1] == 3 else torch.cat([p, torch.zeros((shape[0], 1), dtype=torch.float64, device=p.device)], dim=1)
+    p = np.asarray(points, dtype=np.float64)
+    return np.ascontiguousarray(p if shape[1] == 3 else np.concatenate([p, np.zeros((shape[0], 1))], axis=1))
+
+
+def named_nearest_stats(stats) -> dict:
+    """The statistics block of gr_nearest_points as a dict over NEAREST_STAT_NAMES, and `cell`: the cell side as a float."""
+    stats_h = np.asarray(_host(stats)).astype(np.int64)
+    named = {name: int(stats_h[k]) for k, name in enumerate(NEAREST_STAT_NAMES)}
+    named["cell"] = float(np.array([named["cell_bits"]], dtype=np.int64).view(np.float64)[0])
+    return named
+
+
+def nearest_points(backend, ref, query, *, max_distance=None, cell: float = 0.0, max_rings: int = 2, return_dist2: bool = False,
+                   return_tensor: bool = False):
+    """Rules K1-K9 through `backend.nearest_points`: ref (R, 3), query (Q, 3) -- or (n, 2) for z = 0 --, arrays or device tensors
+    -> (index (Q,) int32: for every query row the row of the nearest ref, the lowest among equally near ones, -1 where there
+    is none (a non-finite query, no finite ref, none within `max_distance`); [dist2 (Q,) float64 with `return_dist2`: the squared
+    distance ((dx dx + dy dy) + dz dz), NaN beside -1;] stats: a dict over NEAREST_STAT_NAMES and `cell`).  The answer is the
+    brute-force argmin, bit for bit; `cell` and `max_rings` steer the search only.  `backend`: a `HipRaster` (None: the shared
+    one) or an object with its `nearest_points` method.  With `return_tensor` the arrays stay where the backend left them."""
+    if backend is None:
+        from geograypher_amd._hip import default_backend
+
+        backend = default_backend()
+    ref, query = points_3d(ref, "ref"), points_3d(query, "query")
+    out = backend.nearest_points(ref, query, max_distance=max_distance, cell=cell, max_rings=max_rings, return_dist2=return_dist2)
+    arrays, named = out[:-1], named_nearest_stats(out[-1])
+    if not return_tensor:
+        arrays = tuple(np.asarray(_host(a)) for a in arrays)
+    return (*arrays, named)
+
+
+def gather_rows(values, index, fill):
+    """out[i] = values[index[i]] where index[i] >= 0, `fill` elsewhere; the dtype and the trailing axes of `values`.  With a
+    device `index` the gather runs on that device and the result comes back as numpy."""
+    values = np.asarray(_host(values))
+    if hasattr(index, "detach"):
+        import torch
+
+        vals_t = torch.as_tensor(np.ascontiguousarray(values)).to(index.device)
+        idx = index.to(torch.int64)
+        if vals_t.shape[0] == 0:
+            out = torch.full((idx.shape[0],) + tuple(vals_t.shape[1:]), fill, dtype=vals_t.dtype, device=index.device)
+        else:
+            out = vals_t[idx.clamp(min=0)]
+            out[idx < 0] = fill
+        return out.cpu().numpy()
+    idx = np.asarray(index, dtype=np.int64)
+    if values.shape[0] == 0:
+        return np.full((idx.shape[0],) + values.shape[1:], fill, dtype=values.dtype)
+    out = values[np.maximum(idx, 0)]
+    out[idx < 0] = fill
+    return out
+
+
 # -- mesh decimation by vertex clustering (DESIGN.md section 8n) ---------------------------------------------------------------------
 CLUSTER_COORD_LIMIT = 1 << 41   # D1: snapped coordinates behind their minimum stay below this
 CLUSTER_CELLS_PER_AXIS = 1 << 21   # D2: a cell component fits 21 bits of the key

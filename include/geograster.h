@@ -901,6 +901,22 @@ enum {
 };
 #include "geograster_components.h"
 
+/* Nearest points (geograster_nearest.h): the words of the statistics block.  The call takes one
+ * descriptor, declared there. */
+enum {
+  GR_NN_STAT_REF_NONFINITE = 0,    /* ref rows with a NaN or infinite coordinate: they take no part                */
+  GR_NN_STAT_QUERY_NONFINITE = 1,  /* query rows with one: index -1, dist2 NaN                                     */
+  GR_NN_STAT_NO_ANSWER = 2,        /* queries whose index is -1 (non-finite, no ref, or none within max_distance)  */
+  GR_NN_STAT_LEVELS = 3,           /* grid levels run                                                              */
+  GR_NN_STAT_CARRIED = 4,          /* queries carried to a coarser level, summed over the levels                   */
+  GR_NN_STAT_CELLS_PROBED = 5,     /* runs of cells looked up in the sorted keys                                   */
+  GR_NN_STAT_CANDIDATES = 6,       /* distances evaluated                                                          */
+  GR_NN_STAT_CELL_BITS = 7,        /* the cell side of the first level, the bits of the float64 (0: no level ran)  */
+  GR_NN_STAT_RING_CAP = 8,         /* 1: a query was not settled within max_rings rings of some level             */
+  GR_NN_STAT_WORDS = 9
+};
+#include "geograster_nearest.h"
+
 #ifdef __cplusplus
 }
 #endif
